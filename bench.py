@@ -24,11 +24,25 @@ hinge --dim 256 --items 10000000` is configs[4].  `--users` / `--max-len` overri
 scatter / owner-reduce / table-update kernels and device copies in place of the collectives, and
 prints the kernel-side cost of the exchange and the bytes every xGMI link would carry.
 
+A plain run (no `--full`) does only what the headline needs: set-up, the GPU pre-warm, W warm-up steps, the K
+timed steps, `--dump-outputs` if given, and the result line — `metric`, `value`, `unit`, `higher_is_better`,
+`dtype`, `ms_per_step` and the timed region's own bookkeeping (`roofline` from the score kernel's HIP events
+inside the timed region, `traffic` from the committed profile).  `--full` adds everything below that takes runs
+of its own: the second, all-timers pass behind `kernels` / `roofline_mfma`, `kernels_standalone`,
+`roofline_cold`, `batch_sweep`, `small_steps`, live PMC `traffic`, `cpu_baseline`, `mrr_gemm`, `test_mrr`,
+`reference_criterion_bench` and, with N > 1, `single_gpu_same_shape`.
+
+`--dump-outputs DIR` writes what the timed path computed, after its last step, as DIR/<name>.npy
+(float32; `item_rows` float64): every parameter and optimiser-state block of the model (item-table blocks on a
+fixed, seeded sample of rows, `item_rows` naming them) and the per-row loss of the last minibatch
+(`loss_rows`).  The inputs depend on the arguments only, so two builds can be compared output for output.
+
 Prints ONE JSON line (rank 0, the last line of stdout).  `roofline` describes the gather +
 WARP-score kernel against the HBM roofline (`traffic` = PMC bytes measured at this operating point,
 profiles/score_kernel_traffic.json + profiles/r03_counter_calibration.md, else null);
 `kernels` lists every kernel family's time inside the timed region (HIP events on the engine's
-streams; concurrent families include each other's contention); `kernels_standalone` comes from a
+streams; concurrent families include each other's contention; without `--full` the score family
+only); `kernels_standalone` comes from a
 second, UNTIMED pass with stream overlap off (N = 1): every family alone, with the sparse update's
 HBM figure and the GEMM-shaped kernels' MFMA figures; `roofline_mfma` are the in-region MFMA
 figures; `cpu_baseline` is the CPU oracle (a scalar C port of the same algorithm; the Rust
@@ -137,7 +151,7 @@ def live_traffic(kernel, warmup_dispatches, timed_dispatches, timeout_s=150):
 
     tmp = tempfile.mkdtemp(prefix="sbr_pmc_", dir="/tmp")
     env = dict(os.environ, TMPDIR="/tmp")
-    drop = {"--traffic"}
+    drop = {"--traffic", "--dump-outputs"}
     argv, skip = [], False
     for a in sys.argv[1:]:
         if skip:
@@ -146,7 +160,7 @@ def live_traffic(kernel, warmup_dispatches, timed_dispatches, timeout_s=150):
         if a in drop:
             skip = True
             continue
-        if a.startswith("--traffic="):
+        if a.startswith(("--traffic=", "--dump-outputs=")):
             continue
         argv.append(a)
     child = [sys.executable, os.path.abspath(__file__)] + argv + ["--traffic", "off", "--no-cpu-baseline", "--no-mrr", "--batch-sweep=",
@@ -358,6 +372,32 @@ def mrr_gemm(model, args, users=8192):
             "users": int(len(ranks)), "items": args.items, "dim": args.dim, "rank_kernels_ms": ms, "launches": int(tm["RANK"][1]),
             "achieved": tf, "peak": FP32_MFMA_PEAK_TF, "unit": "TFLOP/s", "frac": tf / FP32_MFMA_PEAK_TF,
             "mrr_score_wall_ms": 1e3 * wall, "mrr": float(mrr), "note": "untimed extra; the U x I score matrix is never materialised"}
+
+
+DUMP_ITEM_ROWS = 16_384    # item-table rows in the --dump-outputs sample (a d = 256 model's four item blocks: 34 MB)
+DUMP_LOSS_ROWS = 1 << 20   # per-row losses kept from the last minibatch (a seeded sample beyond that)
+
+
+def dump_outputs(out_dir, model, plan, loss_mb, num_items):
+    """--dump-outputs: the model's parameter and optimiser-state blocks as they stand after the last timed step (dense blocks whole,
+    item-table blocks on a fixed, seeded sample of rows) and the per-row loss of the minibatch whose block the step left behind, one
+    DIR/<name>.npy each.  Returns the names written."""
+    from sbr_rs_amd._abi import Debug, Param
+
+    os.makedirs(out_dir, exist_ok=True)
+    rs = np.random.RandomState(20)
+    rows = np.unique(rs.randint(0, num_items, size=min(num_items, DUMP_ITEM_ROWS))).astype(np.uint32)
+    arrays = {"item_rows": rows.astype(np.float64)}
+    for p in Param:
+        if model.param_count(p):
+            arrays[p.name.lower()] = model.get_param_rows(p, rows) if p.name.startswith("ITEM_") else model.get_param(p)
+    loss = plan.debug_fetch(Debug.LOSS, plan.minibatch_rows(loss_mb))
+    if loss.size > DUMP_LOSS_ROWS:
+        loss = loss[np.sort(rs.choice(loss.size, DUMP_LOSS_ROWS, replace=False))]
+    arrays["loss_rows"] = loss
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a if a.dtype == np.float64 else a.astype(np.float32))
+    return sorted(arrays)
 
 
 def quality_neutral_batch():
@@ -678,7 +718,20 @@ def main():
                          "weak-scaling efficiency (every N > 1 line also carries it as `single_gpu_same_shape`)")
     ap.add_argument("--force-exchange", action="store_true",
                     help="run the multi-GPU exchange collectives even at world size 1 (smoke test of the RCCL path)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline (the passes and legs the module docstring lists: per-family kernel "
+                         "times, standalone / cache-cold / batch-sweep / small-step passes, live PMC traffic, CPU baseline, MRR runs, "
+                         "criterion bench, the same-shape single-GPU line); the --no-* / --traffic / --batch-sweep / --standalone-steps / "
+                         "--cold-items options tune those.  Off: set-up, warm-up, the timed steps, --dump-outputs and the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed to DIR/<name>.npy (module docstring)")
     args = ap.parse_args()
+    if not args.full:  # a plain run: the headline only
+        args.no_cpu_baseline = args.no_mrr = True
+        args.standalone_steps = args.cold_items = 0
+        args.batch_sweep = ""
+        if args.traffic == "live":
+            args.traffic = "profile"
 
     import torch
 
@@ -749,6 +802,8 @@ def main():
         else:
             args.batch_sequences = MAX_BATCH
             batch_rule = "default: 50 000 (EWMA: test MRR does not fall with the batch, NOTES.md section 3)" if model_kind == 2 else "default: 50 000"
+    if args.dump_outputs and (args.driver == "group" or args.simulate_world > 1):
+        raise SystemExit("--dump-outputs: the throughput line's path only (not --driver group / --simulate-world)")
     if args.driver == "group":
         if world != 1:
             raise SystemExit("--driver group runs in one process (no launcher)")
@@ -806,6 +861,7 @@ def main():
         rows = plan.minibatch_rows(mb)
         loop.step(mb)  # compute_local + (exchange: scatter, all-to-all, owner reduce, all-gather) + apply
         state["mb"] += 1
+        state["last_mb"] = mb
         return rows
 
     def sync():
@@ -876,9 +932,17 @@ def main():
         per_rank = [1e3 * elapsed / max(args.steps, 1)]
     timing = model.timing_read()
     ex1, neg1 = plan.counters()
+    dumped = None
+    if args.dump_outputs and args.steps > 0:
+        if hasattr(loop, "finish"):
+            loop.finish()  # owner-applied steps: every owner's optimiser-state slice into every replica before rank 0 reads its own
+        if rank == 0:
+            # the staleness-one pipeline has computed one minibatch ahead: the block it left is that one's
+            computed = getattr(loop, "_computed", -1)
+            dumped = dump_outputs(args.dump_outputs, model, plan, computed if computed >= 0 else state["last_mb"], args.items)
     score_timing = timing.get("SCORE")
     rows_families = rows_timed
-    if timers != "all" and hasattr(model, "timing_select"):
+    if args.full and timers != "all" and hasattr(model, "timing_select"):
         # second pass, untimed for `value`: the same steps with every kernel family bracketed by events
         model.timing_select(None)
         rows_families = 0
@@ -981,7 +1045,7 @@ def main():
     if hasattr(loop, "finish"):
         loop.finish()  # owner-applied steps: the owners' optimiser-state slices back on every replica (outside every timed region)
     single_same_shape = None
-    if world > 1 and not args.partition_table:
+    if args.full and world > 1 and not args.partition_table:
         # the denominator of the weak-scaling efficiency, measured in THIS job: rank 0 alone on the same per-GPU shape and batch (the
         # N = 1 default of this script is configs[2]'s shorter sequences, a different workload); the other ranks wait at the barrier
         if rank == 0:
@@ -1166,8 +1230,12 @@ def main():
             "gpu_prewarm": prewarm, "roofline": roofline, "step_bytes": step_bytes, "roofline_cold": cold, "roofline_mfma": mfma, "kernels": kernels, "kernels_standalone": kernels_sa,
             "kernels_source": ("HIP events on every family inside the timed region" if timers == "all" else
                                f"SCORE: HIP events inside the timed region; the other families: a second pass of {args.steps} steps of the same schedule "
-                               "with every family bracketed (events cost the step 1.5-2 %, so the timed region brackets the roofline kernel only)"),
+                               "with every family bracketed (events cost the step 1.5-2 %, so the timed region brackets the roofline kernel only)" if args.full else
+                               "SCORE: HIP events inside the timed region; the other families: --full"),
+            "full": args.full,
         }
+        if dumped:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "names": dumped}
         if world > 1:
             out["config"]["exchange"] = ("owner-applied update, parameter slices all-gathered in place" if getattr(loop, "owner_applied", False) else
                                          "gradient all-gather, whole-table update on every replica") if not args.partition_table else "partitioned table: owner-computes over gradient lists"

@@ -1,8 +1,12 @@
 """CPU: the host-side bookkeeping of bench.py — which BASELINE.json config a run's shape is labelled as, when the measured
-HBM traffic of the score kernel may be printed, and the committed quality-neutral batch."""
+HBM traffic of the score kernel may be printed, and the committed quality-neutral batch.  GPU: what a plain run (no --full)
+prints and what --dump-outputs writes."""
 import json
 import os
 import types
+
+import numpy as np
+import pytest
 
 import bench
 
@@ -124,3 +128,38 @@ def test_pmc_step_window_and_timed_region_table(tmp_path, capsys):
     assert "| `ewma_seq_kernel<256, false>` | 5 | 0.010 | 2.00 |" in whole and "warm_up_only_kernel" in whole
     assert "| `ewma_seq_kernel<256, false>` | 3 | 0.006 | 2.00 |" in timed and "warm_up_only_kernel" not in timed
     capsys.readouterr()
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_and_dumps_the_same_outputs_twice(tmp_path):
+    """`bench.py` without --full: the timed steps and the headline fields, none of the extra passes; --dump-outputs writes the
+    trained parameters (item blocks on a seeded sample of rows) and the last step's per-row losses, float32 / float64, and two runs
+    with the same arguments write the same bits."""
+    import subprocess
+    import sys
+
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--users", "3000", "--items", "20000",
+           "--max-len", "32", "--dim", "64", "--batch-sequences", "1000", "--prewarm-seconds", "0"]
+    lines = []
+    for run in ("a", "b"):
+        res = subprocess.run(cmd + ["--dump-outputs", str(tmp_path / run)], capture_output=True, text=True, timeout=600)
+        assert res.returncode == 0, res.stderr[-2000:]
+        lines.append(json.loads(res.stdout.strip().splitlines()[-1]))
+    for line in lines:
+        assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0 and line["full"] is False
+        assert {line["metric"], line["unit"], line["dtype"], line["higher_is_better"]} == {"train interactions/sec", "interactions/s", "f32", True}
+        assert not {"cpu_baseline", "test_mrr", "mrr_gemm", "batch_sweep", "small_steps", "value_max_batch"} & set(line)
+        assert line["kernels_standalone"] is None and line["roofline_cold"] is None and set(line["kernels"]) <= {"SCORE"}
+    names = lines[0]["dumped_outputs"]["names"]
+    assert names == lines[1]["dumped_outputs"]["names"]
+    assert {"item_rows", "item_embedding", "item_embedding_acc", "item_bias", "lstm_w", "lstm_w_acc", "loss_rows"} <= set(names)
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / "a" / f"{n}.npy"), np.load(tmp_path / "b" / f"{n}.npy")
+        assert a.dtype in (np.float32, np.float64) and a.size, n
+        assert a.shape == b.shape and a.tobytes() == b.tobytes(), n
+        total += a.nbytes
+    assert total <= 64 << 20
+    emb, rows = np.load(tmp_path / "a" / "item_embedding.npy"), np.load(tmp_path / "a" / "item_rows.npy")
+    assert emb.shape == (rows.size, 64) and np.isfinite(emb).all()
+    assert np.isfinite(np.load(tmp_path / "a" / "loss_rows.npy")).all()

@@ -6,7 +6,7 @@ out=$1; shift
 batches=$1; shift
 for envs in "" "$@"; do
   for b in $batches; do
-    line=$(env $envs python bench.py --steps ${STEPS:-20} --warmup 5 --batch-sequences $b --no-cpu-baseline --no-mrr --standalone-steps 0 \
+    line=$(env $envs python bench.py --full --steps ${STEPS:-20} --warmup 5 --batch-sequences $b --no-cpu-baseline --no-mrr --standalone-steps 0 \
            --cold-items 0 --batch-sweep '' $EXTRA 2>/dev/null | tail -1)
     python - "$b" "$envs" "$line" <<'PY' | tee -a "$out"
 import json, sys
