@@ -27,4 +27,7 @@ print(f"Train MRR {sbr.evaluation.mrr_score(model, train_mat):.4f} at loss {loss
       f"test MRR {sbr.evaluation.mrr_score(model, test_mat):.4f} (in {elapsed:.3f} s)")
 user = model.user_representation([50, 181, 258])
 print("scores:", model.predict(user, [1, 100, 300]))
+items, scores = model.recommend(test_mat, 10)  # the whole catalogue on the device, the histories excluded
+for u in range(3):
+    print(f"test user {u}: top 10 {items[u].tolist()}")
 sbr.persistence.save_model(model, "/tmp/sbr_movielens_model.npz")  # parameters + optimiser state + counters

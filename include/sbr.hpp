@@ -486,6 +486,12 @@ namespace models {
 struct ImplicitUser {
     std::vector<float> user_embedding;
 };
+/// Top-k recommendations of ImplicitSequenceModel::recommend: row-major [num_users][k].
+struct Recommendations {
+    std::size_t num_users = 0, k = 0;
+    std::vector<std::uint32_t> items;
+    std::vector<float> scores;
+};
 /// The loss used for training the model (mod.rs:15-23).
 enum class Loss { BPR = SBR_LOSS_BPR, Hinge = SBR_LOSS_HINGE, WARP = SBR_LOSS_WARP };
 /// Optimizer used to train the model (mod.rs:26-32).
@@ -604,6 +610,26 @@ class ImplicitSequenceModel : public OnlineRankingModel<ImplicitUser> {
             return Result<std::vector<float>, PredictionError>::Err(PredictionError::InvalidPredictionValue);
         check(st, "sbr_predict");
         return Result<std::vector<float>, PredictionError>::Ok(std::move(out));
+    }
+
+    /// The k best items of the whole catalogue for each user's history in `interactions` (sbr_recommend): score descending,
+    /// ties to the lower item id, the scores bit-equal to `predict`'s.  Every item of a history is excluded unless
+    /// `exclude_history` is false; a row with fewer than k eligible items is padded with (0xFFFFFFFF, -inf).
+    /// Err(InvalidPredictionValue) on a non-finite score.
+    Result<Recommendations, PredictionError> recommend(const data::CompressedInteractions& interactions, std::size_t k,
+                                                       bool exclude_history = true) const {
+        if (k < 1 || k > SBR_RECOMMEND_MAX_K) throw EngineError(SBR_ERR_INVALID_ARGUMENT, "recommend: k outside 1..SBR_RECOMMEND_MAX_K");
+        Recommendations r;
+        r.num_users = interactions.num_users();
+        r.k = k;
+        r.items.resize(r.num_users * k);
+        r.scores.resize(r.num_users * k);
+        const sbr_status st = sbr_recommend(replicas_->primary(), interactions.user_pointers().data(), interactions.item_ids().data(),
+                                            (std::uint64_t)r.num_users, (std::uint32_t)k, exclude_history ? 0u : SBR_RECOMMEND_INCLUDE_HISTORY,
+                                            r.items.data(), r.scores.data());
+        if (st == SBR_ERR_INVALID_PREDICTION) return Result<Recommendations, PredictionError>::Err(PredictionError::InvalidPredictionValue);
+        check(st, "sbr_recommend");
+        return Result<Recommendations, PredictionError>::Ok(std::move(r));
     }
 
     /// The engine handle (replica 0), for evaluation's fused path and for parameter access.

@@ -392,6 +392,23 @@ sbr_status sbr_predict(sbr_model* m, const float* user_dim, const uint32_t* item
 sbr_status sbr_mrr_score(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids,
                          uint64_t num_users, float* out_mrr, uint32_t* out_ranks, uint64_t* out_num_ranked);
 
+/* Exact top-k of the whole catalogue per user (no counterpart in the reference crate: user_representation + predict over every
+ * item + a sort, on the device).  score(u, i) = bias[i] + <rep_u, E[i]> with the bits of sbr_predict; rows sorted by score
+ * descending, ties to the lower item id (-0.0 == +0.0).  out_items / out_scores (optional): [num_users][k].  A row with fewer than
+ * k eligible items is padded with item 0xFFFFFFFF and score -inf.  1 <= k <= SBR_RECOMMEND_MAX_K.  SBR_ERR_INVALID_PREDICTION if
+ * any score of a scored user is non-finite.  Deterministic.
+ * sbr_recommend: user u's history is item_ids[user_ptr[u] .. user_ptr[u + 1]) (the layout of sbr_mrr_score); its representation is
+ * that of sbr_user_representation (last max_sequence_length items; empty = item 0), every user gets a row, and every item of the
+ * whole history is excluded unless flags has SBR_RECOMMEND_INCLUDE_HISTORY.
+ * sbr_recommend_reps: from representations (embedding_dim floats each, as sbr_user_representation returns them); excl_ptr /
+ * excl_items: optional per-user exclusion lists (CSR; both NULL = none). */
+#define SBR_RECOMMEND_MAX_K 1024u
+#define SBR_RECOMMEND_INCLUDE_HISTORY 1u
+sbr_status sbr_recommend(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users,
+                         uint32_t k, uint32_t flags, uint32_t* out_items, float* out_scores);
+sbr_status sbr_recommend_reps(sbr_model* m, const float* reps, uint64_t num_users, uint32_t k,
+                              const uint64_t* excl_ptr, const uint32_t* excl_items, uint32_t* out_items, float* out_scores);
+
 /* ≙ the serde derives (lstm.rs:204,386; ewma.rs:208,401): element counts and raw access. */
 sbr_status sbr_model_param_count(const sbr_model* m, int32_t which, uint64_t* out_count);
 sbr_status sbr_model_get_param(sbr_model* m, int32_t which, float* host_out, uint64_t count);

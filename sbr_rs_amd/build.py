@@ -17,7 +17,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libsbr_hip.so")
-SOURCES = ["sbr_kernels.hip", "sbr_steps.hip", "sbr_sort.hip", "sbr_wave.hip", "sbr_report.hip", "sbr_engine.hip"]
+SOURCES = ["sbr_kernels.hip", "sbr_steps.hip", "sbr_sort.hip", "sbr_wave.hip", "sbr_report.hip", "sbr_recommend.hip", "sbr_engine.hip"]
 HEADERS = ["sbr_kernels.h", "sbr_device.h", "sbr_wave_seq.h", "sbr_numerics.h", "sbr_approx.h", "sbr_ziggurat_tables.h", os.path.join("..", "..", "include", "sbr_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
          "-Wall", "-Wno-unused-function", "-Wno-unused-result", "-Wno-unused-value"] + os.environ.get("SBR_EXTRA_FLAGS", "").split()
@@ -63,20 +63,34 @@ FACADE_SRC = os.path.join(REPO, "tests", "cpp", "facade_tests.cpp")
 FACADE_BIN = os.path.join(REPO, "tests", "cpp", "_build", "facade_tests")
 
 
-def build_facade_tests(force: bool = False, verbose: bool = True) -> str:
-    """g++ build of the C++ host layer's test program (include/sbr.hpp over libsbr_hip.so)."""
+def _build_cpp_program(src: str, binary: str, force: bool, verbose: bool) -> str:
     cxx = shutil.which("g++") or "g++"
-    deps = [FACADE_SRC, os.path.join(REPO, "include", "sbr.hpp"), os.path.join(REPO, "include", "sbr_hip.h"), LIB]
-    if force or _stale(FACADE_BIN, deps):
-        os.makedirs(os.path.dirname(FACADE_BIN), exist_ok=True)
-        cmd = [cxx, "-std=c++17", "-O2", "-Wall", "-Wextra", "-I" + os.path.join(REPO, "include"), FACADE_SRC, "-o", FACADE_BIN,
+    deps = [src, os.path.join(REPO, "include", "sbr.hpp"), os.path.join(REPO, "include", "sbr_hip.h"), LIB]
+    if force or _stale(binary, deps):
+        os.makedirs(os.path.dirname(binary), exist_ok=True)
+        cmd = [cxx, "-std=c++17", "-O2", "-Wall", "-Wextra", "-I" + os.path.join(REPO, "include"), src, "-o", binary,
                "-L" + HERE, "-lsbr_hip", "-Wl,-rpath,$ORIGIN/../../../sbr_rs_amd"]
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.check_call(cmd)
-    return FACADE_BIN
+    return binary
+
+
+def build_facade_tests(force: bool = False, verbose: bool = True) -> str:
+    """g++ build of the C++ host layer's test program (include/sbr.hpp over libsbr_hip.so)."""
+    return _build_cpp_program(FACADE_SRC, FACADE_BIN, force, verbose)
+
+
+RECOMMEND_SRC = os.path.join(REPO, "tests", "cpp", "recommend_tests.cpp")
+RECOMMEND_BIN = os.path.join(REPO, "tests", "cpp", "_build", "recommend_tests")
+
+
+def build_recommend_tests(force: bool = False, verbose: bool = True) -> str:
+    """g++ build of the C++ host layer's top-k recommendation test program."""
+    return _build_cpp_program(RECOMMEND_SRC, RECOMMEND_BIN, force, verbose)
 
 
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv))
     print(build_facade_tests(force="--force" in sys.argv))
+    print(build_recommend_tests(force="--force" in sys.argv))

@@ -3553,6 +3553,186 @@ sbr_status sbr_mrr_score(sbr_model* m, const uint64_t* user_ptr, const uint32_t*
 }
 
 /* ---------------------------------------------------------------------------------------------
+ * exact top-k recommendation (sbr_recommend.hip)
+ * ------------------------------------------------------------------------------------------- */
+namespace {
+
+/* users per top-k launch: as mrr_score's EVAL_B, and few enough that the per-(user, item range) lists stay under 256 MB */
+size_t recommend_users_cap(const sbr_model* m, uint32_t k) {
+    size_t cap = 8192;
+    for (;;) {
+        uint32_t per = 0;
+        const uint32_t g = sbr::recommend_groups((uint32_t)cap, (uint32_t)m->hp.num_items, k, &per);
+        if (cap <= 128 || cap * g * k * 8 <= ((size_t)256 << 20)) return cap;
+        cap /= 2;
+    }
+}
+
+/* arena bytes of one top-k launch over nu users with nexcl exclusion entries */
+size_t recommend_bytes(const sbr_model* m, size_t nu, size_t nexcl, uint32_t k) {
+    uint32_t per = 0;
+    const size_t g = sbr::recommend_groups((uint32_t)nu, (uint32_t)m->hp.num_items, k, &per);
+    return DeviceArena::padded(nu * 4) + DeviceArena::padded((nu + 1) * 8) + DeviceArena::padded(nexcl * 4 + 4) +
+           DeviceArena::padded(nu * g * k * 8) + DeviceArena::padded(nu * g * 4) + 2 * DeviceArena::padded(nu * k * 4) + DeviceArena::padded(4);
+}
+
+/* top-k of nu users whose representations are rows rep_row[i] of H (eval arena, reserved with recommend_bytes); excl_ptr empty:
+ * no exclusion, else sorted de-duplicated per-user lists.  Results go to out_items / out_scores (host, nu x k; scores optional). */
+sbr_status recommend_launch(sbr_model* m, const float* H, const std::vector<int>& rep_row, size_t nu, const std::vector<uint64_t>& excl_ptr,
+                            const std::vector<uint32_t>& excl_items, uint32_t k, uint32_t* out_items, float* out_scores) {
+    DeviceArena& ar = m->eval_arena;
+    uint32_t per = 0;
+    const size_t g = sbr::recommend_groups((uint32_t)nu, (uint32_t)m->hp.num_items, k, &per);
+    int* d_rep = ar.take<int>(nu);
+    uint64_t* d_eptr = ar.take<uint64_t>(nu + 1);
+    uint32_t* d_excl = ar.take<uint32_t>(excl_items.size() + 1);
+    uint2* d_lists = ar.take<uint2>(nu * g * k);
+    uint32_t* d_lens = ar.take<uint32_t>(nu * g);
+    uint32_t* d_items = ar.take<uint32_t>(nu * k);
+    float* d_scores = ar.take<float>(nu * k);
+    uint32_t* d_flag = ar.take<uint32_t>(1);
+    const bool excl = !excl_ptr.empty();
+    HIPCHK(hipMemcpyAsync(d_rep, rep_row.data(), nu * 4, hipMemcpyHostToDevice, m->stream));
+    if (excl) {
+        HIPCHK(hipMemcpyAsync(d_eptr, excl_ptr.data(), (nu + 1) * 8, hipMemcpyHostToDevice, m->stream));
+        if (!excl_items.empty()) HIPCHK(hipMemcpyAsync(d_excl, excl_items.data(), excl_items.size() * 4, hipMemcpyHostToDevice, m->stream));
+    }
+    HIPCHK(hipMemsetAsync(d_flag, 0, 4, m->stream));
+    {
+        ScopedTimer t(m, SBR_K_RANK, 2);
+        sbr::launch_recommend(m->mv, H, d_rep, (uint32_t)nu, excl ? d_eptr : nullptr, d_excl, k, d_lists, d_lens, d_items,
+                              out_scores ? d_scores : nullptr, d_flag, m->stream);
+    }
+    uint32_t flag = 0;
+    HIPCHK(hipStreamSynchronize(m->stream)); /* the host vectors above are read by the asynchronous copies */
+    HIPCHK(hipMemcpy(&flag, d_flag, 4, hipMemcpyDeviceToHost));
+    if (flag) return SBR_ERR_INVALID_PREDICTION; /* predict fails the call on a non-finite score */
+    HIPCHK(hipMemcpy(out_items, d_items, nu * k * 4, hipMemcpyDeviceToHost));
+    if (out_scores) HIPCHK(hipMemcpy(out_scores, d_scores, nu * k * 4, hipMemcpyDeviceToHost));
+    return SBR_OK;
+}
+
+}  // namespace
+
+sbr_status sbr_recommend(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users, uint32_t k, uint32_t flags,
+                         uint32_t* out_items, float* out_scores) {
+    if (!m || !user_ptr || (num_users && !out_items)) return SBR_ERR_INVALID_ARGUMENT;
+    if (k < 1 || k > SBR_RECOMMEND_MAX_K || (flags & ~SBR_RECOMMEND_INCLUDE_HISTORY)) return SBR_ERR_INVALID_ARGUMENT;
+    std::lock_guard<std::mutex> lock(m->mu);
+    SBRCHK(ensure_device(m));
+    const uint64_t T = m->hp.max_sequence_length;
+    for (uint64_t u = 0; u < num_users; ++u)
+        if (user_ptr[u + 1] < user_ptr[u]) return SBR_ERR_INVALID_ARGUMENT; /* pointers must be non-decreasing */
+    const uint64_t nnz = user_ptr[num_users] - user_ptr[0];
+    if (nnz && !item_ids) return SBR_ERR_INVALID_ARGUMENT;
+    for (uint64_t i = user_ptr[0]; i < user_ptr[num_users]; ++i)
+        if (item_ids[i] >= m->hp.num_items) return SBR_ERR_INVALID_ARGUMENT;
+    const bool exclude = !(flags & SBR_RECOMMEND_INCLUDE_HISTORY);
+    static const uint32_t zero = 0;
+    const size_t cap = recommend_users_cap(m, k);
+    const size_t eval_rows_cap = (size_t)1 << 22; /* as mrr_score: the forward pass's scratch is (users x steps) rows */
+    for (size_t c0 = 0, c1 = 0; c0 < num_users; c0 = c1) {
+        size_t rows = 0;
+        for (c1 = c0; c1 < num_users && c1 - c0 < cap; ++c1) {
+            rows += (size_t)std::max<uint64_t>(1, std::min<uint64_t>(user_ptr[c1 + 1] - user_ptr[c1], T));
+            if (rows > eval_rows_cap && c1 > c0) break;
+        }
+        const size_t nu = c1 - c0;
+        std::vector<const uint32_t*> first(nu);
+        std::vector<int> nsteps(nu);
+        std::vector<uint64_t> hist_ptr, raw_ptr(nu + 1, 0);
+        std::vector<uint32_t> hist_items, uniq_count(nu, 0);
+        if (exclude) {
+            for (size_t i = 0; i < nu; ++i) raw_ptr[i + 1] = raw_ptr[i] + (user_ptr[c0 + i + 1] - user_ptr[c0 + i]);
+            hist_items.resize(raw_ptr[nu]);
+            hist_ptr.assign(nu + 1, 0);
+        }
+        /* the WHOLE history is masked (evaluation.rs:30-32), the last T items feed the state (sequence_model.rs:188), an empty
+         * history is step 0 with item 0 (lstm.rs:262-264); as mrr_score, sorted + de-duplicated in place, a few host threads */
+        auto prepare = [&](size_t i0, size_t i1) {
+            for (size_t i = i0; i < i1; ++i) {
+                const uint32_t* it = item_ids ? item_ids + user_ptr[c0 + i] : nullptr;
+                const uint64_t n = user_ptr[c0 + i + 1] - user_ptr[c0 + i];
+                const uint64_t keep = std::min(n, T);
+                first[i] = n ? it + (n - keep) : &zero;
+                nsteps[i] = n ? (int)keep : 1;
+                if (!exclude || n == 0) continue;
+                uint32_t* h = hist_items.data() + raw_ptr[i];
+                std::memcpy(h, it, n * 4);
+                std::sort(h, h + n);
+                uniq_count[i] = (uint32_t)(std::unique(h, h + n) - h);
+            }
+        };
+        {
+            const size_t nthreads = nu >= 2048 ? 8 : 1;
+            if (nthreads == 1) prepare(0, nu);
+            else {
+                std::vector<std::thread> workers;
+                for (size_t t = 0; t < nthreads; ++t) workers.emplace_back(prepare, nu * t / nthreads, nu * (t + 1) / nthreads);
+                for (auto& w : workers) w.join();
+            }
+        }
+        if (exclude) {
+            for (size_t i = 0; i < nu; ++i) { /* close the gaps the de-duplication left */
+                if (hist_ptr[i] != raw_ptr[i]) std::memmove(hist_items.data() + hist_ptr[i], hist_items.data() + raw_ptr[i], (size_t)uniq_count[i] * 4);
+                hist_ptr[i + 1] = hist_ptr[i] + uniq_count[i];
+            }
+            hist_items.resize(hist_ptr[nu]);
+        }
+        float* H = nullptr;
+        std::vector<int> rep_row;
+        SBRCHK(forward_histories(m, first, nsteps, &H, &rep_row, recommend_bytes(m, nu, hist_items.size(), k)));
+        SBRCHK(recommend_launch(m, H, rep_row, nu, hist_ptr, hist_items, k, out_items + c0 * k, out_scores ? out_scores + c0 * k : nullptr));
+    }
+    return SBR_OK;
+}
+
+sbr_status sbr_recommend_reps(sbr_model* m, const float* reps, uint64_t num_users, uint32_t k, const uint64_t* excl_ptr,
+                              const uint32_t* excl_items, uint32_t* out_items, float* out_scores) {
+    if (!m || (num_users && (!reps || !out_items))) return SBR_ERR_INVALID_ARGUMENT;
+    if (k < 1 || k > SBR_RECOMMEND_MAX_K) return SBR_ERR_INVALID_ARGUMENT;
+    if ((excl_ptr == nullptr) != (excl_items == nullptr) && !(excl_ptr && excl_ptr[num_users] == excl_ptr[0])) return SBR_ERR_INVALID_ARGUMENT;
+    std::lock_guard<std::mutex> lock(m->mu);
+    SBRCHK(ensure_device(m));
+    if (excl_ptr) {
+        for (uint64_t u = 0; u < num_users; ++u)
+            if (excl_ptr[u + 1] < excl_ptr[u]) return SBR_ERR_INVALID_ARGUMENT;
+        for (uint64_t i = excl_ptr[0]; i < excl_ptr[num_users]; ++i)
+            if (excl_items[i] >= m->hp.num_items) return SBR_ERR_INVALID_ARGUMENT;
+    }
+    const size_t d = (size_t)m->d, dl = (size_t)m->dl;
+    const size_t cap = recommend_users_cap(m, k);
+    for (size_t c0 = 0; c0 < num_users; c0 += cap) {
+        const size_t nu = std::min<size_t>(cap, num_users - c0);
+        std::vector<uint64_t> eptr;
+        std::vector<uint32_t> eitems;
+        if (excl_ptr) {
+            eptr.assign(nu + 1, 0);
+            for (size_t i = 0; i < nu; ++i) {
+                const uint32_t* b = excl_items + excl_ptr[c0 + i];
+                const uint32_t* e = excl_items + excl_ptr[c0 + i + 1];
+                const size_t at = eitems.size();
+                eitems.insert(eitems.end(), b, e);
+                std::sort(eitems.begin() + at, eitems.end());
+                eitems.erase(std::unique(eitems.begin() + at, eitems.end()), eitems.end());
+                eptr[i + 1] = eitems.size();
+            }
+        }
+        DeviceArena& ar = m->eval_arena;
+        HIPCHK(hipStreamSynchronize(m->stream)); /* nothing of an earlier call may still read the arena */
+        SBRCHK(ar.reserve(DeviceArena::padded(nu * d * 4) + recommend_bytes(m, nu, eitems.size(), k)));
+        float* H = ar.take<float>(nu * d);
+        /* padded to the storage width: the columns past embedding_dim are zero, as in the model's own states */
+        HIPCHK(hipMemsetAsync(H, 0, nu * d * 4, m->stream));
+        HIPCHK(hipMemcpy2DAsync(H, d * 4, reps + c0 * dl, dl * 4, dl * 4, nu, hipMemcpyHostToDevice, m->stream));
+        std::vector<int> rep_row(nu);
+        for (size_t i = 0; i < nu; ++i) rep_row[i] = (int)i;
+        SBRCHK(recommend_launch(m, H, rep_row, nu, eptr, eitems, k, out_items + c0 * k, out_scores ? out_scores + c0 * k : nullptr));
+    }
+    return SBR_OK;
+}
+
+/* ---------------------------------------------------------------------------------------------
  * numerics self-tests (tests/test_numerics_gpu.py): run the contract's primitives on the device
  * ------------------------------------------------------------------------------------------- */
 sbr_status sbr_selftest_math(const float* x, uint64_t n, float* out_cell_h, float* out_sig, float* out_tanh) {

@@ -270,6 +270,15 @@ void launch_predict(const ModelView& m, const float* user, const uint32_t* items
 void launch_rank(const ModelView& m, const float* reps, const int* rep_row, uint32_t num_users, const uint32_t* test_item,
                  const uint32_t* test_in_hist, const uint64_t* hist_ptr, const uint32_t* hist_items, float* ts_scratch,
                  uint32_t* ranks, uint32_t* nonfinite_flag, hipStream_t s);
+/* exact top-k of the catalogue per user (sbr_recommend.hip): topk_gemm_kernel keeps per (user, item range) a sorted list of the
+ * k best (score desc, id asc) in `lists` [num_users][groups][k] with its length in `lens` [num_users][groups]; topk_merge_kernel
+ * merges a user's lists in LDS into out_items / out_scores [num_users][k] (padding: 0xFFFFFFFF / -inf).  excl_ptr / excl_items:
+ * sorted, de-duplicated per-user exclusion lists (NULL: none).  groups * k <= TK_MERGE_MAX. */
+constexpr uint32_t TK_MERGE_MAX = 8192;
+uint32_t recommend_groups(uint32_t num_users, uint32_t num_items, uint32_t k, uint32_t* items_per_group);
+void launch_recommend(const ModelView& m, const float* reps, const int* rep_row, uint32_t num_users, const uint64_t* excl_ptr,
+                      const uint32_t* excl_items, uint32_t k, uint2* lists, uint32_t* lens, uint32_t* out_items, float* out_scores,
+                      uint32_t* nonfinite_flag, hipStream_t s);
 /* device self-tests of the numerics contract (tests/test_numerics_gpu.py) */
 void launch_selftest_math(const float* x, float* out_cell_h, float* out_sig, float* out_tanh, uint64_t n, hipStream_t s);
 void launch_selftest_dot_tree(const float* x, const float* y, int d, uint64_t nrows, float* out, hipStream_t s);

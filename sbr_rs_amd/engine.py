@@ -11,6 +11,11 @@ from ._abi import NUM_KERNEL_FAMILIES, KernelFamily, SbrHparams, Status, storage
 from .errors import EngineError, FittingError, PredictionError
 
 
+RECOMMEND_MAX_K = 1024  # SBR_RECOMMEND_MAX_K
+RECOMMEND_INCLUDE_HISTORY = 1  # SBR_RECOMMEND_INCLUDE_HISTORY
+RECOMMEND_NO_ITEM = 0xFFFFFFFF  # item id of a padding entry (its score is -inf)
+
+
 def _check(st: int):
     if st == Status.OK:
         return
@@ -517,6 +522,39 @@ class Model:
         mrr, n = C.c_float(), C.c_uint64()
         _check(self._L.sbr_mrr_score(self._h, _ptr(up), _ptr(it), len(up) - 1, C.byref(mrr), _ptr(ranks), C.byref(n)))
         return mrr.value, ranks[: n.value].copy()
+
+    def recommend(self, user_ptr, item_ids, k: int, include_history: bool = False):
+        """Exact top-k of the whole catalogue for each history (CSR, the layout of mrr_score): items [U, k] u32 and scores
+        [U, k] f32, score descending, ties to the lower id; short rows padded with (RECOMMEND_NO_ITEM, -inf)."""
+        up = np.ascontiguousarray(user_ptr, dtype=np.uint64)
+        it = np.ascontiguousarray(item_ids, dtype=np.uint32)
+        nu = max(len(up) - 1, 0)
+        items = np.zeros((nu, max(int(k), 0)), dtype=np.uint32)
+        scores = np.zeros((nu, max(int(k), 0)), dtype=np.float32)
+        flags = RECOMMEND_INCLUDE_HISTORY if include_history else 0
+        _check(self._L.sbr_recommend(self._h, _ptr(up), _ptr(it), nu, int(k) & 0xFFFFFFFF, flags, _ptr(items), _ptr(scores)))
+        return items, scores
+
+    def recommend_reps(self, reps, k: int, exclude=None):
+        """As recommend, from representations [U, embedding_dim] (user_representation's); exclude: None or one sequence of
+        item ids per user."""
+        reps = np.ascontiguousarray(reps, dtype=np.float32).reshape(-1, self.dim)
+        nu = reps.shape[0]
+        items = np.zeros((nu, max(int(k), 0)), dtype=np.uint32)
+        scores = np.zeros((nu, max(int(k), 0)), dtype=np.float32)
+        ep = ei = None
+        if exclude is not None:
+            if len(exclude) != nu:
+                raise ValueError("one exclusion list per user")
+            lists = [np.asarray(e, dtype=np.uint32).ravel() for e in exclude]
+            ep = np.zeros(nu + 1, dtype=np.uint64)
+            ep[1:] = np.cumsum([x.size for x in lists])
+            ei = np.ascontiguousarray(np.concatenate(lists) if lists else np.zeros(0, np.uint32), dtype=np.uint32)
+            if ei.size == 0:
+                ei = np.zeros(1, dtype=np.uint32)
+        _check(self._L.sbr_recommend_reps(self._h, _ptr(reps), nu, int(k) & 0xFFFFFFFF, None if ep is None else _ptr(ep),
+                                          None if ei is None else _ptr(ei), _ptr(items), _ptr(scores)))
+        return items, scores
 
     def close(self):
         if getattr(self, "_h", None):

@@ -230,6 +230,20 @@ class _ImplicitSequenceModel:
     def predict(self, user: ImplicitUser, item_ids) -> np.ndarray:
         return self.params.predict(user.user_embedding, np.asarray(item_ids, dtype=np.uint32))
 
+    def recommend(self, interactions_or_histories, k: int, exclude_history: bool = True):
+        """The k best items of the whole catalogue for each user's history, on the device: (items [U, k] u32, scores
+        [U, k] f32), score descending, ties to the lower item id.  ``interactions_or_histories`` is a
+        CompressedInteractions or a list of item-id sequences.  Every item of a history is excluded unless
+        ``exclude_history`` is False; a row with fewer than k eligible items is padded with (0xFFFFFFFF, -inf)."""
+        if isinstance(interactions_or_histories, CompressedInteractions):
+            up, it = interactions_or_histories.user_pointers, interactions_or_histories.item_ids
+        else:
+            seqs = [np.asarray(h, dtype=np.uint32).ravel() for h in interactions_or_histories]
+            up = np.zeros(len(seqs) + 1, dtype=np.uint64)
+            up[1:] = np.cumsum([s.size for s in seqs])
+            it = np.concatenate(seqs) if seqs else np.zeros(0, dtype=np.uint32)
+        return self.params.recommend(up, it, k, include_history=not exclude_history)
+
 
 class ImplicitLSTMModel(_ImplicitSequenceModel):
     """An LSTM-based sequence model for implicit feedback (lstm.rs:386-416)."""
