@@ -1,0 +1,539 @@
+/* sbr_catalogue.hip — the prediction side: scores of items for a user state, and scans of the whole catalogue for a batch of
+ * user states (mrr_score's ranks, recommend's top k).
+ *
+ *   predict_kernel         : b[i] + chain_dot(h, E[i]), k ascending from 0 (sbr_predict)
+ *   rank_test_score_kernel : ts[u] = MIN if the test item is in the history, else bias + chain dot
+ *   rank_gemm_kernel       : counts S[u][i] >= ts[u] (mrr_score, evaluation.rs:27-43)
+ *   rank_history_kernel    : corrects the count for the (unique) history items, which the reference masks to f32::MIN
+ *                            (evaluation.rs:30-32)
+ *   topk_gemm_kernel       : per user and item range, a running sorted list of the k best (score desc, id asc) in global scratch
+ *                            and its k-th entry as the threshold in LDS.  A score that beats the threshold is staged in LDS; a
+ *                            full staging buffer is sorted and merged into the list (which raises the threshold).
+ *   topk_merge_kernel      : one workgroup per user merges the item ranges' lists into the final k, padded with
+ *                            (0xFFFFFFFF, -inf).
+ *
+ * The two GEMM kernels share one catalogue scan, S[u][i] = b[i] + sum_k h[u][k] E[i][k] on v_mfma_f32_32x32x2_f32: a workgroup
+ * owns 128 users (4 waves x 32, their states held in registers as MFMA A fragments) and a contiguous range of items, whose
+ * 32-item tiles of E and b stream through an LDS double buffer; k ascends from 0, so every score has the bits of sbr_predict.  The
+ * U x I score matrix never leaves the registers.  The top-k epilogue cannot overflow (a staging buffer that fills is merged and
+ * the candidates that did not fit are offered again), and its result is the first k of a total order, so it is deterministic. */
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "sbr_device.h"
+#include "sbr_kernels.h"
+
+namespace sbr {
+
+namespace {
+
+/* ---- the catalogue scan shared by rank_gemm_kernel and topk_gemm_kernel ---- */
+
+/* The user of accumulator register q of a lane in wave half hh, for a wave whose 32 users start at u0 (the C layout of
+ * v_mfma_f32_32x32x2_f32: row (q & 3) + 8 (q >> 2) + 4 hh; the lane's item is lane & 31). */
+template <class T>
+__device__ __forceinline__ T acc_user(T u0, int q, int hh) { return u0 + (q & 3) + 8 * (q >> 2) + 4 * hh; }
+
+/* Per-user LDS state of a workgroup is indexed by slot p = wave * 32 + hh * 16 + q, the order its accumulator registers read it
+ * (16-byte broadcasts); the user of slot p among the workgroup's 128. */
+__device__ __forceinline__ int slot_user(int p) { return acc_user((p >> 5) * 32, p & 15, (p >> 4) & 1); }
+
+/* A fragments of the wave's users u0 + (lane & 31), held for the whole item range: a[s] = h[u][2 s + lane / 32]; zero past the
+ * last user. */
+template <int D>
+__device__ __forceinline__ void load_user_fragments(float (&a)[D / 2], const float* reps, const int* rep_row, uint32_t num_users,
+                                                    uint32_t u0) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t u = u0 + (lane & 31);
+    const int hh = lane >> 5;
+    const float* h = reps + (size_t)rep_row[u < num_users ? u : num_users - 1] * D;
+#pragma unroll
+    for (int s = 0; s < D / 2; ++s) a[s] = u < num_users ? h[2 * s + hh] : 0.0f;
+}
+
+/* The 32-item tiles of E and b in the workgroup's item range [i_begin, i_end) (range blockIdx.y): fetch() loads one into
+ * registers, zeros past i_end; stage() writes them to one half of the LDS double buffer (E rows LDE floats apart).  Thread map:
+ * idx = tid + 256 it -> item row idx / (D / 4), float4 column idx % (D / 4). */
+template <int D>
+struct ItemTiles {
+    static constexpr int LDE = D + 1;
+    static constexpr int NV = 32 * (D / 4);
+    static constexpr int ITER = (NV + 255) / 256;
+    uint32_t i_begin, i_end;
+    int ntiles;
+    float4 ev[ITER];
+    float bv = 0.0f;
+
+    __device__ __forceinline__ ItemTiles(const ModelView& m, uint32_t items_per_group) {
+        i_begin = blockIdx.y * items_per_group;
+        i_end = i_begin + items_per_group;
+        if (i_end > m.num_items) i_end = m.num_items;
+        ntiles = i_begin < i_end ? (int)((i_end - i_begin + 31) / 32) : 0;
+    }
+    __device__ __forceinline__ void fetch(const ModelView& m, int tile) {
+        const int tid = threadIdx.x;
+        const uint32_t ib = i_begin + (uint32_t)tile * 32;
+#pragma unroll
+        for (int it = 0; it < ITER; ++it) {
+            const int idx = tid + it * 256;
+            const int r = idx / (D / 4);
+            const int c4 = (idx % (D / 4)) * 4;
+            ev[it] = (idx < NV && ib + r < i_end) ? ld4(m.E + (size_t)(ib + r) * D + c4) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        if (tid < 32) bv = ib + tid < i_end ? m.b[ib + tid] : 0.0f;
+    }
+    __device__ __forceinline__ void stage(float* Es, float* Bs) {
+        const int tid = threadIdx.x;
+#pragma unroll
+        for (int it = 0; it < ITER; ++it) {
+            const int idx = tid + it * 256;
+            if (idx < NV) {
+                const int r = idx / (D / 4);
+                const int c4 = (idx % (D / 4)) * 4;
+                float* dst = &Es[r * LDE + c4];
+                dst[0] = ev[it].x; dst[1] = ev[it].y; dst[2] = ev[it].z; dst[3] = ev[it].w;
+            }
+        }
+        if (tid < 32) Bs[tid] = bv;
+    }
+};
+
+/* One staged tile's dots: acc[q] = sum_k h[u][k] E[i][k] for user acc_user(u0, q, hh) and item lane & 31, a chain of
+ * v_mfma_f32_32x32x2_f32 with k ascending from 0 (the numerics contract: bias + acc[q] has the bits of sbr_predict). */
+template <int D>
+__device__ __forceinline__ f32x16 tile_dots(const float (&a)[D / 2], const float* Es) {
+    const int lane = threadIdx.x & 63;
+    f32x16 acc;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) acc[q] = 0.0f;
+    const float* eb = &Es[(lane & 31) * ItemTiles<D>::LDE + (lane >> 5)];
+#pragma unroll
+    for (int s = 0; s < D / 2; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s], eb[2 * s], acc, 0, 0, 0);
+    return acc;
+}
+
+/* Item ranges of a scan over utiles 128-user tiles: about target_wgs workgroups in all, whole 32-item tiles per range, at most
+ * max_groups ranges of at most max_per items.  Returns the number of ranges; *items_per_group their length. */
+uint32_t split_items(uint32_t num_items, uint32_t utiles, uint32_t target_wgs, uint32_t max_groups, uint32_t max_per,
+                     uint32_t* items_per_group) {
+    uint32_t groups = (target_wgs + utiles - 1) / utiles;
+    if (groups > (num_items + 31) / 32) groups = (num_items + 31) / 32;
+    if (groups > max_groups) groups = max_groups;
+    if (groups < 1) groups = 1;
+    uint32_t per = (num_items + groups - 1) / groups;
+    per = ((per + 31) / 32) * 32;
+    if (per > max_per) per = max_per;
+    *items_per_group = per;
+    return (num_items + per - 1) / per;
+}
+
+constexpr int TK_STAGE = 32;                 /* staged candidates per user between merges */
+constexpr uint32_t TK_NONE = 0xFFFFFFFFu;    /* padding id; its score is -inf */
+
+/* (score desc, id asc); -0.0 == +0.0 */
+__device__ __forceinline__ bool tk_better(float as, uint32_t ai, float bs, uint32_t bi) { return as > bs || (as == bs && ai < bi); }
+
+}  // namespace
+
+// ------------------------------------------------------------------------------------------------
+// bias + chain-order dot (≙ an f32 MFMA accumulation over k)
+// ------------------------------------------------------------------------------------------------
+template <int D>
+__device__ __forceinline__ float chain_dot(const float* __restrict__ h, const float* __restrict__ e) {
+    float acc = 0.0f;
+#pragma unroll
+    for (int k4 = 0; k4 < D; k4 += 4) {
+        const float4 v = ld4(e + k4);
+        acc = sbr_fma(h[k4 + 0], v.x, acc);
+        acc = sbr_fma(h[k4 + 1], v.y, acc);
+        acc = sbr_fma(h[k4 + 2], v.z, acc);
+        acc = sbr_fma(h[k4 + 3], v.w, acc);
+    }
+    return acc;
+}
+
+template <int D>
+__global__ void predict_kernel(ModelView m, const float* user, const uint32_t* items, uint64_t n, float* out) {
+    __shared__ float hs[D];
+    for (int k = threadIdx.x; k < D; k += blockDim.x) hs[k] = user[k];
+    __syncthreads();
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t it = items[i];
+    out[i] = m.b[it] + chain_dot<D>(hs, m.E + (size_t)it * D);
+}
+
+// ------------------------------------------------------------------------------------------------
+// mrr_score's ranks: the catalogue scan with a rank-count epilogue
+// ------------------------------------------------------------------------------------------------
+template <int D>
+__global__ void rank_test_score_kernel(ModelView m, const float* reps, const int* rep_row, uint32_t num_users,
+                                       const uint32_t* test_item, const uint32_t* test_in_hist, float* ts, uint32_t* ranks) {
+    const uint32_t u = blockIdx.x * blockDim.x + threadIdx.x;
+    if (u >= num_users) return;
+    const uint32_t ti = test_item[u];
+    ts[u] = test_in_hist[u] ? SBR_F32_MIN : m.b[ti] + chain_dot<D>(reps + (size_t)rep_row[u] * D, m.E + (size_t)ti * D);
+    ranks[u] = 0;
+}
+
+template <int D>
+__global__ __launch_bounds__(256, D <= 128 ? 4 : 2) void rank_gemm_kernel(ModelView m, const float* reps, const int* rep_row, uint32_t num_users,
+                                                                         const float* ts, uint32_t items_per_group, uint32_t* ranks,
+                                                                         uint32_t* nonfinite_flag) {
+    __shared__ float Es[2][32 * ItemTiles<D>::LDE];
+    __shared__ float Bs[2][32];
+    __shared__ float Ts[128]; /* thresholds by slot (slot_user) */
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = tid >> 6;
+    const int l31 = lane & 31;
+    const int hh = lane >> 5;
+    const uint32_t u0 = blockIdx.x * 128 + wave * 32;
+    float a[D / 2];
+    load_user_fragments<D>(a, reps, rep_row, num_users, u0);
+    if (tid < 128) {
+        const uint32_t u = blockIdx.x * 128 + (uint32_t)slot_user(tid);
+        Ts[tid] = u < num_users ? ts[u] : 0.0f;
+    }
+    // per-lane counters of "score >= threshold", two 16-bit counters per register (a lane adds at most one per tile and
+    // register: the launcher keeps an item range below 65 536 tiles)
+    uint32_t cnt2[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) cnt2[q] = 0;
+    bool bad = false;
+    ItemTiles<D> tiles(m, items_per_group);
+    const int ntiles = tiles.ntiles;
+    if (ntiles > 0) {
+        tiles.fetch(m, 0);
+        tiles.stage(Es[0], Bs[0]);
+    }
+    __syncthreads();
+    const int pbase = wave * 32 + hh * 16;
+    for (int tile = 0; tile < ntiles; ++tile) {
+        const int buf = tile & 1;
+        if (tile + 1 < ntiles) tiles.fetch(m, tile + 1);
+        const f32x16 acc = tile_dots<D>(a, Es[buf]);
+        const float bias = Bs[buf][l31];
+        const bool item_ok = tiles.i_begin + (uint32_t)tile * 32 + l31 < tiles.i_end;
+#pragma unroll
+        for (int q4 = 0; q4 < 4; ++q4) {
+            const float4 t4 = ld4(&Ts[pbase + 4 * q4]);
+            const float tq[4] = {t4.x, t4.y, t4.z, t4.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int q = 4 * q4 + j;
+                const float sc = bias + acc[q];
+                if (item_ok) {
+                    if (!(sc - sc == 0.0f)) bad = true;
+                    if (sc >= tq[j]) cnt2[q >> 1] += (q & 1) ? 0x10000u : 1u;
+                }
+            }
+        }
+        if (tile + 1 < ntiles) tiles.stage(Es[buf ^ 1], Bs[buf ^ 1]);
+        __syncthreads();
+    }
+    // per-user totals: sum over the 32 item lanes of each half-wave
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+        int c = (int)((cnt2[q >> 1] >> ((q & 1) * 16)) & 0xFFFFu);
+#pragma unroll
+        for (int off = 16; off >= 1; off >>= 1) c += __shfl_xor(c, off, 64);
+        const uint32_t u = acc_user(u0, q, hh);
+        if (l31 == 0 && u < num_users && c) atomicAdd(&ranks[u], (uint32_t)c);
+    }
+    if (__any(bad) && lane == 0) atomicOr(nonfinite_flag, 1u);
+}
+
+template <int D>
+__global__ __launch_bounds__(64) void rank_history_kernel(ModelView m, const float* reps, const int* rep_row, const float* ts,
+                                                          const uint64_t* hist_ptr, const uint32_t* hist_items, uint32_t* ranks) {
+    const int u = blockIdx.x;
+    const float* h = reps + (size_t)rep_row[u] * D;
+    const float t = ts[u];
+    int cnt = 0;
+    for (uint64_t e = hist_ptr[u] + threadIdx.x; e < hist_ptr[u + 1]; e += 64) {
+        const uint32_t i = hist_items[e];
+        const float s = m.b[i] + chain_dot<D>(h, m.E + (size_t)i * D);
+        if (s >= t) --cnt;               /* it was counted by the GEMM pass ...          */
+        if (SBR_F32_MIN >= t) ++cnt;     /* ... but the masked value only counts against MIN */
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
+    if (threadIdx.x == 0 && cnt) atomicAdd(&ranks[u], (uint32_t)cnt); /* two's complement: adds a negative delta */
+}
+
+// ------------------------------------------------------------------------------------------------
+// recommend's top k: the catalogue scan with a top-k epilogue, then a merge of the item ranges
+// ------------------------------------------------------------------------------------------------
+template <int D>
+__global__ __launch_bounds__(256, D <= 128 ? 2 : 1) void topk_gemm_kernel(ModelView m, const float* reps, const int* rep_row, uint32_t num_users,
+                                                                         const uint64_t* excl_ptr, const uint32_t* excl_items,
+                                                                         uint32_t items_per_group, uint32_t k, uint2* lists, uint32_t* lens,
+                                                                         uint32_t* nonfinite_flag) {
+    __shared__ float Es[2][32 * ItemTiles<D>::LDE];
+    __shared__ float Bs[2][32];
+    // per-user state by slot (slot_user)
+    __shared__ float thS[128];
+    __shared__ uint32_t thI[128];
+    __shared__ uint32_t cnt[128];
+    __shared__ uint32_t len[128];
+    __shared__ uint2 st[128][TK_STAGE];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = tid >> 6;
+    const int l31 = lane & 31;
+    const int hh = lane >> 5;
+    const uint32_t G = gridDim.y;
+    const uint32_t u0 = blockIdx.x * 128 + wave * 32;
+    float a[D / 2];
+    load_user_fragments<D>(a, reps, rep_row, num_users, u0);
+    if (tid < 128) {
+        thS[tid] = -INFINITY;
+        thI[tid] = TK_NONE;
+        cnt[tid] = 0;
+        len[tid] = 0;
+    }
+    uint32_t umask = 0; /* accumulator registers q whose user exists */
+#pragma unroll
+    for (int q = 0; q < 16; ++q)
+        if (acc_user(u0, q, hh) < num_users) umask |= 1u << q;
+    bool bad = false;
+    ItemTiles<D> tiles(m, items_per_group);
+    const int ntiles = tiles.ntiles;
+    // Merges the staged candidates of every user with at least `min_count` of them into the user's list.  Half a wave per user
+    // (at most 32 staged), users p = wave + 4 j; a user's list is only ever touched by the same wave.
+    auto merge_staged = [&](uint32_t min_count) {
+        const int h32 = lane >> 5, ln = lane & 31;
+        for (int j = 0; j < 16; ++j) {
+            const int p = wave + 4 * (2 * j + h32);
+            const uint32_t c = cnt[p];
+            if (c < min_count || c == 0) continue;
+            const int n = c < (uint32_t)TK_STAGE ? (int)c : TK_STAGE;
+            const int qq = p & 15; /* slot_user(p) written out: through the helper this kernel compiled up to 3 % slower (d = 128) */
+            const uint32_t ug = blockIdx.x * 128 + (uint32_t)((p >> 5) * 32 + (qq & 3) + 8 * (qq >> 2) + 4 * ((p >> 4) & 1));
+            float s = -INFINITY;
+            uint32_t id = TK_NONE;
+            if (ln < n) {
+                const uint2 e = st[p][ln];
+                s = __uint_as_float(e.x);
+                id = e.y;
+                if (excl_ptr) { /* sorted, de-duplicated exclusion list of the user */
+                    uint64_t lo = excl_ptr[ug], hi = excl_ptr[ug + 1];
+                    while (lo < hi) {
+                        const uint64_t mid = (lo + hi) >> 1;
+                        if (excl_items[mid] < id) lo = mid + 1; else hi = mid;
+                    }
+                    if (lo < excl_ptr[ug + 1] && excl_items[lo] == id) { s = -INFINITY; id = TK_NONE; }
+                }
+            }
+            // bitonic sort of the 32 lanes, best first
+#pragma unroll
+            for (int kk = 2; kk <= 32; kk <<= 1)
+#pragma unroll
+                for (int jj = kk >> 1; jj > 0; jj >>= 1) {
+                    const float os = __shfl_xor(s, jj, 64);
+                    const uint32_t oi = (uint32_t)__shfl_xor((int)id, jj, 64);
+                    const bool keep_better = ((ln & jj) == 0) == ((ln & kk) == 0);
+                    if (keep_better ? tk_better(os, oi, s, id) : tk_better(s, id, os, oi)) { s = os; id = oi; }
+                }
+            const uint64_t real = __ballot(id != TK_NONE);
+            const int ne = __popcll(h32 ? (real >> 32) : (real & 0xFFFFFFFFull));
+            if (ne == 0) {
+                if (ln == 0) cnt[p] = 0;
+                continue;
+            }
+            st[p][ln] = make_uint2(__float_as_uint(s), id);
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            const uint32_t L0 = len[p];
+            uint2* L = lists + ((size_t)ug * G + blockIdx.y) * k;
+            // new position of staged entry ln: ln + #{list entries better than it}
+            uint32_t pos = 0;
+            if (ln < ne) {
+                uint32_t lo = 0, hi = L0;
+                while (lo < hi) {
+                    const uint32_t mid = (lo + hi) >> 1;
+                    const uint2 e = L[mid];
+                    if (tk_better(__uint_as_float(e.x), e.y, s, id)) lo = mid + 1; else hi = mid;
+                }
+                pos = (uint32_t)ln + lo;
+            }
+            const uint32_t first = (uint32_t)__shfl((int)pos, h32 * 32, 64); /* list entries before it stay where they are */
+            // list entries [first, L0) move back by the number of staged entries better than them: chunks of 32 from the back, every
+            // chunk read before it is written (a chunk's entries only move to higher positions than its own)
+            if (L0 > first) {
+                for (uint32_t cb = first + ((L0 - 1 - first) / 32) * 32;; cb -= 32) {
+                    const uint32_t i = cb + (uint32_t)ln;
+                    if (i < L0) {
+                        const uint2 e = L[i];
+                        const float es = __uint_as_float(e.x);
+                        int lo = 0, hi = ne;
+                        while (lo < hi) {
+                            const int mid = (lo + hi) >> 1;
+                            const uint2 sv = st[p][mid];
+                            if (tk_better(__uint_as_float(sv.x), sv.y, es, e.y)) lo = mid + 1; else hi = mid;
+                        }
+                        const uint32_t np = i + (uint32_t)lo;
+                        if (np < k) {
+                            L[np] = e;
+                            if (np == k - 1) { thS[p] = es; thI[p] = e.y; }
+                        }
+                    }
+                    if (cb == first) break;
+                }
+            }
+            if (ln < ne && pos < k) {
+                L[pos] = make_uint2(__float_as_uint(s), id);
+                if (pos == k - 1) { thS[p] = s; thI[p] = id; }
+            }
+            if (ln == 0) {
+                len[p] = L0 + (uint32_t)ne < k ? L0 + (uint32_t)ne : k;
+                cnt[p] = 0;
+            }
+        }
+    };
+    if (ntiles > 0) {
+        tiles.fetch(m, 0);
+        tiles.stage(Es[0], Bs[0]);
+    }
+    __syncthreads();
+    const int pbase = wave * 32 + hh * 16;
+    for (int tile = 0; tile < ntiles; ++tile) {
+        const int buf = tile & 1;
+        if (tile + 1 < ntiles) tiles.fetch(m, tile + 1);
+        const f32x16 acc = tile_dots<D>(a, Es[buf]);
+        const float bias = Bs[buf][l31];
+        const uint32_t id = tiles.i_begin + (uint32_t)tile * 32 + (uint32_t)l31;
+        uint32_t pend = id < tiles.i_end ? umask : 0u;
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            const float sc = bias + acc[q];
+            if (((pend >> q) & 1u) && !(sc - sc == 0.0f)) { bad = true; pend &= ~(1u << q); }
+        }
+        // offers the pending scores: below the threshold they are dropped, above it they take a staging slot if one is left
+        auto offer = [&]() {
+            if (!pend) return;
+#pragma unroll
+            for (int q4 = 0; q4 < 4; ++q4) {
+                const float4 t4 = ld4(&thS[pbase + 4 * q4]);
+                const uint4 i4 = *reinterpret_cast<const uint4*>(&thI[pbase + 4 * q4]);
+                const float ts[4] = {t4.x, t4.y, t4.z, t4.w};
+                const uint32_t ti[4] = {i4.x, i4.y, i4.z, i4.w};
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int q = 4 * q4 + j;
+                    const float sc = bias + acc[q];
+                    if (((pend >> q) & 1u) && !tk_better(sc, id, ts[j], ti[j])) pend &= ~(1u << q);
+                }
+            }
+            if (!pend) return;
+#pragma unroll
+            for (int q = 0; q < 16; ++q)
+                if ((pend >> q) & 1u) {
+                    const float sc = bias + acc[q];
+                    const uint32_t slot = atomicAdd(&cnt[pbase + q], 1u);
+                    if (slot < (uint32_t)TK_STAGE) {
+                        st[pbase + q][slot] = make_uint2(__float_as_uint(sc), id);
+                        pend &= ~(1u << q);
+                    }
+                }
+        };
+        offer();
+        if (tile + 1 < ntiles) tiles.stage(Es[buf ^ 1], Bs[buf ^ 1]);
+        // a user whose staging filled is merged, then what did not fit is offered again (it fits: at most 32 per user and tile)
+        while (__syncthreads_or(pend != 0u)) {
+            merge_staged((uint32_t)TK_STAGE);
+            __syncthreads();
+            offer();
+        }
+    }
+    merge_staged(1u);
+    __syncthreads();
+    if (tid < 128) {
+        const uint32_t u = blockIdx.x * 128 + (uint32_t)slot_user(tid);
+        if (u < num_users) lens[(size_t)u * G + blockIdx.y] = len[tid];
+    }
+    if (__any(bad) && lane == 0) atomicOr(nonfinite_flag, 1u);
+}
+
+/* The G sorted lists of one user -> its k best, by a bitonic sort of all their entries in LDS (n = power of two >= G k, at most
+ * TK_MERGE_MAX entries; empty slots hold the padding pair, which sorts last). */
+__global__ __launch_bounds__(512) void topk_merge_kernel(const uint2* lists, const uint32_t* lens, uint32_t G, uint32_t k, uint32_t n,
+                                                         uint32_t* out_items, float* out_scores) {
+    __shared__ uint2 sm[TK_MERGE_MAX];
+    const uint32_t u = blockIdx.x;
+    const uint2* L = lists + (size_t)u * G * k;
+    for (uint32_t e = threadIdx.x; e < n; e += blockDim.x) {
+        const uint32_t g = e / k, j = e - g * k;
+        sm[e] = (g < G && j < lens[(size_t)u * G + g]) ? L[e] : make_uint2(__float_as_uint(-INFINITY), TK_NONE);
+    }
+    __syncthreads();
+    for (uint32_t kk = 2; kk <= n; kk <<= 1)
+        for (uint32_t jj = kk >> 1; jj > 0; jj >>= 1) {
+            for (uint32_t i = threadIdx.x; i < n / 2; i += blockDim.x) {
+                const uint32_t lo = 2 * jj * (i / jj) + (i % jj), hi = lo + jj;
+                const uint2 x = sm[lo], y = sm[hi];
+                const bool yb = tk_better(__uint_as_float(y.x), y.y, __uint_as_float(x.x), x.y);
+                const bool xb = tk_better(__uint_as_float(x.x), x.y, __uint_as_float(y.x), y.y);
+                if ((lo & kk) == 0 ? yb : xb) { sm[lo] = y; sm[hi] = x; }
+            }
+            __syncthreads();
+        }
+    for (uint32_t j = threadIdx.x; j < k; j += blockDim.x) {
+        const uint2 e = j < n ? sm[j] : make_uint2(__float_as_uint(-INFINITY), TK_NONE);
+        out_items[(size_t)u * k + j] = e.y;
+        if (out_scores) out_scores[(size_t)u * k + j] = __uint_as_float(e.x);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// launchers
+// ------------------------------------------------------------------------------------------------
+void launch_predict(const ModelView& m, const float* user, const uint32_t* items, uint64_t n, float* out, hipStream_t s) {
+    if (n == 0) return;
+    DISPATCH_D(m.d, { hipLaunchKernelGGL((predict_kernel<DD>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, m, user, items, n, out); });
+}
+
+void launch_rank(const ModelView& m, const float* reps, const int* rep_row, uint32_t num_users, const uint32_t* test_item,
+                 const uint32_t* test_in_hist, const uint64_t* hist_ptr, const uint32_t* hist_items, float* ts_scratch,
+                 uint32_t* ranks, uint32_t* nonfinite_flag, hipStream_t s) {
+    if (num_users == 0) return;
+    // 32 users per wave (128 per workgroup, four waves per SIMD).  (A 64-users-per-wave form — half the barriers and LDS fills per
+    // flop at half the waves — measured 5 % slower at 8 192 users x 1e6 items, d = 128: 100 against 105 TFLOP/s; removed.)
+    const uint32_t utiles = (num_users + 127) / 128;
+    // item ranges: MANY more workgroups than the chip holds at once (a launch of 1 024 workgroups on 768 resident slots ran one
+    // full round and a third of a second one); the kernel's per-lane counters are 16 bits wide: fewer than 65 536 tiles per range
+    uint32_t per = 0;
+    const uint32_t groups = split_items(m.num_items, utiles, 768u * 6u, UINT32_MAX, 65535u * 32u, &per);
+    DISPATCH_D(m.d, {
+        hipLaunchKernelGGL((rank_test_score_kernel<DD>), dim3((num_users + 255) / 256), dim3(256), 0, s, m, reps, rep_row, num_users, test_item, test_in_hist, ts_scratch, ranks);
+        hipLaunchKernelGGL((rank_gemm_kernel<DD>), dim3(utiles, groups), dim3(256), 0, s, m, reps, rep_row, num_users, ts_scratch, per, ranks, nonfinite_flag);
+        hipLaunchKernelGGL((rank_history_kernel<DD>), dim3(num_users), dim3(64), 0, s, m, reps, rep_row, ts_scratch, hist_ptr, hist_items, ranks);
+    });
+}
+
+uint32_t recommend_groups(uint32_t num_users, uint32_t num_items, uint32_t k, uint32_t* items_per_group) {
+    // Two rounds of the chip's resident slots (two workgroups per CU at d <= 128), not launch_rank's six: a range's first k items
+    // are all candidates and the rest about k ln(range / k), so fewer, longer ranges merge less (8 192 users x 1e6 items, d = 128,
+    // k = 100: 113 ms of kernels at 4 608 workgroups); at most TK_MERGE_MAX / k lists per user for the merge
+    return split_items(num_items, (num_users + 127) / 128, 256u * 2u * 2u, TK_MERGE_MAX / k, UINT32_MAX, items_per_group);
+}
+
+void launch_recommend(const ModelView& m, const float* reps, const int* rep_row, uint32_t num_users, const uint64_t* excl_ptr,
+                      const uint32_t* excl_items, uint32_t k, uint2* lists, uint32_t* lens, uint32_t* out_items, float* out_scores,
+                      uint32_t* nonfinite_flag, hipStream_t s) {
+    if (num_users == 0) return;
+    uint32_t per = 0;
+    const uint32_t groups = recommend_groups(num_users, m.num_items, k, &per);
+    const uint32_t utiles = (num_users + 127) / 128;
+    uint32_t n = 1;
+    while (n < groups * k) n <<= 1;
+    DISPATCH_D(m.d, {
+        hipLaunchKernelGGL((topk_gemm_kernel<DD>), dim3(utiles, groups), dim3(256), 0, s, m, reps, rep_row, num_users, excl_ptr, excl_items,
+                           per, k, lists, lens, nonfinite_flag);
+        hipLaunchKernelGGL(topk_merge_kernel, dim3(num_users), dim3(512), 0, s, lists, lens, groups, k, n, out_items, out_scores);
+    });
+}
+
+}  // namespace sbr

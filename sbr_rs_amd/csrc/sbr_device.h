@@ -1,6 +1,7 @@
-/* sbr_device.h — device-side helpers shared by the kernel translation units (sbr_kernels.hip, sbr_steps.hip): 16-byte loads and
- * stores, the group all-reduce that realises the contract's dot order, the optimiser element update, the packed-f32 forms of the
- * rational tanh, and the SmallTail of a one-sequence step (header + loss accumulators + lagged loss figure + key ordering).
+/* sbr_device.h — device-side helpers shared by the kernel translation units (sbr_kernels.hip, sbr_steps.hip, sbr_catalogue.hip):
+ * 16-byte loads and stores, the group all-reduce that realises the contract's dot order, the optimiser element update, the
+ * packed-f32 forms of the rational tanh, and the SmallTail of a one-sequence step (header + loss accumulators + lagged loss figure
+ * + key ordering); and the launchers' dispatch on d (DISPATCH_D).
  * Everything here is __device__ __forceinline__: no symbol leaves a translation unit. */
 #ifndef SBR_DEVICE_H
 #define SBR_DEVICE_H
@@ -12,6 +13,8 @@
 #include "sbr_numerics.h"
 
 namespace sbr {
+
+typedef float f32x16 __attribute__((ext_vector_type(16))); /* the accumulators of v_mfma_f32_32x32x2_f32 */
 
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
@@ -196,4 +199,15 @@ __device__ __forceinline__ void small_tail(const MbView& mb, const BlockView& bl
 }
 
 }  // namespace sbr
+
+/* host side: runs the statement list with constexpr int DD = d for the storage widths the kernels are built for */
+#define DISPATCH_D(d, ...)                                         \
+    switch (d) {                                                   \
+        case 16: { constexpr int DD = 16; __VA_ARGS__; } break;    \
+        case 32: { constexpr int DD = 32; __VA_ARGS__; } break;    \
+        case 64: { constexpr int DD = 64; __VA_ARGS__; } break;    \
+        case 128: { constexpr int DD = 128; __VA_ARGS__; } break;  \
+        case 256: { constexpr int DD = 256; __VA_ARGS__; } break;  \
+        default: break;                                            \
+    }
 #endif

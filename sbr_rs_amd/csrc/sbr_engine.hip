@@ -3,7 +3,7 @@
 // Owns device memory (parameters resident in HBM for the life of the model), restates the
 // reference's training driver (fit_sequence_model, /root/reference/src/models/sequence_model.rs:
 // 70-178) as host-side index work (chunking, shuffles, partitioning, packing) and drives the
-// gfx950 kernels of sbr_kernels.hip on one HIP stream.  There is no CPU compute fallback: without
+// gfx950 kernels of sbr_kernels.hip and sbr_catalogue.hip on one HIP stream.  There is no CPU compute fallback: without
 // a HIP device every entry point returns SBR_ERR_NO_DEVICE.
 
 #include <hip/hip_runtime.h>
@@ -3394,20 +3394,75 @@ sbr_status forward_histories(sbr_model* m, const std::vector<const uint32_t*>& f
     return SBR_OK;
 }
 
+/* The state of a history of n items: its last T items (sequence_model.rs:188); an empty history is one step of item 0
+ * (lstm.rs:262-264). */
+void state_window(const uint32_t* items, uint64_t n, uint64_t T, const uint32_t** first, int* nsteps) {
+    static const uint32_t zero = 0;
+    const uint64_t keep = std::min(n, T);
+    *first = n ? items + (n - keep) : &zero;
+    *nsteps = n ? (int)keep : 1;
+}
+
+/* A batch of users, user i's history items[i][0, len[i]): the state windows and, with lists, each history sorted and
+ * de-duplicated in one CSR buffer (list_ptr [nu + 1], list_items; both empty without lists). */
+struct UserBatch {
+    std::vector<const uint32_t*> first;
+    std::vector<int> nsteps;
+    std::vector<uint64_t> list_ptr;
+    std::vector<uint32_t> list_items;
+};
+
+void prepare_users(const std::vector<const uint32_t*>& items, const std::vector<uint64_t>& len, uint64_t T, bool lists, UserBatch* out) {
+    const size_t nu = items.size();
+    UserBatch& b = *out;
+    b.first.resize(nu);
+    b.nsteps.resize(nu);
+    std::vector<uint64_t> raw_ptr(nu + 1, 0);
+    std::vector<uint32_t> uniq_count(nu, 0);
+    if (lists) {
+        for (size_t i = 0; i < nu; ++i) raw_ptr[i + 1] = raw_ptr[i] + len[i];
+        b.list_items.resize(raw_ptr[nu]);
+        b.list_ptr.assign(nu + 1, 0);
+    }
+    /* sorted + de-duplicated in place inside one buffer (a vector per user was a third of mrr_score's host time at 8 192 users),
+     * a few host threads over user ranges */
+    auto prepare = [&](size_t i0, size_t i1) {
+        for (size_t i = i0; i < i1; ++i) {
+            state_window(items[i], len[i], T, &b.first[i], &b.nsteps[i]);
+            if (!lists || len[i] == 0) continue;
+            uint32_t* h = b.list_items.data() + raw_ptr[i];
+            std::memcpy(h, items[i], len[i] * 4);
+            std::sort(h, h + len[i]);
+            uniq_count[i] = (uint32_t)(std::unique(h, h + len[i]) - h);
+        }
+    };
+    const size_t nthreads = nu >= 2048 ? 8 : 1;
+    if (nthreads == 1) prepare(0, nu);
+    else {
+        std::vector<std::thread> workers;
+        for (size_t t = 0; t < nthreads; ++t) workers.emplace_back(prepare, nu * t / nthreads, nu * (t + 1) / nthreads);
+        for (auto& w : workers) w.join();
+    }
+    if (lists) {
+        for (size_t i = 0; i < nu; ++i) { /* close the gaps the de-duplication left */
+            if (b.list_ptr[i] != raw_ptr[i]) std::memmove(b.list_items.data() + b.list_ptr[i], b.list_items.data() + raw_ptr[i], (size_t)uniq_count[i] * 4);
+            b.list_ptr[i + 1] = b.list_ptr[i] + uniq_count[i];
+        }
+        b.list_items.resize(b.list_ptr[nu]);
+    }
+}
+
 }  // namespace
 
 sbr_status sbr_user_representation(sbr_model* m, const uint32_t* item_ids, uint64_t n, float* out_dim) {
     if (!m || !out_dim || (n && !item_ids)) return SBR_ERR_INVALID_ARGUMENT;
     std::lock_guard<std::mutex> lock(m->mu);
     SBRCHK(ensure_device(m));
-    const uint64_t T = m->hp.max_sequence_length;
-    static const uint32_t zero = 0;
-    if (n > T) { item_ids += n - T; n = T; } /* sequence_model.rs:188 */
-    if (n == 0) { item_ids = &zero; n = 1; } /* default index 0 (lstm.rs:262-264) */
-    for (uint64_t t = 0; t < n; ++t)
-        if (item_ids[t] >= m->hp.num_items) return SBR_ERR_INVALID_ARGUMENT;
-    std::vector<const uint32_t*> first{item_ids};
-    std::vector<int> nsteps{(int)n};
+    std::vector<const uint32_t*> first(1);
+    std::vector<int> nsteps(1);
+    state_window(item_ids, n, m->hp.max_sequence_length, &first[0], &nsteps[0]);
+    for (int t = 0; t < nsteps[0]; ++t)
+        if (first[0][t] >= m->hp.num_items) return SBR_ERR_INVALID_ARGUMENT;
     float* H = nullptr;
     std::vector<int> rep_row;
     SBRCHK(forward_histories(m, first, nsteps, &H, &rep_row, 0));
@@ -3471,52 +3526,27 @@ sbr_status sbr_mrr_score(sbr_model* m, const uint64_t* user_ptr, const uint32_t*
             if (rows > eval_rows_cap && c1 > c0) break;
         }
         const size_t nu = c1 - c0;
-        std::vector<const uint32_t*> first(nu);
-        std::vector<int> nsteps(nu);
-        std::vector<uint32_t> test_item(nu), test_in_hist(nu, 0), hist_items;
-        std::vector<uint64_t> hist_ptr(nu + 1, 0), raw_ptr(nu + 1, 0);
-        for (size_t i = 0; i < nu; ++i) raw_ptr[i + 1] = raw_ptr[i] + (user_ptr[users[c0 + i] + 1] - user_ptr[users[c0 + i]] - 1);
-        hist_items.resize(raw_ptr[nu]);
-        std::vector<uint32_t> uniq_count(nu, 0);
-        /* ALL history items of a user are masked (evaluation.rs:30-32): sorted + de-duplicated in place inside one buffer (a vector
-         * per user was a third of mrr_score's host time at 8 192 users), a few host threads over user ranges */
-        auto prepare = [&](size_t i0, size_t i1) {
-            for (size_t i = i0; i < i1; ++i) {
-                const uint64_t u = users[c0 + i];
-                const uint32_t* it = item_ids + user_ptr[u];
-                const uint64_t n = user_ptr[u + 1] - user_ptr[u];
-                const uint64_t nh = n - 1; /* train_items = all but last (evaluation.rs:24) */
-                test_item[i] = it[n - 1];
-                const uint64_t keep = std::min(nh, T); /* last T items feed the state (sequence_model.rs:188) */
-                first[i] = it + (nh - keep);
-                nsteps[i] = (int)keep;
-                uint32_t* h = hist_items.data() + raw_ptr[i];
-                std::memcpy(h, it, nh * 4);
-                std::sort(h, h + nh);
-                uint32_t* e = std::unique(h, h + nh);
-                test_in_hist[i] = std::binary_search(h, e, test_item[i]) ? 1u : 0u;
-                uniq_count[i] = (uint32_t)(e - h);
-            }
-        };
-        {
-            const size_t nthreads = nu >= 2048 ? 8 : 1;
-            if (nthreads == 1) prepare(0, nu);
-            else {
-                std::vector<std::thread> workers;
-                for (size_t k = 0; k < nthreads; ++k) workers.emplace_back(prepare, nu * k / nthreads, nu * (k + 1) / nthreads);
-                for (auto& w : workers) w.join();
-            }
+        std::vector<const uint32_t*> hist(nu);
+        std::vector<uint64_t> nh(nu);
+        std::vector<uint32_t> test_item(nu), test_in_hist(nu);
+        for (size_t i = 0; i < nu; ++i) { /* train_items = all but last (evaluation.rs:24) */
+            const uint64_t u = users[c0 + i];
+            hist[i] = item_ids + user_ptr[u];
+            nh[i] = user_ptr[u + 1] - user_ptr[u] - 1;
+            test_item[i] = hist[i][nh[i]];
         }
-        for (size_t i = 0; i < nu; ++i) { /* close the gaps the de-duplication left */
-            if (hist_ptr[i] != raw_ptr[i]) std::memmove(hist_items.data() + hist_ptr[i], hist_items.data() + raw_ptr[i], (size_t)uniq_count[i] * 4);
-            hist_ptr[i + 1] = hist_ptr[i] + uniq_count[i];
-        }
-        hist_items.resize(hist_ptr[nu]);
+        /* ALL history items of a user are masked (evaluation.rs:30-32) */
+        UserBatch b;
+        prepare_users(hist, nh, T, true, &b);
+        const std::vector<uint64_t>& hist_ptr = b.list_ptr;
+        const std::vector<uint32_t>& hist_items = b.list_items;
+        for (size_t i = 0; i < nu; ++i)
+            test_in_hist[i] = std::binary_search(hist_items.data() + hist_ptr[i], hist_items.data() + hist_ptr[i + 1], test_item[i]) ? 1u : 0u;
         float* H = nullptr;
         std::vector<int> rep_row;
         const size_t rank_bytes = 6 * DeviceArena::padded(nu * 4) + DeviceArena::padded(hist_items.size() * 4 + 4) + DeviceArena::padded(4) +
                                   DeviceArena::padded((nu + 1) * 8);
-        SBRCHK(forward_histories(m, first, nsteps, &H, &rep_row, rank_bytes));
+        SBRCHK(forward_histories(m, b.first, b.nsteps, &H, &rep_row, rank_bytes));
         DeviceArena& ar = m->eval_arena;
         int* d_rep = ar.take<int>(nu);
         uint32_t *d_test = ar.take<uint32_t>(nu), *d_tih = ar.take<uint32_t>(nu), *d_hist = ar.take<uint32_t>(hist_items.size()),
@@ -3553,7 +3583,7 @@ sbr_status sbr_mrr_score(sbr_model* m, const uint64_t* user_ptr, const uint32_t*
 }
 
 /* ---------------------------------------------------------------------------------------------
- * exact top-k recommendation (sbr_recommend.hip)
+ * exact top-k recommendation (sbr_catalogue.hip)
  * ------------------------------------------------------------------------------------------- */
 namespace {
 
@@ -3628,7 +3658,6 @@ sbr_status sbr_recommend(sbr_model* m, const uint64_t* user_ptr, const uint32_t*
     for (uint64_t i = user_ptr[0]; i < user_ptr[num_users]; ++i)
         if (item_ids[i] >= m->hp.num_items) return SBR_ERR_INVALID_ARGUMENT;
     const bool exclude = !(flags & SBR_RECOMMEND_INCLUDE_HISTORY);
-    static const uint32_t zero = 0;
     const size_t cap = recommend_users_cap(m, k);
     const size_t eval_rows_cap = (size_t)1 << 22; /* as mrr_score: the forward pass's scratch is (users x steps) rows */
     for (size_t c0 = 0, c1 = 0; c0 < num_users; c0 = c1) {
@@ -3638,51 +3667,19 @@ sbr_status sbr_recommend(sbr_model* m, const uint64_t* user_ptr, const uint32_t*
             if (rows > eval_rows_cap && c1 > c0) break;
         }
         const size_t nu = c1 - c0;
-        std::vector<const uint32_t*> first(nu);
-        std::vector<int> nsteps(nu);
-        std::vector<uint64_t> hist_ptr, raw_ptr(nu + 1, 0);
-        std::vector<uint32_t> hist_items, uniq_count(nu, 0);
-        if (exclude) {
-            for (size_t i = 0; i < nu; ++i) raw_ptr[i + 1] = raw_ptr[i] + (user_ptr[c0 + i + 1] - user_ptr[c0 + i]);
-            hist_items.resize(raw_ptr[nu]);
-            hist_ptr.assign(nu + 1, 0);
+        std::vector<const uint32_t*> hist(nu);
+        std::vector<uint64_t> n(nu);
+        for (size_t i = 0; i < nu; ++i) {
+            hist[i] = item_ids ? item_ids + user_ptr[c0 + i] : nullptr;
+            n[i] = user_ptr[c0 + i + 1] - user_ptr[c0 + i];
         }
-        /* the WHOLE history is masked (evaluation.rs:30-32), the last T items feed the state (sequence_model.rs:188), an empty
-         * history is step 0 with item 0 (lstm.rs:262-264); as mrr_score, sorted + de-duplicated in place, a few host threads */
-        auto prepare = [&](size_t i0, size_t i1) {
-            for (size_t i = i0; i < i1; ++i) {
-                const uint32_t* it = item_ids ? item_ids + user_ptr[c0 + i] : nullptr;
-                const uint64_t n = user_ptr[c0 + i + 1] - user_ptr[c0 + i];
-                const uint64_t keep = std::min(n, T);
-                first[i] = n ? it + (n - keep) : &zero;
-                nsteps[i] = n ? (int)keep : 1;
-                if (!exclude || n == 0) continue;
-                uint32_t* h = hist_items.data() + raw_ptr[i];
-                std::memcpy(h, it, n * 4);
-                std::sort(h, h + n);
-                uniq_count[i] = (uint32_t)(std::unique(h, h + n) - h);
-            }
-        };
-        {
-            const size_t nthreads = nu >= 2048 ? 8 : 1;
-            if (nthreads == 1) prepare(0, nu);
-            else {
-                std::vector<std::thread> workers;
-                for (size_t t = 0; t < nthreads; ++t) workers.emplace_back(prepare, nu * t / nthreads, nu * (t + 1) / nthreads);
-                for (auto& w : workers) w.join();
-            }
-        }
-        if (exclude) {
-            for (size_t i = 0; i < nu; ++i) { /* close the gaps the de-duplication left */
-                if (hist_ptr[i] != raw_ptr[i]) std::memmove(hist_items.data() + hist_ptr[i], hist_items.data() + raw_ptr[i], (size_t)uniq_count[i] * 4);
-                hist_ptr[i + 1] = hist_ptr[i] + uniq_count[i];
-            }
-            hist_items.resize(hist_ptr[nu]);
-        }
+        /* the WHOLE history is masked (evaluation.rs:30-32) */
+        UserBatch b;
+        prepare_users(hist, n, T, exclude, &b);
         float* H = nullptr;
         std::vector<int> rep_row;
-        SBRCHK(forward_histories(m, first, nsteps, &H, &rep_row, recommend_bytes(m, nu, hist_items.size(), k)));
-        SBRCHK(recommend_launch(m, H, rep_row, nu, hist_ptr, hist_items, k, out_items + c0 * k, out_scores ? out_scores + c0 * k : nullptr));
+        SBRCHK(forward_histories(m, b.first, b.nsteps, &H, &rep_row, recommend_bytes(m, nu, b.list_items.size(), k)));
+        SBRCHK(recommend_launch(m, H, rep_row, nu, b.list_ptr, b.list_items, k, out_items + c0 * k, out_scores ? out_scores + c0 * k : nullptr));
     }
     return SBR_OK;
 }
@@ -3704,30 +3701,26 @@ sbr_status sbr_recommend_reps(sbr_model* m, const float* reps, uint64_t num_user
     const size_t cap = recommend_users_cap(m, k);
     for (size_t c0 = 0; c0 < num_users; c0 += cap) {
         const size_t nu = std::min<size_t>(cap, num_users - c0);
-        std::vector<uint64_t> eptr;
-        std::vector<uint32_t> eitems;
+        UserBatch excl; /* the caller's exclusion lists, sorted and de-duplicated (their state windows go unused) */
         if (excl_ptr) {
-            eptr.assign(nu + 1, 0);
+            std::vector<const uint32_t*> lists(nu);
+            std::vector<uint64_t> n(nu);
             for (size_t i = 0; i < nu; ++i) {
-                const uint32_t* b = excl_items + excl_ptr[c0 + i];
-                const uint32_t* e = excl_items + excl_ptr[c0 + i + 1];
-                const size_t at = eitems.size();
-                eitems.insert(eitems.end(), b, e);
-                std::sort(eitems.begin() + at, eitems.end());
-                eitems.erase(std::unique(eitems.begin() + at, eitems.end()), eitems.end());
-                eptr[i + 1] = eitems.size();
+                lists[i] = excl_items + excl_ptr[c0 + i];
+                n[i] = excl_ptr[c0 + i + 1] - excl_ptr[c0 + i];
             }
+            prepare_users(lists, n, m->hp.max_sequence_length, true, &excl);
         }
         DeviceArena& ar = m->eval_arena;
         HIPCHK(hipStreamSynchronize(m->stream)); /* nothing of an earlier call may still read the arena */
-        SBRCHK(ar.reserve(DeviceArena::padded(nu * d * 4) + recommend_bytes(m, nu, eitems.size(), k)));
+        SBRCHK(ar.reserve(DeviceArena::padded(nu * d * 4) + recommend_bytes(m, nu, excl.list_items.size(), k)));
         float* H = ar.take<float>(nu * d);
         /* padded to the storage width: the columns past embedding_dim are zero, as in the model's own states */
         HIPCHK(hipMemsetAsync(H, 0, nu * d * 4, m->stream));
         HIPCHK(hipMemcpy2DAsync(H, d * 4, reps + c0 * dl, dl * 4, dl * 4, nu, hipMemcpyHostToDevice, m->stream));
         std::vector<int> rep_row(nu);
         for (size_t i = 0; i < nu; ++i) rep_row[i] = (int)i;
-        SBRCHK(recommend_launch(m, H, rep_row, nu, eptr, eitems, k, out_items + c0 * k, out_scores ? out_scores + c0 * k : nullptr));
+        SBRCHK(recommend_launch(m, H, rep_row, nu, excl.list_ptr, excl.list_items, k, out_items + c0 * k, out_scores ? out_scores + c0 * k : nullptr));
     }
     return SBR_OK;
 }

@@ -1,5 +1,6 @@
 /* sbr_kernels.h — launch interface between the host engine (sbr_engine.hip) and the gfx950
- * kernels (sbr_kernels.hip).  Internal to libsbr_hip.so; the public ABI is include/sbr_hip.h. */
+ * kernels (sbr_kernels.hip and its neighbours; the prediction side is sbr_catalogue.hip).  Internal to libsbr_hip.so; the public
+ * ABI is include/sbr_hip.h. */
 #ifndef SBR_KERNELS_H
 #define SBR_KERNELS_H
 
@@ -265,12 +266,12 @@ void launch_merge_sort(const PeerLists& pl, int ndev, uint32_t total, uint64_t* 
                        size_t sort_temp_bytes, hipStream_t s);
 void launch_accumulate_loss(const uint8_t* all_blocks, uint64_t block_bytes, int ndev, double* loss_acc,
                             unsigned long long* ex_acc, hipStream_t s);
-/* prediction side */
+/* prediction side (sbr_catalogue.hip) */
 void launch_predict(const ModelView& m, const float* user, const uint32_t* items, uint64_t n, float* out, hipStream_t s);
 void launch_rank(const ModelView& m, const float* reps, const int* rep_row, uint32_t num_users, const uint32_t* test_item,
                  const uint32_t* test_in_hist, const uint64_t* hist_ptr, const uint32_t* hist_items, float* ts_scratch,
                  uint32_t* ranks, uint32_t* nonfinite_flag, hipStream_t s);
-/* exact top-k of the catalogue per user (sbr_recommend.hip): topk_gemm_kernel keeps per (user, item range) a sorted list of the
+/* exact top-k of the catalogue per user (sbr_catalogue.hip): topk_gemm_kernel keeps per (user, item range) a sorted list of the
  * k best (score desc, id asc) in `lists` [num_users][groups][k] with its length in `lens` [num_users][groups]; topk_merge_kernel
  * merges a user's lists in LDS into out_items / out_scores [num_users][k] (padding: 0xFFFFFFFF / -inf).  excl_ptr / excl_items:
  * sorted, de-duplicated per-user exclusion lists (NULL: none).  groups * k <= TK_MERGE_MAX. */

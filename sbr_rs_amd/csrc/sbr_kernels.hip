@@ -1,4 +1,5 @@
-// sbr_kernels.hip — gfx950 (CDNA4, MI355X) kernels of the sequence-recommender hot path.
+// sbr_kernels.hip — gfx950 (CDNA4, MI355X) training and self-test kernels of the sequence-recommender
+// hot path (the prediction side, predict / mrr_score / recommend, is sbr_catalogue.hip).
 //
 // Every kernel reproduces, bit for bit, the association orders fixed in sbr_numerics.h and
 // restated sequentially by the CPU oracle (oracle/sbr_oracle.c):
@@ -11,8 +12,7 @@
 //                             one Adagrad read-modify-write per touched row
 // Reference call sites replaced: the wyrm graph built by Parameters::build
 // (/root/reference/src/models/lstm.rs:258-337, ewma.rs:266-352), driven by fit_sequence_model
-// (/root/reference/src/models/sequence_model.rs:111-169), predict_single (lstm.rs:338-350) and
-// the ranking loop of mrr_score (/root/reference/src/evaluation.rs:27-43).
+// (/root/reference/src/models/sequence_model.rs:111-169).
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off (see sbr_rs_amd/build.py).
 
@@ -30,7 +30,6 @@ namespace sbr {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned v4u32 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 #define EWMA_CHUNK_SEQS 256
 #ifndef SBR_FWD_RT
@@ -3024,204 +3023,6 @@ __global__ void accumulate_loss_kernel(const uint8_t* all_blocks, uint64_t block
 }
 
 // ------------------------------------------------------------------------------------------------
-// Prediction side: bias + chain-order dot (≙ an f32 MFMA accumulation over k)
-// ------------------------------------------------------------------------------------------------
-template <int D>
-__device__ __forceinline__ float chain_dot(const float* __restrict__ h, const float* __restrict__ e) {
-    float acc = 0.0f;
-#pragma unroll
-    for (int k4 = 0; k4 < D; k4 += 4) {
-        const float4 v = ld4(e + k4);
-        acc = sbr_fma(h[k4 + 0], v.x, acc);
-        acc = sbr_fma(h[k4 + 1], v.y, acc);
-        acc = sbr_fma(h[k4 + 2], v.z, acc);
-        acc = sbr_fma(h[k4 + 3], v.w, acc);
-    }
-    return acc;
-}
-
-template <int D>
-__global__ void predict_kernel(ModelView m, const float* user, const uint32_t* items, uint64_t n, float* out) {
-    __shared__ float hs[D];
-    for (int k = threadIdx.x; k < D; k += blockDim.x) hs[k] = user[k];
-    __syncthreads();
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t it = items[i];
-    out[i] = m.b[it] + chain_dot<D>(hs, m.E + (size_t)it * D);
-}
-
-// ------------------------------------------------------------------------------------------------
-// K7: full-catalogue scoring + rank (mrr_score, evaluation.rs:27-43) as an f32 MFMA GEMM with a
-// rank-count epilogue; the U x I score matrix is never materialised.
-//   rank_test_score_kernel : ts[u] = MIN if the test item is in the history, else bias + chain dot
-//   rank_gemm_kernel       : S[u][i] = b[i] + sum_k h[u][k] E[i][k] on v_mfma_f32_32x32x2_f32
-//                            (k ascending from 0 = the oracle's chain order); counts S >= ts[u]
-//   rank_history_kernel    : corrects the count for the (unique) history items, which the reference
-//                            masks to f32::MIN (evaluation.rs:30-32)
-// A workgroup owns 128 users (4 waves x 32) and a contiguous range of items: the users' states
-// stay in registers as MFMA A fragments, 32-item tiles of E stream through LDS.
-// ------------------------------------------------------------------------------------------------
-template <int D>
-__global__ void rank_test_score_kernel(ModelView m, const float* reps, const int* rep_row, uint32_t num_users,
-                                       const uint32_t* test_item, const uint32_t* test_in_hist, float* ts, uint32_t* ranks) {
-    const uint32_t u = blockIdx.x * blockDim.x + threadIdx.x;
-    if (u >= num_users) return;
-    const uint32_t ti = test_item[u];
-    ts[u] = test_in_hist[u] ? SBR_F32_MIN : m.b[ti] + chain_dot<D>(reps + (size_t)rep_row[u] * D, m.E + (size_t)ti * D);
-    ranks[u] = 0;
-}
-
-template <int D, int UW>
-__global__ __launch_bounds__(256, UW == 1 ? (D <= 128 ? 4 : 2) : (D * UW <= 64 ? 4 : (D * UW <= 128 ? 3 : 2))) void rank_gemm_kernel(ModelView m, const float* reps, const int* rep_row, uint32_t num_users,
-                                                                            const float* ts, uint32_t items_per_group, uint32_t* ranks,
-                                                                            uint32_t* nonfinite_flag) {
-    // UW = 32-user tiles per wave (a workgroup owns 128 * UW users): every staged 32-item tile of E feeds UW x 64 MFMAs per
-    // wave between two barriers — UW = 2 halves the barriers, the LDS fills and the L2 traffic per flop at half the waves
-    constexpr int LDE = D + 1;
-    constexpr int KS = D / 2;  // MFMA k-steps
-    constexpr int WGU = 128 * UW;  // users per workgroup
-    __shared__ float Es[2][32 * LDE];
-    __shared__ float Bs[2][32];
-    // thresholds of the workgroup's users in the order the accumulator registers want them: Ts[wave][tile][hh][q] = threshold
-    // of user (wave * UW + tile) * 32 + (q & 3) + 8 (q >> 2) + 4 hh — read back per item tile as 16-byte broadcasts instead of
-    // living in 16 registers per user tile
-    __shared__ float Ts[4][UW][2][16];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = tid >> 6;
-    const int l31 = lane & 31;
-    const int hh = lane >> 5;
-    const uint32_t u0 = blockIdx.x * WGU + wave * 32 * UW;
-    // A fragments of this wave's users: a[t][s] = h[u0 + 32 t + l31][2 s + hh], held for the whole item range
-    float a[UW][KS];
-#pragma unroll
-    for (int t = 0; t < UW; ++t) {
-        const uint32_t u = u0 + 32 * t + l31;
-        const float* h = reps + (size_t)rep_row[u < num_users ? u : num_users - 1] * D;
-#pragma unroll
-        for (int s = 0; s < KS; ++s) a[t][s] = u < num_users ? h[2 * s + hh] : 0.0f;
-    }
-    for (int e = tid; e < 4 * UW * 32; e += 256) {
-        const int w2 = e / (UW * 32), t2 = (e / 32) % UW, h2 = (e >> 4) & 1, q = e & 15;
-        const uint32_t u = blockIdx.x * WGU + (w2 * UW + t2) * 32 + (q & 3) + 8 * (q >> 2) + 4 * h2;
-        Ts[w2][t2][h2][q] = u < num_users ? ts[u] : 0.0f;
-    }
-    // per-lane counters of "score >= threshold", two 16-bit counters per register (a lane adds at most one per tile and
-    // register: the launcher keeps an item range below 65 536 tiles)
-    uint32_t cnt2[UW][8];
-#pragma unroll
-    for (int t = 0; t < UW; ++t)
-#pragma unroll
-        for (int q = 0; q < 8; ++q) cnt2[t][q] = 0;
-    bool bad = false;
-    const uint32_t i_begin = blockIdx.y * items_per_group;
-    uint32_t i_end = i_begin + items_per_group;
-    if (i_end > m.num_items) i_end = m.num_items;
-    const int ntiles = i_begin < i_end ? (int)((i_end - i_begin + 31) / 32) : 0;
-    // staging map: thread -> (item row tid/8, float4 columns (tid%8) + 8 j)
-    constexpr int NV = 32 * (D / 4);
-    constexpr int ITER = (NV + 255) / 256;
-    float4 ev[ITER];
-    float bv = 0.0f;
-    auto fetch = [&](int tile) {
-        const uint32_t ib = i_begin + (uint32_t)tile * 32;
-#pragma unroll
-        for (int it = 0; it < ITER; ++it) {
-            const int idx = tid + it * 256;
-            const int r = idx / (D / 4);
-            const int c4 = (idx % (D / 4)) * 4;
-            ev[it] = (idx < NV && ib + r < i_end) ? ld4(m.E + (size_t)(ib + r) * D + c4) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-        if (tid < 32) bv = ib + tid < i_end ? m.b[ib + tid] : 0.0f;
-    };
-    auto stage = [&](int buf) {
-#pragma unroll
-        for (int it = 0; it < ITER; ++it) {
-            const int idx = tid + it * 256;
-            if (idx < NV) {
-                const int r = idx / (D / 4);
-                const int c4 = (idx % (D / 4)) * 4;
-                float* dst = &Es[buf][r * LDE + c4];
-                dst[0] = ev[it].x; dst[1] = ev[it].y; dst[2] = ev[it].z; dst[3] = ev[it].w;
-            }
-        }
-        if (tid < 32) Bs[buf][tid] = bv;
-    };
-    if (ntiles > 0) {
-        fetch(0);
-        stage(0);
-    }
-    __syncthreads();
-    for (int tile = 0; tile < ntiles; ++tile) {
-        const int buf = tile & 1;
-        if (tile + 1 < ntiles) fetch(tile + 1);
-        f32x16 acc[UW];
-#pragma unroll
-        for (int t = 0; t < UW; ++t)
-#pragma unroll
-            for (int q = 0; q < 16; ++q) acc[t][q] = 0.0f;
-        const float* eb = &Es[buf][l31 * LDE + hh];
-#pragma unroll
-        for (int s = 0; s < KS; ++s) {
-            const float bvs = eb[2 * s];
-#pragma unroll
-            for (int t = 0; t < UW; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t][s], bvs, acc[t], 0, 0, 0);
-        }
-        const float bias = Bs[buf][l31];
-        const bool item_ok = i_begin + (uint32_t)tile * 32 + l31 < i_end;
-#pragma unroll
-        for (int t = 0; t < UW; ++t)
-#pragma unroll
-            for (int q4 = 0; q4 < 4; ++q4) {
-                const float4 t4 = ld4(&Ts[wave][t][hh][4 * q4]);
-                const float tq[4] = {t4.x, t4.y, t4.z, t4.w};
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int q = 4 * q4 + j;
-                    const float sc = bias + acc[t][q];
-                    if (item_ok) {
-                        if (!(sc - sc == 0.0f)) bad = true;
-                        if (sc >= tq[j]) cnt2[t][q >> 1] += (q & 1) ? 0x10000u : 1u;
-                    }
-                }
-            }
-        if (tile + 1 < ntiles) stage(buf ^ 1);
-        __syncthreads();
-    }
-    // per-user totals: sum over the 32 item lanes of each half-wave
-#pragma unroll
-    for (int t = 0; t < UW; ++t)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            int c = (int)((cnt2[t][q >> 1] >> ((q & 1) * 16)) & 0xFFFFu);
-#pragma unroll
-            for (int off = 16; off >= 1; off >>= 1) c += __shfl_xor(c, off, 64);
-            const uint32_t u = u0 + 32 * t + (q & 3) + 8 * (q >> 2) + 4 * hh;
-            if (l31 == 0 && u < num_users && c) atomicAdd(&ranks[u], (uint32_t)c);
-        }
-    if (__any(bad) && lane == 0) atomicOr(nonfinite_flag, 1u);
-}
-
-template <int D>
-__global__ __launch_bounds__(64) void rank_history_kernel(ModelView m, const float* reps, const int* rep_row, const float* ts,
-                                                          const uint64_t* hist_ptr, const uint32_t* hist_items, uint32_t* ranks) {
-    const int u = blockIdx.x;
-    const float* h = reps + (size_t)rep_row[u] * D;
-    const float t = ts[u];
-    int cnt = 0;
-    for (uint64_t e = hist_ptr[u] + threadIdx.x; e < hist_ptr[u + 1]; e += 64) {
-        const uint32_t i = hist_items[e];
-        const float s = m.b[i] + chain_dot<D>(h, m.E + (size_t)i * D);
-        if (s >= t) --cnt;               /* it was counted by the GEMM pass ...          */
-        if (SBR_F32_MIN >= t) ++cnt;     /* ... but the masked value only counts against MIN */
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
-    if (threadIdx.x == 0 && cnt) atomicAdd(&ranks[u], (uint32_t)cnt); /* two's complement: adds a negative delta */
-}
-
-// ------------------------------------------------------------------------------------------------
 // numerics self-tests
 // ------------------------------------------------------------------------------------------------
 __global__ void selftest_math_kernel(const float* x, float* e, float* s, float* t, uint64_t n) {
@@ -3275,16 +3076,6 @@ __global__ void selftest_mfma32_chain_kernel(const float* a, const float* b, int
 // ================================================================================================
 // launchers
 // ================================================================================================
-#define DISPATCH_D(d, ...)                                         \
-    switch (d) {                                                   \
-        case 16: { constexpr int DD = 16; __VA_ARGS__; } break;    \
-        case 32: { constexpr int DD = 32; __VA_ARGS__; } break;    \
-        case 64: { constexpr int DD = 64; __VA_ARGS__; } break;    \
-        case 128: { constexpr int DD = 128; __VA_ARGS__; } break;  \
-        case 256: { constexpr int DD = 256; __VA_ARGS__; } break;  \
-        default: break;                                            \
-    }
-
 /* Resident grids of the memory-bound grid-stride kernels: SBR_RESIDENT_WG_PER_CU workgroups of 256 threads per CU.  Eight
  * would fill every wave slot of the chip; seven leave one wave per SIMD for whatever runs beside them on another stream
  * (the key sort's short kernels could otherwise only advance at the main stream's kernel boundaries). */
@@ -3774,37 +3565,6 @@ void launch_owner_list_apply(const ModelView& m, const PeerLists& pl_in, const P
         if (ndev <= 4) hipLaunchKernelGGL((owner_list_apply_kernel<DD, 4>), dim3(grid), dim3(256), 0, s, m, pl, mkeys_sorted);
         else if (ndev <= 8) hipLaunchKernelGGL((owner_list_apply_kernel<DD, 8>), dim3(grid), dim3(256), 0, s, m, pl, mkeys_sorted);
         else hipLaunchKernelGGL((owner_list_apply_kernel<DD, 16>), dim3(grid), dim3(256), 0, s, m, pl, mkeys_sorted);
-    });
-}
-
-void launch_predict(const ModelView& m, const float* user, const uint32_t* items, uint64_t n, float* out, hipStream_t s) {
-    if (n == 0) return;
-    DISPATCH_D(m.d, { hipLaunchKernelGGL((predict_kernel<DD>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, m, user, items, n, out); });
-}
-
-void launch_rank(const ModelView& m, const float* reps, const int* rep_row, uint32_t num_users, const uint32_t* test_item,
-                 const uint32_t* test_in_hist, const uint64_t* hist_ptr, const uint32_t* hist_items, float* ts_scratch,
-                 uint32_t* ranks, uint32_t* nonfinite_flag, hipStream_t s) {
-    if (num_users == 0) return;
-    // 32 users per wave (128 per workgroup, four waves per SIMD).  (A 64-users-per-wave form — half the barriers and LDS fills per
-    // flop at half the waves — measured 5 % slower at 8 192 users x 1e6 items, d = 128: 100 against 105 TFLOP/s; removed.)
-    const uint32_t wgu = 128u;
-    const uint32_t utiles = (num_users + wgu - 1) / wgu;
-    // item groups: at least one 32-item tile each, and MANY more workgroups than the chip holds at once (a launch of
-    // 1 024 workgroups on 768 resident slots ran one full round and a third of a second one)
-    constexpr uint32_t target_wgs = 768u * 6u;
-    uint32_t groups = (target_wgs + utiles - 1) / utiles;
-    const uint32_t max_groups = (m.num_items + 31) / 32;
-    if (groups > max_groups) groups = max_groups;
-    if (groups < 1) groups = 1;
-    uint32_t per = (m.num_items + groups - 1) / groups;
-    per = ((per + 31) / 32) * 32;
-    if (per > 65535u * 32u) per = 65535u * 32u; /* the kernel's per-lane counters are 16 bits wide: fewer than 65 536 tiles per range */
-    groups = (m.num_items + per - 1) / per;
-    DISPATCH_D(m.d, {
-        hipLaunchKernelGGL((rank_test_score_kernel<DD>), dim3((num_users + 255) / 256), dim3(256), 0, s, m, reps, rep_row, num_users, test_item, test_in_hist, ts_scratch, ranks);
-        hipLaunchKernelGGL((rank_gemm_kernel<DD, 1>), dim3(utiles, groups), dim3(256), 0, s, m, reps, rep_row, num_users, ts_scratch, per, ranks, nonfinite_flag);
-        hipLaunchKernelGGL((rank_history_kernel<DD>), dim3(num_users), dim3(64), 0, s, m, reps, rep_row, ts_scratch, hist_ptr, hist_items, ranks);
     });
 }
 

@@ -1,4 +1,4 @@
-"""GPU: sbr_recommend / sbr_recommend_reps (exact top-k of the whole catalogue, sbr_recommend.hip) against the oracle:
+"""GPU: sbr_recommend / sbr_recommend_reps (exact top-k of the whole catalogue, sbr_catalogue.hip) against the oracle:
 orc_user_representation + orc_predict over every item, then recommend_expect.topk_expectation.  Items and score bits must be
 equal."""
 import numpy as np
