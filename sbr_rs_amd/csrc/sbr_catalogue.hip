@@ -20,6 +20,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cstdlib>
+
 #include "sbr_device.h"
 #include "sbr_kernels.h"
 
@@ -112,11 +114,22 @@ __device__ __forceinline__ f32x16 tile_dots(const float (&a)[D / 2], const float
     return acc;
 }
 
-/* Item ranges of a scan over utiles 128-user tiles: about target_wgs workgroups in all, whole 32-item tiles per range, at most
- * max_groups ranges of at most max_per items.  Returns the number of ranges; *items_per_group their length. */
-uint32_t split_items(uint32_t num_items, uint32_t utiles, uint32_t target_wgs, uint32_t max_groups, uint32_t max_per,
-                     uint32_t* items_per_group) {
-    uint32_t groups = (target_wgs + utiles - 1) / utiles;
+/* The wanted number of item ranges of a scan: by_default unless SBR_CATALOGUE_GROUPS=n (n >= 1) is set, a TEST HOOK read per call
+ * (the tests force one long range or a few, whatever the split heuristics of the day prefer: tests/test_catalogue_gpu.py).  The
+ * hard limits of split_items apply after it. */
+uint32_t wanted_groups(uint32_t by_default) {
+    const char* e = std::getenv("SBR_CATALOGUE_GROUPS");
+    if (e && *e) {
+        const long long n = std::atoll(e);
+        if (n >= 1) return n < (long long)UINT32_MAX ? (uint32_t)n : UINT32_MAX;
+    }
+    return by_default;
+}
+
+/* Item ranges of a scan: `wanted` of them, but whole 32-item tiles per range, at most max_groups ranges of at most max_per items.
+ * Returns the number of ranges; *items_per_group their length. */
+uint32_t split_items(uint32_t num_items, uint32_t wanted, uint32_t max_groups, uint32_t max_per, uint32_t* items_per_group) {
+    uint32_t groups = wanted;
     if (groups > (num_items + 31) / 32) groups = (num_items + 31) / 32;
     if (groups > max_groups) groups = max_groups;
     if (groups < 1) groups = 1;
@@ -130,7 +143,8 @@ uint32_t split_items(uint32_t num_items, uint32_t utiles, uint32_t target_wgs, u
 constexpr int TK_STAGE = 32;                 /* staged candidates per user between merges */
 constexpr uint32_t TK_NONE = 0xFFFFFFFFu;    /* padding id; its score is -inf */
 
-/* (score desc, id asc); -0.0 == +0.0 */
+/* (score desc, id asc).  A score of -0.0 is rare but possible (a -0.0 bias plus a chain that ends at -0.0: negative products
+ * that underflow); it compares equal to +0.0, so the id orders the two, and its bits are reported as computed. */
 __device__ __forceinline__ bool tk_better(float as, uint32_t ai, float bs, uint32_t bi) { return as > bs || (as == bs && ai < bi); }
 
 }  // namespace
@@ -505,7 +519,7 @@ void launch_rank(const ModelView& m, const float* reps, const int* rep_row, uint
     // item ranges: MANY more workgroups than the chip holds at once (a launch of 1 024 workgroups on 768 resident slots ran one
     // full round and a third of a second one); the kernel's per-lane counters are 16 bits wide: fewer than 65 536 tiles per range
     uint32_t per = 0;
-    const uint32_t groups = split_items(m.num_items, utiles, 768u * 6u, UINT32_MAX, 65535u * 32u, &per);
+    const uint32_t groups = split_items(m.num_items, wanted_groups((768u * 6u + utiles - 1) / utiles), UINT32_MAX, 65535u * 32u, &per);
     DISPATCH_D(m.d, {
         hipLaunchKernelGGL((rank_test_score_kernel<DD>), dim3((num_users + 255) / 256), dim3(256), 0, s, m, reps, rep_row, num_users, test_item, test_in_hist, ts_scratch, ranks);
         hipLaunchKernelGGL((rank_gemm_kernel<DD>), dim3(utiles, groups), dim3(256), 0, s, m, reps, rep_row, num_users, ts_scratch, per, ranks, nonfinite_flag);
@@ -517,7 +531,8 @@ uint32_t recommend_groups(uint32_t num_users, uint32_t num_items, uint32_t k, ui
     // Two rounds of the chip's resident slots (two workgroups per CU at d <= 128), not launch_rank's six: a range's first k items
     // are all candidates and the rest about k ln(range / k), so fewer, longer ranges merge less (8 192 users x 1e6 items, d = 128,
     // k = 100: 113 ms of kernels at 4 608 workgroups); at most TK_MERGE_MAX / k lists per user for the merge
-    return split_items(num_items, (num_users + 127) / 128, 256u * 2u * 2u, TK_MERGE_MAX / k, UINT32_MAX, items_per_group);
+    const uint32_t utiles = (num_users + 127) / 128;
+    return split_items(num_items, wanted_groups((256u * 2u * 2u + utiles - 1) / utiles), TK_MERGE_MAX / k, UINT32_MAX, items_per_group);
 }
 
 void launch_recommend(const ModelView& m, const float* reps, const int* rep_row, uint32_t num_users, const uint64_t* excl_ptr,

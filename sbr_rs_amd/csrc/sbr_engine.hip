@@ -3587,7 +3587,10 @@ sbr_status sbr_mrr_score(sbr_model* m, const uint64_t* user_ptr, const uint32_t*
  * ------------------------------------------------------------------------------------------- */
 namespace {
 
-/* users per top-k launch: as mrr_score's EVAL_B, and few enough that the per-(user, item range) lists stay under 256 MB */
+/* users per top-k launch: as mrr_score's EVAL_B, and few enough that the per-(user, item range) lists stay within 256 MB.  With
+ * ranges * k <= TK_MERGE_MAX the lists of 8 192 users are at most 512 MB, so the loop halves at most once: 8 192 users while
+ * ranges * k <= 4 096 (every k <= 256: at most 16 ranges are wanted for 64 user tiles), 4 096 users above that (possible from
+ * k = 257 on; k = 1 024 from 5 ranges on) or where SBR_CATALOGUE_GROUPS forces more ranges. */
 size_t recommend_users_cap(const sbr_model* m, uint32_t k) {
     size_t cap = 8192;
     for (;;) {

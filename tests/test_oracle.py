@@ -443,6 +443,16 @@ def test_mrr_masks_all_history_and_counts_ties(oracle_lib):
     assert mrr == np.float32((np.float32(1) / 2 + np.float32(1) / 4 + np.float32(1) / 6) / np.float32(3))
 
 
+def test_mrr_without_a_ranked_user_is_nan(oracle_lib):
+    """evaluation.rs:18-47: users with fewer than two interactions are filtered out, and the mean of the remaining reciprocal
+    ranks is `sum / len as f32`; with none left that is 0.0 / 0.0 = NaN, returned as Ok.  The oracle does the same: NaN, no
+    ranks, no error (the engine is held to it in tests/test_catalogue_gpu.py::test_mrr_no_ranked_user)."""
+    m = OracleModel(hparams(6, 4, 16, int(ModelKind.EWMA), LOSS_HINGE))
+    for ptr, items in (([0], []), ([0, 1], [3]), ([0, 1, 1, 2], [3, 5])):
+        mrr, ranks = m.mrr_score(np.array(ptr, dtype=np.uint64), np.array(items, dtype=np.uint32))
+        assert np.isnan(mrr) and ranks.size == 0
+
+
 def test_adam_and_adagrad_element_updates_match_float64_formulas(oracle_lib):
     """wyrm's optimisers as recalled: Adagrad eps 1e-10; Adam beta 0.9/0.999, eps 1e-8,
     L2 folded into the gradient, bias correction by step count."""

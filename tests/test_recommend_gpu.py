@@ -176,7 +176,9 @@ def test_recommend_errors():
 
 def test_recommend_headline_shape():
     """BASELINE configs[2]'s table (1e6 items, d = 128), 8 192 users, k = 100, seeded parameters: 32 sampled users against the
-    oracle; two calls bitwise identical over all users."""
+    oracle; two calls bitwise identical over all users; the whole first user tile (users 0..127) and the last 128 users against
+    the top k of the engine's own predict over all items (predict is held to the oracle in test_parity_gpu.py and by the 32
+    users here)."""
     items, d, T, k, U = 1_000_000, 128, 64, 100, 8192
     hp = hparams(items, T, d, int(ModelKind.LSTM_NORMAL), LOSS_HINGE, B=32)
     g = Model(hp)
@@ -188,6 +190,14 @@ def test_recommend_headline_shape():
     users = np.unique(np.concatenate([[0, 1, 127, 128, 4095, 4096, U - 1], np.random.RandomState(3).choice(U, 25, replace=False)]))
     want = oracle_recommend(o, items, ptr, it, k, users=users)
     _same((a[0][users], a[1][users]), want)
+    ptr64 = np.asarray(ptr, dtype=np.int64)
+    all_items = np.arange(items, dtype=np.uint32)
+    tiles = np.concatenate([np.arange(128), np.arange(U - 128, U)])
+    rows = []
+    for u in tiles:
+        h = it[ptr64[u]: ptr64[u + 1]]
+        rows.append(topk_expectation(g.predict(g.user_representation(h), all_items), np.unique(h), k))
+    _same((a[0][tiles], a[1][tiles]), (np.array([r[0] for r in rows]), np.array([r[1] for r in rows])))
 
 
 def test_recommend_partitioned_replica():
