@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import f64_model
 from helpers import LOSS_BPR, LOSS_HINGE, LOSS_WARP, hparams, synthetic_interactions
 from oracle.oracle import OracleModel
 from sbr_rs_amd._abi import Debug, ModelKind, Param
@@ -60,8 +61,21 @@ def _torch_reference(model_kind, loss_kind, d, params, seqs, negs):
 @pytest.mark.parametrize("model_kind", [ModelKind.LSTM_NORMAL, ModelKind.LSTM_COUPLED, ModelKind.EWMA])
 @pytest.mark.parametrize("loss_kind", [LOSS_HINGE, LOSS_BPR, LOSS_WARP])
 def test_oracle_gradients_match_autograd(oracle_lib, model_kind, loss_kind):
-    I, d, T, B = 60, 16, 9, 5
-    ptr, items = synthetic_interactions(12, I, T, seed=3)
+    _check_against_autograd(model_kind, loss_kind, 60, 16, 9, synthetic_interactions(12, 60, 9, seed=3))
+
+
+@pytest.mark.parametrize("model_kind,loss_kind,I,d,T,seed", [
+    (ModelKind.LSTM_NORMAL, LOSS_HINGE, 300, 128, 12, 6),
+    (ModelKind.EWMA, LOSS_WARP, 150, 64, 14, 3),
+])
+def test_oracle_gradients_match_autograd_larger(oracle_lib, model_kind, loss_kind, I, d, T, seed):
+    """Shapes at which guessing the packed layout from index coincidences failed (60 Zipf users, hundreds of rows)."""
+    _check_against_autograd(model_kind, loss_kind, I, d, T, synthetic_interactions(60, I, T + 5, seed=seed, zipf=True))
+
+
+def _check_against_autograd(model_kind, loss_kind, I, d, T, data):
+    ptr, items = data
+    B = len(f64_model.subsequences(ptr, items, T))   # the whole epoch is one minibatch: its length multiset is the input's
     hp = hparams(I, T, d, int(model_kind), loss_kind, epochs=1, B=B, l2=0.0)
     m = OracleModel(hp)
     rs = np.random.RandomState(0)
@@ -84,7 +98,7 @@ def test_oracle_gradients_match_autograd(oracle_lib, model_kind, loss_kind):
         params["W"], params["bW"] = W, bW
     plan = m.fit_begin(ptr, items)
     nmb = plan.epoch_prepare()
-    assert nmb >= 1
+    assert nmb == 1
     R = plan.minibatch_rows(0)
     plan.step_local(0)
     in_idx = plan.debug_fetch(Debug.IN_IDX, R)
@@ -95,16 +109,14 @@ def test_oracle_gradients_match_autograd(oracle_lib, model_kind, loss_kind):
     dX = plan.debug_fetch(Debug.DINPUT, R)
     dense = plan.debug_fetch(Debug.DENSE_GRAD, R)
 
-    # Rebuild the sequences from the packed time-major rows: row(t, b) = off[t] + b, sequences in
-    # length-descending order; step-t rows are a prefix of the step-(t-1) sequences.
+    # The packed time-major rows: row(t, b) = off[t] + b, sequences in length-descending order; step-t rows are a prefix
+    # of the step-(t-1) sequences.  off follows from the input's chunk lengths alone; the recovered columns must chain and
+    # be exactly the input's subsequences.
     seq_rows = []
-    seqs_sorted = _minibatch_sequences(ptr, items, T, hp, m, plan)
-    nb = len(seqs_sorted)
-    maxlen = max(len(s) for s in seqs_sorted)
-    off = [0]
-    for t in range(maxlen - 1):
-        off.append(off[-1] + sum(1 for s in seqs_sorted if len(s) - 1 > t))
-    assert off[-1] == R
+    off = f64_model.layout_whole_epoch(ptr, items, T, R)
+    seqs_sorted = [list(s) for s in f64_model.check_layout(off, in_idx.astype(np.int64), out_idx.astype(np.int64), ptr, items, T,
+                                                            whole_epoch=True)]
+    assert [len(s) for s in seqs_sorted] == sorted((len(s) for s in seqs_sorted), reverse=True)
     negs = []
     for bi, s in enumerate(seqs_sorted):
         rows = [off[t] + bi for t in range(len(s) - 1)]
@@ -131,39 +143,3 @@ def test_oracle_gradients_match_autograd(oracle_lib, model_kind, loss_kind):
         np.testing.assert_allclose(dW, leaves[2].grad.numpy(), rtol=2e-4, atol=2e-5)
         np.testing.assert_allclose(dbW, leaves[3].grad.numpy(), rtol=2e-4, atol=2e-5)
 
-
-def _minibatch_sequences(ptr, items, T, hp, m, plan):
-    """Sequences of minibatch 0 in the oracle's packed order, recovered from its index rows."""
-    R = plan.minibatch_rows(0)
-    in_idx = plan.debug_fetch(Debug.IN_IDX, R)
-    out_idx = plan.debug_fetch(Debug.OUT_IDX, R)
-    # B_0 = number of rows at t = 0.  Step-t rows are a prefix of step-(t-1) sequences, and
-    # in_idx[t+1][b] == out_idx[t][b]; walk greedily.
-    B = int(hp.batch_sequences)
-    # candidate B_0 values: any nb <= B such that chains are consistent and total rows == R
-    for nb in range(min(B, R), 0, -1):
-        seqs = [[int(in_idx[b])] for b in range(nb)]
-        last_out = [int(out_idx[b]) for b in range(nb)]
-        alive = nb
-        pos = nb
-        ok = True
-        while pos < R:
-            # next step has bt <= alive rows
-            bt = 0
-            while bt < alive and pos + bt < R and int(in_idx[pos + bt]) == last_out[bt]:
-                bt += 1
-            # bt might be over-counted by coincidence only if ids repeat; accept greedy
-            if bt == 0:
-                ok = False
-                break
-            for b in range(bt):
-                seqs[b].append(last_out[b])
-                last_out[b] = int(out_idx[pos + b])
-            alive = bt
-            pos += bt
-        if ok and pos == R:
-            for b in range(nb):
-                seqs[b].append(last_out[b])
-            if all(len(s) <= T for s in seqs) and sorted((len(s) for s in seqs), reverse=True) == [len(s) for s in seqs]:
-                return seqs
-    raise AssertionError("could not recover minibatch structure")
