@@ -25,6 +25,10 @@ loss = model.fit(train_mat)
 elapsed = time.perf_counter() - start
 print(f"Train MRR {sbr.evaluation.mrr_score(model, train_mat):.4f} at loss {loss:.4f} and "
       f"test MRR {sbr.evaluation.mrr_score(model, test_mat):.4f} (in {elapsed:.3f} s)")
+metrics = sbr.evaluation.ranking_metrics(model, test_mat, ks=(10, 100), holdout=5)  # exact ranks of 5 held-out items per user, one scan
+print(f"test hold-out of 5 ({metrics['num_users_ranked']} users): recall@10 {metrics['recall'][10]:.4f}, "
+      f"NDCG@10 {metrics['ndcg'][10]:.4f}, recall@100 {metrics['recall'][100]:.4f}, NDCG@100 {metrics['ndcg'][100]:.4f}, "
+      f"MRR {metrics['mrr']:.4f}, mean rank {metrics['mean_rank']:.1f}")
 user = model.user_representation([50, 181, 258])
 print("scores:", model.predict(user, [1, 100, 300]))
 items, scores = model.recommend(test_mat, 10)  # the whole catalogue on the device, the histories excluded

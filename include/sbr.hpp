@@ -632,6 +632,27 @@ class ImplicitSequenceModel : public OnlineRankingModel<ImplicitUser> {
         return Result<Recommendations, PredictionError>::Ok(std::move(r));
     }
 
+    /// Exact ranks of each user's targets among the whole catalogue from ONE device scan (sbr_rank_targets): user u's history is
+    /// row u of `histories`, its targets target_items[target_ptr[u] .. target_ptr[u + 1]).  rank = #{items whose masked score >=
+    /// the target's}: the target counts itself, ties count against it, the WHOLE history is masked to f32::MIN unless
+    /// `mask_history` is false (a target inside it then has rank num_items).  One rank per target, in target order.
+    /// Err(InvalidPredictionValue) on a non-finite score.
+    Result<std::vector<std::uint32_t>, PredictionError> rank_targets(const data::CompressedInteractions& histories,
+                                                                     const std::vector<std::uint64_t>& target_ptr,
+                                                                     const std::vector<std::uint32_t>& target_items,
+                                                                     bool mask_history = true) const {
+        using R = Result<std::vector<std::uint32_t>, PredictionError>;
+        if (target_ptr.size() != histories.num_users() + 1 || target_ptr.back() - target_ptr.front() > target_items.size())
+            throw EngineError(SBR_ERR_INVALID_ARGUMENT, "rank_targets: one target range per user");
+        std::vector<std::uint32_t> ranks(target_ptr.back() - target_ptr.front());
+        const sbr_status st = sbr_rank_targets(replicas_->primary(), histories.user_pointers().data(), histories.item_ids().data(),
+                                               (std::uint64_t)histories.num_users(), target_ptr.data(), target_items.data(),
+                                               mask_history ? 0u : SBR_RANK_INCLUDE_HISTORY, ranks.data());
+        if (st == SBR_ERR_INVALID_PREDICTION) return R::Err(PredictionError::InvalidPredictionValue);
+        check(st, "sbr_rank_targets");
+        return R::Ok(std::move(ranks));
+    }
+
     /// The engine handle (replica 0), for evaluation's fused path and for parameter access.
     sbr_model* handle() const { return replicas_->primary(); }
     const sbr_hparams& hparams() const { return replicas_->hparams(); }
@@ -970,6 +991,108 @@ inline Result<float, PredictionError> mrr_score(const models::detail::ImplicitSe
         *out_ranks = std::move(ranks);
     }
     return Result<float, PredictionError>::Ok(mrr);
+}
+
+/// Ranking metrics at several k over a hold-out of one or more items per user (no counterpart in the reference crate).
+/// The means are over the ranked users (NaN without one, as mrr_score's 0 / 0); `per_user_*` hold one value per ranked user,
+/// the at-k ones row-major [num_users_ranked][ks.size()].
+struct RankingMetrics {
+    std::vector<std::size_t> ks;
+    std::size_t num_users_ranked = 0;
+    std::vector<std::size_t> users;  ///< the ranked users' indices
+    std::vector<double> precision, recall, hit_rate, ndcg;  ///< one mean per k
+    double mrr = 0.0, mean_rank = 0.0;
+    std::vector<double> per_user_precision, per_user_recall, per_user_hit_rate, per_user_ndcg, per_user_mrr, per_user_mean_rank;
+};
+
+/// precision / recall / hit rate / NDCG at every k, MRR (1 / best rank) and mean rank from the catalogue ranks of each user's
+/// DISTINCT relevant items, user u's being ranks[ranks_ptr[u] .. ranks_ptr[u + 1]) (r of them):
+///   hits_k = #{t : rank_t <= k}, precision = hits_k / k, recall = hits_k / r, hit_rate = hits_k > 0,
+///   ndcg = sum_{rank_t <= k} 1 / log2(1 + rank_t)  /  sum_{j = 1..min(r, k)} 1 / log2(1 + j).
+/// Users without ranks are left out.  Host only, float64.
+inline RankingMetrics ranking_metrics_from_ranks(const std::vector<std::uint64_t>& ranks_ptr, const std::vector<std::uint32_t>& ranks,
+                                                 const std::vector<std::size_t>& ks) {
+    RankingMetrics out;
+    out.ks = ks;
+    const std::size_t nk = ks.size();
+    std::size_t kmax = 0;
+    for (std::size_t k : ks) {
+        if (k < 1) throw std::invalid_argument("ranking_metrics: every k must be >= 1");
+        kmax = std::max(kmax, k);
+    }
+    std::vector<double> ideal(kmax + 1, 0.0);
+    for (std::size_t j = 1; j <= kmax; ++j) ideal[j] = ideal[j - 1] + 1.0 / std::log2(1.0 + (double)j);
+    for (std::size_t u = 0; u + 1 < ranks_ptr.size(); ++u) {
+        std::vector<std::uint32_t> r(ranks.begin() + (std::ptrdiff_t)ranks_ptr[u], ranks.begin() + (std::ptrdiff_t)ranks_ptr[u + 1]);
+        if (r.empty()) continue;
+        std::sort(r.begin(), r.end());
+        out.users.push_back(u);
+        out.per_user_mrr.push_back(1.0 / (double)r[0]);
+        double sum = 0.0;
+        for (std::uint32_t x : r) sum += (double)x;
+        out.per_user_mean_rank.push_back(sum / (double)r.size());
+        for (std::size_t k : ks) {
+            const std::size_t hits = (std::size_t)(std::upper_bound(r.begin(), r.end(), (std::uint32_t)std::min<std::size_t>(k, 0xFFFFFFFFu)) - r.begin());
+            double dcg = 0.0;
+            for (std::size_t j = 0; j < hits; ++j) dcg += 1.0 / std::log2(1.0 + (double)r[j]);
+            out.per_user_precision.push_back((double)hits / (double)k);
+            out.per_user_recall.push_back((double)hits / (double)r.size());
+            out.per_user_hit_rate.push_back(hits ? 1.0 : 0.0);
+            out.per_user_ndcg.push_back(dcg / ideal[std::min(r.size(), k)]);
+        }
+    }
+    const std::size_t n = out.num_users_ranked = out.users.size();
+    auto mean_at = [&](const std::vector<double>& v, std::size_t j, std::size_t stride) {
+        double s = 0.0;
+        for (std::size_t i = 0; i < n; ++i) s += v[i * stride + j];
+        return s / (double)n;
+    };
+    for (std::size_t j = 0; j < nk; ++j) {
+        out.precision.push_back(mean_at(out.per_user_precision, j, nk));
+        out.recall.push_back(mean_at(out.per_user_recall, j, nk));
+        out.hit_rate.push_back(mean_at(out.per_user_hit_rate, j, nk));
+        out.ndcg.push_back(mean_at(out.per_user_ndcg, j, nk));
+    }
+    out.mrr = mean_at(out.per_user_mrr, 0, 1);
+    out.mean_rank = mean_at(out.per_user_mean_rank, 0, 1);
+    return out;
+}
+
+/// precision@k, recall@k, hit-rate@k, NDCG@k at every k of `ks`, MRR and mean rank over a hold-out: the last `holdout` items of
+/// each test sequence are the targets (de-duplicated, first occurrence kept), the rest the history; users with fewer than
+/// holdout + 1 items are skipped (the reference's >= 2 at holdout = 1).  The exact ranks come from one device scan
+/// (ImplicitSequenceModel::rank_targets), whose cost does not depend on k; `out_ranks` (optional) receives them, one per
+/// distinct target in user order.  `users` of the result index the test set's users.
+inline Result<RankingMetrics, PredictionError> ranking_metrics(const models::detail::ImplicitSequenceModel& model,
+                                                               const data::CompressedInteractions& test,
+                                                               const std::vector<std::size_t>& ks = {10, 100}, std::size_t holdout = 1,
+                                                               std::vector<std::uint32_t>* out_ranks = nullptr) {
+    if (holdout < 1) throw std::invalid_argument("ranking_metrics: holdout must be >= 1");
+    std::vector<std::size_t> users;
+    std::vector<std::uint64_t> hist_ptr{0}, target_ptr{0}, timestamps;
+    std::vector<std::uint32_t> hist_items, target_items;
+    const std::vector<std::uint64_t>& ptr = test.user_pointers();
+    for (std::size_t u = 0; u < test.num_users(); ++u) {
+        const std::uint64_t b = ptr[u], e = ptr[u + 1];
+        if (e - b < holdout + 1) continue;
+        users.push_back(u);
+        hist_items.insert(hist_items.end(), test.item_ids().begin() + (std::ptrdiff_t)b, test.item_ids().begin() + (std::ptrdiff_t)(e - holdout));
+        hist_ptr.push_back(hist_items.size());
+        for (std::uint64_t x = e - holdout; x < e; ++x) {
+            const std::uint32_t t = test.item_ids()[x];
+            if (std::find(target_items.begin() + (std::ptrdiff_t)target_ptr.back(), target_items.end(), t) == target_items.end())
+                target_items.push_back(t);
+        }
+        target_ptr.push_back(target_items.size());
+    }
+    timestamps.assign(hist_items.size(), 0);
+    const data::CompressedInteractions histories(users.size(), test.num_items(), hist_ptr, hist_items, timestamps);
+    auto ranks = model.rank_targets(histories, target_ptr, target_items);
+    if (ranks.is_err()) return Result<RankingMetrics, PredictionError>::Err(ranks.unwrap_err());
+    RankingMetrics out = ranking_metrics_from_ranks(target_ptr, ranks.unwrap(), ks);
+    for (std::size_t& u : out.users) u = users[u];
+    if (out_ranks) *out_ranks = ranks.unwrap();
+    return Result<RankingMetrics, PredictionError>::Ok(std::move(out));
 }
 
 } // namespace evaluation

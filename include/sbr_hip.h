@@ -409,6 +409,26 @@ sbr_status sbr_recommend(sbr_model* m, const uint64_t* user_ptr, const uint32_t*
 sbr_status sbr_recommend_reps(sbr_model* m, const float* reps, uint64_t num_users, uint32_t k,
                               const uint64_t* excl_ptr, const uint32_t* excl_items, uint32_t* out_items, float* out_scores);
 
+/* Exact ranks of many held-out items per user from ONE scan of the catalogue (no counterpart in the reference crate beyond the one
+ * item of evaluation.rs:12-48, whose rule this applies to each target on its own).  With score(u, i) as above and the masked score
+ * m(u, i) = f32::MIN if i is in the user's mask list, else score(u, i):
+ *     rank(u, t) = #{ i in [0, num_items) : m(u, i) >= m(u, t) }
+ * so the target counts itself (rank >= 1), ties count against it, other targets are ordinary items, a masked target has rank
+ * num_items, and duplicate targets get equal ranks.  User u's targets are target_items[target_ptr[u] .. target_ptr[u + 1]) (any
+ * number, none included); out_ranks[e - target_ptr[0]] is the rank of target_items[e].  Precision / recall / hit rate / NDCG at any k
+ * and the mean rank follow from the ranks on the host.  SBR_ERR_INVALID_PREDICTION if any score of a scanned user is non-finite;
+ * SBR_ERR_INVALID_ARGUMENT for decreasing pointers, ids >= num_items, unknown flags.  Deterministic (integer counts).
+ * sbr_rank_targets: histories as sbr_recommend's (representation of the last max_sequence_length items, empty = item 0); the mask
+ * is the WHOLE history unless flags has SBR_RANK_INCLUDE_HISTORY.  With one target per user (the last item) and the rest as history
+ * the result is sbr_mrr_score's rank.
+ * sbr_rank_targets_reps: from representations; excl_ptr / excl_items: optional per-user mask lists (CSR; both NULL = none). */
+#define SBR_RANK_INCLUDE_HISTORY 1u
+sbr_status sbr_rank_targets(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users,
+                            const uint64_t* target_ptr, const uint32_t* target_items, uint32_t flags, uint32_t* out_ranks);
+sbr_status sbr_rank_targets_reps(sbr_model* m, const float* reps, uint64_t num_users,
+                                 const uint64_t* excl_ptr, const uint32_t* excl_items,
+                                 const uint64_t* target_ptr, const uint32_t* target_items, uint32_t* out_ranks);
+
 /* ≙ the serde derives (lstm.rs:204,386; ewma.rs:208,401): element counts and raw access. */
 sbr_status sbr_model_param_count(const sbr_model* m, int32_t which, uint64_t* out_count);
 sbr_status sbr_model_get_param(sbr_model* m, int32_t which, float* host_out, uint64_t count);

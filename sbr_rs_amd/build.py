@@ -90,7 +90,17 @@ def build_recommend_tests(force: bool = False, verbose: bool = True) -> str:
     return _build_cpp_program(RECOMMEND_SRC, RECOMMEND_BIN, force, verbose)
 
 
+RANKING_SRC = os.path.join(REPO, "tests", "cpp", "ranking_tests.cpp")
+RANKING_BIN = os.path.join(REPO, "tests", "cpp", "_build", "ranking_tests")
+
+
+def build_ranking_tests(force: bool = False, verbose: bool = True) -> str:
+    """g++ build of the C++ host layer's rank_targets / ranking_metrics test program."""
+    return _build_cpp_program(RANKING_SRC, RANKING_BIN, force, verbose)
+
+
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv))
     print(build_facade_tests(force="--force" in sys.argv))
     print(build_recommend_tests(force="--force" in sys.argv))
+    print(build_ranking_tests(force="--force" in sys.argv))

@@ -1,18 +1,21 @@
 /* sbr_catalogue.hip — the prediction side: scores of items for a user state, and scans of the whole catalogue for a batch of
- * user states (mrr_score's ranks, recommend's top k).
+ * user states (mrr_score's ranks, rank_targets' ranks of many targets per user, recommend's top k).
  *
  *   predict_kernel         : b[i] + chain_dot(h, E[i]), k ascending from 0 (sbr_predict)
  *   rank_test_score_kernel : ts[u] = MIN if the test item is in the history, else bias + chain dot
  *   rank_gemm_kernel       : counts S[u][i] >= ts[u] (mrr_score, evaluation.rs:27-43)
  *   rank_history_kernel    : corrects the count for the (unique) history items, which the reference masks to f32::MIN
  *                            (evaluation.rs:30-32)
+ *   rank_targets_*_kernel  : rank_targets' exact ranks of many targets per user from one scan: prepare (thresholds, sorted per
+ *                            scan-user), gemm (each score counted into the bucket between two thresholds, in LDS), finish (prefix
+ *                            sums and the mask correction)
  *   topk_gemm_kernel       : per user and item range, a running sorted list of the k best (score desc, id asc) in global scratch
  *                            and its k-th entry as the threshold in LDS.  A score that beats the threshold is staged in LDS; a
  *                            full staging buffer is sorted and merged into the list (which raises the threshold).
  *   topk_merge_kernel      : one workgroup per user merges the item ranges' lists into the final k, padded with
  *                            (0xFFFFFFFF, -inf).
  *
- * The two GEMM kernels share one catalogue scan, S[u][i] = b[i] + sum_k h[u][k] E[i][k] on v_mfma_f32_32x32x2_f32: a workgroup
+ * The three GEMM kernels share one catalogue scan, S[u][i] = b[i] + sum_k h[u][k] E[i][k] on v_mfma_f32_32x32x2_f32: a workgroup
  * owns 128 users (4 waves x 32, their states held in registers as MFMA A fragments) and a contiguous range of items, whose
  * 32-item tiles of E and b stream through an LDS double buffer; k ascends from 0, so every score has the bits of sbr_predict.  The
  * U x I score matrix never leaves the registers.  The top-k epilogue cannot overflow (a staging buffer that fills is merged and
@@ -29,7 +32,7 @@ namespace sbr {
 
 namespace {
 
-/* ---- the catalogue scan shared by rank_gemm_kernel and topk_gemm_kernel ---- */
+/* ---- the catalogue scan shared by rank_gemm_kernel, rank_targets_gemm_kernel and topk_gemm_kernel ---- */
 
 /* The user of accumulator register q of a lane in wave half hh, for a wave whose 32 users start at u0 (the C layout of
  * v_mfma_f32_32x32x2_f32: row (q & 3) + 8 (q >> 2) + 4 hh; the lane's item is lane & 31). */
@@ -274,6 +277,229 @@ __global__ __launch_bounds__(64) void rank_history_kernel(ModelView m, const flo
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
     if (threadIdx.x == 0 && cnt) atomicAdd(&ranks[u], (uint32_t)cnt); /* two's complement: adds a negative delta */
+}
+
+// ------------------------------------------------------------------------------------------------
+// rank_targets: the catalogue scan with a multi-threshold rank epilogue
+// ------------------------------------------------------------------------------------------------
+/* A scan-user is one user state with at most TM targets (the host splits a user with more into several scan-users that share a
+ * representation row); scan-user s owns the targets [sptr[s], sptr[s + 1]) of the launch's flat target list.
+ *
+ * One thread per (scan-user, slot j < TM): the threshold of target j, ts = m(u, t) — MIN if the target is in the user's mask list,
+ * else bias + chain dot — then the scan-user's thresholds in descending order (position = number of thresholds that come before:
+ * greater, or equal with a lower slot) into th[s][0..n), padded with -inf up to TM; tmin[s] = the lowest and tmin2[s] the one before
+ * it (+inf where there is one threshold); the buckets and the total zeroed. */
+template <int D, int TM>
+__global__ __launch_bounds__(256) void rank_targets_prepare_kernel(ModelView m, const float* reps, const int* rep_row, const uint32_t* su_user,
+                                                                   const uint32_t* sptr, uint32_t num_su, const uint32_t* tgt_items,
+                                                                   const uint64_t* mask_ptr, const uint32_t* mask_items, float* ts, uint32_t* pos,
+                                                                   float* th, float* tmin, float* tmin2, uint32_t* buckets,
+                                                                   uint32_t* totals) {
+    __shared__ float tl[256];
+    const int tid = threadIdx.x;
+    const int j = tid % TM;
+    const uint32_t s = blockIdx.x * (256 / TM) + tid / TM;
+    uint32_t e = 0, n = 0;
+    float t = -INFINITY;
+    if (s < num_su) {
+        e = sptr[s] + j;
+        n = sptr[s + 1] - sptr[s];
+    }
+    const bool real = (uint32_t)j < n;
+    if (real) {
+        const uint32_t ti = tgt_items[e];
+        bool masked = false;
+        if (mask_ptr) { /* sorted, de-duplicated mask list of the user */
+            const uint32_t u = su_user[s];
+            uint64_t lo = mask_ptr[u], hi = mask_ptr[u + 1];
+            while (lo < hi) {
+                const uint64_t mid = (lo + hi) >> 1;
+                if (mask_items[mid] < ti) lo = mid + 1; else hi = mid;
+            }
+            masked = lo < mask_ptr[u + 1] && mask_items[lo] == ti;
+        }
+        t = masked ? SBR_F32_MIN : m.b[ti] + chain_dot<D>(reps + (size_t)rep_row[s] * D, m.E + (size_t)ti * D);
+    }
+    tl[tid] = t;
+    __syncthreads();
+    if (s >= num_su) return;
+    uint32_t p = (uint32_t)j; /* the padding keeps its slot (>= n) */
+    if (real) {
+        p = 0;
+        const float* mine = &tl[tid - j];
+        for (uint32_t o = 0; o < n; ++o) {
+            const float x = mine[o];
+            p += (x > t || (x == t && o < (uint32_t)j)) ? 1u : 0u;
+        }
+        ts[e] = t;
+        pos[e] = p;
+        if (p == n - 1) tmin[s] = t;
+        if (p + 2 == n) tmin2[s] = t;
+    }
+    if (j == 0) {
+        if (n == 1) tmin2[s] = INFINITY;
+        totals[s] = 0;
+    }
+    th[(size_t)s * TM + p] = t;
+    buckets[(size_t)s * TM + j] = 0;
+}
+
+/* The scan.  Per workgroup and slot (slot_user) the TM descending thresholds and TM buckets live in LDS.  A score sc of a real item
+ * that reaches the slot's lowest threshold (the one compare rank_gemm_kernel pays too) is counted in the lane's registers as there:
+ * the total is the rank of the lowest target.  A score that also reaches the second lowest threshold is searched: j = #{thresholds
+ * > sc}, which is below n - 1 for n thresholds because the last two are not above sc, and bucket j counts it with an LDS atomic; rank
+ * of the target at sorted position r < n - 1 = sum of buckets 0..r.  So one target per user costs no search and no atomic, and a
+ * trained model, whose scores mostly lie below all but the lowest targets, few.  The search is branch-free over the -inf padded
+ * array (log2 TM dependent LDS reads), and the 16 users of a lane take each step together so the reads of a step are in flight at
+ * once.  Within a half-wave the 32 lanes read one slot's TM consecutive words: distinct banks or a broadcast.  Buckets are 32 bits
+ * wide; the lane counters 16, two per register: the launcher keeps an item range below 65 536 tiles. */
+template <int D, int TM>
+__global__ __launch_bounds__(256, D <= 128 ? 3 : 2) void rank_targets_gemm_kernel(ModelView m, const float* reps, const int* rep_row, uint32_t num_su,
+                                                                                 const float* th, const float* tmin, const float* tmin2,
+                                                                                 uint32_t items_per_group, uint32_t* buckets, uint32_t* totals,
+                                                                                 uint32_t* nonfinite_flag) {
+    __shared__ float Es[2][32 * ItemTiles<D>::LDE];
+    __shared__ float Bs[2][32];
+    __shared__ float Tmin[128];      /* by slot (slot_user) */
+    __shared__ float Tmin2[128];
+    __shared__ float Th[128 * TM];
+    __shared__ uint32_t Hist[128 * TM];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = tid >> 6;
+    const int l31 = lane & 31;
+    const int hh = lane >> 5;
+    const uint32_t u0 = blockIdx.x * 128 + wave * 32;
+    float a[D / 2];
+    load_user_fragments<D>(a, reps, rep_row, num_su, u0);
+    if (tid < 128) {
+        const uint32_t u = blockIdx.x * 128 + (uint32_t)slot_user(tid);
+        Tmin[tid] = u < num_su ? tmin[u] : INFINITY; /* no scan-user: nothing passes */
+        Tmin2[tid] = u < num_su ? tmin2[u] : INFINITY;
+    }
+    uint32_t cnt2[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) cnt2[q] = 0;
+    for (int idx = tid; idx < 128 * TM; idx += 256) {
+        const uint32_t u = blockIdx.x * 128 + (uint32_t)slot_user(idx / TM);
+        Th[idx] = u < num_su ? th[(size_t)u * TM + idx % TM] : -INFINITY;
+        Hist[idx] = 0;
+    }
+    bool bad = false;
+    ItemTiles<D> tiles(m, items_per_group);
+    const int ntiles = tiles.ntiles;
+    if (ntiles > 0) {
+        tiles.fetch(m, 0);
+        tiles.stage(Es[0], Bs[0]);
+    }
+    __syncthreads();
+    const int pbase = wave * 32 + hh * 16;
+    for (int tile = 0; tile < ntiles; ++tile) {
+        const int buf = tile & 1;
+        if (tile + 1 < ntiles) tiles.fetch(m, tile + 1);
+        const f32x16 acc = tile_dots<D>(a, Es[buf]);
+        const float bias = Bs[buf][l31];
+        const bool item_ok = tiles.i_begin + (uint32_t)tile * 32 + l31 < tiles.i_end;
+        uint32_t pass = 0; /* accumulator registers q whose score reaches the slot's second lowest threshold */
+#pragma unroll
+        for (int q4 = 0; q4 < 4; ++q4) {
+            const float4 t4 = ld4(&Tmin[pbase + 4 * q4]);
+            const float4 s4 = ld4(&Tmin2[pbase + 4 * q4]);
+            const float tq[4] = {t4.x, t4.y, t4.z, t4.w};
+            const float sq[4] = {s4.x, s4.y, s4.z, s4.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int q = 4 * q4 + j;
+                const float sc = bias + acc[q];
+                if (item_ok) {
+                    if (!(sc - sc == 0.0f)) bad = true;
+                    if (sc >= tq[j]) cnt2[q >> 1] += (q & 1) ? 0x10000u : 1u;
+                    if (sc >= sq[j]) pass |= 1u << q;
+                }
+            }
+        }
+        if (__any(pass != 0u)) {
+            int at[16]; /* #{thresholds > score} so far */
+#pragma unroll
+            for (int q = 0; q < 16; ++q) at[q] = 0;
+#pragma unroll
+            for (int step = TM / 2; step >= 1; step >>= 1)
+#pragma unroll
+                for (int q = 0; q < 16; ++q)
+                    if (Th[(pbase + q) * TM + at[q] + step - 1] > bias + acc[q]) at[q] += step;
+#pragma unroll
+            for (int q = 0; q < 16; ++q)
+                if ((pass >> q) & 1u) atomicAdd(&Hist[(pbase + q) * TM + at[q]], 1u);
+        }
+        if (tile + 1 < ntiles) tiles.stage(Es[buf ^ 1], Bs[buf ^ 1]);
+        __syncthreads();
+    }
+    // per-slot totals: sum over the 32 item lanes of each half-wave
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+        int c = (int)((cnt2[q >> 1] >> ((q & 1) * 16)) & 0xFFFFu);
+#pragma unroll
+        for (int off = 16; off >= 1; off >>= 1) c += __shfl_xor(c, off, 64);
+        const uint32_t u = acc_user(u0, q, hh);
+        if (l31 == 0 && u < num_su && c) atomicAdd(&totals[u], (uint32_t)c);
+    }
+    // the workgroup's buckets join the other item ranges'
+    for (int idx = tid; idx < 128 * TM; idx += 256) {
+        const uint32_t u = blockIdx.x * 128 + (uint32_t)slot_user(idx / TM);
+        const uint32_t c = Hist[idx];
+        if (u < num_su && c) atomicAdd(&buckets[(size_t)u * TM + idx % TM], c);
+    }
+    if (__any(bad) && lane == 0) atomicOr(nonfinite_flag, 1u);
+}
+
+/* One wave per scan-user: the mask correction of every target (rank_history_kernel's, with each masked item scored once for all
+ * the scan-user's targets: its real score leaves the count, its masked value counts only against thresholds <= MIN), then
+ * rank = buckets 0..position (the total at the last position) + correction. */
+template <int D, int TM>
+__global__ __launch_bounds__(64) void rank_targets_finish_kernel(ModelView m, const float* reps, const int* rep_row, const uint32_t* su_user,
+                                                                 const uint32_t* sptr, const float* ts, const uint32_t* pos,
+                                                                 const uint32_t* buckets, const uint32_t* totals, const uint64_t* mask_ptr,
+                                                                 const uint32_t* mask_items, uint32_t* ranks) {
+    __shared__ float tl[TM];
+    __shared__ int delta[TM];
+    const uint32_t s = blockIdx.x;
+    const int lane = threadIdx.x;
+    const uint32_t e0 = sptr[s];
+    const int n = (int)(sptr[s + 1] - e0);
+    if (lane < TM) tl[lane] = lane < n ? ts[e0 + lane] : INFINITY;
+    __syncthreads();
+    int cnt[TM];
+#pragma unroll
+    for (int r = 0; r < TM; ++r) cnt[r] = 0;
+    if (mask_ptr) {
+        const uint32_t u = su_user[s];
+        const float* h = reps + (size_t)rep_row[s] * D;
+        for (uint64_t e = mask_ptr[u] + lane; e < mask_ptr[u + 1]; e += 64) {
+            const uint32_t i = mask_items[e];
+            const float sc = m.b[i] + chain_dot<D>(h, m.E + (size_t)i * D);
+#pragma unroll
+            for (int r = 0; r < TM; ++r) {
+                const float t = tl[r];
+                cnt[r] += (SBR_F32_MIN >= t ? 1 : 0) - (sc >= t ? 1 : 0);
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < TM; ++r) {
+        int c = cnt[r];
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) c += __shfl_xor(c, off, 64);
+        if (lane == r) delta[r] = c;
+    }
+    __syncthreads();
+    if (lane < n) {
+        const uint32_t p = pos[e0 + lane];
+        uint32_t rank = 0;
+        if (p + 1 == (uint32_t)n) rank = totals[s];
+        else
+            for (uint32_t j = 0; j <= p; ++j) rank += buckets[(size_t)s * TM + j];
+        ranks[e0 + lane] = rank + (uint32_t)delta[lane]; /* two's complement: adds a negative delta */
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -524,6 +750,32 @@ void launch_rank(const ModelView& m, const float* reps, const int* rep_row, uint
         hipLaunchKernelGGL((rank_test_score_kernel<DD>), dim3((num_users + 255) / 256), dim3(256), 0, s, m, reps, rep_row, num_users, test_item, test_in_hist, ts_scratch, ranks);
         hipLaunchKernelGGL((rank_gemm_kernel<DD>), dim3(utiles, groups), dim3(256), 0, s, m, reps, rep_row, num_users, ts_scratch, per, ranks, nonfinite_flag);
         hipLaunchKernelGGL((rank_history_kernel<DD>), dim3(num_users), dim3(64), 0, s, m, reps, rep_row, ts_scratch, hist_ptr, hist_items, ranks);
+    });
+}
+
+uint32_t rank_targets_tmax(int d) {
+    // the thresholds and buckets of 128 slots (2 x 128 x TM words of LDS) beside the item tiles: three workgroups per CU at d <= 128
+    // (50 KB each), two at d = 256 (75 KB; with 16 thresholds a workgroup would take 83 KB and a CU hold one)
+    return d <= 128 ? 16u : 8u;
+}
+
+void launch_rank_targets(const ModelView& m, const float* reps, const int* rep_row, const uint32_t* su_user, const uint32_t* sptr,
+                         uint32_t num_su, const uint32_t* tgt_items, const uint64_t* mask_ptr, const uint32_t* mask_items, float* ts,
+                         uint32_t* pos, float* th, float* tmin, float* tmin2, uint32_t* buckets, uint32_t* totals, uint32_t* ranks,
+                         uint32_t* nonfinite_flag, hipStream_t s) {
+    if (num_su == 0) return;
+    const uint32_t utiles = (num_su + 127) / 128;
+    // item ranges as launch_rank's, and its limit: the kernel's per-lane counters are 16 bits wide, fewer than 65 536 tiles per range
+    uint32_t per = 0;
+    const uint32_t groups = split_items(m.num_items, wanted_groups((768u * 6u + utiles - 1) / utiles), UINT32_MAX, 65535u * 32u, &per);
+    DISPATCH_D(m.d, {
+        constexpr int TM = DD <= 128 ? 16 : 8; /* = rank_targets_tmax(DD) */
+        hipLaunchKernelGGL((rank_targets_prepare_kernel<DD, TM>), dim3((num_su + 256 / TM - 1) / (256 / TM)), dim3(256), 0, s, m, reps, rep_row,
+                           su_user, sptr, num_su, tgt_items, mask_ptr, mask_items, ts, pos, th, tmin, tmin2, buckets, totals);
+        hipLaunchKernelGGL((rank_targets_gemm_kernel<DD, TM>), dim3(utiles, groups), dim3(256), 0, s, m, reps, rep_row, num_su, th, tmin, tmin2,
+                           per, buckets, totals, nonfinite_flag);
+        hipLaunchKernelGGL((rank_targets_finish_kernel<DD, TM>), dim3(num_su), dim3(64), 0, s, m, reps, rep_row, su_user, sptr, ts, pos,
+                           buckets, totals, mask_ptr, mask_items, ranks);
     });
 }
 

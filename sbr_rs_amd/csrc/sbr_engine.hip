@@ -3729,6 +3729,206 @@ sbr_status sbr_recommend_reps(sbr_model* m, const float* reps, uint64_t num_user
 }
 
 /* ---------------------------------------------------------------------------------------------
+ * exact ranks of many targets per user from one catalogue scan (sbr_catalogue.hip)
+ * ------------------------------------------------------------------------------------------- */
+namespace {
+
+/* The scan-users of a call: user u's targets in runs of at most tmax, in user and target order (a user without targets has none). */
+struct ScanUsers {
+    std::vector<uint64_t> user;  /* the user of scan-user s */
+    std::vector<uint64_t> begin; /* its first target, an index into target_items */
+    std::vector<uint32_t> count; /* 1 .. tmax */
+};
+
+sbr_status rank_targets_check(const sbr_model* m, uint64_t num_users, const uint64_t* target_ptr, const uint32_t* target_items,
+                              uint32_t* out_ranks, uint32_t tmax, ScanUsers* su) {
+    if (!target_ptr) return SBR_ERR_INVALID_ARGUMENT;
+    for (uint64_t u = 0; u < num_users; ++u)
+        if (target_ptr[u + 1] < target_ptr[u]) return SBR_ERR_INVALID_ARGUMENT; /* pointers must be non-decreasing */
+    const uint64_t nt = target_ptr[num_users] - target_ptr[0];
+    if (nt && (!target_items || !out_ranks)) return SBR_ERR_INVALID_ARGUMENT;
+    for (uint64_t e = target_ptr[0]; e < target_ptr[num_users]; ++e)
+        if (target_items[e] >= m->hp.num_items) return SBR_ERR_INVALID_ARGUMENT;
+    for (uint64_t u = 0; u < num_users; ++u)
+        for (uint64_t e = target_ptr[u]; e < target_ptr[u + 1]; e += tmax) {
+            su->user.push_back(u);
+            su->begin.push_back(e);
+            su->count.push_back((uint32_t)std::min<uint64_t>(tmax, target_ptr[u + 1] - e));
+        }
+    return SBR_OK;
+}
+
+/* users per scan launch as mrr_score's EVAL_B, counted in scan-users */
+constexpr size_t RANK_TARGETS_B = 8192;
+
+/* arena bytes of one launch over ns scan-users of nlu users with nt targets and nmask mask entries */
+size_t rank_targets_bytes(size_t ns, size_t nlu, size_t nt, size_t nmask, uint32_t tmax) {
+    return 2 * DeviceArena::padded(ns * 4) + DeviceArena::padded((ns + 1) * 4) + 4 * DeviceArena::padded(nt * 4 + 4) +
+           DeviceArena::padded((nlu + 1) * 8) + DeviceArena::padded(nmask * 4 + 4) + 2 * DeviceArena::padded(ns * tmax * 4) +
+           3 * DeviceArena::padded(ns * 4) + DeviceArena::padded(4);
+}
+
+/* Ranks of the scan-users [c0, c1) of `su`, whose users are local rows: scan-user s has representation row rep_row[lu[s - c0]] of H
+ * (eval arena, reserved with rank_targets_bytes) and the mask list lu[s - c0] of mask_ptr / mask_items (mask_ptr empty: no mask).  The
+ * targets of a chunk are contiguous in target_items, and so are their ranks in `out` (out[0] = rank of target su.begin[c0]). */
+sbr_status rank_targets_launch(sbr_model* m, const float* H, const std::vector<int>& rep_row, const ScanUsers& su, size_t c0, size_t c1,
+                               const std::vector<uint32_t>& lu, size_t nlu, const std::vector<uint64_t>& mask_ptr,
+                               const std::vector<uint32_t>& mask_items, const uint32_t* target_items, uint32_t tmax, uint32_t* out) {
+    DeviceArena& ar = m->eval_arena;
+    const size_t ns = c1 - c0;
+    const uint64_t t0 = su.begin[c0];
+    const size_t nt = (size_t)(su.begin[c1 - 1] + su.count[c1 - 1] - t0);
+    std::vector<int> srep(ns);
+    std::vector<uint32_t> sptr(ns + 1);
+    for (size_t i = 0; i < ns; ++i) {
+        srep[i] = rep_row[lu[i]];
+        sptr[i] = (uint32_t)(su.begin[c0 + i] - t0);
+    }
+    sptr[ns] = (uint32_t)nt;
+    int* d_rep = ar.take<int>(ns);
+    uint32_t* d_lu = ar.take<uint32_t>(ns);
+    uint32_t* d_sptr = ar.take<uint32_t>(ns + 1);
+    uint32_t* d_tgt = ar.take<uint32_t>(nt + 1);
+    float* d_ts = ar.take<float>(nt + 1);
+    uint32_t* d_pos = ar.take<uint32_t>(nt + 1);
+    uint32_t* d_ranks = ar.take<uint32_t>(nt + 1);
+    uint64_t* d_mptr = ar.take<uint64_t>(nlu + 1);
+    uint32_t* d_mask = ar.take<uint32_t>(mask_items.size() + 1);
+    float* d_th = ar.take<float>(ns * tmax);
+    uint32_t* d_buckets = ar.take<uint32_t>(ns * tmax);
+    float* d_tmin = ar.take<float>(ns);
+    float* d_tmin2 = ar.take<float>(ns);
+    uint32_t* d_totals = ar.take<uint32_t>(ns);
+    uint32_t* d_flag = ar.take<uint32_t>(1);
+    const bool mask = !mask_ptr.empty();
+    HIPCHK(hipMemcpyAsync(d_rep, srep.data(), ns * 4, hipMemcpyHostToDevice, m->stream));
+    HIPCHK(hipMemcpyAsync(d_lu, lu.data(), ns * 4, hipMemcpyHostToDevice, m->stream));
+    HIPCHK(hipMemcpyAsync(d_sptr, sptr.data(), (ns + 1) * 4, hipMemcpyHostToDevice, m->stream));
+    HIPCHK(hipMemcpyAsync(d_tgt, target_items + t0, nt * 4, hipMemcpyHostToDevice, m->stream));
+    if (mask) {
+        HIPCHK(hipMemcpyAsync(d_mptr, mask_ptr.data(), (nlu + 1) * 8, hipMemcpyHostToDevice, m->stream));
+        if (!mask_items.empty()) HIPCHK(hipMemcpyAsync(d_mask, mask_items.data(), mask_items.size() * 4, hipMemcpyHostToDevice, m->stream));
+    }
+    HIPCHK(hipMemsetAsync(d_flag, 0, 4, m->stream));
+    {
+        ScopedTimer t(m, SBR_K_RANK, 3);
+        sbr::launch_rank_targets(m->mv, H, d_rep, d_lu, d_sptr, (uint32_t)ns, d_tgt, mask ? d_mptr : nullptr, d_mask, d_ts, d_pos, d_th,
+                                 d_tmin, d_tmin2, d_buckets, d_totals, d_ranks, d_flag, m->stream);
+    }
+    uint32_t flag = 0;
+    HIPCHK(hipStreamSynchronize(m->stream)); /* the host vectors above are read by the asynchronous copies */
+    HIPCHK(hipMemcpy(&flag, d_flag, 4, hipMemcpyDeviceToHost));
+    if (flag) return SBR_ERR_INVALID_PREDICTION; /* predict fails the call on a non-finite score */
+    HIPCHK(hipMemcpy(out, d_ranks, nt * 4, hipMemcpyDeviceToHost));
+    return SBR_OK;
+}
+
+}  // namespace
+
+sbr_status sbr_rank_targets(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users,
+                            const uint64_t* target_ptr, const uint32_t* target_items, uint32_t flags, uint32_t* out_ranks) {
+    if (!m || !user_ptr || (flags & ~SBR_RANK_INCLUDE_HISTORY)) return SBR_ERR_INVALID_ARGUMENT;
+    std::lock_guard<std::mutex> lock(m->mu);
+    SBRCHK(ensure_device(m));
+    const uint64_t T = m->hp.max_sequence_length;
+    for (uint64_t u = 0; u < num_users; ++u)
+        if (user_ptr[u + 1] < user_ptr[u]) return SBR_ERR_INVALID_ARGUMENT; /* pointers must be non-decreasing */
+    if (user_ptr[num_users] - user_ptr[0] && !item_ids) return SBR_ERR_INVALID_ARGUMENT;
+    for (uint64_t i = user_ptr[0]; i < user_ptr[num_users]; ++i)
+        if (item_ids[i] >= m->hp.num_items) return SBR_ERR_INVALID_ARGUMENT;
+    const uint32_t tmax = sbr::rank_targets_tmax(m->d);
+    ScanUsers su;
+    SBRCHK(rank_targets_check(m, num_users, target_ptr, target_items, out_ranks, tmax, &su));
+    const bool mask = !(flags & SBR_RANK_INCLUDE_HISTORY);
+    const size_t eval_rows_cap = (size_t)1 << 22; /* as mrr_score: the forward pass's scratch is (users x steps) rows */
+    auto rows_of = [&](uint64_t u) { return (size_t)std::max<uint64_t>(1, std::min<uint64_t>(user_ptr[u + 1] - user_ptr[u], T)); };
+    for (size_t c0 = 0, c1 = 0; c0 < su.user.size(); c0 = c1) {
+        /* a chunk is a run of scan-users; a user cut by its end is forwarded again in the next one */
+        size_t rows = 0;
+        for (c1 = c0; c1 < su.user.size() && c1 - c0 < RANK_TARGETS_B; ++c1) {
+            if (c1 == c0 || su.user[c1] != su.user[c1 - 1]) {
+                rows += rows_of(su.user[c1]);
+                if (rows > eval_rows_cap && c1 > c0) break;
+            }
+        }
+        std::vector<uint32_t> lu(c1 - c0);
+        std::vector<const uint32_t*> hist;
+        std::vector<uint64_t> n;
+        for (size_t s = c0; s < c1; ++s) {
+            const uint64_t u = su.user[s];
+            if (s == c0 || u != su.user[s - 1]) {
+                hist.push_back(item_ids ? item_ids + user_ptr[u] : nullptr);
+                n.push_back(user_ptr[u + 1] - user_ptr[u]);
+            }
+            lu[s - c0] = (uint32_t)(hist.size() - 1);
+        }
+        /* the WHOLE history is masked (evaluation.rs:30-32) */
+        UserBatch b;
+        prepare_users(hist, n, T, mask, &b);
+        const size_t nt = (size_t)(su.begin[c1 - 1] + su.count[c1 - 1] - su.begin[c0]);
+        float* H = nullptr;
+        std::vector<int> rep_row;
+        SBRCHK(forward_histories(m, b.first, b.nsteps, &H, &rep_row, rank_targets_bytes(c1 - c0, hist.size(), nt, b.list_items.size(), tmax)));
+        SBRCHK(rank_targets_launch(m, H, rep_row, su, c0, c1, lu, hist.size(), b.list_ptr, b.list_items, target_items, tmax,
+                                   out_ranks + (su.begin[c0] - target_ptr[0])));
+    }
+    return SBR_OK;
+}
+
+sbr_status sbr_rank_targets_reps(sbr_model* m, const float* reps, uint64_t num_users, const uint64_t* excl_ptr, const uint32_t* excl_items,
+                                 const uint64_t* target_ptr, const uint32_t* target_items, uint32_t* out_ranks) {
+    if (!m || (num_users && !reps)) return SBR_ERR_INVALID_ARGUMENT;
+    if ((excl_ptr == nullptr) != (excl_items == nullptr) && !(excl_ptr && excl_ptr[num_users] == excl_ptr[0])) return SBR_ERR_INVALID_ARGUMENT;
+    std::lock_guard<std::mutex> lock(m->mu);
+    SBRCHK(ensure_device(m));
+    if (excl_ptr) {
+        for (uint64_t u = 0; u < num_users; ++u)
+            if (excl_ptr[u + 1] < excl_ptr[u]) return SBR_ERR_INVALID_ARGUMENT;
+        for (uint64_t i = excl_ptr[0]; i < excl_ptr[num_users]; ++i)
+            if (excl_items[i] >= m->hp.num_items) return SBR_ERR_INVALID_ARGUMENT;
+    }
+    const uint32_t tmax = sbr::rank_targets_tmax(m->d);
+    ScanUsers su;
+    SBRCHK(rank_targets_check(m, num_users, target_ptr, target_items, out_ranks, tmax, &su));
+    const size_t d = (size_t)m->d, dl = (size_t)m->dl;
+    for (size_t c0 = 0; c0 < su.user.size(); c0 += RANK_TARGETS_B) {
+        const size_t c1 = std::min(su.user.size(), c0 + RANK_TARGETS_B);
+        std::vector<uint32_t> lu(c1 - c0);
+        std::vector<uint64_t> users; /* the chunk's users, ascending */
+        for (size_t s = c0; s < c1; ++s) {
+            if (s == c0 || su.user[s] != su.user[s - 1]) users.push_back(su.user[s]);
+            lu[s - c0] = (uint32_t)(users.size() - 1);
+        }
+        const size_t nlu = users.size();
+        UserBatch excl; /* the caller's mask lists, sorted and de-duplicated (their state windows go unused) */
+        if (excl_ptr) {
+            std::vector<const uint32_t*> lists(nlu);
+            std::vector<uint64_t> n(nlu);
+            for (size_t i = 0; i < nlu; ++i) {
+                lists[i] = excl_items + excl_ptr[users[i]];
+                n[i] = excl_ptr[users[i] + 1] - excl_ptr[users[i]];
+            }
+            prepare_users(lists, n, m->hp.max_sequence_length, true, &excl);
+        }
+        const size_t nt = (size_t)(su.begin[c1 - 1] + su.count[c1 - 1] - su.begin[c0]);
+        DeviceArena& ar = m->eval_arena;
+        HIPCHK(hipStreamSynchronize(m->stream)); /* nothing of an earlier call may still read the arena */
+        SBRCHK(ar.reserve(DeviceArena::padded(nlu * d * 4) + rank_targets_bytes(c1 - c0, nlu, nt, excl.list_items.size(), tmax)));
+        float* H = ar.take<float>(nlu * d);
+        /* padded to the storage width: the columns past embedding_dim are zero, as in the model's own states */
+        HIPCHK(hipMemsetAsync(H, 0, nlu * d * 4, m->stream));
+        std::vector<float> rows(nlu * dl);
+        for (size_t i = 0; i < nlu; ++i) std::memcpy(rows.data() + i * dl, reps + users[i] * dl, dl * 4);
+        HIPCHK(hipMemcpy2DAsync(H, d * 4, rows.data(), dl * 4, dl * 4, nlu, hipMemcpyHostToDevice, m->stream));
+        std::vector<int> rep_row(nlu);
+        for (size_t i = 0; i < nlu; ++i) rep_row[i] = (int)i;
+        SBRCHK(rank_targets_launch(m, H, rep_row, su, c0, c1, lu, nlu, excl.list_ptr, excl.list_items, target_items, tmax,
+                                   out_ranks + (su.begin[c0] - target_ptr[0])));
+    }
+    return SBR_OK;
+}
+
+/* ---------------------------------------------------------------------------------------------
  * numerics self-tests (tests/test_numerics_gpu.py): run the contract's primitives on the device
  * ------------------------------------------------------------------------------------------- */
 sbr_status sbr_selftest_math(const float* x, uint64_t n, float* out_cell_h, float* out_sig, float* out_tanh) {

@@ -271,6 +271,15 @@ void launch_predict(const ModelView& m, const float* user, const uint32_t* items
 void launch_rank(const ModelView& m, const float* reps, const int* rep_row, uint32_t num_users, const uint32_t* test_item,
                  const uint32_t* test_in_hist, const uint64_t* hist_ptr, const uint32_t* hist_items, float* ts_scratch,
                  uint32_t* ranks, uint32_t* nonfinite_flag, hipStream_t s);
+/* exact ranks of many targets per user state from one scan (sbr_catalogue.hip).  A scan-user is a representation row rep_row[s]
+ * with the targets tgt_items[sptr[s] .. sptr[s + 1]), at most rank_targets_tmax(d) of them and at least one; su_user[s] indexes
+ * mask_ptr / mask_items, the sorted de-duplicated lists of items masked to f32::MIN (NULL: none).  ranks [sptr[num_su]] in target
+ * order.  Scratch: ts, pos [targets]; th, buckets [num_su][tmax]; tmin, tmin2, totals [num_su]. */
+uint32_t rank_targets_tmax(int d);
+void launch_rank_targets(const ModelView& m, const float* reps, const int* rep_row, const uint32_t* su_user, const uint32_t* sptr,
+                         uint32_t num_su, const uint32_t* tgt_items, const uint64_t* mask_ptr, const uint32_t* mask_items, float* ts,
+                         uint32_t* pos, float* th, float* tmin, float* tmin2, uint32_t* buckets, uint32_t* totals, uint32_t* ranks,
+                         uint32_t* nonfinite_flag, hipStream_t s);
 /* exact top-k of the catalogue per user (sbr_catalogue.hip): topk_gemm_kernel keeps per (user, item range) a sorted list of the
  * k best (score desc, id asc) in `lists` [num_users][groups][k] with its length in `lens` [num_users][groups]; topk_merge_kernel
  * merges a user's lists in LDS into out_items / out_scores [num_users][k] (padding: 0xFFFFFFFF / -inf).  excl_ptr / excl_items:

@@ -13,6 +13,7 @@ from .errors import EngineError, FittingError, PredictionError
 
 RECOMMEND_MAX_K = 1024  # SBR_RECOMMEND_MAX_K
 RECOMMEND_INCLUDE_HISTORY = 1  # SBR_RECOMMEND_INCLUDE_HISTORY
+RANK_INCLUDE_HISTORY = 1  # SBR_RANK_INCLUDE_HISTORY
 RECOMMEND_NO_ITEM = 0xFFFFFFFF  # item id of a padding entry (its score is -inf)
 
 
@@ -555,6 +556,47 @@ class Model:
         _check(self._L.sbr_recommend_reps(self._h, _ptr(reps), nu, int(k) & 0xFFFFFFFF, None if ep is None else _ptr(ep),
                                           None if ei is None else _ptr(ei), _ptr(items), _ptr(scores)))
         return items, scores
+
+    def rank_targets(self, user_ptr, item_ids, target_ptr, target_items, include_history: bool = False) -> np.ndarray:
+        """Exact ranks of every user's targets among the whole catalogue from one scan (sbr_rank_targets): user u's history is
+        item_ids[user_ptr[u]: user_ptr[u + 1]], its targets target_items[target_ptr[u]: target_ptr[u + 1]]; rank =
+        #{items whose masked score >= the target's}, the whole history masked to f32::MIN unless include_history.  One u32 per
+        target, in target order."""
+        up = np.ascontiguousarray(user_ptr, dtype=np.uint64)
+        it = np.ascontiguousarray(item_ids, dtype=np.uint32)
+        tp = np.ascontiguousarray(target_ptr, dtype=np.uint64)
+        ti = np.ascontiguousarray(target_items, dtype=np.uint32)
+        if len(tp) != len(up):
+            raise ValueError("one target range per user")
+        nu = max(len(up) - 1, 0)
+        ranks = np.zeros(max(ti.size, 1), dtype=np.uint32)
+        flags = RANK_INCLUDE_HISTORY if include_history else 0
+        _check(self._L.sbr_rank_targets(self._h, _ptr(up), _ptr(it), nu, _ptr(tp), _ptr(ti), flags, _ptr(ranks)))
+        return ranks[: ti.size]
+
+    def rank_targets_reps(self, reps, target_ptr, target_items, exclude=None) -> np.ndarray:
+        """As rank_targets, from representations [U, embedding_dim]; exclude: None or one sequence of masked item ids per
+        user."""
+        reps = np.ascontiguousarray(reps, dtype=np.float32).reshape(-1, self.dim)
+        nu = reps.shape[0]
+        tp = np.ascontiguousarray(target_ptr, dtype=np.uint64)
+        ti = np.ascontiguousarray(target_items, dtype=np.uint32)
+        if len(tp) != nu + 1:
+            raise ValueError("one target range per user")
+        ep = ei = None
+        if exclude is not None:
+            if len(exclude) != nu:
+                raise ValueError("one exclusion list per user")
+            lists = [np.asarray(e, dtype=np.uint32).ravel() for e in exclude]
+            ep = np.zeros(nu + 1, dtype=np.uint64)
+            ep[1:] = np.cumsum([x.size for x in lists])
+            ei = np.ascontiguousarray(np.concatenate(lists) if lists else np.zeros(0, np.uint32), dtype=np.uint32)
+            if ei.size == 0:
+                ei = np.zeros(1, dtype=np.uint32)
+        ranks = np.zeros(max(ti.size, 1), dtype=np.uint32)
+        _check(self._L.sbr_rank_targets_reps(self._h, _ptr(reps), nu, None if ep is None else _ptr(ep),
+                                             None if ei is None else _ptr(ei), _ptr(tp), _ptr(ti), _ptr(ranks)))
+        return ranks[: ti.size]
 
     def close(self):
         if getattr(self, "_h", None):

@@ -244,6 +244,13 @@ class _ImplicitSequenceModel:
             it = np.concatenate(seqs) if seqs else np.zeros(0, dtype=np.uint32)
         return self.params.recommend(up, it, k, include_history=not exclude_history)
 
+    def rank_targets(self, histories, targets, mask_history: bool = True):
+        """Exact catalogue ranks of each user's targets from one device scan (``evaluation.rank_targets``): one uint32 array
+        per user, in target order."""
+        from .evaluation import rank_targets
+
+        return rank_targets(self, histories, targets, mask_history=mask_history)
+
 
 class ImplicitLSTMModel(_ImplicitSequenceModel):
     """An LSTM-based sequence model for implicit feedback (lstm.rs:386-416)."""
