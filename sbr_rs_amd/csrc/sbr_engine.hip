@@ -386,14 +386,20 @@ struct SharedTable {
     }
 };
 
-/* Scratch of the prediction side (user_representation / mrr_score), kept for the life of the model: one device allocation that
- * only grows, carved per call — a call used to make and free ~25 device allocations (a quarter of mrr_score's wall time at
- * 8 192 users x 1e6 items went to the allocator and its implicit synchronisations). */
+/* Scratch of the prediction side (user_representation, mrr_score, recommend*, rank_targets*), kept for the life of the model: one
+ * device allocation that only grows, carved per launch — a call used to make and free ~25 device allocations (a quarter of
+ * mrr_score's wall time at 8 192 users x 1e6 items went to the allocator and its implicit synchronisations).  What a launch needs
+ * is not computed beside its takes but found by running them: measure(), the takes (which then only count), reserve(used), the
+ * same takes again (carve_arena). */
 struct DeviceArena {
     uint8_t* base = nullptr;
     size_t cap = 0, used = 0;
+    bool measuring = false;
+    bool overrun = false; /* a take since the last reserve went past cap (and got null): the call fails */
+    void measure() { used = 0; measuring = true; }
     sbr_status reserve(size_t need) {
         used = 0;
+        measuring = overrun = false;
         if (need <= cap) return SBR_OK;
         if (base) (void)hipFree(base);
         base = nullptr; cap = 0;
@@ -405,9 +411,11 @@ struct DeviceArena {
     static size_t padded(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
     template <typename T>
     T* take(size_t count) {
-        T* p = reinterpret_cast<T*>(base + used);
+        const size_t at = used;
         used += padded((count ? count : 1) * sizeof(T));
-        return p;
+        if (measuring) return nullptr;
+        if (used > cap) { overrun = true; return nullptr; }
+        return reinterpret_cast<T*>(base + at);
     }
     void release() { if (base) (void)hipFree(base); base = nullptr; cap = used = 0; }
 };
@@ -3345,35 +3353,49 @@ sbr_status sbr_fit_debug_fetch(sbr_fit_plan* p, int32_t which, void* host_out, u
  * ------------------------------------------------------------------------------------------- */
 namespace {
 
-/* Runs the recurrent forward for a batch of histories; the hidden states are left in *H_out — memory of the model's eval arena,
- * valid until the next arena.reserve — and rep_row[i] = packed row of the final state of history i.  `extra_bytes`: what the
- * caller will carve from the arena afterwards (the rank kernels' arrays), reserved in the same allocation. */
-size_t arena_bytes_forward(const sbr_model* m, uint64_t R, uint64_t B, uint64_t noff) {
-    const uint64_t d = (uint64_t)m->d;
-    size_t n = 4 * DeviceArena::padded(R * 4) + DeviceArena::padded(noff * 4) + DeviceArena::padded(B * 4) + DeviceArena::padded(R * d * 4);
-    if (m->ng) n += 2 * DeviceArena::padded(R * d * 4) + DeviceArena::padded(R * d * 16);
-    return n + 4096;
+using Carve = std::function<void(DeviceArena&)>; /* a run of takes */
+
+/* Reserves the model's eval arena for one launch and carves it: `carve` — the one place that says which buffers the launch has —
+ * runs once measuring, the arena is reserved to what that took, and it runs again for real. */
+sbr_status carve_arena(sbr_model* m, const Carve& carve) {
+    DeviceArena& ar = m->eval_arena;
+    ar.measure();
+    carve(ar);
+    HIPCHK(hipStreamSynchronize(m->stream)); /* nothing of an earlier call may still read the arena */
+    SBRCHK(ar.reserve(ar.used));
+    carve(ar);
+    return ar.overrun ? SBR_ERR_OUT_OF_MEMORY : SBR_OK;
 }
 
+/* device buffers of the recurrent forward over the packed sequences `pk` */
+struct ForwardBufs {
+    DevicePacked dp;
+    float* H = nullptr;
+    WorkBuffers wb;
+    void carve(DeviceArena& ar, const sbr_model* m, const Packed& pk) {
+        const size_t R = (size_t)pk.R, d = (size_t)m->d;
+        dp.in_idx = ar.take<uint32_t>(R); dp.out_idx = ar.take<uint32_t>(R); dp.ctr = ar.take<uint32_t>(R);
+        dp.prev_row = ar.take<int>(R); dp.off = ar.take<int>(pk.off.size()); dp.steps = ar.take<int>((size_t)pk.B);
+        H = ar.take<float>(R * d);
+        if (m->ng) {
+            wb.v.C = ar.take<float>(R * d);
+            wb.v.G = ar.take<float>(R * d * 4);
+            wb.v.X = ar.take<float>(R * d);
+        }
+    }
+};
+
+/* Runs the recurrent forward for a batch of histories; the hidden states are left in *H_out — memory of the model's eval arena,
+ * valid until the next carve_arena — and rep_row[i] = packed row of the final state of history i.  `carve_epilogue`: what the
+ * caller uses from the arena afterwards (the scan kernels' arrays), carved behind the forward pass's in the same allocation. */
 sbr_status forward_histories(sbr_model* m, const std::vector<const uint32_t*>& first, const std::vector<int>& nsteps,
-                             float** H_out, std::vector<int>* rep_row, size_t extra_bytes) {
+                             const Carve& carve_epilogue, float** H_out, std::vector<int>* rep_row) {
     Packed pk;
     pack_sequences(first, nsteps, false, nullptr, (int)m->hp.max_sequence_length, &pk);
-    DeviceArena& ar = m->eval_arena;
-    HIPCHK(hipStreamSynchronize(m->stream)); /* nothing of an earlier call may still read the arena */
-    SBRCHK(ar.reserve(arena_bytes_forward(m, (uint64_t)pk.R, (uint64_t)pk.B, pk.off.size()) + extra_bytes));
-    const uint64_t R = (uint64_t)pk.R, d = (uint64_t)m->d;
-    DevicePacked dp;
-    dp.in_idx = ar.take<uint32_t>(R); dp.out_idx = ar.take<uint32_t>(R); dp.ctr = ar.take<uint32_t>(R);
-    dp.prev_row = ar.take<int>(R); dp.off = ar.take<int>(pk.off.size()); dp.steps = ar.take<int>((size_t)pk.B);
-    float* H = ar.take<float>(R * d);
-    WorkBuffers wb;
-    wb.v.fold_max_tiles = SBR_FOLD_MAX_TILES_DEFAULT;
-    if (m->ng) {
-        wb.v.C = ar.take<float>(R * d);
-        wb.v.G = ar.take<float>(R * d * 4);
-        wb.v.X = ar.take<float>(R * d);
-    }
+    ForwardBufs fb;
+    fb.wb.v.fold_max_tiles = SBR_FOLD_MAX_TILES_DEFAULT;
+    SBRCHK(carve_arena(m, [&](DeviceArena& ar) { fb.carve(ar, m, pk); carve_epilogue(ar); }));
+    const DevicePacked& dp = fb.dp;
     HIPCHK(hipMemcpyAsync(dp.in_idx, pk.in_idx.data(), (size_t)pk.R * 4, hipMemcpyHostToDevice, m->stream));
     HIPCHK(hipMemcpyAsync(dp.prev_row, pk.prev_row.data(), (size_t)pk.R * 4, hipMemcpyHostToDevice, m->stream));
     HIPCHK(hipMemcpyAsync(dp.off, pk.off.data(), pk.off.size() * 4, hipMemcpyHostToDevice, m->stream));
@@ -3384,13 +3406,13 @@ sbr_status forward_histories(sbr_model* m, const std::vector<const uint32_t*>& f
     mv.in_idx = dp.in_idx; mv.out_idx = dp.out_idx; mv.ctr = dp.ctr;
     {
         ScopedTimer t(m, SBR_K_RECURRENT_FWD, m->ng && m->d > 128 ? (uint64_t)pk.Tm : 1);
-        sbr::launch_recurrent_forward(m->mv, mv, H, wb.v, pk.Tm, pk.off.data(), m->stream);
+        sbr::launch_recurrent_forward(m->mv, mv, fb.H, fb.wb.v, pk.Tm, pk.off.data(), m->stream);
     }
     /* the host vectors of `pk` are read by the asynchronous copies above: drain them before pk goes out of scope */
     HIPCHK(hipStreamSynchronize(m->stream));
     rep_row->assign(first.size(), 0);
     for (int b = 0; b < pk.B; ++b) (*rep_row)[pk.order[b]] = pk.off[pk.steps[b] - 1] + b;
-    *H_out = H;
+    *H_out = fb.H;
     return SBR_OK;
 }
 
@@ -3452,21 +3474,143 @@ void prepare_users(const std::vector<const uint32_t*>& items, const std::vector<
     }
 }
 
+/* A CSR argument of a call (histories, exclusion lists, target lists): ptr[0 .. n] non-decreasing and every id of
+ * ids[from, ptr[n]) below num_items, from = 0 (from_zero) or ptr[0]; ids may be null only where that range is empty. */
+sbr_status check_csr(const sbr_model* m, const uint64_t* ptr, uint64_t n, const uint32_t* ids, bool from_zero) {
+    for (uint64_t u = 0; u < n; ++u)
+        if (ptr[u + 1] < ptr[u]) return SBR_ERR_INVALID_ARGUMENT;
+    const uint64_t from = from_zero ? 0 : ptr[0];
+    if (ptr[n] > from && !ids) return SBR_ERR_INVALID_ARGUMENT;
+    for (uint64_t i = from; i < ptr[n]; ++i)
+        if (ids[i] >= m->hp.num_items) return SBR_ERR_INVALID_ARGUMENT;
+    return SBR_OK;
+}
+
+/* Where a call's user representations come from: the histories ptr / items (the recurrent forward runs), or the rows `reps`
+ * ([users, embedding_dim]) of the caller, ptr / items then being the exclusion lists (ptr null: none). */
+struct RepSource {
+    const uint64_t* ptr;
+    const uint32_t* items;
+    const float* reps;  /* null: from histories */
+    uint64_t held_out;  /* histories: this many items at the end of each are not part of it (mrr_score: the test item) */
+    bool lists;         /* whether the sorted, de-duplicated lists of ptr / items are wanted (with reps: always) */
+};
+
+/* The representations of a chunk's users: user i's is row rep_row[i] of H (eval arena, valid until the next carve_arena);
+ * b.list_ptr / b.list_items are the users' sorted, de-duplicated lists (both empty: none). */
+struct UserReps {
+    float* H = nullptr;
+    std::vector<int> rep_row;
+    UserBatch b;
+    std::vector<float> gathered; /* caller's rows of users that are not consecutive, read by an asynchronous copy */
+};
+
+/* Fills *out for `users` of `s`; `carve_epilogue` as forward_histories' (it may read out->b, which is complete by then).  The
+ * uploads are asynchronous: *out lives until the stream is synchronised. */
+sbr_status user_reps(sbr_model* m, const RepSource& s, const std::vector<uint64_t>& users, const Carve& carve_epilogue, UserReps* out) {
+    const size_t nu = users.size(), d = (size_t)m->d, dl = (size_t)m->dl;
+    const uint64_t T = m->hp.max_sequence_length;
+    if (s.ptr) {
+        std::vector<const uint32_t*> list(nu);
+        std::vector<uint64_t> n(nu);
+        for (size_t i = 0; i < nu; ++i) {
+            list[i] = s.items ? s.items + s.ptr[users[i]] : nullptr;
+            n[i] = s.ptr[users[i] + 1] - s.ptr[users[i]] - s.held_out;
+        }
+        /* with reps: the caller's lists, sorted and de-duplicated (their state windows go unused) */
+        prepare_users(list, n, T, s.lists, &out->b);
+    }
+    if (!s.reps) return forward_histories(m, out->b.first, out->b.nsteps, carve_epilogue, &out->H, &out->rep_row);
+    SBRCHK(carve_arena(m, [&](DeviceArena& ar) { out->H = ar.take<float>(nu * d); carve_epilogue(ar); }));
+    const float* rows = s.reps + users[0] * dl;
+    if (users[nu - 1] - users[0] + 1 != nu) {
+        out->gathered.resize(nu * dl);
+        for (size_t i = 0; i < nu; ++i) std::memcpy(out->gathered.data() + i * dl, s.reps + users[i] * dl, dl * 4);
+        rows = out->gathered.data();
+    }
+    /* padded to the storage width: the columns past embedding_dim are zero, as in the model's own states */
+    HIPCHK(hipMemsetAsync(out->H, 0, nu * d * 4, m->stream));
+    HIPCHK(hipMemcpy2DAsync(out->H, d * 4, rows, dl * 4, dl * 4, nu, hipMemcpyHostToDevice, m->stream));
+    out->rep_row.resize(nu);
+    for (size_t i = 0; i < nu; ++i) out->rep_row[i] = (int)i;
+    return SBR_OK;
+}
+
+/* Scan units per launch (a unit: a user, or a scan-user of rank_targets): the scan GEMM streams the item table once per 128 units
+ * whatever the launch size, but every launch has its ramp and tail — mrr_score at 8 192 users x 1e6 items, d = 128: 104 / 108 /
+ * 109 / 112 TFLOP/s at 1 024 / 2 048 / 4 096 / 8 192 users per launch */
+constexpr size_t eval_units_cap = 8192;
+/* the forward pass's scratch is (users x history steps) rows of 6d floats: bound a launch by rows as well */
+constexpr size_t eval_rows_cap = (size_t)1 << 22;
+
+/* One launch's share [c0, c1) of a call's scan units: its distinct users, ascending, and each unit's index into them */
+struct Chunk {
+    size_t c0 = 0, c1 = 0;
+    std::vector<uint64_t> users;
+    std::vector<uint32_t> lu;
+};
+
+/* Moves *ch to the chunk after it (a fresh Chunk: to the first); false when the units are used up.  unit_user[i] = user of unit
+ * i, units of one user adjacent.  A chunk ends at unit_cap units and, where the forward pass runs, before the user whose rows take
+ * it past eval_rows_cap unless it is the chunk's first; a user cut by a chunk's end is forwarded again in the next one. */
+bool next_chunk(const std::vector<uint64_t>& unit_user, size_t unit_cap, const RepSource& s, uint64_t T, Chunk* ch) {
+    const size_t c0 = ch->c1;
+    if (c0 >= unit_user.size()) return false;
+    ch->users.clear();
+    ch->lu.clear();
+    size_t c1 = c0, rows = 0;
+    for (; c1 < unit_user.size() && c1 - c0 < unit_cap; ++c1) {
+        const uint64_t u = unit_user[c1];
+        if (c1 == c0 || u != unit_user[c1 - 1]) {
+            if (!s.reps) {
+                rows += (size_t)std::max<uint64_t>(1, std::min<uint64_t>(s.ptr[u + 1] - s.ptr[u] - s.held_out, T));
+                if (rows > eval_rows_cap && c1 > c0) break;
+            }
+            ch->users.push_back(u);
+        }
+        ch->lu.push_back((uint32_t)(ch->users.size() - 1));
+    }
+    ch->c0 = c0;
+    ch->c1 = c1;
+    return true;
+}
+
+struct CopyOut { void* host; const void* device; size_t bytes; }; /* host null: not wanted */
+
+/* The tail of every catalogue scan: `launch` (its `launches` kernels, timed as SBR_K_RANK) with the non-finite-score flag cleared
+ * before it, then — the stream drained, so the caller's host vectors have been read by their asynchronous copies — the flag
+ * and, if it is clear, the results. */
+sbr_status scan_launch(sbr_model* m, uint64_t launches, uint32_t* d_flag, const std::function<void()>& launch,
+                       std::initializer_list<CopyOut> outs) {
+    HIPCHK(hipMemsetAsync(d_flag, 0, 4, m->stream));
+    {
+        ScopedTimer t(m, SBR_K_RANK, launches);
+        launch();
+    }
+    uint32_t flag = 0;
+    HIPCHK(hipStreamSynchronize(m->stream));
+    HIPCHK(hipMemcpy(&flag, d_flag, 4, hipMemcpyDeviceToHost));
+    if (flag) return SBR_ERR_INVALID_PREDICTION; /* predict fails the call on a non-finite score */
+    for (const CopyOut& o : outs)
+        if (o.host) HIPCHK(hipMemcpy(o.host, o.device, o.bytes, hipMemcpyDeviceToHost));
+    return SBR_OK;
+}
+
 }  // namespace
 
 sbr_status sbr_user_representation(sbr_model* m, const uint32_t* item_ids, uint64_t n, float* out_dim) {
     if (!m || !out_dim || (n && !item_ids)) return SBR_ERR_INVALID_ARGUMENT;
     std::lock_guard<std::mutex> lock(m->mu);
     SBRCHK(ensure_device(m));
-    std::vector<const uint32_t*> first(1);
-    std::vector<int> nsteps(1);
-    state_window(item_ids, n, m->hp.max_sequence_length, &first[0], &nsteps[0]);
-    for (int t = 0; t < nsteps[0]; ++t)
-        if (first[0][t] >= m->hp.num_items) return SBR_ERR_INVALID_ARGUMENT;
-    float* H = nullptr;
-    std::vector<int> rep_row;
-    SBRCHK(forward_histories(m, first, nsteps, &H, &rep_row, 0));
-    hipError_t e = hipMemcpy(out_dim, H + (size_t)rep_row[0] * m->d, (size_t)m->dl * 4, hipMemcpyDeviceToHost);
+    const uint32_t* first = nullptr;
+    int nsteps = 0;
+    state_window(item_ids, n, m->hp.max_sequence_length, &first, &nsteps);
+    for (int t = 0; t < nsteps; ++t)
+        if (first[t] >= m->hp.num_items) return SBR_ERR_INVALID_ARGUMENT;
+    const uint64_t ptr[2] = {0, n};
+    UserReps ur;
+    SBRCHK(user_reps(m, RepSource{ptr, item_ids, nullptr, 0, false}, std::vector<uint64_t>(1, 0), [](DeviceArena&) {}, &ur));
+    hipError_t e = hipMemcpy(out_dim, ur.H + (size_t)ur.rep_row[0] * m->d, (size_t)m->dl * 4, hipMemcpyDeviceToHost);
     return e == hipSuccess ? SBR_OK : SBR_ERR_HIP;
 }
 
@@ -3495,85 +3639,58 @@ sbr_status sbr_predict(sbr_model* m, const float* user_dim, const uint32_t* item
     return SBR_OK;
 }
 
+namespace {
+
+/* device buffers of launch_rank over nu users with nhist mask entries */
+struct MrrBufs {
+    int* rep;
+    uint32_t *test, *tih, *hist, *ranks, *flag;
+    float* ts;
+    uint64_t* hptr;
+    void carve(DeviceArena& ar, size_t nu, size_t nhist) {
+        rep = ar.take<int>(nu);
+        test = ar.take<uint32_t>(nu); tih = ar.take<uint32_t>(nu); hist = ar.take<uint32_t>(nhist);
+        ranks = ar.take<uint32_t>(nu); flag = ar.take<uint32_t>(1);
+        ts = ar.take<float>(nu);
+        hptr = ar.take<uint64_t>(nu + 1);
+    }
+};
+
+}  // namespace
+
 sbr_status sbr_mrr_score(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users,
                          float* out_mrr, uint32_t* out_ranks, uint64_t* out_num_ranked) {
     if (!m || !user_ptr || !out_mrr) return SBR_ERR_INVALID_ARGUMENT;
     std::lock_guard<std::mutex> lock(m->mu);
     SBRCHK(ensure_device(m));
-    const uint64_t T = m->hp.max_sequence_length;
-    for (uint64_t u = 0; u < num_users; ++u)
-        if (user_ptr[u + 1] < user_ptr[u]) return SBR_ERR_INVALID_ARGUMENT; /* pointers must be non-decreasing */
-    const uint64_t nnz = user_ptr[num_users];
-    if (nnz && !item_ids) return SBR_ERR_INVALID_ARGUMENT;
-    for (uint64_t i = 0; i < nnz; ++i)
-        if (item_ids[i] >= m->hp.num_items) return SBR_ERR_INVALID_ARGUMENT;
+    SBRCHK(check_csr(m, user_ptr, num_users, item_ids, true));
     std::vector<uint64_t> users; /* users with >= 2 interactions (evaluation.rs:20) */
     for (uint64_t u = 0; u < num_users; ++u)
         if (user_ptr[u + 1] - user_ptr[u] >= 2) users.push_back(u);
     if (out_num_ranked) *out_num_ranked = users.size();
     std::vector<uint32_t> ranks(users.size(), 0);
-    /* users per scoring launch: the rank GEMM streams the item table once per 128 users whatever the launch size, but every
-     * launch has its ramp and tail — 8 192 users x 1e6 items at d = 128: 104 / 108 / 109 / 112 TFLOP/s at 1 024 / 2 048 /
-     * 4 096 / 8 192 users per launch */
-    constexpr size_t EVAL_B = 8192;
-    /* the forward pass's scratch is (users x history steps) rows of 6d floats: bound a launch by rows as well */
-    const size_t eval_rows_cap = (size_t)1 << 22;
-    for (size_t c0 = 0, c1 = 0; c0 < users.size(); c0 = c1) {
-        size_t rows = 0;
-        for (c1 = c0; c1 < users.size() && c1 - c0 < EVAL_B; ++c1) {
-            const uint64_t nh = user_ptr[users[c1] + 1] - user_ptr[users[c1]] - 1;
-            rows += (size_t)std::min<uint64_t>(nh, T);
-            if (rows > eval_rows_cap && c1 > c0) break;
-        }
-        const size_t nu = c1 - c0;
-        std::vector<const uint32_t*> hist(nu);
-        std::vector<uint64_t> nh(nu);
+    /* train_items = all but last (evaluation.rs:24); ALL history items of a user are masked (evaluation.rs:30-32) */
+    const RepSource s{user_ptr, item_ids, nullptr, 1, true};
+    for (Chunk ch; next_chunk(users, eval_units_cap, s, m->hp.max_sequence_length, &ch);) {
+        const size_t nu = ch.users.size();
+        UserReps ur;
+        MrrBufs mb;
+        SBRCHK(user_reps(m, s, ch.users, [&](DeviceArena& ar) { mb.carve(ar, nu, ur.b.list_items.size()); }, &ur));
+        const std::vector<uint64_t>& hist_ptr = ur.b.list_ptr;
+        const std::vector<uint32_t>& hist_items = ur.b.list_items;
         std::vector<uint32_t> test_item(nu), test_in_hist(nu);
-        for (size_t i = 0; i < nu; ++i) { /* train_items = all but last (evaluation.rs:24) */
-            const uint64_t u = users[c0 + i];
-            hist[i] = item_ids + user_ptr[u];
-            nh[i] = user_ptr[u + 1] - user_ptr[u] - 1;
-            test_item[i] = hist[i][nh[i]];
-        }
-        /* ALL history items of a user are masked (evaluation.rs:30-32) */
-        UserBatch b;
-        prepare_users(hist, nh, T, true, &b);
-        const std::vector<uint64_t>& hist_ptr = b.list_ptr;
-        const std::vector<uint32_t>& hist_items = b.list_items;
-        for (size_t i = 0; i < nu; ++i)
+        for (size_t i = 0; i < nu; ++i) {
+            test_item[i] = item_ids[user_ptr[ch.users[i] + 1] - 1];
             test_in_hist[i] = std::binary_search(hist_items.data() + hist_ptr[i], hist_items.data() + hist_ptr[i + 1], test_item[i]) ? 1u : 0u;
-        float* H = nullptr;
-        std::vector<int> rep_row;
-        const size_t rank_bytes = 6 * DeviceArena::padded(nu * 4) + DeviceArena::padded(hist_items.size() * 4 + 4) + DeviceArena::padded(4) +
-                                  DeviceArena::padded((nu + 1) * 8);
-        SBRCHK(forward_histories(m, b.first, b.nsteps, &H, &rep_row, rank_bytes));
-        DeviceArena& ar = m->eval_arena;
-        int* d_rep = ar.take<int>(nu);
-        uint32_t *d_test = ar.take<uint32_t>(nu), *d_tih = ar.take<uint32_t>(nu), *d_hist = ar.take<uint32_t>(hist_items.size()),
-                 *d_ranks = ar.take<uint32_t>(nu), *d_flag = ar.take<uint32_t>(1);
-        float* d_ts = ar.take<float>(nu);
-        uint64_t* d_hptr = ar.take<uint64_t>(nu + 1);
-        sbr_status st = SBR_OK;
-        {
-            hipMemcpyAsync(d_rep, rep_row.data(), nu * 4, hipMemcpyHostToDevice, m->stream);
-            hipMemcpyAsync(d_test, test_item.data(), nu * 4, hipMemcpyHostToDevice, m->stream);
-            hipMemcpyAsync(d_tih, test_in_hist.data(), nu * 4, hipMemcpyHostToDevice, m->stream);
-            if (!hist_items.empty()) hipMemcpyAsync(d_hist, hist_items.data(), hist_items.size() * 4, hipMemcpyHostToDevice, m->stream);
-            hipMemcpyAsync(d_hptr, hist_ptr.data(), (nu + 1) * 8, hipMemcpyHostToDevice, m->stream);
-            hipMemsetAsync(d_flag, 0, 4, m->stream);
-            {
-                ScopedTimer t(m, SBR_K_RANK, 1);
-                sbr::launch_rank(m->mv, H, d_rep, (uint32_t)nu, d_test, d_tih, d_hptr, d_hist, d_ts, d_ranks, d_flag, m->stream);
-            }
-            uint32_t flag = 0;
-            if (hipStreamSynchronize(m->stream) != hipSuccess ||
-                hipMemcpy(ranks.data() + c0, d_ranks, nu * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-                hipMemcpy(&flag, d_flag, 4, hipMemcpyDeviceToHost) != hipSuccess)
-                st = SBR_ERR_HIP;
-            else if (flag)
-                st = SBR_ERR_INVALID_PREDICTION; /* predict fails the call on a non-finite score */
         }
-        if (st != SBR_OK) return st;
+        HIPCHK(hipMemcpyAsync(mb.rep, ur.rep_row.data(), nu * 4, hipMemcpyHostToDevice, m->stream));
+        HIPCHK(hipMemcpyAsync(mb.test, test_item.data(), nu * 4, hipMemcpyHostToDevice, m->stream));
+        HIPCHK(hipMemcpyAsync(mb.tih, test_in_hist.data(), nu * 4, hipMemcpyHostToDevice, m->stream));
+        if (!hist_items.empty()) HIPCHK(hipMemcpyAsync(mb.hist, hist_items.data(), hist_items.size() * 4, hipMemcpyHostToDevice, m->stream));
+        HIPCHK(hipMemcpyAsync(mb.hptr, hist_ptr.data(), (nu + 1) * 8, hipMemcpyHostToDevice, m->stream));
+        SBRCHK(scan_launch(m, 1, mb.flag, [&] {
+            sbr::launch_rank(m->mv, ur.H, mb.rep, (uint32_t)nu, mb.test, mb.tih, mb.hptr, mb.hist, mb.ts, mb.ranks, mb.flag, m->stream);
+        }, {{ranks.data() + ch.c0, mb.ranks, nu * 4}}));
     }
     float sum = 0.0f; /* evaluation.rs:47 — sequential f32 sum in user order */
     for (size_t i = 0; i < ranks.size(); ++i) sum += 1.0f / (float)ranks[i];
@@ -3587,12 +3704,12 @@ sbr_status sbr_mrr_score(sbr_model* m, const uint64_t* user_ptr, const uint32_t*
  * ------------------------------------------------------------------------------------------- */
 namespace {
 
-/* users per top-k launch: as mrr_score's EVAL_B, and few enough that the per-(user, item range) lists stay within 256 MB.  With
+/* users per top-k launch: eval_units_cap, and few enough that the per-(user, item range) lists stay within 256 MB.  With
  * ranges * k <= TK_MERGE_MAX the lists of 8 192 users are at most 512 MB, so the loop halves at most once: 8 192 users while
  * ranges * k <= 4 096 (every k <= 256: at most 16 ranges are wanted for 64 user tiles), 4 096 users above that (possible from
  * k = 257 on; k = 1 024 from 5 ranges on) or where SBR_CATALOGUE_GROUPS forces more ranges. */
 size_t recommend_users_cap(const sbr_model* m, uint32_t k) {
-    size_t cap = 8192;
+    size_t cap = eval_units_cap;
     for (;;) {
         uint32_t per = 0;
         const uint32_t g = sbr::recommend_groups((uint32_t)cap, (uint32_t)m->hp.num_items, k, &per);
@@ -3601,48 +3718,55 @@ size_t recommend_users_cap(const sbr_model* m, uint32_t k) {
     }
 }
 
-/* arena bytes of one top-k launch over nu users with nexcl exclusion entries */
-size_t recommend_bytes(const sbr_model* m, size_t nu, size_t nexcl, uint32_t k) {
-    uint32_t per = 0;
-    const size_t g = sbr::recommend_groups((uint32_t)nu, (uint32_t)m->hp.num_items, k, &per);
-    return DeviceArena::padded(nu * 4) + DeviceArena::padded((nu + 1) * 8) + DeviceArena::padded(nexcl * 4 + 4) +
-           DeviceArena::padded(nu * g * k * 8) + DeviceArena::padded(nu * g * 4) + 2 * DeviceArena::padded(nu * k * 4) + DeviceArena::padded(4);
+/* device buffers of launch_recommend over nu users with nexcl exclusion entries */
+struct TopkBufs {
+    int* rep;
+    uint64_t* eptr;
+    uint32_t *excl, *lens, *items, *flag;
+    uint2* lists;
+    float* scores;
+    void carve(DeviceArena& ar, const sbr_model* m, size_t nu, size_t nexcl, uint32_t k) {
+        uint32_t per = 0;
+        const size_t g = sbr::recommend_groups((uint32_t)nu, (uint32_t)m->hp.num_items, k, &per);
+        rep = ar.take<int>(nu);
+        eptr = ar.take<uint64_t>(nu + 1);
+        excl = ar.take<uint32_t>(nexcl + 1);
+        lists = ar.take<uint2>(nu * g * k);
+        lens = ar.take<uint32_t>(nu * g);
+        items = ar.take<uint32_t>(nu * k);
+        scores = ar.take<float>(nu * k);
+        flag = ar.take<uint32_t>(1);
+    }
+};
+
+/* top-k of every user of `s`, in chunks; results to out_items / out_scores (host, num_users x k; scores optional) */
+sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, uint32_t k, uint32_t* out_items, float* out_scores) {
+    std::vector<uint64_t> users(num_users);
+    for (uint64_t u = 0; u < num_users; ++u) users[u] = u;
+    const size_t cap = recommend_users_cap(m, k);
+    for (Chunk ch; next_chunk(users, cap, s, m->hp.max_sequence_length, &ch);) {
+        const size_t nu = ch.users.size();
+        UserReps ur; /* its lists: what is excluded (list_ptr empty: nothing) */
+        TopkBufs tb;
+        SBRCHK(user_reps(m, s, ch.users, [&](DeviceArena& ar) { tb.carve(ar, m, nu, ur.b.list_items.size(), k); }, &ur));
+        const bool excl = !ur.b.list_ptr.empty();
+        HIPCHK(hipMemcpyAsync(tb.rep, ur.rep_row.data(), nu * 4, hipMemcpyHostToDevice, m->stream));
+        if (excl) {
+            HIPCHK(hipMemcpyAsync(tb.eptr, ur.b.list_ptr.data(), (nu + 1) * 8, hipMemcpyHostToDevice, m->stream));
+            if (!ur.b.list_items.empty())
+                HIPCHK(hipMemcpyAsync(tb.excl, ur.b.list_items.data(), ur.b.list_items.size() * 4, hipMemcpyHostToDevice, m->stream));
+        }
+        SBRCHK(scan_launch(m, 2, tb.flag, [&] {
+            sbr::launch_recommend(m->mv, ur.H, tb.rep, (uint32_t)nu, excl ? tb.eptr : nullptr, tb.excl, k, tb.lists, tb.lens, tb.items,
+                                  out_scores ? tb.scores : nullptr, tb.flag, m->stream);
+        }, {{out_items + ch.c0 * k, tb.items, nu * k * 4}, {out_scores ? out_scores + ch.c0 * k : nullptr, tb.scores, nu * k * 4}}));
+    }
+    return SBR_OK;
 }
 
-/* top-k of nu users whose representations are rows rep_row[i] of H (eval arena, reserved with recommend_bytes); excl_ptr empty:
- * no exclusion, else sorted de-duplicated per-user lists.  Results go to out_items / out_scores (host, nu x k; scores optional). */
-sbr_status recommend_launch(sbr_model* m, const float* H, const std::vector<int>& rep_row, size_t nu, const std::vector<uint64_t>& excl_ptr,
-                            const std::vector<uint32_t>& excl_items, uint32_t k, uint32_t* out_items, float* out_scores) {
-    DeviceArena& ar = m->eval_arena;
-    uint32_t per = 0;
-    const size_t g = sbr::recommend_groups((uint32_t)nu, (uint32_t)m->hp.num_items, k, &per);
-    int* d_rep = ar.take<int>(nu);
-    uint64_t* d_eptr = ar.take<uint64_t>(nu + 1);
-    uint32_t* d_excl = ar.take<uint32_t>(excl_items.size() + 1);
-    uint2* d_lists = ar.take<uint2>(nu * g * k);
-    uint32_t* d_lens = ar.take<uint32_t>(nu * g);
-    uint32_t* d_items = ar.take<uint32_t>(nu * k);
-    float* d_scores = ar.take<float>(nu * k);
-    uint32_t* d_flag = ar.take<uint32_t>(1);
-    const bool excl = !excl_ptr.empty();
-    HIPCHK(hipMemcpyAsync(d_rep, rep_row.data(), nu * 4, hipMemcpyHostToDevice, m->stream));
-    if (excl) {
-        HIPCHK(hipMemcpyAsync(d_eptr, excl_ptr.data(), (nu + 1) * 8, hipMemcpyHostToDevice, m->stream));
-        if (!excl_items.empty()) HIPCHK(hipMemcpyAsync(d_excl, excl_items.data(), excl_items.size() * 4, hipMemcpyHostToDevice, m->stream));
-    }
-    HIPCHK(hipMemsetAsync(d_flag, 0, 4, m->stream));
-    {
-        ScopedTimer t(m, SBR_K_RANK, 2);
-        sbr::launch_recommend(m->mv, H, d_rep, (uint32_t)nu, excl ? d_eptr : nullptr, d_excl, k, d_lists, d_lens, d_items,
-                              out_scores ? d_scores : nullptr, d_flag, m->stream);
-    }
-    uint32_t flag = 0;
-    HIPCHK(hipStreamSynchronize(m->stream)); /* the host vectors above are read by the asynchronous copies */
-    HIPCHK(hipMemcpy(&flag, d_flag, 4, hipMemcpyDeviceToHost));
-    if (flag) return SBR_ERR_INVALID_PREDICTION; /* predict fails the call on a non-finite score */
-    HIPCHK(hipMemcpy(out_items, d_items, nu * k * 4, hipMemcpyDeviceToHost));
-    if (out_scores) HIPCHK(hipMemcpy(out_scores, d_scores, nu * k * 4, hipMemcpyDeviceToHost));
-    return SBR_OK;
+/* the exclusion-list arguments of the *_reps calls: both or neither, or lists that are all empty and no items */
+bool excl_args_ok(const uint64_t* excl_ptr, const uint32_t* excl_items, uint64_t num_users) {
+    return (excl_ptr == nullptr) == (excl_items == nullptr) || (excl_ptr && excl_ptr[num_users] == excl_ptr[0]);
 }
 
 }  // namespace
@@ -3653,79 +3777,20 @@ sbr_status sbr_recommend(sbr_model* m, const uint64_t* user_ptr, const uint32_t*
     if (k < 1 || k > SBR_RECOMMEND_MAX_K || (flags & ~SBR_RECOMMEND_INCLUDE_HISTORY)) return SBR_ERR_INVALID_ARGUMENT;
     std::lock_guard<std::mutex> lock(m->mu);
     SBRCHK(ensure_device(m));
-    const uint64_t T = m->hp.max_sequence_length;
-    for (uint64_t u = 0; u < num_users; ++u)
-        if (user_ptr[u + 1] < user_ptr[u]) return SBR_ERR_INVALID_ARGUMENT; /* pointers must be non-decreasing */
-    const uint64_t nnz = user_ptr[num_users] - user_ptr[0];
-    if (nnz && !item_ids) return SBR_ERR_INVALID_ARGUMENT;
-    for (uint64_t i = user_ptr[0]; i < user_ptr[num_users]; ++i)
-        if (item_ids[i] >= m->hp.num_items) return SBR_ERR_INVALID_ARGUMENT;
-    const bool exclude = !(flags & SBR_RECOMMEND_INCLUDE_HISTORY);
-    const size_t cap = recommend_users_cap(m, k);
-    const size_t eval_rows_cap = (size_t)1 << 22; /* as mrr_score: the forward pass's scratch is (users x steps) rows */
-    for (size_t c0 = 0, c1 = 0; c0 < num_users; c0 = c1) {
-        size_t rows = 0;
-        for (c1 = c0; c1 < num_users && c1 - c0 < cap; ++c1) {
-            rows += (size_t)std::max<uint64_t>(1, std::min<uint64_t>(user_ptr[c1 + 1] - user_ptr[c1], T));
-            if (rows > eval_rows_cap && c1 > c0) break;
-        }
-        const size_t nu = c1 - c0;
-        std::vector<const uint32_t*> hist(nu);
-        std::vector<uint64_t> n(nu);
-        for (size_t i = 0; i < nu; ++i) {
-            hist[i] = item_ids ? item_ids + user_ptr[c0 + i] : nullptr;
-            n[i] = user_ptr[c0 + i + 1] - user_ptr[c0 + i];
-        }
-        /* the WHOLE history is masked (evaluation.rs:30-32) */
-        UserBatch b;
-        prepare_users(hist, n, T, exclude, &b);
-        float* H = nullptr;
-        std::vector<int> rep_row;
-        SBRCHK(forward_histories(m, b.first, b.nsteps, &H, &rep_row, recommend_bytes(m, nu, b.list_items.size(), k)));
-        SBRCHK(recommend_launch(m, H, rep_row, nu, b.list_ptr, b.list_items, k, out_items + c0 * k, out_scores ? out_scores + c0 * k : nullptr));
-    }
-    return SBR_OK;
+    SBRCHK(check_csr(m, user_ptr, num_users, item_ids, false));
+    /* the WHOLE history is masked (evaluation.rs:30-32) */
+    return recommend_scan(m, RepSource{user_ptr, item_ids, nullptr, 0, !(flags & SBR_RECOMMEND_INCLUDE_HISTORY)}, num_users, k, out_items, out_scores);
 }
 
 sbr_status sbr_recommend_reps(sbr_model* m, const float* reps, uint64_t num_users, uint32_t k, const uint64_t* excl_ptr,
                               const uint32_t* excl_items, uint32_t* out_items, float* out_scores) {
     if (!m || (num_users && (!reps || !out_items))) return SBR_ERR_INVALID_ARGUMENT;
     if (k < 1 || k > SBR_RECOMMEND_MAX_K) return SBR_ERR_INVALID_ARGUMENT;
-    if ((excl_ptr == nullptr) != (excl_items == nullptr) && !(excl_ptr && excl_ptr[num_users] == excl_ptr[0])) return SBR_ERR_INVALID_ARGUMENT;
+    if (!excl_args_ok(excl_ptr, excl_items, num_users)) return SBR_ERR_INVALID_ARGUMENT;
     std::lock_guard<std::mutex> lock(m->mu);
     SBRCHK(ensure_device(m));
-    if (excl_ptr) {
-        for (uint64_t u = 0; u < num_users; ++u)
-            if (excl_ptr[u + 1] < excl_ptr[u]) return SBR_ERR_INVALID_ARGUMENT;
-        for (uint64_t i = excl_ptr[0]; i < excl_ptr[num_users]; ++i)
-            if (excl_items[i] >= m->hp.num_items) return SBR_ERR_INVALID_ARGUMENT;
-    }
-    const size_t d = (size_t)m->d, dl = (size_t)m->dl;
-    const size_t cap = recommend_users_cap(m, k);
-    for (size_t c0 = 0; c0 < num_users; c0 += cap) {
-        const size_t nu = std::min<size_t>(cap, num_users - c0);
-        UserBatch excl; /* the caller's exclusion lists, sorted and de-duplicated (their state windows go unused) */
-        if (excl_ptr) {
-            std::vector<const uint32_t*> lists(nu);
-            std::vector<uint64_t> n(nu);
-            for (size_t i = 0; i < nu; ++i) {
-                lists[i] = excl_items + excl_ptr[c0 + i];
-                n[i] = excl_ptr[c0 + i + 1] - excl_ptr[c0 + i];
-            }
-            prepare_users(lists, n, m->hp.max_sequence_length, true, &excl);
-        }
-        DeviceArena& ar = m->eval_arena;
-        HIPCHK(hipStreamSynchronize(m->stream)); /* nothing of an earlier call may still read the arena */
-        SBRCHK(ar.reserve(DeviceArena::padded(nu * d * 4) + recommend_bytes(m, nu, excl.list_items.size(), k)));
-        float* H = ar.take<float>(nu * d);
-        /* padded to the storage width: the columns past embedding_dim are zero, as in the model's own states */
-        HIPCHK(hipMemsetAsync(H, 0, nu * d * 4, m->stream));
-        HIPCHK(hipMemcpy2DAsync(H, d * 4, reps + c0 * dl, dl * 4, dl * 4, nu, hipMemcpyHostToDevice, m->stream));
-        std::vector<int> rep_row(nu);
-        for (size_t i = 0; i < nu; ++i) rep_row[i] = (int)i;
-        SBRCHK(recommend_launch(m, H, rep_row, nu, excl.list_ptr, excl.list_items, k, out_items + c0 * k, out_scores ? out_scores + c0 * k : nullptr));
-    }
-    return SBR_OK;
+    if (excl_ptr) SBRCHK(check_csr(m, excl_ptr, num_users, excl_items, false));
+    return recommend_scan(m, RepSource{excl_ptr, excl_items, reps, 0, true}, num_users, k, out_items, out_scores);
 }
 
 /* ---------------------------------------------------------------------------------------------
@@ -3733,93 +3798,75 @@ sbr_status sbr_recommend_reps(sbr_model* m, const float* reps, uint64_t num_user
  * ------------------------------------------------------------------------------------------- */
 namespace {
 
-/* The scan-users of a call: user u's targets in runs of at most tmax, in user and target order (a user without targets has none). */
-struct ScanUsers {
-    std::vector<uint64_t> user;  /* the user of scan-user s */
-    std::vector<uint64_t> begin; /* its first target, an index into target_items */
-    std::vector<uint32_t> count; /* 1 .. tmax */
+/* device buffers of launch_rank_targets over ns scan-users of nlu users with nt targets and nmask mask entries */
+struct RankTargetsBufs {
+    int* rep;
+    uint32_t *lu, *sptr, *tgt, *pos, *ranks, *mask, *buckets, *totals, *flag;
+    float *ts, *th, *tmin, *tmin2;
+    uint64_t* mptr;
+    void carve(DeviceArena& ar, size_t ns, size_t nlu, size_t nt, size_t nmask, uint32_t tmax) {
+        rep = ar.take<int>(ns);
+        lu = ar.take<uint32_t>(ns);
+        sptr = ar.take<uint32_t>(ns + 1);
+        tgt = ar.take<uint32_t>(nt + 1);
+        ts = ar.take<float>(nt + 1);
+        pos = ar.take<uint32_t>(nt + 1);
+        ranks = ar.take<uint32_t>(nt + 1);
+        mptr = ar.take<uint64_t>(nlu + 1);
+        mask = ar.take<uint32_t>(nmask + 1);
+        th = ar.take<float>(ns * tmax);
+        buckets = ar.take<uint32_t>(ns * tmax);
+        tmin = ar.take<float>(ns);
+        tmin2 = ar.take<float>(ns);
+        totals = ar.take<uint32_t>(ns);
+        flag = ar.take<uint32_t>(1);
+    }
 };
 
-sbr_status rank_targets_check(const sbr_model* m, uint64_t num_users, const uint64_t* target_ptr, const uint32_t* target_items,
-                              uint32_t* out_ranks, uint32_t tmax, ScanUsers* su) {
+/* Ranks of every user's targets, users from `s`: validates the targets, cuts each user's into scan-users — runs of at most tmax,
+ * in user and target order (a user without targets has none) — and scans them in chunks.  The targets of a chunk are contiguous in
+ * target_items, and so are their ranks in out_ranks. */
+sbr_status rank_targets_scan(sbr_model* m, const RepSource& s, uint64_t num_users, const uint64_t* target_ptr, const uint32_t* target_items,
+                             uint32_t* out_ranks) {
     if (!target_ptr) return SBR_ERR_INVALID_ARGUMENT;
-    for (uint64_t u = 0; u < num_users; ++u)
-        if (target_ptr[u + 1] < target_ptr[u]) return SBR_ERR_INVALID_ARGUMENT; /* pointers must be non-decreasing */
-    const uint64_t nt = target_ptr[num_users] - target_ptr[0];
-    if (nt && (!target_items || !out_ranks)) return SBR_ERR_INVALID_ARGUMENT;
-    for (uint64_t e = target_ptr[0]; e < target_ptr[num_users]; ++e)
-        if (target_items[e] >= m->hp.num_items) return SBR_ERR_INVALID_ARGUMENT;
+    SBRCHK(check_csr(m, target_ptr, num_users, target_items, false));
+    if (target_ptr[num_users] - target_ptr[0] && !out_ranks) return SBR_ERR_INVALID_ARGUMENT;
+    const uint32_t tmax = sbr::rank_targets_tmax(m->d);
+    std::vector<uint64_t> su_user, su_begin; /* the user of scan-user i; its first target, an index into target_items */
     for (uint64_t u = 0; u < num_users; ++u)
         for (uint64_t e = target_ptr[u]; e < target_ptr[u + 1]; e += tmax) {
-            su->user.push_back(u);
-            su->begin.push_back(e);
-            su->count.push_back((uint32_t)std::min<uint64_t>(tmax, target_ptr[u + 1] - e));
+            su_user.push_back(u);
+            su_begin.push_back(e);
         }
-    return SBR_OK;
-}
-
-/* users per scan launch as mrr_score's EVAL_B, counted in scan-users */
-constexpr size_t RANK_TARGETS_B = 8192;
-
-/* arena bytes of one launch over ns scan-users of nlu users with nt targets and nmask mask entries */
-size_t rank_targets_bytes(size_t ns, size_t nlu, size_t nt, size_t nmask, uint32_t tmax) {
-    return 2 * DeviceArena::padded(ns * 4) + DeviceArena::padded((ns + 1) * 4) + 4 * DeviceArena::padded(nt * 4 + 4) +
-           DeviceArena::padded((nlu + 1) * 8) + DeviceArena::padded(nmask * 4 + 4) + 2 * DeviceArena::padded(ns * tmax * 4) +
-           3 * DeviceArena::padded(ns * 4) + DeviceArena::padded(4);
-}
-
-/* Ranks of the scan-users [c0, c1) of `su`, whose users are local rows: scan-user s has representation row rep_row[lu[s - c0]] of H
- * (eval arena, reserved with rank_targets_bytes) and the mask list lu[s - c0] of mask_ptr / mask_items (mask_ptr empty: no mask).  The
- * targets of a chunk are contiguous in target_items, and so are their ranks in `out` (out[0] = rank of target su.begin[c0]). */
-sbr_status rank_targets_launch(sbr_model* m, const float* H, const std::vector<int>& rep_row, const ScanUsers& su, size_t c0, size_t c1,
-                               const std::vector<uint32_t>& lu, size_t nlu, const std::vector<uint64_t>& mask_ptr,
-                               const std::vector<uint32_t>& mask_items, const uint32_t* target_items, uint32_t tmax, uint32_t* out) {
-    DeviceArena& ar = m->eval_arena;
-    const size_t ns = c1 - c0;
-    const uint64_t t0 = su.begin[c0];
-    const size_t nt = (size_t)(su.begin[c1 - 1] + su.count[c1 - 1] - t0);
-    std::vector<int> srep(ns);
-    std::vector<uint32_t> sptr(ns + 1);
-    for (size_t i = 0; i < ns; ++i) {
-        srep[i] = rep_row[lu[i]];
-        sptr[i] = (uint32_t)(su.begin[c0 + i] - t0);
+    for (Chunk ch; next_chunk(su_user, eval_units_cap, s, m->hp.max_sequence_length, &ch);) {
+        const size_t ns = ch.c1 - ch.c0, nlu = ch.users.size();
+        const uint64_t t0 = su_begin[ch.c0];
+        const size_t nt = (size_t)(std::min(su_begin[ch.c1 - 1] + tmax, target_ptr[su_user[ch.c1 - 1] + 1]) - t0);
+        UserReps ur; /* its lists: the masks (list_ptr empty: no mask) */
+        RankTargetsBufs rb;
+        SBRCHK(user_reps(m, s, ch.users, [&](DeviceArena& ar) { rb.carve(ar, ns, nlu, nt, ur.b.list_items.size(), tmax); }, &ur));
+        std::vector<int> srep(ns);
+        std::vector<uint32_t> sptr(ns + 1);
+        for (size_t i = 0; i < ns; ++i) {
+            srep[i] = ur.rep_row[ch.lu[i]];
+            sptr[i] = (uint32_t)(su_begin[ch.c0 + i] - t0);
+        }
+        sptr[ns] = (uint32_t)nt;
+        const bool mask = !ur.b.list_ptr.empty();
+        HIPCHK(hipMemcpyAsync(rb.rep, srep.data(), ns * 4, hipMemcpyHostToDevice, m->stream));
+        HIPCHK(hipMemcpyAsync(rb.lu, ch.lu.data(), ns * 4, hipMemcpyHostToDevice, m->stream));
+        HIPCHK(hipMemcpyAsync(rb.sptr, sptr.data(), (ns + 1) * 4, hipMemcpyHostToDevice, m->stream));
+        HIPCHK(hipMemcpyAsync(rb.tgt, target_items + t0, nt * 4, hipMemcpyHostToDevice, m->stream));
+        if (mask) {
+            HIPCHK(hipMemcpyAsync(rb.mptr, ur.b.list_ptr.data(), (nlu + 1) * 8, hipMemcpyHostToDevice, m->stream));
+            if (!ur.b.list_items.empty())
+                HIPCHK(hipMemcpyAsync(rb.mask, ur.b.list_items.data(), ur.b.list_items.size() * 4, hipMemcpyHostToDevice, m->stream));
+        }
+        SBRCHK(scan_launch(m, 3, rb.flag, [&] {
+            sbr::launch_rank_targets(m->mv, ur.H, rb.rep, rb.lu, rb.sptr, (uint32_t)ns, rb.tgt, mask ? rb.mptr : nullptr, rb.mask, rb.ts, rb.pos,
+                                     rb.th, rb.tmin, rb.tmin2, rb.buckets, rb.totals, rb.ranks, rb.flag, m->stream);
+        }, {{out_ranks + (t0 - target_ptr[0]), rb.ranks, nt * 4}}));
     }
-    sptr[ns] = (uint32_t)nt;
-    int* d_rep = ar.take<int>(ns);
-    uint32_t* d_lu = ar.take<uint32_t>(ns);
-    uint32_t* d_sptr = ar.take<uint32_t>(ns + 1);
-    uint32_t* d_tgt = ar.take<uint32_t>(nt + 1);
-    float* d_ts = ar.take<float>(nt + 1);
-    uint32_t* d_pos = ar.take<uint32_t>(nt + 1);
-    uint32_t* d_ranks = ar.take<uint32_t>(nt + 1);
-    uint64_t* d_mptr = ar.take<uint64_t>(nlu + 1);
-    uint32_t* d_mask = ar.take<uint32_t>(mask_items.size() + 1);
-    float* d_th = ar.take<float>(ns * tmax);
-    uint32_t* d_buckets = ar.take<uint32_t>(ns * tmax);
-    float* d_tmin = ar.take<float>(ns);
-    float* d_tmin2 = ar.take<float>(ns);
-    uint32_t* d_totals = ar.take<uint32_t>(ns);
-    uint32_t* d_flag = ar.take<uint32_t>(1);
-    const bool mask = !mask_ptr.empty();
-    HIPCHK(hipMemcpyAsync(d_rep, srep.data(), ns * 4, hipMemcpyHostToDevice, m->stream));
-    HIPCHK(hipMemcpyAsync(d_lu, lu.data(), ns * 4, hipMemcpyHostToDevice, m->stream));
-    HIPCHK(hipMemcpyAsync(d_sptr, sptr.data(), (ns + 1) * 4, hipMemcpyHostToDevice, m->stream));
-    HIPCHK(hipMemcpyAsync(d_tgt, target_items + t0, nt * 4, hipMemcpyHostToDevice, m->stream));
-    if (mask) {
-        HIPCHK(hipMemcpyAsync(d_mptr, mask_ptr.data(), (nlu + 1) * 8, hipMemcpyHostToDevice, m->stream));
-        if (!mask_items.empty()) HIPCHK(hipMemcpyAsync(d_mask, mask_items.data(), mask_items.size() * 4, hipMemcpyHostToDevice, m->stream));
-    }
-    HIPCHK(hipMemsetAsync(d_flag, 0, 4, m->stream));
-    {
-        ScopedTimer t(m, SBR_K_RANK, 3);
-        sbr::launch_rank_targets(m->mv, H, d_rep, d_lu, d_sptr, (uint32_t)ns, d_tgt, mask ? d_mptr : nullptr, d_mask, d_ts, d_pos, d_th,
-                                 d_tmin, d_tmin2, d_buckets, d_totals, d_ranks, d_flag, m->stream);
-    }
-    uint32_t flag = 0;
-    HIPCHK(hipStreamSynchronize(m->stream)); /* the host vectors above are read by the asynchronous copies */
-    HIPCHK(hipMemcpy(&flag, d_flag, 4, hipMemcpyDeviceToHost));
-    if (flag) return SBR_ERR_INVALID_PREDICTION; /* predict fails the call on a non-finite score */
-    HIPCHK(hipMemcpy(out, d_ranks, nt * 4, hipMemcpyDeviceToHost));
     return SBR_OK;
 }
 
@@ -3830,102 +3877,20 @@ sbr_status sbr_rank_targets(sbr_model* m, const uint64_t* user_ptr, const uint32
     if (!m || !user_ptr || (flags & ~SBR_RANK_INCLUDE_HISTORY)) return SBR_ERR_INVALID_ARGUMENT;
     std::lock_guard<std::mutex> lock(m->mu);
     SBRCHK(ensure_device(m));
-    const uint64_t T = m->hp.max_sequence_length;
-    for (uint64_t u = 0; u < num_users; ++u)
-        if (user_ptr[u + 1] < user_ptr[u]) return SBR_ERR_INVALID_ARGUMENT; /* pointers must be non-decreasing */
-    if (user_ptr[num_users] - user_ptr[0] && !item_ids) return SBR_ERR_INVALID_ARGUMENT;
-    for (uint64_t i = user_ptr[0]; i < user_ptr[num_users]; ++i)
-        if (item_ids[i] >= m->hp.num_items) return SBR_ERR_INVALID_ARGUMENT;
-    const uint32_t tmax = sbr::rank_targets_tmax(m->d);
-    ScanUsers su;
-    SBRCHK(rank_targets_check(m, num_users, target_ptr, target_items, out_ranks, tmax, &su));
-    const bool mask = !(flags & SBR_RANK_INCLUDE_HISTORY);
-    const size_t eval_rows_cap = (size_t)1 << 22; /* as mrr_score: the forward pass's scratch is (users x steps) rows */
-    auto rows_of = [&](uint64_t u) { return (size_t)std::max<uint64_t>(1, std::min<uint64_t>(user_ptr[u + 1] - user_ptr[u], T)); };
-    for (size_t c0 = 0, c1 = 0; c0 < su.user.size(); c0 = c1) {
-        /* a chunk is a run of scan-users; a user cut by its end is forwarded again in the next one */
-        size_t rows = 0;
-        for (c1 = c0; c1 < su.user.size() && c1 - c0 < RANK_TARGETS_B; ++c1) {
-            if (c1 == c0 || su.user[c1] != su.user[c1 - 1]) {
-                rows += rows_of(su.user[c1]);
-                if (rows > eval_rows_cap && c1 > c0) break;
-            }
-        }
-        std::vector<uint32_t> lu(c1 - c0);
-        std::vector<const uint32_t*> hist;
-        std::vector<uint64_t> n;
-        for (size_t s = c0; s < c1; ++s) {
-            const uint64_t u = su.user[s];
-            if (s == c0 || u != su.user[s - 1]) {
-                hist.push_back(item_ids ? item_ids + user_ptr[u] : nullptr);
-                n.push_back(user_ptr[u + 1] - user_ptr[u]);
-            }
-            lu[s - c0] = (uint32_t)(hist.size() - 1);
-        }
-        /* the WHOLE history is masked (evaluation.rs:30-32) */
-        UserBatch b;
-        prepare_users(hist, n, T, mask, &b);
-        const size_t nt = (size_t)(su.begin[c1 - 1] + su.count[c1 - 1] - su.begin[c0]);
-        float* H = nullptr;
-        std::vector<int> rep_row;
-        SBRCHK(forward_histories(m, b.first, b.nsteps, &H, &rep_row, rank_targets_bytes(c1 - c0, hist.size(), nt, b.list_items.size(), tmax)));
-        SBRCHK(rank_targets_launch(m, H, rep_row, su, c0, c1, lu, hist.size(), b.list_ptr, b.list_items, target_items, tmax,
-                                   out_ranks + (su.begin[c0] - target_ptr[0])));
-    }
-    return SBR_OK;
+    SBRCHK(check_csr(m, user_ptr, num_users, item_ids, false));
+    /* the WHOLE history is masked (evaluation.rs:30-32) */
+    return rank_targets_scan(m, RepSource{user_ptr, item_ids, nullptr, 0, !(flags & SBR_RANK_INCLUDE_HISTORY)}, num_users, target_ptr,
+                             target_items, out_ranks);
 }
 
 sbr_status sbr_rank_targets_reps(sbr_model* m, const float* reps, uint64_t num_users, const uint64_t* excl_ptr, const uint32_t* excl_items,
                                  const uint64_t* target_ptr, const uint32_t* target_items, uint32_t* out_ranks) {
     if (!m || (num_users && !reps)) return SBR_ERR_INVALID_ARGUMENT;
-    if ((excl_ptr == nullptr) != (excl_items == nullptr) && !(excl_ptr && excl_ptr[num_users] == excl_ptr[0])) return SBR_ERR_INVALID_ARGUMENT;
+    if (!excl_args_ok(excl_ptr, excl_items, num_users)) return SBR_ERR_INVALID_ARGUMENT;
     std::lock_guard<std::mutex> lock(m->mu);
     SBRCHK(ensure_device(m));
-    if (excl_ptr) {
-        for (uint64_t u = 0; u < num_users; ++u)
-            if (excl_ptr[u + 1] < excl_ptr[u]) return SBR_ERR_INVALID_ARGUMENT;
-        for (uint64_t i = excl_ptr[0]; i < excl_ptr[num_users]; ++i)
-            if (excl_items[i] >= m->hp.num_items) return SBR_ERR_INVALID_ARGUMENT;
-    }
-    const uint32_t tmax = sbr::rank_targets_tmax(m->d);
-    ScanUsers su;
-    SBRCHK(rank_targets_check(m, num_users, target_ptr, target_items, out_ranks, tmax, &su));
-    const size_t d = (size_t)m->d, dl = (size_t)m->dl;
-    for (size_t c0 = 0; c0 < su.user.size(); c0 += RANK_TARGETS_B) {
-        const size_t c1 = std::min(su.user.size(), c0 + RANK_TARGETS_B);
-        std::vector<uint32_t> lu(c1 - c0);
-        std::vector<uint64_t> users; /* the chunk's users, ascending */
-        for (size_t s = c0; s < c1; ++s) {
-            if (s == c0 || su.user[s] != su.user[s - 1]) users.push_back(su.user[s]);
-            lu[s - c0] = (uint32_t)(users.size() - 1);
-        }
-        const size_t nlu = users.size();
-        UserBatch excl; /* the caller's mask lists, sorted and de-duplicated (their state windows go unused) */
-        if (excl_ptr) {
-            std::vector<const uint32_t*> lists(nlu);
-            std::vector<uint64_t> n(nlu);
-            for (size_t i = 0; i < nlu; ++i) {
-                lists[i] = excl_items + excl_ptr[users[i]];
-                n[i] = excl_ptr[users[i] + 1] - excl_ptr[users[i]];
-            }
-            prepare_users(lists, n, m->hp.max_sequence_length, true, &excl);
-        }
-        const size_t nt = (size_t)(su.begin[c1 - 1] + su.count[c1 - 1] - su.begin[c0]);
-        DeviceArena& ar = m->eval_arena;
-        HIPCHK(hipStreamSynchronize(m->stream)); /* nothing of an earlier call may still read the arena */
-        SBRCHK(ar.reserve(DeviceArena::padded(nlu * d * 4) + rank_targets_bytes(c1 - c0, nlu, nt, excl.list_items.size(), tmax)));
-        float* H = ar.take<float>(nlu * d);
-        /* padded to the storage width: the columns past embedding_dim are zero, as in the model's own states */
-        HIPCHK(hipMemsetAsync(H, 0, nlu * d * 4, m->stream));
-        std::vector<float> rows(nlu * dl);
-        for (size_t i = 0; i < nlu; ++i) std::memcpy(rows.data() + i * dl, reps + users[i] * dl, dl * 4);
-        HIPCHK(hipMemcpy2DAsync(H, d * 4, rows.data(), dl * 4, dl * 4, nlu, hipMemcpyHostToDevice, m->stream));
-        std::vector<int> rep_row(nlu);
-        for (size_t i = 0; i < nlu; ++i) rep_row[i] = (int)i;
-        SBRCHK(rank_targets_launch(m, H, rep_row, su, c0, c1, lu, nlu, excl.list_ptr, excl.list_items, target_items, tmax,
-                                   out_ranks + (su.begin[c0] - target_ptr[0])));
-    }
-    return SBR_OK;
+    if (excl_ptr) SBRCHK(check_csr(m, excl_ptr, num_users, excl_items, false));
+    return rank_targets_scan(m, RepSource{excl_ptr, excl_items, reps, 0, true}, num_users, target_ptr, target_items, out_ranks);
 }
 
 /* ---------------------------------------------------------------------------------------------

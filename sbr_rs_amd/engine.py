@@ -28,6 +28,22 @@ def _check(st: int):
     raise EngineError(Status(st), msg)
 
 
+def _exclusion_csr(exclude, nu: int):
+    """One sequence of item ids per user -> (ptr u64 [nu + 1], items u32, never empty: a one-element dummy stands in for no
+    items at all); (None, None) for exclude = None."""
+    if exclude is None:
+        return None, None
+    if len(exclude) != nu:
+        raise ValueError("one exclusion list per user")
+    lists = [np.asarray(e, dtype=np.uint32).ravel() for e in exclude]
+    ep = np.zeros(nu + 1, dtype=np.uint64)
+    ep[1:] = np.cumsum([x.size for x in lists])
+    ei = np.ascontiguousarray(np.concatenate(lists) if lists else np.zeros(0, np.uint32), dtype=np.uint32)
+    if ei.size == 0:
+        ei = np.zeros(1, dtype=np.uint32)
+    return ep, ei
+
+
 def _ptr(a: np.ndarray):
     return a.ctypes.data_as(C.c_void_p)
 
@@ -543,16 +559,7 @@ class Model:
         nu = reps.shape[0]
         items = np.zeros((nu, max(int(k), 0)), dtype=np.uint32)
         scores = np.zeros((nu, max(int(k), 0)), dtype=np.float32)
-        ep = ei = None
-        if exclude is not None:
-            if len(exclude) != nu:
-                raise ValueError("one exclusion list per user")
-            lists = [np.asarray(e, dtype=np.uint32).ravel() for e in exclude]
-            ep = np.zeros(nu + 1, dtype=np.uint64)
-            ep[1:] = np.cumsum([x.size for x in lists])
-            ei = np.ascontiguousarray(np.concatenate(lists) if lists else np.zeros(0, np.uint32), dtype=np.uint32)
-            if ei.size == 0:
-                ei = np.zeros(1, dtype=np.uint32)
+        ep, ei = _exclusion_csr(exclude, nu)
         _check(self._L.sbr_recommend_reps(self._h, _ptr(reps), nu, int(k) & 0xFFFFFFFF, None if ep is None else _ptr(ep),
                                           None if ei is None else _ptr(ei), _ptr(items), _ptr(scores)))
         return items, scores
@@ -583,16 +590,7 @@ class Model:
         ti = np.ascontiguousarray(target_items, dtype=np.uint32)
         if len(tp) != nu + 1:
             raise ValueError("one target range per user")
-        ep = ei = None
-        if exclude is not None:
-            if len(exclude) != nu:
-                raise ValueError("one exclusion list per user")
-            lists = [np.asarray(e, dtype=np.uint32).ravel() for e in exclude]
-            ep = np.zeros(nu + 1, dtype=np.uint64)
-            ep[1:] = np.cumsum([x.size for x in lists])
-            ei = np.ascontiguousarray(np.concatenate(lists) if lists else np.zeros(0, np.uint32), dtype=np.uint32)
-            if ei.size == 0:
-                ei = np.zeros(1, dtype=np.uint32)
+        ep, ei = _exclusion_csr(exclude, nu)
         ranks = np.zeros(max(ti.size, 1), dtype=np.uint32)
         _check(self._L.sbr_rank_targets_reps(self._h, _ptr(reps), nu, None if ep is None else _ptr(ep),
                                              None if ei is None else _ptr(ei), _ptr(tp), _ptr(ti), _ptr(ranks)))
