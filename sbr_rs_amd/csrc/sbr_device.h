@@ -1,7 +1,8 @@
 /* sbr_device.h — device-side helpers shared by the kernel translation units (sbr_kernels.hip, sbr_steps.hip, sbr_catalogue.hip):
  * 16-byte loads and stores, the group all-reduce that realises the contract's dot order, the optimiser element update, the
- * packed-f32 forms of the rational tanh, and the SmallTail of a one-sequence step (header + loss accumulators + lagged loss figure
- * + key ordering); and the launchers' dispatch on d (DISPATCH_D).
+ * sparse item-table update's one statement (LaneGroup, entry_source, RowSum, RowUpdate), the packed-f32 forms of the rational
+ * tanh, and the SmallTail of a one-sequence step (header + loss accumulators + lagged loss figure + key ordering); and the
+ * launchers' dispatches on d (DISPATCH_D) and on the owner kernels' device count (DISPATCH_NQ).
  * Everything here is __device__ __forceinline__: no symbol leaves a translation unit. */
 #ifndef SBR_DEVICE_H
 #define SBR_DEVICE_H
@@ -54,6 +55,174 @@ __device__ __forceinline__ void opt_update(const ModelView& m, float* w, float* 
     if (m.optimizer == SBR_OPT_ADAM) sbr_adam(w, mom, acc, g, m.lr, m.l2, m.c1, m.c2);
     else sbr_adagrad(w, acc, g, m.lr, m.l2);
 }
+
+// ---- the sparse item-table update ("sparse row gradients"): THE statement of a row's gradient sum and of its one
+// optimiser update.  Every kernel that reduces entries, combines chunk or device partials, or updates a table row does it through
+// these types; the kernels differ only in how they get keys and rows in flight. ----
+
+// The D/4-lane group of a wave that owns one unit (row, segment, chunk) at a time in the grid-stride kernels: lane `lg` of the
+// group holds elements 4 lg .. 4 lg + 3 of the row.  A wave-uniform loop runs `for (i0 = wave_first; i0 < n; i0 += stride)` with
+// the group's unit at i0 + grp; a per-group loop starts at first().
+template <int D>
+struct LaneGroup {
+    static constexpr int L = D / 4, GPW = 64 / L;  // lanes per group, groups per wave
+    int lg, grp;
+    uint64_t wave_first, stride;
+    // By default the whole grid's waves.  (Default ARGUMENTS, not a second constructor: they are evaluated in the kernel's own
+    // body, where the compiler reads blockDim.x as the launch's uniform workgroup size; inside a helper function it reads the
+    // possibly-partial last workgroup's size instead — a vector-memory load and a wait at the top of every kernel.)
+    __device__ __forceinline__ LaneGroup(uint64_t wave = (blockIdx.x * (uint64_t)blockDim.x + threadIdx.x) >> 6,
+                                         uint64_t nwaves = ((uint64_t)gridDim.x * blockDim.x) >> 6)
+        : lg((int)(threadIdx.x & 63) % L), grp((int)(threadIdx.x & 63) / L), wave_first(wave * GPW), stride(nwaves * GPW) {}
+    __device__ __forceinline__ uint64_t first() const { return wave_first + grp; }
+};
+
+// An entry of the sparse update, decoded from its key's low word (3 x packed row + kind): kind 0 = the row's input (gradient row
+// dX[r], scale 1, no bias term), 1 = its target (-coef[r] * H[r]), 2 = its negative (+coef[r] * H[r]); the last two carry the bias
+// term, whose gradient is the scale itself.
+struct EntrySource {
+    uint32_t r, kind;
+    __device__ __forceinline__ const float* rows(const float* dX, const float* H) const { return kind == 0 ? dX : H; }
+    __device__ __forceinline__ float scale(float c) const { return kind == 0 ? 1.0f : (kind == 1 ? -c : c); }  // c = coef[r]
+    __device__ __forceinline__ float scale_at(const float* coef) const { return kind == 0 ? 1.0f : scale(coef[r]); }  // no load for an input
+    __device__ __forceinline__ bool carries_bias() const { return kind != 0; }
+};
+__device__ __forceinline__ EntrySource entry_source(uint32_t key_lo) { return EntrySource{key_lo / 3, key_lo % 3}; }
+
+// A row's ordered gradient sum (4 elements per lane of the row's group, and the bias term).  Entries are added in key order,
+// partials (chunks of SBR_SEG_CHUNK entries; devices) in their order; the FIRST term of either kind initialises the sum — it is
+// not added to zero, so a first term of -0.0 stays -0.0 — and the bias term exists only where some entry carried one.
+// The two "seen" flags (a term has arrived; a bias term has arrived) are kept as two booleans (RowSum: the sums over entries and
+// chunks — scalar-register masks) or as the flag word of the exchange chunks and gradient lists, bit 0 = row touched, bit 1 =
+// bias present (RowSumW: the owner kernels' sums over devices, whose inputs are such words).  The storage is the only
+// difference; it is a template argument because either kind of kernel lost registers with the other's (seg_chunk_kernel, at
+// its 80-register budget, spills with the word; owner_update_kernel<., 16> drops to one wave per SIMD with the booleans).
+struct SeenBools {
+    bool empty, hb;
+    __device__ __forceinline__ SeenBools(bool any_, bool has_b_) : empty(!any_), hb(has_b_) {}
+    __device__ __forceinline__ bool any() const { return !empty; }
+    __device__ __forceinline__ bool has_b() const { return hb; }
+};
+struct SeenWord {
+    uint32_t w;
+    __device__ __forceinline__ SeenWord(bool any_, bool has_b_) : w((any_ ? 1u : 0u) | (has_b_ ? 2u : 0u)) {}
+    __device__ __forceinline__ bool any() const { return (w & 1u) != 0; }
+    __device__ __forceinline__ bool has_b() const { return (w & 2u) != 0; }
+};
+template <class Seen>
+struct RowSumT {
+    float4 g;
+    float gb;
+    Seen seen;
+    __device__ __forceinline__ RowSumT() : g(make_float4(0.f, 0.f, 0.f, 0.f)), gb(0.0f), seen(false, false) {}
+    __device__ __forceinline__ RowSumT(float4 g_, float gb_, bool any_, bool has_b_) : g(g_), gb(gb_), seen(any_, has_b_) {}
+    __device__ __forceinline__ RowSumT(float4 g_, float gb_, uint32_t fl) : RowSumT(g_, gb_, (fl & 1u) != 0, (fl & 2u) != 0) {}
+    __device__ __forceinline__ bool any() const { return seen.any(); }
+    __device__ __forceinline__ bool has_b() const { return seen.has_b(); }
+    __device__ __forceinline__ uint32_t flags() const { return (any() ? 1u : 0u) | (has_b() ? 2u : 0u); }
+    __device__ __forceinline__ void add_entry(float4 v, float scale, bool carries_bias) { *this = with_entry(*this, v, scale, carries_bias); }
+    template <class S2>
+    __device__ __forceinline__ void add_partial(const RowSumT<S2>& o) { *this = with_partial(*this, o.g, o.gb, o.any(), o.has_b()); }
+
+private:
+    // (Both operations are stated on local copies that replace *this, with the first flag as "empty": with the members updated in
+    // place, or with that flag's sense inverted, seg_chunk_kernel spilled two registers.)
+    static __device__ __forceinline__ RowSumT with_entry(const RowSumT& s, float4 v, float scale, bool carries_bias) {
+        float4 g = s.g;
+        float gb = s.gb;
+        bool empty = !s.any(), has_b = s.has_b();
+        if (empty) {  // product, then add: no fused multiply-add
+            g = make_float4(scale * v.x, scale * v.y, scale * v.z, scale * v.w);
+            empty = false;
+        } else {
+            g.x = g.x + scale * v.x; g.y = g.y + scale * v.y;
+            g.z = g.z + scale * v.z; g.w = g.w + scale * v.w;
+        }
+        if (carries_bias) {
+            gb = has_b ? gb + scale : scale;
+            has_b = true;
+        }
+        return RowSumT(g, gb, !empty, has_b);
+    }
+    static __device__ __forceinline__ RowSumT with_partial(const RowSumT& s, float4 v, float vb, bool o_any, bool o_has_b) {
+        float4 g = s.g;
+        float gb = s.gb;
+        bool empty = !s.any(), has_b = s.has_b();
+        if (o_any) {
+            if (empty) g = v;
+            else { g.x = g.x + v.x; g.y = g.y + v.y; g.z = g.z + v.z; g.w = g.w + v.w; }
+            empty = false;
+        }
+        if (o_has_b) {
+            gb = has_b ? gb + vb : vb;
+            has_b = true;
+        }
+        return RowSumT(g, gb, !empty, has_b);
+    }
+};
+typedef RowSumT<SeenBools> RowSum;
+typedef RowSumT<SeenWord> RowSumW;
+
+// how a row's parameter / optimiser-state quads travel: plain here; a kernel beside whose traffic they should not stay cached
+// passes its own policy (sbr_kernels.hip: UpdAccess)
+struct PlainAccess {
+    static __device__ __forceinline__ float4 ld(const float* p) { return ld4(p); }
+    static __device__ __forceinline__ void st(float* p, float4 v) { st4(p, v); }
+};
+
+// One optimiser update of an item-table row: the group's quads of E / Eacc / (Adam: Em) and, on the group's lane 0, the bias
+// trio b / bacc / (bm).  load / apply / store are separate so that every kernel issues the loads where its schedule wants them
+// (a value that is not loaded stays 0 and must not be stored).  ADAGRAD_ONLY: the caller's shape checks admit Adagrad only —
+// no Adam code is generated.
+template <int D, bool ADAGRAD_ONLY = false>
+struct RowUpdate {
+    float4 w, a, mo;
+    float bv, ba, bmo;
+    __device__ __forceinline__ RowUpdate() : w(make_float4(0.f, 0.f, 0.f, 0.f)), a(w), mo(w), bv(0.0f), ba(0.0f), bmo(0.0f) {}
+    static __device__ __forceinline__ bool adam(const ModelView& m) { return !ADAGRAD_ONLY && m.optimizer == SBR_OPT_ADAM; }
+    static __device__ __forceinline__ void element(const ModelView& m, float* wv, float* acc, float* mom, float g) {
+        if constexpr (ADAGRAD_ONLY) sbr_adagrad(wv, acc, g, m.lr, m.l2);
+        else opt_update(m, wv, acc, mom, g);
+    }
+    template <class Access = PlainAccess>
+    __device__ __forceinline__ void load(const ModelView& m, uint64_t row, int lg) {
+        w = Access::ld(m.E + row * D + 4 * lg);
+        a = Access::ld(m.Eacc + row * D + 4 * lg);
+        if (adam(m)) mo = ld4(m.Em + row * D + 4 * lg);
+    }
+    __device__ __forceinline__ void load_bias(const ModelView& m, uint64_t row) {
+        bv = m.b[row]; ba = m.bacc[row];
+        if (adam(m)) bmo = m.bm[row];
+    }
+    template <class Sum>
+    __device__ __forceinline__ void apply(const ModelView& m, const Sum& s) {
+        element(m, &w.x, &a.x, &mo.x, s.g.x);
+        element(m, &w.y, &a.y, &mo.y, s.g.y);
+        element(m, &w.z, &a.z, &mo.z, s.g.z);
+        element(m, &w.w, &a.w, &mo.w, s.g.w);
+    }
+    template <class Sum>
+    __device__ __forceinline__ void apply_bias(const ModelView& m, const Sum& s) { element(m, &bv, &ba, &bmo, s.gb); }
+    template <class Access = PlainAccess>
+    __device__ __forceinline__ void store(const ModelView& m, uint64_t row, int lg) const {
+        Access::st(m.E + row * D + 4 * lg, w);
+        Access::st(m.Eacc + row * D + 4 * lg, a);
+        if (adam(m)) st4(m.Em + row * D + 4 * lg, mo);
+    }
+    __device__ __forceinline__ void store_bias(const ModelView& m, uint64_t row) const {
+        m.b[row] = bv;
+        m.bacc[row] = ba;
+        if (adam(m)) m.bm[row] = bmo;
+    }
+    // the bias trio's whole read-modify-write on the group's lane 0, for the kernels that do not request it ahead
+    template <class Sum>
+    __device__ __forceinline__ void update_bias(const ModelView& m, uint64_t row, int lg, const Sum& s) {
+        if (lg != 0 || !s.has_b()) return;
+        load_bias(m, row);
+        apply_bias(m, s);
+        store_bias(m, row);
+    }
+};
 
 // A kernel-argument pointer passed through an empty asm: the compiler can no longer hoist "pointer + per-lane
 // offset" out of the time loop as a 64-bit VGPR pair that lives across it (those pairs were being spilled to
@@ -210,4 +379,12 @@ __device__ __forceinline__ void small_tail(const MbView& mb, const BlockView& bl
         case 256: { constexpr int DD = 256; __VA_ARGS__; } break;  \
         default: break;                                            \
     }
+/* host side: the owner kernels' instantiation for ndev devices (their requests are unrolled for NQ = 4 / 8 / 16): runs the
+ * statement list with constexpr int NQ */
+#define DISPATCH_NQ(ndev, ...)                                           \
+    do {                                                                 \
+        if ((ndev) <= 4) { constexpr int NQ = 4; __VA_ARGS__; }          \
+        else if ((ndev) <= 8) { constexpr int NQ = 8; __VA_ARGS__; }     \
+        else { constexpr int NQ = 16; __VA_ARGS__; }                     \
+    } while (0)
 #endif

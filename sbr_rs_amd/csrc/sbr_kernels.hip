@@ -9,7 +9,9 @@
 //   * dense gradients       : v_mfma_f32_32x32x2_f32 over fixed 1024-row chunks, chunk partials
 //                             added in chunk order
 //   * sparse row gradients  : (row, source) keys in key order (sbr_sort.hip), per-row in-order reduction,
-//                             one Adagrad read-modify-write per touched row
+//                             one optimiser read-modify-write per touched row — the order and the update are
+//                             stated once, in sbr_device.h (RowSum, entry_source, RowUpdate); the kernels
+//                             here only schedule the loads
 // Reference call sites replaced: the wyrm graph built by Parameters::build
 // (/root/reference/src/models/lstm.rs:258-337, ewma.rs:266-352), driven by fit_sequence_model
 // (/root/reference/src/models/sequence_model.rs:111-169).
@@ -2208,33 +2210,6 @@ __global__ void repack_lstm_kernel(ModelView m) {
     m.WTp[wtp_index(k, jcol, m.d, m.ng)] = wv;
 }
 
-// one optimiser update of an item-embedding row (4 elements per lane of the row's group) and its bias
-__device__ __forceinline__ void bias_update(const ModelView& m, uint64_t row, int lg, float gb) {
-    if (lg != 0) return;
-    const bool adam = m.optimizer == SBR_OPT_ADAM;
-    float bv = m.b[row], ba = m.bacc[row], bmm = adam ? m.bm[row] : 0.0f;
-    opt_update(m, &bv, &ba, &bmm, gb);
-    m.b[row] = bv;
-    m.bacc[row] = ba;
-    if (adam) m.bm[row] = bmm;
-}
-template <int D>
-__device__ __forceinline__ void row_update(const ModelView& m, uint64_t row, int lg, float4 g, bool has_b, float gb) {
-    const bool adam = m.optimizer == SBR_OPT_ADAM;
-    float* wrow = m.E + row * D + 4 * lg;
-    float* arow = m.Eacc + row * D + 4 * lg;
-    float4 wv = ld4(wrow), av = ld4(arow);
-    float4 mv = adam ? ld4(m.Em + row * D + 4 * lg) : make_float4(0.f, 0.f, 0.f, 0.f);
-    opt_update(m, &wv.x, &av.x, &mv.x, g.x);
-    opt_update(m, &wv.y, &av.y, &mv.y, g.y);
-    opt_update(m, &wv.z, &av.z, &mv.z, g.z);
-    opt_update(m, &wv.w, &av.w, &mv.w, g.w);
-    st4(wrow, wv);
-    st4(arow, av);
-    if (adam) st4(m.Em + row * D + 4 * lg, mv);
-    if (has_b) bias_update(m, row, lg, gb);
-}
-
 // ------------------------------------------------------------------------------------------------
 // K6 sparse: (row, source) keys -> radix sort -> per-row reduction in the contract's chunked order
 // (SBR_SEG_CHUNK, sbr_numerics.h) -> Emit.  One lane group (D/4 lanes) owns a row segment of the sorted
@@ -2245,48 +2220,43 @@ __device__ __forceinline__ void row_update(const ModelView& m, uint64_t row, int
 // finished row (Emit): optimiser update, write into the owner's send chunk, or entry of the list.
 // ------------------------------------------------------------------------------------------------
 
-struct RowPrefetch {  // the row's parameter / optimiser-state quads, requested as soon as the row id is known
-    float4 w, a, mo;
+struct UpdAccess {  // the single-device update's E / Eacc traffic: streaming where SBR_NT_UPD / SBR_NT_UPD_ST say so
+    static __device__ __forceinline__ float4 ld(const float* p) { return ld4_upd(p); }
+    static __device__ __forceinline__ void st(float* p, float4 v) { st4_upd(p, v); }
 };
-struct EmitApply {  // single device: one optimiser update per touched row
+struct NoPrefetch {};
+struct EmitApply {  // single device: one optimiser update per touched row (RowUpdate, sbr_device.h)
     ModelView m;
+    // the row's parameter / optimiser-state quads, requested as soon as the row id is known
     template <int D>
-    __device__ __forceinline__ RowPrefetch pre(uint32_t r, int lg) const {
-        RowPrefetch q;
-        q.w = ld4_upd(m.E + (size_t)r * D + 4 * lg);
-        q.a = ld4_upd(m.Eacc + (size_t)r * D + 4 * lg);
-        q.mo = m.optimizer == SBR_OPT_ADAM ? ld4(m.Em + (size_t)r * D + 4 * lg) : make_float4(0.f, 0.f, 0.f, 0.f);
+    __device__ __forceinline__ RowUpdate<D> pre(uint32_t r, int lg) const {
+        RowUpdate<D> q;
+        q.template load<UpdAccess>(m, r, lg);
         return q;
     }
     template <int D>
-    __device__ __forceinline__ void row(uint32_t r, uint64_t, int lg, float4 g, bool has_b, float gb, RowPrefetch q) const {
-        const bool adam = m.optimizer == SBR_OPT_ADAM;
-        opt_update(m, &q.w.x, &q.a.x, &q.mo.x, g.x);
-        opt_update(m, &q.w.y, &q.a.y, &q.mo.y, g.y);
-        opt_update(m, &q.w.z, &q.a.z, &q.mo.z, g.z);
-        opt_update(m, &q.w.w, &q.a.w, &q.mo.w, g.w);
-        st4_upd(m.E + (size_t)r * D + 4 * lg, q.w);
-        st4_upd(m.Eacc + (size_t)r * D + 4 * lg, q.a);
-        if (adam) st4(m.Em + (size_t)r * D + 4 * lg, q.mo);
-        if (has_b) bias_update(m, r, lg, gb);
+    __device__ __forceinline__ void row(uint32_t r, uint64_t, int lg, const RowSum& s, RowUpdate<D> q) const {
+        q.apply(m, s);
+        q.template store<UpdAccess>(m, r, lg);
+        q.update_bias(m, r, lg, s);
     }
 };
 struct EmitChunk {  // replicated multi-device: the row's sum goes into the owner's dense send chunk
     void* send;
     uint64_t S;
     template <int D>
-    __device__ __forceinline__ RowPrefetch pre(uint32_t, int) const { return RowPrefetch{}; }
+    __device__ __forceinline__ NoPrefetch pre(uint32_t, int) const { return NoPrefetch{}; }
     template <int D>
-    __device__ __forceinline__ void row(uint32_t r, uint64_t, int lg, float4 g, bool has_b, float gb, RowPrefetch) const {
+    __device__ __forceinline__ void row(uint32_t r, uint64_t, int lg, const RowSum& s, NoPrefetch) const {
         /* (S = ceil(num_items / num_devices) < 2^32: the owner and the row inside its slice by 32-bit division — the 64-bit one cost this
          * kernel a third of its registers) */
         const uint32_t S32 = (uint32_t)S, owner = r / S32;
         float* c = reinterpret_cast<float*>(send) + (uint64_t)owner * S * ((uint64_t)D + 2);
         const uint64_t lr = r - owner * S32;
-        st4(c + lr * D + 4 * lg, g);
+        st4(c + lr * D + 4 * lg, s.g);
         if (lg == 0) {
-            if (has_b) c[S * D + lr] = gb;
-            reinterpret_cast<uint32_t*>(c + S * D + S)[lr] = 1u | (has_b ? 2u : 0u);
+            if (s.has_b()) c[S * D + lr] = s.gb;
+            reinterpret_cast<uint32_t*>(c + S * D + S)[lr] = 1u | (s.has_b() ? 2u : 0u);
         }
     }
 };
@@ -2295,25 +2265,22 @@ struct EmitList {  // partitioned table: list entry addressed by the position of
     float* gbl;
     uint32_t* fl;
     template <int D>
-    __device__ __forceinline__ RowPrefetch pre(uint32_t, int) const { return RowPrefetch{}; }
+    __device__ __forceinline__ NoPrefetch pre(uint32_t, int) const { return NoPrefetch{}; }
     template <int D>
-    __device__ __forceinline__ void row(uint32_t, uint64_t p, int lg, float4 g, bool has_b, float gb, RowPrefetch) const {
-        st4(G + p * D + 4 * lg, g);
+    __device__ __forceinline__ void row(uint32_t, uint64_t p, int lg, const RowSum& s, NoPrefetch) const {
+        st4(G + p * D + 4 * lg, s.g);
         if (lg == 0) {
-            gbl[p] = gb;
-            fl[p] = 1u | (has_b ? 2u : 0u);
+            gbl[p] = s.gb;
+            fl[p] = 1u | (s.has_b() ? 2u : 0u);
         }
     }
 };
 
-// in-order sum of the entries keys[begin, end) of one row (the first one initialises); the row loads of
+// in-order sum of the entries keys[begin, end) of one row (the first one initialises: RowSum::add_entry); the row loads of
 // four consecutive entries are issued together, the adds stay in order
 template <int D>
-__device__ __forceinline__ void seg_accumulate(const BlockView& blk, const uint64_t* keys, uint64_t begin, uint64_t end, int lg,
-                                               float4* g_out, float* gb_out, bool* has_b_out) {
-    float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
-    float gb = 0.0f;
-    bool has_b = false, first = true;
+__device__ __forceinline__ RowSum seg_accumulate(const BlockView& blk, const uint64_t* keys, uint64_t begin, uint64_t end, int lg) {
+    RowSum s;
     for (uint64_t e = begin; e < end; e += 4) {
         float4 v[4];
         float sc[4];
@@ -2324,31 +2291,17 @@ __device__ __forceinline__ void seg_accumulate(const BlockView& blk, const uint6
             sc[i] = 0.0f;
             bias[i] = false;
             if (e + i < end) { /* no traffic for the slots past the segment (most segments have 1-3 entries) */
-                const uint32_t src = (uint32_t)keys[e + i];
-                const uint32_t r = src / 3, kind = src % 3;
-                v[i] = ld4((kind == 0 ? blk.dX : blk.H) + (size_t)r * D + 4 * lg);
-                sc[i] = kind == 0 ? 1.0f : (kind == 1 ? -blk.coef[r] : blk.coef[r]);
-                bias[i] = kind != 0;
+                const EntrySource src = entry_source((uint32_t)keys[e + i]);
+                v[i] = ld4(src.rows(blk.dX, blk.H) + (size_t)src.r * D + 4 * lg);
+                sc[i] = src.scale_at(blk.coef);
+                bias[i] = src.carries_bias();
             }
         }
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            if (e + i < end) {
-                if (first) {
-                    g = make_float4(sc[i] * v[i].x, sc[i] * v[i].y, sc[i] * v[i].z, sc[i] * v[i].w);
-                    first = false;
-                } else {
-                    g.x = g.x + sc[i] * v[i].x; g.y = g.y + sc[i] * v[i].y;
-                    g.z = g.z + sc[i] * v[i].z; g.w = g.w + sc[i] * v[i].w;
-                }
-                if (bias[i]) {
-                    gb = has_b ? gb + sc[i] : sc[i];
-                    has_b = true;
-                }
-            }
-        }
+        for (int i = 0; i < 4; ++i)
+            if (e + i < end) s.add_entry(v[i], sc[i], bias[i]);
     }
-    *g_out = g; *gb_out = gb; *has_b_out = has_b;
+    return s;
 }
 
 // The same in-order sum for the chunks of LONG segments (hot rows: up to SBR_SEG_CHUNK entries per call): NB entries per batch
@@ -2360,11 +2313,8 @@ __device__ __forceinline__ void seg_accumulate(const BlockView& blk, const uint6
 // (140) its workgroups could not become resident until the GEMM's tail even when there was nothing for them to do (uniform items:
 // 1.85 ms of elapsed time for an empty launch at 50 000 sequences per step), and 1 024 workgroups took four rounds.
 template <int D, int NB>
-__device__ __forceinline__ void seg_accumulate_long(const BlockView& blk, const uint64_t* keys, uint64_t begin, uint64_t end, int lg,
-                                                    float4* g_out, float* gb_out, bool* has_b_out) {
-    float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
-    float gb = 0.0f;
-    bool has_b = false, first = true;
+__device__ __forceinline__ RowSum seg_accumulate_long(const BlockView& blk, const uint64_t* keys, uint64_t begin, uint64_t end, int lg) {
+    RowSum s;
     const uint32_t* klo = reinterpret_cast<const uint32_t*>(keys);  // the low word of a key is its source (3 x packed row + kind)
     uint32_t src_n[NB];
 #pragma unroll
@@ -2373,40 +2323,24 @@ __device__ __forceinline__ void seg_accumulate_long(const BlockView& blk, const 
     for (uint64_t e = begin; e < end; e += NB) {
         float4 v[NB];
         float sc[NB];
-        uint32_t kind[NB];
+        EntrySource src[NB];
 #pragma unroll
         for (int i = 0; i < NB; ++i) {
-            const uint32_t src = src_n[i];
-            const uint32_t r = src / 3;
-            kind[i] = src % 3;
+            src[i] = entry_source(src_n[i]);
             v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
             sc[i] = 0.0f;
             if (e + i < end) {
-                v[i] = ld4((kind[i] == 0 ? blk.dX : blk.H) + (size_t)r * D + 4 * lg);
-                sc[i] = blk.coef[r];
+                v[i] = ld4(src[i].rows(blk.dX, blk.H) + (size_t)src[i].r * D + 4 * lg);
+                sc[i] = blk.coef[src[i].r];
             }
         }
 #pragma unroll
         for (int i = 0; i < NB; ++i) src_n[i] = e + NB + i < end ? klo[2 * (e + NB + i)] : 0u;
 #pragma unroll
-        for (int i = 0; i < NB; ++i) {
-            if (e + i < end) {
-                const float s = kind[i] == 0 ? 1.0f : (kind[i] == 1 ? -sc[i] : sc[i]);
-                if (first) {
-                    g = make_float4(s * v[i].x, s * v[i].y, s * v[i].z, s * v[i].w);
-                    first = false;
-                } else {
-                    g.x = g.x + s * v[i].x; g.y = g.y + s * v[i].y;
-                    g.z = g.z + s * v[i].z; g.w = g.w + s * v[i].w;
-                }
-                if (kind[i] != 0) {
-                    gb = has_b ? gb + s : s;
-                    has_b = true;
-                }
-            }
-        }
+        for (int i = 0; i < NB; ++i)
+            if (e + i < end) s.add_entry(v[i], src[i].scale(sc[i]), src[i].carries_bias());
     }
-    *g_out = g; *gb_out = gb; *has_b_out = has_b;
+    return s;
 }
 
 // first position in [lo, hi) whose row differs from `row` (keys are sorted by row)
@@ -2431,13 +2365,12 @@ __device__ __forceinline__ uint64_t seg_end(const uint64_t* keys, uint64_t lo, u
 template <int D, class Emit, bool INLINE_LONG>
 __device__ __forceinline__ void seg_short_rows(const BlockView& blk, const uint64_t* keys, uint64_t n, const SegScratch& sc, const Emit& emit,
                                                uint32_t wave, uint32_t nwaves) {
-    constexpr int L = D / 4;
-    constexpr int GPW = 64 / L;
-    const int lane = threadIdx.x & 63, lg = lane % L, grp = lane / L;
-    const int gbase = grp * L;
+    const LaneGroup<D> lanes(wave, nwaves);
+    constexpr int L = LaneGroup<D>::L;
+    const int lg = lanes.lg, gbase = lanes.grp * L;
     const uint32_t nheads = *sc.nheads;
-    const uint32_t stride = nwaves * GPW;
-    uint32_t h = wave * GPW + grp;
+    const uint32_t stride = (uint32_t)lanes.stride;
+    uint32_t h = (uint32_t)lanes.first();
     auto head_at = [&](uint32_t hh) { return sc.head_pos[hh < nheads ? hh : nheads]; };
     auto window_key = [&](uint32_t p0, uint32_t p1) {  // this lane's key of the segment [p0, p1) (clamped to valid memory)
         const uint32_t c = p1 - p0 < (uint32_t)L ? p1 - p0 : (uint32_t)L;
@@ -2447,7 +2380,7 @@ __device__ __forceinline__ void seg_short_rows(const BlockView& blk, const uint6
     uint32_t p_cur = head_at(h), p_end = head_at(h + 1);
     uint32_t p_next = head_at(h + stride), p_next_end = head_at(h + stride + 1);
     uint64_t kmine = window_key(p_cur, p_end);
-    for (uint32_t h0 = wave * GPW; h0 < nheads; h0 += stride, h += stride) {  // wave-uniform trip count
+    for (uint32_t h0 = (uint32_t)lanes.wave_first; h0 < nheads; h0 += stride, h += stride) {  // wave-uniform trip count
         const bool active = h < nheads;
         const uint32_t p_nn = head_at(h + 2 * stride), p_nn_end = head_at(h + 2 * stride + 1);
         const uint64_t p = p_cur;
@@ -2463,23 +2396,11 @@ __device__ __forceinline__ void seg_short_rows(const BlockView& blk, const uint6
         p_next = p_nn;
         p_next_end = p_nn_end;
         if (INLINE_LONG && len > SBR_SEG_CHUNK) { /* chunk partials in order: the first initialises (seg_chunk / seg_finish) */
-            const RowPrefetch pre = emit.template pre<D>(row, lg);
-            float4 g;
-            float gb;
-            bool has_b;
-            seg_accumulate_long<D, 8>(blk, keys, p, p + SBR_SEG_CHUNK, lg, &g, &gb, &has_b);
-            for (uint64_t q = p + SBR_SEG_CHUNK; q < p + len; q += SBR_SEG_CHUNK) {
-                float4 v;
-                float vb;
-                bool vh;
-                seg_accumulate_long<D, 8>(blk, keys, q, q + SBR_SEG_CHUNK < p + len ? q + SBR_SEG_CHUNK : p + len, lg, &v, &vb, &vh);
-                g.x = g.x + v.x; g.y = g.y + v.y; g.z = g.z + v.z; g.w = g.w + v.w;
-                if (vh) {
-                    gb = has_b ? gb + vb : vb;
-                    has_b = true;
-                }
-            }
-            emit.template row<D>(row, p, lg, g, has_b, gb, pre);
+            const auto pre = emit.template pre<D>(row, lg);
+            RowSum s = seg_accumulate_long<D, 8>(blk, keys, p, p + SBR_SEG_CHUNK, lg);
+            for (uint64_t q = p + SBR_SEG_CHUNK; q < p + len; q += SBR_SEG_CHUNK)
+                s.add_partial(seg_accumulate_long<D, 8>(blk, keys, q, q + SBR_SEG_CHUNK < p + len ? q + SBR_SEG_CHUNK : p + len, lg));
+            emit.template row<D>(row, p, lg, s, pre);
             continue;
         }
         if (!INLINE_LONG && len > SBR_SEG_ROUTE) { /* long segment: registered for the chunked path (or listed already: seg_long_list_kernel) */
@@ -2493,15 +2414,9 @@ __device__ __forceinline__ void seg_short_rows(const BlockView& blk, const uint6
             continue;
         }
         if (!active) continue;
-        const RowPrefetch pre = emit.template pre<D>(row, lg);
-        float4 g;
-        float gb;
-        bool has_b;
-        if (len <= (uint32_t)L) { /* the whole segment is in the window */
-            g = make_float4(0.f, 0.f, 0.f, 0.f);
-            gb = 0.0f;
-            has_b = false;
-            bool first = true;
+        const auto pre = emit.template pre<D>(row, lg);
+        RowSum s;
+        if (len <= (uint32_t)L) { /* the whole segment is in the window: seg_accumulate with the keys taken from the group's lanes */
             for (int e = 0; e < (int)cnt; e += 4) {
                 float4 v[4];
                 float scl[4];
@@ -2512,34 +2427,20 @@ __device__ __forceinline__ void seg_short_rows(const BlockView& blk, const uint6
                     scl[i] = 0.0f;
                     bias[i] = false;
                     if (e + i < (int)cnt) {
-                        const uint32_t src = (uint32_t)__shfl((int)lo, gbase + e + i, 64);
-                        const uint32_t r = src / 3, kind = src % 3;
-                        v[i] = ld4((kind == 0 ? blk.dX : blk.H) + (size_t)r * D + 4 * lg);
-                        scl[i] = kind == 0 ? 1.0f : (kind == 1 ? -blk.coef[r] : blk.coef[r]);
-                        bias[i] = kind != 0;
+                        const EntrySource src = entry_source((uint32_t)__shfl((int)lo, gbase + e + i, 64));
+                        v[i] = ld4(src.rows(blk.dX, blk.H) + (size_t)src.r * D + 4 * lg);
+                        scl[i] = src.scale_at(blk.coef);
+                        bias[i] = src.carries_bias();
                     }
                 }
 #pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    if (e + i < (int)cnt) {
-                        if (first) {
-                            g = make_float4(scl[i] * v[i].x, scl[i] * v[i].y, scl[i] * v[i].z, scl[i] * v[i].w);
-                            first = false;
-                        } else {
-                            g.x = g.x + scl[i] * v[i].x; g.y = g.y + scl[i] * v[i].y;
-                            g.z = g.z + scl[i] * v[i].z; g.w = g.w + scl[i] * v[i].w;
-                        }
-                        if (bias[i]) {
-                            gb = has_b ? gb + scl[i] : scl[i];
-                            has_b = true;
-                        }
-                    }
-                }
+                for (int i = 0; i < 4; ++i)
+                    if (e + i < (int)cnt) s.add_entry(v[i], scl[i], bias[i]);
             }
         } else {
-            seg_accumulate<D>(blk, keys, p, p + len, lg, &g, &gb, &has_b);
+            s = seg_accumulate<D>(blk, keys, p, p + len, lg);
         }
-        emit.template row<D>(row, p, lg, g, has_b, gb, pre);
+        emit.template row<D>(row, p, lg, s, pre);
     }
 }
 template <int D, class Emit, bool INLINE_LONG = false>
@@ -2656,14 +2557,11 @@ __global__ void seg_units_kernel(SegScratch sc) {
 
 template <int D>
 __global__ __launch_bounds__(256, 6) void seg_chunk_kernel(BlockView blk, const uint64_t* keys, SegScratch sc) {
-    constexpr int L = D / 4;
-    constexpr int GPW = 64 / L;
-    const int lane = threadIdx.x & 63, lg = lane % L, grp = lane / L;
-    const uint64_t wave = (blockIdx.x * (uint64_t)blockDim.x + threadIdx.x) >> 6;
-    const uint64_t nwaves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+    const LaneGroup<D> lanes;
+    const int lg = lanes.lg;
     const uint32_t nlong = sc.counters[0] < sc.cap ? sc.counters[0] : sc.cap;
     const uint32_t units = sc.counters[1];
-    for (uint64_t u = wave * GPW + grp; u < units; u += nwaves * GPW) {
+    for (uint64_t u = lanes.first(); u < units; u += lanes.stride) {
         uint32_t lo = 0, hi = nlong; /* last segment whose unit_base <= u */
         while (hi - lo > 1) {
             const uint32_t mid = lo + (hi - lo) / 2;
@@ -2671,31 +2569,24 @@ __global__ __launch_bounds__(256, 6) void seg_chunk_kernel(BlockView blk, const 
         }
         const uint64_t begin = (uint64_t)sc.long_start[lo] + (u - sc.unit_base[lo]) * SBR_SEG_CHUNK;
         const uint64_t end = begin + SBR_SEG_CHUNK < sc.long_end[lo] ? begin + SBR_SEG_CHUNK : sc.long_end[lo];
-        float4 g;
-        float gb;
-        bool has_b;
-        seg_accumulate_long<D, 4>(blk, keys, begin, end, lg, &g, &gb, &has_b);
-        st4(sc.P + u * D + 4 * lg, g);
+        const RowSum s = seg_accumulate_long<D, 4>(blk, keys, begin, end, lg);
+        st4(sc.P + u * D + 4 * lg, s.g);
         if (lg == 0) {
-            sc.Pb[u] = gb;
-            sc.Pf[u] = has_b ? 1u : 0u;
+            sc.Pb[u] = s.gb;
+            sc.Pf[u] = s.has_b() ? 1u : 0u;
         }
     }
 }
 
 template <int D, class Emit>
 __global__ __launch_bounds__(256) void seg_finish_kernel(const uint64_t* keys, SegScratch sc, Emit emit) {
-    constexpr int L = D / 4;
-    constexpr int GPW = 64 / L;
-    const int lane = threadIdx.x & 63, lg = lane % L, grp = lane / L;
-    const uint64_t wave = (blockIdx.x * (uint64_t)blockDim.x + threadIdx.x) >> 6;
-    const uint64_t nwaves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+    const LaneGroup<D> lanes;
+    const int lg = lanes.lg;
     const uint32_t nlong = sc.counters[0] < sc.cap ? sc.counters[0] : sc.cap;
-    for (uint64_t sidx = wave * GPW + grp; sidx < nlong; sidx += nwaves * GPW) {
+    for (uint64_t sidx = lanes.first(); sidx < nlong; sidx += lanes.stride) {
         const uint32_t u0 = sc.unit_base[sidx], u1 = sc.unit_base[sidx + 1];
-        float4 g = ld4(sc.P + (uint64_t)u0 * D + 4 * lg);
-        bool has_b = sc.Pf[u0] != 0;
-        float gb = has_b ? sc.Pb[u0] : 0.0f;
+        const bool hb0 = sc.Pf[u0] != 0;
+        RowSum s(ld4(sc.P + (uint64_t)u0 * D + 4 * lg), hb0 ? sc.Pb[u0] : 0.0f, true, hb0);
         for (uint32_t u = u0 + 1; u < u1; u += 4) { /* chunk partials in order; four loads in flight */
             float4 v[4];
 #pragma unroll
@@ -2703,17 +2594,14 @@ __global__ __launch_bounds__(256) void seg_finish_kernel(const uint64_t* keys, S
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 if (u + i < u1) {
-                    g.x = g.x + v[i].x; g.y = g.y + v[i].y; g.z = g.z + v[i].z; g.w = g.w + v[i].w;
-                    if (sc.Pf[u + i]) {
-                        gb = has_b ? gb + sc.Pb[u + i] : sc.Pb[u + i];
-                        has_b = true;
-                    }
+                    const bool hb = sc.Pf[u + i] != 0; /* (the bias partial is read only where flagged) */
+                    s.add_partial(RowSum(v[i], hb ? sc.Pb[u + i] : 0.0f, true, hb));
                 }
             }
         }
         const uint64_t p = sc.long_start[sidx];
         const uint32_t row = (uint32_t)(keys[p] >> 32);
-        emit.template row<D>(row, p, lg, g, has_b, gb, emit.template pre<D>(row, lg));
+        emit.template row<D>(row, p, lg, s, emit.template pre<D>(row, lg));
     }
 }
 
@@ -2736,15 +2624,12 @@ __global__ void clear_chunk_flags_kernel(void* buf, int nchunks, uint64_t S, int
 // owner: contributions of the devices added in device order (first toucher initialises)
 template <int D, int NQ>  // NQ: devices the row's requests are unrolled for (ndev <= NQ); flags first, then every touched contribution together
 __global__ __launch_bounds__(256) void owner_reduce_kernel(ChunkPtrs recv, int ndev, uint64_t S, void* own) {
-    constexpr int L = D / 4;
-    constexpr int GPW = 64 / L;
-    const int lane = threadIdx.x & 63, lg = lane % L, grp = lane / L;
-    const uint64_t wave = (blockIdx.x * (uint64_t)blockDim.x + threadIdx.x) >> 6;
-    const uint64_t nwaves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+    const LaneGroup<D> lanes;
+    const int lg = lanes.lg;
     float* out = reinterpret_cast<float*>(own);
     uint32_t* ofl = reinterpret_cast<uint32_t*>(out + S * D + S);
-    for (uint64_t i0 = wave * GPW; i0 < S; i0 += nwaves * GPW) {  // wave-uniform trip count
-        const uint64_t i = i0 + grp;
+    for (uint64_t i0 = lanes.wave_first; i0 < S; i0 += lanes.stride) {  // wave-uniform trip count
+        const uint64_t i = i0 + lanes.grp;
         uint32_t f[NQ];
 #pragma unroll
         for (int q = 0; q < NQ; ++q)
@@ -2759,23 +2644,14 @@ __global__ __launch_bounds__(256) void owner_reduce_kernel(ChunkPtrs recv, int n
             if (f[q] & 1u) v[q] = ld4(c + i * D + 4 * lg);
             if (f[q] & 2u) vb[q] = c[S * D + i];
         }
-        float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
-        float gb = 0.0f;
-        uint32_t fl = 0;
+        RowSumW s;
 #pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-            if (f[q] & 1u) {
-                if (fl & 1u) { g.x = g.x + v[q].x; g.y = g.y + v[q].y; g.z = g.z + v[q].z; g.w = g.w + v[q].w; }
-                else g = v[q];
-            }
-            if (f[q] & 2u) gb = (fl & 2u) ? gb + vb[q] : vb[q];
-            fl |= f[q];
-        }
+        for (int q = 0; q < NQ; ++q) s.add_partial(RowSumW(v[q], vb[q], f[q]));
         if (i < S) {
-            if (fl & 1u) st4(out + i * D + 4 * lg, g);
+            if (s.any()) st4(out + i * D + 4 * lg, s.g);
             if (lg == 0) {
-                if (fl & 2u) out[S * D + i] = gb;
-                ofl[i] = fl;
+                if (s.has_b()) out[S * D + i] = s.gb;
+                ofl[i] = s.flags();
             }
         }
     }
@@ -2789,12 +2665,8 @@ __global__ __launch_bounds__(256) void owner_reduce_kernel(ChunkPtrs recv, int n
 // lives on its owner only.
 template <int D, int NQ>  // NQ: devices the row's requests are unrolled for (ndev <= NQ)
 __global__ __launch_bounds__(256) void owner_update_kernel(ModelView m, ChunkPtrs recv, int ndev, uint64_t S, uint64_t row0, uint64_t nrows) {
-    constexpr int L = D / 4;
-    constexpr int GPW = 64 / L;
-    const int lane = threadIdx.x & 63, lg = lane % L, grp = lane / L;
-    const uint64_t wave = (blockIdx.x * (uint64_t)blockDim.x + threadIdx.x) >> 6;
-    const uint64_t nwaves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
-    const bool adam = m.optimizer == SBR_OPT_ADAM;
+    const LaneGroup<D> lanes;
+    const int lg = lanes.lg;
     /* A row is TWO dependent round trips: the devices' flags of the row, then — all requested together — the touched devices'
      * contributions, their bias words and the row's own parameter / optimiser-state quads; the adds stay in device order.  (The
      * first form requested a contribution only after the previous device's had been added: up to ten round trips per row.) */
@@ -2803,10 +2675,10 @@ __global__ __launch_bounds__(256) void owner_update_kernel(ModelView m, ChunkPtr
         for (int q = 0; q < NQ; ++q)
             f[q] = (q < ndev && i < nrows) ? reinterpret_cast<const uint32_t*>(reinterpret_cast<const float*>(recv.p[q]) + S * D + S)[i] : 0u;
     };
-    uint64_t i = wave * GPW + grp;
+    uint64_t i = lanes.first();
     uint32_t f[NQ];
     flags_of(i, f);
-    for (uint64_t i0 = wave * GPW; i0 < nrows; i0 += nwaves * GPW, i += nwaves * GPW) {  // wave-uniform trip count
+    for (uint64_t i0 = lanes.wave_first; i0 < nrows; i0 += lanes.stride, i += lanes.stride) {  // wave-uniform trip count
         uint32_t fl = 0;
 #pragma unroll
         for (int q = 0; q < NQ; ++q) fl |= f[q];
@@ -2821,47 +2693,23 @@ __global__ __launch_bounds__(256) void owner_update_kernel(ModelView m, ChunkPtr
             if (f[q] & 2u) vb[q] = c[S * D + i];
         }
         const uint64_t row = row0 + i;
-        float4 wv = make_float4(0.f, 0.f, 0.f, 0.f), av = wv, mv = wv;
-        float bv = 0.0f, ba = 0.0f, bmm = 0.0f;
-        if (fl & 1u) {
-            wv = ld4(m.E + row * D + 4 * lg);
-            av = ld4(m.Eacc + row * D + 4 * lg);
-            if (adam) mv = ld4(m.Em + row * D + 4 * lg);
-        }
-        if ((fl & 2u) && lg == 0) {
-            bv = m.b[row]; ba = m.bacc[row];
-            if (adam) bmm = m.bm[row];
-        }
+        RowUpdate<D> upd;
+        if (fl & 1u) upd.load(m, row, lg);
+        if ((fl & 2u) && lg == 0) upd.load_bias(m, row);
         uint32_t fcur[NQ];
 #pragma unroll
         for (int q = 0; q < NQ; ++q) fcur[q] = f[q];
-        flags_of(i + nwaves * GPW, f);  /* the next row's flags travel underneath this row's contributions */
-        float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
-        float gb = 0.0f;
-        uint32_t seen = 0;
+        flags_of(i + lanes.stride, f);  /* the next row's flags travel underneath this row's contributions */
+        RowSumW s;
 #pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-            if (fcur[q] & 1u) {
-                if (seen & 1u) { g.x = g.x + v[q].x; g.y = g.y + v[q].y; g.z = g.z + v[q].z; g.w = g.w + v[q].w; }
-                else g = v[q];
-            }
-            if (fcur[q] & 2u) gb = (seen & 2u) ? gb + vb[q] : vb[q];
-            seen |= fcur[q];
+        for (int q = 0; q < NQ; ++q) s.add_partial(RowSumW(v[q], vb[q], fcur[q]));
+        if (fl & 1u) {
+            upd.apply(m, s);
+            upd.store(m, row, lg);
         }
-        if (fl & 1u) {  /* row_update */
-            opt_update(m, &wv.x, &av.x, &mv.x, g.x);
-            opt_update(m, &wv.y, &av.y, &mv.y, g.y);
-            opt_update(m, &wv.z, &av.z, &mv.z, g.z);
-            opt_update(m, &wv.w, &av.w, &mv.w, g.w);
-            st4(m.E + row * D + 4 * lg, wv);
-            st4(m.Eacc + row * D + 4 * lg, av);
-            if (adam) st4(m.Em + row * D + 4 * lg, mv);
-        }
-        if ((fl & 2u) && lg == 0) {  /* bias_update */
-            opt_update(m, &bv, &ba, &bmm, gb);
-            m.b[row] = bv;
-            m.bacc[row] = ba;
-            if (adam) m.bm[row] = bmm;
+        if ((fl & 2u) && lg == 0) {
+            upd.apply_bias(m, s);
+            upd.store_bias(m, row);
         }
     }
 }
@@ -2869,19 +2717,19 @@ __global__ __launch_bounds__(256) void owner_update_kernel(ModelView m, ChunkPtr
 // every device: Adagrad on every touched row from the gathered global sums
 template <int D>
 __global__ __launch_bounds__(256) void table_apply_kernel(ModelView m, ChunkPtrs table, uint64_t S) {
-    constexpr int L = D / 4;
-    constexpr int GPW = 64 / L;
-    const int lane = threadIdx.x & 63, lg = lane % L, grp = lane / L;
-    const uint64_t wave = (blockIdx.x * (uint64_t)blockDim.x + threadIdx.x) >> 6;
-    const uint64_t nwaves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
-    for (uint64_t row = wave * GPW + grp; row < m.num_items; row += nwaves * GPW) {
+    const LaneGroup<D> lanes;
+    const int lg = lanes.lg;
+    for (uint64_t row = lanes.first(); row < m.num_items; row += lanes.stride) {
         const float* c = reinterpret_cast<const float*>(table.p[row / S]); /* the reduced chunk of the row's owner */
         const uint64_t lr = row % S;
         const uint32_t fl = reinterpret_cast<const uint32_t*>(c + S * D + S)[lr];
+        RowUpdate<D> upd;
         if (fl & 1u) {
-            row_update<D>(m, row, lg, ld4(c + lr * D + 4 * lg), false, 0.0f);
+            upd.load(m, row, lg);
+            upd.apply(m, RowSum(ld4(c + lr * D + 4 * lg), 0.0f, 1u));
+            upd.store(m, row, lg);
         }
-        if (fl & 2u) bias_update(m, row, lg, c[S * D + lr]);
+        if (fl & 2u) upd.update_bias(m, row, lg, RowSum(make_float4(0.f, 0.f, 0.f, 0.f), c[S * D + lr], 2u));
     }
 }
 
@@ -2929,15 +2777,11 @@ __global__ void merge_plan_kernel(PeerBounds pb, int ndev, int q, MergePlan* out
 // up to 2 ndev + 2 dependent round trips per row, each of them an xGMI round trip for a peer's list.)
 template <int D, int NQ>
 __global__ __launch_bounds__(256) void owner_list_apply_kernel(ModelView m, PeerLists pl, const uint64_t* mkeys) {
-    constexpr int L = D / 4;
-    constexpr int GPW = 64 / L;
-    const int lane = threadIdx.x & 63, lg = lane % L, grp = lane / L;
-    const uint64_t wave = (blockIdx.x * (uint64_t)blockDim.x + threadIdx.x) >> 6;
-    const uint64_t nwaves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+    const LaneGroup<D> lanes;
+    const int lg = lanes.lg;
     const uint64_t n = pl.plan->base[16];  /* merge keys of this step (grid-stride: the launch does not depend on it) */
-    const bool adam = m.optimizer == SBR_OPT_ADAM;
-    for (uint64_t i0 = wave * GPW; i0 < n; i0 += nwaves * GPW) {  // wave-uniform trip count
-        const uint64_t i = i0 + grp;
+    for (uint64_t i0 = lanes.wave_first; i0 < n; i0 += lanes.stride) {  // wave-uniform trip count
+        const uint64_t i = i0 + lanes.grp;
         uint64_t k[NQ];
 #pragma unroll
         for (int j = 0; j < NQ; ++j) k[j] = i + j < n ? mkeys[i + j] : ~0ull;
@@ -2963,40 +2807,18 @@ __global__ __launch_bounds__(256) void owner_list_apply_kernel(ModelView m, Peer
                 vb[j] = pl.gb[r][p];
             }
         }
-        float4 wv = ld4(m.E + (size_t)row * D + 4 * lg), av = ld4(m.Eacc + (size_t)row * D + 4 * lg);
-        float4 mv = adam ? ld4(m.Em + (size_t)row * D + 4 * lg) : make_float4(0.f, 0.f, 0.f, 0.f);
-        float bv = 0.0f, ba = 0.0f, bmm = 0.0f;
-        if (lg == 0) {  /* requested with the rest; used only if some device's entry carries a bias term */
-            bv = m.b[row]; ba = m.bacc[row];
-            if (adam) bmm = m.bm[row];
-        }
-        float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
-        float gb = 0.0f;
-        bool has_b = false, first = true;
+        RowUpdate<D> upd;
+        upd.load(m, row, lg);
+        if (lg == 0) upd.load_bias(m, row);  /* requested with the rest; used only if some device's entry carries a bias term */
+        RowSum s;
 #pragma unroll
-        for (int j = 0; j < NQ; ++j) {
-            if (in[j]) {
-                if (first) { g = v[j]; first = false; }
-                else { g.x = g.x + v[j].x; g.y = g.y + v[j].y; g.z = g.z + v[j].z; g.w = g.w + v[j].w; }
-                if (vf[j] & 2u) {
-                    gb = has_b ? gb + vb[j] : vb[j];
-                    has_b = true;
-                }
-            }
-        }
-        /* row_update + bias_update */
-        opt_update(m, &wv.x, &av.x, &mv.x, g.x);
-        opt_update(m, &wv.y, &av.y, &mv.y, g.y);
-        opt_update(m, &wv.z, &av.z, &mv.z, g.z);
-        opt_update(m, &wv.w, &av.w, &mv.w, g.w);
-        st4(m.E + (size_t)row * D + 4 * lg, wv);
-        st4(m.Eacc + (size_t)row * D + 4 * lg, av);
-        if (adam) st4(m.Em + (size_t)row * D + 4 * lg, mv);
-        if (has_b && lg == 0) {
-            opt_update(m, &bv, &ba, &bmm, gb);
-            m.b[row] = bv;
-            m.bacc[row] = ba;
-            if (adam) m.bm[row] = bmm;
+        for (int j = 0; j < NQ; ++j)  /* (vf[j] = 0 where !in[j], set above: no bias term without the row's; a head: in[0], the sum is not empty) */
+            s.add_partial(RowSum(v[j], vb[j], in[j], (vf[j] & 2u) != 0));
+        upd.apply(m, s);
+        upd.store(m, row, lg);
+        if (s.has_b() && lg == 0) {
+            upd.apply_bias(m, s);
+            upd.store_bias(m, row);
         }
     }
 }
@@ -3038,11 +2860,10 @@ __global__ void selftest_math_kernel(const float* x, float* e, float* s, float* 
 }
 template <int D>
 __global__ void selftest_dot_tree_kernel(const float* x, const float* y, uint64_t nrows, float* out) {
-    constexpr int L = D / 4;
-    constexpr int GPW = 64 / L;
-    const int lane = threadIdx.x & 63, lg = lane % L, grp = lane / L;
-    const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const uint64_t r = wave * GPW + grp;
+    const LaneGroup<D> lanes;
+    constexpr int L = LaneGroup<D>::L;
+    const int lg = lanes.lg;
+    const uint64_t r = lanes.first();
     const uint64_t rr = r < nrows ? r : nrows - 1;
     const float v = group_allreduce<L>(dot4(ld4(x + rr * D + 4 * lg), ld4(y + rr * D + 4 * lg)));
     if (r < nrows && lg == 0) out[r] = v;
@@ -3082,6 +2903,9 @@ __global__ void selftest_mfma32_chain_kernel(const float* a, const float* b, int
 #ifndef SBR_RESIDENT_WG_PER_CU
 #define SBR_RESIDENT_WG_PER_CU 7
 #endif
+/* lane groups (D / 4 lanes, one row each) in a workgroup of 256 threads */
+template <int D>
+constexpr int groups_per_block() { return 4 * (64 / (D / 4)); }
 static inline int grid_for_groups(long long groups, int groups_per_block) {
     constexpr int per_cu = SBR_RESIDENT_WG_PER_CU;
     long long g = (groups + groups_per_block - 1) / groups_per_block;
@@ -3108,7 +2932,7 @@ void launch_recurrent_forward(const ModelView& m, const MbView& mb, float* H, co
     w.stream_activations = stream_policy(mb.R, m.d) ? 1 : 0;
     if (m.ng == 0) {
         DISPATCH_D(m.d, {
-            const int gpb = 4 * (64 / (DD / 4));
+            constexpr int gpb = groups_per_block<DD>();
             hipLaunchKernelGGL((ewma_forward_kernel<DD>), dim3(grid_for_groups(mb.B, gpb)), dim3(256), 0, s, m, mb, H);
         });
         return;
@@ -3266,7 +3090,7 @@ void launch_recurrent_backward(const ModelView& m, const MbView& mb, const Block
     }
     if (m.ng == 0) {
         DISPATCH_D(m.d, {
-            const int gpb = 4 * (64 / (DD / 4));
+            constexpr int gpb = groups_per_block<DD>();
             hipLaunchKernelGGL((ewma_backward_kernel<DD>), dim3(grid_for_groups(b_host, gpb)), dim3(256), 0, s, m, mb, blk, w);
         });
         return; /* dalpha: launch_dense_gradient (the side stream, beside the sparse update) */
@@ -3426,7 +3250,7 @@ static void launch_seg_reduce(int d, const BlockView& blk, uint32_t rows_host, c
     const uint64_t total = 3ull * rows_host;
     if (total <= SBR_SEG_INLINE_MAX_KEYS) { /* small step: one launch, long segments reduced in place */
         DISPATCH_D(d, {
-            const int gpb = 4 * (64 / (DD / 4));
+            constexpr int gpb = groups_per_block<DD>();
             hipLaunchKernelGGL((seg_short_kernel<DD, Emit, true>), dim3(grid_for_groups((long long)total / 2 + 1, gpb)), dim3(256), 0, s, blk,
                                keys_sorted, total, sc, emit);
         });
@@ -3434,7 +3258,7 @@ static void launch_seg_reduce(int d, const BlockView& blk, uint32_t rows_host, c
     }
     if (!sc.prelisted) (void)hipMemsetAsync(sc.counters, 0, 2 * sizeof(uint32_t), s);
     DISPATCH_D(d, {
-        const int gpb = 4 * (64 / (DD / 4));
+        constexpr int gpb = groups_per_block<DD>();
         /* 4 workgroups per CU: with 8 the update's waves fill the register file and the dense-gradient GEMM on the side
          * stream cannot become resident beside it (measured: 14.04 ms per step at 2048, 13.92 at 1024; the update alone
          * takes the same 1.13-1.2 ms either way) */
@@ -3468,7 +3292,7 @@ void launch_small_back(const ModelView& m, const MbView& mb, const BlockView& bl
     const uint64_t total = 3ull * rows_host;
     DISPATCH_D(m.d, {
         if constexpr (DD <= 32) {
-            const int gpb = 4 * (64 / (DD / 4));
+            constexpr int gpb = groups_per_block<DD>();
             const int seg_blocks = grid_for_groups((long long)total / 2 + 1, gpb);
             const size_t lds = m.ng ? ((size_t)rows_host * m.ng * DD + (size_t)(256 / (m.ng * DD) + 2) * rows_host) * 4 : 0;
             static std::atomic<size_t> granted[64]; /* dynamic LDS beyond 64 KB is granted per kernel and device, once */
@@ -3515,28 +3339,24 @@ void launch_seg_scatter(const ModelView& m, const BlockView& blk, uint32_t rows_
 
 void launch_owner_reduce(const ModelView& m, const ChunkPtrs& recv, int ndev, uint64_t slice_rows, void* own, hipStream_t s) {
     DISPATCH_D(m.d, {
-        const int gpb = 4 * (64 / (DD / 4));
+        constexpr int gpb = groups_per_block<DD>();
         const dim3 grid(grid_for_groups((long long)slice_rows, gpb));
-        if (ndev <= 4) hipLaunchKernelGGL((owner_reduce_kernel<DD, 4>), grid, dim3(256), 0, s, recv, ndev, slice_rows, own);
-        else if (ndev <= 8) hipLaunchKernelGGL((owner_reduce_kernel<DD, 8>), grid, dim3(256), 0, s, recv, ndev, slice_rows, own);
-        else hipLaunchKernelGGL((owner_reduce_kernel<DD, 16>), grid, dim3(256), 0, s, recv, ndev, slice_rows, own);
+        DISPATCH_NQ(ndev, hipLaunchKernelGGL((owner_reduce_kernel<DD, NQ>), grid, dim3(256), 0, s, recv, ndev, slice_rows, own));
     });
 }
 
 void launch_owner_update(const ModelView& m, const ChunkPtrs& recv, int ndev, uint64_t slice_rows, uint64_t row0, uint64_t nrows, hipStream_t s) {
     if (nrows == 0) return;
     DISPATCH_D(m.d, {
-        const int gpb = 4 * (64 / (DD / 4));
+        constexpr int gpb = groups_per_block<DD>();
         const dim3 grid(grid_for_groups((long long)nrows, gpb));
-        if (ndev <= 4) hipLaunchKernelGGL((owner_update_kernel<DD, 4>), grid, dim3(256), 0, s, m, recv, ndev, slice_rows, row0, nrows);
-        else if (ndev <= 8) hipLaunchKernelGGL((owner_update_kernel<DD, 8>), grid, dim3(256), 0, s, m, recv, ndev, slice_rows, row0, nrows);
-        else hipLaunchKernelGGL((owner_update_kernel<DD, 16>), grid, dim3(256), 0, s, m, recv, ndev, slice_rows, row0, nrows);
+        DISPATCH_NQ(ndev, hipLaunchKernelGGL((owner_update_kernel<DD, NQ>), grid, dim3(256), 0, s, m, recv, ndev, slice_rows, row0, nrows));
     });
 }
 
 void launch_table_apply(const ModelView& m, const ChunkPtrs& table, uint64_t slice_rows, hipStream_t s) {
     DISPATCH_D(m.d, {
-        const int gpb = 4 * (64 / (DD / 4));
+        constexpr int gpb = groups_per_block<DD>();
         hipLaunchKernelGGL((table_apply_kernel<DD>), dim3(grid_for_groups((long long)m.num_items, gpb)), dim3(256), 0, s, m, table, slice_rows);
     });
 }
@@ -3557,14 +3377,12 @@ void launch_owner_list_apply(const ModelView& m, const PeerLists& pl_in, const P
     hipLaunchKernelGGL(merge_plan_kernel, dim3(1), dim3(64), 0, s, pb, ndev, owner, plan);
     launch_merge_sort(pl, ndev, capacity, mkeys, mkeys_sorted, sort_temp, sort_temp_bytes, s);  /* (row, device, position) order */
     DISPATCH_D(m.d, {
-        const int gpb = 4 * (64 / (DD / 4));
+        constexpr int gpb = groups_per_block<DD>();
         /* grid-stride over the merge keys, whose number only the device knows: as many lane groups as the capacity would take, at
          * most 2 048 workgroups */
         int grid = grid_for_groups((long long)capacity, gpb);
         if (grid > 2048) grid = 2048;
-        if (ndev <= 4) hipLaunchKernelGGL((owner_list_apply_kernel<DD, 4>), dim3(grid), dim3(256), 0, s, m, pl, mkeys_sorted);
-        else if (ndev <= 8) hipLaunchKernelGGL((owner_list_apply_kernel<DD, 8>), dim3(grid), dim3(256), 0, s, m, pl, mkeys_sorted);
-        else hipLaunchKernelGGL((owner_list_apply_kernel<DD, 16>), dim3(grid), dim3(256), 0, s, m, pl, mkeys_sorted);
+        DISPATCH_NQ(ndev, hipLaunchKernelGGL((owner_list_apply_kernel<DD, NQ>), dim3(grid), dim3(256), 0, s, m, pl, mkeys_sorted));
     });
 }
 
@@ -3573,7 +3391,7 @@ void launch_selftest_math(const float* x, float* out_cell_h, float* out_sig, flo
 }
 void launch_selftest_dot_tree(const float* x, const float* y, int d, uint64_t nrows, float* out, hipStream_t s) {
     DISPATCH_D(d, {
-        const int gpb = 4 * (64 / (DD / 4));
+        constexpr int gpb = groups_per_block<DD>();
         hipLaunchKernelGGL((selftest_dot_tree_kernel<DD>), dim3((unsigned)((nrows + gpb - 1) / gpb)), dim3(256), 0, s, x, y, nrows, out);
     });
 }

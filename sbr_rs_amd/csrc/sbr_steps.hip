@@ -157,6 +157,57 @@ __global__ __launch_bounds__(256) void score_refstream_kernel(ModelView m, MbVie
 // 31 us per step on the reference's Criterion shape, 152 against 118 us on MovieLens-100K.  The launches' dispatch overhead was
 // already hidden behind their predecessors; what a step waits for is its dependent memory round trips and the instruction count
 // of lone waves (~9 cycles per instruction), and one CU's four waves are fewer than the launches' workgroups.  Removed; NOTES.md.)
+// ---- the sparse update of a one-sequence step whose working set is in LDS (ewma_steps_kernel, lstm_steps_kernel) -------------
+// A lane group per SEGMENT of the ordered keys kb[0, n3) (a position whose row differs from its predecessor's starts one); entries
+// in (packed row, kind) order, the first initialises, SBR_SEG_CHUNK-entry chunk partials added in order (RowSum, sbr_device.h).
+// The row's parameters are the gathered copy of any of its entries (X / P / N by the kind of the head's entry), its optimiser
+// state came with the gather (A at the head's position; the bias and its state with the first target / negative entry).
+// EmitApply::row's update (RowUpdate), Adagrad only: the run kernels' shape checks admit nothing else.
+struct StepRows {
+    const float *X, *P, *N, *A;      // gathered E rows of the inputs / targets / negatives; E_acc of the row at segment head p
+    const float *dX, *H, *coef;      // the entries' sources
+    const float *bp, *bn, *bpa, *bna;  // gathered b and b_acc of the targets / negatives
+};
+template <int D, int NGRP>
+__device__ __forceinline__ void steps_sparse_update(const ModelView& m, const uint64_t* kb, int n3, const StepRows& t, int grp, int lg) {
+    for (int p0 = 0; p0 < n3; p0 += NGRP) {
+        const int p = p0 + grp;
+        if (p >= n3) continue;
+        const uint32_t row = (uint32_t)(kb[p] >> 32);
+        if (p > 0 && (uint32_t)(kb[p - 1] >> 32) == row) continue;
+        RowUpdate<D, true> upd;
+        {
+            const EntrySource src = entry_source((uint32_t)kb[p]);
+            upd.w = ld4((src.kind == 0 ? t.X : (src.kind == 1 ? t.P : t.N)) + (size_t)src.r * D + 4 * lg);
+            upd.a = ld4(t.A + (size_t)p * D + 4 * lg);
+        }
+        RowSum tot, chunk;
+        bool have_bias = false;
+        int in_chunk = 0;
+        for (int e = p; e < n3 && (uint32_t)(kb[e] >> 32) == row; ++e) {
+            const EntrySource src = entry_source((uint32_t)kb[e]);
+            chunk.add_entry(ld4(src.rows(t.dX, t.H) + (size_t)src.r * D + 4 * lg), src.scale_at(t.coef), src.carries_bias());
+            if (src.carries_bias() && !have_bias) {
+                upd.bv = src.kind == 1 ? t.bp[src.r] : t.bn[src.r];
+                upd.ba = src.kind == 1 ? t.bpa[src.r] : t.bna[src.r];
+                have_bias = true;
+            }
+            if (++in_chunk == SBR_SEG_CHUNK) { /* a chunk is complete: the partials are added in order, the first initialises */
+                tot.add_partial(chunk);
+                chunk = RowSum();
+                in_chunk = 0;
+            }
+        }
+        if (in_chunk) tot.add_partial(chunk);
+        upd.apply(m, tot);
+        upd.store(m, row, lg);
+        if (tot.has_b() && lg == 0) {
+            upd.apply_bias(m, tot);
+            upd.store_bias(m, row);
+        }
+    }
+}
+
 // ---- EWMA + single-negative loss: a run of one-sequence steps with the step's whole working set in LDS --------------------
 // (ewma.rs:266-352 for one subsequence; sequence_model.rs:111-169 around it.)  A one-sequence EWMA step is ~3 n rows of 4 d bytes
 // and a few hundred flops; as launches — and as the concatenated phases of epoch_steps_kernel — it was a chain of ~10 dependent
@@ -457,65 +508,8 @@ __global__ __launch_bounds__(256) void ewma_steps_kernel(ModelView m, EpochView 
             alphaAcc[lane] = G;
             if (last) blk.dense[lane] = galpha;
         }
-        /* ---- sparse update: a lane group per SEGMENT of the ordered keys (a position whose row differs from its predecessor's starts
-         * one); entries in (packed row, kind) order, the first initialises, SBR_SEG_CHUNK-entry chunk partials added in order.  The
-         * row's parameters are the gathered copy of any of its entries, its optimiser state came with the gather. */
-        for (int p0 = 0; p0 < n3; p0 += NGRP) {
-            const int p = p0 + grp;
-            if (p >= n3) continue;
-            const uint32_t row = (uint32_t)(kb[p] >> 32);
-            if (p > 0 && (uint32_t)(kb[p - 1] >> 32) == row) continue;
-            struct { float4 w, a, mo; } q;
-            {
-                const uint32_t src = (uint32_t)kb[p];
-                const uint32_t r = src / 3, kind = src % 3;
-                q.w = ld4((kind == 0 ? X : (kind == 1 ? P : N)) + (size_t)r * D + 4 * lg);
-                q.a = ld4(A + (size_t)p * D + 4 * lg);
-                q.mo = make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-            float4 tot = make_float4(0.f, 0.f, 0.f, 0.f), g = tot;
-            float totb = 0.0f, gb = 0.0f, bv = 0.0f, ba = 0.0f;
-            bool tot_first = true, tot_hb = false, first = true, has_b = false, have_bias = false;
-            int in_chunk = 0;
-            for (int e = p; e < n3 && (uint32_t)(kb[e] >> 32) == row; ++e) {
-                const uint32_t src = (uint32_t)kb[e];
-                const uint32_t r = src / 3, kind = src % 3;
-                const float4 v = ld4((kind == 0 ? DS : H) + (size_t)r * D + 4 * lg);
-                const float scl = kind == 0 ? 1.0f : (kind == 1 ? -coef[r] : coef[r]);
-                if (first) {
-                    g = make_float4(scl * v.x, scl * v.y, scl * v.z, scl * v.w);
-                    first = false;
-                } else {
-                    g.x = g.x + scl * v.x; g.y = g.y + scl * v.y; g.z = g.z + scl * v.z; g.w = g.w + scl * v.w;
-                }
-                if (kind != 0) {
-                    gb = has_b ? gb + scl : scl;
-                    has_b = true;
-                    if (!have_bias) { bv = kind == 1 ? bp[r] : bn[r]; ba = kind == 1 ? bpa[r] : bna[r]; have_bias = true; }
-                }
-                if (++in_chunk == SBR_SEG_CHUNK) { /* a chunk is complete: the partials are added in order, the first initialises */
-                    if (tot_first) { tot = g; tot_first = false; } else { tot.x = tot.x + g.x; tot.y = tot.y + g.y; tot.z = tot.z + g.z; tot.w = tot.w + g.w; }
-                    if (has_b) { totb = tot_hb ? totb + gb : gb; tot_hb = true; }
-                    first = true; has_b = false; in_chunk = 0; gb = 0.0f;
-                }
-            }
-            if (in_chunk) {
-                if (tot_first) { tot = g; tot_first = false; } else { tot.x = tot.x + g.x; tot.y = tot.y + g.y; tot.z = tot.z + g.z; tot.w = tot.w + g.w; }
-                if (has_b) { totb = tot_hb ? totb + gb : gb; tot_hb = true; }
-            }
-            /* EmitApply::row + bias_update (Adagrad) */
-            sbr_adagrad(&q.w.x, &q.a.x, tot.x, m.lr, m.l2);
-            sbr_adagrad(&q.w.y, &q.a.y, tot.y, m.lr, m.l2);
-            sbr_adagrad(&q.w.z, &q.a.z, tot.z, m.lr, m.l2);
-            sbr_adagrad(&q.w.w, &q.a.w, tot.w, m.lr, m.l2);
-            st4(m.E + (size_t)row * D + 4 * lg, q.w);
-            st4(m.Eacc + (size_t)row * D + 4 * lg, q.a);
-            if (tot_hb && lg == 0) {
-                sbr_adagrad(&bv, &ba, totb, m.lr, m.l2);
-                m.b[row] = bv;
-                m.bacc[row] = ba;
-            }
-        }
+        /* ---- sparse update (steps_sparse_update) */
+        steps_sparse_update<D, NGRP>(m, kb, n3, StepRows{X, P, N, A, DS, H, coef, bp, bn, bpa, bna}, grp, lg);
         SBR_PHASE_CLOCK(3)
         if (last) { /* the block of the run's last step, for sbr_fit_debug_fetch / sbr_fit_sparse_stats */
             for (int idx = tid; idx < n * L; idx += 256) {
@@ -882,61 +876,8 @@ __global__ __launch_bounds__(512) void lstm_steps_kernel(ModelView m, EpochView 
         }
         __syncthreads();
         SBR_PHASE_CLOCK(2)
-        /* ---- sparse update: a lane group per segment of the ordered keys (as in ewma_steps_kernel) */
-        for (int p0 = 0; p0 < n3; p0 += NGRP) {
-            const int p = p0 + grp;
-            if (p >= n3) continue;
-            const uint32_t row = (uint32_t)(kb[p] >> 32);
-            if (p > 0 && (uint32_t)(kb[p - 1] >> 32) == row) continue;
-            float4 qw, qa;
-            {
-                const uint32_t src = (uint32_t)kb[p];
-                const uint32_t r = src / 3, kind = src % 3;
-                qw = ld4((kind == 0 ? X : (kind == 1 ? P : N)) + (size_t)r * D + 4 * lg);
-                qa = ld4(A + (size_t)p * D + 4 * lg);
-            }
-            float4 tot = make_float4(0.f, 0.f, 0.f, 0.f), g = tot;
-            float totb = 0.0f, gb = 0.0f, bv = 0.0f, ba = 0.0f;
-            bool tot_first = true, tot_hb = false, first = true, has_b = false, have_bias = false;
-            int in_chunk = 0;
-            for (int e = p; e < n3 && (uint32_t)(kb[e] >> 32) == row; ++e) {
-                const uint32_t src = (uint32_t)kb[e];
-                const uint32_t r = src / 3, kind = src % 3;
-                const float4 v = ld4((kind == 0 ? DH : H) + (size_t)r * D + 4 * lg);
-                const float scl = kind == 0 ? 1.0f : (kind == 1 ? -coef[r] : coef[r]);
-                if (first) {
-                    g = make_float4(scl * v.x, scl * v.y, scl * v.z, scl * v.w);
-                    first = false;
-                } else {
-                    g.x = g.x + scl * v.x; g.y = g.y + scl * v.y; g.z = g.z + scl * v.z; g.w = g.w + scl * v.w;
-                }
-                if (kind != 0) {
-                    gb = has_b ? gb + scl : scl;
-                    has_b = true;
-                    if (!have_bias) { bv = kind == 1 ? bp[r] : bn[r]; ba = kind == 1 ? bpa[r] : bna[r]; have_bias = true; }
-                }
-                if (++in_chunk == SBR_SEG_CHUNK) {
-                    if (tot_first) { tot = g; tot_first = false; } else { tot.x = tot.x + g.x; tot.y = tot.y + g.y; tot.z = tot.z + g.z; tot.w = tot.w + g.w; }
-                    if (has_b) { totb = tot_hb ? totb + gb : gb; tot_hb = true; }
-                    first = true; has_b = false; in_chunk = 0; gb = 0.0f;
-                }
-            }
-            if (in_chunk) {
-                if (tot_first) { tot = g; tot_first = false; } else { tot.x = tot.x + g.x; tot.y = tot.y + g.y; tot.z = tot.z + g.z; tot.w = tot.w + g.w; }
-                if (has_b) { totb = tot_hb ? totb + gb : gb; tot_hb = true; }
-            }
-            sbr_adagrad(&qw.x, &qa.x, tot.x, m.lr, m.l2);
-            sbr_adagrad(&qw.y, &qa.y, tot.y, m.lr, m.l2);
-            sbr_adagrad(&qw.z, &qa.z, tot.z, m.lr, m.l2);
-            sbr_adagrad(&qw.w, &qa.w, tot.w, m.lr, m.l2);
-            st4(m.E + (size_t)row * D + 4 * lg, qw);
-            st4(m.Eacc + (size_t)row * D + 4 * lg, qa);
-            if (tot_hb && lg == 0) {
-                sbr_adagrad(&bv, &ba, totb, m.lr, m.l2);
-                m.b[row] = bv;
-                m.bacc[row] = ba;
-            }
-        }
+        /* ---- sparse update (steps_sparse_update) */
+        steps_sparse_update<D, NGRP>(m, kb, n3, StepRows{X, P, N, A, DH, H, coef, bp, bn, bpa, bna}, grp, lg);
         SBR_PHASE_CLOCK(3)
         /* ---- dense gradient + dense update: thread (ksub, j) owns column j of the rows k = ksub + 4 e of [x ; h]: per packed row ONE
          * dz value and sixteen broadcast reads of its xh values feed sixteen independent chains (row-ascending from +0: small_back_kernel's

@@ -219,6 +219,8 @@ def test_whole_fit_bit_exact(kind, loss, d, items, users, T, B):
     (ModelKind.LSTM_NORMAL, LOSS_WARP, 128, 8, "gradient"),
     (ModelKind.EWMA, LOSS_HINGE, 256, 8, "owner"),
     (ModelKind.EWMA, LOSS_HINGE, 64, 3, "gradient"),
+    (ModelKind.EWMA, LOSS_WARP, 32, 9, "owner"),       # more than eight devices: the kernels' 16-device instantiations
+    (ModelKind.LSTM_NORMAL, LOSS_HINGE, 32, 9, "gradient"),
 ])
 def test_multi_device_halves_on_one_gpu(kind, loss, d, world, exchange):
     """The multi-GPU protocol through the C-ABI halves with `world` simulated ranks on ONE GPU (tests/simulated_ranks.py: the
@@ -294,6 +296,7 @@ def test_group_fit_single_process(kind, loss, d, world, opt, par):
     (ModelKind.EWMA, LOSS_HINGE, 128, 1, 0),          # a group of one: the table is just mapped memory
     (ModelKind.EWMA, LOSS_HINGE, 256, 8, 0),          # configs[4]'s world: eight owners
     (ModelKind.LSTM_NORMAL, LOSS_WARP, 128, 8, 0),
+    (ModelKind.EWMA, LOSS_WARP, 64, 9, 0),            # more than eight owners: the list merge's 16-device instantiation
 ])
 def test_partitioned_item_table_group_fit(kind, loss, d, world, opt):
     """sbr_group_create(SBR_GROUP_PARTITION_ITEM_TABLE): the item table exists once (row range r on
@@ -731,23 +734,34 @@ def test_movielens_fit_bit_exact_and_mrr(kind, loss, B, bound):
     assert mg > bound
 
 
-@pytest.mark.parametrize("kind,loss,d,mode", [
-    (ModelKind.EWMA, LOSS_HINGE, 32, "single"),
-    (ModelKind.LSTM_NORMAL, LOSS_WARP, 128, "single"),
-    (ModelKind.LSTM_COUPLED, LOSS_BPR, 16, "replicated"),
-    (ModelKind.EWMA, LOSS_WARP, 64, "partitioned"),
+@pytest.mark.parametrize("kind,loss,d,mode,items,opt", [
+    (ModelKind.EWMA, LOSS_HINGE, 32, "single", 9, 0),
+    (ModelKind.LSTM_NORMAL, LOSS_WARP, 128, "single", 9, 0),
+    (ModelKind.LSTM_COUPLED, LOSS_BPR, 16, "replicated", 9, 0),
+    (ModelKind.EWMA, LOSS_WARP, 64, "partitioned", 9, 0),
+    # mixed segment lengths, and Adam, on the chunked path
+    (ModelKind.EWMA, LOSS_HINGE, 256, "single", 120, OPT_ADAM),
+    (ModelKind.LSTM_COUPLED, LOSS_WARP, 64, "replicated", 120, OPT_ADAM),
+    (ModelKind.LSTM_NORMAL, LOSS_BPR, 32, "partitioned", 120, OPT_ADAM),
 ])
-def test_hot_rows_take_the_chunked_reduction(kind, loss, d, mode):
+def test_hot_rows_take_the_chunked_reduction(kind, loss, d, mode, items, opt):
     """A tiny catalogue under a big minibatch: every row collects far more than SBR_SEG_CHUNK (256)
     entries per step, some thousands — the long-segment path (parallel chunk partials, in-order
     combination) of all three consumers of the sparse reduction, bit for bit against the oracle's
-    sequential statement of the same chunked order."""
+    sequential statement of the same chunked order.
+
+    9 items: every segment is longer than 256 entries (0 / 0 / 9 segments in the length classes <= 32 / 33..256 / > 256).
+    120 Zipf items with the same users, T and B (a numpy census of the keys): on one device 9 198 keys per step and
+    14 / 102 / 4 segments in the three classes; on three devices about 6 000 keys per device and step and 69 / 48 / 3
+    segments.  So all three classes occur — the 33..256 class is routed to the chunk kernels as a single chunk — and a
+    step stays above the 4 096 keys up to which the reduction is a single launch.  These cases run Adam, which
+    otherwise never meets the chunk partials' combination or the owners' long rows."""
     from sbr_rs_amd.engine import group_create, group_fit
 
-    items, T, users = 9, 14, 700
+    T, users = 14, 700
     ptr, it = synthetic_interactions(users, items, T + 3, seed=41, zipf=True)
     world = 1 if mode == "single" else 3
-    hp = hparams(items, T, d, int(kind), loss, epochs=2, B=400, ndev=world)
+    hp = hparams(items, T, d, int(kind), loss, epochs=2, B=400, ndev=world, opt=opt, lr=0.02 if opt == OPT_ADAM else 0.16)
     o = OracleModel(hp)
     lo = o.fit(ptr, it)
     if mode == "single":
