@@ -486,12 +486,14 @@ namespace models {
 struct ImplicitUser {
     std::vector<float> user_embedding;
 };
-/// Top-k recommendations of ImplicitSequenceModel::recommend: row-major [num_users][k].
+/// Top-k recommendations of ImplicitSequenceModel::recommend: row-major [num_users][k] (similar_items: a row per query item).
 struct Recommendations {
     std::size_t num_users = 0, k = 0;
     std::vector<std::uint32_t> items;
     std::vector<float> scores;
 };
+/// What ImplicitSequenceModel::similar_items ranks by: the cosine of two item embeddings, or their plain dot product.
+enum class Similarity { Cosine = SBR_SIMILAR_COSINE, Dot = SBR_SIMILAR_DOT };
 /// The loss used for training the model (mod.rs:15-23).
 enum class Loss { BPR = SBR_LOSS_BPR, Hinge = SBR_LOSS_HINGE, WARP = SBR_LOSS_WARP };
 /// Optimizer used to train the model (mod.rs:26-32).
@@ -629,6 +631,27 @@ class ImplicitSequenceModel : public OnlineRankingModel<ImplicitUser> {
                                             r.items.data(), r.scores.data());
         if (st == SBR_ERR_INVALID_PREDICTION) return Result<Recommendations, PredictionError>::Err(PredictionError::InvalidPredictionValue);
         check(st, "sbr_recommend");
+        return Result<Recommendations, PredictionError>::Ok(std::move(r));
+    }
+
+    /// The k items most like each of `items` among the whole catalogue (sbr_similar_items): row j of the result is query
+    /// items[j]'s, by the cosine of the item embeddings (or their dot product; the item bias takes no part), score descending,
+    /// ties to the lower item id.  The query is left out of its own row unless `include_self`; a row with fewer than k eligible
+    /// items is padded with (0xFFFFFFFF, -inf).  Err(InvalidPredictionValue) on a non-finite norm or score.
+    Result<Recommendations, PredictionError> similar_items(const std::vector<ItemId>& items, std::size_t k,
+                                                           Similarity metric = Similarity::Cosine, bool include_self = false) const {
+        if (k < 1 || k > SBR_RECOMMEND_MAX_K) throw EngineError(SBR_ERR_INVALID_ARGUMENT, "similar_items: k outside 1..SBR_RECOMMEND_MAX_K");
+        const std::vector<std::uint32_t> ids = narrow(items);
+        Recommendations r;
+        r.num_users = ids.size();
+        r.k = k;
+        r.items.resize(r.num_users * k);
+        r.scores.resize(r.num_users * k);
+        const sbr_status st = sbr_similar_items(replicas_->primary(), ids.data(), (std::uint64_t)ids.size(), (std::uint32_t)k,
+                                                (std::uint32_t)metric, include_self ? SBR_SIMILAR_INCLUDE_SELF : 0u, nullptr, nullptr,
+                                                r.items.data(), r.scores.data());
+        if (st == SBR_ERR_INVALID_PREDICTION) return Result<Recommendations, PredictionError>::Err(PredictionError::InvalidPredictionValue);
+        check(st, "sbr_similar_items");
         return Result<Recommendations, PredictionError>::Ok(std::move(r));
     }
 

@@ -409,6 +409,31 @@ sbr_status sbr_recommend(sbr_model* m, const uint64_t* user_ptr, const uint32_t*
 sbr_status sbr_recommend_reps(sbr_model* m, const float* reps, uint64_t num_users, uint32_t k,
                               const uint64_t* excl_ptr, const uint32_t* excl_items, uint32_t* out_items, float* out_scores);
 
+/* Exact top-k neighbours of catalogue items: "which items are like this one" (no counterpart in the reference crate: the whole
+ * item table to the host, normalised and sorted there).  With E the item-embedding table — one table, shared by the input side and
+ * the scoring side — and chain_dot(x, y) the k-ascending fused-multiply-add chain from +0.0 that sbr_predict uses:
+ *     n2[i] = chain_dot(E[i], E[i])
+ *     r[i]  = n2[i] > 0 ? 1.0f / sqrtf(n2[i]) : 0.0f                      (IEEE division and square root)
+ *     SBR_SIMILAR_COSINE:  qhat = E[q] * r[q]  (elementwise, each product rounded to f32)
+ *                          s(q, i) = chain_dot(qhat, E[i]) * r[i]
+ *     SBR_SIMILAR_DOT:     s(q, i) = chain_dot(E[q], E[i])                (the same with r == 1.0f; x * 1.0f is exact)
+ * The item bias takes no part.  A zero row has similarity 0 with everything.  Values are not clamped: a duplicate row can score
+ * 1.0000006.  Row j of out_items / out_scores (optional), [num_queries][k], holds the k best items for query_items[j]: score
+ * descending, ties to the lower item id (-0.0 == +0.0); a row with fewer than k eligible items is padded with item 0xFFFFFFFF and
+ * score -inf.  1 <= k <= SBR_RECOMMEND_MAX_K.  The query item is excluded from its own row unless flags has
+ * SBR_SIMILAR_INCLUDE_SELF; excl_ptr / excl_items: optional per-query exclusion lists (CSR, as sbr_recommend_reps': both NULL =
+ * none; the library sorts and de-duplicates them).  Queries may repeat and come in any order; every query gets a row.
+ * SBR_ERR_INVALID_PREDICTION if any n2[i] of the catalogue is non-finite (COSINE) or any score of a scanned pair is;
+ * SBR_ERR_INVALID_ARGUMENT for a query or excluded id >= num_items, k out of range, an unknown metric or flag, or exclusion
+ * arguments of which only one is NULL while a list is non-empty.  num_queries == 0: nothing is done, SBR_OK.  Deterministic; reads
+ * parameters only; runs on every model sbr_recommend runs on. */
+#define SBR_SIMILAR_COSINE 0u
+#define SBR_SIMILAR_DOT 1u
+#define SBR_SIMILAR_INCLUDE_SELF 1u
+sbr_status sbr_similar_items(sbr_model* m, const uint32_t* query_items, uint64_t num_queries, uint32_t k,
+                             uint32_t metric, uint32_t flags, const uint64_t* excl_ptr, const uint32_t* excl_items,
+                             uint32_t* out_items, float* out_scores);
+
 /* Exact ranks of many held-out items per user from ONE scan of the catalogue (no counterpart in the reference crate beyond the one
  * item of evaluation.rs:12-48, whose rule this applies to each target on its own).  With score(u, i) as above and the masked score
  * m(u, i) = f32::MIN if i is in the user's mask list, else score(u, i):

@@ -78,6 +78,7 @@ def load():
         "sbr_mrr_score": [vp, vp, vp, C.c_uint64, fp, vp, u64p],
         "sbr_recommend": [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp],
         "sbr_recommend_reps": [vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp],
+        "sbr_similar_items": [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp],
         "sbr_rank_targets": [vp, vp, vp, C.c_uint64, vp, vp, C.c_uint32, vp],
         "sbr_rank_targets_reps": [vp, vp, C.c_uint64, vp, vp, vp, vp, vp],
         "sbr_model_param_count": [vp, C.c_int32, u64p],
@@ -170,5 +171,5 @@ DECLARED_SYMBOLS = [
     "sbr_fit_step_owner_update", "sbr_model_table_slice", "sbr_model_optimizer_state_gathered", "sbr_model_optimizer_state_is_partial",
     "sbr_group_plan_set_exchange", "sbr_group_gather_optimizer_state", "sbr_comm_gather_optimizer_state",
     "sbr_fit_step_reduce_own_queued", "sbr_fit_step_owner_apply_queued",
-    "sbr_recommend", "sbr_recommend_reps", "sbr_rank_targets", "sbr_rank_targets_reps",
+    "sbr_recommend", "sbr_recommend_reps", "sbr_rank_targets", "sbr_rank_targets_reps", "sbr_similar_items",
 ]

@@ -90,6 +90,15 @@ def build_recommend_tests(force: bool = False, verbose: bool = True) -> str:
     return _build_cpp_program(RECOMMEND_SRC, RECOMMEND_BIN, force, verbose)
 
 
+SIMILAR_SRC = os.path.join(REPO, "tests", "cpp", "similar_tests.cpp")
+SIMILAR_BIN = os.path.join(REPO, "tests", "cpp", "_build", "similar_tests")
+
+
+def build_similar_tests(force: bool = False, verbose: bool = True) -> str:
+    """g++ build of the C++ host layer's similar_items test program."""
+    return _build_cpp_program(SIMILAR_SRC, SIMILAR_BIN, force, verbose)
+
+
 RANKING_SRC = os.path.join(REPO, "tests", "cpp", "ranking_tests.cpp")
 RANKING_BIN = os.path.join(REPO, "tests", "cpp", "_build", "ranking_tests")
 
@@ -104,3 +113,4 @@ if __name__ == "__main__":
     print(build_facade_tests(force="--force" in sys.argv))
     print(build_recommend_tests(force="--force" in sys.argv))
     print(build_ranking_tests(force="--force" in sys.argv))
+    print(build_similar_tests(force="--force" in sys.argv))

@@ -14,6 +14,9 @@
  *                            full staging buffer is sorted and merged into the list (which raises the threshold).
  *   topk_merge_kernel      : one workgroup per user merges the item ranges' lists into the final k, padded with
  *                            (0xFFFFFFFF, -inf).
+ *   item_rnorm_kernel      : similar_items' r[i] = 1 / sqrt(chain_dot(E[i], E[i])) (0 for a zero row) of the whole catalogue
+ *   similar_query_kernel   : similar_items' scan rows H[j] = E[q_j] * r[q_j]; the scan is topk_gemm_kernel with the ScaleMul
+ *                            score policy, s(q, i) = chain_dot(H[j], E[i]) * r[i], r in the bias's place
  *
  * The three GEMM kernels share one catalogue scan, S[u][i] = b[i] + sum_k h[u][k] E[i][k] on v_mfma_f32_32x32x2_f32: a workgroup
  * owns 128 users (4 waves x 32, their states held in registers as MFMA A fragments) and a contiguous range of items, whose
@@ -505,7 +508,16 @@ __global__ __launch_bounds__(64) void rank_targets_finish_kernel(ModelView m, co
 // ------------------------------------------------------------------------------------------------
 // recommend's top k: the catalogue scan with a top-k epilogue, then a merge of the item ranges
 // ------------------------------------------------------------------------------------------------
-template <int D>
+/* What the scan's per-item value (the Bs tile, ModelView::b) does to a dot: recommend adds the item bias, similar_items multiplies
+ * by the item's reciprocal norm (launch_similar_items passes a ModelView whose b is r).  The policy is a constant and TK_SCORE the
+ * one statement of the score, a macro on purpose: through a function of the policy — a forceinline static member, a plain one, a
+ * lambda in the kernel — the BiasAdd instantiations compiled to 12 more VGPRs at every d <= 128 (101 -> 113 at d = 16, 178 -> 190
+ * at d = 128); this form leaves their instruction streams what they were (profiles/similar_items_8192x1M_d128.md). */
+struct BiasAdd { static constexpr bool scale = false; };
+struct ScaleMul { static constexpr bool scale = true; };
+#define TK_SCORE(q) (Score::scale ? acc[q] * bias : bias + acc[q])
+
+template <int D, class Score>
 __global__ __launch_bounds__(256, D <= 128 ? 2 : 1) void topk_gemm_kernel(ModelView m, const float* reps, const int* rep_row, uint32_t num_users,
                                                                          const uint64_t* excl_ptr, const uint32_t* excl_items,
                                                                          uint32_t items_per_group, uint32_t k, uint2* lists, uint32_t* lens,
@@ -648,7 +660,7 @@ __global__ __launch_bounds__(256, D <= 128 ? 2 : 1) void topk_gemm_kernel(ModelV
         uint32_t pend = id < tiles.i_end ? umask : 0u;
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
-            const float sc = bias + acc[q];
+            const float sc = TK_SCORE(q);
             if (((pend >> q) & 1u) && !(sc - sc == 0.0f)) { bad = true; pend &= ~(1u << q); }
         }
         // offers the pending scores: below the threshold they are dropped, above it they take a staging slot if one is left
@@ -663,7 +675,7 @@ __global__ __launch_bounds__(256, D <= 128 ? 2 : 1) void topk_gemm_kernel(ModelV
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const int q = 4 * q4 + j;
-                    const float sc = bias + acc[q];
+                    const float sc = TK_SCORE(q);
                     if (((pend >> q) & 1u) && !tk_better(sc, id, ts[j], ti[j])) pend &= ~(1u << q);
                 }
             }
@@ -671,7 +683,7 @@ __global__ __launch_bounds__(256, D <= 128 ? 2 : 1) void topk_gemm_kernel(ModelV
 #pragma unroll
             for (int q = 0; q < 16; ++q)
                 if ((pend >> q) & 1u) {
-                    const float sc = bias + acc[q];
+                    const float sc = TK_SCORE(q);
                     const uint32_t slot = atomicAdd(&cnt[pbase + q], 1u);
                     if (slot < (uint32_t)TK_STAGE) {
                         st[pbase + q][slot] = make_uint2(__float_as_uint(sc), id);
@@ -696,6 +708,7 @@ __global__ __launch_bounds__(256, D <= 128 ? 2 : 1) void topk_gemm_kernel(ModelV
     }
     if (__any(bad) && lane == 0) atomicOr(nonfinite_flag, 1u);
 }
+#undef TK_SCORE
 
 /* The G sorted lists of one user -> its k best, by a bitonic sort of all their entries in LDS (n = power of two >= G k, at most
  * TK_MERGE_MAX entries; empty slots hold the padding pair, which sorts last). */
@@ -725,6 +738,73 @@ __global__ __launch_bounds__(512) void topk_merge_kernel(const uint2* lists, con
         out_items[(size_t)u * k + j] = e.y;
         if (out_scores) out_scores[(size_t)u * k + j] = __uint_as_float(e.x);
     }
+}
+
+// ------------------------------------------------------------------------------------------------
+// similar_items: reciprocal norms of the catalogue and the scaled query rows; the scan is topk_gemm_kernel<D, ScaleMul>
+// ------------------------------------------------------------------------------------------------
+/* r[i] = n2 > 0 ? 1 / sqrt(n2) : 0 with n2 = chain_dot(E[i], E[i]), and the non-finite flag for a non-finite n2; without `cosine`
+ * r is all 1.0f and nothing is checked (x * 1.0f is exact: the dot-product metric is the same scan).  The chain over a row is
+ * sequential, so one thread owns a row; a workgroup's 256 rows come through LDS CH columns at a time, rows CH + 1 floats apart
+ * (ItemTiles' stride: a wave reads one column of 64 rows from distinct banks), so the global loads are whole 128-byte pieces of
+ * rows next to each other, not 64 lanes at a stride of 4 D bytes. */
+template <int D>
+__global__ __launch_bounds__(256) void item_rnorm_kernel(ModelView m, int cosine, float* r, uint32_t* nonfinite_flag) {
+    constexpr int CH = D < 32 ? D : 32;
+    constexpr int LD = CH + 1;
+    constexpr int ITER = CH / 4; /* float4 loads per thread and column block: 256 rows x CH / 4 quads over 256 threads */
+    __shared__ float Xs[256 * LD];
+    const int tid = threadIdx.x;
+    const uint64_t row0 = (uint64_t)blockIdx.x * 256;
+    const uint64_t row = row0 + (uint64_t)tid;
+    if (!cosine) {
+        if (row < m.num_items) r[row] = 1.0f;
+        return;
+    }
+    float n2 = 0.0f;
+    for (int c0 = 0; c0 < D; c0 += CH) {
+        float4 ev[ITER];
+#pragma unroll
+        for (int it = 0; it < ITER; ++it) {
+            const int idx = tid + it * 256;
+            const int rr = idx / (CH / 4);
+            const int c4 = (idx % (CH / 4)) * 4;
+            ev[it] = row0 + rr < m.num_items ? ld4(m.E + (size_t)(row0 + rr) * D + c0 + c4) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+#pragma unroll
+        for (int it = 0; it < ITER; ++it) {
+            const int idx = tid + it * 256;
+            float* dst = &Xs[(idx / (CH / 4)) * LD + (idx % (CH / 4)) * 4];
+            dst[0] = ev[it].x; dst[1] = ev[it].y; dst[2] = ev[it].z; dst[3] = ev[it].w;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < CH; ++k) {
+            const float x = Xs[tid * LD + k];
+            n2 = sbr_fma(x, x, n2);
+        }
+        __syncthreads();
+    }
+    bool bad = false;
+    if (row < m.num_items) {
+        bad = !(n2 - n2 == 0.0f);
+        r[row] = n2 > 0.0f ? 1.0f / __builtin_sqrtf(n2) : 0.0f;
+    }
+    if (__any(bad) && (tid & 63) == 0) atomicOr(nonfinite_flag, 1u);
+}
+
+/* The scan rows of the launch's queries at storage width: H[j][c] = E[q_j][c] * r[q_j], each product rounded to f32 (the padding
+ * columns stay zero because E's are). */
+template <int D>
+__global__ __launch_bounds__(256) void similar_query_kernel(ModelView m, const float* r, const uint32_t* query, uint32_t num_queries, float* H) {
+    const uint64_t idx = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    const uint64_t j = idx / (D / 4);
+    const int c4 = (int)(idx % (D / 4)) * 4;
+    if (j >= num_queries) return;
+    const uint32_t q = query[j];
+    const float s = r[q];
+    const float4 v = ld4(m.E + (size_t)q * D + c4);
+    st4(H + (size_t)j * D + c4, make_float4(v.x * s, v.y * s, v.z * s, v.w * s));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -797,9 +877,31 @@ void launch_recommend(const ModelView& m, const float* reps, const int* rep_row,
     uint32_t n = 1;
     while (n < groups * k) n <<= 1;
     DISPATCH_D(m.d, {
-        hipLaunchKernelGGL((topk_gemm_kernel<DD>), dim3(utiles, groups), dim3(256), 0, s, m, reps, rep_row, num_users, excl_ptr, excl_items,
+        hipLaunchKernelGGL((topk_gemm_kernel<DD, BiasAdd>), dim3(utiles, groups), dim3(256), 0, s, m, reps, rep_row, num_users, excl_ptr, excl_items,
                            per, k, lists, lens, nonfinite_flag);
         hipLaunchKernelGGL(topk_merge_kernel, dim3(num_users), dim3(512), 0, s, lists, lens, groups, k, n, out_items, out_scores);
+    });
+}
+
+void launch_similar_items(const ModelView& m, const uint32_t* query, uint32_t num_queries, bool cosine, float* rnorm, float* H,
+                          const int* rep_row, const uint64_t* excl_ptr, const uint32_t* excl_items, uint32_t k, uint2* lists,
+                          uint32_t* lens, uint32_t* out_items, float* out_scores, uint32_t* nonfinite_flag, hipStream_t s) {
+    if (num_queries == 0) return;
+    uint32_t per = 0;
+    const uint32_t groups = recommend_groups(num_queries, m.num_items, k, &per);
+    const uint32_t utiles = (num_queries + 127) / 128;
+    uint32_t n = 1;
+    while (n < groups * k) n <<= 1;
+    ModelView mr = m; /* the scan's per-item value: r in the bias's place, so ItemTiles brings it in as it brings the bias */
+    mr.b = rnorm;
+    DISPATCH_D(m.d, {
+        hipLaunchKernelGGL((item_rnorm_kernel<DD>), dim3((unsigned)(((uint64_t)m.num_items + 255) / 256)), dim3(256), 0, s, m, cosine ? 1 : 0, rnorm,
+                           nonfinite_flag);
+        hipLaunchKernelGGL((similar_query_kernel<DD>), dim3((unsigned)(((uint64_t)num_queries * (DD / 4) + 255) / 256)), dim3(256), 0, s, m, rnorm,
+                           query, num_queries, H);
+        hipLaunchKernelGGL((topk_gemm_kernel<DD, ScaleMul>), dim3(utiles, groups), dim3(256), 0, s, mr, H, rep_row, num_queries, excl_ptr, excl_items,
+                           per, k, lists, lens, nonfinite_flag);
+        hipLaunchKernelGGL(topk_merge_kernel, dim3(num_queries), dim3(512), 0, s, lists, lens, groups, k, n, out_items, out_scores);
     });
 }
 

@@ -3486,23 +3486,29 @@ sbr_status check_csr(const sbr_model* m, const uint64_t* ptr, uint64_t n, const 
     return SBR_OK;
 }
 
-/* Where a call's user representations come from: the histories ptr / items (the recurrent forward runs), or the rows `reps`
- * ([users, embedding_dim]) of the caller, ptr / items then being the exclusion lists (ptr null: none). */
+/* Where a call's user representations come from: the histories ptr / items (the recurrent forward runs), the rows `reps`
+ * ([users, embedding_dim]) of the caller, or rows the device makes from the item table, user u's from item item_rows[u]
+ * (similar_items); in the last two cases ptr / items are the exclusion lists (ptr null: none). */
 struct RepSource {
     const uint64_t* ptr;
     const uint32_t* items;
-    const float* reps;  /* null: from histories */
+    const float* reps;  /* null: from histories or item rows */
     uint64_t held_out;  /* histories: this many items at the end of each are not part of it (mrr_score: the test item) */
-    bool lists;         /* whether the sorted, de-duplicated lists of ptr / items are wanted (with reps: always) */
+    bool lists;         /* whether the sorted, de-duplicated lists of ptr / items are wanted (with reps or item rows: always) */
+    const uint32_t* item_rows = nullptr; /* non-null: the rows come from these item ids, on the device */
+    bool from_histories() const { return !reps && !item_rows; }
 };
 
-/* The representations of a chunk's users: user i's is row rep_row[i] of H (eval arena, valid until the next carve_arena);
+/* The representations of a chunk's users: user i's is row rep_row[i] of H (eval arena, valid until the next carve_arena; with
+ * item rows H is not filled yet: the launch does that from d_item_rows);
  * b.list_ptr / b.list_items are the users' sorted, de-duplicated lists (both empty: none). */
 struct UserReps {
     float* H = nullptr;
     std::vector<int> rep_row;
     UserBatch b;
     std::vector<float> gathered; /* caller's rows of users that are not consecutive, read by an asynchronous copy */
+    std::vector<uint32_t> item_rows;  /* item rows: the users' item ids, read by an asynchronous copy into ... */
+    uint32_t* d_item_rows = nullptr;  /* ... the arena; the launch fills H from them */
 };
 
 /* Fills *out for `users` of `s`; `carve_epilogue` as forward_histories' (it may read out->b, which is complete by then).  The
@@ -3517,11 +3523,23 @@ sbr_status user_reps(sbr_model* m, const RepSource& s, const std::vector<uint64_
             list[i] = s.items ? s.items + s.ptr[users[i]] : nullptr;
             n[i] = s.ptr[users[i] + 1] - s.ptr[users[i]] - s.held_out;
         }
-        /* with reps: the caller's lists, sorted and de-duplicated (their state windows go unused) */
+        /* with reps or item rows: the caller's lists, sorted and de-duplicated (their state windows go unused) */
         prepare_users(list, n, T, s.lists, &out->b);
     }
-    if (!s.reps) return forward_histories(m, out->b.first, out->b.nsteps, carve_epilogue, &out->H, &out->rep_row);
-    SBRCHK(carve_arena(m, [&](DeviceArena& ar) { out->H = ar.take<float>(nu * d); carve_epilogue(ar); }));
+    if (s.from_histories()) return forward_histories(m, out->b.first, out->b.nsteps, carve_epilogue, &out->H, &out->rep_row);
+    SBRCHK(carve_arena(m, [&](DeviceArena& ar) {
+        out->H = ar.take<float>(nu * d);
+        if (s.item_rows) out->d_item_rows = ar.take<uint32_t>(nu);
+        carve_epilogue(ar);
+    }));
+    out->rep_row.resize(nu);
+    for (size_t i = 0; i < nu; ++i) out->rep_row[i] = (int)i;
+    if (s.item_rows) {
+        out->item_rows.resize(nu);
+        for (size_t i = 0; i < nu; ++i) out->item_rows[i] = s.item_rows[users[i]];
+        HIPCHK(hipMemcpyAsync(out->d_item_rows, out->item_rows.data(), nu * 4, hipMemcpyHostToDevice, m->stream));
+        return SBR_OK;
+    }
     const float* rows = s.reps + users[0] * dl;
     if (users[nu - 1] - users[0] + 1 != nu) {
         out->gathered.resize(nu * dl);
@@ -3531,8 +3549,6 @@ sbr_status user_reps(sbr_model* m, const RepSource& s, const std::vector<uint64_
     /* padded to the storage width: the columns past embedding_dim are zero, as in the model's own states */
     HIPCHK(hipMemsetAsync(out->H, 0, nu * d * 4, m->stream));
     HIPCHK(hipMemcpy2DAsync(out->H, d * 4, rows, dl * 4, dl * 4, nu, hipMemcpyHostToDevice, m->stream));
-    out->rep_row.resize(nu);
-    for (size_t i = 0; i < nu; ++i) out->rep_row[i] = (int)i;
     return SBR_OK;
 }
 
@@ -3562,7 +3578,7 @@ bool next_chunk(const std::vector<uint64_t>& unit_user, size_t unit_cap, const R
     for (; c1 < unit_user.size() && c1 - c0 < unit_cap; ++c1) {
         const uint64_t u = unit_user[c1];
         if (c1 == c0 || u != unit_user[c1 - 1]) {
-            if (!s.reps) {
+            if (s.from_histories()) {
                 rows += (size_t)std::max<uint64_t>(1, std::min<uint64_t>(s.ptr[u + 1] - s.ptr[u] - s.held_out, T));
                 if (rows > eval_rows_cap && c1 > c0) break;
             }
@@ -3739,8 +3755,10 @@ struct TopkBufs {
     }
 };
 
-/* top-k of every user of `s`, in chunks; results to out_items / out_scores (host, num_users x k; scores optional) */
-sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, uint32_t k, uint32_t* out_items, float* out_scores) {
+/* top-k of every user of `s`, in chunks; results to out_items / out_scores (host, num_users x k; scores optional).  With item rows
+ * (similar_items: the users are the queries) the launch makes the rows itself and ranks by cosine, or by the plain dot product. */
+sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, uint32_t k, uint32_t* out_items, float* out_scores,
+                          bool cosine = false) {
     std::vector<uint64_t> users(num_users);
     for (uint64_t u = 0; u < num_users; ++u) users[u] = u;
     const size_t cap = recommend_users_cap(m, k);
@@ -3748,7 +3766,11 @@ sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, 
         const size_t nu = ch.users.size();
         UserReps ur; /* its lists: what is excluded (list_ptr empty: nothing) */
         TopkBufs tb;
-        SBRCHK(user_reps(m, s, ch.users, [&](DeviceArena& ar) { tb.carve(ar, m, nu, ur.b.list_items.size(), k); }, &ur));
+        float* rnorm = nullptr; /* item rows: the catalogue's reciprocal norms, once per chunk (the arena does not outlive a carve) */
+        SBRCHK(user_reps(m, s, ch.users, [&](DeviceArena& ar) {
+            tb.carve(ar, m, nu, ur.b.list_items.size(), k);
+            if (s.item_rows) rnorm = ar.take<float>(m->hp.num_items);
+        }, &ur));
         const bool excl = !ur.b.list_ptr.empty();
         HIPCHK(hipMemcpyAsync(tb.rep, ur.rep_row.data(), nu * 4, hipMemcpyHostToDevice, m->stream));
         if (excl) {
@@ -3756,9 +3778,13 @@ sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, 
             if (!ur.b.list_items.empty())
                 HIPCHK(hipMemcpyAsync(tb.excl, ur.b.list_items.data(), ur.b.list_items.size() * 4, hipMemcpyHostToDevice, m->stream));
         }
-        SBRCHK(scan_launch(m, 2, tb.flag, [&] {
-            sbr::launch_recommend(m->mv, ur.H, tb.rep, (uint32_t)nu, excl ? tb.eptr : nullptr, tb.excl, k, tb.lists, tb.lens, tb.items,
-                                  out_scores ? tb.scores : nullptr, tb.flag, m->stream);
+        SBRCHK(scan_launch(m, s.item_rows ? 4 : 2, tb.flag, [&] {
+            if (s.item_rows)
+                sbr::launch_similar_items(m->mv, ur.d_item_rows, (uint32_t)nu, cosine, rnorm, ur.H, tb.rep, excl ? tb.eptr : nullptr, tb.excl, k,
+                                          tb.lists, tb.lens, tb.items, out_scores ? tb.scores : nullptr, tb.flag, m->stream);
+            else
+                sbr::launch_recommend(m->mv, ur.H, tb.rep, (uint32_t)nu, excl ? tb.eptr : nullptr, tb.excl, k, tb.lists, tb.lens, tb.items,
+                                      out_scores ? tb.scores : nullptr, tb.flag, m->stream);
         }, {{out_items + ch.c0 * k, tb.items, nu * k * 4}, {out_scores ? out_scores + ch.c0 * k : nullptr, tb.scores, nu * k * 4}}));
     }
     return SBR_OK;
@@ -3791,6 +3817,37 @@ sbr_status sbr_recommend_reps(sbr_model* m, const float* reps, uint64_t num_user
     SBRCHK(ensure_device(m));
     if (excl_ptr) SBRCHK(check_csr(m, excl_ptr, num_users, excl_items, false));
     return recommend_scan(m, RepSource{excl_ptr, excl_items, reps, 0, true}, num_users, k, out_items, out_scores);
+}
+
+/* ---------------------------------------------------------------------------------------------
+ * exact top-k neighbours of catalogue items (sbr_catalogue.hip)
+ * ------------------------------------------------------------------------------------------- */
+sbr_status sbr_similar_items(sbr_model* m, const uint32_t* query_items, uint64_t num_queries, uint32_t k, uint32_t metric, uint32_t flags,
+                             const uint64_t* excl_ptr, const uint32_t* excl_items, uint32_t* out_items, float* out_scores) {
+    if (!m || (num_queries && (!query_items || !out_items))) return SBR_ERR_INVALID_ARGUMENT;
+    if (k < 1 || k > SBR_RECOMMEND_MAX_K || metric > SBR_SIMILAR_DOT || (flags & ~SBR_SIMILAR_INCLUDE_SELF)) return SBR_ERR_INVALID_ARGUMENT;
+    if (!excl_args_ok(excl_ptr, excl_items, num_queries)) return SBR_ERR_INVALID_ARGUMENT;
+    std::lock_guard<std::mutex> lock(m->mu);
+    SBRCHK(ensure_device(m));
+    for (uint64_t j = 0; j < num_queries; ++j)
+        if (query_items[j] >= m->hp.num_items) return SBR_ERR_INVALID_ARGUMENT;
+    if (excl_ptr) SBRCHK(check_csr(m, excl_ptr, num_queries, excl_items, false));
+    /* what a query's row may not hold: the caller's list and, unless it is wanted, the query itself */
+    const bool self = (flags & SBR_SIMILAR_INCLUDE_SELF) != 0;
+    std::vector<uint64_t> eptr;
+    std::vector<uint32_t> eitems;
+    if (!self) {
+        eptr.assign(num_queries + 1, 0);
+        eitems.reserve((size_t)num_queries + (excl_ptr ? (size_t)(excl_ptr[num_queries] - excl_ptr[0]) : 0));
+        for (uint64_t j = 0; j < num_queries; ++j) {
+            if (excl_ptr && excl_ptr[j + 1] > excl_ptr[j]) eitems.insert(eitems.end(), excl_items + excl_ptr[j], excl_items + excl_ptr[j + 1]);
+            eitems.push_back(query_items[j]);
+            eptr[j + 1] = eitems.size();
+        }
+    }
+    RepSource s{self ? excl_ptr : eptr.data(), self ? excl_items : eitems.data(), nullptr, 0, true};
+    s.item_rows = query_items;
+    return recommend_scan(m, s, num_queries, k, out_items, out_scores, metric == SBR_SIMILAR_COSINE);
 }
 
 /* ---------------------------------------------------------------------------------------------

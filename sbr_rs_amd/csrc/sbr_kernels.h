@@ -289,6 +289,13 @@ uint32_t recommend_groups(uint32_t num_users, uint32_t num_items, uint32_t k, ui
 void launch_recommend(const ModelView& m, const float* reps, const int* rep_row, uint32_t num_users, const uint64_t* excl_ptr,
                       const uint32_t* excl_items, uint32_t k, uint2* lists, uint32_t* lens, uint32_t* out_items, float* out_scores,
                       uint32_t* nonfinite_flag, hipStream_t s);
+/* exact top-k neighbours of catalogue items (sbr_catalogue.hip): item_rnorm_kernel writes rnorm [num_items] (1 / |E[i]|, 0 for a zero
+ * row; all 1.0f unless `cosine`) and raises the flag for a non-finite squared norm, similar_query_kernel writes the scan rows
+ * H [num_queries][d] = E[query[j]] * rnorm[query[j]], and launch_recommend's two kernels rank s(j, i) = chain_dot(H[j], E[i]) *
+ * rnorm[i] (no bias) with rep_row, the exclusion lists, lists / lens and the outputs as there (the same recommend_groups split). */
+void launch_similar_items(const ModelView& m, const uint32_t* query, uint32_t num_queries, bool cosine, float* rnorm, float* H,
+                          const int* rep_row, const uint64_t* excl_ptr, const uint32_t* excl_items, uint32_t k, uint2* lists,
+                          uint32_t* lens, uint32_t* out_items, float* out_scores, uint32_t* nonfinite_flag, hipStream_t s);
 /* device self-tests of the numerics contract (tests/test_numerics_gpu.py) */
 void launch_selftest_math(const float* x, float* out_cell_h, float* out_sig, float* out_tanh, uint64_t n, hipStream_t s);
 void launch_selftest_dot_tree(const float* x, const float* y, int d, uint64_t nrows, float* out, hipStream_t s);

@@ -15,6 +15,10 @@ RECOMMEND_MAX_K = 1024  # SBR_RECOMMEND_MAX_K
 RECOMMEND_INCLUDE_HISTORY = 1  # SBR_RECOMMEND_INCLUDE_HISTORY
 RANK_INCLUDE_HISTORY = 1  # SBR_RANK_INCLUDE_HISTORY
 RECOMMEND_NO_ITEM = 0xFFFFFFFF  # item id of a padding entry (its score is -inf)
+SIMILAR_COSINE = 0  # SBR_SIMILAR_COSINE
+SIMILAR_DOT = 1  # SBR_SIMILAR_DOT
+SIMILAR_INCLUDE_SELF = 1  # SBR_SIMILAR_INCLUDE_SELF
+_SIMILAR_METRICS = {"cosine": SIMILAR_COSINE, "dot": SIMILAR_DOT}
 
 
 def _check(st: int):
@@ -562,6 +566,26 @@ class Model:
         ep, ei = _exclusion_csr(exclude, nu)
         _check(self._L.sbr_recommend_reps(self._h, _ptr(reps), nu, int(k) & 0xFFFFFFFF, None if ep is None else _ptr(ep),
                                           None if ei is None else _ptr(ei), _ptr(items), _ptr(scores)))
+        return items, scores
+
+    def similar_items(self, query_items, k: int, metric="cosine", include_self: bool = False, exclude=None):
+        """Exact top-k neighbours of each query item among the whole catalogue (sbr_similar_items): items [Q, k] u32 and scores
+        [Q, k] f32, score descending, ties to the lower id; short rows padded with (RECOMMEND_NO_ITEM, -inf).  metric: "cosine"
+        (of the item embeddings; a zero row has similarity 0 with everything) or "dot" (their plain dot product) — the item bias
+        takes no part in either.  The query itself is left out of its row unless include_self; exclude: None or one sequence of
+        item ids per query.  Queries may repeat."""
+        q = np.ascontiguousarray(query_items, dtype=np.uint32).ravel()
+        if isinstance(metric, str):
+            if metric not in _SIMILAR_METRICS:
+                raise ValueError(f"metric {metric!r}: 'cosine' or 'dot'")
+            metric = _SIMILAR_METRICS[metric]
+        nq = q.size
+        items = np.zeros((nq, max(int(k), 0)), dtype=np.uint32)
+        scores = np.zeros((nq, max(int(k), 0)), dtype=np.float32)
+        ep, ei = _exclusion_csr(exclude, nq)
+        _check(self._L.sbr_similar_items(self._h, _ptr(q), nq, int(k) & 0xFFFFFFFF, int(metric) & 0xFFFFFFFF,
+                                         SIMILAR_INCLUDE_SELF if include_self else 0, None if ep is None else _ptr(ep),
+                                         None if ei is None else _ptr(ei), _ptr(items), _ptr(scores)))
         return items, scores
 
     def rank_targets(self, user_ptr, item_ids, target_ptr, target_items, include_history: bool = False) -> np.ndarray:

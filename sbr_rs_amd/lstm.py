@@ -244,6 +244,13 @@ class _ImplicitSequenceModel:
             it = np.concatenate(seqs) if seqs else np.zeros(0, dtype=np.uint32)
         return self.params.recommend(up, it, k, include_history=not exclude_history)
 
+    def similar_items(self, query_items, k: int, metric: str = "cosine", include_self: bool = False, exclude=None):
+        """The k items most like each query item, on the device: (items [Q, k] u32, scores [Q, k] f32), by the cosine of the
+        item embeddings (``metric="dot"``: their dot product), score descending, ties to the lower item id.  The query is left
+        out of its own row unless ``include_self``; ``exclude``: None or one sequence of item ids per query; a row with fewer
+        than k eligible items is padded with (0xFFFFFFFF, -inf)."""
+        return self.params.similar_items(query_items, k, metric=metric, include_self=include_self, exclude=exclude)
+
     def rank_targets(self, histories, targets, mask_history: bool = True):
         """Exact catalogue ranks of each user's targets from one device scan (``evaluation.rank_targets``): one uint32 array
         per user, in target order."""
