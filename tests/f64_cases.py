@@ -1,5 +1,6 @@
-"""The case table and the one comparison that tests/test_f64_truth.py (oracle, CPU) and tests/test_f64_truth_gpu.py (engine,
-GPU) share: a training step, its intermediates and its optimiser update against tests/f64_model.py.
+"""The case tables and the comparisons that tests/test_f64_truth.py (oracle, CPU) and tests/test_f64_truth_gpu.py (engine,
+GPU) share: a training step, its intermediates and its optimiser update against tests/f64_model.py — on one device (run_case)
+and as the group step of N devices (run_world_case, run_partition_check; second half of the file).
 
 A `driver` hides the only differences between the two implementations' Python bindings (how a model is made, how the two
 halves of a step are called, where the optimiser step count is read).  Nothing here imports the oracle or the engine.
@@ -12,13 +13,14 @@ a stored f32) for the step's intermediates and 2^-24 * max|after| / max|change| 
 """
 from __future__ import annotations
 
+from collections import Counter
 from typing import NamedTuple
 
 import numpy as np
 import torch
 
 import f64_model as F
-from helpers import LOSS_BPR, LOSS_HINGE, LOSS_WARP, OPT_ADAGRAD, OPT_ADAM, hparams, synthetic_interactions
+from helpers import LOSS_BPR, LOSS_HINGE, LOSS_WARP, OPT_ADAGRAD, OPT_ADAM, PAR_ASYNC, PAR_SYNC, hparams, synthetic_interactions
 from sbr_rs_amd._abi import Debug, ModelKind, Param, storage_dim
 
 M_BOUND = {"forward": 32.0, "rowgrad": 32.0, "dense": 32.0, "param": 32.0}
@@ -333,4 +335,283 @@ def run_case(case: Case, driver, mutation=None, steps=3, whole_step=False, setup
                     F.predict(p64, r.astype(np.float64), allit, dtype=torch.float32))
     rep.one_launch_steps = plan.phase_clocks()[5] if hasattr(plan, "phase_clocks") else None
     plan.close()
+    return rep
+
+
+# ================================================================ world N ====================================================
+# The group step of DESIGN.md §8 against tests/f64_model.py: N devices, one optimiser update.  M_BOUND, the floors and
+# MIN_MARGIN are the ones above.
+class WorldCase(NamedTuple):
+    name: str
+    world: int
+    kind: int
+    loss: int
+    d: int
+    items: int             # items % world != 0: the last owner slice is short
+    users: int             # every user is one subsequence of L items; users % world != 0: a remainder is dropped
+    T: int
+    L: int
+    B: int                 # sequences per device and step
+    opt: int = OPT_ADAGRAD
+    l2: float = 4e-4
+    lr: float = 0.16
+    seed: int = 1          # data seed, searched on the CPU so that the input conditions of run_world_case hold
+    pipeline: bool = False  # Parallelism::Asynchronous on a replicated table: the staleness-one pipeline
+    steps: int = 3
+
+
+WORLD_CASES = [
+    WorldCase("w2-normal-hinge-16", 2, NORMAL, LOSS_HINGE, 16, 41, 25, 9, 9, 4, seed=1),
+    WorldCase("w3-ewma-warp-64", 3, EWMA, LOSS_WARP, 64, 100, 38, 10, 10, 4, seed=1),
+    WorldCase("w4-coupled-bpr-24-adam", 4, COUPLED, LOSS_BPR, 24, 90, 39, 8, 8, 3, opt=OPT_ADAM, lr=0.01, seed=1),
+    WorldCase("w8-normal-warp-128", 8, NORMAL, LOSS_WARP, 128, 150, 53, 8, 8, 2, seed=1),
+    WorldCase("w8-ewma-hinge-256", 8, EWMA, LOSS_HINGE, 256, 203, 75, 9, 9, 3, l2=0.0, seed=1),
+    WorldCase("w9-ewma-warp-32", 9, EWMA, LOSS_WARP, 32, 210, 58, 9, 9, 2, seed=1),
+    # three minibatches per epoch, four steps: staleness one at step 2, the restart at step 3 (the next epoch's first)
+    WorldCase("pipe-w2-normal-warp-64", 2, NORMAL, LOSS_WARP, 64, 61, 17, 9, 9, 3, seed=2, pipeline=True, steps=4),
+    WorldCase("pipe-w3-ewma-hinge-32", 3, EWMA, LOSS_HINGE, 32, 70, 32, 10, 10, 4, seed=1, pipeline=True, steps=4),
+]
+WORLD_CASE_BY_NAME = {c.name: c for c in WORLD_CASES}
+
+
+def world_case_data(case: WorldCase):
+    return synthetic_interactions(case.users, case.items, case.L, seed=case.seed, min_len=case.L, zipf=True)
+
+
+def world_hparams(case: WorldCase, rank=0):
+    return hparams(case.items, case.T, case.d, case.kind, case.loss, lr=case.lr, l2=case.l2, epochs=2, B=case.B, opt=case.opt,
+                   ndev=case.world, rank=rank, par=PAR_ASYNC if case.pipeline else PAR_SYNC)
+
+
+_DEBUG_BLOCKS = (Debug.IN_IDX, Debug.OUT_IDX, Debug.NEGATIVES, Debug.HIDDEN, Debug.LOSS, Debug.COEF, Debug.TRIES, Debug.DINPUT,
+                 Debug.DENSE_GRAD, Debug.DHIDDEN)
+
+
+def _read_devices(case, drv, mb):
+    """Every device's debug blocks of the local half that has just run."""
+    out = []
+    for q in range(case.world):
+        R = drv.rows(mb, q)
+        blocks = _DEBUG_BLOCKS if drv.keeps_dhidden else _DEBUG_BLOCKS[:-1]
+        out.append({w: drv.debug_fetch(q, w, R) for w in blocks})
+    return out
+
+
+def _f64(state):
+    return {k: v[0].astype(np.float64) for k, v in state.items()}
+
+
+class _Conditions:
+    """Item 3's conditions on the indices of a group step; each must hold on some step of the case."""
+
+    def __init__(self, case):
+        self.case, self.S = case, (case.items + case.world - 1) // case.world
+        self.every = self.foreign = self.last_slice = self.straddle = False
+        assert case.items % case.world != 0 and (case.world - 1) * self.S < case.items, "no short last owner slice"
+
+    def see(self, dev_rows):
+        case, S, n = self.case, self.S, self.case.world
+        cnt = np.zeros(case.items, dtype=np.int64)
+        sole = np.zeros(case.items, dtype=np.int64)
+        for q, rows in enumerate(dev_rows):
+            cnt[rows] += 1
+            sole[rows] = q
+        self.every |= bool((cnt == n).any())
+        once = np.flatnonzero(cnt == 1)
+        self.foreign |= bool((sole[once] != once // S).any())
+        self.last_slice |= bool((np.flatnonzero(cnt) >= (n - 1) * S).any())
+        self.straddle |= any(cnt[r * S - 1] > 0 and cnt[r * S] > 0 for r in range(1, n) if r * S < case.items)
+
+    def assert_all(self):
+        assert self.every, f"{self.case.name}: no row is referenced by every device in one step"
+        assert self.foreign, f"{self.case.name}: no row is referenced by exactly one device that is not its owner"
+        assert self.last_slice, f"{self.case.name}: no referenced row in the last, short owner slice"
+        assert self.straddle, f"{self.case.name}: no owner change r with rows r*S - 1 and r*S both referenced"
+
+
+def _compare_world_step(rep, case, step, dbgs, snap, snap_mut, before, after, t, mutation, cond, totals, keeps_dhidden):
+    """One group step.  dbgs: the devices' debug blocks; snap: the state the gradient was taken at (snap_mut: where the planted
+    pipeline mutant believes it was taken); before / after: the state around the update."""
+    kind, loss, d, n = case.kind, case.loss, case.d, case.world
+    lr, l2 = float(np.float32(case.lr)), float(np.float32(case.l2))      # as stored: rounded to f32
+    p64, pm = _f64(snap), _f64(snap_mut)
+    mutated_snap = snap_mut is not snap
+    parts, dev_g, dev_idx = [], [], []
+    for q, dbg in enumerate(dbgs):
+        in_idx, out_idx, neg = (dbg[w].astype(np.int64) for w in (Debug.IN_IDX, Debug.OUT_IDX, Debug.NEGATIVES))
+        assert neg.min() >= 0 and neg.max() < case.items
+        off = F.layout_equal_lengths(case.L - 1, len(in_idx))
+        parts.append((in_idx, out_idx, neg, off))
+        dev_idx.append((in_idx, out_idx, neg))
+        g64 = F.step_gradients(kind, loss, d, p64, in_idx, out_idx, neg, off)
+        g32 = F.step_gradients(kind, loss, d, p64, in_idx, out_idx, neg, off, dtype=torch.float32)
+        gm = F.step_gradients(kind, loss, d, pm, in_idx, out_idx, neg, off) if mutated_snap else g64
+        dev_g.append(gm)
+        if loss != LOSS_BPR:
+            assert np.abs(g64["margin"]).min() >= MIN_MARGIN, f"{case.name} step {step} device {q}: a row sits on the kink ({np.abs(g64['margin']).min():.2e})"
+            rep.check(np.array_equal(dbg[Debug.COEF] != 0, g64["margin"] > 0), f"step {step} device {q}: COEF is not non-zero exactly on the violating rows")
+        if loss == LOSS_WARP:
+            tries = dbg[Debug.TRIES]
+            rep.check(tries.min() >= 1 and tries.max() <= 5, f"step {step} device {q}: TRIES outside 1..5")
+            rep.check(bool(np.all(g64["margin"][tries < 5] > 0)), f"step {step} device {q}: a negative kept before the fifth try does not violate")
+        cmp = lambda v, cls, name, key: rep.compare(step, f"dev{q}.{name}", cls, v, gm[key], g32[key], g64[key])
+        cmp(dbg[Debug.HIDDEN][:, :d], "forward", "HIDDEN", "H")
+        cmp(dbg[Debug.LOSS], "forward", "LOSS", "loss")
+        cmp(dbg[Debug.COEF], "rowgrad", "COEF", "coef")
+        if keeps_dhidden:
+            cmp(dbg[Debug.DHIDDEN][:, :d], "rowgrad", "DHIDDEN", "dH")
+        cmp(dbg[Debug.DINPUT][:, :d], "rowgrad", "DINPUT", "dX")
+        dense, pad = unpack_dense(case, dbg[Debug.DENSE_GRAD])
+        for k, v in dense.items():
+            cmp(v, "dense", "DENSE_GRAD." + k, k)
+        pads = [dbg[w][:, d:] for w in (Debug.HIDDEN, Debug.DINPUT) + ((Debug.DHIDDEN,) if keeps_dhidden else ())]
+        rep.check(not _bits(pads[0]).any() and all(not np.any(p) for p in pads) and not np.any(pad),
+                  f"step {step} device {q}: padding columns are not zero")
+        totals[q][0] += g64["loss"].sum()
+        totals[q][1] += g32["loss"].sum()
+        totals[q][2] += len(in_idx)
+    cond.see([np.unique(np.concatenate(ix)) for ix in dev_idx])
+
+    # ---- the one update, from the union minibatch
+    u_in, u_out, u_neg, u_off = F.concat_packed(parts)
+    idx = (u_in, u_out, u_neg)
+    g64 = F.step_gradients(kind, loss, d, p64, u_in, u_out, u_neg, u_off)
+    g32 = F.step_gradients(kind, loss, d, p64, u_in, u_out, u_neg, u_off, dtype=torch.float32)
+    gm = F.step_gradients(kind, loss, d, pm, u_in, u_out, u_neg, u_off) if mutated_snap else g64
+    copy64 = lambda: {k: [None if a is None else a.astype(np.float64) for a in v] for k, v in before.items()}
+    s64, sm = copy64(), copy64()
+    s32 = {k: [None if a is None else a.copy() for a in v] for k, v in before.items()}
+    rows_e, rows_b = F.optimiser_step(kind, case.opt, lr, l2, t, s64, g64, *idx)
+    F.world_optimiser_step(kind, case.opt, lr, l2, t, sm, gm, idx, dev_g, dev_idx, mutation=mutation)
+    F.optimiser_step(kind, case.opt, lr, l2, t, s32, {k: (None if v is None else v.astype(np.float32)) for k, v in g32.items()},
+                     *idx, dtype=np.float32)
+    for name in before:
+        for slot, what in enumerate(("", ".acc", ".m")):
+            if before[name][slot] is None:
+                continue
+            b0 = before[name][slot].astype(np.float64)
+            c64, cm = s64[name][slot] - b0, sm[name][slot] - b0
+            floor = EPS32 * np.abs(after[name][slot]).max() / max(np.abs(cm).max(), 1e-300)
+            rep.compare(step, name + what, "param", after[name][slot].astype(np.float64) - b0, cm,
+                        s32[name][slot].astype(np.float64) - b0, c64, floor=floor)
+    for name, rows in (("E", rows_e), ("b", rows_b)):            # exact: which rows moved, by run_case's rule
+        changed = _changed_rows(before[name], after[name])
+        if case.l2 > 0 or case.opt == OPT_ADAM:
+            rep.check(np.array_equal(changed, rows), f"step {step}: changed {name} rows are not the union's referenced rows "
+                      f"({len(changed)} changed, {len(rows)} referenced)")
+        else:
+            g = g64["gE" if name == "E" else "gb"]
+            moving = rows[np.abs(g[rows]).reshape(len(rows), -1).max(axis=1) > 0]
+            rep.check(np.array_equal(changed, moving), f"step {step}: changed {name} rows are not the union's referenced rows with a gradient")
+
+
+def _after_update(rep, case, drv, step, t):
+    """The state after a group step, read from replica 0 once every replica is bit-identical to it and has counted t steps."""
+    drv.gather_state()
+    states = [fetch_state(case, m) for m in drv.replicas]
+    for q, st in enumerate(states[1:], 1):
+        same = all(np.array_equal(_bits(a), _bits(b)) for k in st for a, b in zip(st[k], states[0][k]) if a is not None)
+        rep.check(same, f"step {step}: replica {q} is not bit-identical to replica 0")
+    rep.check(all(drv.opt_steps(m) == t for m in drv.replicas), f"step {step}: the optimiser step count is not {t} on every replica")
+    return states[0]
+
+
+def run_world_case(case: WorldCase, driver, mutation=None) -> Report:
+    """case.steps group steps of `driver(case, ptr, items)` (see tests/test_f64_truth.py::OracleWorld for what a driver is).
+    Synchronous: every step restarts from seeded state on every replica.  Pipeline: seeded once; the float64 gradient of step
+    k is taken at the state read when step_local(k) ran, the float64 update at the state read when update k was applied."""
+    rep = Report(case)
+    assert mutation is None or mutation in F.WORLD_MUTATIONS
+    n = case.world
+    ptr, items = world_case_data(case)
+    nseq = len(F.subsequences(ptr, items, case.T))
+    assert nseq == case.users and nseq % n != 0, "the partitions must drop a remainder"
+    drv = driver(case, ptr, items)
+    nmb, mb = drv.epoch_prepare(), 0
+    assert nmb == (nseq // n + case.B - 1) // case.B
+    cond = _Conditions(case)
+    totals = [[0.0, 0.0, 0] for _ in range(n)]     # per device: float64 loss sum, float32 loss sum, examples
+    reseed = lambda step: [seed_state(case._replace(seed=case.seed + 1000 * step), m, sum(drv.rows(mb, q) for q in range(n)))
+                           for m in drv.replicas]
+    nonzero = lambda st: case.l2 == 0 or all(np.all(v[0] != 0) for v in st.values())
+    local = prev_snap = None                       # pipeline: (state at step_local, blocks) of the minibatch about to be applied
+    for step in range(case.steps):
+        if mb == nmb:
+            nmb, mb, local = drv.epoch_prepare(), 0, None
+        if not case.pipeline:
+            reseed(step)
+            before = fetch_state(case, drv.replicas[0])
+            t = drv.opt_steps(drv.replicas[0]) + 1
+            drv.step_local(mb)
+            dbgs = _read_devices(case, drv, mb)
+            drv.exchange(mb)
+            snap = snap_mut = before
+        else:
+            if step == 0:
+                reseed(0)
+            if local is None:                      # an epoch's first minibatch: nothing is in flight
+                start = fetch_state(case, drv.replicas[0])
+                drv.step_local(mb)
+                local = (start, _read_devices(case, drv, mb))
+            snap, dbgs = local
+            drv.scatter(mb)
+            before = fetch_state(case, drv.replicas[0])
+            local = None
+            if mb + 1 < nmb and step + 1 < case.steps:   # minibatch mb + 1 is computed before update mb lands
+                drv.step_local(mb + 1)
+                local = (before, _read_devices(case, drv, mb + 1))
+            t = drv.opt_steps(drv.replicas[0]) + 1
+            drv.apply(mb)
+            snap_mut = {None: snap, "pipeline_fresh_gradient": before,
+                        "pipeline_stale_by_two": snap if prev_snap is None else prev_snap}.get(mutation, snap)
+            prev_snap = snap
+        assert nonzero(before), "start values must be non-zero under l2 > 0"
+        after = _after_update(rep, case, drv, step, t)
+        _compare_world_step(rep, case, step, dbgs, snap, snap_mut, before, after, t, mutation, cond, totals, drv.keeps_dhidden)
+        mb += 1
+    cond.assert_all()
+    # ---- the loss of the fit: the devices' terms, each its loss sum over (1 + its examples)
+    got = drv.end()
+    rep.compare("end", "loss", "forward", np.array([got]), np.array([sum(t[0] / (1 + t[2]) for t in totals)]),
+                np.array([sum(t[1] / (1 + t[2]) for t in totals)]))
+    drv.close()
+    return rep
+
+
+def run_partition_check(case: WorldCase, driver, mutation=None) -> Report:
+    """One whole epoch at world N, step by step, exact: from every device's IN_IDX / OUT_IDX of every minibatch its
+    subsequences.  Every device holds floor(nseq / N), the devices' multisets are disjoint parts of the input's, and nseq mod N
+    subsequences (not zero) are trained by nobody.  mutation = "remainder_kept" expects them trained."""
+    rep = Report(case)
+    n = case.world
+    ptr, items = world_case_data(case)
+    have = Counter(F.subsequences(ptr, items, case.T))
+    nseq = sum(have.values())
+    assert nseq % n != 0
+    drv = driver(case, ptr, items)
+    held = [Counter() for _ in range(n)]
+    for mb in range(drv.epoch_prepare()):
+        drv.step_local(mb)
+        for q in range(n):
+            R = drv.rows(mb, q)
+            in_idx, out_idx = (drv.debug_fetch(q, w, R).astype(np.int64) for w in (Debug.IN_IDX, Debug.OUT_IDX))
+            off = F.layout_equal_lengths(case.L - 1, R)
+            held[q].update(F.check_layout(off, in_idx, out_idx, ptr, items, case.T, whole_epoch=False))
+        if case.pipeline:
+            drv.scatter(mb)
+            drv.apply(mb)
+        else:
+            drv.exchange(mb)
+    union = sum(held, Counter())
+    want_each = nseq // n
+    want_missing = 0 if mutation == "remainder_kept" else nseq % n
+    rep.check(all(sum(h.values()) == want_each for h in held), f"a device does not hold floor(nseq / N) = {want_each} subsequences: "
+              f"{[sum(h.values()) for h in held]}")
+    # disjoint as multisets and inside the input: the union takes no subsequence more often than the input has it
+    rep.check(all(have[s] >= c for s, c in union.items()), "the devices' subsequences overlap or are not the input's")
+    missing = nseq - sum(union.values())
+    rep.check(missing == want_missing, f"{missing} subsequences are trained by nobody, not {want_missing}")
+    rep.compare("epoch", "trained", "forward", np.array([float(sum(union.values()))]), np.array([float(nseq - want_missing)]),
+                np.array([float(nseq - nseq % n)]), np.array([float(nseq - nseq % n)]))
+    drv.close()
     return rep

@@ -4,8 +4,11 @@ Written from the crate's graph (lstm.rs:258-337, ewma.rs:266-352, sequence_model
 is torch autograd (float64, or float32 to measure what plain f32 arithmetic loses), the optimiser is numpy.  Nothing here
 imports the oracle or the engine; model and loss kinds are the plain integers of the C ABI.
 
-`mutation=` plants one plausible misreading of the contract (MUTATIONS); tests/test_f64_truth.py uses it to show that the
-comparison can fail.  Nothing else passes it.
+The world-N group step of DESIGN.md §8 is the same step on the concatenation of the N devices' minibatches: `concat_packed`
+and `world_optimiser_step` add nothing else.
+
+`mutation=` plants one plausible misreading of the contract (MUTATIONS; WORLD_MUTATIONS for the world-N step);
+tests/test_f64_truth.py uses it to show that the comparison can fail.  Nothing else passes it.
 """
 from __future__ import annotations
 
@@ -29,6 +32,19 @@ MUTATIONS = (
     "coupled_f_from_i",            # coupled LSTM: first gate block read as i, f = 1 - i
     "adam_decays_untouched_rows",  # moments of untouched rows decayed
     "adam_bias_step_off_by_one",   # 1 - beta^(t + 1)
+)
+
+# Misreadings of the world-N step: each is the identity at N = 1, so only tests/f64_cases.py::run_world_case can
+# see them.  Kept apart from MUTATIONS: those are planted in the one-device step.
+WORLD_MUTATIONS = (
+    "mean_over_devices",                   # the devices' gradients averaged for summed
+    "update_per_device",                   # N optimiser applications per step, one per device in device order
+    "accumulator_of_per_device_squares",   # second moment from sum_q g_q^2 for (sum_q g_q)^2
+    "l2_per_device",                       # the L2 term added once per device
+    "adam_t_counts_devices",               # the step count advances by N
+    "remainder_kept",                      # the nseq mod N subsequences beyond the partitions trained as well
+    "pipeline_fresh_gradient",             # Asynchronous: gradient k taken after update k - 1 (staleness 0)
+    "pipeline_stale_by_two",               # Asynchronous: gradient k taken where gradient k - 1 was taken (staleness 2)
 )
 
 
@@ -96,6 +112,23 @@ def check_layout(off, in_idx, out_idx, ptr, items, T, whole_epoch):
     else:
         assert all(have[s] >= c for s, c in got.items()), "a column is not a subsequence of the input"
     return seqs
+
+
+def concat_packed(parts):
+    """The N devices' minibatches of one group step as ONE packed minibatch: parts[q] = (in_idx, out_idx, neg, off) as read
+    back from device q.  The sequences of all devices, longest first (device order among equals), packed time-major again.
+    Returns (in_idx, out_idx, neg, off) of the union."""
+    cols = [(q, rows) for q, part in enumerate(parts) for rows in columns(part[3])]
+    order = sorted(range(len(cols)), key=lambda c: -len(cols[c][1]))     # stable
+    off = offsets_from_steps([len(cols[c][1]) for c in order])
+    out = [np.zeros(int(off[-1]), dtype=np.int64) for _ in range(3)]
+    for b, c in enumerate(order):
+        q, rows = cols[c]
+        dst = off[:len(rows)] + b
+        for k in range(3):
+            out[k][dst] = np.asarray(parts[q][k], dtype=np.int64)[rows]
+    assert int(off[-1]) == sum(len(part[0]) for part in parts)
+    return out[0], out[1], out[2], off
 
 
 # ---------------------------------------------------------------- the graph ---------------------------------------------------
@@ -200,30 +233,33 @@ def predict(params, rep, item_ids, dtype=torch.float64):
 
 
 # ---------------------------------------------------------------- the optimiser -----------------------------------------------
-def _apply(opt, w, acc, mom, g, lr, l2, t, ft, l2_mask=None, mutation=None):
-    """Element update of DESIGN §2 on arrays of one shape, in place.  acc: Adagrad's sum of squares / Adam's second moment."""
+def _apply(opt, w, acc, mom, g, lr, l2, t, ft, l2_mask=None, mutation=None, cross=None):
+    """Element update of DESIGN §2 on arrays of one shape, in place.  acc: Adagrad's sum of squares / Adam's second moment.
+    cross (a world mutant's only): subtracted from the square of the gradient."""
     g = g + (l2 * w if l2_mask is None else l2 * w * l2_mask)
+    gg = g * g if cross is None else g * g - cross
     if opt == OPT_ADAGRAD:
-        acc += g * g
+        acc += gg
         w -= lr / (ft(1e-10) + np.sqrt(acc)) * g
     else:
         b1, b2 = ft(0.9), ft(0.999)
         if mutation == "adam_bias_step_off_by_one":
             t = t + 1
         mom[...] = b1 * mom + (1 - b1) * g
-        acc[...] = b2 * acc + (1 - b2) * g * g
+        acc[...] = b2 * acc + (1 - b2) * gg
         c1, c2 = ft(1.0 - 0.9 ** t), ft(1.0 - 0.999 ** t)
         w -= lr / (np.sqrt(acc / c2) + ft(1e-8)) * (mom / c1)
 
 
-def optimiser_step(kind, opt, lr, l2, t, state, grads, in_idx, out_idx, neg, dtype=np.float64, mutation=None):
+def optimiser_step(kind, opt, lr, l2, t, state, grads, in_idx, out_idx, neg, dtype=np.float64, mutation=None, cross=None):
     """state: {name: (w, acc, mom or None)} for E, b and the dense parameters, updated in place (arrays of `dtype`).
-    t: the optimiser step being taken, counted from 1.  Returns (touched embedding rows, touched bias rows)."""
+    t: the optimiser step being taken, counted from 1.  Returns (touched embedding rows, touched bias rows).
+    cross: {gradient name: array} taken off the squared gradients (world_optimiser_step's accumulator mutant only)."""
     ft = dtype
     lr, l2 = ft(lr), ft(l2)
     for k in dense_names(kind):
         w, acc, mom = state[k]
-        _apply(opt, w, acc, mom, grads[k].astype(dtype), lr, l2, t, ft, mutation=mutation)
+        _apply(opt, w, acc, mom, grads[k].astype(dtype), lr, l2, t, ft, mutation=mutation, cross=None if cross is None else cross[k])
     rows_e = np.unique(np.concatenate([in_idx, out_idx, neg]).astype(np.int64))
     rows_b = np.unique(np.concatenate([out_idx, neg] + ([in_idx] if mutation == "bias_touched_by_inputs" else [])).astype(np.int64))
     if mutation == "update_per_occurrence":
@@ -238,7 +274,8 @@ def optimiser_step(kind, opt, lr, l2, t, state, grads, in_idx, out_idx, neg, dty
             mask = (nz.any(axis=1, keepdims=True) if gr.ndim == 2 else nz).astype(dtype)
         wr, ar = w[rows], acc[rows]
         mr = mom[rows] if mom is not None else None
-        _apply(opt, wr, ar, mr, gr, lr, l2, t, ft, l2_mask=mask, mutation=mutation)
+        _apply(opt, wr, ar, mr, gr, lr, l2, t, ft, l2_mask=mask, mutation=mutation,
+               cross=None if cross is None else cross["gE" if name == "E" else "gb"][rows])
         w[rows], acc[rows] = wr, ar
         if mom is not None:
             mom[rows] = mr
@@ -247,6 +284,32 @@ def optimiser_step(kind, opt, lr, l2, t, state, grads, in_idx, out_idx, neg, dty
                 mom[rest] *= ft(0.9)
                 acc[rest] *= ft(0.999)
     return rows_e, rows_b
+
+
+def world_optimiser_step(kind, opt, lr, l2, t, state, grads, idx, dev_grads, dev_idx, dtype=np.float64, mutation=None):
+    """The ONE optimiser update of a world-N group step: `optimiser_step` on the union minibatch — grads and
+    idx = (in_idx, out_idx, neg) of concat_packed's union; the devices' gradients are summed there because the union's loss
+    is one sum.  L2 once, one accumulator update from the summed gradient, t advances by 1.  dev_grads / dev_idx (the same
+    per device) serve the mutants alone.  Returns (touched embedding rows, touched bias rows) of the union."""
+    n = len(dev_idx)
+    names = ("gE", "gb") + dense_names(kind)
+    rows = optimiser_step(kind, opt, lr, l2, t, {k: [None if a is None else a.copy() for a in v] for k, v in state.items()},
+                          grads, *idx, dtype=dtype)           # the union's touched rows, whatever the mutant does
+    if mutation == "update_per_device":
+        for q in range(n):
+            optimiser_step(kind, opt, lr, l2, t, state, dev_grads[q], *dev_idx[q], dtype=dtype)
+        return rows
+    cross = None
+    if mutation == "mean_over_devices":
+        grads = dict(grads, **{k: grads[k] / n for k in names})
+    elif mutation == "l2_per_device":
+        l2 = l2 * n
+    elif mutation == "adam_t_counts_devices":
+        t = t * n
+    elif mutation == "accumulator_of_per_device_squares":
+        cross = {k: sum(g[k] for g in dev_grads) ** 2 - sum(g[k] ** 2 for g in dev_grads) for k in names}
+    optimiser_step(kind, opt, lr, l2, t, state, grads, *idx, dtype=dtype, cross=cross)
+    return rows
 
 
 def _per_occurrence(opt, lr, l2, t, state, grads, in_idx, out_idx, neg, ft):
