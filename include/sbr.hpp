@@ -634,6 +634,54 @@ class ImplicitSequenceModel : public OnlineRankingModel<ImplicitUser> {
         return Result<Recommendations, PredictionError>::Ok(std::move(r));
     }
 
+    /// `recommend` with every item outside `among` ineligible (sbr_recommend_among): the exact top k of that item set — ids in any
+    /// order, duplicates allowed — as catalogue ids, ordered and padded as `recommend`'s rows.  Only the set's rows are scanned: an
+    /// empty set gives rows of padding, and a non-finite score outside the set does not fail the call.
+    Result<Recommendations, PredictionError> recommend(const data::CompressedInteractions& interactions, std::size_t k, bool exclude_history,
+                                                       const std::vector<ItemId>& among) const {
+        if (k < 1 || k > SBR_RECOMMEND_MAX_K) throw EngineError(SBR_ERR_INVALID_ARGUMENT, "recommend: k outside 1..SBR_RECOMMEND_MAX_K");
+        const std::vector<std::uint32_t> subset = narrow(among);
+        Recommendations r;
+        r.num_users = interactions.num_users();
+        r.k = k;
+        r.items.resize(r.num_users * k);
+        r.scores.resize(r.num_users * k);
+        const sbr_status st = sbr_recommend_among(replicas_->primary(), interactions.user_pointers().data(), interactions.item_ids().data(),
+                                                  (std::uint64_t)r.num_users, (std::uint32_t)k, exclude_history ? 0u : SBR_RECOMMEND_INCLUDE_HISTORY,
+                                                  subset.data(), (std::uint64_t)subset.size(), r.items.data(), r.scores.data());
+        if (st == SBR_ERR_INVALID_PREDICTION) return Result<Recommendations, PredictionError>::Err(PredictionError::InvalidPredictionValue);
+        check(st, "sbr_recommend_among");
+        return Result<Recommendations, PredictionError>::Ok(std::move(r));
+    }
+
+    /// `user_representation` of every history of `histories` in one device pass (sbr_user_representations): row-major
+    /// [num_users][embedding_dim], row u with the bits of the single call on history u.
+    std::vector<float> user_representations(const data::CompressedInteractions& histories) const {
+        std::vector<float> reps(histories.num_users() * (std::size_t)replicas_->hparams().embedding_dim);
+        check(sbr_user_representations(replicas_->primary(), histories.user_pointers().data(), histories.item_ids().data(),
+                                       (std::uint64_t)histories.num_users(), reps.data()),
+              "sbr_user_representations");
+        return reps;
+    }
+
+    /// `predict` for many users in one device pass (sbr_score_candidates): user u's history is row u of `histories`, its
+    /// candidates cand_items[cand_ptr[u] .. cand_ptr[u + 1]) (any order, duplicates allowed, none included).  One score per
+    /// candidate, in candidate order, with the bits of `predict`; nothing is masked.  Err(InvalidPredictionValue) on a
+    /// non-finite score.
+    Result<std::vector<float>, PredictionError> score_candidates(const data::CompressedInteractions& histories,
+                                                                 const std::vector<std::uint64_t>& cand_ptr,
+                                                                 const std::vector<std::uint32_t>& cand_items) const {
+        using R = Result<std::vector<float>, PredictionError>;
+        if (cand_ptr.size() != histories.num_users() + 1 || cand_ptr.back() < cand_ptr.front() || cand_ptr.back() > cand_items.size())
+            throw EngineError(SBR_ERR_INVALID_ARGUMENT, "score_candidates: one candidate range per user");
+        std::vector<float> scores(cand_ptr.back() - cand_ptr.front());
+        const sbr_status st = sbr_score_candidates(replicas_->primary(), histories.user_pointers().data(), histories.item_ids().data(),
+                                                   (std::uint64_t)histories.num_users(), cand_ptr.data(), cand_items.data(), scores.data());
+        if (st == SBR_ERR_INVALID_PREDICTION) return R::Err(PredictionError::InvalidPredictionValue);
+        check(st, "sbr_score_candidates");
+        return R::Ok(std::move(scores));
+    }
+
     /// The k items most like each of `items` among the whole catalogue (sbr_similar_items): row j of the result is query
     /// items[j]'s, by the cosine of the item embeddings (or their dot product; the item bias takes no part), score descending,
     /// ties to the lower item id.  The query is left out of its own row unless `include_self`; a row with fewer than k eligible

@@ -434,6 +434,44 @@ sbr_status sbr_similar_items(sbr_model* m, const uint32_t* query_items, uint64_t
                              uint32_t metric, uint32_t flags, const uint64_t* excl_ptr, const uint32_t* excl_items,
                              uint32_t* out_items, float* out_scores);
 
+/* Recommend within an item subset, batched candidate scoring, batched representations (no counterparts in the reference crate:
+ * loops over user_representation and predict, and a host-side filter).  Throughout, score(u, i) = bias[i] + chain_dot(rep_u, E[i])
+ * has the bits of sbr_predict, and a history's representation is sbr_user_representation's (last max_sequence_length items; an
+ * empty history = item 0).  All five calls are deterministic, read parameters only, run on every model sbr_recommend runs on and
+ * refuse where it refuses.
+ *
+ * sbr_user_representations: out_reps [num_users][embedding_dim]; row u has the bits of sbr_user_representation of history
+ * item_ids[user_ptr[u] .. user_ptr[u + 1]), and every user gets a row.  Ids are validated as sbr_recommend validates them.
+ * num_users == 0: nothing is done, SBR_OK.
+ *
+ * sbr_score_candidates / _reps: the batched sbr_predict.  User u's candidates are cand_items[cand_ptr[u] .. cand_ptr[u + 1]): any
+ * number, none included, in any order, duplicates allowed; out_scores[e - cand_ptr[0]] = score(u, cand_items[e]), in the caller's
+ * order, nothing masked.  SBR_ERR_INVALID_PREDICTION if any computed score is non-finite (out_scores is then unspecified);
+ * SBR_ERR_INVALID_ARGUMENT for decreasing pointers, ids >= num_items, cand_items NULL while a list is non-empty.  No pairs: nothing is
+ * done, SBR_OK.  _reps: from representations (embedding_dim floats each).
+ *
+ * sbr_recommend_among / _reps: sbr_recommend / sbr_recommend_reps with every item outside S = subset_items[0 .. num_subset)
+ * ineligible — the same order (score descending, ties to the lower item id, -0.0 == +0.0), padding (0xFFFFFFFF, -inf), range of k,
+ * history / exclusion rules and flags; out_items holds catalogue ids, not positions in S.  S may be unsorted and hold duplicates
+ * (the library sorts and de-duplicates it); num_subset == 0 gives rows of padding; with S the whole catalogue the result is bit-equal
+ * to sbr_recommend's.  Only pairs (scanned user, item of S) are scored: a non-finite score outside S does not fail the call, one
+ * inside S does (SBR_ERR_INVALID_PREDICTION).  SBR_ERR_INVALID_ARGUMENT for an id >= num_items in S, and wherever sbr_recommend /
+ * sbr_recommend_reps give it.  Each launch copies S's rows and biases into scratch, |S| * (4 * storage width + 4) bytes;
+ * SBR_ERR_OUT_OF_MEMORY if the device cannot hold that. */
+sbr_status sbr_user_representations(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids,
+                                    uint64_t num_users, float* out_reps);
+sbr_status sbr_score_candidates(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users,
+                                const uint64_t* cand_ptr, const uint32_t* cand_items, float* out_scores);
+sbr_status sbr_score_candidates_reps(sbr_model* m, const float* reps, uint64_t num_users,
+                                     const uint64_t* cand_ptr, const uint32_t* cand_items, float* out_scores);
+sbr_status sbr_recommend_among(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users,
+                               uint32_t k, uint32_t flags, const uint32_t* subset_items, uint64_t num_subset,
+                               uint32_t* out_items, float* out_scores);
+sbr_status sbr_recommend_among_reps(sbr_model* m, const float* reps, uint64_t num_users, uint32_t k,
+                                    const uint64_t* excl_ptr, const uint32_t* excl_items,
+                                    const uint32_t* subset_items, uint64_t num_subset,
+                                    uint32_t* out_items, float* out_scores);
+
 /* Exact ranks of many held-out items per user from ONE scan of the catalogue (no counterpart in the reference crate beyond the one
  * item of evaluation.rs:12-48, whose rule this applies to each target on its own).  With score(u, i) as above and the masked score
  * m(u, i) = f32::MIN if i is in the user's mask list, else score(u, i):

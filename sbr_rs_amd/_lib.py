@@ -79,6 +79,11 @@ def load():
         "sbr_recommend": [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp],
         "sbr_recommend_reps": [vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp],
         "sbr_similar_items": [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp],
+        "sbr_user_representations": [vp, vp, vp, C.c_uint64, vp],
+        "sbr_score_candidates": [vp, vp, vp, C.c_uint64, vp, vp, vp],
+        "sbr_score_candidates_reps": [vp, vp, C.c_uint64, vp, vp, vp],
+        "sbr_recommend_among": [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, C.c_uint64, vp, vp],
+        "sbr_recommend_among_reps": [vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp, C.c_uint64, vp, vp],
         "sbr_rank_targets": [vp, vp, vp, C.c_uint64, vp, vp, C.c_uint32, vp],
         "sbr_rank_targets_reps": [vp, vp, C.c_uint64, vp, vp, vp, vp, vp],
         "sbr_model_param_count": [vp, C.c_int32, u64p],
@@ -172,4 +177,5 @@ DECLARED_SYMBOLS = [
     "sbr_group_plan_set_exchange", "sbr_group_gather_optimizer_state", "sbr_comm_gather_optimizer_state",
     "sbr_fit_step_reduce_own_queued", "sbr_fit_step_owner_apply_queued",
     "sbr_recommend", "sbr_recommend_reps", "sbr_rank_targets", "sbr_rank_targets_reps", "sbr_similar_items",
+    "sbr_user_representations", "sbr_score_candidates", "sbr_score_candidates_reps", "sbr_recommend_among", "sbr_recommend_among_reps",
 ]

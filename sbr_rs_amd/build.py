@@ -99,6 +99,15 @@ def build_similar_tests(force: bool = False, verbose: bool = True) -> str:
     return _build_cpp_program(SIMILAR_SRC, SIMILAR_BIN, force, verbose)
 
 
+CANDIDATES_SRC = os.path.join(REPO, "tests", "cpp", "candidates_tests.cpp")
+CANDIDATES_BIN = os.path.join(REPO, "tests", "cpp", "_build", "candidates_tests")
+
+
+def build_candidates_tests(force: bool = False, verbose: bool = True) -> str:
+    """g++ build of the C++ host layer's recommend-among / score_candidates test program."""
+    return _build_cpp_program(CANDIDATES_SRC, CANDIDATES_BIN, force, verbose)
+
+
 RANKING_SRC = os.path.join(REPO, "tests", "cpp", "ranking_tests.cpp")
 RANKING_BIN = os.path.join(REPO, "tests", "cpp", "_build", "ranking_tests")
 
@@ -114,3 +123,4 @@ if __name__ == "__main__":
     print(build_recommend_tests(force="--force" in sys.argv))
     print(build_ranking_tests(force="--force" in sys.argv))
     print(build_similar_tests(force="--force" in sys.argv))
+    print(build_candidates_tests(force="--force" in sys.argv))

@@ -17,6 +17,11 @@
  *   item_rnorm_kernel      : similar_items' r[i] = 1 / sqrt(chain_dot(E[i], E[i])) (0 for a zero row) of the whole catalogue
  *   similar_query_kernel   : similar_items' scan rows H[j] = E[q_j] * r[q_j]; the scan is topk_gemm_kernel with the ScaleMul
  *                            score policy, s(q, i) = chain_dot(H[j], E[i]) * r[i], r in the bias's place
+ *   subset_gather_kernel   : recommend_among's sub-table E'[j] = E[S[j]], b'[j] = b[S[j]] of a sorted, unique item set S; the scan is
+ *                            topk_gemm_kernel + topk_merge_kernel on a ModelView of E', b', |S|, and
+ *   subset_ids_kernel      : maps the merged lists' positions in S back to catalogue ids
+ *   candidate_score_kernel : score_candidates' b[i] + chain_dot(rep_u, E[i]) of a flat list of (user, item) pairs, 64 per wave
+ *   rep_rows_kernel        : user_representations' rows rep_row[i] of H, embedding_dim floats each, in user order
  *
  * The three GEMM kernels share one catalogue scan, S[u][i] = b[i] + sum_k h[u][k] E[i][k] on v_mfma_f32_32x32x2_f32: a workgroup
  * owns 128 users (4 waves x 32, their states held in registers as MFMA A fragments) and a contiguous range of items, whose
@@ -808,6 +813,113 @@ __global__ __launch_bounds__(256) void similar_query_kernel(ModelView m, const f
 }
 
 // ------------------------------------------------------------------------------------------------
+// recommend_among: the sub-table of an item set S and the way back from positions in S to catalogue ids
+// ------------------------------------------------------------------------------------------------
+/* E'[j] = E[S[j]] at storage width and b'[j] = b[S[j]]: one thread per 16-byte quad, so a row's D / 4 threads are neighbours and
+ * both the read and the write are whole 4 D-byte runs.  The rows are read once and the copy is what the scan then reads 64 times
+ * over: the reads stream, the writes stay plain. */
+template <int D>
+__global__ __launch_bounds__(256) void subset_gather_kernel(ModelView m, const uint32_t* subset, uint32_t num_subset, float* Es, float* bs) {
+    const uint64_t idx = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    const uint64_t j = idx / (D / 4);
+    const int c4 = (int)(idx % (D / 4)) * 4;
+    if (j >= num_subset) return;
+    const uint32_t i = subset[j];
+    st4(Es + (size_t)j * D + c4, ld4s(m.E + (size_t)i * D + c4));
+    if (c4 == 0) bs[j] = m.b[i];
+}
+
+/* items[e] = S[items[e]] for the n entries of the merged rows; the padding id stays what it is.  S is sorted and unique, so the
+ * order of positions the scan ranked ties by is the order of ids. */
+__global__ __launch_bounds__(256) void subset_ids_kernel(const uint32_t* subset, uint32_t* items, uint64_t n) {
+    const uint64_t e = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= n) return;
+    const uint32_t p = items[e];
+    if (p != TK_NONE) items[e] = subset[p];
+}
+
+// ------------------------------------------------------------------------------------------------
+// score_candidates: b[i] + chain_dot(rep_u, E[i]) of a flat list of (user, item) pairs
+// ------------------------------------------------------------------------------------------------
+/* A wave owns 64 consecutive pairs, lane l the pair p0 + l: its item row comes through the wave's own LDS block CH columns at a time
+ * (item_rnorm_kernel's layout: rows CH + 1 floats apart, a lane reads its row's column from its own bank), so the global loads are
+ * CH / 4 neighbouring lanes per 4 CH-byte piece of a row, not 64 lanes at a stride of 4 D bytes; every piece of a row is read once
+ * by the launch, so the loads stream (score_kernel's policy for its one-touch rows).  The lane then runs predict's chain — k
+ * ascending from +0.0, one sbr_fma per column — against its user's representation row rep[pair_row[p]], which neighbouring pairs of
+ * one user share (a broadcast, and cache-resident), and adds the bias.  No workgroup barrier: the four waves of a workgroup
+ * share nothing.  Lanes past the last pair gather row 0 and store nothing. */
+template <int D>
+__global__ __launch_bounds__(256) void candidate_score_kernel(ModelView m, const float* reps, const uint32_t* pair_row, const uint32_t* pair_item,
+                                                              uint64_t num_pairs, float* out, uint32_t* nonfinite_flag) {
+    constexpr int CH = D < 32 ? D : 32;
+    constexpr int LD = CH + 1;
+    constexpr int ITER = CH / 4; /* float4 loads per lane and column block: 64 rows x CH / 4 quads over 64 lanes */
+    __shared__ float Xs[4][64 * LD];
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    float* X = Xs[wave];
+    const uint64_t p = ((uint64_t)blockIdx.x * 4 + wave) * 64 + lane;
+    const bool real = p < num_pairs;
+    const uint32_t item = real ? pair_item[p] : 0u;
+    const float* h = reps + (size_t)(real ? pair_row[p] : 0u) * D;
+    float acc = 0.0f;
+    float4 ev[ITER];
+    auto fetch = [&](int c0) { /* the wave's 64 rows' columns [c0, c0 + CH): quad idx % (CH / 4) of row idx / (CH / 4) */
+#pragma unroll
+        for (int it = 0; it < ITER; ++it) {
+            const int idx = lane + it * 64;
+            const uint32_t ri = (uint32_t)__shfl((int)item, idx / (CH / 4), 64);
+            ev[it] = ld4s(m.E + (size_t)ri * D + c0 + (idx % (CH / 4)) * 4);
+        }
+    };
+    fetch(0);
+    /* not unrolled: unrolled, the compiler hoists every block's loads to the top — 264 VGPRs at d = 128, spills at d = 256 */
+#pragma unroll 1
+    for (int c0 = 0; c0 < D; c0 += CH) {
+#pragma unroll
+        for (int it = 0; it < ITER; ++it) {
+            const int idx = lane + it * 64;
+            float* dst = &X[(idx / (CH / 4)) * LD + (idx % (CH / 4)) * 4];
+            dst[0] = ev[it].x; dst[1] = ev[it].y; dst[2] = ev[it].z; dst[3] = ev[it].w;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        if (c0 + CH < D) fetch(c0 + CH); /* the next block is in flight under this block's chain */
+#pragma unroll
+        for (int k4 = 0; k4 < CH; k4 += 4) {
+            const float4 hv = ld4(h + c0 + k4);
+            acc = sbr_fma(hv.x, X[lane * LD + k4 + 0], acc);
+            acc = sbr_fma(hv.y, X[lane * LD + k4 + 1], acc);
+            acc = sbr_fma(hv.z, X[lane * LD + k4 + 2], acc);
+            acc = sbr_fma(hv.w, X[lane * LD + k4 + 3], acc);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+    bool bad = false;
+    if (real) {
+        const float sc = m.b[item] + acc;
+        bad = !(sc - sc == 0.0f);
+        out[p] = sc;
+    }
+    if (__any(bad) && lane == 0) atomicOr(nonfinite_flag, 1u);
+}
+
+// ------------------------------------------------------------------------------------------------
+// user_representations: the users' final states out of the forward pass's packed rows
+// ------------------------------------------------------------------------------------------------
+/* out[i][c] = H[rep_row[i]][c] for c < dl (embedding_dim; H's rows are d floats): the rows in user order and at the caller's width,
+ * so one copy brings the launch's representations to the host. */
+__global__ __launch_bounds__(256) void rep_rows_kernel(const float* H, const int* rep_row, uint32_t num_users, int d, int dl, float* out) {
+    const uint64_t idx = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    const uint64_t i = idx / (uint64_t)dl;
+    if (i >= num_users) return;
+    out[idx] = H[(size_t)rep_row[i] * d + (idx - i * (uint64_t)dl)];
+}
+
+// ------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------
 void launch_predict(const ModelView& m, const float* user, const uint32_t* items, uint64_t n, float* out, hipStream_t s) {
@@ -903,6 +1015,37 @@ void launch_similar_items(const ModelView& m, const uint32_t* query, uint32_t nu
                            per, k, lists, lens, nonfinite_flag);
         hipLaunchKernelGGL(topk_merge_kernel, dim3(num_queries), dim3(512), 0, s, lists, lens, groups, k, n, out_items, out_scores);
     });
+}
+
+void launch_recommend_among(const ModelView& m, const uint32_t* subset, uint32_t num_subset, float* Esub, float* bsub, const float* reps,
+                            const int* rep_row, uint32_t num_users, const uint64_t* excl_ptr, const uint32_t* excl_items, uint32_t k,
+                            uint2* lists, uint32_t* lens, uint32_t* out_items, float* out_scores, uint32_t* nonfinite_flag, hipStream_t s) {
+    if (num_users == 0 || num_subset == 0) return;
+    DISPATCH_D(m.d, {
+        hipLaunchKernelGGL((subset_gather_kernel<DD>), dim3((unsigned)(((uint64_t)num_subset * (DD / 4) + 255) / 256)), dim3(256), 0, s, m, subset,
+                           num_subset, Esub, bsub);
+    });
+    ModelView ms = m; /* the scan's catalogue: the sub-table, whose item j is S[j] */
+    ms.E = Esub;
+    ms.b = bsub;
+    ms.num_items = num_subset;
+    launch_recommend(ms, reps, rep_row, num_users, excl_ptr, excl_items, k, lists, lens, out_items, out_scores, nonfinite_flag, s);
+    const uint64_t n = (uint64_t)num_users * k;
+    hipLaunchKernelGGL(subset_ids_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, subset, out_items, n);
+}
+
+void launch_candidate_scores(const ModelView& m, const float* reps, const uint32_t* pair_row, const uint32_t* pair_item, uint64_t num_pairs,
+                             float* out, uint32_t* nonfinite_flag, hipStream_t s) {
+    if (num_pairs == 0) return;
+    DISPATCH_D(m.d, {
+        hipLaunchKernelGGL((candidate_score_kernel<DD>), dim3((unsigned)((num_pairs + 255) / 256)), dim3(256), 0, s, m, reps, pair_row, pair_item,
+                           num_pairs, out, nonfinite_flag);
+    });
+}
+
+void launch_rep_rows(const float* H, const int* rep_row, uint32_t num_users, int d, int dl, float* out, hipStream_t s) {
+    if (num_users == 0) return;
+    hipLaunchKernelGGL(rep_rows_kernel, dim3((unsigned)(((uint64_t)num_users * dl + 255) / 256)), dim3(256), 0, s, H, rep_row, num_users, d, dl, out);
 }
 
 }  // namespace sbr

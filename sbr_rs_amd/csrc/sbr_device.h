@@ -19,6 +19,16 @@ typedef float f32x16 __attribute__((ext_vector_type(16))); /* the accumulators o
 
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
+// the streaming (non-temporal, `nt`) forms, for rows a kernel touches once (which kernels use them: sbr_kernels.hip, sbr_catalogue.hip)
+typedef float v4f_nt __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ float4 ld4s(const float* p) {
+    const v4f_nt v = __builtin_nontemporal_load(reinterpret_cast<const v4f_nt*>(p));
+    return make_float4(v.x, v.y, v.z, v.w);
+}
+__device__ __forceinline__ void st4s(float* p, float4 v) {
+    v4f_nt t; t.x = v.x; t.y = v.y; t.z = v.z; t.w = v.w;
+    __builtin_nontemporal_store(t, reinterpret_cast<v4f_nt*>(p));
+}
 
 // All-reduce over the L lanes of a group in the contract's tree order: p += p[lane ^ off] for off = L/2 ... 1
 // (the dot order of sbr_numerics.h).  Every step is a cross-lane move inside the VALU — v_permlane32_swap /

@@ -3724,26 +3724,27 @@ namespace {
  * ranges * k <= TK_MERGE_MAX the lists of 8 192 users are at most 512 MB, so the loop halves at most once: 8 192 users while
  * ranges * k <= 4 096 (every k <= 256: at most 16 ranges are wanted for 64 user tiles), 4 096 users above that (possible from
  * k = 257 on; k = 1 024 from 5 ranges on) or where SBR_CATALOGUE_GROUPS forces more ranges. */
-size_t recommend_users_cap(const sbr_model* m, uint32_t k) {
+size_t recommend_users_cap(uint32_t num_items, uint32_t k) {
     size_t cap = eval_units_cap;
     for (;;) {
         uint32_t per = 0;
-        const uint32_t g = sbr::recommend_groups((uint32_t)cap, (uint32_t)m->hp.num_items, k, &per);
+        const uint32_t g = sbr::recommend_groups((uint32_t)cap, num_items, k, &per);
         if (cap <= 128 || cap * g * k * 8 <= ((size_t)256 << 20)) return cap;
         cap /= 2;
     }
 }
 
-/* device buffers of launch_recommend over nu users with nexcl exclusion entries */
+/* device buffers of launch_recommend over nu users with nexcl exclusion entries and a catalogue of num_items (the model's, or the
+ * size of recommend_among's item set: the scan splits what it scans) */
 struct TopkBufs {
     int* rep;
     uint64_t* eptr;
     uint32_t *excl, *lens, *items, *flag;
     uint2* lists;
     float* scores;
-    void carve(DeviceArena& ar, const sbr_model* m, size_t nu, size_t nexcl, uint32_t k) {
+    void carve(DeviceArena& ar, uint32_t num_items, size_t nu, size_t nexcl, uint32_t k) {
         uint32_t per = 0;
-        const size_t g = sbr::recommend_groups((uint32_t)nu, (uint32_t)m->hp.num_items, k, &per);
+        const size_t g = sbr::recommend_groups((uint32_t)nu, num_items, k, &per);
         rep = ar.take<int>(nu);
         eptr = ar.take<uint64_t>(nu + 1);
         excl = ar.take<uint32_t>(nexcl + 1);
@@ -3755,31 +3756,71 @@ struct TopkBufs {
     }
 };
 
+/* device buffers of recommend_among's sub-table of ns items, made anew by every launch (the arena does not outlive a carve) */
+struct SubsetBufs {
+    uint32_t* ids;
+    float *E, *b;
+    void carve(DeviceArena& ar, size_t ns, size_t d) {
+        ids = ar.take<uint32_t>(ns);
+        E = ar.take<float>(ns * d);
+        b = ar.take<float>(ns);
+    }
+};
+
+/* The users' sorted, de-duplicated lists as positions in the sorted, unique item set `subset`; entries outside it are dropped (they
+ * are not scanned).  Both sides ascend, so the positions do too. */
+void lists_to_subset_positions(const std::vector<uint32_t>& subset, std::vector<uint64_t>* list_ptr, std::vector<uint32_t>* list_items) {
+    size_t w = 0;
+    for (size_t u = 0; u + 1 < list_ptr->size(); ++u) {
+        const uint64_t e0 = (*list_ptr)[u], e1 = (*list_ptr)[u + 1];
+        (*list_ptr)[u] = w; /* w <= e0: entry u + 1 is still the old bound when user u + 1 reads it */
+        auto at = subset.begin();
+        for (uint64_t e = e0; e < e1; ++e) {
+            at = std::lower_bound(at, subset.end(), (*list_items)[e]);
+            if (at == subset.end()) break;
+            if (*at == (*list_items)[e]) (*list_items)[w++] = (uint32_t)(at - subset.begin());
+        }
+    }
+    if (!list_ptr->empty()) list_ptr->back() = w;
+    list_items->resize(w);
+}
+
 /* top-k of every user of `s`, in chunks; results to out_items / out_scores (host, num_users x k; scores optional).  With item rows
- * (similar_items: the users are the queries) the launch makes the rows itself and ranks by cosine, or by the plain dot product. */
+ * (similar_items: the users are the queries) the launch makes the rows itself and ranks by cosine, or by the plain dot product.
+ * With `subset` (recommend_among: sorted, unique, not empty) only its items are scanned, as a sub-table every launch gathers. */
 sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, uint32_t k, uint32_t* out_items, float* out_scores,
-                          bool cosine = false) {
+                          bool cosine = false, const std::vector<uint32_t>* subset = nullptr) {
     std::vector<uint64_t> users(num_users);
     for (uint64_t u = 0; u < num_users; ++u) users[u] = u;
-    const size_t cap = recommend_users_cap(m, k);
+    const uint32_t scanned_items = subset ? (uint32_t)subset->size() : (uint32_t)m->hp.num_items;
+    const size_t cap = recommend_users_cap(scanned_items, k);
     for (Chunk ch; next_chunk(users, cap, s, m->hp.max_sequence_length, &ch);) {
         const size_t nu = ch.users.size();
         UserReps ur; /* its lists: what is excluded (list_ptr empty: nothing) */
         TopkBufs tb;
+        SubsetBufs sb;
         float* rnorm = nullptr; /* item rows: the catalogue's reciprocal norms, once per chunk (the arena does not outlive a carve) */
         SBRCHK(user_reps(m, s, ch.users, [&](DeviceArena& ar) {
-            tb.carve(ar, m, nu, ur.b.list_items.size(), k);
+            tb.carve(ar, scanned_items, nu, ur.b.list_items.size(), k);
             if (s.item_rows) rnorm = ar.take<float>(m->hp.num_items);
+            if (subset) sb.carve(ar, subset->size(), (size_t)m->d);
         }, &ur));
         const bool excl = !ur.b.list_ptr.empty();
+        if (subset) {
+            if (excl) lists_to_subset_positions(*subset, &ur.b.list_ptr, &ur.b.list_items);
+            HIPCHK(hipMemcpyAsync(sb.ids, subset->data(), subset->size() * 4, hipMemcpyHostToDevice, m->stream));
+        }
         HIPCHK(hipMemcpyAsync(tb.rep, ur.rep_row.data(), nu * 4, hipMemcpyHostToDevice, m->stream));
         if (excl) {
             HIPCHK(hipMemcpyAsync(tb.eptr, ur.b.list_ptr.data(), (nu + 1) * 8, hipMemcpyHostToDevice, m->stream));
             if (!ur.b.list_items.empty())
                 HIPCHK(hipMemcpyAsync(tb.excl, ur.b.list_items.data(), ur.b.list_items.size() * 4, hipMemcpyHostToDevice, m->stream));
         }
-        SBRCHK(scan_launch(m, s.item_rows ? 4 : 2, tb.flag, [&] {
-            if (s.item_rows)
+        SBRCHK(scan_launch(m, s.item_rows || subset ? 4 : 2, tb.flag, [&] {
+            if (subset)
+                sbr::launch_recommend_among(m->mv, sb.ids, scanned_items, sb.E, sb.b, ur.H, tb.rep, (uint32_t)nu, excl ? tb.eptr : nullptr, tb.excl,
+                                            k, tb.lists, tb.lens, tb.items, out_scores ? tb.scores : nullptr, tb.flag, m->stream);
+            else if (s.item_rows)
                 sbr::launch_similar_items(m->mv, ur.d_item_rows, (uint32_t)nu, cosine, rnorm, ur.H, tb.rep, excl ? tb.eptr : nullptr, tb.excl, k,
                                           tb.lists, tb.lens, tb.items, out_scores ? tb.scores : nullptr, tb.flag, m->stream);
             else
@@ -3848,6 +3889,147 @@ sbr_status sbr_similar_items(sbr_model* m, const uint32_t* query_items, uint64_t
     RepSource s{self ? excl_ptr : eptr.data(), self ? excl_items : eitems.data(), nullptr, 0, true};
     s.item_rows = query_items;
     return recommend_scan(m, s, num_queries, k, out_items, out_scores, metric == SBR_SIMILAR_COSINE);
+}
+
+/* ---------------------------------------------------------------------------------------------
+ * recommend within an item subset, batched candidate scoring, batched representations (sbr_catalogue.hip)
+ * ------------------------------------------------------------------------------------------- */
+namespace {
+
+/* recommend_scan over the item set subset_items[0, num_subset) — validated, sorted and de-duplicated here; an empty set is rows of
+ * padding without a scan */
+sbr_status recommend_among_scan(sbr_model* m, const RepSource& s, uint64_t num_users, uint32_t k, const uint32_t* subset_items,
+                                uint64_t num_subset, uint32_t* out_items, float* out_scores) {
+    if (num_subset && !subset_items) return SBR_ERR_INVALID_ARGUMENT;
+    for (uint64_t j = 0; j < num_subset; ++j)
+        if (subset_items[j] >= m->hp.num_items) return SBR_ERR_INVALID_ARGUMENT;
+    std::vector<uint32_t> subset(subset_items, subset_items + num_subset);
+    std::sort(subset.begin(), subset.end());
+    subset.erase(std::unique(subset.begin(), subset.end()), subset.end());
+    if (subset.empty()) {
+        std::fill(out_items, out_items + num_users * k, 0xFFFFFFFFu);
+        if (out_scores) std::fill(out_scores, out_scores + num_users * k, -INFINITY);
+        return SBR_OK;
+    }
+    return recommend_scan(m, s, num_users, k, out_items, out_scores, false, &subset);
+}
+
+/* device buffers of launch_candidate_scores over np pairs */
+struct CandidateBufs {
+    uint32_t *row, *item, *flag;
+    float* scores;
+    void carve(DeviceArena& ar, size_t np) {
+        row = ar.take<uint32_t>(np);
+        item = ar.take<uint32_t>(np);
+        scores = ar.take<float>(np);
+        flag = ar.take<uint32_t>(1);
+    }
+};
+
+/* Scores of every user's candidates, users from `s`.  The users that have candidates go through next_chunk; a chunk's pairs are
+ * contiguous in cand_items (the users between them have none) and are scored in launches of at most candidate_pairs_cap pairs
+ * against the chunk's one forward pass, a launch ending wherever in a user's list the cap falls. */
+sbr_status score_candidates_scan(sbr_model* m, const RepSource& s, uint64_t num_users, const uint64_t* cand_ptr, const uint32_t* cand_items,
+                                 float* out_scores) {
+    if (!cand_ptr) return SBR_ERR_INVALID_ARGUMENT;
+    SBRCHK(check_csr(m, cand_ptr, num_users, cand_items, false));
+    if (cand_ptr[num_users] == cand_ptr[0]) return SBR_OK;
+    if (!out_scores) return SBR_ERR_INVALID_ARGUMENT;
+    std::vector<uint64_t> users;
+    for (uint64_t u = 0; u < num_users; ++u)
+        if (cand_ptr[u + 1] > cand_ptr[u]) users.push_back(u);
+    for (Chunk ch; next_chunk(users, eval_units_cap, s, m->hp.max_sequence_length, &ch);) {
+        const size_t nu = ch.users.size();
+        const uint64_t p0 = cand_ptr[ch.users[0]], p1 = cand_ptr[ch.users[nu - 1] + 1];
+        const size_t cap = (size_t)std::min<uint64_t>(p1 - p0, sbr::candidate_pairs_cap);
+        UserReps ur;
+        CandidateBufs cb;
+        SBRCHK(user_reps(m, s, ch.users, [&](DeviceArena& ar) { cb.carve(ar, cap); }, &ur));
+        std::vector<uint32_t> row(cap);
+        size_t i = 0; /* the chunk's user of the pair in hand */
+        for (uint64_t q = p0; q < p1; q += cap) {
+            const size_t n = (size_t)std::min<uint64_t>(cap, p1 - q);
+            for (size_t j = 0; j < n; ++j) {
+                while (cand_ptr[ch.users[i] + 1] <= q + j) ++i;
+                row[j] = (uint32_t)ur.rep_row[i];
+            }
+            HIPCHK(hipMemcpyAsync(cb.row, row.data(), n * 4, hipMemcpyHostToDevice, m->stream));
+            HIPCHK(hipMemcpyAsync(cb.item, cand_items + q, n * 4, hipMemcpyHostToDevice, m->stream));
+            SBRCHK(scan_launch(m, 1, cb.flag, [&] {
+                sbr::launch_candidate_scores(m->mv, ur.H, cb.row, cb.item, n, cb.scores, cb.flag, m->stream);
+            }, {{out_scores + (q - cand_ptr[0]), cb.scores, n * 4}}));
+        }
+    }
+    return SBR_OK;
+}
+
+}  // namespace
+
+sbr_status sbr_user_representations(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users, float* out_reps) {
+    if (!m || !user_ptr || (num_users && !out_reps)) return SBR_ERR_INVALID_ARGUMENT;
+    std::lock_guard<std::mutex> lock(m->mu);
+    SBRCHK(ensure_device(m));
+    SBRCHK(check_csr(m, user_ptr, num_users, item_ids, false));
+    std::vector<uint64_t> users(num_users);
+    for (uint64_t u = 0; u < num_users; ++u) users[u] = u;
+    const RepSource s{user_ptr, item_ids, nullptr, 0, false};
+    const size_t dl = (size_t)m->dl;
+    for (Chunk ch; next_chunk(users, eval_units_cap, s, m->hp.max_sequence_length, &ch);) {
+        const size_t nu = ch.users.size();
+        UserReps ur;
+        int* rep = nullptr;
+        float* rows = nullptr;
+        uint32_t* flag = nullptr; /* scan_launch's; nothing here raises it */
+        SBRCHK(user_reps(m, s, ch.users, [&](DeviceArena& ar) {
+            rep = ar.take<int>(nu);
+            rows = ar.take<float>(nu * dl);
+            flag = ar.take<uint32_t>(1);
+        }, &ur));
+        HIPCHK(hipMemcpyAsync(rep, ur.rep_row.data(), nu * 4, hipMemcpyHostToDevice, m->stream));
+        SBRCHK(scan_launch(m, 1, flag, [&] { sbr::launch_rep_rows(ur.H, rep, (uint32_t)nu, m->d, m->dl, rows, m->stream); },
+                           {{out_reps + ch.c0 * dl, rows, nu * dl * 4}}));
+    }
+    return SBR_OK;
+}
+
+sbr_status sbr_score_candidates(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users,
+                                const uint64_t* cand_ptr, const uint32_t* cand_items, float* out_scores) {
+    if (!m || !user_ptr) return SBR_ERR_INVALID_ARGUMENT;
+    std::lock_guard<std::mutex> lock(m->mu);
+    SBRCHK(ensure_device(m));
+    SBRCHK(check_csr(m, user_ptr, num_users, item_ids, false));
+    return score_candidates_scan(m, RepSource{user_ptr, item_ids, nullptr, 0, false}, num_users, cand_ptr, cand_items, out_scores);
+}
+
+sbr_status sbr_score_candidates_reps(sbr_model* m, const float* reps, uint64_t num_users, const uint64_t* cand_ptr, const uint32_t* cand_items,
+                                     float* out_scores) {
+    if (!m || (num_users && !reps)) return SBR_ERR_INVALID_ARGUMENT;
+    std::lock_guard<std::mutex> lock(m->mu);
+    SBRCHK(ensure_device(m));
+    return score_candidates_scan(m, RepSource{nullptr, nullptr, reps, 0, false}, num_users, cand_ptr, cand_items, out_scores);
+}
+
+sbr_status sbr_recommend_among(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users, uint32_t k, uint32_t flags,
+                               const uint32_t* subset_items, uint64_t num_subset, uint32_t* out_items, float* out_scores) {
+    if (!m || !user_ptr || (num_users && !out_items)) return SBR_ERR_INVALID_ARGUMENT;
+    if (k < 1 || k > SBR_RECOMMEND_MAX_K || (flags & ~SBR_RECOMMEND_INCLUDE_HISTORY)) return SBR_ERR_INVALID_ARGUMENT;
+    std::lock_guard<std::mutex> lock(m->mu);
+    SBRCHK(ensure_device(m));
+    SBRCHK(check_csr(m, user_ptr, num_users, item_ids, false));
+    return recommend_among_scan(m, RepSource{user_ptr, item_ids, nullptr, 0, !(flags & SBR_RECOMMEND_INCLUDE_HISTORY)}, num_users, k, subset_items,
+                                num_subset, out_items, out_scores);
+}
+
+sbr_status sbr_recommend_among_reps(sbr_model* m, const float* reps, uint64_t num_users, uint32_t k, const uint64_t* excl_ptr,
+                                    const uint32_t* excl_items, const uint32_t* subset_items, uint64_t num_subset, uint32_t* out_items,
+                                    float* out_scores) {
+    if (!m || (num_users && (!reps || !out_items))) return SBR_ERR_INVALID_ARGUMENT;
+    if (k < 1 || k > SBR_RECOMMEND_MAX_K) return SBR_ERR_INVALID_ARGUMENT;
+    if (!excl_args_ok(excl_ptr, excl_items, num_users)) return SBR_ERR_INVALID_ARGUMENT;
+    std::lock_guard<std::mutex> lock(m->mu);
+    SBRCHK(ensure_device(m));
+    if (excl_ptr) SBRCHK(check_csr(m, excl_ptr, num_users, excl_items, false));
+    return recommend_among_scan(m, RepSource{excl_ptr, excl_items, reps, 0, true}, num_users, k, subset_items, num_subset, out_items, out_scores);
 }
 
 /* ---------------------------------------------------------------------------------------------

@@ -296,6 +296,21 @@ void launch_recommend(const ModelView& m, const float* reps, const int* rep_row,
 void launch_similar_items(const ModelView& m, const uint32_t* query, uint32_t num_queries, bool cosine, float* rnorm, float* H,
                           const int* rep_row, const uint64_t* excl_ptr, const uint32_t* excl_items, uint32_t k, uint2* lists,
                           uint32_t* lens, uint32_t* out_items, float* out_scores, uint32_t* nonfinite_flag, hipStream_t s);
+/* launch_recommend restricted to the item set subset[0 .. num_subset), sorted and unique (sbr_catalogue.hip): subset_gather_kernel
+ * copies the set's rows and biases into Esub [num_subset][d] / bsub [num_subset], launch_recommend's two kernels scan that sub-table
+ * — lists / lens sized by recommend_groups(num_users, num_subset, k), excl_items POSITIONS in the subset — and subset_ids_kernel turns
+ * out_items' positions into catalogue ids.  Only pairs (user, item of the subset) are scored. */
+void launch_recommend_among(const ModelView& m, const uint32_t* subset, uint32_t num_subset, float* Esub, float* bsub, const float* reps,
+                            const int* rep_row, uint32_t num_users, const uint64_t* excl_ptr, const uint32_t* excl_items, uint32_t k,
+                            uint2* lists, uint32_t* lens, uint32_t* out_items, float* out_scores, uint32_t* nonfinite_flag, hipStream_t s);
+/* out[p] = b[i] + chain_dot(reps[pair_row[p]], E[i]), i = pair_item[p], for the num_pairs pairs of a launch, with the bits of
+ * launch_predict; raises the flag for a non-finite score.  A launch takes at most candidate_pairs_cap pairs: the host cuts a call's
+ * flat candidate list there (12 bytes of device buffers per pair), wherever in a user's list that falls. */
+constexpr size_t candidate_pairs_cap = (size_t)1 << 22;
+void launch_candidate_scores(const ModelView& m, const float* reps, const uint32_t* pair_row, const uint32_t* pair_item, uint64_t num_pairs,
+                             float* out, uint32_t* nonfinite_flag, hipStream_t s);
+/* out [num_users][dl] = the first dl columns of rows rep_row[i] of H [.][d] (user_representations) */
+void launch_rep_rows(const float* H, const int* rep_row, uint32_t num_users, int d, int dl, float* out, hipStream_t s);
 /* device self-tests of the numerics contract (tests/test_numerics_gpu.py) */
 void launch_selftest_math(const float* x, float* out_cell_h, float* out_sig, float* out_tanh, uint64_t n, hipStream_t s);
 void launch_selftest_dot_tree(const float* x, const float* y, int d, uint64_t nrows, float* out, hipStream_t s);

@@ -98,15 +98,7 @@ typedef unsigned v4u32 __attribute__((ext_vector_type(4)));
 //   sparse update's parameter / optimiser-state rows (read, rewritten once per step): ON (step -0.5 %, the GEMM beside it -1.5 %);
 //   forward gather: OFF (its rows are the score kernel's target rows one step later: cached, they are hits there);
 //   BPTT's re-gather: neutral; the EWMA scans: OFF (the backward scan re-reads what the forward scan gathered: 1.36 -> 1.57 ms).
-typedef float v4f_nt __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float4 ld4s(const float* p) {
-    const v4f_nt v = __builtin_nontemporal_load(reinterpret_cast<const v4f_nt*>(p));
-    return make_float4(v.x, v.y, v.z, v.w);
-}
-__device__ __forceinline__ void st4s(float* p, float4 v) {
-    v4f_nt t; t.x = v.x; t.y = v.y; t.z = v.z; t.w = v.w;
-    __builtin_nontemporal_store(t, reinterpret_cast<v4f_nt*>(p));
-}
+// (ld4s / st4s themselves: sbr_device.h)
 #ifndef SBR_NT_SCORE
 #define SBR_NT_SCORE 1
 #endif

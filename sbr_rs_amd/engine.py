@@ -588,6 +588,76 @@ class Model:
                                          None if ei is None else _ptr(ei), _ptr(items), _ptr(scores)))
         return items, scores
 
+    def user_representations(self, user_ptr, item_ids) -> np.ndarray:
+        """user_representation of every history of a CSR in one call (sbr_user_representations): [U, embedding_dim] f32, row u
+        with the bits of the single call on history u; an empty history gets item 0's state."""
+        up = np.ascontiguousarray(user_ptr, dtype=np.uint64)
+        it = np.ascontiguousarray(item_ids, dtype=np.uint32)
+        nu = max(len(up) - 1, 0)
+        out = np.zeros((nu, self.dim), dtype=np.float32)
+        _check(self._L.sbr_user_representations(self._h, _ptr(up), _ptr(it), nu, _ptr(out)))
+        return out
+
+    @staticmethod
+    def _per_user(flat: np.ndarray, ptr: np.ndarray):
+        base = int(ptr[0])
+        return [flat[int(ptr[u]) - base: int(ptr[u + 1]) - base] for u in range(len(ptr) - 1)]
+
+    def score_candidates(self, user_ptr, item_ids, cand_ptr, cand_items):
+        """predict for many users in one call (sbr_score_candidates): user u's history is item_ids[user_ptr[u]: user_ptr[u + 1]],
+        its candidates cand_items[cand_ptr[u]: cand_ptr[u + 1]] (any order, duplicates allowed, none included).  One f32 array
+        per user, in candidate order, with the bits of predict(user_representation(history), candidates); nothing is masked."""
+        up = np.ascontiguousarray(user_ptr, dtype=np.uint64)
+        it = np.ascontiguousarray(item_ids, dtype=np.uint32)
+        cp = np.ascontiguousarray(cand_ptr, dtype=np.uint64)
+        ci = np.ascontiguousarray(cand_items, dtype=np.uint32)
+        if len(cp) != len(up):
+            raise ValueError("one candidate range per user")
+        nu = max(len(up) - 1, 0)
+        scores = np.zeros(max(ci.size, 1), dtype=np.float32)
+        _check(self._L.sbr_score_candidates(self._h, _ptr(up), _ptr(it), nu, _ptr(cp), _ptr(ci) if ci.size else None, _ptr(scores)))
+        return self._per_user(scores, cp)
+
+    def score_candidates_reps(self, reps, cand_ptr, cand_items):
+        """As score_candidates, from representations [U, embedding_dim]."""
+        reps = np.ascontiguousarray(reps, dtype=np.float32).reshape(-1, self.dim)
+        nu = reps.shape[0]
+        cp = np.ascontiguousarray(cand_ptr, dtype=np.uint64)
+        ci = np.ascontiguousarray(cand_items, dtype=np.uint32)
+        if len(cp) != nu + 1:
+            raise ValueError("one candidate range per user")
+        scores = np.zeros(max(ci.size, 1), dtype=np.float32)
+        _check(self._L.sbr_score_candidates_reps(self._h, _ptr(reps), nu, _ptr(cp), _ptr(ci) if ci.size else None, _ptr(scores)))
+        return self._per_user(scores, cp)
+
+    def recommend_among(self, user_ptr, item_ids, k: int, among, include_history: bool = False):
+        """recommend with every item outside `among` ineligible (sbr_recommend_among): the exact top-k of that item set — item
+        ids in any order, duplicates allowed — as catalogue ids, ordered and padded as recommend's rows.  Only the set's rows are
+        scanned."""
+        up = np.ascontiguousarray(user_ptr, dtype=np.uint64)
+        it = np.ascontiguousarray(item_ids, dtype=np.uint32)
+        sub = np.ascontiguousarray(among, dtype=np.uint32).ravel()
+        nu = max(len(up) - 1, 0)
+        items = np.zeros((nu, max(int(k), 0)), dtype=np.uint32)
+        scores = np.zeros((nu, max(int(k), 0)), dtype=np.float32)
+        flags = RECOMMEND_INCLUDE_HISTORY if include_history else 0
+        _check(self._L.sbr_recommend_among(self._h, _ptr(up), _ptr(it), nu, int(k) & 0xFFFFFFFF, flags, _ptr(sub) if sub.size else None,
+                                           sub.size, _ptr(items), _ptr(scores)))
+        return items, scores
+
+    def recommend_among_reps(self, reps, k: int, among, exclude=None):
+        """As recommend_among, from representations [U, embedding_dim]; exclude: None or one sequence of item ids per user."""
+        reps = np.ascontiguousarray(reps, dtype=np.float32).reshape(-1, self.dim)
+        sub = np.ascontiguousarray(among, dtype=np.uint32).ravel()
+        nu = reps.shape[0]
+        items = np.zeros((nu, max(int(k), 0)), dtype=np.uint32)
+        scores = np.zeros((nu, max(int(k), 0)), dtype=np.float32)
+        ep, ei = _exclusion_csr(exclude, nu)
+        _check(self._L.sbr_recommend_among_reps(self._h, _ptr(reps), nu, int(k) & 0xFFFFFFFF, None if ep is None else _ptr(ep),
+                                                None if ei is None else _ptr(ei), _ptr(sub) if sub.size else None, sub.size,
+                                                _ptr(items), _ptr(scores)))
+        return items, scores
+
     def rank_targets(self, user_ptr, item_ids, target_ptr, target_items, include_history: bool = False) -> np.ndarray:
         """Exact ranks of every user's targets among the whole catalogue from one scan (sbr_rank_targets): user u's history is
         item_ids[user_ptr[u]: user_ptr[u + 1]], its targets target_items[target_ptr[u]: target_ptr[u + 1]]; rank =

@@ -230,19 +230,51 @@ class _ImplicitSequenceModel:
     def predict(self, user: ImplicitUser, item_ids) -> np.ndarray:
         return self.params.predict(user.user_embedding, np.asarray(item_ids, dtype=np.uint32))
 
-    def recommend(self, interactions_or_histories, k: int, exclude_history: bool = True):
+    @staticmethod
+    def _csr(interactions_or_histories):
+        """A CompressedInteractions or a list of item-id sequences -> (pointers u64, item ids u32)"""
+        if isinstance(interactions_or_histories, CompressedInteractions):
+            return interactions_or_histories.user_pointers, interactions_or_histories.item_ids
+        seqs = [np.asarray(h, dtype=np.uint32).ravel() for h in interactions_or_histories]
+        up = np.zeros(len(seqs) + 1, dtype=np.uint64)
+        up[1:] = np.cumsum([s.size for s in seqs])
+        return up, (np.concatenate(seqs) if seqs else np.zeros(0, dtype=np.uint32))
+
+    def recommend(self, interactions_or_histories, k: int, exclude_history: bool = True, among=None):
         """The k best items of the whole catalogue for each user's history, on the device: (items [U, k] u32, scores
         [U, k] f32), score descending, ties to the lower item id.  ``interactions_or_histories`` is a
         CompressedInteractions or a list of item-id sequences.  Every item of a history is excluded unless
-        ``exclude_history`` is False; a row with fewer than k eligible items is padded with (0xFFFFFFFF, -inf)."""
-        if isinstance(interactions_or_histories, CompressedInteractions):
-            up, it = interactions_or_histories.user_pointers, interactions_or_histories.item_ids
-        else:
-            seqs = [np.asarray(h, dtype=np.uint32).ravel() for h in interactions_or_histories]
-            up = np.zeros(len(seqs) + 1, dtype=np.uint64)
-            up[1:] = np.cumsum([s.size for s in seqs])
-            it = np.concatenate(seqs) if seqs else np.zeros(0, dtype=np.uint32)
-        return self.params.recommend(up, it, k, include_history=not exclude_history)
+        ``exclude_history`` is False; a row with fewer than k eligible items is padded with (0xFFFFFFFF, -inf).
+        ``among``: None, or the item ids the answer is restricted to (in stock, one category, ...; any order, duplicates
+        allowed) — the exact top k of that set, found by scanning its rows only."""
+        up, it = self._csr(interactions_or_histories)
+        if among is None:
+            return self.params.recommend(up, it, k, include_history=not exclude_history)
+        return self.params.recommend_among(up, it, k, among, include_history=not exclude_history)
+
+    def user_representations(self, histories) -> np.ndarray:
+        """``user_representation`` of many histories in one device pass: [U, embedding_dim] f32, row u for history u."""
+        return self.params.user_representations(*self._csr(histories))
+
+    def score_candidates(self, histories, candidates):
+        """``predict`` for many users in one device pass: ``candidates[u]`` are the item ids to score for history u (any
+        order, duplicates allowed, may be empty).  One f32 array per user, in candidate order; nothing is masked."""
+        up, it = self._csr(histories)
+        cp, ci = self._csr(candidates)
+        return self.params.score_candidates(up, it, cp, ci)
+
+    def rerank(self, histories, candidates, k=None):
+        """Each user's candidates ordered by the model: a list of (items u32, scores f32) per user, score descending, ties to
+        the lower item id, duplicates removed, cut to the first ``k`` if given.  The scores come from ``score_candidates`` on
+        the device; the per-user sort (``np.lexsort``) is host work."""
+        cands = [np.asarray(c, dtype=np.uint32).ravel() for c in candidates]
+        out = []
+        for c, s in zip(cands, self.score_candidates(histories, cands)):
+            ids, first = np.unique(c, return_index=True)
+            sc = s[first]
+            order = np.lexsort((ids, -sc))[:k]
+            out.append((ids[order], sc[order]))
+        return out
 
     def similar_items(self, query_items, k: int, metric: str = "cosine", include_self: bool = False, exclude=None):
         """The k items most like each query item, on the device: (items [Q, k] u32, scores [Q, k] f32), by the cosine of the

@@ -1,7 +1,8 @@
 // hbm_ceiling.hip — what this MI355X's memory system sustains for the access shapes of the hot path,
 // measured with nothing else in the kernels: sequential float4 read / copy, and random ROW gathers and
 // read-modify-writes of 512 B and 1 KiB rows out of tables far larger than the 256 MiB Infinity Cache
-// (the item-table accesses of score_kernel / seg_short_kernel).  The roofline fractions in DESIGN.md are
+// (the item-table accesses of score_kernel / seg_short_kernel), and gathers of 512 B and 128 B rows out of the 1 M-row tables
+// candidate_score_kernel is measured on (profiles/candidates_8192x1M_d128.md).  The roofline fractions in DESIGN.md are
 // quoted against the 8 TB/s spec; this prints the attainable figures beside it.
 //
 //   hipcc --offload-arch=gfx950 -O3 tools/hbm_ceiling.hip -o tools/bin/hbm_ceiling && tools/bin/hbm_ceiling
@@ -135,6 +136,12 @@ int main() {
         const size_t rows = 1000000;
         hipLaunchKernelGGL(fill_idx, dim3((n_access + 255) / 256), dim3(256), 0, 0, idx, n_access, (uint32_t)rows, 3ull);
         run_rows<32, 4, false>("random row gather", tab, rows, idx, n_access, out);
+    }
+    {  // 128-byte rows (d = 32) of a 1 M-row table: 122 MiB, inside the Infinity Cache (score_candidates at d = 32)
+        const size_t rows = 1000000;
+        hipLaunchKernelGGL(fill_idx, dim3((n_access + 255) / 256), dim3(256), 0, 0, idx, n_access, (uint32_t)rows, 4ull);
+        run_rows<8, 4, false>("random row gather", tab, rows, idx, n_access, out);
+        run_rows<8, 8, false>("random row gather", tab, rows, idx, n_access, out);
     }
     return 0;
 }
