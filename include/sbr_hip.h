@@ -264,6 +264,9 @@ sbr_status sbr_device_count(int32_t* out_count);
  *   sbr_group_step            one optimiser step of the whole group (Synchronous / partitioned / the staleness-one pipeline);
  *                             returns when it is QUEUED on the devices' streams (a partitioned step too since round 6: its owners
  *                             wait for the devices' events on their streams and read the owner bounds on the device)
+ *                             A partitioned table's rows are updated on their OWNERS' streams: a prediction-side call or
+ *                             sbr_model_get_param on any replica between steps waits, on that replica's stream, for the other
+ *                             owners' last updates first, so it may follow sbr_group_step without a sbr_group_synchronize.
  *   sbr_group_step_local      parity access: only the local halves of `minibatch` (forward, scoring, BPTT on every replica); the
  *                             next sbr_group_step(minibatch) then runs the exchange and the update alone.  Not for Asynchronous.
  *   sbr_group_member_plan     replica r's plan, borrowed (sbr_fit_debug_fetch, sbr_fit_minibatch_rows, sbr_fit_counters)
@@ -560,6 +563,22 @@ sbr_status sbr_selftest_mfma(const float* a, const float* b, const float* c0, ui
  * out_head_pos[*out_nheads + 1] = positions where a new row starts, then n. */
 sbr_status sbr_selftest_sort(const uint32_t* rows, uint64_t n, uint32_t row_bits, uint64_t* out_keys, uint32_t* out_head_pos,
                              uint32_t* out_nheads);
+
+/* Stream-delay test hook (tests/test_stream_joins_gpu.py).  A training step is spread over three or four streams
+ * per model (main, side, sorter, copier) and one exchange stream per member of a group plan (xs), tied together by events.  The
+ * environment variable
+ *     SBR_TEST_STREAM_DELAY="<role>[@<device>]=<microseconds>[,...]"     roles: main side sorter copier xs
+ * read per call, makes the named streams LATE: a delay kernel (one wave, no memory traffic; it sleeps until a constant-rate
+ * clock has advanced by the requested time, at most 5 000 us, under a fixed cap of polls — a bounded wait) is queued right
+ * behind every cross-stream wait the engine issues on such a stream, and at the head of the first work a call queues on it where
+ * no wait precedes that work.  @<device> restricts an entry to the model whose device_rank it names.  A consumer that waits for
+ * the late stream's event computes the same bits; one that does not reads stale data.  Unset: nothing changes.
+ * sbr_test_delays_queued: the delay kernels queued on this model's streams per role, in the order above, since the last read.
+ * sbr_selftest_stream_delay: the method's own check — a device float that is 1.0; one stream is delayed, stores 2.0 and records
+ * an event; a second stream waits for that event (with_join != 0) or not and copies the float: *out = 2.0 with the join, 1.0
+ * without it. */
+sbr_status sbr_test_delays_queued(sbr_model* m, uint64_t out[5]);
+sbr_status sbr_selftest_stream_delay(uint32_t delay_us, int32_t with_join, float* out);
 
 #ifdef __cplusplus
 }

@@ -133,6 +133,8 @@ def load():
         "sbr_selftest_dot_tree": [vp, vp, C.c_uint32, C.c_uint64, vp],
         "sbr_selftest_mfma": [vp, vp, vp, C.c_uint32, vp, vp, vp, vp],
         "sbr_selftest_sort": [vp, C.c_uint64, C.c_uint32, vp, vp, vp],
+        "sbr_test_delays_queued": [vp, u64p],
+        "sbr_selftest_stream_delay": [C.c_uint32, C.c_int32, fp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -178,4 +180,5 @@ DECLARED_SYMBOLS = [
     "sbr_fit_step_reduce_own_queued", "sbr_fit_step_owner_apply_queued",
     "sbr_recommend", "sbr_recommend_reps", "sbr_rank_targets", "sbr_rank_targets_reps", "sbr_similar_items",
     "sbr_user_representations", "sbr_score_candidates", "sbr_score_candidates_reps", "sbr_recommend_among", "sbr_recommend_among_reps",
+    "sbr_test_delays_queued", "sbr_selftest_stream_delay",
 ]

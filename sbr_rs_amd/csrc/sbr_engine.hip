@@ -284,6 +284,10 @@ struct SharedTable {
     float *E = nullptr, *Eacc = nullptr, *Em = nullptr, *b = nullptr, *bacc = nullptr, *bm = nullptr;
     int local_rank = -1;
     uint64_t slice = 0;
+    /* single-process group: owner q's last update of its rows, as the group plan's partitioned step recorded it on q's stream
+     * (the plan's event; null before the first step and after the plan is gone).  The rows of the table are written on their
+     * OWNERS' streams, so whoever reads the table on another replica's stream joins these first (join_table_owners). */
+    std::vector<hipEvent_t> owner_updated;
 
     ~SharedTable() {
         for (auto& pt : parts) {
@@ -455,6 +459,7 @@ struct sbr_model {
     std::vector<TimingPair> pending;
     double ms[SBR_K_FAMILIES] = {0};
     uint64_t launches[SBR_K_FAMILIES] = {0};
+    std::atomic<uint64_t> test_delays[5] = {}; /* SBR_TEST_STREAM_DELAY: delay kernels queued per role since sbr_test_delays_queued last read them */
 };
 
 namespace {
@@ -478,7 +483,118 @@ struct ScopedTimer {
         hipEventRecord(tp.b, st);
         m->pending.push_back(tp);
     }
+    /* the bracket is closed here and a new one of the same family (no further launch counted) opened behind whatever the
+     * caller queues in between: a delay of the stream-delay test hook is never inside a bracket */
+    void pause() {
+        if (!on) return;
+        hipEventRecord(tp.b, st);
+        m->pending.push_back(tp);
+    }
+    void resume() {
+        if (!on) return;
+        tp.launches = 0;
+        hipEventCreate(&tp.a);
+        hipEventCreate(&tp.b);
+        hipEventRecord(tp.a, st);
+    }
 };
+
+/* ---- the stream-delay test hook ---------------------------------------------------------------------------
+ * SBR_TEST_STREAM_DELAY="<role>[@<device>]=<microseconds>[,...]", read per call; roles: main, side, sorter, copier, xs;
+ * @<device> = the model's device_rank, without it every model.  A stream named there is made LATE: a delay kernel (one wave, no
+ * memory traffic, bounded) is queued right behind every cross-stream wait the engine issues on it — stream_wait() below is the
+ * only place the engine calls hipStreamWaitEvent — and at the head of the first work a call queues on it where no wait precedes
+ * that work (stream_head()).  A consumer that really waits for the late stream's event sees no difference; one that does not reads
+ * stale data and loses bit-parity with the oracle (tests/test_stream_joins_gpu.py).  Unset: no launch, nothing inside a kernel. */
+enum { ROLE_MAIN = 0, ROLE_SIDE = 1, ROLE_SORTER = 2, ROLE_COPIER = 3, ROLE_XS = 4, ROLE_COUNT = 5 };
+constexpr uint32_t test_delay_max_us = 5000;
+
+int stream_role(const sbr_model* m, hipStream_t s) {
+    if (s == m->stream) return ROLE_MAIN;
+    if (s == m->side) return ROLE_SIDE;
+    if (s == m->sorter) return ROLE_SORTER;
+    if (s == m->copier) return ROLE_COPIER;
+    return ROLE_XS; /* the group plan's exchange stream is the only other stream the engine waits on */
+}
+
+/* microseconds by which `role` of this model is to be late (0: not named, or the variable is unset or malformed) */
+uint32_t test_delay_us(const sbr_model* m, int role) {
+    const char* e = std::getenv("SBR_TEST_STREAM_DELAY");
+    if (!e || !*e) return 0;
+    static const char* const names[ROLE_COUNT] = {"main", "side", "sorter", "copier", "xs"};
+    const size_t nl = std::strlen(names[role]);
+    uint32_t us = 0;
+    while (*e) {
+        const char* end = std::strchr(e, ',');
+        const size_t len = end ? (size_t)(end - e) : std::strlen(e);
+        if (len > nl && std::strncmp(e, names[role], nl) == 0 && (e[nl] == '=' || e[nl] == '@')) {
+            const char* q = e + nl;
+            bool mine = true;
+            if (*q == '@') {
+                char* after = nullptr;
+                const unsigned long dev = std::strtoul(q + 1, &after, 10);
+                mine = after != q + 1 && dev == (unsigned long)m->hp.device_rank;
+                q = after;
+            }
+            if (mine && q && *q == '=') {
+                char* after = nullptr;
+                const unsigned long v = std::strtoul(q + 1, &after, 10);
+                if (after != q + 1 && after <= e + len) us = (uint32_t)std::min<unsigned long>(v, test_delay_max_us);
+            }
+        }
+        e += len + (end ? 1 : 0);
+    }
+    return us;
+}
+
+int wall_clock_khz() { /* the rate of the kernels' wall_clock64() (100 MHz on CDNA) */
+    int v = 0, dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeWallClockRate, dev) != hipSuccess || v <= 0) v = 100000;
+    return v;
+}
+
+sbr_status queue_test_delay(sbr_model* m, hipStream_t s, int role, uint32_t us, ScopedTimer* open) {
+    static const int khz = wall_clock_khz();
+    const bool bracketed = open && open->on && open->st == s;
+    if (bracketed) open->pause();
+    sbr::launch_stream_delay((unsigned long long)us * (unsigned long long)khz / 1000ull, s);
+    m->test_delays[role].fetch_add(1, std::memory_order_relaxed);
+    if (bracketed) open->resume();
+    HIPCHK(hipGetLastError());
+    return SBR_OK;
+}
+
+/* every cross-stream join of the engine: stream `s` of model m waits for `e` (`open`: the timing bracket the caller holds, if any) */
+sbr_status stream_wait(sbr_model* m, hipStream_t s, hipEvent_t e, ScopedTimer* open = nullptr) {
+    HIPCHK(hipStreamWaitEvent(s, e, 0));
+    const int role = stream_role(m, s);
+    const uint32_t us = test_delay_us(m, role);
+    return us ? queue_test_delay(m, s, role, us, open) : SBR_OK;
+}
+
+/* the head of the first work a call queues on `s` where no wait precedes it */
+sbr_status stream_head(sbr_model* m, hipStream_t s) {
+    const int role = stream_role(m, s);
+    const uint32_t us = test_delay_us(m, role);
+    return us ? queue_test_delay(m, s, role, us, nullptr) : SBR_OK;
+}
+
+/* A partitioned table is updated by its owners on THEIR streams (sbr_group_plan::partitioned_step): a reader of the table on this
+ * model's stream — prediction, evaluation, sbr_model_get_param — waits for the other owners' last updates first.  (The next
+ * training step does the same through the plan's wait_applied.) */
+sbr_status join_table_owners(sbr_model* m) {
+    if (!m->shared) return SBR_OK;
+    const std::vector<hipEvent_t>& ev = m->shared->owner_updated;
+    for (size_t q = 0; q < ev.size(); ++q)
+        if (ev[q] && q != (size_t)m->hp.device_rank) SBRCHK(stream_wait(m, m->stream, ev[q]));
+    return SBR_OK;
+}
+
+/* entry of a call that reads the model's parameters on its stream */
+sbr_status enter_reader(sbr_model* m) {
+    HIPCHK(hipSetDevice(m->device));
+    return join_table_owners(m);
+}
 
 uint64_t dense_count(const sbr_model* m) {
     return m->ng ? (uint64_t)(2 * m->d + 1) * m->ng * m->d : (uint64_t)m->d;
@@ -1046,7 +1162,7 @@ sbr_status sbr_model_get_param(sbr_model* m, int32_t which, float* host_out, uin
     float* p = param_ptr(m, which, &n, &stored, &shape);
     if (!p || n != count) return SBR_ERR_INVALID_ARGUMENT;
     if (m->opt_state_partial && is_table_optimizer_state(which)) return SBR_ERR_INVALID_ARGUMENT; /* gather the owners' slices first */
-    SBRCHK(ensure_device(m));
+    SBRCHK(enter_reader(m));
     HIPCHK(hipStreamSynchronize(m->stream));
     if (stored == n) {
         HIPCHK(hipMemcpy(host_out, p, n * 4, hipMemcpyDeviceToHost));
@@ -1068,7 +1184,7 @@ sbr_status sbr_model_get_param_rows(sbr_model* m, int32_t which, const uint32_t*
     const bool table = shape == SHAPE_ROWS, bias = shape == SHAPE_FLAT && stored == I && (which == SBR_PARAM_ITEM_BIAS || which == SBR_PARAM_ITEM_BIAS_ACC || which == SBR_PARAM_ITEM_BIAS_M);
     if (!p || !count || (!table && !bias)) return SBR_ERR_INVALID_ARGUMENT;
     if (m->opt_state_partial && is_table_optimizer_state(which)) return SBR_ERR_INVALID_ARGUMENT;
-    SBRCHK(ensure_device(m));
+    SBRCHK(enter_reader(m));
     HIPCHK(hipStreamSynchronize(m->stream));
     const uint64_t w = table ? (uint64_t)m->dl : 1, ws = table ? (uint64_t)m->d : 1;
     for (uint64_t i = 0; i < n; ++i) {
@@ -1472,6 +1588,7 @@ static sbr_status build_epoch(sbr_fit_plan* p, sbr_fit_plan::Epoch& e) {
         e.rows_cap = row_base; e.off_cap = e.off_host.size(); e.seq_cap = seq_base;
     }
     hipStream_t cs = p->copy_stream;
+    SBRCHK(stream_head(m, cs));
     e.desc_host.clear();
     if (B == 1 && p->ndev == 1) {
         e.desc_host.resize(nmb);
@@ -1536,7 +1653,7 @@ sbr_status sbr_fit_minibatch_rows(const sbr_fit_plan* p, uint64_t minibatch, uin
 
 static sbr_status join_dense(sbr_fit_plan* p) {
     if (p->dense_pending) {
-        HIPCHK(hipStreamWaitEvent(p->m->stream, p->m->ev_join, 0));
+        SBRCHK(stream_wait(p->m, p->m->stream, p->m->ev_join));
         p->dense_pending = false;
     }
     return SBR_OK;
@@ -1562,6 +1679,7 @@ sbr_status sbr_fit_step_local(sbr_fit_plan* p, uint64_t minibatch) {
     const sbr::MbView mv = mb_view(p, minibatch);
     const sbr::BlockView bv = block_view(m, block, p->rmax);
     const int* off_host = ep.off_host.data() + mb.off_base;
+    SBRCHK(stream_head(m, m->stream));
     /* The sort of the sparse-update keys needs only the index arrays and the negatives: it runs on its own stream,
      * underneath the backward pass (WARP: the negatives come out of the score kernel) or, for the single-negative losses
      * whose negatives are a hash of the row counter, from the very start of the step (joined by step_apply / step_scatter). */
@@ -1595,7 +1713,7 @@ sbr_status sbr_fit_step_local(sbr_fit_plan* p, uint64_t minibatch) {
             /* everything before: the previous step's readers of the keys, this step's score (a WARP step records the event
              * itself, before it queues the backward pass) */
             if (early_sort) HIPCHK(hipEventRecord(m->ev_scored, m->stream));
-            HIPCHK(hipStreamWaitEvent(on, m->ev_scored, 0));
+            SBRCHK(stream_wait(m, on, m->ev_scored));
         }
         if (side_header) { /* the step's loss bookkeeping rides on the ordering's stream: nothing on the main stream waits for it */
             sbr::launch_seq_loss(mv, p->wb.v.loss, p->lag_seqsum, p->lag_state, mb.B, on);
@@ -1629,7 +1747,7 @@ sbr_status sbr_fit_step_local(sbr_fit_plan* p, uint64_t minibatch) {
     if (early_sort && !small_tail) SBRCHK(launch_sort(overlap ? m->sorter : m->stream));
     if (small_tail) {
         if (p->lag_busy) { /* an earlier step's chain on the ordering's stream still owns lag_state */
-            HIPCHK(hipStreamWaitEvent(m->stream, p->ev_lagged, 0));
+            SBRCHK(stream_wait(m, m->stream, p->ev_lagged));
             p->lag_busy = false;
         }
         p->sort_off_stream = false;
@@ -1675,7 +1793,7 @@ sbr_status sbr_fit_step_local(sbr_fit_plan* p, uint64_t minibatch) {
         HIPCHK(hipEventRecord(m->ev_scored, m->stream)); /* right behind the score kernel */
     } else {
         if (p->lag_busy) { /* the previous step's chain may still be running on the sorter stream: it owns lag_state / lag_seqsum */
-            HIPCHK(hipStreamWaitEvent(m->stream, p->ev_lagged, 0));
+            SBRCHK(stream_wait(m, m->stream, p->ev_lagged));
             p->lag_busy = false;
         }
         if (!fuse_lag) {
@@ -1701,7 +1819,7 @@ sbr_status sbr_fit_step_local(sbr_fit_plan* p, uint64_t minibatch) {
      * step_dense before anything reads blk.dense */
     if (side != m->stream) {
         HIPCHK(hipEventRecord(m->ev_fork, m->stream));
-        HIPCHK(hipStreamWaitEvent(side, m->ev_fork, 0));
+        SBRCHK(stream_wait(m, side, m->ev_fork));
     }
     p->dw_deferred = m->step_fusion >= 1 && p->fuse_back && !overlap && p->ndev == 1 && sbr::small_back_shape_ok(m->mv, (int)mb.R) && (m->ng || mb.B <= 256);
     if (p->dw_deferred) p->dense_unreduced_chunks = 0;
@@ -1715,7 +1833,7 @@ sbr_status sbr_fit_step_local(sbr_fit_plan* p, uint64_t minibatch) {
     p->dense_pending = side != m->stream;
     if (!fuse_lag) {
         hipStream_t ls = overlap ? m->sorter : m->stream;
-        if (ls != m->stream && !side_header) HIPCHK(hipStreamWaitEvent(ls, p->ev_seqsum, 0)); /* (side_header: same stream as seq_loss) */
+        if (ls != m->stream && !side_header) SBRCHK(stream_wait(m, ls, p->ev_seqsum)); /* (side_header: same stream as seq_loss) */
         sbr::launch_lagged_chain(mv, p->lag_seqsum, mb.B, p->lag_state, ls);
         if (ls != m->stream) {
             HIPCHK(hipEventRecord(p->ev_lagged, ls));
@@ -1734,13 +1852,14 @@ sbr_status sbr_fit_step_apply(sbr_fit_plan* p, uint64_t minibatch) {
     sbr_model* m = p->m;
     SBRCHK(ensure_device(m));
     const uint8_t* all = p->block;
+    SBRCHK(stream_head(m, m->stream));
     begin_optimizer_step(m);
     if (!p->header_accumulated) sbr::launch_accumulate_loss(all, p->block_bytes, 1, p->loss_acc, p->ex_acc, m->stream);
     p->header_accumulated = false;
     if (p->dw_deferred) { /* small LSTM step: dense gradient + dense update + sparse update in one launch */
         p->dw_deferred = false;
         ScopedTimer t(m, SBR_K_SPARSE_UPDATE, 1);
-        if (p->sort_off_stream) HIPCHK(hipStreamWaitEvent(m->stream, m->ev_sorted, 0));
+        if (p->sort_off_stream) SBRCHK(stream_wait(m, m->stream, m->ev_sorted, &t));
         sbr::launch_small_back(m->mv, mb_view(p, minibatch), block_view(m, p->block, p->rmax), p->wb.v, p->ep[p->cur].rows_of_dev[minibatch],
                                p->keys_sorted, p->seg, m->stream);
         HIPCHK(hipGetLastError());
@@ -1748,7 +1867,7 @@ sbr_status sbr_fit_step_apply(sbr_fit_plan* p, uint64_t minibatch) {
     }
     {
         ScopedTimer t(m, SBR_K_SPARSE_UPDATE, 1);
-        if (p->sort_off_stream) HIPCHK(hipStreamWaitEvent(m->stream, m->ev_sorted, 0));
+        if (p->sort_off_stream) SBRCHK(stream_wait(m, m->stream, m->ev_sorted, &t));
         sbr::SegScratch sc = p->seg;
         sc.prelisted = p->hot_prelisted ? 1u : 0u;
         const sbr::BlockView bv = block_view(m, p->block, p->rmax);
@@ -1756,10 +1875,10 @@ sbr_status sbr_fit_step_apply(sbr_fit_plan* p, uint64_t minibatch) {
         if (p->hot_prelisted) { /* the listed hot rows: chunk partials + ordered finish on the ordering's stream (behind the list, and
                                  * behind BPTT: ev_fork), beside the short segments' pass — disjoint table rows */
             p->hot_prelisted = false;
-            HIPCHK(hipStreamWaitEvent(m->sorter, m->ev_fork, 0));
+            SBRCHK(stream_wait(m, m->sorter, m->ev_fork, &t));
             sbr::launch_seg_hot_apply(m->mv, bv, p->keys_sorted, sc, m->sorter);
             HIPCHK(hipEventRecord(p->ev_hot, m->sorter));
-            HIPCHK(hipStreamWaitEvent(m->stream, p->ev_hot, 0));
+            SBRCHK(stream_wait(m, m->stream, p->ev_hot, &t));
         }
     }
     SBRCHK(join_dense(p));
@@ -1828,11 +1947,12 @@ sbr_status sbr_fit_steps(sbr_fit_plan* p, uint64_t first, uint64_t count) {
             ++e;
         }
         if (p->lag_busy) { /* an earlier step's chain on the ordering's stream still owns lag_state */
-            HIPCHK(hipStreamWaitEvent(m->stream, p->ev_lagged, 0));
+            SBRCHK(stream_wait(m, m->stream, p->ev_lagged));
             p->lag_busy = false;
         }
-        if (p->sorted_event_live) HIPCHK(hipStreamWaitEvent(m->stream, m->ev_sorted, 0)); /* (a larger step before: its ordering owned the keys) */
+        if (p->sorted_event_live) SBRCHK(stream_wait(m, m->stream, m->ev_sorted)); /* (a larger step before: its ordering owned the keys) */
         SBRCHK(join_dense(p));
+        SBRCHK(stream_head(m, m->stream));
         if (ewma_runs) sbr::launch_epoch_steps(m->mv, ev, bv, p->wb.v, epoch_key, tail, (int)b, (int)e, p->T - 1, p->phase_clocks, m->stream);
         else sbr::launch_lstm_steps(m->mv, ev, bv, p->wb.v, epoch_key, tail, (int)b, (int)e, p->T - 1, (int)run_max, p->phase_clocks, m->stream);
         m->opt_steps += e - b; /* Adagrad: no per-step host-side corrections */
@@ -1931,7 +2051,7 @@ sbr_status sbr_fit_step_scatter(sbr_fit_plan* p, uint64_t minibatch, void* devic
     const uint32_t R = p->ep[p->cur].rows_of_dev[minibatch * p->ndev + p->rank];
     {
         ScopedTimer t(m, SBR_K_SPARSE_UPDATE, 1);
-        if (p->sorted_event_live) HIPCHK(hipStreamWaitEvent(m->stream, m->ev_sorted, 0));
+        if (p->sorted_event_live) SBRCHK(stream_wait(m, m->stream, m->ev_sorted, &t));
         sbr::launch_seg_scatter(m->mv, bv, R, p->ndev, slice_rows(p), device_send, p->keys_sorted, p->seg, m->stream);
     }
     HIPCHK(hipGetLastError());
@@ -1948,7 +2068,7 @@ sbr_status sbr_fit_step_dense(sbr_fit_plan* p, void* device_dense_out) {
     SBRCHK(ensure_dense_reduced(p));
     /* a WARP step with the ordering on its own stream writes the block header THERE (side_header in sbr_fit_step_local): join
      * it here rather than rely on the caller having run sbr_fit_step_scatter first */
-    if (p->sorted_event_live && p->sort_off_stream) HIPCHK(hipStreamWaitEvent(m->stream, m->ev_sorted, 0));
+    if (p->sorted_event_live && p->sort_off_stream) SBRCHK(stream_wait(m, m->stream, m->ev_sorted));
     HIPCHK(hipMemcpyAsync(device_dense_out, bv.header, 32, hipMemcpyDeviceToDevice, m->stream));
     HIPCHK(hipMemcpyAsync(reinterpret_cast<uint8_t*>(device_dense_out) + 32, bv.dense, dense_count(m) * 4,
                           hipMemcpyDeviceToDevice, m->stream));
@@ -2155,7 +2275,7 @@ static sbr_status partition_reduce_own(sbr_fit_plan* p, uint64_t minibatch) {
     SBRCHK(partition_buffers(p));
     const sbr::BlockView bv = block_view(m, p->block, p->rmax);
     const uint32_t R = p->ep[p->cur].rows_of_dev[minibatch * p->ndev + p->rank];
-    if (p->sorted_event_live) HIPCHK(hipStreamWaitEvent(m->stream, m->ev_sorted, 0));
+    if (p->sorted_event_live) SBRCHK(stream_wait(m, m->stream, m->ev_sorted));
     {
         ScopedTimer t(m, SBR_K_SPARSE_UPDATE, 1);
         sbr::launch_seg_list(m->mv, bv, R, p->ndev, slice_rows(p), p->keys_sorted, p->glist, p->gblist, p->gfl, p->bounds_dev, p->seg,
@@ -2740,7 +2860,7 @@ struct sbr_group_plan {
     sbr_status wait_applied(uint32_t r, hipStream_t s) { /* peers must be done with the previous step's buffers / table rows */
         if (first) return SBR_OK;
         for (uint32_t q = 0; q < n; ++q)
-            if (q != r) HIPCHK(hipStreamWaitEvent(s, dev[q].applied, 0));
+            if (q != r) SBRCHK(stream_wait(models[r], s, dev[q].applied));
         return SBR_OK;
     }
     /* local half of minibatch mb on device r (a partitioned table must not still be written by the previous step's owners) */
@@ -2765,7 +2885,7 @@ struct sbr_group_plan {
         SBRCHK(phase([&](uint32_t q) -> sbr_status {
             SBRCHK(ensure_device(models[q]));
             for (uint32_t r = 0; r < n; ++r) {
-                if (r != q) HIPCHK(hipStreamWaitEvent(models[q]->stream, dev[r].scattered, 0));
+                if (r != q) SBRCHK(stream_wait(models[q], models[q]->stream, dev[r].scattered));
                 HIPCHK(hipMemcpyAsync(dev[q].recv + (size_t)r * block_bytes, dev[r].plan->block, block_bytes, hipMemcpyDefault, models[q]->stream));
             }
             SBRCHK(sbr_fit_step_apply_blocks_in_order(dev[q].plan, mb, dev[q].recv));
@@ -2797,7 +2917,7 @@ struct sbr_group_plan {
         SBRCHK(phase([&](uint32_t p) -> sbr_status { /* all-to-all: chunk p of every device -> device p */
             SBRCHK(ensure_device(models[p]));
             for (uint32_t r = 0; r < n; ++r) {
-                if (r != p) HIPCHK(hipStreamWaitEvent(models[p]->stream, dev[r].scattered, 0));
+                if (r != p) SBRCHK(stream_wait(models[p], models[p]->stream, dev[r].scattered));
                 HIPCHK(hipMemcpyAsync(dev[p].recv + r * chunk, dev[r].send + p * chunk, chunk, hipMemcpyDefault, models[p]->stream));
             }
             if (owner_applied) SBRCHK(sbr_fit_step_owner_update(dev[p].plan, dev[p].recv));
@@ -2809,7 +2929,7 @@ struct sbr_group_plan {
         SBRCHK(phase([&](uint32_t q) -> sbr_status { /* all-gather of the owners' slices / chunks and of the dense blocks */
             SBRCHK(ensure_device(models[q]));
             for (uint32_t p = 0; p < n; ++p) {
-                if (p != q) HIPCHK(hipStreamWaitEvent(models[q]->stream, dev[p].reduced, 0));
+                if (p != q) SBRCHK(stream_wait(models[q], models[q]->stream, dev[p].reduced));
                 if (owner_applied) {
                     if (p != q) {
                         SBRCHK(copy_slice(q, p, SBR_PARAM_ITEM_EMBEDDING));
@@ -2894,13 +3014,14 @@ struct sbr_group_plan {
                 const sbr_fit_plan* pr = dev[r].plan;
                 pl.keys[r] = pr->keys_sorted; pl.G[r] = pr->glist; pl.gb[r] = pr->gblist; pl.fl[r] = pr->gfl;
                 pb.b[r] = pr->bounds_dev; /* read in place by merge_plan_kernel (peer-readable like the lists) */
-                if (r != q) HIPCHK(hipStreamWaitEvent(models[q]->stream, dev[r].scattered, 0));
+                if (r != q) SBRCHK(stream_wait(models[q], models[q]->stream, dev[r].scattered));
             }
             for (uint32_t r = 0; r < n; ++r)
                 HIPCHK(hipMemcpyAsync(dev[q].dense_all + r * db, dev[r].dense, db, hipMemcpyDefault, models[q]->stream));
             SBRCHK(apply_dense_blocks(dev[q].plan, dev[q].dense_all));
             SBRCHK(partition_owner_apply(dev[q].plan, pl, pb));
             HIPCHK(hipEventRecord(dev[q].applied, models[q]->stream));
+            models[q]->shared->owner_updated[q] = dev[q].applied; /* readers of the table on the other replicas' streams join it */
             return SBR_OK;
         }));
         first = false;
@@ -2928,7 +3049,7 @@ struct sbr_group_plan {
         SBRCHK(phase([&](uint32_t p) -> sbr_status {
             SBRCHK(ensure_device(models[p]));
             for (uint32_t r = 0; r < n; ++r) {
-                HIPCHK(hipStreamWaitEvent(dev[p].xs, dev[r].scattered, 0));
+                SBRCHK(stream_wait(models[p], dev[p].xs, dev[r].scattered));
                 HIPCHK(hipMemcpyAsync(dev[p].recv + r * chunk, dev[r].send + p * chunk, chunk, hipMemcpyDefault, dev[p].xs));
             }
             SBRCHK(sbr_fit_step_owner_reduce_on(dev[p].plan, dev[p].recv, dev[p].own, dev[p].xs)); /* belongs to the exchange stream */
@@ -2938,12 +3059,12 @@ struct sbr_group_plan {
         SBRCHK(phase([&](uint32_t q) -> sbr_status {
             SBRCHK(ensure_device(models[q]));
             for (uint32_t p = 0; p < n; ++p) {
-                if (p != q) HIPCHK(hipStreamWaitEvent(dev[q].xs, dev[p].reduced, 0));
+                if (p != q) SBRCHK(stream_wait(models[q], dev[q].xs, dev[p].reduced));
                 HIPCHK(hipMemcpyAsync(dev[q].table + p * chunk, dev[p].own, chunk, hipMemcpyDefault, dev[q].xs));
                 HIPCHK(hipMemcpyAsync(dev[q].dense_all + p * db, dev[p].dense, db, hipMemcpyDefault, dev[q].xs));
             }
             HIPCHK(hipEventRecord(dev[q].gathered, dev[q].xs));
-            HIPCHK(hipStreamWaitEvent(models[q]->stream, dev[q].gathered, 0));
+            SBRCHK(stream_wait(models[q], models[q]->stream, dev[q].gathered));
             SBRCHK(sbr_fit_step_apply_table(dev[q].plan, dev[q].table, dev[q].dense_all));
             HIPCHK(hipEventRecord(dev[q].applied, models[q]->stream));
             return SBR_OK;
@@ -2956,6 +3077,7 @@ struct sbr_group_plan {
         models.assign(ms, ms + count);
         dev.resize(n);
         partitioned = models[0]->shared != nullptr;
+        if (partitioned) models[0]->shared->owner_updated.assign(n, nullptr);
         /* a partitioned table is updated in place by its owners after a rendezvous, so there is no staleness-one pipeline for
          * it: Parallelism::Asynchronous runs the synchronous step there (same everywhere a partitioned table is driven) */
         async = models[0]->hp.parallelism == SBR_PAR_ASYNCHRONOUS && !partitioned;
@@ -3051,6 +3173,7 @@ struct sbr_group_plan {
         workers.reset();
         (void)gather_optimizer_state(); /* (an abandoned plan as well: the models outlive it) */
         drain();
+        if (partitioned && n && models[0]->shared) models[0]->shared->owner_updated.clear(); /* the events below go; everything has landed */
         for (uint32_t r = 0; r < n; ++r) {
             Dev& v = dev[r];
             hipSetDevice(models[r]->device);
@@ -3617,7 +3740,7 @@ sbr_status scan_launch(sbr_model* m, uint64_t launches, uint32_t* d_flag, const 
 sbr_status sbr_user_representation(sbr_model* m, const uint32_t* item_ids, uint64_t n, float* out_dim) {
     if (!m || !out_dim || (n && !item_ids)) return SBR_ERR_INVALID_ARGUMENT;
     std::lock_guard<std::mutex> lock(m->mu);
-    SBRCHK(ensure_device(m));
+    SBRCHK(enter_reader(m));
     const uint32_t* first = nullptr;
     int nsteps = 0;
     state_window(item_ids, n, m->hp.max_sequence_length, &first, &nsteps);
@@ -3633,7 +3756,7 @@ sbr_status sbr_user_representation(sbr_model* m, const uint32_t* item_ids, uint6
 sbr_status sbr_predict(sbr_model* m, const float* user_dim, const uint32_t* item_ids, uint64_t n, float* out) {
     if (!m || !user_dim || (n && (!item_ids || !out))) return SBR_ERR_INVALID_ARGUMENT;
     std::lock_guard<std::mutex> lock(m->mu);
-    SBRCHK(ensure_device(m));
+    SBRCHK(enter_reader(m));
     for (uint64_t i = 0; i < n; ++i)
         if (item_ids[i] >= m->hp.num_items) return SBR_ERR_INVALID_ARGUMENT;
     if (n == 0) return SBR_OK;
@@ -3678,7 +3801,7 @@ sbr_status sbr_mrr_score(sbr_model* m, const uint64_t* user_ptr, const uint32_t*
                          float* out_mrr, uint32_t* out_ranks, uint64_t* out_num_ranked) {
     if (!m || !user_ptr || !out_mrr) return SBR_ERR_INVALID_ARGUMENT;
     std::lock_guard<std::mutex> lock(m->mu);
-    SBRCHK(ensure_device(m));
+    SBRCHK(enter_reader(m));
     SBRCHK(check_csr(m, user_ptr, num_users, item_ids, true));
     std::vector<uint64_t> users; /* users with >= 2 interactions (evaluation.rs:20) */
     for (uint64_t u = 0; u < num_users; ++u)
@@ -3843,7 +3966,7 @@ sbr_status sbr_recommend(sbr_model* m, const uint64_t* user_ptr, const uint32_t*
     if (!m || !user_ptr || (num_users && !out_items)) return SBR_ERR_INVALID_ARGUMENT;
     if (k < 1 || k > SBR_RECOMMEND_MAX_K || (flags & ~SBR_RECOMMEND_INCLUDE_HISTORY)) return SBR_ERR_INVALID_ARGUMENT;
     std::lock_guard<std::mutex> lock(m->mu);
-    SBRCHK(ensure_device(m));
+    SBRCHK(enter_reader(m));
     SBRCHK(check_csr(m, user_ptr, num_users, item_ids, false));
     /* the WHOLE history is masked (evaluation.rs:30-32) */
     return recommend_scan(m, RepSource{user_ptr, item_ids, nullptr, 0, !(flags & SBR_RECOMMEND_INCLUDE_HISTORY)}, num_users, k, out_items, out_scores);
@@ -3855,7 +3978,7 @@ sbr_status sbr_recommend_reps(sbr_model* m, const float* reps, uint64_t num_user
     if (k < 1 || k > SBR_RECOMMEND_MAX_K) return SBR_ERR_INVALID_ARGUMENT;
     if (!excl_args_ok(excl_ptr, excl_items, num_users)) return SBR_ERR_INVALID_ARGUMENT;
     std::lock_guard<std::mutex> lock(m->mu);
-    SBRCHK(ensure_device(m));
+    SBRCHK(enter_reader(m));
     if (excl_ptr) SBRCHK(check_csr(m, excl_ptr, num_users, excl_items, false));
     return recommend_scan(m, RepSource{excl_ptr, excl_items, reps, 0, true}, num_users, k, out_items, out_scores);
 }
@@ -3869,7 +3992,7 @@ sbr_status sbr_similar_items(sbr_model* m, const uint32_t* query_items, uint64_t
     if (k < 1 || k > SBR_RECOMMEND_MAX_K || metric > SBR_SIMILAR_DOT || (flags & ~SBR_SIMILAR_INCLUDE_SELF)) return SBR_ERR_INVALID_ARGUMENT;
     if (!excl_args_ok(excl_ptr, excl_items, num_queries)) return SBR_ERR_INVALID_ARGUMENT;
     std::lock_guard<std::mutex> lock(m->mu);
-    SBRCHK(ensure_device(m));
+    SBRCHK(enter_reader(m));
     for (uint64_t j = 0; j < num_queries; ++j)
         if (query_items[j] >= m->hp.num_items) return SBR_ERR_INVALID_ARGUMENT;
     if (excl_ptr) SBRCHK(check_csr(m, excl_ptr, num_queries, excl_items, false));
@@ -3968,7 +4091,7 @@ sbr_status score_candidates_scan(sbr_model* m, const RepSource& s, uint64_t num_
 sbr_status sbr_user_representations(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users, float* out_reps) {
     if (!m || !user_ptr || (num_users && !out_reps)) return SBR_ERR_INVALID_ARGUMENT;
     std::lock_guard<std::mutex> lock(m->mu);
-    SBRCHK(ensure_device(m));
+    SBRCHK(enter_reader(m));
     SBRCHK(check_csr(m, user_ptr, num_users, item_ids, false));
     std::vector<uint64_t> users(num_users);
     for (uint64_t u = 0; u < num_users; ++u) users[u] = u;
@@ -3996,7 +4119,7 @@ sbr_status sbr_score_candidates(sbr_model* m, const uint64_t* user_ptr, const ui
                                 const uint64_t* cand_ptr, const uint32_t* cand_items, float* out_scores) {
     if (!m || !user_ptr) return SBR_ERR_INVALID_ARGUMENT;
     std::lock_guard<std::mutex> lock(m->mu);
-    SBRCHK(ensure_device(m));
+    SBRCHK(enter_reader(m));
     SBRCHK(check_csr(m, user_ptr, num_users, item_ids, false));
     return score_candidates_scan(m, RepSource{user_ptr, item_ids, nullptr, 0, false}, num_users, cand_ptr, cand_items, out_scores);
 }
@@ -4005,7 +4128,7 @@ sbr_status sbr_score_candidates_reps(sbr_model* m, const float* reps, uint64_t n
                                      float* out_scores) {
     if (!m || (num_users && !reps)) return SBR_ERR_INVALID_ARGUMENT;
     std::lock_guard<std::mutex> lock(m->mu);
-    SBRCHK(ensure_device(m));
+    SBRCHK(enter_reader(m));
     return score_candidates_scan(m, RepSource{nullptr, nullptr, reps, 0, false}, num_users, cand_ptr, cand_items, out_scores);
 }
 
@@ -4014,7 +4137,7 @@ sbr_status sbr_recommend_among(sbr_model* m, const uint64_t* user_ptr, const uin
     if (!m || !user_ptr || (num_users && !out_items)) return SBR_ERR_INVALID_ARGUMENT;
     if (k < 1 || k > SBR_RECOMMEND_MAX_K || (flags & ~SBR_RECOMMEND_INCLUDE_HISTORY)) return SBR_ERR_INVALID_ARGUMENT;
     std::lock_guard<std::mutex> lock(m->mu);
-    SBRCHK(ensure_device(m));
+    SBRCHK(enter_reader(m));
     SBRCHK(check_csr(m, user_ptr, num_users, item_ids, false));
     return recommend_among_scan(m, RepSource{user_ptr, item_ids, nullptr, 0, !(flags & SBR_RECOMMEND_INCLUDE_HISTORY)}, num_users, k, subset_items,
                                 num_subset, out_items, out_scores);
@@ -4027,7 +4150,7 @@ sbr_status sbr_recommend_among_reps(sbr_model* m, const float* reps, uint64_t nu
     if (k < 1 || k > SBR_RECOMMEND_MAX_K) return SBR_ERR_INVALID_ARGUMENT;
     if (!excl_args_ok(excl_ptr, excl_items, num_users)) return SBR_ERR_INVALID_ARGUMENT;
     std::lock_guard<std::mutex> lock(m->mu);
-    SBRCHK(ensure_device(m));
+    SBRCHK(enter_reader(m));
     if (excl_ptr) SBRCHK(check_csr(m, excl_ptr, num_users, excl_items, false));
     return recommend_among_scan(m, RepSource{excl_ptr, excl_items, reps, 0, true}, num_users, k, subset_items, num_subset, out_items, out_scores);
 }
@@ -4115,7 +4238,7 @@ sbr_status sbr_rank_targets(sbr_model* m, const uint64_t* user_ptr, const uint32
                             const uint64_t* target_ptr, const uint32_t* target_items, uint32_t flags, uint32_t* out_ranks) {
     if (!m || !user_ptr || (flags & ~SBR_RANK_INCLUDE_HISTORY)) return SBR_ERR_INVALID_ARGUMENT;
     std::lock_guard<std::mutex> lock(m->mu);
-    SBRCHK(ensure_device(m));
+    SBRCHK(enter_reader(m));
     SBRCHK(check_csr(m, user_ptr, num_users, item_ids, false));
     /* the WHOLE history is masked (evaluation.rs:30-32) */
     return rank_targets_scan(m, RepSource{user_ptr, item_ids, nullptr, 0, !(flags & SBR_RANK_INCLUDE_HISTORY)}, num_users, target_ptr,
@@ -4127,7 +4250,7 @@ sbr_status sbr_rank_targets_reps(sbr_model* m, const float* reps, uint64_t num_u
     if (!m || (num_users && !reps)) return SBR_ERR_INVALID_ARGUMENT;
     if (!excl_args_ok(excl_ptr, excl_items, num_users)) return SBR_ERR_INVALID_ARGUMENT;
     std::lock_guard<std::mutex> lock(m->mu);
-    SBRCHK(ensure_device(m));
+    SBRCHK(enter_reader(m));
     if (excl_ptr) SBRCHK(check_csr(m, excl_ptr, num_users, excl_items, false));
     return rank_targets_scan(m, RepSource{excl_ptr, excl_items, reps, 0, true}, num_users, target_ptr, target_items, out_ranks);
 }
@@ -4211,6 +4334,49 @@ sbr_status sbr_selftest_sort(const uint32_t* rows, uint64_t n, uint32_t row_bits
     HIPCHK(hipMemcpy(out_head_pos, dheads, ((uint64_t)*out_nheads + 1) * 4, hipMemcpyDeviceToHost));
     dfree(drows); dfree(dheads); dfree(dn); dfree(dtmp); dfree(dout); dfree(temp);
     return SBR_OK;
+}
+
+/* the stream-delay test hook's counter: delay kernels queued per role (main, side, sorter, copier, xs) on this model's streams
+ * since the last read */
+sbr_status sbr_test_delays_queued(sbr_model* m, uint64_t out[5]) {
+    if (!m || !out) return SBR_ERR_INVALID_ARGUMENT;
+    for (int r = 0; r < ROLE_COUNT; ++r) out[r] = m->test_delays[r].exchange(0, std::memory_order_relaxed);
+    return SBR_OK;
+}
+
+/* What the stream-delay method can see (tests/test_stream_joins_gpu.py): a float that is 1.0; stream A: delay, store of 2.0, event;
+ * stream B: waits for the event (with_join) or not, then copies the float.  *out = 2.0 with the join; without it B's copy runs
+ * while A is still held back and reads 1.0.  Only a plain float is ever read early. */
+sbr_status sbr_selftest_stream_delay(uint32_t delay_us, int32_t with_join, float* out) {
+    int nd = 0;
+    if (hipGetDeviceCount(&nd) != hipSuccess || nd == 0) return SBR_ERR_NO_DEVICE;
+    if (!out) return SBR_ERR_INVALID_ARGUMENT;
+    const unsigned long long ticks = (unsigned long long)std::min(delay_us, test_delay_max_us) * (unsigned long long)wall_clock_khz() / 1000ull;
+    float* cell = nullptr; /* [0] the float, [1] B's copy of it */
+    SBRCHK(dmalloc(&cell, 2));
+    const float init[2] = {1.0f, 0.0f};
+    hipStream_t a = nullptr, b = nullptr;
+    hipEvent_t stored = nullptr;
+    sbr_status st = SBR_OK;
+    if (hipMemcpy(cell, init, sizeof(init), hipMemcpyHostToDevice) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+        hipStreamCreateWithFlags(&a, hipStreamNonBlocking) != hipSuccess || hipStreamCreateWithFlags(&b, hipStreamNonBlocking) != hipSuccess ||
+        hipEventCreateWithFlags(&stored, hipEventDisableTiming) != hipSuccess)
+        st = SBR_ERR_HIP;
+    if (st == SBR_OK) {
+        sbr::launch_stream_delay(ticks, a);
+        sbr::launch_selftest_store(cell, 2.0f, a);
+        if (hipEventRecord(stored, a) != hipSuccess) st = SBR_ERR_HIP;
+        if (st == SBR_OK && with_join && hipStreamWaitEvent(b, stored, 0) != hipSuccess) st = SBR_ERR_HIP;
+        if (st == SBR_OK && hipMemcpyAsync(cell + 1, cell, sizeof(float), hipMemcpyDeviceToDevice, b) != hipSuccess) st = SBR_ERR_HIP;
+    }
+    if (b && hipStreamSynchronize(b) != hipSuccess) st = SBR_ERR_HIP;
+    if (a && hipStreamSynchronize(a) != hipSuccess) st = SBR_ERR_HIP;
+    if (st == SBR_OK && hipMemcpy(out, cell + 1, sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) st = SBR_ERR_HIP;
+    if (stored) hipEventDestroy(stored);
+    if (a) hipStreamDestroy(a);
+    if (b) hipStreamDestroy(b);
+    dfree(cell);
+    return st;
 }
 
 sbr_status sbr_set_device(int32_t ordinal) {

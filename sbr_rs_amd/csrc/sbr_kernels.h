@@ -319,6 +319,10 @@ void launch_selftest_mfma32_chain(const float* a, const float* b, int k, float* 
 /* the key ordering alone: keys (rows[e] << 32 | e) of n entries in (row, e) order + segment heads */
 void launch_selftest_sort(const uint32_t* rows, uint32_t n, int row_bits, uint64_t* tmp, uint64_t* out, void* temp, uint32_t* head_pos,
                           uint32_t* nheads, hipStream_t s);
+/* test hook (SBR_TEST_STREAM_DELAY): one wave, no memory traffic, that ends once the constant-rate clock has advanced by `ticks`
+ * (or after a fixed number of polls, whichever comes first); *dst = v by one lane (sbr_selftest_stream_delay) */
+void launch_stream_delay(unsigned long long ticks, hipStream_t s);
+void launch_selftest_store(float* dst, float v, hipStream_t s);
 
 }  // namespace sbr
 #endif

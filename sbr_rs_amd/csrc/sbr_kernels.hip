@@ -2886,6 +2886,22 @@ __global__ void selftest_mfma32_chain_kernel(const float* a, const float* b, int
     for (int q = 0; q < 16; ++q) out[((q & 3) + 8 * (q >> 2) + 4 * hh) * 32 + l31] = acc[q];
 }
 
+// ------------------------------------------------------------------------------------------------
+// stream-delay test hook (SBR_TEST_STREAM_DELAY, sbr_selftest_stream_delay)
+// ------------------------------------------------------------------------------------------------
+// One wave that holds its stream until the constant-rate clock (wall_clock64) has advanced by `ticks`: it sleeps between
+// looks at the clock and touches no memory.  `max_polls` ends it whatever the clock does — a bounded wait, never a hang.
+__global__ void stream_delay_kernel(unsigned long long ticks, unsigned max_polls) {
+    const unsigned long long t0 = (unsigned long long)wall_clock64();
+    for (unsigned i = 0; i < max_polls; ++i) {
+        if ((unsigned long long)wall_clock64() - t0 >= ticks) break;
+        __builtin_amdgcn_s_sleep(127);
+    }
+}
+__global__ void selftest_store_kernel(float* dst, float v) {
+    if (threadIdx.x == 0) *dst = v;
+}
+
 // ================================================================================================
 // launchers
 // ================================================================================================
@@ -3392,6 +3408,14 @@ void launch_selftest_mfma_chain(const float* a, const float* b, const float* c0,
 }
 void launch_selftest_mfma32_chain(const float* a, const float* b, int k, float* out, hipStream_t s) {
     hipLaunchKernelGGL(selftest_mfma32_chain_kernel, dim3(1), dim3(64), 0, s, a, b, k, out);
+}
+void launch_stream_delay(unsigned long long ticks, hipStream_t s) {
+    /* a poll is one s_sleep 127 (8 128 clocks: > 2 us at any engine clock) + one look at the clock; 16 384 polls are more than
+     * 30 ms of sleeping for a request that the engine clamps to 5 ms, and the end of the kernel whatever the clock reads */
+    hipLaunchKernelGGL(stream_delay_kernel, dim3(1), dim3(64), 0, s, ticks, 16384u);
+}
+void launch_selftest_store(float* dst, float v, hipStream_t s) {
+    hipLaunchKernelGGL(selftest_store_kernel, dim3(1), dim3(64), 0, s, dst, v);
 }
 
 }  // namespace sbr

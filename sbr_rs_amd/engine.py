@@ -52,6 +52,16 @@ def _ptr(a: np.ndarray):
     return a.ctypes.data_as(C.c_void_p)
 
 
+STREAM_ROLES = ("main", "side", "sorter", "copier", "xs")  # the roles SBR_TEST_STREAM_DELAY names, in the counter's order
+
+
+def selftest_stream_delay(delay_us: int, with_join: bool) -> float:
+    """sbr_selftest_stream_delay: what a stream reads of a float (1.0) that a stream late by ``delay_us`` sets to 2.0."""
+    out = C.c_float()
+    _check(_lib.load().sbr_selftest_stream_delay(int(delay_us), 1 if with_join else 0, C.byref(out)))
+    return out.value
+
+
 def device_info():
     L = _lib.load()
     name = C.create_string_buffer(64)
@@ -497,6 +507,13 @@ class Model:
     def set_overlap(self, on: bool = True):
         """False: side-stream work runs on the main stream, so kernel families are timed standalone."""
         _check(self._L.sbr_model_set_overlap(self._h, 1 if on else 0))
+
+    def test_delays_queued(self):
+        """Delay kernels the stream-delay test hook (SBR_TEST_STREAM_DELAY) has queued on this model's streams since the last
+        read, per role (sbr_test_delays_queued)."""
+        n = (C.c_uint64 * len(STREAM_ROLES))()
+        _check(self._L.sbr_test_delays_queued(self._h, n))
+        return {role: int(n[i]) for i, role in enumerate(STREAM_ROLES)}
 
     def timing_read(self):
         ms = (C.c_double * NUM_KERNEL_FAMILIES)()

@@ -61,6 +61,8 @@ def test_no_device_fails_loudly():
     assert e.value.status == Status.NO_DEVICE
     x = np.zeros(4, np.float32)
     assert _lib.load().sbr_selftest_math(x.ctypes.data_as(C.c_void_p), 4, None, None, None) == Status.NO_DEVICE
+    out = C.c_float(-1.0)
+    assert _lib.load().sbr_selftest_stream_delay(100, 1, C.byref(out)) == Status.NO_DEVICE and out.value == -1.0
 
 
 def test_python_surface_mirrors_reference_names():
