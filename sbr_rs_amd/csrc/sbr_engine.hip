@@ -726,6 +726,73 @@ sbr_status alloc_work(const sbr_model* m, uint64_t rmax, uint64_t bmax, bool tra
     return SBR_OK;
 }
 
+/* ---- a training step's stream schedule: what the local half of ONE step queues on which stream.  Decided once, by step_schedule(),
+ * before anything is queued; the step's consumers read the form of the block from the copy left in the plan (StepLeft). ---- */
+enum SortAt {
+    SORT_IN_SCORE,    /* the score launch orders the keys itself (StepSchedule::small_tail): no ordering launch */
+    SORT_AT_START,    /* single-negative losses: the negatives are a hash of the row counter, the ordering needs only the index arrays */
+    SORT_AFTER_SCORE, /* WARP (the negatives come out of the score kernel), everything on the main stream: between score and BPTT */
+    SORT_AFTER_BPTT,  /* WARP with the side streams: behind the score kernel's event on the sorter, but queued by the host BEHIND
+                       * BPTT — the ordering's up to nine short launches would otherwise sit in the host's queue ahead of the backward
+                       * pass (50 us at a few hundred sequences per step, as long as the pass itself).  There it takes whatever slots
+                       * BPTT's retiring workgroups free and is finished by the time the update needs the keys.  (Measured and dropped:
+                       * the main stream before or right after BPTT for large steps — its 0.1-0.3 ms are then on the critical path;
+                       * profiles/r04_tail_experiments.md (c).) */
+};
+struct StepSchedule {
+    /* The side streams engage.  A small step (its sparse update is the single-launch form: <= 4 096 keys, 1 365 rows) is a chain of
+     * launches of a few microseconds each; the event hand-offs between three streams then cost more than the overlap buys
+     * (MovieLens-100K at one sequence per step: 1.67 s with the side streams, 1.57 s on one), so everything goes on the main stream. */
+    bool overlap = false;
+    /* the dense-gradient GEMM (MFMA-bound, reads dZ / X / H only): with overlap the side stream, so that the HBM-bound sparse
+     * update that follows on the main stream overlaps it (ev_fork -> ev_join) */
+    hipStream_t dense_on = nullptr;
+    /* the key ordering: with overlap the sorter stream, underneath the backward pass (ev_scored -> ev_sorted); queued at sort_at */
+    hipStream_t sort_on = nullptr;
+    SortAt sort_at = SORT_IN_SCORE;
+    /* WARP step with the ordering on the sorter: the per-sequence loss sums and the block header (row count, loss sum; the
+     * single-device accumulators) are queued on THAT stream, behind the score kernel's event and ahead of the ordering — between
+     * score and BPTT they were two launches and their gaps (~35 us of a 2.5 ms step) on the critical path for nobody's benefit.
+     * Their consumers (update / scatter / dense / fit_end) all join the ordering's stream first. */
+    bool side_header = false;
+    /* EWMA + single-negative loss (BASELINE configs[4]): scan, scores and backward scan of a sequence in ONE pass (ewma_seq_kernel;
+     * same bits as scan | score | backward scan, which EWMA + WARP and the reference-order mode still take: their negatives depend
+     * on the scores / on a sequential stream) */
+    bool ewma_fused = false;
+    /* the figure the reference's fit returns (sbr_report.hip): a small step folds the lagged chain into the header launch; otherwise
+     * the per-sequence sums come from a parallel kernel and the sequential chain runs as one wave on the ordering's stream, queued
+     * at the end of the local half, off the critical path (ev_seqsum -> ev_lagged) */
+    bool fuse_lag = false;
+    /* under sbr_fit_step, small LSTM step: the dense gradient is left to the optimiser half's single launch (sbr::launch_small_back) */
+    bool dw_deferred = false;
+    /* Single device: the hot rows (segments of more than SBR_SEG_CHUNK entries: a skewed catalogue) are listed and their chunk units
+     * counted behind the ordering on ITS stream, still underneath BPTT — registering them during the short-segment pass put their
+     * three launches behind it on the update's critical path (Zipf(1) items at 8 192 sequences per step: 0.13 of 2.66 ms).  Only
+     * under sbr_fit_step: the list's only consumer is sbr_fit_step_apply; a caller that drives ONE device through the exchange halves
+     * (scatter / reduce_own register long segments themselves, on the main stream) must not find the list kernels beside them. */
+    bool hot_prelist = false;
+    bool header_accumulates = false; /* single device: the header kernel adds the step to loss_acc / ex_acc itself (one launch fewer) */
+    /* ONE subsequence per step at d <= 32 (the reference's own schedule): header, lagged loss figure and the ordering of the step's
+     * keys run at the end of the score launch (sbr::SmallTail) — three launches of ~5 us fewer in a step of ~40-100 us */
+    bool small_tail() const { return sort_at == SORT_IN_SCORE; }
+};
+/* What the main stream may have to join before it reads or overwrites something a step left on another stream (join_main):
+ *   need       event      recorded on   guards
+ *   KEYS       ev_sorted  sorter        keys_sorted and the segment heads
+ *   HEADER     ev_sorted  sorter        the block header and the loss accumulators of a step with a side header
+ *   DENSE      ev_join    side          blk.dense (or its chunk partials)
+ *   LAG_STATE  ev_lagged  sorter        lag_state / lag_seqsum (the lagged chain)
+ *   TABLE      ev_hot     sorter        the hot rows of the item table (sbr_fit_step_apply's pass beside the short segments)
+ * The rule, for every event alike: recording it makes it OWED; join_main() waits for what is owed among the caller's needs and
+ * clears it; nothing else does.  A debt so outlives the step that made it: where a step whose ordering ran on the main stream
+ * follows one whose ordering ran on the sorter and nobody has joined that one, the next reader of the keys still waits for
+ * ev_sorted, on one device or several.  An event the main stream has joined is not waited for again. */
+enum : unsigned { KEYS = 1, HEADER = 2, DENSE = 4, LAG_STATE = 8, TABLE = 16 };
+struct StepLeft { /* what a step's local half leaves in the plan for its consumers */
+    StepSchedule form;              /* of the last local half; cleared by the step's last consumer (step_consumed) */
+    int dense_unreduced_chunks = 0; /* > 0: blk.dense is still that many chunk partials in wb.v.partials (one device: reduced by its consumer) */
+    unsigned owed = 0;              /* the needs above whose event the main stream has not joined */
+};
 }  // namespace
 
 struct sbr_fit_plan {
@@ -778,23 +845,13 @@ struct sbr_fit_plan {
     bool ref_rng_live = false;     /* ... and it has been advanced since the host last held it */
     unsigned long long* phase_clocks = nullptr; /* [6] epoch_steps_kernel's per-phase s_memtime ticks + steps (sbr_fit_debug_phase_clocks) */
     sbr::SegScratch seg{}; /* long-segment path of the sparse reduction (hot rows) */
-    bool dense_pending = false; /* the side stream still owes blk.dense */
-    bool hot_prelisted = false; /* this step's long segments (hot rows) were listed behind the ordering: their chunks are reduced on the
-                                 * ordering's stream beside the short-segment pass (sbr_fit_step_apply) */
+    StepLeft left; /* the last step's form and what the main stream has not joined of it (join_main) */
     hipEvent_t ev_hot = nullptr;
-    bool fuse_back = false;     /* sbr_fit_step: the step's optimiser half may take the single-launch form (sbr::launch_small_back) */
-    bool dw_deferred = false;   /* ... and step_local left the dense gradient to it */
-    int dense_unreduced_chunks = 0; /* > 0: blk.dense is still that many chunk partials in wb.v.partials (one device: reduced by its consumer) */
-    bool sort_off_stream = false; /* the step's key ordering ran on another stream than the main one: ev_sorted joins it */
-    bool sorted_event_live = false; /* ev_sorted has been recorded at least once: the multi-device consumers wait on it whatever the
-                                     * last step's placement was (a completed event costs nothing; the flag above belongs to ONE step) */
-    bool header_accumulated = false; /* single device: block_header_kernel already added this step to loss_acc / ex_acc */
     /* the loss figure the reference's fit returns (sbr_report.hip): [accumulator | loss-node value per sequence length], the
      * per-sequence sums of the current step, and the events that order the one-wave chain kernel (sorter stream) against the
      * main stream */
     float *lag_state = nullptr, *lag_seqsum = nullptr;
     hipEvent_t ev_seqsum = nullptr, ev_lagged = nullptr;
-    bool lag_busy = false; /* ev_lagged is pending on another stream than the main one */
     /* partitioned item table: this device's gradient list (addressed by sorted-key position), the owner
      * bounds, and the owner-side merge buffers */
     float *glist = nullptr, *gblist = nullptr;
@@ -1651,200 +1708,160 @@ sbr_status sbr_fit_minibatch_rows(const sbr_fit_plan* p, uint64_t minibatch, uin
     return SBR_OK;
 }
 
-static sbr_status join_dense(sbr_fit_plan* p) {
-    if (p->dense_pending) {
-        SBRCHK(stream_wait(p->m, p->m->stream, p->m->ev_join));
-        p->dense_pending = false;
+/* The main stream joins what earlier steps left on other streams, as far as the caller is about to read or overwrite it (`needs`: the
+ * table above StepLeft) and it is still owed: the only place a step function makes the main stream wait (`open`: as stream_wait) */
+static sbr_status join_main(sbr_fit_plan* p, unsigned needs, ScopedTimer* open = nullptr) {
+    sbr_model* m = p->m;
+    const struct { unsigned needs; hipEvent_t ev; } joins[] = {
+        {LAG_STATE, p->ev_lagged}, {KEYS | HEADER, m->ev_sorted}, {DENSE, m->ev_join}, {TABLE, p->ev_hot}};
+    for (const auto& j : joins) {
+        if (!(needs & p->left.owed & j.needs)) continue;
+        SBRCHK(stream_wait(m, m->stream, j.ev, open));
+        p->left.owed &= ~j.needs;
     }
     return SBR_OK;
 }
 
 /* blk.dense complete on the main stream: joins the GEMM and, if its chunk partials are still unreduced, reduces them */
 static sbr_status ensure_dense_reduced(sbr_fit_plan* p) {
-    SBRCHK(join_dense(p));
-    if (p->dense_unreduced_chunks > 0) {
-        sbr::launch_dense_reduce(p->m->mv, p->wb.v, p->dense_unreduced_chunks, block_view(p->m, p->block, p->rmax), p->m->stream);
-        p->dense_unreduced_chunks = 0;
+    SBRCHK(join_main(p, DENSE));
+    if (p->left.dense_unreduced_chunks > 0) {
+        sbr::launch_dense_reduce(p->m->mv, p->wb.v, p->left.dense_unreduced_chunks, block_view(p->m, p->block, p->rmax), p->m->stream);
+        p->left.dense_unreduced_chunks = 0;
     }
     return SBR_OK;
 }
 
-sbr_status sbr_fit_step_local(sbr_fit_plan* p, uint64_t minibatch) {
-    if (!p || minibatch >= p->ep[p->cur].num_mb) return SBR_ERR_INVALID_ARGUMENT;
+/* the step's last consumer has run (or the block has been overwritten): its form says nothing any more; what is owed stays owed */
+static void step_consumed(sbr_fit_plan* p) {
+    p->left = StepLeft{StepSchedule{}, 0, p->left.owed};
+}
+
+/* no side effects, no HIP calls; fuse_back: called under sbr_fit_step, where nobody looks at the block between the two halves */
+static StepSchedule step_schedule(const sbr_fit_plan* p, const sbr_fit_plan::Mb& mb, bool fuse_back) {
+    const sbr_model* m = p->m;
+    const bool one = p->ndev == 1, warp = m->hp.loss == SBR_LOSS_WARP;
+    constexpr int small_rows = 1365;
+    StepSchedule s;
+    s.overlap = m->overlap && mb.R > small_rows;
+    s.dense_on = s.overlap ? m->side : m->stream;
+    s.sort_on = s.overlap ? m->sorter : m->stream;
+    const bool small_tail = (m->step_fusion >= 1 || m->reference_order) && !s.overlap && (one || m->reference_order) &&
+                            sbr::small_tail_shape_ok(m->mv, (int)mb.B, (int)mb.R, m->reference_order);
+    s.sort_at = small_tail ? SORT_IN_SCORE : !warp ? SORT_AT_START : s.overlap ? SORT_AFTER_BPTT : SORT_AFTER_SCORE;
+    s.side_header = s.overlap && warp;
+    s.ewma_fused = !m->ng && !warp && mb.R > 0 && !m->reference_order;
+    s.fuse_lag = !s.overlap && mb.B <= SBR_HEADER_LAG_MAX_B;
+    s.dw_deferred = m->step_fusion >= 1 && fuse_back && !s.overlap && one && sbr::small_back_shape_ok(m->mv, (int)mb.R) && (m->ng || mb.B <= 256);
+    s.hot_prelist = one && s.overlap && fuse_back && 3ull * (uint64_t)mb.R > 4096;
+    s.header_accumulates = one;
+    return s;
+}
+
+static sbr_status step_local(sbr_fit_plan* p, uint64_t minibatch, bool fuse_back) {
+    if (minibatch >= p->ep[p->cur].num_mb) return SBR_ERR_INVALID_ARGUMENT;
     sbr_model* m = p->m;
     SBRCHK(ensure_device(m));
-    void* block = p->block;
     const sbr_fit_plan::Epoch& ep = p->ep[p->cur];
     const sbr_fit_plan::Mb& mb = ep.mbs[minibatch];
     const sbr::MbView mv = mb_view(p, minibatch);
-    const sbr::BlockView bv = block_view(m, block, p->rmax);
+    const sbr::BlockView bv = block_view(m, p->block, p->rmax);
     const int* off_host = ep.off_host.data() + mb.off_base;
     SBRCHK(stream_head(m, m->stream));
-    /* The sort of the sparse-update keys needs only the index arrays and the negatives: it runs on its own stream,
-     * underneath the backward pass (WARP: the negatives come out of the score kernel) or, for the single-negative losses
-     * whose negatives are a hash of the row counter, from the very start of the step (joined by step_apply / step_scatter). */
-    /* A small step (its sparse update is the single-launch form: <= 4 096 keys) is a chain of launches of a few microseconds
-     * each; the event hand-offs between three streams then cost more than the overlap buys (MovieLens-100K at one sequence per
-     * step: 1.67 s with the side streams, 1.57 s on one), so everything is queued on the main stream. */
-    constexpr int small_rows = 1365;
-    const bool overlap = m->overlap && mb.R > small_rows;
-    hipStream_t side = overlap ? m->side : m->stream;
-    /* Where the key ordering of a WARP step runs (its negatives come out of the score kernel): on its own stream from the end of the
-     * score kernel on — it takes whatever slots the backward pass's retiring workgroups free, and is finished by the time the update
-     * needs the keys; a small step (everything on one stream) orders between score and backward pass.  (Measured and dropped: the
-     * main stream before or right after the backward pass for large steps — its 0.1-0.3 ms are then on the critical path;
-     * profiles/r04_tail_experiments.md (c).) */
-    enum { SORT_OWN_STREAM, SORT_PRE };
-    const int place = overlap ? SORT_OWN_STREAM : SORT_PRE;
-    hipStream_t sorter = place == SORT_OWN_STREAM ? m->sorter : m->stream;
-    const bool early_sort = m->hp.loss != SBR_LOSS_WARP;
+    const StepSchedule s = step_schedule(p, mb, fuse_back);
+    StepLeft& left = p->left = StepLeft{s, 0, p->left.owed};
     const uint64_t epoch_key = sbr_epoch_key(p->fit_seed[p->rank], ep.epoch_key_epoch);
-    /* WARP step with the ordering on its own stream: the per-sequence loss sums and the block header (row count, loss sum; the
-     * single-device accumulators) are queued on THAT stream, behind the score kernel's event and ahead of the ordering — between
-     * score and BPTT they were two launches and their gaps (~35 us of a 2.5 ms step) on the critical path for nobody's benefit.
-     * Their consumers (update / scatter / dense / fit_end) all join the ordering's stream first. */
-    const bool side_header = overlap && !early_sort && place == SORT_OWN_STREAM;
-    /* ONE subsequence per step at d <= 32 (the reference's own schedule): header, lagged loss figure and the ordering of the step's
-     * keys run at the end of the score launch (sbr::SmallTail) — three launches of ~5 us fewer in a step of ~40-100 us */
-    const bool small_tail = (m->step_fusion >= 1 || m->reference_order) && !overlap && (p->ndev == 1 || m->reference_order) &&
-                            sbr::small_tail_shape_ok(m->mv, (int)mb.B, (int)mb.R, m->reference_order);
-    auto launch_sort = [&](hipStream_t on) -> sbr_status {
-        if (on != m->stream) {
-            /* everything before: the previous step's readers of the keys, this step's score (a WARP step records the event
-             * itself, before it queues the backward pass) */
-            if (early_sort) HIPCHK(hipEventRecord(m->ev_scored, m->stream));
+    double* const loss_acc = s.header_accumulates ? p->loss_acc : nullptr;
+    unsigned long long* const ex_acc = s.header_accumulates ? p->ex_acc : nullptr;
+    const sbr::SmallTail tail{bv.header, loss_acc, ex_acc, p->lag_state, p->keys_sorted, p->seg.head_pos, p->seg.nheads};
+    auto queue_sort = [&]() -> sbr_status {
+        hipStream_t on = s.sort_on;
+        if (s.overlap) {
+            /* everything before: the previous step's readers of the keys, this step's score (a step with a side header has
+             * recorded the event itself, before it queued the backward pass) */
+            if (s.sort_at == SORT_AT_START) HIPCHK(hipEventRecord(m->ev_scored, m->stream));
             SBRCHK(stream_wait(m, on, m->ev_scored));
         }
-        if (side_header) { /* the step's loss bookkeeping rides on the ordering's stream: nothing on the main stream waits for it */
+        if (s.side_header) { /* the step's loss bookkeeping rides on the ordering's stream: nothing on the main stream waits for it */
             sbr::launch_seq_loss(mv, p->wb.v.loss, p->lag_seqsum, p->lag_state, mb.B, on);
-            sbr::launch_block_header(m->mv, bv, p->wb.v, mv, mb.R, p->header_accumulated ? p->loss_acc : nullptr,
-                                     p->header_accumulated ? p->ex_acc : nullptr, nullptr, on);
+            sbr::launch_block_header(m->mv, bv, p->wb.v, mv, mb.R, loss_acc, ex_acc, nullptr, on);
         }
         {
             ScopedTimer t(m, SBR_K_SPARSE_SORT, 1, on);
             sbr::launch_own_sort(bv, (uint32_t)mb.R, p->keys, p->keys_sorted, p->sort_temp, p->sort_temp_bytes, p->key_bits, p->seg, on,
-                                 early_sort ? &mv : nullptr, epoch_key, m->hp.num_items);
+                                 s.sort_at == SORT_AT_START ? &mv : nullptr, epoch_key, m->hp.num_items);
         }
-        p->sort_off_stream = on != m->stream; /* on the main stream the update is ordered behind the sort anyway: no event */
-        if (p->sort_off_stream) {
+        if (s.overlap) { /* on the main stream the update is ordered behind the sort anyway: no event */
             HIPCHK(hipEventRecord(m->ev_sorted, on));
-            p->sorted_event_live = true;
-            /* single device: the hot rows (segments of more than SBR_SEG_CHUNK entries: a skewed catalogue) are listed and their
-             * chunk units counted HERE, still underneath BPTT — registering them during the short-segment pass put their three
-             * launches behind it on the update's critical path (Zipf(1) items at 8 192 sequences per step: 0.13 of 2.66 ms).
-             * (after ev_sorted: the short-segment pass does not wait for the list)
-             * Only under sbr_fit_step (fuse_back): the list's only consumer is sbr_fit_step_apply; a caller that drives ONE device
-             * through the exchange halves (scatter / reduce_own register long segments themselves, on the main stream) must not
-             * find the list kernels running beside them on this stream. */
-            if (p->ndev == 1 && overlap && p->fuse_back && 3ull * (uint64_t)mb.R > 4096) {
-                sbr::launch_seg_prelist(p->seg, on);
-                p->hot_prelisted = true;
-            }
+            left.owed |= KEYS | HEADER;
+            if (s.hot_prelist) sbr::launch_seg_prelist(p->seg, on);
         }
         return SBR_OK;
     };
-    p->hot_prelisted = false;
-    if (early_sort && !small_tail) SBRCHK(launch_sort(overlap ? m->sorter : m->stream));
-    if (small_tail) {
-        if (p->lag_busy) { /* an earlier step's chain on the ordering's stream still owns lag_state */
-            SBRCHK(stream_wait(m, m->stream, p->ev_lagged));
-            p->lag_busy = false;
-        }
-        p->sort_off_stream = false;
-    }
-    /* EWMA + single-negative loss (BASELINE configs[4]): scan, scores and backward scan of a sequence in ONE pass (ewma_seq_kernel; same
-     * bits as scan | score | backward scan, which EWMA + WARP and the reference-order mode still take: their negatives depend on the
-     * scores / on a sequential stream) */
-    const bool ewma_fused = !m->ng && m->hp.loss != SBR_LOSS_WARP && mb.R > 0 && !m->reference_order;
-    if (ewma_fused) {
+    if (s.sort_at == SORT_AT_START) SBRCHK(queue_sort());
+    if (s.small_tail()) SBRCHK(join_main(p, LAG_STATE)); /* an earlier step's chain on the sorter still owns lag_state */
+    if (s.ewma_fused) {
         ScopedTimer t(m, SBR_K_SCORE, 1);
-        p->header_accumulated = p->ndev == 1;
-        const sbr::SmallTail tail{bv.header, p->header_accumulated ? p->loss_acc : nullptr, p->header_accumulated ? p->ex_acc : nullptr,
-                                  p->lag_state, p->keys_sorted, p->seg.head_pos, p->seg.nheads};
-        sbr::launch_ewma_sequences(m->mv, mv, bv, p->wb.v, epoch_key, mb.R, m->stream, small_tail ? &tail : nullptr);
+        sbr::launch_ewma_sequences(m->mv, mv, bv, p->wb.v, epoch_key, mb.R, m->stream, s.small_tail() ? &tail : nullptr);
     } else {
         {
             ScopedTimer t(m, SBR_K_RECURRENT_FWD, m->ng && m->d > 128 ? (uint64_t)mb.Tm : 1); /* d <= 128: one sequence-resident launch */
             sbr::launch_recurrent_forward(m->mv, mv, bv.H, p->wb.v, mb.Tm, off_host, m->stream);
         }
-        {
-            ScopedTimer t(m, SBR_K_SCORE, 1);
-            p->header_accumulated = p->ndev == 1;
-            const sbr::SmallTail tail{bv.header, p->header_accumulated ? p->loss_acc : nullptr, p->header_accumulated ? p->ex_acc : nullptr,
-                                      p->lag_state, p->keys_sorted, p->seg.head_pos, p->seg.nheads};
-            if (m->reference_order) {
-                if (!p->ref_rng || !small_tail || !sbr::launch_score_reference_order(m->mv, mv, bv, p->wb.v, p->ref_rng, mb.R, m->stream, tail))
-                    return SBR_ERR_UNSUPPORTED;
-                p->ref_rng_live = true;
-            } else {
-                sbr::launch_score(m->mv, mv, bv, p->wb.v, epoch_key, mb.R, m->stream, small_tail ? &tail : nullptr);
-            }
+        ScopedTimer t(m, SBR_K_SCORE, 1);
+        if (m->reference_order) {
+            if (!p->ref_rng || !s.small_tail() || !sbr::launch_score_reference_order(m->mv, mv, bv, p->wb.v, p->ref_rng, mb.R, m->stream, tail))
+                return SBR_ERR_UNSUPPORTED;
+            p->ref_rng_live = true;
+        } else {
+            sbr::launch_score(m->mv, mv, bv, p->wb.v, epoch_key, mb.R, m->stream, s.small_tail() ? &tail : nullptr);
         }
     }
-    /* the figure the reference's fit returns (sbr_report.hip): a small step folds it into the header launch; otherwise the
-     * per-sequence sums come from a parallel kernel here and the sequential chain over the sequences runs as one wave on the
-     * sorter stream (queued at the end of this call), off the critical path */
-    /* single device: the loss accumulators take the block's header in the header kernel itself (one launch fewer per step) */
-    p->header_accumulated = p->ndev == 1;
-    const bool fuse_lag = !overlap && mb.B <= SBR_HEADER_LAG_MAX_B;
-    if (small_tail) {
-        /* done by the score launch */
-    } else if (side_header) {
+    if (s.side_header) {
         HIPCHK(hipEventRecord(m->ev_scored, m->stream)); /* right behind the score kernel */
-    } else {
-        if (p->lag_busy) { /* the previous step's chain may still be running on the sorter stream: it owns lag_state / lag_seqsum */
-            SBRCHK(stream_wait(m, m->stream, p->ev_lagged));
-            p->lag_busy = false;
-        }
-        if (!fuse_lag) {
+    } else if (!s.small_tail()) { /* (small tail: header and lagged figure are done by the score launch) */
+        SBRCHK(join_main(p, LAG_STATE)); /* the previous step's chain may still be running on the sorter: it owns lag_state / lag_seqsum */
+        if (!s.fuse_lag) {
             sbr::launch_seq_loss(mv, p->wb.v.loss, p->lag_seqsum, p->lag_state, mb.B, m->stream);
-            if (overlap) HIPCHK(hipEventRecord(p->ev_seqsum, m->stream));
+            if (s.overlap) HIPCHK(hipEventRecord(p->ev_seqsum, m->stream));
         }
-        sbr::launch_block_header(m->mv, bv, p->wb.v, mv, mb.R, p->header_accumulated ? p->loss_acc : nullptr,
-                                 p->header_accumulated ? p->ex_acc : nullptr, fuse_lag ? p->lag_state : nullptr, m->stream);
+        sbr::launch_block_header(m->mv, bv, p->wb.v, mv, mb.R, loss_acc, ex_acc, s.fuse_lag ? p->lag_state : nullptr, m->stream);
     }
-    /* host order: with the ordering on its own stream the backward pass is queued FIRST — the ordering's up to nine short
-     * launches would otherwise sit in the host's queue ahead of it (50 us at a few hundred sequences per step, as long as
-     * the pass itself); ev_scored, recorded here, is what the ordering waits for either way */
-    const bool sort_first = place == SORT_PRE;
-    if (!early_sort && sort_first && !small_tail) SBRCHK(launch_sort(sorter));
-    if (!early_sort && place == SORT_OWN_STREAM && !side_header) HIPCHK(hipEventRecord(m->ev_scored, m->stream));
-    if (!ewma_fused) {
+    if (s.sort_at == SORT_AFTER_SCORE) SBRCHK(queue_sort());
+    if (!s.ewma_fused) {
         ScopedTimer t(m, SBR_K_RECURRENT_BWD, m->ng && m->d > 128 ? 2 * (uint64_t)mb.Tm : 1);
         sbr::launch_recurrent_backward(m->mv, mv, bv, p->wb.v, mb.Tm, mb.R, mb.B, off_host, m->stream);
     }
-    if (!early_sort && place == SORT_OWN_STREAM) SBRCHK(launch_sort(sorter));
-    /* the dense-gradient GEMM (MFMA-bound, reads dZ / X / H only) goes to the side stream so that the
-     * HBM-bound sparse update that follows on the main stream overlaps it; joined in step_apply /
-     * step_dense before anything reads blk.dense */
-    if (side != m->stream) {
+    if (s.sort_at == SORT_AFTER_BPTT) SBRCHK(queue_sort());
+    if (s.overlap) { /* the side stream starts behind BPTT; joined by whoever reads blk.dense first (join_main DENSE) */
         HIPCHK(hipEventRecord(m->ev_fork, m->stream));
-        SBRCHK(stream_wait(m, side, m->ev_fork));
+        SBRCHK(stream_wait(m, s.dense_on, m->ev_fork));
     }
-    p->dw_deferred = m->step_fusion >= 1 && p->fuse_back && !overlap && p->ndev == 1 && sbr::small_back_shape_ok(m->mv, (int)mb.R) && (m->ng || mb.B <= 256);
-    if (p->dw_deferred) p->dense_unreduced_chunks = 0;
-    if (!p->dw_deferred) {
+    if (!s.dw_deferred) {
         /* one device: the ordered reduction of the chunk partials is left to the consumer — the optimiser step folds it into
          * the dense update's launch (sbr_fit_step_apply); the exchange halves and the debug fetch reduce on demand */
-        ScopedTimer t(m, SBR_K_DENSE_GRAD, 1, side);
-        p->dense_unreduced_chunks = sbr::launch_dense_gradient(m->mv, mv, bv, p->wb.v, mb.R, mb.B, side, /*defer_reduce=*/p->ndev == 1);
+        ScopedTimer t(m, SBR_K_DENSE_GRAD, 1, s.dense_on);
+        left.dense_unreduced_chunks = sbr::launch_dense_gradient(m->mv, mv, bv, p->wb.v, mb.R, mb.B, s.dense_on, /*defer_reduce=*/p->ndev == 1);
     }
-    if (side != m->stream) HIPCHK(hipEventRecord(m->ev_join, side));
-    p->dense_pending = side != m->stream;
-    if (!fuse_lag) {
-        hipStream_t ls = overlap ? m->sorter : m->stream;
-        if (ls != m->stream && !side_header) SBRCHK(stream_wait(m, ls, p->ev_seqsum)); /* (side_header: same stream as seq_loss) */
-        sbr::launch_lagged_chain(mv, p->lag_seqsum, mb.B, p->lag_state, ls);
-        if (ls != m->stream) {
-            HIPCHK(hipEventRecord(p->ev_lagged, ls));
-            p->lag_busy = true;
+    if (s.overlap) {
+        HIPCHK(hipEventRecord(m->ev_join, s.dense_on));
+        left.owed |= DENSE;
+    }
+    if (!s.fuse_lag) {
+        if (s.overlap && !s.side_header) SBRCHK(stream_wait(m, s.sort_on, p->ev_seqsum)); /* (side_header: same stream as seq_loss) */
+        sbr::launch_lagged_chain(mv, p->lag_seqsum, mb.B, p->lag_state, s.sort_on);
+        if (s.overlap) {
+            HIPCHK(hipEventRecord(p->ev_lagged, s.sort_on));
+            left.owed |= LAG_STATE;
         }
     }
     p->last_R = mb.R;
-    p->last_block = block;
+    p->last_block = p->block;
     HIPCHK(hipGetLastError());
     return SBR_OK;
 }
+
+sbr_status sbr_fit_step_local(sbr_fit_plan* p, uint64_t minibatch) { return p ? step_local(p, minibatch, false) : SBR_ERR_INVALID_ARGUMENT; }
 
 /* single device: optimiser step straight from the local block */
 sbr_status sbr_fit_step_apply(sbr_fit_plan* p, uint64_t minibatch) {
@@ -1854,54 +1871,44 @@ sbr_status sbr_fit_step_apply(sbr_fit_plan* p, uint64_t minibatch) {
     const uint8_t* all = p->block;
     SBRCHK(stream_head(m, m->stream));
     begin_optimizer_step(m);
-    if (!p->header_accumulated) sbr::launch_accumulate_loss(all, p->block_bytes, 1, p->loss_acc, p->ex_acc, m->stream);
-    p->header_accumulated = false;
-    if (p->dw_deferred) { /* small LSTM step: dense gradient + dense update + sparse update in one launch */
-        p->dw_deferred = false;
+    const StepSchedule s = p->left.form;
+    const sbr::BlockView bv = block_view(m, p->block, p->rmax);
+    const uint32_t R = p->ep[p->cur].rows_of_dev[minibatch];
+    if (!s.header_accumulates) sbr::launch_accumulate_loss(all, p->block_bytes, 1, p->loss_acc, p->ex_acc, m->stream);
+    if (s.dw_deferred) { /* small LSTM step: dense gradient + dense update + sparse update in one launch */
         ScopedTimer t(m, SBR_K_SPARSE_UPDATE, 1);
-        if (p->sort_off_stream) SBRCHK(stream_wait(m, m->stream, m->ev_sorted, &t));
-        sbr::launch_small_back(m->mv, mb_view(p, minibatch), block_view(m, p->block, p->rmax), p->wb.v, p->ep[p->cur].rows_of_dev[minibatch],
-                               p->keys_sorted, p->seg, m->stream);
-        HIPCHK(hipGetLastError());
-        return SBR_OK;
-    }
-    {
-        ScopedTimer t(m, SBR_K_SPARSE_UPDATE, 1);
-        if (p->sort_off_stream) SBRCHK(stream_wait(m, m->stream, m->ev_sorted, &t));
-        sbr::SegScratch sc = p->seg;
-        sc.prelisted = p->hot_prelisted ? 1u : 0u;
-        const sbr::BlockView bv = block_view(m, p->block, p->rmax);
-        sbr::launch_seg_apply(m->mv, bv, p->ep[p->cur].rows_of_dev[minibatch], p->keys_sorted, sc, m->stream);
-        if (p->hot_prelisted) { /* the listed hot rows: chunk partials + ordered finish on the ordering's stream (behind the list, and
-                                 * behind BPTT: ev_fork), beside the short segments' pass — disjoint table rows */
-            p->hot_prelisted = false;
-            SBRCHK(stream_wait(m, m->sorter, m->ev_fork, &t));
-            sbr::launch_seg_hot_apply(m->mv, bv, p->keys_sorted, sc, m->sorter);
-            HIPCHK(hipEventRecord(p->ev_hot, m->sorter));
-            SBRCHK(stream_wait(m, m->stream, p->ev_hot, &t));
+        SBRCHK(join_main(p, KEYS, &t));
+        sbr::launch_small_back(m->mv, mb_view(p, minibatch), bv, p->wb.v, R, p->keys_sorted, p->seg, m->stream);
+    } else {
+        {
+            ScopedTimer t(m, SBR_K_SPARSE_UPDATE, 1);
+            SBRCHK(join_main(p, KEYS, &t));
+            sbr::SegScratch sc = p->seg;
+            sc.prelisted = s.hot_prelist ? 1u : 0u;
+            sbr::launch_seg_apply(m->mv, bv, R, p->keys_sorted, sc, m->stream);
+            if (s.hot_prelist) { /* the listed hot rows: chunk partials + ordered finish on the ordering's stream (behind the list, and
+                                  * behind BPTT: ev_fork), beside the short segments' pass — disjoint table rows */
+                SBRCHK(stream_wait(m, m->sorter, m->ev_fork, &t));
+                sbr::launch_seg_hot_apply(m->mv, bv, p->keys_sorted, sc, m->sorter);
+                HIPCHK(hipEventRecord(p->ev_hot, m->sorter));
+                p->left.owed |= TABLE;
+                SBRCHK(join_main(p, TABLE, &t));
+            }
         }
-    }
-    SBRCHK(join_dense(p));
-    {
+        SBRCHK(join_main(p, DENSE));
         ScopedTimer t(m, SBR_K_DENSE_UPDATE, 1);
-        if (p->dense_unreduced_chunks > 0) { /* ordered reduction of the chunk partials + dense update in ONE launch */
-            sbr::launch_dense_reduce_apply(m->mv, p->wb.v, p->dense_unreduced_chunks, block_view(m, p->block, p->rmax), m->stream);
-            p->dense_unreduced_chunks = 0;
-        } else {
-            sbr::launch_dense_apply(m->mv, all, p->block_bytes, dense_offset_bytes(m, p->rmax), 1, m->stream);
-        }
+        if (p->left.dense_unreduced_chunks > 0) /* ordered reduction of the chunk partials + dense update in ONE launch */
+            sbr::launch_dense_reduce_apply(m->mv, p->wb.v, p->left.dense_unreduced_chunks, bv, m->stream);
+        else sbr::launch_dense_apply(m->mv, all, p->block_bytes, dense_offset_bytes(m, p->rmax), 1, m->stream);
     }
+    step_consumed(p);
     HIPCHK(hipGetLastError());
     return SBR_OK;
 }
 
 sbr_status sbr_fit_step(sbr_fit_plan* p, uint64_t minibatch) {
-    if (!p) return SBR_ERR_INVALID_ARGUMENT;
-    if (p->ndev != 1) return SBR_ERR_INVALID_ARGUMENT; /* multi-device: the owner-reduce halves below, driven by the host */
-    p->fuse_back = true; /* nobody looks at the block between the two halves */
-    const sbr_status st = sbr_fit_step_local(p, minibatch);
-    p->fuse_back = false;
-    SBRCHK(st);
+    if (!p || p->ndev != 1) return SBR_ERR_INVALID_ARGUMENT; /* multi-device: the owner-reduce halves below, driven by the host */
+    SBRCHK(step_local(p, minibatch, /*fuse_back=*/true));
     return sbr_fit_step_apply(p, minibatch);
 }
 
@@ -1946,18 +1953,12 @@ sbr_status sbr_fit_steps(sbr_fit_plan* p, uint64_t first, uint64_t count) {
             run_max = std::max(run_max, ep.desc_host[e].rows);
             ++e;
         }
-        if (p->lag_busy) { /* an earlier step's chain on the ordering's stream still owns lag_state */
-            SBRCHK(stream_wait(m, m->stream, p->ev_lagged));
-            p->lag_busy = false;
-        }
-        if (p->sorted_event_live) SBRCHK(stream_wait(m, m->stream, m->ev_sorted)); /* (a larger step before: its ordering owned the keys) */
-        SBRCHK(join_dense(p));
+        SBRCHK(join_main(p, KEYS | HEADER | DENSE | LAG_STATE)); /* the run writes them all (a larger step before may still own them) */
         SBRCHK(stream_head(m, m->stream));
         if (ewma_runs) sbr::launch_epoch_steps(m->mv, ev, bv, p->wb.v, epoch_key, tail, (int)b, (int)e, p->T - 1, p->phase_clocks, m->stream);
         else sbr::launch_lstm_steps(m->mv, ev, bv, p->wb.v, epoch_key, tail, (int)b, (int)e, p->T - 1, (int)run_max, p->phase_clocks, m->stream);
         m->opt_steps += e - b; /* Adagrad: no per-step host-side corrections */
-        p->hot_prelisted = p->sort_off_stream = p->dw_deferred = p->header_accumulated = false;
-        p->dense_unreduced_chunks = 0;
+        step_consumed(p);
         p->last_R = ep.mbs[e - 1].R;
         p->last_block = p->block;
         b = e;
@@ -1983,9 +1984,8 @@ sbr_status sbr_fit_step_apply_blocks_in_order(sbr_fit_plan* p, uint64_t minibatc
     sbr_model* m = p->m;
     SBRCHK(ensure_device(m));
     const uint8_t* all = reinterpret_cast<const uint8_t*>(device_blocks);
-    SBRCHK(join_dense(p));
+    SBRCHK(join_main(p, DENSE));
     sbr::launch_accumulate_loss(all, p->block_bytes, p->ndev, p->loss_acc, p->ex_acc, m->stream);
-    p->header_accumulated = false;
     for (int q = 0; q < p->ndev; ++q) {
         const uint32_t R = p->ep[p->cur].rows_of_dev[minibatch * p->ndev + q];
         uint8_t* base = const_cast<uint8_t*>(all) + (size_t)q * p->block_bytes;
@@ -1997,7 +1997,7 @@ sbr_status sbr_fit_step_apply_blocks_in_order(sbr_fit_plan* p, uint64_t minibatc
         sbr::launch_seg_apply(m->mv, bv, R, p->keys_sorted, sc, m->stream);
         sbr::launch_dense_apply(m->mv, base, p->block_bytes, dense_offset_bytes(m, p->rmax), 1, m->stream);
     }
-    p->sort_off_stream = false;
+    step_consumed(p);
     HIPCHK(hipGetLastError());
     return SBR_OK;
 }
@@ -2051,7 +2051,7 @@ sbr_status sbr_fit_step_scatter(sbr_fit_plan* p, uint64_t minibatch, void* devic
     const uint32_t R = p->ep[p->cur].rows_of_dev[minibatch * p->ndev + p->rank];
     {
         ScopedTimer t(m, SBR_K_SPARSE_UPDATE, 1);
-        if (p->sorted_event_live) SBRCHK(stream_wait(m, m->stream, m->ev_sorted, &t));
+        SBRCHK(join_main(p, KEYS, &t));
         sbr::launch_seg_scatter(m->mv, bv, R, p->ndev, slice_rows(p), device_send, p->keys_sorted, p->seg, m->stream);
     }
     HIPCHK(hipGetLastError());
@@ -2066,9 +2066,7 @@ sbr_status sbr_fit_step_dense(sbr_fit_plan* p, void* device_dense_out) {
     SBRCHK(ensure_device(m));
     const sbr::BlockView bv = block_view(m, p->block, p->rmax);
     SBRCHK(ensure_dense_reduced(p));
-    /* a WARP step with the ordering on its own stream writes the block header THERE (side_header in sbr_fit_step_local): join
-     * it here rather than rely on the caller having run sbr_fit_step_scatter first */
-    if (p->sorted_event_live && p->sort_off_stream) SBRCHK(stream_wait(m, m->stream, m->ev_sorted));
+    SBRCHK(join_main(p, HEADER)); /* (side_header: written on the sorter; not left to the caller having run sbr_fit_step_scatter first) */
     HIPCHK(hipMemcpyAsync(device_dense_out, bv.header, 32, hipMemcpyDeviceToDevice, m->stream));
     HIPCHK(hipMemcpyAsync(reinterpret_cast<uint8_t*>(device_dense_out) + 32, bv.dense, dense_count(m) * 4,
                           hipMemcpyDeviceToDevice, m->stream));
@@ -2116,9 +2114,8 @@ static sbr_status apply_dense_blocks(sbr_fit_plan* p, const void* device_dense_a
     const uint8_t* dall = reinterpret_cast<const uint8_t*>(device_dense_all);
     if (begins_step) begin_optimizer_step(m);
     /* one device driven through the exchange halves (bench.py --force-exchange): step_local's header launch has already added
-     * this step to the plan's loss accumulators */
-    if (!(p->ndev == 1 && p->header_accumulated)) sbr::launch_accumulate_loss(dall, db, p->ndev, p->loss_acc, p->ex_acc, m->stream);
-    p->header_accumulated = false;
+     * this step to the plan's loss accumulators.  (The form stays: under the staleness-one pipeline it is the NEXT step's already.) */
+    if (!p->left.form.header_accumulates) sbr::launch_accumulate_loss(dall, db, p->ndev, p->loss_acc, p->ex_acc, m->stream);
     {
         ScopedTimer t(m, SBR_K_DENSE_UPDATE, 1);
         sbr::launch_dense_apply(m->mv, dall, db, 32, p->ndev, m->stream);
@@ -2275,7 +2272,7 @@ static sbr_status partition_reduce_own(sbr_fit_plan* p, uint64_t minibatch) {
     SBRCHK(partition_buffers(p));
     const sbr::BlockView bv = block_view(m, p->block, p->rmax);
     const uint32_t R = p->ep[p->cur].rows_of_dev[minibatch * p->ndev + p->rank];
-    if (p->sorted_event_live) SBRCHK(stream_wait(m, m->stream, m->ev_sorted));
+    SBRCHK(join_main(p, KEYS));
     {
         ScopedTimer t(m, SBR_K_SPARSE_UPDATE, 1);
         sbr::launch_seg_list(m->mv, bv, R, p->ndev, slice_rows(p), p->keys_sorted, p->glist, p->gblist, p->gfl, p->bounds_dev, p->seg,
@@ -3442,7 +3439,7 @@ sbr_status sbr_fit_debug_fetch(sbr_fit_plan* p, int32_t which, void* host_out, u
     sbr_model* m = p->m;
     SBRCHK(ensure_device(m));
     if (which == SBR_DBG_DENSE_GRAD) SBRCHK(ensure_dense_reduced(p));
-    else SBRCHK(join_dense(p));
+    else SBRCHK(join_main(p, DENSE));
     HIPCHK(hipStreamSynchronize(m->stream));
     const sbr::BlockView bv = block_view(m, const_cast<void*>(p->last_block), p->rmax);
     const uint64_t R = (uint64_t)p->last_R, d = (uint64_t)m->d;

@@ -5,6 +5,10 @@ sbr_fit_step_apply): 160 sequences per step, all of length 12 -> 1 760 rows per 
 5 280 sparse-update keys (the single-launch ordering and the hot-row pre-list end at 4 096); 300 items drawn Zipf(1), so that a
 table row collects more than SBR_SEG_CHUNK = 256 entries in a step (check_shape asserts all of this from the oracle's indices);
 three epochs of two steps, so that steps follow steps across an epoch switch and both epoch buffers are used again.
+
+The MIXED data set adds a third, short step to every epoch (40 sequences -> 440 rows, 1 320 keys): everything on the main stream,
+single-launch ordering.  What a step leaves for the next one (which events the main stream still has to join) then crosses a change
+of form in both directions, the second one across an epoch switch (check_mixed_shape).
 """
 from __future__ import annotations
 
@@ -20,11 +24,31 @@ from sbr_rs_amd._abi import Debug, ModelKind, Param
 
 ITEMS, T, B, STEPS_PER_EPOCH, EPOCHS = 300, 12, 160, 2, 3
 ROWS_PER_STEP = B * (T - 1)
-OVERLAP_ABOVE_ROWS = 1365      # sbr_fit_step_local: small_rows
+OVERLAP_ABOVE_ROWS = 1365      # step_schedule: small_rows
 SINGLE_LAUNCH_SORT_KEYS = 4096
 SEG_CHUNK = 256                # SBR_SEG_CHUNK
 TOP_K = 10
 EVAL_USERS = 6
+
+
+@dataclass(frozen=True)
+class Data:
+    name: str
+    users: int     # histories per device
+    rows: tuple    # rows of the steps of every epoch
+
+    @property
+    def steps(self):
+        return EPOCHS * len(self.rows)
+
+    @property
+    def overlapped_steps(self):   # the steps that queue anything on the side and sorter streams
+        return EPOCHS * sum(r > OVERLAP_ABOVE_ROWS for r in self.rows)
+
+
+UNIFORM = Data("uniform", B * STEPS_PER_EPOCH, (ROWS_PER_STEP,) * STEPS_PER_EPOCH)
+MIXED = Data("mixed", 360, (ROWS_PER_STEP, ROWS_PER_STEP, 40 * (T - 1)))   # steps of 160, 160 and 40 sequences
+MIXED_CASES = ["normal-warp-32", "coupled-hinge-16", "ewma-bpr-32"]
 
 
 @dataclass(frozen=True)
@@ -45,7 +69,7 @@ class Case:
                        opt=self.opt, par=par)
 
 
-# every branch of sbr_fit_step_local's schedule
+# every branch of step_schedule (sbr_engine.hip)
 CASES = [
     Case("normal-warp-32", ModelKind.LSTM_NORMAL, LOSS_WARP, 32),        # side_header, the ordering behind the score kernel
     Case("coupled-hinge-16", ModelKind.LSTM_COUPLED, LOSS_HINGE, 16),    # early ordering, from the start of the step
@@ -68,10 +92,14 @@ def params_of(case):
     return base + dense + moments
 
 
+def train_data(world=1, data=UNIFORM):
+    return _train_data(world, data)   # (one cache entry however the defaults are spelled)
+
+
 @functools.lru_cache(maxsize=None)
-def train_data(world=1):
-    """world x 320 histories of exactly T items, Zipf(1) over 300 items: one sequence of T - 1 rows each."""
-    return synthetic_interactions(world * B * STEPS_PER_EPOCH, ITEMS, T, seed=41, min_len=T, zipf=True)
+def _train_data(world, data):
+    """world x 320 (MIXED: 360) histories of exactly T items, Zipf(1) over 300 items: one sequence of T - 1 rows each."""
+    return synthetic_interactions(world * data.users, ITEMS, T, seed=41, min_len=T, zipf=True)
 
 
 @functools.lru_cache(maxsize=None)
@@ -99,6 +127,7 @@ class Expect:
     rec_scores: np.ndarray
     hidden: list = field(default_factory=list)   # per step, in order (one device only)
     dense: list = field(default_factory=list)
+    rows: list = field(default_factory=list)     # the oracle's row count of every step
     hottest_row_entries: int = 0                 # of the first step, from its indices
 
 
@@ -111,23 +140,28 @@ def _evaluation(o):
     return mrr, ranks, pred, ri, rs
 
 
+def oracle_single(name, data=UNIFORM) -> Expect:
+    return _oracle_single(name, data)
+
+
 @functools.lru_cache(maxsize=None)
-def oracle_single(name) -> Expect:
+def _oracle_single(name, data) -> Expect:
     """The oracle's run of the case, step by step (the hidden states and the dense gradient of every step are kept: the engine's
-    debug fetch between the two halves of a step is compared with them).  Computed once per case and process."""
+    debug fetch between the two halves of a step is compared with them).  Computed once per case, data set and process."""
     from oracle.oracle import OracleModel
 
     case = CASE_BY_NAME[name]
-    ptr, it = train_data()
+    ptr, it = train_data(1, data)
     o = OracleModel(case.hp())
     po = o.fit_begin(ptr, it)
-    hidden, dense, hottest = [], [], 0
+    hidden, dense, rows, hottest = [], [], [], 0
     for e in range(EPOCHS):
         nmb = po.epoch_prepare()
-        assert nmb == STEPS_PER_EPOCH
+        assert nmb == len(data.rows)
         for mb in range(nmb):
             R = po.minibatch_rows(mb)
-            assert R == ROWS_PER_STEP
+            assert R == data.rows[mb]
+            rows.append(R)
             po.step_local(mb)
             hidden.append(po.debug_fetch(Debug.HIDDEN, R))
             dense.append(po.debug_fetch(Debug.DENSE_GRAD, R))
@@ -138,19 +172,23 @@ def oracle_single(name) -> Expect:
     lagged = po.end_lagged()
     loss = po.end()[0]
     po.close()
-    ex = Expect({p: o.get_param(p) for p in params_of(case)}, loss, lagged, *_evaluation(o), hidden=hidden, dense=dense,
+    ex = Expect({p: o.get_param(p) for p in params_of(case)}, loss, lagged, *_evaluation(o), hidden=hidden, dense=dense, rows=rows,
                 hottest_row_entries=hottest)
     o.close()
     return ex
 
 
+def oracle_world(name, world, par, data=UNIFORM) -> Expect:
+    return _oracle_world(name, world, par, data)
+
+
 @functools.lru_cache(maxsize=None)
-def oracle_world(name, world, par) -> Expect:
+def _oracle_world(name, world, par, data) -> Expect:
     """The oracle's whole fit with num_devices = world (every device takes B sequences of a step)."""
     from oracle.oracle import OracleModel
 
     case = CASE_BY_NAME[name]
-    ptr, it = train_data(world)
+    ptr, it = train_data(world, data)
     o = OracleModel(case.hp(world=world, par=par))
     loss = o.fit(ptr, it)
     ex = Expect({p: o.get_param(p) for p in params_of(case)}, loss, o.last_fit_lagged_loss(), *_evaluation(o))
@@ -165,6 +203,16 @@ def check_shape(name):
     assert 3 * ROWS_PER_STEP > SINGLE_LAUNCH_SORT_KEYS, "the ordering is the single-launch form; no hot-row pre-list"
     assert ex.hottest_row_entries > SEG_CHUNK, f"no table row with more than {SEG_CHUNK} entries ({ex.hottest_row_entries})"
     assert len(ex.hidden) == EPOCHS * STEPS_PER_EPOCH
+
+
+def check_mixed_shape(name):
+    """Every epoch of the MIXED data is two steps of the whole overlapped schedule and one that stays on the main stream with the
+    single-launch ordering, by the oracle's row counts: both changes of form occur, the second across an epoch switch."""
+    rows = oracle_single(name, MIXED).rows
+    assert rows == [1760, 1760, 440] * EPOCHS
+    large, small = rows[0], rows[2]
+    assert large > OVERLAP_ABOVE_ROWS and 3 * large > SINGLE_LAUNCH_SORT_KEYS, "the first two steps do not engage the side streams"
+    assert small <= OVERLAP_ABOVE_ROWS and 3 * small <= SINGLE_LAUNCH_SORT_KEYS, "the third step is not the everything-on-main form"
 
 
 # ---- one sequence per step (the one-launch runs of sbr_fit_steps, which timing switches off) ----

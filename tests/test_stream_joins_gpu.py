@@ -15,7 +15,8 @@ compared with the same expectation, which the default run (no delay, no switch) 
 bits is equal to the default run's bits.
 
 The shape (tests/stream_join_cases.py) is the smallest at which the whole schedule engages; test_shape_engages_the_whole_schedule
-asserts that from the indices.
+asserts that from the indices.  The MIXED data set ends every epoch with a step that stays on the main stream, so that what one step
+leaves for the next (the events the main stream has not joined) crosses a change of form in both directions.
 
 Limits.  The group cases run world 2 on ONE GPU: two models' eight or more streams over the process's four hardware queues may
 still share a queue, and a queue serialises what it carries whatever the events say, so a pass there bounds less than the
@@ -94,23 +95,25 @@ def check_model(model, case, ex, loss, lagged, what):
     assert_same_bits(np.array([lagged], np.float32), np.array([ex.lagged], np.float32), f"{what}: lagged loss figure")
 
 
-def check_counters(counts, delayed, what):
-    """The hook acted: at least one delay per step on every delayed role (the copier works once per epoch), none elsewhere."""
+def check_counters(counts, delayed, what, data=S.UNIFORM):
+    """The hook acted: at least one delay per step on every delayed role (the copier works once per epoch; a step that stays on
+    the main stream queues nothing on side and sorter), none elsewhere."""
     for role in STREAM_ROLES:
         if role in delayed:
-            least = S.EPOCHS if role == "copier" else STEPS
+            least = S.EPOCHS if role == "copier" else data.overlapped_steps if role in ("side", "sorter") else data.steps
             assert counts[role] >= least, f"{what}: {role} was delayed {counts[role]} times, expected at least {least}"
         else:
             assert counts[role] == 0, f"{what}: {role} was delayed though not named"
 
 
-def run_single(name, drive, setup=None, before_read=None, timing=None):
-    """One model through three epochs of two steps, `drive` = "step" (sbr_fit_step), "halves" (step_local | debug fetch of the
-    dense gradient and the hidden states | step_apply) or "fit"; then the evaluation calls and every parameter against the oracle.
+def run_single(name, drive, setup=None, before_read=None, timing=None, data=S.UNIFORM):
+    """One model through the three epochs of `data`, `drive` = "step" (sbr_fit_step), "halves" (step_local | debug fetch of the
+    dense gradient and the hidden states | step_apply), "fit" or "step+steps" (sbr_fit_step for the steps that engage the side
+    streams, sbr_fit_steps for the others); then the evaluation calls and every parameter against the oracle.
     timing: the families expected to report launches (the steps' timing is read before the evaluation calls)."""
-    case, ex = S.CASE_BY_NAME[name], S.oracle_single(name)
-    ptr, it = S.train_data()
-    what = f"{name} via {drive} [{os.environ.get(VAR, 'no delay')}]"
+    case, ex = S.CASE_BY_NAME[name], S.oracle_single(name, data)
+    ptr, it = S.train_data(1, data)
+    what = f"{name} on {data.name} via {drive} [{os.environ.get(VAR, 'no delay')}]"
     m = Model(case.hp())
     if setup:
         setup(m)
@@ -124,16 +127,18 @@ def run_single(name, drive, setup=None, before_read=None, timing=None):
             k = 0
             for e in range(S.EPOCHS):
                 nmb = plan.epoch_prepare()
-                assert nmb == S.STEPS_PER_EPOCH
+                assert nmb == len(data.rows)
                 if e + 1 < S.EPOCHS:
                     plan.epoch_prefetch()
                 for mb in range(nmb):
-                    if drive == "step":
+                    if drive == "step" or (drive == "step+steps" and ex.rows[k] > S.OVERLAP_ABOVE_ROWS):
                         plan.step(mb)
+                    elif drive == "step+steps":
+                        plan.steps(mb, 1)
                     else:
                         plan.step_local(mb)
-                        assert_same_bits(plan.debug_fetch(Debug.DENSE_GRAD, S.ROWS_PER_STEP), ex.dense[k], f"{what}: step {k} dense gradient")
-                        assert_same_bits(plan.debug_fetch(Debug.HIDDEN, S.ROWS_PER_STEP), ex.hidden[k], f"{what}: step {k} hidden states")
+                        assert_same_bits(plan.debug_fetch(Debug.DENSE_GRAD, ex.rows[k]), ex.dense[k], f"{what}: step {k} dense gradient")
+                        assert_same_bits(plan.debug_fetch(Debug.HIDDEN, ex.rows[k]), ex.hidden[k], f"{what}: step {k} hidden states")
                         plan.step_apply(mb)
                     k += 1
             if timing is not None:
@@ -211,6 +216,38 @@ def test_late_stream_changes_no_bit(monkeypatch, name, drive, roles):
     check_counters(counts, roles, f"{name} {drive} {roles}")
 
 
+# ------------------------------------------------- one device, steps of two forms ----------------------------------------------
+# What a step leaves for the next one — which events the main stream has not joined — crosses a change of the step's form here:
+# every epoch of the MIXED data is two steps on all the streams and one that stays on the main stream (S.check_mixed_shape).
+MIXED_ROLE_SETS = [(), ("main",), ("sorter",), ("side", "sorter", "copier")]
+
+
+@pytest.mark.parametrize("name", S.MIXED_CASES)
+def test_mixed_epoch_changes_the_form_of_the_step(name):
+    S.check_mixed_shape(name)
+
+
+@pytest.mark.parametrize("roles", MIXED_ROLE_SETS, ids=["+".join(r) or "undelayed" for r in MIXED_ROLE_SETS])
+@pytest.mark.parametrize("drive", ["step", "halves", "fit"])
+@pytest.mark.parametrize("name", S.MIXED_CASES)
+def test_mixed_epoch_late_stream_changes_no_bit(monkeypatch, name, drive, roles):
+    if roles:
+        monkeypatch.setenv(VAR, delay_spec(roles))
+    counts = run_single(name, drive, data=S.MIXED)
+    check_counters(counts, roles, f"{name} mixed {drive} {roles}", S.MIXED)
+
+
+@pytest.mark.parametrize("role", ["sorter", "main"])
+@pytest.mark.parametrize("name", S.MIXED_CASES)
+def test_steps_behind_a_large_step_late_stream_changes_no_bit(monkeypatch, name, role):
+    """sbr_fit_steps on a plan whose last step ran on all the streams: it joins whatever that step left.  (The one-launch runs of
+    sbr_fit_steps need a plan of one sequence per step, whose steps never engage the side streams: the short step goes through
+    sbr_fit_steps' step-by-step form.)"""
+    monkeypatch.setenv(VAR, delay_spec((role,)))
+    counts = run_single(name, "step+steps", data=S.MIXED)
+    check_counters(counts, (role,), f"{name} mixed step+steps {role}", S.MIXED)
+
+
 # ---------------------------------------------------------------- world 2 ------------------------------------------------------
 # form: (case, partitioned table, gradient exchange, parallelism)
 FORMS = {
@@ -225,11 +262,11 @@ GROUP_ROLES = ["main@0", "main@1", "xs@0", "xs@1", "sorter@1"]
 GROUP_DELAYS = [(form, role) for form in FORMS for role in GROUP_ROLES if form == "pipeline" or not role.startswith("xs")]
 
 
-def run_group(form, threads):
+def run_group(form, threads, data=S.UNIFORM):
     name, partition, gradient, par = FORMS[form]
-    case, ex = S.CASE_BY_NAME[name], S.oracle_world(name, WORLD, par)
-    ptr, it = S.train_data(WORLD)
-    what = f"{form} ({name}), host threads {threads} [{os.environ.get(VAR, 'no delay')}]"
+    case, ex = S.CASE_BY_NAME[name], S.oracle_world(name, WORLD, par, data)
+    ptr, it = S.train_data(WORLD, data)
+    what = f"{form} ({name}) on {data.name}, host threads {threads} [{os.environ.get(VAR, 'no delay')}]"
     models = group_create(case.hp(world=WORLD, par=par), WORLD, partition_item_table=partition)
     gp = GroupPlan(models, ptr, it, host_threads=threads)
     try:
@@ -237,8 +274,9 @@ def run_group(form, threads):
             gp.set_exchange(gradient)
         for e in range(S.EPOCHS):
             nmb = gp.epoch_prepare(prefetch_next=e + 1 < S.EPOCHS)
-            assert nmb == S.STEPS_PER_EPOCH
+            assert nmb == len(data.rows)
             for mb in range(nmb):
+                assert gp.member(0).minibatch_rows(mb) == data.rows[mb]
                 gp.step(mb)
         for q in range(WORLD):
             check_evaluation(models[q], ex, f"{what} replica {q}")
@@ -268,6 +306,16 @@ def test_group_late_stream_changes_no_bit(monkeypatch, form, role, threads):
     counts = run_group(form, threads)
     for q in range(WORLD):
         check_counters(counts[q], (r,) if q == int(dev) else (), f"{form} {role} replica {q}")
+
+
+@pytest.mark.parametrize("role", ["main@0", "sorter@1"])
+@pytest.mark.parametrize("form", ["gradient", "partitioned"])
+def test_group_mixed_epoch_late_stream_changes_no_bit(monkeypatch, form, role):
+    r, dev = role.split("@")
+    monkeypatch.setenv(VAR, f"{role}={DELAY_US}")
+    counts = run_group(form, False, S.MIXED)
+    for q in range(WORLD):
+        check_counters(counts[q], (r,) if q == int(dev) else (), f"{form} mixed {role} replica {q}", S.MIXED)
 
 
 # ---------------------------------------------------------------- switches -----------------------------------------------------
