@@ -516,6 +516,128 @@ inline std::vector<std::uint32_t> narrow(const std::vector<ItemId>& ids) {
     return out;
 }
 
+/// A session store on one model (sbr_sessions_*): `capacity` slots of recurrent state on the device — h, c of the LSTM, s of
+/// EWMA — each advanced by the items appended to it, one cell step per item, and read in place by `recommend` /
+/// `score_candidates`.  A slot's representation has the bits of `user_representation` of the items appended since its last reset
+/// (an empty slot: of the empty history) while they are at most max_sequence_length; beyond that a session keeps the recurrence
+/// over everything appended where the windowed call truncates.  After the model's parameters change (`fit`, a restored
+/// checkpoint) every call but `reset_all` throws EngineError(SBR_ERR_INVALID_ARGUMENT) until `reset_all` re-binds the store.
+/// Obtained from ImplicitSequenceModel::sessions; the model must outlive it.  Movable, not copyable.
+class Sessions {
+  public:
+    Sessions(sbr_model* model, std::size_t capacity, std::size_t embedding_dim) : dim_(embedding_dim) {
+        check(sbr_sessions_create(model, (std::uint64_t)capacity, &h_), "sbr_sessions_create");
+    }
+    Sessions(const Sessions&) = delete;
+    Sessions& operator=(const Sessions&) = delete;
+    Sessions(Sessions&& o) noexcept : h_(o.h_), dim_(o.dim_) { o.h_ = nullptr; }
+    Sessions& operator=(Sessions&& o) noexcept {
+        if (this != &o) { release(); h_ = o.h_; dim_ = o.dim_; o.h_ = nullptr; }
+        return *this;
+    }
+    ~Sessions() { release(); }
+
+    std::size_t capacity() const {
+        std::uint64_t c = 0;
+        check(sbr_sessions_capacity(h_, &c), "sbr_sessions_capacity");
+        return (std::size_t)c;
+    }
+    /// Appends item_ids[item_ptr[i] .. item_ptr[i + 1]), in order, to slot slots[i].
+    void append(const std::vector<std::uint32_t>& slots, const std::vector<std::uint64_t>& item_ptr, const std::vector<std::uint32_t>& item_ids) {
+        if (item_ptr.size() != slots.size() + 1 || item_ptr.back() > item_ids.size())
+            throw EngineError(SBR_ERR_INVALID_ARGUMENT, "Sessions::append: one item range per slot");
+        check(sbr_sessions_append(h_, slots.data(), (std::uint64_t)slots.size(), item_ptr.data(), item_ids.data()), "sbr_sessions_append");
+    }
+    /// One item for each of `slots`.
+    void append(const std::vector<std::uint32_t>& slots, const std::vector<std::uint32_t>& one_item_each) {
+        std::vector<std::uint64_t> ptr(slots.size() + 1);
+        std::iota(ptr.begin(), ptr.end(), (std::uint64_t)0);
+        append(slots, ptr, one_item_each);
+    }
+    std::vector<std::uint64_t> lengths(const std::vector<std::uint32_t>& slots) const {
+        std::vector<std::uint64_t> out(slots.size());
+        check(sbr_sessions_lengths(h_, slots.data(), (std::uint64_t)slots.size(), out.data()), "sbr_sessions_lengths");
+        return out;
+    }
+    /// Row-major [slots.size()][embedding_dim].
+    std::vector<float> representations(const std::vector<std::uint32_t>& slots) const {
+        std::vector<float> out(slots.size() * dim_);
+        check(sbr_sessions_representations(h_, slots.data(), (std::uint64_t)slots.size(), out.data()), "sbr_sessions_representations");
+        return out;
+    }
+    void reset(const std::vector<std::uint32_t>& slots) { check(sbr_sessions_reset(h_, slots.data(), (std::uint64_t)slots.size()), "sbr_sessions_reset"); }
+    /// Every slot emptied and the store re-bound to the model's current parameters.
+    void reset_all() { check(sbr_sessions_reset_all(h_), "sbr_sessions_reset_all"); }
+    /// The k best items of the whole catalogue for each slot's state, read in place (sbr_sessions_recommend): ordered and padded as
+    /// ImplicitSequenceModel::recommend's rows.  The store keeps no item history: slot i's excluded items are
+    /// excl_items[excl_ptr[i] .. excl_ptr[i + 1]) (both empty: none).
+    Result<Recommendations, PredictionError> recommend(const std::vector<std::uint32_t>& slots, std::size_t k,
+                                                       const std::vector<std::uint64_t>& excl_ptr = {},
+                                                       const std::vector<std::uint32_t>& excl_items = {}) const {
+        if (k < 1 || k > SBR_RECOMMEND_MAX_K) throw EngineError(SBR_ERR_INVALID_ARGUMENT, "Sessions::recommend: k outside 1..SBR_RECOMMEND_MAX_K");
+        if (!excl_ptr.empty() && (excl_ptr.size() != slots.size() + 1 || excl_ptr.back() > excl_items.size()))
+            throw EngineError(SBR_ERR_INVALID_ARGUMENT, "Sessions::recommend: one exclusion range per slot");
+        Recommendations r;
+        r.num_users = slots.size();
+        r.k = k;
+        r.items.resize(r.num_users * k);
+        r.scores.resize(r.num_users * k);
+        const std::uint32_t none = 0;
+        const sbr_status st = sbr_sessions_recommend(h_, slots.data(), (std::uint64_t)slots.size(), (std::uint32_t)k,
+                                                     excl_ptr.empty() ? nullptr : excl_ptr.data(),
+                                                     excl_ptr.empty() ? nullptr : (excl_items.empty() ? &none : excl_items.data()), 0u,
+                                                     r.items.data(), r.scores.data());
+        if (st == SBR_ERR_INVALID_PREDICTION) return Result<Recommendations, PredictionError>::Err(PredictionError::InvalidPredictionValue);
+        check(st, "sbr_sessions_recommend");
+        return Result<Recommendations, PredictionError>::Ok(std::move(r));
+    }
+    /// One score per candidate, in candidate order, slot i's candidates cand_items[cand_ptr[i] .. cand_ptr[i + 1]) (sbr_sessions_score_candidates).
+    Result<std::vector<float>, PredictionError> score_candidates(const std::vector<std::uint32_t>& slots, const std::vector<std::uint64_t>& cand_ptr,
+                                                                 const std::vector<std::uint32_t>& cand_items) const {
+        using R = Result<std::vector<float>, PredictionError>;
+        if (cand_ptr.size() != slots.size() + 1 || cand_ptr.back() < cand_ptr.front() || cand_ptr.back() > cand_items.size())
+            throw EngineError(SBR_ERR_INVALID_ARGUMENT, "Sessions::score_candidates: one candidate range per slot");
+        std::vector<float> scores(cand_ptr.back() - cand_ptr.front());
+        const sbr_status st = sbr_sessions_score_candidates(h_, slots.data(), (std::uint64_t)slots.size(), cand_ptr.data(), cand_items.data(),
+                                                            scores.data());
+        if (st == SBR_ERR_INVALID_PREDICTION) return R::Err(PredictionError::InvalidPredictionValue);
+        check(st, "sbr_sessions_score_candidates");
+        return R::Ok(std::move(scores));
+    }
+    /// Checkpoint of the named slots (sbr_sessions_get_state): h and c row-major [slots.size()][embedding_dim] (c stays empty for
+    /// EWMA, `lstm` false), len per slot.
+    struct State {
+        std::vector<float> h, c;
+        std::vector<std::uint64_t> len;
+    };
+    State get_state(const std::vector<std::uint32_t>& slots, bool lstm) const {
+        State s;
+        s.h.resize(slots.size() * dim_);
+        if (lstm) s.c.resize(slots.size() * dim_);
+        s.len.resize(slots.size());
+        check(sbr_sessions_get_state(h_, slots.data(), (std::uint64_t)slots.size(), s.h.data(), lstm ? s.c.data() : nullptr, s.len.data()),
+              "sbr_sessions_get_state");
+        return s;
+    }
+    /// Restores a checkpoint into the named slots of this store (sbr_sessions_set_state); `state.c` empty for EWMA.
+    void set_state(const std::vector<std::uint32_t>& slots, const State& state) {
+        if (state.h.size() != slots.size() * dim_ || state.len.size() != slots.size() || (!state.c.empty() && state.c.size() != state.h.size()))
+            throw EngineError(SBR_ERR_INVALID_ARGUMENT, "Sessions::set_state: one state per slot");
+        check(sbr_sessions_set_state(h_, slots.data(), (std::uint64_t)slots.size(), state.h.data(), state.c.empty() ? nullptr : state.c.data(),
+                                     state.len.data()),
+              "sbr_sessions_set_state");
+    }
+    sbr_sessions* handle() const { return h_; }
+
+  private:
+    void release() {
+        if (h_) sbr_sessions_destroy(h_);
+        h_ = nullptr;
+    }
+    sbr_sessions* h_ = nullptr;
+    std::size_t dim_;
+};
+
 /// Owner of the device replicas behind one model object: `num_threads` replicas (≙ the worker
 /// threads of sequence_model.rs:90-102), replica r on HIP device r mod device_count
 /// (sbr_group_create).
@@ -723,6 +845,10 @@ class ImplicitSequenceModel : public OnlineRankingModel<ImplicitUser> {
         check(st, "sbr_rank_targets");
         return R::Ok(std::move(ranks));
     }
+
+    /// A session store of `capacity` slots on the primary replica: device-resident user states advanced one appended item at a
+    /// time (see Sessions).  Destroy it before this model.
+    Sessions sessions(std::size_t capacity) const { return Sessions(replicas_->primary(), capacity, replicas_->hparams().embedding_dim); }
 
     /// The engine handle (replica 0), for evaluation's fused path and for parameter access.
     sbr_model* handle() const { return replicas_->primary(); }
@@ -1008,7 +1134,9 @@ class Hyperparameters : public detail::HyperparametersBase<Hyperparameters> {
 };
 
 } // namespace ewma
+using Sessions = detail::Sessions;
 } // namespace models
+using Sessions = models::Sessions;
 
 // =============================================================================================
 // sbr::evaluation  (src/evaluation.rs)

@@ -495,6 +495,66 @@ sbr_status sbr_rank_targets_reps(sbr_model* m, const float* reps, uint64_t num_u
                                  const uint64_t* excl_ptr, const uint32_t* excl_items,
                                  const uint64_t* target_ptr, const uint32_t* target_items, uint32_t* out_ranks);
 
+/* SESSIONS — device-resident user states advanced one event at a time (no counterpart in the reference crate, whose
+ * user_representation walks the whole history on every call, sequence_model.rs:182-211).  A store belongs to one model and has
+ * `capacity` slots; a slot holds len, the number of items appended since its last reset, and the recurrent state after those items:
+ * h, c for the LSTM, s for EWMA (storage width; the columns past embedding_dim are zero, as in the model's own states).
+ *
+ * Appending item x to a slot is one step of the forward pass from the stored state: LSTM z = b + [E[x] ; h] W as a k-ascending fma
+ * chain seeded with the bias, then the cell, from h = c = 0 when len == 0; EWMA s = E[x] for the first item
+ * (ewma.rs:306) and s = fma(a, s, (1 - a) * E[x]), a = sigmoid(alpha), afterwards.  The representation of a slot is its h (s) when
+ * len >= 1, and sbr_user_representation of the empty history — one step of item 0 from the zero state, lstm.rs:262-264 — when
+ * len == 0; that step is not stored: the first real append still starts from zero.
+ *
+ * EXACT: a slot whose appended items are x_1 .. x_n, n <= max_sequence_length, however they were split across calls, has a
+ * representation with the BITS of sbr_user_representation(x_1 .. x_n), at every embedding_dim and for all three model kinds.
+ * BEYOND max_sequence_length a session does NOT truncate to the last max_sequence_length items as sbr_user_representation does
+ * (state_window): it holds the recurrence over everything appended, i.e. the bits of user_representation of a model with the same
+ * parameters and max_sequence_length >= n.  This is the one place sessions depart from the windowed call; a caller who wants the
+ * window resets the slot and appends the window.
+ *
+ * STALENESS: the model has a parameter generation, bumped by whatever can write parameters — a fit plan opening by any route
+ * (sbr_fit_begin, sbr_group_fit_begin, sbr_model_fit, sbr_model_fit_comm, sbr_group_fit) or closing, and sbr_model_set_param.  A store
+ * remembers the generation of its creation or last sbr_sessions_reset_all; while the model's differs, every store call except
+ * reset_all, capacity and destroy returns SBR_ERR_INVALID_ARGUMENT: no call mixes states of two parameter sets.  While a fit plan
+ * is open on the model (from sbr_fit_begin to sbr_fit_plan_destroy; sbr_model_fit and the group fits open and destroy theirs
+ * inside the call) its steps rewrite parameters, so every store call but capacity and destroy — sbr_sessions_reset_all included —
+ * returns SBR_ERR_INVALID_ARGUMENT until the plan is destroyed.
+ *
+ * Every call validates before it launches anything, and an error leaves every slot as it was.  SBR_ERR_INVALID_ARGUMENT: a slot
+ * >= capacity, the same slot twice in one call, decreasing pointers, an item id >= num_items, k outside sbr_recommend's range, flags
+ * other than 0.  Slots need not be sorted or contiguous; a slot listed with no items is left alone; slots a call does not name keep
+ * their bits.  A store works wherever sbr_user_representations works on its model, takes the model's mutex and runs on the model's
+ * stream; it is destroyed before its model.
+ *
+ *   sbr_sessions_create          capacity slots, all empty (1 <= capacity < 2^31 - 1); SBR_ERR_OUT_OF_MEMORY if the device cannot hold them
+ *   sbr_sessions_reset           the named slots: len = 0, zero state
+ *   sbr_sessions_reset_all       every slot, and the store re-bound to the model's current parameters
+ *   sbr_sessions_append          items item_ids[item_ptr[i] .. item_ptr[i + 1]) to slot slots[i], in order
+ *   sbr_sessions_lengths         out_lengths[i] = len of slots[i]
+ *   sbr_sessions_representations out_reps [n][embedding_dim], rows laid out as sbr_user_representations'
+ *   sbr_sessions_get_state / _set_state   checkpoint / restore: h, c [n][embedding_dim] (c NULL for EWMA, required for the LSTM), len
+ *                                [n]; a restored len of 0 is the empty slot (zero state, whatever h holds)
+ *   sbr_sessions_recommend / _score_candidates   sbr_recommend_reps / sbr_score_candidates_reps on sbr_sessions_representations of
+ *                                the same slots — results, padding, errors, non-finite handling, bit for bit — with the scan reading
+ *                                the store's rows in place.  The store keeps no item history: exclusions are the caller's lists.
+ * The other scans are reached through sbr_sessions_representations and the *_reps calls. */
+typedef struct sbr_sessions sbr_sessions;
+sbr_status sbr_sessions_create(sbr_model* m, uint64_t capacity, sbr_sessions** out);
+void sbr_sessions_destroy(sbr_sessions* st);
+sbr_status sbr_sessions_capacity(const sbr_sessions* st, uint64_t* out);
+sbr_status sbr_sessions_reset(sbr_sessions* st, const uint32_t* slots, uint64_t n);
+sbr_status sbr_sessions_reset_all(sbr_sessions* st);
+sbr_status sbr_sessions_append(sbr_sessions* st, const uint32_t* slots, uint64_t n, const uint64_t* item_ptr, const uint32_t* item_ids);
+sbr_status sbr_sessions_lengths(sbr_sessions* st, const uint32_t* slots, uint64_t n, uint64_t* out_lengths);
+sbr_status sbr_sessions_representations(sbr_sessions* st, const uint32_t* slots, uint64_t n, float* out_reps);
+sbr_status sbr_sessions_get_state(sbr_sessions* st, const uint32_t* slots, uint64_t n, float* out_h, float* out_c, uint64_t* out_len);
+sbr_status sbr_sessions_set_state(sbr_sessions* st, const uint32_t* slots, uint64_t n, const float* h, const float* c, const uint64_t* len);
+sbr_status sbr_sessions_recommend(sbr_sessions* st, const uint32_t* slots, uint64_t n, uint32_t k, const uint64_t* excl_ptr,
+                                  const uint32_t* excl_items, uint32_t flags, uint32_t* out_items, float* out_scores);
+sbr_status sbr_sessions_score_candidates(sbr_sessions* st, const uint32_t* slots, uint64_t n, const uint64_t* cand_ptr,
+                                         const uint32_t* cand_items, float* out_scores);
+
 /* ≙ the serde derives (lstm.rs:204,386; ewma.rs:208,401): element counts and raw access. */
 sbr_status sbr_model_param_count(const sbr_model* m, int32_t which, uint64_t* out_count);
 sbr_status sbr_model_get_param(sbr_model* m, int32_t which, float* host_out, uint64_t count);

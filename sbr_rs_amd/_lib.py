@@ -135,6 +135,17 @@ def load():
         "sbr_selftest_sort": [vp, C.c_uint64, C.c_uint32, vp, vp, vp],
         "sbr_test_delays_queued": [vp, u64p],
         "sbr_selftest_stream_delay": [C.c_uint32, C.c_int32, fp],
+        "sbr_sessions_create": [vp, C.c_uint64, C.POINTER(vp)],
+        "sbr_sessions_capacity": [vp, u64p],
+        "sbr_sessions_reset": [vp, vp, C.c_uint64],
+        "sbr_sessions_reset_all": [vp],
+        "sbr_sessions_append": [vp, vp, C.c_uint64, vp, vp],
+        "sbr_sessions_lengths": [vp, vp, C.c_uint64, vp],
+        "sbr_sessions_representations": [vp, vp, C.c_uint64, vp],
+        "sbr_sessions_get_state": [vp, vp, C.c_uint64, vp, vp, vp],
+        "sbr_sessions_set_state": [vp, vp, C.c_uint64, vp, vp, vp],
+        "sbr_sessions_recommend": [vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint32, vp, vp],
+        "sbr_sessions_score_candidates": [vp, vp, C.c_uint64, vp, vp, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -144,6 +155,8 @@ def load():
     L.sbr_model_destroy.restype = None
     L.sbr_fit_plan_destroy.argtypes = [vp]
     L.sbr_fit_plan_destroy.restype = None
+    L.sbr_sessions_destroy.argtypes = [vp]
+    L.sbr_sessions_destroy.restype = None
     L.sbr_comm_destroy.argtypes = [vp]
     L.sbr_comm_destroy.restype = None
     L.sbr_group_plan_destroy.argtypes = [vp]
@@ -181,4 +194,7 @@ DECLARED_SYMBOLS = [
     "sbr_recommend", "sbr_recommend_reps", "sbr_rank_targets", "sbr_rank_targets_reps", "sbr_similar_items",
     "sbr_user_representations", "sbr_score_candidates", "sbr_score_candidates_reps", "sbr_recommend_among", "sbr_recommend_among_reps",
     "sbr_test_delays_queued", "sbr_selftest_stream_delay",
+    "sbr_sessions_create", "sbr_sessions_destroy", "sbr_sessions_capacity", "sbr_sessions_reset", "sbr_sessions_reset_all",
+    "sbr_sessions_append", "sbr_sessions_lengths", "sbr_sessions_representations", "sbr_sessions_get_state", "sbr_sessions_set_state",
+    "sbr_sessions_recommend", "sbr_sessions_score_candidates",
 ]

@@ -17,7 +17,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libsbr_hip.so")
-SOURCES = ["sbr_kernels.hip", "sbr_steps.hip", "sbr_sort.hip", "sbr_wave.hip", "sbr_report.hip", "sbr_catalogue.hip", "sbr_engine.hip"]
+SOURCES = ["sbr_kernels.hip", "sbr_steps.hip", "sbr_sort.hip", "sbr_wave.hip", "sbr_report.hip", "sbr_catalogue.hip", "sbr_sessions.hip", "sbr_engine.hip"]
 HEADERS = ["sbr_kernels.h", "sbr_device.h", "sbr_wave_seq.h", "sbr_numerics.h", "sbr_approx.h", "sbr_ziggurat_tables.h", os.path.join("..", "..", "include", "sbr_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
          "-Wall", "-Wno-unused-function", "-Wno-unused-result", "-Wno-unused-value"] + os.environ.get("SBR_EXTRA_FLAGS", "").split()
@@ -108,6 +108,15 @@ def build_candidates_tests(force: bool = False, verbose: bool = True) -> str:
     return _build_cpp_program(CANDIDATES_SRC, CANDIDATES_BIN, force, verbose)
 
 
+SESSIONS_SRC = os.path.join(REPO, "tests", "cpp", "sessions_tests.cpp")
+SESSIONS_BIN = os.path.join(REPO, "tests", "cpp", "_build", "sessions_tests")
+
+
+def build_sessions_tests(force: bool = False, verbose: bool = True) -> str:
+    """g++ build of the C++ host layer's session-store test program."""
+    return _build_cpp_program(SESSIONS_SRC, SESSIONS_BIN, force, verbose)
+
+
 RANKING_SRC = os.path.join(REPO, "tests", "cpp", "ranking_tests.cpp")
 RANKING_BIN = os.path.join(REPO, "tests", "cpp", "_build", "ranking_tests")
 
@@ -124,3 +133,4 @@ if __name__ == "__main__":
     print(build_ranking_tests(force="--force" in sys.argv))
     print(build_similar_tests(force="--force" in sys.argv))
     print(build_candidates_tests(force="--force" in sys.argv))
+    print(build_sessions_tests(force="--force" in sys.argv))

@@ -437,6 +437,10 @@ struct sbr_model {
     bool partition_finalized = true;
     uint64_t global_epoch = 0;
     uint64_t opt_steps = 0; /* optimiser steps taken (Adam bias correction) */
+    uint64_t param_gen = 0; /* parameter generation: bumped by whatever can write parameters (a fit plan opening or closing,
+                             * sbr_model_set_param); a session store serves only the generation it was last bound to */
+    uint32_t open_plans = 0; /* fit plans open on this model: their steps write parameters, so no session store call (reset_all
+                              * included) is served until they are destroyed */
     float last_lagged_loss = 0.0f; /* what the reference's fit would have returned for the last sbr_model_fit / sbr_group_fit */
     bool opt_state_partial = false; /* owner-applied steps (sbr_fit_step_owner_update) have run since the item table's optimiser state was last
                                      * complete on this replica: only the rows this rank owns are current (sbr_model_table_slice /
@@ -916,7 +920,7 @@ sbr_status ensure_device(const sbr_model* m) {
 
 extern "C" {
 
-uint32_t sbr_abi_version(void) { return 10; }
+uint32_t sbr_abi_version(void) { return 11; }
 
 void sbr_release_cached_memory(void) { scratch_cache().trim(); }
 
@@ -1259,6 +1263,7 @@ sbr_status sbr_model_set_param(sbr_model* m, int32_t which, const float* host_in
     if (!p || n != count) return SBR_ERR_INVALID_ARGUMENT;
     SBRCHK(ensure_device(m));
     HIPCHK(hipStreamSynchronize(m->stream));
+    m->param_gen += 1;
     if (stored == n) {
         HIPCHK(hipMemcpy(p, host_in, n * 4, hipMemcpyHostToDevice));
     } else {
@@ -1387,6 +1392,7 @@ sbr_status sbr_fit_begin(sbr_model* m, const uint64_t* user_ptr, const uint32_t*
     if (part == 0) return SBR_ERR_INVALID_ARGUMENT; /* the reference panics here (chunks_mut(0)) */
     sbr_fit_plan* p = new (std::nothrow) sbr_fit_plan();
     if (!p) return SBR_ERR_OUT_OF_MEMORY;
+    m->param_gen += 1; /* every fit opens its plans here: session states of the old parameters go stale */
     p->m = m; p->ndev = ndev; p->rank = (int)m->hp.device_rank; p->T = (int)T;
     p->nseq_total = nseq; p->part_len = part;
     start.resize((size_t)ndev * part);
@@ -1406,6 +1412,7 @@ sbr_status sbr_fit_begin(sbr_model* m, const uint64_t* user_ptr, const uint32_t*
     p->bmax = m->hp.batch_sequences;
     p->rmax = p->bmax * (T - 1);
     if (3 * p->rmax >= (1ull << 32) || part * T >= (1ull << 32)) { delete p; return SBR_ERR_INVALID_ARGUMENT; }
+    m->open_plans += 1; /* until sbr_fit_plan_destroy, which every later exit goes through */
     sbr_status st = alloc_work(m, p->rmax, p->bmax, true, &p->wb);
     if (st == SBR_OK) { p->block_bytes = block_bytes_for(m, p->rmax); st = dmalloc(&p->block, p->block_bytes); }
     const uint64_t max_entries = 3 * p->rmax; /* only a device's own entries are ever sorted */
@@ -1468,6 +1475,8 @@ sbr_status sbr_fit_begin(sbr_model* m, const uint64_t* user_ptr, const uint32_t*
 void sbr_fit_plan_destroy(sbr_fit_plan* p) {
     if (!p) return;
     hipSetDevice(p->m->device);
+    p->m->param_gen += 1;
+    p->m->open_plans -= 1;
     if (p->pending) { p->worker.join(); p->pending = false; }
     hipStreamSynchronize(p->m->side);
     hipStreamSynchronize(p->m->sorter);
@@ -3607,8 +3616,9 @@ sbr_status check_csr(const sbr_model* m, const uint64_t* ptr, uint64_t n, const 
 }
 
 /* Where a call's user representations come from: the histories ptr / items (the recurrent forward runs), the rows `reps`
- * ([users, embedding_dim]) of the caller, or rows the device makes from the item table, user u's from item item_rows[u]
- * (similar_items); in the last two cases ptr / items are the exclusion lists (ptr null: none). */
+ * ([users, embedding_dim]) of the caller, rows the device makes from the item table, user u's from item item_rows[u]
+ * (similar_items), or rows that already lie on the device at the storage width, user u's row dev_row[u] of dev_rows (a session
+ * store: read in place); in the last three cases ptr / items are the exclusion lists (ptr null: none). */
 struct RepSource {
     const uint64_t* ptr;
     const uint32_t* items;
@@ -3616,7 +3626,9 @@ struct RepSource {
     uint64_t held_out;  /* histories: this many items at the end of each are not part of it (mrr_score: the test item) */
     bool lists;         /* whether the sorted, de-duplicated lists of ptr / items are wanted (with reps or item rows: always) */
     const uint32_t* item_rows = nullptr; /* non-null: the rows come from these item ids, on the device */
-    bool from_histories() const { return !reps && !item_rows; }
+    const float* dev_rows = nullptr;     /* non-null: device rows [.][storage width], read in place ... */
+    const int* dev_row = nullptr;        /* ... user u's is row dev_row[u] */
+    bool from_histories() const { return !reps && !item_rows && !dev_rows; }
 };
 
 /* The representations of a chunk's users: user i's is row rep_row[i] of H (eval arena, valid until the next carve_arena; with
@@ -3647,6 +3659,13 @@ sbr_status user_reps(sbr_model* m, const RepSource& s, const std::vector<uint64_
         prepare_users(list, n, T, s.lists, &out->b);
     }
     if (s.from_histories()) return forward_histories(m, out->b.first, out->b.nsteps, carve_epilogue, &out->H, &out->rep_row);
+    if (s.dev_rows) { /* nothing is made or moved: the scan reads the caller's device rows through rep_row */
+        SBRCHK(carve_arena(m, carve_epilogue));
+        out->H = const_cast<float*>(s.dev_rows);
+        out->rep_row.resize(nu);
+        for (size_t i = 0; i < nu; ++i) out->rep_row[i] = s.dev_row[users[i]];
+        return SBR_OK;
+    }
     SBRCHK(carve_arena(m, [&](DeviceArena& ar) {
         out->H = ar.take<float>(nu * d);
         if (s.item_rows) out->d_item_rows = ar.take<uint32_t>(nu);
@@ -4250,6 +4269,316 @@ sbr_status sbr_rank_targets_reps(sbr_model* m, const float* reps, uint64_t num_u
     SBRCHK(enter_reader(m));
     if (excl_ptr) SBRCHK(check_csr(m, excl_ptr, num_users, excl_items, false));
     return rank_targets_scan(m, RepSource{excl_ptr, excl_items, reps, 0, true}, num_users, target_ptr, target_items, out_ranks);
+}
+
+/* ---------------------------------------------------------------------------------------------
+ * session store: device-resident recurrent states advanced one event at a time (sbr_sessions.hip)
+ * ------------------------------------------------------------------------------------------- */
+}  // extern "C"
+
+struct sbr_sessions {
+    sbr_model* m = nullptr;
+    uint64_t capacity = 0;
+    uint64_t gen = 0;       /* the model's param_gen the states were computed under (creation / the last reset_all) */
+    sbr::SessionView v{nullptr, nullptr, nullptr}; /* rows [capacity + 1]: the last one is the empty-history row */
+    std::vector<uint64_t> host_len; /* the host's copy of len, kept by every successful call: which slots read the empty-history row */
+};
+
+namespace {
+
+constexpr uint64_t sessions_max_capacity = 0x7FFFFFFEull; /* the scans index rows with an int; one more row follows the slots */
+
+/* a call's slots: each below capacity, none twice */
+sbr_status check_slots(const sbr_sessions* st, const uint32_t* slots, uint64_t n) {
+    if (n && !slots) return SBR_ERR_INVALID_ARGUMENT;
+    for (uint64_t i = 0; i < n; ++i)
+        if (slots[i] >= st->capacity) return SBR_ERR_INVALID_ARGUMENT;
+    std::vector<uint32_t> sorted(slots, slots + n);
+    std::sort(sorted.begin(), sorted.end());
+    return std::adjacent_find(sorted.begin(), sorted.end()) == sorted.end() ? SBR_OK : SBR_ERR_INVALID_ARGUMENT;
+}
+
+/* entry of every store call but reset_all / capacity / destroy (the caller holds the model's mutex): the model's reader entry, and
+ * no call mixes states of two parameter sets — not while a fit plan is open either, whose steps change parameters under the store */
+sbr_status enter_sessions(sbr_sessions* st) {
+    SBRCHK(enter_reader(st->m));
+    return st->gen == st->m->param_gen && st->m->open_plans == 0 ? SBR_OK : SBR_ERR_INVALID_ARGUMENT;
+}
+
+/* Appends items[ptr[i] .. ptr[i + 1]) to slot slots[i] (already validated; slot == capacity with advance = 0: the empty-history
+ * row).  Sessions without items take no part; the others are ordered by item count descending, as the packers order sequences. */
+sbr_status sessions_append(sbr_sessions* st, const uint32_t* slots, uint64_t n, const uint64_t* ptr, const uint32_t* ids, int advance) {
+    sbr_model* m = st->m;
+    const uint64_t total = ptr[n] - ptr[0];
+    if (total == 0) return SBR_OK;
+    if (total >= (1ull << 31)) return SBR_ERR_INVALID_ARGUMENT; /* packed rows are addressed with an int */
+    std::vector<uint32_t> order;
+    for (uint64_t i = 0; i < n; ++i)
+        if (ptr[i + 1] > ptr[i]) order.push_back((uint32_t)i);
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return ptr[a + 1] - ptr[a] > ptr[b + 1] - ptr[b]; });
+    const size_t ns = order.size(), d = (size_t)m->d;
+    const int tm = (int)(ptr[order[0] + 1] - ptr[order[0]]);
+    std::vector<uint32_t> slot(ns), count(ns), packed;
+    std::vector<unsigned long long> start(ns);
+    std::vector<int> off;
+    for (size_t b = 0; b < ns; ++b) {
+        slot[b] = slots[order[b]];
+        count[b] = (uint32_t)(ptr[order[b] + 1] - ptr[order[b]]);
+        start[b] = ptr[order[b]] - ptr[0];
+    }
+    const bool lstm = m->ng != 0;
+    if (lstm) { /* time-major: step t covers the sessions with more than t items, a prefix */
+        off.assign((size_t)tm + 1, 0);
+        packed.resize(total);
+        size_t alive = ns;
+        for (int t = 0; t < tm; ++t) {
+            while (alive > 0 && count[alive - 1] <= (uint32_t)t) --alive;
+            for (size_t b = 0; b < alive; ++b) packed[(size_t)off[t] + b] = ids[ptr[order[b]] + (uint64_t)t];
+            off[t + 1] = off[t] + (int)alive;
+        }
+    }
+    sbr::SessionAppend a{};
+    uint32_t *d_slot = nullptr, *d_count = nullptr, *d_items = nullptr;
+    unsigned long long* d_start = nullptr;
+    SBRCHK(carve_arena(m, [&](DeviceArena& ar) {
+        d_slot = ar.take<uint32_t>(ns);
+        d_count = ar.take<uint32_t>(ns);
+        d_items = ar.take<uint32_t>(total);
+        if (lstm) { a.Hs = ar.take<float>(2 * ns * d); a.Cs = ar.take<float>(2 * ns * d); }
+        else d_start = ar.take<unsigned long long>(ns);
+    }));
+    HIPCHK(hipMemcpyAsync(d_slot, slot.data(), ns * 4, hipMemcpyHostToDevice, m->stream));
+    HIPCHK(hipMemcpyAsync(d_count, count.data(), ns * 4, hipMemcpyHostToDevice, m->stream));
+    HIPCHK(hipMemcpyAsync(d_items, lstm ? packed.data() : ids + ptr[0], total * 4, hipMemcpyHostToDevice, m->stream));
+    if (!lstm) HIPCHK(hipMemcpyAsync(d_start, start.data(), ns * 8, hipMemcpyHostToDevice, m->stream));
+    a.n = (int)ns; a.tm = tm;
+    a.slot = d_slot; a.count = d_count; a.items = d_items; a.start = d_start;
+    a.off_host = off.data();
+    a.advance = advance;
+    {
+        ScopedTimer t(m, SBR_K_RECURRENT_FWD, lstm ? (uint64_t)tm + 1 : 1);
+        if (sbr::launch_session_append(m->mv, st->v, a, m->stream) < 0) return SBR_ERR_UNSUPPORTED;
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(m->stream)); /* the host vectors are read by the asynchronous copies above */
+    if (advance)
+        for (size_t b = 0; b < ns; ++b) st->host_len[slot[b]] += count[b];
+    return SBR_OK;
+}
+
+/* every slot empty, the empty-history row made from the model's current parameters, the store bound to them */
+sbr_status sessions_rebind(sbr_sessions* st) {
+    sbr_model* m = st->m;
+    const size_t rows = (size_t)st->capacity + 1, d = (size_t)m->d;
+    HIPCHK(hipMemsetAsync(st->v.H, 0, rows * d * 4, m->stream));
+    if (st->v.C) HIPCHK(hipMemsetAsync(st->v.C, 0, rows * d * 4, m->stream));
+    HIPCHK(hipMemsetAsync(st->v.len, 0, rows * 8, m->stream));
+    std::fill(st->host_len.begin(), st->host_len.end(), 0);
+    const uint32_t row = (uint32_t)st->capacity, item0 = 0; /* one step of item 0 from zero (lstm.rs:262-264); not a length */
+    const uint64_t ptr[2] = {0, 1};
+    SBRCHK(sessions_append(st, &row, 1, ptr, &item0, 0));
+    st->gen = m->param_gen;
+    return SBR_OK;
+}
+
+/* the row each slot's representation is read from: its own, or the empty-history row */
+std::vector<int> session_rep_rows(const sbr_sessions* st, const uint32_t* slots, uint64_t n) {
+    std::vector<int> rows(n);
+    for (uint64_t i = 0; i < n; ++i) rows[i] = st->host_len[slots[i]] ? (int)slots[i] : (int)st->capacity;
+    return rows;
+}
+
+/* h_out / c_out [n][embedding_dim] and len_out [n] (each optional) of rows `rows` of the store */
+sbr_status sessions_gather(sbr_sessions* st, const uint32_t* rows, uint64_t n, float* h_out, float* c_out, uint64_t* len_out) {
+    sbr_model* m = st->m;
+    if (n == 0) return SBR_OK;
+    const size_t dl = (size_t)m->dl;
+    uint32_t* d_rows = nullptr;
+    float *d_h = nullptr, *d_c = nullptr;
+    unsigned long long* d_len = nullptr;
+    SBRCHK(carve_arena(m, [&](DeviceArena& ar) {
+        d_rows = ar.take<uint32_t>(n);
+        if (h_out) d_h = ar.take<float>(n * dl);
+        if (c_out) d_c = ar.take<float>(n * dl);
+        if (len_out) d_len = ar.take<unsigned long long>(n);
+    }));
+    HIPCHK(hipMemcpyAsync(d_rows, rows, n * 4, hipMemcpyHostToDevice, m->stream));
+    sbr::launch_session_get_state(st->v, d_rows, (int)n, m->d, m->dl, d_h, d_c, d_len, m->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(m->stream));
+    if (h_out) HIPCHK(hipMemcpy(h_out, d_h, n * dl * 4, hipMemcpyDeviceToHost));
+    if (c_out) HIPCHK(hipMemcpy(c_out, d_c, n * dl * 4, hipMemcpyDeviceToHost));
+    if (len_out) HIPCHK(hipMemcpy(len_out, d_len, n * 8, hipMemcpyDeviceToHost));
+    return SBR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+sbr_status sbr_sessions_create(sbr_model* m, uint64_t capacity, sbr_sessions** out) {
+    if (!m || !out || capacity == 0 || capacity > sessions_max_capacity) return SBR_ERR_INVALID_ARGUMENT;
+    *out = nullptr;
+    std::lock_guard<std::mutex> lock(m->mu);
+    SBRCHK(enter_reader(m));
+    sbr_sessions* st = new (std::nothrow) sbr_sessions();
+    if (!st) return SBR_ERR_OUT_OF_MEMORY;
+    st->m = m;
+    st->capacity = capacity;
+    const size_t rows = (size_t)capacity + 1, d = (size_t)m->d;
+    sbr_status s = dmalloc(&st->v.H, rows * d);
+    if (s == SBR_OK && m->ng) s = dmalloc(&st->v.C, rows * d);
+    if (s == SBR_OK) s = dmalloc(&st->v.len, rows);
+    if (s == SBR_OK) {
+        st->host_len.assign(capacity, 0);
+        s = sessions_rebind(st);
+    }
+    if (s != SBR_OK) {
+        hipStreamSynchronize(m->stream);
+        dfree(st->v.H); dfree(st->v.C); dfree(st->v.len);
+        delete st;
+        return s;
+    }
+    *out = st;
+    return SBR_OK;
+}
+
+void sbr_sessions_destroy(sbr_sessions* st) {
+    if (!st) return;
+    {
+        std::lock_guard<std::mutex> lock(st->m->mu);
+        hipSetDevice(st->m->device);
+        hipStreamSynchronize(st->m->stream); /* the rows go back to the scratch cache: nothing may still read them */
+        dfree(st->v.H); dfree(st->v.C); dfree(st->v.len);
+    }
+    delete st;
+}
+
+sbr_status sbr_sessions_capacity(const sbr_sessions* st, uint64_t* out) {
+    if (!st || !out) return SBR_ERR_INVALID_ARGUMENT;
+    *out = st->capacity;
+    return SBR_OK;
+}
+
+sbr_status sbr_sessions_reset_all(sbr_sessions* st) {
+    if (!st) return SBR_ERR_INVALID_ARGUMENT;
+    std::lock_guard<std::mutex> lock(st->m->mu);
+    SBRCHK(enter_reader(st->m));
+    if (st->m->open_plans) return SBR_ERR_INVALID_ARGUMENT; /* states bound now would go stale with the plan's next step */
+    return sessions_rebind(st);
+}
+
+sbr_status sbr_sessions_reset(sbr_sessions* st, const uint32_t* slots, uint64_t n) {
+    if (!st) return SBR_ERR_INVALID_ARGUMENT;
+    sbr_model* m = st->m;
+    std::lock_guard<std::mutex> lock(m->mu);
+    SBRCHK(enter_sessions(st));
+    SBRCHK(check_slots(st, slots, n));
+    if (n == 0) return SBR_OK;
+    uint32_t* d_slot = nullptr;
+    SBRCHK(carve_arena(m, [&](DeviceArena& ar) { d_slot = ar.take<uint32_t>(n); }));
+    HIPCHK(hipMemcpyAsync(d_slot, slots, n * 4, hipMemcpyHostToDevice, m->stream));
+    sbr::launch_session_reset(st->v, d_slot, (int)n, m->d, m->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(m->stream));
+    for (uint64_t i = 0; i < n; ++i) st->host_len[slots[i]] = 0;
+    return SBR_OK;
+}
+
+sbr_status sbr_sessions_append(sbr_sessions* st, const uint32_t* slots, uint64_t n, const uint64_t* item_ptr, const uint32_t* item_ids) {
+    if (!st || !item_ptr) return SBR_ERR_INVALID_ARGUMENT;
+    std::lock_guard<std::mutex> lock(st->m->mu);
+    SBRCHK(enter_sessions(st));
+    SBRCHK(check_slots(st, slots, n));
+    SBRCHK(check_csr(st->m, item_ptr, n, item_ids, false));
+    return sessions_append(st, slots, n, item_ptr, item_ids, 1);
+}
+
+sbr_status sbr_sessions_lengths(sbr_sessions* st, const uint32_t* slots, uint64_t n, uint64_t* out_lengths) {
+    if (!st || (n && !out_lengths)) return SBR_ERR_INVALID_ARGUMENT;
+    std::lock_guard<std::mutex> lock(st->m->mu);
+    SBRCHK(enter_sessions(st));
+    SBRCHK(check_slots(st, slots, n));
+    for (uint64_t i = 0; i < n; ++i) out_lengths[i] = st->host_len[slots[i]]; /* the host's copy is exact; get_state reads the device's */
+    return SBR_OK;
+}
+
+sbr_status sbr_sessions_representations(sbr_sessions* st, const uint32_t* slots, uint64_t n, float* out_reps) {
+    if (!st || (n && !out_reps)) return SBR_ERR_INVALID_ARGUMENT;
+    std::lock_guard<std::mutex> lock(st->m->mu);
+    SBRCHK(enter_sessions(st));
+    SBRCHK(check_slots(st, slots, n));
+    const std::vector<int> rows = session_rep_rows(st, slots, n);
+    return sessions_gather(st, reinterpret_cast<const uint32_t*>(rows.data()), n, out_reps, nullptr, nullptr);
+}
+
+sbr_status sbr_sessions_get_state(sbr_sessions* st, const uint32_t* slots, uint64_t n, float* out_h, float* out_c, uint64_t* out_len) {
+    if (!st || (n && (!out_h || !out_len))) return SBR_ERR_INVALID_ARGUMENT;
+    if (n && (out_c != nullptr) != (st->m->ng != 0)) return SBR_ERR_INVALID_ARGUMENT; /* c: the LSTM's, NULL for EWMA */
+    std::lock_guard<std::mutex> lock(st->m->mu);
+    SBRCHK(enter_sessions(st));
+    SBRCHK(check_slots(st, slots, n));
+    return sessions_gather(st, slots, n, out_h, out_c, out_len);
+}
+
+sbr_status sbr_sessions_set_state(sbr_sessions* st, const uint32_t* slots, uint64_t n, const float* h, const float* c, const uint64_t* len) {
+    if (!st || (n && (!h || !len))) return SBR_ERR_INVALID_ARGUMENT;
+    if (n && (c != nullptr) != (st->m->ng != 0)) return SBR_ERR_INVALID_ARGUMENT;
+    sbr_model* m = st->m;
+    std::lock_guard<std::mutex> lock(m->mu);
+    SBRCHK(enter_sessions(st));
+    SBRCHK(check_slots(st, slots, n));
+    if (n == 0) return SBR_OK;
+    const size_t dl = (size_t)m->dl;
+    uint32_t* d_slot = nullptr;
+    float *d_h = nullptr, *d_c = nullptr;
+    unsigned long long* d_len = nullptr;
+    SBRCHK(carve_arena(m, [&](DeviceArena& ar) {
+        d_slot = ar.take<uint32_t>(n);
+        d_h = ar.take<float>(n * dl);
+        if (c) d_c = ar.take<float>(n * dl);
+        d_len = ar.take<unsigned long long>(n);
+    }));
+    HIPCHK(hipMemcpyAsync(d_slot, slots, n * 4, hipMemcpyHostToDevice, m->stream));
+    HIPCHK(hipMemcpyAsync(d_h, h, n * dl * 4, hipMemcpyHostToDevice, m->stream));
+    if (c) HIPCHK(hipMemcpyAsync(d_c, c, n * dl * 4, hipMemcpyHostToDevice, m->stream));
+    HIPCHK(hipMemcpyAsync(d_len, len, n * 8, hipMemcpyHostToDevice, m->stream));
+    sbr::launch_session_set_state(st->v, d_slot, (int)n, m->d, m->dl, d_h, d_c, d_len, m->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(m->stream));
+    for (uint64_t i = 0; i < n; ++i) st->host_len[slots[i]] = len[i];
+    return SBR_OK;
+}
+
+sbr_status sbr_sessions_recommend(sbr_sessions* st, const uint32_t* slots, uint64_t n, uint32_t k, const uint64_t* excl_ptr,
+                                  const uint32_t* excl_items, uint32_t flags, uint32_t* out_items, float* out_scores) {
+    if (!st || (n && !out_items) || flags) return SBR_ERR_INVALID_ARGUMENT;
+    if (k < 1 || k > SBR_RECOMMEND_MAX_K) return SBR_ERR_INVALID_ARGUMENT;
+    if (!excl_args_ok(excl_ptr, excl_items, n)) return SBR_ERR_INVALID_ARGUMENT;
+    sbr_model* m = st->m;
+    std::lock_guard<std::mutex> lock(m->mu);
+    SBRCHK(enter_sessions(st));
+    SBRCHK(check_slots(st, slots, n));
+    if (excl_ptr) SBRCHK(check_csr(m, excl_ptr, n, excl_items, false));
+    const std::vector<int> rows = session_rep_rows(st, slots, n);
+    RepSource s{excl_ptr, excl_items, nullptr, 0, true};
+    s.dev_rows = st->v.H;
+    s.dev_row = rows.data();
+    return recommend_scan(m, s, n, k, out_items, out_scores);
+}
+
+sbr_status sbr_sessions_score_candidates(sbr_sessions* st, const uint32_t* slots, uint64_t n, const uint64_t* cand_ptr,
+                                         const uint32_t* cand_items, float* out_scores) {
+    if (!st) return SBR_ERR_INVALID_ARGUMENT;
+    sbr_model* m = st->m;
+    std::lock_guard<std::mutex> lock(m->mu);
+    SBRCHK(enter_sessions(st));
+    SBRCHK(check_slots(st, slots, n));
+    const std::vector<int> rows = session_rep_rows(st, slots, n);
+    RepSource s{nullptr, nullptr, nullptr, 0, false};
+    s.dev_rows = st->v.H;
+    s.dev_row = rows.data();
+    return score_candidates_scan(m, s, n, cand_ptr, cand_items, out_scores);
 }
 
 /* ---------------------------------------------------------------------------------------------

@@ -311,6 +311,32 @@ void launch_candidate_scores(const ModelView& m, const float* reps, const uint32
                              float* out, uint32_t* nonfinite_flag, hipStream_t s);
 /* out [num_users][dl] = the first dl columns of rows rep_row[i] of H [.][d] (user_representations) */
 void launch_rep_rows(const float* H, const int* rep_row, uint32_t num_users, int d, int dl, float* out, hipStream_t s);
+/* session store (sbr_sessions.hip): H [capacity + 1][d] (LSTM h / EWMA s), C likewise (LSTM; null for EWMA), len [capacity + 1];
+ * row `capacity` is the empty-history row (one step of item 0 from zero), len[capacity] stays 0 */
+struct SessionView {
+    float *H, *C;
+    unsigned long long* len;
+};
+/* One append call's n sessions, ordered by item count descending (device arrays unless named host).  LSTM: items time-major, the
+ * item of (step t, session b) at items[off_host[t] + b], step t covering sessions [0, off_host[t + 1] - off_host[t]); Hs / Cs: scratch
+ * [2][n][d] the steps write alternately.  EWMA: items = the call's id array, session b's at [start[b], start[b] + count[b]).  tm = the
+ * largest count (0: nothing is launched).  advance = 0: len is left alone (the empty-history row). */
+struct SessionAppend {
+    int n, tm;
+    const uint32_t *slot, *count, *items;
+    const unsigned long long* start;
+    const int* off_host;
+    float *Hs, *Cs;
+    int advance;
+};
+/* launches queued (LSTM: tm steps + the commit, which alone writes the store; EWMA: one, in place); -1: no kernel for m.d */
+int launch_session_append(const ModelView& m, const SessionView& sv, const SessionAppend& a, hipStream_t s);
+void launch_session_reset(const SessionView& sv, const uint32_t* slot, int n, int d, hipStream_t s);
+/* rows slot[i] <- h_in / c_in [n][dl] (zero where len_in[i] == 0 and past dl), len <- len_in; and the reverse (null outputs skipped) */
+void launch_session_set_state(const SessionView& sv, const uint32_t* slot, int n, int d, int dl, const float* h_in, const float* c_in,
+                              const unsigned long long* len_in, hipStream_t s);
+void launch_session_get_state(const SessionView& sv, const uint32_t* slot, int n, int d, int dl, float* h_out, float* c_out,
+                              unsigned long long* len_out, hipStream_t s);
 /* device self-tests of the numerics contract (tests/test_numerics_gpu.py) */
 void launch_selftest_math(const float* x, float* out_cell_h, float* out_sig, float* out_tanh, uint64_t n, hipStream_t s);
 void launch_selftest_dot_tree(const float* x, const float* y, int d, uint64_t nrows, float* out, hipStream_t s);

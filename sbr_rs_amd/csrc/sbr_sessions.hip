@@ -1,0 +1,368 @@
+// sbr_sessions.hip — gfx950 kernels of the session store (sbr_sessions_*, include/sbr_hip.h): device-resident recurrent states,
+// one row per slot, advanced by appended items and read in place by the catalogue scans (sbr_catalogue.hip).
+//
+// A store is H [capacity + 1][D] (h of the LSTM, s of EWMA), C [capacity + 1][D] (LSTM cell states) and len [capacity + 1]; row
+// `capacity` is the empty-history row: the state after one step of item 0 from zero (lstm.rs:262-264), which the scans read for a
+// slot with len == 0.  The arithmetic of a step is the forward pass's (sbr_kernels.hip: lstm_fwd_step_kernel,
+// ewma_forward_kernel), operation for operation, so a slot's state has the bits of sbr_user_representation of the items appended
+// to it, however they were split across calls.
+//
+//   session_lstm_step_kernel : one LSTM cell step of the sessions that still have an item at step t of a call
+//   session_commit_kernel    : the call's final h, c into the store's rows and len += items appended (the ONLY writer of the store
+//                              on the LSTM append path)
+//   session_ewma_step_kernel : all of a call's items of a session, in place
+//   session_reset_kernel / session_set_state_kernel / session_get_state_kernel : zero / scatter / gather of slots' rows and len
+//
+// Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off (see sbr_rs_amd/build.py).
+
+#include "sbr_kernels.h"
+
+#include "../../include/sbr_hip.h"
+#include "sbr_device.h"
+#include "sbr_numerics.h"
+
+namespace sbr {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+// ------------------------------------------------------------------------------------------------
+// LSTM step of a session store.  FORM: the STEP form — grid = (32-session tiles of step t) x (16-unit tiles), one wave per gate,
+// one launch per step of the call — writing the new h, c into SCRATCH rows, never into the rows it reads; session_commit_kernel,
+// next on the stream, copies each session's final state into the store.  Why: a workgroup of unit tile ut reads ALL of a row's h
+// while the workgroups of the other unit tiles write their units of the same row, so writing h in place would race; the
+// sequence-resident form (one workgroup per session tile for all units and steps) avoids that too but needs a workgroup of D / 16
+// waves with every gate's accumulators live, which does not exist at D = 256 (the forward pass itself takes per-step launches
+// there), and a call appends one item far more often than many.  The sequence-resident form is not built here: this kernel is the
+// only one that steps a store's LSTM state.
+//
+// Arithmetic = lstm_fwd_step_kernel: wave g computes z_g = [E[item] ; h] Wp_g + b_g for 32 sessions x 16 units on
+// v_mfma_f32_16x16x4_f32 (accumulator seeded with the bias, k ascending, the x half then the h half), the gate pre-activations
+// meet in LDS and sbr_lstm_cell_fwd is applied by all threads.  No G, no X: nothing here trains.
+//
+// Rows: session b of the step (b < bt; the host orders a call's sessions by item count descending, so step t covers a prefix)
+// reads h, c from Hin / Cin row (in_row ? in_row[b] : b) — the store's rows through the slot index at the call's first step, the
+// scratch rows of the step before afterwards — as zeros where len is given and len[row] == 0 (an empty slot starts from
+// h = c = 0), and writes row b of Hout / Cout.
+// ------------------------------------------------------------------------------------------------
+template <int D, int NG>
+__global__ __launch_bounds__(NG * 64) void session_lstm_step_kernel(ModelView m, const uint32_t* __restrict__ items, int bt,
+                                                                    const uint32_t* __restrict__ in_row,
+                                                                    const unsigned long long* __restrict__ len,
+                                                                    const float* __restrict__ Hin, const float* __restrict__ Cin,
+                                                                    float* __restrict__ Hout, float* __restrict__ Cout) {
+    constexpr int LDA = D + 2;
+    constexpr int NSH = D / 16;       // weight k-blocks (16 k each) per half
+    constexpr int RT = 2;             // 16-row tiles per workgroup
+    constexpr int ROWS = 16 * RT;
+    constexpr int NT = NG * 64;
+    constexpr int LDZ = NG * 16 + 1;
+    constexpr int PF = NSH < 8 ? NSH : 8;
+    constexpr int LDS_FLOATS = ROWS * (LDA > LDZ ? LDA : LDZ);  // A halves and the gate exchange share one buffer
+    __shared__ float As[LDS_FLOATS];
+    __shared__ int src_row[ROWS];     // row of Hin / Cin of the tile's sessions; -1: zero state (or past the tile's end)
+    float* Zs = As;
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int g = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int j16 = lane & 15;
+    const int kq = lane >> 4;
+    const int ut = blockIdx.y;
+    const int b0 = blockIdx.x * ROWS;
+    const int nrows = bt - b0 < ROWS ? bt - b0 : ROWS;
+    if (tid < ROWS) {
+        int r = -1;
+        if (tid < nrows) {
+            r = in_row ? (int)in_row[b0 + tid] : b0 + tid;
+            if (len && len[r] == 0ull) r = -1;
+        }
+        src_row[tid] = r;
+    }
+    const float* wp = m.Wp + (((size_t)(ut * NG + g) * (2 * NSH)) * 64 + lane) * 4;
+    float4 bf[PF];
+#pragma unroll
+    for (int S = 0; S < PF; ++S) bf[S] = ld4(wp + (size_t)S * 256);
+    const float bias = m.bW[g * D + ut * 16 + j16];
+    __syncthreads();
+    // both halves of the A tile are requested up front
+    constexpr int NV = ROWS * (D / 4);
+    constexpr int ITER = (NV + NT - 1) / NT;
+    float4 xv[ITER], hv[ITER];
+#pragma unroll
+    for (int it = 0; it < ITER; ++it) {
+        const int idx = tid + it * NT;
+        const int i = idx / (D / 4);
+        const int c4 = (idx % (D / 4)) * 4;
+        xv[it] = make_float4(0.f, 0.f, 0.f, 0.f);
+        hv[it] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (idx < NV && i < nrows) {
+            xv[it] = ld4(m.E + (size_t)items[b0 + i] * D + c4);
+            const int r = src_row[i];
+            if (r >= 0) hv[it] = ld4(Hin + (size_t)r * D + c4);
+        }
+    }
+    auto stage = [&](const float4* v) {
+#pragma unroll
+        for (int it = 0; it < ITER; ++it) {
+            const int idx = tid + it * NT;
+            if (idx < NV) {
+                const int i = idx / (D / 4);
+                const int c4 = (idx % (D / 4)) * 4;
+                float2* dst = reinterpret_cast<float2*>(&As[i * LDA + c4]);
+                dst[0] = make_float2(v[it].x, v[it].y);
+                dst[1] = make_float2(v[it].z, v[it].w);
+            }
+        }
+    };
+    f32x4 acc[RT];
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) acc[rt] = (f32x4){bias, bias, bias, bias};
+    auto mma_half = [&](int half) {
+#pragma unroll
+        for (int S0 = 0; S0 < NSH; S0 += PF) {
+            float4 cur[PF];
+#pragma unroll
+            for (int S = 0; S < PF; ++S) cur[S] = bf[S];
+            // request the next group of weight k-blocks (possibly of the other half)
+            const int nextS = half * NSH + S0 + PF;
+            if (nextS < 2 * NSH) {
+#pragma unroll
+                for (int S = 0; S < PF; ++S) bf[S] = ld4(wp + (size_t)(nextS + S) * 256);
+            }
+#pragma unroll
+            for (int S = 0; S < PF; ++S) {
+                float av[RT][4];
+#pragma unroll
+                for (int rt = 0; rt < RT; ++rt) {
+                    const float* arow = &As[(rt * 16 + j16) * LDA + 16 * (S0 + S) + kq];
+                    av[rt][0] = arow[0]; av[rt][1] = arow[4]; av[rt][2] = arow[8]; av[rt][3] = arow[12];
+                }
+                // independent accumulators alternate so that no MFMA waits on its predecessor
+#pragma unroll
+                for (int rt = 0; rt < RT; ++rt) acc[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[rt][0], cur[S].x, acc[rt], 0, 0, 0);
+#pragma unroll
+                for (int rt = 0; rt < RT; ++rt) acc[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[rt][1], cur[S].y, acc[rt], 0, 0, 0);
+#pragma unroll
+                for (int rt = 0; rt < RT; ++rt) acc[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[rt][2], cur[S].z, acc[rt], 0, 0, 0);
+#pragma unroll
+                for (int rt = 0; rt < RT; ++rt) acc[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[rt][3], cur[S].w, acc[rt], 0, 0, 0);
+            }
+        }
+    };
+    stage(xv);
+    __syncthreads();
+    mma_half(0);
+    __syncthreads();
+    stage(hv);
+    __syncthreads();
+    mma_half(1);
+    __syncthreads();
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) Zs[(rt * 16 + kq * 4 + reg) * LDZ + g * 16 + j16] = acc[rt][reg];
+    __syncthreads();
+    for (int e = tid; e < ROWS * 16; e += NT) {
+        const int i = e >> 4;
+        const int uu = e & 15;
+        if (i < nrows) {
+            const int u = ut * 16 + uu;
+            const int r = src_row[i];
+            const float cprev = r >= 0 ? Cin[(size_t)r * D + u] : 0.0f;
+            const float* z = &Zs[i * LDZ + uu];
+            float zi, zf, zg, zo;
+            if (NG == 4) { zi = z[0]; zf = z[16]; zg = z[32]; zo = z[(NG - 1) * 16]; }
+            else { zi = 0.0f; zf = z[0]; zg = z[16]; zo = z[32]; }
+            float gi, gf, gg, go, cc, hh;
+            sbr_lstm_cell_fwd(zi, zf, zg, zo, cprev, NG == 3, &gi, &gf, &gg, &go, &cc, &hh);
+            Cout[(size_t)(b0 + i) * D + u] = cc;
+            Hout[(size_t)(b0 + i) * D + u] = hh;
+        }
+    }
+}
+
+// The append's commit: session b (count[b] items this call, final state in the scratch rows of parity (count[b] - 1) & 1) ->
+// the store's row slot[b]; len[slot[b]] += count[b] * advance (advance = 0: the empty-history row, which has no length).  Sessions
+// with no items are left alone.  16 B per lane.
+template <int D>
+__global__ __launch_bounds__(256) void session_commit_kernel(const uint32_t* __restrict__ slot, const uint32_t* __restrict__ count, int n,
+                                                             const float* __restrict__ Hs, const float* __restrict__ Cs, size_t parity_stride,
+                                                             float* __restrict__ H, float* __restrict__ C, unsigned long long* __restrict__ len,
+                                                             int advance) {
+    constexpr int L = D / 4;
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t b = idx / L;
+    if (b >= (size_t)n) return;
+    const uint32_t cnt = count[b];
+    if (cnt == 0) return;
+    const int c4 = (int)(idx % L) * 4;
+    const size_t src = (size_t)((cnt - 1) & 1u) * parity_stride + b * D + c4;
+    const size_t dst = (size_t)slot[b] * D + c4;
+    st4(H + dst, ld4(Hs + src));
+    st4(C + dst, ld4(Cs + src));
+    if (c4 == 0 && advance) len[slot[b]] += cnt;
+}
+
+// ------------------------------------------------------------------------------------------------
+// EWMA step of a session store: one D/4-lane group per session, 16 B per lane, walks the call's items of its session —
+// ids[start[b] .. start[b] + count[b]) — from the slot's stored s and writes s and len back IN PLACE (each element depends only on
+// itself and one lane group owns a row).  The first item ever appended to a slot (len == 0) sets s = E[x] (ewma.rs:306); every
+// other one is ewma_forward_kernel's expression s = fma(a, s, (1 - a) * E[x]), a = sbr_sigmoidf(alpha).
+// ------------------------------------------------------------------------------------------------
+template <int D>
+__global__ __launch_bounds__(256) void session_ewma_step_kernel(ModelView m, const uint32_t* __restrict__ slot,
+                                                                const unsigned long long* __restrict__ start,
+                                                                const uint32_t* __restrict__ count, int n, const uint32_t* __restrict__ ids,
+                                                                float* __restrict__ S, unsigned long long* __restrict__ len, int advance) {
+    constexpr int L = D / 4;
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t b = idx / L;
+    if (b >= (size_t)n) return;
+    const int lg = (int)(idx % L);
+    const uint32_t cnt = count[b];
+    if (cnt == 0) return;
+    float a[4], oma[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        a[j] = sbr_sigmoidf(m.alpha[4 * lg + j]);
+        oma[j] = 1.0f - a[j];
+    }
+    const uint32_t sl = slot[b];
+    const unsigned long long have = len[sl];
+    float* row = S + (size_t)sl * D + 4 * lg;
+    float4 s = ld4(row);
+    const uint32_t* it = ids + start[b];
+    for (uint32_t t = 0; t < cnt; ++t) {
+        const float4 x = ld4(m.E + (size_t)it[t] * D + 4 * lg);
+        if (have == 0ull && t == 0) {
+            s = x;
+        } else {
+            s.x = sbr_fma(a[0], s.x, oma[0] * x.x);
+            s.y = sbr_fma(a[1], s.y, oma[1] * x.y);
+            s.z = sbr_fma(a[2], s.z, oma[2] * x.z);
+            s.w = sbr_fma(a[3], s.w, oma[3] * x.w);
+        }
+    }
+    st4(row, s);
+    if (lg == 0 && advance) len[sl] = have + cnt;
+}
+
+// rows slot[i] of H (and C) zeroed, len = 0
+__global__ __launch_bounds__(256) void session_reset_kernel(const uint32_t* __restrict__ slot, int n, int d, float* __restrict__ H,
+                                                            float* __restrict__ C, unsigned long long* __restrict__ len) {
+    const int L = d / 4;
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t i = idx / L;
+    if (i >= (size_t)n) return;
+    const int c4 = (int)(idx % L) * 4;
+    const size_t at = (size_t)slot[i] * d + c4;
+    st4(H + at, make_float4(0.f, 0.f, 0.f, 0.f));
+    if (C) st4(C + at, make_float4(0.f, 0.f, 0.f, 0.f));
+    if (c4 == 0) len[slot[i]] = 0ull;
+}
+
+// restore: row slot[i] of H (C) = h_in[i] (c_in[i]), embedding_dim floats each, the columns past it zero; len[slot[i]] = len_in[i].
+// A restored length of 0 is the empty slot: its state is zero whatever h_in holds.
+__global__ __launch_bounds__(256) void session_set_state_kernel(const uint32_t* __restrict__ slot, int n, int d, int dl,
+                                                                const float* __restrict__ h_in, const float* __restrict__ c_in,
+                                                                const unsigned long long* __restrict__ len_in, float* __restrict__ H,
+                                                                float* __restrict__ C, unsigned long long* __restrict__ len) {
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t i = idx / d;
+    if (i >= (size_t)n) return;
+    const int c = (int)(idx % d);
+    const bool live = c < dl && len_in[i] != 0ull;
+    const size_t at = (size_t)slot[i] * d + c;
+    H[at] = live ? h_in[i * dl + c] : 0.0f;
+    if (C) C[at] = live ? c_in[i * dl + c] : 0.0f;
+    if (c == 0) len[slot[i]] = len_in[i];
+}
+
+// checkpoint: h_out[i] (c_out[i]) = the first embedding_dim columns of row slot[i] of H (C), len_out[i] = len[slot[i]]; any output
+// may be null
+__global__ __launch_bounds__(256) void session_get_state_kernel(const uint32_t* __restrict__ slot, int n, int d, int dl,
+                                                                const float* __restrict__ H, const float* __restrict__ C,
+                                                                const unsigned long long* __restrict__ len, float* __restrict__ h_out,
+                                                                float* __restrict__ c_out, unsigned long long* __restrict__ len_out) {
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t i = idx / dl;
+    if (i >= (size_t)n) return;
+    const int c = (int)(idx % dl);
+    const size_t at = (size_t)slot[i] * d + c;
+    if (h_out) h_out[i * dl + c] = H[at];
+    if (c_out) c_out[i * dl + c] = C[at];
+    if (c == 0 && len_out) len_out[i] = len[slot[i]];
+}
+
+namespace {
+
+inline unsigned blocks_for(size_t threads) { return (unsigned)((threads + 255) / 256); }
+
+template <int D>
+void lstm_append_d(const ModelView& m, const SessionView& sv, const SessionAppend& a, hipStream_t s) {
+    const size_t parity_stride = (size_t)a.n * D;
+    for (int t = 0; t < a.tm; ++t) {
+        const int bt = a.off_host[t + 1] - a.off_host[t];
+        const uint32_t* items = a.items + a.off_host[t];
+        const float* Hin = t == 0 ? sv.H : a.Hs + (size_t)((t - 1) & 1) * parity_stride;
+        const float* Cin = t == 0 ? sv.C : a.Cs + (size_t)((t - 1) & 1) * parity_stride;
+        float* Hout = a.Hs + (size_t)(t & 1) * parity_stride;
+        float* Cout = a.Cs + (size_t)(t & 1) * parity_stride;
+        const dim3 grid((unsigned)((bt + 31) / 32), D / 16);
+        if (m.ng == 4)
+            hipLaunchKernelGGL((session_lstm_step_kernel<D, 4>), grid, dim3(256), 0, s, m, items, bt, t == 0 ? a.slot : nullptr,
+                               t == 0 ? sv.len : nullptr, Hin, Cin, Hout, Cout);
+        else
+            hipLaunchKernelGGL((session_lstm_step_kernel<D, 3>), grid, dim3(192), 0, s, m, items, bt, t == 0 ? a.slot : nullptr,
+                               t == 0 ? sv.len : nullptr, Hin, Cin, Hout, Cout);
+    }
+    if (a.tm > 0)
+        hipLaunchKernelGGL((session_commit_kernel<D>), dim3(blocks_for((size_t)a.n * (D / 4))), dim3(256), 0, s, a.slot, a.count, a.n, a.Hs,
+                           a.Cs, parity_stride, sv.H, sv.C, sv.len, a.advance);
+}
+
+template <int D>
+void ewma_append_d(const ModelView& m, const SessionView& sv, const SessionAppend& a, hipStream_t s) {
+    if (a.tm > 0)
+        hipLaunchKernelGGL((session_ewma_step_kernel<D>), dim3(blocks_for((size_t)a.n * (D / 4))), dim3(256), 0, s, m, a.slot, a.start, a.count,
+                           a.n, a.items, sv.H, sv.len, a.advance);
+}
+
+}  // namespace
+
+int launch_session_append(const ModelView& m, const SessionView& sv, const SessionAppend& a, hipStream_t s) {
+#define SBR_SESSION_D(DD)                                  \
+    case DD:                                               \
+        if (m.ng) lstm_append_d<DD>(m, sv, a, s);          \
+        else ewma_append_d<DD>(m, sv, a, s);               \
+        break;
+    switch (m.d) {
+        SBR_SESSION_D(16)
+        SBR_SESSION_D(32)
+        SBR_SESSION_D(64)
+        SBR_SESSION_D(128)
+        SBR_SESSION_D(256)
+        default: return -1; /* no such storage width: the caller fails the call */
+    }
+#undef SBR_SESSION_D
+    return a.tm > 0 ? (m.ng ? a.tm + 1 : 1) : 0;
+}
+
+void launch_session_reset(const SessionView& sv, const uint32_t* slot, int n, int d, hipStream_t s) {
+    if (n > 0) hipLaunchKernelGGL(session_reset_kernel, dim3(blocks_for((size_t)n * (d / 4))), dim3(256), 0, s, slot, n, d, sv.H, sv.C, sv.len);
+}
+
+void launch_session_set_state(const SessionView& sv, const uint32_t* slot, int n, int d, int dl, const float* h_in, const float* c_in,
+                              const unsigned long long* len_in, hipStream_t s) {
+    if (n > 0)
+        hipLaunchKernelGGL(session_set_state_kernel, dim3(blocks_for((size_t)n * d)), dim3(256), 0, s, slot, n, d, dl, h_in, c_in, len_in, sv.H,
+                           sv.C, sv.len);
+}
+
+void launch_session_get_state(const SessionView& sv, const uint32_t* slot, int n, int d, int dl, float* h_out, float* c_out,
+                              unsigned long long* len_out, hipStream_t s) {
+    if (n > 0)
+        hipLaunchKernelGGL(session_get_state_kernel, dim3(blocks_for((size_t)n * dl)), dim3(256), 0, s, slot, n, d, dl, sv.H, sv.C, sv.len, h_out,
+                           c_out, len_out);
+}
+
+}  // namespace sbr

@@ -3,6 +3,7 @@ parity tests read symmetrically, but talks only to libsbr_hip.so."""
 from __future__ import annotations
 
 import ctypes as C
+import weakref
 
 import numpy as np
 
@@ -707,10 +708,147 @@ class Model:
                                              None if ei is None else _ptr(ei), _ptr(tp), _ptr(ti), _ptr(ranks)))
         return ranks[: ti.size]
 
+    def sessions(self, capacity: int) -> "Sessions":
+        """A session store of ``capacity`` slots on this model (sbr_sessions_create): device-resident user states advanced one
+        appended item at a time and read in place by recommend / score_candidates."""
+        return Sessions(self, capacity)
+
     def close(self):
         if getattr(self, "_h", None):
+            for st in list(getattr(self, "_stores", ())):  # stores are destroyed before their model
+                st.close()
             self._L.sbr_model_destroy(self._h)
             self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _items_csr(items, n: int):
+    """``items`` of Sessions.append — a list of item-id sequences, one per slot, or a (ptr, ids) tuple — as (ptr u64 [n + 1], ids
+    u32, never empty)."""
+    if isinstance(items, tuple):  # a tuple is always the CSR pair
+        if len(items) != 2 or len(items[0]) != n + 1:
+            raise ValueError("a (ptr, ids) pair with one range per slot")
+        ptr = np.ascontiguousarray(items[0], dtype=np.uint64)
+        ids = np.ascontiguousarray(items[1], dtype=np.uint32).ravel()
+    else:
+        if len(items) != n:
+            raise ValueError("one item sequence per slot")
+        seqs = [np.asarray(x, dtype=np.uint32).ravel() for x in items]
+        ptr = np.zeros(n + 1, dtype=np.uint64)
+        ptr[1:] = np.cumsum([x.size for x in seqs])
+        ids = np.ascontiguousarray(np.concatenate(seqs) if seqs else np.zeros(0, np.uint32), dtype=np.uint32)
+    if ids.size == 0:
+        ids = np.zeros(1, dtype=np.uint32)
+    return ptr, ids
+
+
+class Sessions:
+    """A session store (sbr_sessions_*): ``capacity`` slots of recurrent state on the device — h, c of the LSTM, s of EWMA — each
+    advanced by the items appended to it, one cell step per item.  A slot's representation has the bits of
+    ``user_representation`` of the items appended since its last reset (an empty slot: of the empty history) as long as they are
+    at most max_sequence_length; beyond that a session keeps the recurrence over everything appended where the windowed call
+    truncates.  After the model's parameters change (fit, set_param, load) every call but ``reset()`` of the whole store raises
+    until that reset re-binds it; while a fit plan is open on the model every call raises.  The object keeps its model alive, and
+    ``Model.close`` closes the model's live stores first."""
+
+    def __init__(self, model: Model, capacity: int):
+        self.model = model
+        self._L = _lib.load()
+        h = C.c_void_p()
+        _check(self._L.sbr_sessions_create(model._h, int(capacity), C.byref(h)))
+        self._h = h
+        self._lstm = int(model.hp.model) != 2
+        if not hasattr(model, "_stores"):
+            model._stores = weakref.WeakSet()  # Model.close closes its live stores first
+        model._stores.add(self)
+
+    @property
+    def capacity(self) -> int:
+        n = C.c_uint64()
+        _check(self._L.sbr_sessions_capacity(self._h, C.byref(n)))
+        return n.value
+
+    @staticmethod
+    def _slots(slots) -> np.ndarray:
+        return np.ascontiguousarray(slots, dtype=np.uint32).ravel()
+
+    def append(self, slots, items):
+        """Appends ``items[i]`` (a sequence of item ids, possibly empty), in order, to slot ``slots[i]``; ``items`` may also be a
+        CSR pair (ptr [n + 1], ids)."""
+        sl = self._slots(slots)
+        ptr, ids = _items_csr(items, sl.size)
+        _check(self._L.sbr_sessions_append(self._h, _ptr(sl), sl.size, _ptr(ptr), _ptr(ids)))
+
+    def lengths(self, slots) -> np.ndarray:
+        sl = self._slots(slots)
+        out = np.zeros(max(sl.size, 1), dtype=np.uint64)
+        _check(self._L.sbr_sessions_lengths(self._h, _ptr(sl), sl.size, _ptr(out)))
+        return out[: sl.size]
+
+    def representations(self, slots) -> np.ndarray:
+        """[n, embedding_dim] f32: row i is slot ``slots[i]``'s representation."""
+        sl = self._slots(slots)
+        out = np.zeros((sl.size, self.model.dim), dtype=np.float32)
+        _check(self._L.sbr_sessions_representations(self._h, _ptr(sl), sl.size, _ptr(out)))
+        return out
+
+    def recommend(self, slots, k: int, exclude=None):
+        """``Model.recommend_reps(self.representations(slots), k, exclude)`` with the scan reading the store's rows in place: items
+        [n, k] u32, scores [n, k] f32.  The store keeps no item history: ``exclude`` is None or one sequence of item ids per slot."""
+        sl = self._slots(slots)
+        items = np.zeros((sl.size, max(int(k), 0)), dtype=np.uint32)
+        scores = np.zeros((sl.size, max(int(k), 0)), dtype=np.float32)
+        ep, ei = _exclusion_csr(exclude, sl.size)
+        _check(self._L.sbr_sessions_recommend(self._h, _ptr(sl), sl.size, int(k) & 0xFFFFFFFF, None if ep is None else _ptr(ep),
+                                              None if ei is None else _ptr(ei), 0, _ptr(items), _ptr(scores)))
+        return items, scores
+
+    def score_candidates(self, slots, candidates):
+        """``Model.score_candidates_reps`` on the slots' representations, read in place: one f32 array per slot, in candidate
+        order.  ``candidates``: one sequence of item ids per slot, or a CSR pair (ptr, ids)."""
+        sl = self._slots(slots)
+        cp, ci = _items_csr(candidates, sl.size)
+        scores = np.zeros(max(int(cp[-1] - cp[0]), 1), dtype=np.float32)
+        _check(self._L.sbr_sessions_score_candidates(self._h, _ptr(sl), sl.size, _ptr(cp), _ptr(ci), _ptr(scores)))
+        return Model._per_user(scores, cp)
+
+    def reset(self, slots=None):
+        """Empties the named slots; ``slots=None``: every slot, and the store is re-bound to the model's current parameters."""
+        if slots is None:
+            _check(self._L.sbr_sessions_reset_all(self._h))
+        else:
+            sl = self._slots(slots)
+            _check(self._L.sbr_sessions_reset(self._h, _ptr(sl), sl.size))
+
+    def state(self, slots):
+        """Checkpoint of the named slots: (h [n, embedding_dim], c likewise — None for EWMA —, len [n] u64)."""
+        sl = self._slots(slots)
+        h = np.zeros((sl.size, self.model.dim), dtype=np.float32)
+        c = np.zeros((sl.size, self.model.dim), dtype=np.float32) if self._lstm else None
+        n = np.zeros(max(sl.size, 1), dtype=np.uint64)
+        _check(self._L.sbr_sessions_get_state(self._h, _ptr(sl), sl.size, _ptr(h), None if c is None else _ptr(c), _ptr(n)))
+        return h, c, n[: sl.size]
+
+    def set_state(self, slots, h, c, lengths):
+        """Restores a checkpoint taken by ``state`` (of this store or another one of the same model and parameters)."""
+        sl = self._slots(slots)
+        h = np.ascontiguousarray(h, dtype=np.float32).reshape(sl.size, self.model.dim)
+        c = None if c is None else np.ascontiguousarray(c, dtype=np.float32).reshape(sl.size, self.model.dim)
+        n = np.ascontiguousarray(lengths, dtype=np.uint64).ravel()
+        if n.size != sl.size:
+            raise ValueError("one length per slot")
+        _check(self._L.sbr_sessions_set_state(self._h, _ptr(sl), sl.size, _ptr(h), None if c is None else _ptr(c), _ptr(n)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.sbr_sessions_destroy(self._h)
+            self._h = None
+            self.model._stores.discard(self)
 
     def __del__(self):
         try:

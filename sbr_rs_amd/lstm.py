@@ -283,6 +283,13 @@ class _ImplicitSequenceModel:
         than k eligible items is padded with (0xFFFFFFFF, -inf)."""
         return self.params.similar_items(query_items, k, metric=metric, include_self=include_self, exclude=exclude)
 
+    def sessions(self, capacity: int):
+        """A session store of ``capacity`` slots on the device (``engine.Sessions``): each slot holds one user's recurrent state,
+        ``append`` advances it by one cell step per item instead of re-running the whole history, and ``recommend`` /
+        ``score_candidates`` read the states in place.  Exact: a slot's representation has the bits of ``user_representation``
+        of what was appended to it, up to max_sequence_length items; beyond that a session does not truncate."""
+        return self.params.sessions(capacity)
+
     def rank_targets(self, histories, targets, mask_history: bool = True):
         """Exact catalogue ranks of each user's targets from one device scan (``evaluation.rank_targets``): one uint32 array
         per user, in target order."""
