@@ -591,6 +591,30 @@ class Sessions {
         check(st, "sbr_sessions_recommend");
         return Result<Recommendations, PredictionError>::Ok(std::move(r));
     }
+    /// `recommend` without the near-duplicates (sbr_sessions_recommend_diverse): from each slot's `pool` best items, k picked
+    /// greedily by maximal marginal relevance, as ImplicitSequenceModel::recommend_diverse picks them; rows in pick order.
+    Result<Recommendations, PredictionError> recommend_diverse(const std::vector<std::uint32_t>& slots, std::size_t k, std::size_t pool,
+                                                               float trade_off = 0.5f, Similarity metric = Similarity::Cosine,
+                                                               const std::vector<std::uint64_t>& excl_ptr = {},
+                                                               const std::vector<std::uint32_t>& excl_items = {}) const {
+        if (k < 1 || pool < k || pool > SBR_DIVERSE_MAX_POOL)
+            throw EngineError(SBR_ERR_INVALID_ARGUMENT, "Sessions::recommend_diverse: 1 <= k <= pool <= SBR_DIVERSE_MAX_POOL");
+        if (!excl_ptr.empty() && (excl_ptr.size() != slots.size() + 1 || excl_ptr.back() > excl_items.size()))
+            throw EngineError(SBR_ERR_INVALID_ARGUMENT, "Sessions::recommend_diverse: one exclusion range per slot");
+        Recommendations r;
+        r.num_users = slots.size();
+        r.k = k;
+        r.items.resize(r.num_users * k);
+        r.scores.resize(r.num_users * k);
+        const std::uint32_t none = 0;
+        const sbr_status st = sbr_sessions_recommend_diverse(h_, slots.data(), (std::uint64_t)slots.size(), (std::uint32_t)k, (std::uint32_t)pool,
+                                                             trade_off, (std::uint32_t)metric, excl_ptr.empty() ? nullptr : excl_ptr.data(),
+                                                             excl_ptr.empty() ? nullptr : (excl_items.empty() ? &none : excl_items.data()),
+                                                             r.items.data(), r.scores.data());
+        if (st == SBR_ERR_INVALID_PREDICTION) return Result<Recommendations, PredictionError>::Err(PredictionError::InvalidPredictionValue);
+        check(st, "sbr_sessions_recommend_diverse");
+        return Result<Recommendations, PredictionError>::Ok(std::move(r));
+    }
     /// One score per candidate, in candidate order, slot i's candidates cand_items[cand_ptr[i] .. cand_ptr[i + 1]) (sbr_sessions_score_candidates).
     Result<std::vector<float>, PredictionError> score_candidates(const std::vector<std::uint32_t>& slots, const std::vector<std::uint64_t>& cand_ptr,
                                                                  const std::vector<std::uint32_t>& cand_items) const {
@@ -773,6 +797,39 @@ class ImplicitSequenceModel : public OnlineRankingModel<ImplicitUser> {
                                                   subset.data(), (std::uint64_t)subset.size(), r.items.data(), r.scores.data());
         if (st == SBR_ERR_INVALID_PREDICTION) return Result<Recommendations, PredictionError>::Err(PredictionError::InvalidPredictionValue);
         check(st, "sbr_recommend_among");
+        return Result<Recommendations, PredictionError>::Ok(std::move(r));
+    }
+
+    /// The largest `pool` of recommend_diverse on this model (sbr_recommend_diverse_max_pool): a user's pool lives in one
+    /// workgroup's LDS, min(1024, 32768 / storage width) rows.
+    std::size_t diverse_max_pool() const {
+        std::uint32_t p = 0;
+        check(sbr_recommend_diverse_max_pool(replicas_->primary(), &p), "sbr_recommend_diverse_max_pool");
+        return (std::size_t)p;
+    }
+
+    /// `recommend` without the near-duplicates (sbr_recommend_diverse): from each user's `pool` best items — recommend's row at
+    /// k = pool — k are picked greedily by maximal marginal relevance, trade_off * score - (1 - trade_off) * (the largest
+    /// similarity to an item already picked), similarity as `similar_items` measures it; the first pick is the best item.  Rows
+    /// in pick order with `recommend`'s score bits, padded with (0xFFFFFFFF, -inf).  pool = 0: min(4 k, diverse_max_pool()).
+    /// trade_off = 1 is recommend(k).  Err(InvalidPredictionValue) on a non-finite score, norm or similarity the selection uses.
+    Result<Recommendations, PredictionError> recommend_diverse(const data::CompressedInteractions& interactions, std::size_t k,
+                                                               std::size_t pool = 0, float trade_off = 0.5f,
+                                                               Similarity metric = Similarity::Cosine, bool exclude_history = true) const {
+        if (pool == 0) pool = std::min<std::size_t>(4 * k, diverse_max_pool());
+        if (k < 1 || pool < k || pool > SBR_DIVERSE_MAX_POOL)
+            throw EngineError(SBR_ERR_INVALID_ARGUMENT, "recommend_diverse: 1 <= k <= pool <= SBR_DIVERSE_MAX_POOL");
+        Recommendations r;
+        r.num_users = interactions.num_users();
+        r.k = k;
+        r.items.resize(r.num_users * k);
+        r.scores.resize(r.num_users * k);
+        const sbr_status st = sbr_recommend_diverse(replicas_->primary(), interactions.user_pointers().data(), interactions.item_ids().data(),
+                                                    (std::uint64_t)r.num_users, (std::uint32_t)k, (std::uint32_t)pool, trade_off,
+                                                    (std::uint32_t)metric, exclude_history ? 0u : SBR_RECOMMEND_INCLUDE_HISTORY,
+                                                    r.items.data(), r.scores.data());
+        if (st == SBR_ERR_INVALID_PREDICTION) return Result<Recommendations, PredictionError>::Err(PredictionError::InvalidPredictionValue);
+        check(st, "sbr_recommend_diverse");
         return Result<Recommendations, PredictionError>::Ok(std::move(r));
     }
 

@@ -412,6 +412,41 @@ sbr_status sbr_recommend(sbr_model* m, const uint64_t* user_ptr, const uint32_t*
 sbr_status sbr_recommend_reps(sbr_model* m, const float* reps, uint64_t num_users, uint32_t k,
                               const uint64_t* excl_ptr, const uint32_t* excl_items, uint32_t* out_items, float* out_scores);
 
+/* Diversified top-k: a greedy maximal-marginal-relevance (MMR) selection of k items from the pool of a user's best `pool` items (no
+ * counterpart in the reference crate: recommend(k = pool) to the host, the pool's rows after it, and a loop per user).  With
+ * chain_dot, n2[i] and r[i] exactly as in sbr_similar_items below (SBR_SIMILAR_DOT: r == 1.0f), per user:
+ *   POOL       c_0 .. c_{n-1} with scores s_0 .. s_{n-1}: the non-padding entries of the row sbr_recommend / sbr_recommend_reps /
+ *              sbr_sessions_recommend returns with k = pool — the same masking, order and score bits — so n <= pool.
+ *   SIMILARITY of a picked item a to a pool item j: sim(a, j) = chain_dot(E[a] * r[a], E[c_j]) * r[c_j], which is
+ *              sbr_similar_items' s(q = a, i = c_j) with the picked item as the query.  Bit-wise it is not symmetric: the
+ *              definition fixes the direction.
+ *   SELECTION  lam = trade_off, mu = 1.0f - lam (one f32 subtraction).  Pick 0 is pool position 0.  After pick t (position a_t)
+ *              every unpicked j has m_j = sim(a_t, j) at t = 0 and m_j = max(m_j, sim(a_t, j)) after that, and pick t + 1 is the
+ *              unpicked j that maximises v_j = (lam * s_j) - (mu * m_j): both products and the subtraction each rounded to f32, no
+ *              fused multiply-add; ties to the lower pool position; -0.0 == +0.0 in the max and in the comparison.  It stops after
+ *              min(k, n) picks; the similarities of the last pick are not needed and take no part in the error rule below.
+ *   OUTPUT     row u of out_items / out_scores (optional), [num_users][k]: the picked items in pick order with their pool scores s
+ *              (sbr_predict's bits), padded with (0xFFFFFFFF, -inf) from n on.
+ * So trade_off == 1.0f gives sbr_recommend(k)'s row bit for bit, pool == k a permutation of it, and with trade_off == 0 the scores
+ * only break ties.  metric: SBR_SIMILAR_COSINE or SBR_SIMILAR_DOT; flags: SBR_RECOMMEND_INCLUDE_HISTORY only; histories,
+ * representations and exclusion lists as the plain calls take them.
+ * A user's pool lives in one workgroup's LDS: pool <= sbr_recommend_diverse_max_pool = min(1024, 32768 / storage width), i.e. 1 024
+ * up to embedding_dim 32, 512 up to 64, 256 up to 128, 128 up to 256.  There is no path for a larger pool.
+ * SBR_ERR_INVALID_ARGUMENT: k < 1, pool < k, pool > sbr_recommend_diverse_max_pool, trade_off outside [0, 1] or NaN, an unknown
+ * metric or flag, and wherever the plain call gives it.  SBR_ERR_INVALID_PREDICTION: wherever the pool's scan gives it, and when a
+ * value the selection uses is non-finite — n2 of a pool item (COSINE), or sim of a picked item against a not yet picked pool item;
+ * a non-finite row outside every pool, with finite scores, does not fail the call.  num_users == 0: nothing is done, SBR_OK.
+ * Deterministic; reads parameters only; runs on every model sbr_recommend runs on.  The session form (declared with the session
+ * store below) is refused while the store is stale, as sbr_sessions_recommend is. */
+#define SBR_DIVERSE_MAX_POOL 1024u
+sbr_status sbr_recommend_diverse_max_pool(const sbr_model* m, uint32_t* out);
+sbr_status sbr_recommend_diverse(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users,
+                                 uint32_t k, uint32_t pool, float trade_off, uint32_t metric, uint32_t flags,
+                                 uint32_t* out_items, float* out_scores);
+sbr_status sbr_recommend_diverse_reps(sbr_model* m, const float* reps, uint64_t num_users, uint32_t k, uint32_t pool,
+                                      float trade_off, uint32_t metric, const uint64_t* excl_ptr, const uint32_t* excl_items,
+                                      uint32_t* out_items, float* out_scores);
+
 /* Exact top-k neighbours of catalogue items: "which items are like this one" (no counterpart in the reference crate: the whole
  * item table to the host, normalised and sorted there).  With E the item-embedding table — one table, shared by the input side and
  * the scoring side — and chain_dot(x, y) the k-ascending fused-multiply-add chain from +0.0 that sbr_predict uses:
@@ -554,6 +589,10 @@ sbr_status sbr_sessions_recommend(sbr_sessions* st, const uint32_t* slots, uint6
                                   const uint32_t* excl_items, uint32_t flags, uint32_t* out_items, float* out_scores);
 sbr_status sbr_sessions_score_candidates(sbr_sessions* st, const uint32_t* slots, uint64_t n, const uint64_t* cand_ptr,
                                          const uint32_t* cand_items, float* out_scores);
+/* sbr_recommend_diverse_reps on sbr_sessions_representations of the same slots, the scan reading the store's rows in place */
+sbr_status sbr_sessions_recommend_diverse(sbr_sessions* st, const uint32_t* slots, uint64_t n, uint32_t k, uint32_t pool,
+                                          float trade_off, uint32_t metric, const uint64_t* excl_ptr, const uint32_t* excl_items,
+                                          uint32_t* out_items, float* out_scores);
 
 /* ≙ the serde derives (lstm.rs:204,386; ewma.rs:208,401): element counts and raw access. */
 sbr_status sbr_model_param_count(const sbr_model* m, int32_t which, uint64_t* out_count);

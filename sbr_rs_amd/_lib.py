@@ -78,6 +78,9 @@ def load():
         "sbr_mrr_score": [vp, vp, vp, C.c_uint64, fp, vp, u64p],
         "sbr_recommend": [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp],
         "sbr_recommend_reps": [vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp],
+        "sbr_recommend_diverse_max_pool": [vp, u32p],
+        "sbr_recommend_diverse": [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, C.c_uint32, vp, vp],
+        "sbr_recommend_diverse_reps": [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, vp, vp, vp, vp],
         "sbr_similar_items": [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp],
         "sbr_user_representations": [vp, vp, vp, C.c_uint64, vp],
         "sbr_score_candidates": [vp, vp, vp, C.c_uint64, vp, vp, vp],
@@ -146,6 +149,7 @@ def load():
         "sbr_sessions_set_state": [vp, vp, C.c_uint64, vp, vp, vp],
         "sbr_sessions_recommend": [vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint32, vp, vp],
         "sbr_sessions_score_candidates": [vp, vp, C.c_uint64, vp, vp, vp],
+        "sbr_sessions_recommend_diverse": [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, vp, vp, vp, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -197,4 +201,5 @@ DECLARED_SYMBOLS = [
     "sbr_sessions_create", "sbr_sessions_destroy", "sbr_sessions_capacity", "sbr_sessions_reset", "sbr_sessions_reset_all",
     "sbr_sessions_append", "sbr_sessions_lengths", "sbr_sessions_representations", "sbr_sessions_get_state", "sbr_sessions_set_state",
     "sbr_sessions_recommend", "sbr_sessions_score_candidates",
+    "sbr_recommend_diverse_max_pool", "sbr_recommend_diverse", "sbr_recommend_diverse_reps", "sbr_sessions_recommend_diverse",
 ]

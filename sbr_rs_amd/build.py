@@ -99,6 +99,15 @@ def build_similar_tests(force: bool = False, verbose: bool = True) -> str:
     return _build_cpp_program(SIMILAR_SRC, SIMILAR_BIN, force, verbose)
 
 
+DIVERSE_SRC = os.path.join(REPO, "tests", "cpp", "diverse_tests.cpp")
+DIVERSE_BIN = os.path.join(REPO, "tests", "cpp", "_build", "diverse_tests")
+
+
+def build_diverse_tests(force: bool = False, verbose: bool = True) -> str:
+    """g++ build of the C++ host layer's recommend_diverse test program."""
+    return _build_cpp_program(DIVERSE_SRC, DIVERSE_BIN, force, verbose)
+
+
 CANDIDATES_SRC = os.path.join(REPO, "tests", "cpp", "candidates_tests.cpp")
 CANDIDATES_BIN = os.path.join(REPO, "tests", "cpp", "_build", "candidates_tests")
 
@@ -132,5 +141,6 @@ if __name__ == "__main__":
     print(build_recommend_tests(force="--force" in sys.argv))
     print(build_ranking_tests(force="--force" in sys.argv))
     print(build_similar_tests(force="--force" in sys.argv))
+    print(build_diverse_tests(force="--force" in sys.argv))
     print(build_candidates_tests(force="--force" in sys.argv))
     print(build_sessions_tests(force="--force" in sys.argv))

@@ -17,6 +17,8 @@
  *   item_rnorm_kernel      : similar_items' r[i] = 1 / sqrt(chain_dot(E[i], E[i])) (0 for a zero row) of the whole catalogue
  *   similar_query_kernel   : similar_items' scan rows H[j] = E[q_j] * r[q_j]; the scan is topk_gemm_kernel with the ScaleMul
  *                            score policy, s(q, i) = chain_dot(H[j], E[i]) * r[i], r in the bias's place
+ *   diverse_select_kernel  : recommend_diverse's greedy maximal-marginal-relevance picks from topk_merge_kernel's rows at k = pool:
+ *                            one workgroup per user, the pool's rows in LDS
  *   subset_gather_kernel   : recommend_among's sub-table E'[j] = E[S[j]], b'[j] = b[S[j]] of a sorted, unique item set S; the scan is
  *                            topk_gemm_kernel + topk_merge_kernel on a ModelView of E', b', |S|, and
  *   subset_ids_kernel      : maps the merged lists' positions in S back to catalogue ids
@@ -31,6 +33,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
 #include <cstdlib>
 
 #include "sbr_device.h"
@@ -813,6 +816,148 @@ __global__ __launch_bounds__(256) void similar_query_kernel(ModelView m, const f
 }
 
 // ------------------------------------------------------------------------------------------------
+// recommend_diverse: greedy maximal-marginal-relevance selection of k_out items from the pool of a user's best `pool`
+// ------------------------------------------------------------------------------------------------
+/* One workgroup per user.  Its pool is row u of topk_merge_kernel's output at k = pool: n real entries, best first, then padding.
+ * Dynamic LDS, sized by the launch's pool (not the largest one, so small pools keep several workgroups on a CU):
+ *     qh [D]            the last pick's row scaled by its r (similar_items' qhat)
+ *     X  [pool][D + 1]  the pool's rows, gathered by id once: whole 16-byte pieces, streaming (every row is read once per user);
+ *                       rows D + 1 floats apart (ItemTiles' stride), so lanes that own different rows read different banks
+ *     id, s, mx, r, pk [pool]   ids, pool scores, the running maximum similarity to the picks, reciprocal norms, picked flags
+ *     red [8]           the waves' (value, position) of a round's arg-max
+ * r is item_rnorm_kernel's formula over the pool's rows only (a non-finite row outside every pool does not matter here), all 1.0f
+ * for the dot metric.  Thread tid owns the pool positions tid, tid + 256, ...: in each round it runs similar_items' score of the
+ * last pick a against its unpicked rows, sim = chain_dot(E[a] * r[a], E[c_j]) * r[c_j] with k ascending from +0.0, folds it into
+ * mx, and offers v = lam * s - mu * mx — two products and a difference, each rounded to f32 — to the arg-max (value descending,
+ * position ascending: a total order, v is never NaN while s and mx are finite and lam, mu lie in [0, 1]).  Pick 0 is position 0; the
+ * similarities of the last pick are not computed.  A non-finite squared norm (cosine) or sim raises the flag. */
+template <int D>
+__global__ __launch_bounds__(256) void diverse_select_kernel(ModelView m, const uint32_t* pool_items, const float* pool_scores, uint32_t pool,
+                                                             uint32_t k_out, float lam, int cosine, uint32_t* out_items, float* out_scores,
+                                                             uint32_t* nonfinite_flag) {
+    constexpr int LD = D + 1;
+    constexpr int QPR = D / 4; /* 16-byte pieces per row */
+    extern __shared__ float dv_lds[];
+    float* qh = dv_lds;
+    float* X = qh + D;
+    uint32_t* ids = reinterpret_cast<uint32_t*>(X + (size_t)pool * LD);
+    float* sc = reinterpret_cast<float*>(ids + pool);
+    float* mx = sc + pool;
+    float* rn = mx + pool;
+    uint32_t* pk = reinterpret_cast<uint32_t*>(rn + pool);
+    uint32_t* red = pk + pool;
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = tid >> 6;
+    const size_t u = blockIdx.x;
+    if (tid == 0) red[0] = 0;
+    __syncthreads();
+    uint32_t mine = 0; /* real entries among this thread's positions; the real entries are a prefix of the row */
+    for (uint32_t j = tid; j < pool; j += 256) {
+        const uint32_t id = pool_items[u * pool + j];
+        ids[j] = id;
+        sc[j] = pool_scores[u * pool + j];
+        pk[j] = 0;
+        mine += id != TK_NONE ? 1u : 0u;
+    }
+    if (mine) atomicAdd(&red[0], mine);
+    __syncthreads();
+    const uint32_t np = red[0]; /* the pool's size n; red is written again only behind the gather's barrier */
+    /* the gather: piece idx = row idx / QPR, quad idx % QPR; four loads in flight per thread */
+    const uint32_t pieces = np * QPR;
+    for (uint32_t base = 0; base < pieces; base += 4 * 256) {
+        float4 ev[4];
+#pragma unroll
+        for (int it = 0; it < 4; ++it) {
+            const uint32_t idx = base + it * 256 + tid;
+            const uint32_t id = idx < pieces ? ids[idx / QPR] : TK_NONE;
+            ev[it] = id < m.num_items ? ld4s(m.E + (size_t)id * D + (idx % QPR) * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+#pragma unroll
+        for (int it = 0; it < 4; ++it) {
+            const uint32_t idx = base + it * 256 + tid;
+            if (idx < pieces) {
+                float* dst = &X[(size_t)(idx / QPR) * LD + (idx % QPR) * 4];
+                dst[0] = ev[it].x; dst[1] = ev[it].y; dst[2] = ev[it].z; dst[3] = ev[it].w;
+            }
+        }
+    }
+    __syncthreads();
+    bool bad = false;
+    for (uint32_t j = tid; j < np; j += 256) {
+        float r = 1.0f;
+        if (cosine) {
+            const float* x = &X[(size_t)j * LD];
+            float n2 = 0.0f;
+#pragma unroll 8
+            for (int k = 0; k < D; ++k) n2 = sbr_fma(x[k], x[k], n2);
+            bad |= !(n2 - n2 == 0.0f);
+            r = n2 > 0.0f ? 1.0f / __builtin_sqrtf(n2) : 0.0f;
+        }
+        rn[j] = r;
+    }
+    const uint32_t picks = k_out < np ? k_out : np;
+    const float mu = 1.0f - lam;
+    uint32_t a = 0; /* the last pick's position */
+    for (uint32_t t = 0; t < picks; ++t) {
+        if (t > 0) {
+            __syncthreads(); /* rn (first round), pk and the last round's reads of qh and red */
+            if (tid < D) qh[tid] = X[(size_t)a * LD + tid] * rn[a];
+            __syncthreads();
+            float bv = -INFINITY;
+            uint32_t bp = TK_NONE;
+            for (uint32_t j = tid; j < np; j += 256) {
+                if (pk[j]) continue;
+                const float* x = &X[(size_t)j * LD];
+                float acc = 0.0f;
+#pragma unroll 8
+                for (int k4 = 0; k4 < D; k4 += 4) {
+                    const float4 q = ld4(&qh[k4]);
+                    acc = sbr_fma(q.x, x[k4 + 0], acc);
+                    acc = sbr_fma(q.y, x[k4 + 1], acc);
+                    acc = sbr_fma(q.z, x[k4 + 2], acc);
+                    acc = sbr_fma(q.w, x[k4 + 3], acc);
+                }
+                const float sim = acc * rn[j];
+                bad |= !(sim - sim == 0.0f);
+                const float mj = t == 1 ? sim : fmaxf(mx[j], sim);
+                mx[j] = mj;
+                float v = __fsub_rn(__fmul_rn(lam, sc[j]), __fmul_rn(mu, mj));
+                if (!(v == v)) v = -INFINITY; /* only behind a non-finite sim, which fails the call: the order stays total */
+                if (v > bv || bp == TK_NONE) { bv = v; bp = j; } /* j ascends: an equal value keeps the lower position */
+            }
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) {
+                const float ov = __shfl_xor(bv, off, 64);
+                const uint32_t op = (uint32_t)__shfl_xor((int)bp, off, 64);
+                if (tk_better(ov, op, bv, bp)) { bv = ov; bp = op; }
+            }
+            if (lane == 0) {
+                red[2 * wave] = __float_as_uint(bv);
+                red[2 * wave + 1] = bp;
+            }
+            __syncthreads();
+            bv = __uint_as_float(red[0]);
+            bp = red[1];
+#pragma unroll
+            for (int w = 1; w < 4; ++w)
+                if (tk_better(__uint_as_float(red[2 * w]), red[2 * w + 1], bv, bp)) { bv = __uint_as_float(red[2 * w]); bp = red[2 * w + 1]; }
+            a = bp; /* every thread holds the same winner; it exists: t < picks <= np leaves an unpicked position */
+        }
+        if (tid == 0) {
+            pk[a] = 1;
+            out_items[u * k_out + t] = ids[a];
+            if (out_scores) out_scores[u * k_out + t] = sc[a];
+        }
+    }
+    for (uint32_t t = picks + tid; t < k_out; t += 256) {
+        out_items[u * k_out + t] = TK_NONE;
+        if (out_scores) out_scores[u * k_out + t] = -INFINITY;
+    }
+    if (__any(bad) && lane == 0) atomicOr(nonfinite_flag, 1u);
+}
+
+// ------------------------------------------------------------------------------------------------
 // recommend_among: the sub-table of an item set S and the way back from positions in S to catalogue ids
 // ------------------------------------------------------------------------------------------------
 /* E'[j] = E[S[j]] at storage width and b'[j] = b[S[j]]: one thread per 16-byte quad, so a row's D / 4 threads are neighbours and
@@ -992,6 +1137,33 @@ void launch_recommend(const ModelView& m, const float* reps, const int* rep_row,
         hipLaunchKernelGGL((topk_gemm_kernel<DD, BiasAdd>), dim3(utiles, groups), dim3(256), 0, s, m, reps, rep_row, num_users, excl_ptr, excl_items,
                            per, k, lists, lens, nonfinite_flag);
         hipLaunchKernelGGL(topk_merge_kernel, dim3(num_users), dim3(512), 0, s, lists, lens, groups, k, n, out_items, out_scores);
+    });
+}
+
+uint32_t diverse_max_pool(int d) {
+    // the pool's rows at most 32 768 floats (128 KiB); the padding column, ids, scores, maxima, norms and flags of such a pool fit
+    // in what is left of the CU's 160 KiB: 256 rows at d = 128, 128 at d = 256, 1 024 (recommend's largest k) up to d = 32
+    const uint32_t p = 32768u / (uint32_t)d;
+    return p < 1024u ? p : 1024u;
+}
+
+void launch_diverse_select(const ModelView& m, const uint32_t* pool_items, const float* pool_scores, uint32_t num_users, uint32_t pool,
+                           uint32_t k_out, float trade_off, bool cosine, uint32_t* out_items, float* out_scores, uint32_t* nonfinite_flag,
+                           hipStream_t s) {
+    if (num_users == 0) return;
+    /* qh + X + (id, s, mx, r, pk) + red: diverse_select_kernel's layout */
+    const size_t lds = ((size_t)m.d + (size_t)pool * (m.d + 1) + 5 * (size_t)pool + 8) * 4;
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    dev = dev >= 0 && dev < 64 ? dev : 0;
+    DISPATCH_D(m.d, {
+        static std::atomic<size_t> granted[64]; /* dynamic LDS beyond 64 KB is granted per kernel and device, once */
+        if (lds > granted[dev]) {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(diverse_select_kernel<DD>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            granted[dev] = lds;
+        }
+        hipLaunchKernelGGL((diverse_select_kernel<DD>), dim3(num_users), dim3(256), lds, s, m, pool_items, pool_scores, pool, k_out, trade_off,
+                           cosine ? 1 : 0, out_items, out_scores, nonfinite_flag);
     });
 }
 

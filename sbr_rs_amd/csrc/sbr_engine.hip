@@ -3924,11 +3924,20 @@ void lists_to_subset_positions(const std::vector<uint32_t>& subset, std::vector<
     list_items->resize(w);
 }
 
+/* recommend_diverse's selection behind a scan: k_out of the scan's k (the pool) per user, by greedy maximal marginal relevance */
+struct Diverse {
+    uint32_t k_out;
+    float trade_off;
+    uint32_t metric;
+};
+
 /* top-k of every user of `s`, in chunks; results to out_items / out_scores (host, num_users x k; scores optional).  With item rows
  * (similar_items: the users are the queries) the launch makes the rows itself and ranks by cosine, or by the plain dot product.
- * With `subset` (recommend_among: sorted, unique, not empty) only its items are scanned, as a sub-table every launch gathers. */
+ * With `subset` (recommend_among: sorted, unique, not empty) only its items are scanned, as a sub-table every launch gathers.
+ * With `dv` (recommend_diverse; not with item rows or a subset) the scan's rows are the users' pools: the same launch selects
+ * dv->k_out of each, and the results are num_users x dv->k_out. */
 sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, uint32_t k, uint32_t* out_items, float* out_scores,
-                          bool cosine = false, const std::vector<uint32_t>* subset = nullptr) {
+                          bool cosine = false, const std::vector<uint32_t>* subset = nullptr, const Diverse* dv = nullptr) {
     std::vector<uint64_t> users(num_users);
     for (uint64_t u = 0; u < num_users; ++u) users[u] = u;
     const uint32_t scanned_items = subset ? (uint32_t)subset->size() : (uint32_t)m->hp.num_items;
@@ -3939,10 +3948,16 @@ sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, 
         TopkBufs tb;
         SubsetBufs sb;
         float* rnorm = nullptr; /* item rows: the catalogue's reciprocal norms, once per chunk (the arena does not outlive a carve) */
+        uint32_t* dv_items = nullptr; /* dv: the selection's rows, nu x dv->k_out */
+        float* dv_scores = nullptr;
         SBRCHK(user_reps(m, s, ch.users, [&](DeviceArena& ar) {
             tb.carve(ar, scanned_items, nu, ur.b.list_items.size(), k);
             if (s.item_rows) rnorm = ar.take<float>(m->hp.num_items);
             if (subset) sb.carve(ar, subset->size(), (size_t)m->d);
+            if (dv) {
+                dv_items = ar.take<uint32_t>(nu * dv->k_out);
+                dv_scores = ar.take<float>(nu * dv->k_out);
+            }
         }, &ur));
         const bool excl = !ur.b.list_ptr.empty();
         if (subset) {
@@ -3955,8 +3970,14 @@ sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, 
             if (!ur.b.list_items.empty())
                 HIPCHK(hipMemcpyAsync(tb.excl, ur.b.list_items.data(), ur.b.list_items.size() * 4, hipMemcpyHostToDevice, m->stream));
         }
-        SBRCHK(scan_launch(m, s.item_rows || subset ? 4 : 2, tb.flag, [&] {
-            if (subset)
+        const size_t ko = dv ? dv->k_out : k; /* the width of the rows that leave */
+        SBRCHK(scan_launch(m, s.item_rows || subset ? 4 : dv ? 3 : 2, tb.flag, [&] {
+            if (dv) { /* the selection reads the pool's scores whether or not the caller wants any */
+                sbr::launch_recommend(m->mv, ur.H, tb.rep, (uint32_t)nu, excl ? tb.eptr : nullptr, tb.excl, k, tb.lists, tb.lens, tb.items,
+                                      tb.scores, tb.flag, m->stream);
+                sbr::launch_diverse_select(m->mv, tb.items, tb.scores, (uint32_t)nu, k, dv->k_out, dv->trade_off, dv->metric == SBR_SIMILAR_COSINE,
+                                           dv_items, out_scores ? dv_scores : nullptr, tb.flag, m->stream);
+            } else if (subset)
                 sbr::launch_recommend_among(m->mv, sb.ids, scanned_items, sb.E, sb.b, ur.H, tb.rep, (uint32_t)nu, excl ? tb.eptr : nullptr, tb.excl,
                                             k, tb.lists, tb.lens, tb.items, out_scores ? tb.scores : nullptr, tb.flag, m->stream);
             else if (s.item_rows)
@@ -3965,7 +3986,8 @@ sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, 
             else
                 sbr::launch_recommend(m->mv, ur.H, tb.rep, (uint32_t)nu, excl ? tb.eptr : nullptr, tb.excl, k, tb.lists, tb.lens, tb.items,
                                       out_scores ? tb.scores : nullptr, tb.flag, m->stream);
-        }, {{out_items + ch.c0 * k, tb.items, nu * k * 4}, {out_scores ? out_scores + ch.c0 * k : nullptr, tb.scores, nu * k * 4}}));
+        }, {{out_items + ch.c0 * ko, dv ? dv_items : tb.items, nu * ko * 4},
+            {out_scores ? out_scores + ch.c0 * ko : nullptr, dv ? dv_scores : tb.scores, nu * ko * 4}}));
     }
     return SBR_OK;
 }
@@ -3997,6 +4019,50 @@ sbr_status sbr_recommend_reps(sbr_model* m, const float* reps, uint64_t num_user
     SBRCHK(enter_reader(m));
     if (excl_ptr) SBRCHK(check_csr(m, excl_ptr, num_users, excl_items, false));
     return recommend_scan(m, RepSource{excl_ptr, excl_items, reps, 0, true}, num_users, k, out_items, out_scores);
+}
+
+/* ---------------------------------------------------------------------------------------------
+ * diversified top-k: recommend's scan at k = pool, then the selection (sbr_catalogue.hip)
+ * ------------------------------------------------------------------------------------------- */
+namespace {
+
+/* the arguments the three recommend_diverse calls share */
+bool diverse_args_ok(const sbr_model* m, uint32_t k, uint32_t pool, float trade_off, uint32_t metric) {
+    return k >= 1 && pool >= k && pool <= sbr::diverse_max_pool(m->d) && trade_off >= 0.0f && trade_off <= 1.0f /* false for a NaN */ &&
+           metric <= SBR_SIMILAR_DOT;
+}
+
+}  // namespace
+
+sbr_status sbr_recommend_diverse_max_pool(const sbr_model* m, uint32_t* out) {
+    if (!m || !out) return SBR_ERR_INVALID_ARGUMENT;
+    *out = sbr::diverse_max_pool(m->d);
+    return SBR_OK;
+}
+
+sbr_status sbr_recommend_diverse(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users, uint32_t k, uint32_t pool,
+                                 float trade_off, uint32_t metric, uint32_t flags, uint32_t* out_items, float* out_scores) {
+    if (!m || !user_ptr || (num_users && !out_items)) return SBR_ERR_INVALID_ARGUMENT;
+    if (!diverse_args_ok(m, k, pool, trade_off, metric) || (flags & ~SBR_RECOMMEND_INCLUDE_HISTORY)) return SBR_ERR_INVALID_ARGUMENT;
+    std::lock_guard<std::mutex> lock(m->mu);
+    SBRCHK(enter_reader(m));
+    SBRCHK(check_csr(m, user_ptr, num_users, item_ids, false));
+    const Diverse dv{k, trade_off, metric};
+    return recommend_scan(m, RepSource{user_ptr, item_ids, nullptr, 0, !(flags & SBR_RECOMMEND_INCLUDE_HISTORY)}, num_users, pool, out_items,
+                          out_scores, false, nullptr, &dv);
+}
+
+sbr_status sbr_recommend_diverse_reps(sbr_model* m, const float* reps, uint64_t num_users, uint32_t k, uint32_t pool, float trade_off,
+                                      uint32_t metric, const uint64_t* excl_ptr, const uint32_t* excl_items, uint32_t* out_items,
+                                      float* out_scores) {
+    if (!m || (num_users && (!reps || !out_items))) return SBR_ERR_INVALID_ARGUMENT;
+    if (!diverse_args_ok(m, k, pool, trade_off, metric)) return SBR_ERR_INVALID_ARGUMENT;
+    if (!excl_args_ok(excl_ptr, excl_items, num_users)) return SBR_ERR_INVALID_ARGUMENT;
+    std::lock_guard<std::mutex> lock(m->mu);
+    SBRCHK(enter_reader(m));
+    if (excl_ptr) SBRCHK(check_csr(m, excl_ptr, num_users, excl_items, false));
+    const Diverse dv{k, trade_off, metric};
+    return recommend_scan(m, RepSource{excl_ptr, excl_items, reps, 0, true}, num_users, pool, out_items, out_scores, false, nullptr, &dv);
 }
 
 /* ---------------------------------------------------------------------------------------------
@@ -4565,6 +4631,25 @@ sbr_status sbr_sessions_recommend(sbr_sessions* st, const uint32_t* slots, uint6
     s.dev_rows = st->v.H;
     s.dev_row = rows.data();
     return recommend_scan(m, s, n, k, out_items, out_scores);
+}
+
+sbr_status sbr_sessions_recommend_diverse(sbr_sessions* st, const uint32_t* slots, uint64_t n, uint32_t k, uint32_t pool, float trade_off,
+                                          uint32_t metric, const uint64_t* excl_ptr, const uint32_t* excl_items, uint32_t* out_items,
+                                          float* out_scores) {
+    if (!st || (n && !out_items)) return SBR_ERR_INVALID_ARGUMENT;
+    if (!diverse_args_ok(st->m, k, pool, trade_off, metric)) return SBR_ERR_INVALID_ARGUMENT;
+    if (!excl_args_ok(excl_ptr, excl_items, n)) return SBR_ERR_INVALID_ARGUMENT;
+    sbr_model* m = st->m;
+    std::lock_guard<std::mutex> lock(m->mu);
+    SBRCHK(enter_sessions(st));
+    SBRCHK(check_slots(st, slots, n));
+    if (excl_ptr) SBRCHK(check_csr(m, excl_ptr, n, excl_items, false));
+    const std::vector<int> rows = session_rep_rows(st, slots, n);
+    RepSource s{excl_ptr, excl_items, nullptr, 0, true};
+    s.dev_rows = st->v.H;
+    s.dev_row = rows.data();
+    const Diverse dv{k, trade_off, metric};
+    return recommend_scan(m, s, n, pool, out_items, out_scores, false, nullptr, &dv);
 }
 
 sbr_status sbr_sessions_score_candidates(sbr_sessions* st, const uint32_t* slots, uint64_t n, const uint64_t* cand_ptr,

@@ -289,6 +289,15 @@ uint32_t recommend_groups(uint32_t num_users, uint32_t num_items, uint32_t k, ui
 void launch_recommend(const ModelView& m, const float* reps, const int* rep_row, uint32_t num_users, const uint64_t* excl_ptr,
                       const uint32_t* excl_items, uint32_t k, uint2* lists, uint32_t* lens, uint32_t* out_items, float* out_scores,
                       uint32_t* nonfinite_flag, hipStream_t s);
+/* greedy maximal-marginal-relevance selection (sbr_catalogue.hip, diverse_select_kernel; the contract: sbr_recommend_diverse in
+ * include/sbr_hip.h): pool_items / pool_scores [num_users][pool] are launch_recommend's outputs at k = pool; out_items / out_scores
+ * [num_users][k_out] the picks in pick order with their pool scores, padded as the pool's rows.  1 <= k_out <= pool <=
+ * diverse_max_pool(d): a user's pool lives in one workgroup's LDS.  Raises the flag for a non-finite squared norm of a pool row
+ * (cosine) or a non-finite similarity the selection uses. */
+uint32_t diverse_max_pool(int d);
+void launch_diverse_select(const ModelView& m, const uint32_t* pool_items, const float* pool_scores, uint32_t num_users, uint32_t pool,
+                           uint32_t k_out, float trade_off, bool cosine, uint32_t* out_items, float* out_scores, uint32_t* nonfinite_flag,
+                           hipStream_t s);
 /* exact top-k neighbours of catalogue items (sbr_catalogue.hip): item_rnorm_kernel writes rnorm [num_items] (1 / |E[i]|, 0 for a zero
  * row; all 1.0f unless `cosine`) and raises the flag for a non-finite squared norm, similar_query_kernel writes the scan rows
  * H [num_queries][d] = E[query[j]] * rnorm[query[j]], and launch_recommend's two kernels rank s(j, i) = chain_dot(H[j], E[i]) *

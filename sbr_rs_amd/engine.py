@@ -33,6 +33,15 @@ def _check(st: int):
     raise EngineError(Status(st), msg)
 
 
+def _similar_metric(metric) -> int:
+    """"cosine" / "dot", or the C value as it is (the library refuses an unknown one)"""
+    if isinstance(metric, str):
+        if metric not in _SIMILAR_METRICS:
+            raise ValueError(f"metric {metric!r}: 'cosine' or 'dot'")
+        return _SIMILAR_METRICS[metric]
+    return int(metric) & 0xFFFFFFFF
+
+
 def _exclusion_csr(exclude, nu: int):
     """One sequence of item ids per user -> (ptr u64 [nu + 1], items u32, never empty: a one-element dummy stands in for no
     items at all); (None, None) for exclude = None."""
@@ -586,6 +595,42 @@ class Model:
                                           None if ei is None else _ptr(ei), _ptr(items), _ptr(scores)))
         return items, scores
 
+    def diverse_max_pool(self) -> int:
+        """The largest ``pool`` of recommend_diverse on this model (sbr_recommend_diverse_max_pool): a user's pool lives in one
+        workgroup's LDS, min(1024, 32768 / storage width) rows."""
+        n = C.c_uint32()
+        _check(self._L.sbr_recommend_diverse_max_pool(self._h, C.byref(n)))
+        return n.value
+
+    def recommend_diverse(self, user_ptr, item_ids, k: int, pool: int, trade_off: float = 0.5, metric="cosine",
+                          include_history: bool = False):
+        """Diversified top-k (sbr_recommend_diverse): from the ``pool`` best items of each history — recommend's row at k = pool —
+        k are picked greedily by maximal marginal relevance, trade_off * score - (1 - trade_off) * (the largest similarity to an
+        item picked before), the first pick being the best item.  Items [U, k] u32 in pick order and their scores [U, k] f32
+        (recommend's bits); short rows padded with (RECOMMEND_NO_ITEM, -inf).  metric: similar_items' "cosine" or "dot".
+        trade_off = 1 is recommend(k); pool == k reorders it.  k <= pool <= diverse_max_pool()."""
+        up = np.ascontiguousarray(user_ptr, dtype=np.uint64)
+        it = np.ascontiguousarray(item_ids, dtype=np.uint32)
+        nu = max(len(up) - 1, 0)
+        items = np.zeros((nu, max(int(k), 0)), dtype=np.uint32)
+        scores = np.zeros((nu, max(int(k), 0)), dtype=np.float32)
+        flags = RECOMMEND_INCLUDE_HISTORY if include_history else 0
+        _check(self._L.sbr_recommend_diverse(self._h, _ptr(up), _ptr(it), nu, int(k) & 0xFFFFFFFF, int(pool) & 0xFFFFFFFF, float(trade_off),
+                                             _similar_metric(metric), flags, _ptr(items), _ptr(scores)))
+        return items, scores
+
+    def recommend_diverse_reps(self, reps, k: int, pool: int, trade_off: float = 0.5, metric="cosine", exclude=None):
+        """As recommend_diverse, from representations [U, embedding_dim]; exclude: None or one sequence of item ids per user."""
+        reps = np.ascontiguousarray(reps, dtype=np.float32).reshape(-1, self.dim)
+        nu = reps.shape[0]
+        items = np.zeros((nu, max(int(k), 0)), dtype=np.uint32)
+        scores = np.zeros((nu, max(int(k), 0)), dtype=np.float32)
+        ep, ei = _exclusion_csr(exclude, nu)
+        _check(self._L.sbr_recommend_diverse_reps(self._h, _ptr(reps), nu, int(k) & 0xFFFFFFFF, int(pool) & 0xFFFFFFFF, float(trade_off),
+                                                  _similar_metric(metric), None if ep is None else _ptr(ep),
+                                                  None if ei is None else _ptr(ei), _ptr(items), _ptr(scores)))
+        return items, scores
+
     def similar_items(self, query_items, k: int, metric="cosine", include_self: bool = False, exclude=None):
         """Exact top-k neighbours of each query item among the whole catalogue (sbr_similar_items): items [Q, k] u32 and scores
         [Q, k] f32, score descending, ties to the lower id; short rows padded with (RECOMMEND_NO_ITEM, -inf).  metric: "cosine"
@@ -593,15 +638,12 @@ class Model:
         takes no part in either.  The query itself is left out of its row unless include_self; exclude: None or one sequence of
         item ids per query.  Queries may repeat."""
         q = np.ascontiguousarray(query_items, dtype=np.uint32).ravel()
-        if isinstance(metric, str):
-            if metric not in _SIMILAR_METRICS:
-                raise ValueError(f"metric {metric!r}: 'cosine' or 'dot'")
-            metric = _SIMILAR_METRICS[metric]
+        metric = _similar_metric(metric)
         nq = q.size
         items = np.zeros((nq, max(int(k), 0)), dtype=np.uint32)
         scores = np.zeros((nq, max(int(k), 0)), dtype=np.float32)
         ep, ei = _exclusion_csr(exclude, nq)
-        _check(self._L.sbr_similar_items(self._h, _ptr(q), nq, int(k) & 0xFFFFFFFF, int(metric) & 0xFFFFFFFF,
+        _check(self._L.sbr_similar_items(self._h, _ptr(q), nq, int(k) & 0xFFFFFFFF, metric,
                                          SIMILAR_INCLUDE_SELF if include_self else 0, None if ep is None else _ptr(ep),
                                          None if ei is None else _ptr(ei), _ptr(items), _ptr(scores)))
         return items, scores
@@ -806,6 +848,18 @@ class Sessions:
         ep, ei = _exclusion_csr(exclude, sl.size)
         _check(self._L.sbr_sessions_recommend(self._h, _ptr(sl), sl.size, int(k) & 0xFFFFFFFF, None if ep is None else _ptr(ep),
                                               None if ei is None else _ptr(ei), 0, _ptr(items), _ptr(scores)))
+        return items, scores
+
+    def recommend_diverse(self, slots, k: int, pool: int, trade_off: float = 0.5, metric="cosine", exclude=None):
+        """``Model.recommend_diverse_reps(self.representations(slots), k, pool, ...)`` with the scan reading the store's rows in
+        place: items [n, k] u32 in pick order, scores [n, k] f32."""
+        sl = self._slots(slots)
+        items = np.zeros((sl.size, max(int(k), 0)), dtype=np.uint32)
+        scores = np.zeros((sl.size, max(int(k), 0)), dtype=np.float32)
+        ep, ei = _exclusion_csr(exclude, sl.size)
+        _check(self._L.sbr_sessions_recommend_diverse(self._h, _ptr(sl), sl.size, int(k) & 0xFFFFFFFF, int(pool) & 0xFFFFFFFF,
+                                                      float(trade_off), _similar_metric(metric), None if ep is None else _ptr(ep),
+                                                      None if ei is None else _ptr(ei), _ptr(items), _ptr(scores)))
         return items, scores
 
     def score_candidates(self, slots, candidates):

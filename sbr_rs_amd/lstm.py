@@ -283,6 +283,18 @@ class _ImplicitSequenceModel:
         than k eligible items is padded with (0xFFFFFFFF, -inf)."""
         return self.params.similar_items(query_items, k, metric=metric, include_self=include_self, exclude=exclude)
 
+    def recommend_diverse(self, interactions_or_histories, k: int, pool=None, trade_off: float = 0.5, metric: str = "cosine",
+                          exclude_history: bool = True):
+        """``recommend`` without the near-duplicates, on the device: from each user's ``pool`` best items, k are picked greedily by
+        maximal marginal relevance — ``trade_off`` * score - (1 - ``trade_off``) * (the largest similarity to an item already
+        picked), similarity as ``similar_items`` measures it; the first pick is the best item.  (items [U, k] u32 in pick order,
+        scores [U, k] f32, ``recommend``'s bits.)  ``pool=None``: min(4 k, the largest pool the device holds for this embedding
+        width, ``params.diverse_max_pool()``); ``trade_off=1`` is ``recommend(k)``."""
+        up, it = self._csr(interactions_or_histories)
+        if pool is None:
+            pool = min(4 * int(k), self.params.diverse_max_pool())
+        return self.params.recommend_diverse(up, it, k, pool, trade_off=trade_off, metric=metric, include_history=not exclude_history)
+
     def sessions(self, capacity: int):
         """A session store of ``capacity`` slots on the device (``engine.Sessions``): each slot holds one user's recurrent state,
         ``append`` advances it by one cell step per item instead of re-running the whole history, and ``recommend`` /
