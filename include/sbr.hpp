@@ -492,6 +492,13 @@ struct Recommendations {
     std::vector<std::uint32_t> items;
     std::vector<float> scores;
 };
+/// The per-user tag filter of the *_filtered top-k calls (named methods, so that no braced argument of a plain form changes its
+/// meaning), against the model's item tags (ImplicitSequenceModel::set_item_tags): user u may see
+/// item i iff (tags[i] & none_of[u]) == 0 && (any_of[u] == 0 || (tags[i] & any_of[u]) != 0).  Each vector is empty (all zeros), holds
+/// one mask for every user, or one mask per user (query, slot) of the call.
+struct TagFilter {
+    std::vector<std::uint32_t> any_of, none_of;
+};
 /// What ImplicitSequenceModel::similar_items ranks by: the cosine of two item embeddings, or their plain dot product.
 enum class Similarity { Cosine = SBR_SIMILAR_COSINE, Dot = SBR_SIMILAR_DOT };
 /// The loss used for training the model (mod.rs:15-23).
@@ -508,6 +515,13 @@ namespace detail {
 
 inline void check(sbr_status st, const char* where) {
     if (st != SBR_OK) throw EngineError(st, where);
+}
+
+/// One mask vector of a TagFilter as the n words a *_filtered call takes (n == 0: one word, never read).
+inline std::vector<std::uint32_t> tag_masks(const std::vector<std::uint32_t>& mask, std::size_t n, const char* where) {
+    if (mask.size() > 1 && mask.size() != n) throw EngineError(SBR_ERR_INVALID_ARGUMENT, where);
+    if (mask.size() == n && n > 0) return mask;
+    return std::vector<std::uint32_t>(n ? n : 1, mask.empty() ? 0u : mask[0]);
 }
 
 inline std::vector<std::uint32_t> narrow(const std::vector<ItemId>& ids) {
@@ -613,6 +627,54 @@ class Sessions {
                                                              r.items.data(), r.scores.data());
         if (st == SBR_ERR_INVALID_PREDICTION) return Result<Recommendations, PredictionError>::Err(PredictionError::InvalidPredictionValue);
         check(st, "sbr_sessions_recommend_diverse");
+        return Result<Recommendations, PredictionError>::Ok(std::move(r));
+    }
+    /// `recommend` under a tag filter, one mask pair per slot of the call (sbr_sessions_recommend_filtered).
+    Result<Recommendations, PredictionError> recommend_filtered(const std::vector<std::uint32_t>& slots, std::size_t k, const TagFilter& filter,
+                                                       const std::vector<std::uint64_t>& excl_ptr = {},
+                                                       const std::vector<std::uint32_t>& excl_items = {}) const {
+        if (k < 1 || k > SBR_RECOMMEND_MAX_K) throw EngineError(SBR_ERR_INVALID_ARGUMENT, "Sessions::recommend: k outside 1..SBR_RECOMMEND_MAX_K");
+        if (!excl_ptr.empty() && (excl_ptr.size() != slots.size() + 1 || excl_ptr.back() > excl_items.size()))
+            throw EngineError(SBR_ERR_INVALID_ARGUMENT, "Sessions::recommend: one exclusion range per slot");
+        const std::vector<std::uint32_t> any = tag_masks(filter.any_of, slots.size(), "Sessions::recommend: one any_of mask per slot");
+        const std::vector<std::uint32_t> none_of = tag_masks(filter.none_of, slots.size(), "Sessions::recommend: one none_of mask per slot");
+        Recommendations r;
+        r.num_users = slots.size();
+        r.k = k;
+        r.items.resize(r.num_users * k);
+        r.scores.resize(r.num_users * k);
+        const std::uint32_t none = 0;
+        const sbr_status st = sbr_sessions_recommend_filtered(h_, slots.data(), (std::uint64_t)slots.size(), (std::uint32_t)k,
+                                                              excl_ptr.empty() ? nullptr : excl_ptr.data(),
+                                                              excl_ptr.empty() ? nullptr : (excl_items.empty() ? &none : excl_items.data()), 0u,
+                                                              any.data(), none_of.data(), r.items.data(), r.scores.data());
+        if (st == SBR_ERR_INVALID_PREDICTION) return Result<Recommendations, PredictionError>::Err(PredictionError::InvalidPredictionValue);
+        check(st, "sbr_sessions_recommend_filtered");
+        return Result<Recommendations, PredictionError>::Ok(std::move(r));
+    }
+    /// `recommend_diverse` under a tag filter: the pool holds eligible items only (sbr_sessions_recommend_diverse_filtered).
+    Result<Recommendations, PredictionError> recommend_diverse_filtered(const std::vector<std::uint32_t>& slots, std::size_t k, std::size_t pool,
+                                                               float trade_off, Similarity metric, const TagFilter& filter,
+                                                               const std::vector<std::uint64_t>& excl_ptr = {},
+                                                               const std::vector<std::uint32_t>& excl_items = {}) const {
+        if (k < 1 || pool < k || pool > SBR_DIVERSE_MAX_POOL)
+            throw EngineError(SBR_ERR_INVALID_ARGUMENT, "Sessions::recommend_diverse: 1 <= k <= pool <= SBR_DIVERSE_MAX_POOL");
+        if (!excl_ptr.empty() && (excl_ptr.size() != slots.size() + 1 || excl_ptr.back() > excl_items.size()))
+            throw EngineError(SBR_ERR_INVALID_ARGUMENT, "Sessions::recommend_diverse: one exclusion range per slot");
+        const std::vector<std::uint32_t> any = tag_masks(filter.any_of, slots.size(), "Sessions::recommend_diverse: one any_of mask per slot");
+        const std::vector<std::uint32_t> none_of = tag_masks(filter.none_of, slots.size(), "Sessions::recommend_diverse: one none_of mask per slot");
+        Recommendations r;
+        r.num_users = slots.size();
+        r.k = k;
+        r.items.resize(r.num_users * k);
+        r.scores.resize(r.num_users * k);
+        const std::uint32_t none = 0;
+        const sbr_status st = sbr_sessions_recommend_diverse_filtered(
+            h_, slots.data(), (std::uint64_t)slots.size(), (std::uint32_t)k, (std::uint32_t)pool, trade_off, (std::uint32_t)metric,
+            excl_ptr.empty() ? nullptr : excl_ptr.data(), excl_ptr.empty() ? nullptr : (excl_items.empty() ? &none : excl_items.data()),
+            any.data(), none_of.data(), r.items.data(), r.scores.data());
+        if (st == SBR_ERR_INVALID_PREDICTION) return Result<Recommendations, PredictionError>::Err(PredictionError::InvalidPredictionValue);
+        check(st, "sbr_sessions_recommend_diverse_filtered");
         return Result<Recommendations, PredictionError>::Ok(std::move(r));
     }
     /// One score per candidate, in candidate order, slot i's candidates cand_items[cand_ptr[i] .. cand_ptr[i + 1]) (sbr_sessions_score_candidates).
@@ -780,6 +842,44 @@ class ImplicitSequenceModel : public OnlineRankingModel<ImplicitUser> {
         return Result<Recommendations, PredictionError>::Ok(std::move(r));
     }
 
+    /// One 32-bit tag word per item, kept on the device for `recommend_filtered`, `recommend_diverse_filtered`,
+    /// `similar_items_filtered` and the Sessions forms (sbr_model_set_item_tags).  Serving metadata: `fit` leaves the tags alone, a session store stays usable,
+    /// and they are not part of a saved model — set them again after a restore.
+    void set_item_tags(const std::vector<std::uint32_t>& tags) {
+        if (tags.size() != (std::size_t)replicas_->hparams().num_items)
+            throw EngineError(SBR_ERR_INVALID_ARGUMENT, "set_item_tags: one tag word per item");
+        check(sbr_model_set_item_tags(replicas_->primary(), tags.data()), "sbr_model_set_item_tags");
+    }
+    /// The model has no tags again: the *_filtered calls throw EngineError(SBR_ERR_INVALID_ARGUMENT) until they are set.
+    void clear_item_tags() { check(sbr_model_set_item_tags(replicas_->primary(), nullptr), "sbr_model_set_item_tags"); }
+    /// The tag words last set; throws EngineError(SBR_ERR_INVALID_ARGUMENT) while the model has none.
+    std::vector<std::uint32_t> item_tags() const {
+        std::vector<std::uint32_t> out((std::size_t)replicas_->hparams().num_items);
+        check(sbr_model_get_item_tags(replicas_->primary(), out.data()), "sbr_model_get_item_tags");
+        return out;
+    }
+
+    /// `recommend` under a per-user tag filter (sbr_recommend_filtered): the exact top k of the items each user's masks allow, the
+    /// bits of `recommend` with every other item added to the user's exclusions; tested inside the scan.  Not with `among`.
+    Result<Recommendations, PredictionError> recommend_filtered(const data::CompressedInteractions& interactions, std::size_t k,
+                                                                bool exclude_history, const TagFilter& filter) const {
+        if (k < 1 || k > SBR_RECOMMEND_MAX_K) throw EngineError(SBR_ERR_INVALID_ARGUMENT, "recommend: k outside 1..SBR_RECOMMEND_MAX_K");
+        Recommendations r;
+        r.num_users = interactions.num_users();
+        r.k = k;
+        r.items.resize(r.num_users * k);
+        r.scores.resize(r.num_users * k);
+        const std::vector<std::uint32_t> any = tag_masks(filter.any_of, r.num_users, "recommend: one any_of mask per user");
+        const std::vector<std::uint32_t> none_of = tag_masks(filter.none_of, r.num_users, "recommend: one none_of mask per user");
+        const sbr_status st = sbr_recommend_filtered(replicas_->primary(), interactions.user_pointers().data(), interactions.item_ids().data(),
+                                                     (std::uint64_t)r.num_users, (std::uint32_t)k,
+                                                     exclude_history ? 0u : SBR_RECOMMEND_INCLUDE_HISTORY, any.data(), none_of.data(),
+                                                     r.items.data(), r.scores.data());
+        if (st == SBR_ERR_INVALID_PREDICTION) return Result<Recommendations, PredictionError>::Err(PredictionError::InvalidPredictionValue);
+        check(st, "sbr_recommend_filtered");
+        return Result<Recommendations, PredictionError>::Ok(std::move(r));
+    }
+
     /// `recommend` with every item outside `among` ineligible (sbr_recommend_among): the exact top k of that item set — ids in any
     /// order, duplicates allowed — as catalogue ids, ordered and padded as `recommend`'s rows.  Only the set's rows are scanned: an
     /// empty set gives rows of padding, and a non-finite score outside the set does not fail the call.
@@ -833,6 +933,30 @@ class ImplicitSequenceModel : public OnlineRankingModel<ImplicitUser> {
         return Result<Recommendations, PredictionError>::Ok(std::move(r));
     }
 
+    /// `recommend_diverse` under a per-user tag filter (sbr_recommend_diverse_filtered): the pool is the filtered row at k = pool.
+    Result<Recommendations, PredictionError> recommend_diverse_filtered(const data::CompressedInteractions& interactions, std::size_t k,
+                                                                        std::size_t pool, float trade_off, Similarity metric,
+                                                                        bool exclude_history, const TagFilter& filter) const {
+        if (pool == 0) pool = std::min<std::size_t>(4 * k, diverse_max_pool());
+        if (k < 1 || pool < k || pool > SBR_DIVERSE_MAX_POOL)
+            throw EngineError(SBR_ERR_INVALID_ARGUMENT, "recommend_diverse: 1 <= k <= pool <= SBR_DIVERSE_MAX_POOL");
+        Recommendations r;
+        r.num_users = interactions.num_users();
+        r.k = k;
+        r.items.resize(r.num_users * k);
+        r.scores.resize(r.num_users * k);
+        const std::vector<std::uint32_t> any = tag_masks(filter.any_of, r.num_users, "recommend_diverse: one any_of mask per user");
+        const std::vector<std::uint32_t> none_of = tag_masks(filter.none_of, r.num_users, "recommend_diverse: one none_of mask per user");
+        const sbr_status st = sbr_recommend_diverse_filtered(replicas_->primary(), interactions.user_pointers().data(),
+                                                             interactions.item_ids().data(), (std::uint64_t)r.num_users, (std::uint32_t)k,
+                                                             (std::uint32_t)pool, trade_off, (std::uint32_t)metric,
+                                                             exclude_history ? 0u : SBR_RECOMMEND_INCLUDE_HISTORY, any.data(), none_of.data(),
+                                                             r.items.data(), r.scores.data());
+        if (st == SBR_ERR_INVALID_PREDICTION) return Result<Recommendations, PredictionError>::Err(PredictionError::InvalidPredictionValue);
+        check(st, "sbr_recommend_diverse_filtered");
+        return Result<Recommendations, PredictionError>::Ok(std::move(r));
+    }
+
     /// `user_representation` of every history of `histories` in one device pass (sbr_user_representations): row-major
     /// [num_users][embedding_dim], row u with the bits of the single call on history u.
     std::vector<float> user_representations(const data::CompressedInteractions& histories) const {
@@ -879,6 +1003,27 @@ class ImplicitSequenceModel : public OnlineRankingModel<ImplicitUser> {
                                                 r.items.data(), r.scores.data());
         if (st == SBR_ERR_INVALID_PREDICTION) return Result<Recommendations, PredictionError>::Err(PredictionError::InvalidPredictionValue);
         check(st, "sbr_similar_items");
+        return Result<Recommendations, PredictionError>::Ok(std::move(r));
+    }
+
+    /// `similar_items` under a tag filter with one mask pair per query (sbr_similar_items_filtered): "similar items of the same
+    /// category" is any_of[j] = the tag word of items[j].
+    Result<Recommendations, PredictionError> similar_items_filtered(const std::vector<ItemId>& items, std::size_t k, Similarity metric,
+                                                                    bool include_self, const TagFilter& filter) const {
+        if (k < 1 || k > SBR_RECOMMEND_MAX_K) throw EngineError(SBR_ERR_INVALID_ARGUMENT, "similar_items: k outside 1..SBR_RECOMMEND_MAX_K");
+        const std::vector<std::uint32_t> ids = narrow(items);
+        Recommendations r;
+        r.num_users = ids.size();
+        r.k = k;
+        r.items.resize(r.num_users * k);
+        r.scores.resize(r.num_users * k);
+        const std::vector<std::uint32_t> any = tag_masks(filter.any_of, ids.size(), "similar_items: one any_of mask per query");
+        const std::vector<std::uint32_t> none_of = tag_masks(filter.none_of, ids.size(), "similar_items: one none_of mask per query");
+        const sbr_status st = sbr_similar_items_filtered(replicas_->primary(), ids.data(), (std::uint64_t)ids.size(), (std::uint32_t)k,
+                                                         (std::uint32_t)metric, include_self ? SBR_SIMILAR_INCLUDE_SELF : 0u, nullptr, nullptr,
+                                                         any.data(), none_of.data(), r.items.data(), r.scores.data());
+        if (st == SBR_ERR_INVALID_PREDICTION) return Result<Recommendations, PredictionError>::Err(PredictionError::InvalidPredictionValue);
+        check(st, "sbr_similar_items_filtered");
         return Result<Recommendations, PredictionError>::Ok(std::move(r));
     }
 

@@ -472,6 +472,49 @@ sbr_status sbr_similar_items(sbr_model* m, const uint32_t* query_items, uint64_t
                              uint32_t metric, uint32_t flags, const uint64_t* excl_ptr, const uint32_t* excl_items,
                              uint32_t* out_items, float* out_scores);
 
+/* ITEM TAGS and per-user tag filters of the top-k scans: "only what this user may see" — territory, age rating, subscription tier,
+ * in stock, not this category (no counterpart in the reference crate: a larger k and a filter on the host, which is not exact).
+ * A model may hold item tags, tags[num_items], one 32-bit word per item, on its device; it has none until they are set.
+ *   sbr_model_set_item_tags   copies tags[0 .. num_items) to the device; tags == NULL clears them (the model has none again)
+ *   sbr_model_get_item_tags   out[0 .. num_items) = the words last set; SBR_ERR_INVALID_ARGUMENT while the model has none
+ * Tags are serving metadata, not parameters: sbr_model_fit and the other fits, sbr_model_set_param and a load through it do not
+ * touch them, setting them does not bump the parameter generation (a session store stays usable), and they are NOT PERSISTED — the
+ * parameter blocks a save writes do not hold them, so whoever restores a model sets its tags again.  They are freed with the model
+ * and live on the model's own device, so they work on a replica of a group and on a partitioned model wherever sbr_recommend runs.
+ *
+ * A *_filtered call is the plain call of the same name plus any_of[n] and none_of[n], one mask pair per user (query, slot) of the
+ * call in the call's order; either may be NULL, which means all zeros.  Item i is ALLOWED for user u iff
+ *     (tags[i] & none_of[u]) == 0 && (any_of[u] == 0 || (tags[i] & any_of[u]) != 0)
+ * and the result is BIT FOR BIT that of the plain call with user u's exclusion list extended by every item that is not allowed for
+ * u: items, score bits, order, padding with (0xFFFFFFFF, -inf), and the status.  So the non-finite rule is the plain call's — it
+ * covers every scanned score, of an allowed item or not, as it covers excluded items; with all masks zero the result is the plain
+ * call's; a user with no allowed item gets a row of padding.  For the diverse forms the pool is the filtered row at k = pool, as the
+ * POOL clause above defines it; for sbr_similar_items_filtered the masks are per query ("similar items of the same category"), and
+ * the query's own exclusion and SBR_SIMILAR_INCLUDE_SELF are the plain call's.  With histories the masks belong to the call's user
+ * u, not to its history: two users with one history may carry different masks.
+ * Nothing is materialised per user: the scan tests an item's tag word against the user's two mask words before the score is
+ * offered to the user's list, 4 bytes read beside each item row.
+ * SBR_ERR_INVALID_ARGUMENT: a filtered call on a model without tags (even with both masks NULL), and wherever the plain call gives
+ * it.  NOT BUILT: a filter together with sbr_recommend_among's subset (the tags would have to be gathered with the sub-table; there
+ * is no such entry point), sbr_rank_targets under a filter, and persistence of the tags. */
+sbr_status sbr_model_set_item_tags(sbr_model* m, const uint32_t* tags);
+sbr_status sbr_model_get_item_tags(sbr_model* m, uint32_t* out);
+sbr_status sbr_recommend_filtered(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users,
+                                  uint32_t k, uint32_t flags, const uint32_t* any_of, const uint32_t* none_of,
+                                  uint32_t* out_items, float* out_scores);
+sbr_status sbr_recommend_filtered_reps(sbr_model* m, const float* reps, uint64_t num_users, uint32_t k,
+                                       const uint64_t* excl_ptr, const uint32_t* excl_items,
+                                       const uint32_t* any_of, const uint32_t* none_of, uint32_t* out_items, float* out_scores);
+sbr_status sbr_recommend_diverse_filtered(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users,
+                                          uint32_t k, uint32_t pool, float trade_off, uint32_t metric, uint32_t flags,
+                                          const uint32_t* any_of, const uint32_t* none_of, uint32_t* out_items, float* out_scores);
+sbr_status sbr_recommend_diverse_filtered_reps(sbr_model* m, const float* reps, uint64_t num_users, uint32_t k, uint32_t pool,
+                                               float trade_off, uint32_t metric, const uint64_t* excl_ptr, const uint32_t* excl_items,
+                                               const uint32_t* any_of, const uint32_t* none_of, uint32_t* out_items, float* out_scores);
+sbr_status sbr_similar_items_filtered(sbr_model* m, const uint32_t* query_items, uint64_t num_queries, uint32_t k,
+                                      uint32_t metric, uint32_t flags, const uint64_t* excl_ptr, const uint32_t* excl_items,
+                                      const uint32_t* any_of, const uint32_t* none_of, uint32_t* out_items, float* out_scores);
+
 /* Recommend within an item subset, batched candidate scoring, batched representations (no counterparts in the reference crate:
  * loops over user_representation and predict, and a host-side filter).  Throughout, score(u, i) = bias[i] + chain_dot(rep_u, E[i])
  * has the bits of sbr_predict, and a history's representation is sbr_user_representation's (last max_sequence_length items; an
@@ -593,6 +636,14 @@ sbr_status sbr_sessions_score_candidates(sbr_sessions* st, const uint32_t* slots
 sbr_status sbr_sessions_recommend_diverse(sbr_sessions* st, const uint32_t* slots, uint64_t n, uint32_t k, uint32_t pool,
                                           float trade_off, uint32_t metric, const uint64_t* excl_ptr, const uint32_t* excl_items,
                                           uint32_t* out_items, float* out_scores);
+/* sbr_recommend_filtered_reps / sbr_recommend_diverse_filtered_reps on sbr_sessions_representations of the same slots: any_of /
+ * none_of [n], slot slots[i]'s pair at i (ITEM TAGS above); setting the model's tags does not make a store stale */
+sbr_status sbr_sessions_recommend_filtered(sbr_sessions* st, const uint32_t* slots, uint64_t n, uint32_t k, const uint64_t* excl_ptr,
+                                           const uint32_t* excl_items, uint32_t flags, const uint32_t* any_of, const uint32_t* none_of,
+                                           uint32_t* out_items, float* out_scores);
+sbr_status sbr_sessions_recommend_diverse_filtered(sbr_sessions* st, const uint32_t* slots, uint64_t n, uint32_t k, uint32_t pool,
+                                                   float trade_off, uint32_t metric, const uint64_t* excl_ptr, const uint32_t* excl_items,
+                                                   const uint32_t* any_of, const uint32_t* none_of, uint32_t* out_items, float* out_scores);
 
 /* ≙ the serde derives (lstm.rs:204,386; ewma.rs:208,401): element counts and raw access. */
 sbr_status sbr_model_param_count(const sbr_model* m, int32_t which, uint64_t* out_count);

@@ -150,6 +150,15 @@ def load():
         "sbr_sessions_recommend": [vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint32, vp, vp],
         "sbr_sessions_score_candidates": [vp, vp, C.c_uint64, vp, vp, vp],
         "sbr_sessions_recommend_diverse": [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, vp, vp, vp, vp],
+        "sbr_model_set_item_tags": [vp, vp],
+        "sbr_model_get_item_tags": [vp, vp],
+        "sbr_recommend_filtered": [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp, vp],
+        "sbr_recommend_filtered_reps": [vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp, vp, vp],
+        "sbr_recommend_diverse_filtered": [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, C.c_uint32, vp, vp, vp, vp],
+        "sbr_recommend_diverse_filtered_reps": [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, vp, vp, vp, vp, vp, vp],
+        "sbr_similar_items_filtered": [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp],
+        "sbr_sessions_recommend_filtered": [vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint32, vp, vp, vp, vp],
+        "sbr_sessions_recommend_diverse_filtered": [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, vp, vp, vp, vp, vp, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -202,4 +211,7 @@ DECLARED_SYMBOLS = [
     "sbr_sessions_append", "sbr_sessions_lengths", "sbr_sessions_representations", "sbr_sessions_get_state", "sbr_sessions_set_state",
     "sbr_sessions_recommend", "sbr_sessions_score_candidates",
     "sbr_recommend_diverse_max_pool", "sbr_recommend_diverse", "sbr_recommend_diverse_reps", "sbr_sessions_recommend_diverse",
+    "sbr_model_set_item_tags", "sbr_model_get_item_tags", "sbr_recommend_filtered", "sbr_recommend_filtered_reps",
+    "sbr_recommend_diverse_filtered", "sbr_recommend_diverse_filtered_reps", "sbr_similar_items_filtered",
+    "sbr_sessions_recommend_filtered", "sbr_sessions_recommend_diverse_filtered",
 ]

@@ -135,6 +135,15 @@ def build_ranking_tests(force: bool = False, verbose: bool = True) -> str:
     return _build_cpp_program(RANKING_SRC, RANKING_BIN, force, verbose)
 
 
+FILTERED_SRC = os.path.join(REPO, "tests", "cpp", "filtered_tests.cpp")
+FILTERED_BIN = os.path.join(REPO, "tests", "cpp", "_build", "filtered_tests")
+
+
+def build_filtered_tests(force: bool = False, verbose: bool = True) -> str:
+    """g++ build of the C++ host layer's tag-filter test program."""
+    return _build_cpp_program(FILTERED_SRC, FILTERED_BIN, force, verbose)
+
+
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv))
     print(build_facade_tests(force="--force" in sys.argv))
@@ -144,3 +153,4 @@ if __name__ == "__main__":
     print(build_diverse_tests(force="--force" in sys.argv))
     print(build_candidates_tests(force="--force" in sys.argv))
     print(build_sessions_tests(force="--force" in sys.argv))
+    print(build_filtered_tests(force="--force" in sys.argv))

@@ -11,7 +11,9 @@
  *                            sums and the mask correction)
  *   topk_gemm_kernel       : per user and item range, a running sorted list of the k best (score desc, id asc) in global scratch
  *                            and its k-th entry as the threshold in LDS.  A score that beats the threshold is staged in LDS; a
- *                            full staging buffer is sorted and merged into the list (which raises the threshold).
+ *                            full staging buffer is sorted and merged into the list (which raises the threshold).  With the
+ *                            TagFilter policy an item's 32-bit tag word is tested against the user's two mask words before its
+ *                            score is offered.
  *   topk_merge_kernel      : one workgroup per user merges the item ranges' lists into the final k, padded with
  *                            (0xFFFFFFFF, -inf).
  *   item_rnorm_kernel      : similar_items' r[i] = 1 / sqrt(chain_dot(E[i], E[i])) (0 for a zero row) of the whole catalogue
@@ -69,7 +71,9 @@ __device__ __forceinline__ void load_user_fragments(float (&a)[D / 2], const flo
 
 /* The 32-item tiles of E and b in the workgroup's item range [i_begin, i_end) (range blockIdx.y): fetch() loads one into
  * registers, zeros past i_end; stage() writes them to one half of the LDS double buffer (E rows LDE floats apart).  Thread map:
- * idx = tid + 256 it -> item row idx / (D / 4), float4 column idx % (D / 4). */
+ * idx = tid + 256 it -> item row idx / (D / 4), float4 column idx % (D / 4).  fetch_tags() / stage_tags() bring the tile's 32 item
+ * tag words in beside the bias for the scan that filters by them (topk_gemm_kernel's TagFilter): the lane group behind the bias's,
+ * zero past i_end. */
 template <int D>
 struct ItemTiles {
     static constexpr int LDE = D + 1;
@@ -111,6 +115,16 @@ struct ItemTiles {
             }
         }
         if (tid < 32) Bs[tid] = bv;
+    }
+    uint32_t tv = 0;
+    __device__ __forceinline__ void fetch_tags(const uint32_t* tags, int tile) {
+        const int tid = threadIdx.x;
+        const uint32_t i = i_begin + (uint32_t)tile * 32 + (uint32_t)(tid - 32);
+        if (tid >= 32 && tid < 64) tv = i < i_end ? tags[i] : 0u;
+    }
+    __device__ __forceinline__ void stage_tags(uint32_t* Ts) {
+        const int tid = threadIdx.x;
+        if (tid >= 32 && tid < 64) Ts[tid - 32] = tv;
     }
 };
 
@@ -525,13 +539,39 @@ struct BiasAdd { static constexpr bool scale = false; };
 struct ScaleMul { static constexpr bool scale = true; };
 #define TK_SCORE(q) (Score::scale ? acc[q] * bias : bias + acc[q])
 
-template <int D, class Score>
+/* Whether the scan filters items by tag, the third constant policy.  TagFilter: item i is offered to user u only if
+ * (tags[i] & none_of[u]) == 0 && (any_of[u] == 0 || (tags[i] & any_of[u]) != 0) — tags [num_items] the model's item tags, any_of /
+ * none_of [num_users] the launch's masks.  A tile's 32 tag words come in beside its biases (Ts, a double buffer as Bs) and the
+ * workgroup's 128 users' masks sit in LDS by slot for the whole range (with a third word per user, 1 where any_of is 0, so that
+ * the any_of test is one AND-OR and one compare), read as thS / thI are: 1 792 more bytes of LDS.  The test
+ * clears bits of `pend` behind the non-finite test, which therefore still sees every scanned score, and before the first offer(),
+ * so an item that is not allowed never takes a staging slot; nothing else of the epilogue knows of the filter.  The result is the
+ * first k of the same total order over the allowed items that are not excluded: what exclusion lists holding every other item give.
+ * NoFilter's arguments are an empty struct at the end of the argument block and every statement of the filter sits under
+ * `if constexpr`: those instantiations keep their instruction streams (profiles/filtered_asm_stats.md). */
+struct NoFilter {
+    static constexpr bool on = false;
+    struct Args {};
+};
+struct TagFilter {
+    static constexpr bool on = true;
+    struct Args {
+        const uint32_t *tags, *any_of, *none_of;
+    };
+};
+
+template <int D, class Score, class Filter>
 __global__ __launch_bounds__(256, D <= 128 ? 2 : 1) void topk_gemm_kernel(ModelView m, const float* reps, const int* rep_row, uint32_t num_users,
                                                                          const uint64_t* excl_ptr, const uint32_t* excl_items,
                                                                          uint32_t items_per_group, uint32_t k, uint2* lists, uint32_t* lens,
-                                                                         uint32_t* nonfinite_flag) {
+                                                                         uint32_t* nonfinite_flag, typename Filter::Args fa) {
     __shared__ float Es[2][32 * ItemTiles<D>::LDE];
     __shared__ float Bs[2][32];
+    // TagFilter only: the tiles' tag words, and the users' masks by slot (slot_user), read 16 bytes at a time
+    __shared__ uint32_t Ts[2][Filter::on ? 32 : 1];
+    __shared__ __align__(16) uint32_t anyS[Filter::on ? 128 : 4];
+    __shared__ __align__(16) uint32_t anyZ[Filter::on ? 128 : 4]; /* 1 where the user's any_of is 0 (every tag passes it), else 0 */
+    __shared__ __align__(16) uint32_t noneS[Filter::on ? 128 : 4];
     // per-user state by slot (slot_user)
     __shared__ float thS[128];
     __shared__ uint32_t thI[128];
@@ -552,6 +592,13 @@ __global__ __launch_bounds__(256, D <= 128 ? 2 : 1) void topk_gemm_kernel(ModelV
         thI[tid] = TK_NONE;
         cnt[tid] = 0;
         len[tid] = 0;
+        if constexpr (Filter::on) {
+            const uint32_t u = blockIdx.x * 128 + (uint32_t)slot_user(tid);
+            const uint32_t any = u < num_users ? fa.any_of[u] : 0u;
+            anyS[tid] = any;
+            anyZ[tid] = any == 0u ? 1u : 0u;
+            noneS[tid] = u < num_users ? fa.none_of[u] : 0u;
+        }
     }
     uint32_t umask = 0; /* accumulator registers q whose user exists */
 #pragma unroll
@@ -656,12 +703,19 @@ __global__ __launch_bounds__(256, D <= 128 ? 2 : 1) void topk_gemm_kernel(ModelV
     if (ntiles > 0) {
         tiles.fetch(m, 0);
         tiles.stage(Es[0], Bs[0]);
+        if constexpr (Filter::on) {
+            tiles.fetch_tags(fa.tags, 0);
+            tiles.stage_tags(Ts[0]);
+        }
     }
     __syncthreads();
     const int pbase = wave * 32 + hh * 16;
     for (int tile = 0; tile < ntiles; ++tile) {
         const int buf = tile & 1;
-        if (tile + 1 < ntiles) tiles.fetch(m, tile + 1);
+        if (tile + 1 < ntiles) {
+            tiles.fetch(m, tile + 1);
+            if constexpr (Filter::on) tiles.fetch_tags(fa.tags, tile + 1);
+        }
         const f32x16 acc = tile_dots<D>(a, Es[buf]);
         const float bias = Bs[buf][l31];
         const uint32_t id = tiles.i_begin + (uint32_t)tile * 32 + (uint32_t)l31;
@@ -670,6 +724,29 @@ __global__ __launch_bounds__(256, D <= 128 ? 2 : 1) void topk_gemm_kernel(ModelV
         for (int q = 0; q < 16; ++q) {
             const float sc = TK_SCORE(q);
             if (((pend >> q) & 1u) && !(sc - sc == 0.0f)) { bad = true; pend &= ~(1u << q); }
+        }
+        if constexpr (Filter::on) { /* the lane's item against its 16 users' masks: what is not allowed is not offered */
+            const uint32_t tag = Ts[buf][l31];
+            uint32_t drop = 0;
+#pragma unroll
+            for (int q4 = 0; q4 < 4; ++q4) {
+                const uint4 a4 = *reinterpret_cast<const uint4*>(&anyS[pbase + 4 * q4]);
+                const uint4 z4 = *reinterpret_cast<const uint4*>(&anyZ[pbase + 4 * q4]);
+                const uint4 n4 = *reinterpret_cast<const uint4*>(&noneS[pbase + 4 * q4]);
+                const uint32_t any[4] = {a4.x, a4.y, a4.z, a4.w};
+                const uint32_t anyz[4] = {z4.x, z4.y, z4.z, z4.w};
+                const uint32_t none[4] = {n4.x, n4.y, n4.z, n4.w};
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    /* two ANDs (one with the OR folded in) and two compares per user; `|`, not `||`: with the short-circuit form
+                     * the compiler put every user's any_of test behind a branch on its none_of test (two exec-mask regions per
+                     * user and tile) */
+                    const uint32_t hit = (tag & none[j]) != 0u ? 1u : 0u;
+                    const uint32_t miss = ((tag & any[j]) | anyz[j]) == 0u ? 1u : 0u;
+                    drop |= (hit | miss) << (4 * q4 + j);
+                }
+            }
+            pend &= ~drop;
         }
         // offers the pending scores: below the threshold they are dropped, above it they take a staging slot if one is left
         auto offer = [&]() {
@@ -700,7 +777,10 @@ __global__ __launch_bounds__(256, D <= 128 ? 2 : 1) void topk_gemm_kernel(ModelV
                 }
         };
         offer();
-        if (tile + 1 < ntiles) tiles.stage(Es[buf ^ 1], Bs[buf ^ 1]);
+        if (tile + 1 < ntiles) {
+            tiles.stage(Es[buf ^ 1], Bs[buf ^ 1]);
+            if constexpr (Filter::on) tiles.stage_tags(Ts[buf ^ 1]);
+        }
         // a user whose staging filled is merged, then what did not fit is offered again (it fits: at most 32 per user and tile)
         while (__syncthreads_or(pend != 0u)) {
             merge_staged((uint32_t)TK_STAGE);
@@ -1126,7 +1206,7 @@ uint32_t recommend_groups(uint32_t num_users, uint32_t num_items, uint32_t k, ui
 
 void launch_recommend(const ModelView& m, const float* reps, const int* rep_row, uint32_t num_users, const uint64_t* excl_ptr,
                       const uint32_t* excl_items, uint32_t k, uint2* lists, uint32_t* lens, uint32_t* out_items, float* out_scores,
-                      uint32_t* nonfinite_flag, hipStream_t s) {
+                      uint32_t* nonfinite_flag, hipStream_t s, const TagMasks* f) {
     if (num_users == 0) return;
     uint32_t per = 0;
     const uint32_t groups = recommend_groups(num_users, m.num_items, k, &per);
@@ -1134,8 +1214,12 @@ void launch_recommend(const ModelView& m, const float* reps, const int* rep_row,
     uint32_t n = 1;
     while (n < groups * k) n <<= 1;
     DISPATCH_D(m.d, {
-        hipLaunchKernelGGL((topk_gemm_kernel<DD, BiasAdd>), dim3(utiles, groups), dim3(256), 0, s, m, reps, rep_row, num_users, excl_ptr, excl_items,
-                           per, k, lists, lens, nonfinite_flag);
+        if (f)
+            hipLaunchKernelGGL((topk_gemm_kernel<DD, BiasAdd, TagFilter>), dim3(utiles, groups), dim3(256), 0, s, m, reps, rep_row, num_users, excl_ptr,
+                               excl_items, per, k, lists, lens, nonfinite_flag, TagFilter::Args{f->tags, f->any_of, f->none_of});
+        else
+            hipLaunchKernelGGL((topk_gemm_kernel<DD, BiasAdd, NoFilter>), dim3(utiles, groups), dim3(256), 0, s, m, reps, rep_row, num_users, excl_ptr,
+                               excl_items, per, k, lists, lens, nonfinite_flag, NoFilter::Args{});
         hipLaunchKernelGGL(topk_merge_kernel, dim3(num_users), dim3(512), 0, s, lists, lens, groups, k, n, out_items, out_scores);
     });
 }
@@ -1169,7 +1253,7 @@ void launch_diverse_select(const ModelView& m, const uint32_t* pool_items, const
 
 void launch_similar_items(const ModelView& m, const uint32_t* query, uint32_t num_queries, bool cosine, float* rnorm, float* H,
                           const int* rep_row, const uint64_t* excl_ptr, const uint32_t* excl_items, uint32_t k, uint2* lists,
-                          uint32_t* lens, uint32_t* out_items, float* out_scores, uint32_t* nonfinite_flag, hipStream_t s) {
+                          uint32_t* lens, uint32_t* out_items, float* out_scores, uint32_t* nonfinite_flag, hipStream_t s, const TagMasks* f) {
     if (num_queries == 0) return;
     uint32_t per = 0;
     const uint32_t groups = recommend_groups(num_queries, m.num_items, k, &per);
@@ -1183,8 +1267,12 @@ void launch_similar_items(const ModelView& m, const uint32_t* query, uint32_t nu
                            nonfinite_flag);
         hipLaunchKernelGGL((similar_query_kernel<DD>), dim3((unsigned)(((uint64_t)num_queries * (DD / 4) + 255) / 256)), dim3(256), 0, s, m, rnorm,
                            query, num_queries, H);
-        hipLaunchKernelGGL((topk_gemm_kernel<DD, ScaleMul>), dim3(utiles, groups), dim3(256), 0, s, mr, H, rep_row, num_queries, excl_ptr, excl_items,
-                           per, k, lists, lens, nonfinite_flag);
+        if (f)
+            hipLaunchKernelGGL((topk_gemm_kernel<DD, ScaleMul, TagFilter>), dim3(utiles, groups), dim3(256), 0, s, mr, H, rep_row, num_queries, excl_ptr,
+                               excl_items, per, k, lists, lens, nonfinite_flag, TagFilter::Args{f->tags, f->any_of, f->none_of});
+        else
+            hipLaunchKernelGGL((topk_gemm_kernel<DD, ScaleMul, NoFilter>), dim3(utiles, groups), dim3(256), 0, s, mr, H, rep_row, num_queries, excl_ptr,
+                               excl_items, per, k, lists, lens, nonfinite_flag, NoFilter::Args{});
         hipLaunchKernelGGL(topk_merge_kernel, dim3(num_queries), dim3(512), 0, s, lists, lens, groups, k, n, out_items, out_scores);
     });
 }

@@ -448,6 +448,8 @@ struct sbr_model {
     bool reference_order = false; /* sbr_model_set_reference_order: negatives from the worker's sequential stream (one sequence per step) */
     int step_fusion = 2; /* one-sequence steps at d <= 32 (sbr_model_set_step_fusion): 0 separate launches, 1 fused launches
                           * (SmallTail + small_back: four per step), 2 runs of steps in one launch where the shape allows */
+    uint32_t* item_tags = nullptr; /* sbr_model_set_item_tags: one tag word per item on this model's device, null until set.  Serving
+                                    * metadata (guarded by mu), not a parameter: no generation bump, not saved, freed with the model */
     DeviceArena eval_arena;        /* prediction-side scratch (guarded by mu) */
     hipStream_t stream = nullptr;
     bool own_stream = false;
@@ -920,7 +922,7 @@ sbr_status ensure_device(const sbr_model* m) {
 
 extern "C" {
 
-uint32_t sbr_abi_version(void) { return 11; }
+uint32_t sbr_abi_version(void) { return 12; }
 
 void sbr_release_cached_memory(void) { scratch_cache().trim(); }
 
@@ -1117,6 +1119,7 @@ void sbr_model_destroy(sbr_model* m) {
     dfree(v.W); dfree(v.Wacc); dfree(v.bW); dfree(v.bWacc); dfree(v.Wp); dfree(v.WTp);
     dfree(v.alpha); dfree(v.alpha_acc);
     dfree(v.Wm); dfree(v.bWm); dfree(v.alpha_m);
+    dfree(m->item_tags);
     for (auto& tp : m->pending) { hipEventDestroy(tp.a); hipEventDestroy(tp.b); }
     m->eval_arena.release();
     if (m->own_stream && m->stream) hipStreamDestroy(m->stream);
@@ -3879,12 +3882,17 @@ struct TopkBufs {
     int* rep;
     uint64_t* eptr;
     uint32_t *excl, *lens, *items, *flag;
+    uint32_t *any_of = nullptr, *none_of = nullptr; /* the tag filter's masks, one pair per user (with_masks) */
     uint2* lists;
     float* scores;
-    void carve(DeviceArena& ar, uint32_t num_items, size_t nu, size_t nexcl, uint32_t k) {
+    void carve(DeviceArena& ar, uint32_t num_items, size_t nu, size_t nexcl, uint32_t k, bool with_masks) {
         uint32_t per = 0;
         const size_t g = sbr::recommend_groups((uint32_t)nu, num_items, k, &per);
         rep = ar.take<int>(nu);
+        if (with_masks) {
+            any_of = ar.take<uint32_t>(nu);
+            none_of = ar.take<uint32_t>(nu);
+        }
         eptr = ar.take<uint64_t>(nu + 1);
         excl = ar.take<uint32_t>(nexcl + 1);
         lists = ar.take<uint2>(nu * g * k);
@@ -3931,13 +3939,22 @@ struct Diverse {
     uint32_t metric;
 };
 
+/* the tag filter of a *_filtered call: the caller's masks, one pair per user of the call (a null array: all zeros) */
+struct TagFilterArg {
+    const uint32_t *any_of, *none_of;
+};
+
 /* top-k of every user of `s`, in chunks; results to out_items / out_scores (host, num_users x k; scores optional).  With item rows
  * (similar_items: the users are the queries) the launch makes the rows itself and ranks by cosine, or by the plain dot product.
  * With `subset` (recommend_among: sorted, unique, not empty) only its items are scanned, as a sub-table every launch gathers.
  * With `dv` (recommend_diverse; not with item rows or a subset) the scan's rows are the users' pools: the same launch selects
- * dv->k_out of each, and the results are num_users x dv->k_out. */
+ * dv->k_out of each, and the results are num_users x dv->k_out.
+ * With `flt` (not with a subset) the scan offers user u only the items its masks allow against the model's item tags, which must be
+ * set; the masks go with the call's user u through the chunks, whatever row of H holds its representation. */
 sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, uint32_t k, uint32_t* out_items, float* out_scores,
-                          bool cosine = false, const std::vector<uint32_t>* subset = nullptr, const Diverse* dv = nullptr) {
+                          bool cosine = false, const std::vector<uint32_t>* subset = nullptr, const Diverse* dv = nullptr,
+                          const TagFilterArg* flt = nullptr) {
+    if (flt && (!m->item_tags || subset)) return SBR_ERR_INVALID_ARGUMENT;
     std::vector<uint64_t> users(num_users);
     for (uint64_t u = 0; u < num_users; ++u) users[u] = u;
     const uint32_t scanned_items = subset ? (uint32_t)subset->size() : (uint32_t)m->hp.num_items;
@@ -3951,7 +3968,7 @@ sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, 
         uint32_t* dv_items = nullptr; /* dv: the selection's rows, nu x dv->k_out */
         float* dv_scores = nullptr;
         SBRCHK(user_reps(m, s, ch.users, [&](DeviceArena& ar) {
-            tb.carve(ar, scanned_items, nu, ur.b.list_items.size(), k);
+            tb.carve(ar, scanned_items, nu, ur.b.list_items.size(), k, flt != nullptr);
             if (s.item_rows) rnorm = ar.take<float>(m->hp.num_items);
             if (subset) sb.carve(ar, subset->size(), (size_t)m->d);
             if (dv) {
@@ -3970,11 +3987,23 @@ sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, 
             if (!ur.b.list_items.empty())
                 HIPCHK(hipMemcpyAsync(tb.excl, ur.b.list_items.data(), ur.b.list_items.size() * 4, hipMemcpyHostToDevice, m->stream));
         }
+        std::vector<uint32_t> masks; /* the chunk's users' any_of, then their none_of */
+        sbr::TagMasks tm{m->item_tags, tb.any_of, tb.none_of};
+        const sbr::TagMasks* f = flt ? &tm : nullptr;
+        if (flt) {
+            masks.assign(2 * nu, 0u);
+            for (size_t i = 0; i < nu; ++i) {
+                if (flt->any_of) masks[i] = flt->any_of[ch.users[i]];
+                if (flt->none_of) masks[nu + i] = flt->none_of[ch.users[i]];
+            }
+            HIPCHK(hipMemcpyAsync(tb.any_of, masks.data(), nu * 4, hipMemcpyHostToDevice, m->stream));
+            HIPCHK(hipMemcpyAsync(tb.none_of, masks.data() + nu, nu * 4, hipMemcpyHostToDevice, m->stream));
+        }
         const size_t ko = dv ? dv->k_out : k; /* the width of the rows that leave */
         SBRCHK(scan_launch(m, s.item_rows || subset ? 4 : dv ? 3 : 2, tb.flag, [&] {
             if (dv) { /* the selection reads the pool's scores whether or not the caller wants any */
                 sbr::launch_recommend(m->mv, ur.H, tb.rep, (uint32_t)nu, excl ? tb.eptr : nullptr, tb.excl, k, tb.lists, tb.lens, tb.items,
-                                      tb.scores, tb.flag, m->stream);
+                                      tb.scores, tb.flag, m->stream, f);
                 sbr::launch_diverse_select(m->mv, tb.items, tb.scores, (uint32_t)nu, k, dv->k_out, dv->trade_off, dv->metric == SBR_SIMILAR_COSINE,
                                            dv_items, out_scores ? dv_scores : nullptr, tb.flag, m->stream);
             } else if (subset)
@@ -3982,10 +4011,10 @@ sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, 
                                             k, tb.lists, tb.lens, tb.items, out_scores ? tb.scores : nullptr, tb.flag, m->stream);
             else if (s.item_rows)
                 sbr::launch_similar_items(m->mv, ur.d_item_rows, (uint32_t)nu, cosine, rnorm, ur.H, tb.rep, excl ? tb.eptr : nullptr, tb.excl, k,
-                                          tb.lists, tb.lens, tb.items, out_scores ? tb.scores : nullptr, tb.flag, m->stream);
+                                          tb.lists, tb.lens, tb.items, out_scores ? tb.scores : nullptr, tb.flag, m->stream, f);
             else
                 sbr::launch_recommend(m->mv, ur.H, tb.rep, (uint32_t)nu, excl ? tb.eptr : nullptr, tb.excl, k, tb.lists, tb.lens, tb.items,
-                                      out_scores ? tb.scores : nullptr, tb.flag, m->stream);
+                                      out_scores ? tb.scores : nullptr, tb.flag, m->stream, f);
         }, {{out_items + ch.c0 * ko, dv ? dv_items : tb.items, nu * ko * 4},
             {out_scores ? out_scores + ch.c0 * ko : nullptr, dv ? dv_scores : tb.scores, nu * ko * 4}}));
     }
@@ -3997,28 +4026,81 @@ bool excl_args_ok(const uint64_t* excl_ptr, const uint32_t* excl_items, uint64_t
     return (excl_ptr == nullptr) == (excl_items == nullptr) || (excl_ptr && excl_ptr[num_users] == excl_ptr[0]);
 }
 
-}  // namespace
-
-sbr_status sbr_recommend(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users, uint32_t k, uint32_t flags,
-                         uint32_t* out_items, float* out_scores) {
+/* the plain calls and their *_filtered forms (flt non-null) */
+sbr_status recommend_call(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users, uint32_t k, uint32_t flags,
+                          uint32_t* out_items, float* out_scores, const TagFilterArg* flt) {
     if (!m || !user_ptr || (num_users && !out_items)) return SBR_ERR_INVALID_ARGUMENT;
     if (k < 1 || k > SBR_RECOMMEND_MAX_K || (flags & ~SBR_RECOMMEND_INCLUDE_HISTORY)) return SBR_ERR_INVALID_ARGUMENT;
     std::lock_guard<std::mutex> lock(m->mu);
     SBRCHK(enter_reader(m));
     SBRCHK(check_csr(m, user_ptr, num_users, item_ids, false));
     /* the WHOLE history is masked (evaluation.rs:30-32) */
-    return recommend_scan(m, RepSource{user_ptr, item_ids, nullptr, 0, !(flags & SBR_RECOMMEND_INCLUDE_HISTORY)}, num_users, k, out_items, out_scores);
+    return recommend_scan(m, RepSource{user_ptr, item_ids, nullptr, 0, !(flags & SBR_RECOMMEND_INCLUDE_HISTORY)}, num_users, k, out_items, out_scores,
+                          false, nullptr, nullptr, flt);
 }
 
-sbr_status sbr_recommend_reps(sbr_model* m, const float* reps, uint64_t num_users, uint32_t k, const uint64_t* excl_ptr,
-                              const uint32_t* excl_items, uint32_t* out_items, float* out_scores) {
+sbr_status recommend_reps_call(sbr_model* m, const float* reps, uint64_t num_users, uint32_t k, const uint64_t* excl_ptr,
+                               const uint32_t* excl_items, uint32_t* out_items, float* out_scores, const TagFilterArg* flt) {
     if (!m || (num_users && (!reps || !out_items))) return SBR_ERR_INVALID_ARGUMENT;
     if (k < 1 || k > SBR_RECOMMEND_MAX_K) return SBR_ERR_INVALID_ARGUMENT;
     if (!excl_args_ok(excl_ptr, excl_items, num_users)) return SBR_ERR_INVALID_ARGUMENT;
     std::lock_guard<std::mutex> lock(m->mu);
     SBRCHK(enter_reader(m));
     if (excl_ptr) SBRCHK(check_csr(m, excl_ptr, num_users, excl_items, false));
-    return recommend_scan(m, RepSource{excl_ptr, excl_items, reps, 0, true}, num_users, k, out_items, out_scores);
+    return recommend_scan(m, RepSource{excl_ptr, excl_items, reps, 0, true}, num_users, k, out_items, out_scores, false, nullptr, nullptr, flt);
+}
+
+}  // namespace
+
+sbr_status sbr_recommend(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users, uint32_t k, uint32_t flags,
+                         uint32_t* out_items, float* out_scores) {
+    return recommend_call(m, user_ptr, item_ids, num_users, k, flags, out_items, out_scores, nullptr);
+}
+
+sbr_status sbr_recommend_reps(sbr_model* m, const float* reps, uint64_t num_users, uint32_t k, const uint64_t* excl_ptr,
+                              const uint32_t* excl_items, uint32_t* out_items, float* out_scores) {
+    return recommend_reps_call(m, reps, num_users, k, excl_ptr, excl_items, out_items, out_scores, nullptr);
+}
+
+/* ---------------------------------------------------------------------------------------------
+ * item tags and the filtered scans (sbr_catalogue.hip, topk_gemm_kernel's TagFilter)
+ * ------------------------------------------------------------------------------------------- */
+sbr_status sbr_model_set_item_tags(sbr_model* m, const uint32_t* tags) {
+    if (!m) return SBR_ERR_INVALID_ARGUMENT;
+    std::lock_guard<std::mutex> lock(m->mu);
+    SBRCHK(ensure_device(m));
+    HIPCHK(hipStreamSynchronize(m->stream)); /* no scan of this model is reading the old words */
+    if (!tags) {
+        dfree(m->item_tags);
+        m->item_tags = nullptr;
+        return SBR_OK;
+    }
+    if (!m->item_tags) SBRCHK(dmalloc(&m->item_tags, (size_t)m->hp.num_items));
+    HIPCHK(hipMemcpy(m->item_tags, tags, (size_t)m->hp.num_items * 4, hipMemcpyHostToDevice));
+    return SBR_OK;
+}
+
+sbr_status sbr_model_get_item_tags(sbr_model* m, uint32_t* out) {
+    if (!m || !out) return SBR_ERR_INVALID_ARGUMENT;
+    std::lock_guard<std::mutex> lock(m->mu);
+    if (!m->item_tags) return SBR_ERR_INVALID_ARGUMENT;
+    SBRCHK(ensure_device(m));
+    HIPCHK(hipStreamSynchronize(m->stream));
+    HIPCHK(hipMemcpy(out, m->item_tags, (size_t)m->hp.num_items * 4, hipMemcpyDeviceToHost));
+    return SBR_OK;
+}
+
+sbr_status sbr_recommend_filtered(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users, uint32_t k,
+                                  uint32_t flags, const uint32_t* any_of, const uint32_t* none_of, uint32_t* out_items, float* out_scores) {
+    const TagFilterArg flt{any_of, none_of};
+    return recommend_call(m, user_ptr, item_ids, num_users, k, flags, out_items, out_scores, &flt);
+}
+
+sbr_status sbr_recommend_filtered_reps(sbr_model* m, const float* reps, uint64_t num_users, uint32_t k, const uint64_t* excl_ptr,
+                                       const uint32_t* excl_items, const uint32_t* any_of, const uint32_t* none_of, uint32_t* out_items,
+                                       float* out_scores) {
+    const TagFilterArg flt{any_of, none_of};
+    return recommend_reps_call(m, reps, num_users, k, excl_ptr, excl_items, out_items, out_scores, &flt);
 }
 
 /* ---------------------------------------------------------------------------------------------
@@ -4032,6 +4114,32 @@ bool diverse_args_ok(const sbr_model* m, uint32_t k, uint32_t pool, float trade_
            metric <= SBR_SIMILAR_DOT;
 }
 
+sbr_status recommend_diverse_call(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users, uint32_t k,
+                                  uint32_t pool, float trade_off, uint32_t metric, uint32_t flags, uint32_t* out_items, float* out_scores,
+                                  const TagFilterArg* flt) {
+    if (!m || !user_ptr || (num_users && !out_items)) return SBR_ERR_INVALID_ARGUMENT;
+    if (!diverse_args_ok(m, k, pool, trade_off, metric) || (flags & ~SBR_RECOMMEND_INCLUDE_HISTORY)) return SBR_ERR_INVALID_ARGUMENT;
+    std::lock_guard<std::mutex> lock(m->mu);
+    SBRCHK(enter_reader(m));
+    SBRCHK(check_csr(m, user_ptr, num_users, item_ids, false));
+    const Diverse dv{k, trade_off, metric};
+    return recommend_scan(m, RepSource{user_ptr, item_ids, nullptr, 0, !(flags & SBR_RECOMMEND_INCLUDE_HISTORY)}, num_users, pool, out_items,
+                          out_scores, false, nullptr, &dv, flt);
+}
+
+sbr_status recommend_diverse_reps_call(sbr_model* m, const float* reps, uint64_t num_users, uint32_t k, uint32_t pool, float trade_off,
+                                       uint32_t metric, const uint64_t* excl_ptr, const uint32_t* excl_items, uint32_t* out_items,
+                                       float* out_scores, const TagFilterArg* flt) {
+    if (!m || (num_users && (!reps || !out_items))) return SBR_ERR_INVALID_ARGUMENT;
+    if (!diverse_args_ok(m, k, pool, trade_off, metric)) return SBR_ERR_INVALID_ARGUMENT;
+    if (!excl_args_ok(excl_ptr, excl_items, num_users)) return SBR_ERR_INVALID_ARGUMENT;
+    std::lock_guard<std::mutex> lock(m->mu);
+    SBRCHK(enter_reader(m));
+    if (excl_ptr) SBRCHK(check_csr(m, excl_ptr, num_users, excl_items, false));
+    const Diverse dv{k, trade_off, metric};
+    return recommend_scan(m, RepSource{excl_ptr, excl_items, reps, 0, true}, num_users, pool, out_items, out_scores, false, nullptr, &dv, flt);
+}
+
 }  // namespace
 
 sbr_status sbr_recommend_diverse_max_pool(const sbr_model* m, uint32_t* out) {
@@ -4042,34 +4150,37 @@ sbr_status sbr_recommend_diverse_max_pool(const sbr_model* m, uint32_t* out) {
 
 sbr_status sbr_recommend_diverse(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users, uint32_t k, uint32_t pool,
                                  float trade_off, uint32_t metric, uint32_t flags, uint32_t* out_items, float* out_scores) {
-    if (!m || !user_ptr || (num_users && !out_items)) return SBR_ERR_INVALID_ARGUMENT;
-    if (!diverse_args_ok(m, k, pool, trade_off, metric) || (flags & ~SBR_RECOMMEND_INCLUDE_HISTORY)) return SBR_ERR_INVALID_ARGUMENT;
-    std::lock_guard<std::mutex> lock(m->mu);
-    SBRCHK(enter_reader(m));
-    SBRCHK(check_csr(m, user_ptr, num_users, item_ids, false));
-    const Diverse dv{k, trade_off, metric};
-    return recommend_scan(m, RepSource{user_ptr, item_ids, nullptr, 0, !(flags & SBR_RECOMMEND_INCLUDE_HISTORY)}, num_users, pool, out_items,
-                          out_scores, false, nullptr, &dv);
+    return recommend_diverse_call(m, user_ptr, item_ids, num_users, k, pool, trade_off, metric, flags, out_items, out_scores, nullptr);
+}
+
+sbr_status sbr_recommend_diverse_filtered(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users, uint32_t k,
+                                          uint32_t pool, float trade_off, uint32_t metric, uint32_t flags, const uint32_t* any_of,
+                                          const uint32_t* none_of, uint32_t* out_items, float* out_scores) {
+    const TagFilterArg flt{any_of, none_of};
+    return recommend_diverse_call(m, user_ptr, item_ids, num_users, k, pool, trade_off, metric, flags, out_items, out_scores, &flt);
 }
 
 sbr_status sbr_recommend_diverse_reps(sbr_model* m, const float* reps, uint64_t num_users, uint32_t k, uint32_t pool, float trade_off,
                                       uint32_t metric, const uint64_t* excl_ptr, const uint32_t* excl_items, uint32_t* out_items,
                                       float* out_scores) {
-    if (!m || (num_users && (!reps || !out_items))) return SBR_ERR_INVALID_ARGUMENT;
-    if (!diverse_args_ok(m, k, pool, trade_off, metric)) return SBR_ERR_INVALID_ARGUMENT;
-    if (!excl_args_ok(excl_ptr, excl_items, num_users)) return SBR_ERR_INVALID_ARGUMENT;
-    std::lock_guard<std::mutex> lock(m->mu);
-    SBRCHK(enter_reader(m));
-    if (excl_ptr) SBRCHK(check_csr(m, excl_ptr, num_users, excl_items, false));
-    const Diverse dv{k, trade_off, metric};
-    return recommend_scan(m, RepSource{excl_ptr, excl_items, reps, 0, true}, num_users, pool, out_items, out_scores, false, nullptr, &dv);
+    return recommend_diverse_reps_call(m, reps, num_users, k, pool, trade_off, metric, excl_ptr, excl_items, out_items, out_scores, nullptr);
+}
+
+sbr_status sbr_recommend_diverse_filtered_reps(sbr_model* m, const float* reps, uint64_t num_users, uint32_t k, uint32_t pool, float trade_off,
+                                               uint32_t metric, const uint64_t* excl_ptr, const uint32_t* excl_items, const uint32_t* any_of,
+                                               const uint32_t* none_of, uint32_t* out_items, float* out_scores) {
+    const TagFilterArg flt{any_of, none_of};
+    return recommend_diverse_reps_call(m, reps, num_users, k, pool, trade_off, metric, excl_ptr, excl_items, out_items, out_scores, &flt);
 }
 
 /* ---------------------------------------------------------------------------------------------
  * exact top-k neighbours of catalogue items (sbr_catalogue.hip)
  * ------------------------------------------------------------------------------------------- */
-sbr_status sbr_similar_items(sbr_model* m, const uint32_t* query_items, uint64_t num_queries, uint32_t k, uint32_t metric, uint32_t flags,
-                             const uint64_t* excl_ptr, const uint32_t* excl_items, uint32_t* out_items, float* out_scores) {
+namespace {
+
+sbr_status similar_items_call(sbr_model* m, const uint32_t* query_items, uint64_t num_queries, uint32_t k, uint32_t metric, uint32_t flags,
+                              const uint64_t* excl_ptr, const uint32_t* excl_items, uint32_t* out_items, float* out_scores,
+                              const TagFilterArg* flt) {
     if (!m || (num_queries && (!query_items || !out_items))) return SBR_ERR_INVALID_ARGUMENT;
     if (k < 1 || k > SBR_RECOMMEND_MAX_K || metric > SBR_SIMILAR_DOT || (flags & ~SBR_SIMILAR_INCLUDE_SELF)) return SBR_ERR_INVALID_ARGUMENT;
     if (!excl_args_ok(excl_ptr, excl_items, num_queries)) return SBR_ERR_INVALID_ARGUMENT;
@@ -4093,7 +4204,21 @@ sbr_status sbr_similar_items(sbr_model* m, const uint32_t* query_items, uint64_t
     }
     RepSource s{self ? excl_ptr : eptr.data(), self ? excl_items : eitems.data(), nullptr, 0, true};
     s.item_rows = query_items;
-    return recommend_scan(m, s, num_queries, k, out_items, out_scores, metric == SBR_SIMILAR_COSINE);
+    return recommend_scan(m, s, num_queries, k, out_items, out_scores, metric == SBR_SIMILAR_COSINE, nullptr, nullptr, flt);
+}
+
+}  // namespace
+
+sbr_status sbr_similar_items(sbr_model* m, const uint32_t* query_items, uint64_t num_queries, uint32_t k, uint32_t metric, uint32_t flags,
+                             const uint64_t* excl_ptr, const uint32_t* excl_items, uint32_t* out_items, float* out_scores) {
+    return similar_items_call(m, query_items, num_queries, k, metric, flags, excl_ptr, excl_items, out_items, out_scores, nullptr);
+}
+
+sbr_status sbr_similar_items_filtered(sbr_model* m, const uint32_t* query_items, uint64_t num_queries, uint32_t k, uint32_t metric,
+                                      uint32_t flags, const uint64_t* excl_ptr, const uint32_t* excl_items, const uint32_t* any_of,
+                                      const uint32_t* none_of, uint32_t* out_items, float* out_scores) {
+    const TagFilterArg flt{any_of, none_of};
+    return similar_items_call(m, query_items, num_queries, k, metric, flags, excl_ptr, excl_items, out_items, out_scores, &flt);
 }
 
 /* ---------------------------------------------------------------------------------------------
@@ -4616,8 +4741,10 @@ sbr_status sbr_sessions_set_state(sbr_sessions* st, const uint32_t* slots, uint6
     return SBR_OK;
 }
 
-sbr_status sbr_sessions_recommend(sbr_sessions* st, const uint32_t* slots, uint64_t n, uint32_t k, const uint64_t* excl_ptr,
-                                  const uint32_t* excl_items, uint32_t flags, uint32_t* out_items, float* out_scores) {
+namespace {
+
+sbr_status sessions_recommend_call(sbr_sessions* st, const uint32_t* slots, uint64_t n, uint32_t k, const uint64_t* excl_ptr,
+                                   const uint32_t* excl_items, uint32_t flags, uint32_t* out_items, float* out_scores, const TagFilterArg* flt) {
     if (!st || (n && !out_items) || flags) return SBR_ERR_INVALID_ARGUMENT;
     if (k < 1 || k > SBR_RECOMMEND_MAX_K) return SBR_ERR_INVALID_ARGUMENT;
     if (!excl_args_ok(excl_ptr, excl_items, n)) return SBR_ERR_INVALID_ARGUMENT;
@@ -4630,12 +4757,12 @@ sbr_status sbr_sessions_recommend(sbr_sessions* st, const uint32_t* slots, uint6
     RepSource s{excl_ptr, excl_items, nullptr, 0, true};
     s.dev_rows = st->v.H;
     s.dev_row = rows.data();
-    return recommend_scan(m, s, n, k, out_items, out_scores);
+    return recommend_scan(m, s, n, k, out_items, out_scores, false, nullptr, nullptr, flt);
 }
 
-sbr_status sbr_sessions_recommend_diverse(sbr_sessions* st, const uint32_t* slots, uint64_t n, uint32_t k, uint32_t pool, float trade_off,
-                                          uint32_t metric, const uint64_t* excl_ptr, const uint32_t* excl_items, uint32_t* out_items,
-                                          float* out_scores) {
+sbr_status sessions_recommend_diverse_call(sbr_sessions* st, const uint32_t* slots, uint64_t n, uint32_t k, uint32_t pool, float trade_off,
+                                           uint32_t metric, const uint64_t* excl_ptr, const uint32_t* excl_items, uint32_t* out_items,
+                                           float* out_scores, const TagFilterArg* flt) {
     if (!st || (n && !out_items)) return SBR_ERR_INVALID_ARGUMENT;
     if (!diverse_args_ok(st->m, k, pool, trade_off, metric)) return SBR_ERR_INVALID_ARGUMENT;
     if (!excl_args_ok(excl_ptr, excl_items, n)) return SBR_ERR_INVALID_ARGUMENT;
@@ -4649,7 +4776,34 @@ sbr_status sbr_sessions_recommend_diverse(sbr_sessions* st, const uint32_t* slot
     s.dev_rows = st->v.H;
     s.dev_row = rows.data();
     const Diverse dv{k, trade_off, metric};
-    return recommend_scan(m, s, n, pool, out_items, out_scores, false, nullptr, &dv);
+    return recommend_scan(m, s, n, pool, out_items, out_scores, false, nullptr, &dv, flt);
+}
+
+}  // namespace
+
+sbr_status sbr_sessions_recommend(sbr_sessions* st, const uint32_t* slots, uint64_t n, uint32_t k, const uint64_t* excl_ptr,
+                                  const uint32_t* excl_items, uint32_t flags, uint32_t* out_items, float* out_scores) {
+    return sessions_recommend_call(st, slots, n, k, excl_ptr, excl_items, flags, out_items, out_scores, nullptr);
+}
+
+sbr_status sbr_sessions_recommend_filtered(sbr_sessions* st, const uint32_t* slots, uint64_t n, uint32_t k, const uint64_t* excl_ptr,
+                                           const uint32_t* excl_items, uint32_t flags, const uint32_t* any_of, const uint32_t* none_of,
+                                           uint32_t* out_items, float* out_scores) {
+    const TagFilterArg flt{any_of, none_of};
+    return sessions_recommend_call(st, slots, n, k, excl_ptr, excl_items, flags, out_items, out_scores, &flt);
+}
+
+sbr_status sbr_sessions_recommend_diverse(sbr_sessions* st, const uint32_t* slots, uint64_t n, uint32_t k, uint32_t pool, float trade_off,
+                                          uint32_t metric, const uint64_t* excl_ptr, const uint32_t* excl_items, uint32_t* out_items,
+                                          float* out_scores) {
+    return sessions_recommend_diverse_call(st, slots, n, k, pool, trade_off, metric, excl_ptr, excl_items, out_items, out_scores, nullptr);
+}
+
+sbr_status sbr_sessions_recommend_diverse_filtered(sbr_sessions* st, const uint32_t* slots, uint64_t n, uint32_t k, uint32_t pool,
+                                                   float trade_off, uint32_t metric, const uint64_t* excl_ptr, const uint32_t* excl_items,
+                                                   const uint32_t* any_of, const uint32_t* none_of, uint32_t* out_items, float* out_scores) {
+    const TagFilterArg flt{any_of, none_of};
+    return sessions_recommend_diverse_call(st, slots, n, k, pool, trade_off, metric, excl_ptr, excl_items, out_items, out_scores, &flt);
 }
 
 sbr_status sbr_sessions_score_candidates(sbr_sessions* st, const uint32_t* slots, uint64_t n, const uint64_t* cand_ptr,

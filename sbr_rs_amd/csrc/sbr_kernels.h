@@ -283,12 +283,18 @@ void launch_rank_targets(const ModelView& m, const float* reps, const int* rep_r
 /* exact top-k of the catalogue per user (sbr_catalogue.hip): topk_gemm_kernel keeps per (user, item range) a sorted list of the
  * k best (score desc, id asc) in `lists` [num_users][groups][k] with its length in `lens` [num_users][groups]; topk_merge_kernel
  * merges a user's lists in LDS into out_items / out_scores [num_users][k] (padding: 0xFFFFFFFF / -inf).  excl_ptr / excl_items:
- * sorted, de-duplicated per-user exclusion lists (NULL: none).  groups * k <= TK_MERGE_MAX. */
+ * sorted, de-duplicated per-user exclusion lists (NULL: none).  groups * k <= TK_MERGE_MAX.
+ * f (NULL: none): the scan's tag filter (topk_gemm_kernel's TagFilter policy) — device arrays tags [num_items], any_of / none_of
+ * [num_users], none of them NULL; item i is eligible for user u only if (tags[i] & none_of[u]) == 0 && (any_of[u] == 0 ||
+ * (tags[i] & any_of[u]) != 0). */
 constexpr uint32_t TK_MERGE_MAX = 8192;
+struct TagMasks {
+    const uint32_t *tags, *any_of, *none_of;
+};
 uint32_t recommend_groups(uint32_t num_users, uint32_t num_items, uint32_t k, uint32_t* items_per_group);
 void launch_recommend(const ModelView& m, const float* reps, const int* rep_row, uint32_t num_users, const uint64_t* excl_ptr,
                       const uint32_t* excl_items, uint32_t k, uint2* lists, uint32_t* lens, uint32_t* out_items, float* out_scores,
-                      uint32_t* nonfinite_flag, hipStream_t s);
+                      uint32_t* nonfinite_flag, hipStream_t s, const TagMasks* f = nullptr);
 /* greedy maximal-marginal-relevance selection (sbr_catalogue.hip, diverse_select_kernel; the contract: sbr_recommend_diverse in
  * include/sbr_hip.h): pool_items / pool_scores [num_users][pool] are launch_recommend's outputs at k = pool; out_items / out_scores
  * [num_users][k_out] the picks in pick order with their pool scores, padded as the pool's rows.  1 <= k_out <= pool <=
@@ -301,10 +307,12 @@ void launch_diverse_select(const ModelView& m, const uint32_t* pool_items, const
 /* exact top-k neighbours of catalogue items (sbr_catalogue.hip): item_rnorm_kernel writes rnorm [num_items] (1 / |E[i]|, 0 for a zero
  * row; all 1.0f unless `cosine`) and raises the flag for a non-finite squared norm, similar_query_kernel writes the scan rows
  * H [num_queries][d] = E[query[j]] * rnorm[query[j]], and launch_recommend's two kernels rank s(j, i) = chain_dot(H[j], E[i]) *
- * rnorm[i] (no bias) with rep_row, the exclusion lists, lists / lens and the outputs as there (the same recommend_groups split). */
+ * rnorm[i] (no bias) with rep_row, the exclusion lists, the tag filter f (masks per query), lists / lens and the outputs as there (the
+ * same recommend_groups split). */
 void launch_similar_items(const ModelView& m, const uint32_t* query, uint32_t num_queries, bool cosine, float* rnorm, float* H,
                           const int* rep_row, const uint64_t* excl_ptr, const uint32_t* excl_items, uint32_t k, uint2* lists,
-                          uint32_t* lens, uint32_t* out_items, float* out_scores, uint32_t* nonfinite_flag, hipStream_t s);
+                          uint32_t* lens, uint32_t* out_items, float* out_scores, uint32_t* nonfinite_flag, hipStream_t s,
+                          const TagMasks* f = nullptr);
 /* launch_recommend restricted to the item set subset[0 .. num_subset), sorted and unique (sbr_catalogue.hip): subset_gather_kernel
  * copies the set's rows and biases into Esub [num_subset][d] / bsub [num_subset], launch_recommend's two kernels scan that sub-table
  * — lists / lens sized by recommend_groups(num_users, num_subset, k), excl_items POSITIONS in the subset — and subset_ids_kernel turns

@@ -62,6 +62,26 @@ def _ptr(a: np.ndarray):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def _tag_masks(any_of, none_of, nu: int):
+    """The mask keywords of a filtered call -> None when both are None (the plain entry point is called), else (any_of, none_of) as
+    u32 [nu] arrays: a scalar applies to every user, None is all zeros, an array must have one entry per user."""
+    if any_of is None and none_of is None:
+        return None
+
+    def one(mask, name):
+        if mask is None:
+            return np.zeros(max(nu, 1), dtype=np.uint32)
+        a = np.asarray(mask)
+        if a.ndim == 0:
+            return np.full(max(nu, 1), int(a) & 0xFFFFFFFF, dtype=np.uint32)
+        a = np.ascontiguousarray(a.ravel(), dtype=np.uint32)
+        if a.size != nu:
+            raise ValueError(f"{name}: one mask per user ({nu}), or a scalar; got {a.size}")
+        return a if nu else np.zeros(1, dtype=np.uint32)
+
+    return one(any_of, "any_of"), one(none_of, "none_of")
+
+
 STREAM_ROLES = ("main", "side", "sorter", "copier", "xs")  # the roles SBR_TEST_STREAM_DELAY names, in the counter's order
 
 
@@ -448,6 +468,24 @@ class Model:
         values = np.ascontiguousarray(values, dtype=np.float32).ravel()
         _check(self._L.sbr_model_set_param(self._h, int(which), _ptr(values), values.size))
 
+    def set_item_tags(self, tags):
+        """One 32-bit tag word per item, kept on the device for the ``any_of=`` / ``none_of=`` filters of the top-k calls
+        (sbr_model_set_item_tags); ``None`` clears them.  Serving metadata: fit, set_param and load leave them alone, a session
+        store stays usable, and ``save`` does not write them."""
+        if tags is None:
+            _check(self._L.sbr_model_set_item_tags(self._h, None))
+            return
+        t = np.ascontiguousarray(np.asarray(tags).ravel(), dtype=np.uint32)
+        if t.size != int(self.hp.num_items):
+            raise ValueError(f"one tag word per item ({int(self.hp.num_items)}); got {t.size}")
+        _check(self._L.sbr_model_set_item_tags(self._h, _ptr(t)))
+
+    def item_tags(self) -> np.ndarray:
+        """The tag words last set, u32 [num_items] (sbr_model_get_item_tags); raises while the model has none."""
+        out = np.zeros(int(self.hp.num_items), dtype=np.uint32)
+        _check(self._L.sbr_model_get_item_tags(self._h, _ptr(out)))
+        return out
+
     def global_epoch(self) -> int:
         n = C.c_uint64()
         _check(self._L.sbr_model_get_epoch(self._h, C.byref(n)))
@@ -571,28 +609,42 @@ class Model:
         _check(self._L.sbr_mrr_score(self._h, _ptr(up), _ptr(it), len(up) - 1, C.byref(mrr), _ptr(ranks), C.byref(n)))
         return mrr.value, ranks[: n.value].copy()
 
-    def recommend(self, user_ptr, item_ids, k: int, include_history: bool = False):
+    def recommend(self, user_ptr, item_ids, k: int, include_history: bool = False, any_of=None, none_of=None):
         """Exact top-k of the whole catalogue for each history (CSR, the layout of mrr_score): items [U, k] u32 and scores
-        [U, k] f32, score descending, ties to the lower id; short rows padded with (RECOMMEND_NO_ITEM, -inf)."""
+        [U, k] f32, score descending, ties to the lower id; short rows padded with (RECOMMEND_NO_ITEM, -inf).
+        any_of / none_of: the per-user tag filter (sbr_recommend_filtered; the model needs ``set_item_tags``) — a u32 mask per
+        user, or a scalar for all: item i is eligible for user u iff tags[i] & none_of[u] == 0 and (any_of[u] == 0 or
+        tags[i] & any_of[u] != 0)."""
         up = np.ascontiguousarray(user_ptr, dtype=np.uint64)
         it = np.ascontiguousarray(item_ids, dtype=np.uint32)
         nu = max(len(up) - 1, 0)
+        masks = _tag_masks(any_of, none_of, nu)
         items = np.zeros((nu, max(int(k), 0)), dtype=np.uint32)
         scores = np.zeros((nu, max(int(k), 0)), dtype=np.float32)
         flags = RECOMMEND_INCLUDE_HISTORY if include_history else 0
-        _check(self._L.sbr_recommend(self._h, _ptr(up), _ptr(it), nu, int(k) & 0xFFFFFFFF, flags, _ptr(items), _ptr(scores)))
+        if masks is None:
+            _check(self._L.sbr_recommend(self._h, _ptr(up), _ptr(it), nu, int(k) & 0xFFFFFFFF, flags, _ptr(items), _ptr(scores)))
+        else:
+            _check(self._L.sbr_recommend_filtered(self._h, _ptr(up), _ptr(it), nu, int(k) & 0xFFFFFFFF, flags, _ptr(masks[0]),
+                                                  _ptr(masks[1]), _ptr(items), _ptr(scores)))
         return items, scores
 
-    def recommend_reps(self, reps, k: int, exclude=None):
+    def recommend_reps(self, reps, k: int, exclude=None, any_of=None, none_of=None):
         """As recommend, from representations [U, embedding_dim] (user_representation's); exclude: None or one sequence of
-        item ids per user."""
+        item ids per user; any_of / none_of: recommend's tag filter."""
         reps = np.ascontiguousarray(reps, dtype=np.float32).reshape(-1, self.dim)
         nu = reps.shape[0]
+        masks = _tag_masks(any_of, none_of, nu)
         items = np.zeros((nu, max(int(k), 0)), dtype=np.uint32)
         scores = np.zeros((nu, max(int(k), 0)), dtype=np.float32)
         ep, ei = _exclusion_csr(exclude, nu)
-        _check(self._L.sbr_recommend_reps(self._h, _ptr(reps), nu, int(k) & 0xFFFFFFFF, None if ep is None else _ptr(ep),
-                                          None if ei is None else _ptr(ei), _ptr(items), _ptr(scores)))
+        if masks is None:
+            _check(self._L.sbr_recommend_reps(self._h, _ptr(reps), nu, int(k) & 0xFFFFFFFF, None if ep is None else _ptr(ep),
+                                              None if ei is None else _ptr(ei), _ptr(items), _ptr(scores)))
+        else:
+            _check(self._L.sbr_recommend_filtered_reps(self._h, _ptr(reps), nu, int(k) & 0xFFFFFFFF, None if ep is None else _ptr(ep),
+                                                       None if ei is None else _ptr(ei), _ptr(masks[0]), _ptr(masks[1]), _ptr(items),
+                                                       _ptr(scores)))
         return items, scores
 
     def diverse_max_pool(self) -> int:
@@ -603,49 +655,71 @@ class Model:
         return n.value
 
     def recommend_diverse(self, user_ptr, item_ids, k: int, pool: int, trade_off: float = 0.5, metric="cosine",
-                          include_history: bool = False):
+                          include_history: bool = False, any_of=None, none_of=None):
         """Diversified top-k (sbr_recommend_diverse): from the ``pool`` best items of each history — recommend's row at k = pool —
         k are picked greedily by maximal marginal relevance, trade_off * score - (1 - trade_off) * (the largest similarity to an
         item picked before), the first pick being the best item.  Items [U, k] u32 in pick order and their scores [U, k] f32
         (recommend's bits); short rows padded with (RECOMMEND_NO_ITEM, -inf).  metric: similar_items' "cosine" or "dot".
-        trade_off = 1 is recommend(k); pool == k reorders it.  k <= pool <= diverse_max_pool()."""
+        trade_off = 1 is recommend(k); pool == k reorders it.  k <= pool <= diverse_max_pool().  any_of / none_of: recommend's
+        tag filter; the pool is then the filtered row."""
         up = np.ascontiguousarray(user_ptr, dtype=np.uint64)
         it = np.ascontiguousarray(item_ids, dtype=np.uint32)
         nu = max(len(up) - 1, 0)
+        masks = _tag_masks(any_of, none_of, nu)
         items = np.zeros((nu, max(int(k), 0)), dtype=np.uint32)
         scores = np.zeros((nu, max(int(k), 0)), dtype=np.float32)
         flags = RECOMMEND_INCLUDE_HISTORY if include_history else 0
-        _check(self._L.sbr_recommend_diverse(self._h, _ptr(up), _ptr(it), nu, int(k) & 0xFFFFFFFF, int(pool) & 0xFFFFFFFF, float(trade_off),
-                                             _similar_metric(metric), flags, _ptr(items), _ptr(scores)))
+        if masks is None:
+            _check(self._L.sbr_recommend_diverse(self._h, _ptr(up), _ptr(it), nu, int(k) & 0xFFFFFFFF, int(pool) & 0xFFFFFFFF,
+                                                 float(trade_off), _similar_metric(metric), flags, _ptr(items), _ptr(scores)))
+        else:
+            _check(self._L.sbr_recommend_diverse_filtered(self._h, _ptr(up), _ptr(it), nu, int(k) & 0xFFFFFFFF, int(pool) & 0xFFFFFFFF,
+                                                          float(trade_off), _similar_metric(metric), flags, _ptr(masks[0]),
+                                                          _ptr(masks[1]), _ptr(items), _ptr(scores)))
         return items, scores
 
-    def recommend_diverse_reps(self, reps, k: int, pool: int, trade_off: float = 0.5, metric="cosine", exclude=None):
+    def recommend_diverse_reps(self, reps, k: int, pool: int, trade_off: float = 0.5, metric="cosine", exclude=None, any_of=None,
+                               none_of=None):
         """As recommend_diverse, from representations [U, embedding_dim]; exclude: None or one sequence of item ids per user."""
         reps = np.ascontiguousarray(reps, dtype=np.float32).reshape(-1, self.dim)
         nu = reps.shape[0]
+        masks = _tag_masks(any_of, none_of, nu)
         items = np.zeros((nu, max(int(k), 0)), dtype=np.uint32)
         scores = np.zeros((nu, max(int(k), 0)), dtype=np.float32)
         ep, ei = _exclusion_csr(exclude, nu)
-        _check(self._L.sbr_recommend_diverse_reps(self._h, _ptr(reps), nu, int(k) & 0xFFFFFFFF, int(pool) & 0xFFFFFFFF, float(trade_off),
-                                                  _similar_metric(metric), None if ep is None else _ptr(ep),
-                                                  None if ei is None else _ptr(ei), _ptr(items), _ptr(scores)))
+        if masks is None:
+            _check(self._L.sbr_recommend_diverse_reps(self._h, _ptr(reps), nu, int(k) & 0xFFFFFFFF, int(pool) & 0xFFFFFFFF,
+                                                      float(trade_off), _similar_metric(metric), None if ep is None else _ptr(ep),
+                                                      None if ei is None else _ptr(ei), _ptr(items), _ptr(scores)))
+        else:
+            _check(self._L.sbr_recommend_diverse_filtered_reps(self._h, _ptr(reps), nu, int(k) & 0xFFFFFFFF, int(pool) & 0xFFFFFFFF,
+                                                               float(trade_off), _similar_metric(metric),
+                                                               None if ep is None else _ptr(ep), None if ei is None else _ptr(ei),
+                                                               _ptr(masks[0]), _ptr(masks[1]), _ptr(items), _ptr(scores)))
         return items, scores
 
-    def similar_items(self, query_items, k: int, metric="cosine", include_self: bool = False, exclude=None):
+    def similar_items(self, query_items, k: int, metric="cosine", include_self: bool = False, exclude=None, any_of=None, none_of=None):
         """Exact top-k neighbours of each query item among the whole catalogue (sbr_similar_items): items [Q, k] u32 and scores
         [Q, k] f32, score descending, ties to the lower id; short rows padded with (RECOMMEND_NO_ITEM, -inf).  metric: "cosine"
         (of the item embeddings; a zero row has similarity 0 with everything) or "dot" (their plain dot product) — the item bias
         takes no part in either.  The query itself is left out of its row unless include_self; exclude: None or one sequence of
-        item ids per query.  Queries may repeat."""
+        item ids per query.  Queries may repeat.  any_of / none_of: recommend's tag filter with one mask pair per query
+        (sbr_similar_items_filtered: "similar items of the same category")."""
         q = np.ascontiguousarray(query_items, dtype=np.uint32).ravel()
         metric = _similar_metric(metric)
         nq = q.size
+        masks = _tag_masks(any_of, none_of, nq)
         items = np.zeros((nq, max(int(k), 0)), dtype=np.uint32)
         scores = np.zeros((nq, max(int(k), 0)), dtype=np.float32)
         ep, ei = _exclusion_csr(exclude, nq)
-        _check(self._L.sbr_similar_items(self._h, _ptr(q), nq, int(k) & 0xFFFFFFFF, metric,
-                                         SIMILAR_INCLUDE_SELF if include_self else 0, None if ep is None else _ptr(ep),
-                                         None if ei is None else _ptr(ei), _ptr(items), _ptr(scores)))
+        flags = SIMILAR_INCLUDE_SELF if include_self else 0
+        if masks is None:
+            _check(self._L.sbr_similar_items(self._h, _ptr(q), nq, int(k) & 0xFFFFFFFF, metric, flags, None if ep is None else _ptr(ep),
+                                             None if ei is None else _ptr(ei), _ptr(items), _ptr(scores)))
+        else:
+            _check(self._L.sbr_similar_items_filtered(self._h, _ptr(q), nq, int(k) & 0xFFFFFFFF, metric, flags,
+                                                      None if ep is None else _ptr(ep), None if ei is None else _ptr(ei),
+                                                      _ptr(masks[0]), _ptr(masks[1]), _ptr(items), _ptr(scores)))
         return items, scores
 
     def user_representations(self, user_ptr, item_ids) -> np.ndarray:
@@ -839,27 +913,42 @@ class Sessions:
         _check(self._L.sbr_sessions_representations(self._h, _ptr(sl), sl.size, _ptr(out)))
         return out
 
-    def recommend(self, slots, k: int, exclude=None):
+    def recommend(self, slots, k: int, exclude=None, any_of=None, none_of=None):
         """``Model.recommend_reps(self.representations(slots), k, exclude)`` with the scan reading the store's rows in place: items
-        [n, k] u32, scores [n, k] f32.  The store keeps no item history: ``exclude`` is None or one sequence of item ids per slot."""
+        [n, k] u32, scores [n, k] f32.  The store keeps no item history: ``exclude`` is None or one sequence of item ids per slot.
+        any_of / none_of: ``Model.recommend``'s tag filter, one mask pair per slot of the call."""
         sl = self._slots(slots)
+        masks = _tag_masks(any_of, none_of, sl.size)
         items = np.zeros((sl.size, max(int(k), 0)), dtype=np.uint32)
         scores = np.zeros((sl.size, max(int(k), 0)), dtype=np.float32)
         ep, ei = _exclusion_csr(exclude, sl.size)
-        _check(self._L.sbr_sessions_recommend(self._h, _ptr(sl), sl.size, int(k) & 0xFFFFFFFF, None if ep is None else _ptr(ep),
-                                              None if ei is None else _ptr(ei), 0, _ptr(items), _ptr(scores)))
+        if masks is None:
+            _check(self._L.sbr_sessions_recommend(self._h, _ptr(sl), sl.size, int(k) & 0xFFFFFFFF, None if ep is None else _ptr(ep),
+                                                  None if ei is None else _ptr(ei), 0, _ptr(items), _ptr(scores)))
+        else:
+            _check(self._L.sbr_sessions_recommend_filtered(self._h, _ptr(sl), sl.size, int(k) & 0xFFFFFFFF,
+                                                           None if ep is None else _ptr(ep), None if ei is None else _ptr(ei), 0,
+                                                           _ptr(masks[0]), _ptr(masks[1]), _ptr(items), _ptr(scores)))
         return items, scores
 
-    def recommend_diverse(self, slots, k: int, pool: int, trade_off: float = 0.5, metric="cosine", exclude=None):
+    def recommend_diverse(self, slots, k: int, pool: int, trade_off: float = 0.5, metric="cosine", exclude=None, any_of=None,
+                          none_of=None):
         """``Model.recommend_diverse_reps(self.representations(slots), k, pool, ...)`` with the scan reading the store's rows in
         place: items [n, k] u32 in pick order, scores [n, k] f32."""
         sl = self._slots(slots)
+        masks = _tag_masks(any_of, none_of, sl.size)
         items = np.zeros((sl.size, max(int(k), 0)), dtype=np.uint32)
         scores = np.zeros((sl.size, max(int(k), 0)), dtype=np.float32)
         ep, ei = _exclusion_csr(exclude, sl.size)
-        _check(self._L.sbr_sessions_recommend_diverse(self._h, _ptr(sl), sl.size, int(k) & 0xFFFFFFFF, int(pool) & 0xFFFFFFFF,
-                                                      float(trade_off), _similar_metric(metric), None if ep is None else _ptr(ep),
-                                                      None if ei is None else _ptr(ei), _ptr(items), _ptr(scores)))
+        if masks is None:
+            _check(self._L.sbr_sessions_recommend_diverse(self._h, _ptr(sl), sl.size, int(k) & 0xFFFFFFFF, int(pool) & 0xFFFFFFFF,
+                                                          float(trade_off), _similar_metric(metric), None if ep is None else _ptr(ep),
+                                                          None if ei is None else _ptr(ei), _ptr(items), _ptr(scores)))
+        else:
+            _check(self._L.sbr_sessions_recommend_diverse_filtered(self._h, _ptr(sl), sl.size, int(k) & 0xFFFFFFFF, int(pool) & 0xFFFFFFFF,
+                                                                   float(trade_off), _similar_metric(metric),
+                                                                   None if ep is None else _ptr(ep), None if ei is None else _ptr(ei),
+                                                                   _ptr(masks[0]), _ptr(masks[1]), _ptr(items), _ptr(scores)))
         return items, scores
 
     def score_candidates(self, slots, candidates):

@@ -240,16 +240,32 @@ class _ImplicitSequenceModel:
         up[1:] = np.cumsum([s.size for s in seqs])
         return up, (np.concatenate(seqs) if seqs else np.zeros(0, dtype=np.uint32))
 
-    def recommend(self, interactions_or_histories, k: int, exclude_history: bool = True, among=None):
+    def set_item_tags(self, tags):
+        """One 32-bit tag word per item for the ``any_of=`` / ``none_of=`` filters of ``recommend``, ``recommend_diverse``,
+        ``similar_items`` and the session calls, kept on the device; ``None`` clears them.  Tags are serving metadata: ``fit``
+        leaves them alone and ``save`` does not write them — set them again after ``load``."""
+        self.params.set_item_tags(tags)
+        return self
+
+    def item_tags(self) -> np.ndarray:
+        """The tag words last set (u32 [num_items]); raises while the model has none."""
+        return self.params.item_tags()
+
+    def recommend(self, interactions_or_histories, k: int, exclude_history: bool = True, among=None, any_of=None, none_of=None):
         """The k best items of the whole catalogue for each user's history, on the device: (items [U, k] u32, scores
         [U, k] f32), score descending, ties to the lower item id.  ``interactions_or_histories`` is a
         CompressedInteractions or a list of item-id sequences.  Every item of a history is excluded unless
         ``exclude_history`` is False; a row with fewer than k eligible items is padded with (0xFFFFFFFF, -inf).
         ``among``: None, or the item ids the answer is restricted to (in stock, one category, ...; any order, duplicates
-        allowed) — the exact top k of that set, found by scanning its rows only."""
+        allowed) — the exact top k of that set, found by scanning its rows only.
+        ``any_of`` / ``none_of``: the per-user tag filter against ``set_item_tags`` — a u32 mask per user, or one for all: item
+        i is eligible for user u iff ``tags[i] & none_of[u] == 0 and (any_of[u] == 0 or tags[i] & any_of[u] != 0)`` (territory,
+        rating, tier, in stock, "not this category"), tested inside the scan.  Not together with ``among`` yet."""
         up, it = self._csr(interactions_or_histories)
         if among is None:
-            return self.params.recommend(up, it, k, include_history=not exclude_history)
+            return self.params.recommend(up, it, k, include_history=not exclude_history, any_of=any_of, none_of=none_of)
+        if any_of is not None or none_of is not None:
+            raise ValueError("a tag filter together with among= is not supported: filter the item set instead")
         return self.params.recommend_among(up, it, k, among, include_history=not exclude_history)
 
     def user_representations(self, histories) -> np.ndarray:
@@ -276,24 +292,29 @@ class _ImplicitSequenceModel:
             out.append((ids[order], sc[order]))
         return out
 
-    def similar_items(self, query_items, k: int, metric: str = "cosine", include_self: bool = False, exclude=None):
+    def similar_items(self, query_items, k: int, metric: str = "cosine", include_self: bool = False, exclude=None, any_of=None,
+                      none_of=None):
         """The k items most like each query item, on the device: (items [Q, k] u32, scores [Q, k] f32), by the cosine of the
         item embeddings (``metric="dot"``: their dot product), score descending, ties to the lower item id.  The query is left
         out of its own row unless ``include_self``; ``exclude``: None or one sequence of item ids per query; a row with fewer
-        than k eligible items is padded with (0xFFFFFFFF, -inf)."""
-        return self.params.similar_items(query_items, k, metric=metric, include_self=include_self, exclude=exclude)
+        than k eligible items is padded with (0xFFFFFFFF, -inf).  ``any_of`` / ``none_of``: ``recommend``'s tag filter with one
+        mask pair per query."""
+        return self.params.similar_items(query_items, k, metric=metric, include_self=include_self, exclude=exclude, any_of=any_of,
+                                         none_of=none_of)
 
     def recommend_diverse(self, interactions_or_histories, k: int, pool=None, trade_off: float = 0.5, metric: str = "cosine",
-                          exclude_history: bool = True):
+                          exclude_history: bool = True, any_of=None, none_of=None):
         """``recommend`` without the near-duplicates, on the device: from each user's ``pool`` best items, k are picked greedily by
         maximal marginal relevance — ``trade_off`` * score - (1 - ``trade_off``) * (the largest similarity to an item already
         picked), similarity as ``similar_items`` measures it; the first pick is the best item.  (items [U, k] u32 in pick order,
         scores [U, k] f32, ``recommend``'s bits.)  ``pool=None``: min(4 k, the largest pool the device holds for this embedding
-        width, ``params.diverse_max_pool()``); ``trade_off=1`` is ``recommend(k)``."""
+        width, ``params.diverse_max_pool()``); ``trade_off=1`` is ``recommend(k)``.  ``any_of`` / ``none_of``: ``recommend``'s tag
+        filter; the pool then holds eligible items only."""
         up, it = self._csr(interactions_or_histories)
         if pool is None:
             pool = min(4 * int(k), self.params.diverse_max_pool())
-        return self.params.recommend_diverse(up, it, k, pool, trade_off=trade_off, metric=metric, include_history=not exclude_history)
+        return self.params.recommend_diverse(up, it, k, pool, trade_off=trade_off, metric=metric, include_history=not exclude_history,
+                                             any_of=any_of, none_of=none_of)
 
     def sessions(self, capacity: int):
         """A session store of ``capacity`` slots on the device (``engine.Sessions``): each slot holds one user's recurrent state,
