@@ -536,11 +536,16 @@ inline std::vector<std::uint32_t> narrow(const std::vector<ItemId>& ids) {
 /// (an empty slot: of the empty history) while they are at most max_sequence_length; beyond that a session keeps the recurrence
 /// over everything appended where the windowed call truncates.  After the model's parameters change (`fit`, a restored
 /// checkpoint) every call but `reset_all` throws EngineError(SBR_ERR_INVALID_ARGUMENT) until `reset_all` re-binds the store.
+/// With a seen-item memory (`seen_capacity` > 0) a slot also remembers, on the device, the last seen_capacity items appended
+/// to it since its last reset, in append order with repeats; `reset`, `reset_all` and `set_state` empty it, `set_seen` restores it.
+/// The recommend calls of such a store exclude each slot's remembered items, united with the caller's lists, as
+/// ImplicitSequenceModel::recommend excludes the history; `score_candidates` masks nothing.
 /// Obtained from ImplicitSequenceModel::sessions; the model must outlive it.  Movable, not copyable.
 class Sessions {
   public:
-    Sessions(sbr_model* model, std::size_t capacity, std::size_t embedding_dim) : dim_(embedding_dim) {
-        check(sbr_sessions_create(model, (std::uint64_t)capacity, &h_), "sbr_sessions_create");
+    Sessions(sbr_model* model, std::size_t capacity, std::size_t embedding_dim, std::size_t seen_capacity = 0) : dim_(embedding_dim) {
+        if (seen_capacity > SBR_SESSIONS_MAX_SEEN) throw EngineError(SBR_ERR_INVALID_ARGUMENT, "Sessions: seen_capacity above SBR_SESSIONS_MAX_SEEN");
+        check(sbr_sessions_create_seen(model, (std::uint64_t)capacity, (std::uint32_t)seen_capacity, &h_), "sbr_sessions_create_seen");
     }
     Sessions(const Sessions&) = delete;
     Sessions& operator=(const Sessions&) = delete;
@@ -556,6 +561,35 @@ class Sessions {
         check(sbr_sessions_capacity(h_, &c), "sbr_sessions_capacity");
         return (std::size_t)c;
     }
+    /// Items each slot remembers (0: a store without seen-item memory).
+    std::size_t seen_capacity() const {
+        std::uint32_t w = 0;
+        check(sbr_sessions_seen_capacity(h_, &w), "sbr_sessions_seen_capacity");
+        return (std::size_t)w;
+    }
+    /// The named slots' remembered items, oldest first, repeats kept (sbr_sessions_get_seen): slot i's are items[ptr[i] .. ptr[i + 1]).
+    struct Seen {
+        std::vector<std::uint64_t> ptr;
+        std::vector<std::uint32_t> items;
+    };
+    Seen seen(const std::vector<std::uint32_t>& slots) const {
+        Seen s;
+        s.ptr.assign(slots.size() + 1, 0);
+        s.items.resize(slots.size() * seen_capacity() + 1);
+        check(sbr_sessions_get_seen(h_, slots.data(), (std::uint64_t)slots.size(), s.ptr.data(), s.items.data()), "sbr_sessions_get_seen");
+        s.items.resize((std::size_t)s.ptr.back());
+        return s;
+    }
+    /// Replaces the named slots' memory with the last seen_capacity() items of each list (sbr_sessions_set_seen); after `set_state`
+    /// it completes the restore of a checkpoint taken with `get_state` + `seen`.
+    void set_seen(const std::vector<std::uint32_t>& slots, const std::vector<std::uint64_t>& ptr, const std::vector<std::uint32_t>& items) {
+        if (ptr.size() != slots.size() + 1 || ptr.back() > items.size())
+            throw EngineError(SBR_ERR_INVALID_ARGUMENT, "Sessions::set_seen: one item range per slot");
+        const std::uint32_t none = 0;
+        check(sbr_sessions_set_seen(h_, slots.data(), (std::uint64_t)slots.size(), ptr.data(), items.empty() ? &none : items.data()),
+              "sbr_sessions_set_seen");
+    }
+    void set_seen(const std::vector<std::uint32_t>& slots, const Seen& s) { set_seen(slots, s.ptr, s.items); }
     /// Appends item_ids[item_ptr[i] .. item_ptr[i + 1]), in order, to slot slots[i].
     void append(const std::vector<std::uint32_t>& slots, const std::vector<std::uint64_t>& item_ptr, const std::vector<std::uint32_t>& item_ids) {
         if (item_ptr.size() != slots.size() + 1 || item_ptr.back() > item_ids.size())
@@ -583,11 +617,12 @@ class Sessions {
     /// Every slot emptied and the store re-bound to the model's current parameters.
     void reset_all() { check(sbr_sessions_reset_all(h_), "sbr_sessions_reset_all"); }
     /// The k best items of the whole catalogue for each slot's state, read in place (sbr_sessions_recommend): ordered and padded as
-    /// ImplicitSequenceModel::recommend's rows.  The store keeps no item history: slot i's excluded items are
-    /// excl_items[excl_ptr[i] .. excl_ptr[i + 1]) (both empty: none).
+    /// ImplicitSequenceModel::recommend's rows.  Slot i's excluded items are excl_items[excl_ptr[i] .. excl_ptr[i + 1]) (both
+    /// empty: none), united with the slot's remembered items on a store with seen-item memory unless `include_seen` (which a
+    /// store without memory refuses).
     Result<Recommendations, PredictionError> recommend(const std::vector<std::uint32_t>& slots, std::size_t k,
                                                        const std::vector<std::uint64_t>& excl_ptr = {},
-                                                       const std::vector<std::uint32_t>& excl_items = {}) const {
+                                                       const std::vector<std::uint32_t>& excl_items = {}, bool include_seen = false) const {
         if (k < 1 || k > SBR_RECOMMEND_MAX_K) throw EngineError(SBR_ERR_INVALID_ARGUMENT, "Sessions::recommend: k outside 1..SBR_RECOMMEND_MAX_K");
         if (!excl_ptr.empty() && (excl_ptr.size() != slots.size() + 1 || excl_ptr.back() > excl_items.size()))
             throw EngineError(SBR_ERR_INVALID_ARGUMENT, "Sessions::recommend: one exclusion range per slot");
@@ -599,8 +634,8 @@ class Sessions {
         const std::uint32_t none = 0;
         const sbr_status st = sbr_sessions_recommend(h_, slots.data(), (std::uint64_t)slots.size(), (std::uint32_t)k,
                                                      excl_ptr.empty() ? nullptr : excl_ptr.data(),
-                                                     excl_ptr.empty() ? nullptr : (excl_items.empty() ? &none : excl_items.data()), 0u,
-                                                     r.items.data(), r.scores.data());
+                                                     excl_ptr.empty() ? nullptr : (excl_items.empty() ? &none : excl_items.data()),
+                                                     include_seen ? SBR_RECOMMEND_INCLUDE_HISTORY : 0u, r.items.data(), r.scores.data());
         if (st == SBR_ERR_INVALID_PREDICTION) return Result<Recommendations, PredictionError>::Err(PredictionError::InvalidPredictionValue);
         check(st, "sbr_sessions_recommend");
         return Result<Recommendations, PredictionError>::Ok(std::move(r));
@@ -632,7 +667,7 @@ class Sessions {
     /// `recommend` under a tag filter, one mask pair per slot of the call (sbr_sessions_recommend_filtered).
     Result<Recommendations, PredictionError> recommend_filtered(const std::vector<std::uint32_t>& slots, std::size_t k, const TagFilter& filter,
                                                        const std::vector<std::uint64_t>& excl_ptr = {},
-                                                       const std::vector<std::uint32_t>& excl_items = {}) const {
+                                                       const std::vector<std::uint32_t>& excl_items = {}, bool include_seen = false) const {
         if (k < 1 || k > SBR_RECOMMEND_MAX_K) throw EngineError(SBR_ERR_INVALID_ARGUMENT, "Sessions::recommend: k outside 1..SBR_RECOMMEND_MAX_K");
         if (!excl_ptr.empty() && (excl_ptr.size() != slots.size() + 1 || excl_ptr.back() > excl_items.size()))
             throw EngineError(SBR_ERR_INVALID_ARGUMENT, "Sessions::recommend: one exclusion range per slot");
@@ -646,8 +681,9 @@ class Sessions {
         const std::uint32_t none = 0;
         const sbr_status st = sbr_sessions_recommend_filtered(h_, slots.data(), (std::uint64_t)slots.size(), (std::uint32_t)k,
                                                               excl_ptr.empty() ? nullptr : excl_ptr.data(),
-                                                              excl_ptr.empty() ? nullptr : (excl_items.empty() ? &none : excl_items.data()), 0u,
-                                                              any.data(), none_of.data(), r.items.data(), r.scores.data());
+                                                              excl_ptr.empty() ? nullptr : (excl_items.empty() ? &none : excl_items.data()),
+                                                              include_seen ? SBR_RECOMMEND_INCLUDE_HISTORY : 0u, any.data(), none_of.data(),
+                                                              r.items.data(), r.scores.data());
         if (st == SBR_ERR_INVALID_PREDICTION) return Result<Recommendations, PredictionError>::Err(PredictionError::InvalidPredictionValue);
         check(st, "sbr_sessions_recommend_filtered");
         return Result<Recommendations, PredictionError>::Ok(std::move(r));
@@ -1051,6 +1087,11 @@ class ImplicitSequenceModel : public OnlineRankingModel<ImplicitUser> {
     /// A session store of `capacity` slots on the primary replica: device-resident user states advanced one appended item at a
     /// time (see Sessions).  Destroy it before this model.
     Sessions sessions(std::size_t capacity) const { return Sessions(replicas_->primary(), capacity, replicas_->hparams().embedding_dim); }
+    /// The same with a seen-item memory of `seen_capacity` items per slot (1 .. SBR_SESSIONS_MAX_SEEN; 0: the store above), which
+    /// the store's recommend calls exclude.
+    Sessions sessions(std::size_t capacity, std::size_t seen_capacity) const {
+        return Sessions(replicas_->primary(), capacity, replicas_->hparams().embedding_dim, seen_capacity);
+    }
 
     /// The engine handle (replica 0), for evaluation's fused path and for parameter access.
     sbr_model* handle() const { return replicas_->primary(); }

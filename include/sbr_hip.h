@@ -615,10 +615,34 @@ sbr_status sbr_rank_targets_reps(sbr_model* m, const float* reps, uint64_t num_u
  *                                [n]; a restored len of 0 is the empty slot (zero state, whatever h holds)
  *   sbr_sessions_recommend / _score_candidates   sbr_recommend_reps / sbr_score_candidates_reps on sbr_sessions_representations of
  *                                the same slots — results, padding, errors, non-finite handling, bit for bit — with the scan reading
- *                                the store's rows in place.  The store keeps no item history: exclusions are the caller's lists.
- * The other scans are reached through sbr_sessions_representations and the *_reps calls. */
+ *                                the store's rows in place.  A store without seen-item memory keeps no item history: exclusions
+ *                                are the caller's lists.
+ * The other scans are reached through sbr_sessions_representations and the *_reps calls.
+ *
+ * SEEN-ITEM MEMORY: sbr_sessions_create_seen makes a store whose slots also remember the last seen_capacity items appended to them
+ * since their last reset (1 <= seen_capacity <= SBR_SESSIONS_MAX_SEEN; capacity * seen_capacity * 4 more bytes on the device;
+ * seen_capacity = 0 is sbr_sessions_create), in append order, repeats kept: a ring of u32 ids and a u64 count per slot, written on
+ * the device by the call that appends (of more than seen_capacity items to one slot in one call, the last seen_capacity).
+ * sbr_sessions_reset, _reset_all and _set_state empty the memory of the slots they touch (a restored state's items are unknown);
+ * the empty-history row has none.  On such a store sbr_sessions_recommend, _recommend_filtered, _recommend_diverse and
+ * _recommend_diverse_filtered exclude each slot's remembered items as sbr_recommend excludes the history — the result is, bit
+ * for bit, the *_reps call on sbr_sessions_representations with user i's list = sbr_sessions_get_seen of slot i united with the
+ * caller's list — and the two calls with `flags` accept SBR_RECOMMEND_INCLUDE_HISTORY, which ignores the memory for that call; on
+ * a store without memory flags other than 0 stay SBR_ERR_INVALID_ARGUMENT.  sbr_sessions_score_candidates masks nothing.
+ *   sbr_sessions_seen_capacity   *out = seen_capacity (0: no memory)
+ *   sbr_sessions_get_seen        slot slots[i]'s remembered items, oldest first, at out_items[out_ptr[i] .. out_ptr[i + 1]);
+ *                                out_ptr [n + 1] from 0, out_items holds n * seen_capacity ids
+ *   sbr_sessions_set_seen        slot slots[i]'s memory = the last seen_capacity of items[ptr[i] .. ptr[i + 1]) (ids validated as
+ *                                every CSR argument's); get_state + get_seen, then set_state + set_seen in that order, restore a
+ *                                slot exactly
+ * get_seen / set_seen on a store without memory: SBR_ERR_INVALID_ARGUMENT. */
+#define SBR_SESSIONS_MAX_SEEN 1024u
 typedef struct sbr_sessions sbr_sessions;
 sbr_status sbr_sessions_create(sbr_model* m, uint64_t capacity, sbr_sessions** out);
+sbr_status sbr_sessions_create_seen(sbr_model* m, uint64_t capacity, uint32_t seen_capacity, sbr_sessions** out);
+sbr_status sbr_sessions_seen_capacity(const sbr_sessions* st, uint32_t* out);
+sbr_status sbr_sessions_get_seen(sbr_sessions* st, const uint32_t* slots, uint64_t n, uint64_t* out_ptr, uint32_t* out_items);
+sbr_status sbr_sessions_set_seen(sbr_sessions* st, const uint32_t* slots, uint64_t n, const uint64_t* ptr, const uint32_t* items);
 void sbr_sessions_destroy(sbr_sessions* st);
 sbr_status sbr_sessions_capacity(const sbr_sessions* st, uint64_t* out);
 sbr_status sbr_sessions_reset(sbr_sessions* st, const uint32_t* slots, uint64_t n);
@@ -666,6 +690,7 @@ sbr_status sbr_model_set_counters(sbr_model* m, uint64_t global_epoch, uint64_t 
 /* Library / device identification ("gfx950", CU count, HBM bytes); device_name may be NULL. */
 sbr_status sbr_device_info(char* device_name, uint64_t name_bytes, uint32_t* out_cus, uint64_t* out_hbm_bytes);
 const char* sbr_status_string(sbr_status s);
+#define SBR_ABI_VERSION 13u /* what sbr_abi_version returns from a library built from this header */
 uint32_t sbr_abi_version(void);
 
 /* Scratch of a fit call (device and pinned-host blocks up to 64 MiB, at most 768 MiB of each kind per process) is kept for the

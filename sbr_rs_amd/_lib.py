@@ -139,6 +139,10 @@ def load():
         "sbr_test_delays_queued": [vp, u64p],
         "sbr_selftest_stream_delay": [C.c_uint32, C.c_int32, fp],
         "sbr_sessions_create": [vp, C.c_uint64, C.POINTER(vp)],
+        "sbr_sessions_create_seen": [vp, C.c_uint64, C.c_uint32, C.POINTER(vp)],
+        "sbr_sessions_seen_capacity": [vp, u32p],
+        "sbr_sessions_get_seen": [vp, vp, C.c_uint64, vp, vp],
+        "sbr_sessions_set_seen": [vp, vp, C.c_uint64, vp, vp],
         "sbr_sessions_capacity": [vp, u64p],
         "sbr_sessions_reset": [vp, vp, C.c_uint64],
         "sbr_sessions_reset_all": [vp],
@@ -214,4 +218,5 @@ DECLARED_SYMBOLS = [
     "sbr_model_set_item_tags", "sbr_model_get_item_tags", "sbr_recommend_filtered", "sbr_recommend_filtered_reps",
     "sbr_recommend_diverse_filtered", "sbr_recommend_diverse_filtered_reps", "sbr_similar_items_filtered",
     "sbr_sessions_recommend_filtered", "sbr_sessions_recommend_diverse_filtered",
+    "sbr_sessions_create_seen", "sbr_sessions_seen_capacity", "sbr_sessions_get_seen", "sbr_sessions_set_seen",
 ]

@@ -126,6 +126,15 @@ def build_sessions_tests(force: bool = False, verbose: bool = True) -> str:
     return _build_cpp_program(SESSIONS_SRC, SESSIONS_BIN, force, verbose)
 
 
+SESSIONS_SEEN_SRC = os.path.join(REPO, "tests", "cpp", "sessions_seen_tests.cpp")
+SESSIONS_SEEN_BIN = os.path.join(REPO, "tests", "cpp", "_build", "sessions_seen_tests")
+
+
+def build_sessions_seen_tests(force: bool = False, verbose: bool = True) -> str:
+    """g++ build of the C++ host layer's test program of the session store's seen-item memory."""
+    return _build_cpp_program(SESSIONS_SEEN_SRC, SESSIONS_SEEN_BIN, force, verbose)
+
+
 RANKING_SRC = os.path.join(REPO, "tests", "cpp", "ranking_tests.cpp")
 RANKING_BIN = os.path.join(REPO, "tests", "cpp", "_build", "ranking_tests")
 
@@ -153,4 +162,5 @@ if __name__ == "__main__":
     print(build_diverse_tests(force="--force" in sys.argv))
     print(build_candidates_tests(force="--force" in sys.argv))
     print(build_sessions_tests(force="--force" in sys.argv))
+    print(build_sessions_seen_tests(force="--force" in sys.argv))
     print(build_filtered_tests(force="--force" in sys.argv))

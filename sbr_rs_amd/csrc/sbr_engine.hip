@@ -922,7 +922,7 @@ sbr_status ensure_device(const sbr_model* m) {
 
 extern "C" {
 
-uint32_t sbr_abi_version(void) { return 12; }
+uint32_t sbr_abi_version(void) { return SBR_ABI_VERSION; }
 
 void sbr_release_cached_memory(void) { scratch_cache().trim(); }
 
@@ -3621,7 +3621,9 @@ sbr_status check_csr(const sbr_model* m, const uint64_t* ptr, uint64_t n, const 
 /* Where a call's user representations come from: the histories ptr / items (the recurrent forward runs), the rows `reps`
  * ([users, embedding_dim]) of the caller, rows the device makes from the item table, user u's from item item_rows[u]
  * (similar_items), or rows that already lie on the device at the storage width, user u's row dev_row[u] of dev_rows (a session
- * store: read in place); in the last three cases ptr / items are the exclusion lists (ptr null: none). */
+ * store: read in place); in the last three cases ptr / items are the exclusion lists (ptr null: none).  With `seen` (a session
+ * store's seen-item memory; only with device rows, and only recommend_scan reads it) the device unites user u's list with what
+ * slot seen_slots[u] remembers. */
 struct RepSource {
     const uint64_t* ptr;
     const uint32_t* items;
@@ -3631,6 +3633,8 @@ struct RepSource {
     const uint32_t* item_rows = nullptr; /* non-null: the rows come from these item ids, on the device */
     const float* dev_rows = nullptr;     /* non-null: device rows [.][storage width], read in place ... */
     const int* dev_row = nullptr;        /* ... user u's is row dev_row[u] */
+    const sbr::SeenView* seen = nullptr; /* non-null: lists come from a store's memory as well ... */
+    const uint32_t* seen_slots = nullptr; /* ... user u's (the CALL's index) from this slot */
     bool from_histories() const { return !reps && !item_rows && !dev_rows; }
 };
 
@@ -3950,11 +3954,16 @@ struct TagFilterArg {
  * With `dv` (recommend_diverse; not with item rows or a subset) the scan's rows are the users' pools: the same launch selects
  * dv->k_out of each, and the results are num_users x dv->k_out.
  * With `flt` (not with a subset) the scan offers user u only the items its masks allow against the model's item tags, which must be
- * set; the masks go with the call's user u through the chunks, whatever row of H holds its representation. */
+ * set; the masks go with the call's user u through the chunks, whatever row of H holds its representation.
+ * With s.seen (a session store's memory; not with a subset) the exclusion CSR is made on the device: user i of a chunk has the
+ * segment [i w + c_i, (i + 1) w + c_(i + 1)), c = the chunk's caller-list pointers — known to the host without any device-side
+ * count — which session_seen_lists_kernel fills, ahead of the scan, with the merge of the slot's memory and the caller's list. */
 sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, uint32_t k, uint32_t* out_items, float* out_scores,
                           bool cosine = false, const std::vector<uint32_t>* subset = nullptr, const Diverse* dv = nullptr,
                           const TagFilterArg* flt = nullptr) {
     if (flt && (!m->item_tags || subset)) return SBR_ERR_INVALID_ARGUMENT;
+    if (s.seen && subset) return SBR_ERR_INVALID_ARGUMENT;
+    const size_t seen_w = s.seen ? s.seen->w : 0;
     std::vector<uint64_t> users(num_users);
     for (uint64_t u = 0; u < num_users; ++u) users[u] = u;
     const uint32_t scanned_items = subset ? (uint32_t)subset->size() : (uint32_t)m->hp.num_items;
@@ -3967,8 +3976,13 @@ sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, 
         float* rnorm = nullptr; /* item rows: the catalogue's reciprocal norms, once per chunk (the arena does not outlive a carve) */
         uint32_t* dv_items = nullptr; /* dv: the selection's rows, nu x dv->k_out */
         float* dv_scores = nullptr;
+        uint32_t *seen_slot = nullptr, *seen_caller = nullptr; /* s.seen: the chunk's slots and caller lists, the build kernel's inputs */
         SBRCHK(user_reps(m, s, ch.users, [&](DeviceArena& ar) {
-            tb.carve(ar, scanned_items, nu, ur.b.list_items.size(), k, flt != nullptr);
+            tb.carve(ar, scanned_items, nu, nu * seen_w + ur.b.list_items.size(), k, flt != nullptr);
+            if (s.seen) {
+                seen_slot = ar.take<uint32_t>(nu);
+                seen_caller = ar.take<uint32_t>(ur.b.list_items.size() + 1);
+            }
             if (s.item_rows) rnorm = ar.take<float>(m->hp.num_items);
             if (subset) sb.carve(ar, subset->size(), (size_t)m->d);
             if (dv) {
@@ -3976,13 +3990,24 @@ sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, 
                 dv_scores = ar.take<float>(nu * dv->k_out);
             }
         }, &ur));
-        const bool excl = !ur.b.list_ptr.empty();
+        const bool excl = !ur.b.list_ptr.empty() || s.seen;
+        std::vector<uint64_t> seen_eptr; /* s.seen: the segments' bounds and the chunk's slots, read by asynchronous copies */
+        std::vector<uint32_t> seen_slots;
         if (subset) {
             if (excl) lists_to_subset_positions(*subset, &ur.b.list_ptr, &ur.b.list_items);
             HIPCHK(hipMemcpyAsync(sb.ids, subset->data(), subset->size() * 4, hipMemcpyHostToDevice, m->stream));
         }
         HIPCHK(hipMemcpyAsync(tb.rep, ur.rep_row.data(), nu * 4, hipMemcpyHostToDevice, m->stream));
-        if (excl) {
+        if (s.seen) {
+            seen_eptr.resize(nu + 1);
+            seen_slots.resize(nu);
+            for (size_t i = 0; i <= nu; ++i) seen_eptr[i] = i * seen_w + (ur.b.list_ptr.empty() ? 0 : ur.b.list_ptr[i]);
+            for (size_t i = 0; i < nu; ++i) seen_slots[i] = s.seen_slots[ch.users[i]]; /* the call's index, not the chunk's */
+            HIPCHK(hipMemcpyAsync(seen_slot, seen_slots.data(), nu * 4, hipMemcpyHostToDevice, m->stream));
+            HIPCHK(hipMemcpyAsync(tb.eptr, seen_eptr.data(), (nu + 1) * 8, hipMemcpyHostToDevice, m->stream));
+            if (!ur.b.list_items.empty())
+                HIPCHK(hipMemcpyAsync(seen_caller, ur.b.list_items.data(), ur.b.list_items.size() * 4, hipMemcpyHostToDevice, m->stream));
+        } else if (excl) {
             HIPCHK(hipMemcpyAsync(tb.eptr, ur.b.list_ptr.data(), (nu + 1) * 8, hipMemcpyHostToDevice, m->stream));
             if (!ur.b.list_items.empty())
                 HIPCHK(hipMemcpyAsync(tb.excl, ur.b.list_items.data(), ur.b.list_items.size() * 4, hipMemcpyHostToDevice, m->stream));
@@ -4000,7 +4025,8 @@ sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, 
             HIPCHK(hipMemcpyAsync(tb.none_of, masks.data() + nu, nu * 4, hipMemcpyHostToDevice, m->stream));
         }
         const size_t ko = dv ? dv->k_out : k; /* the width of the rows that leave */
-        SBRCHK(scan_launch(m, s.item_rows || subset ? 4 : dv ? 3 : 2, tb.flag, [&] {
+        SBRCHK(scan_launch(m, (s.item_rows || subset ? 4 : dv ? 3 : 2) + (s.seen ? 1 : 0), tb.flag, [&] {
+            if (s.seen) sbr::launch_session_seen_lists(*s.seen, seen_slot, (int)nu, tb.eptr, seen_caller, tb.excl, m->stream);
             if (dv) { /* the selection reads the pool's scores whether or not the caller wants any */
                 sbr::launch_recommend(m->mv, ur.H, tb.rep, (uint32_t)nu, excl ? tb.eptr : nullptr, tb.excl, k, tb.lists, tb.lens, tb.items,
                                       tb.scores, tb.flag, m->stream, f);
@@ -4473,6 +4499,7 @@ struct sbr_sessions {
     uint64_t gen = 0;       /* the model's param_gen the states were computed under (creation / the last reset_all) */
     sbr::SessionView v{nullptr, nullptr, nullptr}; /* rows [capacity + 1]: the last one is the empty-history row */
     std::vector<uint64_t> host_len; /* the host's copy of len, kept by every successful call: which slots read the empty-history row */
+    sbr::SeenView seen{nullptr, nullptr, 0}; /* seen-item memory: ring [capacity][w], cnt [capacity]; w == 0: none (and no launch of its kernels) */
 };
 
 namespace {
@@ -4529,26 +4556,30 @@ sbr_status sessions_append(sbr_sessions* st, const uint32_t* slots, uint64_t n, 
         }
     }
     sbr::SessionAppend a{};
-    uint32_t *d_slot = nullptr, *d_count = nullptr, *d_items = nullptr;
+    uint32_t *d_slot = nullptr, *d_count = nullptr, *d_items = nullptr, *d_raw = nullptr;
     unsigned long long* d_start = nullptr;
+    const bool remember = advance && st->seen.w; /* the ring writes read the call's ids session-major: EWMA's own arrays, a second copy for the LSTM */
     SBRCHK(carve_arena(m, [&](DeviceArena& ar) {
         d_slot = ar.take<uint32_t>(ns);
         d_count = ar.take<uint32_t>(ns);
         d_items = ar.take<uint32_t>(total);
         if (lstm) { a.Hs = ar.take<float>(2 * ns * d); a.Cs = ar.take<float>(2 * ns * d); }
         else d_start = ar.take<unsigned long long>(ns);
+        if (lstm && remember) { d_raw = ar.take<uint32_t>(total); d_start = ar.take<unsigned long long>(ns); }
     }));
     HIPCHK(hipMemcpyAsync(d_slot, slot.data(), ns * 4, hipMemcpyHostToDevice, m->stream));
     HIPCHK(hipMemcpyAsync(d_count, count.data(), ns * 4, hipMemcpyHostToDevice, m->stream));
     HIPCHK(hipMemcpyAsync(d_items, lstm ? packed.data() : ids + ptr[0], total * 4, hipMemcpyHostToDevice, m->stream));
-    if (!lstm) HIPCHK(hipMemcpyAsync(d_start, start.data(), ns * 8, hipMemcpyHostToDevice, m->stream));
+    if (!lstm || remember) HIPCHK(hipMemcpyAsync(d_start, start.data(), ns * 8, hipMemcpyHostToDevice, m->stream));
+    if (lstm && remember) HIPCHK(hipMemcpyAsync(d_raw, ids + ptr[0], total * 4, hipMemcpyHostToDevice, m->stream));
     a.n = (int)ns; a.tm = tm;
     a.slot = d_slot; a.count = d_count; a.items = d_items; a.start = d_start;
     a.off_host = off.data();
     a.advance = advance;
     {
-        ScopedTimer t(m, SBR_K_RECURRENT_FWD, lstm ? (uint64_t)tm + 1 : 1);
+        ScopedTimer t(m, SBR_K_RECURRENT_FWD, (lstm ? (uint64_t)tm + 1 : 1) + (remember ? 1 : 0));
         if (sbr::launch_session_append(m->mv, st->v, a, m->stream) < 0) return SBR_ERR_UNSUPPORTED;
+        if (remember) sbr::launch_session_seen_append(st->seen, d_slot, d_start, d_count, lstm ? d_raw : d_items, (int)ns, m->stream);
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(m->stream)); /* the host vectors are read by the asynchronous copies above */
@@ -4564,6 +4595,7 @@ sbr_status sessions_rebind(sbr_sessions* st) {
     HIPCHK(hipMemsetAsync(st->v.H, 0, rows * d * 4, m->stream));
     if (st->v.C) HIPCHK(hipMemsetAsync(st->v.C, 0, rows * d * 4, m->stream));
     HIPCHK(hipMemsetAsync(st->v.len, 0, rows * 8, m->stream));
+    if (st->seen.w) HIPCHK(hipMemsetAsync(st->seen.cnt, 0, (size_t)st->capacity * 8, m->stream)); /* every memory empty; the ring needs no clearing */
     std::fill(st->host_len.begin(), st->host_len.end(), 0);
     const uint32_t row = (uint32_t)st->capacity, item0 = 0; /* one step of item 0 from zero (lstm.rs:262-264); not a length */
     const uint64_t ptr[2] = {0, 1};
@@ -4607,8 +4639,10 @@ sbr_status sessions_gather(sbr_sessions* st, const uint32_t* rows, uint64_t n, f
 
 extern "C" {
 
-sbr_status sbr_sessions_create(sbr_model* m, uint64_t capacity, sbr_sessions** out) {
-    if (!m || !out || capacity == 0 || capacity > sessions_max_capacity) return SBR_ERR_INVALID_ARGUMENT;
+sbr_status sbr_sessions_create(sbr_model* m, uint64_t capacity, sbr_sessions** out) { return sbr_sessions_create_seen(m, capacity, 0, out); }
+
+sbr_status sbr_sessions_create_seen(sbr_model* m, uint64_t capacity, uint32_t seen_capacity, sbr_sessions** out) {
+    if (!m || !out || capacity == 0 || capacity > sessions_max_capacity || seen_capacity > SBR_SESSIONS_MAX_SEEN) return SBR_ERR_INVALID_ARGUMENT;
     *out = nullptr;
     std::lock_guard<std::mutex> lock(m->mu);
     SBRCHK(enter_reader(m));
@@ -4620,13 +4654,16 @@ sbr_status sbr_sessions_create(sbr_model* m, uint64_t capacity, sbr_sessions** o
     sbr_status s = dmalloc(&st->v.H, rows * d);
     if (s == SBR_OK && m->ng) s = dmalloc(&st->v.C, rows * d);
     if (s == SBR_OK) s = dmalloc(&st->v.len, rows);
+    if (s == SBR_OK && seen_capacity) s = dmalloc(&st->seen.ring, (size_t)capacity * seen_capacity);
+    if (s == SBR_OK && seen_capacity) s = dmalloc(&st->seen.cnt, (size_t)capacity);
     if (s == SBR_OK) {
+        st->seen.w = seen_capacity;
         st->host_len.assign(capacity, 0);
         s = sessions_rebind(st);
     }
     if (s != SBR_OK) {
         hipStreamSynchronize(m->stream);
-        dfree(st->v.H); dfree(st->v.C); dfree(st->v.len);
+        dfree(st->v.H); dfree(st->v.C); dfree(st->v.len); dfree(st->seen.ring); dfree(st->seen.cnt);
         delete st;
         return s;
     }
@@ -4640,7 +4677,7 @@ void sbr_sessions_destroy(sbr_sessions* st) {
         std::lock_guard<std::mutex> lock(st->m->mu);
         hipSetDevice(st->m->device);
         hipStreamSynchronize(st->m->stream); /* the rows go back to the scratch cache: nothing may still read them */
-        dfree(st->v.H); dfree(st->v.C); dfree(st->v.len);
+        dfree(st->v.H); dfree(st->v.C); dfree(st->v.len); dfree(st->seen.ring); dfree(st->seen.cnt);
     }
     delete st;
 }
@@ -4648,6 +4685,12 @@ void sbr_sessions_destroy(sbr_sessions* st) {
 sbr_status sbr_sessions_capacity(const sbr_sessions* st, uint64_t* out) {
     if (!st || !out) return SBR_ERR_INVALID_ARGUMENT;
     *out = st->capacity;
+    return SBR_OK;
+}
+
+sbr_status sbr_sessions_seen_capacity(const sbr_sessions* st, uint32_t* out) {
+    if (!st || !out) return SBR_ERR_INVALID_ARGUMENT;
+    *out = st->seen.w;
     return SBR_OK;
 }
 
@@ -4670,6 +4713,7 @@ sbr_status sbr_sessions_reset(sbr_sessions* st, const uint32_t* slots, uint64_t 
     SBRCHK(carve_arena(m, [&](DeviceArena& ar) { d_slot = ar.take<uint32_t>(n); }));
     HIPCHK(hipMemcpyAsync(d_slot, slots, n * 4, hipMemcpyHostToDevice, m->stream));
     sbr::launch_session_reset(st->v, d_slot, (int)n, m->d, m->stream);
+    sbr::launch_session_seen_clear(st->seen, d_slot, (int)n, m->stream); /* nothing without memory */
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(m->stream));
     for (uint64_t i = 0; i < n; ++i) st->host_len[slots[i]] = 0;
@@ -4735,17 +4779,81 @@ sbr_status sbr_sessions_set_state(sbr_sessions* st, const uint32_t* slots, uint6
     if (c) HIPCHK(hipMemcpyAsync(d_c, c, n * dl * 4, hipMemcpyHostToDevice, m->stream));
     HIPCHK(hipMemcpyAsync(d_len, len, n * 8, hipMemcpyHostToDevice, m->stream));
     sbr::launch_session_set_state(st->v, d_slot, (int)n, m->d, m->dl, d_h, d_c, d_len, m->stream);
+    sbr::launch_session_seen_clear(st->seen, d_slot, (int)n, m->stream); /* the restored state's items are unknown: set_seen follows */
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(m->stream));
     for (uint64_t i = 0; i < n; ++i) st->host_len[slots[i]] = len[i];
     return SBR_OK;
 }
 
+/* slot slots[i]'s remembered items, oldest first: out_items[out_ptr[i] .. out_ptr[i + 1]) */
+sbr_status sbr_sessions_get_seen(sbr_sessions* st, const uint32_t* slots, uint64_t n, uint64_t* out_ptr, uint32_t* out_items) {
+    if (!st || !out_ptr || (n && !out_items) || !st->seen.w) return SBR_ERR_INVALID_ARGUMENT;
+    sbr_model* m = st->m;
+    std::lock_guard<std::mutex> lock(m->mu);
+    SBRCHK(enter_sessions(st));
+    SBRCHK(check_slots(st, slots, n));
+    out_ptr[0] = 0;
+    if (n == 0) return SBR_OK;
+    const size_t w = st->seen.w;
+    uint32_t *d_slot = nullptr, *d_n = nullptr, *d_items = nullptr;
+    SBRCHK(carve_arena(m, [&](DeviceArena& ar) {
+        d_slot = ar.take<uint32_t>(n);
+        d_n = ar.take<uint32_t>(n);
+        d_items = ar.take<uint32_t>(n * w);
+    }));
+    HIPCHK(hipMemcpyAsync(d_slot, slots, n * 4, hipMemcpyHostToDevice, m->stream));
+    sbr::launch_session_seen_get(st->seen, d_slot, (int)n, d_n, d_items, m->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(m->stream));
+    std::vector<uint32_t> count(n), padded(n * w);
+    HIPCHK(hipMemcpy(count.data(), d_n, n * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(padded.data(), d_items, n * w * 4, hipMemcpyDeviceToHost));
+    for (uint64_t i = 0; i < n; ++i) { /* the device's rows of w, closed up */
+        std::memcpy(out_items + out_ptr[i], padded.data() + i * w, (size_t)count[i] * 4);
+        out_ptr[i + 1] = out_ptr[i] + count[i];
+    }
+    return SBR_OK;
+}
+
+sbr_status sbr_sessions_set_seen(sbr_sessions* st, const uint32_t* slots, uint64_t n, const uint64_t* ptr, const uint32_t* items) {
+    if (!st || !ptr || !st->seen.w) return SBR_ERR_INVALID_ARGUMENT;
+    sbr_model* m = st->m;
+    std::lock_guard<std::mutex> lock(m->mu);
+    SBRCHK(enter_sessions(st));
+    SBRCHK(check_slots(st, slots, n));
+    SBRCHK(check_csr(m, ptr, n, items, false));
+    if (n == 0) return SBR_OK;
+    const size_t total = (size_t)(ptr[n] - ptr[0]);
+    uint32_t *d_slot = nullptr, *d_ids = nullptr;
+    uint64_t* d_ptr = nullptr;
+    SBRCHK(carve_arena(m, [&](DeviceArena& ar) {
+        d_slot = ar.take<uint32_t>(n);
+        d_ptr = ar.take<uint64_t>(n + 1);
+        d_ids = ar.take<uint32_t>(total + 1);
+    }));
+    HIPCHK(hipMemcpyAsync(d_slot, slots, n * 4, hipMemcpyHostToDevice, m->stream));
+    HIPCHK(hipMemcpyAsync(d_ptr, ptr, (n + 1) * 8, hipMemcpyHostToDevice, m->stream));
+    if (total) HIPCHK(hipMemcpyAsync(d_ids, items + ptr[0], total * 4, hipMemcpyHostToDevice, m->stream));
+    sbr::launch_session_seen_set(st->seen, d_slot, (int)n, d_ptr, d_ids, m->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(m->stream));
+    return SBR_OK;
+}
+
 namespace {
+
+/* the store's memory as the scan's source of lists, slot by the call's index */
+void with_seen(RepSource* s, const sbr_sessions* st, const uint32_t* slots) {
+    s->seen = &st->seen;
+    s->seen_slots = slots;
+}
 
 sbr_status sessions_recommend_call(sbr_sessions* st, const uint32_t* slots, uint64_t n, uint32_t k, const uint64_t* excl_ptr,
                                    const uint32_t* excl_items, uint32_t flags, uint32_t* out_items, float* out_scores, const TagFilterArg* flt) {
-    if (!st || (n && !out_items) || flags) return SBR_ERR_INVALID_ARGUMENT;
+    if (!st || (n && !out_items)) return SBR_ERR_INVALID_ARGUMENT;
+    /* a store with memory takes sbr_recommend's flag; one without keeps refusing every flag */
+    if (st->seen.w ? (flags & ~SBR_RECOMMEND_INCLUDE_HISTORY) != 0 : flags != 0) return SBR_ERR_INVALID_ARGUMENT;
     if (k < 1 || k > SBR_RECOMMEND_MAX_K) return SBR_ERR_INVALID_ARGUMENT;
     if (!excl_args_ok(excl_ptr, excl_items, n)) return SBR_ERR_INVALID_ARGUMENT;
     sbr_model* m = st->m;
@@ -4757,6 +4865,7 @@ sbr_status sessions_recommend_call(sbr_sessions* st, const uint32_t* slots, uint
     RepSource s{excl_ptr, excl_items, nullptr, 0, true};
     s.dev_rows = st->v.H;
     s.dev_row = rows.data();
+    if (st->seen.w && !(flags & SBR_RECOMMEND_INCLUDE_HISTORY)) with_seen(&s, st, slots);
     return recommend_scan(m, s, n, k, out_items, out_scores, false, nullptr, nullptr, flt);
 }
 
@@ -4775,6 +4884,7 @@ sbr_status sessions_recommend_diverse_call(sbr_sessions* st, const uint32_t* slo
     RepSource s{excl_ptr, excl_items, nullptr, 0, true};
     s.dev_rows = st->v.H;
     s.dev_row = rows.data();
+    if (st->seen.w) with_seen(&s, st, slots);
     const Diverse dv{k, trade_off, metric};
     return recommend_scan(m, s, n, pool, out_items, out_scores, false, nullptr, &dv, flt);
 }

@@ -354,6 +354,29 @@ void launch_session_set_state(const SessionView& sv, const uint32_t* slot, int n
                               const unsigned long long* len_in, hipStream_t s);
 void launch_session_get_state(const SessionView& sv, const uint32_t* slot, int n, int d, int dl, float* h_out, float* c_out,
                               unsigned long long* len_out, hipStream_t s);
+/* seen-item memory of a session store (sbr_sessions.hip): ring [capacity][w], the last w items appended to each slot since its
+ * reset — the q-th of them (q from 0) at entry q % w — and cnt [capacity], how many were remembered since then (the valid
+ * entries: min(cnt, w), which are entries [0, cnt) while cnt < w and every entry afterwards).  w == 0: a store without memory. */
+struct SeenView {
+    uint32_t* ring;
+    unsigned long long* cnt;
+    uint32_t w;
+};
+/* One append call's ring writes: session b's items ids[start[b] .. start[b] + count[b]) (the call's id array, session-major) to
+ * slot slot[b], its last w where count[b] > w, and cnt[slot[b]] += count[b].  One launch. */
+void launch_session_seen_append(const SeenView& sn, const uint32_t* slot, const unsigned long long* start, const uint32_t* count,
+                                const uint32_t* ids, int n, hipStream_t s);
+/* cnt[slot[i]] = 0 (reset, set_state) */
+void launch_session_seen_clear(const SeenView& sn, const uint32_t* slot, int n, hipStream_t s);
+/* The exclusion CSR a scan of n users reads: segment i = [eptr[i], eptr[i + 1]) of out, eptr[i] = i * w + (entries of the
+ * caller's lists before user i) — the ascending merge of slot[i]'s remembered ids (repeats kept) and the caller's sorted,
+ * de-duplicated ids caller[eptr[i] - i * w .. eptr[i + 1] - (i + 1) * w), then 0xFFFFFFFF to the segment's end.  One launch. */
+void launch_session_seen_lists(const SeenView& sn, const uint32_t* slot, int n, const uint64_t* eptr, const uint32_t* caller, uint32_t* out,
+                               hipStream_t s);
+/* out_n[i] = slot[i]'s remembered items, out_items[i * w ..] = those, oldest first; and the reverse: slot[i]'s memory = the last
+ * w of ids[ptr[i] - ptr[0] .. ptr[i + 1] - ptr[0]) */
+void launch_session_seen_get(const SeenView& sn, const uint32_t* slot, int n, uint32_t* out_n, uint32_t* out_items, hipStream_t s);
+void launch_session_seen_set(const SeenView& sn, const uint32_t* slot, int n, const uint64_t* ptr, const uint32_t* ids, hipStream_t s);
 /* device self-tests of the numerics contract (tests/test_numerics_gpu.py) */
 void launch_selftest_math(const float* x, float* out_cell_h, float* out_sig, float* out_tanh, uint64_t n, hipStream_t s);
 void launch_selftest_dot_tree(const float* x, const float* y, int d, uint64_t nrows, float* out, hipStream_t s);

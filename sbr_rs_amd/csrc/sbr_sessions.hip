@@ -13,6 +13,11 @@
 //   session_ewma_step_kernel : all of a call's items of a session, in place
 //   session_reset_kernel / session_set_state_kernel / session_get_state_kernel : zero / scatter / gather of slots' rows and len
 //
+// A store with seen-item memory (SeenView: w > 0) also has ring [capacity][w] and cnt [capacity]; nothing above reads or writes them:
+//   session_seen_append_kernel : an append call's ring writes and cnt += items appended, behind the kernels above
+//   session_seen_lists_kernel  : per scan chunk, the exclusion CSR the catalogue scan binary-searches (sbr_catalogue.hip)
+//   session_seen_clear_kernel / session_seen_get_kernel / session_seen_set_kernel : cnt = 0 / the ring oldest first / restore
+//
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off (see sbr_rs_amd/build.py).
 
 #include "sbr_kernels.h"
@@ -293,6 +298,142 @@ __global__ __launch_bounds__(256) void session_get_state_kernel(const uint32_t* 
     if (c == 0 && len_out) len_out[i] = len[slot[i]];
 }
 
+// ------------------------------------------------------------------------------------------------
+// Seen-item memory.  The q-th item remembered by a slot since its reset lies at ring[slot][q % w]; cnt[slot] counts them all, so
+// the valid entries are [0, cnt) while cnt < w and the whole ring afterwards, the oldest at (cnt - min(cnt, w)) % w.
+// ------------------------------------------------------------------------------------------------
+
+// One wave per session of an append call: its last min(count, w) items into the ring — lane j the j-th of them, so a wave's
+// stores are consecutive words of the slot's segment (split once where the ring wraps) and no two land on one entry — then
+// cnt += count by lane 0.  Every lane has read cnt before lane 0 stores it (one instruction stream), and no other wave touches
+// the slot: a call names a slot once.
+__global__ __launch_bounds__(256) void session_seen_append_kernel(const uint32_t* __restrict__ slot, const unsigned long long* __restrict__ start,
+                                                                  const uint32_t* __restrict__ count, const uint32_t* __restrict__ ids, int n,
+                                                                  uint32_t w, uint32_t* __restrict__ ring, unsigned long long* cnt) {
+    const int b = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
+    const uint32_t lane = threadIdx.x & 63u;
+    if (b >= n) return;
+    const uint32_t c = count[b];
+    if (c == 0) return;
+    const uint32_t sl = slot[b];
+    const unsigned long long have = cnt[sl];
+    const uint32_t keep = c < w ? c : w;
+    const uint32_t* src = ids + start[b] + (c - keep);
+    uint32_t* dst = ring + (size_t)sl * w;
+    const uint32_t at = (uint32_t)((have + (unsigned long long)(c - keep)) % w);
+    for (uint32_t j = lane; j < keep; j += 64u) {
+        uint32_t p = at + j; /* < 2 w */
+        if (p >= w) p -= w;
+        dst[p] = src[j];
+    }
+    if (lane == 0) cnt[sl] = have + c;
+}
+
+__global__ __launch_bounds__(256) void session_seen_clear_kernel(const uint32_t* __restrict__ slot, int n, unsigned long long* __restrict__ cnt) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < (size_t)n) cnt[slot[i]] = 0ull;
+}
+
+// out_n[i] = min(cnt, w) of slot[i]; out_items[i * w + j] = its j-th oldest remembered item: the ring unrolled
+__global__ __launch_bounds__(256) void session_seen_get_kernel(const uint32_t* __restrict__ slot, int n, uint32_t w,
+                                                               const uint32_t* __restrict__ ring, const unsigned long long* __restrict__ cnt,
+                                                               uint32_t* __restrict__ out_n, uint32_t* __restrict__ out_items) {
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t i = idx / w;
+    if (i >= (size_t)n) return;
+    const uint32_t j = (uint32_t)(idx % w);
+    const uint32_t sl = slot[i];
+    const unsigned long long c = cnt[sl];
+    const uint32_t nv = c < w ? (uint32_t)c : w;
+    if (j == 0) out_n[i] = nv;
+    if (j < nv) out_items[i * w + j] = ring[(size_t)sl * w + (size_t)((c - nv + j) % w)];
+}
+
+// slot[i]'s memory = the last min(len, w) of ids[ptr[i] - ptr[0] .. ptr[i + 1] - ptr[0]) at entries [0, that many), cnt = that many
+__global__ __launch_bounds__(256) void session_seen_set_kernel(const uint32_t* __restrict__ slot, int n, uint32_t w,
+                                                               const uint64_t* __restrict__ ptr, const uint32_t* __restrict__ ids,
+                                                               uint32_t* __restrict__ ring, unsigned long long* __restrict__ cnt) {
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t i = idx / w;
+    if (i >= (size_t)n) return;
+    const uint32_t j = (uint32_t)(idx % w);
+    const uint32_t sl = slot[i];
+    const uint64_t len = ptr[i + 1] - ptr[i];
+    const uint32_t keep = len < (uint64_t)w ? (uint32_t)len : w;
+    if (j == 0) cnt[sl] = keep;
+    if (j < keep) ring[(size_t)sl * w + j] = ids[ptr[i + 1] - ptr[0] - keep + j];
+}
+
+// The exclusion CSR of a scan chunk.  A group of G threads per user (G = 64: four users per workgroup, for p <= 64; G = 256: one)
+// brings the slot's valid ring entries into LDS, padded with 0xFFFFFFFF to p = the power of two >= w, sorts them ascending there
+// (bitonic; every thread of the workgroup walks the same p, so the barriers are uniform) and merges them with the caller's list
+// straight into the user's segment [eptr[i], eptr[i + 1]) of out, whose length is w + (the caller's entries): sorted entry r goes to
+// r + (caller entries below it), caller entry q to q + (ring entries not above it) — a merge without collisions, equal ids the
+// ring's first — and 0xFFFFFFFF fills the rest.  The caller's list of user i is caller[eptr[i] - i w ..), any length.
+//
+// What topk_gemm_kernel needs of a segment (sbr_catalogue.hip, the excl_ptr block of its merge): it takes the lower bound of a
+// real id (< num_items) and tests that entry for equality, so the segment must be NON-DECREASING — nothing more.  Repeated ids
+// (an item seen twice, or seen and also in the caller's list) leave the lower bound on the first of them, which is equal; the
+// 0xFFFFFFFF tail is above every real id and so keeps the order, and is never equal to one.  Hence no de-duplication here.
+template <int G>
+__global__ __launch_bounds__(256) void session_seen_lists_kernel(const uint32_t* __restrict__ slot, int n, uint32_t w, uint32_t p,
+                                                                 const uint32_t* __restrict__ ring, const unsigned long long* __restrict__ cnt,
+                                                                 const uint64_t* __restrict__ eptr, const uint32_t* __restrict__ caller,
+                                                                 uint32_t* __restrict__ out) {
+    constexpr int UPB = 256 / G;                       // users per workgroup
+    constexpr uint32_t PMAX = G == 64 ? 64u : 1024u;   // the largest p of this form
+    constexpr uint32_t NONE = 0xFFFFFFFFu;
+    __shared__ uint32_t buf[UPB * PMAX];
+    const uint32_t grp = threadIdx.x / G, g = threadIdx.x % G;
+    const size_t i = (size_t)blockIdx.x * UPB + grp;
+    const bool live = i < (size_t)n;
+    uint32_t* b = buf + grp * PMAX;
+    uint32_t nv = 0, sl = 0;
+    uint64_t e0 = 0, e1 = 0;
+    if (live) {
+        sl = slot[i];
+        const unsigned long long c = cnt[sl];
+        nv = c < w ? (uint32_t)c : w;
+        e0 = eptr[i];
+        e1 = eptr[i + 1];
+    }
+    for (uint32_t j = g; j < p; j += G) b[j] = j < nv ? ring[(size_t)sl * w + j] : NONE;
+    __syncthreads();
+    for (uint32_t k = 2; k <= p; k <<= 1)
+        for (uint32_t jj = k >> 1; jj > 0; jj >>= 1) {
+            for (uint32_t t = g; t < (p >> 1); t += G) {
+                const uint32_t lo = 2 * t - (t & (jj - 1)), hi = lo + jj; /* the pair whose indices differ in bit jj */
+                const bool asc = (lo & k) == 0;
+                const uint32_t x = b[lo], y = b[hi];
+                if ((x > y) == asc) { b[lo] = y; b[hi] = x; }
+            }
+            __syncthreads();
+        }
+    if (!live) return;
+    const uint64_t nc = e1 - e0 - w;
+    const uint32_t* cl = caller + (e0 - i * w); /* not read where nc == 0 (caller may be null then) */
+    uint32_t* o = out + e0;
+    for (uint32_t r = g; r < nv; r += G) {
+        const uint32_t v = b[r];
+        uint64_t lo = 0, hi = nc;
+        while (lo < hi) {
+            const uint64_t mid = (lo + hi) >> 1;
+            if (cl[mid] < v) lo = mid + 1; else hi = mid;
+        }
+        o[r + lo] = v;
+    }
+    for (uint64_t q = g; q < nc; q += G) {
+        const uint32_t v = cl[q];
+        uint32_t lo = 0, hi = nv;
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (b[mid] <= v) lo = mid + 1; else hi = mid;
+        }
+        o[q + lo] = v;
+    }
+    for (uint64_t j = nv + nc + g; j < w + nc; j += G) o[j] = NONE;
+}
+
 namespace {
 
 inline unsigned blocks_for(size_t threads) { return (unsigned)((threads + 255) / 256); }
@@ -363,6 +504,38 @@ void launch_session_get_state(const SessionView& sv, const uint32_t* slot, int n
     if (n > 0)
         hipLaunchKernelGGL(session_get_state_kernel, dim3(blocks_for((size_t)n * dl)), dim3(256), 0, s, slot, n, d, dl, sv.H, sv.C, sv.len, h_out,
                            c_out, len_out);
+}
+
+void launch_session_seen_append(const SeenView& sn, const uint32_t* slot, const unsigned long long* start, const uint32_t* count,
+                                const uint32_t* ids, int n, hipStream_t s) {
+    if (n > 0 && sn.w)
+        hipLaunchKernelGGL(session_seen_append_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, slot, start, count, ids, n, sn.w, sn.ring, sn.cnt);
+}
+
+void launch_session_seen_clear(const SeenView& sn, const uint32_t* slot, int n, hipStream_t s) {
+    if (n > 0 && sn.w) hipLaunchKernelGGL(session_seen_clear_kernel, dim3(blocks_for((size_t)n)), dim3(256), 0, s, slot, n, sn.cnt);
+}
+
+void launch_session_seen_lists(const SeenView& sn, const uint32_t* slot, int n, const uint64_t* eptr, const uint32_t* caller, uint32_t* out,
+                               hipStream_t s) {
+    if (n <= 0 || !sn.w) return;
+    uint32_t p = 1;
+    while (p < sn.w) p <<= 1;
+    if (p <= 64)
+        hipLaunchKernelGGL((session_seen_lists_kernel<64>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, slot, n, sn.w, p, sn.ring, sn.cnt, eptr,
+                           caller, out);
+    else
+        hipLaunchKernelGGL((session_seen_lists_kernel<256>), dim3((unsigned)n), dim3(256), 0, s, slot, n, sn.w, p, sn.ring, sn.cnt, eptr, caller, out);
+}
+
+void launch_session_seen_get(const SeenView& sn, const uint32_t* slot, int n, uint32_t* out_n, uint32_t* out_items, hipStream_t s) {
+    if (n > 0 && sn.w)
+        hipLaunchKernelGGL(session_seen_get_kernel, dim3(blocks_for((size_t)n * sn.w)), dim3(256), 0, s, slot, n, sn.w, sn.ring, sn.cnt, out_n, out_items);
+}
+
+void launch_session_seen_set(const SeenView& sn, const uint32_t* slot, int n, const uint64_t* ptr, const uint32_t* ids, hipStream_t s) {
+    if (n > 0 && sn.w)
+        hipLaunchKernelGGL(session_seen_set_kernel, dim3(blocks_for((size_t)n * sn.w)), dim3(256), 0, s, slot, n, sn.w, ptr, ids, sn.ring, sn.cnt);
 }
 
 }  // namespace sbr

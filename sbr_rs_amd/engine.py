@@ -19,6 +19,8 @@ RECOMMEND_NO_ITEM = 0xFFFFFFFF  # item id of a padding entry (its score is -inf)
 SIMILAR_COSINE = 0  # SBR_SIMILAR_COSINE
 SIMILAR_DOT = 1  # SBR_SIMILAR_DOT
 SIMILAR_INCLUDE_SELF = 1  # SBR_SIMILAR_INCLUDE_SELF
+RECOMMEND_INCLUDE_HISTORY = 1  # SBR_RECOMMEND_INCLUDE_HISTORY
+SESSIONS_MAX_SEEN = 1024  # SBR_SESSIONS_MAX_SEEN
 _SIMILAR_METRICS = {"cosine": SIMILAR_COSINE, "dot": SIMILAR_DOT}
 
 
@@ -824,10 +826,12 @@ class Model:
                                              None if ei is None else _ptr(ei), _ptr(tp), _ptr(ti), _ptr(ranks)))
         return ranks[: ti.size]
 
-    def sessions(self, capacity: int) -> "Sessions":
+    def sessions(self, capacity: int, remember: int = 0) -> "Sessions":
         """A session store of ``capacity`` slots on this model (sbr_sessions_create): device-resident user states advanced one
-        appended item at a time and read in place by recommend / score_candidates."""
-        return Sessions(self, capacity)
+        appended item at a time and read in place by recommend / score_candidates.  ``remember`` > 0 (at most 1 024;
+        sbr_sessions_create_seen): each slot also remembers the last ``remember`` items appended to it, and the store's
+        recommend / recommend_diverse exclude them."""
+        return Sessions(self, capacity, remember)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -870,14 +874,26 @@ class Sessions:
     at most max_sequence_length; beyond that a session keeps the recurrence over everything appended where the windowed call
     truncates.  After the model's parameters change (fit, set_param, load) every call but ``reset()`` of the whole store raises
     until that reset re-binds it; while a fit plan is open on the model every call raises.  The object keeps its model alive, and
-    ``Model.close`` closes the model's live stores first."""
+    ``Model.close`` closes the model's live stores first.
 
-    def __init__(self, model: Model, capacity: int):
+    With ``remember`` = W > 0 a slot also remembers, on the device, the last W items appended to it since its last reset, in
+    append order with repeats (``seen``); ``reset`` and ``set_state`` empty that memory, ``set_seen`` restores it.  ``recommend``
+    and ``recommend_diverse`` of such a store exclude each slot's remembered items, united with ``exclude``, as
+    ``Model.recommend`` excludes the history; ``score_candidates`` masks nothing."""
+
+    def __init__(self, model: Model, capacity: int, remember: int = 0):
         self.model = model
         self._L = _lib.load()
         h = C.c_void_p()
-        _check(self._L.sbr_sessions_create(model._h, int(capacity), C.byref(h)))
+        remember = int(remember)
+        if remember < 0 or remember > SESSIONS_MAX_SEEN:
+            raise ValueError(f"remember: 0..{SESSIONS_MAX_SEEN} items per slot")
+        if remember:
+            _check(self._L.sbr_sessions_create_seen(model._h, int(capacity), remember, C.byref(h)))
+        else:
+            _check(self._L.sbr_sessions_create(model._h, int(capacity), C.byref(h)))
         self._h = h
+        self._seen = remember
         self._lstm = int(model.hp.model) != 2
         if not hasattr(model, "_stores"):
             model._stores = weakref.WeakSet()  # Model.close closes its live stores first
@@ -888,6 +904,28 @@ class Sessions:
         n = C.c_uint64()
         _check(self._L.sbr_sessions_capacity(self._h, C.byref(n)))
         return n.value
+
+    @property
+    def seen_capacity(self) -> int:
+        """Items each slot remembers (0: a store without seen-item memory)."""
+        n = C.c_uint32()
+        _check(self._L.sbr_sessions_seen_capacity(self._h, C.byref(n)))
+        return n.value
+
+    def seen(self, slots):
+        """Each named slot's remembered items, oldest first (at most ``seen_capacity``, repeats kept): a list of u32 arrays."""
+        sl = self._slots(slots)
+        ptr = np.zeros(sl.size + 1, dtype=np.uint64)
+        items = np.zeros(max(sl.size * self._seen, 1), dtype=np.uint32)
+        _check(self._L.sbr_sessions_get_seen(self._h, _ptr(sl), sl.size, _ptr(ptr), _ptr(items)))
+        return Model._per_user(items, ptr)
+
+    def set_seen(self, slots, items):
+        """Replaces each named slot's memory with the last ``seen_capacity`` of ``items[i]`` (one sequence per slot, or a CSR
+        pair): after ``set_state`` it completes the restore of a checkpoint taken with ``state`` + ``seen``."""
+        sl = self._slots(slots)
+        ptr, ids = _items_csr(items, sl.size)
+        _check(self._L.sbr_sessions_set_seen(self._h, _ptr(sl), sl.size, _ptr(ptr), _ptr(ids)))
 
     @staticmethod
     def _slots(slots) -> np.ndarray:
@@ -913,10 +951,14 @@ class Sessions:
         _check(self._L.sbr_sessions_representations(self._h, _ptr(sl), sl.size, _ptr(out)))
         return out
 
-    def recommend(self, slots, k: int, exclude=None, any_of=None, none_of=None):
+    def recommend(self, slots, k: int, exclude=None, any_of=None, none_of=None, include_seen: bool = False):
         """``Model.recommend_reps(self.representations(slots), k, exclude)`` with the scan reading the store's rows in place: items
-        [n, k] u32, scores [n, k] f32.  The store keeps no item history: ``exclude`` is None or one sequence of item ids per slot.
-        any_of / none_of: ``Model.recommend``'s tag filter, one mask pair per slot of the call."""
+        [n, k] u32, scores [n, k] f32.  ``exclude`` is None or one sequence of item ids per slot; a store with seen-item memory
+        unites it with ``seen`` of the slot unless ``include_seen`` (a ValueError on a store without memory, which has nothing to
+        include).  any_of / none_of: ``Model.recommend``'s tag filter, one mask pair per slot of the call."""
+        if include_seen and not self._seen:
+            raise ValueError("include_seen: this store has no seen-item memory (sessions(capacity, remember=W))")
+        flags = RECOMMEND_INCLUDE_HISTORY if include_seen else 0
         sl = self._slots(slots)
         masks = _tag_masks(any_of, none_of, sl.size)
         items = np.zeros((sl.size, max(int(k), 0)), dtype=np.uint32)
@@ -924,17 +966,18 @@ class Sessions:
         ep, ei = _exclusion_csr(exclude, sl.size)
         if masks is None:
             _check(self._L.sbr_sessions_recommend(self._h, _ptr(sl), sl.size, int(k) & 0xFFFFFFFF, None if ep is None else _ptr(ep),
-                                                  None if ei is None else _ptr(ei), 0, _ptr(items), _ptr(scores)))
+                                                  None if ei is None else _ptr(ei), flags, _ptr(items), _ptr(scores)))
         else:
             _check(self._L.sbr_sessions_recommend_filtered(self._h, _ptr(sl), sl.size, int(k) & 0xFFFFFFFF,
-                                                           None if ep is None else _ptr(ep), None if ei is None else _ptr(ei), 0,
+                                                           None if ep is None else _ptr(ep), None if ei is None else _ptr(ei), flags,
                                                            _ptr(masks[0]), _ptr(masks[1]), _ptr(items), _ptr(scores)))
         return items, scores
 
     def recommend_diverse(self, slots, k: int, pool: int, trade_off: float = 0.5, metric="cosine", exclude=None, any_of=None,
                           none_of=None):
         """``Model.recommend_diverse_reps(self.representations(slots), k, pool, ...)`` with the scan reading the store's rows in
-        place: items [n, k] u32 in pick order, scores [n, k] f32."""
+        place: items [n, k] u32 in pick order, scores [n, k] f32.  A store with seen-item memory always excludes ``seen`` of the
+        slot here; ``representations`` + ``Model.recommend_diverse_reps`` is the call that does not."""
         sl = self._slots(slots)
         masks = _tag_masks(any_of, none_of, sl.size)
         items = np.zeros((sl.size, max(int(k), 0)), dtype=np.uint32)

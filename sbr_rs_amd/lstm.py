@@ -316,12 +316,14 @@ class _ImplicitSequenceModel:
         return self.params.recommend_diverse(up, it, k, pool, trade_off=trade_off, metric=metric, include_history=not exclude_history,
                                              any_of=any_of, none_of=none_of)
 
-    def sessions(self, capacity: int):
+    def sessions(self, capacity: int, remember: int = 0):
         """A session store of ``capacity`` slots on the device (``engine.Sessions``): each slot holds one user's recurrent state,
         ``append`` advances it by one cell step per item instead of re-running the whole history, and ``recommend`` /
         ``score_candidates`` read the states in place.  Exact: a slot's representation has the bits of ``user_representation``
-        of what was appended to it, up to max_sequence_length items; beyond that a session does not truncate."""
-        return self.params.sessions(capacity)
+        of what was appended to it, up to max_sequence_length items; beyond that a session does not truncate.  ``remember`` > 0:
+        every slot also remembers the last ``remember`` items appended to it, on the device, and ``recommend`` /
+        ``recommend_diverse`` of the store exclude them as ``recommend`` excludes the history."""
+        return self.params.sessions(capacity, remember)
 
     def rank_targets(self, histories, targets, mask_history: bool = True):
         """Exact catalogue ranks of each user's targets from one device scan (``evaluation.rank_targets``): one uint32 array
