@@ -713,6 +713,35 @@ class Sessions {
         check(st, "sbr_sessions_recommend_diverse_filtered");
         return Result<Recommendations, PredictionError>::Ok(std::move(r));
     }
+    /// Which sessions for this item (sbr_sessions_audience): row j of the result holds, for query item items[j], the k candidate
+    /// slots whose states score it highest — `items` of the result are SLOT ids, the scores have the bits of `score_candidates`,
+    /// score descending, ties to the lower slot, short rows padded with (0xFFFFFFFF, -inf).  Candidates: `slots`, or with
+    /// `all_live_slots` (and `slots` empty) every slot of length > 0.  Query j's excluded slots are excl_slots[excl_ptr[j] ..
+    /// excl_ptr[j + 1]) (both empty: none); on a store with seen-item memory a candidate whose memory holds the query item is left
+    /// out as well unless `include_seen` (which a store without memory refuses).
+    Result<Recommendations, PredictionError> audience(const std::vector<std::uint32_t>& items, std::size_t k,
+                                                      const std::vector<std::uint32_t>& slots = {}, bool all_live_slots = true,
+                                                      const std::vector<std::uint64_t>& excl_ptr = {},
+                                                      const std::vector<std::uint32_t>& excl_slots = {}, bool include_seen = false) const {
+        if (k < 1 || k > SBR_RECOMMEND_MAX_K) throw EngineError(SBR_ERR_INVALID_ARGUMENT, "Sessions::audience: k outside 1..SBR_RECOMMEND_MAX_K");
+        if (!excl_ptr.empty() && (excl_ptr.size() != items.size() + 1 || excl_ptr.back() > excl_slots.size()))
+            throw EngineError(SBR_ERR_INVALID_ARGUMENT, "Sessions::audience: one exclusion range per query");
+        if (all_live_slots && !slots.empty()) throw EngineError(SBR_ERR_INVALID_ARGUMENT, "Sessions::audience: slots together with all_live_slots");
+        Recommendations r;
+        r.num_users = items.size();
+        r.k = k;
+        r.items.resize(r.num_users * k);
+        r.scores.resize(r.num_users * k);
+        const std::uint32_t none = 0;
+        const sbr_status st = sbr_sessions_audience(h_, items.data(), (std::uint64_t)items.size(), (std::uint32_t)k,
+                                                    all_live_slots ? nullptr : (slots.empty() ? &none : slots.data()),
+                                                    (std::uint64_t)slots.size(), excl_ptr.empty() ? nullptr : excl_ptr.data(),
+                                                    excl_ptr.empty() ? nullptr : (excl_slots.empty() ? &none : excl_slots.data()),
+                                                    include_seen ? SBR_RECOMMEND_INCLUDE_HISTORY : 0u, r.items.data(), r.scores.data());
+        if (st == SBR_ERR_INVALID_PREDICTION) return Result<Recommendations, PredictionError>::Err(PredictionError::InvalidPredictionValue);
+        check(st, "sbr_sessions_audience");
+        return Result<Recommendations, PredictionError>::Ok(std::move(r));
+    }
     /// One score per candidate, in candidate order, slot i's candidates cand_items[cand_ptr[i] .. cand_ptr[i + 1]) (sbr_sessions_score_candidates).
     Result<std::vector<float>, PredictionError> score_candidates(const std::vector<std::uint32_t>& slots, const std::vector<std::uint64_t>& cand_ptr,
                                                                  const std::vector<std::uint32_t>& cand_items) const {
@@ -1001,6 +1030,54 @@ class ImplicitSequenceModel : public OnlineRankingModel<ImplicitUser> {
                                        (std::uint64_t)histories.num_users(), reps.data()),
               "sbr_user_representations");
         return reps;
+    }
+
+    /// The reverse of `recommend` over caller-supplied representations (sbr_audience_reps): row j of the result holds, for query
+    /// item items[j], the k rows of `reps` (row-major [num_rows][embedding_dim]) that score it highest — `items` of the result are
+    /// ROW indices, the scores have the bits of `predict`, score descending, ties to the lower row, short rows padded with
+    /// (0xFFFFFFFF, -inf).  Query j's excluded rows are excl_rows[excl_ptr[j] .. excl_ptr[j + 1]) (both empty: none).
+    Result<Recommendations, PredictionError> audience_reps(const std::vector<float>& reps, const std::vector<ItemId>& items, std::size_t k,
+                                                           const std::vector<std::uint64_t>& excl_ptr = {},
+                                                           const std::vector<std::uint32_t>& excl_rows = {}) const {
+        const std::size_t dim = (std::size_t)replicas_->hparams().embedding_dim;
+        if (k < 1 || k > SBR_RECOMMEND_MAX_K) throw EngineError(SBR_ERR_INVALID_ARGUMENT, "audience_reps: k outside 1..SBR_RECOMMEND_MAX_K");
+        if (reps.size() % dim) throw EngineError(SBR_ERR_INVALID_ARGUMENT, "audience_reps: rows of embedding_dim floats");
+        if (!excl_ptr.empty() && (excl_ptr.size() != items.size() + 1 || excl_ptr.back() > excl_rows.size()))
+            throw EngineError(SBR_ERR_INVALID_ARGUMENT, "audience_reps: one exclusion range per query");
+        const std::vector<std::uint32_t> q = narrow(items);
+        Recommendations r;
+        r.num_users = q.size();
+        r.k = k;
+        r.items.resize(r.num_users * k);
+        r.scores.resize(r.num_users * k);
+        const std::uint32_t none = 0;
+        const float zero = 0.0f;
+        const sbr_status st = sbr_audience_reps(replicas_->primary(), reps.empty() ? &zero : reps.data(), (std::uint64_t)(reps.size() / dim),
+                                                q.data(), (std::uint64_t)q.size(), (std::uint32_t)k, excl_ptr.empty() ? nullptr : excl_ptr.data(),
+                                                excl_ptr.empty() ? nullptr : (excl_rows.empty() ? &none : excl_rows.data()), r.items.data(),
+                                                r.scores.data());
+        if (st == SBR_ERR_INVALID_PREDICTION) return Result<Recommendations, PredictionError>::Err(PredictionError::InvalidPredictionValue);
+        check(st, "sbr_audience_reps");
+        return Result<Recommendations, PredictionError>::Ok(std::move(r));
+    }
+
+    /// `audience_reps` on `user_representations` of `histories` (sbr_audience): `items` of the result are USER indices.  With
+    /// `exclude_history` a user whose history holds the query item is left out of that item's row.
+    Result<Recommendations, PredictionError> audience(const data::CompressedInteractions& histories, const std::vector<ItemId>& items,
+                                                      std::size_t k, bool exclude_history = true) const {
+        if (k < 1 || k > SBR_RECOMMEND_MAX_K) throw EngineError(SBR_ERR_INVALID_ARGUMENT, "audience: k outside 1..SBR_RECOMMEND_MAX_K");
+        const std::vector<std::uint32_t> q = narrow(items);
+        Recommendations r;
+        r.num_users = q.size();
+        r.k = k;
+        r.items.resize(r.num_users * k);
+        r.scores.resize(r.num_users * k);
+        const sbr_status st = sbr_audience(replicas_->primary(), histories.user_pointers().data(), histories.item_ids().data(),
+                                           (std::uint64_t)histories.num_users(), q.data(), (std::uint64_t)q.size(), (std::uint32_t)k,
+                                           exclude_history ? 0u : SBR_RECOMMEND_INCLUDE_HISTORY, r.items.data(), r.scores.data());
+        if (st == SBR_ERR_INVALID_PREDICTION) return Result<Recommendations, PredictionError>::Err(PredictionError::InvalidPredictionValue);
+        check(st, "sbr_audience");
+        return Result<Recommendations, PredictionError>::Ok(std::move(r));
     }
 
     /// `predict` for many users in one device pass (sbr_score_candidates): user u's history is row u of `histories`, its

@@ -669,6 +669,33 @@ sbr_status sbr_sessions_recommend_diverse_filtered(sbr_sessions* st, const uint3
                                                    float trade_off, uint32_t metric, const uint64_t* excl_ptr, const uint32_t* excl_items,
                                                    const uint32_t* any_of, const uint32_t* none_of, uint32_t* out_items, float* out_scores);
 
+/* AUDIENCE — the reverse question, "which rows for this item": for each of num_queries query items q = items[j] (any order, repeats
+ * allowed, each < num_items) the k candidate rows that score it highest, score(q, s) = b[q] + chain_dot(h_s, E[q]) with the bits of
+ * sbr_predict / sbr_score_candidates for that (state, item) pair: the catalogue scan with the operands' roles exchanged (every
+ * product of the chain commutes), the query's bias added in the epilogue.  Row j of out_rows / out_scores [num_queries][k]: score
+ * descending, ties to the lower row id, short rows padded with (0xFFFFFFFF, -inf); out_scores may be NULL.  sbr_recommend's rules:
+ * 1 <= k <= SBR_RECOMMEND_MAX_K, -0.0 == +0.0, a non-finite score of a scanned (query, candidate) pair is
+ * SBR_ERR_INVALID_PREDICTION for the call — a non-finite row outside the candidates does not fail it.  num_queries == 0 is a no-op.
+ *   sbr_audience_reps      candidates = the caller's rows reps [num_rows][embedding_dim]; results are row indices.  excl_ptr /
+ *                          excl_rows: per QUERY a list of row indices (each < num_rows, any order) left out of its row; both NULL: none
+ *   sbr_audience           candidates = sbr_user_representations of the histories; results are user indices.  Unless flags has
+ *                          SBR_RECOMMEND_INCLUDE_HISTORY a user whose (whole) history holds the query item is left out of its row
+ *   sbr_sessions_audience  candidates = the store's slots `slots` [num_slots] (each < capacity, none twice, any order; an empty slot
+ *                          reads the empty-history row), or with slots == NULL (and num_slots == 0) every slot of length > 0;
+ *                          results are slot ids.  excl_ptr / excl_slots: per query a list of slot ids (each < capacity; one that
+ *                          is no candidate is ignored).  On a store with seen-item memory a candidate whose memory holds the query
+ *                          item is left out as well — the lists are inverted on the device, the ring never visits the host — unless
+ *                          flags has SBR_RECOMMEND_INCLUDE_HISTORY; on a store without memory flags other than 0 are
+ *                          SBR_ERR_INVALID_ARGUMENT.  A stale store refuses the call as it refuses every other.
+ * Not offered: tag filters per slot, k above SBR_RECOMMEND_MAX_K, a threshold form, item subsets. */
+sbr_status sbr_audience_reps(sbr_model* m, const float* reps, uint64_t num_rows, const uint32_t* items, uint64_t num_queries, uint32_t k,
+                             const uint64_t* excl_ptr, const uint32_t* excl_rows, uint32_t* out_rows, float* out_scores);
+sbr_status sbr_audience(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users, const uint32_t* items,
+                        uint64_t num_queries, uint32_t k, uint32_t flags, uint32_t* out_users, float* out_scores);
+sbr_status sbr_sessions_audience(sbr_sessions* st, const uint32_t* items, uint64_t num_queries, uint32_t k, const uint32_t* slots,
+                                 uint64_t num_slots, const uint64_t* excl_ptr, const uint32_t* excl_slots, uint32_t flags, uint32_t* out_slots,
+                                 float* out_scores);
+
 /* ≙ the serde derives (lstm.rs:204,386; ewma.rs:208,401): element counts and raw access. */
 sbr_status sbr_model_param_count(const sbr_model* m, int32_t which, uint64_t* out_count);
 sbr_status sbr_model_get_param(sbr_model* m, int32_t which, float* host_out, uint64_t count);

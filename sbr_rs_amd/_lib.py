@@ -163,6 +163,9 @@ def load():
         "sbr_similar_items_filtered": [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp],
         "sbr_sessions_recommend_filtered": [vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint32, vp, vp, vp, vp],
         "sbr_sessions_recommend_diverse_filtered": [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, vp, vp, vp, vp, vp, vp],
+        "sbr_audience_reps": [vp, vp, C.c_uint64, vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp],
+        "sbr_audience": [vp, vp, vp, C.c_uint64, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp],
+        "sbr_sessions_audience": [vp, vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, vp, vp, C.c_uint32, vp, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -219,4 +222,5 @@ DECLARED_SYMBOLS = [
     "sbr_recommend_diverse_filtered", "sbr_recommend_diverse_filtered_reps", "sbr_similar_items_filtered",
     "sbr_sessions_recommend_filtered", "sbr_sessions_recommend_diverse_filtered",
     "sbr_sessions_create_seen", "sbr_sessions_seen_capacity", "sbr_sessions_get_seen", "sbr_sessions_set_seen",
+    "sbr_audience_reps", "sbr_audience", "sbr_sessions_audience",
 ]

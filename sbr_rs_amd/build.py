@@ -153,6 +153,15 @@ def build_filtered_tests(force: bool = False, verbose: bool = True) -> str:
     return _build_cpp_program(FILTERED_SRC, FILTERED_BIN, force, verbose)
 
 
+AUDIENCE_SRC = os.path.join(REPO, "tests", "cpp", "audience_tests.cpp")
+AUDIENCE_BIN = os.path.join(REPO, "tests", "cpp", "_build", "audience_tests")
+
+
+def build_audience_tests(force: bool = False, verbose: bool = True) -> str:
+    """g++ build of the C++ host layer's audience (reverse scan) test program."""
+    return _build_cpp_program(AUDIENCE_SRC, AUDIENCE_BIN, force, verbose)
+
+
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv))
     print(build_facade_tests(force="--force" in sys.argv))
@@ -164,3 +173,4 @@ if __name__ == "__main__":
     print(build_sessions_tests(force="--force" in sys.argv))
     print(build_sessions_seen_tests(force="--force" in sys.argv))
     print(build_filtered_tests(force="--force" in sys.argv))
+    print(build_audience_tests(force="--force" in sys.argv))

@@ -24,6 +24,9 @@
  *   subset_gather_kernel   : recommend_among's sub-table E'[j] = E[S[j]], b'[j] = b[S[j]] of a sorted, unique item set S; the scan is
  *                            topk_gemm_kernel + topk_merge_kernel on a ModelView of E', b', |S|, and
  *   subset_ids_kernel      : maps the merged lists' positions in S back to catalogue ids
+ *   (audience)             : the reverse scan, "which rows for this item": topk_gemm_kernel with the QueryBias score policy — the
+ *                            A operand is the query items' rows of E (reps = E, rep_row = the item ids), the scanned table a set of
+ *                            state rows, and the bias the query's, b[q], held in LDS by slot
  *   candidate_score_kernel : score_candidates' b[i] + chain_dot(rep_u, E[i]) of a flat list of (user, item) pairs, 64 per wave
  *   rep_rows_kernel        : user_representations' rows rep_row[i] of H, embedding_dim floats each, in user order
  *
@@ -535,9 +538,27 @@ __global__ __launch_bounds__(64) void rank_targets_finish_kernel(ModelView m, co
  * one statement of the score, a macro on purpose: through a function of the policy — a forceinline static member, a plain one, a
  * lambda in the kernel — the BiasAdd instantiations compiled to 12 more VGPRs at every d <= 128 (101 -> 113 at d = 16, 178 -> 190
  * at d = 128); this form leaves their instruction streams what they were (profiles/similar_items_8192x1M_d128.md). */
-struct BiasAdd { static constexpr bool scale = false; };
-struct ScaleMul { static constexpr bool scale = true; };
-#define TK_SCORE(q) (Score::scale ? acc[q] * bias : bias + acc[q])
+struct BiasAdd {
+    static constexpr bool scale = false, query = false;
+    struct Args {};
+};
+struct ScaleMul {
+    static constexpr bool scale = true, query = false;
+    struct Args {};
+};
+/* audience's policy: the bias belongs to the scan's "user" — a query item q whose row E[q] is the A operand — not to the scanned
+ * row (a session's state): score = b[q] + chain_dot(E[q], h_s), the bits of predict for (h_s, q) because every product of the chain
+ * commutes.  The workgroup's 128 queries' biases sit in LDS by slot (qbS, as thS) and are added to the tile's accumulators once,
+ * ahead of the epilogue, which then reads acc[q] as the score; the scanned row's Bs value takes no part.  Args is empty for the
+ * other two policies, at the end of the argument block behind Filter::Args, and every statement of this one sits under
+ * `if constexpr`: their instantiations keep their instruction streams (profiles/audience_asm_stats.md). */
+struct QueryBias {
+    static constexpr bool scale = false, query = true;
+    struct Args {
+        const float* qb; /* [the A table's rows]: the bias of query item rep_row[u] */
+    };
+};
+#define TK_SCORE(q) (Score::query ? acc[q] : Score::scale ? acc[q] * bias : bias + acc[q])
 
 /* Whether the scan filters items by tag, the third constant policy.  TagFilter: item i is offered to user u only if
  * (tags[i] & none_of[u]) == 0 && (any_of[u] == 0 || (tags[i] & any_of[u]) != 0) — tags [num_items] the model's item tags, any_of /
@@ -564,9 +585,11 @@ template <int D, class Score, class Filter>
 __global__ __launch_bounds__(256, D <= 128 ? 2 : 1) void topk_gemm_kernel(ModelView m, const float* reps, const int* rep_row, uint32_t num_users,
                                                                          const uint64_t* excl_ptr, const uint32_t* excl_items,
                                                                          uint32_t items_per_group, uint32_t k, uint2* lists, uint32_t* lens,
-                                                                         uint32_t* nonfinite_flag, typename Filter::Args fa) {
+                                                                         uint32_t* nonfinite_flag, typename Filter::Args fa,
+                                                                         typename Score::Args sa) {
     __shared__ float Es[2][32 * ItemTiles<D>::LDE];
     __shared__ float Bs[2][32];
+    __shared__ __align__(16) float qbS[Score::query ? 128 : 4]; /* QueryBias only: the queries' biases by slot (slot_user) */
     // TagFilter only: the tiles' tag words, and the users' masks by slot (slot_user), read 16 bytes at a time
     __shared__ uint32_t Ts[2][Filter::on ? 32 : 1];
     __shared__ __align__(16) uint32_t anyS[Filter::on ? 128 : 4];
@@ -598,6 +621,10 @@ __global__ __launch_bounds__(256, D <= 128 ? 2 : 1) void topk_gemm_kernel(ModelV
             anyS[tid] = any;
             anyZ[tid] = any == 0u ? 1u : 0u;
             noneS[tid] = u < num_users ? fa.none_of[u] : 0u;
+        }
+        if constexpr (Score::query) {
+            const uint32_t u = blockIdx.x * 128 + (uint32_t)slot_user(tid);
+            qbS[tid] = u < num_users ? sa.qb[rep_row[u]] : 0.0f;
         }
     }
     uint32_t umask = 0; /* accumulator registers q whose user exists */
@@ -716,8 +743,18 @@ __global__ __launch_bounds__(256, D <= 128 ? 2 : 1) void topk_gemm_kernel(ModelV
             tiles.fetch(m, tile + 1);
             if constexpr (Filter::on) tiles.fetch_tags(fa.tags, tile + 1);
         }
-        const f32x16 acc = tile_dots<D>(a, Es[buf]);
+        f32x16 acc = tile_dots<D>(a, Es[buf]);
         const float bias = Bs[buf][l31];
+        if constexpr (Score::query) { /* the score is b[q] + dot, one rounding, as predict's; acc[q] holds it from here on */
+#pragma unroll
+            for (int q4 = 0; q4 < 4; ++q4) {
+                const float4 b4 = ld4(&qbS[pbase + 4 * q4]);
+                acc[4 * q4 + 0] = b4.x + acc[4 * q4 + 0];
+                acc[4 * q4 + 1] = b4.y + acc[4 * q4 + 1];
+                acc[4 * q4 + 2] = b4.z + acc[4 * q4 + 2];
+                acc[4 * q4 + 3] = b4.w + acc[4 * q4 + 3];
+            }
+        }
         const uint32_t id = tiles.i_begin + (uint32_t)tile * 32 + (uint32_t)l31;
         uint32_t pend = id < tiles.i_end ? umask : 0u;
 #pragma unroll
@@ -1216,10 +1253,10 @@ void launch_recommend(const ModelView& m, const float* reps, const int* rep_row,
     DISPATCH_D(m.d, {
         if (f)
             hipLaunchKernelGGL((topk_gemm_kernel<DD, BiasAdd, TagFilter>), dim3(utiles, groups), dim3(256), 0, s, m, reps, rep_row, num_users, excl_ptr,
-                               excl_items, per, k, lists, lens, nonfinite_flag, TagFilter::Args{f->tags, f->any_of, f->none_of});
+                               excl_items, per, k, lists, lens, nonfinite_flag, TagFilter::Args{f->tags, f->any_of, f->none_of}, BiasAdd::Args{});
         else
             hipLaunchKernelGGL((topk_gemm_kernel<DD, BiasAdd, NoFilter>), dim3(utiles, groups), dim3(256), 0, s, m, reps, rep_row, num_users, excl_ptr,
-                               excl_items, per, k, lists, lens, nonfinite_flag, NoFilter::Args{});
+                               excl_items, per, k, lists, lens, nonfinite_flag, NoFilter::Args{}, BiasAdd::Args{});
         hipLaunchKernelGGL(topk_merge_kernel, dim3(num_users), dim3(512), 0, s, lists, lens, groups, k, n, out_items, out_scores);
     });
 }
@@ -1269,10 +1306,10 @@ void launch_similar_items(const ModelView& m, const uint32_t* query, uint32_t nu
                            query, num_queries, H);
         if (f)
             hipLaunchKernelGGL((topk_gemm_kernel<DD, ScaleMul, TagFilter>), dim3(utiles, groups), dim3(256), 0, s, mr, H, rep_row, num_queries, excl_ptr,
-                               excl_items, per, k, lists, lens, nonfinite_flag, TagFilter::Args{f->tags, f->any_of, f->none_of});
+                               excl_items, per, k, lists, lens, nonfinite_flag, TagFilter::Args{f->tags, f->any_of, f->none_of}, ScaleMul::Args{});
         else
             hipLaunchKernelGGL((topk_gemm_kernel<DD, ScaleMul, NoFilter>), dim3(utiles, groups), dim3(256), 0, s, mr, H, rep_row, num_queries, excl_ptr,
-                               excl_items, per, k, lists, lens, nonfinite_flag, NoFilter::Args{});
+                               excl_items, per, k, lists, lens, nonfinite_flag, NoFilter::Args{}, ScaleMul::Args{});
         hipLaunchKernelGGL(topk_merge_kernel, dim3(num_queries), dim3(512), 0, s, lists, lens, groups, k, n, out_items, out_scores);
     });
 }
@@ -1292,6 +1329,45 @@ void launch_recommend_among(const ModelView& m, const uint32_t* subset, uint32_t
     launch_recommend(ms, reps, rep_row, num_users, excl_ptr, excl_items, k, lists, lens, out_items, out_scores, nonfinite_flag, s);
     const uint64_t n = (uint64_t)num_users * k;
     hipLaunchKernelGGL(subset_ids_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, subset, out_items, n);
+}
+
+void launch_audience_gather(const ModelView& m, const float* rows_table, const uint32_t* rows, uint32_t num_rows, float* T, float* bT,
+                            hipStream_t s) {
+    if (num_rows == 0) return;
+    ModelView mh = m; /* the gather's source: the state rows where the item table stands; its per-row value is read and unused, so
+                         any readable memory of the table's length does (the rows themselves), and bT is zeroed behind it */
+    mh.E = const_cast<float*>(rows_table);
+    mh.b = const_cast<float*>(rows_table);
+    DISPATCH_D(m.d, {
+        hipLaunchKernelGGL((subset_gather_kernel<DD>), dim3((unsigned)(((uint64_t)num_rows * (DD / 4) + 255) / 256)), dim3(256), 0, s, mh, rows,
+                           num_rows, T, bT);
+    });
+    (void)hipMemsetAsync(bT, 0, (size_t)num_rows * 4, s);
+}
+
+void launch_audience(const ModelView& m, const float* T, const float* bT, uint32_t num_rows, const uint32_t* row_ids, const uint32_t* query,
+                     uint32_t num_queries, const uint64_t* excl_ptr, const uint32_t* excl_rows, uint32_t k, uint2* lists, uint32_t* lens,
+                     uint32_t* out_rows, float* out_scores, uint32_t* nonfinite_flag, hipStream_t s) {
+    if (num_queries == 0 || num_rows == 0) return;
+    ModelView mt = m; /* the scan's catalogue: the candidate rows, whose "item" j is row j of T */
+    mt.E = const_cast<float*>(T);
+    mt.b = const_cast<float*>(bT);
+    mt.num_items = num_rows;
+    uint32_t per = 0;
+    const uint32_t groups = recommend_groups(num_queries, num_rows, k, &per);
+    const uint32_t utiles = (num_queries + 127) / 128;
+    uint32_t n = 1;
+    while (n < groups * k) n <<= 1;
+    DISPATCH_D(m.d, {
+        hipLaunchKernelGGL((topk_gemm_kernel<DD, QueryBias, NoFilter>), dim3(utiles, groups), dim3(256), 0, s, mt, m.E,
+                           reinterpret_cast<const int*>(query), num_queries, excl_ptr, excl_rows, per, k, lists, lens, nonfinite_flag,
+                           NoFilter::Args{}, QueryBias::Args{m.b});
+    });
+    hipLaunchKernelGGL(topk_merge_kernel, dim3(num_queries), dim3(512), 0, s, lists, lens, groups, k, n, out_rows, out_scores);
+    if (row_ids) {
+        const uint64_t ne = (uint64_t)num_queries * k;
+        hipLaunchKernelGGL(subset_ids_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, s, row_ids, out_rows, ne);
+    }
 }
 
 void launch_candidate_scores(const ModelView& m, const float* reps, const uint32_t* pair_row, const uint32_t* pair_item, uint64_t num_pairs,

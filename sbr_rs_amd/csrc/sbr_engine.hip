@@ -4931,6 +4931,291 @@ sbr_status sbr_sessions_score_candidates(sbr_sessions* st, const uint32_t* slots
 }
 
 /* ---------------------------------------------------------------------------------------------
+ * audience: the reverse scan — for each query item the k best candidate rows (sbr_catalogue.hip, the QueryBias policy)
+ * ------------------------------------------------------------------------------------------- */
+}  // extern "C"
+
+namespace {
+
+/* Where an audience call's candidate rows come from: the caller's host rows [num_rows][embedding_dim], or device rows at the storage
+ * width (a session store's), candidate j's being row dev_row[j].  ids (ascending; null: the positions themselves) are what the
+ * positions stand for in the results; with `seen` they are slots whose memories exclude. */
+struct AudienceSource {
+    const float* reps = nullptr;
+    const float* dev_rows = nullptr;
+    const uint32_t* dev_row = nullptr;
+    const uint32_t* ids = nullptr;
+    const sbr::SeenView* seen = nullptr;
+};
+
+/* device blocks of one call or chunk outside the eval arena (which does not outlive a carve); given back once the stream is idle */
+struct DeviceBlocks {
+    hipStream_t stream;
+    std::vector<void*> blocks;
+    explicit DeviceBlocks(hipStream_t s) : stream(s) {}
+    DeviceBlocks(const DeviceBlocks&) = delete;
+    DeviceBlocks& operator=(const DeviceBlocks&) = delete;
+    template <typename T>
+    sbr_status take(T** p, size_t count) {
+        SBRCHK(dmalloc(p, count ? count : 1));
+        blocks.push_back(*p);
+        return SBR_OK;
+    }
+    ~DeviceBlocks() {
+        if (blocks.empty()) return;
+        (void)hipStreamSynchronize(stream);
+        for (void* b : blocks) dfree(b);
+    }
+};
+
+int bits_for(uint64_t n) { /* bits that hold every value below n */
+    int b = 1;
+    while (b < 32 && (1ull << b) < n) ++b;
+    return b;
+}
+
+/* The k best of the num_rows candidate rows for each of num_queries query items, in chunks of queries; the candidate table is made
+ * once per call, outside the arena: one gather (or upload) however many chunks follow.  excl_ptr / excl_pos: per query the sorted,
+ * de-duplicated candidate POSITIONS the caller excludes (excl_ptr empty: none).  With src.seen the chunk's exclusion CSR is built on
+ * the device — a count pass over the candidates' rings, one u64 read back to size the key arrays, a fill pass behind the caller's
+ * (query, position) keys, the key ordering, and the segment bounds — and never visits the host. */
+sbr_status audience_scan(sbr_model* m, const AudienceSource& src, uint64_t num_rows, const uint32_t* items, uint64_t num_queries, uint32_t k,
+                         const std::vector<uint64_t>& excl_ptr, const std::vector<uint32_t>& excl_pos, uint32_t* out_rows, float* out_scores) {
+    if (num_queries == 0) return SBR_OK;
+    if (num_rows == 0) { /* nobody to rank: rows of padding */
+        for (uint64_t e = 0; e < num_queries * k; ++e) {
+            out_rows[e] = 0xFFFFFFFFu;
+            if (out_scores) out_scores[e] = -INFINITY;
+        }
+        return SBR_OK;
+    }
+    /* the scan indexes its A rows (item ids) with an int and its scanned rows with a u32 below the padding id */
+    if (m->hp.num_items > 0x7FFFFFFFull || num_rows > 0x7FFFFFFFull) return SBR_ERR_UNSUPPORTED;
+    const size_t S = (size_t)num_rows, d = (size_t)m->d, dl = (size_t)m->dl;
+    DeviceBlocks call(m->stream);
+    float *T = nullptr, *bT = nullptr;
+    uint32_t *d_ids = nullptr, *d_rowidx = nullptr;
+    SBRCHK(call.take(&T, S * d));
+    SBRCHK(call.take(&bT, S));
+    if (src.ids) {
+        SBRCHK(call.take(&d_ids, S));
+        HIPCHK(hipMemcpyAsync(d_ids, src.ids, S * 4, hipMemcpyHostToDevice, m->stream));
+    }
+    if (src.dev_rows) {
+        SBRCHK(call.take(&d_rowidx, S));
+        HIPCHK(hipMemcpyAsync(d_rowidx, src.dev_row, S * 4, hipMemcpyHostToDevice, m->stream));
+        sbr::launch_audience_gather(m->mv, src.dev_rows, d_rowidx, (uint32_t)S, T, bT, m->stream);
+    } else { /* padded to the storage width: the columns past embedding_dim are zero, as in the model's own states */
+        HIPCHK(hipMemsetAsync(T, 0, S * d * 4, m->stream));
+        HIPCHK(hipMemcpy2DAsync(T, d * 4, src.reps, dl * 4, dl * 4, S, hipMemcpyHostToDevice, m->stream));
+        HIPCHK(hipMemsetAsync(bT, 0, S * 4, m->stream));
+    }
+    HIPCHK(hipGetLastError());
+    const bool caller_lists = !excl_ptr.empty();
+    size_t cap = recommend_users_cap((uint32_t)S, k);
+    if (src.seen && cap > sbr::audience_seen_max_queries) cap = sbr::audience_seen_max_queries;
+    for (uint64_t q0 = 0; q0 < num_queries; q0 += cap) {
+        const size_t n = (size_t)std::min<uint64_t>(cap, num_queries - q0);
+        const uint64_t c0 = caller_lists ? excl_ptr[q0] : 0, c1 = caller_lists ? excl_ptr[q0 + n] : 0;
+        const size_t nc = (size_t)(c1 - c0);
+        TopkBufs tb;
+        uint32_t *qs_item = nullptr, *qs_idx = nullptr;
+        unsigned long long* counters = nullptr; /* [0] the count pass's total, [1] the fill pass's cursor */
+        SBRCHK(carve_arena(m, [&](DeviceArena& ar) {
+            tb.carve(ar, (uint32_t)S, n, src.seen ? 0 : nc, k, false);
+            if (src.seen) {
+                qs_item = ar.take<uint32_t>(n);
+                qs_idx = ar.take<uint32_t>(n);
+                counters = ar.take<unsigned long long>(2);
+            }
+        }));
+        HIPCHK(hipMemcpyAsync(tb.rep, items + q0, n * 4, hipMemcpyHostToDevice, m->stream)); /* the scan's rep_row: item ids */
+        std::vector<uint64_t> eptr;      /* host vectors the asynchronous copies read: they outlive `chunk`, which drains the stream */
+        std::vector<uint32_t> order, sorted_items;
+        std::vector<uint64_t> caller_keys;
+        DeviceBlocks chunk(m->stream);
+        const uint64_t* d_eptr = nullptr;
+        const uint32_t* d_excl = tb.excl;
+        if (!src.seen) {
+            if (caller_lists) {
+                eptr.resize(n + 1);
+                for (size_t j = 0; j <= n; ++j) eptr[j] = excl_ptr[q0 + j] - c0;
+                HIPCHK(hipMemcpyAsync(tb.eptr, eptr.data(), (n + 1) * 8, hipMemcpyHostToDevice, m->stream));
+                if (nc) HIPCHK(hipMemcpyAsync(tb.excl, excl_pos.data() + c0, nc * 4, hipMemcpyHostToDevice, m->stream));
+                d_eptr = tb.eptr;
+            }
+        } else {
+            order.resize(n);
+            for (size_t j = 0; j < n; ++j) order[j] = (uint32_t)j;
+            std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return items[q0 + a] < items[q0 + b]; });
+            sorted_items.resize(n);
+            for (size_t j = 0; j < n; ++j) sorted_items[j] = items[q0 + order[j]];
+            HIPCHK(hipMemcpyAsync(qs_item, sorted_items.data(), n * 4, hipMemcpyHostToDevice, m->stream));
+            HIPCHK(hipMemcpyAsync(qs_idx, order.data(), n * 4, hipMemcpyHostToDevice, m->stream));
+            HIPCHK(hipMemsetAsync(counters, 0, 16, m->stream));
+            sbr::launch_audience_seen_count(*src.seen, d_ids, (uint32_t)S, qs_item, qs_idx, (uint32_t)n, counters, m->stream);
+            HIPCHK(hipGetLastError());
+            unsigned long long total = 0;
+            HIPCHK(hipStreamSynchronize(m->stream));
+            HIPCHK(hipMemcpy(&total, counters, 8, hipMemcpyDeviceToHost));
+            const unsigned long long nkeys = total + nc;
+            if (nkeys >= (1ull << 31)) return SBR_ERR_OUT_OF_MEMORY; /* the key ordering counts with 32 bits */
+            d_eptr = tb.eptr;
+            if (nkeys == 0) {
+                HIPCHK(hipMemsetAsync(tb.eptr, 0, (n + 1) * 8, m->stream));
+            } else {
+                uint64_t *keys = nullptr, *ka = nullptr, *kb = nullptr;
+                uint8_t* temp = nullptr;
+                uint32_t* excl = nullptr;
+                SBRCHK(chunk.take(&keys, (size_t)nkeys));
+                SBRCHK(chunk.take(&ka, (size_t)nkeys));
+                SBRCHK(chunk.take(&kb, (size_t)nkeys));
+                SBRCHK(chunk.take(&temp, sbr::pair_sort_temp_bytes((size_t)nkeys)));
+                SBRCHK(chunk.take(&excl, (size_t)nkeys));
+                if (nc) {
+                    caller_keys.resize(nc);
+                    for (size_t j = 0; j < n; ++j)
+                        for (uint64_t e = excl_ptr[q0 + j]; e < excl_ptr[q0 + j + 1]; ++e) caller_keys[e - c0] = ((uint64_t)j << 32) | excl_pos[e];
+                    HIPCHK(hipMemcpyAsync(keys, caller_keys.data(), nc * 8, hipMemcpyHostToDevice, m->stream));
+                }
+                sbr::launch_audience_seen_fill(*src.seen, d_ids, (uint32_t)S, qs_item, qs_idx, (uint32_t)n, keys + nc, total, counters + 1, m->stream);
+                sbr::launch_pair_sort(keys, (uint32_t)nkeys, bits_for(n), bits_for(S), ka, kb, temp, m->stream);
+                sbr::launch_audience_seen_csr(keys, (uint32_t)nkeys, (uint32_t)n, tb.eptr, excl, m->stream);
+                HIPCHK(hipGetLastError());
+                d_excl = excl;
+            }
+        }
+        SBRCHK(scan_launch(m, d_ids ? 3 : 2, tb.flag, [&] {
+            sbr::launch_audience(m->mv, T, bT, (uint32_t)S, d_ids, reinterpret_cast<const uint32_t*>(tb.rep), (uint32_t)n, d_eptr, d_excl, k, tb.lists,
+                                 tb.lens, tb.items, out_scores ? tb.scores : nullptr, tb.flag, m->stream);
+        }, {{out_rows + q0 * k, tb.items, n * k * 4}, {out_scores ? out_scores + q0 * k : nullptr, tb.scores, n * k * 4}}));
+    }
+    return SBR_OK;
+}
+
+/* A caller's per-query lists of row ids (each below `bound`) as sorted, de-duplicated POSITIONS in the ascending candidate ids
+ * `cand` (null: the ids are the positions); ids that are no candidates are dropped.  ptr null: no lists (both outputs empty). */
+sbr_status audience_exclusions(const uint64_t* ptr, const uint32_t* ids, uint64_t num_queries, uint64_t bound, const std::vector<uint32_t>* cand,
+                               std::vector<uint64_t>* out_ptr, std::vector<uint32_t>* out_pos) {
+    out_ptr->clear();
+    out_pos->clear();
+    if (!ptr) return SBR_OK;
+    for (uint64_t j = 0; j < num_queries; ++j)
+        if (ptr[j + 1] < ptr[j]) return SBR_ERR_INVALID_ARGUMENT;
+    if (ptr[num_queries] > ptr[0] && !ids) return SBR_ERR_INVALID_ARGUMENT;
+    out_ptr->assign(num_queries + 1, 0);
+    for (uint64_t j = 0; j < num_queries; ++j) {
+        const size_t from = out_pos->size();
+        for (uint64_t e = ptr[j]; e < ptr[j + 1]; ++e) {
+            if (ids[e] >= bound) return SBR_ERR_INVALID_ARGUMENT;
+            if (!cand) out_pos->push_back(ids[e]);
+            else {
+                const auto at = std::lower_bound(cand->begin(), cand->end(), ids[e]);
+                if (at != cand->end() && *at == ids[e]) out_pos->push_back((uint32_t)(at - cand->begin()));
+            }
+        }
+        std::sort(out_pos->begin() + from, out_pos->end());
+        out_pos->erase(std::unique(out_pos->begin() + from, out_pos->end()), out_pos->end());
+        (*out_ptr)[j + 1] = out_pos->size();
+    }
+    return SBR_OK;
+}
+
+bool audience_args_ok(const void* handle, const uint32_t* items, uint64_t num_queries, uint32_t k, const uint64_t* excl_ptr, const uint32_t* excl_ids,
+                      const uint32_t* out_rows) {
+    if (!handle || (num_queries && (!items || !out_rows))) return false;
+    if (k < 1 || k > SBR_RECOMMEND_MAX_K) return false;
+    return excl_args_ok(excl_ptr, excl_ids, num_queries);
+}
+
+}  // namespace
+
+extern "C" {
+
+sbr_status sbr_audience_reps(sbr_model* m, const float* reps, uint64_t num_rows, const uint32_t* items, uint64_t num_queries, uint32_t k,
+                             const uint64_t* excl_ptr, const uint32_t* excl_rows, uint32_t* out_rows, float* out_scores) {
+    if (!audience_args_ok(m, items, num_queries, k, excl_ptr, excl_rows, out_rows) || (num_rows && !reps)) return SBR_ERR_INVALID_ARGUMENT;
+    std::lock_guard<std::mutex> lock(m->mu);
+    SBRCHK(enter_reader(m));
+    for (uint64_t j = 0; j < num_queries; ++j)
+        if (items[j] >= m->hp.num_items) return SBR_ERR_INVALID_ARGUMENT;
+    std::vector<uint64_t> eptr;
+    std::vector<uint32_t> epos;
+    SBRCHK(audience_exclusions(excl_ptr, excl_rows, num_queries, num_rows, nullptr, &eptr, &epos));
+    AudienceSource src;
+    src.reps = reps;
+    return audience_scan(m, src, num_rows, items, num_queries, k, eptr, epos, out_rows, out_scores);
+}
+
+sbr_status sbr_audience(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users, const uint32_t* items,
+                        uint64_t num_queries, uint32_t k, uint32_t flags, uint32_t* out_users, float* out_scores) {
+    if (!audience_args_ok(m, items, num_queries, k, nullptr, nullptr, out_users) || !user_ptr) return SBR_ERR_INVALID_ARGUMENT;
+    if (flags & ~SBR_RECOMMEND_INCLUDE_HISTORY) return SBR_ERR_INVALID_ARGUMENT;
+    for (uint64_t j = 0; j < num_queries; ++j)
+        if (items[j] >= m->hp.num_items) return SBR_ERR_INVALID_ARGUMENT;
+    std::vector<float> reps((size_t)num_users * (size_t)m->dl + 1);
+    SBRCHK(sbr_user_representations(m, user_ptr, item_ids, num_users, reps.data())); /* validates the histories */
+    if (flags & SBR_RECOMMEND_INCLUDE_HISTORY)
+        return sbr_audience_reps(m, reps.data(), num_users, items, num_queries, k, nullptr, nullptr, out_users, out_scores);
+    /* per query, the users whose WHOLE history holds the item (recommend's mask, evaluation.rs:30-32), ascending */
+    std::vector<uint32_t> uniq(items, items + num_queries);
+    std::sort(uniq.begin(), uniq.end());
+    uniq.erase(std::unique(uniq.begin(), uniq.end()), uniq.end());
+    std::vector<std::vector<uint32_t>> holders(uniq.size());
+    for (uint64_t u = 0; u < num_users; ++u)
+        for (uint64_t e = user_ptr[u]; e < user_ptr[u + 1]; ++e) {
+            const auto at = std::lower_bound(uniq.begin(), uniq.end(), item_ids[e]);
+            if (at == uniq.end() || *at != item_ids[e]) continue;
+            std::vector<uint32_t>& h = holders[(size_t)(at - uniq.begin())];
+            if (h.empty() || h.back() != (uint32_t)u) h.push_back((uint32_t)u);
+        }
+    std::vector<uint64_t> eptr(num_queries + 1, 0);
+    std::vector<uint32_t> eusers;
+    for (uint64_t j = 0; j < num_queries; ++j) {
+        const std::vector<uint32_t>& h = holders[(size_t)(std::lower_bound(uniq.begin(), uniq.end(), items[j]) - uniq.begin())];
+        eusers.insert(eusers.end(), h.begin(), h.end());
+        eptr[j + 1] = eusers.size();
+    }
+    const uint32_t none = 0;
+    return sbr_audience_reps(m, reps.data(), num_users, items, num_queries, k, eptr.data(), eusers.empty() ? &none : eusers.data(), out_users,
+                             out_scores);
+}
+
+sbr_status sbr_sessions_audience(sbr_sessions* st, const uint32_t* items, uint64_t num_queries, uint32_t k, const uint32_t* slots,
+                                 uint64_t num_slots, const uint64_t* excl_ptr, const uint32_t* excl_slots, uint32_t flags, uint32_t* out_slots,
+                                 float* out_scores) {
+    if (!audience_args_ok(st, items, num_queries, k, excl_ptr, excl_slots, out_slots)) return SBR_ERR_INVALID_ARGUMENT;
+    /* a store with memory takes sbr_recommend's flag; one without keeps refusing every flag */
+    if (st->seen.w ? (flags & ~SBR_RECOMMEND_INCLUDE_HISTORY) != 0 : flags != 0) return SBR_ERR_INVALID_ARGUMENT;
+    sbr_model* m = st->m;
+    std::lock_guard<std::mutex> lock(m->mu);
+    SBRCHK(enter_sessions(st));
+    for (uint64_t j = 0; j < num_queries; ++j)
+        if (items[j] >= m->hp.num_items) return SBR_ERR_INVALID_ARGUMENT;
+    std::vector<uint32_t> cand; /* ascending slot ids: a tie goes to the lower position, which is then the lower slot */
+    if (slots) {
+        SBRCHK(check_slots(st, slots, num_slots));
+        cand.assign(slots, slots + num_slots);
+        std::sort(cand.begin(), cand.end());
+    } else {
+        if (num_slots) return SBR_ERR_INVALID_ARGUMENT;
+        for (uint64_t sl = 0; sl < st->capacity; ++sl)
+            if (st->host_len[sl]) cand.push_back((uint32_t)sl);
+    }
+    std::vector<uint64_t> eptr;
+    std::vector<uint32_t> epos;
+    SBRCHK(audience_exclusions(excl_ptr, excl_slots, num_queries, st->capacity, &cand, &eptr, &epos));
+    std::vector<uint32_t> rows(cand.size());
+    for (size_t j = 0; j < cand.size(); ++j) rows[j] = st->host_len[cand[j]] ? cand[j] : (uint32_t)st->capacity;
+    AudienceSource src;
+    src.dev_rows = st->v.H;
+    src.dev_row = rows.data();
+    src.ids = cand.data();
+    if (st->seen.w && !(flags & SBR_RECOMMEND_INCLUDE_HISTORY)) src.seen = &st->seen;
+    return audience_scan(m, src, cand.size(), items, num_queries, k, eptr, epos, out_slots, out_scores);
+}
+
+/* ---------------------------------------------------------------------------------------------
  * numerics self-tests (tests/test_numerics_gpu.py): run the contract's primitives on the device
  * ------------------------------------------------------------------------------------------- */
 sbr_status sbr_selftest_math(const float* x, uint64_t n, float* out_cell_h, float* out_sig, float* out_tanh) {

@@ -320,6 +320,18 @@ void launch_similar_items(const ModelView& m, const uint32_t* query, uint32_t nu
 void launch_recommend_among(const ModelView& m, const uint32_t* subset, uint32_t num_subset, float* Esub, float* bsub, const float* reps,
                             const int* rep_row, uint32_t num_users, const uint64_t* excl_ptr, const uint32_t* excl_items, uint32_t k,
                             uint2* lists, uint32_t* lens, uint32_t* out_items, float* out_scores, uint32_t* nonfinite_flag, hipStream_t s);
+/* audience, the reverse scan (sbr_catalogue.hip): for each of num_queries query items q = query[j] the k best rows of the candidate
+ * table T [num_rows][d] by s(q, r) = b[q] + chain_dot(E[q], T[r]) — predict's bits for (state T[r], item q) — score descending, ties
+ * to the lower row, padded as launch_recommend's rows.  topk_gemm_kernel with the QueryBias policy: reps = E, rep_row = query, the
+ * scanned ModelView's E = T and its b = bT [num_rows] (fetched, never used: any finite memory; launch_audience_gather zeroes it).
+ * excl_ptr / excl_rows: per QUERY a non-decreasing list of row positions (NULL: none); lists / lens sized by
+ * recommend_groups(num_queries, num_rows, k).  row_ids non-null (ascending): out_rows' positions become row_ids[position].
+ * launch_audience_gather: T[j] = rows_table[rows[j]] (rows of d floats), bT = 0. */
+void launch_audience_gather(const ModelView& m, const float* rows_table, const uint32_t* rows, uint32_t num_rows, float* T, float* bT,
+                            hipStream_t s);
+void launch_audience(const ModelView& m, const float* T, const float* bT, uint32_t num_rows, const uint32_t* row_ids, const uint32_t* query,
+                     uint32_t num_queries, const uint64_t* excl_ptr, const uint32_t* excl_rows, uint32_t k, uint2* lists, uint32_t* lens,
+                     uint32_t* out_rows, float* out_scores, uint32_t* nonfinite_flag, hipStream_t s);
 /* out[p] = b[i] + chain_dot(reps[pair_row[p]], E[i]), i = pair_item[p], for the num_pairs pairs of a launch, with the bits of
  * launch_predict; raises the flag for a non-finite score.  A launch takes at most candidate_pairs_cap pairs: the host cuts a call's
  * flat candidate list there (12 bytes of device buffers per pair), wherever in a user's list that falls. */
@@ -377,6 +389,25 @@ void launch_session_seen_lists(const SeenView& sn, const uint32_t* slot, int n, 
  * w of ids[ptr[i] - ptr[0] .. ptr[i + 1] - ptr[0]) */
 void launch_session_seen_get(const SeenView& sn, const uint32_t* slot, int n, uint32_t* out_n, uint32_t* out_items, hipStream_t s);
 void launch_session_seen_set(const SeenView& sn, const uint32_t* slot, int n, const uint64_t* ptr, const uint32_t* ids, hipStream_t s);
+/* The inverted seen lists of an audience scan (sbr_sessions.hip): which candidates' memories hold which query item.  The chunk's
+ * queries come sorted by item: qs_item [nq] ascending (repeats kept), qs_idx [nq] the query each stands for; candidate position p
+ * is slot cand_slot[p].  A key is (query << 32 | position), one per (query, position) whose slot's min(cnt, w) valid ring entries hold
+ * the query's item — a repeat in a ring counts once.  launch_audience_seen_count adds the number of keys to *total (zeroed by the
+ * caller); launch_audience_seen_fill writes them, in no particular order, to keys[0 .. cap) through the cursor *cursor (zeroed by
+ * the caller; a key past cap is dropped, which cannot happen with cap = the count).  nq <= audience_seen_max_queries. */
+constexpr uint32_t audience_seen_max_queries = 8192;
+void launch_audience_seen_count(const SeenView& sn, const uint32_t* cand_slot, uint32_t num_cand, const uint32_t* qs_item,
+                                const uint32_t* qs_idx, uint32_t nq, unsigned long long* total, hipStream_t s);
+void launch_audience_seen_fill(const SeenView& sn, const uint32_t* cand_slot, uint32_t num_cand, const uint32_t* qs_item,
+                               const uint32_t* qs_idx, uint32_t nq, uint64_t* keys, unsigned long long cap, unsigned long long* cursor,
+                               hipStream_t s);
+/* sbr_sort.hip: n keys (hi << 32 | lo), generated in any order, into ascending order in place (hi < 2^hi_bits, lo < 2^lo_bits; a, b:
+ * scratch of n keys each; temp: pair_sort_temp_bytes(n)) */
+size_t pair_sort_temp_bytes(size_t n);
+void launch_pair_sort(uint64_t* keys, uint32_t n, int hi_bits, int lo_bits, uint64_t* a, uint64_t* b, void* temp, hipStream_t s);
+/* the exclusion CSR of an audience chunk out of its n sorted keys: eptr[j] = the first key of query j or above (j = 0 .. nq, so
+ * eptr[nq] = n) and excl[e] = key e's position */
+void launch_audience_seen_csr(const uint64_t* keys, uint32_t n, uint32_t nq, uint64_t* eptr, uint32_t* excl, hipStream_t s);
 /* device self-tests of the numerics contract (tests/test_numerics_gpu.py) */
 void launch_selftest_math(const float* x, float* out_cell_h, float* out_sig, float* out_tanh, uint64_t n, hipStream_t s);
 void launch_selftest_dot_tree(const float* x, const float* y, int d, uint64_t nrows, float* out, hipStream_t s);

@@ -16,6 +16,9 @@
 // A store with seen-item memory (SeenView: w > 0) also has ring [capacity][w] and cnt [capacity]; nothing above reads or writes them:
 //   session_seen_append_kernel : an append call's ring writes and cnt += items appended, behind the kernels above
 //   session_seen_lists_kernel  : per scan chunk, the exclusion CSR the catalogue scan binary-searches (sbr_catalogue.hip)
+//   audience_seen_match_kernel : the audience scan's inverted lists: (query, candidate position) keys of the candidates whose memory holds
+//                                a query item, counted in one pass and written in a second; audience_seen_csr_kernel turns the sorted
+//                                keys into the CSR over queries the scan binary-searches
 //   session_seen_clear_kernel / session_seen_get_kernel / session_seen_set_kernel : cnt = 0 / the ring oldest first / restore
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off (see sbr_rs_amd/build.py).
@@ -434,6 +437,79 @@ __global__ __launch_bounds__(256) void session_seen_lists_kernel(const uint32_t*
     for (uint64_t j = nv + nc + g; j < w + nc; j += G) o[j] = NONE;
 }
 
+// ------------------------------------------------------------------------------------------------
+// The audience scan's inverted seen lists: per QUERY item, the candidate positions whose slot remembers it.
+//
+// A workgroup holds the chunk's queries' items, sorted ascending with repeats, in LDS (at most 8 192: 32 KB) and walks candidate
+// positions p = wave, wave + (waves of the grid), ...: lane j of a position's wave takes ring entries j, j + 64, ... of the
+// min(cnt, w) valid ones, finds the first query of that item by binary search and — where there is one, and no EARLIER valid entry
+// of the ring holds the same item (a repeat counts once: the walk over the entries before it runs only for the few that matched) —
+// produces one key (query << 32 | p) per query of that item.  FILL = false counts the keys (one atomic per wave); FILL = true writes
+// them through a cursor, in no particular order: launch_pair_sort orders them.  Bounds: a ring read is below min(cnt, w) <= w of
+// a slot below capacity (the host validated the slots), a key is written only at an index below cap.
+// ------------------------------------------------------------------------------------------------
+template <bool FILL>
+__global__ __launch_bounds__(256) void audience_seen_match_kernel(const uint32_t* __restrict__ cand_slot, uint32_t num_cand, uint32_t w,
+                                                                  const uint32_t* __restrict__ ring, const unsigned long long* __restrict__ cnt,
+                                                                  const uint32_t* __restrict__ qs_item, const uint32_t* __restrict__ qs_idx,
+                                                                  uint32_t nq, uint64_t* __restrict__ keys, unsigned long long cap,
+                                                                  unsigned long long* counter) {
+    __shared__ uint32_t qs[8192];
+    for (uint32_t i = threadIdx.x; i < nq; i += 256) qs[i] = qs_item[i];
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave0 = blockIdx.x * 4u + (threadIdx.x >> 6);
+    const uint32_t nwaves = gridDim.x * 4u;
+    unsigned long long mine = 0;
+    for (uint32_t p = wave0; p < num_cand; p += nwaves) {
+        const uint32_t sl = cand_slot[p];
+        const unsigned long long c = cnt[sl];
+        const uint32_t nv = c < w ? (uint32_t)c : w;
+        const uint32_t* rg = ring + (size_t)sl * w;
+        for (uint32_t j = lane; j < nv; j += 64u) {
+            const uint32_t item = rg[j];
+            uint32_t lo = 0, hi = nq;
+            while (lo < hi) {
+                const uint32_t mid = (lo + hi) >> 1;
+                if (qs[mid] < item) lo = mid + 1; else hi = mid;
+            }
+            if (lo >= nq || qs[lo] != item) continue;
+            bool repeat = false;
+            for (uint32_t e = 0; e < j && !repeat; ++e) repeat = rg[e] == item;
+            if (repeat) continue;
+            for (uint32_t t = lo; t < nq && qs[t] == item; ++t) {
+                if (FILL) {
+                    const unsigned long long at = atomicAdd(counter, 1ull);
+                    if (at < cap) keys[at] = ((uint64_t)qs_idx[t] << 32) | (uint64_t)p;
+                } else {
+                    ++mine;
+                }
+            }
+        }
+    }
+    if (!FILL) {
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) mine += __shfl_xor(mine, off, 64);
+        if (lane == 0 && mine) atomicAdd(counter, mine);
+    }
+}
+
+// eptr[j] = the number of sorted keys below (j << 32), j = 0 .. nq; excl[e] = the position half of key e
+__global__ __launch_bounds__(256) void audience_seen_csr_kernel(const uint64_t* __restrict__ keys, uint32_t n, uint32_t nq,
+                                                                uint64_t* __restrict__ eptr, uint32_t* __restrict__ excl) {
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (t < (size_t)n) excl[t] = (uint32_t)keys[t];
+    if (t <= (size_t)nq) {
+        const uint64_t bound = (uint64_t)t << 32;
+        uint32_t lo = 0, hi = n;
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (keys[mid] < bound) lo = mid + 1; else hi = mid;
+        }
+        eptr[t] = lo;
+    }
+}
+
 namespace {
 
 inline unsigned blocks_for(size_t threads) { return (unsigned)((threads + 255) / 256); }
@@ -536,6 +612,34 @@ void launch_session_seen_get(const SeenView& sn, const uint32_t* slot, int n, ui
 void launch_session_seen_set(const SeenView& sn, const uint32_t* slot, int n, const uint64_t* ptr, const uint32_t* ids, hipStream_t s) {
     if (n > 0 && sn.w)
         hipLaunchKernelGGL(session_seen_set_kernel, dim3(blocks_for((size_t)n * sn.w)), dim3(256), 0, s, slot, n, sn.w, ptr, ids, sn.ring, sn.cnt);
+}
+
+namespace {
+/* waves enough to fill the chip a few times over, no more than one per candidate */
+inline unsigned audience_seen_grid(uint32_t num_cand) {
+    const unsigned want = (num_cand + 3) / 4;
+    return want < 2048u ? (want ? want : 1u) : 2048u;
+}
+}  // namespace
+
+void launch_audience_seen_count(const SeenView& sn, const uint32_t* cand_slot, uint32_t num_cand, const uint32_t* qs_item,
+                                const uint32_t* qs_idx, uint32_t nq, unsigned long long* total, hipStream_t s) {
+    if (num_cand == 0 || nq == 0 || !sn.w || nq > audience_seen_max_queries) return;
+    hipLaunchKernelGGL((audience_seen_match_kernel<false>), dim3(audience_seen_grid(num_cand)), dim3(256), 0, s, cand_slot, num_cand, sn.w, sn.ring,
+                       sn.cnt, qs_item, qs_idx, nq, (uint64_t*)nullptr, 0ull, total);
+}
+
+void launch_audience_seen_fill(const SeenView& sn, const uint32_t* cand_slot, uint32_t num_cand, const uint32_t* qs_item,
+                               const uint32_t* qs_idx, uint32_t nq, uint64_t* keys, unsigned long long cap, unsigned long long* cursor,
+                               hipStream_t s) {
+    if (num_cand == 0 || nq == 0 || !sn.w || cap == 0 || nq > audience_seen_max_queries) return;
+    hipLaunchKernelGGL((audience_seen_match_kernel<true>), dim3(audience_seen_grid(num_cand)), dim3(256), 0, s, cand_slot, num_cand, sn.w, sn.ring,
+                       sn.cnt, qs_item, qs_idx, nq, keys, cap, cursor);
+}
+
+void launch_audience_seen_csr(const uint64_t* keys, uint32_t n, uint32_t nq, uint64_t* eptr, uint32_t* excl, hipStream_t s) {
+    const size_t threads = (size_t)n > (size_t)nq + 1 ? (size_t)n : (size_t)nq + 1;
+    hipLaunchKernelGGL(audience_seen_csr_kernel, dim3(blocks_for(threads)), dim3(256), 0, s, keys, n, nq, eptr, excl);
 }
 
 }  // namespace sbr

@@ -99,6 +99,10 @@ struct SrcRows {  // self-test: entry e of a plain row array
     const uint32_t* rows;
     __device__ __forceinline__ uint64_t operator()(uint32_t e) const { return ((uint64_t)rows[e] << 32) | e; }
 };
+struct SrcSwapped {  // a key array with its halves exchanged: what lay in the low 32 bits is what this sort orders by
+    const uint64_t* k;
+    __device__ __forceinline__ uint64_t operator()(uint32_t e) const { const uint64_t v = k[e]; return (v << 32) | (v >> 32); }
+};
 struct SrcMerge {  // partitioned table: (row, device, position) of every list head in the owner's row range; where that range
     PeerLists pl;   // lies in every device's sorted keys is DEVICE-resident (merge_plan_kernel): the host never learns it
     int ndev;
@@ -537,6 +541,18 @@ void launch_merge_sort(const PeerLists& pl, int ndev, uint32_t capacity, uint64_
     (void)sort_temp_bytes;
     if (capacity == 0) return;
     radix_sort(SrcMerge{pl, ndev}, capacity, 32, mkeys, mkeys_sorted, carve(sort_temp, capacity, 32), s, &pl.plan->base[16]);
+}
+
+size_t pair_sort_temp_bytes(size_t n) { return sparse_sort_temp_bytes(n, 64); }
+
+// Full order of n keys (hi << 32 | lo) that were generated in NO particular order, hi < 2^hi_bits and lo < 2^lo_bits, by two stable
+// sorts of the kind above: by lo (the keys read with their halves exchanged, so lo lies in the row bits), then — exchanged back —
+// by hi.  The result is left in `keys`; a and b are scratch of n keys each.
+void launch_pair_sort(uint64_t* keys, uint32_t n, int hi_bits, int lo_bits, uint64_t* a, uint64_t* b, void* temp, hipStream_t s) {
+    if (n == 0) return;
+    const Scratch scr = carve(temp, n, 32);
+    radix_sort(SrcSwapped{keys}, n, lo_bits, a, b, scr, s); /* never writes keys; ends in b */
+    radix_sort(SrcSwapped{b}, n, hi_bits, a, keys, scr, s);  /* never writes b; ends in keys */
 }
 
 void launch_selftest_sort(const uint32_t* rows, uint32_t n, int row_bits, uint64_t* tmp, uint64_t* out, void* temp, uint32_t* head_pos,

@@ -766,6 +766,34 @@ class Model:
         _check(self._L.sbr_score_candidates_reps(self._h, _ptr(reps), nu, _ptr(cp), _ptr(ci) if ci.size else None, _ptr(scores)))
         return self._per_user(scores, cp)
 
+    def audience_reps(self, reps, items, k: int, exclude=None):
+        """The reverse scan (sbr_audience_reps): for each query item ``items[j]`` the k rows of ``reps`` [S, embedding_dim] that
+        score it highest — rows [Q, k] u32 (indices into ``reps``) and scores [Q, k] f32 with the bits of ``predict(reps[s],
+        [item])``, score descending, ties to the lower row, short rows padded with (RECOMMEND_NO_ITEM, -inf).  Queries may repeat
+        and come in any order.  exclude: None or one sequence of row indices per query."""
+        reps = np.ascontiguousarray(reps, dtype=np.float32).reshape(-1, self.dim)
+        q = np.ascontiguousarray(items, dtype=np.uint32).ravel()
+        rows = np.zeros((q.size, max(int(k), 0)), dtype=np.uint32)
+        scores = np.zeros((q.size, max(int(k), 0)), dtype=np.float32)
+        ep, ei = _exclusion_csr(exclude, q.size)
+        _check(self._L.sbr_audience_reps(self._h, _ptr(reps), reps.shape[0], _ptr(q), q.size, int(k) & 0xFFFFFFFF,
+                                         None if ep is None else _ptr(ep), None if ei is None else _ptr(ei), _ptr(rows), _ptr(scores)))
+        return rows, scores
+
+    def audience(self, user_ptr, item_ids, items, k: int, include_history: bool = False):
+        """``audience_reps`` on ``user_representations`` of the histories (sbr_audience): users [Q, k] u32 and scores [Q, k] f32.
+        Unless include_history a user whose history holds the query item is left out of that item's row."""
+        up = np.ascontiguousarray(user_ptr, dtype=np.uint64)
+        it = np.ascontiguousarray(item_ids, dtype=np.uint32)
+        q = np.ascontiguousarray(items, dtype=np.uint32).ravel()
+        nu = max(len(up) - 1, 0)
+        users = np.zeros((q.size, max(int(k), 0)), dtype=np.uint32)
+        scores = np.zeros((q.size, max(int(k), 0)), dtype=np.float32)
+        flags = RECOMMEND_INCLUDE_HISTORY if include_history else 0
+        _check(self._L.sbr_audience(self._h, _ptr(up), _ptr(it), nu, _ptr(q), q.size, int(k) & 0xFFFFFFFF, flags, _ptr(users),
+                                    _ptr(scores)))
+        return users, scores
+
     def recommend_among(self, user_ptr, item_ids, k: int, among, include_history: bool = False):
         """recommend with every item outside `among` ineligible (sbr_recommend_among): the exact top-k of that item set — item
         ids in any order, duplicates allowed — as catalogue ids, ordered and padded as recommend's rows.  Only the set's rows are
@@ -993,6 +1021,36 @@ class Sessions:
                                                                    None if ep is None else _ptr(ep), None if ei is None else _ptr(ei),
                                                                    _ptr(masks[0]), _ptr(masks[1]), _ptr(items), _ptr(scores)))
         return items, scores
+
+    def audience(self, items, k: int, slots=None, exclude=None, include_seen: bool = False):
+        """Which sessions for this item (sbr_sessions_audience): for each query item ``items[j]`` the k candidate slots whose
+        states score it highest — slots [Q, k] u32 (slot ids) and scores [Q, k] f32 with the bits of ``score_candidates`` for
+        that (slot, item) pair, score descending, ties to the lower slot id, short rows padded with (RECOMMEND_NO_ITEM, -inf).
+        Candidates: ``slots`` (any valid slots, none twice, any order; an empty slot reads the empty-history row), or with
+        ``slots=None`` every slot of length > 0.  ``exclude`` is None or one sequence of slot ids per query.  On a store with
+        seen-item memory a candidate whose memory holds the query item is left out unless ``include_seen`` (a ValueError on a
+        store without memory).  The state rows, the memories and the Q x S scores stay on the device."""
+        if include_seen and not self._seen:
+            raise ValueError("include_seen: this store has no seen-item memory (sessions(capacity, remember=W))")
+        if not 1 <= int(k) <= RECOMMEND_MAX_K:
+            raise ValueError(f"k: 1..{RECOMMEND_MAX_K}")
+        flags = RECOMMEND_INCLUDE_HISTORY if include_seen else 0
+        q = np.ascontiguousarray(items, dtype=np.uint32).ravel()
+        sl = None if slots is None else self._slots(slots)
+        if sl is not None and np.unique(sl).size != sl.size:
+            raise ValueError("slots: none twice")
+        out_slots = np.zeros((q.size, max(int(k), 0)), dtype=np.uint32)
+        scores = np.zeros((q.size, max(int(k), 0)), dtype=np.float32)
+        ep, ei = _exclusion_csr(exclude, q.size)
+        if sl is not None and sl.size == 0:
+            sl = np.zeros(1, dtype=np.uint32)  # an empty candidate list, not "every live slot": a valid pointer, zero slots
+            nsl = 0
+        else:
+            nsl = 0 if sl is None else sl.size
+        _check(self._L.sbr_sessions_audience(self._h, _ptr(q), q.size, int(k) & 0xFFFFFFFF, None if sl is None else _ptr(sl), nsl,
+                                             None if ep is None else _ptr(ep), None if ei is None else _ptr(ei), flags,
+                                             _ptr(out_slots), _ptr(scores)))
+        return out_slots, scores
 
     def score_candidates(self, slots, candidates):
         """``Model.score_candidates_reps`` on the slots' representations, read in place: one f32 array per slot, in candidate

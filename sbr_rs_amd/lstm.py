@@ -268,6 +268,14 @@ class _ImplicitSequenceModel:
             raise ValueError("a tag filter together with among= is not supported: filter the item set instead")
         return self.params.recommend_among(up, it, k, among, include_history=not exclude_history)
 
+    def audience(self, interactions_or_histories, items, k: int, exclude_history: bool = True):
+        """The reverse of ``recommend``: for each query item of ``items`` the k users whose histories score it highest, on the
+        device — (users [Q, k] u32, scores [Q, k] f32), ``predict``'s bits, score descending, ties to the lower user, short rows
+        padded with (0xFFFFFFFF, -inf).  Runs ``user_representations``, then ``params.audience_reps``; with ``exclude_history`` a
+        user whose history holds the query item is left out of that item's row.  For live sessions: ``sessions(...).audience``."""
+        up, it = self._csr(interactions_or_histories)
+        return self.params.audience(up, it, items, k, include_history=not exclude_history)
+
     def user_representations(self, histories) -> np.ndarray:
         """``user_representation`` of many histories in one device pass: [U, embedding_dim] f32, row u for history u."""
         return self.params.user_representations(*self._csr(histories))
