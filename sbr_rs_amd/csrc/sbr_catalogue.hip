@@ -1189,10 +1189,10 @@ void launch_predict(const ModelView& m, const float* user, const uint32_t* items
     DISPATCH_D(m.d, { hipLaunchKernelGGL((predict_kernel<DD>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, m, user, items, n, out); });
 }
 
-void launch_rank(const ModelView& m, const float* reps, const int* rep_row, uint32_t num_users, const uint32_t* test_item,
-                 const uint32_t* test_in_hist, const uint64_t* hist_ptr, const uint32_t* hist_items, float* ts_scratch,
-                 uint32_t* ranks, uint32_t* nonfinite_flag, hipStream_t s) {
-    if (num_users == 0) return;
+int launch_rank(const ModelView& m, const float* reps, const int* rep_row, uint32_t num_users, const uint32_t* test_item,
+                const uint32_t* test_in_hist, const uint64_t* hist_ptr, const uint32_t* hist_items, float* ts_scratch,
+                uint32_t* ranks, uint32_t* nonfinite_flag, hipStream_t s) {
+    if (num_users == 0) return 0;
     // 32 users per wave (128 per workgroup, four waves per SIMD).  (A 64-users-per-wave form — half the barriers and LDS fills per
     // flop at half the waves — measured 5 % slower at 8 192 users x 1e6 items, d = 128: 100 against 105 TFLOP/s; removed.)
     const uint32_t utiles = (num_users + 127) / 128;
@@ -1205,6 +1205,7 @@ void launch_rank(const ModelView& m, const float* reps, const int* rep_row, uint
         hipLaunchKernelGGL((rank_gemm_kernel<DD>), dim3(utiles, groups), dim3(256), 0, s, m, reps, rep_row, num_users, ts_scratch, per, ranks, nonfinite_flag);
         hipLaunchKernelGGL((rank_history_kernel<DD>), dim3(num_users), dim3(64), 0, s, m, reps, rep_row, ts_scratch, hist_ptr, hist_items, ranks);
     });
+    return 1; /* the ledger's count of mrr_score's scan (sbr_kernels.h) */
 }
 
 uint32_t rank_targets_tmax(int d) {
@@ -1213,11 +1214,11 @@ uint32_t rank_targets_tmax(int d) {
     return d <= 128 ? 16u : 8u;
 }
 
-void launch_rank_targets(const ModelView& m, const float* reps, const int* rep_row, const uint32_t* su_user, const uint32_t* sptr,
-                         uint32_t num_su, const uint32_t* tgt_items, const uint64_t* mask_ptr, const uint32_t* mask_items, float* ts,
-                         uint32_t* pos, float* th, float* tmin, float* tmin2, uint32_t* buckets, uint32_t* totals, uint32_t* ranks,
-                         uint32_t* nonfinite_flag, hipStream_t s) {
-    if (num_su == 0) return;
+int launch_rank_targets(const ModelView& m, const float* reps, const int* rep_row, const uint32_t* su_user, const uint32_t* sptr,
+                        uint32_t num_su, const uint32_t* tgt_items, const uint64_t* mask_ptr, const uint32_t* mask_items, float* ts,
+                        uint32_t* pos, float* th, float* tmin, float* tmin2, uint32_t* buckets, uint32_t* totals, uint32_t* ranks,
+                        uint32_t* nonfinite_flag, hipStream_t s) {
+    if (num_su == 0) return 0;
     const uint32_t utiles = (num_su + 127) / 128;
     // item ranges as launch_rank's, and its limit: the kernel's per-lane counters are 16 bits wide, fewer than 65 536 tiles per range
     uint32_t per = 0;
@@ -1231,6 +1232,7 @@ void launch_rank_targets(const ModelView& m, const float* reps, const int* rep_r
         hipLaunchKernelGGL((rank_targets_finish_kernel<DD, TM>), dim3(num_su), dim3(64), 0, s, m, reps, rep_row, su_user, sptr, ts, pos,
                            buckets, totals, mask_ptr, mask_items, ranks);
     });
+    return 3;
 }
 
 uint32_t recommend_groups(uint32_t num_users, uint32_t num_items, uint32_t k, uint32_t* items_per_group) {
@@ -1241,24 +1243,48 @@ uint32_t recommend_groups(uint32_t num_users, uint32_t num_items, uint32_t k, ui
     return split_items(num_items, wanted_groups((256u * 2u * 2u + utiles - 1) / utiles), TK_MERGE_MAX / k, UINT32_MAX, items_per_group);
 }
 
-void launch_recommend(const ModelView& m, const float* reps, const int* rep_row, uint32_t num_users, const uint64_t* excl_ptr,
-                      const uint32_t* excl_items, uint32_t k, uint2* lists, uint32_t* lens, uint32_t* out_items, float* out_scores,
-                      uint32_t* nonfinite_flag, hipStream_t s, const TagMasks* f) {
-    if (num_users == 0) return;
+namespace {
+
+template <int D, class Score, class Filter>
+void topk_gemm_launch(dim3 grid, const ModelView& cat, const float* reps, const TopkScan& sc, uint32_t items_per_group, typename Filter::Args fa,
+                      typename Score::Args sa, hipStream_t s) {
+    hipLaunchKernelGGL((topk_gemm_kernel<D, Score, Filter>), grid, dim3(256), 0, s, cat, reps, sc.rep_row, sc.n, sc.excl_ptr, sc.excl_items,
+                       items_per_group, sc.k, sc.lists, sc.lens, sc.nonfinite_flag, fa, sa);
+}
+
+/* The top-k scan of every launcher below, two launches: topk_gemm_kernel<cat.d, Score, .> over the catalogue `cat` (its E, b,
+ * num_items: the model's, or a launcher's rewrite of them) with the A rows reps[sc.rep_row[u]], split into recommend_groups' item
+ * ranges, then topk_merge_kernel.  The only place that decides the split, the grid, the merge size and the Filter instantiation:
+ * TagFilter where sc.f is set — never under QueryBias (audience has no filter), so that pair, five large kernels, does not exist. */
+template <class Score>
+int topk_scan(const ModelView& cat, const float* reps, const TopkScan& sc, typename Score::Args sa, hipStream_t s) {
     uint32_t per = 0;
-    const uint32_t groups = recommend_groups(num_users, m.num_items, k, &per);
-    const uint32_t utiles = (num_users + 127) / 128;
+    const uint32_t groups = recommend_groups(sc.n, cat.num_items, sc.k, &per);
+    const dim3 grid((sc.n + 127) / 128, groups);
     uint32_t n = 1;
-    while (n < groups * k) n <<= 1;
-    DISPATCH_D(m.d, {
-        if (f)
-            hipLaunchKernelGGL((topk_gemm_kernel<DD, BiasAdd, TagFilter>), dim3(utiles, groups), dim3(256), 0, s, m, reps, rep_row, num_users, excl_ptr,
-                               excl_items, per, k, lists, lens, nonfinite_flag, TagFilter::Args{f->tags, f->any_of, f->none_of}, BiasAdd::Args{});
-        else
-            hipLaunchKernelGGL((topk_gemm_kernel<DD, BiasAdd, NoFilter>), dim3(utiles, groups), dim3(256), 0, s, m, reps, rep_row, num_users, excl_ptr,
-                               excl_items, per, k, lists, lens, nonfinite_flag, NoFilter::Args{}, BiasAdd::Args{});
-        hipLaunchKernelGGL(topk_merge_kernel, dim3(num_users), dim3(512), 0, s, lists, lens, groups, k, n, out_items, out_scores);
+    while (n < groups * sc.k) n <<= 1;
+    const bool filtered = !Score::query && sc.f.tags;
+    DISPATCH_D(cat.d, {
+        if constexpr (!Score::query)
+            if (filtered) topk_gemm_launch<DD, Score, TagFilter>(grid, cat, reps, sc, per, TagFilter::Args{sc.f.tags, sc.f.any_of, sc.f.none_of}, sa, s);
+        if (!filtered) topk_gemm_launch<DD, Score, NoFilter>(grid, cat, reps, sc, per, NoFilter::Args{}, sa, s);
     });
+    hipLaunchKernelGGL(topk_merge_kernel, dim3(sc.n), dim3(512), 0, s, sc.lists, sc.lens, groups, sc.k, n, sc.out_items, sc.out_scores);
+    return 2;
+}
+
+/* out_items' positions in a sub-table or a candidate list -> the ids they stand for; one launch */
+int launch_subset_ids(const uint32_t* ids, const TopkScan& sc, hipStream_t s) {
+    const uint64_t n = (uint64_t)sc.n * sc.k;
+    hipLaunchKernelGGL(subset_ids_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ids, sc.out_items, n);
+    return 1;
+}
+
+}  // namespace
+
+int launch_recommend(const ModelView& m, const float* reps, const TopkScan& sc, hipStream_t s) {
+    if (sc.n == 0) return 0;
+    return topk_scan<BiasAdd>(m, reps, sc, BiasAdd::Args{}, s);
 }
 
 uint32_t diverse_max_pool(int d) {
@@ -1268,10 +1294,10 @@ uint32_t diverse_max_pool(int d) {
     return p < 1024u ? p : 1024u;
 }
 
-void launch_diverse_select(const ModelView& m, const uint32_t* pool_items, const float* pool_scores, uint32_t num_users, uint32_t pool,
-                           uint32_t k_out, float trade_off, bool cosine, uint32_t* out_items, float* out_scores, uint32_t* nonfinite_flag,
-                           hipStream_t s) {
-    if (num_users == 0) return;
+int launch_diverse_select(const ModelView& m, const uint32_t* pool_items, const float* pool_scores, uint32_t num_users, uint32_t pool,
+                          uint32_t k_out, float trade_off, bool cosine, uint32_t* out_items, float* out_scores, uint32_t* nonfinite_flag,
+                          hipStream_t s) {
+    if (num_users == 0) return 0;
     /* qh + X + (id, s, mx, r, pk) + red: diverse_select_kernel's layout */
     const size_t lds = ((size_t)m.d + (size_t)pool * (m.d + 1) + 5 * (size_t)pool + 8) * 4;
     int dev = 0;
@@ -1286,38 +1312,25 @@ void launch_diverse_select(const ModelView& m, const uint32_t* pool_items, const
         hipLaunchKernelGGL((diverse_select_kernel<DD>), dim3(num_users), dim3(256), lds, s, m, pool_items, pool_scores, pool, k_out, trade_off,
                            cosine ? 1 : 0, out_items, out_scores, nonfinite_flag);
     });
+    return 1;
 }
 
-void launch_similar_items(const ModelView& m, const uint32_t* query, uint32_t num_queries, bool cosine, float* rnorm, float* H,
-                          const int* rep_row, const uint64_t* excl_ptr, const uint32_t* excl_items, uint32_t k, uint2* lists,
-                          uint32_t* lens, uint32_t* out_items, float* out_scores, uint32_t* nonfinite_flag, hipStream_t s, const TagMasks* f) {
-    if (num_queries == 0) return;
-    uint32_t per = 0;
-    const uint32_t groups = recommend_groups(num_queries, m.num_items, k, &per);
-    const uint32_t utiles = (num_queries + 127) / 128;
-    uint32_t n = 1;
-    while (n < groups * k) n <<= 1;
-    ModelView mr = m; /* the scan's per-item value: r in the bias's place, so ItemTiles brings it in as it brings the bias */
-    mr.b = rnorm;
+int launch_similar_items(const ModelView& m, const uint32_t* query, bool cosine, float* rnorm, float* H, const TopkScan& sc, hipStream_t s) {
+    if (sc.n == 0) return 0;
     DISPATCH_D(m.d, {
         hipLaunchKernelGGL((item_rnorm_kernel<DD>), dim3((unsigned)(((uint64_t)m.num_items + 255) / 256)), dim3(256), 0, s, m, cosine ? 1 : 0, rnorm,
-                           nonfinite_flag);
-        hipLaunchKernelGGL((similar_query_kernel<DD>), dim3((unsigned)(((uint64_t)num_queries * (DD / 4) + 255) / 256)), dim3(256), 0, s, m, rnorm,
-                           query, num_queries, H);
-        if (f)
-            hipLaunchKernelGGL((topk_gemm_kernel<DD, ScaleMul, TagFilter>), dim3(utiles, groups), dim3(256), 0, s, mr, H, rep_row, num_queries, excl_ptr,
-                               excl_items, per, k, lists, lens, nonfinite_flag, TagFilter::Args{f->tags, f->any_of, f->none_of}, ScaleMul::Args{});
-        else
-            hipLaunchKernelGGL((topk_gemm_kernel<DD, ScaleMul, NoFilter>), dim3(utiles, groups), dim3(256), 0, s, mr, H, rep_row, num_queries, excl_ptr,
-                               excl_items, per, k, lists, lens, nonfinite_flag, NoFilter::Args{}, ScaleMul::Args{});
-        hipLaunchKernelGGL(topk_merge_kernel, dim3(num_queries), dim3(512), 0, s, lists, lens, groups, k, n, out_items, out_scores);
+                           sc.nonfinite_flag);
+        hipLaunchKernelGGL((similar_query_kernel<DD>), dim3((unsigned)(((uint64_t)sc.n * (DD / 4) + 255) / 256)), dim3(256), 0, s, m, rnorm,
+                           query, sc.n, H);
     });
+    ModelView mr = m; /* the scan's per-item value: r in the bias's place, so ItemTiles brings it in as it brings the bias */
+    mr.b = rnorm;
+    return 2 + topk_scan<ScaleMul>(mr, H, sc, ScaleMul::Args{}, s);
 }
 
-void launch_recommend_among(const ModelView& m, const uint32_t* subset, uint32_t num_subset, float* Esub, float* bsub, const float* reps,
-                            const int* rep_row, uint32_t num_users, const uint64_t* excl_ptr, const uint32_t* excl_items, uint32_t k,
-                            uint2* lists, uint32_t* lens, uint32_t* out_items, float* out_scores, uint32_t* nonfinite_flag, hipStream_t s) {
-    if (num_users == 0 || num_subset == 0) return;
+int launch_recommend_among(const ModelView& m, const uint32_t* subset, uint32_t num_subset, float* Esub, float* bsub, const float* reps,
+                           const TopkScan& sc, hipStream_t s) {
+    if (sc.n == 0 || num_subset == 0) return 0;
     DISPATCH_D(m.d, {
         hipLaunchKernelGGL((subset_gather_kernel<DD>), dim3((unsigned)(((uint64_t)num_subset * (DD / 4) + 255) / 256)), dim3(256), 0, s, m, subset,
                            num_subset, Esub, bsub);
@@ -1326,9 +1339,7 @@ void launch_recommend_among(const ModelView& m, const uint32_t* subset, uint32_t
     ms.E = Esub;
     ms.b = bsub;
     ms.num_items = num_subset;
-    launch_recommend(ms, reps, rep_row, num_users, excl_ptr, excl_items, k, lists, lens, out_items, out_scores, nonfinite_flag, s);
-    const uint64_t n = (uint64_t)num_users * k;
-    hipLaunchKernelGGL(subset_ids_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, subset, out_items, n);
+    return 1 + launch_recommend(ms, reps, sc, s) + launch_subset_ids(subset, sc, s);
 }
 
 void launch_audience_gather(const ModelView& m, const float* rows_table, const uint32_t* rows, uint32_t num_rows, float* T, float* bT,
@@ -1345,43 +1356,31 @@ void launch_audience_gather(const ModelView& m, const float* rows_table, const u
     (void)hipMemsetAsync(bT, 0, (size_t)num_rows * 4, s);
 }
 
-void launch_audience(const ModelView& m, const float* T, const float* bT, uint32_t num_rows, const uint32_t* row_ids, const uint32_t* query,
-                     uint32_t num_queries, const uint64_t* excl_ptr, const uint32_t* excl_rows, uint32_t k, uint2* lists, uint32_t* lens,
-                     uint32_t* out_rows, float* out_scores, uint32_t* nonfinite_flag, hipStream_t s) {
-    if (num_queries == 0 || num_rows == 0) return;
+int launch_audience(const ModelView& m, const float* T, const float* bT, uint32_t num_rows, const uint32_t* row_ids, const TopkScan& sc,
+                    hipStream_t s) {
+    if (sc.n == 0 || num_rows == 0) return 0;
     ModelView mt = m; /* the scan's catalogue: the candidate rows, whose "item" j is row j of T */
     mt.E = const_cast<float*>(T);
     mt.b = const_cast<float*>(bT);
     mt.num_items = num_rows;
-    uint32_t per = 0;
-    const uint32_t groups = recommend_groups(num_queries, num_rows, k, &per);
-    const uint32_t utiles = (num_queries + 127) / 128;
-    uint32_t n = 1;
-    while (n < groups * k) n <<= 1;
-    DISPATCH_D(m.d, {
-        hipLaunchKernelGGL((topk_gemm_kernel<DD, QueryBias, NoFilter>), dim3(utiles, groups), dim3(256), 0, s, mt, m.E,
-                           reinterpret_cast<const int*>(query), num_queries, excl_ptr, excl_rows, per, k, lists, lens, nonfinite_flag,
-                           NoFilter::Args{}, QueryBias::Args{m.b});
-    });
-    hipLaunchKernelGGL(topk_merge_kernel, dim3(num_queries), dim3(512), 0, s, lists, lens, groups, k, n, out_rows, out_scores);
-    if (row_ids) {
-        const uint64_t ne = (uint64_t)num_queries * k;
-        hipLaunchKernelGGL(subset_ids_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, s, row_ids, out_rows, ne);
-    }
+    const int launches = topk_scan<QueryBias>(mt, m.E, sc, QueryBias::Args{m.b}, s);
+    return launches + (row_ids ? launch_subset_ids(row_ids, sc, s) : 0);
 }
 
-void launch_candidate_scores(const ModelView& m, const float* reps, const uint32_t* pair_row, const uint32_t* pair_item, uint64_t num_pairs,
-                             float* out, uint32_t* nonfinite_flag, hipStream_t s) {
-    if (num_pairs == 0) return;
+int launch_candidate_scores(const ModelView& m, const float* reps, const uint32_t* pair_row, const uint32_t* pair_item, uint64_t num_pairs,
+                            float* out, uint32_t* nonfinite_flag, hipStream_t s) {
+    if (num_pairs == 0) return 0;
     DISPATCH_D(m.d, {
         hipLaunchKernelGGL((candidate_score_kernel<DD>), dim3((unsigned)((num_pairs + 255) / 256)), dim3(256), 0, s, m, reps, pair_row, pair_item,
                            num_pairs, out, nonfinite_flag);
     });
+    return 1;
 }
 
-void launch_rep_rows(const float* H, const int* rep_row, uint32_t num_users, int d, int dl, float* out, hipStream_t s) {
-    if (num_users == 0) return;
+int launch_rep_rows(const float* H, const int* rep_row, uint32_t num_users, int d, int dl, float* out, hipStream_t s) {
+    if (num_users == 0) return 0;
     hipLaunchKernelGGL(rep_rows_kernel, dim3((unsigned)(((uint64_t)num_users * dl + 255) / 256)), dim3(256), 0, s, H, rep_row, num_users, d, dl, out);
+    return 1;
 }
 
 }  // namespace sbr

@@ -3,8 +3,9 @@
 // Owns device memory (parameters resident in HBM for the life of the model), restates the
 // reference's training driver (fit_sequence_model, /root/reference/src/models/sequence_model.rs:
 // 70-178) as host-side index work (chunking, shuffles, partitioning, packing) and drives the
-// gfx950 kernels of sbr_kernels.hip and sbr_catalogue.hip on one HIP stream.  There is no CPU compute fallback: without
-// a HIP device every entry point returns SBR_ERR_NO_DEVICE.
+// gfx950 kernels of sbr_kernels.hip and its neighbours: a training step over the model's main stream and the fit plan's side streams
+// (side, sorter, copier, exchange), joined by events; the prediction side (sbr_catalogue.hip, sbr_sessions.hip) on the
+// main stream alone.  There is no CPU compute fallback: without a HIP device every entry point returns SBR_ERR_NO_DEVICE.
 
 #include <hip/hip_runtime.h>
 
@@ -3625,17 +3626,38 @@ sbr_status check_csr(const sbr_model* m, const uint64_t* ptr, uint64_t n, const 
  * store's seen-item memory; only with device rows, and only recommend_scan reads it) the device unites user u's list with what
  * slot seen_slots[u] remembers. */
 struct RepSource {
-    const uint64_t* ptr;
-    const uint32_t* items;
-    const float* reps;  /* null: from histories or item rows */
-    uint64_t held_out;  /* histories: this many items at the end of each are not part of it (mrr_score: the test item) */
-    bool lists;         /* whether the sorted, de-duplicated lists of ptr / items are wanted (with reps or item rows: always) */
+    const uint64_t* ptr = nullptr;
+    const uint32_t* items = nullptr;
+    const float* reps = nullptr;  /* null: from histories or item rows */
+    uint64_t held_out = 0;  /* histories: this many items at the end of each are not part of it (mrr_score: the test item) */
+    bool lists = true;      /* whether the sorted, de-duplicated lists of ptr / items are wanted (with reps or item rows: always) */
     const uint32_t* item_rows = nullptr; /* non-null: the rows come from these item ids, on the device */
     const float* dev_rows = nullptr;     /* non-null: device rows [.][storage width], read in place ... */
     const int* dev_row = nullptr;        /* ... user u's is row dev_row[u] */
     const sbr::SeenView* seen = nullptr; /* non-null: lists come from a store's memory as well ... */
     const uint32_t* seen_slots = nullptr; /* ... user u's (the CALL's index) from this slot */
     bool from_histories() const { return !reps && !item_rows && !dev_rows; }
+    /* the makers (member functions: the file's helpers stand inside extern "C", where a free function may not return a struct) */
+    static RepSource of_histories(const uint64_t* ptr, const uint32_t* items, uint64_t held_out, bool lists) {
+        RepSource s;
+        s.ptr = ptr; s.items = items; s.held_out = held_out; s.lists = lists;
+        return s;
+    }
+    static RepSource of_rows(const float* reps, const uint64_t* excl_ptr = nullptr, const uint32_t* excl_items = nullptr) {
+        RepSource s;
+        s.ptr = excl_ptr; s.items = excl_items; s.reps = reps;
+        return s;
+    }
+    static RepSource of_item_rows(const uint32_t* item_rows, const uint64_t* excl_ptr, const uint32_t* excl_items) {
+        RepSource s;
+        s.ptr = excl_ptr; s.items = excl_items; s.item_rows = item_rows;
+        return s;
+    }
+    /* a session store's rows, read in place: `rows` = session_rep_rows of the call's slots (the caller keeps it alive over the
+     * scan), excl_ptr / excl_items the caller's exclusion lists (null: none); seen_slots non-null (a store with memory): the call's
+     * slots, whose memories the scan unites with those lists */
+    static RepSource of_sessions(const sbr_sessions* st, const std::vector<int>& rows, const uint64_t* excl_ptr, const uint32_t* excl_items,
+                                 const uint32_t* seen_slots);
 };
 
 /* The representations of a chunk's users: user i's is row rep_row[i] of H (eval arena, valid until the next carve_arena; with
@@ -3739,15 +3761,21 @@ bool next_chunk(const std::vector<uint64_t>& unit_user, size_t unit_cap, const R
 
 struct CopyOut { void* host; const void* device; size_t bytes; }; /* host null: not wanted */
 
-/* The tail of every catalogue scan: `launch` (its `launches` kernels, timed as SBR_K_RANK) with the non-finite-score flag cleared
- * before it, then — the stream drained, so the caller's host vectors have been read by their asynchronous copies — the flag
- * and, if it is clear, the results. */
-sbr_status scan_launch(sbr_model* m, uint64_t launches, uint32_t* d_flag, const std::function<void()>& launch,
-                       std::initializer_list<CopyOut> outs) {
+/* a host CSR to its device arrays, by asynchronous copies: ptr, then the items unless there are none */
+sbr_status upload_csr(sbr_model* m, uint64_t* d_ptr, const std::vector<uint64_t>& ptr, uint32_t* d_items, const std::vector<uint32_t>& items) {
+    HIPCHK(hipMemcpyAsync(d_ptr, ptr.data(), ptr.size() * 8, hipMemcpyHostToDevice, m->stream));
+    if (!items.empty()) HIPCHK(hipMemcpyAsync(d_items, items.data(), items.size() * 4, hipMemcpyHostToDevice, m->stream));
+    return SBR_OK;
+}
+
+/* The tail of every catalogue scan: `launch` (timed as SBR_K_RANK; it returns the launches its launchers report, the ledger's
+ * count) with the non-finite-score flag cleared before it, then — the stream drained, so the caller's host vectors have been read
+ * by their asynchronous copies — the flag and, if it is clear, the results. */
+sbr_status scan_launch(sbr_model* m, uint32_t* d_flag, const std::function<int()>& launch, std::initializer_list<CopyOut> outs) {
     HIPCHK(hipMemsetAsync(d_flag, 0, 4, m->stream));
     {
-        ScopedTimer t(m, SBR_K_RANK, launches);
-        launch();
+        ScopedTimer t(m, SBR_K_RANK, 0);
+        t.tp.launches = (uint64_t)launch();
     }
     uint32_t flag = 0;
     HIPCHK(hipStreamSynchronize(m->stream));
@@ -3771,7 +3799,7 @@ sbr_status sbr_user_representation(sbr_model* m, const uint32_t* item_ids, uint6
         if (first[t] >= m->hp.num_items) return SBR_ERR_INVALID_ARGUMENT;
     const uint64_t ptr[2] = {0, n};
     UserReps ur;
-    SBRCHK(user_reps(m, RepSource{ptr, item_ids, nullptr, 0, false}, std::vector<uint64_t>(1, 0), [](DeviceArena&) {}, &ur));
+    SBRCHK(user_reps(m, RepSource::of_histories(ptr, item_ids, 0, false), std::vector<uint64_t>(1, 0), [](DeviceArena&) {}, &ur));
     hipError_t e = hipMemcpy(out_dim, ur.H + (size_t)ur.rep_row[0] * m->d, (size_t)m->dl * 4, hipMemcpyDeviceToHost);
     return e == hipSuccess ? SBR_OK : SBR_ERR_HIP;
 }
@@ -3832,7 +3860,7 @@ sbr_status sbr_mrr_score(sbr_model* m, const uint64_t* user_ptr, const uint32_t*
     if (out_num_ranked) *out_num_ranked = users.size();
     std::vector<uint32_t> ranks(users.size(), 0);
     /* train_items = all but last (evaluation.rs:24); ALL history items of a user are masked (evaluation.rs:30-32) */
-    const RepSource s{user_ptr, item_ids, nullptr, 1, true};
+    const RepSource s = RepSource::of_histories(user_ptr, item_ids, 1, true);
     for (Chunk ch; next_chunk(users, eval_units_cap, s, m->hp.max_sequence_length, &ch);) {
         const size_t nu = ch.users.size();
         UserReps ur;
@@ -3848,10 +3876,9 @@ sbr_status sbr_mrr_score(sbr_model* m, const uint64_t* user_ptr, const uint32_t*
         HIPCHK(hipMemcpyAsync(mb.rep, ur.rep_row.data(), nu * 4, hipMemcpyHostToDevice, m->stream));
         HIPCHK(hipMemcpyAsync(mb.test, test_item.data(), nu * 4, hipMemcpyHostToDevice, m->stream));
         HIPCHK(hipMemcpyAsync(mb.tih, test_in_hist.data(), nu * 4, hipMemcpyHostToDevice, m->stream));
-        if (!hist_items.empty()) HIPCHK(hipMemcpyAsync(mb.hist, hist_items.data(), hist_items.size() * 4, hipMemcpyHostToDevice, m->stream));
-        HIPCHK(hipMemcpyAsync(mb.hptr, hist_ptr.data(), (nu + 1) * 8, hipMemcpyHostToDevice, m->stream));
-        SBRCHK(scan_launch(m, 1, mb.flag, [&] {
-            sbr::launch_rank(m->mv, ur.H, mb.rep, (uint32_t)nu, mb.test, mb.tih, mb.hptr, mb.hist, mb.ts, mb.ranks, mb.flag, m->stream);
+        SBRCHK(upload_csr(m, mb.hptr, hist_ptr, mb.hist, hist_items));
+        SBRCHK(scan_launch(m, mb.flag, [&] {
+            return sbr::launch_rank(m->mv, ur.H, mb.rep, (uint32_t)nu, mb.test, mb.tih, mb.hptr, mb.hist, mb.ts, mb.ranks, mb.flag, m->stream);
         }, {{ranks.data() + ch.c0, mb.ranks, nu * 4}}));
     }
     float sum = 0.0f; /* evaluation.rs:47 — sequential f32 sum in user order */
@@ -3905,6 +3932,17 @@ struct TopkBufs {
         scores = ar.take<float>(nu * k);
         flag = ar.take<uint32_t>(1);
     }
+    /* the launch's descriptor over these buffers: nu users at k, with the exclusion CSR in eptr / excl or without one, scores
+     * wanted or not, tags = the model's item tags where the masks filter (with_masks), else null */
+    sbr::TopkScan scan(size_t nu, uint32_t k, bool exclusions, bool want_scores, const uint32_t* tags = nullptr) const {
+        sbr::TopkScan sc{};
+        sc.rep_row = rep; sc.n = (uint32_t)nu; sc.k = k;
+        sc.excl_ptr = exclusions ? eptr : nullptr; sc.excl_items = excl;
+        sc.lists = lists; sc.lens = lens; sc.out_items = items; sc.out_scores = want_scores ? scores : nullptr;
+        sc.nonfinite_flag = flag;
+        sc.f = sbr::TagMasks{tags, any_of, none_of};
+        return sc;
+    }
 };
 
 /* device buffers of recommend_among's sub-table of ns items, made anew by every launch (the arena does not outlive a carve) */
@@ -3948,25 +3986,39 @@ struct TagFilterArg {
     const uint32_t *any_of, *none_of;
 };
 
+/* which variant of the top-k scan a call asks for; the default is plain recommend */
+struct ScanVariant {
+    bool cosine = false;                            /* item rows: rank by cosine, not by the plain dot product */
+    const std::vector<uint32_t>* subset = nullptr;  /* recommend_among's item set */
+    const Diverse* dv = nullptr;
+    const TagFilterArg* flt = nullptr;
+    static ScanVariant of(const Diverse* dv, const TagFilterArg* flt) {
+        ScanVariant v;
+        v.dv = dv; v.flt = flt;
+        return v;
+    }
+};
+
 /* top-k of every user of `s`, in chunks; results to out_items / out_scores (host, num_users x k; scores optional).  With item rows
- * (similar_items: the users are the queries) the launch makes the rows itself and ranks by cosine, or by the plain dot product.
- * With `subset` (recommend_among: sorted, unique, not empty) only its items are scanned, as a sub-table every launch gathers.
- * With `dv` (recommend_diverse; not with item rows or a subset) the scan's rows are the users' pools: the same launch selects
+ * (similar_items: the users are the queries) the launch makes the rows itself and ranks by cosine (v.cosine), or by the plain dot
+ * product.
+ * With v.subset (recommend_among: sorted, unique, not empty) only its items are scanned, as a sub-table every launch gathers.
+ * With v.dv (recommend_diverse; not with item rows or a subset) the scan's rows are the users' pools: the same launch selects
  * dv->k_out of each, and the results are num_users x dv->k_out.
- * With `flt` (not with a subset) the scan offers user u only the items its masks allow against the model's item tags, which must be
+ * With v.flt (not with a subset) the scan offers user u only the items its masks allow against the model's item tags, which must be
  * set; the masks go with the call's user u through the chunks, whatever row of H holds its representation.
  * With s.seen (a session store's memory; not with a subset) the exclusion CSR is made on the device: user i of a chunk has the
  * segment [i w + c_i, (i + 1) w + c_(i + 1)), c = the chunk's caller-list pointers — known to the host without any device-side
  * count — which session_seen_lists_kernel fills, ahead of the scan, with the merge of the slot's memory and the caller's list. */
 sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, uint32_t k, uint32_t* out_items, float* out_scores,
-                          bool cosine = false, const std::vector<uint32_t>* subset = nullptr, const Diverse* dv = nullptr,
-                          const TagFilterArg* flt = nullptr) {
-    if (flt && (!m->item_tags || subset)) return SBR_ERR_INVALID_ARGUMENT;
-    if (s.seen && subset) return SBR_ERR_INVALID_ARGUMENT;
+                          const ScanVariant& v = ScanVariant()) {
+    const Diverse* dv = v.dv;
+    if (v.flt && (!m->item_tags || v.subset)) return SBR_ERR_INVALID_ARGUMENT;
+    if (s.seen && v.subset) return SBR_ERR_INVALID_ARGUMENT;
     const size_t seen_w = s.seen ? s.seen->w : 0;
     std::vector<uint64_t> users(num_users);
     for (uint64_t u = 0; u < num_users; ++u) users[u] = u;
-    const uint32_t scanned_items = subset ? (uint32_t)subset->size() : (uint32_t)m->hp.num_items;
+    const uint32_t scanned_items = v.subset ? (uint32_t)v.subset->size() : (uint32_t)m->hp.num_items;
     const size_t cap = recommend_users_cap(scanned_items, k);
     for (Chunk ch; next_chunk(users, cap, s, m->hp.max_sequence_length, &ch);) {
         const size_t nu = ch.users.size();
@@ -3978,13 +4030,13 @@ sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, 
         float* dv_scores = nullptr;
         uint32_t *seen_slot = nullptr, *seen_caller = nullptr; /* s.seen: the chunk's slots and caller lists, the build kernel's inputs */
         SBRCHK(user_reps(m, s, ch.users, [&](DeviceArena& ar) {
-            tb.carve(ar, scanned_items, nu, nu * seen_w + ur.b.list_items.size(), k, flt != nullptr);
+            tb.carve(ar, scanned_items, nu, nu * seen_w + ur.b.list_items.size(), k, v.flt != nullptr);
             if (s.seen) {
                 seen_slot = ar.take<uint32_t>(nu);
                 seen_caller = ar.take<uint32_t>(ur.b.list_items.size() + 1);
             }
             if (s.item_rows) rnorm = ar.take<float>(m->hp.num_items);
-            if (subset) sb.carve(ar, subset->size(), (size_t)m->d);
+            if (v.subset) sb.carve(ar, v.subset->size(), (size_t)m->d);
             if (dv) {
                 dv_items = ar.take<uint32_t>(nu * dv->k_out);
                 dv_scores = ar.take<float>(nu * dv->k_out);
@@ -3993,9 +4045,9 @@ sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, 
         const bool excl = !ur.b.list_ptr.empty() || s.seen;
         std::vector<uint64_t> seen_eptr; /* s.seen: the segments' bounds and the chunk's slots, read by asynchronous copies */
         std::vector<uint32_t> seen_slots;
-        if (subset) {
-            if (excl) lists_to_subset_positions(*subset, &ur.b.list_ptr, &ur.b.list_items);
-            HIPCHK(hipMemcpyAsync(sb.ids, subset->data(), subset->size() * 4, hipMemcpyHostToDevice, m->stream));
+        if (v.subset) {
+            if (excl) lists_to_subset_positions(*v.subset, &ur.b.list_ptr, &ur.b.list_items);
+            HIPCHK(hipMemcpyAsync(sb.ids, v.subset->data(), v.subset->size() * 4, hipMemcpyHostToDevice, m->stream));
         }
         HIPCHK(hipMemcpyAsync(tb.rep, ur.rep_row.data(), nu * 4, hipMemcpyHostToDevice, m->stream));
         if (s.seen) {
@@ -4004,43 +4056,31 @@ sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, 
             for (size_t i = 0; i <= nu; ++i) seen_eptr[i] = i * seen_w + (ur.b.list_ptr.empty() ? 0 : ur.b.list_ptr[i]);
             for (size_t i = 0; i < nu; ++i) seen_slots[i] = s.seen_slots[ch.users[i]]; /* the call's index, not the chunk's */
             HIPCHK(hipMemcpyAsync(seen_slot, seen_slots.data(), nu * 4, hipMemcpyHostToDevice, m->stream));
-            HIPCHK(hipMemcpyAsync(tb.eptr, seen_eptr.data(), (nu + 1) * 8, hipMemcpyHostToDevice, m->stream));
-            if (!ur.b.list_items.empty())
-                HIPCHK(hipMemcpyAsync(seen_caller, ur.b.list_items.data(), ur.b.list_items.size() * 4, hipMemcpyHostToDevice, m->stream));
-        } else if (excl) {
-            HIPCHK(hipMemcpyAsync(tb.eptr, ur.b.list_ptr.data(), (nu + 1) * 8, hipMemcpyHostToDevice, m->stream));
-            if (!ur.b.list_items.empty())
-                HIPCHK(hipMemcpyAsync(tb.excl, ur.b.list_items.data(), ur.b.list_items.size() * 4, hipMemcpyHostToDevice, m->stream));
-        }
+            SBRCHK(upload_csr(m, tb.eptr, seen_eptr, seen_caller, ur.b.list_items));
+        } else if (excl)
+            SBRCHK(upload_csr(m, tb.eptr, ur.b.list_ptr, tb.excl, ur.b.list_items));
         std::vector<uint32_t> masks; /* the chunk's users' any_of, then their none_of */
-        sbr::TagMasks tm{m->item_tags, tb.any_of, tb.none_of};
-        const sbr::TagMasks* f = flt ? &tm : nullptr;
-        if (flt) {
+        if (v.flt) {
             masks.assign(2 * nu, 0u);
             for (size_t i = 0; i < nu; ++i) {
-                if (flt->any_of) masks[i] = flt->any_of[ch.users[i]];
-                if (flt->none_of) masks[nu + i] = flt->none_of[ch.users[i]];
+                if (v.flt->any_of) masks[i] = v.flt->any_of[ch.users[i]];
+                if (v.flt->none_of) masks[nu + i] = v.flt->none_of[ch.users[i]];
             }
             HIPCHK(hipMemcpyAsync(tb.any_of, masks.data(), nu * 4, hipMemcpyHostToDevice, m->stream));
             HIPCHK(hipMemcpyAsync(tb.none_of, masks.data() + nu, nu * 4, hipMemcpyHostToDevice, m->stream));
         }
         const size_t ko = dv ? dv->k_out : k; /* the width of the rows that leave */
-        SBRCHK(scan_launch(m, (s.item_rows || subset ? 4 : dv ? 3 : 2) + (s.seen ? 1 : 0), tb.flag, [&] {
-            if (s.seen) sbr::launch_session_seen_lists(*s.seen, seen_slot, (int)nu, tb.eptr, seen_caller, tb.excl, m->stream);
-            if (dv) { /* the selection reads the pool's scores whether or not the caller wants any */
-                sbr::launch_recommend(m->mv, ur.H, tb.rep, (uint32_t)nu, excl ? tb.eptr : nullptr, tb.excl, k, tb.lists, tb.lens, tb.items,
-                                      tb.scores, tb.flag, m->stream, f);
-                sbr::launch_diverse_select(m->mv, tb.items, tb.scores, (uint32_t)nu, k, dv->k_out, dv->trade_off, dv->metric == SBR_SIMILAR_COSINE,
-                                           dv_items, out_scores ? dv_scores : nullptr, tb.flag, m->stream);
-            } else if (subset)
-                sbr::launch_recommend_among(m->mv, sb.ids, scanned_items, sb.E, sb.b, ur.H, tb.rep, (uint32_t)nu, excl ? tb.eptr : nullptr, tb.excl,
-                                            k, tb.lists, tb.lens, tb.items, out_scores ? tb.scores : nullptr, tb.flag, m->stream);
-            else if (s.item_rows)
-                sbr::launch_similar_items(m->mv, ur.d_item_rows, (uint32_t)nu, cosine, rnorm, ur.H, tb.rep, excl ? tb.eptr : nullptr, tb.excl, k,
-                                          tb.lists, tb.lens, tb.items, out_scores ? tb.scores : nullptr, tb.flag, m->stream, f);
-            else
-                sbr::launch_recommend(m->mv, ur.H, tb.rep, (uint32_t)nu, excl ? tb.eptr : nullptr, tb.excl, k, tb.lists, tb.lens, tb.items,
-                                      out_scores ? tb.scores : nullptr, tb.flag, m->stream, f);
+        /* the selection reads the pool's scores whether or not the caller wants any */
+        const sbr::TopkScan sc = tb.scan(nu, k, excl, out_scores || dv, v.flt ? m->item_tags : nullptr);
+        SBRCHK(scan_launch(m, tb.flag, [&] {
+            int n = s.seen ? sbr::launch_session_seen_lists(*s.seen, seen_slot, (int)nu, tb.eptr, seen_caller, tb.excl, m->stream) : 0;
+            if (v.subset) n += sbr::launch_recommend_among(m->mv, sb.ids, scanned_items, sb.E, sb.b, ur.H, sc, m->stream);
+            else if (s.item_rows) n += sbr::launch_similar_items(m->mv, ur.d_item_rows, v.cosine, rnorm, ur.H, sc, m->stream);
+            else n += sbr::launch_recommend(m->mv, ur.H, sc, m->stream);
+            if (dv)
+                n += sbr::launch_diverse_select(m->mv, tb.items, tb.scores, (uint32_t)nu, k, dv->k_out, dv->trade_off, dv->metric == SBR_SIMILAR_COSINE,
+                                                dv_items, out_scores ? dv_scores : nullptr, tb.flag, m->stream);
+            return n;
         }, {{out_items + ch.c0 * ko, dv ? dv_items : tb.items, nu * ko * 4},
             {out_scores ? out_scores + ch.c0 * ko : nullptr, dv ? dv_scores : tb.scores, nu * ko * 4}}));
     }
@@ -4052,28 +4092,41 @@ bool excl_args_ok(const uint64_t* excl_ptr, const uint32_t* excl_items, uint64_t
     return (excl_ptr == nullptr) == (excl_items == nullptr) || (excl_ptr && excl_ptr[num_users] == excl_ptr[0]);
 }
 
-/* the plain calls and their *_filtered forms (flt non-null) */
+/* the arguments the recommend_diverse calls share */
+bool diverse_args_ok(const sbr_model* m, uint32_t k, uint32_t pool, float trade_off, uint32_t metric) {
+    return k >= 1 && pool >= k && pool <= sbr::diverse_max_pool(m->d) && trade_off >= 0.0f && trade_off <= 1.0f /* false for a NaN */ &&
+           metric <= SBR_SIMILAR_DOT;
+}
+
+/* k of a call of the recommend family, which scans at k: the plain call's own k, or with dv (recommend_diverse) the pool, of
+ * which the selection keeps dv->k_out, the caller's k */
+bool scan_k_ok(const sbr_model* m, uint32_t k, const Diverse* dv) {
+    return dv ? diverse_args_ok(m, dv->k_out, k, dv->trade_off, dv->metric) : k >= 1 && k <= SBR_RECOMMEND_MAX_K;
+}
+
+/* the plain calls, their *_filtered forms (flt non-null) and their diverse forms (dv non-null: k is the pool) */
 sbr_status recommend_call(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users, uint32_t k, uint32_t flags,
-                          uint32_t* out_items, float* out_scores, const TagFilterArg* flt) {
+                          uint32_t* out_items, float* out_scores, const TagFilterArg* flt, const Diverse* dv = nullptr) {
     if (!m || !user_ptr || (num_users && !out_items)) return SBR_ERR_INVALID_ARGUMENT;
-    if (k < 1 || k > SBR_RECOMMEND_MAX_K || (flags & ~SBR_RECOMMEND_INCLUDE_HISTORY)) return SBR_ERR_INVALID_ARGUMENT;
+    if (!scan_k_ok(m, k, dv) || (flags & ~SBR_RECOMMEND_INCLUDE_HISTORY)) return SBR_ERR_INVALID_ARGUMENT;
     std::lock_guard<std::mutex> lock(m->mu);
     SBRCHK(enter_reader(m));
     SBRCHK(check_csr(m, user_ptr, num_users, item_ids, false));
     /* the WHOLE history is masked (evaluation.rs:30-32) */
-    return recommend_scan(m, RepSource{user_ptr, item_ids, nullptr, 0, !(flags & SBR_RECOMMEND_INCLUDE_HISTORY)}, num_users, k, out_items, out_scores,
-                          false, nullptr, nullptr, flt);
+    return recommend_scan(m, RepSource::of_histories(user_ptr, item_ids, 0, !(flags & SBR_RECOMMEND_INCLUDE_HISTORY)), num_users, k, out_items,
+                          out_scores, ScanVariant::of(dv, flt));
 }
 
 sbr_status recommend_reps_call(sbr_model* m, const float* reps, uint64_t num_users, uint32_t k, const uint64_t* excl_ptr,
-                               const uint32_t* excl_items, uint32_t* out_items, float* out_scores, const TagFilterArg* flt) {
+                               const uint32_t* excl_items, uint32_t* out_items, float* out_scores, const TagFilterArg* flt,
+                               const Diverse* dv = nullptr) {
     if (!m || (num_users && (!reps || !out_items))) return SBR_ERR_INVALID_ARGUMENT;
-    if (k < 1 || k > SBR_RECOMMEND_MAX_K) return SBR_ERR_INVALID_ARGUMENT;
+    if (!scan_k_ok(m, k, dv)) return SBR_ERR_INVALID_ARGUMENT;
     if (!excl_args_ok(excl_ptr, excl_items, num_users)) return SBR_ERR_INVALID_ARGUMENT;
     std::lock_guard<std::mutex> lock(m->mu);
     SBRCHK(enter_reader(m));
     if (excl_ptr) SBRCHK(check_csr(m, excl_ptr, num_users, excl_items, false));
-    return recommend_scan(m, RepSource{excl_ptr, excl_items, reps, 0, true}, num_users, k, out_items, out_scores, false, nullptr, nullptr, flt);
+    return recommend_scan(m, RepSource::of_rows(reps, excl_ptr, excl_items), num_users, k, out_items, out_scores, ScanVariant::of(dv, flt));
 }
 
 }  // namespace
@@ -4132,42 +4185,6 @@ sbr_status sbr_recommend_filtered_reps(sbr_model* m, const float* reps, uint64_t
 /* ---------------------------------------------------------------------------------------------
  * diversified top-k: recommend's scan at k = pool, then the selection (sbr_catalogue.hip)
  * ------------------------------------------------------------------------------------------- */
-namespace {
-
-/* the arguments the three recommend_diverse calls share */
-bool diverse_args_ok(const sbr_model* m, uint32_t k, uint32_t pool, float trade_off, uint32_t metric) {
-    return k >= 1 && pool >= k && pool <= sbr::diverse_max_pool(m->d) && trade_off >= 0.0f && trade_off <= 1.0f /* false for a NaN */ &&
-           metric <= SBR_SIMILAR_DOT;
-}
-
-sbr_status recommend_diverse_call(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users, uint32_t k,
-                                  uint32_t pool, float trade_off, uint32_t metric, uint32_t flags, uint32_t* out_items, float* out_scores,
-                                  const TagFilterArg* flt) {
-    if (!m || !user_ptr || (num_users && !out_items)) return SBR_ERR_INVALID_ARGUMENT;
-    if (!diverse_args_ok(m, k, pool, trade_off, metric) || (flags & ~SBR_RECOMMEND_INCLUDE_HISTORY)) return SBR_ERR_INVALID_ARGUMENT;
-    std::lock_guard<std::mutex> lock(m->mu);
-    SBRCHK(enter_reader(m));
-    SBRCHK(check_csr(m, user_ptr, num_users, item_ids, false));
-    const Diverse dv{k, trade_off, metric};
-    return recommend_scan(m, RepSource{user_ptr, item_ids, nullptr, 0, !(flags & SBR_RECOMMEND_INCLUDE_HISTORY)}, num_users, pool, out_items,
-                          out_scores, false, nullptr, &dv, flt);
-}
-
-sbr_status recommend_diverse_reps_call(sbr_model* m, const float* reps, uint64_t num_users, uint32_t k, uint32_t pool, float trade_off,
-                                       uint32_t metric, const uint64_t* excl_ptr, const uint32_t* excl_items, uint32_t* out_items,
-                                       float* out_scores, const TagFilterArg* flt) {
-    if (!m || (num_users && (!reps || !out_items))) return SBR_ERR_INVALID_ARGUMENT;
-    if (!diverse_args_ok(m, k, pool, trade_off, metric)) return SBR_ERR_INVALID_ARGUMENT;
-    if (!excl_args_ok(excl_ptr, excl_items, num_users)) return SBR_ERR_INVALID_ARGUMENT;
-    std::lock_guard<std::mutex> lock(m->mu);
-    SBRCHK(enter_reader(m));
-    if (excl_ptr) SBRCHK(check_csr(m, excl_ptr, num_users, excl_items, false));
-    const Diverse dv{k, trade_off, metric};
-    return recommend_scan(m, RepSource{excl_ptr, excl_items, reps, 0, true}, num_users, pool, out_items, out_scores, false, nullptr, &dv, flt);
-}
-
-}  // namespace
-
 sbr_status sbr_recommend_diverse_max_pool(const sbr_model* m, uint32_t* out) {
     if (!m || !out) return SBR_ERR_INVALID_ARGUMENT;
     *out = sbr::diverse_max_pool(m->d);
@@ -4176,27 +4193,31 @@ sbr_status sbr_recommend_diverse_max_pool(const sbr_model* m, uint32_t* out) {
 
 sbr_status sbr_recommend_diverse(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users, uint32_t k, uint32_t pool,
                                  float trade_off, uint32_t metric, uint32_t flags, uint32_t* out_items, float* out_scores) {
-    return recommend_diverse_call(m, user_ptr, item_ids, num_users, k, pool, trade_off, metric, flags, out_items, out_scores, nullptr);
+    const Diverse dv{k, trade_off, metric};
+    return recommend_call(m, user_ptr, item_ids, num_users, pool, flags, out_items, out_scores, nullptr, &dv);
 }
 
 sbr_status sbr_recommend_diverse_filtered(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users, uint32_t k,
                                           uint32_t pool, float trade_off, uint32_t metric, uint32_t flags, const uint32_t* any_of,
                                           const uint32_t* none_of, uint32_t* out_items, float* out_scores) {
     const TagFilterArg flt{any_of, none_of};
-    return recommend_diverse_call(m, user_ptr, item_ids, num_users, k, pool, trade_off, metric, flags, out_items, out_scores, &flt);
+    const Diverse dv{k, trade_off, metric};
+    return recommend_call(m, user_ptr, item_ids, num_users, pool, flags, out_items, out_scores, &flt, &dv);
 }
 
 sbr_status sbr_recommend_diverse_reps(sbr_model* m, const float* reps, uint64_t num_users, uint32_t k, uint32_t pool, float trade_off,
                                       uint32_t metric, const uint64_t* excl_ptr, const uint32_t* excl_items, uint32_t* out_items,
                                       float* out_scores) {
-    return recommend_diverse_reps_call(m, reps, num_users, k, pool, trade_off, metric, excl_ptr, excl_items, out_items, out_scores, nullptr);
+    const Diverse dv{k, trade_off, metric};
+    return recommend_reps_call(m, reps, num_users, pool, excl_ptr, excl_items, out_items, out_scores, nullptr, &dv);
 }
 
 sbr_status sbr_recommend_diverse_filtered_reps(sbr_model* m, const float* reps, uint64_t num_users, uint32_t k, uint32_t pool, float trade_off,
                                                uint32_t metric, const uint64_t* excl_ptr, const uint32_t* excl_items, const uint32_t* any_of,
                                                const uint32_t* none_of, uint32_t* out_items, float* out_scores) {
     const TagFilterArg flt{any_of, none_of};
-    return recommend_diverse_reps_call(m, reps, num_users, k, pool, trade_off, metric, excl_ptr, excl_items, out_items, out_scores, &flt);
+    const Diverse dv{k, trade_off, metric};
+    return recommend_reps_call(m, reps, num_users, pool, excl_ptr, excl_items, out_items, out_scores, &flt, &dv);
 }
 
 /* ---------------------------------------------------------------------------------------------
@@ -4228,9 +4249,10 @@ sbr_status similar_items_call(sbr_model* m, const uint32_t* query_items, uint64_
             eptr[j + 1] = eitems.size();
         }
     }
-    RepSource s{self ? excl_ptr : eptr.data(), self ? excl_items : eitems.data(), nullptr, 0, true};
-    s.item_rows = query_items;
-    return recommend_scan(m, s, num_queries, k, out_items, out_scores, metric == SBR_SIMILAR_COSINE, nullptr, nullptr, flt);
+    ScanVariant v = ScanVariant::of(nullptr, flt);
+    v.cosine = metric == SBR_SIMILAR_COSINE;
+    return recommend_scan(m, RepSource::of_item_rows(query_items, self ? excl_ptr : eptr.data(), self ? excl_items : eitems.data()), num_queries, k,
+                          out_items, out_scores, v);
 }
 
 }  // namespace
@@ -4267,7 +4289,9 @@ sbr_status recommend_among_scan(sbr_model* m, const RepSource& s, uint64_t num_u
         if (out_scores) std::fill(out_scores, out_scores + num_users * k, -INFINITY);
         return SBR_OK;
     }
-    return recommend_scan(m, s, num_users, k, out_items, out_scores, false, &subset);
+    ScanVariant v;
+    v.subset = &subset;
+    return recommend_scan(m, s, num_users, k, out_items, out_scores, v);
 }
 
 /* device buffers of launch_candidate_scores over np pairs */
@@ -4311,8 +4335,8 @@ sbr_status score_candidates_scan(sbr_model* m, const RepSource& s, uint64_t num_
             }
             HIPCHK(hipMemcpyAsync(cb.row, row.data(), n * 4, hipMemcpyHostToDevice, m->stream));
             HIPCHK(hipMemcpyAsync(cb.item, cand_items + q, n * 4, hipMemcpyHostToDevice, m->stream));
-            SBRCHK(scan_launch(m, 1, cb.flag, [&] {
-                sbr::launch_candidate_scores(m->mv, ur.H, cb.row, cb.item, n, cb.scores, cb.flag, m->stream);
+            SBRCHK(scan_launch(m, cb.flag, [&] {
+                return sbr::launch_candidate_scores(m->mv, ur.H, cb.row, cb.item, n, cb.scores, cb.flag, m->stream);
             }, {{out_scores + (q - cand_ptr[0]), cb.scores, n * 4}}));
         }
     }
@@ -4328,7 +4352,7 @@ sbr_status sbr_user_representations(sbr_model* m, const uint64_t* user_ptr, cons
     SBRCHK(check_csr(m, user_ptr, num_users, item_ids, false));
     std::vector<uint64_t> users(num_users);
     for (uint64_t u = 0; u < num_users; ++u) users[u] = u;
-    const RepSource s{user_ptr, item_ids, nullptr, 0, false};
+    const RepSource s = RepSource::of_histories(user_ptr, item_ids, 0, false);
     const size_t dl = (size_t)m->dl;
     for (Chunk ch; next_chunk(users, eval_units_cap, s, m->hp.max_sequence_length, &ch);) {
         const size_t nu = ch.users.size();
@@ -4342,7 +4366,7 @@ sbr_status sbr_user_representations(sbr_model* m, const uint64_t* user_ptr, cons
             flag = ar.take<uint32_t>(1);
         }, &ur));
         HIPCHK(hipMemcpyAsync(rep, ur.rep_row.data(), nu * 4, hipMemcpyHostToDevice, m->stream));
-        SBRCHK(scan_launch(m, 1, flag, [&] { sbr::launch_rep_rows(ur.H, rep, (uint32_t)nu, m->d, m->dl, rows, m->stream); },
+        SBRCHK(scan_launch(m, flag, [&] { return sbr::launch_rep_rows(ur.H, rep, (uint32_t)nu, m->d, m->dl, rows, m->stream); },
                            {{out_reps + ch.c0 * dl, rows, nu * dl * 4}}));
     }
     return SBR_OK;
@@ -4354,7 +4378,7 @@ sbr_status sbr_score_candidates(sbr_model* m, const uint64_t* user_ptr, const ui
     std::lock_guard<std::mutex> lock(m->mu);
     SBRCHK(enter_reader(m));
     SBRCHK(check_csr(m, user_ptr, num_users, item_ids, false));
-    return score_candidates_scan(m, RepSource{user_ptr, item_ids, nullptr, 0, false}, num_users, cand_ptr, cand_items, out_scores);
+    return score_candidates_scan(m, RepSource::of_histories(user_ptr, item_ids, 0, false), num_users, cand_ptr, cand_items, out_scores);
 }
 
 sbr_status sbr_score_candidates_reps(sbr_model* m, const float* reps, uint64_t num_users, const uint64_t* cand_ptr, const uint32_t* cand_items,
@@ -4362,7 +4386,7 @@ sbr_status sbr_score_candidates_reps(sbr_model* m, const float* reps, uint64_t n
     if (!m || (num_users && !reps)) return SBR_ERR_INVALID_ARGUMENT;
     std::lock_guard<std::mutex> lock(m->mu);
     SBRCHK(enter_reader(m));
-    return score_candidates_scan(m, RepSource{nullptr, nullptr, reps, 0, false}, num_users, cand_ptr, cand_items, out_scores);
+    return score_candidates_scan(m, RepSource::of_rows(reps), num_users, cand_ptr, cand_items, out_scores);
 }
 
 sbr_status sbr_recommend_among(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users, uint32_t k, uint32_t flags,
@@ -4372,7 +4396,7 @@ sbr_status sbr_recommend_among(sbr_model* m, const uint64_t* user_ptr, const uin
     std::lock_guard<std::mutex> lock(m->mu);
     SBRCHK(enter_reader(m));
     SBRCHK(check_csr(m, user_ptr, num_users, item_ids, false));
-    return recommend_among_scan(m, RepSource{user_ptr, item_ids, nullptr, 0, !(flags & SBR_RECOMMEND_INCLUDE_HISTORY)}, num_users, k, subset_items,
+    return recommend_among_scan(m, RepSource::of_histories(user_ptr, item_ids, 0, !(flags & SBR_RECOMMEND_INCLUDE_HISTORY)), num_users, k, subset_items,
                                 num_subset, out_items, out_scores);
 }
 
@@ -4385,7 +4409,7 @@ sbr_status sbr_recommend_among_reps(sbr_model* m, const float* reps, uint64_t nu
     std::lock_guard<std::mutex> lock(m->mu);
     SBRCHK(enter_reader(m));
     if (excl_ptr) SBRCHK(check_csr(m, excl_ptr, num_users, excl_items, false));
-    return recommend_among_scan(m, RepSource{excl_ptr, excl_items, reps, 0, true}, num_users, k, subset_items, num_subset, out_items, out_scores);
+    return recommend_among_scan(m, RepSource::of_rows(reps, excl_ptr, excl_items), num_users, k, subset_items, num_subset, out_items, out_scores);
 }
 
 /* ---------------------------------------------------------------------------------------------
@@ -4452,13 +4476,9 @@ sbr_status rank_targets_scan(sbr_model* m, const RepSource& s, uint64_t num_user
         HIPCHK(hipMemcpyAsync(rb.lu, ch.lu.data(), ns * 4, hipMemcpyHostToDevice, m->stream));
         HIPCHK(hipMemcpyAsync(rb.sptr, sptr.data(), (ns + 1) * 4, hipMemcpyHostToDevice, m->stream));
         HIPCHK(hipMemcpyAsync(rb.tgt, target_items + t0, nt * 4, hipMemcpyHostToDevice, m->stream));
-        if (mask) {
-            HIPCHK(hipMemcpyAsync(rb.mptr, ur.b.list_ptr.data(), (nlu + 1) * 8, hipMemcpyHostToDevice, m->stream));
-            if (!ur.b.list_items.empty())
-                HIPCHK(hipMemcpyAsync(rb.mask, ur.b.list_items.data(), ur.b.list_items.size() * 4, hipMemcpyHostToDevice, m->stream));
-        }
-        SBRCHK(scan_launch(m, 3, rb.flag, [&] {
-            sbr::launch_rank_targets(m->mv, ur.H, rb.rep, rb.lu, rb.sptr, (uint32_t)ns, rb.tgt, mask ? rb.mptr : nullptr, rb.mask, rb.ts, rb.pos,
+        if (mask) SBRCHK(upload_csr(m, rb.mptr, ur.b.list_ptr, rb.mask, ur.b.list_items));
+        SBRCHK(scan_launch(m, rb.flag, [&] {
+            return sbr::launch_rank_targets(m->mv, ur.H, rb.rep, rb.lu, rb.sptr, (uint32_t)ns, rb.tgt, mask ? rb.mptr : nullptr, rb.mask, rb.ts, rb.pos,
                                      rb.th, rb.tmin, rb.tmin2, rb.buckets, rb.totals, rb.ranks, rb.flag, m->stream);
         }, {{out_ranks + (t0 - target_ptr[0]), rb.ranks, nt * 4}}));
     }
@@ -4474,7 +4494,7 @@ sbr_status sbr_rank_targets(sbr_model* m, const uint64_t* user_ptr, const uint32
     SBRCHK(enter_reader(m));
     SBRCHK(check_csr(m, user_ptr, num_users, item_ids, false));
     /* the WHOLE history is masked (evaluation.rs:30-32) */
-    return rank_targets_scan(m, RepSource{user_ptr, item_ids, nullptr, 0, !(flags & SBR_RANK_INCLUDE_HISTORY)}, num_users, target_ptr,
+    return rank_targets_scan(m, RepSource::of_histories(user_ptr, item_ids, 0, !(flags & SBR_RANK_INCLUDE_HISTORY)), num_users, target_ptr,
                              target_items, out_ranks);
 }
 
@@ -4485,7 +4505,7 @@ sbr_status sbr_rank_targets_reps(sbr_model* m, const float* reps, uint64_t num_u
     std::lock_guard<std::mutex> lock(m->mu);
     SBRCHK(enter_reader(m));
     if (excl_ptr) SBRCHK(check_csr(m, excl_ptr, num_users, excl_items, false));
-    return rank_targets_scan(m, RepSource{excl_ptr, excl_items, reps, 0, true}, num_users, target_ptr, target_items, out_ranks);
+    return rank_targets_scan(m, RepSource::of_rows(reps, excl_ptr, excl_items), num_users, target_ptr, target_items, out_ranks);
 }
 
 /* ---------------------------------------------------------------------------------------------
@@ -4588,6 +4608,11 @@ sbr_status sessions_append(sbr_sessions* st, const uint32_t* slots, uint64_t n, 
     return SBR_OK;
 }
 
+/* the store's device arrays back to the scratch cache (the caller has drained the stream: nothing may still read them) */
+void sessions_free(sbr_sessions* st) {
+    dfree(st->v.H); dfree(st->v.C); dfree(st->v.len); dfree(st->seen.ring); dfree(st->seen.cnt);
+}
+
 /* every slot empty, the empty-history row made from the model's current parameters, the store bound to them */
 sbr_status sessions_rebind(sbr_sessions* st) {
     sbr_model* m = st->m;
@@ -4663,7 +4688,7 @@ sbr_status sbr_sessions_create_seen(sbr_model* m, uint64_t capacity, uint32_t se
     }
     if (s != SBR_OK) {
         hipStreamSynchronize(m->stream);
-        dfree(st->v.H); dfree(st->v.C); dfree(st->v.len); dfree(st->seen.ring); dfree(st->seen.cnt);
+        sessions_free(st);
         delete st;
         return s;
     }
@@ -4677,7 +4702,7 @@ void sbr_sessions_destroy(sbr_sessions* st) {
         std::lock_guard<std::mutex> lock(st->m->mu);
         hipSetDevice(st->m->device);
         hipStreamSynchronize(st->m->stream); /* the rows go back to the scratch cache: nothing may still read them */
-        dfree(st->v.H); dfree(st->v.C); dfree(st->v.len); dfree(st->seen.ring); dfree(st->seen.cnt);
+        sessions_free(st);
     }
     delete st;
 }
@@ -4843,18 +4868,22 @@ sbr_status sbr_sessions_set_seen(sbr_sessions* st, const uint32_t* slots, uint64
 
 namespace {
 
-/* the store's memory as the scan's source of lists, slot by the call's index */
-void with_seen(RepSource* s, const sbr_sessions* st, const uint32_t* slots) {
-    s->seen = &st->seen;
-    s->seen_slots = slots;
+RepSource RepSource::of_sessions(const sbr_sessions* st, const std::vector<int>& rows, const uint64_t* excl_ptr, const uint32_t* excl_items,
+                                 const uint32_t* seen_slots) {
+    RepSource s;
+    s.ptr = excl_ptr; s.items = excl_items; s.dev_rows = st->v.H; s.dev_row = rows.data();
+    if (seen_slots) { s.seen = &st->seen; s.seen_slots = seen_slots; }
+    return s;
 }
 
+/* sbr_sessions_recommend*, and with dv (k is the pool) sbr_sessions_recommend_diverse*, which have no flags argument: flags = 0 */
 sbr_status sessions_recommend_call(sbr_sessions* st, const uint32_t* slots, uint64_t n, uint32_t k, const uint64_t* excl_ptr,
-                                   const uint32_t* excl_items, uint32_t flags, uint32_t* out_items, float* out_scores, const TagFilterArg* flt) {
+                                   const uint32_t* excl_items, uint32_t flags, uint32_t* out_items, float* out_scores, const TagFilterArg* flt,
+                                   const Diverse* dv = nullptr) {
     if (!st || (n && !out_items)) return SBR_ERR_INVALID_ARGUMENT;
     /* a store with memory takes sbr_recommend's flag; one without keeps refusing every flag */
     if (st->seen.w ? (flags & ~SBR_RECOMMEND_INCLUDE_HISTORY) != 0 : flags != 0) return SBR_ERR_INVALID_ARGUMENT;
-    if (k < 1 || k > SBR_RECOMMEND_MAX_K) return SBR_ERR_INVALID_ARGUMENT;
+    if (!scan_k_ok(st->m, k, dv)) return SBR_ERR_INVALID_ARGUMENT;
     if (!excl_args_ok(excl_ptr, excl_items, n)) return SBR_ERR_INVALID_ARGUMENT;
     sbr_model* m = st->m;
     std::lock_guard<std::mutex> lock(m->mu);
@@ -4862,31 +4891,9 @@ sbr_status sessions_recommend_call(sbr_sessions* st, const uint32_t* slots, uint
     SBRCHK(check_slots(st, slots, n));
     if (excl_ptr) SBRCHK(check_csr(m, excl_ptr, n, excl_items, false));
     const std::vector<int> rows = session_rep_rows(st, slots, n);
-    RepSource s{excl_ptr, excl_items, nullptr, 0, true};
-    s.dev_rows = st->v.H;
-    s.dev_row = rows.data();
-    if (st->seen.w && !(flags & SBR_RECOMMEND_INCLUDE_HISTORY)) with_seen(&s, st, slots);
-    return recommend_scan(m, s, n, k, out_items, out_scores, false, nullptr, nullptr, flt);
-}
-
-sbr_status sessions_recommend_diverse_call(sbr_sessions* st, const uint32_t* slots, uint64_t n, uint32_t k, uint32_t pool, float trade_off,
-                                           uint32_t metric, const uint64_t* excl_ptr, const uint32_t* excl_items, uint32_t* out_items,
-                                           float* out_scores, const TagFilterArg* flt) {
-    if (!st || (n && !out_items)) return SBR_ERR_INVALID_ARGUMENT;
-    if (!diverse_args_ok(st->m, k, pool, trade_off, metric)) return SBR_ERR_INVALID_ARGUMENT;
-    if (!excl_args_ok(excl_ptr, excl_items, n)) return SBR_ERR_INVALID_ARGUMENT;
-    sbr_model* m = st->m;
-    std::lock_guard<std::mutex> lock(m->mu);
-    SBRCHK(enter_sessions(st));
-    SBRCHK(check_slots(st, slots, n));
-    if (excl_ptr) SBRCHK(check_csr(m, excl_ptr, n, excl_items, false));
-    const std::vector<int> rows = session_rep_rows(st, slots, n);
-    RepSource s{excl_ptr, excl_items, nullptr, 0, true};
-    s.dev_rows = st->v.H;
-    s.dev_row = rows.data();
-    if (st->seen.w) with_seen(&s, st, slots);
-    const Diverse dv{k, trade_off, metric};
-    return recommend_scan(m, s, n, pool, out_items, out_scores, false, nullptr, &dv, flt);
+    const bool seen = st->seen.w && !(flags & SBR_RECOMMEND_INCLUDE_HISTORY);
+    return recommend_scan(m, RepSource::of_sessions(st, rows, excl_ptr, excl_items, seen ? slots : nullptr), n, k, out_items, out_scores,
+                          ScanVariant::of(dv, flt));
 }
 
 }  // namespace
@@ -4906,14 +4913,16 @@ sbr_status sbr_sessions_recommend_filtered(sbr_sessions* st, const uint32_t* slo
 sbr_status sbr_sessions_recommend_diverse(sbr_sessions* st, const uint32_t* slots, uint64_t n, uint32_t k, uint32_t pool, float trade_off,
                                           uint32_t metric, const uint64_t* excl_ptr, const uint32_t* excl_items, uint32_t* out_items,
                                           float* out_scores) {
-    return sessions_recommend_diverse_call(st, slots, n, k, pool, trade_off, metric, excl_ptr, excl_items, out_items, out_scores, nullptr);
+    const Diverse dv{k, trade_off, metric};
+    return sessions_recommend_call(st, slots, n, pool, excl_ptr, excl_items, 0, out_items, out_scores, nullptr, &dv);
 }
 
 sbr_status sbr_sessions_recommend_diverse_filtered(sbr_sessions* st, const uint32_t* slots, uint64_t n, uint32_t k, uint32_t pool,
                                                    float trade_off, uint32_t metric, const uint64_t* excl_ptr, const uint32_t* excl_items,
                                                    const uint32_t* any_of, const uint32_t* none_of, uint32_t* out_items, float* out_scores) {
     const TagFilterArg flt{any_of, none_of};
-    return sessions_recommend_diverse_call(st, slots, n, k, pool, trade_off, metric, excl_ptr, excl_items, out_items, out_scores, &flt);
+    const Diverse dv{k, trade_off, metric};
+    return sessions_recommend_call(st, slots, n, pool, excl_ptr, excl_items, 0, out_items, out_scores, &flt, &dv);
 }
 
 sbr_status sbr_sessions_score_candidates(sbr_sessions* st, const uint32_t* slots, uint64_t n, const uint64_t* cand_ptr,
@@ -4924,10 +4933,7 @@ sbr_status sbr_sessions_score_candidates(sbr_sessions* st, const uint32_t* slots
     SBRCHK(enter_sessions(st));
     SBRCHK(check_slots(st, slots, n));
     const std::vector<int> rows = session_rep_rows(st, slots, n);
-    RepSource s{nullptr, nullptr, nullptr, 0, false};
-    s.dev_rows = st->v.H;
-    s.dev_row = rows.data();
-    return score_candidates_scan(m, s, n, cand_ptr, cand_items, out_scores);
+    return score_candidates_scan(m, RepSource::of_sessions(st, rows, nullptr, nullptr, nullptr), n, cand_ptr, cand_items, out_scores);
 }
 
 /* ---------------------------------------------------------------------------------------------
@@ -5034,7 +5040,7 @@ sbr_status audience_scan(sbr_model* m, const AudienceSource& src, uint64_t num_r
         std::vector<uint32_t> order, sorted_items;
         std::vector<uint64_t> caller_keys;
         DeviceBlocks chunk(m->stream);
-        const uint64_t* d_eptr = nullptr;
+        bool lists = false;              /* whether tb.eptr holds an exclusion CSR, its entries at d_excl */
         const uint32_t* d_excl = tb.excl;
         if (!src.seen) {
             if (caller_lists) {
@@ -5042,7 +5048,7 @@ sbr_status audience_scan(sbr_model* m, const AudienceSource& src, uint64_t num_r
                 for (size_t j = 0; j <= n; ++j) eptr[j] = excl_ptr[q0 + j] - c0;
                 HIPCHK(hipMemcpyAsync(tb.eptr, eptr.data(), (n + 1) * 8, hipMemcpyHostToDevice, m->stream));
                 if (nc) HIPCHK(hipMemcpyAsync(tb.excl, excl_pos.data() + c0, nc * 4, hipMemcpyHostToDevice, m->stream));
-                d_eptr = tb.eptr;
+                lists = true;
             }
         } else {
             order.resize(n);
@@ -5060,7 +5066,7 @@ sbr_status audience_scan(sbr_model* m, const AudienceSource& src, uint64_t num_r
             HIPCHK(hipMemcpy(&total, counters, 8, hipMemcpyDeviceToHost));
             const unsigned long long nkeys = total + nc;
             if (nkeys >= (1ull << 31)) return SBR_ERR_OUT_OF_MEMORY; /* the key ordering counts with 32 bits */
-            d_eptr = tb.eptr;
+            lists = true;
             if (nkeys == 0) {
                 HIPCHK(hipMemsetAsync(tb.eptr, 0, (n + 1) * 8, m->stream));
             } else {
@@ -5085,10 +5091,9 @@ sbr_status audience_scan(sbr_model* m, const AudienceSource& src, uint64_t num_r
                 d_excl = excl;
             }
         }
-        SBRCHK(scan_launch(m, d_ids ? 3 : 2, tb.flag, [&] {
-            sbr::launch_audience(m->mv, T, bT, (uint32_t)S, d_ids, reinterpret_cast<const uint32_t*>(tb.rep), (uint32_t)n, d_eptr, d_excl, k, tb.lists,
-                                 tb.lens, tb.items, out_scores ? tb.scores : nullptr, tb.flag, m->stream);
-        }, {{out_rows + q0 * k, tb.items, n * k * 4}, {out_scores ? out_scores + q0 * k : nullptr, tb.scores, n * k * 4}}));
+        sbr::TopkScan sc = tb.scan(n, k, lists, out_scores != nullptr);
+        sc.excl_items = d_excl;
+        SBRCHK(scan_launch(m, tb.flag, [&] { return sbr::launch_audience(m->mv, T, bT, (uint32_t)S, d_ids, sc, m->stream); }, {{out_rows + q0 * k, tb.items, n * k * 4}, {out_scores ? out_scores + q0 * k : nullptr, tb.scores, n * k * 4}}));
     }
     return SBR_OK;
 }

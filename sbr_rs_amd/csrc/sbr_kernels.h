@@ -266,80 +266,90 @@ void launch_merge_sort(const PeerLists& pl, int ndev, uint32_t total, uint64_t* 
                        size_t sort_temp_bytes, hipStream_t s);
 void launch_accumulate_loss(const uint8_t* all_blocks, uint64_t block_bytes, int ndev, double* loss_acc,
                             unsigned long long* ex_acc, hipStream_t s);
-/* prediction side (sbr_catalogue.hip) */
+/* prediction side (sbr_catalogue.hip).  A launcher of a catalogue scan (the host's scan_launch brackets it as SBR_K_RANK) returns the
+ * launches the timing ledger counts for it: the kernels it queued, 0 where it had nothing to do — and launch_rank 1, its scan, as
+ * mrr_score has always been counted (its two per-user passes beside the GEMM are not). */
 void launch_predict(const ModelView& m, const float* user, const uint32_t* items, uint64_t n, float* out, hipStream_t s);
-void launch_rank(const ModelView& m, const float* reps, const int* rep_row, uint32_t num_users, const uint32_t* test_item,
-                 const uint32_t* test_in_hist, const uint64_t* hist_ptr, const uint32_t* hist_items, float* ts_scratch,
-                 uint32_t* ranks, uint32_t* nonfinite_flag, hipStream_t s);
+int launch_rank(const ModelView& m, const float* reps, const int* rep_row, uint32_t num_users, const uint32_t* test_item,
+                const uint32_t* test_in_hist, const uint64_t* hist_ptr, const uint32_t* hist_items, float* ts_scratch,
+                uint32_t* ranks, uint32_t* nonfinite_flag, hipStream_t s);
 /* exact ranks of many targets per user state from one scan (sbr_catalogue.hip).  A scan-user is a representation row rep_row[s]
  * with the targets tgt_items[sptr[s] .. sptr[s + 1]), at most rank_targets_tmax(d) of them and at least one; su_user[s] indexes
  * mask_ptr / mask_items, the sorted de-duplicated lists of items masked to f32::MIN (NULL: none).  ranks [sptr[num_su]] in target
  * order.  Scratch: ts, pos [targets]; th, buckets [num_su][tmax]; tmin, tmin2, totals [num_su]. */
 uint32_t rank_targets_tmax(int d);
-void launch_rank_targets(const ModelView& m, const float* reps, const int* rep_row, const uint32_t* su_user, const uint32_t* sptr,
-                         uint32_t num_su, const uint32_t* tgt_items, const uint64_t* mask_ptr, const uint32_t* mask_items, float* ts,
-                         uint32_t* pos, float* th, float* tmin, float* tmin2, uint32_t* buckets, uint32_t* totals, uint32_t* ranks,
-                         uint32_t* nonfinite_flag, hipStream_t s);
+int launch_rank_targets(const ModelView& m, const float* reps, const int* rep_row, const uint32_t* su_user, const uint32_t* sptr,
+                        uint32_t num_su, const uint32_t* tgt_items, const uint64_t* mask_ptr, const uint32_t* mask_items, float* ts,
+                        uint32_t* pos, float* th, float* tmin, float* tmin2, uint32_t* buckets, uint32_t* totals, uint32_t* ranks,
+                        uint32_t* nonfinite_flag, hipStream_t s);
 /* exact top-k of the catalogue per user (sbr_catalogue.hip): topk_gemm_kernel keeps per (user, item range) a sorted list of the
- * k best (score desc, id asc) in `lists` [num_users][groups][k] with its length in `lens` [num_users][groups]; topk_merge_kernel
- * merges a user's lists in LDS into out_items / out_scores [num_users][k] (padding: 0xFFFFFFFF / -inf).  excl_ptr / excl_items:
- * sorted, de-duplicated per-user exclusion lists (NULL: none).  groups * k <= TK_MERGE_MAX.
- * f (NULL: none): the scan's tag filter (topk_gemm_kernel's TagFilter policy) — device arrays tags [num_items], any_of / none_of
- * [num_users], none of them NULL; item i is eligible for user u only if (tags[i] & none_of[u]) == 0 && (any_of[u] == 0 ||
+ * k best (score desc, id asc) in `lists` [n][groups][k] with its length in `lens` [n][groups]; topk_merge_kernel merges a user's
+ * lists in LDS into out_items / out_scores [n][k] (padding: 0xFFFFFFFF / -inf).  excl_ptr / excl_items: sorted, de-duplicated
+ * per-user exclusion lists (excl_ptr NULL: none).  groups * k <= TK_MERGE_MAX.
+ * f (f.tags NULL: none): the scan's tag filter (topk_gemm_kernel's TagFilter policy) — device arrays tags [num_items], any_of /
+ * none_of [n], none of them NULL; item i is eligible for user u only if (tags[i] & none_of[u]) == 0 && (any_of[u] == 0 ||
  * (tags[i] & any_of[u]) != 0). */
 constexpr uint32_t TK_MERGE_MAX = 8192;
 struct TagMasks {
     const uint32_t *tags, *any_of, *none_of;
 };
+/* what every top-k scan launch is given beside its catalogue and its A-operand table: device arrays, over the launch's n scan
+ * rows ("users": users, query items) */
+struct TopkScan {
+    const int* rep_row;         /* [n] scan row u's row of the A-operand table */
+    uint32_t n;
+    const uint64_t* excl_ptr;   /* [n + 1], NULL: no exclusion lists */
+    const uint32_t* excl_items;
+    uint32_t k;
+    uint2* lists;               /* lists / lens: sized by recommend_groups(n, the scanned catalogue's items, k) */
+    uint32_t *lens, *out_items;
+    float* out_scores;          /* NULL: not wanted */
+    uint32_t* nonfinite_flag;
+    TagMasks f;
+};
 uint32_t recommend_groups(uint32_t num_users, uint32_t num_items, uint32_t k, uint32_t* items_per_group);
-void launch_recommend(const ModelView& m, const float* reps, const int* rep_row, uint32_t num_users, const uint64_t* excl_ptr,
-                      const uint32_t* excl_items, uint32_t k, uint2* lists, uint32_t* lens, uint32_t* out_items, float* out_scores,
-                      uint32_t* nonfinite_flag, hipStream_t s, const TagMasks* f = nullptr);
+int launch_recommend(const ModelView& m, const float* reps, const TopkScan& sc, hipStream_t s);
 /* greedy maximal-marginal-relevance selection (sbr_catalogue.hip, diverse_select_kernel; the contract: sbr_recommend_diverse in
  * include/sbr_hip.h): pool_items / pool_scores [num_users][pool] are launch_recommend's outputs at k = pool; out_items / out_scores
  * [num_users][k_out] the picks in pick order with their pool scores, padded as the pool's rows.  1 <= k_out <= pool <=
  * diverse_max_pool(d): a user's pool lives in one workgroup's LDS.  Raises the flag for a non-finite squared norm of a pool row
  * (cosine) or a non-finite similarity the selection uses. */
 uint32_t diverse_max_pool(int d);
-void launch_diverse_select(const ModelView& m, const uint32_t* pool_items, const float* pool_scores, uint32_t num_users, uint32_t pool,
-                           uint32_t k_out, float trade_off, bool cosine, uint32_t* out_items, float* out_scores, uint32_t* nonfinite_flag,
-                           hipStream_t s);
+int launch_diverse_select(const ModelView& m, const uint32_t* pool_items, const float* pool_scores, uint32_t num_users, uint32_t pool,
+                          uint32_t k_out, float trade_off, bool cosine, uint32_t* out_items, float* out_scores, uint32_t* nonfinite_flag,
+                          hipStream_t s);
 /* exact top-k neighbours of catalogue items (sbr_catalogue.hip): item_rnorm_kernel writes rnorm [num_items] (1 / |E[i]|, 0 for a zero
  * row; all 1.0f unless `cosine`) and raises the flag for a non-finite squared norm, similar_query_kernel writes the scan rows
- * H [num_queries][d] = E[query[j]] * rnorm[query[j]], and launch_recommend's two kernels rank s(j, i) = chain_dot(H[j], E[i]) *
- * rnorm[i] (no bias) with rep_row, the exclusion lists, the tag filter f (masks per query), lists / lens and the outputs as there (the
- * same recommend_groups split). */
-void launch_similar_items(const ModelView& m, const uint32_t* query, uint32_t num_queries, bool cosine, float* rnorm, float* H,
-                          const int* rep_row, const uint64_t* excl_ptr, const uint32_t* excl_items, uint32_t k, uint2* lists,
-                          uint32_t* lens, uint32_t* out_items, float* out_scores, uint32_t* nonfinite_flag, hipStream_t s,
-                          const TagMasks* f = nullptr);
+ * H [sc.n][d] = E[query[j]] * rnorm[query[j]], and launch_recommend's two kernels rank s(j, i) = chain_dot(H[j], E[i]) *
+ * rnorm[i] (no bias) with sc as there: rep_row, the exclusion lists, the tag filter (masks per query), lists / lens and the outputs
+ * (the same recommend_groups split). */
+int launch_similar_items(const ModelView& m, const uint32_t* query, bool cosine, float* rnorm, float* H, const TopkScan& sc, hipStream_t s);
 /* launch_recommend restricted to the item set subset[0 .. num_subset), sorted and unique (sbr_catalogue.hip): subset_gather_kernel
  * copies the set's rows and biases into Esub [num_subset][d] / bsub [num_subset], launch_recommend's two kernels scan that sub-table
- * — lists / lens sized by recommend_groups(num_users, num_subset, k), excl_items POSITIONS in the subset — and subset_ids_kernel turns
- * out_items' positions into catalogue ids.  Only pairs (user, item of the subset) are scored. */
-void launch_recommend_among(const ModelView& m, const uint32_t* subset, uint32_t num_subset, float* Esub, float* bsub, const float* reps,
-                            const int* rep_row, uint32_t num_users, const uint64_t* excl_ptr, const uint32_t* excl_items, uint32_t k,
-                            uint2* lists, uint32_t* lens, uint32_t* out_items, float* out_scores, uint32_t* nonfinite_flag, hipStream_t s);
-/* audience, the reverse scan (sbr_catalogue.hip): for each of num_queries query items q = query[j] the k best rows of the candidate
+ * — sc.lists / lens sized by recommend_groups(sc.n, num_subset, sc.k), sc.excl_items POSITIONS in the subset, no tag filter — and
+ * subset_ids_kernel turns out_items' positions into catalogue ids.  Only pairs (user, item of the subset) are scored. */
+int launch_recommend_among(const ModelView& m, const uint32_t* subset, uint32_t num_subset, float* Esub, float* bsub, const float* reps,
+                           const TopkScan& sc, hipStream_t s);
+/* audience, the reverse scan (sbr_catalogue.hip): for each of the sc.n query items q = sc.rep_row[j] the k best rows of the candidate
  * table T [num_rows][d] by s(q, r) = b[q] + chain_dot(E[q], T[r]) — predict's bits for (state T[r], item q) — score descending, ties
- * to the lower row, padded as launch_recommend's rows.  topk_gemm_kernel with the QueryBias policy: reps = E, rep_row = query, the
- * scanned ModelView's E = T and its b = bT [num_rows] (fetched, never used: any finite memory; launch_audience_gather zeroes it).
- * excl_ptr / excl_rows: per QUERY a non-decreasing list of row positions (NULL: none); lists / lens sized by
- * recommend_groups(num_queries, num_rows, k).  row_ids non-null (ascending): out_rows' positions become row_ids[position].
+ * to the lower row, padded as launch_recommend's rows.  topk_gemm_kernel with the QueryBias policy: reps = E, rep_row = the query
+ * items' ids, the scanned ModelView's E = T and its b = bT [num_rows] (fetched, never used: any finite memory;
+ * launch_audience_gather zeroes it).  sc.excl_ptr / excl_items: per QUERY a non-decreasing list of row positions (NULL: none);
+ * sc.lists / lens sized by recommend_groups(sc.n, num_rows, sc.k); no tag filter.  row_ids non-null (ascending): the positions in
+ * sc.out_items become row_ids[position].
  * launch_audience_gather: T[j] = rows_table[rows[j]] (rows of d floats), bT = 0. */
 void launch_audience_gather(const ModelView& m, const float* rows_table, const uint32_t* rows, uint32_t num_rows, float* T, float* bT,
                             hipStream_t s);
-void launch_audience(const ModelView& m, const float* T, const float* bT, uint32_t num_rows, const uint32_t* row_ids, const uint32_t* query,
-                     uint32_t num_queries, const uint64_t* excl_ptr, const uint32_t* excl_rows, uint32_t k, uint2* lists, uint32_t* lens,
-                     uint32_t* out_rows, float* out_scores, uint32_t* nonfinite_flag, hipStream_t s);
+int launch_audience(const ModelView& m, const float* T, const float* bT, uint32_t num_rows, const uint32_t* row_ids, const TopkScan& sc,
+                    hipStream_t s);
 /* out[p] = b[i] + chain_dot(reps[pair_row[p]], E[i]), i = pair_item[p], for the num_pairs pairs of a launch, with the bits of
  * launch_predict; raises the flag for a non-finite score.  A launch takes at most candidate_pairs_cap pairs: the host cuts a call's
  * flat candidate list there (12 bytes of device buffers per pair), wherever in a user's list that falls. */
 constexpr size_t candidate_pairs_cap = (size_t)1 << 22;
-void launch_candidate_scores(const ModelView& m, const float* reps, const uint32_t* pair_row, const uint32_t* pair_item, uint64_t num_pairs,
-                             float* out, uint32_t* nonfinite_flag, hipStream_t s);
+int launch_candidate_scores(const ModelView& m, const float* reps, const uint32_t* pair_row, const uint32_t* pair_item, uint64_t num_pairs,
+                            float* out, uint32_t* nonfinite_flag, hipStream_t s);
 /* out [num_users][dl] = the first dl columns of rows rep_row[i] of H [.][d] (user_representations) */
-void launch_rep_rows(const float* H, const int* rep_row, uint32_t num_users, int d, int dl, float* out, hipStream_t s);
+int launch_rep_rows(const float* H, const int* rep_row, uint32_t num_users, int d, int dl, float* out, hipStream_t s);
 /* session store (sbr_sessions.hip): H [capacity + 1][d] (LSTM h / EWMA s), C likewise (LSTM; null for EWMA), len [capacity + 1];
  * row `capacity` is the empty-history row (one step of item 0 from zero), len[capacity] stays 0 */
 struct SessionView {
@@ -382,9 +392,10 @@ void launch_session_seen_append(const SeenView& sn, const uint32_t* slot, const 
 void launch_session_seen_clear(const SeenView& sn, const uint32_t* slot, int n, hipStream_t s);
 /* The exclusion CSR a scan of n users reads: segment i = [eptr[i], eptr[i + 1]) of out, eptr[i] = i * w + (entries of the
  * caller's lists before user i) — the ascending merge of slot[i]'s remembered ids (repeats kept) and the caller's sorted,
- * de-duplicated ids caller[eptr[i] - i * w .. eptr[i + 1] - (i + 1) * w), then 0xFFFFFFFF to the segment's end.  One launch. */
-void launch_session_seen_lists(const SeenView& sn, const uint32_t* slot, int n, const uint64_t* eptr, const uint32_t* caller, uint32_t* out,
-                               hipStream_t s);
+ * de-duplicated ids caller[eptr[i] - i * w .. eptr[i + 1] - (i + 1) * w), then 0xFFFFFFFF to the segment's end.  One launch (the
+ * return value, as the scan launchers'; 0 without sessions or memory). */
+int launch_session_seen_lists(const SeenView& sn, const uint32_t* slot, int n, const uint64_t* eptr, const uint32_t* caller, uint32_t* out,
+                              hipStream_t s);
 /* out_n[i] = slot[i]'s remembered items, out_items[i * w ..] = those, oldest first; and the reverse: slot[i]'s memory = the last
  * w of ids[ptr[i] - ptr[0] .. ptr[i + 1] - ptr[0]) */
 void launch_session_seen_get(const SeenView& sn, const uint32_t* slot, int n, uint32_t* out_n, uint32_t* out_items, hipStream_t s);

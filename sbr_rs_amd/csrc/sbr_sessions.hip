@@ -592,9 +592,9 @@ void launch_session_seen_clear(const SeenView& sn, const uint32_t* slot, int n, 
     if (n > 0 && sn.w) hipLaunchKernelGGL(session_seen_clear_kernel, dim3(blocks_for((size_t)n)), dim3(256), 0, s, slot, n, sn.cnt);
 }
 
-void launch_session_seen_lists(const SeenView& sn, const uint32_t* slot, int n, const uint64_t* eptr, const uint32_t* caller, uint32_t* out,
-                               hipStream_t s) {
-    if (n <= 0 || !sn.w) return;
+int launch_session_seen_lists(const SeenView& sn, const uint32_t* slot, int n, const uint64_t* eptr, const uint32_t* caller, uint32_t* out,
+                              hipStream_t s) {
+    if (n <= 0 || !sn.w) return 0;
     uint32_t p = 1;
     while (p < sn.w) p <<= 1;
     if (p <= 64)
@@ -602,6 +602,7 @@ void launch_session_seen_lists(const SeenView& sn, const uint32_t* slot, int n, 
                            caller, out);
     else
         hipLaunchKernelGGL((session_seen_lists_kernel<256>), dim3((unsigned)n), dim3(256), 0, s, slot, n, sn.w, p, sn.ring, sn.cnt, eptr, caller, out);
+    return 1;
 }
 
 void launch_session_seen_get(const SeenView& sn, const uint32_t* slot, int n, uint32_t* out_n, uint32_t* out_items, hipStream_t s) {

@@ -593,3 +593,60 @@ def test_mrr_no_ranked_user():
         mg, rg = g.mrr_score(ptr, it)
         mo, ro = o.mrr_score(ptr, it)
         assert rg.size == ro.size == 0 and np.isnan(mg) and np.isnan(mo)
+
+
+def test_rank_family_launch_counts():
+    """The launches each catalogue call reports in the RANK family of the timing ledger (timing_read()["RANK"][1]; the read
+    resets it): every tools/time_*.py "kernel time" is the event bracket these counts label.  One call each, all single-chunk:
+    EWMA, d = 16, 300 items, 40 users with histories of 3..6 items, k = 5, pool = 8, an item subset of 50, 8 query items, item
+    tags set, a session store of capacity 40 without memory and one with remember = 4.  The scan's own kernels count (top-k:
+    the GEMM and the merge, plus the sub-table gather and the id translation of recommend_among, the norms and the query rows of
+    similar_items, the selection of recommend_diverse, the seen-list build of a store with memory, the id translation of the
+    store's audience); mrr_score reports its scan as one."""
+    users, items, d, T, k, pool = 40, 300, 16, 8, 5, 8
+    rs = np.random.RandomState(7)
+    E, bias = _heavy_tie_params(items, d, 3)
+    hp = hparams(items, T, d, int(ModelKind.EWMA), LOSS_HINGE, B=8)
+    m = Model(hp)
+    m.set_param(Param.ITEM_EMBEDDING, E)
+    m.set_param(Param.ITEM_BIAS, bias)
+    m.set_item_tags(rs.randint(1, 8, items).astype(np.uint32))
+    hists = [rs.randint(0, items, rs.randint(3, 7)).astype(np.uint32) for _ in range(users)]
+    ptr, it = _csr(hists)
+    reps = m.user_representations(ptr, it)
+    among = rs.choice(items, 50, replace=False).astype(np.uint32)
+    queries = rs.randint(0, items, 8).astype(np.uint32)
+    one_ptr = np.arange(users + 1, dtype=np.uint64)  # one candidate / one target per user
+    one_item = rs.randint(0, items, users).astype(np.uint32)
+    slots = np.arange(users, dtype=np.uint32)
+    plain, memory = m.sessions(users), m.sessions(users, remember=4)
+    plain.append(slots, hists)
+    memory.append(slots, hists)
+    calls = [
+        ("mrr_score", 1, lambda: m.mrr_score(ptr, it)),
+        ("recommend", 2, lambda: m.recommend(ptr, it, k)),
+        ("recommend with masks", 2, lambda: m.recommend(ptr, it, k, any_of=3, none_of=4)),
+        ("recommend_reps", 2, lambda: m.recommend_reps(reps, k)),
+        ("recommend_diverse", 3, lambda: m.recommend_diverse(ptr, it, k, pool)),
+        ("recommend_among", 4, lambda: m.recommend_among(ptr, it, k, among)),
+        ("similar_items", 4, lambda: m.similar_items(queries, k)),
+        ("similar_items with masks", 4, lambda: m.similar_items(queries, k, any_of=3, none_of=4)),
+        ("score_candidates", 1, lambda: m.score_candidates(ptr, it, one_ptr, one_item)),
+        ("user_representations", 1, lambda: m.user_representations(ptr, it)),
+        ("rank_targets", 3, lambda: m.rank_targets(ptr, it, one_ptr, one_item)),
+        ("audience_reps", 2, lambda: m.audience_reps(reps, queries, k)),
+        ("Sessions.recommend, no memory", 2, lambda: plain.recommend(slots, k)),
+        ("Sessions.recommend, memory", 3, lambda: memory.recommend(slots, k)),
+        ("Sessions.recommend, memory, include_seen", 2, lambda: memory.recommend(slots, k, include_seen=True)),
+        ("Sessions.recommend_diverse, memory", 4, lambda: memory.recommend_diverse(slots, k, pool)),
+        ("Sessions.audience", 3, lambda: plain.audience(queries, k)),
+    ]
+    m.timing_enable(True)
+    m.timing_read()
+    got = {}
+    for what, _, call in calls:
+        call()
+        got[what] = int(m.timing_read()["RANK"][1])
+    m.timing_enable(False)
+    print(got)
+    assert got == {what: n for what, n, _ in calls}
