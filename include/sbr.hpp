@@ -535,7 +535,8 @@ inline std::vector<std::uint32_t> narrow(const std::vector<ItemId>& ids) {
 /// `score_candidates`.  A slot's representation has the bits of `user_representation` of the items appended since its last reset
 /// (an empty slot: of the empty history) while they are at most max_sequence_length; beyond that a session keeps the recurrence
 /// over everything appended where the windowed call truncates.  After the model's parameters change (`fit`, a restored
-/// checkpoint) every call but `reset_all` throws EngineError(SBR_ERR_INVALID_ARGUMENT) until `reset_all` re-binds the store.
+/// checkpoint) every call but `reset_all` — and, with a seen-item memory, `replay()` of the whole store, which recomputes every
+/// state from the remembered items — throws EngineError(SBR_ERR_INVALID_ARGUMENT) until one of the two re-binds the store.
 /// With a seen-item memory (`seen_capacity` > 0) a slot also remembers, on the device, the last seen_capacity items appended
 /// to it since its last reset, in append order with repeats; `reset`, `reset_all` and `set_state` empty it, `set_seen` restores it.
 /// The recommend calls of such a store exclude each slot's remembered items, united with the caller's lists, as
@@ -616,6 +617,22 @@ class Sessions {
     void reset(const std::vector<std::uint32_t>& slots) { check(sbr_sessions_reset(h_, slots.data(), (std::uint64_t)slots.size()), "sbr_sessions_reset"); }
     /// Every slot emptied and the store re-bound to the model's current parameters.
     void reset_all() { check(sbr_sessions_reset_all(h_), "sbr_sessions_reset_all"); }
+    /// Every slot's state recomputed on the device from its remembered items under the model's current parameters, and the store
+    /// re-bound to them (sbr_sessions_replay): the second call, beside reset_all, that a stale store accepts.  A slot with an empty
+    /// memory becomes empty; one whose memory has wrapped keeps the recurrence over its last seen_capacity() items.  Returns the
+    /// number of slots that had a non-empty memory.  A store without seen-item memory refuses the call.
+    std::size_t replay() {
+        std::uint64_t n = 0;
+        check(sbr_sessions_replay(h_, nullptr, 0, &n), "sbr_sessions_replay");
+        return (std::size_t)n;
+    }
+    /// The same for the named slots of a current store (a slot named twice counts once); every other slot keeps its bits.
+    std::size_t replay(const std::vector<std::uint32_t>& slots) {
+        std::uint64_t n = 0;
+        const std::uint32_t none = 0;
+        check(sbr_sessions_replay(h_, slots.empty() ? &none : slots.data(), (std::uint64_t)slots.size(), &n), "sbr_sessions_replay");
+        return (std::size_t)n;
+    }
     /// The k best items of the whole catalogue for each slot's state, read in place (sbr_sessions_recommend): ordered and padded as
     /// ImplicitSequenceModel::recommend's rows.  Slot i's excluded items are excl_items[excl_ptr[i] .. excl_ptr[i + 1]) (both
     /// empty: none), united with the slot's remembered items on a store with seen-item memory unless `include_seen` (which a

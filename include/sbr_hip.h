@@ -593,8 +593,9 @@ sbr_status sbr_rank_targets_reps(sbr_model* m, const float* reps, uint64_t num_u
  *
  * STALENESS: the model has a parameter generation, bumped by whatever can write parameters — a fit plan opening by any route
  * (sbr_fit_begin, sbr_group_fit_begin, sbr_model_fit, sbr_model_fit_comm, sbr_group_fit) or closing, and sbr_model_set_param.  A store
- * remembers the generation of its creation or last sbr_sessions_reset_all; while the model's differs, every store call except
- * reset_all, capacity and destroy returns SBR_ERR_INVALID_ARGUMENT: no call mixes states of two parameter sets.  While a fit plan
+ * remembers the generation of its creation, last sbr_sessions_reset_all or last whole-store sbr_sessions_replay (REPLAY below);
+ * while the model's differs, every store call except those two, capacity and destroy returns SBR_ERR_INVALID_ARGUMENT: no call
+ * mixes states of two parameter sets.  While a fit plan
  * is open on the model (from sbr_fit_begin to sbr_fit_plan_destroy; sbr_model_fit and the group fits open and destroy theirs
  * inside the call) its steps rewrite parameters, so every store call but capacity and destroy — sbr_sessions_reset_all included —
  * returns SBR_ERR_INVALID_ARGUMENT until the plan is destroyed.
@@ -635,7 +636,27 @@ sbr_status sbr_rank_targets_reps(sbr_model* m, const float* reps, uint64_t num_u
  *   sbr_sessions_set_seen        slot slots[i]'s memory = the last seen_capacity of items[ptr[i] .. ptr[i + 1]) (ids validated as
  *                                every CSR argument's); get_state + get_seen, then set_state + set_seen in that order, restore a
  *                                slot exactly
- * get_seen / set_seen on a store without memory: SBR_ERR_INVALID_ARGUMENT. */
+ * get_seen / set_seen on a store without memory: SBR_ERR_INVALID_ARGUMENT.
+ *
+ * REPLAY: sbr_sessions_replay recomputes slots' states from their seen-item memories under the model's CURRENT parameters, on the
+ * device: a store survives a parameter change (a retrain, sbr_model_set_param, a load) with what it still knows of its sessions.
+ * Let items_s be slot s's remembered items, oldest first — what sbr_sessions_get_seen returns, the min(cnt, seen_capacity) valid ring
+ * entries.
+ *   slots == NULL   every slot of the store (n ignored).  Allowed on a STALE store — besides sbr_sessions_reset_all it is the one
+ *                   call such a store accepts — and afterwards the store is bound to the model's current parameters, its
+ *                   empty-history row rebuilt as sbr_sessions_reset_all builds it.
+ *   slots != NULL   the n named slots only, each < capacity; a slot named more than once counts once.  The store must be current,
+ *                   as for every other call; every slot not named keeps every bit of its state, its length and its memory.
+ * Every replayed slot then holds, bit for bit, the state a freshly reset slot holds after sbr_sessions_append of items_s: h (c),
+ * and len = |items_s|.  A slot whose memory is empty becomes an empty slot (len 0, reading the empty-history row) even if
+ * sbr_sessions_set_state had given it a state.  A slot whose memory has WRAPPED (more than seen_capacity items remembered since
+ * its reset) gets the recurrence over its last seen_capacity items only and len = seen_capacity: what the store still knows,
+ * not what it was told.  The memory itself — ring and count — is not written: sbr_sessions_get_seen returns the same lists before
+ * and after.  *out_replayed (optional) = the number of slots, of those the call covers, that had a non-empty memory.
+ * SBR_ERR_INVALID_ARGUMENT, with the store left as it was: a store without seen-item memory (there is nothing to replay from), a fit
+ * plan open on the model, a slot >= capacity, slots != NULL on a stale store.  The rings never visit the host: it reads the slots'
+ * counts (8 bytes per slot) to order them, the items are fed to the step kernels of sbr_sessions_append from the rings in chunks of
+ * sessions sized to the model's scratch arena. */
 #define SBR_SESSIONS_MAX_SEEN 1024u
 typedef struct sbr_sessions sbr_sessions;
 sbr_status sbr_sessions_create(sbr_model* m, uint64_t capacity, sbr_sessions** out);
@@ -643,6 +664,7 @@ sbr_status sbr_sessions_create_seen(sbr_model* m, uint64_t capacity, uint32_t se
 sbr_status sbr_sessions_seen_capacity(const sbr_sessions* st, uint32_t* out);
 sbr_status sbr_sessions_get_seen(sbr_sessions* st, const uint32_t* slots, uint64_t n, uint64_t* out_ptr, uint32_t* out_items);
 sbr_status sbr_sessions_set_seen(sbr_sessions* st, const uint32_t* slots, uint64_t n, const uint64_t* ptr, const uint32_t* items);
+sbr_status sbr_sessions_replay(sbr_sessions* st, const uint32_t* slots, uint64_t n, uint64_t* out_replayed);
 void sbr_sessions_destroy(sbr_sessions* st);
 sbr_status sbr_sessions_capacity(const sbr_sessions* st, uint64_t* out);
 sbr_status sbr_sessions_reset(sbr_sessions* st, const uint32_t* slots, uint64_t n);

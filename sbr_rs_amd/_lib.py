@@ -166,6 +166,7 @@ def load():
         "sbr_audience_reps": [vp, vp, C.c_uint64, vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp],
         "sbr_audience": [vp, vp, vp, C.c_uint64, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp],
         "sbr_sessions_audience": [vp, vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, vp, vp, C.c_uint32, vp, vp],
+        "sbr_sessions_replay": [vp, vp, C.c_uint64, u64p],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -223,4 +224,5 @@ DECLARED_SYMBOLS = [
     "sbr_sessions_recommend_filtered", "sbr_sessions_recommend_diverse_filtered",
     "sbr_sessions_create_seen", "sbr_sessions_seen_capacity", "sbr_sessions_get_seen", "sbr_sessions_set_seen",
     "sbr_audience_reps", "sbr_audience", "sbr_sessions_audience",
+    "sbr_sessions_replay",
 ]

@@ -18,7 +18,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libsbr_hip.so")
 SOURCES = ["sbr_kernels.hip", "sbr_steps.hip", "sbr_sort.hip", "sbr_wave.hip", "sbr_report.hip", "sbr_catalogue.hip", "sbr_sessions.hip", "sbr_engine.hip"]
-HEADERS = ["sbr_kernels.h", "sbr_device.h", "sbr_wave_seq.h", "sbr_numerics.h", "sbr_approx.h", "sbr_ziggurat_tables.h", os.path.join("..", "..", "include", "sbr_hip.h")]
+HEADERS = ["sbr_kernels.h", "sbr_device.h", "sbr_wave_seq.h", "sbr_numerics.h", "sbr_approx.h", "sbr_ziggurat_tables.h", "sbr_replay_plan.h", os.path.join("..", "..", "include", "sbr_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
          "-Wall", "-Wno-unused-function", "-Wno-unused-result", "-Wno-unused-value"] + os.environ.get("SBR_EXTRA_FLAGS", "").split()
 
@@ -135,6 +135,15 @@ def build_sessions_seen_tests(force: bool = False, verbose: bool = True) -> str:
     return _build_cpp_program(SESSIONS_SEEN_SRC, SESSIONS_SEEN_BIN, force, verbose)
 
 
+SESSIONS_REPLAY_SRC = os.path.join(REPO, "tests", "cpp", "sessions_replay_tests.cpp")
+SESSIONS_REPLAY_BIN = os.path.join(REPO, "tests", "cpp", "_build", "sessions_replay_tests")
+
+
+def build_sessions_replay_tests(force: bool = False, verbose: bool = True) -> str:
+    """g++ build of the C++ host layer's test program of the session store's replay."""
+    return _build_cpp_program(SESSIONS_REPLAY_SRC, SESSIONS_REPLAY_BIN, force, verbose)
+
+
 RANKING_SRC = os.path.join(REPO, "tests", "cpp", "ranking_tests.cpp")
 RANKING_BIN = os.path.join(REPO, "tests", "cpp", "_build", "ranking_tests")
 
@@ -172,5 +181,6 @@ if __name__ == "__main__":
     print(build_candidates_tests(force="--force" in sys.argv))
     print(build_sessions_tests(force="--force" in sys.argv))
     print(build_sessions_seen_tests(force="--force" in sys.argv))
+    print(build_sessions_replay_tests(force="--force" in sys.argv))
     print(build_filtered_tests(force="--force" in sys.argv))
     print(build_audience_tests(force="--force" in sys.argv))

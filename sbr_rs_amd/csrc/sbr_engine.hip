@@ -30,6 +30,7 @@
 #include "../../include/sbr_hip.h"
 #include "sbr_kernels.h"
 #include "sbr_numerics.h"
+#include "sbr_replay_plan.h"
 
 namespace {
 
@@ -4660,6 +4661,60 @@ sbr_status sessions_gather(sbr_sessions* st, const uint32_t* rows, uint64_t n, f
     return SBR_OK;
 }
 
+/* Sessions per replay chunk.  A chunk's scratch in the eval arena is its slot and count words, its item feed (at most w words per
+ * session) and, for the LSTM, the two parities of scratch h and c rows the steps write: the chunk is as large as keeps that within
+ * 256 MB — the bound the top-k scans keep their per-user lists to (recommend_users_cap) — and its feed addressable with an int.
+ * SBR_SESSIONS_REPLAY_CHUNK=n (n >= 1) is a TEST HOOK read per call that replaces the first bound; the second still applies. */
+size_t replay_chunk_cap(const sbr_model* m, uint32_t w) {
+    constexpr size_t budget = (size_t)256 << 20;
+    const size_t per = 8 + (size_t)w * 4 + (m->ng ? (size_t)m->d * 16 : 8);
+    size_t cap = std::max<size_t>(budget / per, 1);
+    if (const char* e = std::getenv("SBR_SESSIONS_REPLAY_CHUNK")) {
+        const long long v = std::atoll(e);
+        if (v >= 1) cap = (size_t)v;
+    }
+    return std::min<size_t>(cap, (size_t)0x7FFFFFFF / w);
+}
+
+/* One replay chunk (sbr_replay_plan.h): the feed written from the rings, then an append call's launches over it — the step
+ * kernels' arithmetic is the contract — with no ring write.  The chunk's rows of H, C, len are zero when this runs. */
+sbr_status sessions_replay_chunk(sbr_sessions* st, const sbr::ReplayPlan& plan, const sbr::ReplayChunk& ch) {
+    sbr_model* m = st->m;
+    const size_t ns = ch.n, d = (size_t)m->d;
+    const bool lstm = m->ng != 0;
+    sbr::SessionAppend a{};
+    uint32_t *d_slot = nullptr, *d_count = nullptr, *d_items = nullptr;
+    unsigned long long* d_start = nullptr;
+    int* d_off = nullptr;
+    SBRCHK(carve_arena(m, [&](DeviceArena& ar) {
+        d_slot = ar.take<uint32_t>(ns);
+        d_count = ar.take<uint32_t>(ns);
+        d_items = ar.take<uint32_t>(ch.total);
+        if (lstm) { a.Hs = ar.take<float>(2 * ns * d); a.Cs = ar.take<float>(2 * ns * d); d_off = ar.take<int>(ch.off.size()); }
+        else d_start = ar.take<unsigned long long>(ns);
+    }));
+    HIPCHK(hipMemcpyAsync(d_slot, plan.slot.data() + ch.first, ns * 4, hipMemcpyHostToDevice, m->stream));
+    HIPCHK(hipMemcpyAsync(d_count, plan.count.data() + ch.first, ns * 4, hipMemcpyHostToDevice, m->stream));
+    if (lstm) HIPCHK(hipMemcpyAsync(d_off, ch.off.data(), ch.off.size() * 4, hipMemcpyHostToDevice, m->stream));
+    else HIPCHK(hipMemcpyAsync(d_start, ch.start.data(), ns * 8, hipMemcpyHostToDevice, m->stream));
+    a.n = (int)ns; a.tm = ch.tm;
+    a.slot = d_slot; a.count = d_count; a.items = d_items; a.start = d_start;
+    a.off_host = ch.off.data();
+    a.advance = 1;
+    { /* the feed is bracketed as the ordering family, which no other prediction-side call uses: timing_read splits a replay into feed and steps */
+        ScopedTimer t(m, SBR_K_SPARSE_SORT, 1);
+        sbr::launch_session_replay_feed(st->seen, d_slot, d_count, (int)ns, ch.tm, d_off, d_start, d_items, m->stream);
+    }
+    {
+        ScopedTimer t(m, SBR_K_RECURRENT_FWD, lstm ? (uint64_t)ch.tm + 1 : 1);
+        if (sbr::launch_session_append(m->mv, st->v, a, m->stream) < 0) return SBR_ERR_UNSUPPORTED;
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(m->stream)); /* the plan's vectors are read by the asynchronous copies above */
+    for (size_t b = 0; b < ns; ++b) st->host_len[plan.slot[ch.first + b]] = plan.count[ch.first + b];
+    return SBR_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -4863,6 +4918,64 @@ sbr_status sbr_sessions_set_seen(sbr_sessions* st, const uint32_t* slots, uint64
     sbr::launch_session_seen_set(st->seen, d_slot, (int)n, d_ptr, d_ids, m->stream);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(m->stream));
+    return SBR_OK;
+}
+
+/* States recomputed from the seen-item memories under the model's current parameters (REPLAY, include/sbr_hip.h).  Of the memory
+ * the host reads cnt alone; the rings feed the step kernels on the device. */
+sbr_status sbr_sessions_replay(sbr_sessions* st, const uint32_t* slots, uint64_t n, uint64_t* out_replayed) {
+    if (!st || !st->seen.w) return SBR_ERR_INVALID_ARGUMENT;
+    sbr_model* m = st->m;
+    std::lock_guard<std::mutex> lock(m->mu);
+    SBRCHK(enter_reader(m));
+    if (m->open_plans) return SBR_ERR_INVALID_ARGUMENT; /* states bound now would go stale with the plan's next step */
+    const bool whole = slots == nullptr;
+    std::vector<uint32_t> named; /* the subset form's slots, each once */
+    if (!whole) {
+        if (st->gen != m->param_gen) return SBR_ERR_INVALID_ARGUMENT; /* the slots not named would keep states of other parameters */
+        for (uint64_t i = 0; i < n; ++i)
+            if (slots[i] >= st->capacity) return SBR_ERR_INVALID_ARGUMENT;
+        named.assign(slots, slots + n);
+        std::sort(named.begin(), named.end());
+        named.erase(std::unique(named.begin(), named.end()), named.end());
+    }
+    const size_t ns = whole ? (size_t)st->capacity : named.size();
+    if (out_replayed) *out_replayed = 0;
+    if (ns == 0) return SBR_OK;
+    std::vector<unsigned long long> cnt(ns);
+    uint32_t* d_slot = nullptr;
+    HIPCHK(hipStreamSynchronize(m->stream));
+    if (whole) {
+        HIPCHK(hipMemcpy(cnt.data(), st->seen.cnt, ns * 8, hipMemcpyDeviceToHost));
+    } else {
+        unsigned long long* d_cnt = nullptr;
+        SBRCHK(carve_arena(m, [&](DeviceArena& ar) { d_slot = ar.take<uint32_t>(ns); d_cnt = ar.take<unsigned long long>(ns); }));
+        HIPCHK(hipMemcpyAsync(d_slot, named.data(), ns * 4, hipMemcpyHostToDevice, m->stream));
+        sbr::launch_session_seen_counts(st->seen, d_slot, (int)ns, d_cnt, m->stream);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(m->stream));
+        HIPCHK(hipMemcpy(cnt.data(), d_cnt, ns * 8, hipMemcpyDeviceToHost));
+    }
+    sbr::ReplayPlan plan;
+    sbr::plan_replay(whole ? nullptr : named.data(), cnt.data(), ns, st->seen.w, replay_chunk_cap(m, st->seen.w), &plan);
+    if (whole) { /* sessions_rebind without its cnt = 0: every state and length zero, the empty-history row of the current parameters */
+        const size_t rows = (size_t)st->capacity + 1, d = (size_t)m->d;
+        HIPCHK(hipMemsetAsync(st->v.H, 0, rows * d * 4, m->stream));
+        if (st->v.C) HIPCHK(hipMemsetAsync(st->v.C, 0, rows * d * 4, m->stream));
+        HIPCHK(hipMemsetAsync(st->v.len, 0, rows * 8, m->stream));
+        std::fill(st->host_len.begin(), st->host_len.end(), 0);
+        const uint32_t row = (uint32_t)st->capacity, item0 = 0;
+        const uint64_t ptr[2] = {0, 1};
+        SBRCHK(sessions_append(st, &row, 1, ptr, &item0, 0));
+    } else { /* d_slot is still the arena's: nothing has carved it since */
+        sbr::launch_session_reset(st->v, d_slot, (int)ns, m->d, m->stream);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(m->stream));
+        for (uint32_t s : named) st->host_len[s] = 0;
+    }
+    for (const sbr::ReplayChunk& ch : plan.chunks) SBRCHK(sessions_replay_chunk(st, plan, ch));
+    if (whole) st->gen = m->param_gen;
+    if (out_replayed) *out_replayed = plan.slot.size();
     return SBR_OK;
 }
 

@@ -400,6 +400,15 @@ int launch_session_seen_lists(const SeenView& sn, const uint32_t* slot, int n, c
  * w of ids[ptr[i] - ptr[0] .. ptr[i + 1] - ptr[0]) */
 void launch_session_seen_get(const SeenView& sn, const uint32_t* slot, int n, uint32_t* out_n, uint32_t* out_items, hipStream_t s);
 void launch_session_seen_set(const SeenView& sn, const uint32_t* slot, int n, const uint64_t* ptr, const uint32_t* ids, hipStream_t s);
+/* out[i] = cnt[slot[i]] */
+void launch_session_seen_counts(const SeenView& sn, const uint32_t* slot, int n, unsigned long long* out, hipStream_t s);
+/* The item feed of a replay chunk (sbr_sessions_replay; the plan: sbr_replay_plan.h), written from the rings without a visit to the
+ * host: session b = slot slot[b] with count[b] = min(cnt, w) >= 1 items, counts descending, tm = count[0].  off != null (LSTM): the
+ * time-major SessionAppend::items, the item of (step t, session b) at items[off[t] + b], off [tm + 1] on the device; off == null
+ * (EWMA): session-major, session b's at items[start[b] .. start[b] + count[b]).  The ring and cnt are read only.  One launch (the
+ * return value; 0 where nothing is to do). */
+int launch_session_replay_feed(const SeenView& sn, const uint32_t* slot, const uint32_t* count, int n, int tm, const int* off,
+                               const unsigned long long* start, uint32_t* items, hipStream_t s);
 /* The inverted seen lists of an audience scan (sbr_sessions.hip): which candidates' memories hold which query item.  The chunk's
  * queries come sorted by item: qs_item [nq] ascending (repeats kept), qs_idx [nq] the query each stands for; candidate position p
  * is slot cand_slot[p].  A key is (query << 32 | position), one per (query, position) whose slot's min(cnt, w) valid ring entries hold

@@ -20,6 +20,9 @@
 //                                a query item, counted in one pass and written in a second; audience_seen_csr_kernel turns the sorted
 //                                keys into the CSR over queries the scan binary-searches
 //   session_seen_clear_kernel / session_seen_get_kernel / session_seen_set_kernel : cnt = 0 / the ring oldest first / restore
+//   session_replay_feed_steps_kernel / session_replay_feed_rows_kernel : a replay chunk's items out of the rings, in the order the
+//                                step kernels above read an append call's (LSTM time-major through an LDS transpose / EWMA session-major)
+//   session_seen_count_kernel  : cnt of named slots, for the host's replay plan
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off (see sbr_rs_amd/build.py).
 
@@ -28,6 +31,7 @@
 #include "../../include/sbr_hip.h"
 #include "sbr_device.h"
 #include "sbr_numerics.h"
+#include "sbr_replay_plan.h"
 
 namespace sbr {
 
@@ -367,6 +371,74 @@ __global__ __launch_bounds__(256) void session_seen_set_kernel(const uint32_t* _
     if (j < keep) ring[(size_t)sl * w + j] = ids[ptr[i + 1] - ptr[0] - keep + j];
 }
 
+// out[i] = cnt[slot[i]]: what a replay of named slots reads of their memories on the host
+__global__ __launch_bounds__(256) void session_seen_count_kernel(const uint32_t* __restrict__ slot, int n, const unsigned long long* __restrict__ cnt,
+                                                                 unsigned long long* __restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < (size_t)n) out[i] = cnt[slot[i]];
+}
+
+// ------------------------------------------------------------------------------------------------
+// Replay: the feed of the step kernels straight from the rings (sbr_sessions_replay).  Session b of a replay chunk is slot slot[b]
+// with count[b] = min(cnt, w) remembered items (the host's plan, sbr_replay_plan.h: count descending); its t-th oldest lies at ring
+// position seen_ring_pos(cnt, w, t).  Neither kernel writes the ring or cnt.
+//
+// session_replay_feed_steps_kernel (LSTM): the time-major array session_lstm_step_kernel reads, items[off[t] + b] for b below
+// off[t + 1] - off[t] = the sessions with more than t items.  A workgroup takes 64 sessions x 64 steps: each wave reads 64
+// consecutive steps of one session — consecutive ring words but for the one place the ring wraps — into a row of an LDS tile, and
+// after the barrier writes one step of 64 consecutive sessions, the tile read down a column (rows padded to 65 words: no bank
+// shared).  Lanes walking a step across 64 rings instead would touch one 64-byte sector per word read, w words apart, as
+// item_rnorm_kernel's rows would without its transpose.  Bounds: b < n, t < count[b] <= w on the read; on the write t < tm and
+// b < off[t + 1] - off[t], so the index is below off[t + 1] <= off[tm] = the array's length.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void session_replay_feed_steps_kernel(const uint32_t* __restrict__ slot, const uint32_t* __restrict__ count, int n,
+                                                                        int tm, const int* __restrict__ off, uint32_t w,
+                                                                        const uint32_t* __restrict__ ring, const unsigned long long* __restrict__ cnt,
+                                                                        uint32_t* __restrict__ items) {
+    __shared__ uint32_t tile[64][65];
+    const int b0 = (int)blockIdx.x * 64, t0 = (int)blockIdx.y * 64;
+    if (count[b0] <= (uint32_t)t0) return; /* counts descend: no session of this tile reaches step t0 (the whole workgroup leaves) */
+    const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
+    for (int r = wave; r < 64; r += 4) {
+        const int b = b0 + r;
+        if (b >= n) break;
+        const uint32_t t = (uint32_t)(t0 + lane);
+        if (t < count[b]) {
+            const uint32_t sl = slot[b];
+            uint32_t p = seen_ring_base(cnt[sl], w) + t;
+            if (p >= w) p -= w;
+            tile[r][lane] = ring[(size_t)sl * w + p];
+        }
+    }
+    __syncthreads();
+    for (int r = wave; r < 64; r += 4) {
+        const int t = t0 + r;
+        if (t >= tm) break;
+        const int o = off[t], bt = off[t + 1] - o;
+        const int b = b0 + lane;
+        if (b < bt) items[o + b] = tile[lane][r]; /* b < bt: count[b] > t, so the tile entry was written above */
+    }
+}
+
+// session_replay_feed_rows_kernel (EWMA): the session-major array session_ewma_step_kernel reads, session b's items at
+// [start[b], start[b] + count[b]).  One wave per session; reads and writes are consecutive words.
+__global__ __launch_bounds__(256) void session_replay_feed_rows_kernel(const uint32_t* __restrict__ slot, const unsigned long long* __restrict__ start,
+                                                                       const uint32_t* __restrict__ count, int n, uint32_t w,
+                                                                       const uint32_t* __restrict__ ring, const unsigned long long* __restrict__ cnt,
+                                                                       uint32_t* __restrict__ items) {
+    const int b = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
+    if (b >= n) return;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t c = count[b], sl = slot[b];
+    const uint32_t base = seen_ring_base(cnt[sl], w);
+    uint32_t* dst = items + start[b];
+    for (uint32_t t = lane; t < c; t += 64u) {
+        uint32_t p = base + t;
+        if (p >= w) p -= w;
+        dst[t] = ring[(size_t)sl * w + p];
+    }
+}
+
 // The exclusion CSR of a scan chunk.  A group of G threads per user (G = 64: four users per workgroup, for p <= 64; G = 256: one)
 // brings the slot's valid ring entries into LDS, padded with 0xFFFFFFFF to p = the power of two >= w, sorts them ascending there
 // (bitonic; every thread of the workgroup walks the same p, so the barriers are uniform) and merges them with the caller's list
@@ -613,6 +685,22 @@ void launch_session_seen_get(const SeenView& sn, const uint32_t* slot, int n, ui
 void launch_session_seen_set(const SeenView& sn, const uint32_t* slot, int n, const uint64_t* ptr, const uint32_t* ids, hipStream_t s) {
     if (n > 0 && sn.w)
         hipLaunchKernelGGL(session_seen_set_kernel, dim3(blocks_for((size_t)n * sn.w)), dim3(256), 0, s, slot, n, sn.w, ptr, ids, sn.ring, sn.cnt);
+}
+
+void launch_session_seen_counts(const SeenView& sn, const uint32_t* slot, int n, unsigned long long* out, hipStream_t s) {
+    if (n > 0 && sn.w) hipLaunchKernelGGL(session_seen_count_kernel, dim3(blocks_for((size_t)n)), dim3(256), 0, s, slot, n, sn.cnt, out);
+}
+
+int launch_session_replay_feed(const SeenView& sn, const uint32_t* slot, const uint32_t* count, int n, int tm, const int* off,
+                               const unsigned long long* start, uint32_t* items, hipStream_t s) {
+    if (n <= 0 || tm <= 0 || !sn.w) return 0;
+    if (off)
+        hipLaunchKernelGGL(session_replay_feed_steps_kernel, dim3((unsigned)((n + 63) / 64), (unsigned)((tm + 63) / 64)), dim3(256), 0, s, slot, count,
+                           n, tm, off, sn.w, sn.ring, sn.cnt, items);
+    else
+        hipLaunchKernelGGL(session_replay_feed_rows_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, slot, start, count, n, sn.w, sn.ring,
+                           sn.cnt, items);
+    return 1;
 }
 
 namespace {

@@ -861,6 +861,12 @@ class Model:
         recommend / recommend_diverse exclude them."""
         return Sessions(self, capacity, remember)
 
+    def load_sessions(self, path, capacity=None, remember=None, replay: bool = False) -> "Sessions":
+        """A store of this model restored from a file written by ``Sessions.save`` (``persistence.load_sessions``)."""
+        from .persistence import load_sessions
+
+        return load_sessions(self, path, capacity=capacity, remember=remember, replay=replay)
+
     def close(self):
         if getattr(self, "_h", None):
             for st in list(getattr(self, "_stores", ())):  # stores are destroyed before their model
@@ -900,9 +906,10 @@ class Sessions:
     advanced by the items appended to it, one cell step per item.  A slot's representation has the bits of
     ``user_representation`` of the items appended since its last reset (an empty slot: of the empty history) as long as they are
     at most max_sequence_length; beyond that a session keeps the recurrence over everything appended where the windowed call
-    truncates.  After the model's parameters change (fit, set_param, load) every call but ``reset()`` of the whole store raises
-    until that reset re-binds it; while a fit plan is open on the model every call raises.  The object keeps its model alive, and
-    ``Model.close`` closes the model's live stores first.
+    truncates.  After the model's parameters change (fit, set_param, load) every call but ``reset()`` of the whole store — which
+    empties it — and, on a store with seen-item memory, ``replay()`` of the whole store — which recomputes every state from the
+    remembered items under the new parameters — raises until one of the two re-binds it; while a fit plan is open on the model
+    every call raises.  The object keeps its model alive, and ``Model.close`` closes the model's live stores first.
 
     With ``remember`` = W > 0 a slot also remembers, on the device, the last W items appended to it since its last reset, in
     append order with repeats (``seen``); ``reset`` and ``set_state`` empty that memory, ``set_seen`` restores it.  ``recommend``
@@ -1068,6 +1075,33 @@ class Sessions:
         else:
             sl = self._slots(slots)
             _check(self._L.sbr_sessions_reset(self._h, _ptr(sl), sl.size))
+
+    def replay(self, slots=None) -> int:
+        """Recomputes states from the remembered items, on the device, under the model's current parameters
+        (sbr_sessions_replay); a store with seen-item memory only.  ``slots=None``: every slot, and the store is re-bound to the
+        current parameters — the call for a store gone stale after a retrain.  Otherwise the named slots of a current store
+        (repeats count once); the others keep their bits.  A replayed slot holds the bits a fresh slot holds after ``append`` of
+        ``seen`` of it, and that many items as its length — at most ``seen_capacity``: a slot that was told more keeps the
+        recurrence over what it still remembers; a slot with an empty memory becomes empty.  The memory itself is unchanged.
+        Returns the number of slots that had a non-empty memory."""
+        n = C.c_uint64()
+        if slots is None:
+            _check(self._L.sbr_sessions_replay(self._h, None, 0, C.byref(n)))
+        else:
+            sl = self._slots(slots)
+            if sl.size == 0:
+                sl = np.zeros(1, dtype=np.uint32)  # no slots, not "every slot": a valid pointer, zero slots
+                _check(self._L.sbr_sessions_replay(self._h, _ptr(sl), 0, C.byref(n)))
+            else:
+                _check(self._L.sbr_sessions_replay(self._h, _ptr(sl), sl.size, C.byref(n)))
+        return n.value
+
+    def save(self, path) -> None:
+        """The store's live slots — states, lengths, memories — into an ``.npz`` (``persistence.save_sessions``); a stale store
+        raises: ``replay()`` first."""
+        from .persistence import save_sessions
+
+        save_sessions(self, path)
 
     def state(self, slots):
         """Checkpoint of the named slots: (h [n, embedding_dim], c likewise — None for EWMA —, len [n] u64)."""

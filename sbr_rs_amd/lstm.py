@@ -333,6 +333,12 @@ class _ImplicitSequenceModel:
         ``recommend_diverse`` of the store exclude them as ``recommend`` excludes the history."""
         return self.params.sessions(capacity, remember)
 
+    def load_sessions(self, path, capacity=None, remember=None, replay: bool = False):
+        """A session store restored from a file written by ``store.save(path)`` (``persistence.load_sessions``).  With
+        ``replay=True`` only the remembered items are restored and every state is recomputed from them on the device under this
+        model's parameters (``engine.Sessions.replay``): the route after a retrain."""
+        return self.params.load_sessions(path, capacity=capacity, remember=remember, replay=replay)
+
     def rank_targets(self, histories, targets, mask_history: bool = True):
         """Exact catalogue ranks of each user's targets from one device scan (``evaluation.rank_targets``): one uint32 array
         per user, in target order."""

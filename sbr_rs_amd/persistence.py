@@ -128,3 +128,106 @@ def load_model(path: str):
         group.append(load_engine(path, device_rank=r))
     set_device(0)
     return cls(eng, group=group)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Session stores (engine.Sessions).  The file is an .npz: capacity, seen_capacity, embedding_dim, model (the model kind), and for
+# the n LIVE slots — len > 0 or a non-empty memory — in ascending order: slots [n] u32, h [n, dim] f32, c likewise (LSTM only),
+# len [n] u64, and their remembered items as a CSR, seen_ptr [n + 1] u64 / seen_items u32.  Nothing identifies the parameters the
+# states were computed under: load_sessions(replay=False) takes the caller's word for them.  Both directions move at most
+# SESSIONS_CHUNK slots at a time through Sessions.state / seen / set_state / set_seen; the halves below that turn those calls'
+# arrays into file arrays and back touch no device.
+# ---------------------------------------------------------------------------------------------------------------------------
+SESSIONS_CHUNK = 65536
+
+
+def sessions_file_arrays(capacity: int, seen_capacity: int, embedding_dim: int, kind: int, chunks) -> dict:
+    """The file's arrays from ``chunks``: an iterable of (slots, h, c, lengths, seen) as ``Sessions.state`` and ``Sessions.seen``
+    return them for ascending runs of slots (c None for EWMA; seen None or a list of u32 arrays, one per slot).  Slots with
+    neither a length nor a memory are dropped."""
+    lstm = int(kind) != 2
+    slots, hs, cs, lens, counts, items = [], [], [], [], [], []
+    for sl, h, c, n, seen in chunks:
+        sl = np.asarray(sl, dtype=np.uint32).ravel()
+        n = np.asarray(n, dtype=np.uint64).ravel()
+        cnt = np.zeros(sl.size, dtype=np.uint64) if seen is None else np.asarray([len(x) for x in seen], dtype=np.uint64)
+        if not (n.size == sl.size == cnt.size) or (lstm and c is None):
+            raise ValueError("one state, one length and one seen list per slot")
+        live = np.flatnonzero((n > 0) | (cnt > 0))
+        slots.append(sl[live])
+        hs.append(np.asarray(h, dtype=np.float32).reshape(sl.size, embedding_dim)[live])
+        if lstm:
+            cs.append(np.asarray(c, dtype=np.float32).reshape(sl.size, embedding_dim)[live])
+        lens.append(n[live])
+        counts.append(cnt[live])
+        if seen is not None:
+            items.extend(np.asarray(seen[i], dtype=np.uint32).ravel() for i in live)
+
+    def cat(parts, dtype, shape):
+        return np.concatenate(parts).astype(dtype, copy=False) if parts else np.zeros(shape, dtype)
+
+    out = {"capacity": np.asarray(int(capacity), dtype=np.uint64), "seen_capacity": np.asarray(int(seen_capacity), dtype=np.uint32),
+           "embedding_dim": np.asarray(int(embedding_dim), dtype=np.uint64), "model": np.asarray(int(kind), dtype=np.int32),
+           "slots": cat(slots, np.uint32, 0), "h": cat(hs, np.float32, (0, embedding_dim)), "len": cat(lens, np.uint64, 0)}
+    if lstm:
+        out["c"] = cat(cs, np.float32, (0, embedding_dim))
+    if out["slots"].size > 1 and not np.all(out["slots"][1:] > out["slots"][:-1]):
+        raise ValueError("slots must ascend")
+    ptr = np.zeros(out["slots"].size + 1, dtype=np.uint64)
+    ptr[1:] = np.cumsum(cat(counts, np.uint64, 0))
+    out["seen_ptr"] = ptr
+    out["seen_items"] = cat(items, np.uint32, 0)
+    return out
+
+
+def sessions_file_chunks(z, chunk: int = SESSIONS_CHUNK):
+    """The reverse: (slots, h, c, lengths, seen) per run of at most ``chunk`` saved slots of the file arrays ``z`` (a mapping),
+    shaped for ``Sessions.set_state`` and ``Sessions.set_seen`` (seen as the CSR pair (ptr, items); c None for EWMA)."""
+    slots, ptr, items = np.asarray(z["slots"]), np.asarray(z["seen_ptr"], dtype=np.uint64), np.asarray(z["seen_items"], dtype=np.uint32)
+    c_all = z["c"] if int(np.asarray(z["model"]).item()) != 2 else None
+    for a in range(0, slots.size, chunk):
+        b = min(a + chunk, slots.size)
+        p = ptr[a:b + 1]
+        yield (slots[a:b], z["h"][a:b], None if c_all is None else c_all[a:b], z["len"][a:b],
+               (p - p[0], items[int(p[0]):int(p[-1])]))
+
+
+def save_sessions(store, path: str) -> None:
+    """Writes ``store`` (an engine.Sessions) to ``path`` (.npz).  A stale store raises, as ``state`` does: ``replay()`` first."""
+    eng = store.model
+    cap, w = store.capacity, store.seen_capacity
+
+    def chunks():
+        for a in range(0, cap, SESSIONS_CHUNK):
+            sl = np.arange(a, min(a + SESSIONS_CHUNK, cap), dtype=np.uint32)
+            h, c, n = store.state(sl)
+            yield sl, h, c, n, (store.seen(sl) if w else None)
+
+    np.savez(_npz_path(path), **sessions_file_arrays(cap, w, eng.dim, int(eng.hp.model), chunks()))
+
+
+def load_sessions(model, path: str, capacity=None, remember=None, replay: bool = False):
+    """A new store of ``model`` (a model wrapper or an engine Model) holding what ``save_sessions`` wrote.  ``capacity`` and
+    ``remember`` default to the file's; a capacity that does not hold the highest saved slot, or a model of another kind or
+    embedding_dim, is a ValueError.  ``replay=False`` restores states, lengths and memories exactly — the caller vouches that the
+    model's parameters are the ones the store was saved under.  ``replay=True`` restores the memories only and recomputes every
+    state from them on the device (``Sessions.replay``): the route after a retrain."""
+    eng: Model = getattr(model, "params", model)
+    z = np.load(_npz_path(path))
+    if int(z["model"].item()) != int(eng.hp.model) or int(z["embedding_dim"].item()) != int(eng.dim):
+        raise ValueError("the store was saved from a model of another kind or embedding_dim")
+    capacity = int(z["capacity"].item()) if capacity is None else int(capacity)
+    remember = int(z["seen_capacity"].item()) if remember is None else int(remember)
+    if z["slots"].size and capacity < int(z["slots"][-1]) + 1:
+        raise ValueError(f"capacity {capacity} does not hold the highest saved slot {int(z['slots'][-1])}")
+    if replay and not remember:
+        raise ValueError("replay=True needs a store with seen-item memory")
+    store = eng.sessions(capacity, remember)
+    for sl, h, c, n, seen in sessions_file_chunks(z):
+        if not replay:
+            store.set_state(sl, h, c, n)
+        if remember:
+            store.set_seen(sl, seen)
+    if replay:
+        store.replay()
+    return store
