@@ -499,6 +499,21 @@ struct Recommendations {
 struct TagFilter {
     std::vector<std::uint32_t> any_of, none_of;
 };
+/// The noise of the recommend_sampled calls (struct sbr_sample_args): k draws without replacement from softmax(score / temperature);
+/// the noise of (row, item) is a function of (seed, streams[row], item) alone.  streams: empty (the row's index in the call; for a
+/// session store the slot id) or one per row.
+struct SampleArgs {
+    float temperature = 1.0f;
+    std::uint64_t seed = 0;
+    std::vector<std::uint64_t> streams;
+};
+/// Rows of the recommend_sampled calls, row-major [num_users][k]: the drawn items in draw order, their plain scores (predict's bits,
+/// not sorted) and their keys (descending); short rows padded with (0xFFFFFFFF, -inf, -inf).
+struct SampledRecommendations {
+    std::size_t num_users = 0, k = 0;
+    std::vector<std::uint32_t> items;
+    std::vector<float> scores, keys;
+};
 /// What ImplicitSequenceModel::similar_items ranks by: the cosine of two item embeddings, or their plain dot product.
 enum class Similarity { Cosine = SBR_SIMILAR_COSINE, Dot = SBR_SIMILAR_DOT };
 /// The loss used for training the model (mod.rs:15-23).
@@ -522,6 +537,25 @@ inline std::vector<std::uint32_t> tag_masks(const std::vector<std::uint32_t>& ma
     if (mask.size() > 1 && mask.size() != n) throw EngineError(SBR_ERR_INVALID_ARGUMENT, where);
     if (mask.size() == n && n > 0) return mask;
     return std::vector<std::uint32_t>(n ? n : 1, mask.empty() ? 0u : mask[0]);
+}
+
+/// A SampleArgs as the struct a *_sampled call takes, over n rows; a non-empty `filter` vector as tag_masks makes it (null: none).
+inline sbr_sample_args sample_args(const SampleArgs& a, std::size_t n, const char* where) {
+    if (!a.streams.empty() && a.streams.size() != n) throw EngineError(SBR_ERR_INVALID_ARGUMENT, where);
+    sbr_sample_args s;
+    s.temperature = a.temperature;
+    s.seed = a.seed;
+    s.streams = a.streams.empty() || n == 0 ? nullptr : a.streams.data();
+    return s;
+}
+inline SampledRecommendations sampled_rows(std::size_t n, std::size_t k) {
+    SampledRecommendations r;
+    r.num_users = n;
+    r.k = k;
+    r.items.resize(n * k);
+    r.scores.resize(n * k);
+    r.keys.resize(n * k);
+    return r;
 }
 
 inline std::vector<std::uint32_t> narrow(const std::vector<ItemId>& ids) {
@@ -704,6 +738,33 @@ class Sessions {
         if (st == SBR_ERR_INVALID_PREDICTION) return Result<Recommendations, PredictionError>::Err(PredictionError::InvalidPredictionValue);
         check(st, "sbr_sessions_recommend_filtered");
         return Result<Recommendations, PredictionError>::Ok(std::move(r));
+    }
+    /// `recommend` with a dice (sbr_sessions_recommend_sampled): k draws without replacement from softmax(score / temperature) over
+    /// what each slot may see — exclusion lists, the seen-item memory unless include_seen, and `filter` unless both its vectors are
+    /// empty.  Streams default to the slot ids.
+    Result<SampledRecommendations, PredictionError> recommend_sampled(const std::vector<std::uint32_t>& slots, std::size_t k,
+                                                                      const SampleArgs& sample, const TagFilter& filter = {},
+                                                                      const std::vector<std::uint64_t>& excl_ptr = {},
+                                                                      const std::vector<std::uint32_t>& excl_items = {},
+                                                                      bool include_seen = false) const {
+        if (k < 1 || k > SBR_RECOMMEND_MAX_K) throw EngineError(SBR_ERR_INVALID_ARGUMENT, "Sessions::recommend_sampled: k outside 1..SBR_RECOMMEND_MAX_K");
+        if (!excl_ptr.empty() && (excl_ptr.size() != slots.size() + 1 || excl_ptr.back() > excl_items.size()))
+            throw EngineError(SBR_ERR_INVALID_ARGUMENT, "Sessions::recommend_sampled: one exclusion range per slot");
+        const bool filtered = !filter.any_of.empty() || !filter.none_of.empty();
+        const std::vector<std::uint32_t> any = tag_masks(filter.any_of, slots.size(), "Sessions::recommend_sampled: one any_of mask per slot");
+        const std::vector<std::uint32_t> none_of = tag_masks(filter.none_of, slots.size(), "Sessions::recommend_sampled: one none_of mask per slot");
+        const sbr_sample_args sa = sample_args(sample, slots.size(), "Sessions::recommend_sampled: one stream per slot");
+        SampledRecommendations r = sampled_rows(slots.size(), k);
+        const std::uint32_t none = 0;
+        const sbr_status st = sbr_sessions_recommend_sampled(h_, slots.data(), (std::uint64_t)slots.size(), (std::uint32_t)k,
+                                                             excl_ptr.empty() ? nullptr : excl_ptr.data(),
+                                                             excl_ptr.empty() ? nullptr : (excl_items.empty() ? &none : excl_items.data()),
+                                                             include_seen ? SBR_RECOMMEND_INCLUDE_HISTORY : 0u, &sa,
+                                                             filtered ? any.data() : nullptr, filtered ? none_of.data() : nullptr, r.items.data(),
+                                                             r.scores.data(), r.keys.data());
+        if (st == SBR_ERR_INVALID_PREDICTION) return Result<SampledRecommendations, PredictionError>::Err(PredictionError::InvalidPredictionValue);
+        check(st, "sbr_sessions_recommend_sampled");
+        return Result<SampledRecommendations, PredictionError>::Ok(std::move(r));
     }
     /// `recommend_diverse` under a tag filter: the pool holds eligible items only (sbr_sessions_recommend_diverse_filtered).
     Result<Recommendations, PredictionError> recommend_diverse_filtered(const std::vector<std::uint32_t>& slots, std::size_t k, std::size_t pool,
@@ -960,6 +1021,55 @@ class ImplicitSequenceModel : public OnlineRankingModel<ImplicitUser> {
         if (st == SBR_ERR_INVALID_PREDICTION) return Result<Recommendations, PredictionError>::Err(PredictionError::InvalidPredictionValue);
         check(st, "sbr_recommend_filtered");
         return Result<Recommendations, PredictionError>::Ok(std::move(r));
+    }
+
+    /// `recommend` with a dice (sbr_recommend_sampled): k draws without replacement from softmax(score / temperature) over the items
+    /// each user may see, inside the catalogue scan; rows in draw order with the plain scores and the keys.  The same (seed, stream)
+    /// gives the same row bit for bit; vary `sample.seed` per request.  `filter`: a tag filter unless both its vectors are empty.
+    Result<SampledRecommendations, PredictionError> recommend_sampled(const data::CompressedInteractions& interactions, std::size_t k,
+                                                                      const SampleArgs& sample, bool exclude_history = true,
+                                                                      const TagFilter& filter = {}) const {
+        if (k < 1 || k > SBR_RECOMMEND_MAX_K) throw EngineError(SBR_ERR_INVALID_ARGUMENT, "recommend_sampled: k outside 1..SBR_RECOMMEND_MAX_K");
+        const std::size_t n = interactions.num_users();
+        const bool filtered = !filter.any_of.empty() || !filter.none_of.empty();
+        const std::vector<std::uint32_t> any = tag_masks(filter.any_of, n, "recommend_sampled: one any_of mask per user");
+        const std::vector<std::uint32_t> none_of = tag_masks(filter.none_of, n, "recommend_sampled: one none_of mask per user");
+        const sbr_sample_args sa = sample_args(sample, n, "recommend_sampled: one stream per user");
+        SampledRecommendations r = sampled_rows(n, k);
+        const sbr_status st = sbr_recommend_sampled(replicas_->primary(), interactions.user_pointers().data(), interactions.item_ids().data(),
+                                                    (std::uint64_t)n, (std::uint32_t)k, exclude_history ? 0u : SBR_RECOMMEND_INCLUDE_HISTORY, &sa,
+                                                    filtered ? any.data() : nullptr, filtered ? none_of.data() : nullptr, r.items.data(),
+                                                    r.scores.data(), r.keys.data());
+        if (st == SBR_ERR_INVALID_PREDICTION) return Result<SampledRecommendations, PredictionError>::Err(PredictionError::InvalidPredictionValue);
+        check(st, "sbr_recommend_sampled");
+        return Result<SampledRecommendations, PredictionError>::Ok(std::move(r));
+    }
+    /// recommend_sampled from representations, reps [num_users][embedding_dim] (sbr_recommend_sampled_reps); excl_ptr / excl_items:
+    /// per-user exclusion lists as a CSR (both empty: none).
+    Result<SampledRecommendations, PredictionError> recommend_sampled_reps(const std::vector<float>& reps, std::size_t k, const SampleArgs& sample,
+                                                                           const std::vector<std::uint64_t>& excl_ptr = {},
+                                                                           const std::vector<std::uint32_t>& excl_items = {},
+                                                                           const TagFilter& filter = {}) const {
+        if (k < 1 || k > SBR_RECOMMEND_MAX_K) throw EngineError(SBR_ERR_INVALID_ARGUMENT, "recommend_sampled_reps: k outside 1..SBR_RECOMMEND_MAX_K");
+        const std::size_t dim = (std::size_t)replicas_->hparams().embedding_dim;
+        if (reps.size() % dim) throw EngineError(SBR_ERR_INVALID_ARGUMENT, "recommend_sampled_reps: rows of embedding_dim floats");
+        const std::size_t n = reps.size() / dim;
+        if (!excl_ptr.empty() && (excl_ptr.size() != n + 1 || excl_ptr.back() > excl_items.size()))
+            throw EngineError(SBR_ERR_INVALID_ARGUMENT, "recommend_sampled_reps: one exclusion range per user");
+        const bool filtered = !filter.any_of.empty() || !filter.none_of.empty();
+        const std::vector<std::uint32_t> any = tag_masks(filter.any_of, n, "recommend_sampled_reps: one any_of mask per user");
+        const std::vector<std::uint32_t> none_of = tag_masks(filter.none_of, n, "recommend_sampled_reps: one none_of mask per user");
+        const sbr_sample_args sa = sample_args(sample, n, "recommend_sampled_reps: one stream per user");
+        SampledRecommendations r = sampled_rows(n, k);
+        const std::uint32_t none = 0;
+        const sbr_status st = sbr_recommend_sampled_reps(replicas_->primary(), reps.data(), (std::uint64_t)n, (std::uint32_t)k,
+                                                         excl_ptr.empty() ? nullptr : excl_ptr.data(),
+                                                         excl_ptr.empty() ? nullptr : (excl_items.empty() ? &none : excl_items.data()), &sa,
+                                                         filtered ? any.data() : nullptr, filtered ? none_of.data() : nullptr, r.items.data(),
+                                                         r.scores.data(), r.keys.data());
+        if (st == SBR_ERR_INVALID_PREDICTION) return Result<SampledRecommendations, PredictionError>::Err(PredictionError::InvalidPredictionValue);
+        check(st, "sbr_recommend_sampled_reps");
+        return Result<SampledRecommendations, PredictionError>::Ok(std::move(r));
     }
 
     /// `recommend` with every item outside `among` ineligible (sbr_recommend_among): the exact top k of that item set — ids in any

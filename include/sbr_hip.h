@@ -691,7 +691,50 @@ sbr_status sbr_sessions_recommend_diverse_filtered(sbr_sessions* st, const uint3
                                                    float trade_off, uint32_t metric, const uint64_t* excl_ptr, const uint32_t* excl_items,
                                                    const uint32_t* any_of, const uint32_t* none_of, uint32_t* out_items, float* out_scores);
 
-/* AUDIENCE — the reverse question, "which rows for this item": for each of num_queries query items q = items[j] (any order, repeats
+/* SAMPLING — k draws without replacement from softmax(score / T) over the items a user may see: exploration, slates that differ
+ * between visits, randomised logging that (seed, stream) gives back (no counterpart in the reference crate: predict over the
+ * catalogue and a host loop).  By the Gumbel-top-k identity the draw is the plain scan over
+ *     key(u, i) = fl(fl(score(u, i) * inv_t) + g(seed, streams[u], i)),   inv_t = 1.0f / temperature (one f32 division),
+ * the product and the sum rounded separately, g standard Gumbel noise: the k items with the largest keys, in key order, are k
+ * sequential draws without replacement.  Row u of out_items / out_scores / out_keys [n][k] (the last two optional):
+ *   ORDER        keys descending, ties to the lower item id, short rows padded with (0xFFFFFFFF, -inf, -inf).
+ *   ELIGIBILITY  the plain call's: history (flags: SBR_RECOMMEND_INCLUDE_HISTORY only), exclusion lists, a session's seen-item
+ *                memory, and the tag masks any_of / none_of of ITEM TAGS — both NULL: no filter and no tags needed; either one
+ *                non-NULL: the *_filtered call's rules.  An ineligible item draws no slot and changes no other item's noise.
+ *   out_scores   the plain scores of the drawn items, sbr_predict's bits, in the row's (key) order — not sorted; padding -inf.
+ *   NOISE        of (row, item) depends on (seed, streams[row], item) and on nothing else: not on k, the batch, the row's place in
+ *                it, or how the call is cut up.  The same (seed, stream) with the same arguments returns the same row bit for bit;
+ *                vary seed per request for a fresh draw.  streams: one u64 per row, NULL = the row's index in the call
+ *                (sbr_sessions_recommend_sampled: the slot id).  With sbr_mix64 the 64-bit finaliser of the engine's counters,
+ *                    K  = mix64(seed ^ mix64(stream * 0x9E3779B97F4A7C15 + 1));  k0 = low 32 bits, k1 = high 32 bits
+ *                    x  = item ^ k0
+ *                    x ^= x >> 16; x *= 0x85EBCA6B; x ^= x >> 13; x *= 0xC2B2AE35; x ^= x >> 16
+ *                    x += k1
+ *                    x ^= x >> 16; x *= 0x7FEB352D; x ^= x >> 15; x *= 0x846CA68B; x ^= x >> 16
+ *                    r  = x >> 9;  u = float(2 r + 1) * 2^-24;  g = -log32(-log32(u))
+ *                log32 being the f32 logarithm of DESIGN.md section 6 (+, -, *, / and integer operations, each rounded once, no
+ *                fused multiply-add): |g - exact| <= 5.7e-7 over all 2^23 values of r, g in [-2.8115408, 16.635532].
+ * SBR_ERR_INVALID_ARGUMENT: sample NULL, a temperature that is not finite and > 0 or whose inv_t is not finite and non-zero, k
+ * outside 1 .. SBR_RECOMMEND_MAX_K, masks on a model without tags, and wherever the plain call gives it.
+ * SBR_ERR_INVALID_PREDICTION: a non-finite score of a scanned pair, as in the plain call, or a non-finite fl(score * inv_t) (then the
+ * key is not finite; a finite product cannot give a non-finite key).  Deterministic; reads parameters only. */
+typedef struct sbr_sample_args {
+    float temperature;
+    uint64_t seed;
+    const uint64_t* streams; /* [n] or NULL */
+} sbr_sample_args;
+sbr_status sbr_recommend_sampled(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users, uint32_t k,
+                                 uint32_t flags, const struct sbr_sample_args* sample, const uint32_t* any_of, const uint32_t* none_of,
+                                 uint32_t* out_items, float* out_scores, float* out_keys);
+sbr_status sbr_recommend_sampled_reps(sbr_model* m, const float* reps, uint64_t num_users, uint32_t k, const uint64_t* excl_ptr,
+                                      const uint32_t* excl_items, const struct sbr_sample_args* sample, const uint32_t* any_of,
+                                      const uint32_t* none_of, uint32_t* out_items, float* out_scores, float* out_keys);
+sbr_status sbr_sessions_recommend_sampled(sbr_sessions* st, const uint32_t* slots, uint64_t n, uint32_t k, const uint64_t* excl_ptr,
+                                          const uint32_t* excl_items, uint32_t flags, const struct sbr_sample_args* sample,
+                                          const uint32_t* any_of, const uint32_t* none_of, uint32_t* out_items, float* out_scores,
+                                          float* out_keys);
+
+/* AUDIENCE— the reverse question, "which rows for this item": for each of num_queries query items q = items[j] (any order, repeats
  * allowed, each < num_items) the k candidate rows that score it highest, score(q, s) = b[q] + chain_dot(h_s, E[q]) with the bits of
  * sbr_predict / sbr_score_candidates for that (state, item) pair: the catalogue scan with the operands' roles exchanged (every
  * product of the chain commutes), the query's bias added in the epilogue.  Row j of out_rows / out_scores [num_queries][k]: score

@@ -88,6 +88,15 @@ class SbrHparams(C.Structure):
     ]
 
 
+class SbrSampleArgs(C.Structure):
+    """struct sbr_sample_args of the *_sampled calls"""
+    _fields_ = [
+        ("temperature", C.c_float),
+        ("seed", C.c_uint64),
+        ("streams", C.c_void_p),
+    ]
+
+
 def storage_dim(embedding_dim: int) -> int:
     """Width the engine stores an embedding_dim in (16 / 32 / 64 / 128 / 256; the extra columns are zero and stay
     zero — sbr_engine.hip `storage_dim`).  Parameters, user representations and predictions use embedding_dim;

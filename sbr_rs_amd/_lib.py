@@ -167,6 +167,9 @@ def load():
         "sbr_audience": [vp, vp, vp, C.c_uint64, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp],
         "sbr_sessions_audience": [vp, vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, vp, vp, C.c_uint32, vp, vp],
         "sbr_sessions_replay": [vp, vp, C.c_uint64, u64p],
+        "sbr_recommend_sampled": [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp],
+        "sbr_recommend_sampled_reps": [vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp],
+        "sbr_sessions_recommend_sampled": [vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint32, vp, vp, vp, vp, vp, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -225,4 +228,5 @@ DECLARED_SYMBOLS = [
     "sbr_sessions_create_seen", "sbr_sessions_seen_capacity", "sbr_sessions_get_seen", "sbr_sessions_set_seen",
     "sbr_audience_reps", "sbr_audience", "sbr_sessions_audience",
     "sbr_sessions_replay",
+    "sbr_recommend_sampled", "sbr_recommend_sampled_reps", "sbr_sessions_recommend_sampled",
 ]

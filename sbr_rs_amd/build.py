@@ -171,6 +171,15 @@ def build_audience_tests(force: bool = False, verbose: bool = True) -> str:
     return _build_cpp_program(AUDIENCE_SRC, AUDIENCE_BIN, force, verbose)
 
 
+SAMPLED_SRC = os.path.join(REPO, "tests", "cpp", "sampled_tests.cpp")
+SAMPLED_BIN = os.path.join(REPO, "tests", "cpp", "_build", "sampled_tests")
+
+
+def build_sampled_tests(force: bool = False, verbose: bool = True) -> str:
+    """g++ build of the C++ host layer's recommend_sampled test program."""
+    return _build_cpp_program(SAMPLED_SRC, SAMPLED_BIN, force, verbose)
+
+
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv))
     print(build_facade_tests(force="--force" in sys.argv))
@@ -184,3 +193,4 @@ if __name__ == "__main__":
     print(build_sessions_replay_tests(force="--force" in sys.argv))
     print(build_filtered_tests(force="--force" in sys.argv))
     print(build_audience_tests(force="--force" in sys.argv))
+    print(build_sampled_tests(force="--force" in sys.argv))

@@ -539,11 +539,11 @@ __global__ __launch_bounds__(64) void rank_targets_finish_kernel(ModelView m, co
  * lambda in the kernel — the BiasAdd instantiations compiled to 12 more VGPRs at every d <= 128 (101 -> 113 at d = 16, 178 -> 190
  * at d = 128); this form leaves their instruction streams what they were (profiles/similar_items_8192x1M_d128.md). */
 struct BiasAdd {
-    static constexpr bool scale = false, query = false;
+    static constexpr bool scale = false, query = false, gumbel = false;
     struct Args {};
 };
 struct ScaleMul {
-    static constexpr bool scale = true, query = false;
+    static constexpr bool scale = true, query = false, gumbel = false;
     struct Args {};
 };
 /* audience's policy: the bias belongs to the scan's "user" — a query item q whose row E[q] is the A operand — not to the scanned
@@ -553,12 +553,37 @@ struct ScaleMul {
  * other two policies, at the end of the argument block behind Filter::Args, and every statement of this one sits under
  * `if constexpr`: their instantiations keep their instruction streams (profiles/audience_asm_stats.md). */
 struct QueryBias {
-    static constexpr bool scale = false, query = true;
+    static constexpr bool scale = false, query = true, gumbel = false;
     struct Args {
         const float* qb; /* [the A table's rows]: the bias of query item rep_row[u] */
     };
 };
-#define TK_SCORE(q) (Score::query ? acc[q] : Score::scale ? acc[q] * bias : bias + acc[q])
+/* recommend_sampled's policy: what the epilogue orders is not the score s = b[i] + dot but the key fl(fl(s * inv_t) + g(u, i)), g the
+ * counter-keyed Gumbel noise of sbr_numerics.h under the row's key K[u] — the k best keys are k draws without replacement from
+ * softmax(s / T).  The rows' k0 / k1 sit in LDS by slot (gk0S / gk1S, as qbS) and acc[q] holds the key from the first stage on.  The
+ * noise costs about as much vector ALU as a tile's MFMA chain takes, so it is evaluated only where it can matter; a pending score
+ * passes three stages, each of which may drop it once the row's list is full (the threshold is -inf before):
+ *   1. t = fl(s * inv_t) for every score; dropped unless fl(t + G_MAX) beats the row's threshold, G_MAX the largest g there is;
+ *   2. the 23 noise bits r are hashed; dropped unless fl(t + G[r >> 13]) beats the threshold, G[j] the largest g of the j-th of
+ *      1 024 equal ranges of r (gubS, computed by the workgroup: g never decreases in r, so it is g at the range's last r).  A
+ *      wave pays for stage 3 whenever one of its 64 lanes survives, so the table is fine-grained: with 64 ranges a score survived
+ *      with probability 1 / 64 at least and most waves went on (profiles/sampled_8192x1M_d128.md);
+ *   3. the two logarithms, key = fl(t + g).
+ * f32 addition is monotone and tk_better is monotone in the score at a fixed id, so a bound that does not beat the threshold means
+ * the key does not either: the stages change no result (tests/test_sampled_gpu.py holds every bit to the numpy statement).
+ * The non-finite test is on t: t is non-finite whenever s is (inv_t is finite and not zero), and a finite t cannot give a non-finite
+ * key (|g| < 17 is below half an ulp of any t that close to overflow), so "a non-finite score or key of a scanned pair fails the
+ * call" is decided before any stage drops anything.  The tag filter runs between stages 1 and 2: a disallowed item is never hashed.
+ * Every statement of the policy sits under `if constexpr` and its Args are at the end of the argument block: the other
+ * instantiations keep their instruction streams (profiles/sampled_asm_stats.md). */
+struct GumbelBias {
+    static constexpr bool scale = false, query = false, gumbel = true;
+    struct Args {
+        float inv_t;
+        const uint64_t* keys; /* [num_users]: the row key K of scan row u (sample_keys_kernel) */
+    };
+};
+#define TK_SCORE(q) ((Score::query || Score::gumbel) ? acc[q] : Score::scale ? acc[q] * bias : bias + acc[q])
 
 /* Whether the scan filters items by tag, the third constant policy.  TagFilter: item i is offered to user u only if
  * (tags[i] & none_of[u]) == 0 && (any_of[u] == 0 || (tags[i] & any_of[u]) != 0) — tags [num_items] the model's item tags, any_of /
@@ -590,6 +615,10 @@ __global__ __launch_bounds__(256, D <= 128 ? 2 : 1) void topk_gemm_kernel(ModelV
     __shared__ float Es[2][32 * ItemTiles<D>::LDE];
     __shared__ float Bs[2][32];
     __shared__ __align__(16) float qbS[Score::query ? 128 : 4]; /* QueryBias only: the queries' biases by slot (slot_user) */
+    // GumbelBias only: the rows' keys by slot (slot_user), and the largest noise of each of 1 024 equal ranges of the noise bits
+    __shared__ uint32_t gk0S[Score::gumbel ? 128 : 1];
+    __shared__ uint32_t gk1S[Score::gumbel ? 128 : 1];
+    __shared__ float gubS[Score::gumbel ? 1024 : 1];
     // TagFilter only: the tiles' tag words, and the users' masks by slot (slot_user), read 16 bytes at a time
     __shared__ uint32_t Ts[2][Filter::on ? 32 : 1];
     __shared__ __align__(16) uint32_t anyS[Filter::on ? 128 : 4];
@@ -626,6 +655,16 @@ __global__ __launch_bounds__(256, D <= 128 ? 2 : 1) void topk_gemm_kernel(ModelV
             const uint32_t u = blockIdx.x * 128 + (uint32_t)slot_user(tid);
             qbS[tid] = u < num_users ? sa.qb[rep_row[u]] : 0.0f;
         }
+        if constexpr (Score::gumbel) {
+            const uint32_t u = blockIdx.x * 128 + (uint32_t)slot_user(tid);
+            const uint64_t K = u < num_users ? sa.keys[u] : 0ull;
+            gk0S[tid] = (uint32_t)K;
+            gk1S[tid] = (uint32_t)(K >> 32);
+        }
+    }
+    if constexpr (Score::gumbel) {
+#pragma unroll
+        for (int j = tid; j < 1024; j += 256) gubS[j] = sbr_gumbel_of_bits((((uint32_t)j + 1u) << 13) - 1u);
     }
     uint32_t umask = 0; /* accumulator registers q whose user exists */
 #pragma unroll
@@ -757,10 +796,30 @@ __global__ __launch_bounds__(256, D <= 128 ? 2 : 1) void topk_gemm_kernel(ModelV
         }
         const uint32_t id = tiles.i_begin + (uint32_t)tile * 32 + (uint32_t)l31;
         uint32_t pend = id < tiles.i_end ? umask : 0u;
+        if constexpr (Score::gumbel) { /* stage 1: acc[q] = t, the non-finite test, and the bound that needs no hash */
+            const float gmax = gubS[1023];
 #pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const float sc = TK_SCORE(q);
-            if (((pend >> q) & 1u) && !(sc - sc == 0.0f)) { bad = true; pend &= ~(1u << q); }
+            for (int q4 = 0; q4 < 4; ++q4) {
+                const float4 t4 = ld4(&thS[pbase + 4 * q4]);
+                const uint4 i4 = *reinterpret_cast<const uint4*>(&thI[pbase + 4 * q4]);
+                const float ts[4] = {t4.x, t4.y, t4.z, t4.w};
+                const uint32_t ti[4] = {i4.x, i4.y, i4.z, i4.w};
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int q = 4 * q4 + j;
+                    const float t = __fmul_rn(bias + acc[q], sa.inv_t);
+                    acc[q] = t;
+                    const bool nf = !(t - t == 0.0f);
+                    if (((pend >> q) & 1u) && nf) bad = true;
+                    if (nf || !tk_better(__fadd_rn(t, gmax), id, ts[j], ti[j])) pend &= ~(1u << q);
+                }
+            }
+        } else {
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                const float sc = TK_SCORE(q);
+                if (((pend >> q) & 1u) && !(sc - sc == 0.0f)) { bad = true; pend &= ~(1u << q); }
+            }
         }
         if constexpr (Filter::on) { /* the lane's item against its 16 users' masks: what is not allowed is not offered */
             const uint32_t tag = Ts[buf][l31];
@@ -784,6 +843,18 @@ __global__ __launch_bounds__(256, D <= 128 ? 2 : 1) void topk_gemm_kernel(ModelV
                 }
             }
             pend &= ~drop;
+        }
+        if constexpr (Score::gumbel) { /* stages 2 and 3, for what is still pending: the hash, the range's bound, the noise */
+            if (pend) {
+#pragma unroll
+                for (int q = 0; q < 16; ++q)
+                    if ((pend >> q) & 1u) {
+                        const uint32_t r = sbr_gumbel_bits(gk0S[pbase + q], gk1S[pbase + q], id);
+                        const float t = acc[q];
+                        if (!tk_better(__fadd_rn(t, gubS[r >> 13]), id, thS[pbase + q], thI[pbase + q])) pend &= ~(1u << q);
+                        else acc[q] = __fadd_rn(t, sbr_gumbel_of_bits(r));
+                    }
+            }
         }
         // offers the pending scores: below the threshold they are dropped, above it they take a staging slot if one is left
         auto offer = [&]() {
@@ -1170,6 +1241,35 @@ __global__ __launch_bounds__(256) void candidate_score_kernel(ModelView m, const
 }
 
 // ------------------------------------------------------------------------------------------------
+// recommend_sampled: the rows' noise keys ahead of the scan (topk_gemm_kernel<D, GumbelBias>), the plain scores behind the merge
+// ------------------------------------------------------------------------------------------------
+/* K[u] of the launch's scan rows from the call's seed and the rows' streams (sbr_numerics.h): a function of (seed, stream) alone,
+ * so neither the host's chunks nor the item ranges can change a row's noise. */
+__global__ __launch_bounds__(256) void sample_keys_kernel(uint64_t seed, const uint64_t* streams, uint32_t n, uint64_t* keys) {
+    const uint32_t u = blockIdx.x * 256 + threadIdx.x;
+    if (u < n) keys[u] = sbr_sample_row_key(seed, streams[u]);
+}
+
+/* The merged rows as candidate_score_kernel's pairs: entry j of row u -> (rep_row[u], items[u][j]).  A padding entry stands in with
+ * the row's first item, or item 0 in a row of padding — a pair the scan has scored, so the flag says nothing new — and
+ * sample_pad_kernel gives it its -inf afterwards. */
+__global__ __launch_bounds__(256) void sample_pairs_kernel(const int* rep_row, const uint32_t* items, uint32_t n, uint32_t k, uint32_t* pair_row,
+                                                           uint32_t* pair_item) {
+    const uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= (uint64_t)n * k) return;
+    const uint64_t u = p / k;
+    uint32_t i = items[p];
+    if (i == TK_NONE) i = items[u * k];
+    pair_row[p] = (uint32_t)rep_row[u];
+    pair_item[p] = i == TK_NONE ? 0u : i;
+}
+
+__global__ __launch_bounds__(256) void sample_pad_kernel(const uint32_t* items, uint64_t n, float* scores) {
+    const uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p < n && items[p] == TK_NONE) scores[p] = -INFINITY;
+}
+
+// ------------------------------------------------------------------------------------------------
 // user_representations: the users' final states out of the forward pass's packed rows
 // ------------------------------------------------------------------------------------------------
 /* out[i][c] = H[rep_row[i]][c] for c < dl (embedding_dim; H's rows are d floats): the rows in user order and at the caller's width,
@@ -1285,6 +1385,18 @@ int launch_subset_ids(const uint32_t* ids, const TopkScan& sc, hipStream_t s) {
 int launch_recommend(const ModelView& m, const float* reps, const TopkScan& sc, hipStream_t s) {
     if (sc.n == 0) return 0;
     return topk_scan<BiasAdd>(m, reps, sc, BiasAdd::Args{}, s);
+}
+
+int launch_recommend_sampled(const ModelView& m, const float* reps, const TopkScan& sc, const SampleScan& sp, hipStream_t s) {
+    if (sc.n == 0) return 0;
+    const uint64_t np = (uint64_t)sc.n * sc.k;
+    const unsigned pair_blocks = (unsigned)((np + 255) / 256);
+    hipLaunchKernelGGL(sample_keys_kernel, dim3((sc.n + 255) / 256), dim3(256), 0, s, sp.seed, sp.streams, sc.n, sc.g.keys);
+    int n = 1 + topk_scan<GumbelBias>(m, reps, sc, GumbelBias::Args{sc.g.inv_t, sc.g.keys}, s);
+    hipLaunchKernelGGL(sample_pairs_kernel, dim3(pair_blocks), dim3(256), 0, s, sc.rep_row, sc.out_items, sc.n, sc.k, sp.pair_row, sp.pair_item);
+    n += 1 + launch_candidate_scores(m, reps, sp.pair_row, sp.pair_item, np, sp.plain, sc.nonfinite_flag, s);
+    hipLaunchKernelGGL(sample_pad_kernel, dim3(pair_blocks), dim3(256), 0, s, sc.out_items, np, sp.plain);
+    return n + 1;
 }
 
 uint32_t diverse_max_pool(int d) {

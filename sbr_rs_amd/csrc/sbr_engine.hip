@@ -3987,15 +3987,58 @@ struct TagFilterArg {
     const uint32_t *any_of, *none_of;
 };
 
+/* recommend_sampled's noise on a scan (not with item rows, a subset or a selection): inv_t = 1.0f / temperature, checked by
+ * sample_args; streams: one per user of the call, or null — then user u's is fallback[u] (a session call's slots), or u itself
+ * where that is null too; out_keys (host, num_users x k) nullable */
+struct Sample {
+    float inv_t;
+    uint64_t seed;
+    const uint64_t* streams;
+    const uint32_t* fallback;
+    float* out_keys;
+};
+
+/* the noise of a *_sampled call out of its arguments: false for a temperature that is not finite and positive, or whose
+ * reciprocal is not finite and non-zero in f32 */
+bool sample_args(const sbr_sample_args* a, float* out_keys, Sample* out) {
+    if (!a || !(a->temperature > 0.0f) || !std::isfinite(a->temperature)) return false;
+    const float inv_t = 1.0f / a->temperature;
+    if (!std::isfinite(inv_t) || inv_t == 0.0f) return false;
+    *out = Sample{inv_t, a->seed, a->streams, nullptr, out_keys};
+    return true;
+}
+
+/* the nullable mask pair of a *_sampled call: both null is no filter */
+const TagFilterArg* sample_filter(const uint32_t* any_of, const uint32_t* none_of, TagFilterArg* hold) {
+    if (!any_of && !none_of) return nullptr;
+    *hold = TagFilterArg{any_of, none_of};
+    return hold;
+}
+
+/* device buffers of launch_recommend_sampled beside TopkBufs over nu users */
+struct SampleBufs {
+    uint64_t *keys, *streams;
+    uint32_t *pair_row, *pair_item;
+    float* plain;
+    void carve(DeviceArena& ar, size_t nu, uint32_t k) {
+        keys = ar.take<uint64_t>(nu);
+        streams = ar.take<uint64_t>(nu);
+        pair_row = ar.take<uint32_t>(nu * k);
+        pair_item = ar.take<uint32_t>(nu * k);
+        plain = ar.take<float>(nu * k);
+    }
+};
+
 /* which variant of the top-k scan a call asks for; the default is plain recommend */
 struct ScanVariant {
     bool cosine = false;                            /* item rows: rank by cosine, not by the plain dot product */
     const std::vector<uint32_t>* subset = nullptr;  /* recommend_among's item set */
     const Diverse* dv = nullptr;
     const TagFilterArg* flt = nullptr;
-    static ScanVariant of(const Diverse* dv, const TagFilterArg* flt) {
+    const Sample* sm = nullptr;
+    static ScanVariant of(const Diverse* dv, const TagFilterArg* flt, const Sample* sm = nullptr) {
         ScanVariant v;
-        v.dv = dv; v.flt = flt;
+        v.dv = dv; v.flt = flt; v.sm = sm;
         return v;
     }
 };
@@ -4010,12 +4053,16 @@ struct ScanVariant {
  * set; the masks go with the call's user u through the chunks, whatever row of H holds its representation.
  * With s.seen (a session store's memory; not with a subset) the exclusion CSR is made on the device: user i of a chunk has the
  * segment [i w + c_i, (i + 1) w + c_(i + 1)), c = the chunk's caller-list pointers — known to the host without any device-side
- * count — which session_seen_lists_kernel fills, ahead of the scan, with the merge of the slot's memory and the caller's list. */
+ * count — which session_seen_lists_kernel fills, ahead of the scan, with the merge of the slot's memory and the caller's list.
+ * With v.sm (recommend_sampled; not with item rows, a subset or v.dv) the scan orders by the noisy keys: out_scores receives the
+ * plain scores of the drawn items and v.sm->out_keys the keys; the streams go with the call's user u through the chunks. */
 sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, uint32_t k, uint32_t* out_items, float* out_scores,
                           const ScanVariant& v = ScanVariant()) {
     const Diverse* dv = v.dv;
     if (v.flt && (!m->item_tags || v.subset)) return SBR_ERR_INVALID_ARGUMENT;
     if (s.seen && v.subset) return SBR_ERR_INVALID_ARGUMENT;
+    const Sample* sm = v.sm;
+    if (sm && (s.item_rows || v.subset || dv)) return SBR_ERR_INVALID_ARGUMENT;
     const size_t seen_w = s.seen ? s.seen->w : 0;
     std::vector<uint64_t> users(num_users);
     for (uint64_t u = 0; u < num_users; ++u) users[u] = u;
@@ -4026,6 +4073,7 @@ sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, 
         UserReps ur; /* its lists: what is excluded (list_ptr empty: nothing) */
         TopkBufs tb;
         SubsetBufs sb;
+        SampleBufs smb{};
         float* rnorm = nullptr; /* item rows: the catalogue's reciprocal norms, once per chunk (the arena does not outlive a carve) */
         uint32_t* dv_items = nullptr; /* dv: the selection's rows, nu x dv->k_out */
         float* dv_scores = nullptr;
@@ -4038,6 +4086,7 @@ sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, 
             }
             if (s.item_rows) rnorm = ar.take<float>(m->hp.num_items);
             if (v.subset) sb.carve(ar, v.subset->size(), (size_t)m->d);
+            if (sm) smb.carve(ar, nu, k);
             if (dv) {
                 dv_items = ar.take<uint32_t>(nu * dv->k_out);
                 dv_scores = ar.take<float>(nu * dv->k_out);
@@ -4070,12 +4119,25 @@ sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, 
             HIPCHK(hipMemcpyAsync(tb.any_of, masks.data(), nu * 4, hipMemcpyHostToDevice, m->stream));
             HIPCHK(hipMemcpyAsync(tb.none_of, masks.data() + nu, nu * 4, hipMemcpyHostToDevice, m->stream));
         }
+        std::vector<uint64_t> streams; /* the chunk's users' streams */
+        if (sm) {
+            streams.resize(nu);
+            for (size_t i = 0; i < nu; ++i) {
+                const uint64_t u = ch.users[i]; /* the call's index, not the chunk's */
+                streams[i] = sm->streams ? sm->streams[u] : sm->fallback ? (uint64_t)sm->fallback[u] : u;
+            }
+            HIPCHK(hipMemcpyAsync(smb.streams, streams.data(), nu * 8, hipMemcpyHostToDevice, m->stream));
+        }
         const size_t ko = dv ? dv->k_out : k; /* the width of the rows that leave */
-        /* the selection reads the pool's scores whether or not the caller wants any */
-        const sbr::TopkScan sc = tb.scan(nu, k, excl, out_scores || dv, v.flt ? m->item_tags : nullptr);
+        /* the selection reads the pool's scores whether or not the caller wants any; a sampled scan's are its keys */
+        sbr::TopkScan sc = tb.scan(nu, k, excl, out_scores || dv || sm, v.flt ? m->item_tags : nullptr);
+        if (sm) sc.g = sbr::SampleNoise{sm->inv_t, smb.keys};
         SBRCHK(scan_launch(m, tb.flag, [&] {
             int n = s.seen ? sbr::launch_session_seen_lists(*s.seen, seen_slot, (int)nu, tb.eptr, seen_caller, tb.excl, m->stream) : 0;
-            if (v.subset) n += sbr::launch_recommend_among(m->mv, sb.ids, scanned_items, sb.E, sb.b, ur.H, sc, m->stream);
+            if (sm)
+                n += sbr::launch_recommend_sampled(m->mv, ur.H, sc, sbr::SampleScan{sm->seed, smb.streams, smb.pair_row, smb.pair_item, smb.plain},
+                                                   m->stream);
+            else if (v.subset) n += sbr::launch_recommend_among(m->mv, sb.ids, scanned_items, sb.E, sb.b, ur.H, sc, m->stream);
             else if (s.item_rows) n += sbr::launch_similar_items(m->mv, ur.d_item_rows, v.cosine, rnorm, ur.H, sc, m->stream);
             else n += sbr::launch_recommend(m->mv, ur.H, sc, m->stream);
             if (dv)
@@ -4083,7 +4145,8 @@ sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, 
                                                 dv_items, out_scores ? dv_scores : nullptr, tb.flag, m->stream);
             return n;
         }, {{out_items + ch.c0 * ko, dv ? dv_items : tb.items, nu * ko * 4},
-            {out_scores ? out_scores + ch.c0 * ko : nullptr, dv ? dv_scores : tb.scores, nu * ko * 4}}));
+            {out_scores ? out_scores + ch.c0 * ko : nullptr, dv ? dv_scores : sm ? smb.plain : tb.scores, nu * ko * 4},
+            {sm && sm->out_keys ? sm->out_keys + ch.c0 * ko : nullptr, tb.scores, nu * ko * 4}}));
     }
     return SBR_OK;
 }
@@ -4107,7 +4170,8 @@ bool scan_k_ok(const sbr_model* m, uint32_t k, const Diverse* dv) {
 
 /* the plain calls, their *_filtered forms (flt non-null) and their diverse forms (dv non-null: k is the pool) */
 sbr_status recommend_call(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users, uint32_t k, uint32_t flags,
-                          uint32_t* out_items, float* out_scores, const TagFilterArg* flt, const Diverse* dv = nullptr) {
+                          uint32_t* out_items, float* out_scores, const TagFilterArg* flt, const Diverse* dv = nullptr,
+                          const Sample* sm = nullptr) {
     if (!m || !user_ptr || (num_users && !out_items)) return SBR_ERR_INVALID_ARGUMENT;
     if (!scan_k_ok(m, k, dv) || (flags & ~SBR_RECOMMEND_INCLUDE_HISTORY)) return SBR_ERR_INVALID_ARGUMENT;
     std::lock_guard<std::mutex> lock(m->mu);
@@ -4115,19 +4179,19 @@ sbr_status recommend_call(sbr_model* m, const uint64_t* user_ptr, const uint32_t
     SBRCHK(check_csr(m, user_ptr, num_users, item_ids, false));
     /* the WHOLE history is masked (evaluation.rs:30-32) */
     return recommend_scan(m, RepSource::of_histories(user_ptr, item_ids, 0, !(flags & SBR_RECOMMEND_INCLUDE_HISTORY)), num_users, k, out_items,
-                          out_scores, ScanVariant::of(dv, flt));
+                          out_scores, ScanVariant::of(dv, flt, sm));
 }
 
 sbr_status recommend_reps_call(sbr_model* m, const float* reps, uint64_t num_users, uint32_t k, const uint64_t* excl_ptr,
                                const uint32_t* excl_items, uint32_t* out_items, float* out_scores, const TagFilterArg* flt,
-                               const Diverse* dv = nullptr) {
+                               const Diverse* dv = nullptr, const Sample* sm = nullptr) {
     if (!m || (num_users && (!reps || !out_items))) return SBR_ERR_INVALID_ARGUMENT;
     if (!scan_k_ok(m, k, dv)) return SBR_ERR_INVALID_ARGUMENT;
     if (!excl_args_ok(excl_ptr, excl_items, num_users)) return SBR_ERR_INVALID_ARGUMENT;
     std::lock_guard<std::mutex> lock(m->mu);
     SBRCHK(enter_reader(m));
     if (excl_ptr) SBRCHK(check_csr(m, excl_ptr, num_users, excl_items, false));
-    return recommend_scan(m, RepSource::of_rows(reps, excl_ptr, excl_items), num_users, k, out_items, out_scores, ScanVariant::of(dv, flt));
+    return recommend_scan(m, RepSource::of_rows(reps, excl_ptr, excl_items), num_users, k, out_items, out_scores, ScanVariant::of(dv, flt, sm));
 }
 
 }  // namespace
@@ -4181,6 +4245,28 @@ sbr_status sbr_recommend_filtered_reps(sbr_model* m, const float* reps, uint64_t
                                        float* out_scores) {
     const TagFilterArg flt{any_of, none_of};
     return recommend_reps_call(m, reps, num_users, k, excl_ptr, excl_items, out_items, out_scores, &flt);
+}
+
+/* ---------------------------------------------------------------------------------------------
+ * sampling without replacement from softmax(score / T) (sbr_catalogue.hip, topk_gemm_kernel's GumbelBias)
+ * ------------------------------------------------------------------------------------------- */
+sbr_status sbr_recommend_sampled(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users, uint32_t k, uint32_t flags,
+                                 const struct sbr_sample_args* sample, const uint32_t* any_of, const uint32_t* none_of, uint32_t* out_items,
+                                 float* out_scores, float* out_keys) {
+    Sample sm;
+    TagFilterArg hold;
+    if (!sample_args(sample, out_keys, &sm)) return SBR_ERR_INVALID_ARGUMENT;
+    return recommend_call(m, user_ptr, item_ids, num_users, k, flags, out_items, out_scores, sample_filter(any_of, none_of, &hold), nullptr, &sm);
+}
+
+sbr_status sbr_recommend_sampled_reps(sbr_model* m, const float* reps, uint64_t num_users, uint32_t k, const uint64_t* excl_ptr,
+                                      const uint32_t* excl_items, const struct sbr_sample_args* sample, const uint32_t* any_of,
+                                      const uint32_t* none_of, uint32_t* out_items, float* out_scores, float* out_keys) {
+    Sample sm;
+    TagFilterArg hold;
+    if (!sample_args(sample, out_keys, &sm)) return SBR_ERR_INVALID_ARGUMENT;
+    return recommend_reps_call(m, reps, num_users, k, excl_ptr, excl_items, out_items, out_scores, sample_filter(any_of, none_of, &hold), nullptr,
+                               &sm);
 }
 
 /* ---------------------------------------------------------------------------------------------
@@ -4992,7 +5078,7 @@ RepSource RepSource::of_sessions(const sbr_sessions* st, const std::vector<int>&
 /* sbr_sessions_recommend*, and with dv (k is the pool) sbr_sessions_recommend_diverse*, which have no flags argument: flags = 0 */
 sbr_status sessions_recommend_call(sbr_sessions* st, const uint32_t* slots, uint64_t n, uint32_t k, const uint64_t* excl_ptr,
                                    const uint32_t* excl_items, uint32_t flags, uint32_t* out_items, float* out_scores, const TagFilterArg* flt,
-                                   const Diverse* dv = nullptr) {
+                                   const Diverse* dv = nullptr, const Sample* sm = nullptr) {
     if (!st || (n && !out_items)) return SBR_ERR_INVALID_ARGUMENT;
     /* a store with memory takes sbr_recommend's flag; one without keeps refusing every flag */
     if (st->seen.w ? (flags & ~SBR_RECOMMEND_INCLUDE_HISTORY) != 0 : flags != 0) return SBR_ERR_INVALID_ARGUMENT;
@@ -5006,7 +5092,7 @@ sbr_status sessions_recommend_call(sbr_sessions* st, const uint32_t* slots, uint
     const std::vector<int> rows = session_rep_rows(st, slots, n);
     const bool seen = st->seen.w && !(flags & SBR_RECOMMEND_INCLUDE_HISTORY);
     return recommend_scan(m, RepSource::of_sessions(st, rows, excl_ptr, excl_items, seen ? slots : nullptr), n, k, out_items, out_scores,
-                          ScanVariant::of(dv, flt));
+                          ScanVariant::of(dv, flt, sm));
 }
 
 }  // namespace
@@ -5021,6 +5107,18 @@ sbr_status sbr_sessions_recommend_filtered(sbr_sessions* st, const uint32_t* slo
                                            uint32_t* out_items, float* out_scores) {
     const TagFilterArg flt{any_of, none_of};
     return sessions_recommend_call(st, slots, n, k, excl_ptr, excl_items, flags, out_items, out_scores, &flt);
+}
+
+sbr_status sbr_sessions_recommend_sampled(sbr_sessions* st, const uint32_t* slots, uint64_t n, uint32_t k, const uint64_t* excl_ptr,
+                                          const uint32_t* excl_items, uint32_t flags, const struct sbr_sample_args* sample,
+                                          const uint32_t* any_of, const uint32_t* none_of, uint32_t* out_items, float* out_scores,
+                                          float* out_keys) {
+    Sample sm;
+    TagFilterArg hold;
+    if (!sample_args(sample, out_keys, &sm)) return SBR_ERR_INVALID_ARGUMENT;
+    sm.fallback = slots; /* a session's default stream is its slot id */
+    return sessions_recommend_call(st, slots, n, k, excl_ptr, excl_items, flags, out_items, out_scores, sample_filter(any_of, none_of, &hold),
+                                   nullptr, &sm);
 }
 
 sbr_status sbr_sessions_recommend_diverse(sbr_sessions* st, const uint32_t* slots, uint64_t n, uint32_t k, uint32_t pool, float trade_off,

@@ -293,6 +293,12 @@ constexpr uint32_t TK_MERGE_MAX = 8192;
 struct TagMasks {
     const uint32_t *tags, *any_of, *none_of;
 };
+/* the noise of a sampled scan (topk_gemm_kernel's GumbelBias policy; keys NULL: not one): inv_t = float(1 / temperature), finite and
+ * not zero, and keys [n], the rows' noise keys, which launch_recommend_sampled fills ahead of the scan */
+struct SampleNoise {
+    float inv_t;
+    uint64_t* keys;
+};
 /* what every top-k scan launch is given beside its catalogue and its A-operand table: device arrays, over the launch's n scan
  * rows ("users": users, query items) */
 struct TopkScan {
@@ -306,9 +312,22 @@ struct TopkScan {
     float* out_scores;          /* NULL: not wanted */
     uint32_t* nonfinite_flag;
     TagMasks f;
+    SampleNoise g;
 };
 uint32_t recommend_groups(uint32_t num_users, uint32_t num_items, uint32_t k, uint32_t* items_per_group);
 int launch_recommend(const ModelView& m, const float* reps, const TopkScan& sc, hipStream_t s);
+/* k draws without replacement from softmax(score / T) per scan row (sbr_catalogue.hip; the contract: SAMPLING in include/sbr_hip.h):
+ * launch_recommend with the GumbelBias policy — sc.out_scores (not NULL) receives the rows' KEYS, descending — between a prologue
+ * that writes sc.g.keys[u] from (seed, streams[u]) and an epilogue that scores the merged rows' (row, item) pairs with
+ * launch_candidate_scores into plain [n][k] (padding: -inf).  streams [n], pair_row / pair_item [n k]: device arrays.  Six launches:
+ * keys, scan, merge, pairs, scores, padding. */
+struct SampleScan {
+    uint64_t seed;
+    const uint64_t* streams;
+    uint32_t *pair_row, *pair_item;
+    float* plain;
+};
+int launch_recommend_sampled(const ModelView& m, const float* reps, const TopkScan& sc, const SampleScan& sp, hipStream_t s);
 /* greedy maximal-marginal-relevance selection (sbr_catalogue.hip, diverse_select_kernel; the contract: sbr_recommend_diverse in
  * include/sbr_hip.h): pool_items / pool_scores [num_users][pool] are launch_recommend's outputs at k = pool; out_items / out_scores
  * [num_users][k_out] the picks in pick order with their pool scores, padded as the pool's rows.  1 <= k_out <= pool <=

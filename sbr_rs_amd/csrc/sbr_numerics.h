@@ -94,6 +94,57 @@ SBR_HD uint32_t sbr_neg_draw(uint64_t epoch_key, uint32_t ctr, uint32_t try_idx,
     return (uint32_t)(((x >> 32) * (uint64_t)num_items) >> 32);
 }
 
+/* ---- counter-keyed Gumbel noise (recommend_sampled) ------------------------------------------ */
+/* recommend_sampled orders a row's items by key = fl(fl(score * inv_t) + g), g i.i.d. standard Gumbel noise: the k best keys in
+ * key order are k draws without replacement from softmax(score / T).  g is a function of (seed, the row's stream, the item) and of
+ * nothing else, from integer operations and f32 +, -, *, / only, each rounded once (no fma: the build's -ffp-contract=off, restated
+ * by the pragmas below), so tests/sampled_expect.py states it a second time in numpy and holds the device to its bits.
+ *   row key   K = mix64(seed ^ mix64(stream * 0x9E3779B97F4A7C15 + 1)), k0 its low and k1 its high 32 bits
+ *   r         23 bits: two rounds of a 32-bit finaliser over item ^ k0, k1 added between them
+ *   u         (2 r + 1) 2^-24, exact, in (0, 1)
+ *   g         -log32(-log32(u))
+ * Over all 2^23 values of r: g in [-2.8115408, 16.635532], max |g - float64 libm| = 5.7e-7, and g never decreases as r grows,
+ * which topk_gemm_kernel's bounds rest on (its table holds g at the last r of each of 1 024 equal ranges of r). */
+SBR_HD uint64_t sbr_sample_row_key(uint64_t seed, uint64_t stream) { return sbr_epoch_key(seed, stream); }
+SBR_HD uint32_t sbr_gumbel_bits(uint32_t k0, uint32_t k1, uint32_t item) {
+    uint32_t x = item ^ k0;
+    x ^= x >> 16; x *= 0x85EBCA6Bu; x ^= x >> 13; x *= 0xC2B2AE35u; x ^= x >> 16;
+    x += k1;
+    x ^= x >> 16; x *= 0x7FEB352Du; x ^= x >> 15; x *= 0x846CA68Bu; x ^= x >> 16;
+    return x >> 9;
+}
+/* natural logarithm of a positive normal x: x = 2^e m with m in (sqrt(1/2), sqrt(2)], log m = 2 atanh(s), s = (m - 1) / (m + 1),
+ * by its odd series to s^9, and e ln 2 in two pieces */
+SBR_HD float sbr_log32(float x) {
+#pragma clang fp contract(off)
+    uint32_t b;
+    __builtin_memcpy(&b, &x, 4);
+    int e = (int)(b >> 23) - 127;
+    b = (b & 0x007FFFFFu) | 0x3F800000u;
+    float m;
+    __builtin_memcpy(&m, &b, 4);
+    if (m > 1.41421356f) {
+        m = m * 0.5f;
+        e += 1;
+    }
+    const float f = m - 1.0f;
+    const float s = f / (2.0f + f);
+    const float z = s * s;
+    float p = (float)(1.0 / 9.0) * z + (float)(1.0 / 7.0);
+    p = p * z + (float)(1.0 / 5.0);
+    p = p * z + (float)(1.0 / 3.0);
+    p = p * z;
+    const float s2 = s + s;
+    const float lm = s2 + s2 * p;
+    const float ef = (float)e;
+    return ef * 0.693359375f + (ef * -2.12194440e-4f + lm);
+}
+SBR_HD float sbr_gumbel_of_bits(uint32_t r) {
+#pragma clang fp contract(off)
+    const float u = (float)(2u * r + 1u) * 5.9604644775390625e-8f; /* 2^-24 */
+    return -sbr_log32(-sbr_log32(u));
+}
+
 /* ---- losses (lstm.rs:316-319) ----------------------------------------------------------------- */
 /* pos/neg are "dot + bias".  Returns the loss term and the coefficient g = dloss/dneg
  * (= -dloss/dpos).  Hinge/WARP: relu((1 + neg) - pos), association as in the reference graph. */

@@ -84,6 +84,25 @@ def _tag_masks(any_of, none_of, nu: int):
     return one(any_of, "any_of"), one(none_of, "none_of")
 
 
+def _sample_args(temperature, seed, streams, n: int):
+    """The noise keywords of a *_sampled call -> (SbrSampleArgs, the array it points into, kept alive by the caller).  streams: None
+    (the library's default: the row's index, or a session's slot id) or one u64 per row."""
+    from ._abi import SbrSampleArgs
+
+    sa = SbrSampleArgs()
+    sa.temperature = float(np.float32(temperature))
+    sa.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    st = None
+    if streams is not None:
+        st = np.ascontiguousarray(np.asarray(streams).ravel(), dtype=np.uint64)
+        if st.size != n:
+            raise ValueError(f"streams: one per row ({n}); got {st.size}")
+        if n == 0:
+            st = np.zeros(1, dtype=np.uint64)
+        sa.streams = st.ctypes.data
+    return sa, st
+
+
 STREAM_ROLES = ("main", "side", "sorter", "copier", "xs")  # the roles SBR_TEST_STREAM_DELAY names, in the counter's order
 
 
@@ -649,6 +668,40 @@ class Model:
                                                        _ptr(scores)))
         return items, scores
 
+    def recommend_sampled(self, user_ptr, item_ids, k: int, temperature: float = 1.0, seed: int = 0, streams=None,
+                          include_history: bool = False, any_of=None, none_of=None):
+        """k draws without replacement from softmax(score / temperature) over the items each user may see (sbr_recommend_sampled):
+        items [U, k] u32, scores [U, k] f32 — the plain scores of the drawn items, predict's bits, in draw order — and keys [U, k]
+        f32, descending; short rows padded with (RECOMMEND_NO_ITEM, -inf, -inf).  Eligibility is ``recommend``'s (history, any_of /
+        none_of).  The noise of (row, item) is a function of (seed, streams[row], item) alone — streams: one u64 per row, default the
+        row's index — so the same (seed, stream) returns the same row bit for bit; vary ``seed`` per request."""
+        up = np.ascontiguousarray(user_ptr, dtype=np.uint64)
+        it = np.ascontiguousarray(item_ids, dtype=np.uint32)
+        nu = max(len(up) - 1, 0)
+        masks = _tag_masks(any_of, none_of, nu)
+        sa, _keep = _sample_args(temperature, seed, streams, nu)
+        items, scores, keys = (np.zeros((nu, max(int(k), 0)), dtype=dt) for dt in (np.uint32, np.float32, np.float32))
+        flags = RECOMMEND_INCLUDE_HISTORY if include_history else 0
+        _check(self._L.sbr_recommend_sampled(self._h, _ptr(up), _ptr(it), nu, int(k) & 0xFFFFFFFF, flags, C.byref(sa),
+                                             None if masks is None else _ptr(masks[0]), None if masks is None else _ptr(masks[1]),
+                                             _ptr(items), _ptr(scores), _ptr(keys)))
+        return items, scores, keys
+
+    def recommend_sampled_reps(self, reps, k: int, temperature: float = 1.0, seed: int = 0, streams=None, exclude=None, any_of=None,
+                               none_of=None):
+        """As recommend_sampled, from representations [U, embedding_dim]; exclude: None or one sequence of item ids per user."""
+        reps = np.ascontiguousarray(reps, dtype=np.float32).reshape(-1, self.dim)
+        nu = reps.shape[0]
+        masks = _tag_masks(any_of, none_of, nu)
+        sa, _keep = _sample_args(temperature, seed, streams, nu)
+        items, scores, keys = (np.zeros((nu, max(int(k), 0)), dtype=dt) for dt in (np.uint32, np.float32, np.float32))
+        ep, ei = _exclusion_csr(exclude, nu)
+        _check(self._L.sbr_recommend_sampled_reps(self._h, _ptr(reps), nu, int(k) & 0xFFFFFFFF, None if ep is None else _ptr(ep),
+                                                  None if ei is None else _ptr(ei), C.byref(sa),
+                                                  None if masks is None else _ptr(masks[0]), None if masks is None else _ptr(masks[1]),
+                                                  _ptr(items), _ptr(scores), _ptr(keys)))
+        return items, scores, keys
+
     def diverse_max_pool(self) -> int:
         """The largest ``pool`` of recommend_diverse on this model (sbr_recommend_diverse_max_pool): a user's pool lives in one
         workgroup's LDS, min(1024, 32768 / storage width) rows."""
@@ -1007,6 +1060,25 @@ class Sessions:
                                                            None if ep is None else _ptr(ep), None if ei is None else _ptr(ei), flags,
                                                            _ptr(masks[0]), _ptr(masks[1]), _ptr(items), _ptr(scores)))
         return items, scores
+
+    def recommend_sampled(self, slots, k: int, temperature: float = 1.0, seed: int = 0, streams=None, exclude=None, any_of=None,
+                          none_of=None, include_seen: bool = False):
+        """``Model.recommend_sampled_reps(self.representations(slots), k, ...)`` with the scan reading the store's rows in place and
+        the seen-item memory excluded exactly as in ``recommend``; streams default to the slot ids, so a session's draw under one
+        seed does not depend on who else is in the call."""
+        if include_seen and not self._seen:
+            raise ValueError("include_seen: this store has no seen-item memory (sessions(capacity, remember=W))")
+        flags = RECOMMEND_INCLUDE_HISTORY if include_seen else 0
+        sl = self._slots(slots)
+        masks = _tag_masks(any_of, none_of, sl.size)
+        sa, _keep = _sample_args(temperature, seed, streams, sl.size)
+        items, scores, keys = (np.zeros((sl.size, max(int(k), 0)), dtype=dt) for dt in (np.uint32, np.float32, np.float32))
+        ep, ei = _exclusion_csr(exclude, sl.size)
+        _check(self._L.sbr_sessions_recommend_sampled(self._h, _ptr(sl), sl.size, int(k) & 0xFFFFFFFF, None if ep is None else _ptr(ep),
+                                                      None if ei is None else _ptr(ei), flags, C.byref(sa),
+                                                      None if masks is None else _ptr(masks[0]), None if masks is None else _ptr(masks[1]),
+                                                      _ptr(items), _ptr(scores), _ptr(keys)))
+        return items, scores, keys
 
     def recommend_diverse(self, slots, k: int, pool: int, trade_off: float = 0.5, metric="cosine", exclude=None, any_of=None,
                           none_of=None):

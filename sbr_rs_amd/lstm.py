@@ -268,6 +268,25 @@ class _ImplicitSequenceModel:
             raise ValueError("a tag filter together with among= is not supported: filter the item set instead")
         return self.params.recommend_among(up, it, k, among, include_history=not exclude_history)
 
+    def recommend_sampled(self, interactions_or_histories, k: int, temperature: float = 1.0, seed: int = 0, streams=None,
+                          exclude_history: bool = True, any_of=None, none_of=None):
+        """``recommend`` with a dice: k draws without replacement from softmax(score / ``temperature``) over the items each user
+        may see, inside the catalogue scan — (items [U, k] u32, scores [U, k] f32: the plain scores of the drawn items in draw
+        order, keys [U, k] f32 descending).  Exploration, slates that differ between visits, and reproducible randomised logging:
+        the noise of a row is a function of (``seed``, ``streams[row]``, item) alone — ``streams`` one integer per row (a user or
+        request id), default the row's index — so the same (seed, stream) gives the same row bit for bit.  Eligibility
+        (``exclude_history``, ``any_of`` / ``none_of``) is ``recommend``'s.  A small temperature approaches ``recommend``."""
+        up, it = self._csr(interactions_or_histories)
+        return self.params.recommend_sampled(up, it, k, temperature=temperature, seed=seed, streams=streams,
+                                             include_history=not exclude_history, any_of=any_of, none_of=none_of)
+
+    def recommend_sampled_reps(self, reps, k: int, temperature: float = 1.0, seed: int = 0, streams=None, exclude=None, any_of=None,
+                               none_of=None):
+        """``recommend_sampled`` from representations [U, embedding_dim] (``user_representations``); ``exclude``: None or one
+        sequence of item ids per user."""
+        return self.params.recommend_sampled_reps(reps, k, temperature=temperature, seed=seed, streams=streams, exclude=exclude,
+                                                  any_of=any_of, none_of=none_of)
+
     def audience(self, interactions_or_histories, items, k: int, exclude_history: bool = True):
         """The reverse of ``recommend``: for each query item of ``items`` the k users whose histories score it highest, on the
         device — (users [Q, k] u32, scores [Q, k] f32), ``predict``'s bits, score descending, ties to the lower user, short rows
