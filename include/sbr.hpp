@@ -514,6 +514,62 @@ struct SampledRecommendations {
     std::vector<std::uint32_t> items;
     std::vector<float> scores, keys;
 };
+/// What the log_partition calls return (PARTITION in sbr_hip.h): per row the shift (the largest score / temperature over the items
+/// the row may see; -inf: none), the fixed-point mass (the sum of the items' weights w = floor(exp32(score / T - shift) 2^frac_bits),
+/// exact and independent of the batch and of how the scan is cut up) and the catalogue's frac_bits.  The model's probability of an
+/// item is w / mass; the weights come from sbr_softmax_weights, the library's one host statement of them.
+struct Partition {
+    float temperature = 1.0f;
+    std::uint32_t frac_bits = 0;
+    std::vector<float> shift;
+    std::vector<std::uint64_t> mass;
+    std::size_t num_users() const { return shift.size(); }
+    /// shift + log(mass / 2^frac_bits) per row; -inf for a row that may see nothing.
+    std::vector<double> log_z() const {
+        std::vector<double> z(shift.size());
+        for (std::size_t u = 0; u < z.size(); ++u)
+            z[u] = mass[u] ? (double)shift[u] + std::log(std::ldexp((double)mass[u], -(int)frac_bits)) : -std::numeric_limits<double>::infinity();
+        return z;
+    }
+    /// The weights of plain scores, row-major [num_users][m].
+    std::vector<std::uint64_t> weights(const std::vector<float>& scores) const {
+        const std::size_t n = shift.size();
+        if (n == 0 ? !scores.empty() : scores.size() % n != 0) throw EngineError(SBR_ERR_INVALID_ARGUMENT, "Partition: scores [num_users][m]");
+        const std::size_t m = n ? scores.size() / n : 0;
+        std::vector<std::uint64_t> w(scores.size());
+        const sbr_status st = sbr_softmax_weights_rows(scores.data(), (std::uint64_t)n, (std::uint64_t)m, temperature, shift.data(), frac_bits, w.data());
+        if (st != SBR_OK) throw EngineError(st, "sbr_softmax_weights_rows");
+        return w;
+    }
+    /// log(w / mass) of items with the plain scores [num_users][m]: the log-probability of one draw; -inf where w == 0.
+    std::vector<double> log_prob(const std::vector<float>& scores) const {
+        const std::vector<std::uint64_t> w = weights(scores);
+        const std::size_t m = shift.empty() ? 0 : scores.size() / shift.size();
+        std::vector<double> out(w.size());
+        for (std::size_t p = 0; p < w.size(); ++p)
+            out[p] = w[p] ? std::log((double)w[p]) - std::log((double)mass[p / m]) : -std::numeric_limits<double>::infinity();
+        return out;
+    }
+    /// The Plackett-Luce conditional log-probabilities of draws without replacement with the plain scores [num_users][k] in draw
+    /// order (SampledRecommendations::scores): log(w_j) - log(mass - the w before j), the remaining mass an exact integer; NaN at
+    /// padding (-inf score) and where w_j == 0.  Meaningful only for a partition taken with the draws' exclusions and masks.
+    std::vector<double> slate_log_prob(const std::vector<float>& scores) const {
+        const std::vector<std::uint64_t> w = weights(scores);
+        const std::size_t k = shift.empty() ? 0 : scores.size() / shift.size();
+        std::vector<double> out(w.size(), std::numeric_limits<double>::quiet_NaN());
+        for (std::size_t u = 0; u < shift.size(); ++u) {
+            std::uint64_t rest = mass[u];
+            for (std::size_t j = 0; j < k; ++j) {
+                const std::uint64_t wj = w[u * k + j];
+                if (wj == 0 || std::isinf(scores[u * k + j])) continue;
+                if (rest == 0 || wj > rest) { rest = 0; continue; }
+                out[u * k + j] = std::log((double)wj) - std::log((double)rest);
+                rest -= wj;
+            }
+        }
+        return out;
+    }
+};
 /// What ImplicitSequenceModel::similar_items ranks by: the cosine of two item embeddings, or their plain dot product.
 enum class Similarity { Cosine = SBR_SIMILAR_COSINE, Dot = SBR_SIMILAR_DOT };
 /// The loss used for training the model (mod.rs:15-23).
@@ -765,6 +821,30 @@ class Sessions {
         if (st == SBR_ERR_INVALID_PREDICTION) return Result<SampledRecommendations, PredictionError>::Err(PredictionError::InvalidPredictionValue);
         check(st, "sbr_sessions_recommend_sampled");
         return Result<SampledRecommendations, PredictionError>::Ok(std::move(r));
+    }
+    /// The exact fixed-point mass of softmax(score / temperature) over what each slot may see (sbr_sessions_log_partition), with
+    /// `recommend_sampled`'s eligibility: the propensities of its draws are `Partition::slate_log_prob` of their scores.
+    Result<Partition, PredictionError> log_partition(const std::vector<std::uint32_t>& slots, float temperature, const TagFilter& filter = {},
+                                                     const std::vector<std::uint64_t>& excl_ptr = {},
+                                                     const std::vector<std::uint32_t>& excl_items = {}, bool include_seen = false) const {
+        if (!excl_ptr.empty() && (excl_ptr.size() != slots.size() + 1 || excl_ptr.back() > excl_items.size()))
+            throw EngineError(SBR_ERR_INVALID_ARGUMENT, "Sessions::log_partition: one exclusion range per slot");
+        const bool filtered = !filter.any_of.empty() || !filter.none_of.empty();
+        const std::vector<std::uint32_t> any = tag_masks(filter.any_of, slots.size(), "Sessions::log_partition: one any_of mask per slot");
+        const std::vector<std::uint32_t> none_of = tag_masks(filter.none_of, slots.size(), "Sessions::log_partition: one none_of mask per slot");
+        Partition r;
+        r.temperature = temperature;
+        r.shift.resize(slots.size());
+        r.mass.resize(slots.size());
+        const std::uint32_t none = 0;
+        const sbr_status st = sbr_sessions_log_partition(h_, slots.data(), (std::uint64_t)slots.size(), excl_ptr.empty() ? nullptr : excl_ptr.data(),
+                                                         excl_ptr.empty() ? nullptr : (excl_items.empty() ? &none : excl_items.data()),
+                                                         include_seen ? SBR_RECOMMEND_INCLUDE_HISTORY : 0u, temperature,
+                                                         filtered ? any.data() : nullptr, filtered ? none_of.data() : nullptr, r.shift.data(),
+                                                         r.mass.data(), &r.frac_bits);
+        if (st == SBR_ERR_INVALID_PREDICTION) return Result<Partition, PredictionError>::Err(PredictionError::InvalidPredictionValue);
+        check(st, "sbr_sessions_log_partition");
+        return Result<Partition, PredictionError>::Ok(std::move(r));
     }
     /// `recommend_diverse` under a tag filter: the pool holds eligible items only (sbr_sessions_recommend_diverse_filtered).
     Result<Recommendations, PredictionError> recommend_diverse_filtered(const std::vector<std::uint32_t>& slots, std::size_t k, std::size_t pool,
@@ -1070,6 +1150,53 @@ class ImplicitSequenceModel : public OnlineRankingModel<ImplicitUser> {
         if (st == SBR_ERR_INVALID_PREDICTION) return Result<SampledRecommendations, PredictionError>::Err(PredictionError::InvalidPredictionValue);
         check(st, "sbr_recommend_sampled_reps");
         return Result<SampledRecommendations, PredictionError>::Ok(std::move(r));
+    }
+
+    /// The softmax normaliser of `recommend_sampled`'s distribution, exactly (sbr_log_partition): per user the fixed-point mass of
+    /// softmax(score / temperature) over the items `recommend` would choose from, summed on the device as integers.
+    Result<Partition, PredictionError> log_partition(const data::CompressedInteractions& interactions, float temperature = 1.0f,
+                                                     bool exclude_history = true, const TagFilter& filter = {}) const {
+        const std::size_t n = interactions.num_users();
+        const bool filtered = !filter.any_of.empty() || !filter.none_of.empty();
+        const std::vector<std::uint32_t> any = tag_masks(filter.any_of, n, "log_partition: one any_of mask per user");
+        const std::vector<std::uint32_t> none_of = tag_masks(filter.none_of, n, "log_partition: one none_of mask per user");
+        Partition r;
+        r.temperature = temperature;
+        r.shift.resize(n);
+        r.mass.resize(n);
+        const sbr_status st = sbr_log_partition(replicas_->primary(), interactions.user_pointers().data(), interactions.item_ids().data(),
+                                                (std::uint64_t)n, exclude_history ? 0u : SBR_RECOMMEND_INCLUDE_HISTORY, temperature,
+                                                filtered ? any.data() : nullptr, filtered ? none_of.data() : nullptr, r.shift.data(),
+                                                r.mass.data(), &r.frac_bits);
+        if (st == SBR_ERR_INVALID_PREDICTION) return Result<Partition, PredictionError>::Err(PredictionError::InvalidPredictionValue);
+        check(st, "sbr_log_partition");
+        return Result<Partition, PredictionError>::Ok(std::move(r));
+    }
+    /// log_partition from representations, reps [num_users][embedding_dim] (sbr_log_partition_reps); excl_ptr / excl_items: per-user
+    /// exclusion lists as a CSR (both empty: none).
+    Result<Partition, PredictionError> log_partition_reps(const std::vector<float>& reps, float temperature,
+                                                          const std::vector<std::uint64_t>& excl_ptr = {},
+                                                          const std::vector<std::uint32_t>& excl_items = {}, const TagFilter& filter = {}) const {
+        const std::size_t dim = (std::size_t)replicas_->hparams().embedding_dim;
+        if (reps.size() % dim) throw EngineError(SBR_ERR_INVALID_ARGUMENT, "log_partition_reps: rows of embedding_dim floats");
+        const std::size_t n = reps.size() / dim;
+        if (!excl_ptr.empty() && (excl_ptr.size() != n + 1 || excl_ptr.back() > excl_items.size()))
+            throw EngineError(SBR_ERR_INVALID_ARGUMENT, "log_partition_reps: one exclusion range per user");
+        const bool filtered = !filter.any_of.empty() || !filter.none_of.empty();
+        const std::vector<std::uint32_t> any = tag_masks(filter.any_of, n, "log_partition_reps: one any_of mask per user");
+        const std::vector<std::uint32_t> none_of = tag_masks(filter.none_of, n, "log_partition_reps: one none_of mask per user");
+        Partition r;
+        r.temperature = temperature;
+        r.shift.resize(n);
+        r.mass.resize(n);
+        const std::uint32_t none = 0;
+        const sbr_status st = sbr_log_partition_reps(replicas_->primary(), reps.data(), (std::uint64_t)n, excl_ptr.empty() ? nullptr : excl_ptr.data(),
+                                                     excl_ptr.empty() ? nullptr : (excl_items.empty() ? &none : excl_items.data()), temperature,
+                                                     filtered ? any.data() : nullptr, filtered ? none_of.data() : nullptr, r.shift.data(),
+                                                     r.mass.data(), &r.frac_bits);
+        if (st == SBR_ERR_INVALID_PREDICTION) return Result<Partition, PredictionError>::Err(PredictionError::InvalidPredictionValue);
+        check(st, "sbr_log_partition_reps");
+        return Result<Partition, PredictionError>::Ok(std::move(r));
     }
 
     /// `recommend` with every item outside `among` ineligible (sbr_recommend_among): the exact top k of that item set — ids in any

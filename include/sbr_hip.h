@@ -734,6 +734,50 @@ sbr_status sbr_sessions_recommend_sampled(sbr_sessions* st, const uint32_t* slot
                                           const uint32_t* any_of, const uint32_t* none_of, uint32_t* out_items, float* out_scores,
                                           float* out_keys);
 
+/* PARTITION — the exact mass of softmax(score / T) over the items a row may see, and with it the propensity of every draw the
+ * *_sampled calls make: what off-policy evaluation, inverse-propensity weighting and counterfactual training need beside a logged
+ * draw (no counterpart in the reference crate).  The sum is taken in FIXED POINT: integer addition is associative, so the result does
+ * not depend on the batch, the host's chunks, the item ranges or the lanes' order, and a numpy restatement holds every bit
+ * (tests/partition_expect.py).  One row's result is a function of its representation, the temperature, its exclusions and masks:
+ *   s_i      b[i] + chain_dot(h, E[i]), sbr_predict's bits
+ *   t_i      fl(s_i * inv_t), inv_t = 1.0f / temperature (one f32 division), as the *_sampled calls scale
+ *   allowed  exactly the items the plain call would choose from: history (flags: SBR_RECOMMEND_INCLUDE_HISTORY only), exclusion
+ *            lists, a session's seen-item memory, and the tag masks — both NULL: no filter and no tags needed
+ *   shift    out_shift[u] = the largest t_i over the allowed items = fl(s_max * inv_t); -inf when nothing is allowed; a zero is +0.0
+ *   d_i      fl(t_i - shift)
+ *   w_i      0 where d_i > 0 or d_i < -64, else fix_F(exp32(d_i)) — exp32 the f32 exponential of DESIGN.md section 6 (integer
+ *            operations and f32 +, -, * only, each rounded once; max relative error 2.54e-7 on [-64, 0], exp32(0) == 1 exactly),
+ *            fix_F(x) = floor(x 2^F) by shifting x's 24-bit significand
+ *   F        *out_frac_bits = sbr_softmax_frac_bits(num_items) = min(40, 63 - bit_length(num_items)): the sum cannot overflow
+ *   mass     out_mass[u] = the sum of w_i over the allowed items; >= 2^F whenever something is allowed (the arg-max weighs exactly
+ *            2^F), else 0
+ * and on the host, in float64, log_z = shift + log(mass / 2^F) (-inf for an empty row).  The model's probability of item i is
+ * w_i / mass, the softmax at resolution 2^-F: |mass / 2^F - sum exp(d_i)| <= num_items 2^-F + 2.54e-7 sum exp(d_i).
+ * sbr_softmax_weights is the one host statement of the t / d / exp32 / fix_F chain: out_w[j] = w of scores[j] against `shift` —
+ * log(out_w[j] / mass) is the log-probability of a draw with plain score scores[j]; a slate drawn without replacement has the
+ * Plackett-Luce conditional probabilities w_j / (mass - the w of the draws before it), the remaining mass an exact integer;
+ * sbr_softmax_weights_rows is the same over many rows, each against its own shift, in one call.  The helpers need no device and no
+ * model.
+ * SBR_ERR_INVALID_ARGUMENT: a temperature that is not finite and > 0 or whose inv_t is not finite and non-zero, a NULL output,
+ * frac_bits > 40, masks on a model without tags, and wherever the plain call gives it.  SBR_ERR_INVALID_PREDICTION: a non-finite
+ * s or t of a scanned pair, as in sbr_recommend / sbr_recommend_sampled; then no output is written.  Deterministic; reads
+ * parameters only.  Not built: a single-pass form without the k = 1 scan, among= subsets, and partitions for similar_items,
+ * audience and recommend_diverse. */
+uint32_t sbr_softmax_frac_bits(uint32_t num_items);
+sbr_status sbr_softmax_weights(const float* scores, uint64_t n, float temperature, float shift, uint32_t frac_bits, uint64_t* out_w);
+/* sbr_softmax_weights of `rows` rows of m scores each, row r against shifts[r]: scores / out_w [rows][m] */
+sbr_status sbr_softmax_weights_rows(const float* scores, uint64_t rows, uint64_t m, float temperature, const float* shifts,
+                                    uint32_t frac_bits, uint64_t* out_w);
+sbr_status sbr_log_partition(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users, uint32_t flags,
+                             float temperature, const uint32_t* any_of, const uint32_t* none_of, float* out_shift, uint64_t* out_mass,
+                             uint32_t* out_frac_bits);
+sbr_status sbr_log_partition_reps(sbr_model* m, const float* reps, uint64_t num_users, const uint64_t* excl_ptr, const uint32_t* excl_items,
+                                  float temperature, const uint32_t* any_of, const uint32_t* none_of, float* out_shift, uint64_t* out_mass,
+                                  uint32_t* out_frac_bits);
+sbr_status sbr_sessions_log_partition(sbr_sessions* st, const uint32_t* slots, uint64_t n, const uint64_t* excl_ptr,
+                                      const uint32_t* excl_items, uint32_t flags, float temperature, const uint32_t* any_of,
+                                      const uint32_t* none_of, float* out_shift, uint64_t* out_mass, uint32_t* out_frac_bits);
+
 /* AUDIENCE— the reverse question, "which rows for this item": for each of num_queries query items q = items[j] (any order, repeats
  * allowed, each < num_items) the k candidate rows that score it highest, score(q, s) = b[q] + chain_dot(h_s, E[q]) with the bits of
  * sbr_predict / sbr_score_candidates for that (state, item) pair: the catalogue scan with the operands' roles exchanged (every

@@ -170,6 +170,11 @@ def load():
         "sbr_recommend_sampled": [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp],
         "sbr_recommend_sampled_reps": [vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp],
         "sbr_sessions_recommend_sampled": [vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint32, vp, vp, vp, vp, vp, vp],
+        "sbr_softmax_weights": [vp, C.c_uint64, C.c_float, C.c_float, C.c_uint32, vp],
+        "sbr_softmax_weights_rows": [vp, C.c_uint64, C.c_uint64, C.c_float, vp, C.c_uint32, vp],
+        "sbr_log_partition": [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_float, vp, vp, vp, vp, vp],
+        "sbr_log_partition_reps": [vp, vp, C.c_uint64, vp, vp, C.c_float, vp, vp, vp, vp, vp],
+        "sbr_sessions_log_partition": [vp, vp, C.c_uint64, vp, vp, C.c_uint32, C.c_float, vp, vp, vp, vp, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -187,6 +192,8 @@ def load():
     L.sbr_group_plan_destroy.restype = None
     L.sbr_status_string.argtypes = [C.c_int]
     L.sbr_status_string.restype = C.c_char_p
+    L.sbr_softmax_frac_bits.argtypes = [C.c_uint32]
+    L.sbr_softmax_frac_bits.restype = C.c_uint32
     L.sbr_abi_version.argtypes = []
     L.sbr_abi_version.restype = C.c_uint32
     L.sbr_release_cached_memory.argtypes = []
@@ -229,4 +236,5 @@ DECLARED_SYMBOLS = [
     "sbr_audience_reps", "sbr_audience", "sbr_sessions_audience",
     "sbr_sessions_replay",
     "sbr_recommend_sampled", "sbr_recommend_sampled_reps", "sbr_sessions_recommend_sampled",
+    "sbr_softmax_frac_bits", "sbr_softmax_weights", "sbr_softmax_weights_rows", "sbr_log_partition", "sbr_log_partition_reps", "sbr_sessions_log_partition",
 ]

@@ -180,6 +180,15 @@ def build_sampled_tests(force: bool = False, verbose: bool = True) -> str:
     return _build_cpp_program(SAMPLED_SRC, SAMPLED_BIN, force, verbose)
 
 
+PARTITION_SRC = os.path.join(REPO, "tests", "cpp", "partition_tests.cpp")
+PARTITION_BIN = os.path.join(REPO, "tests", "cpp", "_build", "partition_tests")
+
+
+def build_partition_tests(force: bool = False, verbose: bool = True) -> str:
+    """g++ build of the C++ host layer's log_partition test program."""
+    return _build_cpp_program(PARTITION_SRC, PARTITION_BIN, force, verbose)
+
+
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv))
     print(build_facade_tests(force="--force" in sys.argv))
@@ -194,3 +203,4 @@ if __name__ == "__main__":
     print(build_filtered_tests(force="--force" in sys.argv))
     print(build_audience_tests(force="--force" in sys.argv))
     print(build_sampled_tests(force="--force" in sys.argv))
+    print(build_partition_tests(force="--force" in sys.argv))

@@ -28,6 +28,9 @@
  *                            A operand is the query items' rows of E (reps = E, rep_row = the item ids), the scanned table a set of
  *                            state rows, and the bias the query's, b[q], held in LDS by slot
  *   candidate_score_kernel : score_candidates' b[i] + chain_dot(rep_u, E[i]) of a flat list of (user, item) pairs, 64 per wave
+ *   partition_*_kernel     : log_partition's exact fixed-point mass of softmax(score / T) per row: shift (the row's largest scaled
+ *                            score, from the top-k scan at k = 1), gemm (the catalogue scan with an epilogue that sums integer
+ *                            weights), finish (the exclusion lists' items subtracted exactly)
  *   rep_rows_kernel        : user_representations' rows rep_row[i] of H, embedding_dim floats each, in user order
  *
  * The three GEMM kernels share one catalogue scan, S[u][i] = b[i] + sum_k h[u][k] E[i][k] on v_mfma_f32_32x32x2_f32: a workgroup
@@ -1270,6 +1273,189 @@ __global__ __launch_bounds__(256) void sample_pad_kernel(const uint32_t* items, 
 }
 
 // ------------------------------------------------------------------------------------------------
+// log_partition: the exact fixed-point mass of softmax(score / T) per row — the k = 1 scan (topk_gemm_kernel<D, BiasAdd>) for the
+// shift, a second catalogue scan with a summing epilogue, and the exclusion lists' correction
+// ------------------------------------------------------------------------------------------------
+/* shift[u] = fl(best score * inv_t) of the k = 1 scan's merged rows — the largest t of the row, because a product with a positive
+ * inv_t is monotone — or -inf for a row of padding (nothing allowed); a zero shift is +0.0 whatever the sign of the best score's
+ * zero.  mass[u] = 0 ahead of the scan's atomics. */
+__global__ __launch_bounds__(256) void partition_shift_kernel(const uint32_t* best_item, const float* best_score, uint32_t n, float inv_t,
+                                                              float* shift, unsigned long long* mass) {
+    const uint32_t u = blockIdx.x * 256 + threadIdx.x;
+    if (u >= n) return;
+    shift[u] = best_item[u] == TK_NONE ? -INFINITY : __fadd_rn(__fmul_rn(best_score[u], inv_t), 0.0f);
+    mass[u] = 0ull;
+}
+
+/* The sum scan, rank_gemm_kernel's shape: every score of the workgroup's 128 users x its item range becomes t = fl(s * inv_t),
+ * d = fl(t - shift[u]) and the integer weight w (sbr_softmax_weight), added into 16 64-bit per-lane accumulators; at the end of the
+ * range the 32 item lanes of a half-wave are summed and one 64-bit atomic per user joins the other ranges'.  Integer addition is
+ * associative: lanes, ranges and the host's chunks cannot change a bit of the sum.  The rows' shifts sit in LDS by slot (slot_user);
+ * a row that does not exist, or that may see nothing, has shift -inf, so d = +inf and w = 0.  The exclusion lists are NOT searched
+ * here: an excluded item that passes the tag test and has d <= 0 is added, and partition_finish_kernel subtracts exactly that.
+ * With TagFilter the lane's item is tested against its 16 users' masks as in topk_gemm_kernel.  The non-finite test is on t and sees
+ * every scanned pair of an existing row, allowed or not.  The skip of the polynomial is per tile and per wave, not per register:
+ * a tile none of whose 64 x 16 scores weighs anything for the wave (every d below -64: a trained model at a small T) costs no
+ * exp32; once one lane has one live score, all 16 registers of every lane run it, the dead ones on d = 0 and masked out of the add. */
+template <int D, class Filter>
+__global__ __launch_bounds__(256, D <= 128 ? 2 : 1) void partition_gemm_kernel(ModelView m, const float* reps, const int* rep_row, uint32_t num_users,
+                                                                              const float* shift, float inv_t, uint32_t frac_bits,
+                                                                              uint32_t items_per_group, unsigned long long* mass,
+                                                                              uint32_t* nonfinite_flag, typename Filter::Args fa) {
+    __shared__ float Es[2][32 * ItemTiles<D>::LDE];
+    __shared__ float Bs[2][32];
+    __shared__ __align__(16) float shS[128]; /* shifts by slot (slot_user) */
+    __shared__ uint32_t Ts[2][Filter::on ? 32 : 1];
+    __shared__ __align__(16) uint32_t anyS[Filter::on ? 128 : 4];
+    __shared__ __align__(16) uint32_t anyZ[Filter::on ? 128 : 4]; /* 1 where the user's any_of is 0 (every tag passes it), else 0 */
+    __shared__ __align__(16) uint32_t noneS[Filter::on ? 128 : 4];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = tid >> 6;
+    const int l31 = lane & 31;
+    const int hh = lane >> 5;
+    const uint32_t u0 = blockIdx.x * 128 + wave * 32;
+    float a[D / 2];
+    load_user_fragments<D>(a, reps, rep_row, num_users, u0);
+    if (tid < 128) {
+        const uint32_t u = blockIdx.x * 128 + (uint32_t)slot_user(tid);
+        shS[tid] = u < num_users ? shift[u] : -INFINITY;
+        if constexpr (Filter::on) {
+            const uint32_t any = u < num_users ? fa.any_of[u] : 0u;
+            anyS[tid] = any;
+            anyZ[tid] = any == 0u ? 1u : 0u;
+            noneS[tid] = u < num_users ? fa.none_of[u] : 0u;
+        }
+    }
+    uint32_t umask = 0; /* accumulator registers q whose user exists */
+#pragma unroll
+    for (int q = 0; q < 16; ++q)
+        if (acc_user(u0, q, hh) < num_users) umask |= 1u << q;
+    uint64_t sum[16];
+#pragma unroll
+    for (int q = 0; q < 16; ++q) sum[q] = 0ull;
+    bool bad = false;
+    ItemTiles<D> tiles(m, items_per_group);
+    const int ntiles = tiles.ntiles;
+    if (ntiles > 0) {
+        tiles.fetch(m, 0);
+        tiles.stage(Es[0], Bs[0]);
+        if constexpr (Filter::on) {
+            tiles.fetch_tags(fa.tags, 0);
+            tiles.stage_tags(Ts[0]);
+        }
+    }
+    __syncthreads();
+    const int pbase = wave * 32 + hh * 16;
+    for (int tile = 0; tile < ntiles; ++tile) {
+        const int buf = tile & 1;
+        if (tile + 1 < ntiles) {
+            tiles.fetch(m, tile + 1);
+            if constexpr (Filter::on) tiles.fetch_tags(fa.tags, tile + 1);
+        }
+        const f32x16 acc = tile_dots<D>(a, Es[buf]);
+        const float bias = Bs[buf][l31];
+        const bool item_ok = tiles.i_begin + (uint32_t)tile * 32 + (uint32_t)l31 < tiles.i_end;
+        uint32_t live = item_ok ? umask : 0u; /* accumulator registers q whose score may weigh something */
+        float dq[16];
+#pragma unroll
+        for (int q4 = 0; q4 < 4; ++q4) {
+            const float4 s4 = ld4(&shS[pbase + 4 * q4]);
+            const float sh[4] = {s4.x, s4.y, s4.z, s4.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int q = 4 * q4 + j;
+                const float t = __fmul_rn(bias + acc[q], inv_t);
+                if (((live >> q) & 1u) && !(t - t == 0.0f)) bad = true;
+                const float d = __fsub_rn(t, sh[j]);
+                dq[q] = d;
+                if (!(d <= 0.0f && d >= SBR_SOFTMAX_D_MIN)) live &= ~(1u << q);
+            }
+        }
+        if constexpr (Filter::on) { /* the lane's item against its 16 users' masks, as topk_gemm_kernel's */
+            const uint32_t tag = Ts[buf][l31];
+            uint32_t drop = 0;
+#pragma unroll
+            for (int q4 = 0; q4 < 4; ++q4) {
+                const uint4 a4 = *reinterpret_cast<const uint4*>(&anyS[pbase + 4 * q4]);
+                const uint4 z4 = *reinterpret_cast<const uint4*>(&anyZ[pbase + 4 * q4]);
+                const uint4 n4 = *reinterpret_cast<const uint4*>(&noneS[pbase + 4 * q4]);
+                const uint32_t any[4] = {a4.x, a4.y, a4.z, a4.w};
+                const uint32_t anyz[4] = {z4.x, z4.y, z4.z, z4.w};
+                const uint32_t none[4] = {n4.x, n4.y, n4.z, n4.w};
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const uint32_t hit = (tag & none[j]) != 0u ? 1u : 0u;
+                    const uint32_t miss = ((tag & any[j]) | anyz[j]) == 0u ? 1u : 0u;
+                    drop |= (hit | miss) << (4 * q4 + j);
+                }
+            }
+            live &= ~drop;
+        }
+        if (__any(live != 0u)) {
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                const uint64_t w = sbr_fix(sbr_exp32(((live >> q) & 1u) ? dq[q] : 0.0f), frac_bits);
+                sum[q] += ((live >> q) & 1u) ? w : 0ull;
+            }
+        }
+        if (tile + 1 < ntiles) {
+            tiles.stage(Es[buf ^ 1], Bs[buf ^ 1]);
+            if constexpr (Filter::on) tiles.stage_tags(Ts[buf ^ 1]);
+        }
+        __syncthreads();
+    }
+    // per-user totals: sum over the 32 item lanes of each half-wave, the two halves of the 64-bit sum apart (the carry is added back)
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+        uint64_t c = sum[q];
+#pragma unroll
+        for (int off = 16; off >= 1; off >>= 1) {
+            const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)c, off, 64);
+            const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(c >> 32), off, 64);
+            c += ((uint64_t)hi << 32) | lo;
+        }
+        const uint32_t u = acc_user(u0, q, hh);
+        if (l31 == 0 && u < num_users && c) atomicAdd(&mass[u], (unsigned long long)c);
+    }
+    if (__any(bad) && lane == 0) atomicOr(nonfinite_flag, 1u);
+}
+
+/* One wave per row, as rank_history_kernel: every distinct entry of the row's ascending exclusion list (repeats and the 0xFFFFFFFF
+ * padding of a session's list skipped) is scored again with the scan's functions, and its weight leaves the mass if the scan added
+ * it — the item passes the row's tag test and d <= 0 (sbr_softmax_weight is zero otherwise: an excluded item that outscores every
+ * allowed one was never added).  Integer subtraction of what was added: exact. */
+template <int D>
+__global__ __launch_bounds__(64) void partition_finish_kernel(ModelView m, const float* reps, const int* rep_row, const float* shift, float inv_t,
+                                                              uint32_t frac_bits, const uint64_t* excl_ptr, const uint32_t* excl_items,
+                                                              const uint32_t* tags, const uint32_t* any_of, const uint32_t* none_of,
+                                                              unsigned long long* mass) {
+    const int u = blockIdx.x;
+    const float* h = reps + (size_t)rep_row[u] * D;
+    const float sh = shift[u];
+    const uint32_t any = tags ? any_of[u] : 0u, none = tags ? none_of[u] : 0u;
+    const uint64_t e0 = excl_ptr[u], e1 = excl_ptr[u + 1];
+    uint64_t sub = 0;
+    for (uint64_t e = e0 + threadIdx.x; e < e1; e += 64) {
+        const uint32_t i = excl_items[e];
+        if (i >= m.num_items || (e > e0 && excl_items[e - 1] == i)) continue;
+        if (tags) {
+            const uint32_t tag = tags[i];
+            if ((tag & none) != 0u || (any != 0u && (tag & any) == 0u)) continue;
+        }
+        const float s = m.b[i] + chain_dot<D>(h, m.E + (size_t)i * D);
+        sub += sbr_softmax_weight(__fmul_rn(s, inv_t), sh, frac_bits);
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)sub, off, 64);
+        const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(sub >> 32), off, 64);
+        sub += ((uint64_t)hi << 32) | lo;
+    }
+    if (threadIdx.x == 0 && sub) atomicAdd(&mass[u], (unsigned long long)(0ull - sub)); /* two's complement: subtracts */
+}
+
+// ------------------------------------------------------------------------------------------------
 // user_representations: the users' final states out of the forward pass's packed rows
 // ------------------------------------------------------------------------------------------------
 /* out[i][c] = H[rep_row[i]][c] for c < dl (embedding_dim; H's rows are d floats): the rows in user order and at the caller's width,
@@ -1397,6 +1583,31 @@ int launch_recommend_sampled(const ModelView& m, const float* reps, const TopkSc
     n += 1 + launch_candidate_scores(m, reps, sp.pair_row, sp.pair_item, np, sp.plain, sc.nonfinite_flag, s);
     hipLaunchKernelGGL(sample_pad_kernel, dim3(pair_blocks), dim3(256), 0, s, sc.out_items, np, sp.plain);
     return n + 1;
+}
+
+int launch_log_partition(const ModelView& m, const float* reps, const TopkScan& sc, const PartitionScan& pt, hipStream_t s) {
+    if (sc.n == 0) return 0;
+    int n = topk_scan<BiasAdd>(m, reps, sc, BiasAdd::Args{}, s); /* sc.k == 1: the rows' best allowed items and their scores */
+    hipLaunchKernelGGL(partition_shift_kernel, dim3((sc.n + 255) / 256), dim3(256), 0, s, sc.out_items, sc.out_scores, sc.n, pt.inv_t, pt.shift,
+                       pt.mass);
+    // item ranges as launch_recommend's at k = 1: two rounds of the chip's resident slots (two workgroups per CU at d <= 128)
+    const uint32_t utiles = (sc.n + 127) / 128;
+    uint32_t per = 0;
+    const uint32_t groups = split_items(m.num_items, wanted_groups((256u * 2u * 2u + utiles - 1) / utiles), UINT32_MAX, UINT32_MAX, &per);
+    const uint32_t fb = sbr_softmax_fbits(m.num_items);
+    const dim3 grid(utiles, groups);
+    DISPATCH_D(m.d, {
+        if (sc.f.tags)
+            hipLaunchKernelGGL((partition_gemm_kernel<DD, TagFilter>), grid, dim3(256), 0, s, m, reps, sc.rep_row, sc.n, pt.shift, pt.inv_t, fb, per,
+                               pt.mass, sc.nonfinite_flag, TagFilter::Args{sc.f.tags, sc.f.any_of, sc.f.none_of});
+        else
+            hipLaunchKernelGGL((partition_gemm_kernel<DD, NoFilter>), grid, dim3(256), 0, s, m, reps, sc.rep_row, sc.n, pt.shift, pt.inv_t, fb, per,
+                               pt.mass, sc.nonfinite_flag, NoFilter::Args{});
+        if (sc.excl_ptr)
+            hipLaunchKernelGGL((partition_finish_kernel<DD>), dim3(sc.n), dim3(64), 0, s, m, reps, sc.rep_row, pt.shift, pt.inv_t, fb, sc.excl_ptr,
+                               sc.excl_items, sc.f.tags, sc.f.any_of, sc.f.none_of, pt.mass);
+    });
+    return n + 2 + (sc.excl_ptr ? 1 : 0);
 }
 
 uint32_t diverse_max_pool(int d) {

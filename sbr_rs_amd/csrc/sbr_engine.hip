@@ -4029,6 +4029,23 @@ struct SampleBufs {
     }
 };
 
+/* log_partition on a scan at k = 1 (not with item rows, a subset, a selection or noise): inv_t = 1.0f / temperature, checked by
+ * partition_args; out_shift / out_mass: host, one per user of the call — the call has no item or score rows */
+struct Partition {
+    float inv_t;
+    float* out_shift;
+    uint64_t* out_mass;
+};
+
+/* the arguments the *_log_partition calls share: false for a temperature sample_args refuses or an output that is missing */
+bool partition_args(float temperature, uint64_t n, float* out_shift, uint64_t* out_mass, uint32_t* out_frac_bits, Partition* out) {
+    const sbr_sample_args a{temperature, 0, nullptr};
+    Sample sm;
+    if (!sample_args(&a, nullptr, &sm) || !out_frac_bits || (n && (!out_shift || !out_mass))) return false;
+    *out = Partition{sm.inv_t, out_shift, out_mass};
+    return true;
+}
+
 /* which variant of the top-k scan a call asks for; the default is plain recommend */
 struct ScanVariant {
     bool cosine = false;                            /* item rows: rank by cosine, not by the plain dot product */
@@ -4036,9 +4053,10 @@ struct ScanVariant {
     const Diverse* dv = nullptr;
     const TagFilterArg* flt = nullptr;
     const Sample* sm = nullptr;
-    static ScanVariant of(const Diverse* dv, const TagFilterArg* flt, const Sample* sm = nullptr) {
+    const Partition* pt = nullptr;
+    static ScanVariant of(const Diverse* dv, const TagFilterArg* flt, const Sample* sm = nullptr, const Partition* pt = nullptr) {
         ScanVariant v;
-        v.dv = dv; v.flt = flt; v.sm = sm;
+        v.dv = dv; v.flt = flt; v.sm = sm; v.pt = pt;
         return v;
     }
 };
@@ -4055,7 +4073,9 @@ struct ScanVariant {
  * segment [i w + c_i, (i + 1) w + c_(i + 1)), c = the chunk's caller-list pointers — known to the host without any device-side
  * count — which session_seen_lists_kernel fills, ahead of the scan, with the merge of the slot's memory and the caller's list.
  * With v.sm (recommend_sampled; not with item rows, a subset or v.dv) the scan orders by the noisy keys: out_scores receives the
- * plain scores of the drawn items and v.sm->out_keys the keys; the streams go with the call's user u through the chunks. */
+ * plain scores of the drawn items and v.sm->out_keys the keys; the streams go with the call's user u through the chunks.
+ * With v.pt (log_partition; k == 1, not with item rows, a subset, v.dv or v.sm) the scan finds the rows' shifts and a second scan
+ * sums the softmax weights: out_items / out_scores are unused (null) and the results are v.pt->out_shift / out_mass. */
 sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, uint32_t k, uint32_t* out_items, float* out_scores,
                           const ScanVariant& v = ScanVariant()) {
     const Diverse* dv = v.dv;
@@ -4063,6 +4083,8 @@ sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, 
     if (s.seen && v.subset) return SBR_ERR_INVALID_ARGUMENT;
     const Sample* sm = v.sm;
     if (sm && (s.item_rows || v.subset || dv)) return SBR_ERR_INVALID_ARGUMENT;
+    const Partition* pt = v.pt;
+    if (pt && (s.item_rows || v.subset || dv || sm || k != 1)) return SBR_ERR_INVALID_ARGUMENT;
     const size_t seen_w = s.seen ? s.seen->w : 0;
     std::vector<uint64_t> users(num_users);
     for (uint64_t u = 0; u < num_users; ++u) users[u] = u;
@@ -4078,6 +4100,8 @@ sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, 
         uint32_t* dv_items = nullptr; /* dv: the selection's rows, nu x dv->k_out */
         float* dv_scores = nullptr;
         uint32_t *seen_slot = nullptr, *seen_caller = nullptr; /* s.seen: the chunk's slots and caller lists, the build kernel's inputs */
+        float* pt_shift = nullptr; /* pt: the rows' shifts and masses */
+        unsigned long long* pt_mass = nullptr;
         SBRCHK(user_reps(m, s, ch.users, [&](DeviceArena& ar) {
             tb.carve(ar, scanned_items, nu, nu * seen_w + ur.b.list_items.size(), k, v.flt != nullptr);
             if (s.seen) {
@@ -4087,6 +4111,10 @@ sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, 
             if (s.item_rows) rnorm = ar.take<float>(m->hp.num_items);
             if (v.subset) sb.carve(ar, v.subset->size(), (size_t)m->d);
             if (sm) smb.carve(ar, nu, k);
+            if (pt) {
+                pt_mass = ar.take<unsigned long long>(nu);
+                pt_shift = ar.take<float>(nu);
+            }
             if (dv) {
                 dv_items = ar.take<uint32_t>(nu * dv->k_out);
                 dv_scores = ar.take<float>(nu * dv->k_out);
@@ -4130,11 +4158,12 @@ sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, 
         }
         const size_t ko = dv ? dv->k_out : k; /* the width of the rows that leave */
         /* the selection reads the pool's scores whether or not the caller wants any; a sampled scan's are its keys */
-        sbr::TopkScan sc = tb.scan(nu, k, excl, out_scores || dv || sm, v.flt ? m->item_tags : nullptr);
+        sbr::TopkScan sc = tb.scan(nu, k, excl, out_scores || dv || sm || pt, v.flt ? m->item_tags : nullptr);
         if (sm) sc.g = sbr::SampleNoise{sm->inv_t, smb.keys};
         SBRCHK(scan_launch(m, tb.flag, [&] {
             int n = s.seen ? sbr::launch_session_seen_lists(*s.seen, seen_slot, (int)nu, tb.eptr, seen_caller, tb.excl, m->stream) : 0;
-            if (sm)
+            if (pt) n += sbr::launch_log_partition(m->mv, ur.H, sc, sbr::PartitionScan{pt->inv_t, pt_shift, pt_mass}, m->stream);
+            else if (sm)
                 n += sbr::launch_recommend_sampled(m->mv, ur.H, sc, sbr::SampleScan{sm->seed, smb.streams, smb.pair_row, smb.pair_item, smb.plain},
                                                    m->stream);
             else if (v.subset) n += sbr::launch_recommend_among(m->mv, sb.ids, scanned_items, sb.E, sb.b, ur.H, sc, m->stream);
@@ -4144,7 +4173,9 @@ sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, 
                 n += sbr::launch_diverse_select(m->mv, tb.items, tb.scores, (uint32_t)nu, k, dv->k_out, dv->trade_off, dv->metric == SBR_SIMILAR_COSINE,
                                                 dv_items, out_scores ? dv_scores : nullptr, tb.flag, m->stream);
             return n;
-        }, {{out_items + ch.c0 * ko, dv ? dv_items : tb.items, nu * ko * 4},
+        }, {{out_items ? out_items + ch.c0 * ko : nullptr, dv ? dv_items : tb.items, nu * ko * 4},
+            {pt ? pt->out_shift + ch.c0 : nullptr, pt_shift, nu * 4},
+            {pt ? pt->out_mass + ch.c0 : nullptr, pt_mass, nu * 8},
             {out_scores ? out_scores + ch.c0 * ko : nullptr, dv ? dv_scores : sm ? smb.plain : tb.scores, nu * ko * 4},
             {sm && sm->out_keys ? sm->out_keys + ch.c0 * ko : nullptr, tb.scores, nu * ko * 4}}));
     }
@@ -4267,6 +4298,63 @@ sbr_status sbr_recommend_sampled_reps(sbr_model* m, const float* reps, uint64_t 
     if (!sample_args(sample, out_keys, &sm)) return SBR_ERR_INVALID_ARGUMENT;
     return recommend_reps_call(m, reps, num_users, k, excl_ptr, excl_items, out_items, out_scores, sample_filter(any_of, none_of, &hold), nullptr,
                                &sm);
+}
+
+/* ---------------------------------------------------------------------------------------------
+ * the exact mass of softmax(score / T): the k = 1 scan, the sum scan and the lists' correction (sbr_catalogue.hip)
+ * ------------------------------------------------------------------------------------------- */
+uint32_t sbr_softmax_frac_bits(uint32_t num_items) { return sbr_softmax_fbits(num_items); }
+
+sbr_status sbr_softmax_weights(const float* scores, uint64_t n, float temperature, float shift, uint32_t frac_bits, uint64_t* out_w) {
+    Partition pt;
+    uint32_t fb = 0;
+    if (!partition_args(temperature, 0, nullptr, nullptr, &fb, &pt) || frac_bits > 40u || (n && (!scores || !out_w))) return SBR_ERR_INVALID_ARGUMENT;
+    for (uint64_t i = 0; i < n; ++i) out_w[i] = sbr_softmax_weight(scores[i] * pt.inv_t, shift, frac_bits);
+    return SBR_OK;
+}
+
+sbr_status sbr_softmax_weights_rows(const float* scores, uint64_t rows, uint64_t m, float temperature, const float* shifts, uint32_t frac_bits,
+                                    uint64_t* out_w) {
+    if (rows && m && !shifts) return SBR_ERR_INVALID_ARGUMENT;
+    if (rows == 0 || m == 0) return sbr_softmax_weights(nullptr, 0, temperature, 0.0f, frac_bits, nullptr); /* the argument checks alone */
+    for (uint64_t r = 0; r < rows; ++r) {
+        const sbr_status st = sbr_softmax_weights(scores ? scores + r * m : nullptr, m, temperature, shifts[r], frac_bits, out_w ? out_w + r * m : nullptr);
+        if (st != SBR_OK) return st;
+    }
+    return SBR_OK;
+}
+
+sbr_status sbr_log_partition(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users, uint32_t flags,
+                             float temperature, const uint32_t* any_of, const uint32_t* none_of, float* out_shift, uint64_t* out_mass,
+                             uint32_t* out_frac_bits) {
+    Partition pt;
+    TagFilterArg hold;
+    if (!m || !user_ptr || !partition_args(temperature, num_users, out_shift, out_mass, out_frac_bits, &pt)) return SBR_ERR_INVALID_ARGUMENT;
+    if (flags & ~SBR_RECOMMEND_INCLUDE_HISTORY) return SBR_ERR_INVALID_ARGUMENT;
+    std::lock_guard<std::mutex> lock(m->mu);
+    SBRCHK(enter_reader(m));
+    SBRCHK(check_csr(m, user_ptr, num_users, item_ids, false));
+    const sbr_status r = recommend_scan(m, RepSource::of_histories(user_ptr, item_ids, 0, !(flags & SBR_RECOMMEND_INCLUDE_HISTORY)), num_users, 1,
+                                        nullptr, nullptr, ScanVariant::of(nullptr, sample_filter(any_of, none_of, &hold), nullptr, &pt));
+    if (r == SBR_OK) *out_frac_bits = sbr_softmax_fbits((uint32_t)m->hp.num_items);
+    return r;
+}
+
+sbr_status sbr_log_partition_reps(sbr_model* m, const float* reps, uint64_t num_users, const uint64_t* excl_ptr, const uint32_t* excl_items,
+                                  float temperature, const uint32_t* any_of, const uint32_t* none_of, float* out_shift, uint64_t* out_mass,
+                                  uint32_t* out_frac_bits) {
+    Partition pt;
+    TagFilterArg hold;
+    if (!m || (num_users && !reps) || !partition_args(temperature, num_users, out_shift, out_mass, out_frac_bits, &pt))
+        return SBR_ERR_INVALID_ARGUMENT;
+    if (!excl_args_ok(excl_ptr, excl_items, num_users)) return SBR_ERR_INVALID_ARGUMENT;
+    std::lock_guard<std::mutex> lock(m->mu);
+    SBRCHK(enter_reader(m));
+    if (excl_ptr) SBRCHK(check_csr(m, excl_ptr, num_users, excl_items, false));
+    const sbr_status r = recommend_scan(m, RepSource::of_rows(reps, excl_ptr, excl_items), num_users, 1, nullptr, nullptr,
+                                        ScanVariant::of(nullptr, sample_filter(any_of, none_of, &hold), nullptr, &pt));
+    if (r == SBR_OK) *out_frac_bits = sbr_softmax_fbits((uint32_t)m->hp.num_items);
+    return r;
 }
 
 /* ---------------------------------------------------------------------------------------------
@@ -5078,8 +5166,8 @@ RepSource RepSource::of_sessions(const sbr_sessions* st, const std::vector<int>&
 /* sbr_sessions_recommend*, and with dv (k is the pool) sbr_sessions_recommend_diverse*, which have no flags argument: flags = 0 */
 sbr_status sessions_recommend_call(sbr_sessions* st, const uint32_t* slots, uint64_t n, uint32_t k, const uint64_t* excl_ptr,
                                    const uint32_t* excl_items, uint32_t flags, uint32_t* out_items, float* out_scores, const TagFilterArg* flt,
-                                   const Diverse* dv = nullptr, const Sample* sm = nullptr) {
-    if (!st || (n && !out_items)) return SBR_ERR_INVALID_ARGUMENT;
+                                   const Diverse* dv = nullptr, const Sample* sm = nullptr, const Partition* pt = nullptr) {
+    if (!st || (n && !out_items && !pt)) return SBR_ERR_INVALID_ARGUMENT;
     /* a store with memory takes sbr_recommend's flag; one without keeps refusing every flag */
     if (st->seen.w ? (flags & ~SBR_RECOMMEND_INCLUDE_HISTORY) != 0 : flags != 0) return SBR_ERR_INVALID_ARGUMENT;
     if (!scan_k_ok(st->m, k, dv)) return SBR_ERR_INVALID_ARGUMENT;
@@ -5092,7 +5180,7 @@ sbr_status sessions_recommend_call(sbr_sessions* st, const uint32_t* slots, uint
     const std::vector<int> rows = session_rep_rows(st, slots, n);
     const bool seen = st->seen.w && !(flags & SBR_RECOMMEND_INCLUDE_HISTORY);
     return recommend_scan(m, RepSource::of_sessions(st, rows, excl_ptr, excl_items, seen ? slots : nullptr), n, k, out_items, out_scores,
-                          ScanVariant::of(dv, flt, sm));
+                          ScanVariant::of(dv, flt, sm, pt));
 }
 
 }  // namespace
@@ -5119,6 +5207,18 @@ sbr_status sbr_sessions_recommend_sampled(sbr_sessions* st, const uint32_t* slot
     sm.fallback = slots; /* a session's default stream is its slot id */
     return sessions_recommend_call(st, slots, n, k, excl_ptr, excl_items, flags, out_items, out_scores, sample_filter(any_of, none_of, &hold),
                                    nullptr, &sm);
+}
+
+sbr_status sbr_sessions_log_partition(sbr_sessions* st, const uint32_t* slots, uint64_t n, const uint64_t* excl_ptr, const uint32_t* excl_items,
+                                      uint32_t flags, float temperature, const uint32_t* any_of, const uint32_t* none_of, float* out_shift,
+                                      uint64_t* out_mass, uint32_t* out_frac_bits) {
+    Partition pt;
+    TagFilterArg hold;
+    if (!st || !partition_args(temperature, n, out_shift, out_mass, out_frac_bits, &pt)) return SBR_ERR_INVALID_ARGUMENT;
+    const sbr_status r = sessions_recommend_call(st, slots, n, 1, excl_ptr, excl_items, flags, nullptr, nullptr,
+                                                 sample_filter(any_of, none_of, &hold), nullptr, nullptr, &pt);
+    if (r == SBR_OK) *out_frac_bits = sbr_softmax_fbits((uint32_t)st->m->hp.num_items);
+    return r;
 }
 
 sbr_status sbr_sessions_recommend_diverse(sbr_sessions* st, const uint32_t* slots, uint64_t n, uint32_t k, uint32_t pool, float trade_off,

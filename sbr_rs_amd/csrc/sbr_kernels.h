@@ -328,6 +328,18 @@ struct SampleScan {
     float* plain;
 };
 int launch_recommend_sampled(const ModelView& m, const float* reps, const TopkScan& sc, const SampleScan& sp, hipStream_t s);
+/* the exact fixed-point mass of softmax(score / T) per scan row (sbr_catalogue.hip; the contract: PARTITION in include/sbr_hip.h):
+ * launch_recommend at sc.k == 1 (sc.out_scores not NULL) finds each row's best allowed item, partition_shift_kernel writes
+ * shift[u] = fl(its score * inv_t) (-inf: nothing allowed) and zeroes mass[u], partition_gemm_kernel adds the weights
+ * sbr_softmax_weight(t, shift[u], sbr_softmax_fbits(m.num_items)) of every item that passes sc.f's tag test, and — with
+ * exclusion lists — partition_finish_kernel subtracts those of the lists' distinct items.  shift / mass [n]: device arrays.
+ * Four or five launches: scan, merge, shift, sum scan, finish. */
+struct PartitionScan {
+    float inv_t;
+    float* shift;
+    unsigned long long* mass;
+};
+int launch_log_partition(const ModelView& m, const float* reps, const TopkScan& sc, const PartitionScan& pt, hipStream_t s);
 /* greedy maximal-marginal-relevance selection (sbr_catalogue.hip, diverse_select_kernel; the contract: sbr_recommend_diverse in
  * include/sbr_hip.h): pool_items / pool_scores [num_users][pool] are launch_recommend's outputs at k = pool; out_items / out_scores
  * [num_users][k_out] the picks in pick order with their pool scores, padded as the pool's rows.  1 <= k_out <= pool <=

@@ -145,6 +145,56 @@ SBR_HD float sbr_gumbel_of_bits(uint32_t r) {
     return -sbr_log32(-sbr_log32(u));
 }
 
+/* ---- fixed-point softmax weights (log_partition) --------------------------------------------- */
+/* log_partition sums a row's softmax weights as integers, so the sum does not depend on the order of the additions: with
+ * inv_t = fl(1 / T), t = fl(score * inv_t), shift = the row's largest t over the items it may see and d = fl(t - shift),
+ *   w = 0 where d > 0 or d < -64 (or d is not a number), else fix_F(exp32(d)),   mass = sum of w,
+ * F = sbr_softmax_fbits(num_items) = min(40, 63 - bit_length(num_items)): every w <= 2^F, so num_items of them stay below 2^63.
+ * Integer operations and f32 +, -, * only, each rounded once (no fma, no hardware exponential — v_exp_f32 is not correctly
+ * rounded), so tests/partition_expect.py states them a second time in numpy and holds the device to every bit.
+ *   exp32(d)  n = round(d log2 e) by adding and subtracting 1.5 2^23, r = (d - n ln2_hi) - n ln2_lo (|r| <= 0.347), the degree-6
+ *             Taylor polynomial of e^r in Horner form, times 2^n as a float built from its exponent bits (n >= -93: a normal).
+ *             Over 6 000 001 equally spaced and 4 000 000 logarithmically spaced arguments in [-64, 0]: max relative error
+ *             2.54e-7 against float64 libm (at d = -26.686005), no decrease anywhere along either sorted sweep, never above 1,
+ *             and exp32(0) == 1 exactly — the row's arg-max weighs exactly 2^F.
+ *   fix_F(x)  floor(x 2^F) of a positive normal x <= 1: its 24-bit significand shifted by (exponent - 150 + F). */
+#define SBR_SOFTMAX_D_MIN (-64.0f)
+SBR_HD uint32_t sbr_softmax_fbits(uint32_t num_items) {
+    uint32_t bl = 0;
+    while (bl < 32u && (num_items >> bl) != 0u) ++bl;
+    return 63u - bl < 40u ? 63u - bl : 40u;
+}
+SBR_HD float sbr_exp32(float d) {
+#pragma clang fp contract(off)
+    const float n = (d * 1.44269504f + 12582912.0f) - 12582912.0f;
+    const float r = (d - n * 0.693359375f) - n * -2.12194440e-4f;
+    float p = (float)(1.0 / 720.0) * r + (float)(1.0 / 120.0);
+    p = p * r + (float)(1.0 / 24.0);
+    p = p * r + (float)(1.0 / 6.0);
+    p = p * r + 0.5f;
+    p = p * r + 1.0f;
+    p = p * r + 1.0f;
+    const uint32_t b = (uint32_t)((int)n + 127) << 23;
+    float scale;
+    __builtin_memcpy(&scale, &b, 4);
+    return p * scale;
+}
+SBR_HD uint64_t sbr_fix(float x, uint32_t frac_bits) {
+    uint32_t b;
+    __builtin_memcpy(&b, &x, 4);
+    const int e = (int)((b >> 23) & 0xFFu);
+    const uint64_t m = (uint64_t)((b & 0x007FFFFFu) | 0x00800000u);
+    const int sh = e - 150 + (int)frac_bits;
+    if (e == 0) return 0;
+    return sh >= 0 ? m << (sh < 39 ? sh : 39) : (-sh < 24 ? m >> -sh : 0ull);
+}
+/* w of t = fl(score * inv_t) against the row's shift */
+SBR_HD uint64_t sbr_softmax_weight(float t, float shift, uint32_t frac_bits) {
+#pragma clang fp contract(off)
+    const float d = t - shift;
+    return (d <= 0.0f && d >= SBR_SOFTMAX_D_MIN) ? sbr_fix(sbr_exp32(d), frac_bits) : 0ull;
+}
+
 /* ---- losses (lstm.rs:316-319) ----------------------------------------------------------------- */
 /* pos/neg are "dot + bias".  Returns the loss term and the coefficient g = dloss/dneg
  * (= -dloss/dpos).  Hinge/WARP: relu((1 + neg) - pos), association as in the reference graph. */

@@ -103,6 +103,77 @@ def _sample_args(temperature, seed, streams, n: int):
     return sa, st
 
 
+def softmax_frac_bits(num_items: int) -> int:
+    """F of a catalogue of num_items (sbr_softmax_frac_bits): min(40, 63 - bit_length(num_items)).  Needs no device."""
+    return int(_lib.load().sbr_softmax_frac_bits(int(num_items) & 0xFFFFFFFF))
+
+
+def softmax_weights(scores, temperature, shift, frac_bits: int) -> np.ndarray:
+    """The fixed-point softmax weights w (u64, the shape of ``scores``) of plain scores against a row's ``shift`` — one shift, or an
+    array that broadcasts against the scores' leading axes — by sbr_softmax_weights_rows, one call over all the rows of
+    sbr_softmax_weights, the library's one host statement of the t / d / exp32 / fix_F chain.  Needs no device."""
+    sc = np.ascontiguousarray(scores, dtype=np.float32)
+    w = np.zeros(sc.shape, dtype=np.uint64)
+    if sc.size == 0:
+        return w
+    rows_s = sc.reshape(-1, sc.shape[-1]) if sc.ndim > 1 else sc.reshape(1, -1)
+    shifts = np.ascontiguousarray(np.broadcast_to(np.asarray(shift, dtype=np.float32).reshape(-1, 1) if np.ndim(shift) else np.float32(shift),
+                                                  (rows_s.shape[0], 1)).ravel())
+    _check(_lib.load().sbr_softmax_weights_rows(_ptr(rows_s), rows_s.shape[0], rows_s.shape[1], float(np.float32(temperature)), _ptr(shifts),
+                                                int(frac_bits), _ptr(w)))
+    return w
+
+
+class Partition:
+    """What the log_partition calls return: per row the ``shift`` (f32 [U], the largest score / T over the items the row may see),
+    the fixed-point ``mass`` (u64 [U], the sum of the items' weights w = floor(exp32(score / T - shift) 2^frac_bits)) and the
+    catalogue's ``frac_bits``; ``log_z`` (f64 [U]) = shift + log(mass / 2^frac_bits), -inf for a row that may see nothing.  The
+    model's probability of an item is w / mass."""
+
+    def __init__(self, temperature, shift, mass, frac_bits: int):
+        self.temperature = float(np.float32(temperature))
+        self.shift, self.mass, self.frac_bits = shift, mass, int(frac_bits)
+
+    @property
+    def log_z(self) -> np.ndarray:
+        with np.errstate(divide="ignore"):
+            return self.shift.astype(np.float64) + np.log(self.mass.astype(np.float64) / 2.0 ** self.frac_bits)
+
+    def _weights(self, scores):
+        sc = np.ascontiguousarray(scores, dtype=np.float32)
+        if sc.ndim != 2 or sc.shape[0] != self.shift.size:
+            raise ValueError(f"scores: [{self.shift.size}, m] plain scores, one row per row of the partition")
+        return sc, softmax_weights(sc, self.temperature, self.shift, self.frac_bits)
+
+    def log_prob(self, scores) -> np.ndarray:
+        """log(w / mass), f64 [U, m], of items with the plain ``scores`` [U, m] (score_candidates' or a recommend call's): the
+        log-probability that one draw from the row's softmax is that item; -inf where w == 0."""
+        _, w = self._weights(scores)
+        live = w != 0  # then the row's mass is not 0 either, for a partition taken with the items' exclusions and masks
+        with np.errstate(divide="ignore", invalid="ignore"):
+            lp = np.log(w.astype(np.float64)) - np.log(self.mass.astype(np.float64))[:, None]
+        return np.where(live, lp, -np.inf)
+
+    def slate_log_prob(self, scores) -> np.ndarray:
+        """The Plackett-Luce conditional log-probabilities, f64 [U, k], of draws without replacement with the plain ``scores``
+        [U, k] in draw order, as recommend_sampled returns them: log(w_j) - log(mass - sum of the w before j), the remaining mass
+        an exact integer.  NaN at padding (-inf score) and where w_j == 0.  Meaningful only for a partition taken with the draws'
+        exclusions and masks."""
+        sc, w = self._weights(scores)
+        before = np.zeros(w.shape, dtype=np.uint64)
+        if w.shape[1] > 1:
+            before[:, 1:] = np.cumsum(w[:, :-1], axis=1, dtype=np.uint64)
+        enough = before < self.mass[:, None]
+        rest = np.where(enough, self.mass[:, None] - np.where(enough, before, np.uint64(0)), np.uint64(1))
+        out = np.log(np.maximum(w, np.uint64(1)).astype(np.float64)) - np.log(rest.astype(np.float64))
+        out[~enough | (w > rest) | (w == 0) | np.isneginf(sc)] = np.nan  # a slate that overdraws its partition has no probability
+        return out
+
+
+def _partition_outputs(n: int):
+    return np.zeros(max(n, 1), dtype=np.float32)[:n], np.zeros(max(n, 1), dtype=np.uint64)[:n], C.c_uint32(0)
+
+
 STREAM_ROLES = ("main", "side", "sorter", "copier", "xs")  # the roles SBR_TEST_STREAM_DELAY names, in the counter's order
 
 
@@ -669,12 +740,14 @@ class Model:
         return items, scores
 
     def recommend_sampled(self, user_ptr, item_ids, k: int, temperature: float = 1.0, seed: int = 0, streams=None,
-                          include_history: bool = False, any_of=None, none_of=None):
+                          include_history: bool = False, any_of=None, none_of=None, log_prob: bool = False):
         """k draws without replacement from softmax(score / temperature) over the items each user may see (sbr_recommend_sampled):
         items [U, k] u32, scores [U, k] f32 — the plain scores of the drawn items, predict's bits, in draw order — and keys [U, k]
         f32, descending; short rows padded with (RECOMMEND_NO_ITEM, -inf, -inf).  Eligibility is ``recommend``'s (history, any_of /
         none_of).  The noise of (row, item) is a function of (seed, streams[row], item) alone — streams: one u64 per row, default the
-        row's index — so the same (seed, stream) returns the same row bit for bit; vary ``seed`` per request."""
+        row's index — so the same (seed, stream) returns the same row bit for bit; vary ``seed`` per request.  ``log_prob=True``
+        appends a fourth output, log_prob [U, k] f64: the draws' propensities, ``log_partition`` of the same arguments applied to
+        the scores by ``Partition.slate_log_prob``."""
         up = np.ascontiguousarray(user_ptr, dtype=np.uint64)
         it = np.ascontiguousarray(item_ids, dtype=np.uint32)
         nu = max(len(up) - 1, 0)
@@ -685,10 +758,13 @@ class Model:
         _check(self._L.sbr_recommend_sampled(self._h, _ptr(up), _ptr(it), nu, int(k) & 0xFFFFFFFF, flags, C.byref(sa),
                                              None if masks is None else _ptr(masks[0]), None if masks is None else _ptr(masks[1]),
                                              _ptr(items), _ptr(scores), _ptr(keys)))
+        if log_prob:
+            part = self.log_partition(up, it, temperature, include_history=include_history, any_of=any_of, none_of=none_of)
+            return items, scores, keys, part.slate_log_prob(scores)
         return items, scores, keys
 
     def recommend_sampled_reps(self, reps, k: int, temperature: float = 1.0, seed: int = 0, streams=None, exclude=None, any_of=None,
-                               none_of=None):
+                               none_of=None, log_prob: bool = False):
         """As recommend_sampled, from representations [U, embedding_dim]; exclude: None or one sequence of item ids per user."""
         reps = np.ascontiguousarray(reps, dtype=np.float32).reshape(-1, self.dim)
         nu = reps.shape[0]
@@ -700,7 +776,37 @@ class Model:
                                                   None if ei is None else _ptr(ei), C.byref(sa),
                                                   None if masks is None else _ptr(masks[0]), None if masks is None else _ptr(masks[1]),
                                                   _ptr(items), _ptr(scores), _ptr(keys)))
+        if log_prob:
+            part = self.log_partition_reps(reps, temperature, exclude=exclude, any_of=any_of, none_of=none_of)
+            return items, scores, keys, part.slate_log_prob(scores)
         return items, scores, keys
+
+    def log_partition(self, user_ptr, item_ids, temperature: float = 1.0, include_history: bool = False, any_of=None,
+                      none_of=None) -> Partition:
+        """The exact fixed-point mass of softmax(score / temperature) over the items each user may see (sbr_log_partition):
+        eligibility is ``recommend``'s; the result does not depend on the batch or on how the scan is cut up."""
+        up = np.ascontiguousarray(user_ptr, dtype=np.uint64)
+        it = np.ascontiguousarray(item_ids, dtype=np.uint32)
+        nu = max(len(up) - 1, 0)
+        masks = _tag_masks(any_of, none_of, nu)
+        shift, mass, fb = _partition_outputs(nu)
+        flags = RECOMMEND_INCLUDE_HISTORY if include_history else 0
+        _check(self._L.sbr_log_partition(self._h, _ptr(up), _ptr(it), nu, flags, float(np.float32(temperature)),
+                                         None if masks is None else _ptr(masks[0]), None if masks is None else _ptr(masks[1]),
+                                         _ptr(shift), _ptr(mass), C.byref(fb)))
+        return Partition(temperature, shift, mass, fb.value)
+
+    def log_partition_reps(self, reps, temperature: float = 1.0, exclude=None, any_of=None, none_of=None) -> Partition:
+        """As log_partition, from representations [U, embedding_dim]; exclude: None or one sequence of item ids per user."""
+        reps = np.ascontiguousarray(reps, dtype=np.float32).reshape(-1, self.dim)
+        nu = reps.shape[0]
+        masks = _tag_masks(any_of, none_of, nu)
+        shift, mass, fb = _partition_outputs(nu)
+        ep, ei = _exclusion_csr(exclude, nu)
+        _check(self._L.sbr_log_partition_reps(self._h, _ptr(reps), nu, None if ep is None else _ptr(ep), None if ei is None else _ptr(ei),
+                                              float(np.float32(temperature)), None if masks is None else _ptr(masks[0]),
+                                              None if masks is None else _ptr(masks[1]), _ptr(shift), _ptr(mass), C.byref(fb)))
+        return Partition(temperature, shift, mass, fb.value)
 
     def diverse_max_pool(self) -> int:
         """The largest ``pool`` of recommend_diverse on this model (sbr_recommend_diverse_max_pool): a user's pool lives in one
@@ -1062,7 +1168,7 @@ class Sessions:
         return items, scores
 
     def recommend_sampled(self, slots, k: int, temperature: float = 1.0, seed: int = 0, streams=None, exclude=None, any_of=None,
-                          none_of=None, include_seen: bool = False):
+                          none_of=None, include_seen: bool = False, log_prob: bool = False):
         """``Model.recommend_sampled_reps(self.representations(slots), k, ...)`` with the scan reading the store's rows in place and
         the seen-item memory excluded exactly as in ``recommend``; streams default to the slot ids, so a session's draw under one
         seed does not depend on who else is in the call."""
@@ -1078,7 +1184,27 @@ class Sessions:
                                                       None if ei is None else _ptr(ei), flags, C.byref(sa),
                                                       None if masks is None else _ptr(masks[0]), None if masks is None else _ptr(masks[1]),
                                                       _ptr(items), _ptr(scores), _ptr(keys)))
+        if log_prob:  # the draws' propensities: log_partition of the same arguments (Partition.slate_log_prob)
+            part = self.log_partition(sl, temperature, exclude=exclude, any_of=any_of, none_of=none_of, include_seen=include_seen)
+            return items, scores, keys, part.slate_log_prob(scores)
         return items, scores, keys
+
+    def log_partition(self, slots, temperature: float = 1.0, exclude=None, any_of=None, none_of=None,
+                      include_seen: bool = False) -> Partition:
+        """``Model.log_partition_reps(self.representations(slots), temperature, ...)`` with the scans reading the store's rows in
+        place and the seen-item memory excluded exactly as in ``recommend``."""
+        if include_seen and not self._seen:
+            raise ValueError("include_seen: this store has no seen-item memory (sessions(capacity, remember=W))")
+        flags = RECOMMEND_INCLUDE_HISTORY if include_seen else 0
+        sl = self._slots(slots)
+        masks = _tag_masks(any_of, none_of, sl.size)
+        shift, mass, fb = _partition_outputs(sl.size)
+        ep, ei = _exclusion_csr(exclude, sl.size)
+        _check(self._L.sbr_sessions_log_partition(self._h, _ptr(sl), sl.size, None if ep is None else _ptr(ep),
+                                                  None if ei is None else _ptr(ei), flags, float(np.float32(temperature)),
+                                                  None if masks is None else _ptr(masks[0]), None if masks is None else _ptr(masks[1]),
+                                                  _ptr(shift), _ptr(mass), C.byref(fb)))
+        return Partition(temperature, shift, mass, fb.value)
 
     def recommend_diverse(self, slots, k: int, pool: int, trade_off: float = 0.5, metric="cosine", exclude=None, any_of=None,
                           none_of=None):

@@ -269,23 +269,37 @@ class _ImplicitSequenceModel:
         return self.params.recommend_among(up, it, k, among, include_history=not exclude_history)
 
     def recommend_sampled(self, interactions_or_histories, k: int, temperature: float = 1.0, seed: int = 0, streams=None,
-                          exclude_history: bool = True, any_of=None, none_of=None):
+                          exclude_history: bool = True, any_of=None, none_of=None, log_prob: bool = False):
         """``recommend`` with a dice: k draws without replacement from softmax(score / ``temperature``) over the items each user
         may see, inside the catalogue scan — (items [U, k] u32, scores [U, k] f32: the plain scores of the drawn items in draw
         order, keys [U, k] f32 descending).  Exploration, slates that differ between visits, and reproducible randomised logging:
         the noise of a row is a function of (``seed``, ``streams[row]``, item) alone — ``streams`` one integer per row (a user or
         request id), default the row's index — so the same (seed, stream) gives the same row bit for bit.  Eligibility
-        (``exclude_history``, ``any_of`` / ``none_of``) is ``recommend``'s.  A small temperature approaches ``recommend``."""
+        (``exclude_history``, ``any_of`` / ``none_of``) is ``recommend``'s.  A small temperature approaches ``recommend``.
+        ``log_prob=True`` appends log_prob [U, k] f64, each draw's propensity given the draws before it (``log_partition``)."""
         up, it = self._csr(interactions_or_histories)
         return self.params.recommend_sampled(up, it, k, temperature=temperature, seed=seed, streams=streams,
-                                             include_history=not exclude_history, any_of=any_of, none_of=none_of)
+                                             include_history=not exclude_history, any_of=any_of, none_of=none_of, log_prob=log_prob)
 
     def recommend_sampled_reps(self, reps, k: int, temperature: float = 1.0, seed: int = 0, streams=None, exclude=None, any_of=None,
-                               none_of=None):
+                               none_of=None, log_prob: bool = False):
         """``recommend_sampled`` from representations [U, embedding_dim] (``user_representations``); ``exclude``: None or one
         sequence of item ids per user."""
         return self.params.recommend_sampled_reps(reps, k, temperature=temperature, seed=seed, streams=streams, exclude=exclude,
-                                                  any_of=any_of, none_of=none_of)
+                                                  any_of=any_of, none_of=none_of, log_prob=log_prob)
+
+    def log_partition(self, interactions_or_histories, temperature: float = 1.0, exclude_history: bool = True, any_of=None,
+                      none_of=None):
+        """The softmax normaliser of ``recommend_sampled``'s distribution, exactly: per user the mass of softmax(score /
+        ``temperature``) over the items ``recommend`` would choose from, summed on the device as integers in fixed point, so the
+        result does not depend on the batch or on how the scan is cut up (``engine.Partition``: ``shift``, ``mass``, ``frac_bits``,
+        ``log_z``, ``log_prob(scores)`` and ``slate_log_prob(scores)`` — the propensities that off-policy evaluation needs)."""
+        up, it = self._csr(interactions_or_histories)
+        return self.params.log_partition(up, it, temperature, include_history=not exclude_history, any_of=any_of, none_of=none_of)
+
+    def log_partition_reps(self, reps, temperature: float = 1.0, exclude=None, any_of=None, none_of=None):
+        """``log_partition`` from representations [U, embedding_dim]; ``exclude``: None or one sequence of item ids per user."""
+        return self.params.log_partition_reps(reps, temperature, exclude=exclude, any_of=any_of, none_of=none_of)
 
     def audience(self, interactions_or_histories, items, k: int, exclude_history: bool = True):
         """The reverse of ``recommend``: for each query item of ``items`` the k users whose histories score it highest, on the
