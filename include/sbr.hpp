@@ -570,6 +570,42 @@ struct Partition {
         return out;
     }
 };
+/// The order of each row of an Above: by score descending with ties to the lower id (the total order of every top-k call), or by
+/// ascending id (as the library writes it).
+enum class AboveOrder { Score, Id };
+/// What the *_above calls return (ABOVE in sbr_hip.h): every (row, id, score) pair whose score is >= the row's threshold, as CSR —
+/// row i's pairs are entries ptr[i] .. ptr[i + 1] of ids / scores.  A set, not a list of k: a row may hold far more than
+/// SBR_RECOMMEND_MAX_K entries.
+struct Above {
+    std::vector<std::uint64_t> ptr;  ///< [rows + 1]
+    std::vector<std::uint32_t> ids;
+    std::vector<float> scores;
+    AboveOrder order = AboveOrder::Score;
+    std::size_t rows() const { return ptr.empty() ? 0 : ptr.size() - 1; }
+    std::uint64_t count(std::size_t i) const { return ptr[i + 1] - ptr[i]; }
+    std::uint64_t total() const { return ptr.empty() ? 0 : ptr.back(); }
+    /// Rows in ascending id order -> score order: a stable sort on top of the id order (-0.0 and +0.0 tie), so ties go to the lower id.
+    void sort_by_score() {
+        std::vector<std::size_t> at;
+        std::vector<std::uint32_t> ti;
+        std::vector<float> ts;
+        for (std::size_t r = 0; r < rows(); ++r) {
+            const std::size_t a = (std::size_t)ptr[r], n = (std::size_t)(ptr[r + 1] - ptr[r]);
+            at.resize(n);
+            for (std::size_t j = 0; j < n; ++j) at[j] = j;
+            std::stable_sort(at.begin(), at.end(), [&](std::size_t x, std::size_t y) { return scores[a + x] > scores[a + y]; });
+            ti.assign(ids.begin() + (std::ptrdiff_t)a, ids.begin() + (std::ptrdiff_t)(a + n));
+            ts.assign(scores.begin() + (std::ptrdiff_t)a, scores.begin() + (std::ptrdiff_t)(a + n));
+            for (std::size_t j = 0; j < n; ++j) {
+                ids[a + j] = ti[at[j]];
+                scores[a + j] = ts[at[j]];
+            }
+        }
+        order = AboveOrder::Score;
+    }
+};
+/// The default max_results of the *_above calls: the entries of the one buffer they call with (2^24 pairs).
+constexpr std::uint64_t ABOVE_MAX_RESULTS = 1ull << 24;
 /// What ImplicitSequenceModel::similar_items ranks by: the cosine of two item embeddings, or their plain dot product.
 enum class Similarity { Cosine = SBR_SIMILAR_COSINE, Dot = SBR_SIMILAR_DOT };
 /// The loss used for training the model (mod.rs:15-23).
@@ -593,6 +629,47 @@ inline std::vector<std::uint32_t> tag_masks(const std::vector<std::uint32_t>& ma
     if (mask.size() > 1 && mask.size() != n) throw EngineError(SBR_ERR_INVALID_ARGUMENT, where);
     if (mask.size() == n && n > 0) return mask;
     return std::vector<std::uint32_t>(n ? n : 1, mask.empty() ? 0u : mask[0]);
+}
+
+/// The thresholds of an *_above call over n rows: one value for every row, or one per row; a NaN is refused.
+inline std::vector<float> above_thresholds(const std::vector<float>& t, std::size_t n, const char* where) {
+    if (t.size() != 1 && t.size() != n) throw EngineError(SBR_ERR_INVALID_ARGUMENT, where);
+    std::vector<float> out(n ? n : 1, t.empty() ? 0.0f : t[0]);
+    if (t.size() == n) std::copy(t.begin(), t.end(), out.begin());
+    for (float x : out)
+        if (std::isnan(x)) throw EngineError(SBR_ERR_INVALID_ARGUMENT, where);
+    return out;
+}
+/// The shared tail of the *_above methods.  call(out_counts, out_total, capacity, out_ids, out_scores) invokes the entry point with
+/// the method's leading arguments.  One call with buffers of max_results entries that are allocated but not touched; a total above
+/// max_results throws an EngineError that states the total, never a truncated result.  count_only: the counts alone (ids / scores
+/// stay empty), one scan.  Returns the call's status when it is SBR_ERR_INVALID_PREDICTION, for the caller's Result.
+template <class Call>
+inline sbr_status above_call(Call&& call, std::size_t n, std::uint64_t max_results, AboveOrder order, bool count_only, const char* where,
+                             Above* out) {
+    std::vector<std::uint64_t> counts(n ? n : 1, 0);
+    std::uint64_t total = 0;
+    std::unique_ptr<std::uint32_t[]> ids;
+    std::unique_ptr<float[]> scores;
+    if (!count_only) {
+        ids.reset(new std::uint32_t[max_results ? max_results : 1]);
+        scores.reset(new float[max_results ? max_results : 1]);
+    }
+    const sbr_status st = call(counts.data(), &total, count_only ? 0 : max_results, ids.get(), scores.get());
+    if (st == SBR_ERR_INVALID_PREDICTION) return st;
+    check(st, where);
+    if (!count_only && total > max_results)
+        throw EngineError(SBR_ERR_INVALID_ARGUMENT, std::string(where) + ": " + std::to_string(total) + " pairs pass the threshold, above max_results = " +
+                                                        std::to_string(max_results));
+    out->ptr.assign(n + 1, 0);
+    for (std::size_t i = 0; i < n; ++i) out->ptr[i + 1] = out->ptr[i] + counts[i];
+    out->order = AboveOrder::Id;
+    if (!count_only) {
+        out->ids.assign(ids.get(), ids.get() + total);
+        out->scores.assign(scores.get(), scores.get() + total);
+        if (order == AboveOrder::Score) out->sort_by_score();
+    }
+    return SBR_OK;
 }
 
 /// A SampleArgs as the struct a *_sampled call takes, over n rows; a non-empty `filter` vector as tag_masks makes it (null: none).
@@ -899,6 +976,73 @@ class Sessions {
         if (st == SBR_ERR_INVALID_PREDICTION) return Result<Recommendations, PredictionError>::Err(PredictionError::InvalidPredictionValue);
         check(st, "sbr_sessions_audience");
         return Result<Recommendations, PredictionError>::Ok(std::move(r));
+    }
+    /// `recommend` without a k (sbr_sessions_recommend_above): for each slot EVERY eligible item whose score is >= its threshold —
+    /// `thresholds`: one value for all slots or one per slot; ties at the bar all pass, -inf returns every eligible item.  Eligibility
+    /// (the lists, the filter, the seen-item memory unless `include_seen`) is `recommend`'s.  More than `max_results` pairs throw an
+    /// EngineError that states the total; `count_above` costs one scan and says how many to expect.
+    Result<Above, PredictionError> recommend_above(const std::vector<std::uint32_t>& slots, const std::vector<float>& thresholds,
+                                                   const TagFilter& filter = {}, const std::vector<std::uint64_t>& excl_ptr = {},
+                                                   const std::vector<std::uint32_t>& excl_items = {}, bool include_seen = false,
+                                                   std::uint64_t max_results = ABOVE_MAX_RESULTS, AboveOrder order = AboveOrder::Score,
+                                                   bool count_only = false) const {
+        if (!excl_ptr.empty() && (excl_ptr.size() != slots.size() + 1 || excl_ptr.back() > excl_items.size()))
+            throw EngineError(SBR_ERR_INVALID_ARGUMENT, "Sessions::recommend_above: one exclusion range per slot");
+        const bool filtered = !filter.any_of.empty() || !filter.none_of.empty();
+        const std::vector<std::uint32_t> any = tag_masks(filter.any_of, slots.size(), "Sessions::recommend_above: one any_of mask per slot");
+        const std::vector<std::uint32_t> none_of = tag_masks(filter.none_of, slots.size(), "Sessions::recommend_above: one none_of mask per slot");
+        const std::vector<float> th = detail::above_thresholds(thresholds, slots.size(), "Sessions::recommend_above: one threshold, or one per slot; no NaN");
+        const std::uint32_t none = 0;
+        Above r;
+        const sbr_status st = detail::above_call(
+            [&](std::uint64_t* counts, std::uint64_t* total, std::uint64_t cap, std::uint32_t* ids, float* scores) {
+                return sbr_sessions_recommend_above(h_, slots.data(), (std::uint64_t)slots.size(), th.data(), excl_ptr.empty() ? nullptr : excl_ptr.data(),
+                                                    excl_ptr.empty() ? nullptr : (excl_items.empty() ? &none : excl_items.data()),
+                                                    include_seen ? SBR_RECOMMEND_INCLUDE_HISTORY : 0u, filtered ? any.data() : nullptr,
+                                                    filtered ? none_of.data() : nullptr, counts, total, cap, ids, scores);
+            },
+            slots.size(), max_results, order, count_only, "sbr_sessions_recommend_above", &r);
+        if (st == SBR_ERR_INVALID_PREDICTION) return Result<Above, PredictionError>::Err(PredictionError::InvalidPredictionValue);
+        return Result<Above, PredictionError>::Ok(std::move(r));
+    }
+    /// The rows' counts of `recommend_above` (its `ptr`; `ids` / `scores` stay empty) without writing any pair: one scan.
+    Result<Above, PredictionError> count_above(const std::vector<std::uint32_t>& slots, const std::vector<float>& thresholds,
+                                               const TagFilter& filter = {}, const std::vector<std::uint64_t>& excl_ptr = {},
+                                               const std::vector<std::uint32_t>& excl_items = {}, bool include_seen = false) const {
+        return recommend_above(slots, thresholds, filter, excl_ptr, excl_items, include_seen, 0, AboveOrder::Id, true);
+    }
+    /// Who should hear about this item (sbr_sessions_audience_above): for each query item EVERY candidate slot whose state scores it
+    /// >= its threshold (`thresholds`: one for all queries or one per query) — `ids` of the result are SLOT ids.  Candidates, the
+    /// lists and the seen-item memory as in `audience`; no k.
+    Result<Above, PredictionError> audience_above(const std::vector<std::uint32_t>& items, const std::vector<float>& thresholds,
+                                                  const std::vector<std::uint32_t>& slots = {}, bool all_live_slots = true,
+                                                  const std::vector<std::uint64_t>& excl_ptr = {}, const std::vector<std::uint32_t>& excl_slots = {},
+                                                  bool include_seen = false, std::uint64_t max_results = ABOVE_MAX_RESULTS,
+                                                  AboveOrder order = AboveOrder::Score, bool count_only = false) const {
+        if (!excl_ptr.empty() && (excl_ptr.size() != items.size() + 1 || excl_ptr.back() > excl_slots.size()))
+            throw EngineError(SBR_ERR_INVALID_ARGUMENT, "Sessions::audience_above: one exclusion range per query");
+        if (all_live_slots && !slots.empty()) throw EngineError(SBR_ERR_INVALID_ARGUMENT, "Sessions::audience_above: slots together with all_live_slots");
+        const std::vector<float> th = detail::above_thresholds(thresholds, items.size(), "Sessions::audience_above: one threshold, or one per query; no NaN");
+        const std::uint32_t none = 0;
+        Above r;
+        const sbr_status st = detail::above_call(
+            [&](std::uint64_t* counts, std::uint64_t* total, std::uint64_t cap, std::uint32_t* ids, float* scores) {
+                return sbr_sessions_audience_above(h_, items.data(), (std::uint64_t)items.size(), th.data(),
+                                                   all_live_slots ? nullptr : (slots.empty() ? &none : slots.data()), (std::uint64_t)slots.size(),
+                                                   excl_ptr.empty() ? nullptr : excl_ptr.data(),
+                                                   excl_ptr.empty() ? nullptr : (excl_slots.empty() ? &none : excl_slots.data()),
+                                                   include_seen ? SBR_RECOMMEND_INCLUDE_HISTORY : 0u, counts, total, cap, ids, scores);
+            },
+            items.size(), max_results, order, count_only, "sbr_sessions_audience_above", &r);
+        if (st == SBR_ERR_INVALID_PREDICTION) return Result<Above, PredictionError>::Err(PredictionError::InvalidPredictionValue);
+        return Result<Above, PredictionError>::Ok(std::move(r));
+    }
+    /// The rows' counts of `audience_above` without writing any pair: one scan.
+    Result<Above, PredictionError> count_audience_above(const std::vector<std::uint32_t>& items, const std::vector<float>& thresholds,
+                                                        const std::vector<std::uint32_t>& slots = {}, bool all_live_slots = true,
+                                                        const std::vector<std::uint64_t>& excl_ptr = {},
+                                                        const std::vector<std::uint32_t>& excl_slots = {}, bool include_seen = false) const {
+        return audience_above(items, thresholds, slots, all_live_slots, excl_ptr, excl_slots, include_seen, 0, AboveOrder::Id, true);
     }
     /// One score per candidate, in candidate order, slot i's candidates cand_items[cand_ptr[i] .. cand_ptr[i + 1]) (sbr_sessions_score_candidates).
     Result<std::vector<float>, PredictionError> score_candidates(const std::vector<std::uint32_t>& slots, const std::vector<std::uint64_t>& cand_ptr,
@@ -1332,6 +1476,131 @@ class ImplicitSequenceModel : public OnlineRankingModel<ImplicitUser> {
         if (st == SBR_ERR_INVALID_PREDICTION) return Result<Recommendations, PredictionError>::Err(PredictionError::InvalidPredictionValue);
         check(st, "sbr_audience");
         return Result<Recommendations, PredictionError>::Ok(std::move(r));
+    }
+
+    /// `recommend` without a k (sbr_recommend_above): for each user's history EVERY eligible item whose score is >= its threshold
+    /// — `thresholds`: one value for all users or one per user; the f32 compare, so ties at the bar all pass, -0.0 == +0.0, -inf
+    /// returns every eligible item and +inf none.  An Above over the users, item ids with `predict`'s score bits, each row by score
+    /// descending with ties to the lower id (AboveOrder::Id: ascending id): with the threshold at `recommend(k)`'s k-th score a row
+    /// starts with that call's row.  Eligibility (`exclude_history`, `filter`) is `recommend`'s.  More than `max_results` pairs throw
+    /// an EngineError that states the total; `count_above` costs one scan and says how many to expect.
+    Result<Above, PredictionError> recommend_above(const data::CompressedInteractions& interactions, const std::vector<float>& thresholds,
+                                                   bool exclude_history = true, const TagFilter& filter = {},
+                                                   std::uint64_t max_results = ABOVE_MAX_RESULTS, AboveOrder order = AboveOrder::Score,
+                                                   bool count_only = false) const {
+        const std::size_t n = interactions.num_users();
+        const bool filtered = !filter.any_of.empty() || !filter.none_of.empty();
+        const std::vector<std::uint32_t> any = tag_masks(filter.any_of, n, "recommend_above: one any_of mask per user");
+        const std::vector<std::uint32_t> none_of = tag_masks(filter.none_of, n, "recommend_above: one none_of mask per user");
+        const std::vector<float> th = detail::above_thresholds(thresholds, n, "recommend_above: one threshold, or one per user; no NaN");
+        Above r;
+        const sbr_status st = detail::above_call(
+            [&](std::uint64_t* counts, std::uint64_t* total, std::uint64_t cap, std::uint32_t* ids, float* scores) {
+                return sbr_recommend_above(replicas_->primary(), interactions.user_pointers().data(), interactions.item_ids().data(), (std::uint64_t)n,
+                                           th.data(), exclude_history ? 0u : SBR_RECOMMEND_INCLUDE_HISTORY, filtered ? any.data() : nullptr,
+                                           filtered ? none_of.data() : nullptr, counts, total, cap, ids, scores);
+            },
+            n, max_results, order, count_only, "sbr_recommend_above", &r);
+        if (st == SBR_ERR_INVALID_PREDICTION) return Result<Above, PredictionError>::Err(PredictionError::InvalidPredictionValue);
+        return Result<Above, PredictionError>::Ok(std::move(r));
+    }
+    /// The rows' counts of `recommend_above` (its `ptr`; `ids` / `scores` stay empty) without writing any pair: one scan.
+    Result<Above, PredictionError> count_above(const data::CompressedInteractions& interactions, const std::vector<float>& thresholds,
+                                               bool exclude_history = true, const TagFilter& filter = {}) const {
+        return recommend_above(interactions, thresholds, exclude_history, filter, 0, AboveOrder::Id, true);
+    }
+    /// recommend_above from representations, reps [num_users][embedding_dim] (sbr_recommend_above_reps); excl_ptr / excl_items:
+    /// per-user exclusion lists as a CSR (both empty: none).
+    Result<Above, PredictionError> recommend_above_reps(const std::vector<float>& reps, const std::vector<float>& thresholds,
+                                                        const std::vector<std::uint64_t>& excl_ptr = {},
+                                                        const std::vector<std::uint32_t>& excl_items = {}, const TagFilter& filter = {},
+                                                        std::uint64_t max_results = ABOVE_MAX_RESULTS, AboveOrder order = AboveOrder::Score,
+                                                        bool count_only = false) const {
+        const std::size_t dim = (std::size_t)replicas_->hparams().embedding_dim;
+        if (reps.size() % dim) throw EngineError(SBR_ERR_INVALID_ARGUMENT, "recommend_above_reps: rows of embedding_dim floats");
+        const std::size_t n = reps.size() / dim;
+        if (!excl_ptr.empty() && (excl_ptr.size() != n + 1 || excl_ptr.back() > excl_items.size()))
+            throw EngineError(SBR_ERR_INVALID_ARGUMENT, "recommend_above_reps: one exclusion range per user");
+        const bool filtered = !filter.any_of.empty() || !filter.none_of.empty();
+        const std::vector<std::uint32_t> any = tag_masks(filter.any_of, n, "recommend_above_reps: one any_of mask per user");
+        const std::vector<std::uint32_t> none_of = tag_masks(filter.none_of, n, "recommend_above_reps: one none_of mask per user");
+        const std::vector<float> th = detail::above_thresholds(thresholds, n, "recommend_above_reps: one threshold, or one per user; no NaN");
+        const std::uint32_t none = 0;
+        const float zero = 0.0f;
+        Above r;
+        const sbr_status st = detail::above_call(
+            [&](std::uint64_t* counts, std::uint64_t* total, std::uint64_t cap, std::uint32_t* ids, float* scores) {
+                return sbr_recommend_above_reps(replicas_->primary(), reps.empty() ? &zero : reps.data(), (std::uint64_t)n, th.data(),
+                                                excl_ptr.empty() ? nullptr : excl_ptr.data(),
+                                                excl_ptr.empty() ? nullptr : (excl_items.empty() ? &none : excl_items.data()),
+                                                filtered ? any.data() : nullptr, filtered ? none_of.data() : nullptr, counts, total, cap, ids, scores);
+            },
+            n, max_results, order, count_only, "sbr_recommend_above_reps", &r);
+        if (st == SBR_ERR_INVALID_PREDICTION) return Result<Above, PredictionError>::Err(PredictionError::InvalidPredictionValue);
+        return Result<Above, PredictionError>::Ok(std::move(r));
+    }
+    /// The rows' counts of `recommend_above_reps` without writing any pair: one scan.
+    Result<Above, PredictionError> count_above_reps(const std::vector<float>& reps, const std::vector<float>& thresholds,
+                                                    const std::vector<std::uint64_t>& excl_ptr = {},
+                                                    const std::vector<std::uint32_t>& excl_items = {}, const TagFilter& filter = {}) const {
+        return recommend_above_reps(reps, thresholds, excl_ptr, excl_items, filter, 0, AboveOrder::Id, true);
+    }
+    /// `audience_reps` without a k (sbr_audience_above_reps): for each query item EVERY row of `reps` that scores it >= its threshold
+    /// (`thresholds`: one for all queries or one per query) — `ids` of the result are ROW indices.
+    Result<Above, PredictionError> audience_above_reps(const std::vector<float>& reps, const std::vector<ItemId>& items,
+                                                       const std::vector<float>& thresholds, const std::vector<std::uint64_t>& excl_ptr = {},
+                                                       const std::vector<std::uint32_t>& excl_rows = {},
+                                                       std::uint64_t max_results = ABOVE_MAX_RESULTS, AboveOrder order = AboveOrder::Score,
+                                                       bool count_only = false) const {
+        const std::size_t dim = (std::size_t)replicas_->hparams().embedding_dim;
+        if (reps.size() % dim) throw EngineError(SBR_ERR_INVALID_ARGUMENT, "audience_above_reps: rows of embedding_dim floats");
+        if (!excl_ptr.empty() && (excl_ptr.size() != items.size() + 1 || excl_ptr.back() > excl_rows.size()))
+            throw EngineError(SBR_ERR_INVALID_ARGUMENT, "audience_above_reps: one exclusion range per query");
+        const std::vector<std::uint32_t> q = narrow(items);
+        const std::vector<float> th = detail::above_thresholds(thresholds, q.size(), "audience_above_reps: one threshold, or one per query; no NaN");
+        const std::uint32_t none = 0;
+        const float zero = 0.0f;
+        Above r;
+        const sbr_status st = detail::above_call(
+            [&](std::uint64_t* counts, std::uint64_t* total, std::uint64_t cap, std::uint32_t* ids, float* scores) {
+                return sbr_audience_above_reps(replicas_->primary(), reps.empty() ? &zero : reps.data(), (std::uint64_t)(reps.size() / dim), q.data(),
+                                               (std::uint64_t)q.size(), th.data(), excl_ptr.empty() ? nullptr : excl_ptr.data(),
+                                               excl_ptr.empty() ? nullptr : (excl_rows.empty() ? &none : excl_rows.data()), counts, total, cap, ids,
+                                               scores);
+            },
+            q.size(), max_results, order, count_only, "sbr_audience_above_reps", &r);
+        if (st == SBR_ERR_INVALID_PREDICTION) return Result<Above, PredictionError>::Err(PredictionError::InvalidPredictionValue);
+        return Result<Above, PredictionError>::Ok(std::move(r));
+    }
+    /// The rows' counts of `audience_above_reps` without writing any pair: one scan.
+    Result<Above, PredictionError> count_audience_above_reps(const std::vector<float>& reps, const std::vector<ItemId>& items,
+                                                             const std::vector<float>& thresholds, const std::vector<std::uint64_t>& excl_ptr = {},
+                                                             const std::vector<std::uint32_t>& excl_rows = {}) const {
+        return audience_above_reps(reps, items, thresholds, excl_ptr, excl_rows, 0, AboveOrder::Id, true);
+    }
+    /// `audience_above_reps` on `user_representations` of `histories` (sbr_audience_above): `ids` of the result are USER indices.
+    /// With `exclude_history` a user whose history holds the query item is left out of that item's row.
+    Result<Above, PredictionError> audience_above(const data::CompressedInteractions& histories, const std::vector<ItemId>& items,
+                                                  const std::vector<float>& thresholds, bool exclude_history = true,
+                                                  std::uint64_t max_results = ABOVE_MAX_RESULTS, AboveOrder order = AboveOrder::Score,
+                                                  bool count_only = false) const {
+        const std::vector<std::uint32_t> q = narrow(items);
+        const std::vector<float> th = detail::above_thresholds(thresholds, q.size(), "audience_above: one threshold, or one per query; no NaN");
+        Above r;
+        const sbr_status st = detail::above_call(
+            [&](std::uint64_t* counts, std::uint64_t* total, std::uint64_t cap, std::uint32_t* ids, float* scores) {
+                return sbr_audience_above(replicas_->primary(), histories.user_pointers().data(), histories.item_ids().data(),
+                                          (std::uint64_t)histories.num_users(), q.data(), (std::uint64_t)q.size(), th.data(),
+                                          exclude_history ? 0u : SBR_RECOMMEND_INCLUDE_HISTORY, counts, total, cap, ids, scores);
+            },
+            q.size(), max_results, order, count_only, "sbr_audience_above", &r);
+        if (st == SBR_ERR_INVALID_PREDICTION) return Result<Above, PredictionError>::Err(PredictionError::InvalidPredictionValue);
+        return Result<Above, PredictionError>::Ok(std::move(r));
+    }
+    /// The rows' counts of `audience_above` without writing any pair.
+    Result<Above, PredictionError> count_audience_above(const data::CompressedInteractions& histories, const std::vector<ItemId>& items,
+                                                        const std::vector<float>& thresholds, bool exclude_history = true) const {
+        return audience_above(histories, items, thresholds, exclude_history, 0, AboveOrder::Id, true);
     }
 
     /// `predict` for many users in one device pass (sbr_score_candidates): user u's history is row u of `histories`, its

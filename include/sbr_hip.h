@@ -805,6 +805,50 @@ sbr_status sbr_sessions_audience(sbr_sessions* st, const uint32_t* items, uint64
                                  uint64_t num_slots, const uint64_t* excl_ptr, const uint32_t* excl_slots, uint32_t flags, uint32_t* out_slots,
                                  float* out_scores);
 
+/* ABOVE — the threshold form of the scans: for each row r and a per-row f32 threshold t = thresholds[r], EVERY scanned column whose
+ * score satisfies score >= t — a set, not a list of k, so neither SBR_RECOMMEND_MAX_K nor any other k applies.  A row is a user,
+ * a representation or a slot and a column an item (sbr_recommend_above*), or a row is a query item and a column a candidate row, user
+ * or slot (sbr_audience_above*).  Each call takes the arguments of its top-k sibling with k replaced by thresholds [rows]:
+ *   columns   exactly those the sibling would choose from: not in the row's exclusion list (any order, repeats allowed), allowed by
+ *             the row's tag masks (the recommend forms; any_of / none_of both NULL: no filter and no tags needed), and on a store
+ *             with memory not in the seen ring unless flags has SBR_RECOMMEND_INCLUDE_HISTORY
+ *   scores    the bits of sbr_predict / sbr_score_candidates for the pair
+ *   compare   the f32 compare, the rank rule of sbr_mrr_score and sbr_rank_targets: -0.0 and +0.0 are equal, ties at the threshold
+ *             are all included; t = -inf returns every allowed column, t = +inf none
+ * The result is CSR.  out_counts [rows] (required) receives each row's number of pairs and *out_total (required) their sum.  Row
+ * r's pairs are entries [sum of out_counts before r, + out_counts[r]) of out_ids / out_scores, in ASCENDING id order (the set's
+ * natural order, which the kernel produces by construction; include/sbr.hpp and the Python layer sort a row by score on the host).
+ * out_ids and out_scores both NULL: counts only — one scan, the cheap way to choose a threshold or size a buffer; with empty
+ * masks and no exclusions out_counts[r] is sbr_rank_targets' rank of an item that scores exactly t.  out_scores alone may be NULL.
+ * Pairs are written only if *out_total <= capacity (entries of out_ids / out_scores).  Otherwise the call still returns SBR_OK with
+ * the counts and the total — that is how a caller sizes a second call — and writes no pair; for a call of at most 8 192 rows the two
+ * arrays are then untouched (a longer call runs in chunks of 8 192 rows and may have written the chunks that still fitted).
+ * rows == 0, or nothing to scan, is SBR_OK with zero counts.
+ * SBR_ERR_INVALID_ARGUMENT, before any launch: a NaN threshold, a NULL out_counts / out_total / thresholds, out_scores without
+ * out_ids, and wherever the sibling gives it.  SBR_ERR_INVALID_PREDICTION: a non-finite score of any scanned pair of an existing
+ * row, as in sbr_recommend.  Deterministic; reads parameters only.
+ * Not offered: a device-side sort by score, among= subsets, thresholds on sbr_similar_items or on sampled keys, a tag filter in the
+ * audience orientation. */
+sbr_status sbr_recommend_above(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users, const float* thresholds,
+                               uint32_t flags, const uint32_t* any_of, const uint32_t* none_of, uint64_t* out_counts, uint64_t* out_total,
+                               uint64_t capacity, uint32_t* out_ids, float* out_scores);
+sbr_status sbr_recommend_above_reps(sbr_model* m, const float* reps, uint64_t num_users, const float* thresholds, const uint64_t* excl_ptr,
+                                    const uint32_t* excl_items, const uint32_t* any_of, const uint32_t* none_of, uint64_t* out_counts,
+                                    uint64_t* out_total, uint64_t capacity, uint32_t* out_ids, float* out_scores);
+sbr_status sbr_sessions_recommend_above(sbr_sessions* st, const uint32_t* slots, uint64_t n, const float* thresholds, const uint64_t* excl_ptr,
+                                        const uint32_t* excl_items, uint32_t flags, const uint32_t* any_of, const uint32_t* none_of,
+                                        uint64_t* out_counts, uint64_t* out_total, uint64_t capacity, uint32_t* out_ids, float* out_scores);
+sbr_status sbr_audience_above_reps(sbr_model* m, const float* reps, uint64_t num_rows, const uint32_t* items, uint64_t num_queries,
+                                   const float* thresholds, const uint64_t* excl_ptr, const uint32_t* excl_rows, uint64_t* out_counts,
+                                   uint64_t* out_total, uint64_t capacity, uint32_t* out_ids, float* out_scores);
+sbr_status sbr_audience_above(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users, const uint32_t* items,
+                              uint64_t num_queries, const float* thresholds, uint32_t flags, uint64_t* out_counts, uint64_t* out_total,
+                              uint64_t capacity, uint32_t* out_ids, float* out_scores);
+sbr_status sbr_sessions_audience_above(sbr_sessions* st, const uint32_t* items, uint64_t num_queries, const float* thresholds,
+                                       const uint32_t* slots, uint64_t num_slots, const uint64_t* excl_ptr, const uint32_t* excl_slots,
+                                       uint32_t flags, uint64_t* out_counts, uint64_t* out_total, uint64_t capacity, uint32_t* out_ids,
+                                       float* out_scores);
+
 /* ≙ the serde derives (lstm.rs:204,386; ewma.rs:208,401): element counts and raw access. */
 sbr_status sbr_model_param_count(const sbr_model* m, int32_t which, uint64_t* out_count);
 sbr_status sbr_model_get_param(sbr_model* m, int32_t which, float* host_out, uint64_t count);

@@ -175,6 +175,12 @@ def load():
         "sbr_log_partition": [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_float, vp, vp, vp, vp, vp],
         "sbr_log_partition_reps": [vp, vp, C.c_uint64, vp, vp, C.c_float, vp, vp, vp, vp, vp],
         "sbr_sessions_log_partition": [vp, vp, C.c_uint64, vp, vp, C.c_uint32, C.c_float, vp, vp, vp, vp, vp],
+        "sbr_recommend_above": [vp, vp, vp, C.c_uint64, vp, C.c_uint32, vp, vp, vp, u64p, C.c_uint64, vp, vp],
+        "sbr_recommend_above_reps": [vp, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, u64p, C.c_uint64, vp, vp],
+        "sbr_sessions_recommend_above": [vp, vp, C.c_uint64, vp, vp, vp, C.c_uint32, vp, vp, vp, u64p, C.c_uint64, vp, vp],
+        "sbr_audience_above_reps": [vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp, vp, vp, u64p, C.c_uint64, vp, vp],
+        "sbr_audience_above": [vp, vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint32, vp, u64p, C.c_uint64, vp, vp],
+        "sbr_sessions_audience_above": [vp, vp, C.c_uint64, vp, vp, C.c_uint64, vp, vp, C.c_uint32, vp, u64p, C.c_uint64, vp, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -237,4 +243,6 @@ DECLARED_SYMBOLS = [
     "sbr_sessions_replay",
     "sbr_recommend_sampled", "sbr_recommend_sampled_reps", "sbr_sessions_recommend_sampled",
     "sbr_softmax_frac_bits", "sbr_softmax_weights", "sbr_softmax_weights_rows", "sbr_log_partition", "sbr_log_partition_reps", "sbr_sessions_log_partition",
+    "sbr_recommend_above", "sbr_recommend_above_reps", "sbr_sessions_recommend_above",
+    "sbr_audience_above_reps", "sbr_audience_above", "sbr_sessions_audience_above",
 ]

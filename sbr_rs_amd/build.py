@@ -189,6 +189,15 @@ def build_partition_tests(force: bool = False, verbose: bool = True) -> str:
     return _build_cpp_program(PARTITION_SRC, PARTITION_BIN, force, verbose)
 
 
+ABOVE_SRC = os.path.join(REPO, "tests", "cpp", "above_tests.cpp")
+ABOVE_BIN = os.path.join(REPO, "tests", "cpp", "_build", "above_tests")
+
+
+def build_above_tests(force: bool = False, verbose: bool = True) -> str:
+    """g++ build of the C++ host layer's recommend_above / audience_above test program."""
+    return _build_cpp_program(ABOVE_SRC, ABOVE_BIN, force, verbose)
+
+
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv))
     print(build_facade_tests(force="--force" in sys.argv))
@@ -204,3 +213,4 @@ if __name__ == "__main__":
     print(build_audience_tests(force="--force" in sys.argv))
     print(build_sampled_tests(force="--force" in sys.argv))
     print(build_partition_tests(force="--force" in sys.argv))
+    print(build_above_tests(force="--force" in sys.argv))

@@ -907,7 +907,7 @@ __global__ __launch_bounds__(256, D <= 128 ? 2 : 1) void topk_gemm_kernel(ModelV
     }
     if (__any(bad) && lane == 0) atomicOr(nonfinite_flag, 1u);
 }
-#undef TK_SCORE
+/* TK_SCORE stays defined up to above_gemm_kernel, the other kernel that states a score by policy */
 
 /* The G sorted lists of one user -> its k best, by a bitonic sort of all their entries in LDS (n = power of two >= G k, at most
  * TK_MERGE_MAX entries; empty slots hold the padding pair, which sorts last). */
@@ -1456,6 +1456,262 @@ __global__ __launch_bounds__(64) void partition_finish_kernel(ModelView m, const
 }
 
 // ------------------------------------------------------------------------------------------------
+// recommend_above / audience_above: every scanned column at or over a per-row score — the catalogue scan with an epilogue that
+// counts, then (a second launch) writes
+// ------------------------------------------------------------------------------------------------
+/* partition_gemm_kernel's shape: 128 rows per workgroup, grid (row tiles, item ranges).  The rows' thresholds sit in LDS by slot
+ * (slot_user; +inf for a row that does not exist: nothing passes), their exclusion segments' bounds beside them.  `passes` is the one
+ * statement of what a tile contributes, used by both modes — the fill is only correct if it passes exactly what the count passed:
+ *   1. the non-finite test on every scanned score of an existing row (it fails the call, as in topk_gemm_kernel);
+ *   2. score >= threshold, the f32 compare (-0.0 >= +0.0 holds; the host refuses a NaN threshold);
+ *   3. the tag test (TagFilter, as topk_gemm_kernel's);
+ *   4. only for survivors, the binary search of the row's non-decreasing exclusion segment, as merge_staged does it.
+ * Fill = false: 16 per-lane counters; at the range's end the 32 item lanes of a half-wave are summed and ONE value is stored to
+ *   counts[row * G + range], a slot only this workgroup owns — no atomics, nothing to zero.
+ * Fill = true: accumulator register q has a cursor that belongs to its half-wave alone and starts at offsets[row * G + range] (less
+ *   the launch's base, offsets[0]: a launch writes fewer than 2^32 entries).  Per tile, for each q with a survivor, the half-wave's
+ *   32 ballot bits place a passing lane at cursor + popcount(bits below it) and advance the cursor by their popcount.  Tiles ascend
+ *   within a range and a row's ranges own consecutive slots, so a row's entries ascend by column whatever order the workgroups run
+ *   in.  The cursors live in LDS by slot, each read by its half-wave's 32 lanes and then advanced by its lane 0: held in 16 registers
+ *   per lane through the unrolled writes they took the d = 128 kernel to 256 VGPRs and 84 bytes of scratch, in LDS it needs 170 and
+ *   none.  Every write is checked against the slot's end (offsets[row * G + range + 1], and the buffer's size): a pass beyond it is
+ *   dropped and raises *overrun_flag — a disagreement between the two launches becomes an error, never a store out of bounds. */
+template <int D, class Score, class Filter, bool Fill>
+__global__ __launch_bounds__(256, D <= 128 ? 2 : 1) void above_gemm_kernel(ModelView m, const float* reps, const int* rep_row, uint32_t num_users,
+                                                                          const float* thresholds, const uint64_t* excl_ptr,
+                                                                          const uint32_t* excl_items, uint32_t items_per_group, uint32_t* counts,
+                                                                          const uint64_t* offsets, uint32_t* out_ids, float* out_scores,
+                                                                          uint32_t out_cap, uint32_t* overrun_flag, uint32_t* nonfinite_flag,
+                                                                          typename Filter::Args fa, typename Score::Args sa) {
+    __shared__ float Es[2][32 * ItemTiles<D>::LDE];
+    __shared__ float Bs[2][32];
+    __shared__ __align__(16) float qbS[Score::query ? 128 : 4]; /* QueryBias only: the queries' biases by slot (slot_user) */
+    __shared__ uint32_t Ts[2][Filter::on ? 32 : 1];
+    __shared__ __align__(16) uint32_t anyS[Filter::on ? 128 : 4];
+    __shared__ __align__(16) uint32_t anyZ[Filter::on ? 128 : 4]; /* 1 where the user's any_of is 0 (every tag passes it), else 0 */
+    __shared__ __align__(16) uint32_t noneS[Filter::on ? 128 : 4];
+    // per-row state by slot (slot_user)
+    __shared__ __align__(16) float thS[128];
+    __shared__ uint64_t exLo[128]; /* the row's exclusion segment [exLo, exHi) of excl_items; empty without lists */
+    __shared__ uint64_t exHi[128];
+    __shared__ __align__(16) uint32_t endS[Fill ? 128 : 4]; /* Fill: the end of the row's slot for this range, relative to the launch's base ... */
+    __shared__ __align__(16) uint32_t curS[Fill ? 128 : 4]; /* ... and its cursor, which only the slot's own half-wave reads and advances */
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = tid >> 6;
+    const int l31 = lane & 31;
+    const int hh = lane >> 5;
+    const uint32_t G = gridDim.y;
+    const uint32_t u0 = blockIdx.x * 128 + wave * 32;
+    float a[D / 2];
+    load_user_fragments<D>(a, reps, rep_row, num_users, u0);
+    if (tid < 128) {
+        const uint32_t u = blockIdx.x * 128 + (uint32_t)slot_user(tid);
+        const bool real = u < num_users;
+        thS[tid] = real ? thresholds[u] : INFINITY;
+        exLo[tid] = real && excl_ptr ? excl_ptr[u] : 0ull;
+        exHi[tid] = real && excl_ptr ? excl_ptr[u + 1] : 0ull;
+        if constexpr (Fill) {
+            uint64_t e = real ? offsets[(size_t)u * G + blockIdx.y + 1] - offsets[0] : 0ull;
+            if (e > (uint64_t)out_cap) e = out_cap;
+            endS[tid] = (uint32_t)e;
+            const uint64_t c = real ? offsets[(size_t)u * G + blockIdx.y] - offsets[0] : 0ull;
+            curS[tid] = c < 0xFFFFFFFFull ? (uint32_t)c : 0xFFFFFFFFu;
+        }
+        if constexpr (Filter::on) {
+            const uint32_t any = real ? fa.any_of[u] : 0u;
+            anyS[tid] = any;
+            anyZ[tid] = any == 0u ? 1u : 0u;
+            noneS[tid] = real ? fa.none_of[u] : 0u;
+        }
+        if constexpr (Score::query) qbS[tid] = real ? sa.qb[rep_row[u]] : 0.0f;
+    }
+    uint32_t umask = 0; /* accumulator registers q whose user exists */
+#pragma unroll
+    for (int q = 0; q < 16; ++q)
+        if (acc_user(u0, q, hh) < num_users) umask |= 1u << q;
+    uint32_t cnt[Fill ? 1 : 16]; /* Fill = false: the lane's counts */
+#pragma unroll
+    for (int q = 0; q < (Fill ? 1 : 16); ++q) cnt[q] = 0u;
+    bool bad = false, over = false;
+    ItemTiles<D> tiles(m, items_per_group);
+    const int ntiles = tiles.ntiles;
+    if (ntiles > 0) {
+        tiles.fetch(m, 0);
+        tiles.stage(Es[0], Bs[0]);
+        if constexpr (Filter::on) {
+            tiles.fetch_tags(fa.tags, 0);
+            tiles.stage_tags(Ts[0]);
+        }
+    }
+    __syncthreads();
+    const int pbase = wave * 32 + hh * 16;
+    /* the accumulator registers q of this lane's column `id` that pass their rows: THE pass predicate of both modes */
+    auto passes = [&](const f32x16& acc, float bias, uint32_t id, int buf) -> uint32_t {
+        uint32_t pend = id < tiles.i_end ? umask : 0u;
+#pragma unroll
+        for (int q4 = 0; q4 < 4; ++q4) {
+            const float4 t4 = ld4(&thS[pbase + 4 * q4]);
+            const float tq[4] = {t4.x, t4.y, t4.z, t4.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int q = 4 * q4 + j;
+                const float sc = TK_SCORE(q);
+                if (((pend >> q) & 1u) && !(sc - sc == 0.0f)) bad = true;
+                if (!(sc >= tq[j])) pend &= ~(1u << q); /* a non-finite score passes nothing it should not: the call fails */
+            }
+        }
+        if constexpr (Filter::on) { /* the lane's item against its 16 users' masks, as topk_gemm_kernel's */
+            const uint32_t tag = Ts[buf][l31];
+            uint32_t drop = 0;
+#pragma unroll
+            for (int q4 = 0; q4 < 4; ++q4) {
+                const uint4 a4 = *reinterpret_cast<const uint4*>(&anyS[pbase + 4 * q4]);
+                const uint4 z4 = *reinterpret_cast<const uint4*>(&anyZ[pbase + 4 * q4]);
+                const uint4 n4 = *reinterpret_cast<const uint4*>(&noneS[pbase + 4 * q4]);
+                const uint32_t any[4] = {a4.x, a4.y, a4.z, a4.w};
+                const uint32_t anyz[4] = {z4.x, z4.y, z4.z, z4.w};
+                const uint32_t none[4] = {n4.x, n4.y, n4.z, n4.w};
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const uint32_t hit = (tag & none[j]) != 0u ? 1u : 0u;
+                    const uint32_t miss = ((tag & any[j]) | anyz[j]) == 0u ? 1u : 0u;
+                    drop |= (hit | miss) << (4 * q4 + j);
+                }
+            }
+            pend &= ~drop;
+        }
+        if (excl_ptr) { /* the survivors against their rows' lists: few where the threshold is selective */
+            for (uint32_t rem = pend; rem; rem &= rem - 1u) {
+                const int q = __ffs((int)rem) - 1;
+                uint64_t lo = exLo[pbase + q];
+                const uint64_t e1 = exHi[pbase + q];
+                uint64_t hi = e1;
+                while (lo < hi) {
+                    const uint64_t mid = (lo + hi) >> 1;
+                    if (excl_items[mid] < id) lo = mid + 1; else hi = mid;
+                }
+                if (lo < e1 && excl_items[lo] == id) pend &= ~(1u << q);
+            }
+        }
+        return pend;
+    };
+    for (int tile = 0; tile < ntiles; ++tile) {
+        const int buf = tile & 1;
+        if (tile + 1 < ntiles) {
+            tiles.fetch(m, tile + 1);
+            if constexpr (Filter::on) tiles.fetch_tags(fa.tags, tile + 1);
+        }
+        f32x16 acc = tile_dots<D>(a, Es[buf]);
+        const float bias = Bs[buf][l31];
+        if constexpr (Score::query) { /* the score is b[q] + dot, one rounding, as predict's; acc[q] holds it from here on */
+#pragma unroll
+            for (int q4 = 0; q4 < 4; ++q4) {
+                const float4 b4 = ld4(&qbS[pbase + 4 * q4]);
+                acc[4 * q4 + 0] = b4.x + acc[4 * q4 + 0];
+                acc[4 * q4 + 1] = b4.y + acc[4 * q4 + 1];
+                acc[4 * q4 + 2] = b4.z + acc[4 * q4 + 2];
+                acc[4 * q4 + 3] = b4.w + acc[4 * q4 + 3];
+            }
+        }
+        const uint32_t id = tiles.i_begin + (uint32_t)tile * 32 + (uint32_t)l31;
+        const uint32_t pend = passes(acc, bias, id, buf);
+        if constexpr (!Fill) {
+#pragma unroll
+            for (int q = 0; q < 16; ++q) cnt[q] += (pend >> q) & 1u;
+        } else {
+            if (__any(pend != 0u)) {
+                /* four rows at a time: their cursors and ends in two 16-byte reads, the writes, the cursors back in one 16-byte
+                 * write by the half-wave's lane 0.  One wave's LDS accesses complete in program order, so every lane has its
+                 * cursors before lane 0 advances them; the fence below orders the tile's updates ahead of the next tile's reads. */
+#pragma unroll
+                for (int q4 = 0; q4 < 4; ++q4) {
+                    if (__ballot(((pend >> (4 * q4)) & 0xFu) != 0u) == 0ull) continue; /* wave-uniform */
+                    const uint4 c4 = *reinterpret_cast<const uint4*>(&curS[pbase + 4 * q4]);
+                    const uint4 e4 = *reinterpret_cast<const uint4*>(&endS[pbase + 4 * q4]);
+                    uint32_t c[4] = {c4.x, c4.y, c4.z, c4.w};
+                    const uint32_t e[4] = {e4.x, e4.y, e4.z, e4.w};
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const int q = 4 * q4 + j;
+                        const bool p = ((pend >> q) & 1u) != 0u;
+                        const uint64_t b = __ballot(p);
+                        const uint32_t bits = hh ? (uint32_t)(b >> 32) : (uint32_t)b;
+                        if (p) {
+                            const uint64_t pos = (uint64_t)c[j] + (uint32_t)__popc(bits & ((1u << l31) - 1u));
+                            if (pos < (uint64_t)e[j]) {
+                                out_ids[pos] = id;
+                                if (out_scores) out_scores[pos] = TK_SCORE(q);
+                            } else
+                                over = true;
+                        }
+                        const uint32_t adv = (uint32_t)__popc(bits);
+                        c[j] = c[j] > 0xFFFFFFFFu - adv ? 0xFFFFFFFFu : c[j] + adv;
+                    }
+                    if (l31 == 0) *reinterpret_cast<uint4*>(&curS[pbase + 4 * q4]) = make_uint4(c[0], c[1], c[2], c[3]);
+                }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            }
+        }
+        if (tile + 1 < ntiles) {
+            tiles.stage(Es[buf ^ 1], Bs[buf ^ 1]);
+            if constexpr (Filter::on) tiles.stage_tags(Ts[buf ^ 1]);
+        }
+        __syncthreads();
+    }
+    if constexpr (!Fill) {
+        // per-row counts of the range: sum over the 32 item lanes of each half-wave, one plain store per (row, range)
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            int c = (int)cnt[q];
+#pragma unroll
+            for (int off = 16; off >= 1; off >>= 1) c += __shfl_xor(c, off, 64);
+            const uint32_t u = acc_user(u0, q, hh);
+            if (l31 == 0 && u < num_users) counts[(size_t)u * G + blockIdx.y] = (uint32_t)c;
+        }
+    } else {
+        if (__any(over) && lane == 0) atomicOr(overrun_flag, 1u);
+    }
+    if (__any(bad) && lane == 0) atomicOr(nonfinite_flag, 1u);
+}
+#undef TK_SCORE
+
+/* The exclusive scan of counts [n G] in (row, range) order into offsets [n G + 1], and the rows' totals; one workgroup: each
+ * thread sums a contiguous piece, the 1 024 sums are scanned in LDS, and the piece is walked again.  n G is at most a few hundred
+ * thousand (8 192 rows x above_groups' ranges), a few microseconds next to the scan. */
+__global__ __launch_bounds__(1024) void above_offsets_kernel(const uint32_t* counts, uint32_t n, uint32_t G, uint64_t* offsets, uint32_t* totals) {
+    __shared__ uint64_t part[1024];
+    const uint32_t tid = threadIdx.x;
+    const uint64_t N = (uint64_t)n * G;
+    const uint64_t per = (N + 1023) / 1024;
+    const uint64_t i0 = (uint64_t)tid * per < N ? (uint64_t)tid * per : N;
+    const uint64_t i1 = i0 + per < N ? i0 + per : N;
+    uint64_t sum = 0;
+    for (uint64_t i = i0; i < i1; ++i) sum += counts[i];
+    part[tid] = sum;
+    __syncthreads();
+    for (uint32_t off = 1; off < 1024; off <<= 1) {
+        const uint64_t v = tid >= off ? part[tid - off] : 0ull;
+        __syncthreads();
+        part[tid] += v;
+        __syncthreads();
+    }
+    uint64_t run = part[tid] - sum;
+    for (uint64_t i = i0; i < i1; ++i) {
+        offsets[i] = run;
+        run += counts[i];
+    }
+    if (tid == 1023) offsets[N] = part[1023];
+    for (uint32_t r = tid; r < n; r += 1024) {
+        uint32_t t = 0;
+        for (uint32_t g = 0; g < G; ++g) t += counts[(size_t)r * G + g];
+        totals[r] = t;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // user_representations: the users' final states out of the forward pass's packed rows
 // ------------------------------------------------------------------------------------------------
 /* out[i][c] = H[rep_row[i]][c] for c < dl (embedding_dim; H's rows are d floats): the rows in user order and at the caller's width,
@@ -1608,6 +1864,61 @@ int launch_log_partition(const ModelView& m, const float* reps, const TopkScan& 
                                sc.excl_items, sc.f.tags, sc.f.any_of, sc.f.none_of, pt.mass);
     });
     return n + 2 + (sc.excl_ptr ? 1 : 0);
+}
+
+uint32_t above_groups(uint32_t num_rows, uint32_t num_items, uint32_t* items_per_group) {
+    // item ranges as launch_log_partition's sum scan: two rounds of the chip's resident slots; no limit from a merge, there is none
+    const uint32_t utiles = (num_rows + 127) / 128;
+    return split_items(num_items, wanted_groups((256u * 2u * 2u + utiles - 1) / (utiles ? utiles : 1u)), UINT32_MAX, UINT32_MAX, items_per_group);
+}
+
+namespace {
+
+/* above_gemm_kernel over rows [r0, r0 + nr) of sc: the only place that decides its policies — QueryBias where qb is set (never with
+ * a filter), TagFilter where sc.f.tags is */
+template <bool Fill>
+void above_scan(const ModelView& cat, const float* reps, const float* qb, const AboveScan& sc, uint32_t r0, uint32_t nr, uint32_t* out_ids,
+                float* out_scores, uint32_t out_cap, hipStream_t s) {
+    const dim3 grid((nr + 127) / 128, sc.groups);
+    const size_t g0 = (size_t)r0 * sc.groups;
+    const uint64_t* eptr = sc.excl_ptr ? sc.excl_ptr + r0 : nullptr;
+    DISPATCH_D(cat.d, {
+        if (qb)
+            hipLaunchKernelGGL((above_gemm_kernel<DD, QueryBias, NoFilter, Fill>), grid, dim3(256), 0, s, cat, reps, sc.rep_row + r0, nr,
+                               sc.thresholds + r0, eptr, sc.excl_items, sc.per, sc.counts + g0, sc.offsets + g0, out_ids, out_scores, out_cap,
+                               sc.overrun_flag, sc.nonfinite_flag, NoFilter::Args{}, QueryBias::Args{qb});
+        else if (sc.f.tags)
+            hipLaunchKernelGGL((above_gemm_kernel<DD, BiasAdd, TagFilter, Fill>), grid, dim3(256), 0, s, cat, reps, sc.rep_row + r0, nr,
+                               sc.thresholds + r0, eptr, sc.excl_items, sc.per, sc.counts + g0, sc.offsets + g0, out_ids, out_scores, out_cap,
+                               sc.overrun_flag, sc.nonfinite_flag, TagFilter::Args{sc.f.tags, sc.f.any_of + r0, sc.f.none_of + r0},
+                               BiasAdd::Args{});
+        else
+            hipLaunchKernelGGL((above_gemm_kernel<DD, BiasAdd, NoFilter, Fill>), grid, dim3(256), 0, s, cat, reps, sc.rep_row + r0, nr,
+                               sc.thresholds + r0, eptr, sc.excl_items, sc.per, sc.counts + g0, sc.offsets + g0, out_ids, out_scores, out_cap,
+                               sc.overrun_flag, sc.nonfinite_flag, NoFilter::Args{}, BiasAdd::Args{});
+    });
+}
+
+}  // namespace
+
+int launch_above_count(const ModelView& cat, const float* reps, const float* qb, const AboveScan& sc, hipStream_t s) {
+    if (sc.n == 0 || cat.num_items == 0) return 0;
+    above_scan<false>(cat, reps, qb, sc, 0, sc.n, nullptr, nullptr, 0, s);
+    hipLaunchKernelGGL(above_offsets_kernel, dim3(1), dim3(1024), 0, s, sc.counts, sc.n, sc.groups, sc.offsets, sc.totals);
+    return 2;
+}
+
+int launch_above_fill(const ModelView& cat, const float* reps, const float* qb, const AboveScan& sc, uint32_t r0, uint32_t nr, uint32_t* out_ids,
+                      float* out_scores, uint32_t out_cap, hipStream_t s) {
+    if (nr == 0 || cat.num_items == 0 || out_cap == 0) return 0;
+    above_scan<true>(cat, reps, qb, sc, r0, nr, out_ids, out_scores, out_cap, s);
+    return 1;
+}
+
+int launch_above_ids(const uint32_t* row_ids, uint32_t* ids, uint64_t n, hipStream_t s) {
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(subset_ids_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, row_ids, ids, n);
+    return 1;
 }
 
 uint32_t diverse_max_pool(int d) {

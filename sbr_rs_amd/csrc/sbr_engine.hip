@@ -4046,6 +4046,138 @@ bool partition_args(float temperature, uint64_t n, float* out_shift, uint64_t* o
     return true;
 }
 
+}  // namespace
+}  // extern "C"
+
+namespace {
+
+/* device blocks of one call or chunk outside the eval arena (which does not outlive a carve); given back once the stream is idle */
+struct DeviceBlocks {
+    hipStream_t stream;
+    std::vector<void*> blocks;
+    explicit DeviceBlocks(hipStream_t s) : stream(s) {}
+    DeviceBlocks(const DeviceBlocks&) = delete;
+    DeviceBlocks& operator=(const DeviceBlocks&) = delete;
+    template <typename T>
+    sbr_status take(T** p, size_t count) {
+        SBRCHK(dmalloc(p, count ? count : 1));
+        blocks.push_back(*p);
+        return SBR_OK;
+    }
+    ~DeviceBlocks() {
+        if (blocks.empty()) return;
+        (void)hipStreamSynchronize(stream);
+        for (void* b : blocks) dfree(b);
+    }
+};
+
+}  // namespace
+
+extern "C" {
+namespace {
+
+/* The threshold form of a scan (recommend_above / audience_above; not with item rows, a subset, a selection, noise or a partition):
+ * every scanned column whose score is >= thresholds[row], as CSR.  out_counts [rows of the call] always; the pairs go to out_ids /
+ * out_scores (host, `capacity` entries; out_ids null: counts only, out_scores alone may be null) in row order while the running
+ * total fits the capacity — once it does not, the remaining chunks are counted only.  total: the pairs counted so far. */
+struct Above {
+    const float* thresholds;
+    uint64_t* out_counts;
+    uint64_t capacity;
+    uint32_t* out_ids;
+    float* out_scores;
+    uint64_t total;
+};
+
+/* the output arguments the *_above calls share: false for a missing array, scores without ids, or a NaN threshold */
+bool above_args(const float* thresholds, uint64_t n, uint64_t* out_counts, uint64_t* out_total, uint64_t capacity, uint32_t* out_ids,
+                float* out_scores, Above* out) {
+    if (!out_total || (n && (!thresholds || !out_counts)) || (out_scores && !out_ids)) return false;
+    for (uint64_t i = 0; i < n; ++i)
+        if (std::isnan(thresholds[i])) return false;
+    *out = Above{thresholds, out_counts, capacity, out_ids, out_scores, 0};
+    return true;
+}
+
+/* a fill launch's share of the device output: 256 MB of (id, score) entries, the bound the top-k lists are kept to.
+ * SBR_ABOVE_FILL_BYTES=n (n >= 1) is a TEST HOOK read per call that replaces it (small tests run several fill ranges). */
+size_t above_fill_entries() {
+    size_t bytes = (size_t)256 << 20;
+    if (const char* e = std::getenv("SBR_ABOVE_FILL_BYTES")) {
+        const long long n = std::atoll(e);
+        if (n >= 1) bytes = (size_t)n;
+    }
+    const size_t entries = bytes / 8;
+    return entries < 1 ? 1 : entries > 0xFFFFFFFFull ? 0xFFFFFFFFull : entries; /* a fill launch addresses its entries with 32 bits */
+}
+
+/* device buffers of launch_above_count / launch_above_fill over nu rows beside the scan's own (rep_row, the exclusion CSR, masks) */
+struct AboveBufs {
+    float* th;
+    uint32_t *counts, *totals, *over;
+    uint64_t* offsets;
+    uint32_t groups = 0, per = 0;
+    void carve(DeviceArena& ar, uint32_t num_items, size_t nu) {
+        groups = sbr::above_groups((uint32_t)nu, num_items, &per);
+        th = ar.take<float>(nu);
+        counts = ar.take<uint32_t>(nu * groups);
+        offsets = ar.take<uint64_t>(nu * groups + 1);
+        totals = ar.take<uint32_t>(nu);
+        over = ar.take<uint32_t>(1);
+    }
+};
+
+/* One chunk of a threshold scan: rows [row0, row0 + as.n) of the call.  The count scan (behind `prelaunch`, which builds what the
+ * scan reads and returns its launches), the rows' totals read back — as.n x 4 bytes — and, while the call's running total fits the
+ * capacity, the fill over consecutive row ranges of the chunk whose entries fit above_fill_entries() (at least one row each), every
+ * range copied to the host at its running offset.  cat / A / qb: launch_above_count's; row_ids non-null (audience with named ids):
+ * what the written positions stand for.  as.thresholds is uploaded here. */
+sbr_status above_chunk(sbr_model* m, const sbr::ModelView& cat, const float* A, const float* qb, const sbr::AboveScan& as, const uint32_t* row_ids,
+                       uint64_t row0, Above* ab, const std::function<int()>& prelaunch) {
+    const size_t nu = as.n;
+    HIPCHK(hipMemcpyAsync(const_cast<float*>(as.thresholds), ab->thresholds + row0, nu * 4, hipMemcpyHostToDevice, m->stream));
+    std::vector<uint32_t> totals(nu, 0);
+    SBRCHK(scan_launch(m, as.nonfinite_flag, [&] { return prelaunch() + sbr::launch_above_count(cat, A, qb, as, m->stream); },
+                       {{totals.data(), as.totals, nu * 4}}));
+    uint64_t chunk_total = 0;
+    for (size_t i = 0; i < nu; ++i) {
+        ab->out_counts[row0 + i] = totals[i];
+        chunk_total += totals[i];
+    }
+    uint64_t at = ab->total; /* the chunk's first entry in the caller's arrays */
+    ab->total += chunk_total;
+    if (!ab->out_ids || ab->total > ab->capacity || chunk_total == 0) return SBR_OK;
+    const size_t budget = above_fill_entries();
+    size_t largest = 0; /* entries of the largest range: one device block serves them all */
+    for (size_t r0 = 0; r0 < nu;) {
+        size_t r1 = r0 + 1, n = totals[r0];
+        while (r1 < nu && n + totals[r1] <= budget) n += totals[r1++];
+        largest = std::max(largest, n);
+        r0 = r1;
+    }
+    DeviceBlocks out(m->stream);
+    uint32_t* d_ids = nullptr;
+    float* d_scores = nullptr;
+    SBRCHK(out.take(&d_ids, largest));
+    if (ab->out_scores) SBRCHK(out.take(&d_scores, largest));
+    HIPCHK(hipMemsetAsync(as.overrun_flag, 0, 4, m->stream));
+    for (size_t r0 = 0; r0 < nu;) {
+        size_t r1 = r0 + 1, n = totals[r0];
+        while (r1 < nu && n + totals[r1] <= budget) n += totals[r1++];
+        if (n) {
+            uint32_t over = 0;
+            SBRCHK(scan_launch(m, as.nonfinite_flag, [&] {
+                return sbr::launch_above_fill(cat, A, qb, as, (uint32_t)r0, (uint32_t)(r1 - r0), d_ids, d_scores, (uint32_t)n, m->stream) +
+                       (row_ids ? sbr::launch_above_ids(row_ids, d_ids, n, m->stream) : 0);
+            }, {{&over, as.overrun_flag, 4}, {ab->out_ids + at, d_ids, n * 4}, {ab->out_scores ? ab->out_scores + at : nullptr, d_scores, n * 4}}));
+            if (over) return SBR_ERR_HIP; /* the fill passed what the count did not: nothing was written out of bounds */
+            at += n;
+        }
+        r0 = r1;
+    }
+    return SBR_OK;
+}
+
 /* which variant of the top-k scan a call asks for; the default is plain recommend */
 struct ScanVariant {
     bool cosine = false;                            /* item rows: rank by cosine, not by the plain dot product */
@@ -4054,6 +4186,7 @@ struct ScanVariant {
     const TagFilterArg* flt = nullptr;
     const Sample* sm = nullptr;
     const Partition* pt = nullptr;
+    Above* ab = nullptr;
     static ScanVariant of(const Diverse* dv, const TagFilterArg* flt, const Sample* sm = nullptr, const Partition* pt = nullptr) {
         ScanVariant v;
         v.dv = dv; v.flt = flt; v.sm = sm; v.pt = pt;
@@ -4075,7 +4208,9 @@ struct ScanVariant {
  * With v.sm (recommend_sampled; not with item rows, a subset or v.dv) the scan orders by the noisy keys: out_scores receives the
  * plain scores of the drawn items and v.sm->out_keys the keys; the streams go with the call's user u through the chunks.
  * With v.pt (log_partition; k == 1, not with item rows, a subset, v.dv or v.sm) the scan finds the rows' shifts and a second scan
- * sums the softmax weights: out_items / out_scores are unused (null) and the results are v.pt->out_shift / out_mass. */
+ * sums the softmax weights: out_items / out_scores are unused (null) and the results are v.pt->out_shift / out_mass.
+ * With v.ab (recommend_above; k == 1, not with item rows, a subset, v.dv, v.sm or v.pt) no top-k scan runs: every chunk is
+ * above_chunk's count and fill over the same representations, exclusion CSR and masks; out_items / out_scores are unused (null). */
 sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, uint32_t k, uint32_t* out_items, float* out_scores,
                           const ScanVariant& v = ScanVariant()) {
     const Diverse* dv = v.dv;
@@ -4085,6 +4220,8 @@ sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, 
     if (sm && (s.item_rows || v.subset || dv)) return SBR_ERR_INVALID_ARGUMENT;
     const Partition* pt = v.pt;
     if (pt && (s.item_rows || v.subset || dv || sm || k != 1)) return SBR_ERR_INVALID_ARGUMENT;
+    Above* ab = v.ab;
+    if (ab && (s.item_rows || v.subset || dv || sm || pt || k != 1)) return SBR_ERR_INVALID_ARGUMENT;
     const size_t seen_w = s.seen ? s.seen->w : 0;
     std::vector<uint64_t> users(num_users);
     for (uint64_t u = 0; u < num_users; ++u) users[u] = u;
@@ -4102,6 +4239,7 @@ sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, 
         uint32_t *seen_slot = nullptr, *seen_caller = nullptr; /* s.seen: the chunk's slots and caller lists, the build kernel's inputs */
         float* pt_shift = nullptr; /* pt: the rows' shifts and masses */
         unsigned long long* pt_mass = nullptr;
+        AboveBufs abufs{};
         SBRCHK(user_reps(m, s, ch.users, [&](DeviceArena& ar) {
             tb.carve(ar, scanned_items, nu, nu * seen_w + ur.b.list_items.size(), k, v.flt != nullptr);
             if (s.seen) {
@@ -4111,6 +4249,7 @@ sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, 
             if (s.item_rows) rnorm = ar.take<float>(m->hp.num_items);
             if (v.subset) sb.carve(ar, v.subset->size(), (size_t)m->d);
             if (sm) smb.carve(ar, nu, k);
+            if (ab) abufs.carve(ar, scanned_items, nu);
             if (pt) {
                 pt_mass = ar.take<unsigned long long>(nu);
                 pt_shift = ar.take<float>(nu);
@@ -4155,6 +4294,19 @@ sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, 
                 streams[i] = sm->streams ? sm->streams[u] : sm->fallback ? (uint64_t)sm->fallback[u] : u;
             }
             HIPCHK(hipMemcpyAsync(smb.streams, streams.data(), nu * 8, hipMemcpyHostToDevice, m->stream));
+        }
+        if (ab) { /* the chunk's rows are the call's [ch.c0, ch.c1): every user is one unit */
+            sbr::AboveScan as{};
+            as.rep_row = tb.rep; as.n = (uint32_t)nu; as.thresholds = abufs.th;
+            as.excl_ptr = excl ? tb.eptr : nullptr; as.excl_items = tb.excl;
+            as.f = sbr::TagMasks{v.flt ? m->item_tags : nullptr, tb.any_of, tb.none_of};
+            as.groups = abufs.groups; as.per = abufs.per;
+            as.counts = abufs.counts; as.offsets = abufs.offsets; as.totals = abufs.totals;
+            as.nonfinite_flag = tb.flag; as.overrun_flag = abufs.over;
+            SBRCHK(above_chunk(m, m->mv, ur.H, nullptr, as, nullptr, ch.c0, ab, [&] {
+                return s.seen ? sbr::launch_session_seen_lists(*s.seen, seen_slot, (int)nu, tb.eptr, seen_caller, tb.excl, m->stream) : 0;
+            }));
+            continue;
         }
         const size_t ko = dv ? dv->k_out : k; /* the width of the rows that leave */
         /* the selection reads the pool's scores whether or not the caller wants any; a sampled scan's are its keys */
@@ -4235,6 +4387,44 @@ sbr_status sbr_recommend(sbr_model* m, const uint64_t* user_ptr, const uint32_t*
 sbr_status sbr_recommend_reps(sbr_model* m, const float* reps, uint64_t num_users, uint32_t k, const uint64_t* excl_ptr,
                               const uint32_t* excl_items, uint32_t* out_items, float* out_scores) {
     return recommend_reps_call(m, reps, num_users, k, excl_ptr, excl_items, out_items, out_scores, nullptr);
+}
+
+/* ---------------------------------------------------------------------------------------------
+ * the threshold form: every item at or over a per-row score, as CSR (sbr_catalogue.hip, above_gemm_kernel)
+ * ------------------------------------------------------------------------------------------- */
+sbr_status sbr_recommend_above(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users, const float* thresholds,
+                               uint32_t flags, const uint32_t* any_of, const uint32_t* none_of, uint64_t* out_counts, uint64_t* out_total,
+                               uint64_t capacity, uint32_t* out_ids, float* out_scores) {
+    Above ab;
+    TagFilterArg hold;
+    if (!m || !user_ptr || !above_args(thresholds, num_users, out_counts, out_total, capacity, out_ids, out_scores, &ab)) return SBR_ERR_INVALID_ARGUMENT;
+    if (flags & ~SBR_RECOMMEND_INCLUDE_HISTORY) return SBR_ERR_INVALID_ARGUMENT;
+    std::lock_guard<std::mutex> lock(m->mu);
+    SBRCHK(enter_reader(m));
+    SBRCHK(check_csr(m, user_ptr, num_users, item_ids, false));
+    ScanVariant v = ScanVariant::of(nullptr, sample_filter(any_of, none_of, &hold));
+    v.ab = &ab;
+    SBRCHK(recommend_scan(m, RepSource::of_histories(user_ptr, item_ids, 0, !(flags & SBR_RECOMMEND_INCLUDE_HISTORY)), num_users, 1, nullptr, nullptr, v));
+    *out_total = ab.total;
+    return SBR_OK;
+}
+
+sbr_status sbr_recommend_above_reps(sbr_model* m, const float* reps, uint64_t num_users, const float* thresholds, const uint64_t* excl_ptr,
+                                    const uint32_t* excl_items, const uint32_t* any_of, const uint32_t* none_of, uint64_t* out_counts,
+                                    uint64_t* out_total, uint64_t capacity, uint32_t* out_ids, float* out_scores) {
+    Above ab;
+    TagFilterArg hold;
+    if (!m || (num_users && !reps) || !above_args(thresholds, num_users, out_counts, out_total, capacity, out_ids, out_scores, &ab))
+        return SBR_ERR_INVALID_ARGUMENT;
+    if (!excl_args_ok(excl_ptr, excl_items, num_users)) return SBR_ERR_INVALID_ARGUMENT;
+    std::lock_guard<std::mutex> lock(m->mu);
+    SBRCHK(enter_reader(m));
+    if (excl_ptr) SBRCHK(check_csr(m, excl_ptr, num_users, excl_items, false));
+    ScanVariant v = ScanVariant::of(nullptr, sample_filter(any_of, none_of, &hold));
+    v.ab = &ab;
+    SBRCHK(recommend_scan(m, RepSource::of_rows(reps, excl_ptr, excl_items), num_users, 1, nullptr, nullptr, v));
+    *out_total = ab.total;
+    return SBR_OK;
 }
 
 /* ---------------------------------------------------------------------------------------------
@@ -5166,8 +5356,8 @@ RepSource RepSource::of_sessions(const sbr_sessions* st, const std::vector<int>&
 /* sbr_sessions_recommend*, and with dv (k is the pool) sbr_sessions_recommend_diverse*, which have no flags argument: flags = 0 */
 sbr_status sessions_recommend_call(sbr_sessions* st, const uint32_t* slots, uint64_t n, uint32_t k, const uint64_t* excl_ptr,
                                    const uint32_t* excl_items, uint32_t flags, uint32_t* out_items, float* out_scores, const TagFilterArg* flt,
-                                   const Diverse* dv = nullptr, const Sample* sm = nullptr, const Partition* pt = nullptr) {
-    if (!st || (n && !out_items && !pt)) return SBR_ERR_INVALID_ARGUMENT;
+                                   const Diverse* dv = nullptr, const Sample* sm = nullptr, const Partition* pt = nullptr, Above* ab = nullptr) {
+    if (!st || (n && !out_items && !pt && !ab)) return SBR_ERR_INVALID_ARGUMENT;
     /* a store with memory takes sbr_recommend's flag; one without keeps refusing every flag */
     if (st->seen.w ? (flags & ~SBR_RECOMMEND_INCLUDE_HISTORY) != 0 : flags != 0) return SBR_ERR_INVALID_ARGUMENT;
     if (!scan_k_ok(st->m, k, dv)) return SBR_ERR_INVALID_ARGUMENT;
@@ -5179,8 +5369,9 @@ sbr_status sessions_recommend_call(sbr_sessions* st, const uint32_t* slots, uint
     if (excl_ptr) SBRCHK(check_csr(m, excl_ptr, n, excl_items, false));
     const std::vector<int> rows = session_rep_rows(st, slots, n);
     const bool seen = st->seen.w && !(flags & SBR_RECOMMEND_INCLUDE_HISTORY);
-    return recommend_scan(m, RepSource::of_sessions(st, rows, excl_ptr, excl_items, seen ? slots : nullptr), n, k, out_items, out_scores,
-                          ScanVariant::of(dv, flt, sm, pt));
+    ScanVariant v = ScanVariant::of(dv, flt, sm, pt);
+    v.ab = ab;
+    return recommend_scan(m, RepSource::of_sessions(st, rows, excl_ptr, excl_items, seen ? slots : nullptr), n, k, out_items, out_scores, v);
 }
 
 }  // namespace
@@ -5219,6 +5410,18 @@ sbr_status sbr_sessions_log_partition(sbr_sessions* st, const uint32_t* slots, u
                                                  sample_filter(any_of, none_of, &hold), nullptr, nullptr, &pt);
     if (r == SBR_OK) *out_frac_bits = sbr_softmax_fbits((uint32_t)st->m->hp.num_items);
     return r;
+}
+
+sbr_status sbr_sessions_recommend_above(sbr_sessions* st, const uint32_t* slots, uint64_t n, const float* thresholds, const uint64_t* excl_ptr,
+                                        const uint32_t* excl_items, uint32_t flags, const uint32_t* any_of, const uint32_t* none_of,
+                                        uint64_t* out_counts, uint64_t* out_total, uint64_t capacity, uint32_t* out_ids, float* out_scores) {
+    Above ab;
+    TagFilterArg hold;
+    if (!st || !above_args(thresholds, n, out_counts, out_total, capacity, out_ids, out_scores, &ab)) return SBR_ERR_INVALID_ARGUMENT;
+    SBRCHK(sessions_recommend_call(st, slots, n, 1, excl_ptr, excl_items, flags, nullptr, nullptr, sample_filter(any_of, none_of, &hold), nullptr,
+                                   nullptr, nullptr, &ab));
+    *out_total = ab.total;
+    return SBR_OK;
 }
 
 sbr_status sbr_sessions_recommend_diverse(sbr_sessions* st, const uint32_t* slots, uint64_t n, uint32_t k, uint32_t pool, float trade_off,
@@ -5265,26 +5468,6 @@ struct AudienceSource {
     const sbr::SeenView* seen = nullptr;
 };
 
-/* device blocks of one call or chunk outside the eval arena (which does not outlive a carve); given back once the stream is idle */
-struct DeviceBlocks {
-    hipStream_t stream;
-    std::vector<void*> blocks;
-    explicit DeviceBlocks(hipStream_t s) : stream(s) {}
-    DeviceBlocks(const DeviceBlocks&) = delete;
-    DeviceBlocks& operator=(const DeviceBlocks&) = delete;
-    template <typename T>
-    sbr_status take(T** p, size_t count) {
-        SBRCHK(dmalloc(p, count ? count : 1));
-        blocks.push_back(*p);
-        return SBR_OK;
-    }
-    ~DeviceBlocks() {
-        if (blocks.empty()) return;
-        (void)hipStreamSynchronize(stream);
-        for (void* b : blocks) dfree(b);
-    }
-};
-
 int bits_for(uint64_t n) { /* bits that hold every value below n */
     int b = 1;
     while (b < 32 && (1ull << b) < n) ++b;
@@ -5295,10 +5478,17 @@ int bits_for(uint64_t n) { /* bits that hold every value below n */
  * once per call, outside the arena: one gather (or upload) however many chunks follow.  excl_ptr / excl_pos: per query the sorted,
  * de-duplicated candidate POSITIONS the caller excludes (excl_ptr empty: none).  With src.seen the chunk's exclusion CSR is built on
  * the device — a count pass over the candidates' rings, one u64 read back to size the key arrays, a fill pass behind the caller's
- * (query, position) keys, the key ordering, and the segment bounds — and never visits the host. */
+ * (query, position) keys, the key ordering, and the segment bounds — and never visits the host.
+ * With ab (audience_above; k == 1, out_rows / out_scores unused) every chunk is above_chunk's count and fill over the same table and
+ * exclusion CSR, the queries the rows and the candidates the columns. */
 sbr_status audience_scan(sbr_model* m, const AudienceSource& src, uint64_t num_rows, const uint32_t* items, uint64_t num_queries, uint32_t k,
-                         const std::vector<uint64_t>& excl_ptr, const std::vector<uint32_t>& excl_pos, uint32_t* out_rows, float* out_scores) {
+                         const std::vector<uint64_t>& excl_ptr, const std::vector<uint32_t>& excl_pos, uint32_t* out_rows, float* out_scores,
+                         Above* ab = nullptr) {
     if (num_queries == 0) return SBR_OK;
+    if (ab && num_rows == 0) { /* nobody to pass: empty rows */
+        for (uint64_t j = 0; j < num_queries; ++j) ab->out_counts[j] = 0;
+        return SBR_OK;
+    }
     if (num_rows == 0) { /* nobody to rank: rows of padding */
         for (uint64_t e = 0; e < num_queries * k; ++e) {
             out_rows[e] = 0xFFFFFFFFu;
@@ -5338,8 +5528,10 @@ sbr_status audience_scan(sbr_model* m, const AudienceSource& src, uint64_t num_r
         TopkBufs tb;
         uint32_t *qs_item = nullptr, *qs_idx = nullptr;
         unsigned long long* counters = nullptr; /* [0] the count pass's total, [1] the fill pass's cursor */
+        AboveBufs abufs{};
         SBRCHK(carve_arena(m, [&](DeviceArena& ar) {
             tb.carve(ar, (uint32_t)S, n, src.seen ? 0 : nc, k, false);
+            if (ab) abufs.carve(ar, (uint32_t)S, n);
             if (src.seen) {
                 qs_item = ar.take<uint32_t>(n);
                 qs_idx = ar.take<uint32_t>(n);
@@ -5402,6 +5594,19 @@ sbr_status audience_scan(sbr_model* m, const AudienceSource& src, uint64_t num_r
                 d_excl = excl;
             }
         }
+        if (ab) {
+            sbr::AboveScan as{};
+            as.rep_row = tb.rep; as.n = (uint32_t)n; as.thresholds = abufs.th;
+            as.excl_ptr = lists ? tb.eptr : nullptr; as.excl_items = d_excl;
+            as.f = sbr::TagMasks{nullptr, nullptr, nullptr};
+            as.groups = abufs.groups; as.per = abufs.per;
+            as.counts = abufs.counts; as.offsets = abufs.offsets; as.totals = abufs.totals;
+            as.nonfinite_flag = tb.flag; as.overrun_flag = abufs.over;
+            sbr::ModelView mt = m->mv; /* the scan's catalogue: the candidate rows, as launch_audience's */
+            mt.E = T; mt.b = bT; mt.num_items = (uint32_t)S;
+            SBRCHK(above_chunk(m, mt, m->mv.E, m->mv.b, as, d_ids, q0, ab, [] { return 0; }));
+            continue;
+        }
         sbr::TopkScan sc = tb.scan(n, k, lists, out_scores != nullptr);
         sc.excl_items = d_excl;
         SBRCHK(scan_launch(m, tb.flag, [&] { return sbr::launch_audience(m->mv, T, bT, (uint32_t)S, d_ids, sc, m->stream); }, {{out_rows + q0 * k, tb.items, n * k * 4}, {out_scores ? out_scores + q0 * k : nullptr, tb.scores, n * k * 4}}));
@@ -5438,19 +5643,16 @@ sbr_status audience_exclusions(const uint64_t* ptr, const uint32_t* ids, uint64_
 }
 
 bool audience_args_ok(const void* handle, const uint32_t* items, uint64_t num_queries, uint32_t k, const uint64_t* excl_ptr, const uint32_t* excl_ids,
-                      const uint32_t* out_rows) {
-    if (!handle || (num_queries && (!items || !out_rows))) return false;
+                      const uint32_t* out_rows, const Above* ab = nullptr) {
+    if (!handle || (num_queries && (!items || (!out_rows && !ab)))) return false;
     if (k < 1 || k > SBR_RECOMMEND_MAX_K) return false;
     return excl_args_ok(excl_ptr, excl_ids, num_queries);
 }
 
-}  // namespace
-
-extern "C" {
-
-sbr_status sbr_audience_reps(sbr_model* m, const float* reps, uint64_t num_rows, const uint32_t* items, uint64_t num_queries, uint32_t k,
-                             const uint64_t* excl_ptr, const uint32_t* excl_rows, uint32_t* out_rows, float* out_scores) {
-    if (!audience_args_ok(m, items, num_queries, k, excl_ptr, excl_rows, out_rows) || (num_rows && !reps)) return SBR_ERR_INVALID_ARGUMENT;
+/* sbr_audience_reps, and with ab (k == 1, no output rows) sbr_audience_above_reps */
+sbr_status audience_reps_call(sbr_model* m, const float* reps, uint64_t num_rows, const uint32_t* items, uint64_t num_queries, uint32_t k,
+                              const uint64_t* excl_ptr, const uint32_t* excl_rows, uint32_t* out_rows, float* out_scores, Above* ab) {
+    if (!audience_args_ok(m, items, num_queries, k, excl_ptr, excl_rows, out_rows, ab) || (num_rows && !reps)) return SBR_ERR_INVALID_ARGUMENT;
     std::lock_guard<std::mutex> lock(m->mu);
     SBRCHK(enter_reader(m));
     for (uint64_t j = 0; j < num_queries; ++j)
@@ -5460,19 +5662,20 @@ sbr_status sbr_audience_reps(sbr_model* m, const float* reps, uint64_t num_rows,
     SBRCHK(audience_exclusions(excl_ptr, excl_rows, num_queries, num_rows, nullptr, &eptr, &epos));
     AudienceSource src;
     src.reps = reps;
-    return audience_scan(m, src, num_rows, items, num_queries, k, eptr, epos, out_rows, out_scores);
+    return audience_scan(m, src, num_rows, items, num_queries, k, eptr, epos, out_rows, out_scores, ab);
 }
 
-sbr_status sbr_audience(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users, const uint32_t* items,
-                        uint64_t num_queries, uint32_t k, uint32_t flags, uint32_t* out_users, float* out_scores) {
-    if (!audience_args_ok(m, items, num_queries, k, nullptr, nullptr, out_users) || !user_ptr) return SBR_ERR_INVALID_ARGUMENT;
+/* sbr_audience, and with ab sbr_audience_above */
+sbr_status audience_call(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users, const uint32_t* items,
+                         uint64_t num_queries, uint32_t k, uint32_t flags, uint32_t* out_users, float* out_scores, Above* ab) {
+    if (!audience_args_ok(m, items, num_queries, k, nullptr, nullptr, out_users, ab) || !user_ptr) return SBR_ERR_INVALID_ARGUMENT;
     if (flags & ~SBR_RECOMMEND_INCLUDE_HISTORY) return SBR_ERR_INVALID_ARGUMENT;
     for (uint64_t j = 0; j < num_queries; ++j)
         if (items[j] >= m->hp.num_items) return SBR_ERR_INVALID_ARGUMENT;
     std::vector<float> reps((size_t)num_users * (size_t)m->dl + 1);
     SBRCHK(sbr_user_representations(m, user_ptr, item_ids, num_users, reps.data())); /* validates the histories */
     if (flags & SBR_RECOMMEND_INCLUDE_HISTORY)
-        return sbr_audience_reps(m, reps.data(), num_users, items, num_queries, k, nullptr, nullptr, out_users, out_scores);
+        return audience_reps_call(m, reps.data(), num_users, items, num_queries, k, nullptr, nullptr, out_users, out_scores, ab);
     /* per query, the users whose WHOLE history holds the item (recommend's mask, evaluation.rs:30-32), ascending */
     std::vector<uint32_t> uniq(items, items + num_queries);
     std::sort(uniq.begin(), uniq.end());
@@ -5493,14 +5696,15 @@ sbr_status sbr_audience(sbr_model* m, const uint64_t* user_ptr, const uint32_t* 
         eptr[j + 1] = eusers.size();
     }
     const uint32_t none = 0;
-    return sbr_audience_reps(m, reps.data(), num_users, items, num_queries, k, eptr.data(), eusers.empty() ? &none : eusers.data(), out_users,
-                             out_scores);
+    return audience_reps_call(m, reps.data(), num_users, items, num_queries, k, eptr.data(), eusers.empty() ? &none : eusers.data(), out_users,
+                              out_scores, ab);
 }
 
-sbr_status sbr_sessions_audience(sbr_sessions* st, const uint32_t* items, uint64_t num_queries, uint32_t k, const uint32_t* slots,
-                                 uint64_t num_slots, const uint64_t* excl_ptr, const uint32_t* excl_slots, uint32_t flags, uint32_t* out_slots,
-                                 float* out_scores) {
-    if (!audience_args_ok(st, items, num_queries, k, excl_ptr, excl_slots, out_slots)) return SBR_ERR_INVALID_ARGUMENT;
+/* sbr_sessions_audience, and with ab sbr_sessions_audience_above */
+sbr_status sessions_audience_call(sbr_sessions* st, const uint32_t* items, uint64_t num_queries, uint32_t k, const uint32_t* slots,
+                                  uint64_t num_slots, const uint64_t* excl_ptr, const uint32_t* excl_slots, uint32_t flags, uint32_t* out_slots,
+                                  float* out_scores, Above* ab) {
+    if (!audience_args_ok(st, items, num_queries, k, excl_ptr, excl_slots, out_slots, ab)) return SBR_ERR_INVALID_ARGUMENT;
     /* a store with memory takes sbr_recommend's flag; one without keeps refusing every flag */
     if (st->seen.w ? (flags & ~SBR_RECOMMEND_INCLUDE_HISTORY) != 0 : flags != 0) return SBR_ERR_INVALID_ARGUMENT;
     sbr_model* m = st->m;
@@ -5528,7 +5732,59 @@ sbr_status sbr_sessions_audience(sbr_sessions* st, const uint32_t* items, uint64
     src.dev_row = rows.data();
     src.ids = cand.data();
     if (st->seen.w && !(flags & SBR_RECOMMEND_INCLUDE_HISTORY)) src.seen = &st->seen;
-    return audience_scan(m, src, cand.size(), items, num_queries, k, eptr, epos, out_slots, out_scores);
+    return audience_scan(m, src, cand.size(), items, num_queries, k, eptr, epos, out_slots, out_scores, ab);
+}
+
+}  // namespace
+
+extern "C" {
+
+sbr_status sbr_audience_reps(sbr_model* m, const float* reps, uint64_t num_rows, const uint32_t* items, uint64_t num_queries, uint32_t k,
+                             const uint64_t* excl_ptr, const uint32_t* excl_rows, uint32_t* out_rows, float* out_scores) {
+    return audience_reps_call(m, reps, num_rows, items, num_queries, k, excl_ptr, excl_rows, out_rows, out_scores, nullptr);
+}
+
+sbr_status sbr_audience(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users, const uint32_t* items,
+                        uint64_t num_queries, uint32_t k, uint32_t flags, uint32_t* out_users, float* out_scores) {
+    return audience_call(m, user_ptr, item_ids, num_users, items, num_queries, k, flags, out_users, out_scores, nullptr);
+}
+
+sbr_status sbr_sessions_audience(sbr_sessions* st, const uint32_t* items, uint64_t num_queries, uint32_t k, const uint32_t* slots,
+                                 uint64_t num_slots, const uint64_t* excl_ptr, const uint32_t* excl_slots, uint32_t flags, uint32_t* out_slots,
+                                 float* out_scores) {
+    return sessions_audience_call(st, items, num_queries, k, slots, num_slots, excl_ptr, excl_slots, flags, out_slots, out_scores, nullptr);
+}
+
+/* the threshold forms: every candidate row at or over a per-query score, as CSR (above_gemm_kernel with the QueryBias policy) */
+sbr_status sbr_audience_above_reps(sbr_model* m, const float* reps, uint64_t num_rows, const uint32_t* items, uint64_t num_queries,
+                                   const float* thresholds, const uint64_t* excl_ptr, const uint32_t* excl_rows, uint64_t* out_counts,
+                                   uint64_t* out_total, uint64_t capacity, uint32_t* out_ids, float* out_scores) {
+    Above ab;
+    if (!above_args(thresholds, num_queries, out_counts, out_total, capacity, out_ids, out_scores, &ab)) return SBR_ERR_INVALID_ARGUMENT;
+    SBRCHK(audience_reps_call(m, reps, num_rows, items, num_queries, 1, excl_ptr, excl_rows, nullptr, nullptr, &ab));
+    *out_total = ab.total;
+    return SBR_OK;
+}
+
+sbr_status sbr_audience_above(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users, const uint32_t* items,
+                              uint64_t num_queries, const float* thresholds, uint32_t flags, uint64_t* out_counts, uint64_t* out_total,
+                              uint64_t capacity, uint32_t* out_ids, float* out_scores) {
+    Above ab;
+    if (!above_args(thresholds, num_queries, out_counts, out_total, capacity, out_ids, out_scores, &ab)) return SBR_ERR_INVALID_ARGUMENT;
+    SBRCHK(audience_call(m, user_ptr, item_ids, num_users, items, num_queries, 1, flags, nullptr, nullptr, &ab));
+    *out_total = ab.total;
+    return SBR_OK;
+}
+
+sbr_status sbr_sessions_audience_above(sbr_sessions* st, const uint32_t* items, uint64_t num_queries, const float* thresholds,
+                                       const uint32_t* slots, uint64_t num_slots, const uint64_t* excl_ptr, const uint32_t* excl_slots,
+                                       uint32_t flags, uint64_t* out_counts, uint64_t* out_total, uint64_t capacity, uint32_t* out_ids,
+                                       float* out_scores) {
+    Above ab;
+    if (!above_args(thresholds, num_queries, out_counts, out_total, capacity, out_ids, out_scores, &ab)) return SBR_ERR_INVALID_ARGUMENT;
+    SBRCHK(sessions_audience_call(st, items, num_queries, 1, slots, num_slots, excl_ptr, excl_slots, flags, nullptr, nullptr, &ab));
+    *out_total = ab.total;
+    return SBR_OK;
 }
 
 /* ---------------------------------------------------------------------------------------------

@@ -340,6 +340,36 @@ struct PartitionScan {
     unsigned long long* mass;
 };
 int launch_log_partition(const ModelView& m, const float* reps, const TopkScan& sc, const PartitionScan& pt, hipStream_t s);
+/* every scanned column at or over a per-row score (sbr_catalogue.hip; the contract: ABOVE in include/sbr_hip.h): the catalogue scan
+ * with a count-then-write epilogue, above_gemm_kernel.  A column j passes row u if its score is finite and >= thresholds[u] (the f32
+ * compare), f's tag test allows it and it is not in the row's exclusion segment (non-decreasing; repeats and a 0xFFFFFFFF tail as
+ * the top-k scan takes them).  The item ranges are above_groups' — `groups` of `per` items — the same for both launchers.
+ * launch_above_count: counts[u * groups + g] = row u's passes in range g (plain stores, nothing zeroed), then above_offsets_kernel:
+ *   offsets[0 .. n groups] their exclusive scan in (row, range) order and totals[u] the rows' sums.  Two launches.
+ * launch_above_fill: rows [r0, r0 + nr) write their passes, ascending column, to out_ids / out_scores (NULL: not wanted) at
+ *   offsets[u * groups + g] - offsets[r0 * groups], fewer than 2^32 entries per launch, out_cap the buffers' entries; a pass
+ *   beyond its slot's end or out_cap is not written and sets *overrun_flag.  One launch.
+ * qb NULL: score = b[j] + chain_dot(reps[rep_row[u]], E[j]) of the catalogue `cat` (BiasAdd; f.tags may filter).  qb non-null
+ * (audience): score = qb[rep_row[u]] + chain_dot(reps[rep_row[u]], cat.E[j]), cat.b fetched and unused (QueryBias; no filter). */
+struct AboveScan {
+    const int* rep_row;        /* [n] */
+    uint32_t n;
+    const float* thresholds;   /* [n]; no NaN */
+    const uint64_t* excl_ptr;  /* [n + 1], NULL: no exclusion lists */
+    const uint32_t* excl_items;
+    TagMasks f;
+    uint32_t groups, per;      /* above_groups(n, cat.num_items, &per) */
+    uint32_t* counts;          /* [n groups] */
+    uint64_t* offsets;         /* [n groups + 1] */
+    uint32_t* totals;          /* [n] */
+    uint32_t *nonfinite_flag, *overrun_flag;
+};
+uint32_t above_groups(uint32_t num_rows, uint32_t num_items, uint32_t* items_per_group);
+int launch_above_count(const ModelView& cat, const float* reps, const float* qb, const AboveScan& sc, hipStream_t s);
+int launch_above_fill(const ModelView& cat, const float* reps, const float* qb, const AboveScan& sc, uint32_t r0, uint32_t nr, uint32_t* out_ids,
+                      float* out_scores, uint32_t out_cap, hipStream_t s);
+/* ids[e] = row_ids[ids[e]] for the n entries a fill wrote (audience: positions in the candidate table -> the ids they stand for) */
+int launch_above_ids(const uint32_t* row_ids, uint32_t* ids, uint64_t n, hipStream_t s);
 /* greedy maximal-marginal-relevance selection (sbr_catalogue.hip, diverse_select_kernel; the contract: sbr_recommend_diverse in
  * include/sbr_hip.h): pool_items / pool_scores [num_users][pool] are launch_recommend's outputs at k = pool; out_items / out_scores
  * [num_users][k_out] the picks in pick order with their pool scores, padded as the pool's rows.  1 <= k_out <= pool <=

@@ -174,6 +174,86 @@ def _partition_outputs(n: int):
     return np.zeros(max(n, 1), dtype=np.float32)[:n], np.zeros(max(n, 1), dtype=np.uint64)[:n], C.c_uint32(0)
 
 
+ABOVE_MAX_RESULTS = 1 << 24  # the *_above calls' default max_results: the entries of the one buffer they call with
+ABOVE_ORDERS = ("score", "id")
+
+
+def above_sort(ptr, ids, scores, order: str = "score"):
+    """The rows of a CSR result (ptr u64 [R + 1], ids u32, scores f32, each row in ascending id order, as the library returns it) in
+    ``order``: "id" as they are, "score" by score descending with ties to the lower id — a stable sort on top of the id order, the
+    total order every top-k call uses (-0.0 and +0.0 tie).  Returns (ids, scores)."""
+    if order not in ABOVE_ORDERS:
+        raise ValueError(f"order {order!r}: 'score' or 'id'")
+    ids, scores = np.asarray(ids, dtype=np.uint32), np.asarray(scores, dtype=np.float32)
+    if order == "id" or ids.size == 0:
+        return ids, scores
+    rows = np.repeat(np.arange(len(ptr) - 1, dtype=np.int64), np.diff(np.asarray(ptr, dtype=np.uint64)).astype(np.int64))
+    at = np.lexsort((-scores, rows))  # stable: equal (row, score) keep their id order
+    return ids[at], scores[at]
+
+
+class Above:
+    """What the *_above calls return, a CSR set of (row, id, score) pairs: ``ptr`` u64 [R + 1], ``ids`` u32 [N], ``scores`` f32 [N];
+    row i's pairs are entries ptr[i] .. ptr[i + 1], in the call's ``order``.  ``counts`` u64 [R] = diff(ptr)."""
+
+    def __init__(self, ptr, ids, scores, order: str = "score"):
+        self.ptr, self.ids, self.scores, self.order = ptr, ids, scores, order
+
+    @property
+    def counts(self) -> np.ndarray:
+        return np.diff(self.ptr)
+
+    def __len__(self) -> int:
+        return len(self.ptr) - 1
+
+    def row(self, i: int):
+        """(ids, scores) of row i"""
+        a, b = int(self.ptr[i]), int(self.ptr[i + 1])
+        return self.ids[a:b], self.scores[a:b]
+
+    def pairs(self):
+        """(row index i64 [N], id u32 [N], score f32 [N]), row-major"""
+        return np.repeat(np.arange(len(self), dtype=np.int64), self.counts.astype(np.int64)), self.ids, self.scores
+
+
+def _above_thresholds(threshold, n: int) -> np.ndarray:
+    """``threshold`` -> f32 [n]: a scalar applies to every row, an array must have one value per row; a NaN is refused"""
+    t = np.asarray(threshold, dtype=np.float32)
+    t = np.full(n, t, dtype=np.float32) if t.ndim == 0 else np.ascontiguousarray(t.ravel())
+    if t.size != n:
+        raise ValueError(f"threshold: one per row ({n}), or a scalar; got {t.size}")
+    if np.isnan(t).any():
+        raise ValueError("threshold: NaN")
+    return t if n else np.zeros(1, dtype=np.float32)
+
+
+def _above(call, n: int, threshold, max_results, order: str, count_only: bool):
+    """The shared tail of the *_above / count_above* methods.  ``call(thresholds, out_counts, out_total, capacity, out_ids, out_scores)``
+    invokes the entry point with the method's leading arguments.  One call with a buffer of ``max_results`` entries (np.empty
+    touches nothing); a total above it is a ValueError that states the total, never a truncated result."""
+    if order not in ABOVE_ORDERS:
+        raise ValueError(f"order {order!r}: 'score' or 'id'")
+    th = _above_thresholds(threshold, n)
+    counts = np.zeros(max(n, 1), dtype=np.uint64)
+    total = C.c_uint64(0)
+    if count_only:
+        _check(call(_ptr(th), _ptr(counts), C.byref(total), 0, None, None))
+        return counts[:n]
+    cap = ABOVE_MAX_RESULTS if max_results is None else int(max_results)
+    if cap < 0:
+        raise ValueError("max_results: >= 0")
+    ids = np.empty(max(cap, 1), dtype=np.uint32)
+    scores = np.empty(max(cap, 1), dtype=np.float32)
+    _check(call(_ptr(th), _ptr(counts), C.byref(total), cap, _ptr(ids), _ptr(scores)))
+    if total.value > cap:
+        raise ValueError(f"{total.value} pairs pass the threshold, above max_results = {cap}: raise max_results or the threshold "
+                         f"(count_above* returns the per-row counts)")
+    ptr = np.zeros(n + 1, dtype=np.uint64)
+    ptr[1:] = np.cumsum(counts[:n], dtype=np.uint64)
+    ids, scores = above_sort(ptr, ids[: total.value].copy(), scores[: total.value].copy(), order)
+    return Above(ptr, ids, scores, order)
+
+
 STREAM_ROLES = ("main", "side", "sorter", "copier", "xs")  # the roles SBR_TEST_STREAM_DELAY names, in the counter's order
 
 
@@ -808,6 +888,94 @@ class Model:
                                               None if masks is None else _ptr(masks[1]), _ptr(shift), _ptr(mass), C.byref(fb)))
         return Partition(temperature, shift, mass, fb.value)
 
+    def _recommend_above(self, user_ptr, item_ids, threshold, include_history, any_of, none_of, max_results, order, count_only):
+        up = np.ascontiguousarray(user_ptr, dtype=np.uint64)
+        it = np.ascontiguousarray(item_ids, dtype=np.uint32)
+        nu = max(len(up) - 1, 0)
+        masks = _tag_masks(any_of, none_of, nu)
+        flags = RECOMMEND_INCLUDE_HISTORY if include_history else 0
+        return _above(lambda *out: self._L.sbr_recommend_above(self._h, _ptr(up), _ptr(it), nu, out[0], flags,
+                                                               None if masks is None else _ptr(masks[0]),
+                                                               None if masks is None else _ptr(masks[1]), *out[1:]),
+                      nu, threshold, max_results, order, count_only)
+
+    def recommend_above(self, user_ptr, item_ids, threshold, include_history: bool = False, any_of=None, none_of=None,
+                        max_results=None, order: str = "score") -> Above:
+        """Every item a user may see whose score is >= ``threshold`` (sbr_recommend_above) — a set, so no k and no cap of 1 024:
+        an ``Above`` over the histories' rows, item ids with predict's score bits.  Eligibility is ``recommend``'s (history,
+        any_of / none_of).  threshold: a scalar or one f32 per row; the compare is the f32 ``>=`` (ties at the bar all pass,
+        -0.0 == +0.0, -inf returns every eligible item, +inf none, a NaN is a ValueError).  order: "score" (descending, ties to
+        the lower id: with the threshold at ``recommend(k)``'s k-th score the row starts with that call's row, bit for bit) or
+        "id" (ascending, as the library writes it).  max_results (default ABOVE_MAX_RESULTS = 2^24 pairs) sizes the one call's
+        buffer; a larger total raises a ValueError that states it — ``count_above`` costs one scan and says how many to expect.
+        With ``log_partition``: ``threshold = temperature * (np.log(p) + part.log_z)`` returns every item the user would be drawn
+        with probability at least p."""
+        return self._recommend_above(user_ptr, item_ids, threshold, include_history, any_of, none_of, max_results, order, False)
+
+    def count_above(self, user_ptr, item_ids, threshold, include_history: bool = False, any_of=None, none_of=None) -> np.ndarray:
+        """``recommend_above(...).counts`` (u64 [U]) without writing any pair: one scan.  With no masks and include_history it is
+        ``rank_targets``' rank of an item that scores exactly the threshold."""
+        return self._recommend_above(user_ptr, item_ids, threshold, include_history, any_of, none_of, None, "id", True)
+
+    def _recommend_above_reps(self, reps, threshold, exclude, any_of, none_of, max_results, order, count_only):
+        reps = np.ascontiguousarray(reps, dtype=np.float32).reshape(-1, self.dim)
+        nu = reps.shape[0]
+        masks = _tag_masks(any_of, none_of, nu)
+        ep, ei = _exclusion_csr(exclude, nu)
+        return _above(lambda *out: self._L.sbr_recommend_above_reps(self._h, _ptr(reps), nu, out[0], None if ep is None else _ptr(ep),
+                                                                    None if ei is None else _ptr(ei),
+                                                                    None if masks is None else _ptr(masks[0]),
+                                                                    None if masks is None else _ptr(masks[1]), *out[1:]),
+                      nu, threshold, max_results, order, count_only)
+
+    def recommend_above_reps(self, reps, threshold, exclude=None, any_of=None, none_of=None, max_results=None,
+                             order: str = "score") -> Above:
+        """As recommend_above, from representations [U, embedding_dim]; exclude: None or one sequence of item ids per user."""
+        return self._recommend_above_reps(reps, threshold, exclude, any_of, none_of, max_results, order, False)
+
+    def count_above_reps(self, reps, threshold, exclude=None, any_of=None, none_of=None) -> np.ndarray:
+        """``recommend_above_reps(...).counts`` without writing any pair: one scan."""
+        return self._recommend_above_reps(reps, threshold, exclude, any_of, none_of, None, "id", True)
+
+    def _audience_above_reps(self, reps, items, threshold, exclude, max_results, order, count_only):
+        reps = np.ascontiguousarray(reps, dtype=np.float32).reshape(-1, self.dim)
+        q = np.ascontiguousarray(items, dtype=np.uint32).ravel()
+        ep, ei = _exclusion_csr(exclude, q.size)
+        return _above(lambda *out: self._L.sbr_audience_above_reps(self._h, _ptr(reps), reps.shape[0], _ptr(q), q.size, out[0],
+                                                                   None if ep is None else _ptr(ep), None if ei is None else _ptr(ei),
+                                                                   *out[1:]),
+                      q.size, threshold, max_results, order, count_only)
+
+    def audience_above_reps(self, reps, items, threshold, exclude=None, max_results=None, order: str = "score") -> Above:
+        """The reverse scan's threshold form (sbr_audience_above_reps): for each query item ``items[j]`` every row of ``reps``
+        [S, embedding_dim] that scores it >= ``threshold`` (a scalar or one per query) — an ``Above`` over the queries, row
+        indices with the bits of ``predict(reps[s], [item])``.  exclude: None or one sequence of row indices per query.  The
+        pairs are exactly the transposed pairs of ``recommend_above_reps(reps, t)`` restricted to the query items."""
+        return self._audience_above_reps(reps, items, threshold, exclude, max_results, order, False)
+
+    def count_audience_above_reps(self, reps, items, threshold, exclude=None) -> np.ndarray:
+        """``audience_above_reps(...).counts`` without writing any pair: one scan."""
+        return self._audience_above_reps(reps, items, threshold, exclude, None, "id", True)
+
+    def _audience_above(self, user_ptr, item_ids, items, threshold, include_history, max_results, order, count_only):
+        up = np.ascontiguousarray(user_ptr, dtype=np.uint64)
+        it = np.ascontiguousarray(item_ids, dtype=np.uint32)
+        q = np.ascontiguousarray(items, dtype=np.uint32).ravel()
+        nu = max(len(up) - 1, 0)
+        flags = RECOMMEND_INCLUDE_HISTORY if include_history else 0
+        return _above(lambda *out: self._L.sbr_audience_above(self._h, _ptr(up), _ptr(it), nu, _ptr(q), q.size, out[0], flags, *out[1:]),
+                      q.size, threshold, max_results, order, count_only)
+
+    def audience_above(self, user_ptr, item_ids, items, threshold, include_history: bool = False, max_results=None,
+                       order: str = "score") -> Above:
+        """``audience_above_reps`` on ``user_representations`` of the histories (sbr_audience_above): user indices.  Unless
+        include_history a user whose history holds the query item is left out of that item's row."""
+        return self._audience_above(user_ptr, item_ids, items, threshold, include_history, max_results, order, False)
+
+    def count_audience_above(self, user_ptr, item_ids, items, threshold, include_history: bool = False) -> np.ndarray:
+        """``audience_above(...).counts`` without writing any pair."""
+        return self._audience_above(user_ptr, item_ids, items, threshold, include_history, None, "id", True)
+
     def diverse_max_pool(self) -> int:
         """The largest ``pool`` of recommend_diverse on this model (sbr_recommend_diverse_max_pool): a user's pool lives in one
         workgroup's LDS, min(1024, 32768 / storage width) rows."""
@@ -1256,6 +1424,59 @@ class Sessions:
                                              None if ep is None else _ptr(ep), None if ei is None else _ptr(ei), flags,
                                              _ptr(out_slots), _ptr(scores)))
         return out_slots, scores
+
+    def _recommend_above(self, slots, threshold, exclude, any_of, none_of, include_seen, max_results, order, count_only):
+        if include_seen and not self._seen:
+            raise ValueError("include_seen: this store has no seen-item memory (sessions(capacity, remember=W))")
+        flags = RECOMMEND_INCLUDE_HISTORY if include_seen else 0
+        sl = self._slots(slots)
+        masks = _tag_masks(any_of, none_of, sl.size)
+        ep, ei = _exclusion_csr(exclude, sl.size)
+        return _above(lambda *out: self._L.sbr_sessions_recommend_above(self._h, _ptr(sl), sl.size, out[0], None if ep is None else _ptr(ep),
+                                                                        None if ei is None else _ptr(ei), flags,
+                                                                        None if masks is None else _ptr(masks[0]),
+                                                                        None if masks is None else _ptr(masks[1]), *out[1:]),
+                      sl.size, threshold, max_results, order, count_only)
+
+    def recommend_above(self, slots, threshold, exclude=None, any_of=None, none_of=None, include_seen: bool = False, max_results=None,
+                        order: str = "score") -> Above:
+        """``Model.recommend_above_reps(self.representations(slots), threshold, ...)`` with the scan reading the store's rows in
+        place and the seen-item memory excluded exactly as in ``recommend`` (sbr_sessions_recommend_above)."""
+        return self._recommend_above(slots, threshold, exclude, any_of, none_of, include_seen, max_results, order, False)
+
+    def count_above(self, slots, threshold, exclude=None, any_of=None, none_of=None, include_seen: bool = False) -> np.ndarray:
+        """``recommend_above(...).counts`` without writing any pair: one scan."""
+        return self._recommend_above(slots, threshold, exclude, any_of, none_of, include_seen, None, "id", True)
+
+    def _audience_above(self, items, threshold, slots, exclude, include_seen, max_results, order, count_only):
+        if include_seen and not self._seen:
+            raise ValueError("include_seen: this store has no seen-item memory (sessions(capacity, remember=W))")
+        flags = RECOMMEND_INCLUDE_HISTORY if include_seen else 0
+        q = np.ascontiguousarray(items, dtype=np.uint32).ravel()
+        sl = None if slots is None else self._slots(slots)
+        if sl is not None and np.unique(sl).size != sl.size:
+            raise ValueError("slots: none twice")
+        ep, ei = _exclusion_csr(exclude, q.size)
+        if sl is not None and sl.size == 0:
+            sl = np.zeros(1, dtype=np.uint32)  # an empty candidate list, not "every live slot": a valid pointer, zero slots
+            nsl = 0
+        else:
+            nsl = 0 if sl is None else sl.size
+        return _above(lambda *out: self._L.sbr_sessions_audience_above(self._h, _ptr(q), q.size, out[0], None if sl is None else _ptr(sl),
+                                                                       nsl, None if ep is None else _ptr(ep),
+                                                                       None if ei is None else _ptr(ei), flags, *out[1:]),
+                      q.size, threshold, max_results, order, count_only)
+
+    def audience_above(self, items, threshold, slots=None, exclude=None, include_seen: bool = False, max_results=None,
+                       order: str = "score") -> Above:
+        """Who should hear about this item (sbr_sessions_audience_above): for each query item ``items[j]`` EVERY candidate slot
+        whose state scores it >= ``threshold`` (a scalar or one per query) — an ``Above`` over the queries, slot ids with the bits
+        of ``score_candidates``.  Candidates, ``exclude`` and the seen-item memory as in ``audience``; no k and no cap of 1 024."""
+        return self._audience_above(items, threshold, slots, exclude, include_seen, max_results, order, False)
+
+    def count_audience_above(self, items, threshold, slots=None, exclude=None, include_seen: bool = False) -> np.ndarray:
+        """``audience_above(...).counts`` without writing any pair: one scan."""
+        return self._audience_above(items, threshold, slots, exclude, include_seen, None, "id", True)
 
     def score_candidates(self, slots, candidates):
         """``Model.score_candidates_reps`` on the slots' representations, read in place: one f32 array per slot, in candidate

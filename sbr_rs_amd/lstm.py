@@ -309,6 +309,54 @@ class _ImplicitSequenceModel:
         up, it = self._csr(interactions_or_histories)
         return self.params.audience(up, it, items, k, include_history=not exclude_history)
 
+    def recommend_above(self, interactions_or_histories, threshold, exclude_history: bool = True, any_of=None, none_of=None,
+                        max_results=None, order: str = "score"):
+        """``recommend`` without a k: for each user's history EVERY eligible item whose score is >= ``threshold`` (a scalar or one
+        per user), on the device — an ``engine.Above`` (``ptr``, ``ids``, ``scores``, ``counts``, ``row(i)``, ``pairs()``), each row
+        by score descending with ties to the lower id (``order="id"``: ascending id).  The set may hold far more than
+        ``recommend``'s 1 024 per row.  With ``log_partition``, ``threshold = temperature * (np.log(p) + part.log_z)`` reads
+        "every item this user would be shown with probability at least p".  ``max_results`` (default 2^24 pairs) bounds the
+        result; a larger one raises a ValueError that states the total (``count_above`` says how many to expect)."""
+        up, it = self._csr(interactions_or_histories)
+        return self.params.recommend_above(up, it, threshold, include_history=not exclude_history, any_of=any_of, none_of=none_of,
+                                           max_results=max_results, order=order)
+
+    def count_above(self, interactions_or_histories, threshold, exclude_history: bool = True, any_of=None, none_of=None):
+        """``recommend_above(...).counts`` without writing any pair: one scan, the cheap way to choose a threshold."""
+        up, it = self._csr(interactions_or_histories)
+        return self.params.count_above(up, it, threshold, include_history=not exclude_history, any_of=any_of, none_of=none_of)
+
+    def recommend_above_reps(self, reps, threshold, exclude=None, any_of=None, none_of=None, max_results=None, order: str = "score"):
+        """``recommend_above`` from representations [U, embedding_dim]; ``exclude``: None or one sequence of item ids per user."""
+        return self.params.recommend_above_reps(reps, threshold, exclude=exclude, any_of=any_of, none_of=none_of, max_results=max_results,
+                                                order=order)
+
+    def count_above_reps(self, reps, threshold, exclude=None, any_of=None, none_of=None):
+        """``recommend_above_reps(...).counts`` without writing any pair."""
+        return self.params.count_above_reps(reps, threshold, exclude=exclude, any_of=any_of, none_of=none_of)
+
+    def audience_above(self, interactions_or_histories, items, threshold, exclude_history: bool = True, max_results=None,
+                       order: str = "score"):
+        """``audience`` without a k: for each query item EVERY user whose history scores it >= ``threshold`` (a scalar or one per
+        query) — an ``engine.Above`` over the queries, user indices.  For live sessions: ``sessions(...).audience_above``."""
+        up, it = self._csr(interactions_or_histories)
+        return self.params.audience_above(up, it, items, threshold, include_history=not exclude_history, max_results=max_results,
+                                          order=order)
+
+    def count_audience_above(self, interactions_or_histories, items, threshold, exclude_history: bool = True):
+        """``audience_above(...).counts`` without writing any pair."""
+        up, it = self._csr(interactions_or_histories)
+        return self.params.count_audience_above(up, it, items, threshold, include_history=not exclude_history)
+
+    def audience_above_reps(self, reps, items, threshold, exclude=None, max_results=None, order: str = "score"):
+        """``audience_above`` over representation rows [S, embedding_dim]; ``exclude``: None or one sequence of row indices per
+        query."""
+        return self.params.audience_above_reps(reps, items, threshold, exclude=exclude, max_results=max_results, order=order)
+
+    def count_audience_above_reps(self, reps, items, threshold, exclude=None):
+        """``audience_above_reps(...).counts`` without writing any pair."""
+        return self.params.count_audience_above_reps(reps, items, threshold, exclude=exclude)
+
     def user_representations(self, histories) -> np.ndarray:
         """``user_representation`` of many histories in one device pass: [U, embedding_dim] f32, row u for history u."""
         return self.params.user_representations(*self._csr(histories))
