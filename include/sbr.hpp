@@ -575,12 +575,15 @@ struct Partition {
 enum class AboveOrder { Score, Id };
 /// What the *_above calls return (ABOVE in sbr_hip.h): every (row, id, score) pair whose score is >= the row's threshold, as CSR —
 /// row i's pairs are entries ptr[i] .. ptr[i + 1] of ids / scores.  A set, not a list of k: a row may hold far more than
-/// SBR_RECOMMEND_MAX_K entries.
+/// SBR_RECOMMEND_MAX_K entries.  The *_top calls return the same with `cuts`: each row its exact best n.
 struct Above {
     std::vector<std::uint64_t> ptr;  ///< [rows + 1]
     std::vector<std::uint32_t> ids;
     std::vector<float> scores;
     AboveOrder order = AboveOrder::Score;
+    /// [rows] from a *_top call (TOP in sbr_hip.h): the score of a row's last entry, -inf where the row holds everything eligible,
+    /// +inf for n = 0; empty from an *_above call.
+    std::vector<float> cuts;
     std::size_t rows() const { return ptr.empty() ? 0 : ptr.size() - 1; }
     std::uint64_t count(std::size_t i) const { return ptr[i + 1] - ptr[i]; }
     std::uint64_t total() const { return ptr.empty() ? 0 : ptr.back(); }
@@ -640,13 +643,43 @@ inline std::vector<float> above_thresholds(const std::vector<float>& t, std::siz
         if (std::isnan(x)) throw EngineError(SBR_ERR_INVALID_ARGUMENT, where);
     return out;
 }
-/// The shared tail of the *_above methods.  call(out_counts, out_total, capacity, out_ids, out_scores) invokes the entry point with
-/// the method's leading arguments.  One call with buffers of max_results entries that are allocated but not touched; a total above
-/// max_results throws an EngineError that states the total, never a truncated result.  count_only: the counts alone (ids / scores
+/// What an *_above / *_top method holds its rows to: thresholds (Bar::above) or budgets (Bar::best: the entry point is then the
+/// *_top sibling, which takes n where the thresholds stand and out_cuts ahead of out_counts).  fit() makes one value per row
+/// (`method` and `unit` word the refusal).
+struct Bar {
+    std::vector<float> th;          ///< above: one threshold for all rows or one per row
+    std::vector<std::uint64_t> n;   ///< top: one budget for all rows or one per row
+    std::vector<float> cuts;        ///< top: the entry point's out_cuts
+    bool top = false;
+    static Bar above(const std::vector<float>& t) {
+        Bar b;
+        b.th = t;
+        return b;
+    }
+    static Bar best(const std::vector<std::uint64_t>& n) {
+        Bar b;
+        b.n = n;
+        b.top = true;
+        return b;
+    }
+    void fit(std::size_t rows, const char* method, const char* unit) {
+        if (!top) {
+            th = above_thresholds(th, rows, (std::string(method) + ": one threshold, or one per " + unit + "; no NaN").c_str());
+            return;
+        }
+        if (n.size() != 1 && n.size() != rows) throw EngineError(SBR_ERR_INVALID_ARGUMENT, std::string(method) + ": one n, or one per " + unit);
+        if (n.size() != rows || rows == 0) n.assign(rows ? rows : 1, n.empty() ? 0 : n[0]);
+        cuts.assign(rows ? rows : 1, 0.0f);
+    }
+};
+
+/// The shared tail of the *_above / *_top methods.  call(out_counts, out_total, capacity, out_ids, out_scores) invokes the entry
+/// point with the method's leading arguments (and, for a budget, bar.n and bar.cuts, which end up in out->cuts).  One call with
+/// buffers of max_results entries that are allocated but not touched; a total above max_results throws an EngineError that states the total, never a truncated result.  count_only: the counts alone (ids / scores
 /// stay empty), one scan.  Returns the call's status when it is SBR_ERR_INVALID_PREDICTION, for the caller's Result.
 template <class Call>
 inline sbr_status above_call(Call&& call, std::size_t n, std::uint64_t max_results, AboveOrder order, bool count_only, const char* where,
-                             Above* out) {
+                             const Bar& bar, Above* out) {
     std::vector<std::uint64_t> counts(n ? n : 1, 0);
     std::uint64_t total = 0;
     std::unique_ptr<std::uint32_t[]> ids;
@@ -659,8 +692,11 @@ inline sbr_status above_call(Call&& call, std::size_t n, std::uint64_t max_resul
     if (st == SBR_ERR_INVALID_PREDICTION) return st;
     check(st, where);
     if (!count_only && total > max_results)
-        throw EngineError(SBR_ERR_INVALID_ARGUMENT, std::string(where) + ": " + std::to_string(total) + " pairs pass the threshold, above max_results = " +
+        throw EngineError(SBR_ERR_INVALID_ARGUMENT, std::string(where) + ": " + std::to_string(total) +
+                                                        (bar.top ? " pairs make up the rows' best n, above max_results = "
+                                                                 : " pairs pass the threshold, above max_results = ") +
                                                         std::to_string(max_results));
+    if (bar.top) out->cuts.assign(bar.cuts.begin(), bar.cuts.begin() + (std::ptrdiff_t)n);
     out->ptr.assign(n + 1, 0);
     for (std::size_t i = 0; i < n; ++i) out->ptr[i + 1] = out->ptr[i] + counts[i];
     out->order = AboveOrder::Id;
@@ -977,6 +1013,39 @@ class Sessions {
         check(st, "sbr_sessions_audience");
         return Result<Recommendations, PredictionError>::Ok(std::move(r));
     }
+  private:
+    /// The body the *_above and *_top forms share: `me` names the calling method in refusals, `bar` holds the thresholds or the
+    /// budgets.
+    Result<Above, PredictionError> recommend_bar(const char* me, const std::vector<std::uint32_t>& slots, detail::Bar bar,
+                                                   const TagFilter& filter, const std::vector<std::uint64_t>& excl_ptr,
+                                                   const std::vector<std::uint32_t>& excl_items, bool include_seen,
+                                                   std::uint64_t max_results, AboveOrder order,
+                                                   bool count_only) const {
+        if (!excl_ptr.empty() && (excl_ptr.size() != slots.size() + 1 || excl_ptr.back() > excl_items.size()))
+            throw EngineError(SBR_ERR_INVALID_ARGUMENT, (std::string(me) + ": one exclusion range per slot").c_str());
+        const bool filtered = !filter.any_of.empty() || !filter.none_of.empty();
+        const std::vector<std::uint32_t> any = tag_masks(filter.any_of, slots.size(), (std::string(me) + ": one any_of mask per slot").c_str());
+        const std::vector<std::uint32_t> none_of = tag_masks(filter.none_of, slots.size(), (std::string(me) + ": one none_of mask per slot").c_str());
+        bar.fit(slots.size(), me, "slot");
+        const std::uint32_t none = 0;
+        Above r;
+        const sbr_status st = detail::above_call(
+            [&](std::uint64_t* counts, std::uint64_t* total, std::uint64_t cap, std::uint32_t* ids, float* scores) {
+                if (bar.top)
+                    return sbr_sessions_recommend_top(h_, slots.data(), (std::uint64_t)slots.size(), bar.n.data(), excl_ptr.empty() ? nullptr : excl_ptr.data(),
+                                                        excl_ptr.empty() ? nullptr : (excl_items.empty() ? &none : excl_items.data()),
+                                                        include_seen ? SBR_RECOMMEND_INCLUDE_HISTORY : 0u, filtered ? any.data() : nullptr,
+                                                        filtered ? none_of.data() : nullptr, bar.cuts.data(), counts, total, cap, ids, scores);
+                return sbr_sessions_recommend_above(h_, slots.data(), (std::uint64_t)slots.size(), bar.th.data(), excl_ptr.empty() ? nullptr : excl_ptr.data(),
+                                                    excl_ptr.empty() ? nullptr : (excl_items.empty() ? &none : excl_items.data()),
+                                                    include_seen ? SBR_RECOMMEND_INCLUDE_HISTORY : 0u, filtered ? any.data() : nullptr,
+                                                    filtered ? none_of.data() : nullptr, counts, total, cap, ids, scores);
+            },
+            slots.size(), max_results, order, count_only, bar.top ? "sbr_sessions_recommend_top" : "sbr_sessions_recommend_above", bar, &r);
+        if (st == SBR_ERR_INVALID_PREDICTION) return Result<Above, PredictionError>::Err(PredictionError::InvalidPredictionValue);
+        return Result<Above, PredictionError>::Ok(std::move(r));
+    }
+  public:
     /// `recommend` without a k (sbr_sessions_recommend_above): for each slot EVERY eligible item whose score is >= its threshold —
     /// `thresholds`: one value for all slots or one per slot; ties at the bar all pass, -inf returns every eligible item.  Eligibility
     /// (the lists, the filter, the seen-item memory unless `include_seen`) is `recommend`'s.  More than `max_results` pairs throw an
@@ -986,24 +1055,19 @@ class Sessions {
                                                    const std::vector<std::uint32_t>& excl_items = {}, bool include_seen = false,
                                                    std::uint64_t max_results = ABOVE_MAX_RESULTS, AboveOrder order = AboveOrder::Score,
                                                    bool count_only = false) const {
-        if (!excl_ptr.empty() && (excl_ptr.size() != slots.size() + 1 || excl_ptr.back() > excl_items.size()))
-            throw EngineError(SBR_ERR_INVALID_ARGUMENT, "Sessions::recommend_above: one exclusion range per slot");
-        const bool filtered = !filter.any_of.empty() || !filter.none_of.empty();
-        const std::vector<std::uint32_t> any = tag_masks(filter.any_of, slots.size(), "Sessions::recommend_above: one any_of mask per slot");
-        const std::vector<std::uint32_t> none_of = tag_masks(filter.none_of, slots.size(), "Sessions::recommend_above: one none_of mask per slot");
-        const std::vector<float> th = detail::above_thresholds(thresholds, slots.size(), "Sessions::recommend_above: one threshold, or one per slot; no NaN");
-        const std::uint32_t none = 0;
-        Above r;
-        const sbr_status st = detail::above_call(
-            [&](std::uint64_t* counts, std::uint64_t* total, std::uint64_t cap, std::uint32_t* ids, float* scores) {
-                return sbr_sessions_recommend_above(h_, slots.data(), (std::uint64_t)slots.size(), th.data(), excl_ptr.empty() ? nullptr : excl_ptr.data(),
-                                                    excl_ptr.empty() ? nullptr : (excl_items.empty() ? &none : excl_items.data()),
-                                                    include_seen ? SBR_RECOMMEND_INCLUDE_HISTORY : 0u, filtered ? any.data() : nullptr,
-                                                    filtered ? none_of.data() : nullptr, counts, total, cap, ids, scores);
-            },
-            slots.size(), max_results, order, count_only, "sbr_sessions_recommend_above", &r);
-        if (st == SBR_ERR_INVALID_PREDICTION) return Result<Above, PredictionError>::Err(PredictionError::InvalidPredictionValue);
-        return Result<Above, PredictionError>::Ok(std::move(r));
+        return recommend_bar("Sessions::recommend_above",
+                             slots, detail::Bar::above(thresholds), filter, excl_ptr, excl_items, include_seen, max_results, order, count_only);
+    }
+    /// `recommend` with a budget in place of k (sbr_sessions_recommend_top): each slot's exact best n eligible items — `n`: one value
+    /// for all slots or one per slot, any size (no SBR_RECOMMEND_MAX_K); an Above with `cuts`.  count_only: the select alone — cuts
+    /// and counts, no pair.  Everything else as `recommend_above`.
+    Result<Above, PredictionError> recommend_top(const std::vector<std::uint32_t>& slots, const std::vector<std::uint64_t>& n,
+                                                 const TagFilter& filter = {}, const std::vector<std::uint64_t>& excl_ptr = {},
+                                                 const std::vector<std::uint32_t>& excl_items = {}, bool include_seen = false,
+                                                 std::uint64_t max_results = ABOVE_MAX_RESULTS, AboveOrder order = AboveOrder::Score,
+                                                 bool count_only = false) const {
+        return recommend_bar("Sessions::recommend_top",
+                             slots, detail::Bar::best(n), filter, excl_ptr, excl_items, include_seen, max_results, order, count_only);
     }
     /// The rows' counts of `recommend_above` (its `ptr`; `ids` / `scores` stay empty) without writing any pair: one scan.
     Result<Above, PredictionError> count_above(const std::vector<std::uint32_t>& slots, const std::vector<float>& thresholds,
@@ -1011,6 +1075,39 @@ class Sessions {
                                                const std::vector<std::uint32_t>& excl_items = {}, bool include_seen = false) const {
         return recommend_above(slots, thresholds, filter, excl_ptr, excl_items, include_seen, 0, AboveOrder::Id, true);
     }
+  private:
+    /// The body the *_above and *_top forms share: `me` names the calling method in refusals, `bar` holds the thresholds or the
+    /// budgets.
+    Result<Above, PredictionError> audience_bar(const char* me, const std::vector<std::uint32_t>& items, detail::Bar bar,
+                                                  const std::vector<std::uint32_t>& slots, bool all_live_slots,
+                                                  const std::vector<std::uint64_t>& excl_ptr, const std::vector<std::uint32_t>& excl_slots,
+                                                  bool include_seen, std::uint64_t max_results,
+                                                  AboveOrder order, bool count_only) const {
+        if (!excl_ptr.empty() && (excl_ptr.size() != items.size() + 1 || excl_ptr.back() > excl_slots.size()))
+            throw EngineError(SBR_ERR_INVALID_ARGUMENT, (std::string(me) + ": one exclusion range per query").c_str());
+        if (all_live_slots && !slots.empty()) throw EngineError(SBR_ERR_INVALID_ARGUMENT, (std::string(me) + ": slots together with all_live_slots").c_str());
+        bar.fit(items.size(), me, "query");
+        const std::uint32_t none = 0;
+        Above r;
+        const sbr_status st = detail::above_call(
+            [&](std::uint64_t* counts, std::uint64_t* total, std::uint64_t cap, std::uint32_t* ids, float* scores) {
+                if (bar.top)
+                    return sbr_sessions_audience_top(h_, items.data(), (std::uint64_t)items.size(), bar.n.data(),
+                                                       all_live_slots ? nullptr : (slots.empty() ? &none : slots.data()), (std::uint64_t)slots.size(),
+                                                       excl_ptr.empty() ? nullptr : excl_ptr.data(),
+                                                       excl_ptr.empty() ? nullptr : (excl_slots.empty() ? &none : excl_slots.data()),
+                                                       include_seen ? SBR_RECOMMEND_INCLUDE_HISTORY : 0u, bar.cuts.data(), counts, total, cap, ids, scores);
+                return sbr_sessions_audience_above(h_, items.data(), (std::uint64_t)items.size(), bar.th.data(),
+                                                   all_live_slots ? nullptr : (slots.empty() ? &none : slots.data()), (std::uint64_t)slots.size(),
+                                                   excl_ptr.empty() ? nullptr : excl_ptr.data(),
+                                                   excl_ptr.empty() ? nullptr : (excl_slots.empty() ? &none : excl_slots.data()),
+                                                   include_seen ? SBR_RECOMMEND_INCLUDE_HISTORY : 0u, counts, total, cap, ids, scores);
+            },
+            items.size(), max_results, order, count_only, bar.top ? "sbr_sessions_audience_top" : "sbr_sessions_audience_above", bar, &r);
+        if (st == SBR_ERR_INVALID_PREDICTION) return Result<Above, PredictionError>::Err(PredictionError::InvalidPredictionValue);
+        return Result<Above, PredictionError>::Ok(std::move(r));
+    }
+  public:
     /// Who should hear about this item (sbr_sessions_audience_above): for each query item EVERY candidate slot whose state scores it
     /// >= its threshold (`thresholds`: one for all queries or one per query) — `ids` of the result are SLOT ids.  Candidates, the
     /// lists and the seen-item memory as in `audience`; no k.
@@ -1019,23 +1116,19 @@ class Sessions {
                                                   const std::vector<std::uint64_t>& excl_ptr = {}, const std::vector<std::uint32_t>& excl_slots = {},
                                                   bool include_seen = false, std::uint64_t max_results = ABOVE_MAX_RESULTS,
                                                   AboveOrder order = AboveOrder::Score, bool count_only = false) const {
-        if (!excl_ptr.empty() && (excl_ptr.size() != items.size() + 1 || excl_ptr.back() > excl_slots.size()))
-            throw EngineError(SBR_ERR_INVALID_ARGUMENT, "Sessions::audience_above: one exclusion range per query");
-        if (all_live_slots && !slots.empty()) throw EngineError(SBR_ERR_INVALID_ARGUMENT, "Sessions::audience_above: slots together with all_live_slots");
-        const std::vector<float> th = detail::above_thresholds(thresholds, items.size(), "Sessions::audience_above: one threshold, or one per query; no NaN");
-        const std::uint32_t none = 0;
-        Above r;
-        const sbr_status st = detail::above_call(
-            [&](std::uint64_t* counts, std::uint64_t* total, std::uint64_t cap, std::uint32_t* ids, float* scores) {
-                return sbr_sessions_audience_above(h_, items.data(), (std::uint64_t)items.size(), th.data(),
-                                                   all_live_slots ? nullptr : (slots.empty() ? &none : slots.data()), (std::uint64_t)slots.size(),
-                                                   excl_ptr.empty() ? nullptr : excl_ptr.data(),
-                                                   excl_ptr.empty() ? nullptr : (excl_slots.empty() ? &none : excl_slots.data()),
-                                                   include_seen ? SBR_RECOMMEND_INCLUDE_HISTORY : 0u, counts, total, cap, ids, scores);
-            },
-            items.size(), max_results, order, count_only, "sbr_sessions_audience_above", &r);
-        if (st == SBR_ERR_INVALID_PREDICTION) return Result<Above, PredictionError>::Err(PredictionError::InvalidPredictionValue);
-        return Result<Above, PredictionError>::Ok(std::move(r));
+        return audience_bar("Sessions::audience_above",
+                            items, detail::Bar::above(thresholds), slots, all_live_slots, excl_ptr, excl_slots, include_seen, max_results, order,
+                            count_only);
+    }
+    /// We can reach n people: which n (sbr_sessions_audience_top)?  For each query item its exact best n candidate slots — `n`: one
+    /// value for all queries or one per query, any size; an Above with `cuts`, SLOT ids.  count_only: the select alone.
+    Result<Above, PredictionError> audience_top(const std::vector<std::uint32_t>& items, const std::vector<std::uint64_t>& n,
+                                                const std::vector<std::uint32_t>& slots = {}, bool all_live_slots = true,
+                                                const std::vector<std::uint64_t>& excl_ptr = {}, const std::vector<std::uint32_t>& excl_slots = {},
+                                                bool include_seen = false, std::uint64_t max_results = ABOVE_MAX_RESULTS,
+                                                AboveOrder order = AboveOrder::Score, bool count_only = false) const {
+        return audience_bar("Sessions::audience_top",
+                            items, detail::Bar::best(n), slots, all_live_slots, excl_ptr, excl_slots, include_seen, max_results, order, count_only);
     }
     /// The rows' counts of `audience_above` without writing any pair: one scan.
     Result<Above, PredictionError> count_audience_above(const std::vector<std::uint32_t>& items, const std::vector<float>& thresholds,
@@ -1478,6 +1571,34 @@ class ImplicitSequenceModel : public OnlineRankingModel<ImplicitUser> {
         return Result<Recommendations, PredictionError>::Ok(std::move(r));
     }
 
+  private:
+    /// The body the *_above and *_top forms share: `me` names the calling method in refusals, `bar` holds the thresholds or the
+    /// budgets.
+    Result<Above, PredictionError> recommend_bar(const char* me, const data::CompressedInteractions& interactions, detail::Bar bar,
+                                                   bool exclude_history, const TagFilter& filter,
+                                                   std::uint64_t max_results, AboveOrder order,
+                                                   bool count_only) const {
+        const std::size_t n = interactions.num_users();
+        const bool filtered = !filter.any_of.empty() || !filter.none_of.empty();
+        const std::vector<std::uint32_t> any = tag_masks(filter.any_of, n, (std::string(me) + ": one any_of mask per user").c_str());
+        const std::vector<std::uint32_t> none_of = tag_masks(filter.none_of, n, (std::string(me) + ": one none_of mask per user").c_str());
+        bar.fit(n, me, "user");
+        Above r;
+        const sbr_status st = detail::above_call(
+            [&](std::uint64_t* counts, std::uint64_t* total, std::uint64_t cap, std::uint32_t* ids, float* scores) {
+                if (bar.top)
+                    return sbr_recommend_top(replicas_->primary(), interactions.user_pointers().data(), interactions.item_ids().data(), (std::uint64_t)n,
+                                               bar.n.data(), exclude_history ? 0u : SBR_RECOMMEND_INCLUDE_HISTORY, filtered ? any.data() : nullptr,
+                                               filtered ? none_of.data() : nullptr, bar.cuts.data(), counts, total, cap, ids, scores);
+                return sbr_recommend_above(replicas_->primary(), interactions.user_pointers().data(), interactions.item_ids().data(), (std::uint64_t)n,
+                                           bar.th.data(), exclude_history ? 0u : SBR_RECOMMEND_INCLUDE_HISTORY, filtered ? any.data() : nullptr,
+                                           filtered ? none_of.data() : nullptr, counts, total, cap, ids, scores);
+            },
+            n, max_results, order, count_only, bar.top ? "sbr_recommend_top" : "sbr_recommend_above", bar, &r);
+        if (st == SBR_ERR_INVALID_PREDICTION) return Result<Above, PredictionError>::Err(PredictionError::InvalidPredictionValue);
+        return Result<Above, PredictionError>::Ok(std::move(r));
+    }
+  public:
     /// `recommend` without a k (sbr_recommend_above): for each user's history EVERY eligible item whose score is >= its threshold
     /// — `thresholds`: one value for all users or one per user; the f32 compare, so ties at the bar all pass, -0.0 == +0.0, -inf
     /// returns every eligible item and +inf none.  An Above over the users, item ids with `predict`'s score bits, each row by score
@@ -1488,27 +1609,63 @@ class ImplicitSequenceModel : public OnlineRankingModel<ImplicitUser> {
                                                    bool exclude_history = true, const TagFilter& filter = {},
                                                    std::uint64_t max_results = ABOVE_MAX_RESULTS, AboveOrder order = AboveOrder::Score,
                                                    bool count_only = false) const {
-        const std::size_t n = interactions.num_users();
-        const bool filtered = !filter.any_of.empty() || !filter.none_of.empty();
-        const std::vector<std::uint32_t> any = tag_masks(filter.any_of, n, "recommend_above: one any_of mask per user");
-        const std::vector<std::uint32_t> none_of = tag_masks(filter.none_of, n, "recommend_above: one none_of mask per user");
-        const std::vector<float> th = detail::above_thresholds(thresholds, n, "recommend_above: one threshold, or one per user; no NaN");
-        Above r;
-        const sbr_status st = detail::above_call(
-            [&](std::uint64_t* counts, std::uint64_t* total, std::uint64_t cap, std::uint32_t* ids, float* scores) {
-                return sbr_recommend_above(replicas_->primary(), interactions.user_pointers().data(), interactions.item_ids().data(), (std::uint64_t)n,
-                                           th.data(), exclude_history ? 0u : SBR_RECOMMEND_INCLUDE_HISTORY, filtered ? any.data() : nullptr,
-                                           filtered ? none_of.data() : nullptr, counts, total, cap, ids, scores);
-            },
-            n, max_results, order, count_only, "sbr_recommend_above", &r);
-        if (st == SBR_ERR_INVALID_PREDICTION) return Result<Above, PredictionError>::Err(PredictionError::InvalidPredictionValue);
-        return Result<Above, PredictionError>::Ok(std::move(r));
+        return recommend_bar("recommend_above",
+                             interactions, detail::Bar::above(thresholds), exclude_history, filter, max_results, order, count_only);
+    }
+    /// `recommend` with a budget in place of k (sbr_recommend_top): each user's exact best n eligible items — `n`: one value for all
+    /// users or one per user, any size (no SBR_RECOMMEND_MAX_K; 0: an empty row; past the eligible items: all of them).  An Above
+    /// with `cuts`: for n <= SBR_RECOMMEND_MAX_K a row is `recommend(k = n)`'s without padding, for any n the first n of
+    /// `recommend_above(cuts[row])`'s; of a tie group that straddles the cut exactly the lowest ids are kept.  count_only: the select
+    /// alone — cuts and counts, no pair.  max_results is held against the pairs returned.
+    Result<Above, PredictionError> recommend_top(const data::CompressedInteractions& interactions, const std::vector<std::uint64_t>& n,
+                                                 bool exclude_history = true, const TagFilter& filter = {},
+                                                 std::uint64_t max_results = ABOVE_MAX_RESULTS, AboveOrder order = AboveOrder::Score,
+                                                 bool count_only = false) const {
+        return recommend_bar("recommend_top",
+                             interactions, detail::Bar::best(n), exclude_history, filter, max_results, order, count_only);
     }
     /// The rows' counts of `recommend_above` (its `ptr`; `ids` / `scores` stay empty) without writing any pair: one scan.
     Result<Above, PredictionError> count_above(const data::CompressedInteractions& interactions, const std::vector<float>& thresholds,
                                                bool exclude_history = true, const TagFilter& filter = {}) const {
         return recommend_above(interactions, thresholds, exclude_history, filter, 0, AboveOrder::Id, true);
     }
+  private:
+    /// The body the *_above and *_top forms share: `me` names the calling method in refusals, `bar` holds the thresholds or the
+    /// budgets.
+    Result<Above, PredictionError> recommend_reps_bar(const char* me, const std::vector<float>& reps, detail::Bar bar,
+                                                        const std::vector<std::uint64_t>& excl_ptr,
+                                                        const std::vector<std::uint32_t>& excl_items, const TagFilter& filter,
+                                                        std::uint64_t max_results, AboveOrder order,
+                                                        bool count_only) const {
+        const std::size_t dim = (std::size_t)replicas_->hparams().embedding_dim;
+        if (reps.size() % dim) throw EngineError(SBR_ERR_INVALID_ARGUMENT, (std::string(me) + ": rows of embedding_dim floats").c_str());
+        const std::size_t n = reps.size() / dim;
+        if (!excl_ptr.empty() && (excl_ptr.size() != n + 1 || excl_ptr.back() > excl_items.size()))
+            throw EngineError(SBR_ERR_INVALID_ARGUMENT, (std::string(me) + ": one exclusion range per user").c_str());
+        const bool filtered = !filter.any_of.empty() || !filter.none_of.empty();
+        const std::vector<std::uint32_t> any = tag_masks(filter.any_of, n, (std::string(me) + ": one any_of mask per user").c_str());
+        const std::vector<std::uint32_t> none_of = tag_masks(filter.none_of, n, (std::string(me) + ": one none_of mask per user").c_str());
+        bar.fit(n, me, "user");
+        const std::uint32_t none = 0;
+        const float zero = 0.0f;
+        Above r;
+        const sbr_status st = detail::above_call(
+            [&](std::uint64_t* counts, std::uint64_t* total, std::uint64_t cap, std::uint32_t* ids, float* scores) {
+                if (bar.top)
+                    return sbr_recommend_top_reps(replicas_->primary(), reps.empty() ? &zero : reps.data(), (std::uint64_t)n, bar.n.data(),
+                                                    excl_ptr.empty() ? nullptr : excl_ptr.data(),
+                                                    excl_ptr.empty() ? nullptr : (excl_items.empty() ? &none : excl_items.data()),
+                                                    filtered ? any.data() : nullptr, filtered ? none_of.data() : nullptr, bar.cuts.data(), counts, total, cap, ids, scores);
+                return sbr_recommend_above_reps(replicas_->primary(), reps.empty() ? &zero : reps.data(), (std::uint64_t)n, bar.th.data(),
+                                                excl_ptr.empty() ? nullptr : excl_ptr.data(),
+                                                excl_ptr.empty() ? nullptr : (excl_items.empty() ? &none : excl_items.data()),
+                                                filtered ? any.data() : nullptr, filtered ? none_of.data() : nullptr, counts, total, cap, ids, scores);
+            },
+            n, max_results, order, count_only, bar.top ? "sbr_recommend_top_reps" : "sbr_recommend_above_reps", bar, &r);
+        if (st == SBR_ERR_INVALID_PREDICTION) return Result<Above, PredictionError>::Err(PredictionError::InvalidPredictionValue);
+        return Result<Above, PredictionError>::Ok(std::move(r));
+    }
+  public:
     /// recommend_above from representations, reps [num_users][embedding_dim] (sbr_recommend_above_reps); excl_ptr / excl_items:
     /// per-user exclusion lists as a CSR (both empty: none).
     Result<Above, PredictionError> recommend_above_reps(const std::vector<float>& reps, const std::vector<float>& thresholds,
@@ -1516,28 +1673,17 @@ class ImplicitSequenceModel : public OnlineRankingModel<ImplicitUser> {
                                                         const std::vector<std::uint32_t>& excl_items = {}, const TagFilter& filter = {},
                                                         std::uint64_t max_results = ABOVE_MAX_RESULTS, AboveOrder order = AboveOrder::Score,
                                                         bool count_only = false) const {
-        const std::size_t dim = (std::size_t)replicas_->hparams().embedding_dim;
-        if (reps.size() % dim) throw EngineError(SBR_ERR_INVALID_ARGUMENT, "recommend_above_reps: rows of embedding_dim floats");
-        const std::size_t n = reps.size() / dim;
-        if (!excl_ptr.empty() && (excl_ptr.size() != n + 1 || excl_ptr.back() > excl_items.size()))
-            throw EngineError(SBR_ERR_INVALID_ARGUMENT, "recommend_above_reps: one exclusion range per user");
-        const bool filtered = !filter.any_of.empty() || !filter.none_of.empty();
-        const std::vector<std::uint32_t> any = tag_masks(filter.any_of, n, "recommend_above_reps: one any_of mask per user");
-        const std::vector<std::uint32_t> none_of = tag_masks(filter.none_of, n, "recommend_above_reps: one none_of mask per user");
-        const std::vector<float> th = detail::above_thresholds(thresholds, n, "recommend_above_reps: one threshold, or one per user; no NaN");
-        const std::uint32_t none = 0;
-        const float zero = 0.0f;
-        Above r;
-        const sbr_status st = detail::above_call(
-            [&](std::uint64_t* counts, std::uint64_t* total, std::uint64_t cap, std::uint32_t* ids, float* scores) {
-                return sbr_recommend_above_reps(replicas_->primary(), reps.empty() ? &zero : reps.data(), (std::uint64_t)n, th.data(),
-                                                excl_ptr.empty() ? nullptr : excl_ptr.data(),
-                                                excl_ptr.empty() ? nullptr : (excl_items.empty() ? &none : excl_items.data()),
-                                                filtered ? any.data() : nullptr, filtered ? none_of.data() : nullptr, counts, total, cap, ids, scores);
-            },
-            n, max_results, order, count_only, "sbr_recommend_above_reps", &r);
-        if (st == SBR_ERR_INVALID_PREDICTION) return Result<Above, PredictionError>::Err(PredictionError::InvalidPredictionValue);
-        return Result<Above, PredictionError>::Ok(std::move(r));
+        return recommend_reps_bar("recommend_above_reps",
+                                  reps, detail::Bar::above(thresholds), excl_ptr, excl_items, filter, max_results, order, count_only);
+    }
+    /// recommend_top from representations, reps [num_users][embedding_dim] (sbr_recommend_top_reps).
+    Result<Above, PredictionError> recommend_top_reps(const std::vector<float>& reps, const std::vector<std::uint64_t>& n,
+                                                      const std::vector<std::uint64_t>& excl_ptr = {},
+                                                      const std::vector<std::uint32_t>& excl_items = {}, const TagFilter& filter = {},
+                                                      std::uint64_t max_results = ABOVE_MAX_RESULTS, AboveOrder order = AboveOrder::Score,
+                                                      bool count_only = false) const {
+        return recommend_reps_bar("recommend_top_reps",
+                                  reps, detail::Bar::best(n), excl_ptr, excl_items, filter, max_results, order, count_only);
     }
     /// The rows' counts of `recommend_above_reps` without writing any pair: one scan.
     Result<Above, PredictionError> count_above_reps(const std::vector<float>& reps, const std::vector<float>& thresholds,
@@ -1545,6 +1691,40 @@ class ImplicitSequenceModel : public OnlineRankingModel<ImplicitUser> {
                                                     const std::vector<std::uint32_t>& excl_items = {}, const TagFilter& filter = {}) const {
         return recommend_above_reps(reps, thresholds, excl_ptr, excl_items, filter, 0, AboveOrder::Id, true);
     }
+  private:
+    /// The body the *_above and *_top forms share: `me` names the calling method in refusals, `bar` holds the thresholds or the
+    /// budgets.
+    Result<Above, PredictionError> audience_reps_bar(const char* me, const std::vector<float>& reps, const std::vector<ItemId>& items,
+                                                       detail::Bar bar, const std::vector<std::uint64_t>& excl_ptr,
+                                                       const std::vector<std::uint32_t>& excl_rows,
+                                                       std::uint64_t max_results, AboveOrder order,
+                                                       bool count_only) const {
+        const std::size_t dim = (std::size_t)replicas_->hparams().embedding_dim;
+        if (reps.size() % dim) throw EngineError(SBR_ERR_INVALID_ARGUMENT, (std::string(me) + ": rows of embedding_dim floats").c_str());
+        if (!excl_ptr.empty() && (excl_ptr.size() != items.size() + 1 || excl_ptr.back() > excl_rows.size()))
+            throw EngineError(SBR_ERR_INVALID_ARGUMENT, (std::string(me) + ": one exclusion range per query").c_str());
+        const std::vector<std::uint32_t> q = narrow(items);
+        bar.fit(q.size(), me, "query");
+        const std::uint32_t none = 0;
+        const float zero = 0.0f;
+        Above r;
+        const sbr_status st = detail::above_call(
+            [&](std::uint64_t* counts, std::uint64_t* total, std::uint64_t cap, std::uint32_t* ids, float* scores) {
+                if (bar.top)
+                    return sbr_audience_top_reps(replicas_->primary(), reps.empty() ? &zero : reps.data(), (std::uint64_t)(reps.size() / dim), q.data(),
+                                                   (std::uint64_t)q.size(), bar.n.data(), excl_ptr.empty() ? nullptr : excl_ptr.data(),
+                                                   excl_ptr.empty() ? nullptr : (excl_rows.empty() ? &none : excl_rows.data()), bar.cuts.data(), counts, total, cap, ids,
+                                                   scores);
+                return sbr_audience_above_reps(replicas_->primary(), reps.empty() ? &zero : reps.data(), (std::uint64_t)(reps.size() / dim), q.data(),
+                                               (std::uint64_t)q.size(), bar.th.data(), excl_ptr.empty() ? nullptr : excl_ptr.data(),
+                                               excl_ptr.empty() ? nullptr : (excl_rows.empty() ? &none : excl_rows.data()), counts, total, cap, ids,
+                                               scores);
+            },
+            q.size(), max_results, order, count_only, bar.top ? "sbr_audience_top_reps" : "sbr_audience_above_reps", bar, &r);
+        if (st == SBR_ERR_INVALID_PREDICTION) return Result<Above, PredictionError>::Err(PredictionError::InvalidPredictionValue);
+        return Result<Above, PredictionError>::Ok(std::move(r));
+    }
+  public:
     /// `audience_reps` without a k (sbr_audience_above_reps): for each query item EVERY row of `reps` that scores it >= its threshold
     /// (`thresholds`: one for all queries or one per query) — `ids` of the result are ROW indices.
     Result<Above, PredictionError> audience_above_reps(const std::vector<float>& reps, const std::vector<ItemId>& items,
@@ -1552,25 +1732,18 @@ class ImplicitSequenceModel : public OnlineRankingModel<ImplicitUser> {
                                                        const std::vector<std::uint32_t>& excl_rows = {},
                                                        std::uint64_t max_results = ABOVE_MAX_RESULTS, AboveOrder order = AboveOrder::Score,
                                                        bool count_only = false) const {
-        const std::size_t dim = (std::size_t)replicas_->hparams().embedding_dim;
-        if (reps.size() % dim) throw EngineError(SBR_ERR_INVALID_ARGUMENT, "audience_above_reps: rows of embedding_dim floats");
-        if (!excl_ptr.empty() && (excl_ptr.size() != items.size() + 1 || excl_ptr.back() > excl_rows.size()))
-            throw EngineError(SBR_ERR_INVALID_ARGUMENT, "audience_above_reps: one exclusion range per query");
-        const std::vector<std::uint32_t> q = narrow(items);
-        const std::vector<float> th = detail::above_thresholds(thresholds, q.size(), "audience_above_reps: one threshold, or one per query; no NaN");
-        const std::uint32_t none = 0;
-        const float zero = 0.0f;
-        Above r;
-        const sbr_status st = detail::above_call(
-            [&](std::uint64_t* counts, std::uint64_t* total, std::uint64_t cap, std::uint32_t* ids, float* scores) {
-                return sbr_audience_above_reps(replicas_->primary(), reps.empty() ? &zero : reps.data(), (std::uint64_t)(reps.size() / dim), q.data(),
-                                               (std::uint64_t)q.size(), th.data(), excl_ptr.empty() ? nullptr : excl_ptr.data(),
-                                               excl_ptr.empty() ? nullptr : (excl_rows.empty() ? &none : excl_rows.data()), counts, total, cap, ids,
-                                               scores);
-            },
-            q.size(), max_results, order, count_only, "sbr_audience_above_reps", &r);
-        if (st == SBR_ERR_INVALID_PREDICTION) return Result<Above, PredictionError>::Err(PredictionError::InvalidPredictionValue);
-        return Result<Above, PredictionError>::Ok(std::move(r));
+        return audience_reps_bar("audience_above_reps",
+                                 reps, items, detail::Bar::above(thresholds), excl_ptr, excl_rows, max_results, order, count_only);
+    }
+    /// `audience_reps` with a budget in place of k (sbr_audience_top_reps): for each query item its exact best n rows of `reps` —
+    /// `n`: one value for all queries or one per query, any size; an Above with `cuts`, ROW indices.
+    Result<Above, PredictionError> audience_top_reps(const std::vector<float>& reps, const std::vector<ItemId>& items,
+                                                     const std::vector<std::uint64_t>& n, const std::vector<std::uint64_t>& excl_ptr = {},
+                                                     const std::vector<std::uint32_t>& excl_rows = {},
+                                                     std::uint64_t max_results = ABOVE_MAX_RESULTS, AboveOrder order = AboveOrder::Score,
+                                                     bool count_only = false) const {
+        return audience_reps_bar("audience_top_reps",
+                                 reps, items, detail::Bar::best(n), excl_ptr, excl_rows, max_results, order, count_only);
     }
     /// The rows' counts of `audience_above_reps` without writing any pair: one scan.
     Result<Above, PredictionError> count_audience_above_reps(const std::vector<float>& reps, const std::vector<ItemId>& items,
@@ -1578,24 +1751,47 @@ class ImplicitSequenceModel : public OnlineRankingModel<ImplicitUser> {
                                                              const std::vector<std::uint32_t>& excl_rows = {}) const {
         return audience_above_reps(reps, items, thresholds, excl_ptr, excl_rows, 0, AboveOrder::Id, true);
     }
+  private:
+    /// The body the *_above and *_top forms share: `me` names the calling method in refusals, `bar` holds the thresholds or the
+    /// budgets.
+    Result<Above, PredictionError> audience_bar(const char* me, const data::CompressedInteractions& histories, const std::vector<ItemId>& items,
+                                                  detail::Bar bar, bool exclude_history,
+                                                  std::uint64_t max_results, AboveOrder order,
+                                                  bool count_only) const {
+        const std::vector<std::uint32_t> q = narrow(items);
+        bar.fit(q.size(), me, "query");
+        Above r;
+        const sbr_status st = detail::above_call(
+            [&](std::uint64_t* counts, std::uint64_t* total, std::uint64_t cap, std::uint32_t* ids, float* scores) {
+                if (bar.top)
+                    return sbr_audience_top(replicas_->primary(), histories.user_pointers().data(), histories.item_ids().data(),
+                                              (std::uint64_t)histories.num_users(), q.data(), (std::uint64_t)q.size(), bar.n.data(),
+                                              exclude_history ? 0u : SBR_RECOMMEND_INCLUDE_HISTORY, bar.cuts.data(), counts, total, cap, ids, scores);
+                return sbr_audience_above(replicas_->primary(), histories.user_pointers().data(), histories.item_ids().data(),
+                                          (std::uint64_t)histories.num_users(), q.data(), (std::uint64_t)q.size(), bar.th.data(),
+                                          exclude_history ? 0u : SBR_RECOMMEND_INCLUDE_HISTORY, counts, total, cap, ids, scores);
+            },
+            q.size(), max_results, order, count_only, bar.top ? "sbr_audience_top" : "sbr_audience_above", bar, &r);
+        if (st == SBR_ERR_INVALID_PREDICTION) return Result<Above, PredictionError>::Err(PredictionError::InvalidPredictionValue);
+        return Result<Above, PredictionError>::Ok(std::move(r));
+    }
+  public:
     /// `audience_above_reps` on `user_representations` of `histories` (sbr_audience_above): `ids` of the result are USER indices.
     /// With `exclude_history` a user whose history holds the query item is left out of that item's row.
     Result<Above, PredictionError> audience_above(const data::CompressedInteractions& histories, const std::vector<ItemId>& items,
                                                   const std::vector<float>& thresholds, bool exclude_history = true,
                                                   std::uint64_t max_results = ABOVE_MAX_RESULTS, AboveOrder order = AboveOrder::Score,
                                                   bool count_only = false) const {
-        const std::vector<std::uint32_t> q = narrow(items);
-        const std::vector<float> th = detail::above_thresholds(thresholds, q.size(), "audience_above: one threshold, or one per query; no NaN");
-        Above r;
-        const sbr_status st = detail::above_call(
-            [&](std::uint64_t* counts, std::uint64_t* total, std::uint64_t cap, std::uint32_t* ids, float* scores) {
-                return sbr_audience_above(replicas_->primary(), histories.user_pointers().data(), histories.item_ids().data(),
-                                          (std::uint64_t)histories.num_users(), q.data(), (std::uint64_t)q.size(), th.data(),
-                                          exclude_history ? 0u : SBR_RECOMMEND_INCLUDE_HISTORY, counts, total, cap, ids, scores);
-            },
-            q.size(), max_results, order, count_only, "sbr_audience_above", &r);
-        if (st == SBR_ERR_INVALID_PREDICTION) return Result<Above, PredictionError>::Err(PredictionError::InvalidPredictionValue);
-        return Result<Above, PredictionError>::Ok(std::move(r));
+        return audience_bar("audience_above",
+                            histories, items, detail::Bar::above(thresholds), exclude_history, max_results, order, count_only);
+    }
+    /// `audience_top_reps` on `user_representations` of `histories` (sbr_audience_top): USER indices.
+    Result<Above, PredictionError> audience_top(const data::CompressedInteractions& histories, const std::vector<ItemId>& items,
+                                                const std::vector<std::uint64_t>& n, bool exclude_history = true,
+                                                std::uint64_t max_results = ABOVE_MAX_RESULTS, AboveOrder order = AboveOrder::Score,
+                                                bool count_only = false) const {
+        return audience_bar("audience_top",
+                            histories, items, detail::Bar::best(n), exclude_history, max_results, order, count_only);
     }
     /// The rows' counts of `audience_above` without writing any pair.
     Result<Above, PredictionError> count_audience_above(const data::CompressedInteractions& histories, const std::vector<ItemId>& items,

@@ -849,6 +849,55 @@ sbr_status sbr_sessions_audience_above(sbr_sessions* st, const uint32_t* items, 
                                        uint32_t flags, uint64_t* out_counts, uint64_t* out_total, uint64_t capacity, uint32_t* out_ids,
                                        float* out_scores);
 
+/* TOP — the budget form of the scans: for each row r and a per-row budget n = n[r] (any value >= 0; SBR_RECOMMEND_MAX_K does not
+ * apply), the exact best n of the row.  Rows, columns and scores are ABOVE's: the eligible columns of row r are those
+ * sbr_*_above(thresholds[r] = -inf) returns, m_r of them.  The total order is every other call's: score descending, ties to the
+ * lower id, -0.0 == +0.0.  top(r, n) is the first min(n, m_r) eligible columns in that order, and the row's cut c_r (out_cuts [rows],
+ * required) is
+ *   the score of the last column returned   when m_r >= n >= 1 (a zero cut is written as +0.0, whichever zero that column holds);
+ *   -inf                                    when m_r < n: everything eligible, sbr_*_above(-inf)'s row;
+ *   +inf                                    when n == 0: an empty row.
+ * So for n <= SBR_RECOMMEND_MAX_K the row is the top-k sibling's row at k = n without its padding; for any n it is the first n
+ * entries, by (score descending, id ascending), of sbr_*_above(thresholds[r] = c_r)'s row; that call's count is >= n and the number
+ * of eligible scores > c_r is < n; of a tie group that straddles the cut exactly the lowest ids are kept.
+ * The result is CSR as ABOVE's: out_counts [rows] (required) = min(n[r], m_r), *out_total their sum, row r's pairs in ASCENDING id
+ * order (the hosts layers sort a row by score).  out_ids and out_scores both NULL: the select only — cuts and counts, no pair; the
+ * cheap form.  Pairs are written only if *out_total <= capacity; otherwise SBR_OK with counts, cuts and the total, and no pair (a
+ * call of more than 8 192 rows may have written the chunks that still fitted).  The capacity is held against the pairs returned;
+ * on the device a row's fill first holds every score tied at its cut, which under mass ties is more than n (in ranges of 256 MB of
+ * entries, one row at least).  That intermediate, G = sum over rows of #{eligible score >= c_r}, is not refused at any size: the
+ * device memory it takes is bounded by the ranges, the time is not.  A call with pairs runs 1 + ceil(8 G / 256 MB) + (rows that
+ * alone exceed a range) catalogue scans behind the select's 8, so where ties are few (G close to *out_total) that is the ABOVE
+ * call's cost, and in the worst case — every score of every row equal — G = rows x columns whatever n is: 8 192 rows x 1e6 columns
+ * at n = 1 write 8.2e9 pairs in about 245 rescans to return 8 192.  A caller that cannot rule out mass ties asks for the cuts alone
+ * first (NULL pair outputs) and sizes G with the ABOVE call's count form at those cuts.
+ * Cost: 8 catalogue scans per chunk of 8 192 rows for the cuts (a radix select on the scores' bits, 4 bits a scan, no host round
+ * trip between them), then with pairs ABOVE's count and fill at the cuts and a trim.
+ * SBR_ERR_INVALID_ARGUMENT, before any launch: a NULL n / out_cuts / out_counts / out_total, out_scores without out_ids, and
+ * wherever the sibling gives it.  SBR_ERR_INVALID_PREDICTION: a non-finite score of any scanned pair of an existing row — also of
+ * a row with n == 0.  Deterministic (integer counts only); reads parameters only.
+ * Not offered: a device-side sort by score, a fill that stops inside a tie group, among= subsets, a tag filter in the audience
+ * orientation. */
+sbr_status sbr_recommend_top(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users, const uint64_t* n,
+                             uint32_t flags, const uint32_t* any_of, const uint32_t* none_of, float* out_cuts, uint64_t* out_counts,
+                             uint64_t* out_total, uint64_t capacity, uint32_t* out_ids, float* out_scores);
+sbr_status sbr_recommend_top_reps(sbr_model* m, const float* reps, uint64_t num_users, const uint64_t* n, const uint64_t* excl_ptr,
+                                  const uint32_t* excl_items, const uint32_t* any_of, const uint32_t* none_of, float* out_cuts,
+                                  uint64_t* out_counts, uint64_t* out_total, uint64_t capacity, uint32_t* out_ids, float* out_scores);
+sbr_status sbr_sessions_recommend_top(sbr_sessions* st, const uint32_t* slots, uint64_t n, const uint64_t* top_n, const uint64_t* excl_ptr,
+                                      const uint32_t* excl_items, uint32_t flags, const uint32_t* any_of, const uint32_t* none_of,
+                                      float* out_cuts, uint64_t* out_counts, uint64_t* out_total, uint64_t capacity, uint32_t* out_ids,
+                                      float* out_scores);
+sbr_status sbr_audience_top_reps(sbr_model* m, const float* reps, uint64_t num_rows, const uint32_t* items, uint64_t num_queries,
+                                 const uint64_t* n, const uint64_t* excl_ptr, const uint32_t* excl_rows, float* out_cuts, uint64_t* out_counts,
+                                 uint64_t* out_total, uint64_t capacity, uint32_t* out_ids, float* out_scores);
+sbr_status sbr_audience_top(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users, const uint32_t* items,
+                            uint64_t num_queries, const uint64_t* n, uint32_t flags, float* out_cuts, uint64_t* out_counts, uint64_t* out_total,
+                            uint64_t capacity, uint32_t* out_ids, float* out_scores);
+sbr_status sbr_sessions_audience_top(sbr_sessions* st, const uint32_t* items, uint64_t num_queries, const uint64_t* n, const uint32_t* slots,
+                                     uint64_t num_slots, const uint64_t* excl_ptr, const uint32_t* excl_slots, uint32_t flags, float* out_cuts,
+                                     uint64_t* out_counts, uint64_t* out_total, uint64_t capacity, uint32_t* out_ids, float* out_scores);
+
 /* ≙ the serde derives (lstm.rs:204,386; ewma.rs:208,401): element counts and raw access. */
 sbr_status sbr_model_param_count(const sbr_model* m, int32_t which, uint64_t* out_count);
 sbr_status sbr_model_get_param(sbr_model* m, int32_t which, float* host_out, uint64_t count);

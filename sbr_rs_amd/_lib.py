@@ -181,6 +181,12 @@ def load():
         "sbr_audience_above_reps": [vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp, vp, vp, u64p, C.c_uint64, vp, vp],
         "sbr_audience_above": [vp, vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint32, vp, u64p, C.c_uint64, vp, vp],
         "sbr_sessions_audience_above": [vp, vp, C.c_uint64, vp, vp, C.c_uint64, vp, vp, C.c_uint32, vp, u64p, C.c_uint64, vp, vp],
+        "sbr_recommend_top": [vp, vp, vp, C.c_uint64, vp, C.c_uint32, vp, vp, vp, vp, u64p, C.c_uint64, vp, vp],
+        "sbr_recommend_top_reps": [vp, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, u64p, C.c_uint64, vp, vp],
+        "sbr_sessions_recommend_top": [vp, vp, C.c_uint64, vp, vp, vp, C.c_uint32, vp, vp, vp, vp, u64p, C.c_uint64, vp, vp],
+        "sbr_audience_top_reps": [vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp, vp, vp, vp, u64p, C.c_uint64, vp, vp],
+        "sbr_audience_top": [vp, vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint32, vp, vp, u64p, C.c_uint64, vp, vp],
+        "sbr_sessions_audience_top": [vp, vp, C.c_uint64, vp, vp, C.c_uint64, vp, vp, C.c_uint32, vp, vp, u64p, C.c_uint64, vp, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -245,4 +251,6 @@ DECLARED_SYMBOLS = [
     "sbr_softmax_frac_bits", "sbr_softmax_weights", "sbr_softmax_weights_rows", "sbr_log_partition", "sbr_log_partition_reps", "sbr_sessions_log_partition",
     "sbr_recommend_above", "sbr_recommend_above_reps", "sbr_sessions_recommend_above",
     "sbr_audience_above_reps", "sbr_audience_above", "sbr_sessions_audience_above",
+    "sbr_recommend_top", "sbr_recommend_top_reps", "sbr_sessions_recommend_top",
+    "sbr_audience_top_reps", "sbr_audience_top", "sbr_sessions_audience_top",
 ]

@@ -198,6 +198,15 @@ def build_above_tests(force: bool = False, verbose: bool = True) -> str:
     return _build_cpp_program(ABOVE_SRC, ABOVE_BIN, force, verbose)
 
 
+TOP_SRC = os.path.join(REPO, "tests", "cpp", "top_tests.cpp")
+TOP_BIN = os.path.join(REPO, "tests", "cpp", "_build", "top_tests")
+
+
+def build_top_tests(force: bool = False, verbose: bool = True) -> str:
+    """g++ build of the C++ host layer's recommend_top / audience_top test program."""
+    return _build_cpp_program(TOP_SRC, TOP_BIN, force, verbose)
+
+
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv))
     print(build_facade_tests(force="--force" in sys.argv))
@@ -214,3 +223,4 @@ if __name__ == "__main__":
     print(build_sampled_tests(force="--force" in sys.argv))
     print(build_partition_tests(force="--force" in sys.argv))
     print(build_above_tests(force="--force" in sys.argv))
+    print(build_top_tests(force="--force" in sys.argv))

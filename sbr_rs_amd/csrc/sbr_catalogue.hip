@@ -1475,7 +1475,10 @@ __global__ __launch_bounds__(64) void partition_finish_kernel(ModelView m, const
  *   in.  The cursors live in LDS by slot, each read by its half-wave's 32 lanes and then advanced by its lane 0: held in 16 registers
  *   per lane through the unrolled writes they took the d = 128 kernel to 256 VGPRs and 84 bytes of scratch, in LDS it needs 170 and
  *   none.  Every write is checked against the slot's end (offsets[row * G + range + 1], and the buffer's size): a pass beyond it is
- *   dropped and raises *overrun_flag — a disagreement between the two launches becomes an error, never a store out of bounds. */
+ *   dropped and raises *overrun_flag — a disagreement between the two launches becomes an error, never a store out of bounds.
+ * KEEP IN STEP: select_gemm_kernel below restates this kernel's prologue and stages 1, 3 and 4 of `passes` (the staging, the tag
+ *   test, the exclusion search); recommend_top is only exact if the select and this count / fill pass the same columns, so a
+ *   change to one of those stages here is made there as well (tests/test_top_gpu.py holds the two against each other). */
 template <int D, class Score, class Filter, bool Fill>
 __global__ __launch_bounds__(256, D <= 128 ? 2 : 1) void above_gemm_kernel(ModelView m, const float* reps, const int* rep_row, uint32_t num_users,
                                                                           const float* thresholds, const uint64_t* excl_ptr,
@@ -1676,7 +1679,317 @@ __global__ __launch_bounds__(256, D <= 128 ? 2 : 1) void above_gemm_kernel(Model
     }
     if (__any(bad) && lane == 0) atomicOr(nonfinite_flag, 1u);
 }
+
+// ------------------------------------------------------------------------------------------------
+// recommend_top / audience_top: the n-th largest eligible score of a row — a radix select over scores that are never written, one
+// catalogue scan per 4-bit digit of the key, top digit first; above_gemm_kernel then runs at the cut and top_trim_kernel keeps n
+// ------------------------------------------------------------------------------------------------
+/* the monotone u32 of a score's f32 bits: a < b as floats <=> key(a) < key(b); -0.0 and +0.0 share +0.0's key */
+__device__ __forceinline__ uint32_t select_key(float sc) {
+    const uint32_t b = sc == 0.0f ? 0u : __float_as_uint(sc);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float select_unkey(uint32_t key) { return __uint_as_float((key & 0x80000000u) ? (key & 0x7FFFFFFFu) : ~key); }
+
+/* One round of the select, in above_gemm_kernel's shape (128 rows per workgroup, grid (row tiles, item ranges)) and with its pass
+ * predicate, the threshold compare replaced by the row's active interval: the keys whose decided bits (mask[u]) equal prefix[u].
+ * A row that is decided (n = 0, or fewer eligible columns than n) has mask = 0 and prefix = 1, which no key meets.  Order as above:
+ *   1. the non-finite test on every scanned score of an existing row;
+ *   2. (key & mask) == prefix — everything in round 0, what shares the decided digits after it;
+ *   3. the tag test;
+ *   4. only for survivors, the binary search of the row's exclusion segment.
+ * KEEP IN STEP: the prologue and stages 1, 3 and 4 are above_gemm_kernel's, restated here as a separate template so that its
+ * instantiations keep their code; the count and fill that follow the select must pass exactly the columns it binned, so a change
+ * to one of those stages is made in both kernels.
+ * A survivor is binned by its digit (key >> shift) & 15 into hist[slot][16] in LDS.  Slot p = wave * 32 + hh * 16 + q belongs to
+ * one half-wave alone, so the bins need no atomics: per q the half-waves agree on a digit (the first pending lane's), ballot the
+ * lanes that hold it, and their lane 0 adds the popcount with a plain read and write: one turn per distinct digit among the
+ * pending lanes.  A model's scores share their sign and most of their exponent, so rounds 0 to 2 bin nearly every score (2 to
+ * 2.7 count scans each at 8 192 x 1e6, d = 128) and survivors are rare only from round 4 on, where the block is skipped under
+ * __any and a round costs a count scan.  4 bits: 16 x 128 x 4 B = 8 KB beside the tiles keeps two workgroups per CU at
+ * d <= 128; 8 bits would need 128 KB.  At the range's end the non-zero bins are added to
+ * hist_out[u * 16 + digit] with integer device atomics: the sums do not depend on the order of arrival. */
+template <int D, class Score, class Filter>
+__global__ __launch_bounds__(256, D <= 128 ? 2 : 1) void select_gemm_kernel(ModelView m, const float* reps, const int* rep_row, uint32_t num_users,
+                                                                           const uint32_t* prefix, const uint32_t* mask, int shift,
+                                                                           const uint64_t* excl_ptr, const uint32_t* excl_items,
+                                                                           uint32_t items_per_group, uint32_t* hist_out, uint32_t* nonfinite_flag,
+                                                                           typename Filter::Args fa, typename Score::Args sa) {
+    __shared__ float Es[2][32 * ItemTiles<D>::LDE];
+    __shared__ float Bs[2][32];
+    __shared__ __align__(16) float qbS[Score::query ? 128 : 4];
+    __shared__ uint32_t Ts[2][Filter::on ? 32 : 1];
+    __shared__ __align__(16) uint32_t anyS[Filter::on ? 128 : 4];
+    __shared__ __align__(16) uint32_t anyZ[Filter::on ? 128 : 4];
+    __shared__ __align__(16) uint32_t noneS[Filter::on ? 128 : 4];
+    // per-row state by slot (slot_user)
+    __shared__ __align__(16) uint32_t prefS[128];
+    __shared__ __align__(16) uint32_t maskS[128];
+    __shared__ uint64_t exLo[128];
+    __shared__ uint64_t exHi[128];
+    __shared__ uint32_t hist[128 * 16];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = tid >> 6;
+    const int l31 = lane & 31;
+    const int hh = lane >> 5;
+    const uint32_t u0 = blockIdx.x * 128 + wave * 32;
+    float a[D / 2];
+    load_user_fragments<D>(a, reps, rep_row, num_users, u0);
+    if (tid < 128) {
+        const uint32_t u = blockIdx.x * 128 + (uint32_t)slot_user(tid);
+        const bool real = u < num_users;
+        prefS[tid] = real ? prefix[u] : 1u;
+        maskS[tid] = real ? mask[u] : 0u;
+        exLo[tid] = real && excl_ptr ? excl_ptr[u] : 0ull;
+        exHi[tid] = real && excl_ptr ? excl_ptr[u + 1] : 0ull;
+        if constexpr (Filter::on) {
+            const uint32_t any = real ? fa.any_of[u] : 0u;
+            anyS[tid] = any;
+            anyZ[tid] = any == 0u ? 1u : 0u;
+            noneS[tid] = real ? fa.none_of[u] : 0u;
+        }
+        if constexpr (Score::query) qbS[tid] = real ? sa.qb[rep_row[u]] : 0.0f;
+    }
+    for (int i = tid; i < 128 * 16; i += 256) hist[i] = 0u;
+    uint32_t umask = 0;
+#pragma unroll
+    for (int q = 0; q < 16; ++q)
+        if (acc_user(u0, q, hh) < num_users) umask |= 1u << q;
+    bool bad = false;
+    ItemTiles<D> tiles(m, items_per_group);
+    const int ntiles = tiles.ntiles;
+    if (ntiles > 0) {
+        tiles.fetch(m, 0);
+        tiles.stage(Es[0], Bs[0]);
+        if constexpr (Filter::on) {
+            tiles.fetch_tags(fa.tags, 0);
+            tiles.stage_tags(Ts[0]);
+        }
+    }
+    __syncthreads();
+    const int pbase = wave * 32 + hh * 16;
+    for (int tile = 0; tile < ntiles; ++tile) {
+        const int buf = tile & 1;
+        if (tile + 1 < ntiles) {
+            tiles.fetch(m, tile + 1);
+            if constexpr (Filter::on) tiles.fetch_tags(fa.tags, tile + 1);
+        }
+        f32x16 acc = tile_dots<D>(a, Es[buf]);
+        const float bias = Bs[buf][l31];
+        if constexpr (Score::query) {
+#pragma unroll
+            for (int q4 = 0; q4 < 4; ++q4) {
+                const float4 b4 = ld4(&qbS[pbase + 4 * q4]);
+                acc[4 * q4 + 0] = b4.x + acc[4 * q4 + 0];
+                acc[4 * q4 + 1] = b4.y + acc[4 * q4 + 1];
+                acc[4 * q4 + 2] = b4.z + acc[4 * q4 + 2];
+                acc[4 * q4 + 3] = b4.w + acc[4 * q4 + 3];
+            }
+        }
+        const uint32_t id = tiles.i_begin + (uint32_t)tile * 32 + (uint32_t)l31;
+        uint32_t pend = id < tiles.i_end ? umask : 0u;
+#pragma unroll
+        for (int q4 = 0; q4 < 4; ++q4) {
+            const uint4 p4 = *reinterpret_cast<const uint4*>(&prefS[pbase + 4 * q4]);
+            const uint4 m4 = *reinterpret_cast<const uint4*>(&maskS[pbase + 4 * q4]);
+            const uint32_t pq[4] = {p4.x, p4.y, p4.z, p4.w};
+            const uint32_t mq[4] = {m4.x, m4.y, m4.z, m4.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int q = 4 * q4 + j;
+                const float sc = TK_SCORE(q);
+                if (((pend >> q) & 1u) && !(sc - sc == 0.0f)) bad = true;
+                if ((select_key(sc) & mq[j]) != pq[j]) pend &= ~(1u << q);
+            }
+        }
+        if constexpr (Filter::on) {
+            const uint32_t tag = Ts[buf][l31];
+            uint32_t drop = 0;
+#pragma unroll
+            for (int q4 = 0; q4 < 4; ++q4) {
+                const uint4 a4 = *reinterpret_cast<const uint4*>(&anyS[pbase + 4 * q4]);
+                const uint4 z4 = *reinterpret_cast<const uint4*>(&anyZ[pbase + 4 * q4]);
+                const uint4 n4 = *reinterpret_cast<const uint4*>(&noneS[pbase + 4 * q4]);
+                const uint32_t any[4] = {a4.x, a4.y, a4.z, a4.w};
+                const uint32_t anyz[4] = {z4.x, z4.y, z4.z, z4.w};
+                const uint32_t none[4] = {n4.x, n4.y, n4.z, n4.w};
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const uint32_t hit = (tag & none[j]) != 0u ? 1u : 0u;
+                    const uint32_t miss = ((tag & any[j]) | anyz[j]) == 0u ? 1u : 0u;
+                    drop |= (hit | miss) << (4 * q4 + j);
+                }
+            }
+            pend &= ~drop;
+        }
+        if (excl_ptr) {
+            for (uint32_t rem = pend; rem; rem &= rem - 1u) {
+                const int q = __ffs((int)rem) - 1;
+                uint64_t lo = exLo[pbase + q];
+                const uint64_t e1 = exHi[pbase + q];
+                uint64_t hi = e1;
+                while (lo < hi) {
+                    const uint64_t mid = (lo + hi) >> 1;
+                    if (excl_items[mid] < id) lo = mid + 1; else hi = mid;
+                }
+                if (lo < e1 && excl_items[lo] == id) pend &= ~(1u << q);
+            }
+        }
+        if (__any(pend != 0u)) {
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                const bool p = ((pend >> q) & 1u) != 0u;
+                const uint32_t digit = (select_key(TK_SCORE(q)) >> shift) & 15u;
+                uint64_t rem = __ballot(p);
+                while (rem) { /* wave-uniform: one turn per distinct digit among the pending lanes */
+                    const uint32_t dg = (uint32_t)__shfl((int)digit, (int)__ffsll((unsigned long long)rem) - 1, 64);
+                    const uint64_t same = __ballot(p && digit == dg);
+                    const uint32_t mine = hh ? (uint32_t)(same >> 32) : (uint32_t)same;
+                    if (l31 == 0 && mine) hist[(pbase + q) * 16 + (int)dg] += (uint32_t)__popc(mine);
+                    rem &= ~same;
+                }
+            }
+        }
+        if (tile + 1 < ntiles) {
+            tiles.stage(Es[buf ^ 1], Bs[buf ^ 1]);
+            if constexpr (Filter::on) tiles.stage_tags(Ts[buf ^ 1]);
+        }
+        __syncthreads();
+    }
+    for (int i = tid; i < 128 * 16; i += 256) {
+        const uint32_t u = blockIdx.x * 128 + (uint32_t)slot_user(i >> 4);
+        const uint32_t c = hist[i];
+        if (c && u < num_users) atomicAdd(&hist_out[(size_t)u * 16 + (i & 15)], c);
+    }
+    if (__any(bad) && lane == 0) atomicOr(nonfinite_flag, 1u);
+}
 #undef TK_SCORE
+
+/* Between the select's rounds, one thread per row.  round < 0 starts the search: wanted = n (0: decided, cut +inf), nothing
+ * decided, the histogram cleared.  round r has binned digit 28 - 4 r: the thread sums the row's 16 bins, in round 0 decides a row
+ * with fewer eligible columns than wanted (cut -inf, everything eligible), else walks the bins from the top until the running
+ * count reaches what is still wanted, fixes that digit and keeps the count above it in gt.  After round 7 the key is whole: cut is
+ * its f32 (a zero is +0.0), gt = #{score > cut}, final = min(n, eligible) and keep_eq = n - gt, what top_trim_kernel keeps of the
+ * scores equal to the cut.  The bins are cleared for the next round. */
+__global__ __launch_bounds__(256) void select_step_kernel(uint32_t num_rows, int round, const uint64_t* n, uint64_t* wanted, uint32_t* prefix,
+                                                          uint32_t* mask, uint32_t* hist, float* cuts, uint32_t* gt, uint32_t* final_counts,
+                                                          uint32_t* keep_eq) {
+    const uint32_t r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= num_rows) return;
+    uint32_t* h = hist + (size_t)r * 16;
+    if (round < 0) {
+        const uint64_t w = n[r];
+        wanted[r] = w;
+        prefix[r] = w ? 0u : 1u;
+        mask[r] = 0u;
+        gt[r] = 0u;
+        final_counts[r] = 0u;
+        keep_eq[r] = 0u;
+        cuts[r] = w ? -INFINITY : INFINITY;
+        for (int b = 0; b < 16; ++b) h[b] = 0u;
+        return;
+    }
+    if (mask[r] == 0u && prefix[r] == 1u) return; /* decided */
+    const int shift = 28 - 4 * round;
+    uint32_t c[16];
+    uint64_t total = 0;
+    for (int b = 0; b < 16; ++b) {
+        c[b] = h[b];
+        h[b] = 0u;
+        total += c[b];
+    }
+    const uint64_t w = wanted[r];
+    if (total < w) { /* only in round 0: later rounds hold at least `wanted` in the interval */
+        cuts[r] = -INFINITY;
+        gt[r] = (uint32_t)total;
+        final_counts[r] = (uint32_t)total;
+        keep_eq[r] = 0u;
+        mask[r] = 0u;
+        prefix[r] = 1u;
+        return;
+    }
+    uint64_t run = 0;
+    int b = 0;
+    bool found = false;
+#pragma unroll
+    for (int i = 15; i >= 1; --i) { /* unrolled: c stays in registers; bin 0 takes what the others did not */
+        if (!found && run + c[i] >= w) {
+            found = true;
+            b = i;
+        }
+        if (!found) run += c[i];
+    }
+    const uint32_t pre = prefix[r] | ((uint32_t)b << shift);
+    const uint32_t g = gt[r] + (uint32_t)run;
+    wanted[r] = w - run;
+    gt[r] = g;
+    if (shift > 0) {
+        prefix[r] = pre;
+        mask[r] |= 15u << shift;
+        return;
+    }
+    cuts[r] = select_unkey(pre);
+    final_counts[r] = g + (uint32_t)(w - run);
+    keep_eq[r] = (uint32_t)(w - run);
+    mask[r] = 0u;
+    prefix[r] = 1u;
+}
+
+/* Row r of a fill at the cuts, ascending column at in_ids / in_scores [offsets[r G] - offsets[0], + ge[r]), to its final place
+ * out_ids / out_scores [out_off[r], out_off[r + 1]): every entry over the cut and the first keep_eq[r] that equal it (the f32
+ * compare: both zeros), column order kept.  One workgroup per row, 256 entries at a time; an entry's place is the count of kept
+ * entries before it, which is #{over the cut before it} + min(#{equal before it}, keep_eq).  Reads and writes are bounds-checked:
+ * one outside its buffer or its row's final range is dropped and raises *overrun_flag. */
+__global__ __launch_bounds__(256) void top_trim_kernel(const uint32_t* in_ids, const float* in_scores, uint32_t in_cap, const uint64_t* offsets,
+                                                       uint32_t G, const uint32_t* ge, const float* cuts, const uint32_t* keep_eq,
+                                                       const uint64_t* out_off, uint32_t* out_ids, float* out_scores, uint32_t out_cap,
+                                                       uint32_t* overrun_flag) {
+    __shared__ uint32_t wg[4], we[4];
+    const uint32_t r = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint64_t start = offsets[(size_t)r * G] - offsets[0];
+    const uint32_t len = ge[r];
+    const float cut = cuts[r];
+    const uint32_t keep = keep_eq[r];
+    const uint64_t o0 = out_off[r], o1 = out_off[r + 1];
+    uint32_t gt_before = 0, eq_before = 0; /* of the row's entries ahead of this round's 256 */
+    bool over = false;
+    for (uint32_t base = 0; base < len; base += 256) {
+        const uint64_t at = start + base + (uint32_t)tid;
+        const bool have = base + (uint32_t)tid < len && at < (uint64_t)in_cap;
+        if (base + (uint32_t)tid < len && !have) over = true;
+        const uint32_t id = have ? in_ids[at] : 0u;
+        const float sc = have ? in_scores[at] : 0.0f;
+        const bool is_gt = have && sc > cut, is_eq = have && sc == cut;
+        const uint64_t bg = __ballot(is_gt), be = __ballot(is_eq);
+        if (lane == 0) {
+            wg[wave] = (uint32_t)__popcll(bg);
+            we[wave] = (uint32_t)__popcll(be);
+        }
+        __syncthreads();
+        const uint64_t below = (1ull << lane) - 1ull;
+        uint32_t g = gt_before + (uint32_t)__popcll(bg & below), e = eq_before + (uint32_t)__popcll(be & below);
+        for (int w = 0; w < 4; ++w) {
+            if (w < wave) {
+                g += wg[w];
+                e += we[w];
+            }
+            gt_before += wg[w];
+            eq_before += we[w];
+        }
+        if (is_gt || (is_eq && e < keep)) {
+            const uint64_t pos = o0 + g + (e < keep ? e : keep);
+            if (pos < o1 && pos < (uint64_t)out_cap) {
+                out_ids[pos] = id;
+                if (out_scores) out_scores[pos] = sc;
+            } else
+                over = true;
+        }
+        __syncthreads();
+    }
+    if (__any(over) && lane == 0) atomicOr(overrun_flag, 1u);
+}
 
 /* The exclusive scan of counts [n G] in (row, range) order into offsets [n G + 1], and the rows' totals; one workgroup: each
  * thread sums a contiguous piece, the 1 024 sums are scanned in LDS, and the piece is walked again.  n G is at most a few hundred
@@ -1913,6 +2226,47 @@ int launch_above_fill(const ModelView& cat, const float* reps, const float* qb, 
     if (nr == 0 || cat.num_items == 0 || out_cap == 0) return 0;
     above_scan<true>(cat, reps, qb, sc, r0, nr, out_ids, out_scores, out_cap, s);
     return 1;
+}
+
+int launch_top_select(const ModelView& cat, const float* reps, const float* qb, const AboveScan& sc, const TopSelect& ts, hipStream_t s) {
+    if (sc.n == 0) return 0;
+    const dim3 rows((sc.n + 255) / 256);
+    auto step = [&](int round) {
+        hipLaunchKernelGGL(select_step_kernel, rows, dim3(256), 0, s, sc.n, round, ts.n, ts.wanted, ts.prefix, ts.mask, ts.hist, ts.cuts, ts.gt,
+                           ts.final_counts, ts.keep_eq);
+    };
+    step(-1);
+    const dim3 grid((sc.n + 127) / 128, sc.groups);
+    for (int round = 0; round < 8; ++round) {
+        const int shift = 28 - 4 * round;
+        if (cat.num_items) { /* an empty catalogue: every bin stays zero and round 0 decides every row */
+            DISPATCH_D(cat.d, {
+                if (qb)
+                    hipLaunchKernelGGL((select_gemm_kernel<DD, QueryBias, NoFilter>), grid, dim3(256), 0, s, cat, reps, sc.rep_row, sc.n, ts.prefix,
+                                       ts.mask, shift, sc.excl_ptr, sc.excl_items, sc.per, ts.hist, sc.nonfinite_flag, NoFilter::Args{},
+                                       QueryBias::Args{qb});
+                else if (sc.f.tags)
+                    hipLaunchKernelGGL((select_gemm_kernel<DD, BiasAdd, TagFilter>), grid, dim3(256), 0, s, cat, reps, sc.rep_row, sc.n, ts.prefix,
+                                       ts.mask, shift, sc.excl_ptr, sc.excl_items, sc.per, ts.hist, sc.nonfinite_flag,
+                                       TagFilter::Args{sc.f.tags, sc.f.any_of, sc.f.none_of}, BiasAdd::Args{});
+                else
+                    hipLaunchKernelGGL((select_gemm_kernel<DD, BiasAdd, NoFilter>), grid, dim3(256), 0, s, cat, reps, sc.rep_row, sc.n, ts.prefix,
+                                       ts.mask, shift, sc.excl_ptr, sc.excl_items, sc.per, ts.hist, sc.nonfinite_flag, NoFilter::Args{},
+                                       BiasAdd::Args{});
+            });
+        }
+        step(round);
+    }
+    return cat.num_items ? 17 : 9;
+}
+
+int launch_top_trim(const AboveScan& sc, const TopSelect& ts, uint32_t r0, uint32_t nr, const uint32_t* in_ids, const float* in_scores,
+                    uint32_t in_cap, uint32_t* out_ids, float* out_scores, uint32_t out_cap, hipStream_t s) {
+    if (nr == 0) return 0;
+    hipLaunchKernelGGL(above_offsets_kernel, dim3(1), dim3(1024), 0, s, ts.final_counts + r0, nr, 1u, ts.out_off, ts.out_tot);
+    hipLaunchKernelGGL(top_trim_kernel, dim3(nr), dim3(256), 0, s, in_ids, in_scores, in_cap, sc.offsets + (size_t)r0 * sc.groups, sc.groups,
+                       sc.totals + r0, ts.cuts + r0, ts.keep_eq + r0, ts.out_off, out_ids, out_scores, out_cap, sc.overrun_flag);
+    return 2;
 }
 
 int launch_above_ids(const uint32_t* row_ids, uint32_t* ids, uint64_t n, hipStream_t s) {

@@ -4079,7 +4079,10 @@ namespace {
 /* The threshold form of a scan (recommend_above / audience_above; not with item rows, a subset, a selection, noise or a partition):
  * every scanned column whose score is >= thresholds[row], as CSR.  out_counts [rows of the call] always; the pairs go to out_ids /
  * out_scores (host, `capacity` entries; out_ids null: counts only, out_scores alone may be null) in row order while the running
- * total fits the capacity — once it does not, the remaining chunks are counted only.  total: the pairs counted so far. */
+ * total fits the capacity — once it does not, the remaining chunks are counted only.  total: the pairs counted so far.
+ * The budget form (recommend_top / audience_top) is the same descriptor with n in place of thresholds: the first min(n[row],
+ * eligible) columns of each row in the total order, out_counts that number and out_cuts [rows] the rows' cuts; the capacity is
+ * held against the sum of those counts, whatever the scores tied at the cuts take on the device. */
 struct Above {
     const float* thresholds;
     uint64_t* out_counts;
@@ -4087,6 +4090,8 @@ struct Above {
     uint32_t* out_ids;
     float* out_scores;
     uint64_t total;
+    const uint64_t* n = nullptr; /* the budget form: thresholds is null */
+    float* out_cuts = nullptr;
 };
 
 /* the output arguments the *_above calls share: false for a missing array, scores without ids, or a NaN threshold */
@@ -4096,6 +4101,14 @@ bool above_args(const float* thresholds, uint64_t n, uint64_t* out_counts, uint6
     for (uint64_t i = 0; i < n; ++i)
         if (std::isnan(thresholds[i])) return false;
     *out = Above{thresholds, out_counts, capacity, out_ids, out_scores, 0};
+    return true;
+}
+
+/* the same for the *_top calls: n (any value) where the thresholds stand, and the cuts */
+bool top_args(const uint64_t* n, uint64_t rows, float* out_cuts, uint64_t* out_counts, uint64_t* out_total, uint64_t capacity, uint32_t* out_ids,
+              float* out_scores, Above* out) {
+    if (!out_total || (rows && (!n || !out_counts || !out_cuts)) || (out_scores && !out_ids)) return false;
+    *out = Above{nullptr, out_counts, capacity, out_ids, out_scores, 0, n, out_cuts};
     return true;
 }
 
@@ -4117,13 +4130,22 @@ struct AboveBufs {
     uint32_t *counts, *totals, *over;
     uint64_t* offsets;
     uint32_t groups = 0, per = 0;
-    void carve(DeviceArena& ar, uint32_t num_items, size_t nu) {
+    sbr::TopSelect ts{}; /* top: the select's per-row search state; its cuts are th */
+    void carve(DeviceArena& ar, uint32_t num_items, size_t nu, bool top) {
         groups = sbr::above_groups((uint32_t)nu, num_items, &per);
         th = ar.take<float>(nu);
         counts = ar.take<uint32_t>(nu * groups);
         offsets = ar.take<uint64_t>(nu * groups + 1);
         totals = ar.take<uint32_t>(nu);
         over = ar.take<uint32_t>(1);
+        if (!top) return;
+        ts.cuts = th;
+        ts.n = ts.wanted = ar.take<uint64_t>(nu); /* the step kernel's start reads n[r] and writes wanted[r]: one array serves */
+        ts.out_off = ar.take<uint64_t>(nu + 1);
+        ts.prefix = ar.take<uint32_t>(nu); ts.mask = ar.take<uint32_t>(nu);
+        ts.hist = ar.take<uint32_t>(nu * 16);
+        ts.gt = ar.take<uint32_t>(nu); ts.final_counts = ar.take<uint32_t>(nu); ts.keep_eq = ar.take<uint32_t>(nu);
+        ts.out_tot = ar.take<uint32_t>(nu);
     }
 };
 
@@ -4131,22 +4153,38 @@ struct AboveBufs {
  * scan reads and returns its launches), the rows' totals read back — as.n x 4 bytes — and, while the call's running total fits the
  * capacity, the fill over consecutive row ranges of the chunk whose entries fit above_fill_entries() (at least one row each), every
  * range copied to the host at its running offset.  cat / A / qb: launch_above_count's; row_ids non-null (audience with named ids):
- * what the written positions stand for.  as.thresholds is uploaded here. */
-sbr_status above_chunk(sbr_model* m, const sbr::ModelView& cat, const float* A, const float* qb, const sbr::AboveScan& as, const uint32_t* row_ids,
-                       uint64_t row0, Above* ab, const std::function<int()>& prelaunch) {
+ * what the written positions stand for.  as.thresholds is uploaded here.
+ * The budget form (ab->n; ts: the chunk's select state): the select runs first, behind `prelaunch`, and leaves the cuts in
+ * as.thresholds; the cuts and the final counts are read back (as.n x 8 bytes) and are all a call without pair outputs runs.  With
+ * pairs the count scan follows at the cuts — its totals hold every score tied at a cut and size the fill — and every fill range is
+ * trimmed on the device to its rows' final counts before it is copied out. */
+sbr_status above_chunk(sbr_model* m, const sbr::ModelView& cat, const float* A, const float* qb, const sbr::AboveScan& as, const sbr::TopSelect& ts,
+                       const uint32_t* row_ids, uint64_t row0, Above* ab, const std::function<int()>& prelaunch) {
     const size_t nu = as.n;
-    HIPCHK(hipMemcpyAsync(const_cast<float*>(as.thresholds), ab->thresholds + row0, nu * 4, hipMemcpyHostToDevice, m->stream));
-    std::vector<uint32_t> totals(nu, 0);
-    SBRCHK(scan_launch(m, as.nonfinite_flag, [&] { return prelaunch() + sbr::launch_above_count(cat, A, qb, as, m->stream); },
-                       {{totals.data(), as.totals, nu * 4}}));
+    const bool top = ab->n != nullptr;
+    std::vector<uint32_t> totals(nu, 0), finals;
+    if (top) {
+        finals.assign(nu, 0);
+        HIPCHK(hipMemcpyAsync(ts.wanted, ab->n + row0, nu * 8, hipMemcpyHostToDevice, m->stream));
+        SBRCHK(scan_launch(m, as.nonfinite_flag, [&] { return prelaunch() + sbr::launch_top_select(cat, A, qb, as, ts, m->stream); },
+                           {{finals.data(), ts.final_counts, nu * 4}, {ab->out_cuts + row0, ts.cuts, nu * 4}}));
+    } else {
+        HIPCHK(hipMemcpyAsync(const_cast<float*>(as.thresholds), ab->thresholds + row0, nu * 4, hipMemcpyHostToDevice, m->stream));
+        SBRCHK(scan_launch(m, as.nonfinite_flag, [&] { return prelaunch() + sbr::launch_above_count(cat, A, qb, as, m->stream); },
+                           {{totals.data(), as.totals, nu * 4}}));
+    }
+    const std::vector<uint32_t>& leaving = top ? finals : totals; /* the entries of each row that reach the caller */
     uint64_t chunk_total = 0;
     for (size_t i = 0; i < nu; ++i) {
-        ab->out_counts[row0 + i] = totals[i];
-        chunk_total += totals[i];
+        ab->out_counts[row0 + i] = leaving[i];
+        chunk_total += leaving[i];
     }
     uint64_t at = ab->total; /* the chunk's first entry in the caller's arrays */
     ab->total += chunk_total;
     if (!ab->out_ids || ab->total > ab->capacity || chunk_total == 0) return SBR_OK;
+    if (top) /* what the fill writes: the rows' scores at or over their cuts */
+        SBRCHK(scan_launch(m, as.nonfinite_flag, [&] { return sbr::launch_above_count(cat, A, qb, as, m->stream); },
+                           {{totals.data(), as.totals, nu * 4}}));
     const size_t budget = above_fill_entries();
     size_t largest = 0; /* entries of the largest range: one device block serves them all */
     for (size_t r0 = 0; r0 < nu;) {
@@ -4156,22 +4194,36 @@ sbr_status above_chunk(sbr_model* m, const sbr::ModelView& cat, const float* A, 
         r0 = r1;
     }
     DeviceBlocks out(m->stream);
-    uint32_t* d_ids = nullptr;
-    float* d_scores = nullptr;
+    uint32_t *d_ids = nullptr, *t_ids = nullptr;   /* t_*: the trimmed entries of a range, at most as many as the fill wrote */
+    float *d_scores = nullptr, *t_scores = nullptr;
     SBRCHK(out.take(&d_ids, largest));
-    if (ab->out_scores) SBRCHK(out.take(&d_scores, largest));
+    if (ab->out_scores || top) SBRCHK(out.take(&d_scores, largest)); /* the trim compares the scores */
+    if (top) {
+        SBRCHK(out.take(&t_ids, largest));
+        if (ab->out_scores) SBRCHK(out.take(&t_scores, largest));
+    }
     HIPCHK(hipMemsetAsync(as.overrun_flag, 0, 4, m->stream));
     for (size_t r0 = 0; r0 < nu;) {
         size_t r1 = r0 + 1, n = totals[r0];
         while (r1 < nu && n + totals[r1] <= budget) n += totals[r1++];
         if (n) {
             uint32_t over = 0;
+            size_t keep = n; /* the entries that leave */
+            if (top) {
+                keep = 0;
+                for (size_t i = r0; i < r1; ++i) keep += finals[i];
+            }
+            uint32_t* ids = top ? t_ids : d_ids;
+            float* scores = top ? t_scores : d_scores;
             SBRCHK(scan_launch(m, as.nonfinite_flag, [&] {
-                return sbr::launch_above_fill(cat, A, qb, as, (uint32_t)r0, (uint32_t)(r1 - r0), d_ids, d_scores, (uint32_t)n, m->stream) +
-                       (row_ids ? sbr::launch_above_ids(row_ids, d_ids, n, m->stream) : 0);
-            }, {{&over, as.overrun_flag, 4}, {ab->out_ids + at, d_ids, n * 4}, {ab->out_scores ? ab->out_scores + at : nullptr, d_scores, n * 4}}));
+                int l = sbr::launch_above_fill(cat, A, qb, as, (uint32_t)r0, (uint32_t)(r1 - r0), d_ids, d_scores, (uint32_t)n, m->stream);
+                if (top)
+                    l += sbr::launch_top_trim(as, ts, (uint32_t)r0, (uint32_t)(r1 - r0), d_ids, d_scores, (uint32_t)n, t_ids, t_scores, (uint32_t)keep,
+                                              m->stream);
+                return l + (row_ids ? sbr::launch_above_ids(row_ids, ids, keep, m->stream) : 0);
+            }, {{&over, as.overrun_flag, 4}, {ab->out_ids + at, ids, keep * 4}, {ab->out_scores ? ab->out_scores + at : nullptr, scores, keep * 4}}));
             if (over) return SBR_ERR_HIP; /* the fill passed what the count did not: nothing was written out of bounds */
-            at += n;
+            at += keep;
         }
         r0 = r1;
     }
@@ -4249,7 +4301,7 @@ sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, 
             if (s.item_rows) rnorm = ar.take<float>(m->hp.num_items);
             if (v.subset) sb.carve(ar, v.subset->size(), (size_t)m->d);
             if (sm) smb.carve(ar, nu, k);
-            if (ab) abufs.carve(ar, scanned_items, nu);
+            if (ab) abufs.carve(ar, scanned_items, nu, ab->n != nullptr);
             if (pt) {
                 pt_mass = ar.take<unsigned long long>(nu);
                 pt_shift = ar.take<float>(nu);
@@ -4303,7 +4355,7 @@ sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, 
             as.groups = abufs.groups; as.per = abufs.per;
             as.counts = abufs.counts; as.offsets = abufs.offsets; as.totals = abufs.totals;
             as.nonfinite_flag = tb.flag; as.overrun_flag = abufs.over;
-            SBRCHK(above_chunk(m, m->mv, ur.H, nullptr, as, nullptr, ch.c0, ab, [&] {
+            SBRCHK(above_chunk(m, m->mv, ur.H, nullptr, as, abufs.ts, nullptr, ch.c0, ab, [&] {
                 return s.seen ? sbr::launch_session_seen_lists(*s.seen, seen_slot, (int)nu, tb.eptr, seen_caller, tb.excl, m->stream) : 0;
             }));
             continue;
@@ -4392,12 +4444,13 @@ sbr_status sbr_recommend_reps(sbr_model* m, const float* reps, uint64_t num_user
 /* ---------------------------------------------------------------------------------------------
  * the threshold form: every item at or over a per-row score, as CSR (sbr_catalogue.hip, above_gemm_kernel)
  * ------------------------------------------------------------------------------------------- */
-sbr_status sbr_recommend_above(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users, const float* thresholds,
-                               uint32_t flags, const uint32_t* any_of, const uint32_t* none_of, uint64_t* out_counts, uint64_t* out_total,
-                               uint64_t capacity, uint32_t* out_ids, float* out_scores) {
-    Above ab;
+namespace {
+
+/* sbr_recommend_above and sbr_recommend_top: ab is above_args' or top_args' descriptor, args_ok what that returned */
+sbr_status recommend_above_call(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users, uint32_t flags,
+                                const uint32_t* any_of, const uint32_t* none_of, bool args_ok, Above& ab, uint64_t* out_total) {
     TagFilterArg hold;
-    if (!m || !user_ptr || !above_args(thresholds, num_users, out_counts, out_total, capacity, out_ids, out_scores, &ab)) return SBR_ERR_INVALID_ARGUMENT;
+    if (!m || !user_ptr || !args_ok) return SBR_ERR_INVALID_ARGUMENT;
     if (flags & ~SBR_RECOMMEND_INCLUDE_HISTORY) return SBR_ERR_INVALID_ARGUMENT;
     std::lock_guard<std::mutex> lock(m->mu);
     SBRCHK(enter_reader(m));
@@ -4409,13 +4462,11 @@ sbr_status sbr_recommend_above(sbr_model* m, const uint64_t* user_ptr, const uin
     return SBR_OK;
 }
 
-sbr_status sbr_recommend_above_reps(sbr_model* m, const float* reps, uint64_t num_users, const float* thresholds, const uint64_t* excl_ptr,
-                                    const uint32_t* excl_items, const uint32_t* any_of, const uint32_t* none_of, uint64_t* out_counts,
-                                    uint64_t* out_total, uint64_t capacity, uint32_t* out_ids, float* out_scores) {
-    Above ab;
+/* sbr_recommend_above_reps and sbr_recommend_top_reps */
+sbr_status recommend_above_reps_call(sbr_model* m, const float* reps, uint64_t num_users, const uint64_t* excl_ptr, const uint32_t* excl_items,
+                                     const uint32_t* any_of, const uint32_t* none_of, bool args_ok, Above& ab, uint64_t* out_total) {
     TagFilterArg hold;
-    if (!m || (num_users && !reps) || !above_args(thresholds, num_users, out_counts, out_total, capacity, out_ids, out_scores, &ab))
-        return SBR_ERR_INVALID_ARGUMENT;
+    if (!m || (num_users && !reps) || !args_ok) return SBR_ERR_INVALID_ARGUMENT;
     if (!excl_args_ok(excl_ptr, excl_items, num_users)) return SBR_ERR_INVALID_ARGUMENT;
     std::lock_guard<std::mutex> lock(m->mu);
     SBRCHK(enter_reader(m));
@@ -4425,6 +4476,41 @@ sbr_status sbr_recommend_above_reps(sbr_model* m, const float* reps, uint64_t nu
     SBRCHK(recommend_scan(m, RepSource::of_rows(reps, excl_ptr, excl_items), num_users, 1, nullptr, nullptr, v));
     *out_total = ab.total;
     return SBR_OK;
+}
+
+}  // namespace
+
+sbr_status sbr_recommend_above(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users, const float* thresholds,
+                               uint32_t flags, const uint32_t* any_of, const uint32_t* none_of, uint64_t* out_counts, uint64_t* out_total,
+                               uint64_t capacity, uint32_t* out_ids, float* out_scores) {
+    Above ab;
+    const bool ok = above_args(thresholds, num_users, out_counts, out_total, capacity, out_ids, out_scores, &ab);
+    return recommend_above_call(m, user_ptr, item_ids, num_users, flags, any_of, none_of, ok, ab, out_total);
+}
+
+sbr_status sbr_recommend_above_reps(sbr_model* m, const float* reps, uint64_t num_users, const float* thresholds, const uint64_t* excl_ptr,
+                                    const uint32_t* excl_items, const uint32_t* any_of, const uint32_t* none_of, uint64_t* out_counts,
+                                    uint64_t* out_total, uint64_t capacity, uint32_t* out_ids, float* out_scores) {
+    Above ab;
+    const bool ok = above_args(thresholds, num_users, out_counts, out_total, capacity, out_ids, out_scores, &ab);
+    return recommend_above_reps_call(m, reps, num_users, excl_ptr, excl_items, any_of, none_of, ok, ab, out_total);
+}
+
+/* the budget form: the exact best n[row] of every row and its cut (sbr_catalogue.hip, select_gemm_kernel; TOP in sbr_hip.h) */
+sbr_status sbr_recommend_top(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users, const uint64_t* n, uint32_t flags,
+                             const uint32_t* any_of, const uint32_t* none_of, float* out_cuts, uint64_t* out_counts, uint64_t* out_total,
+                             uint64_t capacity, uint32_t* out_ids, float* out_scores) {
+    Above ab;
+    const bool ok = top_args(n, num_users, out_cuts, out_counts, out_total, capacity, out_ids, out_scores, &ab);
+    return recommend_above_call(m, user_ptr, item_ids, num_users, flags, any_of, none_of, ok, ab, out_total);
+}
+
+sbr_status sbr_recommend_top_reps(sbr_model* m, const float* reps, uint64_t num_users, const uint64_t* n, const uint64_t* excl_ptr,
+                                  const uint32_t* excl_items, const uint32_t* any_of, const uint32_t* none_of, float* out_cuts,
+                                  uint64_t* out_counts, uint64_t* out_total, uint64_t capacity, uint32_t* out_ids, float* out_scores) {
+    Above ab;
+    const bool ok = top_args(n, num_users, out_cuts, out_counts, out_total, capacity, out_ids, out_scores, &ab);
+    return recommend_above_reps_call(m, reps, num_users, excl_ptr, excl_items, any_of, none_of, ok, ab, out_total);
 }
 
 /* ---------------------------------------------------------------------------------------------
@@ -5424,6 +5510,18 @@ sbr_status sbr_sessions_recommend_above(sbr_sessions* st, const uint32_t* slots,
     return SBR_OK;
 }
 
+sbr_status sbr_sessions_recommend_top(sbr_sessions* st, const uint32_t* slots, uint64_t n, const uint64_t* top_n, const uint64_t* excl_ptr,
+                                      const uint32_t* excl_items, uint32_t flags, const uint32_t* any_of, const uint32_t* none_of, float* out_cuts,
+                                      uint64_t* out_counts, uint64_t* out_total, uint64_t capacity, uint32_t* out_ids, float* out_scores) {
+    Above ab;
+    TagFilterArg hold;
+    if (!st || !top_args(top_n, n, out_cuts, out_counts, out_total, capacity, out_ids, out_scores, &ab)) return SBR_ERR_INVALID_ARGUMENT;
+    SBRCHK(sessions_recommend_call(st, slots, n, 1, excl_ptr, excl_items, flags, nullptr, nullptr, sample_filter(any_of, none_of, &hold), nullptr,
+                                   nullptr, nullptr, &ab));
+    *out_total = ab.total;
+    return SBR_OK;
+}
+
 sbr_status sbr_sessions_recommend_diverse(sbr_sessions* st, const uint32_t* slots, uint64_t n, uint32_t k, uint32_t pool, float trade_off,
                                           uint32_t metric, const uint64_t* excl_ptr, const uint32_t* excl_items, uint32_t* out_items,
                                           float* out_scores) {
@@ -5486,7 +5584,10 @@ sbr_status audience_scan(sbr_model* m, const AudienceSource& src, uint64_t num_r
                          Above* ab = nullptr) {
     if (num_queries == 0) return SBR_OK;
     if (ab && num_rows == 0) { /* nobody to pass: empty rows */
-        for (uint64_t j = 0; j < num_queries; ++j) ab->out_counts[j] = 0;
+        for (uint64_t j = 0; j < num_queries; ++j) {
+            ab->out_counts[j] = 0;
+            if (ab->n) ab->out_cuts[j] = ab->n[j] ? -INFINITY : INFINITY;
+        }
         return SBR_OK;
     }
     if (num_rows == 0) { /* nobody to rank: rows of padding */
@@ -5531,7 +5632,7 @@ sbr_status audience_scan(sbr_model* m, const AudienceSource& src, uint64_t num_r
         AboveBufs abufs{};
         SBRCHK(carve_arena(m, [&](DeviceArena& ar) {
             tb.carve(ar, (uint32_t)S, n, src.seen ? 0 : nc, k, false);
-            if (ab) abufs.carve(ar, (uint32_t)S, n);
+            if (ab) abufs.carve(ar, (uint32_t)S, n, ab->n != nullptr);
             if (src.seen) {
                 qs_item = ar.take<uint32_t>(n);
                 qs_idx = ar.take<uint32_t>(n);
@@ -5604,7 +5705,7 @@ sbr_status audience_scan(sbr_model* m, const AudienceSource& src, uint64_t num_r
             as.nonfinite_flag = tb.flag; as.overrun_flag = abufs.over;
             sbr::ModelView mt = m->mv; /* the scan's catalogue: the candidate rows, as launch_audience's */
             mt.E = T; mt.b = bT; mt.num_items = (uint32_t)S;
-            SBRCHK(above_chunk(m, mt, m->mv.E, m->mv.b, as, d_ids, q0, ab, [] { return 0; }));
+            SBRCHK(above_chunk(m, mt, m->mv.E, m->mv.b, as, abufs.ts, d_ids, q0, ab, [] { return 0; }));
             continue;
         }
         sbr::TopkScan sc = tb.scan(n, k, lists, out_scores != nullptr);
@@ -5782,6 +5883,37 @@ sbr_status sbr_sessions_audience_above(sbr_sessions* st, const uint32_t* items, 
                                        float* out_scores) {
     Above ab;
     if (!above_args(thresholds, num_queries, out_counts, out_total, capacity, out_ids, out_scores, &ab)) return SBR_ERR_INVALID_ARGUMENT;
+    SBRCHK(sessions_audience_call(st, items, num_queries, 1, slots, num_slots, excl_ptr, excl_slots, flags, nullptr, nullptr, &ab));
+    *out_total = ab.total;
+    return SBR_OK;
+}
+
+/* the budget forms: the exact best n[query] candidate rows of every query and its cut */
+sbr_status sbr_audience_top_reps(sbr_model* m, const float* reps, uint64_t num_rows, const uint32_t* items, uint64_t num_queries, const uint64_t* n,
+                                 const uint64_t* excl_ptr, const uint32_t* excl_rows, float* out_cuts, uint64_t* out_counts, uint64_t* out_total,
+                                 uint64_t capacity, uint32_t* out_ids, float* out_scores) {
+    Above ab;
+    if (!top_args(n, num_queries, out_cuts, out_counts, out_total, capacity, out_ids, out_scores, &ab)) return SBR_ERR_INVALID_ARGUMENT;
+    SBRCHK(audience_reps_call(m, reps, num_rows, items, num_queries, 1, excl_ptr, excl_rows, nullptr, nullptr, &ab));
+    *out_total = ab.total;
+    return SBR_OK;
+}
+
+sbr_status sbr_audience_top(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users, const uint32_t* items,
+                            uint64_t num_queries, const uint64_t* n, uint32_t flags, float* out_cuts, uint64_t* out_counts, uint64_t* out_total,
+                            uint64_t capacity, uint32_t* out_ids, float* out_scores) {
+    Above ab;
+    if (!top_args(n, num_queries, out_cuts, out_counts, out_total, capacity, out_ids, out_scores, &ab)) return SBR_ERR_INVALID_ARGUMENT;
+    SBRCHK(audience_call(m, user_ptr, item_ids, num_users, items, num_queries, 1, flags, nullptr, nullptr, &ab));
+    *out_total = ab.total;
+    return SBR_OK;
+}
+
+sbr_status sbr_sessions_audience_top(sbr_sessions* st, const uint32_t* items, uint64_t num_queries, const uint64_t* n, const uint32_t* slots,
+                                     uint64_t num_slots, const uint64_t* excl_ptr, const uint32_t* excl_slots, uint32_t flags, float* out_cuts,
+                                     uint64_t* out_counts, uint64_t* out_total, uint64_t capacity, uint32_t* out_ids, float* out_scores) {
+    Above ab;
+    if (!top_args(n, num_queries, out_cuts, out_counts, out_total, capacity, out_ids, out_scores, &ab)) return SBR_ERR_INVALID_ARGUMENT;
     SBRCHK(sessions_audience_call(st, items, num_queries, 1, slots, num_slots, excl_ptr, excl_slots, flags, nullptr, nullptr, &ab));
     *out_total = ab.total;
     return SBR_OK;

@@ -368,6 +368,31 @@ uint32_t above_groups(uint32_t num_rows, uint32_t num_items, uint32_t* items_per
 int launch_above_count(const ModelView& cat, const float* reps, const float* qb, const AboveScan& sc, hipStream_t s);
 int launch_above_fill(const ModelView& cat, const float* reps, const float* qb, const AboveScan& sc, uint32_t r0, uint32_t nr, uint32_t* out_ids,
                       float* out_scores, uint32_t out_cap, hipStream_t s);
+/* the exact best n of a row (sbr_catalogue.hip; the contract: TOP in include/sbr_hip.h): a radix select on the monotone u32 of
+ * the scores, 4 bits a round, finds every row's cut — its n-th largest eligible score — without writing a score; the count and
+ * fill above then run at thresholds = cuts and the trim keeps exactly n of each row.  Eligible: what launch_above_count would pass
+ * at threshold -inf.  All arrays are the caller's device memory, nothing needs zeroing.
+ * launch_top_select: 8 rounds of select_gemm_kernel (one catalogue scan each, the ranges of sc.groups / sc.per; integer device
+ *   atomics into hist) with select_step_kernel between them, no host round trip: 17 launches.  Leaves cuts[u] (+inf for n = 0, -inf
+ *   where fewer than n are eligible, else the n-th score; a zero is +0.0), gt[u] = #{score > cut}, final_counts[u] =
+ *   min(n, eligible) and keep_eq[u] = n - gt.  sc.counts / offsets / totals are not touched.
+ * launch_top_trim: after launch_above_fill(sc with thresholds = cuts, r0, nr) wrote in_ids / in_scores (both wanted): out_off
+ *   [nr + 1] = the exclusive scan of final_counts[r0 ..], and row u's entries over its cut with the first keep_eq[u] that equal it
+ *   go, ascending column, to out_ids / out_scores (NULL: not wanted) at out_off[u - r0].  Bounds-checked against in_cap / out_cap
+ *   and the row's range; a violation is dropped and sets *sc.overrun_flag.  Two launches. */
+struct TopSelect {
+    const uint64_t* n;       /* [sc.n] */
+    uint64_t* wanted;        /* [sc.n] */
+    uint32_t *prefix, *mask; /* [sc.n] */
+    uint32_t* hist;          /* [sc.n x 16] */
+    float* cuts;             /* [sc.n]: sc.thresholds of the count and fill that follow */
+    uint32_t *gt, *final_counts, *keep_eq; /* [sc.n] */
+    uint64_t* out_off;       /* [sc.n + 1] */
+    uint32_t* out_tot;       /* [sc.n]: scratch of the scan */
+};
+int launch_top_select(const ModelView& cat, const float* reps, const float* qb, const AboveScan& sc, const TopSelect& ts, hipStream_t s);
+int launch_top_trim(const AboveScan& sc, const TopSelect& ts, uint32_t r0, uint32_t nr, const uint32_t* in_ids, const float* in_scores,
+                    uint32_t in_cap, uint32_t* out_ids, float* out_scores, uint32_t out_cap, hipStream_t s);
 /* ids[e] = row_ids[ids[e]] for the n entries a fill wrote (audience: positions in the candidate table -> the ids they stand for) */
 int launch_above_ids(const uint32_t* row_ids, uint32_t* ids, uint64_t n, hipStream_t s);
 /* greedy maximal-marginal-relevance selection (sbr_catalogue.hip, diverse_select_kernel; the contract: sbr_recommend_diverse in

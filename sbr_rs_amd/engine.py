@@ -193,11 +193,13 @@ def above_sort(ptr, ids, scores, order: str = "score"):
 
 
 class Above:
-    """What the *_above calls return, a CSR set of (row, id, score) pairs: ``ptr`` u64 [R + 1], ``ids`` u32 [N], ``scores`` f32 [N];
-    row i's pairs are entries ptr[i] .. ptr[i + 1], in the call's ``order``.  ``counts`` u64 [R] = diff(ptr)."""
+    """What the *_above and *_top calls return, a CSR set of (row, id, score) pairs: ``ptr`` u64 [R + 1], ``ids`` u32 [N], ``scores``
+    f32 [N]; row i's pairs are entries ptr[i] .. ptr[i + 1], in the call's ``order``.  ``counts`` u64 [R] = diff(ptr).  ``cuts``:
+    f32 [R] from a *_top call (the score of a row's last entry; -inf where the row holds everything eligible, +inf for n = 0),
+    None from an *_above call."""
 
-    def __init__(self, ptr, ids, scores, order: str = "score"):
-        self.ptr, self.ids, self.scores, self.order = ptr, ids, scores, order
+    def __init__(self, ptr, ids, scores, order: str = "score", cuts=None):
+        self.ptr, self.ids, self.scores, self.order, self.cuts = ptr, ids, scores, order, cuts
 
     @property
     def counts(self) -> np.ndarray:
@@ -227,31 +229,58 @@ def _above_thresholds(threshold, n: int) -> np.ndarray:
     return t if n else np.zeros(1, dtype=np.float32)
 
 
-def _above(call, n: int, threshold, max_results, order: str, count_only: bool):
+def _top_budgets(budget, n: int) -> np.ndarray:
+    """``budget`` (the n of a *_top call) -> u64 [rows]: a scalar applies to every row, an array must have one value per row; whole
+    numbers from 0 to 2^64 - 1, so a NaN, a fraction, a negative value or a float of 2^64 and more (which no u64 holds) is refused"""
+    b = np.asarray(budget)
+    if b.dtype.kind not in "iuf" or (b.dtype.kind == "f" and not (np.isfinite(b).all() and (b == np.floor(b)).all())):
+        raise ValueError("n: whole numbers >= 0")
+    if (b < 0).any():
+        raise ValueError("n: >= 0")
+    if b.dtype.kind == "f" and (b >= 2.0 ** 64).any():
+        raise ValueError("n: below 2^64 (any n past the eligible columns returns them all)")
+    b = np.full(n, b, dtype=np.uint64) if b.ndim == 0 else np.ascontiguousarray(b.ravel()).astype(np.uint64)
+    if b.size != n:
+        raise ValueError(f"n: one per row ({n}), or a scalar; got {b.size}")
+    return b if n else np.zeros(1, dtype=np.uint64)
+
+
+def _above(call, n: int, threshold, max_results, order: str, count_only: bool, budget=None):
     """The shared tail of the *_above / count_above* methods.  ``call(thresholds, out_counts, out_total, capacity, out_ids, out_scores)``
     invokes the entry point with the method's leading arguments.  One call with a buffer of ``max_results`` entries (np.empty
-    touches nothing); a total above it is a ValueError that states the total, never a truncated result."""
+    touches nothing); a total above it is a ValueError that states the total, never a truncated result.
+    With ``budget`` (the *_top / nth_score* methods; threshold unused) the entry point is the *_top sibling, whose list differs in
+    two places: n u64 [rows] where the thresholds stand and out_cuts ahead of out_counts, so ``call(n, out_cuts, out_counts, ...)``.
+    count_only then returns (cuts, counts), and the Above carries the cuts."""
     if order not in ABOVE_ORDERS:
         raise ValueError(f"order {order!r}: 'score' or 'id'")
-    th = _above_thresholds(threshold, n)
+    cuts = None
+    if budget is None:
+        lead = (_ptr(_above_thresholds(threshold, n)),)
+    else:
+        cuts = np.zeros(max(n, 1), dtype=np.float32)
+        lead = (_ptr(_top_budgets(budget, n)), _ptr(cuts))
     counts = np.zeros(max(n, 1), dtype=np.uint64)
     total = C.c_uint64(0)
     if count_only:
-        _check(call(_ptr(th), _ptr(counts), C.byref(total), 0, None, None))
-        return counts[:n]
+        _check(call(*lead, _ptr(counts), C.byref(total), 0, None, None))
+        return counts[:n] if budget is None else (cuts[:n], counts[:n])
     cap = ABOVE_MAX_RESULTS if max_results is None else int(max_results)
     if cap < 0:
         raise ValueError("max_results: >= 0")
     ids = np.empty(max(cap, 1), dtype=np.uint32)
     scores = np.empty(max(cap, 1), dtype=np.float32)
-    _check(call(_ptr(th), _ptr(counts), C.byref(total), cap, _ptr(ids), _ptr(scores)))
+    _check(call(*lead, _ptr(counts), C.byref(total), cap, _ptr(ids), _ptr(scores)))
     if total.value > cap:
+        if budget is not None:
+            raise ValueError(f"{total.value} pairs make up the rows' best n, above max_results = {cap}: raise max_results or lower n "
+                             f"(nth_score* returns the per-row counts and cuts)")
         raise ValueError(f"{total.value} pairs pass the threshold, above max_results = {cap}: raise max_results or the threshold "
                          f"(count_above* returns the per-row counts)")
     ptr = np.zeros(n + 1, dtype=np.uint64)
     ptr[1:] = np.cumsum(counts[:n], dtype=np.uint64)
     ids, scores = above_sort(ptr, ids[: total.value].copy(), scores[: total.value].copy(), order)
-    return Above(ptr, ids, scores, order)
+    return Above(ptr, ids, scores, order, None if cuts is None else cuts[:n])
 
 
 STREAM_ROLES = ("main", "side", "sorter", "copier", "xs")  # the roles SBR_TEST_STREAM_DELAY names, in the counter's order
@@ -888,16 +917,16 @@ class Model:
                                               None if masks is None else _ptr(masks[1]), _ptr(shift), _ptr(mass), C.byref(fb)))
         return Partition(temperature, shift, mass, fb.value)
 
-    def _recommend_above(self, user_ptr, item_ids, threshold, include_history, any_of, none_of, max_results, order, count_only):
+    def _recommend_above(self, user_ptr, item_ids, threshold, include_history, any_of, none_of, max_results, order, count_only, n=None):
         up = np.ascontiguousarray(user_ptr, dtype=np.uint64)
         it = np.ascontiguousarray(item_ids, dtype=np.uint32)
         nu = max(len(up) - 1, 0)
         masks = _tag_masks(any_of, none_of, nu)
         flags = RECOMMEND_INCLUDE_HISTORY if include_history else 0
-        return _above(lambda *out: self._L.sbr_recommend_above(self._h, _ptr(up), _ptr(it), nu, out[0], flags,
-                                                               None if masks is None else _ptr(masks[0]),
-                                                               None if masks is None else _ptr(masks[1]), *out[1:]),
-                      nu, threshold, max_results, order, count_only)
+        return _above(lambda *out: (self._L.sbr_recommend_above if n is None else self._L.sbr_recommend_top)(
+                          self._h, _ptr(up), _ptr(it), nu, out[0], flags, None if masks is None else _ptr(masks[0]),
+                          None if masks is None else _ptr(masks[1]), *out[1:]),
+                      nu, threshold, max_results, order, count_only, n)
 
     def recommend_above(self, user_ptr, item_ids, threshold, include_history: bool = False, any_of=None, none_of=None,
                         max_results=None, order: str = "score") -> Above:
@@ -917,16 +946,15 @@ class Model:
         ``rank_targets``' rank of an item that scores exactly the threshold."""
         return self._recommend_above(user_ptr, item_ids, threshold, include_history, any_of, none_of, None, "id", True)
 
-    def _recommend_above_reps(self, reps, threshold, exclude, any_of, none_of, max_results, order, count_only):
+    def _recommend_above_reps(self, reps, threshold, exclude, any_of, none_of, max_results, order, count_only, n=None):
         reps = np.ascontiguousarray(reps, dtype=np.float32).reshape(-1, self.dim)
         nu = reps.shape[0]
         masks = _tag_masks(any_of, none_of, nu)
         ep, ei = _exclusion_csr(exclude, nu)
-        return _above(lambda *out: self._L.sbr_recommend_above_reps(self._h, _ptr(reps), nu, out[0], None if ep is None else _ptr(ep),
-                                                                    None if ei is None else _ptr(ei),
-                                                                    None if masks is None else _ptr(masks[0]),
-                                                                    None if masks is None else _ptr(masks[1]), *out[1:]),
-                      nu, threshold, max_results, order, count_only)
+        return _above(lambda *out: (self._L.sbr_recommend_above_reps if n is None else self._L.sbr_recommend_top_reps)(
+                          self._h, _ptr(reps), nu, out[0], None if ep is None else _ptr(ep), None if ei is None else _ptr(ei),
+                          None if masks is None else _ptr(masks[0]), None if masks is None else _ptr(masks[1]), *out[1:]),
+                      nu, threshold, max_results, order, count_only, n)
 
     def recommend_above_reps(self, reps, threshold, exclude=None, any_of=None, none_of=None, max_results=None,
                              order: str = "score") -> Above:
@@ -937,14 +965,14 @@ class Model:
         """``recommend_above_reps(...).counts`` without writing any pair: one scan."""
         return self._recommend_above_reps(reps, threshold, exclude, any_of, none_of, None, "id", True)
 
-    def _audience_above_reps(self, reps, items, threshold, exclude, max_results, order, count_only):
+    def _audience_above_reps(self, reps, items, threshold, exclude, max_results, order, count_only, n=None):
         reps = np.ascontiguousarray(reps, dtype=np.float32).reshape(-1, self.dim)
         q = np.ascontiguousarray(items, dtype=np.uint32).ravel()
         ep, ei = _exclusion_csr(exclude, q.size)
-        return _above(lambda *out: self._L.sbr_audience_above_reps(self._h, _ptr(reps), reps.shape[0], _ptr(q), q.size, out[0],
-                                                                   None if ep is None else _ptr(ep), None if ei is None else _ptr(ei),
-                                                                   *out[1:]),
-                      q.size, threshold, max_results, order, count_only)
+        return _above(lambda *out: (self._L.sbr_audience_above_reps if n is None else self._L.sbr_audience_top_reps)(
+                          self._h, _ptr(reps), reps.shape[0], _ptr(q), q.size, out[0], None if ep is None else _ptr(ep),
+                          None if ei is None else _ptr(ei), *out[1:]),
+                      q.size, threshold, max_results, order, count_only, n)
 
     def audience_above_reps(self, reps, items, threshold, exclude=None, max_results=None, order: str = "score") -> Above:
         """The reverse scan's threshold form (sbr_audience_above_reps): for each query item ``items[j]`` every row of ``reps``
@@ -957,14 +985,15 @@ class Model:
         """``audience_above_reps(...).counts`` without writing any pair: one scan."""
         return self._audience_above_reps(reps, items, threshold, exclude, None, "id", True)
 
-    def _audience_above(self, user_ptr, item_ids, items, threshold, include_history, max_results, order, count_only):
+    def _audience_above(self, user_ptr, item_ids, items, threshold, include_history, max_results, order, count_only, n=None):
         up = np.ascontiguousarray(user_ptr, dtype=np.uint64)
         it = np.ascontiguousarray(item_ids, dtype=np.uint32)
         q = np.ascontiguousarray(items, dtype=np.uint32).ravel()
         nu = max(len(up) - 1, 0)
         flags = RECOMMEND_INCLUDE_HISTORY if include_history else 0
-        return _above(lambda *out: self._L.sbr_audience_above(self._h, _ptr(up), _ptr(it), nu, _ptr(q), q.size, out[0], flags, *out[1:]),
-                      q.size, threshold, max_results, order, count_only)
+        return _above(lambda *out: (self._L.sbr_audience_above if n is None else self._L.sbr_audience_top)(
+                          self._h, _ptr(up), _ptr(it), nu, _ptr(q), q.size, out[0], flags, *out[1:]),
+                      q.size, threshold, max_results, order, count_only, n)
 
     def audience_above(self, user_ptr, item_ids, items, threshold, include_history: bool = False, max_results=None,
                        order: str = "score") -> Above:
@@ -975,6 +1004,51 @@ class Model:
     def count_audience_above(self, user_ptr, item_ids, items, threshold, include_history: bool = False) -> np.ndarray:
         """``audience_above(...).counts`` without writing any pair."""
         return self._audience_above(user_ptr, item_ids, items, threshold, include_history, None, "id", True)
+
+    def recommend_top(self, user_ptr, item_ids, n, include_history: bool = False, any_of=None, none_of=None, max_results=None,
+                      order: str = "score") -> Above:
+        """Each user's exact best ``n`` items (sbr_recommend_top) — a budget, with no cap of 1 024: an ``Above`` over the histories'
+        rows with ``cuts`` set.  n: a scalar or one whole number >= 0 per row; 0 gives an empty row, an n past the eligible items
+        all of them.  Eligibility is ``recommend``'s, the order every call's (score descending, ties to the lower id, -0.0 == +0.0):
+        for n <= 1 024 a row is ``recommend(k=n)``'s without padding, for any n the first n of
+        ``recommend_above(threshold=cuts[row])``'s; a tie group that straddles the cut gives up exactly its lowest ids.
+        ``cuts[row]``: the score of the row's last item (a zero as +0.0), -inf where the row holds everything eligible, +inf for
+        n = 0.  The cuts cost 8 catalogue scans on the device (a radix select on the score bits, no host round trip), the pairs
+        ``recommend_above``'s count and fill at the cuts and a trim.  max_results and order as in ``recommend_above``; max_results
+        is held against the pairs returned, sum(min(n, eligible))."""
+        return self._recommend_above(user_ptr, item_ids, None, include_history, any_of, none_of, max_results, order, False, n)
+
+    def nth_score(self, user_ptr, item_ids, n, include_history: bool = False, any_of=None, none_of=None):
+        """``(r.cuts, r.counts)`` of ``r = recommend_top(...)`` (f32 [U], u64 [U]) from the select alone: no pair is written."""
+        return self._recommend_above(user_ptr, item_ids, None, include_history, any_of, none_of, None, "id", True, n)
+
+    def recommend_top_reps(self, reps, n, exclude=None, any_of=None, none_of=None, max_results=None, order: str = "score") -> Above:
+        """As recommend_top, from representations [U, embedding_dim]; exclude: None or one sequence of item ids per user."""
+        return self._recommend_above_reps(reps, None, exclude, any_of, none_of, max_results, order, False, n)
+
+    def nth_score_reps(self, reps, n, exclude=None, any_of=None, none_of=None):
+        """``(cuts, counts)`` of ``recommend_top_reps(...)`` from the select alone."""
+        return self._recommend_above_reps(reps, None, exclude, any_of, none_of, None, "id", True, n)
+
+    def audience_top_reps(self, reps, items, n, exclude=None, max_results=None, order: str = "score") -> Above:
+        """The reverse scan's budget form (sbr_audience_top_reps): for each query item ``items[j]`` the exact best ``n`` (a scalar or
+        one per query; any size) rows of ``reps`` [S, embedding_dim] — "we can reach 50 000 people: which 50 000?".  An ``Above``
+        over the queries with ``cuts``, row indices with the bits of ``predict(reps[s], [item])``; exclude as in ``audience_reps``.
+        For n <= 1 024 a row is ``audience_reps(k=n)``'s without padding."""
+        return self._audience_above_reps(reps, items, None, exclude, max_results, order, False, n)
+
+    def nth_audience_score_reps(self, reps, items, n, exclude=None):
+        """``(cuts, counts)`` of ``audience_top_reps(...)`` from the select alone."""
+        return self._audience_above_reps(reps, items, None, exclude, None, "id", True, n)
+
+    def audience_top(self, user_ptr, item_ids, items, n, include_history: bool = False, max_results=None, order: str = "score") -> Above:
+        """``audience_top_reps`` on ``user_representations`` of the histories (sbr_audience_top): user indices.  Unless
+        include_history a user whose history holds the query item is left out of that item's row."""
+        return self._audience_above(user_ptr, item_ids, items, None, include_history, max_results, order, False, n)
+
+    def nth_audience_score(self, user_ptr, item_ids, items, n, include_history: bool = False):
+        """``(cuts, counts)`` of ``audience_top(...)`` from the select alone."""
+        return self._audience_above(user_ptr, item_ids, items, None, include_history, None, "id", True, n)
 
     def diverse_max_pool(self) -> int:
         """The largest ``pool`` of recommend_diverse on this model (sbr_recommend_diverse_max_pool): a user's pool lives in one
@@ -1425,18 +1499,17 @@ class Sessions:
                                              _ptr(out_slots), _ptr(scores)))
         return out_slots, scores
 
-    def _recommend_above(self, slots, threshold, exclude, any_of, none_of, include_seen, max_results, order, count_only):
+    def _recommend_above(self, slots, threshold, exclude, any_of, none_of, include_seen, max_results, order, count_only, n=None):
         if include_seen and not self._seen:
             raise ValueError("include_seen: this store has no seen-item memory (sessions(capacity, remember=W))")
         flags = RECOMMEND_INCLUDE_HISTORY if include_seen else 0
         sl = self._slots(slots)
         masks = _tag_masks(any_of, none_of, sl.size)
         ep, ei = _exclusion_csr(exclude, sl.size)
-        return _above(lambda *out: self._L.sbr_sessions_recommend_above(self._h, _ptr(sl), sl.size, out[0], None if ep is None else _ptr(ep),
-                                                                        None if ei is None else _ptr(ei), flags,
-                                                                        None if masks is None else _ptr(masks[0]),
-                                                                        None if masks is None else _ptr(masks[1]), *out[1:]),
-                      sl.size, threshold, max_results, order, count_only)
+        return _above(lambda *out: (self._L.sbr_sessions_recommend_above if n is None else self._L.sbr_sessions_recommend_top)(
+                          self._h, _ptr(sl), sl.size, out[0], None if ep is None else _ptr(ep), None if ei is None else _ptr(ei), flags,
+                          None if masks is None else _ptr(masks[0]), None if masks is None else _ptr(masks[1]), *out[1:]),
+                      sl.size, threshold, max_results, order, count_only, n)
 
     def recommend_above(self, slots, threshold, exclude=None, any_of=None, none_of=None, include_seen: bool = False, max_results=None,
                         order: str = "score") -> Above:
@@ -1448,7 +1521,7 @@ class Sessions:
         """``recommend_above(...).counts`` without writing any pair: one scan."""
         return self._recommend_above(slots, threshold, exclude, any_of, none_of, include_seen, None, "id", True)
 
-    def _audience_above(self, items, threshold, slots, exclude, include_seen, max_results, order, count_only):
+    def _audience_above(self, items, threshold, slots, exclude, include_seen, max_results, order, count_only, n=None):
         if include_seen and not self._seen:
             raise ValueError("include_seen: this store has no seen-item memory (sessions(capacity, remember=W))")
         flags = RECOMMEND_INCLUDE_HISTORY if include_seen else 0
@@ -1462,10 +1535,10 @@ class Sessions:
             nsl = 0
         else:
             nsl = 0 if sl is None else sl.size
-        return _above(lambda *out: self._L.sbr_sessions_audience_above(self._h, _ptr(q), q.size, out[0], None if sl is None else _ptr(sl),
-                                                                       nsl, None if ep is None else _ptr(ep),
-                                                                       None if ei is None else _ptr(ei), flags, *out[1:]),
-                      q.size, threshold, max_results, order, count_only)
+        return _above(lambda *out: (self._L.sbr_sessions_audience_above if n is None else self._L.sbr_sessions_audience_top)(
+                          self._h, _ptr(q), q.size, out[0], None if sl is None else _ptr(sl), nsl, None if ep is None else _ptr(ep),
+                          None if ei is None else _ptr(ei), flags, *out[1:]),
+                      q.size, threshold, max_results, order, count_only, n)
 
     def audience_above(self, items, threshold, slots=None, exclude=None, include_seen: bool = False, max_results=None,
                        order: str = "score") -> Above:
@@ -1477,6 +1550,26 @@ class Sessions:
     def count_audience_above(self, items, threshold, slots=None, exclude=None, include_seen: bool = False) -> np.ndarray:
         """``audience_above(...).counts`` without writing any pair: one scan."""
         return self._audience_above(items, threshold, slots, exclude, include_seen, None, "id", True)
+
+    def recommend_top(self, slots, n, exclude=None, any_of=None, none_of=None, include_seen: bool = False, max_results=None,
+                      order: str = "score") -> Above:
+        """``Model.recommend_top_reps(self.representations(slots), n, ...)`` with the scan reading the store's rows in place and the
+        seen-item memory excluded exactly as in ``recommend`` (sbr_sessions_recommend_top)."""
+        return self._recommend_above(slots, None, exclude, any_of, none_of, include_seen, max_results, order, False, n)
+
+    def nth_score(self, slots, n, exclude=None, any_of=None, none_of=None, include_seen: bool = False):
+        """``(cuts, counts)`` of ``recommend_top(...)`` from the select alone: no pair is written."""
+        return self._recommend_above(slots, None, exclude, any_of, none_of, include_seen, None, "id", True, n)
+
+    def audience_top(self, items, n, slots=None, exclude=None, include_seen: bool = False, max_results=None, order: str = "score") -> Above:
+        """We can reach n people: which n (sbr_sessions_audience_top)?  For each query item ``items[j]`` the exact best ``n`` (a
+        scalar or one per query; no cap of 1 024) candidate slots — an ``Above`` over the queries with ``cuts``, slot ids with the
+        bits of ``score_candidates``.  Candidates, ``exclude`` and the seen-item memory as in ``audience``."""
+        return self._audience_above(items, None, slots, exclude, include_seen, max_results, order, False, n)
+
+    def nth_audience_score(self, items, n, slots=None, exclude=None, include_seen: bool = False):
+        """``(cuts, counts)`` of ``audience_top(...)`` from the select alone."""
+        return self._audience_above(items, None, slots, exclude, include_seen, None, "id", True, n)
 
     def score_candidates(self, slots, candidates):
         """``Model.score_candidates_reps`` on the slots' representations, read in place: one f32 array per slot, in candidate

@@ -357,6 +357,48 @@ class _ImplicitSequenceModel:
         """``audience_above_reps(...).counts`` without writing any pair."""
         return self.params.count_audience_above_reps(reps, items, threshold, exclude=exclude)
 
+    def recommend_top(self, interactions_or_histories, n, exclude_history: bool = True, any_of=None, none_of=None, max_results=None,
+                      order: str = "score"):
+        """``recommend`` with a budget in place of k: each user's exact best ``n`` eligible items (a scalar or one per user, any
+        size — no cap of 1 024), on the device — an ``engine.Above`` whose ``cuts`` holds each row's n-th score (-inf where the row
+        is everything eligible, +inf for n = 0).  Same order as every call: for n <= 1 024 a row is ``recommend(k=n)``'s without
+        padding."""
+        up, it = self._csr(interactions_or_histories)
+        return self.params.recommend_top(up, it, n, include_history=not exclude_history, any_of=any_of, none_of=none_of,
+                                         max_results=max_results, order=order)
+
+    def nth_score(self, interactions_or_histories, n, exclude_history: bool = True, any_of=None, none_of=None):
+        """``(cuts, counts)`` of ``recommend_top(...)`` without writing any pair: the select alone."""
+        up, it = self._csr(interactions_or_histories)
+        return self.params.nth_score(up, it, n, include_history=not exclude_history, any_of=any_of, none_of=none_of)
+
+    def recommend_top_reps(self, reps, n, exclude=None, any_of=None, none_of=None, max_results=None, order: str = "score"):
+        """``recommend_top`` from representations [U, embedding_dim]; ``exclude``: None or one sequence of item ids per user."""
+        return self.params.recommend_top_reps(reps, n, exclude=exclude, any_of=any_of, none_of=none_of, max_results=max_results, order=order)
+
+    def nth_score_reps(self, reps, n, exclude=None, any_of=None, none_of=None):
+        """``(cuts, counts)`` of ``recommend_top_reps(...)`` without writing any pair."""
+        return self.params.nth_score_reps(reps, n, exclude=exclude, any_of=any_of, none_of=none_of)
+
+    def audience_top(self, interactions_or_histories, items, n, exclude_history: bool = True, max_results=None, order: str = "score"):
+        """``audience`` with a budget in place of k: for each query item the exact best ``n`` users (a scalar or one per query, any
+        size) — an ``engine.Above`` over the queries with ``cuts``, user indices.  For live sessions: ``sessions(...).audience_top``."""
+        up, it = self._csr(interactions_or_histories)
+        return self.params.audience_top(up, it, items, n, include_history=not exclude_history, max_results=max_results, order=order)
+
+    def nth_audience_score(self, interactions_or_histories, items, n, exclude_history: bool = True):
+        """``(cuts, counts)`` of ``audience_top(...)`` without writing any pair."""
+        up, it = self._csr(interactions_or_histories)
+        return self.params.nth_audience_score(up, it, items, n, include_history=not exclude_history)
+
+    def audience_top_reps(self, reps, items, n, exclude=None, max_results=None, order: str = "score"):
+        """``audience_top`` over representation rows [S, embedding_dim]; ``exclude``: None or one sequence of row indices per query."""
+        return self.params.audience_top_reps(reps, items, n, exclude=exclude, max_results=max_results, order=order)
+
+    def nth_audience_score_reps(self, reps, items, n, exclude=None):
+        """``(cuts, counts)`` of ``audience_top_reps(...)`` without writing any pair."""
+        return self.params.nth_audience_score_reps(reps, items, n, exclude=exclude)
+
     def user_representations(self, histories) -> np.ndarray:
         """``user_representation`` of many histories in one device pass: [U, embedding_dim] f32, row u for history u."""
         return self.params.user_representations(*self._csr(histories))
