@@ -499,6 +499,22 @@ struct Recommendations {
 struct TagFilter {
     std::vector<std::uint32_t> any_of, none_of;
 };
+/// The rule of the recommend_capped calls (struct sbr_cap_args; CAPPED in sbr_hip.h): at most `cap` items of one item group per row
+/// (ImplicitSequenceModel::set_item_groups), applied on the device to each row's best `pool` (0: min(1 024, max(64, 4 k))).  exact:
+/// the rows the pool did not settle are finished through recommend_top at a growing n with the rule on the host.
+struct CapArgs {
+    std::uint32_t cap = 1;
+    std::uint32_t pool = 0;
+    bool exact = true;
+};
+/// Rows of the recommend_capped calls, row-major [num_users][k], padded with (0xFFFFFFFF, -inf), and one flag per row: 1 where the
+/// row is the exact answer over the whole catalogue (always, with CapArgs::exact), 0 where it is a short prefix of it.
+struct CappedRecommendations {
+    std::size_t num_users = 0, k = 0;
+    std::vector<std::uint32_t> items;
+    std::vector<float> scores;
+    std::vector<std::uint8_t> complete;
+};
 /// The noise of the recommend_sampled calls (struct sbr_sample_args): k draws without replacement from softmax(score / temperature);
 /// the noise of (row, item) is a function of (seed, streams[row], item) alone.  streams: empty (the row's index in the call; for a
 /// session store the slot id) or one per row.
@@ -632,6 +648,89 @@ inline std::vector<std::uint32_t> tag_masks(const std::vector<std::uint32_t>& ma
     if (mask.size() > 1 && mask.size() != n) throw EngineError(SBR_ERR_INVALID_ARGUMENT, where);
     if (mask.size() == n && n > 0) return mask;
     return std::vector<std::uint32_t>(n ? n : 1, mask.empty() ? 0u : mask[0]);
+}
+
+/// The pool a *_capped call scans at, and its refusals ahead of the library: cap < 1, k < 1, pool < k, pool > SBR_RECOMMEND_MAX_K.
+inline sbr_cap_args cap_args(const CapArgs& a, std::size_t k, const char* me) {
+    const std::uint64_t pool = a.pool ? a.pool : std::min<std::uint64_t>(1024, std::max<std::uint64_t>(64, 4 * (std::uint64_t)k));
+    if (a.cap < 1 || k < 1 || pool < k || pool > SBR_RECOMMEND_MAX_K)
+        throw EngineError(SBR_ERR_INVALID_ARGUMENT, std::string(me) + ": cap >= 1 and 1 <= k <= pool <= SBR_RECOMMEND_MAX_K");
+    return sbr_cap_args{a.cap, (std::uint32_t)pool};
+}
+
+/// The rule R(L, cap, k) of CAPPED on one row: ids[0 .. n) in the total order -> the positions of the first k kept entries.
+inline std::vector<std::size_t> capped_keep(const std::uint32_t* ids, std::size_t n, const std::vector<std::uint32_t>& groups, std::uint32_t cap,
+                                            std::size_t k) {
+    std::vector<std::size_t> kept;
+    std::unordered_map<std::uint32_t, std::uint32_t> seen;
+    for (std::size_t j = 0; j < n && kept.size() < k; ++j) {
+        const std::uint32_t g = groups[ids[j]];
+        if (g != SBR_NO_GROUP && seen[g]++ >= cap) continue;
+        kept.push_back(j);
+    }
+    return kept;
+}
+
+/// Finishes the rows of `r` whose flag is 0, in place.  top(rows, n) is the matching recommend_top* over those rows of the call only
+/// (same exclusions, masks and include_seen, score order).  n starts at 4 pool and grows fourfold per round up to the catalogue;
+/// a row is done when k are kept or its returned row is shorter than n; the rows of a round go in batches whose rows x n stay
+/// within ABOVE_MAX_RESULTS.  False when a top call met a non-finite score.
+template <class Top>
+inline bool capped_complete(Top top, CappedRecommendations* r, const std::vector<std::uint32_t>& groups, std::uint32_t cap, std::uint32_t pool) {
+    std::vector<std::size_t> todo;
+    for (std::size_t u = 0; u < r->num_users; ++u)
+        if (!r->complete[u]) todo.push_back(u);
+    const std::uint64_t num_items = std::max<std::uint64_t>(groups.size(), 1);
+    for (std::uint64_t n = 4ull * pool; !todo.empty(); n *= 4) {
+        n = std::min(n, num_items);
+        const std::size_t per = (std::size_t)std::max<std::uint64_t>(1, ABOVE_MAX_RESULTS / n);
+        std::vector<std::size_t> left;
+        for (std::size_t b0 = 0; b0 < todo.size(); b0 += per) {
+            const std::vector<std::size_t> rows(todo.begin() + (std::ptrdiff_t)b0, todo.begin() + (std::ptrdiff_t)std::min(todo.size(), b0 + per));
+            auto res = top(rows, n);
+            if (res.is_err()) return false;
+            const Above& a = res.unwrap();
+            for (std::size_t i = 0; i < rows.size(); ++i) {
+                const std::size_t at = (std::size_t)a.ptr[i], len = (std::size_t)a.count(i), u = rows[i];
+                const std::vector<std::size_t> kept = capped_keep(a.ids.data() + at, len, groups, cap, r->k);
+                if (kept.size() < r->k && len >= n && n < num_items) {
+                    left.push_back(u);
+                    continue;
+                }
+                for (std::size_t j = 0; j < r->k; ++j) {
+                    r->items[u * r->k + j] = j < kept.size() ? a.ids[at + kept[j]] : 0xFFFFFFFFu;
+                    r->scores[u * r->k + j] = j < kept.size() ? a.scores[at + kept[j]] : -std::numeric_limits<float>::infinity();
+                }
+                r->complete[u] = 1;
+            }
+        }
+        todo.swap(left);
+    }
+    return true;
+}
+
+/// The exclusion CSR of the named rows of a call's (both empty: none).
+inline void csr_rows(const std::vector<std::uint64_t>& ptr, const std::vector<std::uint32_t>& items, const std::vector<std::size_t>& rows,
+                     std::vector<std::uint64_t>* out_ptr, std::vector<std::uint32_t>* out_items) {
+    out_ptr->clear();
+    out_items->clear();
+    if (ptr.empty()) return;
+    out_ptr->push_back(0);
+    for (std::size_t r : rows) {
+        out_items->insert(out_items->end(), items.begin() + (std::ptrdiff_t)ptr[r], items.begin() + (std::ptrdiff_t)ptr[r + 1]);
+        out_ptr->push_back(out_items->size());
+    }
+}
+
+/// The tag filter of the named rows of a call's: a vector with one mask per row is cut down, anything else applies as it is.
+inline TagFilter filter_rows(const TagFilter& f, std::size_t n, const std::vector<std::size_t>& rows) {
+    TagFilter out = f;
+    for (auto pair : {std::make_pair(&f.any_of, &out.any_of), std::make_pair(&f.none_of, &out.none_of)})
+        if (pair.first->size() == n && n > 1) {
+            pair.second->clear();
+            for (std::size_t r : rows) pair.second->push_back((*pair.first)[r]);
+        }
+    return out;
 }
 
 /// The thresholds of an *_above call over n rows: one value for every row, or one per row; a NaN is refused.
@@ -1069,6 +1168,51 @@ class Sessions {
         return recommend_bar("Sessions::recommend_top",
                              slots, detail::Bar::best(n), filter, excl_ptr, excl_items, include_seen, max_results, order, count_only);
     }
+    /// `recommend` under the group cap (sbr_sessions_recommend_capped; CAPPED in sbr_hip.h): at most cap.cap items of one item group
+    /// per row, with the seen-item memory excluded exactly as in `recommend`.  `groups`: the model's group words on the host
+    /// (ImplicitSequenceModel::item_groups), which the completion of cap.exact applies the rule with.
+    Result<CappedRecommendations, PredictionError> recommend_capped(const std::vector<std::uint32_t>& slots, std::size_t k, const CapArgs& cap,
+                                                                    const std::vector<std::uint32_t>& groups, const TagFilter& filter = {},
+                                                                    const std::vector<std::uint64_t>& excl_ptr = {},
+                                                                    const std::vector<std::uint32_t>& excl_items = {},
+                                                                    bool include_seen = false) const {
+        const sbr_cap_args ca = detail::cap_args(cap, k, "Sessions::recommend_capped");
+        const std::size_t n = slots.size();
+        if (!excl_ptr.empty() && (excl_ptr.size() != n + 1 || excl_ptr.back() > excl_items.size()))
+            throw EngineError(SBR_ERR_INVALID_ARGUMENT, "Sessions::recommend_capped: one exclusion range per slot");
+        const bool filtered = !filter.any_of.empty() || !filter.none_of.empty();
+        const std::vector<std::uint32_t> any = detail::tag_masks(filter.any_of, n, "Sessions::recommend_capped: one any_of mask per slot");
+        const std::vector<std::uint32_t> none_of = detail::tag_masks(filter.none_of, n, "Sessions::recommend_capped: one none_of mask per slot");
+        CappedRecommendations r;
+        r.num_users = n;
+        r.k = k;
+        r.items.resize(n * k);
+        r.scores.resize(n * k);
+        r.complete.assign(n ? n : 1, 0);
+        const std::uint32_t none = 0;
+        const sbr_status st = sbr_sessions_recommend_capped(h_, n ? slots.data() : &none, (std::uint64_t)n, (std::uint32_t)k,
+                                                            excl_ptr.empty() ? nullptr : excl_ptr.data(),
+                                                            excl_ptr.empty() ? nullptr : (excl_items.empty() ? &none : excl_items.data()),
+                                                            include_seen ? SBR_RECOMMEND_INCLUDE_HISTORY : 0u, &ca, filtered ? any.data() : nullptr,
+                                                            filtered ? none_of.data() : nullptr, r.items.data(), r.scores.data(), r.complete.data());
+        if (st == SBR_ERR_INVALID_PREDICTION) return Result<CappedRecommendations, PredictionError>::Err(PredictionError::InvalidPredictionValue);
+        check(st, "sbr_sessions_recommend_capped");
+        r.complete.resize(n);
+        if (cap.exact) {
+            const bool ok = detail::capped_complete(
+                [&](const std::vector<std::size_t>& rows, std::uint64_t top_n) {
+                    std::vector<std::uint32_t> sl;
+                    for (std::size_t i : rows) sl.push_back(slots[i]);
+                    std::vector<std::uint64_t> ep;
+                    std::vector<std::uint32_t> ei;
+                    detail::csr_rows(excl_ptr, excl_items, rows, &ep, &ei);
+                    return recommend_top(sl, {top_n}, detail::filter_rows(filter, n, rows), ep, ei, include_seen);
+                },
+                &r, groups, ca.cap, ca.pool);
+            if (!ok) return Result<CappedRecommendations, PredictionError>::Err(PredictionError::InvalidPredictionValue);
+        }
+        return Result<CappedRecommendations, PredictionError>::Ok(std::move(r));
+    }
     /// The rows' counts of `recommend_above` (its `ptr`; `ids` / `scores` stay empty) without writing any pair: one scan.
     Result<Above, PredictionError> count_above(const std::vector<std::uint32_t>& slots, const std::vector<float>& thresholds,
                                                const TagFilter& filter = {}, const std::vector<std::uint64_t>& excl_ptr = {},
@@ -1318,6 +1462,112 @@ class ImplicitSequenceModel : public OnlineRankingModel<ImplicitUser> {
         check(sbr_model_get_item_tags(replicas_->primary(), out.data()), "sbr_model_get_item_tags");
         return out;
     }
+
+    /// One u32 group word per item — a series, a seller, a category; SBR_NO_GROUP: never capped — kept on the device for the
+    /// recommend_capped calls (sbr_model_set_item_groups).  Serving metadata as the tags: `fit` leaves them alone, a session store
+    /// stays usable, and they are not part of a saved model.
+    void set_item_groups(const std::vector<std::uint32_t>& groups) {
+        if (groups.size() != (std::size_t)replicas_->hparams().num_items)
+            throw EngineError(SBR_ERR_INVALID_ARGUMENT, "set_item_groups: one group word per item");
+        check(sbr_model_set_item_groups(replicas_->primary(), groups.data()), "sbr_model_set_item_groups");
+    }
+    /// The model has no groups again: the recommend_capped calls throw EngineError(SBR_ERR_INVALID_ARGUMENT) until they are set.
+    void clear_item_groups() { check(sbr_model_set_item_groups(replicas_->primary(), nullptr), "sbr_model_set_item_groups"); }
+    /// The group words last set; throws EngineError(SBR_ERR_INVALID_ARGUMENT) while the model has none.
+    std::vector<std::uint32_t> item_groups() const {
+        std::vector<std::uint32_t> out((std::size_t)replicas_->hparams().num_items);
+        check(sbr_model_get_item_groups(replicas_->primary(), out.data()), "sbr_model_get_item_groups");
+        return out;
+    }
+
+    /// `recommend` under the hard slate rule "at most cap.cap items of one item group" (sbr_recommend_capped; CAPPED in sbr_hip.h):
+    /// each row is `recommend`'s order walked from the top, an entry kept while fewer than cap kept entries share its group, k kept
+    /// in all, with predict's bits.  The device applies the rule to each row's best cap.pool; with cap.exact the rows that pool did
+    /// not settle are finished through `recommend_top` and every flag is 1.  `filter`: a tag filter unless both its vectors are empty.
+    Result<CappedRecommendations, PredictionError> recommend_capped(const data::CompressedInteractions& interactions, std::size_t k,
+                                                                    const CapArgs& cap = {}, bool exclude_history = true,
+                                                                    const TagFilter& filter = {}) const {
+        const sbr_cap_args ca = detail::cap_args(cap, k, "recommend_capped");
+        const std::size_t n = interactions.num_users();
+        const bool filtered = !filter.any_of.empty() || !filter.none_of.empty();
+        const std::vector<std::uint32_t> any = tag_masks(filter.any_of, n, "recommend_capped: one any_of mask per user");
+        const std::vector<std::uint32_t> none_of = tag_masks(filter.none_of, n, "recommend_capped: one none_of mask per user");
+        CappedRecommendations r = capped_rows(n, k);
+        const sbr_status st = sbr_recommend_capped(replicas_->primary(), interactions.user_pointers().data(), interactions.item_ids().data(),
+                                                   (std::uint64_t)n, (std::uint32_t)k, exclude_history ? 0u : SBR_RECOMMEND_INCLUDE_HISTORY, &ca,
+                                                   filtered ? any.data() : nullptr, filtered ? none_of.data() : nullptr, r.items.data(),
+                                                   r.scores.data(), r.complete.data());
+        if (st == SBR_ERR_INVALID_PREDICTION) return Result<CappedRecommendations, PredictionError>::Err(PredictionError::InvalidPredictionValue);
+        check(st, "sbr_recommend_capped");
+        r.complete.resize(n);
+        if (cap.exact && std::find(r.complete.begin(), r.complete.end(), 0) != r.complete.end()) {
+            const std::vector<std::uint64_t>& up = interactions.user_pointers();
+            const bool ok = detail::capped_complete(
+                [&](const std::vector<std::size_t>& rows, std::uint64_t top_n) {
+                    std::vector<std::uint64_t> sp, ts;
+                    std::vector<std::uint32_t> si;
+                    detail::csr_rows(up, interactions.item_ids(), rows, &sp, &si);
+                    ts.assign(si.size(), 0);
+                    const data::CompressedInteractions sub(rows.size(), interactions.num_items(), sp, si, ts);
+                    return recommend_top(sub, {top_n}, exclude_history, detail::filter_rows(filter, n, rows));
+                },
+                &r, item_groups(), ca.cap, ca.pool);
+            if (!ok) return Result<CappedRecommendations, PredictionError>::Err(PredictionError::InvalidPredictionValue);
+        }
+        return Result<CappedRecommendations, PredictionError>::Ok(std::move(r));
+    }
+    /// recommend_capped from representations, reps [num_users][embedding_dim] (sbr_recommend_capped_reps); excl_ptr / excl_items:
+    /// per-user exclusion lists as a CSR (both empty: none).
+    Result<CappedRecommendations, PredictionError> recommend_capped_reps(const std::vector<float>& reps, std::size_t k, const CapArgs& cap = {},
+                                                                         const std::vector<std::uint64_t>& excl_ptr = {},
+                                                                         const std::vector<std::uint32_t>& excl_items = {},
+                                                                         const TagFilter& filter = {}) const {
+        const sbr_cap_args ca = detail::cap_args(cap, k, "recommend_capped_reps");
+        const std::size_t dim = (std::size_t)replicas_->hparams().embedding_dim;
+        if (reps.size() % dim) throw EngineError(SBR_ERR_INVALID_ARGUMENT, "recommend_capped_reps: rows of embedding_dim floats");
+        const std::size_t n = reps.size() / dim;
+        if (!excl_ptr.empty() && (excl_ptr.size() != n + 1 || excl_ptr.back() > excl_items.size()))
+            throw EngineError(SBR_ERR_INVALID_ARGUMENT, "recommend_capped_reps: one exclusion range per user");
+        const bool filtered = !filter.any_of.empty() || !filter.none_of.empty();
+        const std::vector<std::uint32_t> any = tag_masks(filter.any_of, n, "recommend_capped_reps: one any_of mask per user");
+        const std::vector<std::uint32_t> none_of = tag_masks(filter.none_of, n, "recommend_capped_reps: one none_of mask per user");
+        CappedRecommendations r = capped_rows(n, k);
+        const std::uint32_t none = 0;
+        const float zero = 0.0f;
+        const sbr_status st = sbr_recommend_capped_reps(replicas_->primary(), reps.empty() ? &zero : reps.data(), (std::uint64_t)n, (std::uint32_t)k,
+                                                        excl_ptr.empty() ? nullptr : excl_ptr.data(),
+                                                        excl_ptr.empty() ? nullptr : (excl_items.empty() ? &none : excl_items.data()), &ca,
+                                                        filtered ? any.data() : nullptr, filtered ? none_of.data() : nullptr, r.items.data(),
+                                                        r.scores.data(), r.complete.data());
+        if (st == SBR_ERR_INVALID_PREDICTION) return Result<CappedRecommendations, PredictionError>::Err(PredictionError::InvalidPredictionValue);
+        check(st, "sbr_recommend_capped_reps");
+        r.complete.resize(n);
+        if (cap.exact && std::find(r.complete.begin(), r.complete.end(), 0) != r.complete.end()) {
+            const bool ok = detail::capped_complete(
+                [&](const std::vector<std::size_t>& rows, std::uint64_t top_n) {
+                    std::vector<float> sub;
+                    for (std::size_t i : rows) sub.insert(sub.end(), reps.begin() + (std::ptrdiff_t)(i * dim), reps.begin() + (std::ptrdiff_t)((i + 1) * dim));
+                    std::vector<std::uint64_t> ep;
+                    std::vector<std::uint32_t> ei;
+                    detail::csr_rows(excl_ptr, excl_items, rows, &ep, &ei);
+                    return recommend_top_reps(sub, {top_n}, ep, ei, detail::filter_rows(filter, n, rows));
+                },
+                &r, item_groups(), ca.cap, ca.pool);
+            if (!ok) return Result<CappedRecommendations, PredictionError>::Err(PredictionError::InvalidPredictionValue);
+        }
+        return Result<CappedRecommendations, PredictionError>::Ok(std::move(r));
+    }
+  private:
+    static CappedRecommendations capped_rows(std::size_t n, std::size_t k) {
+        CappedRecommendations r;
+        r.num_users = n;
+        r.k = k;
+        r.items.resize(n * k);
+        r.scores.resize(n * k);
+        r.complete.assign(n ? n : 1, 0);
+        return r;
+    }
+  public:
 
     /// `recommend` under a per-user tag filter (sbr_recommend_filtered): the exact top k of the items each user's masks allow, the
     /// bits of `recommend` with every other item added to the user's exclusions; tested inside the scan.  Not with `among`.

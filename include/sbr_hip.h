@@ -898,6 +898,50 @@ sbr_status sbr_sessions_audience_top(sbr_sessions* st, const uint32_t* items, ui
                                      uint64_t num_slots, const uint64_t* excl_ptr, const uint32_t* excl_slots, uint32_t flags, float* out_cuts,
                                      uint64_t* out_counts, uint64_t* out_total, uint64_t capacity, uint32_t* out_ids, float* out_scores);
 
+/* CAPPED — exact top-k with at most `cap` items of one ITEM GROUP: "at most one per series", "two per seller", "three of a category"
+ * (no counterpart in the reference crate; a larger k and a filter on the host is not exact, because no k is known to be enough).
+ * ITEM GROUPS: a model may hold groups[num_items], one u32 per item, on its device.  SBR_NO_GROUP = "belongs to no group, never
+ * capped".  Serving metadata exactly as the item tags: fit, sbr_model_set_param and a load leave them alone, setting them bumps no
+ * parameter generation (a session store stays current), they are not saved and are freed with the model.
+ * sbr_model_set_item_groups(m, NULL) clears them; sbr_model_get_item_groups gives SBR_ERR_INVALID_ARGUMENT while there are none.
+ * THE RULE R(L, cap, k): L = a row's eligible items in the total order (score descending, ties to the lower id, -0.0 == +0.0).  Walk
+ * L; keep an entry iff its group is SBR_NO_GROUP or fewer than cap entries of its group were kept before it; stop after k kept.  The
+ * kept entries of a group are its first cap, so an entry is kept iff its ordinal within its group, among the entries before it in
+ * L, is below cap — whatever k, the other groups and every earlier decision are.
+ * THE CALL is the plain call at k = pool followed by R on that row.  Eligibility is the top-k sibling's in everything: history
+ * (flags: SBR_RECOMMEND_INCLUDE_HISTORY) or exclusion lists, a session's seen-item memory, and the masks any_of / none_of of ITEM
+ * TAGS — both NULL: no filter and no tags needed; either one non-NULL: the *_filtered call's rules.  Row u of out_items / out_scores
+ * [n][k] (scores optional): the kept items with their pool scores — sbr_predict's bits — padded with (0xFFFFFFFF, -inf).
+ * out_complete [n] (optional), one byte per row, is 1 iff k entries were kept or the pool row itself had padding (the pool held
+ * every eligible item).  Either way the row is the exact R over the whole catalogue: an item outside the pool scores no better than
+ * every pool entry, and the first k kept never reach it.  Otherwise 0: the row holds fewer than k entries, a prefix of the exact
+ * answer, and a larger pool — or sbr_recommend_top at a growing n with the rule on the host, which the Python and C++ layers do —
+ * finishes it.
+ * ARGUMENTS: cap >= 1; 1 <= k <= pool <= SBR_RECOMMEND_MAX_K; pool == 0: the default min(1 024, max(64, 4 k)).
+ * SBR_ERR_INVALID_ARGUMENT, with nothing written, for anything else, a NULL sbr_cap_args, a model without groups, masks on a model
+ * without tags, and wherever the plain call gives it.  SBR_ERR_INVALID_PREDICTION: the scan's rule, a non-finite score of a scanned
+ * pair.  IDENTITIES: with every item in a group of its own, or every item SBR_NO_GROUP, or cap >= k, the row is the plain call's at
+ * k bit for bit and every row is complete; cap = 1 is "collapse by group".  Cost: the plain scan at k = pool and one workgroup per
+ * row over the pool's ids.  Deterministic; reads parameters only.
+ * Not offered: caps on similar_items, audience, the sampled or diverse calls, a cap per user or per group, among= subsets, saved
+ * groups, a cap inside the scan that needs no pool. */
+#define SBR_NO_GROUP 0xFFFFFFFFu
+typedef struct sbr_cap_args {
+    uint32_t cap;
+    uint32_t pool; /* 0: the default */
+} sbr_cap_args;
+sbr_status sbr_model_set_item_groups(sbr_model* m, const uint32_t* groups);
+sbr_status sbr_model_get_item_groups(sbr_model* m, uint32_t* out);
+sbr_status sbr_recommend_capped(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users, uint32_t k, uint32_t flags,
+                                const struct sbr_cap_args* cap, const uint32_t* any_of, const uint32_t* none_of, uint32_t* out_items,
+                                float* out_scores, uint8_t* out_complete);
+sbr_status sbr_recommend_capped_reps(sbr_model* m, const float* reps, uint64_t num_users, uint32_t k, const uint64_t* excl_ptr,
+                                     const uint32_t* excl_items, const struct sbr_cap_args* cap, const uint32_t* any_of,
+                                     const uint32_t* none_of, uint32_t* out_items, float* out_scores, uint8_t* out_complete);
+sbr_status sbr_sessions_recommend_capped(sbr_sessions* st, const uint32_t* slots, uint64_t n, uint32_t k, const uint64_t* excl_ptr,
+                                         const uint32_t* excl_items, uint32_t flags, const struct sbr_cap_args* cap, const uint32_t* any_of,
+                                         const uint32_t* none_of, uint32_t* out_items, float* out_scores, uint8_t* out_complete);
+
 /* ≙ the serde derives (lstm.rs:204,386; ewma.rs:208,401): element counts and raw access. */
 sbr_status sbr_model_param_count(const sbr_model* m, int32_t which, uint64_t* out_count);
 sbr_status sbr_model_get_param(sbr_model* m, int32_t which, float* host_out, uint64_t count);

@@ -97,6 +97,14 @@ class SbrSampleArgs(C.Structure):
     ]
 
 
+class SbrCapArgs(C.Structure):
+    """struct sbr_cap_args of the *_capped calls"""
+    _fields_ = [
+        ("cap", C.c_uint32),
+        ("pool", C.c_uint32),
+    ]
+
+
 def storage_dim(embedding_dim: int) -> int:
     """Width the engine stores an embedding_dim in (16 / 32 / 64 / 128 / 256; the extra columns are zero and stay
     zero — sbr_engine.hip `storage_dim`).  Parameters, user representations and predictions use embedding_dim;

@@ -187,6 +187,11 @@ def load():
         "sbr_audience_top_reps": [vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp, vp, vp, vp, u64p, C.c_uint64, vp, vp],
         "sbr_audience_top": [vp, vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint32, vp, vp, u64p, C.c_uint64, vp, vp],
         "sbr_sessions_audience_top": [vp, vp, C.c_uint64, vp, vp, C.c_uint64, vp, vp, C.c_uint32, vp, vp, u64p, C.c_uint64, vp, vp],
+        "sbr_model_set_item_groups": [vp, vp],
+        "sbr_model_get_item_groups": [vp, vp],
+        "sbr_recommend_capped": [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp],
+        "sbr_recommend_capped_reps": [vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp],
+        "sbr_sessions_recommend_capped": [vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint32, vp, vp, vp, vp, vp, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -253,4 +258,6 @@ DECLARED_SYMBOLS = [
     "sbr_audience_above_reps", "sbr_audience_above", "sbr_sessions_audience_above",
     "sbr_recommend_top", "sbr_recommend_top_reps", "sbr_sessions_recommend_top",
     "sbr_audience_top_reps", "sbr_audience_top", "sbr_sessions_audience_top",
+    "sbr_model_set_item_groups", "sbr_model_get_item_groups",
+    "sbr_recommend_capped", "sbr_recommend_capped_reps", "sbr_sessions_recommend_capped",
 ]

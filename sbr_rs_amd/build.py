@@ -207,6 +207,15 @@ def build_top_tests(force: bool = False, verbose: bool = True) -> str:
     return _build_cpp_program(TOP_SRC, TOP_BIN, force, verbose)
 
 
+CAPPED_SRC = os.path.join(REPO, "tests", "cpp", "capped_tests.cpp")
+CAPPED_BIN = os.path.join(REPO, "tests", "cpp", "_build", "capped_tests")
+
+
+def build_capped_tests(force: bool = False, verbose: bool = True) -> str:
+    """g++ build of the C++ host layer's recommend_capped test program."""
+    return _build_cpp_program(CAPPED_SRC, CAPPED_BIN, force, verbose)
+
+
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv))
     print(build_facade_tests(force="--force" in sys.argv))
@@ -224,3 +233,4 @@ if __name__ == "__main__":
     print(build_partition_tests(force="--force" in sys.argv))
     print(build_above_tests(force="--force" in sys.argv))
     print(build_top_tests(force="--force" in sys.argv))
+    print(build_capped_tests(force="--force" in sys.argv))

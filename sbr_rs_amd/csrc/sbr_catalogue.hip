@@ -21,6 +21,8 @@
  *                            score policy, s(q, i) = chain_dot(H[j], E[i]) * r[i], r in the bias's place
  *   diverse_select_kernel  : recommend_diverse's greedy maximal-marginal-relevance picks from topk_merge_kernel's rows at k = pool:
  *                            one workgroup per user, the pool's rows in LDS
+ *   capped_select_kernel   : recommend_capped's rule over topk_merge_kernel's rows at k = pool — an entry is kept while fewer than cap
+ *                            earlier entries share its item group — and the compaction of the first k kept: one workgroup per user
  *   subset_gather_kernel   : recommend_among's sub-table E'[j] = E[S[j]], b'[j] = b[S[j]] of a sorted, unique item set S; the scan is
  *                            topk_gemm_kernel + topk_merge_kernel on a ModelView of E', b', |S|, and
  *   subset_ids_kernel      : maps the merged lists' positions in S back to catalogue ids
@@ -1146,6 +1148,74 @@ __global__ __launch_bounds__(256) void diverse_select_kernel(ModelView m, const 
         if (out_scores) out_scores[u * k_out + t] = -INFINITY;
     }
     if (__any(bad) && lane == 0) atomicOr(nonfinite_flag, 1u);
+}
+
+// ------------------------------------------------------------------------------------------------
+// recommend_capped: at most `cap` items of one item group among the first k_out kept entries of a user's best `pool`
+// ------------------------------------------------------------------------------------------------
+/* One workgroup per user.  Its pool is row u of topk_merge_kernel's output at k = pool <= CAP_MAX_POOL: n real entries, best first,
+ * then padding.  Static LDS: ids [pool] and grp [pool], the group words gathered from item_groups by id (8 KB at the largest pool).
+ * An entry is kept iff its group is CAP_NO_GROUP or fewer than `cap` earlier entries of the row share its group — its ordinal within
+ * its group, which depends on no other decision.  Thread tid owns the positions tid, tid + 256, ...: for position j it counts the
+ * earlier positions of j's group (every lane of a wave reads the same grp[i]: an LDS broadcast) and stops at cap; the keep flags of
+ * its at most CAP_MAX_POOL / 256 positions stay in a register.  The compaction runs in position order, one pass per 256 positions:
+ * a ballot and a popcount within the wave, the waves' sums through LDS, a running base across the passes; the first k_out kept
+ * entries leave with their pool scores, then the padding, and complete[u] = kept >= k_out || n < pool (the pool held every eligible
+ * item).  No global atomics; nothing depends on the dispatch order. */
+constexpr uint32_t CAP_NO_GROUP = 0xFFFFFFFFu;
+constexpr uint32_t CAP_MAX_POOL = 1024u;
+__global__ __launch_bounds__(256) void capped_select_kernel(const uint32_t* item_groups, uint32_t num_items, const uint32_t* pool_items,
+                                                            const float* pool_scores, uint32_t pool, uint32_t k_out, uint32_t cap,
+                                                            uint32_t* out_items, float* out_scores, uint8_t* out_complete) {
+    __shared__ uint32_t ids[CAP_MAX_POOL];
+    __shared__ uint32_t grp[CAP_MAX_POOL];
+    __shared__ uint32_t wsum[4];
+    __shared__ uint32_t real;
+    const uint32_t tid = threadIdx.x;
+    const uint32_t lane = tid & 63u;
+    const uint32_t wave = tid >> 6;
+    const size_t u = blockIdx.x;
+    if (tid == 0) real = 0;
+    __syncthreads();
+    uint32_t mine = 0; /* real entries among this thread's positions; the real entries are a prefix of the row */
+    for (uint32_t j = tid; j < pool; j += 256) {
+        const uint32_t id = pool_items[u * pool + j];
+        ids[j] = id;
+        grp[j] = id < num_items ? item_groups[id] : CAP_NO_GROUP;
+        mine += id != TK_NONE ? 1u : 0u;
+    }
+    if (mine) atomicAdd(&real, mine);
+    __syncthreads();
+    const uint32_t np = real; /* the pool's size n */
+    uint32_t keep = 0;        /* bit p: position p * 256 + tid is kept */
+    for (uint32_t p = 0, j = tid; j < np; ++p, j += 256) {
+        const uint32_t g = grp[j];
+        uint32_t c = 0;
+        if (g != CAP_NO_GROUP)
+            for (uint32_t i = 0; i < j && c < cap; ++i) c += grp[i] == g ? 1u : 0u;
+        keep |= (c < cap ? 1u : 0u) << p;
+    }
+    uint32_t base = 0; /* kept entries ahead of the pass: the same in every thread */
+    for (uint32_t p = 0; p * 256 < pool; ++p) {
+        const uint32_t j = p * 256 + tid;
+        const bool kp = (keep >> p) & 1u;
+        const uint64_t b = __ballot(kp);
+        if (lane == 0) wsum[wave] = (uint32_t)__popcll(b);
+        __syncthreads();
+        uint32_t pos = base + (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
+        for (uint32_t w = 0; w < wave; ++w) pos += wsum[w];
+        base += wsum[0] + wsum[1] + wsum[2] + wsum[3];
+        if (kp && pos < k_out) {
+            out_items[u * k_out + pos] = ids[j];
+            if (out_scores) out_scores[u * k_out + pos] = pool_scores[u * pool + j];
+        }
+        __syncthreads(); /* the next pass writes wsum again */
+    }
+    for (uint32_t t = base + tid; t < k_out; t += 256) {
+        out_items[u * k_out + t] = TK_NONE;
+        if (out_scores) out_scores[u * k_out + t] = -INFINITY;
+    }
+    if (tid == 0) out_complete[u] = base >= k_out || np < pool ? 1 : 0;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2300,6 +2370,15 @@ int launch_diverse_select(const ModelView& m, const uint32_t* pool_items, const 
         hipLaunchKernelGGL((diverse_select_kernel<DD>), dim3(num_users), dim3(256), lds, s, m, pool_items, pool_scores, pool, k_out, trade_off,
                            cosine ? 1 : 0, out_items, out_scores, nonfinite_flag);
     });
+    return 1;
+}
+
+int launch_capped_select(const uint32_t* item_groups, uint32_t num_items, const uint32_t* pool_items, const float* pool_scores,
+                         uint32_t num_users, uint32_t pool, uint32_t k_out, uint32_t cap, uint32_t* out_items, float* out_scores,
+                         uint8_t* out_complete, hipStream_t s) {
+    if (num_users == 0 || pool > CAP_MAX_POOL) return 0;
+    hipLaunchKernelGGL(capped_select_kernel, dim3(num_users), dim3(256), 0, s, item_groups, num_items, pool_items, pool_scores, pool, k_out, cap,
+                       out_items, out_scores, out_complete);
     return 1;
 }
 

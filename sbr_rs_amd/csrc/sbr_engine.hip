@@ -452,6 +452,7 @@ struct sbr_model {
                           * (SmallTail + small_back: four per step), 2 runs of steps in one launch where the shape allows */
     uint32_t* item_tags = nullptr; /* sbr_model_set_item_tags: one tag word per item on this model's device, null until set.  Serving
                                     * metadata (guarded by mu), not a parameter: no generation bump, not saved, freed with the model */
+    uint32_t* item_groups = nullptr; /* sbr_model_set_item_groups: one group word per item, stored and freed as item_tags */
     DeviceArena eval_arena;        /* prediction-side scratch (guarded by mu) */
     hipStream_t stream = nullptr;
     bool own_stream = false;
@@ -1122,6 +1123,7 @@ void sbr_model_destroy(sbr_model* m) {
     dfree(v.alpha); dfree(v.alpha_acc);
     dfree(v.Wm); dfree(v.bWm); dfree(v.alpha_m);
     dfree(m->item_tags);
+    dfree(m->item_groups);
     for (auto& tp : m->pending) { hipEventDestroy(tp.a); hipEventDestroy(tp.b); }
     m->eval_arena.release();
     if (m->own_stream && m->stream) hipStreamDestroy(m->stream);
@@ -3982,6 +3984,13 @@ struct Diverse {
     uint32_t metric;
 };
 
+/* recommend_capped's rule behind a scan: the first k_out entries of the scan's k (the pool) per user of which no item group holds
+ * more than cap; out_complete (host, one byte per user of the call) nullable */
+struct Capped {
+    uint32_t k_out, cap;
+    uint8_t* out_complete;
+};
+
 /* the tag filter of a *_filtered call: the caller's masks, one pair per user of the call (a null array: all zeros) */
 struct TagFilterArg {
     const uint32_t *any_of, *none_of;
@@ -4239,6 +4248,7 @@ struct ScanVariant {
     const Sample* sm = nullptr;
     const Partition* pt = nullptr;
     Above* ab = nullptr;
+    const Capped* cp = nullptr;
     static ScanVariant of(const Diverse* dv, const TagFilterArg* flt, const Sample* sm = nullptr, const Partition* pt = nullptr) {
         ScanVariant v;
         v.dv = dv; v.flt = flt; v.sm = sm; v.pt = pt;
@@ -4262,7 +4272,10 @@ struct ScanVariant {
  * With v.pt (log_partition; k == 1, not with item rows, a subset, v.dv or v.sm) the scan finds the rows' shifts and a second scan
  * sums the softmax weights: out_items / out_scores are unused (null) and the results are v.pt->out_shift / out_mass.
  * With v.ab (recommend_above; k == 1, not with item rows, a subset, v.dv, v.sm or v.pt) no top-k scan runs: every chunk is
- * above_chunk's count and fill over the same representations, exclusion CSR and masks; out_items / out_scores are unused (null). */
+ * above_chunk's count and fill over the same representations, exclusion CSR and masks; out_items / out_scores are unused (null).
+ * With v.cp (recommend_capped; the model's item groups set; not with item rows, a subset, v.dv, v.sm, v.pt or v.ab) the scan's rows
+ * are the users' pools: the same launch keeps v.cp->k_out of each under the group cap, the results are num_users x v.cp->k_out and
+ * v.cp->out_complete the rows' flags. */
 sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, uint32_t k, uint32_t* out_items, float* out_scores,
                           const ScanVariant& v = ScanVariant()) {
     const Diverse* dv = v.dv;
@@ -4274,6 +4287,8 @@ sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, 
     if (pt && (s.item_rows || v.subset || dv || sm || k != 1)) return SBR_ERR_INVALID_ARGUMENT;
     Above* ab = v.ab;
     if (ab && (s.item_rows || v.subset || dv || sm || pt || k != 1)) return SBR_ERR_INVALID_ARGUMENT;
+    const Capped* cp = v.cp;
+    if (cp && (!m->item_groups || s.item_rows || v.subset || dv || sm || pt || ab)) return SBR_ERR_INVALID_ARGUMENT;
     const size_t seen_w = s.seen ? s.seen->w : 0;
     std::vector<uint64_t> users(num_users);
     for (uint64_t u = 0; u < num_users; ++u) users[u] = u;
@@ -4288,6 +4303,7 @@ sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, 
         float* rnorm = nullptr; /* item rows: the catalogue's reciprocal norms, once per chunk (the arena does not outlive a carve) */
         uint32_t* dv_items = nullptr; /* dv: the selection's rows, nu x dv->k_out */
         float* dv_scores = nullptr;
+        uint8_t* cp_complete = nullptr; /* cp: the rows' flags; the kept rows are dv_items / dv_scores, nu x cp->k_out */
         uint32_t *seen_slot = nullptr, *seen_caller = nullptr; /* s.seen: the chunk's slots and caller lists, the build kernel's inputs */
         float* pt_shift = nullptr; /* pt: the rows' shifts and masses */
         unsigned long long* pt_mass = nullptr;
@@ -4309,6 +4325,11 @@ sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, 
             if (dv) {
                 dv_items = ar.take<uint32_t>(nu * dv->k_out);
                 dv_scores = ar.take<float>(nu * dv->k_out);
+            }
+            if (cp) {
+                dv_items = ar.take<uint32_t>(nu * cp->k_out);
+                dv_scores = ar.take<float>(nu * cp->k_out);
+                cp_complete = ar.take<uint8_t>(nu);
             }
         }, &ur));
         const bool excl = !ur.b.list_ptr.empty() || s.seen;
@@ -4360,7 +4381,7 @@ sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, 
             }));
             continue;
         }
-        const size_t ko = dv ? dv->k_out : k; /* the width of the rows that leave */
+        const size_t ko = dv ? dv->k_out : cp ? cp->k_out : k; /* the width of the rows that leave */
         /* the selection reads the pool's scores whether or not the caller wants any; a sampled scan's are its keys */
         sbr::TopkScan sc = tb.scan(nu, k, excl, out_scores || dv || sm || pt, v.flt ? m->item_tags : nullptr);
         if (sm) sc.g = sbr::SampleNoise{sm->inv_t, smb.keys};
@@ -4376,11 +4397,15 @@ sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, 
             if (dv)
                 n += sbr::launch_diverse_select(m->mv, tb.items, tb.scores, (uint32_t)nu, k, dv->k_out, dv->trade_off, dv->metric == SBR_SIMILAR_COSINE,
                                                 dv_items, out_scores ? dv_scores : nullptr, tb.flag, m->stream);
+            if (cp)
+                n += sbr::launch_capped_select(m->item_groups, (uint32_t)m->hp.num_items, tb.items, sc.out_scores, (uint32_t)nu, k, cp->k_out,
+                                               cp->cap, dv_items, out_scores ? dv_scores : nullptr, cp_complete, m->stream);
             return n;
-        }, {{out_items ? out_items + ch.c0 * ko : nullptr, dv ? dv_items : tb.items, nu * ko * 4},
+        }, {{out_items ? out_items + ch.c0 * ko : nullptr, dv || cp ? dv_items : tb.items, nu * ko * 4},
+            {cp && cp->out_complete ? cp->out_complete + ch.c0 : nullptr, cp_complete, nu},
             {pt ? pt->out_shift + ch.c0 : nullptr, pt_shift, nu * 4},
             {pt ? pt->out_mass + ch.c0 : nullptr, pt_mass, nu * 8},
-            {out_scores ? out_scores + ch.c0 * ko : nullptr, dv ? dv_scores : sm ? smb.plain : tb.scores, nu * ko * 4},
+            {out_scores ? out_scores + ch.c0 * ko : nullptr, dv || cp ? dv_scores : sm ? smb.plain : tb.scores, nu * ko * 4},
             {sm && sm->out_keys ? sm->out_keys + ch.c0 * ko : nullptr, tb.scores, nu * ko * 4}}));
     }
     return SBR_OK;
@@ -4399,34 +4424,50 @@ bool diverse_args_ok(const sbr_model* m, uint32_t k, uint32_t pool, float trade_
 
 /* k of a call of the recommend family, which scans at k: the plain call's own k, or with dv (recommend_diverse) the pool, of
  * which the selection keeps dv->k_out, the caller's k */
-bool scan_k_ok(const sbr_model* m, uint32_t k, const Diverse* dv) {
+bool scan_k_ok(const sbr_model* m, uint32_t k, const Diverse* dv, const Capped* cp = nullptr) {
+    /* recommend_capped: k is the pool; that the model holds groups is recommend_scan's check, under the model's lock */
+    if (cp && (dv || cp->cap < 1 || cp->k_out < 1 || cp->k_out > k)) return false;
     return dv ? diverse_args_ok(m, dv->k_out, k, dv->trade_off, dv->metric) : k >= 1 && k <= SBR_RECOMMEND_MAX_K;
+}
+
+/* the arguments the *_capped calls share: the rule and the scan's k (the pool; 0: the default min(1 024, max(64, 4 k))) out of
+ * sbr_cap_args, or false without them; the rest is scan_k_ok's */
+bool capped_args(const sbr_cap_args* a, uint32_t k, uint8_t* out_complete, Capped* out, uint32_t* pool) {
+    if (!a) return false;
+    const uint64_t dflt = std::min<uint64_t>(1024, std::max<uint64_t>(64, 4ull * k));
+    *pool = a->pool ? a->pool : (uint32_t)dflt;
+    *out = Capped{k, a->cap, out_complete};
+    return true;
 }
 
 /* the plain calls, their *_filtered forms (flt non-null) and their diverse forms (dv non-null: k is the pool) */
 sbr_status recommend_call(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users, uint32_t k, uint32_t flags,
                           uint32_t* out_items, float* out_scores, const TagFilterArg* flt, const Diverse* dv = nullptr,
-                          const Sample* sm = nullptr) {
+                          const Sample* sm = nullptr, const Capped* cp = nullptr) {
     if (!m || !user_ptr || (num_users && !out_items)) return SBR_ERR_INVALID_ARGUMENT;
-    if (!scan_k_ok(m, k, dv) || (flags & ~SBR_RECOMMEND_INCLUDE_HISTORY)) return SBR_ERR_INVALID_ARGUMENT;
+    if (!scan_k_ok(m, k, dv, cp) || (flags & ~SBR_RECOMMEND_INCLUDE_HISTORY)) return SBR_ERR_INVALID_ARGUMENT;
     std::lock_guard<std::mutex> lock(m->mu);
     SBRCHK(enter_reader(m));
     SBRCHK(check_csr(m, user_ptr, num_users, item_ids, false));
     /* the WHOLE history is masked (evaluation.rs:30-32) */
+    ScanVariant v = ScanVariant::of(dv, flt, sm);
+    v.cp = cp;
     return recommend_scan(m, RepSource::of_histories(user_ptr, item_ids, 0, !(flags & SBR_RECOMMEND_INCLUDE_HISTORY)), num_users, k, out_items,
-                          out_scores, ScanVariant::of(dv, flt, sm));
+                          out_scores, v);
 }
 
 sbr_status recommend_reps_call(sbr_model* m, const float* reps, uint64_t num_users, uint32_t k, const uint64_t* excl_ptr,
                                const uint32_t* excl_items, uint32_t* out_items, float* out_scores, const TagFilterArg* flt,
-                               const Diverse* dv = nullptr, const Sample* sm = nullptr) {
+                               const Diverse* dv = nullptr, const Sample* sm = nullptr, const Capped* cp = nullptr) {
     if (!m || (num_users && (!reps || !out_items))) return SBR_ERR_INVALID_ARGUMENT;
-    if (!scan_k_ok(m, k, dv)) return SBR_ERR_INVALID_ARGUMENT;
+    if (!scan_k_ok(m, k, dv, cp)) return SBR_ERR_INVALID_ARGUMENT;
     if (!excl_args_ok(excl_ptr, excl_items, num_users)) return SBR_ERR_INVALID_ARGUMENT;
     std::lock_guard<std::mutex> lock(m->mu);
     SBRCHK(enter_reader(m));
     if (excl_ptr) SBRCHK(check_csr(m, excl_ptr, num_users, excl_items, false));
-    return recommend_scan(m, RepSource::of_rows(reps, excl_ptr, excl_items), num_users, k, out_items, out_scores, ScanVariant::of(dv, flt, sm));
+    ScanVariant v = ScanVariant::of(dv, flt, sm);
+    v.cp = cp;
+    return recommend_scan(m, RepSource::of_rows(reps, excl_ptr, excl_items), num_users, k, out_items, out_scores, v);
 }
 
 }  // namespace
@@ -4669,6 +4710,56 @@ sbr_status sbr_recommend_diverse_filtered_reps(sbr_model* m, const float* reps, 
     const TagFilterArg flt{any_of, none_of};
     const Diverse dv{k, trade_off, metric};
     return recommend_reps_call(m, reps, num_users, pool, excl_ptr, excl_items, out_items, out_scores, &flt, &dv);
+}
+
+/* ---------------------------------------------------------------------------------------------
+ * item groups and the capped top-k: recommend's scan at k = pool, then the rule (sbr_catalogue.hip, capped_select_kernel)
+ * ------------------------------------------------------------------------------------------- */
+sbr_status sbr_model_set_item_groups(sbr_model* m, const uint32_t* groups) {
+    if (!m) return SBR_ERR_INVALID_ARGUMENT;
+    std::lock_guard<std::mutex> lock(m->mu);
+    SBRCHK(ensure_device(m));
+    HIPCHK(hipStreamSynchronize(m->stream)); /* no scan of this model is reading the old words */
+    if (!groups) {
+        dfree(m->item_groups);
+        m->item_groups = nullptr;
+        return SBR_OK;
+    }
+    if (!m->item_groups) SBRCHK(dmalloc(&m->item_groups, (size_t)m->hp.num_items));
+    HIPCHK(hipMemcpy(m->item_groups, groups, (size_t)m->hp.num_items * 4, hipMemcpyHostToDevice));
+    return SBR_OK;
+}
+
+sbr_status sbr_model_get_item_groups(sbr_model* m, uint32_t* out) {
+    if (!m || !out) return SBR_ERR_INVALID_ARGUMENT;
+    std::lock_guard<std::mutex> lock(m->mu);
+    if (!m->item_groups) return SBR_ERR_INVALID_ARGUMENT;
+    SBRCHK(ensure_device(m));
+    HIPCHK(hipStreamSynchronize(m->stream));
+    HIPCHK(hipMemcpy(out, m->item_groups, (size_t)m->hp.num_items * 4, hipMemcpyDeviceToHost));
+    return SBR_OK;
+}
+
+sbr_status sbr_recommend_capped(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users, uint32_t k, uint32_t flags,
+                                const struct sbr_cap_args* cap, const uint32_t* any_of, const uint32_t* none_of, uint32_t* out_items,
+                                float* out_scores, uint8_t* out_complete) {
+    Capped cp;
+    TagFilterArg hold;
+    uint32_t pool = 0;
+    if (!capped_args(cap, k, out_complete, &cp, &pool)) return SBR_ERR_INVALID_ARGUMENT;
+    return recommend_call(m, user_ptr, item_ids, num_users, pool, flags, out_items, out_scores, sample_filter(any_of, none_of, &hold), nullptr,
+                          nullptr, &cp);
+}
+
+sbr_status sbr_recommend_capped_reps(sbr_model* m, const float* reps, uint64_t num_users, uint32_t k, const uint64_t* excl_ptr,
+                                     const uint32_t* excl_items, const struct sbr_cap_args* cap, const uint32_t* any_of,
+                                     const uint32_t* none_of, uint32_t* out_items, float* out_scores, uint8_t* out_complete) {
+    Capped cp;
+    TagFilterArg hold;
+    uint32_t pool = 0;
+    if (!capped_args(cap, k, out_complete, &cp, &pool)) return SBR_ERR_INVALID_ARGUMENT;
+    return recommend_reps_call(m, reps, num_users, pool, excl_ptr, excl_items, out_items, out_scores, sample_filter(any_of, none_of, &hold),
+                               nullptr, nullptr, &cp);
 }
 
 /* ---------------------------------------------------------------------------------------------
@@ -5442,11 +5533,12 @@ RepSource RepSource::of_sessions(const sbr_sessions* st, const std::vector<int>&
 /* sbr_sessions_recommend*, and with dv (k is the pool) sbr_sessions_recommend_diverse*, which have no flags argument: flags = 0 */
 sbr_status sessions_recommend_call(sbr_sessions* st, const uint32_t* slots, uint64_t n, uint32_t k, const uint64_t* excl_ptr,
                                    const uint32_t* excl_items, uint32_t flags, uint32_t* out_items, float* out_scores, const TagFilterArg* flt,
-                                   const Diverse* dv = nullptr, const Sample* sm = nullptr, const Partition* pt = nullptr, Above* ab = nullptr) {
+                                   const Diverse* dv = nullptr, const Sample* sm = nullptr, const Partition* pt = nullptr, Above* ab = nullptr,
+                                   const Capped* cp = nullptr) {
     if (!st || (n && !out_items && !pt && !ab)) return SBR_ERR_INVALID_ARGUMENT;
     /* a store with memory takes sbr_recommend's flag; one without keeps refusing every flag */
     if (st->seen.w ? (flags & ~SBR_RECOMMEND_INCLUDE_HISTORY) != 0 : flags != 0) return SBR_ERR_INVALID_ARGUMENT;
-    if (!scan_k_ok(st->m, k, dv)) return SBR_ERR_INVALID_ARGUMENT;
+    if (!scan_k_ok(st->m, k, dv, cp)) return SBR_ERR_INVALID_ARGUMENT;
     if (!excl_args_ok(excl_ptr, excl_items, n)) return SBR_ERR_INVALID_ARGUMENT;
     sbr_model* m = st->m;
     std::lock_guard<std::mutex> lock(m->mu);
@@ -5457,6 +5549,7 @@ sbr_status sessions_recommend_call(sbr_sessions* st, const uint32_t* slots, uint
     const bool seen = st->seen.w && !(flags & SBR_RECOMMEND_INCLUDE_HISTORY);
     ScanVariant v = ScanVariant::of(dv, flt, sm, pt);
     v.ab = ab;
+    v.cp = cp;
     return recommend_scan(m, RepSource::of_sessions(st, rows, excl_ptr, excl_items, seen ? slots : nullptr), n, k, out_items, out_scores, v);
 }
 
@@ -5520,6 +5613,17 @@ sbr_status sbr_sessions_recommend_top(sbr_sessions* st, const uint32_t* slots, u
                                    nullptr, nullptr, &ab));
     *out_total = ab.total;
     return SBR_OK;
+}
+
+sbr_status sbr_sessions_recommend_capped(sbr_sessions* st, const uint32_t* slots, uint64_t n, uint32_t k, const uint64_t* excl_ptr,
+                                         const uint32_t* excl_items, uint32_t flags, const struct sbr_cap_args* cap, const uint32_t* any_of,
+                                         const uint32_t* none_of, uint32_t* out_items, float* out_scores, uint8_t* out_complete) {
+    Capped cp;
+    TagFilterArg hold;
+    uint32_t pool = 0;
+    if (!capped_args(cap, k, out_complete, &cp, &pool)) return SBR_ERR_INVALID_ARGUMENT;
+    return sessions_recommend_call(st, slots, n, pool, excl_ptr, excl_items, flags, out_items, out_scores, sample_filter(any_of, none_of, &hold),
+                                   nullptr, nullptr, nullptr, nullptr, &cp);
 }
 
 sbr_status sbr_sessions_recommend_diverse(sbr_sessions* st, const uint32_t* slots, uint64_t n, uint32_t k, uint32_t pool, float trade_off,

@@ -404,6 +404,13 @@ uint32_t diverse_max_pool(int d);
 int launch_diverse_select(const ModelView& m, const uint32_t* pool_items, const float* pool_scores, uint32_t num_users, uint32_t pool,
                           uint32_t k_out, float trade_off, bool cosine, uint32_t* out_items, float* out_scores, uint32_t* nonfinite_flag,
                           hipStream_t s);
+/* the group cap behind a scan (sbr_catalogue.hip, capped_select_kernel; the contract: CAPPED in include/sbr_hip.h): pool_items /
+ * pool_scores [num_users][pool] are launch_recommend's outputs at k = pool (pool_scores and out_scores both null: no scores);
+ * item_groups [num_items] the model's group words.  out_items / out_scores [num_users][k_out]: the first k_out entries of each pool
+ * row that the rule keeps, padded as the pool's rows; out_complete [num_users] the rows' flags.  1 <= k_out <= pool <= 1 024, cap >= 1. */
+int launch_capped_select(const uint32_t* item_groups, uint32_t num_items, const uint32_t* pool_items, const float* pool_scores,
+                         uint32_t num_users, uint32_t pool, uint32_t k_out, uint32_t cap, uint32_t* out_items, float* out_scores,
+                         uint8_t* out_complete, hipStream_t s);
 /* exact top-k neighbours of catalogue items (sbr_catalogue.hip): item_rnorm_kernel writes rnorm [num_items] (1 / |E[i]|, 0 for a zero
  * row; all 1.0f unless `cosine`) and raises the flag for a non-finite squared norm, similar_query_kernel writes the scan rows
  * H [sc.n][d] = E[query[j]] * rnorm[query[j]], and launch_recommend's two kernels rank s(j, i) = chain_dot(H[j], E[i]) *

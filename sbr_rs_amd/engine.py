@@ -22,6 +22,7 @@ SIMILAR_INCLUDE_SELF = 1  # SBR_SIMILAR_INCLUDE_SELF
 RECOMMEND_INCLUDE_HISTORY = 1  # SBR_RECOMMEND_INCLUDE_HISTORY
 SESSIONS_MAX_SEEN = 1024  # SBR_SESSIONS_MAX_SEEN
 _SIMILAR_METRICS = {"cosine": SIMILAR_COSINE, "dot": SIMILAR_DOT}
+NO_GROUP = 0xFFFFFFFF  # SBR_NO_GROUP: an item of no group, never capped
 
 
 def _check(st: int):
@@ -281,6 +282,83 @@ def _above(call, n: int, threshold, max_results, order: str, count_only: bool, b
     ptr[1:] = np.cumsum(counts[:n], dtype=np.uint64)
     ids, scores = above_sort(ptr, ids[: total.value].copy(), scores[: total.value].copy(), order)
     return Above(ptr, ids, scores, order, None if cuts is None else cuts[:n])
+
+
+def capped_default_pool(k: int) -> int:
+    """The pool of a *_capped call that names none: min(1 024, max(64, 4 k)), the library's default."""
+    return min(RECOMMEND_MAX_K, max(64, 4 * int(k)))
+
+
+def _cap_args(k, cap, pool):
+    """The rule keywords of a *_capped call -> (SbrCapArgs, the pool it names); a ValueError, before any call into the library, for
+    cap < 1, k < 1, pool < k or pool > 1 024."""
+    from ._abi import SbrCapArgs
+
+    k, cap = int(k), int(cap)
+    pool = capped_default_pool(k) if pool is None else int(pool)
+    if cap < 1 or cap > 0xFFFFFFFF:
+        raise ValueError(f"cap {cap}: at least 1")
+    if k < 1:
+        raise ValueError(f"k {k}: at least 1")
+    if pool < k:
+        raise ValueError(f"pool {pool} < k {k}")
+    if pool > RECOMMEND_MAX_K:
+        raise ValueError(f"pool {pool} > {RECOMMEND_MAX_K}")
+    ca = SbrCapArgs()
+    ca.cap, ca.pool = cap, pool
+    return ca, pool
+
+
+def capped_keep(ids, groups, cap: int, k: int) -> np.ndarray:
+    """The rule R(L, cap, k) of the *_capped calls on one row: ``ids`` are the row's items in the total order (no padding), ``groups``
+    the u32 group word of every item of the catalogue.  Returns the positions in ``ids`` of the first k kept entries, ascending.  An
+    entry is kept iff its group is NO_GROUP or its ordinal within its group, among the entries before it, is below cap — found
+    with one stable sort by group, no walk."""
+    ids = np.asarray(ids, dtype=np.int64)
+    g = np.asarray(groups, dtype=np.uint32)[ids]
+    n = g.size
+    if n == 0:
+        return np.zeros(0, dtype=np.int64)
+    by = np.argsort(g, kind="stable")
+    gs = g[by]
+    heads = np.flatnonzero(np.concatenate(([True], gs[1:] != gs[:-1])))
+    run0 = np.repeat(heads, np.diff(np.concatenate((heads, [n]))))
+    ordinal = np.empty(n, dtype=np.int64)
+    ordinal[by] = np.arange(n, dtype=np.int64) - run0
+    return np.flatnonzero((g == NO_GROUP) | (ordinal < int(cap)))[: int(k)]
+
+
+def capped_complete(top, items, scores, complete, groups, cap: int, k: int, pool: int, num_items: int, max_results=None):
+    """Finishes the rows a *_capped call returned incomplete, in place, and returns the number of ``top`` calls it made.
+    ``top(rows, n)`` is the matching recommend_top* over those rows of the call only — same exclusions, masks and include_seen,
+    order="score" — an ``Above`` (anything with ``row(i) -> (ids, scores)``).  n starts at 4 pool and grows fourfold per round up to
+    num_items; the rule runs on the host over ``groups``; a row is done when k are kept or its returned row is shorter than n
+    (everything eligible was seen).  The rows of a round go in batches whose rows x n stay within max_results (recommend_top's
+    default).  Both routes carry predict's bits in the same order, so a finished row is what an unbounded pool would have given."""
+    cap_results = ABOVE_MAX_RESULTS if max_results is None else int(max_results)
+    todo = np.flatnonzero(~np.asarray(complete, dtype=bool))
+    calls = 0
+    n = 4 * int(pool)
+    while todo.size:
+        n = min(n, max(int(num_items), 1))
+        per = max(1, cap_results // n)
+        left = []
+        for b0 in range(0, todo.size, per):
+            rows = todo[b0 : b0 + per]
+            res = top(rows, n)
+            calls += 1
+            for i, r in enumerate(rows):
+                ids, sc = res.row(i)
+                kept = capped_keep(ids, groups, cap, k)
+                if kept.size < k and ids.size >= n and n < num_items:
+                    left.append(r)
+                    continue
+                items[r, : kept.size], items[r, kept.size :] = ids[kept], RECOMMEND_NO_ITEM
+                scores[r, : kept.size], scores[r, kept.size :] = sc[kept], -np.inf
+                complete[r] = True
+        todo = np.asarray(left, dtype=np.int64)
+        n *= 4
+    return calls
 
 
 STREAM_ROLES = ("main", "side", "sorter", "copier", "xs")  # the roles SBR_TEST_STREAM_DELAY names, in the counter's order
@@ -686,6 +764,91 @@ class Model:
         out = np.zeros(int(self.hp.num_items), dtype=np.uint32)
         _check(self._L.sbr_model_get_item_tags(self._h, _ptr(out)))
         return out
+
+    def set_item_groups(self, groups):
+        """One u32 group word per item (a series, a seller, a category; ``NO_GROUP`` = never capped), kept on the device for the
+        ``recommend_capped`` calls (sbr_model_set_item_groups); ``None`` clears them.  Serving metadata exactly as the item tags:
+        fit, set_param and load leave them alone, a session store stays usable, and ``save`` does not write them."""
+        if groups is None:
+            _check(self._L.sbr_model_set_item_groups(self._h, None))
+            self._groups = None
+            return
+        g = np.asarray(groups).ravel()
+        if g.size != int(self.hp.num_items):
+            raise ValueError(f"one group word per item ({int(self.hp.num_items)}); got {g.size}")
+        if g.dtype.kind not in "iu" or (g.size and (int(g.min()) < 0 or int(g.max()) > 0xFFFFFFFF)):
+            raise ValueError("groups: whole numbers from 0 to 2^32 - 1 (NO_GROUP)")
+        g = np.ascontiguousarray(g, dtype=np.uint32)
+        _check(self._L.sbr_model_set_item_groups(self._h, _ptr(g)))
+        self._groups = g.copy()
+
+    def item_groups(self) -> np.ndarray:
+        """The group words last set, u32 [num_items] (sbr_model_get_item_groups); raises while the model has none."""
+        out = np.zeros(int(self.hp.num_items), dtype=np.uint32)
+        _check(self._L.sbr_model_get_item_groups(self._h, _ptr(out)))
+        return out
+
+    def _capped_finish(self, top, items, scores, flags, cap, k, pool, exact):
+        """the shared tail of the *_capped methods: flags u8 -> complete bool, the incomplete rows finished when exact"""
+        complete = flags.astype(bool)
+        if exact and not complete.all():
+            groups = getattr(self, "_groups", None)
+            capped_complete(top, items, scores, complete, self.item_groups() if groups is None else groups, cap, k, pool,
+                            int(self.hp.num_items))
+        return items, scores, complete
+
+    def recommend_capped(self, user_ptr, item_ids, k: int, cap: int = 1, pool=None, include_history: bool = False, any_of=None,
+                         none_of=None, exact: bool = True):
+        """Exact top-k with at most ``cap`` items of one item group (``set_item_groups``) per row — "one per series", "two per
+        seller" (sbr_recommend_capped): (items [U, k] u32, scores [U, k] f32, complete [U] bool).  A row is ``recommend``'s order
+        walked from the top, an entry kept while fewer than cap kept entries share its group (NO_GROUP: always), k kept entries
+        in all; eligibility (history, any_of / none_of) is ``recommend``'s, the scores are predict's bits.  The device applies the
+        rule to each row's best ``pool`` (default min(1 024, max(64, 4 k))); a row that neither kept k nor saw everything eligible
+        comes back short with complete False — a prefix of the exact answer.  ``exact=True`` finishes such rows with
+        ``recommend_top`` at a growing n and the rule on the host, so every row is the exact answer and complete is all True;
+        ``exact=False`` returns the library's rows and flags as they are."""
+        ca, pool = _cap_args(k, cap, pool)
+        up = np.ascontiguousarray(user_ptr, dtype=np.uint64)
+        it = np.ascontiguousarray(item_ids, dtype=np.uint32)
+        nu = max(len(up) - 1, 0)
+        masks = _tag_masks(any_of, none_of, nu)
+        items, scores = np.zeros((nu, int(k)), dtype=np.uint32), np.zeros((nu, int(k)), dtype=np.float32)
+        flags_out = np.zeros(max(nu, 1), dtype=np.uint8)
+        flags = RECOMMEND_INCLUDE_HISTORY if include_history else 0
+        _check(self._L.sbr_recommend_capped(self._h, _ptr(up), _ptr(it), nu, int(k), flags, C.byref(ca),
+                                            None if masks is None else _ptr(masks[0]), None if masks is None else _ptr(masks[1]),
+                                            _ptr(items), _ptr(scores), _ptr(flags_out)))
+
+        def top(rows, n):
+            sp = np.zeros(rows.size + 1, dtype=np.uint64)
+            lens = (up[rows + 1] - up[rows]).astype(np.int64)
+            sp[1:] = np.cumsum(lens)
+            si = np.concatenate([it[int(up[r]) : int(up[r + 1])] for r in rows]) if rows.size else np.zeros(0, np.uint32)
+            return self.recommend_top(sp, si, n, include_history=include_history, any_of=None if masks is None else masks[0][rows],
+                                      none_of=None if masks is None else masks[1][rows])
+
+        return self._capped_finish(top, items, scores, flags_out[:nu], int(cap), int(k), pool, exact)
+
+    def recommend_capped_reps(self, reps, k: int, cap: int = 1, pool=None, exclude=None, any_of=None, none_of=None, exact: bool = True):
+        """As recommend_capped, from representations [U, embedding_dim]; exclude: None or one sequence of item ids per user."""
+        ca, pool = _cap_args(k, cap, pool)
+        reps = np.ascontiguousarray(reps, dtype=np.float32).reshape(-1, self.dim)
+        nu = reps.shape[0]
+        masks = _tag_masks(any_of, none_of, nu)
+        items, scores = np.zeros((nu, int(k)), dtype=np.uint32), np.zeros((nu, int(k)), dtype=np.float32)
+        flags_out = np.zeros(max(nu, 1), dtype=np.uint8)
+        ep, ei = _exclusion_csr(exclude, nu)
+        _check(self._L.sbr_recommend_capped_reps(self._h, _ptr(reps), nu, int(k), None if ep is None else _ptr(ep),
+                                                 None if ei is None else _ptr(ei), C.byref(ca),
+                                                 None if masks is None else _ptr(masks[0]), None if masks is None else _ptr(masks[1]),
+                                                 _ptr(items), _ptr(scores), _ptr(flags_out)))
+
+        def top(rows, n):
+            return self.recommend_top_reps(reps[rows], n, exclude=None if exclude is None else [exclude[int(r)] for r in rows],
+                                           any_of=None if masks is None else masks[0][rows],
+                                           none_of=None if masks is None else masks[1][rows])
+
+        return self._capped_finish(top, items, scores, flags_out[:nu], int(cap), int(k), pool, exact)
 
     def global_epoch(self) -> int:
         n = C.c_uint64()
@@ -1408,6 +1571,31 @@ class Sessions:
                                                            None if ep is None else _ptr(ep), None if ei is None else _ptr(ei), flags,
                                                            _ptr(masks[0]), _ptr(masks[1]), _ptr(items), _ptr(scores)))
         return items, scores
+
+    def recommend_capped(self, slots, k: int, cap: int = 1, pool=None, exclude=None, any_of=None, none_of=None,
+                         include_seen: bool = False, exact: bool = True):
+        """``Model.recommend_capped_reps(self.representations(slots), k, ...)`` with the scan reading the store's rows in place and
+        the seen-item memory excluded exactly as in ``recommend`` (sbr_sessions_recommend_capped): (items, scores, complete)."""
+        ca, pool = _cap_args(k, cap, pool)
+        if include_seen and not self._seen:
+            raise ValueError("include_seen: this store has no seen-item memory (sessions(capacity, remember=W))")
+        flags = RECOMMEND_INCLUDE_HISTORY if include_seen else 0
+        sl = self._slots(slots)
+        masks = _tag_masks(any_of, none_of, sl.size)
+        items, scores = np.zeros((sl.size, int(k)), dtype=np.uint32), np.zeros((sl.size, int(k)), dtype=np.float32)
+        flags_out = np.zeros(max(sl.size, 1), dtype=np.uint8)
+        ep, ei = _exclusion_csr(exclude, sl.size)
+        _check(self._L.sbr_sessions_recommend_capped(self._h, _ptr(sl), sl.size, int(k), None if ep is None else _ptr(ep),
+                                                     None if ei is None else _ptr(ei), flags, C.byref(ca),
+                                                     None if masks is None else _ptr(masks[0]), None if masks is None else _ptr(masks[1]),
+                                                     _ptr(items), _ptr(scores), _ptr(flags_out)))
+
+        def top(rows, n):
+            return self.recommend_top(sl[rows], n, exclude=None if exclude is None else [exclude[int(r)] for r in rows],
+                                      any_of=None if masks is None else masks[0][rows],
+                                      none_of=None if masks is None else masks[1][rows], include_seen=include_seen)
+
+        return self.model._capped_finish(top, items, scores, flags_out[: sl.size], int(cap), int(k), pool, exact)
 
     def recommend_sampled(self, slots, k: int, temperature: float = 1.0, seed: int = 0, streams=None, exclude=None, any_of=None,
                           none_of=None, include_seen: bool = False, log_prob: bool = False):

@@ -357,6 +357,33 @@ class _ImplicitSequenceModel:
         """``audience_above_reps(...).counts`` without writing any pair."""
         return self.params.count_audience_above_reps(reps, items, threshold, exclude=exclude)
 
+    def set_item_groups(self, groups):
+        """One u32 group word per item — a series, a seller, a category; ``engine.NO_GROUP`` (0xFFFFFFFF) for an item that is
+        never capped — for ``recommend_capped`` and the session call, kept on the device; ``None`` clears them.  Serving metadata
+        as the tags: ``fit`` leaves them alone and ``save`` does not write them — set them again after ``load``."""
+        self.params.set_item_groups(groups)
+        return self
+
+    def item_groups(self) -> np.ndarray:
+        """The group words last set (u32 [num_items]); raises while the model has none."""
+        return self.params.item_groups()
+
+    def recommend_capped(self, interactions_or_histories, k: int, cap: int = 1, pool=None, exclude_history: bool = True, any_of=None,
+                         none_of=None, exact: bool = True):
+        """``recommend`` under the hard slate rule "at most ``cap`` items of one group" (``set_item_groups``): (items [U, k] u32,
+        scores [U, k] f32, complete [U] bool) — each row is ``recommend``'s order walked from the top, an entry kept while fewer
+        than cap kept entries share its group, k kept in all; exact over the whole catalogue, not a filter of some larger k.  The
+        device applies the rule to each row's best ``pool`` (default min(1 024, max(64, 4 k))); with ``exact=True`` the rows that
+        pool did not settle are finished through ``recommend_top``, and complete is all True.  ``exact=False``: the device's
+        rows as they are, a short row with complete False being a prefix of the exact answer.  Eligibility is ``recommend``'s."""
+        up, it = self._csr(interactions_or_histories)
+        return self.params.recommend_capped(up, it, k, cap=cap, pool=pool, include_history=not exclude_history, any_of=any_of,
+                                            none_of=none_of, exact=exact)
+
+    def recommend_capped_reps(self, reps, k: int, cap: int = 1, pool=None, exclude=None, any_of=None, none_of=None, exact: bool = True):
+        """``recommend_capped`` from representations [U, embedding_dim]; ``exclude``: None or one sequence of item ids per user."""
+        return self.params.recommend_capped_reps(reps, k, cap=cap, pool=pool, exclude=exclude, any_of=any_of, none_of=none_of, exact=exact)
+
     def recommend_top(self, interactions_or_histories, n, exclude_history: bool = True, any_of=None, none_of=None, max_results=None,
                       order: str = "score"):
         """``recommend`` with a budget in place of k: each user's exact best ``n`` eligible items (a scalar or one per user, any
