@@ -1028,6 +1028,21 @@ sbr_status sbr_selftest_sort(const uint32_t* rows, uint64_t n, uint32_t row_bits
 sbr_status sbr_test_delays_queued(sbr_model* m, uint64_t out[5]);
 sbr_status sbr_selftest_stream_delay(uint32_t delay_us, int32_t with_join, float* out);
 
+/* Poisoned-scratch test hook (tests/test_poisoned_scratch_gpu.py).  The engine's scratch comes from three places: a
+ * process-wide cache of device blocks and of pinned host blocks, which hands blocks of finished calls out again with their old
+ * content, and each model's serving arena, which every serving call carves anew out of what the previous call left there.  The
+ * environment variable
+ *     SBR_TEST_POISON=<byte>     1..255; unset or 0: off
+ * read each time memory is handed out, fills every block the cache hands out (the whole block as stored, hit or fresh) and the
+ * part of the arena a carve uses with that byte first.  Code that writes what it reads computes the same bits; code that relies
+ * on zeros or on leftovers does not.  The pages of a partitioned table are parameters, not scratch, and are left alone.
+ * sbr_selftest_scratch: the method's own check — a block of the cache (kind 0 device, 1 pinned host) as handed out, copied to
+ * out_host[0, bytes); the block is zeroed and given back; the same size taken again, the cache hit, copied to
+ * out_host[bytes, 2 bytes).  sbr_selftest_arena: the same with two carves of `bytes` of m's serving arena.  With the hook set
+ * every byte of both copies is the pattern. */
+sbr_status sbr_selftest_scratch(uint32_t kind, uint64_t bytes, void* out_host);
+sbr_status sbr_selftest_arena(sbr_model* m, uint64_t bytes, void* out_host);
+
 #ifdef __cplusplus
 }
 #endif

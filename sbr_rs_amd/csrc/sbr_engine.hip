@@ -50,6 +50,18 @@ namespace {
         if (_s != SBR_OK) return _s;     \
     } while (0)
 
+/* The poisoned-scratch test hook: SBR_TEST_POISON=<byte 1..255>, read each time memory is handed out.  Every
+ * block of ScratchCache::get (device and pinned host, hit or fresh) and the part of the serving arena a carve uses are filled
+ * with that byte first, so a kernel that relies on zeros, or on what the last call left, loses bit-parity with the oracle
+ * (tests/test_poisoned_scratch_gpu.py).  0 = off (unset, 0 or malformed): one getenv, nothing else. */
+int test_poison_byte() {
+    const char* e = std::getenv("SBR_TEST_POISON");
+    if (!e || !*e) return 0;
+    char* after = nullptr;
+    const unsigned long v = std::strtoul(e, &after, 0);
+    return (*after == 0 && v >= 1 && v <= 255) ? (int)v : 0;
+}
+
 /* Scratch of a fit call recycled across calls.  The reference's own bench re-fits one model in a loop (benches/benchmark.rs:40-42:
  * 10 000 interactions, three epochs per call): ~40 hipMalloc + 10 hipHostMalloc at sbr_fit_begin and as many frees at the end
  * cost 4-18 ms per call there — more than the call's kernels.  Blocks up to 64 MiB go back to this process-wide cache (768 MiB at
@@ -65,6 +77,22 @@ struct ScratchCache {
     size_t cached[2] = {0, 0}; /* device, pinned host */
     static bool enabled() { return true; }
     hipError_t get(void** out, size_t bytes, bool host) {
+        size_t stored = 0;
+        const hipError_t e = get_block(out, bytes, host, &stored);
+        if (e != hipSuccess) return e;
+        if (const int poison = test_poison_byte()) {
+            if (host) {
+                std::memset(*out, poison, stored);
+            } else { /* the model's streams are non-blocking: a null-stream memset is ordered against nothing without the sync */
+                hipError_t pe = hipMemset(*out, poison, stored);
+                if (pe == hipSuccess) pe = hipDeviceSynchronize();
+                if (pe != hipSuccess) { put(*out, host); *out = nullptr; return pe; }
+            }
+        }
+        return hipSuccess;
+    }
+    /* *stored = the size of the block handed out: a cache hit may be up to twice the request */
+    hipError_t get_block(void** out, size_t bytes, bool host, size_t* stored) {
         *out = nullptr;
         bytes = (bytes + 255) & ~(size_t)255;
         int device = 0;
@@ -84,6 +112,7 @@ struct ScratchCache {
                 cached[host] -= b.bytes;
                 live[b.p] = b;
                 *out = b.p;
+                *stored = b.bytes;
                 return hipSuccess;
             }
         }
@@ -96,10 +125,12 @@ struct ScratchCache {
             }
             if (e == hipErrorOutOfMemory && have_cached) { /* give the cache back and try once more */
                 trim();
+                *stored = bytes;
                 return host ? hipHostMalloc(out, bytes, hipHostMallocDefault) : hipMalloc(out, bytes);
             }
             return e;
         }
+        *stored = bytes;
         if (enabled() && bytes <= kMaxBlock) {
             std::lock_guard<std::mutex> g(mu);
             live[*out] = Blk{*out, bytes, device, host};
@@ -3498,7 +3529,12 @@ sbr_status carve_arena(sbr_model* m, const Carve& carve) {
     ar.measure();
     carve(ar);
     HIPCHK(hipStreamSynchronize(m->stream)); /* nothing of an earlier call may still read the arena */
-    SBRCHK(ar.reserve(ar.used));
+    const size_t need = ar.used;
+    SBRCHK(ar.reserve(need));
+    if (const int poison = test_poison_byte()) { /* what this carve uses, not cap: an earlier call may have grown it to gigabytes */
+        HIPCHK(hipMemsetAsync(ar.base, poison, need, m->stream));
+        HIPCHK(hipStreamSynchronize(m->stream)); /* a caller may fill its buffers with blocking copies, which no stream orders */
+    }
     carve(ar);
     return ar.overrun ? SBR_ERR_OUT_OF_MEMORY : SBR_OK;
 }
@@ -3510,7 +3546,7 @@ struct ForwardBufs {
     WorkBuffers wb;
     void carve(DeviceArena& ar, const sbr_model* m, const Packed& pk) {
         const size_t R = (size_t)pk.R, d = (size_t)m->d;
-        dp.in_idx = ar.take<uint32_t>(R); dp.out_idx = ar.take<uint32_t>(R); dp.ctr = ar.take<uint32_t>(R);
+        dp.in_idx = ar.take<uint32_t>(R); /* no out_idx / ctr: only the score kernels of a training step read them */
         dp.prev_row = ar.take<int>(R); dp.off = ar.take<int>(pk.off.size()); dp.steps = ar.take<int>((size_t)pk.B);
         H = ar.take<float>(R * d);
         if (m->ng) {
@@ -6145,6 +6181,47 @@ sbr_status sbr_selftest_stream_delay(uint32_t delay_us, int32_t with_join, float
     if (b) hipStreamDestroy(b);
     dfree(cell);
     return st;
+}
+
+/* What the poisoned-scratch hook can see (tests/test_poisoned_scratch_gpu.py): a block of the scratch cache (kind 0 device, 1
+ * pinned host) as it is handed out, copied to out_host[0, bytes); the block is then zeroed and given back, and the same size is
+ * taken again — the cache hit — and copied to out_host[bytes, 2 bytes).  With SBR_TEST_POISON set every byte of both is the pattern. */
+sbr_status sbr_selftest_scratch(uint32_t kind, uint64_t bytes, void* out_host) {
+    int nd = 0;
+    if (hipGetDeviceCount(&nd) != hipSuccess || nd == 0) return SBR_ERR_NO_DEVICE;
+    if (kind > 1 || bytes == 0 || !out_host) return SBR_ERR_INVALID_ARGUMENT;
+    const bool host = kind == 1;
+    for (int round = 0; round < 2; ++round) {
+        uint8_t* p = nullptr;
+        HIPCHK(scratch_cache().get(reinterpret_cast<void**>(&p), bytes, host));
+        uint8_t* dst = static_cast<uint8_t*>(out_host) + (size_t)round * bytes;
+        sbr_status st = SBR_OK;
+        if (host) {
+            std::memcpy(dst, p, bytes);
+            std::memset(p, 0, bytes);
+        } else if (hipMemcpy(dst, p, bytes, hipMemcpyDeviceToHost) != hipSuccess || hipMemset(p, 0, bytes) != hipSuccess ||
+                   hipDeviceSynchronize() != hipSuccess) {
+            st = SBR_ERR_HIP;
+        }
+        scratch_cache().put(p, host);
+        SBRCHK(st);
+    }
+    return SBR_OK;
+}
+
+/* The same for the serving arena: carve `bytes`, copy out, zero, carve the same size again (no growth), copy out. */
+sbr_status sbr_selftest_arena(sbr_model* m, uint64_t bytes, void* out_host) {
+    if (!m || bytes == 0 || !out_host) return SBR_ERR_INVALID_ARGUMENT;
+    std::lock_guard<std::mutex> lock(m->mu);
+    SBRCHK(enter_reader(m));
+    for (int round = 0; round < 2; ++round) {
+        uint8_t* p = nullptr;
+        SBRCHK(carve_arena(m, [&](DeviceArena& ar) { p = ar.take<uint8_t>(bytes); }));
+        HIPCHK(hipMemcpyAsync(static_cast<uint8_t*>(out_host) + (size_t)round * bytes, p, bytes, hipMemcpyDeviceToHost, m->stream));
+        HIPCHK(hipMemsetAsync(p, 0, bytes, m->stream));
+        HIPCHK(hipStreamSynchronize(m->stream));
+    }
+    return SBR_OK;
 }
 
 sbr_status sbr_set_device(int32_t ordinal) {

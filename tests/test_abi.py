@@ -63,6 +63,8 @@ def test_no_device_fails_loudly():
     assert _lib.load().sbr_selftest_math(x.ctypes.data_as(C.c_void_p), 4, None, None, None) == Status.NO_DEVICE
     out = C.c_float(-1.0)
     assert _lib.load().sbr_selftest_stream_delay(100, 1, C.byref(out)) == Status.NO_DEVICE and out.value == -1.0
+    buf = np.full(512, 7, np.uint8)
+    assert _lib.load().sbr_selftest_scratch(0, 256, buf.ctypes.data_as(C.c_void_p)) == Status.NO_DEVICE and (buf == 7).all()
 
 
 def test_python_surface_mirrors_reference_names():
