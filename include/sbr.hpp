@@ -492,6 +492,12 @@ struct Recommendations {
     std::vector<std::uint32_t> items;
     std::vector<float> scores;
 };
+/// The per-position ranks of ImplicitSequenceModel::sequence_ranks, CSR: user u's are ranks[ptr[u] .. ptr[u + 1]), positions ascending.
+struct SequenceRanks {
+    std::vector<std::uint64_t> ptr;
+    std::vector<std::uint32_t> ranks;
+    std::size_t num_users() const { return ptr.empty() ? 0 : ptr.size() - 1; }
+};
 /// The per-user tag filter of the *_filtered top-k calls (named methods, so that no braced argument of a plain form changes its
 /// meaning), against the model's item tags (ImplicitSequenceModel::set_item_tags): user u may see
 /// item i iff (tags[i] & none_of[u]) == 0 && (any_of[u] == 0 || (tags[i] & any_of[u]) != 0).  Each vector is empty (all zeros), holds
@@ -2130,6 +2136,30 @@ class ImplicitSequenceModel : public OnlineRankingModel<ImplicitUser> {
         return R::Ok(std::move(ranks));
     }
 
+    /// Exact next-item rank at every position of every sequence from one forward pass per sequence (sbr_sequence_ranks): with
+    /// W = min(n, max_sequence_length + 1) and w the last W items of user u, position p = 1 .. W - 1 ranks w[p] against the state
+    /// after w[0 .. p), the distinct items of that prefix masked to f32::MIN unless `mask_history` is false — the number
+    /// rank_targets(history = w[0 .. p), targets = { w[p] }) gives.  `last` (0 = all) keeps only the last `last` positions of each
+    /// window.  Row u of the result holds its positions ascending and is empty for n < 2.  Err(InvalidPredictionValue) on a
+    /// non-finite score.
+    Result<SequenceRanks, PredictionError> sequence_ranks(const data::CompressedInteractions& test, bool mask_history = true,
+                                                          std::size_t last = 0) const {
+        using R = Result<SequenceRanks, PredictionError>;
+        if (last > 0xFFFFFFFFull) throw EngineError(SBR_ERR_INVALID_ARGUMENT, "sequence_ranks: last does not fit 32 bits");
+        const std::uint32_t flags = mask_history ? 0u : SBR_RANK_INCLUDE_HISTORY;
+        SequenceRanks r;
+        r.ptr.assign(test.num_users() + 1, 0);
+        check(sbr_sequence_ranks(replicas_->primary(), test.user_pointers().data(), test.item_ids().data(), (std::uint64_t)test.num_users(),
+                                 flags, (std::uint32_t)last, r.ptr.data(), nullptr), "sbr_sequence_ranks");  // sizing: no device work
+        r.ranks.assign(r.ptr.back() + 1, 0);
+        const sbr_status st = sbr_sequence_ranks(replicas_->primary(), test.user_pointers().data(), test.item_ids().data(),
+                                                 (std::uint64_t)test.num_users(), flags, (std::uint32_t)last, r.ptr.data(), r.ranks.data());
+        if (st == SBR_ERR_INVALID_PREDICTION) return R::Err(PredictionError::InvalidPredictionValue);
+        check(st, "sbr_sequence_ranks");
+        r.ranks.resize(r.ptr.back());
+        return R::Ok(std::move(r));
+    }
+
     /// A session store of `capacity` slots on the primary replica: device-resident user states advanced one appended item at a
     /// time (see Sessions).  Destroy it before this model.
     Sessions sessions(std::size_t capacity) const { return Sessions(replicas_->primary(), capacity, replicas_->hparams().embedding_dim); }
@@ -2581,6 +2611,105 @@ inline Result<RankingMetrics, PredictionError> ranking_metrics(const models::det
     for (std::size_t& u : out.users) u = users[u];
     if (out_ranks) *out_ranks = ranks.unwrap();
     return Result<RankingMetrics, PredictionError>::Ok(std::move(out));
+}
+
+/// One set of next-item metrics over some positions (each has ONE relevant item, of rank r): the means of 1 / r, r, [r <= k] and
+/// (r <= k ? 1 / log2(1 + r) : 0), the last two one per k.  NaN where `count` is 0.
+struct PositionMetrics {
+    std::size_t count = 0;
+    double mrr = 0.0, mean_rank = 0.0;
+    std::vector<double> hit_rate, ndcg;
+};
+
+/// The result of sequence_metrics: `micro` over all positions, `macro` the mean of the per-user means (users without positions
+/// left out; its count is the number of such users), and `by_history_length`[p] over the positions whose history has p items,
+/// p = 1 .. max_sequence_length (entry 0 unused) — the j-th entry of a row counts as history length j + 1, which holds for a full
+/// call (last = 0) on sequences of at most max_sequence_length + 1 items.
+struct SequenceMetrics {
+    std::vector<std::size_t> ks;
+    std::size_t num_positions = 0;
+    PositionMetrics micro, macro;
+    std::vector<PositionMetrics> by_history_length;
+};
+
+/// sequence_metrics from the ranks (ImplicitSequenceModel::sequence_ranks).  Host only, float64.
+inline SequenceMetrics sequence_metrics_from_ranks(const models::SequenceRanks& r, const std::vector<std::size_t>& ks,
+                                                   std::size_t max_sequence_length) {
+    for (std::size_t k : ks)
+        if (k < 1) throw std::invalid_argument("sequence_metrics: every k must be >= 1");
+    const std::size_t nk = ks.size();
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    struct Sums {
+        std::size_t n = 0;
+        double rr = 0.0, rank = 0.0;
+        std::vector<double> hit, dcg;
+    };
+    auto fresh = [&] { Sums s; s.hit.assign(nk, 0.0); s.dcg.assign(nk, 0.0); return s; };
+    auto add = [&](Sums& s, std::uint32_t rank) {
+        const double x = (double)rank;
+        s.n += 1; s.rr += 1.0 / x; s.rank += x;
+        for (std::size_t j = 0; j < nk; ++j)
+            if (x <= (double)ks[j]) { s.hit[j] += 1.0; s.dcg[j] += 1.0 / std::log2(1.0 + x); }
+    };
+    auto means = [&](const Sums& s) {
+        PositionMetrics m;
+        m.count = s.n;
+        const double n = (double)s.n;
+        m.mrr = s.n ? s.rr / n : nan;
+        m.mean_rank = s.n ? s.rank / n : nan;
+        for (std::size_t j = 0; j < nk; ++j) {
+            m.hit_rate.push_back(s.n ? s.hit[j] / n : nan);
+            m.ndcg.push_back(s.n ? s.dcg[j] / n : nan);
+        }
+        return m;
+    };
+    SequenceMetrics out;
+    out.ks = ks;
+    Sums all = fresh();
+    std::vector<Sums> by(max_sequence_length + 1, fresh());
+    std::size_t users = 0;
+    double mrr = 0.0, mean_rank = 0.0;
+    std::vector<double> hit(nk, 0.0), ndcg(nk, 0.0);
+    for (std::size_t u = 0; u < r.num_users(); ++u) {
+        if (r.ptr[u + 1] == r.ptr[u]) continue;
+        if (r.ptr[u + 1] - r.ptr[u] > max_sequence_length) throw std::invalid_argument("sequence_metrics: a row has more positions than max_sequence_length");
+        Sums mine = fresh();
+        for (std::uint64_t e = r.ptr[u]; e < r.ptr[u + 1]; ++e) {
+            if (r.ranks[e] < 1) throw std::invalid_argument("sequence_metrics: ranks start at 1");
+            add(all, r.ranks[e]);
+            add(mine, r.ranks[e]);
+            add(by[(std::size_t)(e - r.ptr[u]) + 1], r.ranks[e]);
+        }
+        const PositionMetrics m = means(mine);
+        users += 1; mrr += m.mrr; mean_rank += m.mean_rank;
+        for (std::size_t j = 0; j < nk; ++j) { hit[j] += m.hit_rate[j]; ndcg[j] += m.ndcg[j]; }
+    }
+    out.num_positions = all.n;
+    out.micro = means(all);
+    out.macro.count = users;
+    out.macro.mrr = users ? mrr / (double)users : nan;
+    out.macro.mean_rank = users ? mean_rank / (double)users : nan;
+    for (std::size_t j = 0; j < nk; ++j) {
+        out.macro.hit_rate.push_back(users ? hit[j] / (double)users : nan);
+        out.macro.ndcg.push_back(users ? ndcg[j] / (double)users : nan);
+    }
+    for (const Sums& s : by) out.by_history_length.push_back(means(s));
+    return out;
+}
+
+/// MRR, mean rank, hit-rate@k and NDCG@k of next-item prediction at EVERY position of every test sequence — how good the model is
+/// after 1, 5 or 50 events — from one forward pass per sequence and one scan row per position
+/// (ImplicitSequenceModel::sequence_ranks).  `last` (0 = all) keeps each window's last positions only (by_history_length is then
+/// indexed from the first kept position); `out_ranks` (optional) receives the ranks.
+inline Result<SequenceMetrics, PredictionError> sequence_metrics(const models::detail::ImplicitSequenceModel& model,
+                                                                 const data::CompressedInteractions& test,
+                                                                 const std::vector<std::size_t>& ks = {10, 100}, bool mask_history = true,
+                                                                 std::size_t last = 0, models::SequenceRanks* out_ranks = nullptr) {
+    auto ranks = model.sequence_ranks(test, mask_history, last);
+    if (ranks.is_err()) return Result<SequenceMetrics, PredictionError>::Err(ranks.unwrap_err());
+    SequenceMetrics out = sequence_metrics_from_ranks(ranks.unwrap(), ks, (std::size_t)model.hparams().max_sequence_length);
+    if (out_ranks) *out_ranks = ranks.unwrap();
+    return Result<SequenceMetrics, PredictionError>::Ok(std::move(out));
 }
 
 } // namespace evaluation

@@ -573,6 +573,29 @@ sbr_status sbr_rank_targets_reps(sbr_model* m, const float* reps, uint64_t num_u
                                  const uint64_t* excl_ptr, const uint32_t* excl_items,
                                  const uint64_t* target_ptr, const uint32_t* target_items, uint32_t* out_ranks);
 
+/* Exact next-item rank at EVERY position of a sequence from one forward pass per sequence: the teacher-forced evaluation of a
+ * sequence recommender (no counterpart in the reference crate, whose mrr_score ranks the last item alone, evaluation.rs:12-48).
+ *
+ * WINDOW.  User u's items are x_0 .. x_{n-1} = item_ids[user_ptr[u] .. user_ptr[u + 1]).  With W = min(n, max_sequence_length + 1)
+ * the window is the last W of them, w_0 .. w_{W-1}.  Items before the window are neither in any state nor in any mask: a sliding
+ * window would need a forward pass per position, and callers split longer sequences themselves.
+ * POSITIONS.  p = 1 .. W - 1: the history is w_0 .. w_{p-1} and the target w_p.  rep_p has the bits of
+ * sbr_user_representation(w_0 .. w_{p-1}); a history of at most max_sequence_length items is never truncated.
+ * RANK.  rank_p = #{ i in [0, num_items) : m(i) >= m(w_p) } with m(i) = f32::MIN if i is among the distinct items of
+ * w_0 .. w_{p-1}, else b[i] + chain dot(rep_p, E[i]) with sbr_predict's bits; with SBR_RANK_INCLUDE_HISTORY in flags nothing is
+ * masked.  So the target counts itself, ties count against it, a target that occurs in its own prefix has rank num_items, and a
+ * prefix item that repeats is masked once.  rank_p equals sbr_rank_targets(history = w[0 .. p), targets = { w_p }), and for
+ * n <= max_sequence_length + 1 the last entry of a row equals sbr_mrr_score's rank of that user.
+ * OUTPUT.  CSR: out_ptr u64 [num_users + 1] from 0, out_ranks u32 [out_ptr[num_users]]; row u holds its positions ascending; a user
+ * with n < 2 has an empty row.  last_positions (0 = all) keeps only the last min(last_positions, W - 1) positions of each window —
+ * the scan costs one catalogue row per position, and this is the caller's cost control; the kept ranks are the numbers of the full
+ * call.  out_ranks NULL: out_ptr alone is filled (sizing), with no device work.
+ * ERRORS.  SBR_ERR_INVALID_PREDICTION if any score of a scanned row is non-finite; SBR_ERR_INVALID_ARGUMENT for decreasing
+ * pointers, ids >= num_items, unknown flags, or while a fit plan is open on the model; the outputs are then untouched.
+ * Both model families, every embedding_dim from 1 to 256.  Deterministic (integer counts). */
+sbr_status sbr_sequence_ranks(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users, uint32_t flags,
+                              uint32_t last_positions, uint64_t* out_ptr, uint32_t* out_ranks);
+
 /* SESSIONS — device-resident user states advanced one event at a time (no counterpart in the reference crate, whose
  * user_representation walks the whole history on every call, sequence_model.rs:182-211).  A store belongs to one model and has
  * `capacity` slots; a slot holds len, the number of items appended since its last reset, and the recurrent state after those items:

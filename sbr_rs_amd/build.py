@@ -216,6 +216,15 @@ def build_capped_tests(force: bool = False, verbose: bool = True) -> str:
     return _build_cpp_program(CAPPED_SRC, CAPPED_BIN, force, verbose)
 
 
+SEQUENCE_RANKS_SRC = os.path.join(REPO, "tests", "cpp", "sequence_ranks_tests.cpp")
+SEQUENCE_RANKS_BIN = os.path.join(REPO, "tests", "cpp", "_build", "sequence_ranks_tests")
+
+
+def build_sequence_ranks_tests(force: bool = False, verbose: bool = True) -> str:
+    """g++ build of the C++ host layer's sequence_ranks / sequence_metrics test program."""
+    return _build_cpp_program(SEQUENCE_RANKS_SRC, SEQUENCE_RANKS_BIN, force, verbose)
+
+
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv))
     print(build_facade_tests(force="--force" in sys.argv))
@@ -234,3 +243,4 @@ if __name__ == "__main__":
     print(build_above_tests(force="--force" in sys.argv))
     print(build_top_tests(force="--force" in sys.argv))
     print(build_capped_tests(force="--force" in sys.argv))
+    print(build_sequence_ranks_tests(force="--force" in sys.argv))

@@ -6,7 +6,9 @@
  *   rank_gemm_kernel       : counts S[u][i] >= ts[u] (mrr_score, evaluation.rs:27-43)
  *   rank_history_kernel    : corrects the count for the (unique) history items, which the reference masks to f32::MIN
  *                            (evaluation.rs:30-32)
- *   rank_targets_*_kernel  : rank_targets' exact ranks of many targets per user from one scan: prepare (thresholds, sorted per
+ *   rank_prefix_kernel     : sequence_ranks' correction of the same count for a scan row (sequence, step t) whose mask is the
+ *                            sequence's own first t + 1 input items, read from the forward pass's packed rows
+ *   rank_targets_*_kernel : rank_targets' exact ranks of many targets per user from one scan: prepare (thresholds, sorted per
  *                            scan-user), gemm (each score counted into the bucket between two thresholds, in LDS), finish (prefix
  *                            sums and the mask correction)
  *   topk_gemm_kernel       : per user and item range, a running sorted list of the k best (score desc, id asc) in global scratch
@@ -310,6 +312,43 @@ __global__ __launch_bounds__(64) void rank_history_kernel(ModelView m, const flo
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
     if (threadIdx.x == 0 && cnt) atomicAdd(&ranks[u], (uint32_t)cnt); /* two's complement: adds a negative delta */
+}
+
+/* sequence_ranks' mask correction.  A scan row is (sequence b, step t) of the forward pass's packed layout: its state is the one
+ * after the input items x_0 .. x_t, its mask the distinct items among them, its target x_{t + 1}.  One wave per scan row, lane l the
+ * inputs j = l, l + 64, ... <= t: where x_j is a first occurrence (first_occ, by packed row as in_idx: the flag does not depend on t,
+ * so the host makes it once per sequence and a repeated item is masked once) the item is scored with rank_history_kernel's statement
+ * and corrected by its two lines.  The items come from the packed in_idx rows off[j] + b that the forward pass uploaded: nothing of
+ * size sum(t) exists.  The row's count belongs to this wave alone and the scan's atomics have finished in stream order, so it is added
+ * with a plain read and write.
+ *
+ * The item rows of a sequence are read again by each of its steps' waves.  They are not staged in LDS: a sequence's steps are
+ * neighbouring waves of neighbouring workgroups, the rows of one sequence are at most T x d floats (128 KB at T = 128, d = 256, 32 KB
+ * at T = 64, d = 128) and stay in L2 between them, and the whole pass is about T / 2 dots per scan row against the scan's num_items —
+ * 32 against 1e6 at T = 64.  A workgroup per sequence with the rows in LDS would need the t tiling above 64 KB and a launch shaped by
+ * sequences where `last` keeps a few rows of each; neither pays for itself at that share. */
+template <int D>
+__global__ __launch_bounds__(256) void rank_prefix_kernel(ModelView m, const float* reps, const int* rep_row, const float* ts,
+                                                           const uint2* unit_bt, uint32_t num_units, const int* off,
+                                                           const uint32_t* in_idx, const uint32_t* first_occ, uint32_t* ranks) {
+    const uint32_t unit = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (unit >= num_units) return; /* the whole wave */
+    const uint32_t lane = threadIdx.x & 63;
+    const uint2 bt = unit_bt[unit]; /* (b, t) */
+    const float* h = reps + (size_t)rep_row[unit] * D;
+    const float t = ts[unit];
+    int cnt = 0;
+    for (uint32_t j = lane; j <= bt.y; j += 64) {
+        const uint32_t r = (uint32_t)off[j] + bt.x;
+        if (!first_occ[r]) continue;
+        const uint32_t i = in_idx[r];
+        const float s = m.b[i] + chain_dot<D>(h, m.E + (size_t)i * D);
+        if (s >= t) --cnt;               /* it was counted by the GEMM pass ...          */
+        if (SBR_F32_MIN >= t) ++cnt;     /* ... but the masked value only counts against MIN */
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+    if (lane == 0 && cnt) ranks[unit] += (uint32_t)cnt; /* two's complement: adds a negative delta */
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2131,6 +2170,23 @@ int launch_rank(const ModelView& m, const float* reps, const int* rep_row, uint3
         hipLaunchKernelGGL((rank_history_kernel<DD>), dim3(num_users), dim3(64), 0, s, m, reps, rep_row, ts_scratch, hist_ptr, hist_items, ranks);
     });
     return 1; /* the ledger's count of mrr_score's scan (sbr_kernels.h) */
+}
+
+int launch_sequence_ranks(const ModelView& m, const float* reps, const int* rep_row, uint32_t num_units, const uint32_t* test_item,
+                          const uint32_t* test_in_prefix, const uint2* unit_bt, const int* off, const uint32_t* in_idx,
+                          const uint32_t* first_occ, float* ts_scratch, uint32_t* ranks, uint32_t* nonfinite_flag, hipStream_t s) {
+    if (num_units == 0) return 0;
+    // the scan is launch_rank's: the same user tiles and item ranges
+    const uint32_t utiles = (num_units + 127) / 128;
+    uint32_t per = 0;
+    const uint32_t groups = split_items(m.num_items, wanted_groups((768u * 6u + utiles - 1) / utiles), UINT32_MAX, 65535u * 32u, &per);
+    DISPATCH_D(m.d, {
+        hipLaunchKernelGGL((rank_test_score_kernel<DD>), dim3((num_units + 255) / 256), dim3(256), 0, s, m, reps, rep_row, num_units, test_item, test_in_prefix, ts_scratch, ranks);
+        hipLaunchKernelGGL((rank_gemm_kernel<DD>), dim3(utiles, groups), dim3(256), 0, s, m, reps, rep_row, num_units, ts_scratch, per, ranks, nonfinite_flag);
+        if (unit_bt)
+            hipLaunchKernelGGL((rank_prefix_kernel<DD>), dim3((num_units + 3) / 4), dim3(256), 0, s, m, reps, rep_row, ts_scratch, unit_bt, num_units, off, in_idx, first_occ, ranks);
+    });
+    return 1; /* one scan, as launch_rank */
 }
 
 uint32_t rank_targets_tmax(int d) {

@@ -3557,11 +3557,21 @@ struct ForwardBufs {
     }
 };
 
+/* The packed layout of a forward pass, for a caller that reads more than the final states: history i is sequence b with
+ * pk.order[b] = i, its state after step t is row pk.off[t] + b of H and its t-th input item in_idx[pk.off[t] + b]; d_off / d_in_idx
+ * are the device copies of pk.off / pk.in_idx in the eval arena, valid as long as H. */
+struct PackedLayout {
+    Packed pk;
+    const int* d_off = nullptr;
+    const uint32_t* d_in_idx = nullptr;
+};
+
 /* Runs the recurrent forward for a batch of histories; the hidden states are left in *H_out — memory of the model's eval arena,
  * valid until the next carve_arena — and rep_row[i] = packed row of the final state of history i.  `carve_epilogue`: what the
- * caller uses from the arena afterwards (the scan kernels' arrays), carved behind the forward pass's in the same allocation. */
+ * caller uses from the arena afterwards (the scan kernels' arrays), carved behind the forward pass's in the same allocation.
+ * `layout` non-null: the packed layout is handed back (sequence_ranks scans every step's state, not the last one's alone). */
 sbr_status forward_histories(sbr_model* m, const std::vector<const uint32_t*>& first, const std::vector<int>& nsteps,
-                             const Carve& carve_epilogue, float** H_out, std::vector<int>* rep_row) {
+                             const Carve& carve_epilogue, float** H_out, std::vector<int>* rep_row, PackedLayout* layout = nullptr) {
     Packed pk;
     pack_sequences(first, nsteps, false, nullptr, (int)m->hp.max_sequence_length, &pk);
     ForwardBufs fb;
@@ -3585,6 +3595,11 @@ sbr_status forward_histories(sbr_model* m, const std::vector<const uint32_t*>& f
     rep_row->assign(first.size(), 0);
     for (int b = 0; b < pk.B; ++b) (*rep_row)[pk.order[b]] = pk.off[pk.steps[b] - 1] + b;
     *H_out = fb.H;
+    if (layout) {
+        layout->d_off = dp.off;
+        layout->d_in_idx = dp.in_idx;
+        layout->pk = std::move(pk);
+    }
     return SBR_OK;
 }
 
@@ -3709,6 +3724,7 @@ struct UserReps {
     std::vector<float> gathered; /* caller's rows of users that are not consecutive, read by an asynchronous copy */
     std::vector<uint32_t> item_rows;  /* item rows: the users' item ids, read by an asynchronous copy into ... */
     uint32_t* d_item_rows = nullptr;  /* ... the arena; the launch fills H from them */
+    PackedLayout* layout = nullptr;   /* non-null (the caller's, histories only): forward_histories' packed layout is left here */
 };
 
 /* Fills *out for `users` of `s`; `carve_epilogue` as forward_histories' (it may read out->b, which is complete by then).  The
@@ -3726,7 +3742,7 @@ sbr_status user_reps(sbr_model* m, const RepSource& s, const std::vector<uint64_
         /* with reps or item rows: the caller's lists, sorted and de-duplicated (their state windows go unused) */
         prepare_users(list, n, T, s.lists, &out->b);
     }
-    if (s.from_histories()) return forward_histories(m, out->b.first, out->b.nsteps, carve_epilogue, &out->H, &out->rep_row);
+    if (s.from_histories()) return forward_histories(m, out->b.first, out->b.nsteps, carve_epilogue, &out->H, &out->rep_row, out->layout);
     if (s.dev_rows) { /* nothing is made or moved: the scan reads the caller's device rows through rep_row */
         SBRCHK(carve_arena(m, carve_epilogue));
         out->H = const_cast<float*>(s.dev_rows);
@@ -3924,6 +3940,132 @@ sbr_status sbr_mrr_score(sbr_model* m, const uint64_t* user_ptr, const uint32_t*
     for (size_t i = 0; i < ranks.size(); ++i) sum += 1.0f / (float)ranks[i];
     *out_mrr = sum / (float)ranks.size();
     if (out_ranks) std::memcpy(out_ranks, ranks.data(), ranks.size() * 4);
+    return SBR_OK;
+}
+
+namespace {
+
+/* device buffers of launch_sequence_ranks over ns scan rows of sequences with nrows packed rows */
+struct SequenceRanksBufs {
+    int* rep;
+    uint32_t *test, *tip, *first, *ranks, *flag;
+    uint2* bt;
+    float* ts;
+    void carve(DeviceArena& ar, size_t ns, size_t nrows) {
+        rep = ar.take<int>(ns);
+        test = ar.take<uint32_t>(ns); tip = ar.take<uint32_t>(ns);
+        bt = ar.take<uint2>(ns);
+        first = ar.take<uint32_t>(nrows);
+        ranks = ar.take<uint32_t>(ns); flag = ar.take<uint32_t>(1);
+        ts = ar.take<float>(ns);
+    }
+};
+
+/* first[j] = 1 where w[j] does not occur in w[0 .. j): a stable sort of the positions by item, O(W log W) */
+void first_occurrences(const uint32_t* w, size_t W, std::vector<uint32_t>* idx, uint32_t* first) {
+    idx->resize(W);
+    for (size_t j = 0; j < W; ++j) (*idx)[j] = (uint32_t)j;
+    std::sort(idx->begin(), idx->end(), [&](uint32_t a, uint32_t b) { return w[a] != w[b] ? w[a] < w[b] : a < b; });
+    for (size_t k = 0; k < W; ++k) first[(*idx)[k]] = k == 0 || w[(*idx)[k]] != w[(*idx)[k - 1]] ? 1u : 0u;
+}
+
+}  // namespace
+
+sbr_status sbr_sequence_ranks(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users, uint32_t flags,
+                              uint32_t last_positions, uint64_t* out_ptr, uint32_t* out_ranks) {
+    if (!m || !user_ptr || !out_ptr || (flags & ~SBR_RANK_INCLUDE_HISTORY)) return SBR_ERR_INVALID_ARGUMENT;
+    std::lock_guard<std::mutex> lock(m->mu);
+    SBRCHK(enter_reader(m));
+    if (m->open_plans) return SBR_ERR_INVALID_ARGUMENT; /* the plan's steps write the parameters this call reads row after row */
+    SBRCHK(check_csr(m, user_ptr, num_users, item_ids, false));
+    const uint64_t T = m->hp.max_sequence_length;
+    const bool mask = !(flags & SBR_RANK_INCLUDE_HISTORY);
+    /* the window of a user with n items is its last W = min(n, T + 1); its positions 1 .. W - 1, of which the last `kept` are scanned */
+    auto window = [&](uint64_t u, uint64_t* W, uint64_t* kept) {
+        const uint64_t n = user_ptr[u + 1] - user_ptr[u];
+        *W = std::min(n, T + 1);
+        *kept = n < 2 ? 0 : *W - 1;
+        if (last_positions) *kept = std::min<uint64_t>(*kept, last_positions);
+    };
+    uint64_t total = 0;
+    for (uint64_t u = 0; u < num_users; ++u) {
+        uint64_t W, kept;
+        window(u, &W, &kept);
+        total += kept;
+    }
+    if (out_ranks) {
+        /* scan units: (user, position), a user's adjacent and ascending — the order of the output rows */
+        std::vector<uint64_t> unit_user;
+        std::vector<uint32_t> unit_pos;
+        unit_user.reserve(total);
+        unit_pos.reserve(total);
+        for (uint64_t u = 0; u < num_users; ++u) {
+            uint64_t W, kept;
+            window(u, &W, &kept);
+            for (uint64_t p = W - kept; p < W; ++p) {
+                unit_user.push_back(u);
+                unit_pos.push_back((uint32_t)p);
+            }
+        }
+        std::vector<uint32_t> ranks(total, 0);
+        /* the forward pass runs over the window's first W - 1 items: all but the last item, of which the last T (as mrr_score) */
+        const RepSource s = RepSource::of_histories(user_ptr, item_ids, 1, false);
+        std::vector<uint32_t> order;
+        for (Chunk ch; next_chunk(unit_user, eval_units_cap, s, T, &ch);) {
+            const size_t ns = ch.c1 - ch.c0, nlu = ch.users.size();
+            PackedLayout lay;
+            UserReps ur;
+            ur.layout = &lay;
+            SequenceRanksBufs sb;
+            SBRCHK(user_reps(m, s, ch.users, [&](DeviceArena& ar) {
+                size_t nrows = 0;
+                for (int n : ur.b.nsteps) nrows += (size_t)n;
+                sb.carve(ar, ns, nrows);
+            }, &ur));
+            const Packed& pk = lay.pk;
+            /* per sequence, once: the first-occurrence flags of its window; those of the W - 1 inputs go to the device by packed row,
+             * and position p's own flag says whether its target occurs in its prefix */
+            std::vector<int> seq_of(nlu);
+            for (int b = 0; b < pk.B; ++b) seq_of[pk.order[b]] = b;
+            std::vector<uint64_t> wptr(nlu + 1, 0);
+            for (size_t i = 0; i < nlu; ++i) wptr[i + 1] = wptr[i] + (uint64_t)ur.b.nsteps[i] + 1;
+            std::vector<uint32_t> wfirst(wptr[nlu]), first_rows((size_t)pk.R, 0);
+            for (size_t i = 0; i < nlu; ++i) {
+                const size_t W = (size_t)ur.b.nsteps[i] + 1;
+                first_occurrences(ur.b.first[i], W, &order, wfirst.data() + wptr[i]);
+                for (size_t j = 0; j + 1 < W; ++j) first_rows[(size_t)pk.off[j] + seq_of[i]] = wfirst[wptr[i] + j];
+            }
+            std::vector<int> rep(ns);
+            std::vector<uint32_t> test(ns), tip(ns);
+            std::vector<uint2> bt(ns);
+            for (size_t i = 0; i < ns; ++i) {
+                const uint32_t lu = ch.lu[i], p = unit_pos[ch.c0 + i];
+                const int b = seq_of[lu];
+                rep[i] = pk.off[p - 1] + b;
+                bt[i] = make_uint2((uint32_t)b, p - 1);
+                test[i] = ur.b.first[lu][p];
+                tip[i] = mask && !wfirst[wptr[lu] + p] ? 1u : 0u;
+            }
+            HIPCHK(hipMemcpyAsync(sb.rep, rep.data(), ns * 4, hipMemcpyHostToDevice, m->stream));
+            HIPCHK(hipMemcpyAsync(sb.test, test.data(), ns * 4, hipMemcpyHostToDevice, m->stream));
+            HIPCHK(hipMemcpyAsync(sb.tip, tip.data(), ns * 4, hipMemcpyHostToDevice, m->stream));
+            if (mask) {
+                HIPCHK(hipMemcpyAsync(sb.bt, bt.data(), ns * 8, hipMemcpyHostToDevice, m->stream));
+                HIPCHK(hipMemcpyAsync(sb.first, first_rows.data(), first_rows.size() * 4, hipMemcpyHostToDevice, m->stream));
+            }
+            SBRCHK(scan_launch(m, sb.flag, [&] {
+                return sbr::launch_sequence_ranks(m->mv, ur.H, sb.rep, (uint32_t)ns, sb.test, sb.tip, mask ? sb.bt : nullptr, lay.d_off, lay.d_in_idx,
+                                                  sb.first, sb.ts, sb.ranks, sb.flag, m->stream);
+            }, {{ranks.data() + ch.c0, sb.ranks, ns * 4}}));
+        }
+        if (total) std::memcpy(out_ranks, ranks.data(), total * 4);
+    }
+    out_ptr[0] = 0;
+    for (uint64_t u = 0; u < num_users; ++u) {
+        uint64_t W, kept;
+        window(u, &W, &kept);
+        out_ptr[u + 1] = out_ptr[u] + kept;
+    }
     return SBR_OK;
 }
 

@@ -273,6 +273,13 @@ void launch_predict(const ModelView& m, const float* user, const uint32_t* items
 int launch_rank(const ModelView& m, const float* reps, const int* rep_row, uint32_t num_users, const uint32_t* test_item,
                 const uint32_t* test_in_hist, const uint64_t* hist_ptr, const uint32_t* hist_items, float* ts_scratch,
                 uint32_t* ranks, uint32_t* nonfinite_flag, hipStream_t s);
+/* sequence_ranks' launch: launch_rank's threshold and scan kernels over num_units scan rows, unit i = (sequence b, step t) =
+ * unit_bt[i] of the forward pass's packed layout with rep_row[i] = off[t] + b, then rank_prefix_kernel's mask correction over the
+ * first occurrences (first_occ, by packed row) among the sequence's inputs in_idx[off[j] + b], j <= t.  test_in_prefix[i]: the
+ * target occurs among them.  unit_bt NULL: nothing is masked (off, in_idx, first_occ unread). */
+int launch_sequence_ranks(const ModelView& m, const float* reps, const int* rep_row, uint32_t num_units, const uint32_t* test_item,
+                          const uint32_t* test_in_prefix, const uint2* unit_bt, const int* off, const uint32_t* in_idx,
+                          const uint32_t* first_occ, float* ts_scratch, uint32_t* ranks, uint32_t* nonfinite_flag, hipStream_t s);
 /* exact ranks of many targets per user state from one scan (sbr_catalogue.hip).  A scan-user is a representation row rep_row[s]
  * with the targets tgt_items[sptr[s] .. sptr[s + 1]), at most rank_targets_tmax(d) of them and at least one; su_user[s] indexes
  * mask_ptr / mask_items, the sorted de-duplicated lists of items masked to f32::MIN (NULL: none).  ranks [sptr[num_su]] in target

@@ -1418,6 +1418,28 @@ class Model:
                                              None if ei is None else _ptr(ei), _ptr(tp), _ptr(ti), _ptr(ranks)))
         return ranks[: ti.size]
 
+    def sequence_ranks(self, user_ptr, item_ids, include_history: bool = False, last=None):
+        """Exact next-item rank at every position of every sequence from one forward pass per sequence (sbr_sequence_ranks):
+        with W = min(n, max_sequence_length + 1) and w the last W items of user u, position p = 1 .. W - 1 ranks w[p] against
+        the state after w[:p], the distinct items of w[:p] masked to f32::MIN unless include_history — the number
+        rank_targets(history=w[:p], targets=[w[p]]) gives.  ``last`` (None = all) keeps only the last ``last`` positions of
+        each window.  -> (ptr u64 [U + 1], ranks u32 [ptr[U]]); row u holds its positions ascending, empty for n < 2."""
+        up = np.ascontiguousarray(user_ptr, dtype=np.uint64)
+        it = np.ascontiguousarray(item_ids, dtype=np.uint32)
+        if up.ndim != 1 or up.size < 1:
+            raise ValueError("user_ptr holds num_users + 1 offsets")
+        if last is None:
+            last = 0
+        elif not 1 <= int(last) <= 0xFFFFFFFF:
+            raise ValueError("last must be None or in [1, 2**32)")
+        nu = up.size - 1
+        flags = RANK_INCLUDE_HISTORY if include_history else 0
+        ptr = np.zeros(nu + 1, dtype=np.uint64)
+        _check(self._L.sbr_sequence_ranks(self._h, _ptr(up), _ptr(it), nu, flags, int(last), _ptr(ptr), None))  # sizing: no device work
+        ranks = np.zeros(max(int(ptr[nu]), 1), dtype=np.uint32)
+        _check(self._L.sbr_sequence_ranks(self._h, _ptr(up), _ptr(it), nu, flags, int(last), _ptr(ptr), _ptr(ranks)))
+        return ptr, ranks[: int(ptr[nu])]
+
     def sessions(self, capacity: int, remember: int = 0) -> "Sessions":
         """A session store of ``capacity`` slots on this model (sbr_sessions_create): device-resident user states advanced one
         appended item at a time and read in place by recommend / score_candidates.  ``remember`` > 0 (at most 1 024;

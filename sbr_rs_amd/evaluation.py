@@ -123,3 +123,87 @@ def ranking_metrics(model, test: CompressedInteractions, ks=(10, 100), holdout: 
     out = ranking_metrics_from_ranks(ranks, ks)
     out["users"] = users[out["users"]] if len(users) else users
     return out
+
+
+def sequence_ranks(model, test: CompressedInteractions, mask_history: bool = True, last=None):
+    """Exact next-item rank at EVERY position of every test sequence, from one forward pass per sequence and one scan row per
+    position (``sbr_sequence_ranks``) — the teacher-forced evaluation of a sequence recommender.
+
+    With T = max_sequence_length, W = min(n, T + 1) and w the last W items of a user, position p = 1 .. W - 1 ranks w[p]
+    against the state after w[:p]; while ``mask_history`` the distinct items of w[:p] are masked to f32::MIN (a target that
+    occurs in its own prefix has rank num_items).  Each rank is the number ``rank_targets([w[:p]], [[w[p]]])`` gives; items
+    before the window are neither in a state nor in a mask.  ``last`` (None = all) keeps the last ``last`` positions of each
+    window: the same numbers at a fraction of the scan.  -> one uint32 array per user, positions ascending (empty for n < 2)."""
+    params = getattr(model, "params", model)
+    ptr, ranks = params.sequence_ranks(test.user_pointers, test.item_ids, include_history=not mask_history, last=last)
+    ptr = ptr.astype(np.int64)
+    return [ranks[ptr[u]: ptr[u + 1]].copy() for u in range(len(ptr) - 1)]
+
+
+def _position_metrics(ranks, ks):
+    """mrr, mean_rank, hit_rate[k], ndcg[k] as means over the float64 ``ranks`` (one relevant item per rank); NaN when empty."""
+    if ranks.size == 0:
+        nan = float("nan")
+        return {"mrr": nan, "mean_rank": nan, "hit_rate": {k: nan for k in ks}, "ndcg": {k: nan for k in ks}}
+    gain = 1.0 / np.log2(1.0 + ranks)
+    return {"mrr": float(np.mean(1.0 / ranks)), "mean_rank": float(np.mean(ranks)),
+            "hit_rate": {k: float(np.mean(ranks <= k)) for k in ks},
+            "ndcg": {k: float(np.mean(np.where(ranks <= k, gain, 0.0))) for k in ks}}
+
+
+def sequence_metrics_from_ranks(ranks_per_user, ks=(10, 100), max_sequence_length=None):
+    """The metrics of :func:`sequence_metrics` from the per-user rank rows of :func:`sequence_ranks`.  Pure numpy, float64.
+
+    Every position has ONE relevant item, so with r its rank: reciprocal rank 1 / r, hit@k = [r <= k], ndcg@k = 1 / log2(1 + r)
+    if r <= k else 0.  -> dict with ``ks``, ``num_positions``, ``num_users_ranked``; ``mrr`` / ``mean_rank`` / ``hit_rate``
+    ({k: float}) / ``ndcg`` ({k: float}) as the mean over ALL positions; ``macro`` with the same keys as the mean of the per-user
+    means (users without positions left out); ``by_history_length`` with ``count`` (int64) and ``mrr`` / ``mean_rank`` /
+    ``hit_rate`` / ``ndcg`` as arrays indexed by the history length p (index 0 unused; up to ``max_sequence_length``, or the
+    longest row when that is None), NaN where no position has that history length.  The history length of the j-th entry of a
+    row of m entries is taken as p = j + 1 — exact for rows of a full call (``last`` = None) on sequences of at most
+    max_sequence_length + 1 items; with ``last`` the caller passes rows whose first entries were cut and should not read
+    ``by_history_length``.  Means are NaN when there is no position."""
+    ks = tuple(int(k) for k in ks)
+    if any(k < 1 for k in ks):
+        raise ValueError("every k must be >= 1")
+    rows = [np.asarray(r, dtype=np.float64).ravel() for r in ranks_per_user]
+    if any(r.size and r.min() < 1 for r in rows):
+        raise ValueError("ranks start at 1")
+    ranked = [r for r in rows if r.size]
+    allr = np.concatenate(ranked) if ranked else np.zeros(0, dtype=np.float64)
+    out = {"ks": ks, "num_positions": int(allr.size), "num_users_ranked": len(ranked)}
+    out.update(_position_metrics(allr, ks))
+    per_user = [_position_metrics(r, ks) for r in ranked]
+    mean = (lambda v: float(np.mean(np.asarray(v, dtype=np.float64)))) if ranked else (lambda v: float("nan"))
+    out["macro"] = {"mrr": mean([m["mrr"] for m in per_user]), "mean_rank": mean([m["mean_rank"] for m in per_user]),
+                    "hit_rate": {k: mean([m["hit_rate"][k] for m in per_user]) for k in ks},
+                    "ndcg": {k: mean([m["ndcg"][k] for m in per_user]) for k in ks}}
+    longest = max([r.size for r in rows], default=0)
+    L = longest if max_sequence_length is None else int(max_sequence_length)
+    if L < longest:
+        raise ValueError("a row has more positions than max_sequence_length")
+    by = {"count": np.zeros(L + 1, dtype=np.int64), "mrr": np.full(L + 1, np.nan), "mean_rank": np.full(L + 1, np.nan),
+          "hit_rate": {k: np.full(L + 1, np.nan) for k in ks}, "ndcg": {k: np.full(L + 1, np.nan) for k in ks}}
+    for p in range(1, L + 1):
+        at = np.array([r[p - 1] for r in rows if r.size >= p], dtype=np.float64)
+        by["count"][p] = at.size
+        if at.size:
+            pm = _position_metrics(at, ks)
+            by["mrr"][p], by["mean_rank"][p] = pm["mrr"], pm["mean_rank"]
+            for k in ks:
+                by["hit_rate"][k][p], by["ndcg"][k][p] = pm["hit_rate"][k], pm["ndcg"][k]
+    out["by_history_length"] = by
+    return out
+
+
+def sequence_metrics(model, test: CompressedInteractions, ks=(10, 100), mask_history: bool = True, last=None):
+    """MRR, mean rank, hit-rate@k and NDCG@k of next-item prediction at every position of every test sequence
+    (:func:`sequence_ranks`): micro (over positions), ``macro`` (mean of per-user means) and ``by_history_length`` — how good
+    the model is after 1, 5 or 50 events.  With ``last`` the rows hold each window's last positions only and
+    ``by_history_length`` is indexed from the first KEPT position (see :func:`sequence_metrics_from_ranks`).
+    -> the dict of :func:`sequence_metrics_from_ranks`."""
+    params = getattr(model, "params", model)
+    ranks = sequence_ranks(model, test, mask_history=mask_history, last=last)
+    hp = getattr(params, "hp", None)
+    T = int(hp.max_sequence_length) if hp is not None and hasattr(hp, "max_sequence_length") else None
+    return sequence_metrics_from_ranks(ranks, ks, max_sequence_length=T)

@@ -496,6 +496,13 @@ class _ImplicitSequenceModel:
 
         return rank_targets(self, histories, targets, mask_history=mask_history)
 
+    def sequence_ranks(self, test, mask_history: bool = True, last=None):
+        """Exact next-item rank at every position of every test sequence from one forward pass per sequence
+        (``evaluation.sequence_ranks``): one uint32 array per user, positions ascending."""
+        from .evaluation import sequence_ranks
+
+        return sequence_ranks(self, test, mask_history=mask_history, last=last)
+
 
 class ImplicitLSTMModel(_ImplicitSequenceModel):
     """An LSTM-based sequence model for implicit feedback (lstm.rs:386-416)."""
