@@ -592,6 +592,23 @@ struct Partition {
         return out;
     }
 };
+/// What ImplicitSequenceModel::sequence_partition returns (SEQUENCE PARTITION in sbr_hip.h), CSR over the kept positions: user u's
+/// are entries ptr[u] .. ptr[u + 1), positions ascending, of the partition's rows, of `scores` (the targets' plain scores) and of
+/// `masked` (1 where the policy masks the target: its log-probability is -inf).
+struct SequencePartition {
+    std::vector<std::uint64_t> ptr;
+    Partition partition;
+    std::vector<float> scores;
+    std::vector<std::uint8_t> masked;
+    std::size_t num_users() const { return ptr.empty() ? 0 : ptr.size() - 1; }
+    /// log(w / mass) of every position's target, Partition::log_prob of its score; -inf where it is masked or its weight is 0.
+    std::vector<double> log_probs() const {
+        std::vector<double> lp = partition.log_prob(scores);
+        for (std::size_t p = 0; p < lp.size(); ++p)
+            if (masked[p]) lp[p] = -std::numeric_limits<double>::infinity();
+        return lp;
+    }
+};
 /// The order of each row of an Above: by score descending with ties to the lower id (the total order of every top-k call), or by
 /// ascending id (as the library writes it).
 enum class AboveOrder { Score, Id };
@@ -2160,6 +2177,40 @@ class ImplicitSequenceModel : public OnlineRankingModel<ImplicitUser> {
         return R::Ok(std::move(r));
     }
 
+    /// What softmax(score / temperature) needs to price the next item at every position of every sequence, from one forward pass
+    /// per sequence (sbr_sequence_partition): windows, positions, `last` and the rows are sequence_ranks'; per kept position p the
+    /// shift and mass are log_partition's for the explicit history w[0 .. p) bit for bit, `scores` the plain score of w[p] and
+    /// `masked` 1 where the prefix is masked and w[p] occurs in it.  SequencePartition::log_probs gives the log-probabilities.
+    /// Err(InvalidPredictionValue) on a non-finite score.
+    Result<SequencePartition, PredictionError> sequence_partition(const data::CompressedInteractions& test, float temperature = 1.0f,
+                                                                  bool mask_history = true, std::size_t last = 0) const {
+        using R = Result<SequencePartition, PredictionError>;
+        if (last > 0xFFFFFFFFull) throw EngineError(SBR_ERR_INVALID_ARGUMENT, "sequence_partition: last does not fit 32 bits");
+        const std::uint32_t flags = mask_history ? 0u : SBR_RANK_INCLUDE_HISTORY;
+        SequencePartition r;
+        r.ptr.assign(test.num_users() + 1, 0);
+        check(sbr_sequence_partition(replicas_->primary(), test.user_pointers().data(), test.item_ids().data(), (std::uint64_t)test.num_users(),
+                                     temperature, flags, (std::uint32_t)last, r.ptr.data(), nullptr, nullptr, nullptr, nullptr),
+              "sbr_sequence_partition");  // sizing: no device work
+        const std::size_t n = (std::size_t)r.ptr.back();
+        r.partition.temperature = temperature;
+        r.partition.frac_bits = sbr_softmax_frac_bits((std::uint32_t)replicas_->hparams().num_items);
+        r.partition.shift.assign(n + 1, 0.0f);
+        r.partition.mass.assign(n + 1, 0);
+        r.scores.assign(n + 1, 0.0f);
+        r.masked.assign(n + 1, 0);
+        const sbr_status st = sbr_sequence_partition(replicas_->primary(), test.user_pointers().data(), test.item_ids().data(),
+                                                     (std::uint64_t)test.num_users(), temperature, flags, (std::uint32_t)last, r.ptr.data(),
+                                                     r.partition.shift.data(), r.partition.mass.data(), r.scores.data(), r.masked.data());
+        if (st == SBR_ERR_INVALID_PREDICTION) return R::Err(PredictionError::InvalidPredictionValue);
+        check(st, "sbr_sequence_partition");
+        r.partition.shift.resize(n);
+        r.partition.mass.resize(n);
+        r.scores.resize(n);
+        r.masked.resize(n);
+        return R::Ok(std::move(r));
+    }
+
     /// A session store of `capacity` slots on the primary replica: device-resident user states advanced one appended item at a
     /// time (see Sessions).  Destroy it before this model.
     Sessions sessions(std::size_t capacity) const { return Sessions(replicas_->primary(), capacity, replicas_->hparams().embedding_dim); }
@@ -2710,6 +2761,74 @@ inline Result<SequenceMetrics, PredictionError> sequence_metrics(const models::d
     SequenceMetrics out = sequence_metrics_from_ranks(ranks.unwrap(), ks, (std::size_t)model.hparams().max_sequence_length);
     if (out_ranks) *out_ranks = ranks.unwrap();
     return Result<SequenceMetrics, PredictionError>::Ok(std::move(out));
+}
+
+/// The per-position log-probabilities of sequence_log_probs, CSR: user u's are log_probs[ptr[u] .. ptr[u + 1]), positions ascending;
+/// -inf where the policy masks the target.
+struct SequenceLogProbs {
+    std::vector<std::uint64_t> ptr;
+    std::vector<double> log_probs;
+    std::size_t num_users() const { return ptr.empty() ? 0 : ptr.size() - 1; }
+};
+
+/// The exact log-probability of the item that came next at every position of every test sequence under softmax(score / temperature)
+/// over the items the user may see (ImplicitSequenceModel::sequence_partition; `last` 0 = all positions).
+inline Result<SequenceLogProbs, PredictionError> sequence_log_probs(const models::detail::ImplicitSequenceModel& model,
+                                                                    const data::CompressedInteractions& test, float temperature = 1.0f,
+                                                                    bool mask_history = true, std::size_t last = 0) {
+    auto part = model.sequence_partition(test, temperature, mask_history, last);
+    if (part.is_err()) return Result<SequenceLogProbs, PredictionError>::Err(part.unwrap_err());
+    SequenceLogProbs out;
+    out.log_probs = part.unwrap().log_probs();
+    out.ptr = part.unwrap().ptr;
+    return Result<SequenceLogProbs, PredictionError>::Ok(std::move(out));
+}
+
+/// The result of sequence_log_likelihood.  Positions with log-probability -inf (the masked ones) are left out of every mean and
+/// counted in `masked_positions`; `mean_log_prob` / `perplexity` = exp(-mean) over the `positions` counted, `macro_*` the mean of
+/// the per-user means over `macro_users` users; NaN where nothing is counted.
+struct SequenceLogLikelihood {
+    std::size_t positions = 0, masked_positions = 0, macro_users = 0;
+    double mean_log_prob = 0.0, perplexity = 0.0, macro_mean_log_prob = 0.0, macro_perplexity = 0.0;
+};
+
+/// sequence_log_likelihood from the log-probabilities.  Host only, float64.
+inline SequenceLogLikelihood sequence_log_likelihood_from_log_probs(const SequenceLogProbs& lp) {
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    SequenceLogLikelihood out;
+    double sum = 0.0, user_means = 0.0;
+    for (std::size_t u = 0; u < lp.num_users(); ++u) {
+        double mine = 0.0;
+        std::size_t n = 0;
+        for (std::uint64_t e = lp.ptr[u]; e < lp.ptr[u + 1]; ++e) {
+            if (std::isinf(lp.log_probs[e])) { out.masked_positions += 1; continue; }
+            mine += lp.log_probs[e];
+            n += 1;
+        }
+        if (!n) continue;
+        sum += mine;
+        out.positions += n;
+        user_means += mine / (double)n;
+        out.macro_users += 1;
+    }
+    out.mean_log_prob = out.positions ? sum / (double)out.positions : nan;
+    out.perplexity = std::exp(-out.mean_log_prob);
+    out.macro_mean_log_prob = out.macro_users ? user_means / (double)out.macro_users : nan;
+    out.macro_perplexity = std::exp(-out.macro_mean_log_prob);
+    return out;
+}
+
+/// Mean log-likelihood and perplexity of next-item prediction under softmax(score / temperature) at every position of every test
+/// sequence; `out_log_probs` (optional) receives the log-probabilities.
+inline Result<SequenceLogLikelihood, PredictionError> sequence_log_likelihood(const models::detail::ImplicitSequenceModel& model,
+                                                                              const data::CompressedInteractions& test, float temperature = 1.0f,
+                                                                              bool mask_history = true, std::size_t last = 0,
+                                                                              SequenceLogProbs* out_log_probs = nullptr) {
+    auto lp = sequence_log_probs(model, test, temperature, mask_history, last);
+    if (lp.is_err()) return Result<SequenceLogLikelihood, PredictionError>::Err(lp.unwrap_err());
+    SequenceLogLikelihood out = sequence_log_likelihood_from_log_probs(lp.unwrap());
+    if (out_log_probs) *out_log_probs = lp.unwrap();
+    return Result<SequenceLogLikelihood, PredictionError>::Ok(std::move(out));
 }
 
 } // namespace evaluation

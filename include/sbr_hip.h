@@ -596,6 +596,29 @@ sbr_status sbr_rank_targets_reps(sbr_model* m, const float* reps, uint64_t num_u
 sbr_status sbr_sequence_ranks(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users, uint32_t flags,
                               uint32_t last_positions, uint64_t* out_ptr, uint32_t* out_ranks);
 
+/* SEQUENCE PARTITION — what the policy softmax(score / temperature) over the items a user may see (SAMPLING, PARTITION) needs to
+ * price the item that actually came next at EVERY position of a sequence, from one forward pass per sequence.  WINDOW, POSITIONS,
+ * `last_positions`, the CSR rows and their chunking are sbr_sequence_ranks'.  For every kept position p, with the prefix
+ * w_0 .. w_{p-1} and the target w_p:
+ *   out_shift, out_mass   bit for bit and integer for integer what sbr_log_partition returns for the explicit history w[0 .. p) at
+ *                         this temperature: the largest fl(score * inv_t) over the eligible items (a zero is +0.0; -inf and mass 0
+ *                         if nothing is eligible) and the sum of sbr_softmax_weight over them at sbr_softmax_frac_bits(num_items).
+ *                         Eligible: every item not among the distinct items of the prefix, or with SBR_RANK_INCLUDE_HISTORY in
+ *                         flags every item.
+ *   out_scores            the target's plain score, sbr_predict's bits.
+ *   out_masked            1 iff the prefix is masked and w_p occurs in it: the policy never shows that item, its log-probability
+ *                         is -inf (the case in which sbr_sequence_ranks returns num_items); else 0.
+ * log p(w_p) = log(w / mass) with w = sbr_softmax_weights(score, temperature, shift, frac_bits) is the caller's, on the host.
+ * No result depends on the batch, the host's chunks or the scan's split.  All four outputs NULL: out_ptr alone is filled (sizing),
+ * with no device work; otherwise all four are required, [out_ptr[num_users]] each.
+ * ERRORS.  SBR_ERR_INVALID_ARGUMENT for a temperature that is not finite and > 0 (as sbr_log_partition), decreasing pointers,
+ * ids >= num_items, unknown flags, some but not all outputs, or while a fit plan is open on the model; SBR_ERR_INVALID_PREDICTION
+ * if any score of a scanned row is non-finite; the outputs are then untouched.  Both model families, every embedding_dim from 1
+ * to 256.  Deterministic (integer sums). */
+sbr_status sbr_sequence_partition(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users, float temperature,
+                                  uint32_t flags, uint32_t last_positions, uint64_t* out_ptr, float* out_shift, uint64_t* out_mass,
+                                  float* out_scores, uint8_t* out_masked);
+
 /* SESSIONS — device-resident user states advanced one event at a time (no counterpart in the reference crate, whose
  * user_representation walks the whole history on every call, sequence_model.rs:182-211).  A store belongs to one model and has
  * `capacity` slots; a slot holds len, the number of items appended since its last reset, and the recurrent state after those items:

@@ -195,6 +195,7 @@ def load():
         "sbr_recommend_capped_reps": [vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp],
         "sbr_sessions_recommend_capped": [vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint32, vp, vp, vp, vp, vp, vp],
         "sbr_sequence_ranks": [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp],
+        "sbr_sequence_partition": [vp, vp, vp, C.c_uint64, C.c_float, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -263,5 +264,5 @@ DECLARED_SYMBOLS = [
     "sbr_audience_top_reps", "sbr_audience_top", "sbr_sessions_audience_top",
     "sbr_model_set_item_groups", "sbr_model_get_item_groups",
     "sbr_recommend_capped", "sbr_recommend_capped_reps", "sbr_sessions_recommend_capped",
-    "sbr_sequence_ranks",
+    "sbr_sequence_ranks", "sbr_sequence_partition",
 ]

@@ -225,6 +225,15 @@ def build_sequence_ranks_tests(force: bool = False, verbose: bool = True) -> str
     return _build_cpp_program(SEQUENCE_RANKS_SRC, SEQUENCE_RANKS_BIN, force, verbose)
 
 
+SEQUENCE_PARTITION_SRC = os.path.join(REPO, "tests", "cpp", "sequence_partition_tests.cpp")
+SEQUENCE_PARTITION_BIN = os.path.join(REPO, "tests", "cpp", "_build", "sequence_partition_tests")
+
+
+def build_sequence_partition_tests(force: bool = False, verbose: bool = True) -> str:
+    """g++ build of the C++ host layer's sequence_partition / sequence_log_probs test program."""
+    return _build_cpp_program(SEQUENCE_PARTITION_SRC, SEQUENCE_PARTITION_BIN, force, verbose)
+
+
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv))
     print(build_facade_tests(force="--force" in sys.argv))
@@ -244,3 +253,4 @@ if __name__ == "__main__":
     print(build_top_tests(force="--force" in sys.argv))
     print(build_capped_tests(force="--force" in sys.argv))
     print(build_sequence_ranks_tests(force="--force" in sys.argv))
+    print(build_sequence_partition_tests(force="--force" in sys.argv))

@@ -35,7 +35,10 @@
  *   partition_*_kernel     : log_partition's exact fixed-point mass of softmax(score / T) per row: shift (the row's largest scaled
  *                            score, from the top-k scan at k = 1), gemm (the catalogue scan with an epilogue that sums integer
  *                            weights), finish (the exclusion lists' items subtracted exactly)
- *   rep_rows_kernel        : user_representations' rows rep_row[i] of H, embedding_dim floats each, in user order
+ *   sequence_shift_kernel, partition_prefix_kernel : sequence_partition's shift and mass of a scan row (sequence, step t) whose
+ *                            mask is the sequence's own first t + 1 input items: the shift from a small top-k pool, the prefix
+ *                            items' weights subtracted as finish does
+ *   rep_rows_kernel       : user_representations' rows rep_row[i] of H, embedding_dim floats each, in user order
  *
  * The three GEMM kernels share one catalogue scan, S[u][i] = b[i] + sum_k h[u][k] E[i][k] on v_mfma_f32_32x32x2_f32: a workgroup
  * owns 128 users (4 waves x 32, their states held in registers as MFMA A fragments) and a contiguous range of items, whose
@@ -1564,6 +1567,104 @@ __global__ __launch_bounds__(64) void partition_finish_kernel(ModelView m, const
     if (threadIdx.x == 0 && sub) atomicAdd(&mass[u], (unsigned long long)(0ull - sub)); /* two's complement: subtracts */
 }
 
+/* sequence_partition's masked shift.  A scan row is (sequence b, step t) of the forward pass's packed layout, as in
+ * rank_prefix_kernel: it may see every item that is not one of its inputs x_0 .. x_t.  The top-k scan ran over the row WITHOUT an
+ * exclusion list and left its k best (score desc; padding 0xFFFFFFFF / -inf behind them) in pool_items / pool_scores [n][k]; the
+ * first entry that is no prefix item is the row's best eligible item, and shift = fl(its score * inv_t) + 0.0f is
+ * partition_shift_kernel's statement.  Padding before such an entry: the pool held the whole catalogue and all of it is in the
+ * prefix, nothing is eligible, shift = -inf.  All k entries prefix items: the row is flagged in `unresolved` and the host has the
+ * k = 1 scan decide it with the row's exclusion list (launch_sequence_shift_rows); its shift is -inf until then.
+ * One wave per row.  The pool is walked 64 entries at a time, lane l holding entry e0 + l; the prefix items are loaded lane by lane
+ * from the packed in_idx rows off[j] + b, 64 at a time, and each is broadcast to the wave and compared with the lane's entry.  The
+ * lowest lane that holds padding or an eligible entry decides.  mass[row] = 0 ahead of the sum scan's atomics. */
+__global__ __launch_bounds__(256) void sequence_shift_kernel(const uint32_t* pool_items, const float* pool_scores, uint32_t k,
+                                                              const uint2* unit_bt, uint32_t num_units, const int* off,
+                                                              const uint32_t* in_idx, float inv_t, float* shift, unsigned long long* mass,
+                                                              uint8_t* unresolved) {
+    const uint32_t unit = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (unit >= num_units) return; /* the whole wave */
+    const uint32_t lane = threadIdx.x & 63;
+    const uint2 bt = unit_bt[unit]; /* (b, t) */
+    const uint32_t np = bt.y + 1;   /* prefix items */
+    float sh = -INFINITY;
+    uint32_t open = 1; /* no entry has decided the row yet */
+    for (uint32_t e0 = 0; e0 < k && open; e0 += 64) {
+        const uint32_t e = e0 + lane;
+        const uint32_t item = e < k ? pool_items[(size_t)unit * k + e] : TK_NONE;
+        bool hit = false;
+        for (uint32_t j0 = 0; j0 < np; j0 += 64) {
+            const uint32_t j = j0 + lane;
+            const uint32_t x = j < np ? in_idx[(uint32_t)off[j] + bt.x] : TK_NONE;
+            const uint32_t nj = np - j0 < 64u ? np - j0 : 64u;
+            for (uint32_t jj = 0; jj < nj; ++jj) hit |= (uint32_t)__shfl((int)x, (int)jj, 64) == item;
+        }
+        const bool pad = item == TK_NONE; /* also the lanes past k: reached only when no entry before them decided */
+        const unsigned long long decides = __ballot(pad || !hit);
+        if (decides) {
+            const int f = __ffsll((long long)decides) - 1;
+            const uint32_t fe = e0 + (uint32_t)f;
+            const uint32_t fitem = (uint32_t)__shfl((int)item, f, 64);
+            if (fe < k) {
+                open = 0;
+                if (fitem != TK_NONE) sh = __fadd_rn(__fmul_rn(pool_scores[(size_t)unit * k + fe], inv_t), 0.0f);
+            }
+        }
+    }
+    if (lane == 0) {
+        shift[unit] = sh;
+        mass[unit] = 0ull;
+        unresolved[unit] = open ? 1 : 0;
+    }
+}
+
+/* the shifts of the rows the pool left unresolved, out of the k = 1 scan over them alone: row i of that scan is row rows[i] of the
+ * call's launch; partition_shift_kernel's statement */
+__global__ __launch_bounds__(256) void sequence_shift_rows_kernel(const uint32_t* best_item, const float* best_score, uint32_t n, float inv_t,
+                                                                   const uint32_t* rows, float* shift) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    shift[rows[i]] = best_item[i] == TK_NONE ? -INFINITY : __fadd_rn(__fmul_rn(best_score[i], inv_t), 0.0f);
+}
+
+/* sequence_partition's prefix correction, in the shape of rank_prefix_kernel (one wave per scan row (b, t), lane l the inputs
+ * j = l, l + 64, ... <= t, first occurrences only, item rows through L2 for the reason given there): the sum scan added every item
+ * with d <= 0, the row's own prefix items among them, and this is partition_finish_kernel's subtraction of exactly those weights —
+ * sbr_softmax_weight is zero where d > 0, so a prefix item that outscores the shift was never added.  The row's mass belongs to this
+ * wave and the scan's atomics have finished in stream order: a plain read and write.  unit_bt NULL: nothing is masked and nothing
+ * subtracted.  Lane 63, the one with the fewest inputs, scores the row's target with predict's statement. */
+template <int D>
+__global__ __launch_bounds__(256) void partition_prefix_kernel(ModelView m, const float* reps, const int* rep_row, const float* shift,
+                                                                float inv_t, uint32_t frac_bits, const uint2* unit_bt, uint32_t num_units,
+                                                                const int* off, const uint32_t* in_idx, const uint32_t* first_occ,
+                                                                const uint32_t* target, unsigned long long* mass, float* scores) {
+    const uint32_t unit = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (unit >= num_units) return; /* the whole wave */
+    const uint32_t lane = threadIdx.x & 63;
+    const float* h = reps + (size_t)rep_row[unit] * D;
+    if (lane == 63) {
+        const uint32_t i = target[unit];
+        scores[unit] = m.b[i] + chain_dot<D>(h, m.E + (size_t)i * D);
+    }
+    if (!unit_bt) return;
+    const uint2 bt = unit_bt[unit]; /* (b, t) */
+    const float sh = shift[unit];
+    uint64_t sub = 0;
+    for (uint32_t j = lane; j <= bt.y; j += 64) {
+        const uint32_t r = (uint32_t)off[j] + bt.x;
+        if (!first_occ[r]) continue;
+        const uint32_t i = in_idx[r];
+        const float s = m.b[i] + chain_dot<D>(h, m.E + (size_t)i * D);
+        sub += sbr_softmax_weight(__fmul_rn(s, inv_t), sh, frac_bits);
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)sub, o, 64);
+        const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(sub >> 32), o, 64);
+        sub += ((uint64_t)hi << 32) | lo;
+    }
+    if (lane == 0 && sub) mass[unit] -= (unsigned long long)sub;
+}
+
 // ------------------------------------------------------------------------------------------------
 // recommend_above / audience_above: every scanned column at or over a per-row score — the catalogue scan with an epilogue that
 // counts, then (a second launch) writes
@@ -2280,11 +2381,11 @@ int launch_recommend_sampled(const ModelView& m, const float* reps, const TopkSc
     return n + 1;
 }
 
-int launch_log_partition(const ModelView& m, const float* reps, const TopkScan& sc, const PartitionScan& pt, hipStream_t s) {
-    if (sc.n == 0) return 0;
-    int n = topk_scan<BiasAdd>(m, reps, sc, BiasAdd::Args{}, s); /* sc.k == 1: the rows' best allowed items and their scores */
-    hipLaunchKernelGGL(partition_shift_kernel, dim3((sc.n + 255) / 256), dim3(256), 0, s, sc.out_items, sc.out_scores, sc.n, pt.inv_t, pt.shift,
-                       pt.mass);
+namespace {
+
+/* log_partition's sum scan over sc's rows at pt's shifts, then — with exclusion lists — the finish: the only place that decides the
+ * sum scan's item ranges and its Filter instantiation */
+int partition_sum(const ModelView& m, const float* reps, const TopkScan& sc, const PartitionScan& pt, hipStream_t s) {
     // item ranges as launch_recommend's at k = 1: two rounds of the chip's resident slots (two workgroups per CU at d <= 128)
     const uint32_t utiles = (sc.n + 127) / 128;
     uint32_t per = 0;
@@ -2302,7 +2403,57 @@ int launch_log_partition(const ModelView& m, const float* reps, const TopkScan& 
             hipLaunchKernelGGL((partition_finish_kernel<DD>), dim3(sc.n), dim3(64), 0, s, m, reps, sc.rep_row, pt.shift, pt.inv_t, fb, sc.excl_ptr,
                                sc.excl_items, sc.f.tags, sc.f.any_of, sc.f.none_of, pt.mass);
     });
-    return n + 2 + (sc.excl_ptr ? 1 : 0);
+    return 1 + (sc.excl_ptr ? 1 : 0);
+}
+
+}  // namespace
+
+int launch_log_partition(const ModelView& m, const float* reps, const TopkScan& sc, const PartitionScan& pt, hipStream_t s) {
+    if (sc.n == 0) return 0;
+    int n = topk_scan<BiasAdd>(m, reps, sc, BiasAdd::Args{}, s); /* sc.k == 1: the rows' best allowed items and their scores */
+    hipLaunchKernelGGL(partition_shift_kernel, dim3((sc.n + 255) / 256), dim3(256), 0, s, sc.out_items, sc.out_scores, sc.n, pt.inv_t, pt.shift,
+                       pt.mass);
+    return n + 1 + partition_sum(m, reps, sc, pt, s);
+}
+
+uint32_t sequence_shift_pool() {
+    const char* e = std::getenv("SBR_SEQ_SHIFT_K");
+    if (e && *e) {
+        const long long k = std::atoll(e);
+        if (k >= 1 && k <= 1024) return (uint32_t)k;
+    }
+    return 16; /* a row is unresolved only if its 16 best items of the whole catalogue are all in its own prefix */
+}
+
+int launch_sequence_shift(const ModelView& m, const float* reps, const TopkScan& sc, const SequencePartitionScan& sp, hipStream_t s) {
+    if (sc.n == 0) return 0;
+    int n = topk_scan<BiasAdd>(m, reps, sc, BiasAdd::Args{}, s); /* no exclusion list: the rows' sc.k best of the whole catalogue */
+    if (sp.unit_bt)
+        hipLaunchKernelGGL(sequence_shift_kernel, dim3((sc.n + 3) / 4), dim3(256), 0, s, sc.out_items, sc.out_scores, sc.k, sp.unit_bt, sc.n, sp.off,
+                           sp.in_idx, sp.pt.inv_t, sp.pt.shift, sp.pt.mass, sp.unresolved);
+    else /* sc.k == 1 and nothing masked: log_partition's own shift */
+        hipLaunchKernelGGL(partition_shift_kernel, dim3((sc.n + 255) / 256), dim3(256), 0, s, sc.out_items, sc.out_scores, sc.n, sp.pt.inv_t,
+                           sp.pt.shift, sp.pt.mass);
+    return n + 1;
+}
+
+int launch_sequence_shift_rows(const ModelView& m, const float* reps, const TopkScan& sc, float inv_t, const uint32_t* rows, float* shift,
+                               hipStream_t s) {
+    if (sc.n == 0) return 0;
+    int n = topk_scan<BiasAdd>(m, reps, sc, BiasAdd::Args{}, s); /* sc.k == 1, with the rows' exclusion lists */
+    hipLaunchKernelGGL(sequence_shift_rows_kernel, dim3((sc.n + 255) / 256), dim3(256), 0, s, sc.out_items, sc.out_scores, sc.n, inv_t, rows, shift);
+    return n + 1;
+}
+
+int launch_sequence_partition(const ModelView& m, const float* reps, const TopkScan& sc, const SequencePartitionScan& sp, hipStream_t s) {
+    if (sc.n == 0) return 0;
+    int n = partition_sum(m, reps, sc, sp.pt, s); /* sc has neither lists nor tags: every item with d <= 0 is added */
+    const uint32_t fb = sbr_softmax_fbits(m.num_items);
+    DISPATCH_D(m.d, {
+        hipLaunchKernelGGL((partition_prefix_kernel<DD>), dim3((sc.n + 3) / 4), dim3(256), 0, s, m, reps, sc.rep_row, sp.pt.shift, sp.pt.inv_t, fb,
+                           sp.unit_bt, sc.n, sp.off, sp.in_idx, sp.first_occ, sp.target, sp.pt.mass, sp.scores);
+    });
+    return n + 1;
 }
 
 uint32_t above_groups(uint32_t num_rows, uint32_t num_items, uint32_t* items_per_group) {

@@ -3969,6 +3969,85 @@ void first_occurrences(const uint32_t* w, size_t W, std::vector<uint32_t>* idx, 
     for (size_t k = 0; k < W; ++k) first[(*idx)[k]] = k == 0 || w[(*idx)[k]] != w[(*idx)[k - 1]] ? 1u : 0u;
 }
 
+/* The windows and scan units the sequence_* calls share (the contract: sbr_sequence_ranks in include/sbr_hip.h): the window of a
+ * user with n items is its last W = min(n, T + 1); its positions are 1 .. W - 1, of which the last `kept` are scanned. */
+struct SequenceUnits {
+    const uint64_t* user_ptr;
+    uint64_t num_users, T;
+    uint32_t last_positions;
+    uint64_t total = 0;               /* kept positions of the call */
+    std::vector<uint64_t> unit_user;  /* scan units: (user, position), a user's adjacent and ascending — the order of the output rows */
+    std::vector<uint32_t> unit_pos;
+    SequenceUnits(const sbr_model* m, const uint64_t* ptr, uint64_t nu, uint32_t last)
+        : user_ptr(ptr), num_users(nu), T(m->hp.max_sequence_length), last_positions(last) {
+        for (uint64_t u = 0; u < num_users; ++u) {
+            uint64_t W, kept;
+            window(u, &W, &kept);
+            total += kept;
+        }
+    }
+    void window(uint64_t u, uint64_t* W, uint64_t* kept) const {
+        const uint64_t n = user_ptr[u + 1] - user_ptr[u];
+        *W = std::min(n, T + 1);
+        *kept = n < 2 ? 0 : *W - 1;
+        if (last_positions) *kept = std::min<uint64_t>(*kept, last_positions);
+    }
+    void list_units() {
+        unit_user.reserve(total);
+        unit_pos.reserve(total);
+        for (uint64_t u = 0; u < num_users; ++u) {
+            uint64_t W, kept;
+            window(u, &W, &kept);
+            for (uint64_t p = W - kept; p < W; ++p) {
+                unit_user.push_back(u);
+                unit_pos.push_back((uint32_t)p);
+            }
+        }
+    }
+    void fill_out_ptr(uint64_t* out_ptr) const {
+        out_ptr[0] = 0;
+        for (uint64_t u = 0; u < num_users; ++u) {
+            uint64_t W, kept;
+            window(u, &W, &kept);
+            out_ptr[u + 1] = out_ptr[u] + kept;
+        }
+    }
+};
+
+/* One chunk's scan rows over the forward pass's packed layout: per sequence, once, the first-occurrence flags of its window — those
+ * of the W - 1 inputs by packed row (first_rows, the device's), and position p's own flag says whether its target occurs in its
+ * prefix (in_prefix, set only while `mask`); per scan row its state's packed row, (sequence, step) and target. */
+struct SequenceRows {
+    std::vector<int> seq_of, rep;
+    std::vector<uint64_t> wptr;
+    std::vector<uint32_t> wfirst, first_rows, test, in_prefix;
+    std::vector<uint2> bt;
+    void build(const Chunk& ch, const UserReps& ur, const Packed& pk, const std::vector<uint32_t>& unit_pos, bool mask) {
+        const size_t ns = ch.c1 - ch.c0, nlu = ch.users.size();
+        seq_of.assign(nlu, 0);
+        for (int b = 0; b < pk.B; ++b) seq_of[pk.order[b]] = b;
+        wptr.assign(nlu + 1, 0);
+        for (size_t i = 0; i < nlu; ++i) wptr[i + 1] = wptr[i] + (uint64_t)ur.b.nsteps[i] + 1;
+        wfirst.assign(wptr[nlu], 0);
+        first_rows.assign((size_t)pk.R, 0);
+        std::vector<uint32_t> order;
+        for (size_t i = 0; i < nlu; ++i) {
+            const size_t W = (size_t)ur.b.nsteps[i] + 1;
+            first_occurrences(ur.b.first[i], W, &order, wfirst.data() + wptr[i]);
+            for (size_t j = 0; j + 1 < W; ++j) first_rows[(size_t)pk.off[j] + seq_of[i]] = wfirst[wptr[i] + j];
+        }
+        rep.resize(ns); test.resize(ns); in_prefix.resize(ns); bt.resize(ns);
+        for (size_t i = 0; i < ns; ++i) {
+            const uint32_t lu = ch.lu[i], p = unit_pos[ch.c0 + i];
+            const int b = seq_of[lu];
+            rep[i] = pk.off[p - 1] + b;
+            bt[i] = make_uint2((uint32_t)b, p - 1);
+            test[i] = ur.b.first[lu][p];
+            in_prefix[i] = mask && !wfirst[wptr[lu] + p] ? 1u : 0u;
+        }
+    }
+};
+
 }  // namespace
 
 sbr_status sbr_sequence_ranks(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users, uint32_t flags,
@@ -3980,39 +4059,15 @@ sbr_status sbr_sequence_ranks(sbr_model* m, const uint64_t* user_ptr, const uint
     SBRCHK(check_csr(m, user_ptr, num_users, item_ids, false));
     const uint64_t T = m->hp.max_sequence_length;
     const bool mask = !(flags & SBR_RANK_INCLUDE_HISTORY);
-    /* the window of a user with n items is its last W = min(n, T + 1); its positions 1 .. W - 1, of which the last `kept` are scanned */
-    auto window = [&](uint64_t u, uint64_t* W, uint64_t* kept) {
-        const uint64_t n = user_ptr[u + 1] - user_ptr[u];
-        *W = std::min(n, T + 1);
-        *kept = n < 2 ? 0 : *W - 1;
-        if (last_positions) *kept = std::min<uint64_t>(*kept, last_positions);
-    };
-    uint64_t total = 0;
-    for (uint64_t u = 0; u < num_users; ++u) {
-        uint64_t W, kept;
-        window(u, &W, &kept);
-        total += kept;
-    }
+    SequenceUnits su(m, user_ptr, num_users, last_positions);
+    const uint64_t total = su.total;
     if (out_ranks) {
-        /* scan units: (user, position), a user's adjacent and ascending — the order of the output rows */
-        std::vector<uint64_t> unit_user;
-        std::vector<uint32_t> unit_pos;
-        unit_user.reserve(total);
-        unit_pos.reserve(total);
-        for (uint64_t u = 0; u < num_users; ++u) {
-            uint64_t W, kept;
-            window(u, &W, &kept);
-            for (uint64_t p = W - kept; p < W; ++p) {
-                unit_user.push_back(u);
-                unit_pos.push_back((uint32_t)p);
-            }
-        }
+        su.list_units();
         std::vector<uint32_t> ranks(total, 0);
         /* the forward pass runs over the window's first W - 1 items: all but the last item, of which the last T (as mrr_score) */
         const RepSource s = RepSource::of_histories(user_ptr, item_ids, 1, false);
-        std::vector<uint32_t> order;
-        for (Chunk ch; next_chunk(unit_user, eval_units_cap, s, T, &ch);) {
-            const size_t ns = ch.c1 - ch.c0, nlu = ch.users.size();
+        for (Chunk ch; next_chunk(su.unit_user, eval_units_cap, s, T, &ch);) {
+            const size_t ns = ch.c1 - ch.c0;
             PackedLayout lay;
             UserReps ur;
             ur.layout = &lay;
@@ -4022,36 +4077,14 @@ sbr_status sbr_sequence_ranks(sbr_model* m, const uint64_t* user_ptr, const uint
                 for (int n : ur.b.nsteps) nrows += (size_t)n;
                 sb.carve(ar, ns, nrows);
             }, &ur));
-            const Packed& pk = lay.pk;
-            /* per sequence, once: the first-occurrence flags of its window; those of the W - 1 inputs go to the device by packed row,
-             * and position p's own flag says whether its target occurs in its prefix */
-            std::vector<int> seq_of(nlu);
-            for (int b = 0; b < pk.B; ++b) seq_of[pk.order[b]] = b;
-            std::vector<uint64_t> wptr(nlu + 1, 0);
-            for (size_t i = 0; i < nlu; ++i) wptr[i + 1] = wptr[i] + (uint64_t)ur.b.nsteps[i] + 1;
-            std::vector<uint32_t> wfirst(wptr[nlu]), first_rows((size_t)pk.R, 0);
-            for (size_t i = 0; i < nlu; ++i) {
-                const size_t W = (size_t)ur.b.nsteps[i] + 1;
-                first_occurrences(ur.b.first[i], W, &order, wfirst.data() + wptr[i]);
-                for (size_t j = 0; j + 1 < W; ++j) first_rows[(size_t)pk.off[j] + seq_of[i]] = wfirst[wptr[i] + j];
-            }
-            std::vector<int> rep(ns);
-            std::vector<uint32_t> test(ns), tip(ns);
-            std::vector<uint2> bt(ns);
-            for (size_t i = 0; i < ns; ++i) {
-                const uint32_t lu = ch.lu[i], p = unit_pos[ch.c0 + i];
-                const int b = seq_of[lu];
-                rep[i] = pk.off[p - 1] + b;
-                bt[i] = make_uint2((uint32_t)b, p - 1);
-                test[i] = ur.b.first[lu][p];
-                tip[i] = mask && !wfirst[wptr[lu] + p] ? 1u : 0u;
-            }
-            HIPCHK(hipMemcpyAsync(sb.rep, rep.data(), ns * 4, hipMemcpyHostToDevice, m->stream));
-            HIPCHK(hipMemcpyAsync(sb.test, test.data(), ns * 4, hipMemcpyHostToDevice, m->stream));
-            HIPCHK(hipMemcpyAsync(sb.tip, tip.data(), ns * 4, hipMemcpyHostToDevice, m->stream));
+            SequenceRows sr;
+            sr.build(ch, ur, lay.pk, su.unit_pos, mask);
+            HIPCHK(hipMemcpyAsync(sb.rep, sr.rep.data(), ns * 4, hipMemcpyHostToDevice, m->stream));
+            HIPCHK(hipMemcpyAsync(sb.test, sr.test.data(), ns * 4, hipMemcpyHostToDevice, m->stream));
+            HIPCHK(hipMemcpyAsync(sb.tip, sr.in_prefix.data(), ns * 4, hipMemcpyHostToDevice, m->stream));
             if (mask) {
-                HIPCHK(hipMemcpyAsync(sb.bt, bt.data(), ns * 8, hipMemcpyHostToDevice, m->stream));
-                HIPCHK(hipMemcpyAsync(sb.first, first_rows.data(), first_rows.size() * 4, hipMemcpyHostToDevice, m->stream));
+                HIPCHK(hipMemcpyAsync(sb.bt, sr.bt.data(), ns * 8, hipMemcpyHostToDevice, m->stream));
+                HIPCHK(hipMemcpyAsync(sb.first, sr.first_rows.data(), sr.first_rows.size() * 4, hipMemcpyHostToDevice, m->stream));
             }
             SBRCHK(scan_launch(m, sb.flag, [&] {
                 return sbr::launch_sequence_ranks(m->mv, ur.H, sb.rep, (uint32_t)ns, sb.test, sb.tip, mask ? sb.bt : nullptr, lay.d_off, lay.d_in_idx,
@@ -4060,12 +4093,7 @@ sbr_status sbr_sequence_ranks(sbr_model* m, const uint64_t* user_ptr, const uint
         }
         if (total) std::memcpy(out_ranks, ranks.data(), total * 4);
     }
-    out_ptr[0] = 0;
-    for (uint64_t u = 0; u < num_users; ++u) {
-        uint64_t W, kept;
-        window(u, &W, &kept);
-        out_ptr[u + 1] = out_ptr[u] + kept;
-    }
+    su.fill_out_ptr(out_ptr);
     return SBR_OK;
 }
 
@@ -4850,6 +4878,151 @@ sbr_status sbr_log_partition_reps(sbr_model* m, const float* reps, uint64_t num_
                                         ScanVariant::of(nullptr, sample_filter(any_of, none_of, &hold), nullptr, &pt));
     if (r == SBR_OK) *out_frac_bits = sbr_softmax_fbits((uint32_t)m->hp.num_items);
     return r;
+}
+
+namespace {
+
+/* device buffers of the sequence_partition launchers beside TopkBufs, over ns scan rows of sequences with nrows packed rows */
+struct SequencePartitionBufs {
+    unsigned long long* mass;
+    uint2* bt;
+    uint32_t *target, *first;
+    float *shift, *scores;
+    uint8_t* unresolved;
+    void carve(DeviceArena& ar, size_t ns, size_t nrows) {
+        mass = ar.take<unsigned long long>(ns);
+        bt = ar.take<uint2>(ns);
+        target = ar.take<uint32_t>(ns);
+        first = ar.take<uint32_t>(nrows);
+        shift = ar.take<float>(ns);
+        scores = ar.take<float>(ns);
+        unresolved = ar.take<uint8_t>(ns);
+    }
+};
+
+/* The shifts of a chunk's rows whose pool held prefix items only (`rows`, ascending, not empty): their sorted distinct prefixes as
+ * the exclusion CSR of a k = 1 scan over those rows alone, in device blocks of their own — the arena is the chunk's.  Nothing of
+ * this size exists for a chunk without such rows. */
+sbr_status sequence_unresolved_shifts(sbr_model* m, const float* H, const Chunk& ch, const UserReps& ur, const SequenceRows& sr,
+                                      const std::vector<uint32_t>& unit_pos, const std::vector<uint32_t>& rows, float inv_t, float* d_shift,
+                                      uint32_t* d_flag) {
+    const size_t n = rows.size();
+    std::vector<int> rep(n);
+    std::vector<uint64_t> eptr(n + 1, 0);
+    std::vector<uint32_t> excl;
+    for (size_t i = 0; i < n; ++i) {
+        const uint32_t r = rows[i], p = unit_pos[ch.c0 + r];
+        const uint32_t* w = ur.b.first[ch.lu[r]];
+        rep[i] = sr.rep[r];
+        const size_t e0 = excl.size();
+        excl.insert(excl.end(), w, w + p);
+        std::sort(excl.begin() + e0, excl.end());
+        excl.erase(std::unique(excl.begin() + e0, excl.end()), excl.end());
+        eptr[i + 1] = excl.size();
+    }
+    uint32_t per = 0;
+    const size_t g = sbr::recommend_groups((uint32_t)n, (uint32_t)m->hp.num_items, 1, &per);
+    DeviceBlocks blocks(m->stream);
+    int* d_rep = nullptr;
+    uint64_t* d_eptr = nullptr;
+    uint32_t *d_rows = nullptr, *d_excl = nullptr, *d_lens = nullptr, *d_items = nullptr;
+    uint2* d_lists = nullptr;
+    float* d_scores = nullptr;
+    SBRCHK(blocks.take(&d_rep, n));
+    SBRCHK(blocks.take(&d_rows, n));
+    SBRCHK(blocks.take(&d_eptr, n + 1));
+    SBRCHK(blocks.take(&d_excl, excl.size() + 1));
+    SBRCHK(blocks.take(&d_lists, n * g));
+    SBRCHK(blocks.take(&d_lens, n * g));
+    SBRCHK(blocks.take(&d_items, n));
+    SBRCHK(blocks.take(&d_scores, n));
+    HIPCHK(hipMemcpyAsync(d_rep, rep.data(), n * 4, hipMemcpyHostToDevice, m->stream));
+    HIPCHK(hipMemcpyAsync(d_rows, rows.data(), n * 4, hipMemcpyHostToDevice, m->stream));
+    SBRCHK(upload_csr(m, d_eptr, eptr, d_excl, excl));
+    sbr::TopkScan sc{};
+    sc.rep_row = d_rep; sc.n = (uint32_t)n; sc.k = 1;
+    sc.excl_ptr = d_eptr; sc.excl_items = d_excl;
+    sc.lists = d_lists; sc.lens = d_lens; sc.out_items = d_items; sc.out_scores = d_scores;
+    sc.nonfinite_flag = d_flag;
+    return scan_launch(m, d_flag, [&] { return sbr::launch_sequence_shift_rows(m->mv, H, sc, inv_t, d_rows, d_shift, m->stream); }, {});
+}
+
+}  // namespace
+
+sbr_status sbr_sequence_partition(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users, float temperature,
+                                  uint32_t flags, uint32_t last_positions, uint64_t* out_ptr, float* out_shift, uint64_t* out_mass,
+                                  float* out_scores, uint8_t* out_masked) {
+    if (!m || !user_ptr || !out_ptr || (flags & ~SBR_RANK_INCLUDE_HISTORY)) return SBR_ERR_INVALID_ARGUMENT;
+    const bool sizing = !out_shift && !out_mass && !out_scores && !out_masked;
+    if (!sizing && (!out_shift || !out_mass || !out_scores || !out_masked)) return SBR_ERR_INVALID_ARGUMENT;
+    const sbr_sample_args sa{temperature, 0, nullptr};
+    Sample sm;
+    if (!sample_args(&sa, nullptr, &sm)) return SBR_ERR_INVALID_ARGUMENT;
+    std::lock_guard<std::mutex> lock(m->mu);
+    SBRCHK(enter_reader(m));
+    if (m->open_plans) return SBR_ERR_INVALID_ARGUMENT; /* as sbr_sequence_ranks */
+    SBRCHK(check_csr(m, user_ptr, num_users, item_ids, false));
+    const uint64_t T = m->hp.max_sequence_length;
+    const bool mask = !(flags & SBR_RANK_INCLUDE_HISTORY);
+    SequenceUnits su(m, user_ptr, num_users, last_positions);
+    const uint64_t total = su.total;
+    if (!sizing) {
+        su.list_units();
+        std::vector<float> shift(total), scores(total);
+        std::vector<uint64_t> mass(total);
+        std::vector<uint8_t> masked(total), unresolved;
+        /* the shift scan's k: a pool to look past the row's own prefix items in, or the arg-max alone where nothing is masked */
+        const uint32_t k0 = mask ? sbr::sequence_shift_pool() : 1u;
+        const size_t cap = std::min(eval_units_cap, recommend_users_cap((uint32_t)m->hp.num_items, k0));
+        const RepSource s = RepSource::of_histories(user_ptr, item_ids, 1, false);
+        for (Chunk ch; next_chunk(su.unit_user, cap, s, T, &ch);) {
+            const size_t ns = ch.c1 - ch.c0;
+            PackedLayout lay;
+            UserReps ur;
+            ur.layout = &lay;
+            TopkBufs tb;
+            SequencePartitionBufs pb;
+            SBRCHK(user_reps(m, s, ch.users, [&](DeviceArena& ar) {
+                size_t nrows = 0;
+                for (int n : ur.b.nsteps) nrows += (size_t)n;
+                tb.carve(ar, (uint32_t)m->hp.num_items, ns, 0, k0, false);
+                pb.carve(ar, ns, nrows);
+            }, &ur));
+            SequenceRows sr;
+            sr.build(ch, ur, lay.pk, su.unit_pos, mask);
+            HIPCHK(hipMemcpyAsync(tb.rep, sr.rep.data(), ns * 4, hipMemcpyHostToDevice, m->stream));
+            HIPCHK(hipMemcpyAsync(pb.target, sr.test.data(), ns * 4, hipMemcpyHostToDevice, m->stream));
+            if (mask) {
+                HIPCHK(hipMemcpyAsync(pb.bt, sr.bt.data(), ns * 8, hipMemcpyHostToDevice, m->stream));
+                HIPCHK(hipMemcpyAsync(pb.first, sr.first_rows.data(), sr.first_rows.size() * 4, hipMemcpyHostToDevice, m->stream));
+            }
+            const sbr::TopkScan sc = tb.scan(ns, k0, false, true);
+            const sbr::SequencePartitionScan sp{sbr::PartitionScan{sm.inv_t, pb.shift, pb.mass}, mask ? pb.bt : nullptr, lay.d_off, lay.d_in_idx,
+                                                pb.first, pb.target, pb.scores, pb.unresolved};
+            if (mask) { /* one byte per row comes back: which rows the pool did not resolve */
+                unresolved.resize(ns);
+                SBRCHK(scan_launch(m, tb.flag, [&] { return sbr::launch_sequence_shift(m->mv, ur.H, sc, sp, m->stream); },
+                                   {{unresolved.data(), pb.unresolved, ns}}));
+                std::vector<uint32_t> rows;
+                for (size_t i = 0; i < ns; ++i)
+                    if (unresolved[i]) rows.push_back((uint32_t)i);
+                if (!rows.empty()) SBRCHK(sequence_unresolved_shifts(m, ur.H, ch, ur, sr, su.unit_pos, rows, sm.inv_t, pb.shift, tb.flag));
+            }
+            SBRCHK(scan_launch(m, tb.flag, [&] {
+                const int n = mask ? 0 : sbr::launch_sequence_shift(m->mv, ur.H, sc, sp, m->stream); /* nothing masked: no host step between */
+                return n + sbr::launch_sequence_partition(m->mv, ur.H, sc, sp, m->stream);
+            }, {{shift.data() + ch.c0, pb.shift, ns * 4}, {mass.data() + ch.c0, pb.mass, ns * 8}, {scores.data() + ch.c0, pb.scores, ns * 4}}));
+            for (size_t i = 0; i < ns; ++i) masked[ch.c0 + i] = (uint8_t)sr.in_prefix[i];
+        }
+        if (total) {
+            std::memcpy(out_shift, shift.data(), total * 4);
+            std::memcpy(out_mass, mass.data(), total * 8);
+            std::memcpy(out_scores, scores.data(), total * 4);
+            std::memcpy(out_masked, masked.data(), total);
+        }
+    }
+    su.fill_out_ptr(out_ptr);
+    return SBR_OK;
 }
 
 /* ---------------------------------------------------------------------------------------------

@@ -347,6 +347,34 @@ struct PartitionScan {
     unsigned long long* mass;
 };
 int launch_log_partition(const ModelView& m, const float* reps, const TopkScan& sc, const PartitionScan& pt, hipStream_t s);
+/* sequence_partition (sbr_catalogue.hip; the contract: SEQUENCE PARTITION in include/sbr_hip.h): launch_log_partition's shift and
+ * mass for scan rows that are (sequence b, step t) = unit_bt[i] of the forward pass's packed layout, as launch_sequence_ranks'
+ * (rep_row[i] = off[t] + b; the row's mask: the first occurrences, first_occ by packed row, among in_idx[off[j] + b], j <= t),
+ * without a list of size sum(t).  Three launchers, in stream order, sc without exclusion lists or tags in the first and the last:
+ * launch_sequence_shift: the top-k scan at sc.k (the pool; sc.out_scores not NULL), then sequence_shift_kernel: pt.shift from the
+ *   first pool entry outside the row's prefix, -inf where padding comes first, unresolved[i] = 1 where all sc.k entries are prefix
+ *   items; pt.mass zeroed.  unit_bt NULL (nothing masked; sc.k == 1): partition_shift_kernel instead, unresolved untouched.
+ * launch_sequence_shift_rows: for the unresolved rows alone, sc over them at k = 1 WITH their sorted distinct prefix lists as its
+ *   exclusion CSR; shift[rows[i]] = scan row i's shift.
+ * launch_sequence_partition: partition_gemm_kernel over all rows at pt.shift (it adds prefix items too), then
+ *   partition_prefix_kernel: the prefix items' weights leave pt.mass (unit_bt NULL: none do) and scores[i] = the plain score of
+ *   target[i]. */
+struct SequencePartitionScan {
+    PartitionScan pt;          /* shift, mass [sc.n] */
+    const uint2* unit_bt;      /* [sc.n], NULL: nothing is masked (off, in_idx, first_occ, unresolved unread) */
+    const int* off;
+    const uint32_t *in_idx, *first_occ;
+    const uint32_t* target;    /* [sc.n] */
+    float* scores;             /* [sc.n] */
+    uint8_t* unresolved;       /* [sc.n] */
+};
+/* the pool of launch_sequence_shift's scan where rows are masked: 16 unless SBR_SEQ_SHIFT_K=k (1 .. 1 024) is set, a TEST HOOK read
+ * per call like SBR_CATALOGUE_GROUPS (the tests force small pools so that rows stay unresolved); no result depends on it */
+uint32_t sequence_shift_pool();
+int launch_sequence_shift(const ModelView& m, const float* reps, const TopkScan& sc, const SequencePartitionScan& sp, hipStream_t s);
+int launch_sequence_shift_rows(const ModelView& m, const float* reps, const TopkScan& sc, float inv_t, const uint32_t* rows, float* shift,
+                               hipStream_t s);
+int launch_sequence_partition(const ModelView& m, const float* reps, const TopkScan& sc, const SequencePartitionScan& sp, hipStream_t s);
 /* every scanned column at or over a per-row score (sbr_catalogue.hip; the contract: ABOVE in include/sbr_hip.h): the catalogue scan
  * with a count-then-write epilogue, above_gemm_kernel.  A column j passes row u if its score is finite and >= thresholds[u] (the f32
  * compare), f's tag test allows it and it is not in the row's exclusion segment (non-decreasing; repeats and a 0xFFFFFFFF tail as

@@ -1440,6 +1440,36 @@ class Model:
         _check(self._L.sbr_sequence_ranks(self._h, _ptr(up), _ptr(it), nu, flags, int(last), _ptr(ptr), _ptr(ranks)))
         return ptr, ranks[: int(ptr[nu])]
 
+    def sequence_partition(self, user_ptr, item_ids, temperature: float = 1.0, include_history: bool = False, last=None):
+        """What softmax(score / temperature) needs to price the next item at every position of every sequence, from one forward
+        pass per sequence (sbr_sequence_partition).  Windows, positions, ``last`` and the rows are ``sequence_ranks``'; per kept
+        position p the shift and mass are those of ``log_partition([w[:p]], temperature, include_history)`` bit for bit, the
+        score is the plain score of w[p] and ``masked`` is 1 where the prefix is masked and w[p] occurs in it (the policy never
+        shows it).  -> (ptr u64 [U + 1], Partition over the ptr[U] flat positions, scores f32, masked u8);
+        ``part.log_prob(scores[:, None])[:, 0]`` is the log-probability of each target that is not masked."""
+        up = np.ascontiguousarray(user_ptr, dtype=np.uint64)
+        it = np.ascontiguousarray(item_ids, dtype=np.uint32)
+        if up.ndim != 1 or up.size < 1:
+            raise ValueError("user_ptr holds num_users + 1 offsets")
+        if last is None:
+            last = 0
+        elif not 1 <= int(last) <= 0xFFFFFFFF:
+            raise ValueError("last must be None or in [1, 2**32)")
+        t = float(np.float32(temperature))
+        if not (np.isfinite(t) and t > 0.0):
+            raise ValueError("temperature must be finite and > 0")
+        nu = up.size - 1
+        flags = RANK_INCLUDE_HISTORY if include_history else 0
+        ptr = np.zeros(nu + 1, dtype=np.uint64)
+        _check(self._L.sbr_sequence_partition(self._h, _ptr(up), _ptr(it), nu, t, flags, int(last), _ptr(ptr), None, None, None, None))  # sizing
+        n = int(ptr[nu])
+        shift, mass, _fb = _partition_outputs(n)
+        scores = np.zeros(max(n, 1), dtype=np.float32)
+        masked = np.zeros(max(n, 1), dtype=np.uint8)
+        _check(self._L.sbr_sequence_partition(self._h, _ptr(up), _ptr(it), nu, t, flags, int(last), _ptr(ptr), _ptr(shift), _ptr(mass),
+                                              _ptr(scores), _ptr(masked)))
+        return ptr, Partition(temperature, shift, mass, softmax_frac_bits(self.hp.num_items)), scores[:n], masked[:n]
+
     def sessions(self, capacity: int, remember: int = 0) -> "Sessions":
         """A session store of ``capacity`` slots on this model (sbr_sessions_create): device-resident user states advanced one
         appended item at a time and read in place by recommend / score_candidates.  ``remember`` > 0 (at most 1 024;

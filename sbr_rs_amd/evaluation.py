@@ -207,3 +207,128 @@ def sequence_metrics(model, test: CompressedInteractions, ks=(10, 100), mask_his
     hp = getattr(params, "hp", None)
     T = int(hp.max_sequence_length) if hp is not None and hasattr(hp, "max_sequence_length") else None
     return sequence_metrics_from_ranks(ranks, ks, max_sequence_length=T)
+
+
+def _sequence_log_probs_flat(model, test, temperature, mask_history, last):
+    """(ptr int64 [U + 1], log_prob f64 [positions], masked bool [positions]) of one ``sequence_partition`` call: log(w / mass)
+    through ``Partition.log_prob`` — the one host statement of the weights — and -inf where the policy masks the target."""
+    params = getattr(model, "params", model)
+    ptr, part, scores, masked = params.sequence_partition(test.user_pointers, test.item_ids, temperature=temperature,
+                                                          include_history=not mask_history, last=last)
+    masked = masked.astype(bool)
+    lp = part.log_prob(scores[:, None])[:, 0] if scores.size else np.zeros(0, dtype=np.float64)
+    return ptr.astype(np.int64), np.where(masked, -np.inf, lp), masked
+
+
+def sequence_log_probs(model, test: CompressedInteractions, temperature: float = 1.0, mask_history: bool = True, last=None):
+    """The exact log-probability of the item that came next, at EVERY position of every test sequence, under the policy
+    ``recommend_sampled`` draws from: softmax(score / temperature) over the items the user may see — every item, or while
+    ``mask_history`` every item not among the distinct items of the prefix (``sbr_sequence_partition``: one forward pass per
+    sequence, two catalogue scans per position, no list of prefixes).
+
+    Windows, positions and ``last`` are :func:`sequence_ranks`'.  Each value is ``log_partition([w[:p]]).log_prob`` of the score
+    of w[p]: log(w / mass) over exact integer weights.  A target that occurs in its own masked prefix is never shown by the policy
+    and has -inf; so has a target more than 64 / temperature-scaled units below the row's best (its weight is 0).
+    -> one float64 array per user, positions ascending (empty for n < 2)."""
+    ptr, lp, _ = _sequence_log_probs_flat(model, test, temperature, mask_history, last)
+    return [lp[ptr[u]: ptr[u + 1]].copy() for u in range(len(ptr) - 1)]
+
+
+def sequence_log_likelihood_from_log_probs(log_probs_per_user, max_sequence_length=None):
+    """The summary of :func:`sequence_log_likelihood` from the per-user rows of :func:`sequence_log_probs`.  Pure numpy, float64.
+
+    Positions with log-prob -inf — the masked ones: the policy cannot show them, so no temperature could have predicted them —
+    are LEFT OUT of every mean and counted in ``masked_positions``.  -> dict with ``positions`` (those in the means),
+    ``masked_positions``, ``mean_log_prob`` and ``perplexity`` = exp(-mean) over all counted positions, ``macro`` with
+    ``mean_log_prob`` / ``perplexity`` as the mean of the per-user means and ``users`` (users with a counted position), and
+    ``by_history_length`` with ``count``, ``masked`` (int64) and ``mean_log_prob`` / ``perplexity`` indexed by the history length p
+    (index 0 unused; up to ``max_sequence_length``, or the longest row when that is None; the j-th entry of a row counts as
+    p = j + 1, as in :func:`sequence_metrics_from_ranks`).  Means are NaN where nothing is counted."""
+    rows = [np.asarray(r, dtype=np.float64).ravel() for r in log_probs_per_user]
+    if any(r.size and (np.isnan(r).any() or r.max() > 0.0) for r in rows):
+        raise ValueError("log-probabilities are <= 0")
+    nan = float("nan")
+    kept = [r[~np.isneginf(r)] for r in rows]
+    allp = np.concatenate(kept) if kept else np.zeros(0, dtype=np.float64)
+    mean = float(np.mean(allp)) if allp.size else nan
+    user_means = np.array([np.mean(k) for k in kept if k.size], dtype=np.float64)
+    macro = float(np.mean(user_means)) if user_means.size else nan
+    out = {"positions": int(allp.size), "masked_positions": int(sum(r.size for r in rows) - allp.size),
+           "mean_log_prob": mean, "perplexity": float(np.exp(-mean)),
+           "macro": {"mean_log_prob": macro, "perplexity": float(np.exp(-macro)), "users": int(user_means.size)}}
+    longest = max([r.size for r in rows], default=0)
+    L = longest if max_sequence_length is None else int(max_sequence_length)
+    if L < longest:
+        raise ValueError("a row has more positions than max_sequence_length")
+    by = {"count": np.zeros(L + 1, dtype=np.int64), "masked": np.zeros(L + 1, dtype=np.int64),
+          "mean_log_prob": np.full(L + 1, np.nan), "perplexity": np.full(L + 1, np.nan)}
+    for p in range(1, L + 1):
+        at = np.array([r[p - 1] for r in rows if r.size >= p], dtype=np.float64)
+        live = at[~np.isneginf(at)]
+        by["count"][p], by["masked"][p] = live.size, at.size - live.size
+        if live.size:
+            by["mean_log_prob"][p] = np.mean(live)
+            by["perplexity"][p] = np.exp(-np.mean(live))
+    out["by_history_length"] = by
+    return out
+
+
+def sequence_log_likelihood(model, test: CompressedInteractions, temperature: float = 1.0, mask_history: bool = True, last=None):
+    """Mean log-likelihood and perplexity of next-item prediction under softmax(score / temperature) at every position of every
+    test sequence (:func:`sequence_log_probs`) — the probabilistic counterpart of :func:`sequence_metrics`: micro, ``macro`` and
+    ``by_history_length``.  Masked positions (log-prob -inf) are left out of every mean and counted in ``masked_positions``.
+    With ``last`` the rows hold each window's last positions and ``by_history_length`` is indexed from the first KEPT position.
+    -> the dict of :func:`sequence_log_likelihood_from_log_probs`."""
+    params = getattr(model, "params", model)
+    rows = sequence_log_probs(model, test, temperature=temperature, mask_history=mask_history, last=last)
+    hp = getattr(params, "hp", None)
+    T = int(hp.max_sequence_length) if hp is not None and hasattr(hp, "max_sequence_length") else None
+    return sequence_log_likelihood_from_log_probs(rows, max_sequence_length=T)
+
+
+def golden_section_max(f, lo: float, hi: float, evaluations: int = 24):
+    """The maximiser of a unimodal (for one, concave) ``f`` on [lo, hi] by golden-section search with exactly ``evaluations``
+    calls of f (>= 2): the bracket shrinks by 0.618 per call after the first two.  Where the two interior values tie — two -inf of
+    an extended-valued concave function among them — the LOWER part of the bracket is kept.  -> (x, f(x)), the best point seen."""
+    lo, hi, evaluations = float(lo), float(hi), int(evaluations)
+    if not lo < hi or evaluations < 2:
+        raise ValueError("golden_section_max needs lo < hi and at least two evaluations")
+    r = (np.sqrt(5.0) - 1.0) / 2.0
+    a, b = lo, hi
+    c, d = b - r * (b - a), a + r * (b - a)
+    fc, fd = f(c), f(d)
+    for _ in range(evaluations - 2):
+        if fc >= fd:
+            b, d, fd = d, c, fc
+            c = b - r * (b - a)
+            fc = f(c)
+        else:
+            a, c, fc = c, d, fd
+            d = a + r * (b - a)
+            fd = f(d)
+    return (c, fc) if fc >= fd else (d, fd)
+
+
+def calibrate_temperature(model, validation: CompressedInteractions, bounds=(0.01, 100.0), evaluations: int = 24,
+                          mask_history: bool = True, last=1):
+    """The maximum-likelihood temperature of the policy softmax(score / T) on held-out next items: the T in ``bounds`` with the
+    largest mean :func:`sequence_log_probs` over the positions of ``validation`` that the policy does not mask (``last`` = 1:
+    each sequence's final item; None: every position).
+
+    With beta = 1 / T the mean log-prob is a linear term minus a mean log-sum-exp, so it is concave in beta, and a golden-section
+    search on beta (:func:`golden_section_max`) finds its maximum with ``evaluations`` calls of ``sequence_partition``.  A beta so
+    large that some target's weight is 0 has mean -inf; the search then moves towards smaller beta.
+    -> (temperature, mean_log_prob)."""
+    lo_t, hi_t = float(bounds[0]), float(bounds[1])
+    if not 0.0 < lo_t < hi_t or not np.isfinite(hi_t):
+        raise ValueError("bounds: 0 < lowest temperature < highest, both finite")
+
+    def mean_log_prob(beta):
+        _, lp, masked = _sequence_log_probs_flat(model, validation, 1.0 / beta, mask_history, last)
+        live = lp[~masked]
+        if live.size == 0:
+            raise ValueError("calibrate_temperature: no position of the validation set is priced by the policy")
+        return float(np.mean(live))
+
+    beta, best = golden_section_max(mean_log_prob, 1.0 / hi_t, 1.0 / lo_t, evaluations)
+    return 1.0 / beta, best

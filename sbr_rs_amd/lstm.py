@@ -503,6 +503,19 @@ class _ImplicitSequenceModel:
 
         return sequence_ranks(self, test, mask_history=mask_history, last=last)
 
+    def sequence_log_probs(self, test, temperature: float = 1.0, mask_history: bool = True, last=None):
+        """The exact log-probability of the next item under softmax(score / temperature) at every position of every test
+        sequence (``evaluation.sequence_log_probs``): one float64 array per user, -inf where the policy masks the target."""
+        from .evaluation import sequence_log_probs
+
+        return sequence_log_probs(self, test, temperature=temperature, mask_history=mask_history, last=last)
+
+    def calibrate_temperature(self, validation, bounds=(0.01, 100.0), evaluations: int = 24, mask_history: bool = True, last=1):
+        """The maximum-likelihood temperature on held-out next items (``evaluation.calibrate_temperature``)."""
+        from .evaluation import calibrate_temperature
+
+        return calibrate_temperature(self, validation, bounds=bounds, evaluations=evaluations, mask_history=mask_history, last=last)
+
 
 class ImplicitLSTMModel(_ImplicitSequenceModel):
     """An LSTM-based sequence model for implicit feedback (lstm.rs:386-416)."""
