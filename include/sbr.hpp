@@ -1351,6 +1351,383 @@ class Sessions {
     std::size_t dim_;
 };
 
+/// An item set of one model (sbr_item_set_*; ITEM SETS in sbr_hip.h): the sorted, unique ids S — a category, a territory, what is in
+/// stock — and a device copy of their rows, gathered once, so that every catalogue call restricted to S scans the set's rows and not
+/// the catalogue's.  Every method returns, bit for bit, what the model's method of the same name returns with every item outside S
+/// added to each row's exclusions: catalogue ids, predict's bits, the same noise per (seed, stream, item), the model's frac_bits.
+/// Histories, exclusion lists and a session's seen items stay catalogue ids; entries outside S are ignored.  After the model's
+/// parameters change (`fit`, a restored checkpoint) every call throws EngineError(SBR_ERR_INVALID_ARGUMENT) until `refresh()`;
+/// set_item_tags / set_item_groups take effect without one.  An empty set is legal.
+/// A call's rows are an ItemSet::Rows — of(interactions), of_reps(reps) or of(store, slots) — and every family has the Rows form
+/// plus the model's own signatures for histories and representations; `on(store)` offers Sessions' signatures.
+/// Obtained from ImplicitSequenceModel::item_set; the model (and a store it is used with) must outlive it.  Movable, not copyable.
+class ItemSet {
+  public:
+    ItemSet(sbr_model* model, const std::vector<std::uint32_t>& item_ids, std::size_t embedding_dim, std::size_t num_items)
+        : m_(model), dim_(embedding_dim), num_items_(num_items) {
+        check(sbr_item_set_create(model, item_ids.empty() ? nullptr : item_ids.data(), (std::uint64_t)item_ids.size(), &h_), "sbr_item_set_create");
+    }
+    ItemSet(const ItemSet&) = delete;
+    ItemSet& operator=(const ItemSet&) = delete;
+    ItemSet(ItemSet&& o) noexcept : h_(o.h_), m_(o.m_), dim_(o.dim_), num_items_(o.num_items_) { o.h_ = nullptr; }
+    ItemSet& operator=(ItemSet&& o) noexcept {
+        if (this != &o) { release(); h_ = o.h_; m_ = o.m_; dim_ = o.dim_; num_items_ = o.num_items_; o.h_ = nullptr; }
+        return *this;
+    }
+    ~ItemSet() { release(); }
+
+    std::size_t size() const {
+        std::uint64_t n = 0;
+        check(sbr_item_set_size(h_, &n), "sbr_item_set_size");
+        return (std::size_t)n;
+    }
+    /// The set's ids, sorted and unique.
+    std::vector<std::uint32_t> items() const {
+        std::vector<std::uint32_t> out(size() + 1);
+        check(sbr_item_set_items(h_, out.data()), "sbr_item_set_items");
+        out.pop_back();
+        return out;
+    }
+    /// Gathers the set's rows again from the model's current parameters.
+    void refresh() { check(sbr_item_set_refresh(h_), "sbr_item_set_refresh"); }
+    sbr_item_set* handle() const { return h_; }
+
+    /// The rows of one call (struct sbr_scan_rows with the arrays it points into): histories, representations or a store's slots,
+    /// with the caller's exclusion lists (representations, slots) and a tag filter.
+    class Rows {
+      public:
+        std::size_t size() const { return n_; }
+        /// The same source restricted to some rows of the call.
+        Rows take(const std::vector<std::size_t>& rows) const {
+            Rows r;
+            r.n_ = rows.size();
+            r.flags_ = flags_;
+            r.store_ = store_;
+            r.dim_ = dim_;
+            r.kind_ = kind_;
+            if (kind_ == 0) detail::csr_rows(ptr_, ids_, rows, &r.ptr_, &r.ids_);
+            for (std::size_t i : rows) {
+                if (kind_ == 1) r.reps_.insert(r.reps_.end(), reps_.begin() + (std::ptrdiff_t)(i * dim_), reps_.begin() + (std::ptrdiff_t)((i + 1) * dim_));
+                if (kind_ == 2) r.ids_.push_back(ids_[i]);
+            }
+            detail::csr_rows(excl_ptr_, excl_items_, rows, &r.excl_ptr_, &r.excl_items_);
+            r.filtered_ = filtered_;
+            if (filtered_)
+                for (std::size_t i : rows) {
+                    r.any_.push_back(any_[i]);
+                    r.none_.push_back(none_[i]);
+                }
+            return r;
+        }
+        sbr_scan_rows desc() const {
+            static const std::uint32_t none = 0;
+            static const float zero = 0.0f;
+            sbr_scan_rows d{};
+            d.flags = flags_;
+            if (kind_ == 0) { d.user_ptr = ptr_.data(); d.item_ids = ids_.empty() ? &none : ids_.data(); }
+            if (kind_ == 1) d.reps = reps_.empty() ? &zero : reps_.data();
+            if (kind_ == 2) { d.store = store_; d.slots = ids_.empty() ? &none : ids_.data(); }
+            if (!excl_ptr_.empty()) { d.excl_ptr = excl_ptr_.data(); d.excl_items = excl_items_.empty() ? &none : excl_items_.data(); }
+            if (filtered_) { d.any_of = any_.empty() ? &none : any_.data(); d.none_of = none_.empty() ? &none : none_.data(); }
+            return d;
+        }
+
+      private:
+        friend class ItemSet;
+        void finish(const std::vector<std::uint64_t>& excl_ptr, const std::vector<std::uint32_t>& excl_items, const TagFilter& filter) {
+            if (!excl_ptr.empty() && (excl_ptr.size() != n_ + 1 || excl_ptr.back() > excl_items.size()))
+                throw EngineError(SBR_ERR_INVALID_ARGUMENT, "ItemSet: one exclusion range per row");
+            excl_ptr_ = excl_ptr;
+            excl_items_ = excl_items;
+            filtered_ = !filter.any_of.empty() || !filter.none_of.empty();
+            if (filtered_) {
+                any_ = tag_masks(filter.any_of, n_, "ItemSet: one any_of mask per row");
+                none_ = tag_masks(filter.none_of, n_, "ItemSet: one none_of mask per row");
+                any_.resize(n_);
+                none_.resize(n_);
+            }
+        }
+        int kind_ = 0;  // 0: histories (ptr_, ids_), 1: representations (reps_), 2: a store's slots (store_, ids_)
+        std::size_t n_ = 0, dim_ = 0;
+        std::uint32_t flags_ = 0;
+        sbr_sessions* store_ = nullptr;
+        std::vector<std::uint64_t> ptr_, excl_ptr_;
+        std::vector<std::uint32_t> ids_, excl_items_, any_, none_;
+        std::vector<float> reps_;
+        bool filtered_ = false;
+    };
+    /// Histories: every item of a history is excluded unless `exclude_history` is false.
+    Rows of(const data::CompressedInteractions& interactions, bool exclude_history = true, const TagFilter& filter = {}) const {
+        Rows r;
+        r.kind_ = 0;
+        r.n_ = interactions.num_users();
+        r.ptr_ = interactions.user_pointers();
+        r.ids_ = interactions.item_ids();
+        r.flags_ = exclude_history ? 0u : SBR_RECOMMEND_INCLUDE_HISTORY;
+        r.finish({}, {}, filter);
+        return r;
+    }
+    /// Representations, row-major [rows][embedding_dim], with per-row exclusion lists as a CSR (both empty: none).
+    Rows of_reps(const std::vector<float>& reps, const std::vector<std::uint64_t>& excl_ptr = {}, const std::vector<std::uint32_t>& excl_items = {},
+                 const TagFilter& filter = {}) const {
+        if (reps.size() % dim_) throw EngineError(SBR_ERR_INVALID_ARGUMENT, "ItemSet: rows of embedding_dim floats");
+        Rows r;
+        r.kind_ = 1;
+        r.dim_ = dim_;
+        r.n_ = reps.size() / dim_;
+        r.reps_ = reps;
+        r.finish(excl_ptr, excl_items, filter);
+        return r;
+    }
+    /// Slots of a current store of this set's model; its seen items are excluded unless `include_seen`.
+    Rows of(const Sessions& store, const std::vector<std::uint32_t>& slots, const std::vector<std::uint64_t>& excl_ptr = {},
+            const std::vector<std::uint32_t>& excl_items = {}, bool include_seen = false, const TagFilter& filter = {}) const {
+        Rows r;
+        r.kind_ = 2;
+        r.n_ = slots.size();
+        r.store_ = store.handle();
+        r.ids_ = slots;
+        r.flags_ = include_seen ? SBR_RECOMMEND_INCLUDE_HISTORY : 0u;
+        r.finish(excl_ptr, excl_items, filter);
+        return r;
+    }
+
+    // ---- the families over any rows ----
+    Result<Recommendations, PredictionError> recommend(const Rows& rows, std::size_t k) const {
+        if (k < 1 || k > SBR_RECOMMEND_MAX_K) throw EngineError(SBR_ERR_INVALID_ARGUMENT, "ItemSet::recommend: k outside 1..SBR_RECOMMEND_MAX_K");
+        Recommendations r = top_rows(rows.size(), k);
+        const sbr_scan_rows d = rows.desc();
+        const sbr_status st = sbr_item_set_recommend(h_, &d, (std::uint64_t)rows.size(), (std::uint32_t)k, r.items.data(), r.scores.data());
+        if (st == SBR_ERR_INVALID_PREDICTION) return Result<Recommendations, PredictionError>::Err(PredictionError::InvalidPredictionValue);
+        check(st, "sbr_item_set_recommend");
+        return Result<Recommendations, PredictionError>::Ok(std::move(r));
+    }
+    Result<Recommendations, PredictionError> recommend_diverse(const Rows& rows, std::size_t k, std::size_t pool, float trade_off = 0.5f,
+                                                               Similarity metric = Similarity::Cosine) const {
+        if (k < 1 || pool < k || pool > SBR_DIVERSE_MAX_POOL)
+            throw EngineError(SBR_ERR_INVALID_ARGUMENT, "ItemSet::recommend_diverse: 1 <= k <= pool <= SBR_DIVERSE_MAX_POOL");
+        Recommendations r = top_rows(rows.size(), k);
+        const sbr_scan_rows d = rows.desc();
+        const sbr_status st = sbr_item_set_recommend_diverse(h_, &d, (std::uint64_t)rows.size(), (std::uint32_t)k, (std::uint32_t)pool, trade_off,
+                                                             (std::uint32_t)metric, r.items.data(), r.scores.data());
+        if (st == SBR_ERR_INVALID_PREDICTION) return Result<Recommendations, PredictionError>::Err(PredictionError::InvalidPredictionValue);
+        check(st, "sbr_item_set_recommend_diverse");
+        return Result<Recommendations, PredictionError>::Ok(std::move(r));
+    }
+    Result<SampledRecommendations, PredictionError> recommend_sampled(const Rows& rows, std::size_t k, const SampleArgs& sample) const {
+        if (k < 1 || k > SBR_RECOMMEND_MAX_K) throw EngineError(SBR_ERR_INVALID_ARGUMENT, "ItemSet::recommend_sampled: k outside 1..SBR_RECOMMEND_MAX_K");
+        const sbr_sample_args sa = sample_args(sample, rows.size(), "ItemSet::recommend_sampled: one stream per row");
+        SampledRecommendations r = sampled_rows(rows.size(), k);
+        const sbr_scan_rows d = rows.desc();
+        const sbr_status st = sbr_item_set_recommend_sampled(h_, &d, (std::uint64_t)rows.size(), (std::uint32_t)k, &sa, r.items.data(), r.scores.data(),
+                                                             r.keys.data());
+        if (st == SBR_ERR_INVALID_PREDICTION) return Result<SampledRecommendations, PredictionError>::Err(PredictionError::InvalidPredictionValue);
+        check(st, "sbr_item_set_recommend_sampled");
+        return Result<SampledRecommendations, PredictionError>::Ok(std::move(r));
+    }
+    /// The mass over the set's items the rows may see; frac_bits is the model's.
+    Result<Partition, PredictionError> log_partition(const Rows& rows, float temperature = 1.0f) const {
+        Partition r;
+        r.temperature = temperature;
+        r.shift.resize(rows.size() ? rows.size() : 1);
+        r.mass.resize(rows.size() ? rows.size() : 1);
+        const sbr_scan_rows d = rows.desc();
+        const sbr_status st = sbr_item_set_log_partition(h_, &d, (std::uint64_t)rows.size(), temperature, r.shift.data(), r.mass.data(), &r.frac_bits);
+        if (st == SBR_ERR_INVALID_PREDICTION) return Result<Partition, PredictionError>::Err(PredictionError::InvalidPredictionValue);
+        check(st, "sbr_item_set_log_partition");
+        r.shift.resize(rows.size());
+        r.mass.resize(rows.size());
+        return Result<Partition, PredictionError>::Ok(std::move(r));
+    }
+    Result<Above, PredictionError> recommend_above(const Rows& rows, const std::vector<float>& thresholds, std::uint64_t max_results = ABOVE_MAX_RESULTS,
+                                                   AboveOrder order = AboveOrder::Score, bool count_only = false) const {
+        return bar("ItemSet::recommend_above", rows, detail::Bar::above(thresholds), max_results, order, count_only);
+    }
+    Result<Above, PredictionError> count_above(const Rows& rows, const std::vector<float>& thresholds) const {
+        return recommend_above(rows, thresholds, 0, AboveOrder::Id, true);
+    }
+    Result<Above, PredictionError> recommend_top(const Rows& rows, const std::vector<std::uint64_t>& n, std::uint64_t max_results = ABOVE_MAX_RESULTS,
+                                                 AboveOrder order = AboveOrder::Score, bool count_only = false) const {
+        return bar("ItemSet::recommend_top", rows, detail::Bar::best(n), max_results, order, count_only);
+    }
+    /// cap.exact finishes the rows the pool did not settle with the set's own recommend_top and the rule on the host.
+    Result<CappedRecommendations, PredictionError> recommend_capped(const Rows& rows, std::size_t k, const CapArgs& cap = {}) const {
+        const sbr_cap_args ca = detail::cap_args(cap, k, "ItemSet::recommend_capped");
+        const std::size_t n = rows.size();
+        CappedRecommendations r;
+        r.num_users = n;
+        r.k = k;
+        r.items.resize(n * k);
+        r.scores.resize(n * k);
+        r.complete.assign(n ? n : 1, 0);
+        const sbr_scan_rows d = rows.desc();
+        const sbr_status st = sbr_item_set_recommend_capped(h_, &d, (std::uint64_t)n, (std::uint32_t)k, &ca, r.items.data(), r.scores.data(),
+                                                            r.complete.data());
+        if (st == SBR_ERR_INVALID_PREDICTION) return Result<CappedRecommendations, PredictionError>::Err(PredictionError::InvalidPredictionValue);
+        check(st, "sbr_item_set_recommend_capped");
+        r.complete.resize(n);
+        if (cap.exact && std::find(r.complete.begin(), r.complete.end(), 0) != r.complete.end()) {
+            std::vector<std::uint32_t> groups(num_items_);
+            check(sbr_model_get_item_groups(m_, groups.data()), "sbr_model_get_item_groups");
+            const bool ok = detail::capped_complete(
+                [&](const std::vector<std::size_t>& some, std::uint64_t top_n) { return recommend_top(rows.take(some), {top_n}); }, &r, groups, ca.cap,
+                ca.pool);
+            if (!ok) return Result<CappedRecommendations, PredictionError>::Err(PredictionError::InvalidPredictionValue);
+        }
+        return Result<CappedRecommendations, PredictionError>::Ok(std::move(r));
+    }
+
+    // ---- the model's signatures: histories and representations ----
+    Result<Recommendations, PredictionError> recommend(const data::CompressedInteractions& interactions, std::size_t k, bool exclude_history = true,
+                                                       const TagFilter& filter = {}) const {
+        return recommend(of(interactions, exclude_history, filter), k);
+    }
+    Result<Recommendations, PredictionError> recommend_reps(const std::vector<float>& reps, std::size_t k, const std::vector<std::uint64_t>& excl_ptr = {},
+                                                            const std::vector<std::uint32_t>& excl_items = {}, const TagFilter& filter = {}) const {
+        return recommend(of_reps(reps, excl_ptr, excl_items, filter), k);
+    }
+    Result<SampledRecommendations, PredictionError> recommend_sampled(const data::CompressedInteractions& interactions, std::size_t k,
+                                                                      const SampleArgs& sample, bool exclude_history = true,
+                                                                      const TagFilter& filter = {}) const {
+        return recommend_sampled(of(interactions, exclude_history, filter), k, sample);
+    }
+    Result<SampledRecommendations, PredictionError> recommend_sampled_reps(const std::vector<float>& reps, std::size_t k, const SampleArgs& sample,
+                                                                           const std::vector<std::uint64_t>& excl_ptr = {},
+                                                                           const std::vector<std::uint32_t>& excl_items = {},
+                                                                           const TagFilter& filter = {}) const {
+        return recommend_sampled(of_reps(reps, excl_ptr, excl_items, filter), k, sample);
+    }
+    Result<Partition, PredictionError> log_partition(const data::CompressedInteractions& interactions, float temperature = 1.0f,
+                                                     bool exclude_history = true, const TagFilter& filter = {}) const {
+        return log_partition(of(interactions, exclude_history, filter), temperature);
+    }
+    Result<Partition, PredictionError> log_partition_reps(const std::vector<float>& reps, float temperature, const std::vector<std::uint64_t>& excl_ptr = {},
+                                                          const std::vector<std::uint32_t>& excl_items = {}, const TagFilter& filter = {}) const {
+        return log_partition(of_reps(reps, excl_ptr, excl_items, filter), temperature);
+    }
+    Result<Above, PredictionError> recommend_above(const data::CompressedInteractions& interactions, const std::vector<float>& thresholds,
+                                                   bool exclude_history = true, const TagFilter& filter = {}, std::uint64_t max_results = ABOVE_MAX_RESULTS,
+                                                   AboveOrder order = AboveOrder::Score, bool count_only = false) const {
+        return recommend_above(of(interactions, exclude_history, filter), thresholds, max_results, order, count_only);
+    }
+    Result<Above, PredictionError> recommend_above_reps(const std::vector<float>& reps, const std::vector<float>& thresholds,
+                                                        const std::vector<std::uint64_t>& excl_ptr = {}, const std::vector<std::uint32_t>& excl_items = {},
+                                                        const TagFilter& filter = {}, std::uint64_t max_results = ABOVE_MAX_RESULTS,
+                                                        AboveOrder order = AboveOrder::Score, bool count_only = false) const {
+        return recommend_above(of_reps(reps, excl_ptr, excl_items, filter), thresholds, max_results, order, count_only);
+    }
+    Result<Above, PredictionError> recommend_top(const data::CompressedInteractions& interactions, const std::vector<std::uint64_t>& n,
+                                                 bool exclude_history = true, const TagFilter& filter = {}, std::uint64_t max_results = ABOVE_MAX_RESULTS,
+                                                 AboveOrder order = AboveOrder::Score, bool count_only = false) const {
+        return recommend_top(of(interactions, exclude_history, filter), n, max_results, order, count_only);
+    }
+    Result<Above, PredictionError> recommend_top_reps(const std::vector<float>& reps, const std::vector<std::uint64_t>& n,
+                                                      const std::vector<std::uint64_t>& excl_ptr = {}, const std::vector<std::uint32_t>& excl_items = {},
+                                                      const TagFilter& filter = {}, std::uint64_t max_results = ABOVE_MAX_RESULTS,
+                                                      AboveOrder order = AboveOrder::Score, bool count_only = false) const {
+        return recommend_top(of_reps(reps, excl_ptr, excl_items, filter), n, max_results, order, count_only);
+    }
+    Result<CappedRecommendations, PredictionError> recommend_capped(const data::CompressedInteractions& interactions, std::size_t k, const CapArgs& cap = {},
+                                                                    bool exclude_history = true, const TagFilter& filter = {}) const {
+        return recommend_capped(of(interactions, exclude_history, filter), k, cap);
+    }
+    Result<CappedRecommendations, PredictionError> recommend_capped_reps(const std::vector<float>& reps, std::size_t k, const CapArgs& cap = {},
+                                                                         const std::vector<std::uint64_t>& excl_ptr = {},
+                                                                         const std::vector<std::uint32_t>& excl_items = {},
+                                                                         const TagFilter& filter = {}) const {
+        return recommend_capped(of_reps(reps, excl_ptr, excl_items, filter), k, cap);
+    }
+    Result<Recommendations, PredictionError> recommend_diverse(const data::CompressedInteractions& interactions, std::size_t k, std::size_t pool,
+                                                               float trade_off = 0.5f, Similarity metric = Similarity::Cosine,
+                                                               bool exclude_history = true, const TagFilter& filter = {}) const {
+        return recommend_diverse(of(interactions, exclude_history, filter), k, pool, trade_off, metric);
+    }
+    Result<Recommendations, PredictionError> recommend_diverse_reps(const std::vector<float>& reps, std::size_t k, std::size_t pool, float trade_off = 0.5f,
+                                                                    Similarity metric = Similarity::Cosine, const std::vector<std::uint64_t>& excl_ptr = {},
+                                                                    const std::vector<std::uint32_t>& excl_items = {}, const TagFilter& filter = {}) const {
+        return recommend_diverse(of_reps(reps, excl_ptr, excl_items, filter), k, pool, trade_off, metric);
+    }
+
+    /// `on(store)`: Sessions' scan signatures through the set.
+    class OnSessions {
+      public:
+        OnSessions(const ItemSet& set, const Sessions& store) : set_(set), store_(store) {}
+        Result<Recommendations, PredictionError> recommend(const std::vector<std::uint32_t>& slots, std::size_t k, const std::vector<std::uint64_t>& excl_ptr = {},
+                                                           const std::vector<std::uint32_t>& excl_items = {}, bool include_seen = false,
+                                                           const TagFilter& filter = {}) const {
+            return set_.recommend(set_.of(store_, slots, excl_ptr, excl_items, include_seen, filter), k);
+        }
+        Result<SampledRecommendations, PredictionError> recommend_sampled(const std::vector<std::uint32_t>& slots, std::size_t k, const SampleArgs& sample,
+                                                                          const TagFilter& filter = {}, const std::vector<std::uint64_t>& excl_ptr = {},
+                                                                          const std::vector<std::uint32_t>& excl_items = {}, bool include_seen = false) const {
+            return set_.recommend_sampled(set_.of(store_, slots, excl_ptr, excl_items, include_seen, filter), k, sample);
+        }
+        Result<Partition, PredictionError> log_partition(const std::vector<std::uint32_t>& slots, float temperature, const TagFilter& filter = {},
+                                                         const std::vector<std::uint64_t>& excl_ptr = {}, const std::vector<std::uint32_t>& excl_items = {},
+                                                         bool include_seen = false) const {
+            return set_.log_partition(set_.of(store_, slots, excl_ptr, excl_items, include_seen, filter), temperature);
+        }
+        Result<Above, PredictionError> recommend_above(const std::vector<std::uint32_t>& slots, const std::vector<float>& thresholds, const TagFilter& filter = {},
+                                                       const std::vector<std::uint64_t>& excl_ptr = {}, const std::vector<std::uint32_t>& excl_items = {},
+                                                       bool include_seen = false, std::uint64_t max_results = ABOVE_MAX_RESULTS,
+                                                       AboveOrder order = AboveOrder::Score, bool count_only = false) const {
+            return set_.recommend_above(set_.of(store_, slots, excl_ptr, excl_items, include_seen, filter), thresholds, max_results, order, count_only);
+        }
+        Result<Above, PredictionError> recommend_top(const std::vector<std::uint32_t>& slots, const std::vector<std::uint64_t>& n, const TagFilter& filter = {},
+                                                     const std::vector<std::uint64_t>& excl_ptr = {}, const std::vector<std::uint32_t>& excl_items = {},
+                                                     bool include_seen = false, std::uint64_t max_results = ABOVE_MAX_RESULTS,
+                                                     AboveOrder order = AboveOrder::Score, bool count_only = false) const {
+            return set_.recommend_top(set_.of(store_, slots, excl_ptr, excl_items, include_seen, filter), n, max_results, order, count_only);
+        }
+        Result<CappedRecommendations, PredictionError> recommend_capped(const std::vector<std::uint32_t>& slots, std::size_t k, const CapArgs& cap = {},
+                                                                        const TagFilter& filter = {}, const std::vector<std::uint64_t>& excl_ptr = {},
+                                                                        const std::vector<std::uint32_t>& excl_items = {}, bool include_seen = false) const {
+            return set_.recommend_capped(set_.of(store_, slots, excl_ptr, excl_items, include_seen, filter), k, cap);
+        }
+        Result<Recommendations, PredictionError> recommend_diverse(const std::vector<std::uint32_t>& slots, std::size_t k, std::size_t pool, float trade_off = 0.5f,
+                                                                   Similarity metric = Similarity::Cosine, const std::vector<std::uint64_t>& excl_ptr = {},
+                                                                   const std::vector<std::uint32_t>& excl_items = {}, const TagFilter& filter = {}) const {
+            return set_.recommend_diverse(set_.of(store_, slots, excl_ptr, excl_items, false, filter), k, pool, trade_off, metric);
+        }
+
+      private:
+        const ItemSet& set_;
+        const Sessions& store_;
+    };
+    OnSessions on(const Sessions& store) const { return OnSessions(*this, store); }
+
+  private:
+    static Recommendations top_rows(std::size_t n, std::size_t k) {
+        Recommendations r;
+        r.num_users = n;
+        r.k = k;
+        r.items.resize(n * k);
+        r.scores.resize(n * k);
+        return r;
+    }
+    Result<Above, PredictionError> bar(const char* me, const Rows& rows, detail::Bar b, std::uint64_t max_results, AboveOrder order, bool count_only) const {
+        b.fit(rows.size(), me, "row");
+        const sbr_scan_rows d = rows.desc();
+        Above r;
+        const sbr_status st = detail::above_call(
+            [&](std::uint64_t* counts, std::uint64_t* total, std::uint64_t cap, std::uint32_t* ids, float* scores) {
+                if (b.top)
+                    return sbr_item_set_recommend_top(h_, &d, (std::uint64_t)rows.size(), b.n.data(), b.cuts.data(), counts, total, cap, ids, scores);
+                return sbr_item_set_recommend_above(h_, &d, (std::uint64_t)rows.size(), b.th.data(), counts, total, cap, ids, scores);
+            },
+            rows.size(), max_results, order, count_only, b.top ? "sbr_item_set_recommend_top" : "sbr_item_set_recommend_above", b, &r);
+        if (st == SBR_ERR_INVALID_PREDICTION) return Result<Above, PredictionError>::Err(PredictionError::InvalidPredictionValue);
+        return Result<Above, PredictionError>::Ok(std::move(r));
+    }
+    void release() {
+        if (h_) sbr_item_set_destroy(h_);
+        h_ = nullptr;
+    }
+    sbr_item_set* h_ = nullptr;
+    sbr_model* m_ = nullptr;
+    std::size_t dim_ = 0, num_items_ = 0;
+};
+
 /// Owner of the device replicas behind one model object: `num_threads` replicas (≙ the worker
 /// threads of sequence_model.rs:90-102), replica r on HIP device r mod device_count
 /// (sbr_group_create).
@@ -2220,6 +2597,12 @@ class ImplicitSequenceModel : public OnlineRankingModel<ImplicitUser> {
         return Sessions(replicas_->primary(), capacity, replicas_->hparams().embedding_dim, seen_capacity);
     }
 
+    /// An item set of this model on the primary replica (see ItemSet): `item_ids` in any order, duplicates allowed, each below
+    /// num_items.  Destroy it before this model; call its refresh() after `fit`.
+    ItemSet item_set(const std::vector<std::uint32_t>& item_ids) const {
+        return ItemSet(replicas_->primary(), item_ids, replicas_->hparams().embedding_dim, replicas_->hparams().num_items);
+    }
+
     /// The engine handle (replica 0), for evaluation's fused path and for parameter access.
     sbr_model* handle() const { return replicas_->primary(); }
     const sbr_hparams& hparams() const { return replicas_->hparams(); }
@@ -2505,8 +2888,10 @@ class Hyperparameters : public detail::HyperparametersBase<Hyperparameters> {
 
 } // namespace ewma
 using Sessions = detail::Sessions;
+using ItemSet = detail::ItemSet;
 } // namespace models
 using Sessions = models::Sessions;
+using ItemSet = models::ItemSet;
 
 // =============================================================================================
 // sbr::evaluation  (src/evaluation.rs)

@@ -1009,6 +1009,58 @@ sbr_status sbr_model_set_counters(sbr_model* m, uint64_t global_epoch, uint64_t 
 /* Library / device identification ("gfx950", CU count, HBM bytes); device_name may be NULL. */
 sbr_status sbr_device_info(char* device_name, uint64_t name_bytes, uint32_t* out_cus, uint64_t* out_hbm_bytes);
 const char* sbr_status_string(sbr_status s);
+/* ITEM SETS — every catalogue call above restricted to a set of items S (in stock, one category, this week's releases) that is kept
+ * on the device.  An item set is a handle owned by a model: the sorted, de-duplicated ids S and a persistent device copy of their
+ * rows, E'[j] = E[S[j]] and b'[j] = b[S[j]] at storage width (|S| * (storage width + 1) * 4 bytes of plain device memory), gathered
+ * once at creation, so that a call's cost follows |S| and not the catalogue.
+ * The contract is sbr_recommend_among's, for every family: a call through a set returns, bit for bit, what the same call on the
+ * model returns with every item outside S added to each row's exclusion list — ids (catalogue ids, never positions), score bits,
+ * keys, order, padding, the non-finite rule, shift and mass as integers (out_frac_bits is the MODEL's F), counts, cuts, CSR
+ * contents and complete flags.  The noise of a sampled call is a function of (seed, stream, catalogue id), as on the model.  Inputs
+ * stay catalogue ids — histories, exclusion lists, a session's seen items — and entries outside S are ignored.  Rows outside S are
+ * never read: a non-finite row outside S fails no call, one inside S does.
+ * Lifecycle: the set is bound to the model's parameters as a session store is.  After sbr_model_fit, sbr_model_set_param or a load
+ * every scan through it returns SBR_ERR_INVALID_ARGUMENT until sbr_item_set_refresh gathers the rows again; while a fit plan is
+ * open on the model every call but size / items / destroy does.  Item tags and item groups are not cached: every launch gathers the
+ * set's words, so sbr_model_set_item_tags / sbr_model_set_item_groups take effect at once.  An empty set is legal: every call answers
+ * as the plain call does for a row that may see nothing.  sbr_item_set_create takes ids in any order, duplicates allowed; an id >=
+ * num_items is an argument error.  A set follows the session stores' rule of destruction: it holds a pointer to its model and works
+ * on the model's stream; it is destroyed before its model.
+ * One descriptor names a call's rows — exactly one of three sources (zero or two: an argument error):
+ *   histories        user_ptr / item_ids as sbr_recommend's, flags 0 or SBR_RECOMMEND_INCLUDE_HISTORY; excl_* must be NULL;
+ *   representations  reps [num_rows][embedding_dim] as the *_reps calls', flags 0, with the optional lists excl_ptr / excl_items;
+ *   a store          store / slots as the sbr_sessions_* scans', the store current and of the set's model, flags as theirs
+ *                    (SBR_RECOMMEND_INCLUDE_HISTORY: do not exclude the seen items), with the optional lists.
+ * any_of / none_of (both NULL: no filter) are the tag masks of the filtered forms, one pair per row.  The seven calls take the
+ * descriptor and then the argument tail of their *_reps siblings without the lists and masks, which the descriptor carries. */
+typedef struct sbr_item_set sbr_item_set;
+typedef struct sbr_scan_rows {     /* exactly one of the three sources */
+    const uint64_t* user_ptr; const uint32_t* item_ids; uint32_t flags;   /* histories; SBR_RECOMMEND_INCLUDE_HISTORY */
+    const float* reps;                                                    /* representations */
+    sbr_sessions* store; const uint32_t* slots;                           /* a current store of the set's model; flags' INCLUDE_HISTORY = include_seen */
+    const uint64_t* excl_ptr; const uint32_t* excl_items;                 /* caller's lists (reps, store); nullable */
+    const uint32_t *any_of, *none_of;                                     /* nullable */
+} sbr_scan_rows;
+sbr_status sbr_item_set_create(sbr_model* m, const uint32_t* item_ids, uint64_t n, sbr_item_set** out);
+void sbr_item_set_destroy(sbr_item_set* set);
+sbr_status sbr_item_set_size(const sbr_item_set* set, uint64_t* out);
+sbr_status sbr_item_set_items(const sbr_item_set* set, uint32_t* out); /* out [size]: the sorted unique ids */
+sbr_status sbr_item_set_refresh(sbr_item_set* set);
+sbr_status sbr_item_set_recommend(sbr_item_set* set, const struct sbr_scan_rows* rows, uint64_t num_rows, uint32_t k, uint32_t* out_items,
+                                  float* out_scores);
+sbr_status sbr_item_set_recommend_diverse(sbr_item_set* set, const struct sbr_scan_rows* rows, uint64_t num_rows, uint32_t k, uint32_t pool,
+                                          float trade_off, uint32_t metric, uint32_t* out_items, float* out_scores);
+sbr_status sbr_item_set_recommend_sampled(sbr_item_set* set, const struct sbr_scan_rows* rows, uint64_t num_rows, uint32_t k,
+                                          const struct sbr_sample_args* sample, uint32_t* out_items, float* out_scores, float* out_keys);
+sbr_status sbr_item_set_log_partition(sbr_item_set* set, const struct sbr_scan_rows* rows, uint64_t num_rows, float temperature, float* out_shift,
+                                      uint64_t* out_mass, uint32_t* out_frac_bits);
+sbr_status sbr_item_set_recommend_above(sbr_item_set* set, const struct sbr_scan_rows* rows, uint64_t num_rows, const float* thresholds,
+                                        uint64_t* out_counts, uint64_t* out_total, uint64_t capacity, uint32_t* out_ids, float* out_scores);
+sbr_status sbr_item_set_recommend_top(sbr_item_set* set, const struct sbr_scan_rows* rows, uint64_t num_rows, const uint64_t* n, float* out_cuts,
+                                      uint64_t* out_counts, uint64_t* out_total, uint64_t capacity, uint32_t* out_ids, float* out_scores);
+sbr_status sbr_item_set_recommend_capped(sbr_item_set* set, const struct sbr_scan_rows* rows, uint64_t num_rows, uint32_t k,
+                                         const struct sbr_cap_args* cap, uint32_t* out_items, float* out_scores, uint8_t* out_complete);
+
 #define SBR_ABI_VERSION 13u /* what sbr_abi_version returns from a library built from this header */
 uint32_t sbr_abi_version(void);
 

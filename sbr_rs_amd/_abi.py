@@ -105,6 +105,22 @@ class SbrCapArgs(C.Structure):
     ]
 
 
+class SbrScanRows(C.Structure):
+    """struct sbr_scan_rows of the sbr_item_set_* scans: exactly one of user_ptr / reps / store names the rows"""
+    _fields_ = [
+        ("user_ptr", C.c_void_p),
+        ("item_ids", C.c_void_p),
+        ("flags", C.c_uint32),
+        ("reps", C.c_void_p),
+        ("store", C.c_void_p),
+        ("slots", C.c_void_p),
+        ("excl_ptr", C.c_void_p),
+        ("excl_items", C.c_void_p),
+        ("any_of", C.c_void_p),
+        ("none_of", C.c_void_p),
+    ]
+
+
 def storage_dim(embedding_dim: int) -> int:
     """Width the engine stores an embedding_dim in (16 / 32 / 64 / 128 / 256; the extra columns are zero and stay
     zero — sbr_engine.hip `storage_dim`).  Parameters, user representations and predictions use embedding_dim;

@@ -196,6 +196,18 @@ def load():
         "sbr_sessions_recommend_capped": [vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint32, vp, vp, vp, vp, vp, vp],
         "sbr_sequence_ranks": [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp],
         "sbr_sequence_partition": [vp, vp, vp, C.c_uint64, C.c_float, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp],
+        # item sets: (set, const sbr_scan_rows*, num_rows, ...) and the tail of the *_reps sibling without lists and masks
+        "sbr_item_set_create": [vp, vp, C.c_uint64, C.POINTER(vp)],
+        "sbr_item_set_size": [vp, u64p],
+        "sbr_item_set_items": [vp, vp],
+        "sbr_item_set_refresh": [vp],
+        "sbr_item_set_recommend": [vp, vp, C.c_uint64, C.c_uint32, vp, vp],
+        "sbr_item_set_recommend_diverse": [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, vp, vp],
+        "sbr_item_set_recommend_sampled": [vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp],
+        "sbr_item_set_log_partition": [vp, vp, C.c_uint64, C.c_float, vp, vp, vp],
+        "sbr_item_set_recommend_above": [vp, vp, C.c_uint64, vp, vp, u64p, C.c_uint64, vp, vp],
+        "sbr_item_set_recommend_top": [vp, vp, C.c_uint64, vp, vp, vp, u64p, C.c_uint64, vp, vp],
+        "sbr_item_set_recommend_capped": [vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -207,6 +219,8 @@ def load():
     L.sbr_fit_plan_destroy.restype = None
     L.sbr_sessions_destroy.argtypes = [vp]
     L.sbr_sessions_destroy.restype = None
+    L.sbr_item_set_destroy.argtypes = [vp]
+    L.sbr_item_set_destroy.restype = None
     L.sbr_comm_destroy.argtypes = [vp]
     L.sbr_comm_destroy.restype = None
     L.sbr_group_plan_destroy.argtypes = [vp]
@@ -265,4 +279,7 @@ DECLARED_SYMBOLS = [
     "sbr_model_set_item_groups", "sbr_model_get_item_groups",
     "sbr_recommend_capped", "sbr_recommend_capped_reps", "sbr_sessions_recommend_capped",
     "sbr_sequence_ranks", "sbr_sequence_partition",
+    "sbr_item_set_create", "sbr_item_set_destroy", "sbr_item_set_size", "sbr_item_set_items", "sbr_item_set_refresh",
+    "sbr_item_set_recommend", "sbr_item_set_recommend_diverse", "sbr_item_set_recommend_sampled", "sbr_item_set_log_partition",
+    "sbr_item_set_recommend_above", "sbr_item_set_recommend_top", "sbr_item_set_recommend_capped",
 ]

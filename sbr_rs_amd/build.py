@@ -234,6 +234,15 @@ def build_sequence_partition_tests(force: bool = False, verbose: bool = True) ->
     return _build_cpp_program(SEQUENCE_PARTITION_SRC, SEQUENCE_PARTITION_BIN, force, verbose)
 
 
+ITEM_SET_SRC = os.path.join(REPO, "tests", "cpp", "item_set_tests.cpp")
+ITEM_SET_BIN = os.path.join(REPO, "tests", "cpp", "_build", "item_set_tests")
+
+
+def build_item_set_tests(force: bool = False, verbose: bool = True) -> str:
+    """g++ build of the C++ host layer's item-set test program."""
+    return _build_cpp_program(ITEM_SET_SRC, ITEM_SET_BIN, force, verbose)
+
+
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv))
     print(build_facade_tests(force="--force" in sys.argv))
@@ -254,3 +263,4 @@ if __name__ == "__main__":
     print(build_capped_tests(force="--force" in sys.argv))
     print(build_sequence_ranks_tests(force="--force" in sys.argv))
     print(build_sequence_partition_tests(force="--force" in sys.argv))
+    print(build_item_set_tests(force="--force" in sys.argv))

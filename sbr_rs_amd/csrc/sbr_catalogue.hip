@@ -28,6 +28,10 @@
  *   subset_gather_kernel   : recommend_among's sub-table E'[j] = E[S[j]], b'[j] = b[S[j]] of a sorted, unique item set S; the scan is
  *                            topk_gemm_kernel + topk_merge_kernel on a ModelView of E', b', |S|, and
  *   subset_ids_kernel      : maps the merged lists' positions in S back to catalogue ids
+ *   subset_positions_kernel, subset_words_kernel : an item set's launches (sbr_item_set_*: the sub-table is resident, gathered once):
+ *                            the exclusion CSR in catalogue ids -> positions in S, in place, one wave per segment; the set's tag or
+ *                            group words gathered per launch.  The sampled scan over a set is topk_gemm_kernel's GumbelMapped
+ *                            policy, which hashes the noise from the rows' catalogue ids
  *   (audience)             : the reverse scan, "which rows for this item": topk_gemm_kernel with the QueryBias score policy — the
  *                            A operand is the query items' rows of E (reps = E, rep_row = the item ids), the scanned table a set of
  *                            state rows, and the bias the query's, b[q], held in LDS by slot
@@ -138,6 +142,18 @@ struct ItemTiles {
     __device__ __forceinline__ void stage_tags(uint32_t* Ts) {
         const int tid = threadIdx.x;
         if (tid >= 32 && tid < 64) Ts[tid - 32] = tv;
+    }
+    /* fetch_ids() / stage_ids(): the catalogue ids a sub-table's 32 rows stand for (topk_gemm_kernel's GumbelMapped), the lane group
+     * behind the tag words'; zero past i_end */
+    uint32_t iv = 0;
+    __device__ __forceinline__ void fetch_ids(const uint32_t* ids, int tile) {
+        const int tid = threadIdx.x;
+        const uint32_t i = i_begin + (uint32_t)tile * 32 + (uint32_t)(tid - 64);
+        if (tid >= 64 && tid < 96) iv = i < i_end ? ids[i] : 0u;
+    }
+    __device__ __forceinline__ void stage_ids(uint32_t* Is) {
+        const int tid = threadIdx.x;
+        if (tid >= 64 && tid < 96) Is[tid - 64] = iv;
     }
 };
 
@@ -586,11 +602,11 @@ __global__ __launch_bounds__(64) void rank_targets_finish_kernel(ModelView m, co
  * lambda in the kernel — the BiasAdd instantiations compiled to 12 more VGPRs at every d <= 128 (101 -> 113 at d = 16, 178 -> 190
  * at d = 128); this form leaves their instruction streams what they were (profiles/similar_items_8192x1M_d128.md). */
 struct BiasAdd {
-    static constexpr bool scale = false, query = false, gumbel = false;
+    static constexpr bool scale = false, query = false, gumbel = false, mapped = false;
     struct Args {};
 };
 struct ScaleMul {
-    static constexpr bool scale = true, query = false, gumbel = false;
+    static constexpr bool scale = true, query = false, gumbel = false, mapped = false;
     struct Args {};
 };
 /* audience's policy: the bias belongs to the scan's "user" — a query item q whose row E[q] is the A operand — not to the scanned
@@ -600,7 +616,7 @@ struct ScaleMul {
  * other two policies, at the end of the argument block behind Filter::Args, and every statement of this one sits under
  * `if constexpr`: their instantiations keep their instruction streams (profiles/audience_asm_stats.md). */
 struct QueryBias {
-    static constexpr bool scale = false, query = true, gumbel = false;
+    static constexpr bool scale = false, query = true, gumbel = false, mapped = false;
     struct Args {
         const float* qb; /* [the A table's rows]: the bias of query item rep_row[u] */
     };
@@ -624,10 +640,24 @@ struct QueryBias {
  * Every statement of the policy sits under `if constexpr` and its Args are at the end of the argument block: the other
  * instantiations keep their instruction streams (profiles/sampled_asm_stats.md). */
 struct GumbelBias {
-    static constexpr bool scale = false, query = false, gumbel = true;
+    static constexpr bool scale = false, query = false, gumbel = true, mapped = false;
     struct Args {
         float inv_t;
         const uint64_t* keys; /* [num_users]: the row key K of scan row u (sample_keys_kernel) */
+    };
+};
+/* GumbelBias over an item set's sub-table: the noise of (row, item) is a function of the item's CATALOGUE id, and the scanned row j
+ * stands for item ids[j].  A tile's 32 id words come in beside its biases as the tag words do (Is, a double buffer: 256 more bytes of
+ * LDS) and stages 2 and 3 hash the lane's id word where GumbelBias hashes `id`.  Thresholds, tie-breaks and staged entries stay
+ * positions: ids ascends, so the order of positions is the order of ids and no result differs from the scan of the whole catalogue
+ * with every other item excluded.  A policy of its own, every statement under `if constexpr`: the other instantiations keep their
+ * instruction streams (profiles/item_set_asm_stats.md). */
+struct GumbelMapped {
+    static constexpr bool scale = false, query = false, gumbel = true, mapped = true;
+    struct Args {
+        float inv_t;
+        const uint64_t* keys;
+        const uint32_t* ids; /* [m.num_items]: the catalogue id of scanned row j, ascending */
     };
 };
 #define TK_SCORE(q) ((Score::query || Score::gumbel) ? acc[q] : Score::scale ? acc[q] * bias : bias + acc[q])
@@ -677,6 +707,8 @@ __global__ __launch_bounds__(256, D <= 128 ? 2 : 1) void topk_gemm_kernel(ModelV
     __shared__ uint32_t cnt[128];
     __shared__ uint32_t len[128];
     __shared__ uint2 st[128][TK_STAGE];
+    // GumbelMapped only: the tiles' catalogue id words
+    __shared__ uint32_t Is[2][Score::mapped ? 32 : 1];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = tid >> 6;
@@ -820,6 +852,10 @@ __global__ __launch_bounds__(256, D <= 128 ? 2 : 1) void topk_gemm_kernel(ModelV
             tiles.fetch_tags(fa.tags, 0);
             tiles.stage_tags(Ts[0]);
         }
+        if constexpr (Score::mapped) {
+            tiles.fetch_ids(sa.ids, 0);
+            tiles.stage_ids(Is[0]);
+        }
     }
     __syncthreads();
     const int pbase = wave * 32 + hh * 16;
@@ -828,6 +864,7 @@ __global__ __launch_bounds__(256, D <= 128 ? 2 : 1) void topk_gemm_kernel(ModelV
         if (tile + 1 < ntiles) {
             tiles.fetch(m, tile + 1);
             if constexpr (Filter::on) tiles.fetch_tags(fa.tags, tile + 1);
+            if constexpr (Score::mapped) tiles.fetch_ids(sa.ids, tile + 1);
         }
         f32x16 acc = tile_dots<D>(a, Es[buf]);
         const float bias = Bs[buf][l31];
@@ -892,11 +929,13 @@ __global__ __launch_bounds__(256, D <= 128 ? 2 : 1) void topk_gemm_kernel(ModelV
             pend &= ~drop;
         }
         if constexpr (Score::gumbel) { /* stages 2 and 3, for what is still pending: the hash, the range's bound, the noise */
+            uint32_t nid = id; /* what the noise is a function of: the item's catalogue id */
+            if constexpr (Score::mapped) nid = Is[buf][l31];
             if (pend) {
 #pragma unroll
                 for (int q = 0; q < 16; ++q)
                     if ((pend >> q) & 1u) {
-                        const uint32_t r = sbr_gumbel_bits(gk0S[pbase + q], gk1S[pbase + q], id);
+                        const uint32_t r = sbr_gumbel_bits(gk0S[pbase + q], gk1S[pbase + q], nid);
                         const float t = acc[q];
                         if (!tk_better(__fadd_rn(t, gubS[r >> 13]), id, thS[pbase + q], thI[pbase + q])) pend &= ~(1u << q);
                         else acc[q] = __fadd_rn(t, sbr_gumbel_of_bits(r));
@@ -935,6 +974,7 @@ __global__ __launch_bounds__(256, D <= 128 ? 2 : 1) void topk_gemm_kernel(ModelV
         if (tile + 1 < ntiles) {
             tiles.stage(Es[buf ^ 1], Bs[buf ^ 1]);
             if constexpr (Filter::on) tiles.stage_tags(Ts[buf ^ 1]);
+            if constexpr (Score::mapped) tiles.stage_ids(Is[buf ^ 1]);
         }
         // a user whose staging filled is merged, then what did not fit is offered again (it fits: at most 32 per user and tile)
         while (__syncthreads_or(pend != 0u)) {
@@ -1284,6 +1324,42 @@ __global__ __launch_bounds__(256) void subset_ids_kernel(const uint32_t* subset,
     if (e >= n) return;
     const uint32_t p = items[e];
     if (p != TK_NONE) items[e] = subset[p];
+}
+
+/* dst[j] = src[S[j]]: an item set's tag or group words, gathered per launch (the words are serving metadata the set does not cache) */
+__global__ __launch_bounds__(256) void subset_words_kernel(const uint32_t* subset, uint32_t num_subset, const uint32_t* src, uint32_t* dst) {
+    const uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j < num_subset) dst[j] = src[subset[j]];
+}
+
+/* An exclusion CSR in catalogue ids -> the same segments in positions of the item set S (sorted, unique), in place.  A segment is
+ * what the scans take (the comment above session_seen_lists_kernel): non-decreasing, ids may repeat, a 0xFFFFFFFF tail.  One wave per
+ * segment walks it 64 entries at a time: each lane takes the lower bound of its entry in S, the members are kept by a ballot and
+ * written to base + popcount(the ballot's bits below the lane), and base advances by the ballot's popcount; when the walk ends
+ * 0xFFFFFFFF fills the rest of the segment.  In place is safe: base never passes the block being read, so a block's writes land
+ * below the next block's reads, and every lane's entry of the block is loaded before the ballot — which every store follows — is
+ * known.  The result is non-decreasing in positions, repeats preserved, entries outside S gone; the segment pointers do not change. */
+__global__ __launch_bounds__(256) void subset_positions_kernel(const uint32_t* subset, uint32_t num_subset, const uint64_t* eptr, uint32_t n,
+                                                               uint32_t* excl) {
+    const uint32_t seg = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const uint32_t lane = threadIdx.x & 63u;
+    if (seg >= n) return; /* the whole wave */
+    const uint64_t e0 = eptr[seg], e1 = eptr[seg + 1];
+    uint64_t base = e0;
+    for (uint64_t b0 = e0; b0 < e1; b0 += 64) {
+        const uint64_t e = b0 + lane;
+        const uint32_t id = e < e1 ? excl[e] : TK_NONE;
+        uint32_t lo = 0, hi = num_subset;
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (subset[mid] < id) lo = mid + 1; else hi = mid;
+        }
+        const bool member = id != TK_NONE && lo < num_subset && subset[lo] == id;
+        const uint64_t kept = __ballot(member);
+        if (member) excl[base + (uint64_t)__popcll(kept & ((1ull << lane) - 1ull))] = lo;
+        base += (uint64_t)__popcll(kept);
+    }
+    for (uint64_t e = base + lane; e < e1; e += 64) excl[e] = TK_NONE;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2374,11 +2450,13 @@ int launch_recommend_sampled(const ModelView& m, const float* reps, const TopkSc
     const uint64_t np = (uint64_t)sc.n * sc.k;
     const unsigned pair_blocks = (unsigned)((np + 255) / 256);
     hipLaunchKernelGGL(sample_keys_kernel, dim3((sc.n + 255) / 256), dim3(256), 0, s, sp.seed, sp.streams, sc.n, sc.g.keys);
-    int n = 1 + topk_scan<GumbelBias>(m, reps, sc, GumbelBias::Args{sc.g.inv_t, sc.g.keys}, s);
+    int n = 1 + (sp.ids ? topk_scan<GumbelMapped>(m, reps, sc, GumbelMapped::Args{sc.g.inv_t, sc.g.keys, sp.ids}, s)
+                        : topk_scan<GumbelBias>(m, reps, sc, GumbelBias::Args{sc.g.inv_t, sc.g.keys}, s));
     hipLaunchKernelGGL(sample_pairs_kernel, dim3(pair_blocks), dim3(256), 0, s, sc.rep_row, sc.out_items, sc.n, sc.k, sp.pair_row, sp.pair_item);
     n += 1 + launch_candidate_scores(m, reps, sp.pair_row, sp.pair_item, np, sp.plain, sc.nonfinite_flag, s);
     hipLaunchKernelGGL(sample_pad_kernel, dim3(pair_blocks), dim3(256), 0, s, sc.out_items, np, sp.plain);
-    return n + 1;
+    /* the plain scores were taken on the sub-table by position; only now do the rows' positions become ids */
+    return n + 1 + (sp.ids ? launch_subset_ids(sp.ids, sc, s) : 0);
 }
 
 namespace {
@@ -2390,7 +2468,7 @@ int partition_sum(const ModelView& m, const float* reps, const TopkScan& sc, con
     const uint32_t utiles = (sc.n + 127) / 128;
     uint32_t per = 0;
     const uint32_t groups = split_items(m.num_items, wanted_groups((256u * 2u * 2u + utiles - 1) / utiles), UINT32_MAX, UINT32_MAX, &per);
-    const uint32_t fb = sbr_softmax_fbits(m.num_items);
+    const uint32_t fb = sbr_softmax_fbits(pt.num_items ? pt.num_items : m.num_items);
     const dim3 grid(utiles, groups);
     DISPATCH_D(m.d, {
         if (sc.f.tags)
@@ -2544,6 +2622,27 @@ int launch_top_trim(const AboveScan& sc, const TopSelect& ts, uint32_t r0, uint3
     hipLaunchKernelGGL(top_trim_kernel, dim3(nr), dim3(256), 0, s, in_ids, in_scores, in_cap, sc.offsets + (size_t)r0 * sc.groups, sc.groups,
                        sc.totals + r0, ts.cuts + r0, ts.keep_eq + r0, ts.out_off, out_ids, out_scores, out_cap, sc.overrun_flag);
     return 2;
+}
+
+int launch_subset_words(const uint32_t* subset, uint32_t num_subset, const uint32_t* src, uint32_t* dst, hipStream_t s) {
+    if (num_subset == 0) return 0;
+    hipLaunchKernelGGL(subset_words_kernel, dim3((num_subset + 255) / 256), dim3(256), 0, s, subset, num_subset, src, dst);
+    return 1;
+}
+
+int launch_subset_positions(const uint32_t* subset, uint32_t num_subset, const uint64_t* eptr, uint32_t n, uint32_t* excl, hipStream_t s) {
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(subset_positions_kernel, dim3((n + 3) / 4), dim3(256), 0, s, subset, num_subset, eptr, n, excl);
+    return 1;
+}
+
+int launch_subset_gather(const ModelView& m, const uint32_t* subset, uint32_t num_subset, float* Esub, float* bsub, hipStream_t s) {
+    if (num_subset == 0) return 0;
+    DISPATCH_D(m.d, {
+        hipLaunchKernelGGL((subset_gather_kernel<DD>), dim3((unsigned)(((uint64_t)num_subset * (DD / 4) + 255) / 256)), dim3(256), 0, s, m, subset,
+                           num_subset, Esub, bsub);
+    });
+    return 1;
 }
 
 int launch_above_ids(const uint32_t* row_ids, uint32_t* ids, uint64_t n, hipStream_t s) {

@@ -4264,6 +4264,18 @@ bool partition_args(float temperature, uint64_t n, float* out_shift, uint64_t* o
 }  // namespace
 }  // extern "C"
 
+/* An item set (ITEM SETS in include/sbr_hip.h): the sorted, unique ids S and a persistent device copy of their rows, E'[j] = E[S[j]]
+ * and b'[j] = b[S[j]] at storage width, gathered by subset_gather_kernel at creation and by every refresh — plain device memory, not
+ * the arena, so no launch gathers it again.  Bound to the model's parameter generation as a session store is.  Tags and groups are
+ * not cached: they have no generation, and every launch gathers the set's words into the arena. */
+struct sbr_item_set {
+    sbr_model* m = nullptr;
+    uint64_t gen = 0;           /* the model's param_gen the rows were gathered under */
+    std::vector<uint32_t> ids;  /* S */
+    uint32_t* d_ids = nullptr;  /* all three null for an empty set */
+    float *E = nullptr, *b = nullptr;
+};
+
 namespace {
 
 /* device blocks of one call or chunk outside the eval arena (which does not outlive a carve); given back once the stream is idle */
@@ -4455,6 +4467,7 @@ struct ScanVariant {
     const Partition* pt = nullptr;
     Above* ab = nullptr;
     const Capped* cp = nullptr;
+    const sbr_item_set* set = nullptr; /* the scan runs over the set's resident sub-table; not with item rows or a subset */
     static ScanVariant of(const Diverse* dv, const TagFilterArg* flt, const Sample* sm = nullptr, const Partition* pt = nullptr) {
         ScanVariant v;
         v.dv = dv; v.flt = flt; v.sm = sm; v.pt = pt;
@@ -4481,7 +4494,12 @@ struct ScanVariant {
  * above_chunk's count and fill over the same representations, exclusion CSR and masks; out_items / out_scores are unused (null).
  * With v.cp (recommend_capped; the model's item groups set; not with item rows, a subset, v.dv, v.sm, v.pt or v.ab) the scan's rows
  * are the users' pools: the same launch keeps v.cp->k_out of each under the group cap, the results are num_users x v.cp->k_out and
- * v.cp->out_complete the rows' flags. */
+ * v.cp->out_complete the rows' flags.
+ * With v.set (an item set, current; not with item rows or v.subset) every form above scans the set's resident sub-table where it
+ * scans the catalogue: the exclusion CSR — uploaded, or made by session_seen_lists_kernel — is turned into positions of the set on
+ * the device (subset_positions_kernel), the tag and group words of the set are gathered into the arena per launch, the noise is
+ * hashed from the catalogue ids, F is the model's, and what leaves is catalogue ids.  An empty set answers on the host as a row that
+ * may see nothing. */
 sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, uint32_t k, uint32_t* out_items, float* out_scores,
                           const ScanVariant& v = ScanVariant()) {
     const Diverse* dv = v.dv;
@@ -4495,10 +4513,33 @@ sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, 
     if (ab && (s.item_rows || v.subset || dv || sm || pt || k != 1)) return SBR_ERR_INVALID_ARGUMENT;
     const Capped* cp = v.cp;
     if (cp && (!m->item_groups || s.item_rows || v.subset || dv || sm || pt || ab)) return SBR_ERR_INVALID_ARGUMENT;
+    const sbr_item_set* set = v.set;
+    if (set && (s.item_rows || v.subset)) return SBR_ERR_INVALID_ARGUMENT;
+    if (set && set->ids.empty()) { /* nothing to scan: every row is one that may see nothing */
+        const size_t ko = dv ? dv->k_out : cp ? cp->k_out : k;
+        if (out_items) std::fill(out_items, out_items + num_users * ko, 0xFFFFFFFFu);
+        if (out_scores) std::fill(out_scores, out_scores + num_users * ko, -INFINITY);
+        if (sm && sm->out_keys) std::fill(sm->out_keys, sm->out_keys + num_users * ko, -INFINITY);
+        if (cp && cp->out_complete) std::fill(cp->out_complete, cp->out_complete + num_users, (uint8_t)1); /* the pool held every eligible item */
+        for (uint64_t u = 0; u < num_users; ++u) {
+            if (pt) { pt->out_shift[u] = -INFINITY; pt->out_mass[u] = 0; }
+            if (ab) {
+                ab->out_counts[u] = 0;
+                if (ab->n) ab->out_cuts[u] = ab->n[u] ? -INFINITY : INFINITY;
+            }
+        }
+        return SBR_OK;
+    }
     const size_t seen_w = s.seen ? s.seen->w : 0;
     std::vector<uint64_t> users(num_users);
     for (uint64_t u = 0; u < num_users; ++u) users[u] = u;
-    const uint32_t scanned_items = v.subset ? (uint32_t)v.subset->size() : (uint32_t)m->hp.num_items;
+    const uint32_t scanned_items = set ? (uint32_t)set->ids.size() : v.subset ? (uint32_t)v.subset->size() : (uint32_t)m->hp.num_items;
+    sbr::ModelView cat = m->mv; /* what the launches scan: the catalogue, or the set's sub-table, whose item j is S[j] */
+    if (set) {
+        cat.E = set->E;
+        cat.b = set->b;
+        cat.num_items = scanned_items;
+    }
     const size_t cap = recommend_users_cap(scanned_items, k);
     for (Chunk ch; next_chunk(users, cap, s, m->hp.max_sequence_length, &ch);) {
         const size_t nu = ch.users.size();
@@ -4514,8 +4555,11 @@ sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, 
         float* pt_shift = nullptr; /* pt: the rows' shifts and masses */
         unsigned long long* pt_mass = nullptr;
         AboveBufs abufs{};
+        uint32_t *set_tags = nullptr, *set_groups = nullptr; /* set: its tag / group words, gathered by this launch */
         SBRCHK(user_reps(m, s, ch.users, [&](DeviceArena& ar) {
             tb.carve(ar, scanned_items, nu, nu * seen_w + ur.b.list_items.size(), k, v.flt != nullptr);
+            if (set && v.flt) set_tags = ar.take<uint32_t>(scanned_items);
+            if (set && cp) set_groups = ar.take<uint32_t>(scanned_items);
             if (s.seen) {
                 seen_slot = ar.take<uint32_t>(nu);
                 seen_caller = ar.take<uint32_t>(ur.b.list_items.size() + 1);
@@ -4574,38 +4618,52 @@ sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, 
             }
             HIPCHK(hipMemcpyAsync(smb.streams, streams.data(), nu * 8, hipMemcpyHostToDevice, m->stream));
         }
+        const uint32_t* tags = !v.flt ? nullptr : set ? set_tags : m->item_tags;
+        /* what every form runs ahead of its scan: the seen lists, and for a set the lists as positions and its words */
+        auto prelaunch = [&]() -> int {
+            int n = s.seen ? sbr::launch_session_seen_lists(*s.seen, seen_slot, (int)nu, tb.eptr, seen_caller, tb.excl, m->stream) : 0;
+            if (!set) return n;
+            if (excl) n += sbr::launch_subset_positions(set->d_ids, scanned_items, tb.eptr, (uint32_t)nu, tb.excl, m->stream);
+            if (v.flt) n += sbr::launch_subset_words(set->d_ids, scanned_items, m->item_tags, set_tags, m->stream);
+            if (cp) n += sbr::launch_subset_words(set->d_ids, scanned_items, m->item_groups, set_groups, m->stream);
+            return n;
+        };
         if (ab) { /* the chunk's rows are the call's [ch.c0, ch.c1): every user is one unit */
             sbr::AboveScan as{};
             as.rep_row = tb.rep; as.n = (uint32_t)nu; as.thresholds = abufs.th;
             as.excl_ptr = excl ? tb.eptr : nullptr; as.excl_items = tb.excl;
-            as.f = sbr::TagMasks{v.flt ? m->item_tags : nullptr, tb.any_of, tb.none_of};
+            as.f = sbr::TagMasks{tags, tb.any_of, tb.none_of};
             as.groups = abufs.groups; as.per = abufs.per;
             as.counts = abufs.counts; as.offsets = abufs.offsets; as.totals = abufs.totals;
             as.nonfinite_flag = tb.flag; as.overrun_flag = abufs.over;
-            SBRCHK(above_chunk(m, m->mv, ur.H, nullptr, as, abufs.ts, nullptr, ch.c0, ab, [&] {
-                return s.seen ? sbr::launch_session_seen_lists(*s.seen, seen_slot, (int)nu, tb.eptr, seen_caller, tb.excl, m->stream) : 0;
-            }));
+            SBRCHK(above_chunk(m, cat, ur.H, nullptr, as, abufs.ts, set ? set->d_ids : nullptr, ch.c0, ab, prelaunch));
             continue;
         }
         const size_t ko = dv ? dv->k_out : cp ? cp->k_out : k; /* the width of the rows that leave */
         /* the selection reads the pool's scores whether or not the caller wants any; a sampled scan's are its keys */
-        sbr::TopkScan sc = tb.scan(nu, k, excl, out_scores || dv || sm || pt, v.flt ? m->item_tags : nullptr);
+        sbr::TopkScan sc = tb.scan(nu, k, excl, out_scores || dv || sm || pt, tags);
         if (sm) sc.g = sbr::SampleNoise{sm->inv_t, smb.keys};
         SBRCHK(scan_launch(m, tb.flag, [&] {
-            int n = s.seen ? sbr::launch_session_seen_lists(*s.seen, seen_slot, (int)nu, tb.eptr, seen_caller, tb.excl, m->stream) : 0;
-            if (pt) n += sbr::launch_log_partition(m->mv, ur.H, sc, sbr::PartitionScan{pt->inv_t, pt_shift, pt_mass}, m->stream);
+            int n = prelaunch();
+            /* a set's mass is held to the model's F, and its noise to the catalogue ids, which also leave in the positions' place */
+            if (pt)
+                n += sbr::launch_log_partition(cat, ur.H, sc, sbr::PartitionScan{pt->inv_t, pt_shift, pt_mass, set ? (uint32_t)m->hp.num_items : 0u},
+                                               m->stream);
             else if (sm)
-                n += sbr::launch_recommend_sampled(m->mv, ur.H, sc, sbr::SampleScan{sm->seed, smb.streams, smb.pair_row, smb.pair_item, smb.plain},
-                                                   m->stream);
+                n += sbr::launch_recommend_sampled(cat, ur.H, sc, sbr::SampleScan{sm->seed, smb.streams, smb.pair_row, smb.pair_item, smb.plain,
+                                                                                  set ? set->d_ids : nullptr}, m->stream);
+            else if (set) n += sbr::launch_recommend(cat, ur.H, sc, m->stream);
             else if (v.subset) n += sbr::launch_recommend_among(m->mv, sb.ids, scanned_items, sb.E, sb.b, ur.H, sc, m->stream);
             else if (s.item_rows) n += sbr::launch_similar_items(m->mv, ur.d_item_rows, v.cosine, rnorm, ur.H, sc, m->stream);
             else n += sbr::launch_recommend(m->mv, ur.H, sc, m->stream);
             if (dv)
-                n += sbr::launch_diverse_select(m->mv, tb.items, tb.scores, (uint32_t)nu, k, dv->k_out, dv->trade_off, dv->metric == SBR_SIMILAR_COSINE,
+                n += sbr::launch_diverse_select(cat, tb.items, tb.scores, (uint32_t)nu, k, dv->k_out, dv->trade_off, dv->metric == SBR_SIMILAR_COSINE,
                                                 dv_items, out_scores ? dv_scores : nullptr, tb.flag, m->stream);
             if (cp)
-                n += sbr::launch_capped_select(m->item_groups, (uint32_t)m->hp.num_items, tb.items, sc.out_scores, (uint32_t)nu, k, cp->k_out,
-                                               cp->cap, dv_items, out_scores ? dv_scores : nullptr, cp_complete, m->stream);
+                n += sbr::launch_capped_select(set ? set_groups : m->item_groups, scanned_items, tb.items, sc.out_scores, (uint32_t)nu, k,
+                                               cp->k_out, cp->cap, dv_items, out_scores ? dv_scores : nullptr, cp_complete, m->stream);
+            /* the selections ran on positions against the sub-table and the gathered words; the rows that leave become ids */
+            if (set && !pt && !sm) n += sbr::launch_above_ids(set->d_ids, dv || cp ? dv_items : tb.items, nu * ko, m->stream);
             return n;
         }, {{out_items ? out_items + ch.c0 * ko : nullptr, dv || cp ? dv_items : tb.items, nu * ko * 4},
             {cp && cp->out_complete ? cp->out_complete + ch.c0 : nullptr, cp_complete, nu},
@@ -5990,6 +6048,204 @@ sbr_status sbr_sessions_recommend_diverse_filtered(sbr_sessions* st, const uint3
     const TagFilterArg flt{any_of, none_of};
     const Diverse dv{k, trade_off, metric};
     return sessions_recommend_call(st, slots, n, pool, excl_ptr, excl_items, 0, out_items, out_scores, &flt, &dv);
+}
+
+/* ---------------------------------------------------------------------------------------------
+ * item sets: every catalogue call restricted to a resident sub-table (ITEM SETS in include/sbr_hip.h)
+ * ------------------------------------------------------------------------------------------- */
+namespace {
+
+/* S's rows into the set's device copy, and the set bound to the parameters they were read from (the caller holds the model's mutex) */
+sbr_status item_set_gather(sbr_item_set* set) {
+    sbr_model* m = set->m;
+    if (!set->ids.empty()) {
+        sbr::launch_subset_gather(m->mv, set->d_ids, (uint32_t)set->ids.size(), set->E, set->b, m->stream);
+        HIPCHK(hipGetLastError());
+    }
+    set->gen = m->param_gen;
+    return SBR_OK;
+}
+
+void item_set_free(sbr_item_set* set) {
+    dfree(set->d_ids); dfree(set->E); dfree(set->b);
+}
+
+/* entry of every scan through a set: enter_sessions' rule, for the rows the set holds */
+sbr_status enter_item_set(const sbr_item_set* set) {
+    SBRCHK(enter_reader(set->m));
+    return set->gen == set->m->param_gen && set->m->open_plans == 0 ? SBR_OK : SBR_ERR_INVALID_ARGUMENT;
+}
+
+/* One call through a set: r names exactly one source of rows, v the family (its set, filter and noise are filled in here), sm the
+ * noise of a sampled call (a store's default streams are its slots). */
+sbr_status item_set_scan(sbr_item_set* set, const sbr_scan_rows* r, uint64_t n, uint32_t k, uint32_t* out_items, float* out_scores,
+                         ScanVariant v, Sample* sm = nullptr) {
+    if (!set || !r) return SBR_ERR_INVALID_ARGUMENT;
+    if ((r->user_ptr != nullptr) + (r->reps != nullptr) + (r->store != nullptr) != 1) return SBR_ERR_INVALID_ARGUMENT;
+    if (n && !out_items && !v.pt && !v.ab) return SBR_ERR_INVALID_ARGUMENT;
+    sbr_model* m = set->m;
+    if (!scan_k_ok(m, k, v.dv, v.cp)) return SBR_ERR_INVALID_ARGUMENT;
+    TagFilterArg hold;
+    v.flt = sample_filter(r->any_of, r->none_of, &hold);
+    v.sm = sm;
+    v.set = set;
+    if (r->user_ptr) { /* histories: the lists are the histories themselves */
+        if (r->excl_ptr || r->excl_items || (r->flags & ~SBR_RECOMMEND_INCLUDE_HISTORY)) return SBR_ERR_INVALID_ARGUMENT;
+        std::lock_guard<std::mutex> lock(m->mu);
+        SBRCHK(enter_item_set(set));
+        SBRCHK(check_csr(m, r->user_ptr, n, r->item_ids, false));
+        return recommend_scan(m, RepSource::of_histories(r->user_ptr, r->item_ids, 0, !(r->flags & SBR_RECOMMEND_INCLUDE_HISTORY)), n, k, out_items,
+                              out_scores, v);
+    }
+    if (!excl_args_ok(r->excl_ptr, r->excl_items, n)) return SBR_ERR_INVALID_ARGUMENT;
+    if (r->reps) {
+        if (r->flags || r->item_ids || r->slots) return SBR_ERR_INVALID_ARGUMENT;
+        std::lock_guard<std::mutex> lock(m->mu);
+        SBRCHK(enter_item_set(set));
+        if (r->excl_ptr) SBRCHK(check_csr(m, r->excl_ptr, n, r->excl_items, false));
+        return recommend_scan(m, RepSource::of_rows(r->reps, r->excl_ptr, r->excl_items), n, k, out_items, out_scores, v);
+    }
+    sbr_sessions* st = r->store;
+    if (st->m != m || r->item_ids) return SBR_ERR_INVALID_ARGUMENT;
+    if (st->seen.w ? (r->flags & ~SBR_RECOMMEND_INCLUDE_HISTORY) != 0 : r->flags != 0) return SBR_ERR_INVALID_ARGUMENT;
+    std::lock_guard<std::mutex> lock(m->mu);
+    SBRCHK(enter_item_set(set));
+    SBRCHK(enter_sessions(st));
+    SBRCHK(check_slots(st, r->slots, n));
+    if (r->excl_ptr) SBRCHK(check_csr(m, r->excl_ptr, n, r->excl_items, false));
+    const std::vector<int> rows = session_rep_rows(st, r->slots, n);
+    const bool seen = st->seen.w && !(r->flags & SBR_RECOMMEND_INCLUDE_HISTORY);
+    if (sm) sm->fallback = r->slots;
+    return recommend_scan(m, RepSource::of_sessions(st, rows, r->excl_ptr, r->excl_items, seen ? r->slots : nullptr), n, k, out_items, out_scores, v);
+}
+
+}  // namespace
+
+sbr_status sbr_item_set_create(sbr_model* m, const uint32_t* item_ids, uint64_t n, sbr_item_set** out) {
+    if (!m || !out || (n && !item_ids)) return SBR_ERR_INVALID_ARGUMENT;
+    *out = nullptr;
+    for (uint64_t j = 0; j < n; ++j)
+        if (item_ids[j] >= m->hp.num_items) return SBR_ERR_INVALID_ARGUMENT;
+    std::lock_guard<std::mutex> lock(m->mu);
+    SBRCHK(enter_reader(m));
+    if (m->open_plans) return SBR_ERR_INVALID_ARGUMENT; /* rows gathered now would go stale with the plan's next step */
+    sbr_item_set* set = new (std::nothrow) sbr_item_set();
+    if (!set) return SBR_ERR_OUT_OF_MEMORY;
+    set->m = m;
+    set->ids.assign(item_ids, item_ids + n);
+    std::sort(set->ids.begin(), set->ids.end());
+    set->ids.erase(std::unique(set->ids.begin(), set->ids.end()), set->ids.end());
+    const size_t ns = set->ids.size();
+    sbr_status s = SBR_OK;
+    if (ns) {
+        s = dmalloc(&set->d_ids, ns);
+        if (s == SBR_OK) s = dmalloc(&set->E, ns * (size_t)m->d);
+        if (s == SBR_OK) s = dmalloc(&set->b, ns);
+        if (s == SBR_OK && hipMemcpy(set->d_ids, set->ids.data(), ns * 4, hipMemcpyHostToDevice) != hipSuccess) s = SBR_ERR_HIP;
+    }
+    if (s == SBR_OK) s = item_set_gather(set);
+    if (s != SBR_OK) {
+        hipStreamSynchronize(m->stream);
+        item_set_free(set);
+        delete set;
+        return s;
+    }
+    *out = set;
+    return SBR_OK;
+}
+
+void sbr_item_set_destroy(sbr_item_set* set) {
+    if (!set) return;
+    {
+        std::lock_guard<std::mutex> lock(set->m->mu);
+        hipSetDevice(set->m->device);
+        hipStreamSynchronize(set->m->stream); /* the rows go back to the scratch cache: nothing may still read them */
+        item_set_free(set);
+    }
+    delete set;
+}
+
+sbr_status sbr_item_set_size(const sbr_item_set* set, uint64_t* out) {
+    if (!set || !out) return SBR_ERR_INVALID_ARGUMENT;
+    *out = set->ids.size();
+    return SBR_OK;
+}
+
+sbr_status sbr_item_set_items(const sbr_item_set* set, uint32_t* out) {
+    if (!set || (!out && !set->ids.empty())) return SBR_ERR_INVALID_ARGUMENT;
+    if (!set->ids.empty()) std::memcpy(out, set->ids.data(), set->ids.size() * 4);
+    return SBR_OK;
+}
+
+sbr_status sbr_item_set_refresh(sbr_item_set* set) {
+    if (!set) return SBR_ERR_INVALID_ARGUMENT;
+    std::lock_guard<std::mutex> lock(set->m->mu);
+    SBRCHK(enter_reader(set->m));
+    if (set->m->open_plans) return SBR_ERR_INVALID_ARGUMENT;
+    return item_set_gather(set);
+}
+
+sbr_status sbr_item_set_recommend(sbr_item_set* set, const struct sbr_scan_rows* rows, uint64_t num_rows, uint32_t k, uint32_t* out_items,
+                                  float* out_scores) {
+    return item_set_scan(set, rows, num_rows, k, out_items, out_scores, ScanVariant());
+}
+
+sbr_status sbr_item_set_recommend_diverse(sbr_item_set* set, const struct sbr_scan_rows* rows, uint64_t num_rows, uint32_t k, uint32_t pool,
+                                          float trade_off, uint32_t metric, uint32_t* out_items, float* out_scores) {
+    const Diverse dv{k, trade_off, metric};
+    ScanVariant v;
+    v.dv = &dv;
+    return item_set_scan(set, rows, num_rows, pool, out_items, out_scores, v);
+}
+
+sbr_status sbr_item_set_recommend_sampled(sbr_item_set* set, const struct sbr_scan_rows* rows, uint64_t num_rows, uint32_t k,
+                                          const struct sbr_sample_args* sample, uint32_t* out_items, float* out_scores, float* out_keys) {
+    Sample sm;
+    if (!sample_args(sample, out_keys, &sm)) return SBR_ERR_INVALID_ARGUMENT;
+    return item_set_scan(set, rows, num_rows, k, out_items, out_scores, ScanVariant(), &sm);
+}
+
+sbr_status sbr_item_set_log_partition(sbr_item_set* set, const struct sbr_scan_rows* rows, uint64_t num_rows, float temperature, float* out_shift,
+                                      uint64_t* out_mass, uint32_t* out_frac_bits) {
+    Partition pt;
+    if (!set || !partition_args(temperature, num_rows, out_shift, out_mass, out_frac_bits, &pt)) return SBR_ERR_INVALID_ARGUMENT;
+    ScanVariant v;
+    v.pt = &pt;
+    const sbr_status r = item_set_scan(set, rows, num_rows, 1, nullptr, nullptr, v);
+    if (r == SBR_OK) *out_frac_bits = sbr_softmax_fbits((uint32_t)set->m->hp.num_items); /* the model's, not the set's */
+    return r;
+}
+
+sbr_status sbr_item_set_recommend_above(sbr_item_set* set, const struct sbr_scan_rows* rows, uint64_t num_rows, const float* thresholds,
+                                        uint64_t* out_counts, uint64_t* out_total, uint64_t capacity, uint32_t* out_ids, float* out_scores) {
+    Above ab;
+    if (!above_args(thresholds, num_rows, out_counts, out_total, capacity, out_ids, out_scores, &ab)) return SBR_ERR_INVALID_ARGUMENT;
+    ScanVariant v;
+    v.ab = &ab;
+    SBRCHK(item_set_scan(set, rows, num_rows, 1, nullptr, nullptr, v));
+    *out_total = ab.total;
+    return SBR_OK;
+}
+
+sbr_status sbr_item_set_recommend_top(sbr_item_set* set, const struct sbr_scan_rows* rows, uint64_t num_rows, const uint64_t* n, float* out_cuts,
+                                      uint64_t* out_counts, uint64_t* out_total, uint64_t capacity, uint32_t* out_ids, float* out_scores) {
+    Above ab;
+    if (!top_args(n, num_rows, out_cuts, out_counts, out_total, capacity, out_ids, out_scores, &ab)) return SBR_ERR_INVALID_ARGUMENT;
+    ScanVariant v;
+    v.ab = &ab;
+    SBRCHK(item_set_scan(set, rows, num_rows, 1, nullptr, nullptr, v));
+    *out_total = ab.total;
+    return SBR_OK;
+}
+
+sbr_status sbr_item_set_recommend_capped(sbr_item_set* set, const struct sbr_scan_rows* rows, uint64_t num_rows, uint32_t k,
+                                         const struct sbr_cap_args* cap, uint32_t* out_items, float* out_scores, uint8_t* out_complete) {
+    Capped cp;
+    uint32_t pool = 0;
+    if (!capped_args(cap, k, out_complete, &cp, &pool)) return SBR_ERR_INVALID_ARGUMENT;
+    ScanVariant v;
+    v.cp = &cp;
+    return item_set_scan(set, rows, num_rows, pool, out_items, out_scores, v);
 }
 
 sbr_status sbr_sessions_score_candidates(sbr_sessions* st, const uint32_t* slots, uint64_t n, const uint64_t* cand_ptr,

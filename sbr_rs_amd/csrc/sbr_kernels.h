@@ -333,6 +333,8 @@ struct SampleScan {
     const uint64_t* streams;
     uint32_t *pair_row, *pair_item;
     float* plain;
+    const uint32_t* ids = nullptr; /* an item set's scan (m: its sub-table): [m.num_items] ascending, the catalogue id of scanned row
+                                      j — the noise is hashed from it (GumbelMapped) and the rows leave as ids; null: m's own rows */
 };
 int launch_recommend_sampled(const ModelView& m, const float* reps, const TopkScan& sc, const SampleScan& sp, hipStream_t s);
 /* the exact fixed-point mass of softmax(score / T) per scan row (sbr_catalogue.hip; the contract: PARTITION in include/sbr_hip.h):
@@ -345,6 +347,8 @@ struct PartitionScan {
     float inv_t;
     float* shift;
     unsigned long long* mass;
+    uint32_t num_items = 0; /* what F is taken from: an item set's scan names its MODEL's items here, so that the mass is the plain
+                               call's integer; 0: the scanned catalogue's */
 };
 int launch_log_partition(const ModelView& m, const float* reps, const TopkScan& sc, const PartitionScan& pt, hipStream_t s);
 /* sequence_partition (sbr_catalogue.hip; the contract: SEQUENCE PARTITION in include/sbr_hip.h): launch_log_partition's shift and
@@ -428,6 +432,14 @@ struct TopSelect {
 int launch_top_select(const ModelView& cat, const float* reps, const float* qb, const AboveScan& sc, const TopSelect& ts, hipStream_t s);
 int launch_top_trim(const AboveScan& sc, const TopSelect& ts, uint32_t r0, uint32_t nr, const uint32_t* in_ids, const float* in_scores,
                     uint32_t in_cap, uint32_t* out_ids, float* out_scores, uint32_t out_cap, hipStream_t s);
+/* An item set S (sorted, unique ids, device) beside launch_recommend_among's sub-table, which launch_subset_gather makes once:
+ * launch_subset_words: dst[j] = src[S[j]], the set's tag or group words, per launch.
+ * launch_subset_positions: the exclusion CSR eptr / excl of n segments (non-decreasing catalogue ids, repeats and a 0xFFFFFFFF tail
+ *   allowed — an uploaded CSR or launch_session_seen_lists' output) becomes, in place, the same segments in positions of S: entries
+ *   outside S dropped, repeats kept, the tail refilled; eptr is unchanged.  One launch each (0 where there is nothing to do). */
+int launch_subset_words(const uint32_t* subset, uint32_t num_subset, const uint32_t* src, uint32_t* dst, hipStream_t s);
+int launch_subset_positions(const uint32_t* subset, uint32_t num_subset, const uint64_t* eptr, uint32_t n, uint32_t* excl, hipStream_t s);
+int launch_subset_gather(const ModelView& m, const uint32_t* subset, uint32_t num_subset, float* Esub, float* bsub, hipStream_t s);
 /* ids[e] = row_ids[ids[e]] for the n entries a fill wrote (audience: positions in the candidate table -> the ids they stand for) */
 int launch_above_ids(const uint32_t* row_ids, uint32_t* ids, uint64_t n, hipStream_t s);
 /* greedy maximal-marginal-relevance selection (sbr_catalogue.hip, diverse_select_kernel; the contract: sbr_recommend_diverse in

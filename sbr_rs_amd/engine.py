@@ -9,7 +9,7 @@ import numpy as np
 
 from . import _lib
 from ._abi import NUM_KERNEL_FAMILIES, KernelFamily, SbrHparams, Status, storage_dim
-from .errors import EngineError, FittingError, PredictionError
+from .errors import EngineError, FittingError, InvalidArgument, PredictionError
 
 
 RECOMMEND_MAX_K = 1024  # SBR_RECOMMEND_MAX_K
@@ -1477,6 +1477,11 @@ class Model:
         recommend / recommend_diverse exclude them."""
         return Sessions(self, capacity, remember)
 
+    def item_set(self, item_ids) -> "ItemSet":
+        """An item set of this model (sbr_item_set_create; ``ItemSet``): ``item_ids`` in any order, duplicates allowed, each below
+        num_items.  Its rows are gathered to the device once; every catalogue call is then offered restricted to the set."""
+        return ItemSet(self, item_ids)
+
     def load_sessions(self, path, capacity=None, remember=None, replay: bool = False) -> "Sessions":
         """A store of this model restored from a file written by ``Sessions.save`` (``persistence.load_sessions``)."""
         from .persistence import load_sessions
@@ -1485,7 +1490,7 @@ class Model:
 
     def close(self):
         if getattr(self, "_h", None):
-            for st in list(getattr(self, "_stores", ())):  # stores are destroyed before their model
+            for st in list(getattr(self, "_stores", ())):  # stores and item sets are destroyed before their model
                 st.close()
             self._L.sbr_model_destroy(self._h)
             self._h = None
@@ -1885,6 +1890,309 @@ class Sessions:
             self.close()
         except Exception:
             pass
+
+
+class _ScanRows:
+    """The rows of one call through an ItemSet: the sbr_scan_rows descriptor, the number of rows, the arrays it points into (kept
+    alive here) and ``take(rows)``, the same source restricted to some rows of the call (recommend_capped's completion)."""
+
+    def __init__(self, desc, n: int, keep, take):
+        self.desc, self.n, self._keep, self.take = desc, n, keep, take
+
+
+def _scan_rows(n: int, masks, ep, ei, keep, take, **fields):
+    from ._abi import SbrScanRows
+
+    d = SbrScanRows()
+    for name, value in fields.items():
+        setattr(d, name, value)
+    if ep is not None:
+        d.excl_ptr, d.excl_items = ep.ctypes.data, ei.ctypes.data
+    if masks is not None:
+        d.any_of, d.none_of = masks[0].ctypes.data, masks[1].ctypes.data
+    return _ScanRows(d, n, (keep, masks, ep, ei), take)
+
+
+class ItemSet:
+    """An item set of a model (sbr_item_set_*; ``Model.item_set(item_ids)``): the sorted unique ids ``items`` and a device copy
+    of their embedding rows and biases, gathered once, so that every catalogue call restricted to the set costs what the set
+    costs, not what the catalogue does.  Every method returns, bit for bit, what the model's method of the same name returns
+    with every item outside the set added to each row's exclusions — catalogue ids, predict's score bits, the same noise per
+    (seed, stream, item), the model's ``frac_bits``.  Histories, ``exclude`` lists and a session's seen items stay catalogue
+    ids; entries outside the set are ignored.  After the model's parameters change (fit, set_param, load) every call raises
+    (``errors.InvalidArgument``, a ValueError) until ``refresh()`` gathers the rows again, and likewise while a fit plan is
+    open; ``set_item_tags`` / ``set_item_groups`` take effect without one.  An empty set is legal.  ``on(store)`` gives the
+    session store's scan methods through the set.  The object keeps its model alive; ``Model.close`` closes its sets first."""
+
+    def __init__(self, model: "Model", item_ids):
+        self.model = model
+        self._L = _lib.load()
+        ids = np.ascontiguousarray(np.asarray(item_ids, dtype=np.int64).ravel())
+        if ids.size and (ids.min() < 0 or ids.max() >= int(model.hp.num_items)):
+            raise ValueError(f"item_set: ids must be below num_items = {int(model.hp.num_items)}")
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        h = C.c_void_p()
+        self._h = None
+        self._check(self._L.sbr_item_set_create(model._h, _ptr(ids) if ids.size else None, ids.size, C.byref(h)))
+        self._h = h
+        if not hasattr(model, "_stores"):
+            model._stores = weakref.WeakSet()
+        model._stores.add(self)
+
+    @staticmethod
+    def _check(st: int):
+        if st == Status.INVALID_ARGUMENT:
+            raise InvalidArgument(Status(st), _lib.load().sbr_status_string(st).decode())
+        _check(st)
+
+    @property
+    def size(self) -> int:
+        n = C.c_uint64()
+        self._check(self._L.sbr_item_set_size(self._h, C.byref(n)))
+        return n.value
+
+    def __len__(self) -> int:
+        return self.size
+
+    @property
+    def items(self) -> np.ndarray:
+        """The set's ids, sorted and unique (u32)."""
+        out = np.zeros(max(self.size, 1), dtype=np.uint32)
+        self._check(self._L.sbr_item_set_items(self._h, _ptr(out)))
+        return out[: self.size]
+
+    def refresh(self):
+        """Gathers the set's rows again from the model's current parameters (sbr_item_set_refresh)."""
+        self._check(self._L.sbr_item_set_refresh(self._h))
+        return self
+
+    def on(self, store: "Sessions") -> "ItemSetSessions":
+        """The scan methods of a session store of this set's model, through the set."""
+        return ItemSetSessions(self, store)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.sbr_item_set_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # ---- the sources of rows ----
+    def _hist(self, user_ptr, item_ids, include_history, any_of, none_of) -> _ScanRows:
+        up = np.ascontiguousarray(user_ptr, dtype=np.uint64)
+        it = np.ascontiguousarray(item_ids, dtype=np.uint32)
+        if it.size == 0:
+            it = np.zeros(1, dtype=np.uint32)
+        nu = max(len(up) - 1, 0)
+        masks = _tag_masks(any_of, none_of, nu)
+
+        def take(rows):
+            sp = np.zeros(rows.size + 1, dtype=np.uint64)
+            sp[1:] = np.cumsum((up[rows + 1] - up[rows]).astype(np.int64))
+            si = np.concatenate([it[int(up[r]) : int(up[r + 1])] for r in rows]) if rows.size else np.zeros(0, np.uint32)
+            return self._hist(sp, si, include_history, None if masks is None else masks[0][rows], None if masks is None else masks[1][rows])
+
+        return _scan_rows(nu, masks, None, None, (up, it), take, user_ptr=up.ctypes.data, item_ids=it.ctypes.data,
+                          flags=RECOMMEND_INCLUDE_HISTORY if include_history else 0)
+
+    def _reps(self, reps, exclude, any_of, none_of) -> _ScanRows:
+        reps = np.ascontiguousarray(reps, dtype=np.float32).reshape(-1, self.model.dim)
+        nu = reps.shape[0]
+        masks = _tag_masks(any_of, none_of, nu)
+        ep, ei = _exclusion_csr(exclude, nu)
+        buf = reps if nu else np.zeros((1, self.model.dim), dtype=np.float32)
+
+        def take(rows):
+            return self._reps(reps[rows], None if exclude is None else [exclude[int(r)] for r in rows],
+                              None if masks is None else masks[0][rows], None if masks is None else masks[1][rows])
+
+        return _scan_rows(nu, masks, ep, ei, buf, take, reps=buf.ctypes.data)
+
+    def _store(self, store, slots, exclude, any_of, none_of, include_seen) -> _ScanRows:
+        if include_seen and not store._seen:
+            raise ValueError("include_seen: this store has no seen-item memory (sessions(capacity, remember=W))")
+        sl = Sessions._slots(slots)
+        masks = _tag_masks(any_of, none_of, sl.size)
+        ep, ei = _exclusion_csr(exclude, sl.size)
+        buf = sl if sl.size else np.zeros(1, dtype=np.uint32)
+
+        def take(rows):
+            return self._store(store, sl[rows], None if exclude is None else [exclude[int(r)] for r in rows],
+                               None if masks is None else masks[0][rows], None if masks is None else masks[1][rows], include_seen)
+
+        return _scan_rows(sl.size, masks, ep, ei, (store, buf), take, store=store._h.value, slots=buf.ctypes.data,
+                          flags=RECOMMEND_INCLUDE_HISTORY if include_seen else 0)
+
+    # ---- the families, over any source ----
+    def _recommend(self, src: _ScanRows, k: int):
+        items = np.zeros((src.n, max(int(k), 0)), dtype=np.uint32)
+        scores = np.zeros((src.n, max(int(k), 0)), dtype=np.float32)
+        self._check(self._L.sbr_item_set_recommend(self._h, C.byref(src.desc), src.n, int(k) & 0xFFFFFFFF, _ptr(items), _ptr(scores)))
+        return items, scores
+
+    def _diverse(self, src: _ScanRows, k: int, pool: int, trade_off, metric):
+        items = np.zeros((src.n, max(int(k), 0)), dtype=np.uint32)
+        scores = np.zeros((src.n, max(int(k), 0)), dtype=np.float32)
+        self._check(self._L.sbr_item_set_recommend_diverse(self._h, C.byref(src.desc), src.n, int(k) & 0xFFFFFFFF, int(pool) & 0xFFFFFFFF,
+                                                           float(trade_off), _similar_metric(metric), _ptr(items), _ptr(scores)))
+        return items, scores
+
+    def _log_partition(self, src: _ScanRows, temperature) -> Partition:
+        shift, mass, fb = _partition_outputs(src.n)
+        self._check(self._L.sbr_item_set_log_partition(self._h, C.byref(src.desc), src.n, float(np.float32(temperature)), _ptr(shift),
+                                                       _ptr(mass), C.byref(fb)))
+        return Partition(temperature, shift, mass, fb.value)
+
+    def _sampled(self, src: _ScanRows, k: int, temperature, seed, streams, log_prob: bool):
+        sa, _keep = _sample_args(temperature, seed, streams, src.n)
+        items, scores, keys = (np.zeros((src.n, max(int(k), 0)), dtype=dt) for dt in (np.uint32, np.float32, np.float32))
+        self._check(self._L.sbr_item_set_recommend_sampled(self._h, C.byref(src.desc), src.n, int(k) & 0xFFFFFFFF, C.byref(sa), _ptr(items),
+                                                           _ptr(scores), _ptr(keys)))
+        if log_prob:  # the draws' propensities: the set's own log_partition of the same rows
+            return items, scores, keys, self._log_partition(src, temperature).slate_log_prob(scores)
+        return items, scores, keys
+
+    def _above(self, src: _ScanRows, threshold, max_results, order, count_only, n=None):
+        def call(*out):  # the set's own check raises; _above's then sees OK
+            self._check((self._L.sbr_item_set_recommend_above if n is None else self._L.sbr_item_set_recommend_top)(
+                self._h, C.byref(src.desc), src.n, *out))
+            return int(Status.OK)
+
+        return _above(call, src.n, threshold, max_results, order, count_only, n)
+
+    def _capped(self, src: _ScanRows, k: int, cap: int, pool, exact: bool):
+        ca, pool = _cap_args(k, cap, pool)
+        items, scores = np.zeros((src.n, int(k)), dtype=np.uint32), np.zeros((src.n, int(k)), dtype=np.float32)
+        flags_out = np.zeros(max(src.n, 1), dtype=np.uint8)
+        self._check(self._L.sbr_item_set_recommend_capped(self._h, C.byref(src.desc), src.n, int(k), C.byref(ca), _ptr(items), _ptr(scores),
+                                                          _ptr(flags_out)))
+        complete = flags_out[: src.n].astype(bool)
+        if exact and not complete.all():  # short rows are finished with the set's own recommend_top
+            groups = getattr(self.model, "_groups", None)
+            capped_complete(lambda rows, n: self._above(src.take(rows), None, None, "score", False, n), items, scores, complete,
+                            self.model.item_groups() if groups is None else groups, int(cap), int(k), pool, max(self.size, 1))
+        return items, scores, complete
+
+    # ---- histories: Model's methods of the same names ----
+    def recommend(self, user_ptr, item_ids, k: int, include_history: bool = False, any_of=None, none_of=None):
+        """``Model.recommend`` within the set (sbr_item_set_recommend)."""
+        return self._recommend(self._hist(user_ptr, item_ids, include_history, any_of, none_of), k)
+
+    def recommend_sampled(self, user_ptr, item_ids, k: int, temperature: float = 1.0, seed: int = 0, streams=None,
+                          include_history: bool = False, any_of=None, none_of=None, log_prob: bool = False):
+        """``Model.recommend_sampled`` within the set: the same (seed, stream) draws what the model draws with the set's complement
+        excluded.  ``log_prob=True`` goes through the set's own ``log_partition``."""
+        return self._sampled(self._hist(user_ptr, item_ids, include_history, any_of, none_of), k, temperature, seed, streams, log_prob)
+
+    def log_partition(self, user_ptr, item_ids, temperature: float = 1.0, include_history: bool = False, any_of=None,
+                      none_of=None) -> Partition:
+        """``Model.log_partition`` within the set; ``frac_bits`` is the model's."""
+        return self._log_partition(self._hist(user_ptr, item_ids, include_history, any_of, none_of), temperature)
+
+    def recommend_above(self, user_ptr, item_ids, threshold, include_history: bool = False, any_of=None, none_of=None,
+                        max_results=None, order: str = "score") -> Above:
+        """``Model.recommend_above`` within the set."""
+        return self._above(self._hist(user_ptr, item_ids, include_history, any_of, none_of), threshold, max_results, order, False)
+
+    def count_above(self, user_ptr, item_ids, threshold, include_history: bool = False, any_of=None, none_of=None) -> np.ndarray:
+        return self._above(self._hist(user_ptr, item_ids, include_history, any_of, none_of), threshold, None, "id", True)
+
+    def recommend_top(self, user_ptr, item_ids, n, include_history: bool = False, any_of=None, none_of=None, max_results=None,
+                      order: str = "score") -> Above:
+        """``Model.recommend_top`` within the set."""
+        return self._above(self._hist(user_ptr, item_ids, include_history, any_of, none_of), None, max_results, order, False, n)
+
+    def nth_score(self, user_ptr, item_ids, n, include_history: bool = False, any_of=None, none_of=None):
+        return self._above(self._hist(user_ptr, item_ids, include_history, any_of, none_of), None, None, "id", True, n)
+
+    def recommend_capped(self, user_ptr, item_ids, k: int, cap: int = 1, pool=None, include_history: bool = False, any_of=None,
+                         none_of=None, exact: bool = True):
+        """``Model.recommend_capped`` within the set; ``exact=True`` finishes short rows with the set's ``recommend_top``."""
+        return self._capped(self._hist(user_ptr, item_ids, include_history, any_of, none_of), k, cap, pool, exact)
+
+    def recommend_diverse(self, user_ptr, item_ids, k: int, pool: int, trade_off: float = 0.5, metric="cosine",
+                          include_history: bool = False, any_of=None, none_of=None):
+        """``Model.recommend_diverse`` within the set: the pool is the set's ``recommend`` row."""
+        return self._diverse(self._hist(user_ptr, item_ids, include_history, any_of, none_of), k, pool, trade_off, metric)
+
+    # ---- representations ----
+    def recommend_reps(self, reps, k: int, exclude=None, any_of=None, none_of=None):
+        return self._recommend(self._reps(reps, exclude, any_of, none_of), k)
+
+    def recommend_sampled_reps(self, reps, k: int, temperature: float = 1.0, seed: int = 0, streams=None, exclude=None, any_of=None,
+                               none_of=None, log_prob: bool = False):
+        return self._sampled(self._reps(reps, exclude, any_of, none_of), k, temperature, seed, streams, log_prob)
+
+    def log_partition_reps(self, reps, temperature: float = 1.0, exclude=None, any_of=None, none_of=None) -> Partition:
+        return self._log_partition(self._reps(reps, exclude, any_of, none_of), temperature)
+
+    def recommend_above_reps(self, reps, threshold, exclude=None, any_of=None, none_of=None, max_results=None,
+                             order: str = "score") -> Above:
+        return self._above(self._reps(reps, exclude, any_of, none_of), threshold, max_results, order, False)
+
+    def count_above_reps(self, reps, threshold, exclude=None, any_of=None, none_of=None) -> np.ndarray:
+        return self._above(self._reps(reps, exclude, any_of, none_of), threshold, None, "id", True)
+
+    def recommend_top_reps(self, reps, n, exclude=None, any_of=None, none_of=None, max_results=None, order: str = "score") -> Above:
+        return self._above(self._reps(reps, exclude, any_of, none_of), None, max_results, order, False, n)
+
+    def nth_score_reps(self, reps, n, exclude=None, any_of=None, none_of=None):
+        return self._above(self._reps(reps, exclude, any_of, none_of), None, None, "id", True, n)
+
+    def recommend_capped_reps(self, reps, k: int, cap: int = 1, pool=None, exclude=None, any_of=None, none_of=None, exact: bool = True):
+        return self._capped(self._reps(reps, exclude, any_of, none_of), k, cap, pool, exact)
+
+    def recommend_diverse_reps(self, reps, k: int, pool: int, trade_off: float = 0.5, metric="cosine", exclude=None, any_of=None,
+                               none_of=None):
+        return self._diverse(self._reps(reps, exclude, any_of, none_of), k, pool, trade_off, metric)
+
+
+class ItemSetSessions:
+    """``ItemSet.on(store)``: the scan methods of ``Sessions`` under their names and keywords, restricted to the set.  The store
+    must be current and of the set's model; its seen items are excluded as the store's own calls exclude them."""
+
+    def __init__(self, item_set: ItemSet, store: "Sessions"):
+        self.item_set, self.store = item_set, store
+
+    def _src(self, slots, exclude, any_of, none_of, include_seen):
+        return self.item_set._store(self.store, slots, exclude, any_of, none_of, include_seen)
+
+    def recommend(self, slots, k: int, exclude=None, any_of=None, none_of=None, include_seen: bool = False):
+        return self.item_set._recommend(self._src(slots, exclude, any_of, none_of, include_seen), k)
+
+    def recommend_capped(self, slots, k: int, cap: int = 1, pool=None, exclude=None, any_of=None, none_of=None,
+                         include_seen: bool = False, exact: bool = True):
+        return self.item_set._capped(self._src(slots, exclude, any_of, none_of, include_seen), k, cap, pool, exact)
+
+    def recommend_sampled(self, slots, k: int, temperature: float = 1.0, seed: int = 0, streams=None, exclude=None, any_of=None,
+                          none_of=None, include_seen: bool = False, log_prob: bool = False):
+        return self.item_set._sampled(self._src(slots, exclude, any_of, none_of, include_seen), k, temperature, seed, streams, log_prob)
+
+    def log_partition(self, slots, temperature: float = 1.0, exclude=None, any_of=None, none_of=None,
+                      include_seen: bool = False) -> Partition:
+        return self.item_set._log_partition(self._src(slots, exclude, any_of, none_of, include_seen), temperature)
+
+    def recommend_diverse(self, slots, k: int, pool: int, trade_off: float = 0.5, metric="cosine", exclude=None, any_of=None,
+                          none_of=None):
+        return self.item_set._diverse(self._src(slots, exclude, any_of, none_of, False), k, pool, trade_off, metric)
+
+    def recommend_above(self, slots, threshold, exclude=None, any_of=None, none_of=None, include_seen: bool = False, max_results=None,
+                        order: str = "score") -> Above:
+        return self.item_set._above(self._src(slots, exclude, any_of, none_of, include_seen), threshold, max_results, order, False)
+
+    def count_above(self, slots, threshold, exclude=None, any_of=None, none_of=None, include_seen: bool = False) -> np.ndarray:
+        return self.item_set._above(self._src(slots, exclude, any_of, none_of, include_seen), threshold, None, "id", True)
+
+    def recommend_top(self, slots, n, exclude=None, any_of=None, none_of=None, include_seen: bool = False, max_results=None,
+                      order: str = "score") -> Above:
+        return self.item_set._above(self._src(slots, exclude, any_of, none_of, include_seen), None, max_results, order, False, n)
+
+    def nth_score(self, slots, n, exclude=None, any_of=None, none_of=None, include_seen: bool = False):
+        return self.item_set._above(self._src(slots, exclude, any_of, none_of, include_seen), None, None, "id", True, n)
 
 
 def release_cached_memory() -> None:

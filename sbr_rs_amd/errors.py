@@ -10,6 +10,11 @@ class EngineError(RuntimeError):
         super().__init__(f"{status.name}: {message}")
 
 
+class InvalidArgument(EngineError, ValueError):
+    """SBR_ERR_INVALID_ARGUMENT from a call through an ``ItemSet`` — a stale set, a store of another model, an id out of range:
+    an ``EngineError`` that is also a ``ValueError``."""
+
+
 class FittingError(Exception):
     """Fitting error types (lib.rs:92-97).  ``FittingError.NoInteractions`` is the variant."""
 

@@ -260,12 +260,13 @@ class _ImplicitSequenceModel:
         allowed) — the exact top k of that set, found by scanning its rows only.
         ``any_of`` / ``none_of``: the per-user tag filter against ``set_item_tags`` — a u32 mask per user, or one for all: item
         i is eligible for user u iff ``tags[i] & none_of[u] == 0 and (any_of[u] == 0 or tags[i] & any_of[u] != 0)`` (territory,
-        rating, tier, in stock, "not this category"), tested inside the scan.  Not together with ``among`` yet."""
+        rating, tier, in stock, "not this category"), tested inside the scan.  Not together with ``among``: ``item_set(among)`` takes
+        both, and keeps the set on the device between calls."""
         up, it = self._csr(interactions_or_histories)
         if among is None:
             return self.params.recommend(up, it, k, include_history=not exclude_history, any_of=any_of, none_of=none_of)
         if any_of is not None or none_of is not None:
-            raise ValueError("a tag filter together with among= is not supported: filter the item set instead")
+            raise ValueError("a tag filter together with among= is not supported: filter the item set instead, or use item_set()")
         return self.params.recommend_among(up, it, k, among, include_history=not exclude_history)
 
     def recommend_sampled(self, interactions_or_histories, k: int, temperature: float = 1.0, seed: int = 0, streams=None,
@@ -474,6 +475,15 @@ class _ImplicitSequenceModel:
         return self.params.recommend_diverse(up, it, k, pool, trade_off=trade_off, metric=metric, include_history=not exclude_history,
                                              any_of=any_of, none_of=none_of)
 
+    def item_set(self, item_ids):
+        """A long-lived item set (a category, a territory, what is in stock) kept on the device: ``item_ids`` in any order,
+        duplicates allowed.  The returned ``ItemSetView`` offers ``recommend``, ``recommend_sampled``, ``log_partition``,
+        ``recommend_above`` / ``count_above``, ``recommend_top`` / ``nth_score``, ``recommend_capped`` and ``recommend_diverse``
+        (and their ``*_reps`` forms) under this model's names and keywords, each restricted to the set — bit for bit what the
+        model's call returns with every other item excluded, at the cost of scanning the set's rows only — together with tag
+        filters, and ``on(store)`` for a session store.  Call its ``refresh()`` after ``fit`` or ``load``."""
+        return ItemSetView(self, self.params.item_set(item_ids))
+
     def sessions(self, capacity: int, remember: int = 0):
         """A session store of ``capacity`` slots on the device (``engine.Sessions``): each slot holds one user's recurrent state,
         ``append`` advances it by one cell step per item instead of re-running the whole history, and ``recommend`` /
@@ -515,6 +525,69 @@ class _ImplicitSequenceModel:
         from .evaluation import calibrate_temperature
 
         return calibrate_temperature(self, validation, bounds=bounds, evaluations=evaluations, mask_history=mask_history, last=last)
+
+
+class ItemSetView:
+    """``model.item_set(item_ids)``: an ``engine.ItemSet`` under the model wrappers' conventions — histories as a
+    CompressedInteractions or a list of item-id sequences, ``exclude_history`` where the engine says ``include_history``.  The
+    ``*_reps`` forms, ``size``, ``items``, ``refresh()``, ``close()`` and ``on(store)`` are the engine object's own."""
+
+    def __init__(self, model: "_ImplicitSequenceModel", item_set):
+        self.model, self.set = model, item_set
+
+    def __getattr__(self, name):  # size, items, refresh, close, on and the *_reps methods
+        return getattr(self.set, name)
+
+    def __len__(self) -> int:
+        return self.set.size
+
+    def recommend(self, interactions_or_histories, k: int, exclude_history: bool = True, any_of=None, none_of=None):
+        up, it = self.model._csr(interactions_or_histories)
+        return self.set.recommend(up, it, k, include_history=not exclude_history, any_of=any_of, none_of=none_of)
+
+    def recommend_sampled(self, interactions_or_histories, k: int, temperature: float = 1.0, seed: int = 0, streams=None,
+                          exclude_history: bool = True, any_of=None, none_of=None, log_prob: bool = False):
+        up, it = self.model._csr(interactions_or_histories)
+        return self.set.recommend_sampled(up, it, k, temperature=temperature, seed=seed, streams=streams,
+                                          include_history=not exclude_history, any_of=any_of, none_of=none_of, log_prob=log_prob)
+
+    def log_partition(self, interactions_or_histories, temperature: float = 1.0, exclude_history: bool = True, any_of=None, none_of=None):
+        up, it = self.model._csr(interactions_or_histories)
+        return self.set.log_partition(up, it, temperature, include_history=not exclude_history, any_of=any_of, none_of=none_of)
+
+    def recommend_above(self, interactions_or_histories, threshold, exclude_history: bool = True, any_of=None, none_of=None,
+                        max_results=None, order: str = "score"):
+        up, it = self.model._csr(interactions_or_histories)
+        return self.set.recommend_above(up, it, threshold, include_history=not exclude_history, any_of=any_of, none_of=none_of,
+                                        max_results=max_results, order=order)
+
+    def count_above(self, interactions_or_histories, threshold, exclude_history: bool = True, any_of=None, none_of=None):
+        up, it = self.model._csr(interactions_or_histories)
+        return self.set.count_above(up, it, threshold, include_history=not exclude_history, any_of=any_of, none_of=none_of)
+
+    def recommend_top(self, interactions_or_histories, n, exclude_history: bool = True, any_of=None, none_of=None, max_results=None,
+                      order: str = "score"):
+        up, it = self.model._csr(interactions_or_histories)
+        return self.set.recommend_top(up, it, n, include_history=not exclude_history, any_of=any_of, none_of=none_of,
+                                      max_results=max_results, order=order)
+
+    def nth_score(self, interactions_or_histories, n, exclude_history: bool = True, any_of=None, none_of=None):
+        up, it = self.model._csr(interactions_or_histories)
+        return self.set.nth_score(up, it, n, include_history=not exclude_history, any_of=any_of, none_of=none_of)
+
+    def recommend_capped(self, interactions_or_histories, k: int, cap: int = 1, pool=None, exclude_history: bool = True, any_of=None,
+                         none_of=None, exact: bool = True):
+        up, it = self.model._csr(interactions_or_histories)
+        return self.set.recommend_capped(up, it, k, cap=cap, pool=pool, include_history=not exclude_history, any_of=any_of,
+                                         none_of=none_of, exact=exact)
+
+    def recommend_diverse(self, interactions_or_histories, k: int, pool=None, trade_off: float = 0.5, metric: str = "cosine",
+                          exclude_history: bool = True, any_of=None, none_of=None):
+        up, it = self.model._csr(interactions_or_histories)
+        if pool is None:
+            pool = min(4 * int(k), self.model.params.diverse_max_pool())
+        return self.set.recommend_diverse(up, it, k, pool, trade_off=trade_off, metric=metric, include_history=not exclude_history,
+                                          any_of=any_of, none_of=none_of)
 
 
 class ImplicitLSTMModel(_ImplicitSequenceModel):
