@@ -592,6 +592,32 @@ struct Partition {
         return out;
     }
 };
+/// The arguments of the rollout calls (struct sbr_rollout_args and the lists around it; ROLLOUT in sbr_hip.h).  `sample`: each pick is
+/// the one draw of recommend_sampled(k = 1) at noise.seed + step, else the top-1; noise.temperature is also the per-step partition's
+/// (`log_prob`), in either mode; noise.streams default to the slot ids.  `final_state`: the states after all picks are returned too —
+/// `lstm` says whether the model has cell states (ImplicitSequenceModel::rollout sets it itself).
+struct RolloutArgs {
+    std::size_t steps = 1;
+    bool sample = false, allow_repeats = false, include_seen = false, log_prob = false, final_state = false, lstm = true;
+    SampleArgs noise;
+    TagFilter filter;
+    std::vector<std::uint64_t> excl_ptr;
+    std::vector<std::uint32_t> excl_items;
+};
+/// What the rollout calls return, row-major [num_rows][steps]: row i's picks in pick order with their plain scores, padded with
+/// (0xFFFFFFFF, -inf) from the step at which the row had nothing left to choose from, and lengths [num_rows], its real steps.  keys:
+/// the winning keys of a sampled rollout, else empty.  With log_prob: `partition` holds one row per (row, step) — shift -inf and mass 0
+/// at padding — and log_prob = partition.log_prob of the picks' scores, NaN at padding.  With final_state: h, c (empty for EWMA)
+/// [num_rows][embedding_dim] and len, in Sessions::State's format, after all picks.
+struct Rollout {
+    std::size_t num_rows = 0, steps = 0;
+    std::vector<std::uint32_t> items, lengths;
+    std::vector<float> scores, keys;
+    Partition partition;
+    std::vector<double> log_prob;
+    std::vector<float> h, c;
+    std::vector<std::uint64_t> len;
+};
 /// What ImplicitSequenceModel::sequence_partition returns (SEQUENCE PARTITION in sbr_hip.h), CSR over the kept positions: user u's
 /// are entries ptr[u] .. ptr[u + 1), positions ascending, of the partition's rows, of `scores` (the targets' plain scores) and of
 /// `masked` (1 where the policy masks the target: its log-probability is -inf).
@@ -1080,6 +1106,63 @@ class Sessions {
         if (st == SBR_ERR_INVALID_PREDICTION) return Result<Partition, PredictionError>::Err(PredictionError::InvalidPredictionValue);
         check(st, "sbr_sessions_log_partition");
         return Result<Partition, PredictionError>::Ok(std::move(r));
+    }
+    /// Each slot's next a.steps items, each chosen given the ones before it, picked and fed back on the device
+    /// (sbr_sessions_rollout): what a host loop of recommend(k = 1) + append + a rebuilt exclusion list returns, WITHOUT writing the
+    /// store — a rollout is hypothetical; append its rows to make it happen.  Step j picks among what `recommend` would offer at
+    /// call time minus picks 0 .. j - 1 (with allow_repeats: the picks stay eligible), scored against the state after those picks.
+    /// The insert of a pick into its row's exclusion list costs O(list) per step; steps <= SBR_ROLLOUT_MAX_STEPS.
+    Result<Rollout, PredictionError> rollout(const std::vector<std::uint32_t>& slots, const RolloutArgs& a) const {
+        using R = Result<Rollout, PredictionError>;
+        if (a.steps < 1 || a.steps > SBR_ROLLOUT_MAX_STEPS) throw EngineError(SBR_ERR_INVALID_ARGUMENT, "Sessions::rollout: steps outside 1..SBR_ROLLOUT_MAX_STEPS");
+        if (!a.excl_ptr.empty() && (a.excl_ptr.size() != slots.size() + 1 || a.excl_ptr.back() > a.excl_items.size()))
+            throw EngineError(SBR_ERR_INVALID_ARGUMENT, "Sessions::rollout: one exclusion range per slot");
+        const std::size_t n = slots.size(), cells = n * a.steps;
+        const bool filtered = !a.filter.any_of.empty() || !a.filter.none_of.empty();
+        const std::vector<std::uint32_t> any = tag_masks(a.filter.any_of, n, "Sessions::rollout: one any_of mask per slot");
+        const std::vector<std::uint32_t> none_of = tag_masks(a.filter.none_of, n, "Sessions::rollout: one none_of mask per slot");
+        sbr_rollout_args ra{};
+        ra.steps = (std::uint32_t)a.steps;
+        ra.flags = (a.sample ? SBR_ROLLOUT_SAMPLE : 0u) | (a.allow_repeats ? SBR_ROLLOUT_ALLOW_REPEATS : 0u) |
+                   (a.include_seen ? SBR_ROLLOUT_INCLUDE_SEEN : 0u);
+        ra.sample = sample_args(a.noise, n, "Sessions::rollout: one stream per slot");
+        Rollout r;
+        r.num_rows = n;
+        r.steps = a.steps;
+        r.items.resize(cells);
+        r.scores.resize(cells);
+        r.lengths.resize(n);
+        if (a.sample) r.keys.resize(cells);
+        if (a.log_prob) {
+            r.partition.temperature = a.noise.temperature;
+            r.partition.shift.resize(cells);
+            r.partition.mass.resize(cells);
+        }
+        if (a.final_state) {
+            r.h.resize(n * dim_);
+            if (a.lstm) r.c.resize(n * dim_);
+        }
+        const std::uint32_t none = 0;
+        const sbr_status st = sbr_sessions_rollout(h_, slots.data(), (std::uint64_t)n, &ra, a.excl_ptr.empty() ? nullptr : a.excl_ptr.data(),
+                                                   a.excl_ptr.empty() ? nullptr : (a.excl_items.empty() ? &none : a.excl_items.data()),
+                                                   filtered ? any.data() : nullptr, filtered ? none_of.data() : nullptr, r.items.data(),
+                                                   r.scores.data(), a.sample ? r.keys.data() : nullptr, r.lengths.data(),
+                                                   a.log_prob ? r.partition.shift.data() : nullptr, a.log_prob ? r.partition.mass.data() : nullptr,
+                                                   a.log_prob ? &r.partition.frac_bits : nullptr, a.final_state ? r.h.data() : nullptr,
+                                                   a.final_state && a.lstm ? r.c.data() : nullptr);
+        if (st == SBR_ERR_INVALID_PREDICTION) return R::Err(PredictionError::InvalidPredictionValue);
+        check(st, "sbr_sessions_rollout");
+        if (a.log_prob) { /* one partition row per (row, step): the library's one host statement of the weights */
+            r.log_prob = r.partition.log_prob(r.scores);
+            for (std::size_t p = 0; p < cells; ++p)
+                if (r.items[p] == 0xFFFFFFFFu) r.log_prob[p] = std::numeric_limits<double>::quiet_NaN();
+        }
+        if (a.final_state) {
+            r.len.resize(n);
+            check(sbr_sessions_lengths(h_, slots.data(), (std::uint64_t)n, r.len.data()), "sbr_sessions_lengths");
+            for (std::size_t i = 0; i < n; ++i) r.len[i] += r.lengths[i];
+        }
+        return R::Ok(std::move(r));
     }
     /// `recommend_diverse` under a tag filter: the pool holds eligible items only (sbr_sessions_recommend_diverse_filtered).
     Result<Recommendations, PredictionError> recommend_diverse_filtered(const std::vector<std::uint32_t>& slots, std::size_t k, std::size_t pool,
@@ -2586,6 +2669,35 @@ class ImplicitSequenceModel : public OnlineRankingModel<ImplicitUser> {
         r.scores.resize(n);
         r.masked.resize(n);
         return R::Ok(std::move(r));
+    }
+
+    /// Sessions::rollout from histories, DEFINED as this sequence of calls: a temporary store of one slot per user, `append` of each
+    /// history's last max_sequence_length items, and the store's rollout of all slots — with exclude_history each history's items as
+    /// its exclusion list, replacing a.excl_ptr / a.excl_items.  Streams default to the user's index, the slot id; a.lstm is set
+    /// from the model.
+    Result<Rollout, PredictionError> rollout(const data::CompressedInteractions& histories, RolloutArgs a, bool exclude_history = true) const {
+        const std::vector<std::uint64_t>& up = histories.user_pointers();
+        const std::vector<std::uint32_t>& ids = histories.item_ids();
+        const std::size_t n = histories.num_users(), T = (std::size_t)replicas_->hparams().max_sequence_length;
+        if (n == 0) throw EngineError(SBR_ERR_INVALID_ARGUMENT, "rollout: at least one history");
+        std::vector<std::uint32_t> slots(n), tail;
+        std::vector<std::uint64_t> tail_ptr(n + 1, 0);
+        for (std::size_t u = 0; u < n; ++u) {
+            slots[u] = (std::uint32_t)u;
+            const std::uint64_t keep = std::min<std::uint64_t>(up[u + 1] - up[u], T);
+            tail.insert(tail.end(), ids.begin() + (std::ptrdiff_t)(up[u + 1] - keep), ids.begin() + (std::ptrdiff_t)up[u + 1]);
+            tail_ptr[u + 1] = tail.size();
+        }
+        Sessions store = sessions(n);
+        store.append(slots, tail_ptr, tail);
+        a.lstm = replicas_->hparams().model != 2;
+        a.include_seen = false;
+        if (exclude_history) {
+            a.excl_ptr.assign(up.begin(), up.end());
+            for (std::uint64_t& p : a.excl_ptr) p -= up.front();
+            a.excl_items.assign(ids.begin() + (std::ptrdiff_t)up.front(), ids.begin() + (std::ptrdiff_t)up.back());
+        }
+        return store.rollout(slots, a);
     }
 
     /// A session store of `capacity` slots on the primary replica: device-resident user states advanced one appended item at a

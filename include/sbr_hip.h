@@ -824,6 +824,51 @@ sbr_status sbr_sessions_log_partition(sbr_sessions* st, const uint32_t* slots, u
                                       const uint32_t* excl_items, uint32_t flags, float temperature, const uint32_t* any_of,
                                       const uint32_t* none_of, float* out_shift, uint64_t* out_mass, uint32_t* out_frac_bits);
 
+/* ROLLOUT — a session's next `steps` items, each chosen given the ones before it, picked and fed back on the device: queue
+ * continuation, an "up next" rail, trajectories under the softmax policy (no counterpart in the reference crate: a host loop of
+ * recommend(k = 1) + append + a rebuilt exclusion list per step).  A rollout is HYPOTHETICAL: it reads the store and writes none of
+ * it — not a state, not a length, not the seen-item memory.  Stated against the calls above, for row i and step j = 0 .. steps - 1:
+ *   ELIGIBILITY  X_0 = what sbr_sessions_recommend[_filtered](k = 1) may choose from at call time: excl_ptr / excl_items, the slot's
+ *                seen-item memory (unless SBR_ROLLOUT_INCLUDE_SEEN; only a store with memory takes that flag), the masks any_of /
+ *                none_of (both NULL: no filter).  X_j = X_0 without picks 0 .. j - 1; with SBR_ROLLOUT_ALLOW_REPEATS X_j = X_0.
+ *   GREEDY       pick j = the first item of X_j in every call's order (score descending, ties to the lower id, -0.0 == +0.0), the
+ *                scores taken against the state after picks 0 .. j - 1; out_scores has sbr_predict's bits.  Step 0 of an empty slot
+ *                reads the empty-history row, as sbr_sessions_recommend does.
+ *   SAMPLE       (SBR_ROLLOUT_SAMPLE) pick j = the one draw of sbr_sessions_recommend_sampled(k = 1) over X_j with sample's
+ *                temperature and streams (NULL: the slot ids) and seed (sample->seed + j) mod 2^64 — the noise is a function of
+ *                (seed, stream, item) alone, so one seed for all steps would give an item the same noise at every step.  out_keys
+ *                (optional; must be NULL without the flag) receives the winning keys.  steps = 1 IS that call.
+ *   STATE        after pick j the row's state is what sbr_sessions_append(slot, [pick]) would make of it: one cell step of the forward
+ *                pass's arithmetic, the whole recurrence, no window; an empty slot starts from zero.  out_h / out_c (optional;
+ *                [n][embedding_dim]; out_c with out_h and the LSTM only) receive the states after all steps, the bits of
+ *                sbr_sessions_get_state after appending row i's out_lengths[i] picks — whose len is the slot's length + out_lengths[i].
+ *   END          a row with X_j empty ends: entry j and every later one is (0xFFFFFFFF, -inf), -inf in out_keys, and
+ *                out_lengths[i] = j (optional; steps for a row that never ends); its state stops changing.
+ *   PARTITION    out_shift non-NULL (then out_mass and out_frac_bits too) asks for it, in either mode: out_shift / out_mass [n][steps]
+ *                = sbr_sessions_log_partition's shift and mass for step j's state over X_j at sample->temperature, bit for bit;
+ *                (-inf, 0) at padding.  The log-probability of pick j is log(sbr_softmax_weights(out_scores) / mass), on the host.
+ * out_items / out_scores [n][steps] (scores optional).  1 <= steps <= SBR_ROLLOUT_MAX_STEPS.  The same arguments return the same rows
+ * whatever the batch, the host's chunks or the scan's item ranges.  All steps of a chunk are queued without a host synchronisation;
+ * the insert of a pick into its row's exclusion segment costs O(segment) per row and step.
+ * SBR_ERR_INVALID_ARGUMENT, with nothing launched: args NULL, steps out of range, unknown flags, a temperature sbr_sample_args
+ * refuses (checked in both modes), SBR_ROLLOUT_INCLUDE_SEEN on a store without memory, masks on a model without tags, a stale store,
+ * an open fit plan, a slot out of range or named twice.  SBR_ERR_INVALID_PREDICTION: a non-finite score at any step fails the whole
+ * call, as in sbr_recommend: what the outputs then hold is unspecified, and no binding returns it.  Not built: k > 1 per step (beam search), item sets, a rollout that commits, caps or
+ * thresholds inside a rollout, a per-step temperature, rollouts from *_reps rows. */
+#define SBR_ROLLOUT_MAX_STEPS 1024u
+#define SBR_ROLLOUT_SAMPLE 1u
+#define SBR_ROLLOUT_ALLOW_REPEATS 2u
+#define SBR_ROLLOUT_INCLUDE_SEEN 4u
+typedef struct sbr_rollout_args {
+    uint32_t steps;
+    uint32_t flags;
+    struct sbr_sample_args sample;
+} sbr_rollout_args;
+sbr_status sbr_sessions_rollout(sbr_sessions* st, const uint32_t* slots, uint64_t n, const struct sbr_rollout_args* args,
+                                const uint64_t* excl_ptr, const uint32_t* excl_items, const uint32_t* any_of, const uint32_t* none_of,
+                                uint32_t* out_items, float* out_scores, float* out_keys, uint32_t* out_lengths, float* out_shift,
+                                uint64_t* out_mass, uint32_t* out_frac_bits, float* out_h, float* out_c);
+
 /* AUDIENCE— the reverse question, "which rows for this item": for each of num_queries query items q = items[j] (any order, repeats
  * allowed, each < num_items) the k candidate rows that score it highest, score(q, s) = b[q] + chain_dot(h_s, E[q]) with the bits of
  * sbr_predict / sbr_score_candidates for that (state, item) pair: the catalogue scan with the operands' roles exchanged (every

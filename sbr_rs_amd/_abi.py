@@ -97,6 +97,26 @@ class SbrSampleArgs(C.Structure):
     ]
 
 
+# ROLLOUT — sbr_sessions_rollout (include/sbr_hip.h): a session's next `steps` items, each picked by the k = 1 scan over what the
+# row may still see and fed back as the next cell step's input and the next scan's exclusion, on the device; the store is read only.
+# flags: ROLLOUT_SAMPLE (the pick is recommend_sampled's draw at seed + step; else the top-1), ROLLOUT_ALLOW_REPEATS (picks are not
+# excluded from later steps), ROLLOUT_INCLUDE_SEEN (a store with memory: its seen items stay eligible).  The sample arguments'
+# temperature is also the per-step partition's, which a non-null out_shift asks for.
+ROLLOUT_MAX_STEPS = 1024
+ROLLOUT_SAMPLE = 1
+ROLLOUT_ALLOW_REPEATS = 2
+ROLLOUT_INCLUDE_SEEN = 4
+
+
+class SbrRolloutArgs(C.Structure):
+    """struct sbr_rollout_args of sbr_sessions_rollout"""
+    _fields_ = [
+        ("steps", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("sample", SbrSampleArgs),
+    ]
+
+
 class SbrCapArgs(C.Structure):
     """struct sbr_cap_args of the *_capped calls"""
     _fields_ = [

@@ -243,6 +243,15 @@ def build_item_set_tests(force: bool = False, verbose: bool = True) -> str:
     return _build_cpp_program(ITEM_SET_SRC, ITEM_SET_BIN, force, verbose)
 
 
+ROLLOUT_SRC = os.path.join(REPO, "tests", "cpp", "rollout_tests.cpp")
+ROLLOUT_BIN = os.path.join(REPO, "tests", "cpp", "_build", "rollout_tests")
+
+
+def build_rollout_tests(force: bool = False, verbose: bool = True) -> str:
+    """g++ build of the C++ host layer's rollout test program."""
+    return _build_cpp_program(ROLLOUT_SRC, ROLLOUT_BIN, force, verbose)
+
+
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv))
     print(build_facade_tests(force="--force" in sys.argv))
@@ -264,3 +273,4 @@ if __name__ == "__main__":
     print(build_sequence_ranks_tests(force="--force" in sys.argv))
     print(build_sequence_partition_tests(force="--force" in sys.argv))
     print(build_item_set_tests(force="--force" in sys.argv))
+    print(build_rollout_tests(force="--force" in sys.argv))

@@ -6051,6 +6051,241 @@ sbr_status sbr_sessions_recommend_diverse_filtered(sbr_sessions* st, const uint3
 }
 
 /* ---------------------------------------------------------------------------------------------
+ * rollout: a session's next items, picked and fed back on the device (ROLLOUT in include/sbr_hip.h)
+ * ------------------------------------------------------------------------------------------- */
+namespace {
+
+/* what a rollout call asks for beside its slots and lists; the outputs are host arrays over the call's rows, null: not wanted */
+struct RolloutCall {
+    uint32_t steps;
+    bool allow_repeats, seen;
+    const Sample* sm;        /* null: greedy */
+    const TagFilterArg* flt; /* null: no filter */
+    float inv_t;             /* the partition's, = sm->inv_t in sample mode */
+    uint32_t* out_items;
+    float *out_scores, *out_keys;
+    uint32_t* out_lengths;
+    float* out_shift;        /* non-null: the partition per step, with out_mass */
+    uint64_t* out_mass;
+    float *out_h, *out_c;
+};
+
+/* Sessions per rollout chunk: the scan's bound (recommend_users_cap at k = 1), and few enough that a row's share of the arena — its
+ * exclusion segment with the slack, twice (the tight lists it is spread from), its columns of the outputs and its scratch state —
+ * keeps the chunk within 256 MB.  SBR_ROLLOUT_CHUNK=n (n >= 1) is a TEST HOOK read per call that replaces both, after
+ * SBR_SESSIONS_REPLAY_CHUNK. */
+size_t rollout_chunk_cap(const sbr_model* m, uint32_t w, uint32_t steps) {
+    constexpr size_t budget = (size_t)256 << 20;
+    const size_t per = ((size_t)w + steps) * 8 + (size_t)steps * 24 + (size_t)m->d * 16 + 64;
+    size_t cap = std::min(recommend_users_cap((uint32_t)m->hp.num_items, 1), std::max<size_t>(budget / per, 1));
+    if (const char* e = std::getenv("SBR_ROLLOUT_CHUNK")) {
+        const long long v = std::atoll(e);
+        if (v >= 1) cap = (size_t)v;
+    }
+    return cap;
+}
+
+/* One chunk, rows [c0, c0 + nu) of the call: the scratch state and the exclusion CSR with slack, then per step the unchanged k = 1
+ * scan (and the partition on the same descriptor), rollout_advance_kernel and one cell step — all queued without a synchronisation —
+ * and at the end one flag check and the copies out, as scan_launch does. */
+sbr_status sessions_rollout_chunk(sbr_sessions* st, const uint32_t* slots, const std::vector<int>& rep0, const uint64_t* excl_ptr,
+                                  const uint32_t* excl_items, const RolloutCall& rc, size_t c0, size_t nu) {
+    sbr_model* m = st->m;
+    const size_t d = (size_t)m->d, dl = (size_t)m->dl, S = rc.steps;
+    const bool lstm = m->ng != 0, sample = rc.sm != nullptr, part = rc.out_shift != nullptr;
+    const bool final_state = rc.out_h != nullptr;
+    const size_t seen_w = rc.seen ? st->seen.w : 0;
+    const uint32_t slack = rc.allow_repeats ? 0u : rc.steps;
+    UserBatch ub; /* the caller's lists of the chunk's rows, sorted and de-duplicated */
+    if (excl_ptr) {
+        std::vector<const uint32_t*> list(nu);
+        std::vector<uint64_t> n(nu);
+        for (size_t i = 0; i < nu; ++i) {
+            list[i] = excl_items ? excl_items + excl_ptr[c0 + i] : nullptr;
+            n[i] = excl_ptr[c0 + i + 1] - excl_ptr[c0 + i];
+        }
+        prepare_users(list, n, m->hp.max_sequence_length, true, &ub);
+    }
+    const size_t ncaller = ub.list_items.size();
+    const size_t nsrc = nu * seen_w + ncaller, nexcl = nsrc + nu * slack;
+    const bool excl = excl_ptr || seen_w || slack; /* without any of them nothing is ever excluded */
+    TopkBufs tb;
+    SampleBufs smb{};
+    sbr::RolloutRows rr{};
+    sbr::RolloutOut ro{};
+    uint64_t* src_ptr = nullptr;
+    uint32_t *src = nullptr, *seen_caller = nullptr, *d_slot = nullptr, *d_ident = nullptr, *pt_items = nullptr;
+    unsigned long long* d_start = nullptr;
+    float *pt_scores = nullptr, *pt_shift = nullptr, *fin_h = nullptr, *fin_c = nullptr;
+    unsigned long long* pt_mass = nullptr;
+    SBRCHK(carve_arena(m, [&](DeviceArena& ar) {
+        tb.carve(ar, (uint32_t)m->hp.num_items, nu, nexcl, 1, rc.flt != nullptr);
+        src_ptr = ar.take<uint64_t>(nu + 1);
+        src = ar.take<uint32_t>(nsrc + 1);
+        if (seen_w) seen_caller = ar.take<uint32_t>(ncaller + 1);
+        d_slot = ar.take<uint32_t>(nu);
+        d_ident = ar.take<uint32_t>(nu);
+        d_start = ar.take<unsigned long long>(nu);
+        rr.Hs = ar.take<float>((lstm ? 2 : 1) * nu * d);
+        if (lstm) rr.Cs = ar.take<float>(2 * nu * d);
+        rr.len = ar.take<unsigned long long>(nu);
+        rr.feed = ar.take<uint32_t>(nu);
+        rr.count = ar.take<uint32_t>(nu);
+        rr.ended = ar.take<uint32_t>(nu);
+        rr.lengths = ar.take<uint32_t>(nu);
+        if (sample) smb.carve(ar, nu, 1);
+        if (part) {
+            pt_mass = ar.take<unsigned long long>(nu);
+            pt_shift = ar.take<float>(nu);
+            ro.mass = ar.take<unsigned long long>(nu * S);
+            ro.shift = ar.take<float>(nu * S);
+            if (sample) { pt_items = ar.take<uint32_t>(nu); pt_scores = ar.take<float>(nu); }
+        }
+        ro.items = ar.take<uint32_t>(nu * S);
+        ro.scores = ar.take<float>(nu * S);
+        if (sample) ro.keys = ar.take<float>(nu * S);
+        if (final_state) {
+            fin_h = ar.take<float>(nu * dl);
+            if (lstm) fin_c = ar.take<float>(nu * dl);
+        }
+    }));
+    /* the host vectors below are read by asynchronous copies: they live until the stream is drained at the end */
+    std::vector<uint64_t> h_src_ptr(nu + 1), h_eptr(nu + 1);
+    std::vector<uint32_t> h_ident(nu);
+    std::vector<unsigned long long> h_start(nu);
+    for (size_t i = 0; i <= nu; ++i) {
+        h_src_ptr[i] = i * seen_w + (ub.list_ptr.empty() ? 0 : ub.list_ptr[i]);
+        h_eptr[i] = h_src_ptr[i] + i * slack;
+    }
+    for (size_t i = 0; i < nu; ++i) { h_ident[i] = (uint32_t)i; h_start[i] = i; }
+    HIPCHK(hipMemcpyAsync(tb.rep, rep0.data() + c0, nu * 4, hipMemcpyHostToDevice, m->stream));
+    HIPCHK(hipMemcpyAsync(d_slot, slots + c0, nu * 4, hipMemcpyHostToDevice, m->stream));
+    HIPCHK(hipMemcpyAsync(d_ident, h_ident.data(), nu * 4, hipMemcpyHostToDevice, m->stream));
+    HIPCHK(hipMemcpyAsync(d_start, h_start.data(), nu * 8, hipMemcpyHostToDevice, m->stream));
+    if (excl) {
+        HIPCHK(hipMemcpyAsync(tb.eptr, h_eptr.data(), (nu + 1) * 8, hipMemcpyHostToDevice, m->stream));
+        SBRCHK(upload_csr(m, src_ptr, h_src_ptr, seen_w ? seen_caller : src, ub.list_items));
+    }
+    std::vector<uint32_t> masks; /* the chunk's rows' any_of, then their none_of */
+    if (rc.flt) {
+        masks.assign(2 * nu, 0u);
+        for (size_t i = 0; i < nu; ++i) {
+            if (rc.flt->any_of) masks[i] = rc.flt->any_of[c0 + i];
+            if (rc.flt->none_of) masks[nu + i] = rc.flt->none_of[c0 + i];
+        }
+        HIPCHK(hipMemcpyAsync(tb.any_of, masks.data(), nu * 4, hipMemcpyHostToDevice, m->stream));
+        HIPCHK(hipMemcpyAsync(tb.none_of, masks.data() + nu, nu * 4, hipMemcpyHostToDevice, m->stream));
+    }
+    std::vector<uint64_t> streams;
+    if (sample) {
+        streams.resize(nu);
+        for (size_t i = 0; i < nu; ++i) streams[i] = rc.sm->streams ? rc.sm->streams[c0 + i] : (uint64_t)slots[c0 + i];
+        HIPCHK(hipMemcpyAsync(smb.streams, streams.data(), nu * 8, hipMemcpyHostToDevice, m->stream));
+    }
+    rr.n = (int)nu; rr.steps = rc.steps;
+    rr.slot = d_slot; rr.ident = d_ident; rr.start = d_start;
+    /* the step's scan: the pick's descriptor, and with the partition in sample mode a second one whose k = 1 scan is the plain one */
+    sbr::TopkScan sc = tb.scan(nu, 1, excl, true, rc.flt ? m->item_tags : nullptr);
+    sbr::TopkScan sc_pt = sc;
+    if (sample) {
+        sc.g = sbr::SampleNoise{rc.sm->inv_t, smb.keys};
+        sc_pt.out_items = pt_items;
+        sc_pt.out_scores = pt_scores;
+    }
+    const sbr::RolloutPick pick{tb.items, sample ? smb.plain : tb.scores, sample ? tb.scores : nullptr, pt_shift, pt_mass};
+    const size_t parity_stride = nu * d;
+    HIPCHK(hipMemsetAsync(tb.flag, 0, 4, m->stream));
+    {
+        ScopedTimer t(m, SBR_K_RANK, 0);
+        int n = sbr::launch_rollout_begin(m->mv, st->v, rr, m->stream);
+        if (seen_w) n += sbr::launch_session_seen_lists(st->seen, d_slot, (int)nu, src_ptr, seen_caller, src, m->stream);
+        if (excl) n += sbr::launch_rollout_segments(src_ptr, src, (int)nu, slack, tb.excl, m->stream);
+        t.tp.launches = (uint64_t)n;
+    }
+    for (uint32_t j = 0; j < rc.steps; ++j) {
+        /* step 0 scans the store's rows in place (an empty slot: the empty-history row); later steps the scratch the step before wrote */
+        const float* reps = j == 0 ? st->v.H : lstm ? rr.Hs + (size_t)((j - 1) & 1u) * parity_stride : rr.Hs;
+        sc.rep_row = sc_pt.rep_row = j == 0 ? tb.rep : reinterpret_cast<const int*>(d_ident);
+        {
+            ScopedTimer t(m, SBR_K_RANK, 0);
+            int n = 0;
+            if (sample)
+                n += sbr::launch_recommend_sampled(m->mv, reps, sc, sbr::SampleScan{rc.sm->seed + (uint64_t)j, smb.streams, smb.pair_row,
+                                                                                   smb.pair_item, smb.plain, nullptr}, m->stream);
+            if (part) n += sbr::launch_log_partition(m->mv, reps, sc_pt, sbr::PartitionScan{rc.inv_t, pt_shift, pt_mass, 0u}, m->stream);
+            else if (!sample) n += sbr::launch_recommend(m->mv, reps, sc, m->stream);
+            n += sbr::launch_rollout_advance(rr, j, pick, slack ? tb.eptr : nullptr, tb.excl, ro, m->stream);
+            t.tp.launches = (uint64_t)n;
+        }
+        if (j + 1 == rc.steps && !final_state) break; /* nobody reads the state after the last pick */
+        ScopedTimer t(m, SBR_K_RECURRENT_FWD, lstm ? 2 : 1);
+        if (sbr::launch_rollout_step(m->mv, st->v, rr, j, m->stream) < 0) return SBR_ERR_UNSUPPORTED;
+    }
+    if (final_state) { /* the first embedding_dim columns of the rows after the last step */
+        const sbr::SessionView fin{lstm ? rr.Hs + (size_t)((rc.steps - 1) & 1u) * parity_stride : rr.Hs,
+                                   lstm ? rr.Cs + (size_t)((rc.steps - 1) & 1u) * parity_stride : nullptr, nullptr};
+        sbr::launch_session_get_state(fin, d_ident, (int)nu, m->d, m->dl, fin_h, fin_c, nullptr, m->stream);
+    }
+    HIPCHK(hipGetLastError());
+    uint32_t flag = 0;
+    HIPCHK(hipStreamSynchronize(m->stream));
+    HIPCHK(hipMemcpy(&flag, tb.flag, 4, hipMemcpyDeviceToHost));
+    if (flag) return SBR_ERR_INVALID_PREDICTION; /* a non-finite score at any step fails the whole call */
+    const CopyOut outs[] = {{rc.out_items + c0 * S, ro.items, nu * S * 4},
+                            {rc.out_scores ? rc.out_scores + c0 * S : nullptr, ro.scores, nu * S * 4},
+                            {rc.out_keys ? rc.out_keys + c0 * S : nullptr, ro.keys, nu * S * 4},
+                            {rc.out_lengths ? rc.out_lengths + c0 : nullptr, rr.lengths, nu * 4},
+                            {part ? rc.out_shift + c0 * S : nullptr, ro.shift, nu * S * 4},
+                            {part ? rc.out_mass + c0 * S : nullptr, ro.mass, nu * S * 8},
+                            {rc.out_h ? rc.out_h + c0 * dl : nullptr, fin_h, nu * dl * 4},
+                            {rc.out_c ? rc.out_c + c0 * dl : nullptr, fin_c, nu * dl * 4}};
+    for (const CopyOut& o : outs)
+        if (o.host) HIPCHK(hipMemcpy(o.host, o.device, o.bytes, hipMemcpyDeviceToHost));
+    return SBR_OK;
+}
+
+}  // namespace
+
+sbr_status sbr_sessions_rollout(sbr_sessions* st, const uint32_t* slots, uint64_t n, const struct sbr_rollout_args* args,
+                                const uint64_t* excl_ptr, const uint32_t* excl_items, const uint32_t* any_of, const uint32_t* none_of,
+                                uint32_t* out_items, float* out_scores, float* out_keys, uint32_t* out_lengths, float* out_shift,
+                                uint64_t* out_mass, uint32_t* out_frac_bits, float* out_h, float* out_c) {
+    constexpr uint32_t known = SBR_ROLLOUT_SAMPLE | SBR_ROLLOUT_ALLOW_REPEATS | SBR_ROLLOUT_INCLUDE_SEEN;
+    if (!st || !args || (n && !out_items)) return SBR_ERR_INVALID_ARGUMENT;
+    if (args->steps < 1 || args->steps > SBR_ROLLOUT_MAX_STEPS || (args->flags & ~known)) return SBR_ERR_INVALID_ARGUMENT;
+    const bool sample = (args->flags & SBR_ROLLOUT_SAMPLE) != 0;
+    Sample sm;
+    TagFilterArg hold;
+    if (!sample_args(&args->sample, out_keys, &sm)) return SBR_ERR_INVALID_ARGUMENT;
+    if (!sample && out_keys) return SBR_ERR_INVALID_ARGUMENT; /* a greedy pick has no key */
+    if ((out_shift != nullptr) != (out_mass != nullptr) || (out_shift && !out_frac_bits)) return SBR_ERR_INVALID_ARGUMENT;
+    if ((args->flags & SBR_ROLLOUT_INCLUDE_SEEN) && !st->seen.w) return SBR_ERR_INVALID_ARGUMENT; /* nothing to include */
+    if (out_c && (!out_h || !st->m->ng)) return SBR_ERR_INVALID_ARGUMENT;                         /* c: the LSTM's, with h */
+    if (out_h && st->m->ng && !out_c) return SBR_ERR_INVALID_ARGUMENT;
+    if (!excl_args_ok(excl_ptr, excl_items, n)) return SBR_ERR_INVALID_ARGUMENT;
+    sbr_model* m = st->m;
+    std::lock_guard<std::mutex> lock(m->mu);
+    SBRCHK(enter_sessions(st));
+    SBRCHK(check_slots(st, slots, n));
+    if (excl_ptr) SBRCHK(check_csr(m, excl_ptr, n, excl_items, false));
+    RolloutCall rc{};
+    rc.steps = args->steps;
+    rc.allow_repeats = (args->flags & SBR_ROLLOUT_ALLOW_REPEATS) != 0;
+    rc.seen = st->seen.w && !(args->flags & SBR_ROLLOUT_INCLUDE_SEEN);
+    rc.sm = sample ? &sm : nullptr;
+    rc.flt = sample_filter(any_of, none_of, &hold);
+    if (rc.flt && !m->item_tags) return SBR_ERR_INVALID_ARGUMENT;
+    rc.inv_t = sm.inv_t;
+    rc.out_items = out_items; rc.out_scores = out_scores; rc.out_keys = out_keys; rc.out_lengths = out_lengths;
+    rc.out_shift = out_shift; rc.out_mass = out_mass; rc.out_h = out_h; rc.out_c = out_c;
+    const std::vector<int> rep0 = session_rep_rows(st, slots, n);
+    const size_t cap = rollout_chunk_cap(m, rc.seen ? st->seen.w : 0, rc.steps);
+    for (size_t c0 = 0; c0 < n; c0 += cap) SBRCHK(sessions_rollout_chunk(st, slots, rep0, excl_ptr, excl_items, rc, c0, std::min<size_t>(cap, n - c0)));
+    if (out_frac_bits) *out_frac_bits = sbr_softmax_fbits((uint32_t)m->hp.num_items);
+    return SBR_OK;
+}
+
+/* ---------------------------------------------------------------------------------------------
  * item sets: every catalogue call restricted to a resident sub-table (ITEM SETS in include/sbr_hip.h)
  * ------------------------------------------------------------------------------------------- */
 namespace {

@@ -549,6 +549,43 @@ void launch_session_seen_counts(const SeenView& sn, const uint32_t* slot, int n,
  * return value; 0 where nothing is to do). */
 int launch_session_replay_feed(const SeenView& sn, const uint32_t* slot, const uint32_t* count, int n, int tm, const int* off,
                                const unsigned long long* start, uint32_t* items, hipStream_t s);
+/* A rollout chunk (sbr_sessions.hip; the contract: ROLLOUT in include/sbr_hip.h): n sessions advanced `steps` times by their own
+ * picks on scratch memory, the store read only.  Device arrays: slot [n] the sessions' store rows; ident [n] = 0 .. n - 1 and (EWMA)
+ * start [n] = 0 .. n - 1, the step kernels' indices into the scratch; Hs / Cs the scratch state — LSTM: [2][n][d] each, written
+ * alternately, step j into parity j & 1; EWMA: Hs [n][d] stepped in place with len [n], Cs null; feed / count [n] the next cell step's
+ * item and whether the row takes it; ended / lengths [n].
+ * launch_rollout_begin: ended = 0, lengths = steps, and for EWMA the scratch rows and lengths copied from the store.
+ * launch_rollout_segments: row i's tight non-decreasing segment src[src_ptr[i], src_ptr[i + 1]) to out at src_ptr[i] + i slack, then
+ *   `slack` entries of 0xFFFFFFFF.
+ * launch_rollout_advance: step j's picks p (stride 1, the scan's outputs; keys / shift / mass null where o's are) into column j of
+ *   o [n][steps], the rows' ends, the feed, and — ins_ptr non-null — each live pick into its row's segment [ins_ptr[i],
+ *   ins_ptr[i + 1]) of excl, which must end in 0xFFFFFFFF.
+ * launch_rollout_step: one cell step of every row by its feed item (LSTM: from the store through `slot` at j == 0; an ended row keeps
+ *   its state).  Each returns the launches it queued; launch_rollout_step -1 where there is no kernel for m.d. */
+struct RolloutRows {
+    int n;
+    uint32_t steps;
+    const uint32_t *slot, *ident;
+    const unsigned long long* start;
+    float *Hs, *Cs;
+    unsigned long long* len;
+    uint32_t *feed, *count, *ended, *lengths;
+};
+struct RolloutPick {
+    const uint32_t* items;
+    const float *scores, *keys, *shift;
+    const unsigned long long* mass;
+};
+struct RolloutOut {
+    uint32_t* items;
+    float *scores, *keys, *shift;
+    unsigned long long* mass;
+};
+int launch_rollout_begin(const ModelView& m, const SessionView& sv, const RolloutRows& r, hipStream_t s);
+int launch_rollout_segments(const uint64_t* src_ptr, const uint32_t* src, int n, uint32_t slack, uint32_t* out, hipStream_t s);
+int launch_rollout_advance(const RolloutRows& r, uint32_t j, const RolloutPick& p, const uint64_t* ins_ptr, uint32_t* excl, const RolloutOut& o,
+                           hipStream_t s);
+int launch_rollout_step(const ModelView& m, const SessionView& sv, const RolloutRows& r, uint32_t j, hipStream_t s);
 /* The inverted seen lists of an audience scan (sbr_sessions.hip): which candidates' memories hold which query item.  The chunk's
  * queries come sorted by item: qs_item [nq] ascending (repeats kept), qs_idx [nq] the query each stands for; candidate position p
  * is slot cand_slot[p].  A key is (query << 32 | position), one per (query, position) whose slot's min(cnt, w) valid ring entries hold

@@ -24,6 +24,11 @@
 //                                step kernels above read an append call's (LSTM time-major through an LDS transpose / EWMA session-major)
 //   session_seen_count_kernel  : cnt of named slots, for the host's replay plan
 //
+// A rollout (sbr_sessions_rollout) reads a store and writes scratch only:
+//   rollout_begin_kernel / rollout_segments_kernel : a chunk's scratch state and its exclusion CSR with one entry of slack per step
+//   rollout_advance_kernel     : per step, the scan's pick into the outputs, the row's exclusion segment and the next step's feed
+//   rollout_carry_kernel       : an ended row's state kept across the LSTM step
+//
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off (see sbr_rs_amd/build.py).
 
 #include "sbr_kernels.h"
@@ -582,6 +587,132 @@ __global__ __launch_bounds__(256) void audience_seen_csr_kernel(const uint64_t* 
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Rollout (sbr_sessions_rollout; the contract: ROLLOUT in include/sbr_hip.h): a chunk's sessions advanced by their own picks, step
+// after step, on SCRATCH rows — none of these kernels is given a pointer into the store that it writes through.  Per step the
+// unchanged k = 1 scan leaves row i's pick in stride-1 arrays, rollout_advance_kernel below turns it into column j of the outputs,
+// the next scan's exclusion and the next cell step's item, and the step kernels above advance the scratch state.
+// ------------------------------------------------------------------------------------------------
+
+// The chunk's start: ended = 0 and lengths = steps for every row (a row that never ends keeps that), and for EWMA — whose step
+// kernel works in place — the scratch rows S[i] = H[slot[i]] at the storage width with slen[i] = len[slot[i]].  S null (LSTM): the
+// first cell step reads the store's rows itself, through the slot index, as an append's first step does.
+__global__ __launch_bounds__(256) void rollout_begin_kernel(const uint32_t* __restrict__ slot, int n, int d, uint32_t steps,
+                                                            const float* __restrict__ H, const unsigned long long* __restrict__ len,
+                                                            float* __restrict__ S, unsigned long long* __restrict__ slen,
+                                                            uint32_t* __restrict__ ended, uint32_t* __restrict__ lengths) {
+    const int L = d / 4;
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t i = idx / L;
+    if (i >= (size_t)n) return;
+    const int c4 = (int)(idx % L) * 4;
+    if (S) st4(S + i * d + c4, ld4(H + (size_t)slot[i] * d + c4));
+    if (c4 == 0) {
+        if (S) slen[i] = len[slot[i]];
+        ended[i] = 0u;
+        lengths[i] = steps;
+    }
+}
+
+// The chunk's exclusion CSR with slack: row i's tight segment src[src_ptr[i], src_ptr[i + 1]) — non-decreasing, a 0xFFFFFFFF tail
+// allowed: the caller's sorted list, or session_seen_lists_kernel's merge — to out[src_ptr[i] + i * slack ..), followed by `slack`
+// entries of 0xFFFFFFFF: the room rollout_advance_kernel's inserts take.  One wave per row; every entry of the output is written.
+__global__ __launch_bounds__(256) void rollout_segments_kernel(const uint64_t* __restrict__ src_ptr, const uint32_t* __restrict__ src, int n,
+                                                               uint32_t slack, uint32_t* __restrict__ out) {
+    const int i = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
+    if (i >= n) return;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t s0 = src_ptr[i], have = src_ptr[i + 1] - s0;
+    uint32_t* o = out + s0 + (uint64_t)i * slack;
+    for (uint64_t q = lane; q < have + slack; q += 64u) o[q] = q < have ? src[s0 + q] : 0xFFFFFFFFu;
+}
+
+// One wave per row, step j of a rollout.  The row's merged pick (pick_items[i]; 0xFFFFFFFF: nothing was eligible) becomes
+//   column j of the outputs: the pick with its plain score, and where asked for its key and the step's shift and mass — or, for a
+//     row that has ended, (0xFFFFFFFF, -inf, -inf, -inf, 0);
+//   the row's end: the first padding sets ended[i] and lengths[i] = j, once — an ended row stays ended whatever its scans return;
+//   the next cell step's feed: feed[i] = the pick and count[i] = 1, or item 0 (any valid row of E) and count[i] = 0 for an ended row,
+//     whose state the step leaves alone (EWMA) or rollout_carry_kernel restores (LSTM);
+//   the next scan's exclusion, where ins_ptr is given: the pick inserted into the row's sorted segment [ins_ptr[i], ins_ptr[i + 1]).
+//     The segment is non-decreasing with a 0xFFFFFFFF tail at least one entry long (rollout_segments_kernel's slack: one entry per
+//     step), and does not hold the pick — the scan has just offered it — so its place is the number of entries below it, counted by
+//     the wave; the tail from there moves up by one entry, 64 at a time from the top, each round's loads complete (its stores carry
+//     the loaded values) before its stores and so before the next round's stores, which land below it; then lane 0 writes the pick.
+//     O(segment) per row and step.
+// No atomics; rows are independent and a row is one wave's.
+__global__ __launch_bounds__(256) void rollout_advance_kernel(int n, uint32_t steps, uint32_t j, const uint32_t* __restrict__ pick_items,
+                                                              const float* __restrict__ pick_scores, const float* __restrict__ pick_keys,
+                                                              const float* __restrict__ pick_shift,
+                                                              const unsigned long long* __restrict__ pick_mass,
+                                                              const uint64_t* __restrict__ ins_ptr, uint32_t* excl, uint32_t* ended,
+                                                              uint32_t* __restrict__ lengths, uint32_t* __restrict__ feed,
+                                                              uint32_t* __restrict__ count, uint32_t* __restrict__ out_items,
+                                                              float* __restrict__ out_scores, float* __restrict__ out_keys,
+                                                              float* __restrict__ out_shift, unsigned long long* __restrict__ out_mass) {
+    constexpr uint32_t NONE = 0xFFFFFFFFu;
+    const int i = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
+    if (i >= n) return;
+    const uint32_t lane = threadIdx.x & 63u;
+    const bool was = ended[i] != 0u;
+    const uint32_t v = was ? NONE : pick_items[i];
+    const bool live = v != NONE;
+    if (lane == 0) {
+        const size_t o = (size_t)i * steps + j;
+        out_items[o] = v;
+        out_scores[o] = live ? pick_scores[i] : -INFINITY;
+        if (out_keys) out_keys[o] = live ? pick_keys[i] : -INFINITY;
+        if (out_shift) {
+            out_shift[o] = live ? pick_shift[i] : -INFINITY;
+            out_mass[o] = live ? pick_mass[i] : 0ull;
+        }
+        feed[i] = live ? v : 0u;
+        count[i] = live ? 1u : 0u;
+        if (!live && !was) {
+            ended[i] = 1u;
+            lengths[i] = j;
+        }
+    }
+    if (!live || !ins_ptr) return;
+    const uint64_t e0 = ins_ptr[i], len = ins_ptr[i + 1] - e0;
+    uint32_t* seg = excl + e0;
+    uint32_t below = 0;
+    for (uint64_t q = lane; q < len; q += 64u) below += seg[q] < v ? 1u : 0u;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) below += __shfl_xor(below, off, 64);
+    const uint64_t pos = below; /* < len: the segment's last entry is 0xFFFFFFFF, above every pick */
+    for (uint64_t hi = len; hi > pos + 1;) {
+        const uint64_t lo = hi - (pos + 1) > 64u ? hi - 64u : pos + 1;
+        const uint64_t dst = lo + lane;
+        uint32_t x = 0;
+        if (dst < hi) x = seg[dst - 1];
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        if (dst < hi) seg[dst] = x;
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        hi = lo;
+    }
+    if (lane == 0) seg[pos] = v;
+}
+
+// Behind an LSTM cell step of a rollout: an ended row's state, which the step has just advanced by the feed's stand-in item, is put
+// back — row b of Hout / Cout = the row the step read (session_lstm_step_kernel's in_row / len rule: zeros for an empty slot at the
+// rollout's first step).  So the next scan reads finite data and the final state is the row's last real one.  16 B per lane.
+__global__ __launch_bounds__(256) void rollout_carry_kernel(const uint32_t* __restrict__ ended, int n, int d, const uint32_t* __restrict__ in_row,
+                                                            const unsigned long long* __restrict__ len, const float* __restrict__ Hin,
+                                                            const float* __restrict__ Cin, float* __restrict__ Hout, float* __restrict__ Cout) {
+    const int L = d / 4;
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t b = idx / L;
+    if (b >= (size_t)n || !ended[b]) return;
+    const int c4 = (int)(idx % L) * 4;
+    const size_t r = in_row ? (size_t)in_row[b] : b;
+    const bool zero = len && len[r] == 0ull;
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+    st4(Hout + b * d + c4, zero ? z : ld4(Hin + r * d + c4));
+    st4(Cout + b * d + c4, zero ? z : ld4(Cin + r * d + c4));
+}
+
 namespace {
 
 inline unsigned blocks_for(size_t threads) { return (unsigned)((threads + 255) / 256); }
@@ -634,6 +765,77 @@ int launch_session_append(const ModelView& m, const SessionView& sv, const Sessi
     }
 #undef SBR_SESSION_D
     return a.tm > 0 ? (m.ng ? a.tm + 1 : 1) : 0;
+}
+
+namespace {
+
+/* step j of a rollout's LSTM chunk: every row one cell step by its feed item into the scratch rows of parity j & 1 — from the store's
+ * rows through the slot index at j == 0, as an append's first step, from the other parity afterwards — then the ended rows' carry */
+template <int D>
+void rollout_lstm_step_d(const ModelView& m, const SessionView& sv, const RolloutRows& r, uint32_t j, hipStream_t s) {
+    const size_t parity_stride = (size_t)r.n * D;
+    const float* Hin = j == 0 ? sv.H : r.Hs + (size_t)((j - 1) & 1u) * parity_stride;
+    const float* Cin = j == 0 ? sv.C : r.Cs + (size_t)((j - 1) & 1u) * parity_stride;
+    float* Hout = r.Hs + (size_t)(j & 1u) * parity_stride;
+    float* Cout = r.Cs + (size_t)(j & 1u) * parity_stride;
+    const uint32_t* in_row = j == 0 ? r.slot : nullptr;
+    const unsigned long long* len = j == 0 ? sv.len : nullptr;
+    const dim3 grid((unsigned)((r.n + 31) / 32), D / 16);
+    if (m.ng == 4)
+        hipLaunchKernelGGL((session_lstm_step_kernel<D, 4>), grid, dim3(256), 0, s, m, r.feed, r.n, in_row, len, Hin, Cin, Hout, Cout);
+    else
+        hipLaunchKernelGGL((session_lstm_step_kernel<D, 3>), grid, dim3(192), 0, s, m, r.feed, r.n, in_row, len, Hin, Cin, Hout, Cout);
+    hipLaunchKernelGGL(rollout_carry_kernel, dim3(blocks_for((size_t)r.n * (D / 4))), dim3(256), 0, s, r.ended, r.n, D, in_row, len, Hin, Cin, Hout,
+                       Cout);
+}
+
+/* step j of a rollout's EWMA chunk, in place on the scratch rows: row i's feed item where count[i] == 1, nothing where it is 0 */
+template <int D>
+void rollout_ewma_step_d(const ModelView& m, const RolloutRows& r, hipStream_t s) {
+    hipLaunchKernelGGL((session_ewma_step_kernel<D>), dim3(blocks_for((size_t)r.n * (D / 4))), dim3(256), 0, s, m, r.ident, r.start, r.count, r.n,
+                       r.feed, r.Hs, r.len, 1);
+}
+
+}  // namespace
+
+int launch_rollout_begin(const ModelView& m, const SessionView& sv, const RolloutRows& r, hipStream_t s) {
+    if (r.n <= 0) return 0;
+    hipLaunchKernelGGL(rollout_begin_kernel, dim3(blocks_for((size_t)r.n * (m.d / 4))), dim3(256), 0, s, r.slot, r.n, m.d, r.steps, sv.H, sv.len,
+                       m.ng ? nullptr : r.Hs, r.len, r.ended, r.lengths);
+    return 1;
+}
+
+int launch_rollout_segments(const uint64_t* src_ptr, const uint32_t* src, int n, uint32_t slack, uint32_t* out, hipStream_t s) {
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(rollout_segments_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, src_ptr, src, n, slack, out);
+    return 1;
+}
+
+int launch_rollout_advance(const RolloutRows& r, uint32_t j, const RolloutPick& p, const uint64_t* ins_ptr, uint32_t* excl, const RolloutOut& o,
+                           hipStream_t s) {
+    if (r.n <= 0) return 0;
+    hipLaunchKernelGGL(rollout_advance_kernel, dim3((unsigned)((r.n + 3) / 4)), dim3(256), 0, s, r.n, r.steps, j, p.items, p.scores, p.keys, p.shift,
+                       p.mass, ins_ptr, excl, r.ended, r.lengths, r.feed, r.count, o.items, o.scores, o.keys, o.shift, o.mass);
+    return 1;
+}
+
+int launch_rollout_step(const ModelView& m, const SessionView& sv, const RolloutRows& r, uint32_t j, hipStream_t s) {
+    if (r.n <= 0) return 0;
+#define SBR_ROLLOUT_D(DD)                                          \
+    case DD:                                                       \
+        if (m.ng) rollout_lstm_step_d<DD>(m, sv, r, j, s);         \
+        else rollout_ewma_step_d<DD>(m, r, s);                     \
+        break;
+    switch (m.d) {
+        SBR_ROLLOUT_D(16)
+        SBR_ROLLOUT_D(32)
+        SBR_ROLLOUT_D(64)
+        SBR_ROLLOUT_D(128)
+        SBR_ROLLOUT_D(256)
+        default: return -1; /* no such storage width: the caller fails the call */
+    }
+#undef SBR_ROLLOUT_D
+    return m.ng ? 2 : 1;
 }
 
 void launch_session_reset(const SessionView& sv, const uint32_t* slot, int n, int d, hipStream_t s) {

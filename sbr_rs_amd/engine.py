@@ -175,6 +175,43 @@ def _partition_outputs(n: int):
     return np.zeros(max(n, 1), dtype=np.float32)[:n], np.zeros(max(n, 1), dtype=np.uint64)[:n], C.c_uint32(0)
 
 
+ROLLOUT_MODES = ("greedy", "sample")
+
+
+class Rollout:
+    """What ``Sessions.rollout`` returns: ``items`` u32 [n, steps] and ``scores`` f32 [n, steps] — row i's picks in pick order with
+    their plain scores, (0xFFFFFFFF, -inf) from the step at which the row had nothing left to choose from — and ``lengths`` u32 [n],
+    the real steps of each row.  ``keys`` f32 [n, steps]: the winning keys of a sampled rollout, else None.  With ``log_prob``:
+    ``shift`` f32 / ``mass`` u64 [n, steps] and ``frac_bits``, each step's ``log_partition`` over what the row could still see, and
+    ``log_prob`` f64 [n, steps] = ``Partition.log_prob`` of the pick on them (NaN at padding); else None.  With ``final_state``:
+    ``h``, ``c`` (None for EWMA) and ``len``, in ``Sessions.state``'s format, after all picks; else None."""
+
+    def __init__(self, items, scores, lengths, keys=None, shift=None, mass=None, frac_bits=None, log_prob=None, h=None, c=None, len=None):
+        self.items, self.scores, self.lengths, self.keys = items, scores, lengths, keys
+        self.shift, self.mass, self.frac_bits, self.log_prob = shift, mass, frac_bits, log_prob
+        self.h, self.c, self.len = h, c, len
+
+    def rows(self):
+        """Each row's real picks, one u32 array per row: what ``Sessions.append(slots, rollout.rows())`` makes happen."""
+        return [self.items[i, : int(n)].copy() for i, n in enumerate(self.lengths)]
+
+
+def _rollout_args(steps, mode, temperature):
+    """The checks of a rollout that need no library: steps, mode, temperature -> (steps, sample)."""
+    from ._abi import ROLLOUT_MAX_STEPS
+
+    if mode not in ROLLOUT_MODES:
+        raise ValueError(f"mode {mode!r}: 'greedy' or 'sample'")
+    if isinstance(steps, bool) or int(steps) != steps or not 1 <= int(steps) <= ROLLOUT_MAX_STEPS:
+        raise ValueError(f"steps: 1..{ROLLOUT_MAX_STEPS}; got {steps!r}")
+    t = np.float32(temperature)
+    with np.errstate(divide="ignore", over="ignore"):
+        inv = np.float32(1.0) / t
+    if not (np.isfinite(t) and t > 0 and np.isfinite(inv) and inv != 0):
+        raise ValueError(f"temperature: finite and > 0, with a finite f32 reciprocal; got {temperature!r}")
+    return int(steps), mode == "sample"
+
+
 ABOVE_MAX_RESULTS = 1 << 24  # the *_above calls' default max_results: the entries of the one buffer they call with
 ABOVE_ORDERS = ("score", "id")
 
@@ -1477,6 +1514,27 @@ class Model:
         recommend / recommend_diverse exclude them."""
         return Sessions(self, capacity, remember)
 
+    def rollout(self, histories, steps: int, mode: str = "greedy", temperature: float = 1.0, seed: int = 0, streams=None,
+                exclude_history: bool = True, any_of=None, none_of=None, allow_repeats: bool = False, log_prob: bool = False,
+                final_state: bool = False) -> Rollout:
+        """``Sessions.rollout`` from histories (a list of item-id sequences), DEFINED as this sequence of calls: a temporary store
+        of one slot per history, ``append`` of each history's last max_sequence_length items, and ``store.rollout`` of all slots
+        with — ``exclude_history`` — each history's items as ``exclude``.  Streams default to the row's index, the slot id."""
+        _rollout_args(steps, mode, temperature)
+        seqs = [np.asarray(h, dtype=np.uint32).ravel() for h in histories]
+        if not seqs:
+            raise ValueError("histories: at least one")
+        T = int(self.hp.max_sequence_length)
+        store = Sessions(self, len(seqs))
+        try:
+            slots = np.arange(len(seqs), dtype=np.uint32)
+            store.append(slots, [s[-T:] if s.size > T else s for s in seqs])
+            return store.rollout(slots, steps, mode=mode, temperature=temperature, seed=seed, streams=streams,
+                                 exclude=seqs if exclude_history else None, any_of=any_of, none_of=none_of, allow_repeats=allow_repeats,
+                                 log_prob=log_prob, final_state=final_state)
+        finally:
+            store.close()
+
     def item_set(self, item_ids) -> "ItemSet":
         """An item set of this model (sbr_item_set_create; ``ItemSet``): ``item_ids`` in any order, duplicates allowed, each below
         num_items.  Its rows are gathered to the device once; every catalogue call is then offered restricted to the set."""
@@ -1859,6 +1917,61 @@ class Sessions:
         from .persistence import save_sessions
 
         save_sessions(self, path)
+
+    def rollout(self, slots, steps: int, mode: str = "greedy", temperature: float = 1.0, seed: int = 0, streams=None, exclude=None,
+                any_of=None, none_of=None, include_seen: bool = False, allow_repeats: bool = False, log_prob: bool = False,
+                final_state: bool = False) -> Rollout:
+        """Each slot's next ``steps`` items, each chosen given the ones before it, picked and fed back on the device
+        (sbr_sessions_rollout) — what a host loop of ``recommend(slots, 1, exclude)`` + ``append`` + a rebuilt ``exclude`` returns,
+        without its round trips and WITHOUT writing the store: a rollout is hypothetical, ``append(slots, result.rows())`` makes it
+        happen.  Step j picks among what ``recommend`` would offer at call time (``exclude``, the seen-item memory unless
+        ``include_seen``, ``any_of`` / ``none_of``) minus picks 0 .. j - 1 — with ``allow_repeats`` the picks stay eligible — scored
+        against the state after those picks, advanced as ``append`` advances it.  ``mode="greedy"``: the top-1 in every call's
+        order.  ``mode="sample"``: the one draw of ``recommend_sampled(k=1, temperature, seed=seed + j, streams)``; ``streams``
+        default to the slot ids, so the same (seed, streams) returns the same trajectory whatever the batch.  A row with nothing
+        left ends: padding from there on, ``lengths[i]`` its real steps.  ``log_prob``: each step's exact partition at
+        ``temperature`` and the pick's log-probability under it, in either mode.  ``final_state``: the states after all picks.
+        The insert of a pick into its row's exclusion list costs O(list) per step; steps <= 1 024."""
+        from ._abi import ROLLOUT_ALLOW_REPEATS, ROLLOUT_INCLUDE_SEEN, ROLLOUT_SAMPLE, SbrRolloutArgs
+
+        steps, sample = _rollout_args(steps, mode, temperature)
+        if include_seen and not self._seen:
+            raise ValueError("include_seen: this store has no seen-item memory (sessions(capacity, remember=W))")
+        sl = self._slots(slots)
+        n = sl.size
+        masks = _tag_masks(any_of, none_of, n)
+        sa, _keep = _sample_args(temperature, seed, streams, n)
+        ep, ei = _exclusion_csr(exclude, n)
+        ra = SbrRolloutArgs()
+        ra.steps = steps
+        ra.flags = (ROLLOUT_SAMPLE if sample else 0) | (ROLLOUT_ALLOW_REPEATS if allow_repeats else 0) | (ROLLOUT_INCLUDE_SEEN if include_seen else 0)
+        ra.sample = sa
+        items = np.zeros((n, steps), dtype=np.uint32)
+        scores = np.zeros((n, steps), dtype=np.float32)
+        keys = np.zeros((n, steps), dtype=np.float32) if sample else None
+        lengths = np.zeros(max(n, 1), dtype=np.uint32)
+        shift = np.zeros((n, steps), dtype=np.float32) if log_prob else None
+        mass = np.zeros((n, steps), dtype=np.uint64) if log_prob else None
+        fb = C.c_uint32(0)
+        h = np.zeros((n, self.model.dim), dtype=np.float32) if final_state else None
+        c = np.zeros((n, self.model.dim), dtype=np.float32) if final_state and self._lstm else None
+
+        def opt(a):
+            return None if a is None else _ptr(a)
+
+        _check(self._L.sbr_sessions_rollout(self._h, _ptr(sl), n, C.byref(ra), opt(ep), opt(ei), None if masks is None else _ptr(masks[0]),
+                                            None if masks is None else _ptr(masks[1]), _ptr(items), _ptr(scores), opt(keys), _ptr(lengths),
+                                            opt(shift), opt(mass), C.byref(fb) if log_prob else None, opt(h), opt(c)))
+        lengths = lengths[:n]
+        out = Rollout(items, scores, lengths, keys=keys)
+        if log_prob:  # one partition row per (row, step): the host's one statement of the weights, no second exponential
+            part = Partition(temperature, shift.reshape(-1), mass.reshape(-1), fb.value)
+            lp = part.log_prob(scores.reshape(-1, 1)).reshape(n, steps)
+            lp[items == RECOMMEND_NO_ITEM] = np.nan
+            out.shift, out.mass, out.frac_bits, out.log_prob = shift, mass, fb.value, lp
+        if final_state:
+            out.h, out.c, out.len = h, c, self.lengths(sl) + lengths.astype(np.uint64)
+        return out
 
     def state(self, slots):
         """Checkpoint of the named slots: (h [n, embedding_dim], c likewise — None for EWMA —, len [n] u64)."""

@@ -493,6 +493,17 @@ class _ImplicitSequenceModel:
         ``recommend_diverse`` of the store exclude them as ``recommend`` excludes the history."""
         return self.params.sessions(capacity, remember)
 
+    def rollout(self, histories, steps: int, mode: str = "greedy", temperature: float = 1.0, seed: int = 0, streams=None,
+                exclude_history: bool = True, any_of=None, none_of=None, allow_repeats: bool = False, log_prob: bool = False,
+                final_state: bool = False):
+        """Each history's next ``steps`` items, each chosen given the ones before it, picked and fed back on the device
+        (``engine.Rollout``; ``engine.Sessions.rollout`` is the call, and its docstring the contract): defined as a temporary session
+        store, ``append`` of each history's last max_sequence_length items and ``store.rollout`` — ``mode="greedy"`` the top-1 per
+        step, ``mode="sample"`` one draw of ``recommend_sampled`` per step at seed + step."""
+        return self.params.rollout(histories, steps, mode=mode, temperature=temperature, seed=seed, streams=streams,
+                                   exclude_history=exclude_history, any_of=any_of, none_of=none_of, allow_repeats=allow_repeats,
+                                   log_prob=log_prob, final_state=final_state)
+
     def load_sessions(self, path, capacity=None, remember=None, replay: bool = False):
         """A session store restored from a file written by ``store.save(path)`` (``persistence.load_sessions``).  With
         ``replay=True`` only the remembered items are restored and every state is recomputed from them on the device under this
