@@ -618,6 +618,31 @@ struct Rollout {
     std::vector<float> h, c;
     std::vector<std::uint64_t> len;
 };
+/// The arguments of the beam-search calls (struct sbr_beam_args and the lists around it; BEAM SEARCH in sbr_hip.h): `width` beams
+/// per row, `temperature` the per-step partition's; `partitions`: each (beam, step)'s shift and mass are returned too.
+struct BeamArgs {
+    std::size_t steps = 1, width = 4;
+    float temperature = 1.0f;
+    bool allow_repeats = false, include_seen = false, partitions = false;
+    TagFilter filter;
+    std::vector<std::uint64_t> excl_ptr;
+    std::vector<std::uint32_t> excl_items;
+};
+/// What the beam-search calls return, beams in selection order at each row's last real step: items, scores and step_lp
+/// [num_rows][width][steps] (padding (0xFFFFFFFF, -inf), -inf in step_lp), cum [num_rows][width] (-inf for a missing beam), lengths
+/// (the real steps) and beams (the live beams) [num_rows].  With partitions: `partition` holds one row per (row, beam, step) — shift
+/// -inf and mass 0 at padding.
+struct Beams {
+    std::size_t num_rows = 0, width = 0, steps = 0;
+    std::vector<std::uint32_t> items, lengths, beams;
+    std::vector<float> scores, step_lp, cum;
+    Partition partition;
+    /// beam 0 of row i, its real picks
+    std::vector<std::uint32_t> best(std::size_t i) const {
+        const std::size_t n = beams[i] ? lengths[i] : 0;
+        return std::vector<std::uint32_t>(items.begin() + (std::ptrdiff_t)(i * width * steps), items.begin() + (std::ptrdiff_t)(i * width * steps + n));
+    }
+};
 /// What ImplicitSequenceModel::sequence_partition returns (SEQUENCE PARTITION in sbr_hip.h), CSR over the kept positions: user u's
 /// are entries ptr[u] .. ptr[u + 1), positions ascending, of the partition's rows, of `scores` (the targets' plain scores) and of
 /// `masked` (1 where the policy masks the target: its log-probability is -inf).
@@ -1162,6 +1187,51 @@ class Sessions {
             check(sbr_sessions_lengths(h_, slots.data(), (std::uint64_t)n, r.len.data()), "sbr_sessions_lengths");
             for (std::size_t i = 0; i < n; ++i) r.len[i] += r.lengths[i];
         }
+        return R::Ok(std::move(r));
+    }
+    /// The a.width most likely next-a.steps continuations of each slot, searched on the device (sbr_sessions_beam_search; greedy,
+    /// deterministic) WITHOUT writing the store.  Eligibility is rollout's, minus each beam's own path unless allow_repeats; each
+    /// live beam offers its first width eligible items per step, and the row keeps the width best offers by (cumulative f32 lp
+    /// descending, parent beam ascending, offer position ascending).  width <= SBR_BEAM_MAX_WIDTH, steps <= SBR_ROLLOUT_MAX_STEPS.
+    Result<Beams, PredictionError> beam_search(const std::vector<std::uint32_t>& slots, const BeamArgs& a) const {
+        using R = Result<Beams, PredictionError>;
+        if (a.steps < 1 || a.steps > SBR_ROLLOUT_MAX_STEPS) throw EngineError(SBR_ERR_INVALID_ARGUMENT, "Sessions::beam_search: steps outside 1..SBR_ROLLOUT_MAX_STEPS");
+        if (a.width < 1 || a.width > SBR_BEAM_MAX_WIDTH) throw EngineError(SBR_ERR_INVALID_ARGUMENT, "Sessions::beam_search: width outside 1..SBR_BEAM_MAX_WIDTH");
+        if (!a.excl_ptr.empty() && (a.excl_ptr.size() != slots.size() + 1 || a.excl_ptr.back() > a.excl_items.size()))
+            throw EngineError(SBR_ERR_INVALID_ARGUMENT, "Sessions::beam_search: one exclusion range per slot");
+        const std::size_t n = slots.size(), cells = n * a.width * a.steps;
+        const bool filtered = !a.filter.any_of.empty() || !a.filter.none_of.empty();
+        const std::vector<std::uint32_t> any = tag_masks(a.filter.any_of, n, "Sessions::beam_search: one any_of mask per slot");
+        const std::vector<std::uint32_t> none_of = tag_masks(a.filter.none_of, n, "Sessions::beam_search: one none_of mask per slot");
+        sbr_beam_args ba{};
+        ba.steps = (std::uint32_t)a.steps;
+        ba.width = (std::uint32_t)a.width;
+        ba.flags = (a.allow_repeats ? SBR_ROLLOUT_ALLOW_REPEATS : 0u) | (a.include_seen ? SBR_ROLLOUT_INCLUDE_SEEN : 0u);
+        ba.temperature = a.temperature;
+        Beams r;
+        r.num_rows = n;
+        r.width = a.width;
+        r.steps = a.steps;
+        r.items.resize(cells);
+        r.scores.resize(cells);
+        r.step_lp.resize(cells);
+        r.cum.resize(n * a.width);
+        r.lengths.resize(n);
+        r.beams.resize(n);
+        if (a.partitions) {
+            r.partition.temperature = a.temperature;
+            r.partition.shift.resize(cells);
+            r.partition.mass.resize(cells);
+        }
+        const std::uint32_t none = 0;
+        const sbr_status st = sbr_sessions_beam_search(h_, slots.data(), (std::uint64_t)n, &ba, a.excl_ptr.empty() ? nullptr : a.excl_ptr.data(),
+                                                       a.excl_ptr.empty() ? nullptr : (a.excl_items.empty() ? &none : a.excl_items.data()),
+                                                       filtered ? any.data() : nullptr, filtered ? none_of.data() : nullptr, r.items.data(),
+                                                       r.scores.data(), r.step_lp.data(), r.cum.data(), r.lengths.data(), r.beams.data(),
+                                                       a.partitions ? r.partition.shift.data() : nullptr, a.partitions ? r.partition.mass.data() : nullptr,
+                                                       a.partitions ? &r.partition.frac_bits : nullptr);
+        if (st == SBR_ERR_INVALID_PREDICTION) return R::Err(PredictionError::InvalidPredictionValue);
+        check(st, "sbr_sessions_beam_search");
         return R::Ok(std::move(r));
     }
     /// `recommend_diverse` under a tag filter: the pool holds eligible items only (sbr_sessions_recommend_diverse_filtered).
@@ -2669,6 +2739,33 @@ class ImplicitSequenceModel : public OnlineRankingModel<ImplicitUser> {
         r.scores.resize(n);
         r.masked.resize(n);
         return R::Ok(std::move(r));
+    }
+
+    /// Sessions::beam_search from histories, DEFINED as rollout's form is: a temporary store of one slot per user, `append` of each
+    /// history's last max_sequence_length items, and the store's beam_search of all slots — with exclude_history each history's items
+    /// as its exclusion list, replacing a.excl_ptr / a.excl_items.
+    Result<Beams, PredictionError> beam_search(const data::CompressedInteractions& histories, BeamArgs a, bool exclude_history = true) const {
+        const std::vector<std::uint64_t>& up = histories.user_pointers();
+        const std::vector<std::uint32_t>& ids = histories.item_ids();
+        const std::size_t n = histories.num_users(), T = (std::size_t)replicas_->hparams().max_sequence_length;
+        if (n == 0) throw EngineError(SBR_ERR_INVALID_ARGUMENT, "beam_search: at least one history");
+        std::vector<std::uint32_t> slots(n), tail;
+        std::vector<std::uint64_t> tail_ptr(n + 1, 0);
+        for (std::size_t u = 0; u < n; ++u) {
+            slots[u] = (std::uint32_t)u;
+            const std::uint64_t keep = std::min<std::uint64_t>(up[u + 1] - up[u], T);
+            tail.insert(tail.end(), ids.begin() + (std::ptrdiff_t)(up[u + 1] - keep), ids.begin() + (std::ptrdiff_t)up[u + 1]);
+            tail_ptr[u + 1] = tail.size();
+        }
+        Sessions store = sessions(n);
+        store.append(slots, tail_ptr, tail);
+        a.include_seen = false;
+        if (exclude_history) {
+            a.excl_ptr.assign(up.begin(), up.end());
+            for (std::uint64_t& p : a.excl_ptr) p -= up.front();
+            a.excl_items.assign(ids.begin() + (std::ptrdiff_t)up.front(), ids.begin() + (std::ptrdiff_t)up.back());
+        }
+        return store.beam_search(slots, a);
     }
 
     /// Sessions::rollout from histories, DEFINED as this sequence of calls: a temporary store of one slot per user, `append` of each

@@ -853,7 +853,7 @@ sbr_status sbr_sessions_log_partition(sbr_sessions* st, const uint32_t* slots, u
  * SBR_ERR_INVALID_ARGUMENT, with nothing launched: args NULL, steps out of range, unknown flags, a temperature sbr_sample_args
  * refuses (checked in both modes), SBR_ROLLOUT_INCLUDE_SEEN on a store without memory, masks on a model without tags, a stale store,
  * an open fit plan, a slot out of range or named twice.  SBR_ERR_INVALID_PREDICTION: a non-finite score at any step fails the whole
- * call, as in sbr_recommend: what the outputs then hold is unspecified, and no binding returns it.  Not built: k > 1 per step (beam search), item sets, a rollout that commits, caps or
+ * call, as in sbr_recommend: what the outputs then hold is unspecified, and no binding returns it.  Not built: k > 1 per step (see BEAM SEARCH below), item sets, a rollout that commits, caps or
  * thresholds inside a rollout, a per-step temperature, rollouts from *_reps rows. */
 #define SBR_ROLLOUT_MAX_STEPS 1024u
 #define SBR_ROLLOUT_SAMPLE 1u
@@ -868,6 +868,53 @@ sbr_status sbr_sessions_rollout(sbr_sessions* st, const uint32_t* slots, uint64_
                                 const uint64_t* excl_ptr, const uint32_t* excl_items, const uint32_t* any_of, const uint32_t* none_of,
                                 uint32_t* out_items, float* out_scores, float* out_keys, uint32_t* out_lengths, float* out_shift,
                                 uint64_t* out_mass, uint32_t* out_frac_bits, float* out_h, float* out_c);
+
+/* BEAM SEARCH — the `width` most likely next-`steps` continuations of each session, searched on the device: "up next" rails,
+ * playlist continuation, next-basket candidates (no counterpart in the reference crate: a host loop of temporary slots, set_state,
+ * append, recommend(k = W) and log_partition per step).  Greedy and deterministic; HYPOTHETICAL like ROLLOUT: it writes nothing of
+ * the store.  For row i (slot slots[i]), W = width (1 .. SBR_BEAM_MAX_WIDTH) and steps (1 .. SBR_ROLLOUT_MAX_STEPS):
+ *   ELIGIBILITY  X_0 is ROLLOUT's (excl_ptr / excl_items, the seen-item memory unless SBR_ROLLOUT_INCLUDE_SEEN, the masks any_of /
+ *                none_of).  A beam whose path so far is p_0 .. p_{j-1} may choose from X_j = X_0 without them, or X_0 under
+ *                SBR_ROLLOUT_ALLOW_REPEATS.
+ *   STATE        a beam's state is what sbr_sessions_append(slot, path) would make: the whole recurrence, no window.  Step 0 of an
+ *                empty slot reads the empty-history row.
+ *   STEP LOG-PROBABILITY  an f32 quantity of correctly rounded operations only, (shift, mass) = sbr_sessions_log_partition's for the
+ *                beam's state over X_j at `temperature`, F its frac_bits:
+ *                  inv_t = fl(1 / T); t = fl(score * inv_t); d = fl(t - shift)                        (d <= 0)
+ *                  s = max(0, bit_length(mass) - 24); x = f32(mass >> s) 2^(s - F)                    (exact; x >= 1)
+ *                  L = sbr_log32(x) (one per beam and step); lp = fl(d - L); cum_j = fl(cum_{j-1} + lp_j), cum_{-1} = 0
+ *                lp is finite wherever the scores are and approximates log(w / mass) to about 1e-7 relative where w is not tiny.
+ *                It is NOT Partition.log_prob, which is -inf where w == 0: for the exact f64 value ask for out_shift / out_mass
+ *                and use sbr_softmax_weights on the host.
+ *   SELECTION    at step j every live beam offers its first W items of X_j in every call's order (score descending, ties to the
+ *                lower id, -0.0 == +0.0); the row keeps the W best of all offers by (cum descending, the parent's beam rank
+ *                ascending, the offer's position in its parent's row ascending).  Step 0 has one parent, the slot.  A k = W scan per
+ *                beam is exact: lp does not increase along a beam's score order, so every offer above a kept offer of the same
+ *                parent is kept too.
+ *   END          without repeats |X_j| = |X_0| - j for every beam of a row, so a row's beams end together: out_lengths[i] (optional)
+ *                = the real steps (steps for a row that never ends); out_beams[i] (optional) = the live beams, fewer than W while the
+ *                distinct paths are fewer.
+ * Outputs, beams in selection order at the row's last real step: out_items u32 / out_scores f32 (optional; sbr_predict's bits of
+ * each pick against its beam's state at that step) / out_step_lp f32 (optional) [n][W][steps], out_cum f32 [n][W] (optional);
+ * out_shift f32 / out_mass u64 [n][W][steps] and out_frac_bits (optional, all three or none): the step's partition of the beam.
+ * Padding (0xFFFFFFFF, -inf), -inf in out_step_lp / out_cum / out_shift, 0 in out_mass.  With W = 1 the items and scores are greedy
+ * sbr_sessions_rollout's.  The same arguments return the same bits whatever the batch, the host's chunks or the scan's item ranges.
+ * All steps of a chunk are queued without a host synchronisation.
+ * SBR_ERR_INVALID_ARGUMENT, with nothing launched: args NULL, width or steps out of range, unknown flags (SBR_ROLLOUT_SAMPLE among
+ * them), a temperature sbr_sample_args refuses, SBR_ROLLOUT_INCLUDE_SEEN on a store without memory, masks on a model without tags, a
+ * stale store, an open fit plan, a slot out of range or named twice.  SBR_ERR_INVALID_PREDICTION: a non-finite score at any step
+ * fails the whole call.  Not built: stochastic beam search, item sets, caps, beams that commit to the store. */
+#define SBR_BEAM_MAX_WIDTH 32u
+typedef struct sbr_beam_args {
+    uint32_t steps;
+    uint32_t width;
+    uint32_t flags; /* SBR_ROLLOUT_ALLOW_REPEATS | SBR_ROLLOUT_INCLUDE_SEEN */
+    float temperature;
+} sbr_beam_args;
+sbr_status sbr_sessions_beam_search(sbr_sessions* st, const uint32_t* slots, uint64_t n, const struct sbr_beam_args* args,
+                                    const uint64_t* excl_ptr, const uint32_t* excl_items, const uint32_t* any_of, const uint32_t* none_of,
+                                    uint32_t* out_items, float* out_scores, float* out_step_lp, float* out_cum, uint32_t* out_lengths,
+                                    uint32_t* out_beams, float* out_shift, uint64_t* out_mass, uint32_t* out_frac_bits);
 
 /* AUDIENCE— the reverse question, "which rows for this item": for each of num_queries query items q = items[j] (any order, repeats
  * allowed, each < num_items) the k candidate rows that score it highest, score(q, s) = b[q] + chain_dot(h_s, E[q]) with the bits of

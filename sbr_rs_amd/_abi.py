@@ -117,6 +117,21 @@ class SbrRolloutArgs(C.Structure):
     ]
 
 
+# BEAM SEARCH — sbr_sessions_beam_search (include/sbr_hip.h): the `width` most likely next-`steps` continuations of each session,
+# searched on the device; the store is read only.  flags: ROLLOUT_ALLOW_REPEATS, ROLLOUT_INCLUDE_SEEN (ROLLOUT_SAMPLE is refused).
+BEAM_MAX_WIDTH = 32
+
+
+class SbrBeamArgs(C.Structure):
+    """struct sbr_beam_args of sbr_sessions_beam_search"""
+    _fields_ = [
+        ("steps", C.c_uint32),
+        ("width", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("temperature", C.c_float),
+    ]
+
+
 class SbrCapArgs(C.Structure):
     """struct sbr_cap_args of the *_capped calls"""
     _fields_ = [

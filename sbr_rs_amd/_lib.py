@@ -195,6 +195,7 @@ def load():
         "sbr_recommend_capped_reps": [vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp],
         "sbr_sessions_recommend_capped": [vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint32, vp, vp, vp, vp, vp, vp],
         "sbr_sessions_rollout": [vp, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+        "sbr_sessions_beam_search": [vp, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
         "sbr_sequence_ranks": [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp],
         "sbr_sequence_partition": [vp, vp, vp, C.c_uint64, C.c_float, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp],
         # item sets: (set, const sbr_scan_rows*, num_rows, ...) and the tail of the *_reps sibling without lists and masks
@@ -280,7 +281,7 @@ DECLARED_SYMBOLS = [
     "sbr_model_set_item_groups", "sbr_model_get_item_groups",
     "sbr_recommend_capped", "sbr_recommend_capped_reps", "sbr_sessions_recommend_capped",
     "sbr_sequence_ranks", "sbr_sequence_partition",
-    "sbr_sessions_rollout",
+    "sbr_sessions_rollout", "sbr_sessions_beam_search",
     "sbr_item_set_create", "sbr_item_set_destroy", "sbr_item_set_size", "sbr_item_set_items", "sbr_item_set_refresh",
     "sbr_item_set_recommend", "sbr_item_set_recommend_diverse", "sbr_item_set_recommend_sampled", "sbr_item_set_log_partition",
     "sbr_item_set_recommend_above", "sbr_item_set_recommend_top", "sbr_item_set_recommend_capped",

@@ -252,6 +252,15 @@ def build_rollout_tests(force: bool = False, verbose: bool = True) -> str:
     return _build_cpp_program(ROLLOUT_SRC, ROLLOUT_BIN, force, verbose)
 
 
+BEAM_SRC = os.path.join(REPO, "tests", "cpp", "beam_tests.cpp")
+BEAM_BIN = os.path.join(REPO, "tests", "cpp", "_build", "beam_tests")
+
+
+def build_beam_tests(force: bool = False, verbose: bool = True) -> str:
+    """g++ build of the C++ host layer's beam-search test program."""
+    return _build_cpp_program(BEAM_SRC, BEAM_BIN, force, verbose)
+
+
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv))
     print(build_facade_tests(force="--force" in sys.argv))
@@ -274,3 +283,4 @@ if __name__ == "__main__":
     print(build_sequence_partition_tests(force="--force" in sys.argv))
     print(build_item_set_tests(force="--force" in sys.argv))
     print(build_rollout_tests(force="--force" in sys.argv))
+    print(build_beam_tests(force="--force" in sys.argv))

@@ -1475,6 +1475,16 @@ __global__ __launch_bounds__(256) void partition_shift_kernel(const uint32_t* be
     mass[u] = 0ull;
 }
 
+/* partition_shift_kernel's statement on column 0 of a k-row scan's output [n][k] (launch_topk_partition) */
+__global__ __launch_bounds__(256) void partition_shift_strided_kernel(const uint32_t* items, const float* scores, uint32_t n, uint32_t k,
+                                                                      float inv_t, float* shift, unsigned long long* mass) {
+    const uint32_t u = blockIdx.x * 256 + threadIdx.x;
+    if (u >= n) return;
+    const size_t e = (size_t)u * k;
+    shift[u] = items[e] == TK_NONE ? -INFINITY : __fadd_rn(__fmul_rn(scores[e], inv_t), 0.0f);
+    mass[u] = 0ull;
+}
+
 /* The sum scan, rank_gemm_kernel's shape: every score of the workgroup's 128 users x its item range becomes t = fl(s * inv_t),
  * d = fl(t - shift[u]) and the integer weight w (sbr_softmax_weight), added into 16 64-bit per-lane accumulators; at the end of the
  * range the 32 item lanes of a half-wave are summed and one 64-bit atomic per user joins the other ranges'.  Integer addition is
@@ -2491,6 +2501,14 @@ int launch_log_partition(const ModelView& m, const float* reps, const TopkScan& 
     int n = topk_scan<BiasAdd>(m, reps, sc, BiasAdd::Args{}, s); /* sc.k == 1: the rows' best allowed items and their scores */
     hipLaunchKernelGGL(partition_shift_kernel, dim3((sc.n + 255) / 256), dim3(256), 0, s, sc.out_items, sc.out_scores, sc.n, pt.inv_t, pt.shift,
                        pt.mass);
+    return n + 1 + partition_sum(m, reps, sc, pt, s);
+}
+
+int launch_topk_partition(const ModelView& m, const float* reps, const TopkScan& sc, const PartitionScan& pt, hipStream_t s) {
+    if (sc.n == 0) return 0;
+    int n = topk_scan<BiasAdd>(m, reps, sc, BiasAdd::Args{}, s); /* column 0: the rows' best allowed items, launch_log_partition's pre-scan */
+    hipLaunchKernelGGL(partition_shift_strided_kernel, dim3((sc.n + 255) / 256), dim3(256), 0, s, sc.out_items, sc.out_scores, sc.n, sc.k, pt.inv_t,
+                       pt.shift, pt.mass);
     return n + 1 + partition_sum(m, reps, sc, pt, s);
 }
 

@@ -6286,6 +6286,269 @@ sbr_status sbr_sessions_rollout(sbr_sessions* st, const uint32_t* slots, uint64_
 }
 
 /* ---------------------------------------------------------------------------------------------
+ * beam search: the W most likely next-n continuations of a session, on the device (BEAM SEARCH in include/sbr_hip.h)
+ * ------------------------------------------------------------------------------------------- */
+namespace {
+
+/* what a beam-search call asks for beside its slots and lists; the outputs are host arrays over the call's rows, null: not wanted */
+struct BeamCall {
+    uint32_t steps, w;
+    bool allow_repeats, seen;
+    const TagFilterArg* flt; /* null: no filter */
+    float inv_t;
+    uint32_t* out_items;
+    float *out_scores, *out_lp, *out_cum;
+    uint32_t *out_lengths, *out_beams;
+    float* out_shift; /* non-null: the partition per (beam, step), with out_mass */
+    uint64_t* out_mass;
+};
+
+/* Sessions per beam chunk: the scan's bound on its rows (recommend_users_cap at k = W) over the chunk's n W beam rows, and few enough
+ * that a row's share of the arena — per beam two state parities (h and c), two exclusion segments with one entry of slack per step,
+ * the per-step record (32 B) and the outputs (24 B) per step, the scan's bookkeeping; and the row's tight list — keeps the chunk within
+ * 256 MB.  SBR_BEAM_CHUNK=n (n >= 1) is a TEST HOOK read per call that replaces both. */
+size_t sessions_beam_chunk(const sbr_model* m, uint32_t seen_w, uint32_t w, uint32_t steps) {
+    constexpr size_t budget = (size_t)256 << 20;
+    const size_t per = (size_t)w * (((size_t)seen_w + steps) * 8 + (size_t)steps * 56 + (size_t)m->d * 16 + 128) + (size_t)seen_w * 8 + 64;
+    size_t cap = std::max<size_t>(std::min(recommend_users_cap((uint32_t)m->hp.num_items, w) / w, budget / per), 1);
+    if (const char* e = std::getenv("SBR_BEAM_CHUNK")) {
+        const long long v = std::atoll(e);
+        if (v >= 1) cap = (size_t)v;
+    }
+    return cap;
+}
+
+/* One chunk, rows [c0, c0 + nu) of the call, nb = nu W beam rows: the tight exclusion lists and the segment CSR, then per step the
+ * unchanged top-k scan at k = W with its partition (launch_topk_partition: n rows at step 0, nb after), beam_select_kernel, the
+ * children's segments and one cell step — all queued without a synchronisation — and at the end the backtrack, one flag check and
+ * the copies out. */
+sbr_status sessions_beam_chunk_run(sbr_sessions* st, const uint32_t* slots, const std::vector<int>& rep0, const uint64_t* excl_ptr,
+                                   const uint32_t* excl_items, const BeamCall& bc, size_t c0, size_t nu) {
+    sbr_model* m = st->m;
+    const size_t d = (size_t)m->d, S = bc.steps, W = bc.w, nb = nu * W;
+    const uint32_t num_items = (uint32_t)m->hp.num_items;
+    const bool lstm = m->ng != 0, part_out = bc.out_shift != nullptr;
+    const size_t seen_w = bc.seen ? st->seen.w : 0;
+    const uint32_t slack = bc.allow_repeats ? 0u : bc.steps;
+    UserBatch ub; /* the caller's lists of the chunk's rows, sorted and de-duplicated */
+    if (excl_ptr) {
+        std::vector<const uint32_t*> list(nu);
+        std::vector<uint64_t> n(nu);
+        for (size_t i = 0; i < nu; ++i) {
+            list[i] = excl_items ? excl_items + excl_ptr[c0 + i] : nullptr;
+            n[i] = excl_ptr[c0 + i + 1] - excl_ptr[c0 + i];
+        }
+        prepare_users(list, n, m->hp.max_sequence_length, true, &ub);
+    }
+    const size_t ncaller = ub.list_items.size();
+    const size_t nsrc = nu * seen_w + ncaller, nseg = W * nsrc + nb * slack;
+    const bool excl = excl_ptr || seen_w || slack; /* without any of them nothing is ever excluded */
+    uint32_t per = 0;
+    const size_t nlist = std::max(nu * sbr::recommend_groups((uint32_t)nu, num_items, bc.w, &per),
+                                  nb * sbr::recommend_groups((uint32_t)nb, num_items, bc.w, &per));
+    int* d_rep = nullptr;
+    uint2* lists = nullptr;
+    uint32_t *lens = nullptr, *scan_items = nullptr, *flag = nullptr, *d_slot = nullptr, *d_ident = nullptr;
+    uint32_t *any0 = nullptr, *none0 = nullptr, *anyb = nullptr, *noneb = nullptr;
+    uint32_t *src = nullptr, *seen_caller = nullptr, *seg[2] = {nullptr, nullptr};
+    uint64_t *src_ptr = nullptr, *seg_ptr = nullptr;
+    unsigned long long *d_start = nullptr, *mass = nullptr;
+    float *scan_scores = nullptr, *shift = nullptr;
+    sbr::BeamRows br{};
+    sbr::BeamRecord rec{};
+    sbr::BeamOut bo{};
+    SBRCHK(carve_arena(m, [&](DeviceArena& ar) {
+        d_rep = ar.take<int>(nu);
+        d_slot = ar.take<uint32_t>(nu);
+        d_ident = ar.take<uint32_t>(nb);
+        d_start = ar.take<unsigned long long>(nb);
+        lists = ar.take<uint2>(nlist * W);
+        lens = ar.take<uint32_t>(nlist);
+        scan_items = ar.take<uint32_t>(nb * W);
+        scan_scores = ar.take<float>(nb * W);
+        flag = ar.take<uint32_t>(1);
+        if (bc.flt) {
+            any0 = ar.take<uint32_t>(nu);
+            none0 = ar.take<uint32_t>(nu);
+            anyb = ar.take<uint32_t>(nb);
+            noneb = ar.take<uint32_t>(nb);
+        }
+        src_ptr = ar.take<uint64_t>(nu + 1);
+        src = ar.take<uint32_t>(nsrc + 1);
+        if (seen_w) seen_caller = ar.take<uint32_t>(ncaller + 1);
+        seg_ptr = ar.take<uint64_t>(nb + 1);
+        seg[0] = ar.take<uint32_t>(nseg + 1);
+        if (slack) seg[1] = ar.take<uint32_t>(nseg + 1);
+        shift = ar.take<float>(nb);
+        mass = ar.take<unsigned long long>(nb);
+        br.row_ended = ar.take<uint32_t>(nu);
+        br.lengths = ar.take<uint32_t>(nu);
+        br.beams = ar.take<uint32_t>(nu);
+        br.alive = ar.take<uint32_t>(nb);
+        br.ended = ar.take<uint32_t>(nb);
+        br.in_row = ar.take<uint32_t>(nb);
+        br.src_row = ar.take<uint32_t>(nb);
+        br.feed = ar.take<uint32_t>(nb);
+        br.count = ar.take<uint32_t>(nb);
+        br.pick = ar.take<uint32_t>(nb);
+        br.cum = ar.take<float>(nb);
+        br.Hs = ar.take<float>(2 * nb * d);
+        if (lstm) br.Cs = ar.take<float>(2 * nb * d);
+        else br.len = ar.take<unsigned long long>(2 * nb);
+        rec.parent = ar.take<uint32_t>(S * nb);
+        rec.item = ar.take<uint32_t>(S * nb);
+        rec.score = ar.take<float>(S * nb);
+        rec.lp = ar.take<float>(S * nb);
+        rec.cum = ar.take<float>(S * nb);
+        if (part_out) {
+            rec.shift = ar.take<float>(S * nb);
+            rec.mass = ar.take<unsigned long long>(S * nb);
+            bo.shift = ar.take<float>(nb * S);
+            bo.mass = ar.take<unsigned long long>(nb * S);
+        }
+        bo.items = ar.take<uint32_t>(nb * S);
+        bo.scores = ar.take<float>(nb * S);
+        bo.lp = ar.take<float>(nb * S);
+        bo.cum = ar.take<float>(nb);
+    }));
+    /* the host vectors below are read by asynchronous copies: they live until the stream is drained at the end */
+    std::vector<uint64_t> h_src_ptr(nu + 1), h_seg_ptr(nb + 1, 0);
+    std::vector<uint32_t> h_ident(nb);
+    std::vector<unsigned long long> h_start(nb);
+    for (size_t i = 0; i <= nu; ++i) h_src_ptr[i] = i * seen_w + (ub.list_ptr.empty() ? 0 : ub.list_ptr[i]);
+    for (size_t b = 0; b < nb; ++b) {
+        const size_t i = b / W;
+        h_seg_ptr[b + 1] = h_seg_ptr[b] + (h_src_ptr[i + 1] - h_src_ptr[i]) + slack;
+        h_ident[b] = (uint32_t)b;
+        h_start[b] = b;
+    }
+    HIPCHK(hipMemcpyAsync(d_rep, rep0.data() + c0, nu * 4, hipMemcpyHostToDevice, m->stream));
+    HIPCHK(hipMemcpyAsync(d_slot, slots + c0, nu * 4, hipMemcpyHostToDevice, m->stream));
+    HIPCHK(hipMemcpyAsync(d_ident, h_ident.data(), nb * 4, hipMemcpyHostToDevice, m->stream));
+    HIPCHK(hipMemcpyAsync(d_start, h_start.data(), nb * 8, hipMemcpyHostToDevice, m->stream));
+    if (excl) {
+        HIPCHK(hipMemcpyAsync(seg_ptr, h_seg_ptr.data(), (nb + 1) * 8, hipMemcpyHostToDevice, m->stream));
+        SBRCHK(upload_csr(m, src_ptr, h_src_ptr, seen_w ? seen_caller : src, ub.list_items));
+    }
+    std::vector<uint32_t> masks; /* the chunk's rows' any_of, then their none_of, then the same per beam row */
+    if (bc.flt) {
+        masks.assign(2 * nu + 2 * nb, 0u);
+        for (size_t i = 0; i < nu; ++i) {
+            const uint32_t a = bc.flt->any_of ? bc.flt->any_of[c0 + i] : 0u, z = bc.flt->none_of ? bc.flt->none_of[c0 + i] : 0u;
+            masks[i] = a;
+            masks[nu + i] = z;
+            for (size_t b = 0; b < W; ++b) {
+                masks[2 * nu + i * W + b] = a;
+                masks[2 * nu + nb + i * W + b] = z;
+            }
+        }
+        HIPCHK(hipMemcpyAsync(any0, masks.data(), nu * 4, hipMemcpyHostToDevice, m->stream));
+        HIPCHK(hipMemcpyAsync(none0, masks.data() + nu, nu * 4, hipMemcpyHostToDevice, m->stream));
+        HIPCHK(hipMemcpyAsync(anyb, masks.data() + 2 * nu, nb * 4, hipMemcpyHostToDevice, m->stream));
+        HIPCHK(hipMemcpyAsync(noneb, masks.data() + 2 * nu + nb, nb * 4, hipMemcpyHostToDevice, m->stream));
+    }
+    br.n = (int)nu; br.w = bc.w; br.steps = bc.steps;
+    br.slot = d_slot; br.ident = d_ident; br.start = d_start;
+    const uint32_t fb = sbr_softmax_fbits(num_items);
+    const sbr::BeamScan bs{scan_items, scan_scores, shift, mass, bc.inv_t, fb};
+    const size_t parity_stride = nb * d;
+    HIPCHK(hipMemsetAsync(flag, 0, 4, m->stream));
+    {
+        ScopedTimer t(m, SBR_K_RANK, 0);
+        int n = sbr::launch_beam_begin(br, m->stream);
+        if (seen_w) n += sbr::launch_session_seen_lists(st->seen, d_slot, (int)nu, src_ptr, seen_caller, src, m->stream);
+        if (excl && !slack) n += sbr::launch_beam_segments((int)nb, bc.w, src_ptr, src, nullptr, nullptr, seg_ptr, seg[0], m->stream);
+        t.tp.launches = (uint64_t)n;
+    }
+    for (uint32_t j = 0; j < bc.steps; ++j) {
+        /* step 0 scans the store's rows in place, one per row (an empty slot: the empty-history row); later steps the beam rows the
+         * step before wrote, with their own segments */
+        sbr::TopkScan sc{};
+        sc.rep_row = j == 0 ? d_rep : reinterpret_cast<const int*>(d_ident);
+        sc.n = (uint32_t)(j == 0 ? nu : nb);
+        sc.k = bc.w;
+        sc.excl_ptr = !excl ? nullptr : j == 0 ? src_ptr : seg_ptr;
+        sc.excl_items = j == 0 ? src : seg[slack ? (j - 1) & 1u : 0];
+        sc.lists = lists; sc.lens = lens; sc.out_items = scan_items; sc.out_scores = scan_scores;
+        sc.nonfinite_flag = flag;
+        sc.f = sbr::TagMasks{bc.flt ? m->item_tags : nullptr, j == 0 ? any0 : anyb, j == 0 ? none0 : noneb};
+        const float* reps = j == 0 ? st->v.H : br.Hs + (size_t)((j - 1) & 1u) * parity_stride;
+        {
+            ScopedTimer t(m, SBR_K_RANK, 0);
+            int n = sbr::launch_topk_partition(m->mv, reps, sc, sbr::PartitionScan{bc.inv_t, shift, mass, 0u}, m->stream);
+            n += sbr::launch_beam_select(br, j, bs, rec, m->stream); /* the kernel indexes the record by step */
+            if (j + 1 < bc.steps && slack)
+                n += sbr::launch_beam_segments((int)nb, bc.w, j == 0 ? src_ptr : seg_ptr, j == 0 ? src : seg[(j - 1) & 1u], br.src_row, br.pick,
+                                               seg_ptr, seg[j & 1u], m->stream);
+            t.tp.launches = (uint64_t)n;
+        }
+        if (j + 1 == bc.steps) break; /* nobody reads the state after the last selection */
+        ScopedTimer t(m, SBR_K_RECURRENT_FWD, lstm ? 2 : 1);
+        if (sbr::launch_beam_step(m->mv, st->v, br, j, m->stream) < 0) return SBR_ERR_UNSUPPORTED;
+    }
+    {
+        ScopedTimer t(m, SBR_K_RANK, 0);
+        t.tp.launches = (uint64_t)sbr::launch_beam_backtrack(br, rec, bo, m->stream);
+    }
+    HIPCHK(hipGetLastError());
+    uint32_t flag_h = 0;
+    HIPCHK(hipStreamSynchronize(m->stream));
+    HIPCHK(hipMemcpy(&flag_h, flag, 4, hipMemcpyDeviceToHost));
+    if (flag_h) return SBR_ERR_INVALID_PREDICTION; /* a non-finite score at any step fails the whole call */
+    const CopyOut outs[] = {{bc.out_items + c0 * W * S, bo.items, nb * S * 4},
+                            {bc.out_scores ? bc.out_scores + c0 * W * S : nullptr, bo.scores, nb * S * 4},
+                            {bc.out_lp ? bc.out_lp + c0 * W * S : nullptr, bo.lp, nb * S * 4},
+                            {bc.out_cum ? bc.out_cum + c0 * W : nullptr, bo.cum, nb * 4},
+                            {bc.out_lengths ? bc.out_lengths + c0 : nullptr, br.lengths, nu * 4},
+                            {bc.out_beams ? bc.out_beams + c0 : nullptr, br.beams, nu * 4},
+                            {part_out ? bc.out_shift + c0 * W * S : nullptr, bo.shift, nb * S * 4},
+                            {part_out ? bc.out_mass + c0 * W * S : nullptr, bo.mass, nb * S * 8}};
+    for (const CopyOut& o : outs)
+        if (o.host) HIPCHK(hipMemcpy(o.host, o.device, o.bytes, hipMemcpyDeviceToHost));
+    return SBR_OK;
+}
+
+}  // namespace
+
+sbr_status sbr_sessions_beam_search(sbr_sessions* st, const uint32_t* slots, uint64_t n, const struct sbr_beam_args* args,
+                                    const uint64_t* excl_ptr, const uint32_t* excl_items, const uint32_t* any_of, const uint32_t* none_of,
+                                    uint32_t* out_items, float* out_scores, float* out_step_lp, float* out_cum, uint32_t* out_lengths,
+                                    uint32_t* out_beams, float* out_shift, uint64_t* out_mass, uint32_t* out_frac_bits) {
+    constexpr uint32_t known = SBR_ROLLOUT_ALLOW_REPEATS | SBR_ROLLOUT_INCLUDE_SEEN;
+    if (!st || !args || (n && !out_items)) return SBR_ERR_INVALID_ARGUMENT;
+    if (args->steps < 1 || args->steps > SBR_ROLLOUT_MAX_STEPS || (args->flags & ~known)) return SBR_ERR_INVALID_ARGUMENT;
+    if (args->width < 1 || args->width > SBR_BEAM_MAX_WIDTH) return SBR_ERR_INVALID_ARGUMENT;
+    sbr_sample_args sa{};
+    sa.temperature = args->temperature;
+    Sample sm;
+    TagFilterArg hold;
+    if (!sample_args(&sa, nullptr, &sm)) return SBR_ERR_INVALID_ARGUMENT;
+    if ((out_shift != nullptr) != (out_mass != nullptr) || (out_shift != nullptr) != (out_frac_bits != nullptr)) return SBR_ERR_INVALID_ARGUMENT;
+    if ((args->flags & SBR_ROLLOUT_INCLUDE_SEEN) && !st->seen.w) return SBR_ERR_INVALID_ARGUMENT; /* nothing to include */
+    if (!excl_args_ok(excl_ptr, excl_items, n)) return SBR_ERR_INVALID_ARGUMENT;
+    sbr_model* m = st->m;
+    std::lock_guard<std::mutex> lock(m->mu);
+    SBRCHK(enter_sessions(st));
+    SBRCHK(check_slots(st, slots, n));
+    if (excl_ptr) SBRCHK(check_csr(m, excl_ptr, n, excl_items, false));
+    BeamCall bc{};
+    bc.steps = args->steps;
+    bc.w = args->width;
+    bc.allow_repeats = (args->flags & SBR_ROLLOUT_ALLOW_REPEATS) != 0;
+    bc.seen = st->seen.w && !(args->flags & SBR_ROLLOUT_INCLUDE_SEEN);
+    bc.flt = sample_filter(any_of, none_of, &hold);
+    if (bc.flt && !m->item_tags) return SBR_ERR_INVALID_ARGUMENT;
+    bc.inv_t = sm.inv_t;
+    bc.out_items = out_items; bc.out_scores = out_scores; bc.out_lp = out_step_lp; bc.out_cum = out_cum;
+    bc.out_lengths = out_lengths; bc.out_beams = out_beams; bc.out_shift = out_shift; bc.out_mass = out_mass;
+    const std::vector<int> rep0 = session_rep_rows(st, slots, n);
+    const size_t cap = sessions_beam_chunk(m, bc.seen ? st->seen.w : 0, bc.w, bc.steps);
+    for (size_t c0 = 0; c0 < n; c0 += cap) SBRCHK(sessions_beam_chunk_run(st, slots, rep0, excl_ptr, excl_items, bc, c0, std::min<size_t>(cap, n - c0)));
+    if (out_frac_bits) *out_frac_bits = sbr_softmax_fbits((uint32_t)m->hp.num_items);
+    return SBR_OK;
+}
+
+/* ---------------------------------------------------------------------------------------------
  * item sets: every catalogue call restricted to a resident sub-table (ITEM SETS in include/sbr_hip.h)
  * ------------------------------------------------------------------------------------------- */
 namespace {

@@ -351,6 +351,11 @@ struct PartitionScan {
                                call's integer; 0: the scanned catalogue's */
 };
 int launch_log_partition(const ModelView& m, const float* reps, const TopkScan& sc, const PartitionScan& pt, hipStream_t s);
+/* beam search's scan (the contract: BEAM SEARCH in include/sbr_hip.h): launch_recommend at any sc.k (sc.out_scores not NULL), then
+ * launch_log_partition's shift, sum scan and finish on the same descriptor — the shift taken from column 0 of the k-row scan, whose
+ * first entry IS launch_log_partition's k = 1 pre-scan, so that scan is not run again.  Four or five launches: scan, merge, shift,
+ * sum scan, finish. */
+int launch_topk_partition(const ModelView& m, const float* reps, const TopkScan& sc, const PartitionScan& pt, hipStream_t s);
 /* sequence_partition (sbr_catalogue.hip; the contract: SEQUENCE PARTITION in include/sbr_hip.h): launch_log_partition's shift and
  * mass for scan rows that are (sequence b, step t) = unit_bt[i] of the forward pass's packed layout, as launch_sequence_ranks'
  * (rep_row[i] = off[t] + b; the row's mask: the first occurrences, first_occ by packed row, among in_idx[off[j] + b], j <= t),
@@ -586,6 +591,57 @@ int launch_rollout_segments(const uint64_t* src_ptr, const uint32_t* src, int n,
 int launch_rollout_advance(const RolloutRows& r, uint32_t j, const RolloutPick& p, const uint64_t* ins_ptr, uint32_t* excl, const RolloutOut& o,
                            hipStream_t s);
 int launch_rollout_step(const ModelView& m, const SessionView& sv, const RolloutRows& r, uint32_t j, hipStream_t s);
+/* A beam-search chunk (sbr_sessions.hip; the contract: BEAM SEARCH in include/sbr_hip.h): n rows of w beams each, beam b of row i
+ * the scan row i w + b, advanced `steps` times on scratch memory, the store read only.  Device arrays: slot [n] the rows' store rows;
+ * row_ended / lengths / beams [n]; per beam row [n w]: alive, cum (the beam's path so far), ended (its row has ended: the LSTM
+ * carry), in_row (the state row its cell step reads: the store's through the slot at step 0, else the other parity's), src_row (the
+ * exclusion segment its own is copied from), feed / count / pick (its cell step's item, whether it takes it, the item merged into
+ * its segment); ident / start = 0 .. n w - 1 (the EWMA step's indices); Hs / Cs [2][n w][d] (Cs null: EWMA), len [2][n w] (EWMA).
+ * BeamScan: the step's k = w scan over its rows (n at step 0, n w after) — items / scores [rows][w] — and its partition shift / mass
+ * [rows] at inv_t with F = fbits.  BeamRecord [steps][n w]: parent, item, score, lp, cum, and (shift null: not wanted) shift, mass.
+ * BeamOut: items / scores / lp / shift / mass [n][w][steps], cum [n][w].
+ * launch_beam_begin: no row ended, lengths = steps, beams = 0.
+ * launch_beam_select: step j's selection (beam_select_kernel), one workgroup per row.
+ * launch_beam_segments: nc children's segments [dst_ptr[c], dst_ptr[c + 1]) of dst = segment src_row[c] (null: c / w) of the
+ *   src CSR with pick[c] merged in (null: none), padded with 0xFFFFFFFF.
+ * launch_beam_step: one cell step of every beam row into parity j & 1 (-1 where there is no kernel for m.d).
+ * launch_beam_backtrack: the record walked back into o.  Each returns the launches it queued. */
+struct BeamRows {
+    int n;
+    uint32_t w, steps;
+    const uint32_t* slot;
+    uint32_t *row_ended, *lengths, *beams;
+    uint32_t *alive, *ended, *in_row, *src_row, *feed, *count, *pick;
+    float* cum;
+    const uint32_t* ident;
+    const unsigned long long* start;
+    float *Hs, *Cs;
+    unsigned long long* len;
+};
+struct BeamScan {
+    const uint32_t* items;
+    const float* scores;
+    const float* shift;
+    const unsigned long long* mass;
+    float inv_t;
+    uint32_t fbits;
+};
+struct BeamRecord {
+    uint32_t *parent, *item;
+    float *score, *lp, *cum, *shift;
+    unsigned long long* mass;
+};
+struct BeamOut {
+    uint32_t* items;
+    float *scores, *lp, *cum, *shift;
+    unsigned long long* mass;
+};
+int launch_beam_begin(const BeamRows& r, hipStream_t s);
+int launch_beam_select(const BeamRows& r, uint32_t j, const BeamScan& sc, const BeamRecord& rec, hipStream_t s);
+int launch_beam_segments(int nc, uint32_t w, const uint64_t* src_ptr, const uint32_t* src, const uint32_t* src_row, const uint32_t* pick,
+                         const uint64_t* dst_ptr, uint32_t* dst, hipStream_t s);
+int launch_beam_step(const ModelView& m, const SessionView& sv, const BeamRows& r, uint32_t j, hipStream_t s);
+int launch_beam_backtrack(const BeamRows& r, const BeamRecord& rec, const BeamOut& o, hipStream_t s);
 /* The inverted seen lists of an audience scan (sbr_sessions.hip): which candidates' memories hold which query item.  The chunk's
  * queries come sorted by item: qs_item [nq] ascending (repeats kept), qs_idx [nq] the query each stands for; candidate position p
  * is slot cand_slot[p].  A key is (query << 32 | position), one per (query, position) whose slot's min(cnt, w) valid ring entries hold

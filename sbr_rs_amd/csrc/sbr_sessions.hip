@@ -29,6 +29,12 @@
 //   rollout_advance_kernel     : per step, the scan's pick into the outputs, the row's exclusion segment and the next step's feed
 //   rollout_carry_kernel       : an ended row's state kept across the LSTM step
 //
+// A beam search (sbr_sessions_beam_search) reads a store and writes scratch only; per step, behind the k = W scan and its partition:
+//   beam_select_kernel         : one workgroup per row: the W best of the live beams' offers, in the three-key order
+//   beam_segments_kernel       : each child beam's exclusion segment, its parent's with the pick merged in, into the other parity
+//   beam_gather_rows_kernel    : EWMA: the parents' rows copied into the other parity, ahead of the in-place cell step
+//   beam_backtrack_kernel      : at the chunk's end, the parent pointers walked back into the [n][W][steps] outputs
+//
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off (see sbr_rs_amd/build.py).
 
 #include "sbr_kernels.h"
@@ -713,6 +719,250 @@ __global__ __launch_bounds__(256) void rollout_carry_kernel(const uint32_t* __re
     st4(Cout + b * d + c4, zero ? z : ld4(Cin + r * d + c4));
 }
 
+// ------------------------------------------------------------------------------------------------
+// Beam search (sbr_sessions_beam_search; the contract: BEAM SEARCH in include/sbr_hip.h): W beams per row advanced step after step on
+// SCRATCH rows — beam b of row i is scan row i * W + b — the store read only.  Per step the unchanged top-k scan at k = W leaves
+// each parent's first W eligible items and the partition sum its (shift, mass); beam_select_kernel keeps the row's W best offers,
+// beam_segments_kernel and the cell step (or beam_gather_rows_kernel + the in-place EWMA step) make the children's exclusion
+// segments and states from their parents'.  Parities: the children of step j are written into parity j & 1; the scan of step j + 1
+// reads them.  The per-step record [steps][n W] holds what beam_backtrack_kernel needs to write the paths at the end.
+// ------------------------------------------------------------------------------------------------
+
+// The chunk's start: no row has ended, lengths = steps (a row that never ends keeps that), beams = 0.
+__global__ __launch_bounds__(256) void beam_begin_kernel(int n, uint32_t steps, uint32_t* __restrict__ row_ended, uint32_t* __restrict__ lengths,
+                                                         uint32_t* __restrict__ beams) {
+    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (i >= n) return;
+    row_ended[i] = 0u;
+    lengths[i] = steps;
+    beams[i] = 0u;
+}
+
+// One workgroup per row, step j.  Parents: the slot itself at j == 0 (scan row i), else beams p < W of the row (scan rows i W + p)
+// that are alive.  Parent p offers its scan row's entries q < nv[p] (the scan's non-padding prefix), each with
+//   t = fl(score * inv_t), d = fl(t - shift[p]), lp = fl(d - L[p]), cum = fl(cum[p] + lp)   (cum[p] = 0 at j == 0)
+// where L[p] = sbr_log32(x), x = f32(mass >> s) 2^(s - F) exactly, s = max(0, bit_length(mass) - 24): one log per parent.  The row
+// keeps the W best offers ordered by (cum descending, p ascending, q ascending).  lp never increases along q (fl is monotone and L[p]
+// is constant), so an offer's rank is q plus, for every other parent, the length of that parent's prefix of offers that beat it —
+// counted until it reaches W.  Ranks are distinct, so child c = the offer of rank c; no atomics, no dependence on dispatch order.
+// Children c >= K = min(W, offers) are DEAD: they mirror child 0 (its parent and its pick) so that their state and segment are
+// finite copies of a live beam's, and alive = 0.  No offer at all: the row ends at j (lengths = j; beams keep the last count), and
+// every beam row is carried: parent itself (the slot at j == 0), no pick, ended = 1.  Per child, into the step's record: parent,
+// item, plain score, lp, cum and the PARENT's shift and mass; and for the next kernels in_row (the state row the cell step reads:
+// slot[i] at j == 0, else i W + parent), src_row (the segment the child's is copied from: i at j == 0, else i W + parent), feed /
+// count (the cell step's item; count 0 on ended rows), pick (merged into the segment; 0xFFFFFFFF: nothing).  A row's parents are
+// read into LDS before any of its children is written, so alive / cum are updated in place.
+__global__ __launch_bounds__(256) void beam_select_kernel(int n, uint32_t w, uint32_t j, const uint32_t* __restrict__ slot,
+                                                          const uint32_t* __restrict__ scan_items, const float* __restrict__ scan_scores,
+                                                          const float* __restrict__ shift, const unsigned long long* __restrict__ mass,
+                                                          float inv_t, uint32_t fbits, uint32_t* row_ended, uint32_t* __restrict__ lengths,
+                                                          uint32_t* __restrict__ beams, uint32_t* alive, float* cum, uint32_t* __restrict__ ended,
+                                                          uint32_t* __restrict__ in_row, uint32_t* __restrict__ src_row,
+                                                          uint32_t* __restrict__ feed, uint32_t* __restrict__ count, uint32_t* __restrict__ pick,
+                                                          uint32_t* __restrict__ rec_parent, uint32_t* __restrict__ rec_item,
+                                                          float* __restrict__ rec_score, float* __restrict__ rec_lp, float* __restrict__ rec_cum,
+                                                          float* __restrict__ rec_shift, unsigned long long* __restrict__ rec_mass) {
+    constexpr uint32_t NONE = 0xFFFFFFFFu;
+    __shared__ uint32_t p_nv[32];
+    __shared__ float p_L[32], p_cum[32];
+    __shared__ float o_cum[32 * 32], o_lp[32 * 32];
+    __shared__ int ch[32];
+    __shared__ uint32_t total;
+    const int i = (int)blockIdx.x;
+    if (i >= n) return; /* the whole workgroup */
+    const uint32_t tid = threadIdx.x;
+    const uint32_t P = j == 0 ? 1u : w;
+    const bool was = row_ended[i] != 0u;
+    const size_t b0 = (size_t)i * w;
+    for (uint32_t p = tid; p < P; p += 256u) {
+        const size_t srow = j == 0 ? (size_t)i : b0 + p;
+        const bool live = !was && (j == 0 || alive[b0 + p] != 0u);
+        uint32_t nv = 0;
+        if (live)
+            while (nv < w && scan_items[srow * w + nv] != NONE) ++nv;
+        float L = 0.0f;
+        if (nv) { /* mass >= 2^F: the best offer's weight alone is 2^F */
+            const unsigned long long ms = mass[srow];
+            const int s = ms >> 24 ? 40 - __clzll((long long)ms) : 0; /* = max(0, bit_length(mass) - 24) */
+            L = sbr_log32(ldexpf((float)(ms >> s), s - (int)fbits));
+        }
+        p_nv[p] = nv;
+        p_L[p] = L;
+        p_cum[p] = j == 0 || !live ? 0.0f : cum[b0 + p];
+    }
+    if (tid < w) ch[tid] = -1;
+    __syncthreads();
+    if (tid == 0) {
+        uint32_t t = 0;
+        for (uint32_t p = 0; p < P; ++p) t += p_nv[p];
+        total = t;
+    }
+    for (uint32_t o = tid; o < P * w; o += 256u) {
+        const uint32_t p = o / w, q = o % w;
+        if (q >= p_nv[p]) continue;
+        const size_t srow = j == 0 ? (size_t)i : b0 + p;
+        const float t = __fmul_rn(scan_scores[srow * w + q], inv_t);
+        const float d = __fsub_rn(t, shift[srow]);
+        const float lp = __fsub_rn(d, p_L[p]);
+        o_lp[o] = lp;
+        o_cum[o] = __fadd_rn(p_cum[p], lp);
+    }
+    __syncthreads();
+    for (uint32_t o = tid; o < P * w; o += 256u) {
+        const uint32_t p = o / w, q = o % w;
+        if (q >= p_nv[p]) continue;
+        const float c = o_cum[o];
+        uint32_t rank = q;
+        for (uint32_t p2 = 0; p2 < P && rank < w; ++p2) {
+            if (p2 == p) continue;
+            for (uint32_t q2 = 0; q2 < p_nv[p2]; ++q2) {
+                const float c2 = o_cum[p2 * w + q2];
+                if (!(c2 > c || (c2 == c && p2 < p))) break;
+                if (++rank >= w) break;
+            }
+        }
+        if (rank < w) ch[rank] = (int)o;
+    }
+    __syncthreads();
+    if (tid >= w) return;
+    const uint32_t c = tid;
+    const size_t b = b0 + c;
+    if (was || total == 0u) { /* the row has ended (or ends now): every beam row carried, nothing recorded */
+        if (!was && c == 0) {
+            row_ended[i] = 1u;
+            lengths[i] = j;
+        }
+        in_row[b] = j == 0 ? slot[i] : (uint32_t)b;
+        src_row[b] = j == 0 ? (uint32_t)i : (uint32_t)b;
+        feed[b] = 0u;
+        count[b] = 0u;
+        pick[b] = NONE;
+        ended[b] = 1u;
+        alive[b] = 0u;
+        cum[b] = -INFINITY;
+        return;
+    }
+    const uint32_t K = total < w ? total : w;
+    const bool live = c < K;
+    int o = ch[live ? c : 0];
+    if (o < 0) o = ch[0] < 0 ? 0 : ch[0]; /* only where the scores are not numbers (the call fails): keep every index in range */
+    const uint32_t p = (uint32_t)o / w, q = (uint32_t)o % w;
+    const size_t srow = j == 0 ? (size_t)i : b0 + p;
+    const uint32_t item = scan_items[srow * w + q];
+    const uint32_t it = item == NONE ? 0u : item;
+    in_row[b] = j == 0 ? slot[i] : (uint32_t)(b0 + p);
+    src_row[b] = j == 0 ? (uint32_t)i : (uint32_t)(b0 + p);
+    feed[b] = it;
+    count[b] = 1u;
+    pick[b] = it;
+    ended[b] = 0u;
+    alive[b] = live ? 1u : 0u;
+    cum[b] = live ? o_cum[o] : -INFINITY;
+    const size_t r = (size_t)j * n * w + b;
+    rec_parent[r] = live ? p : 0u;
+    rec_item[r] = live ? item : NONE;
+    rec_score[r] = live ? scan_scores[srow * w + q] : -INFINITY;
+    rec_lp[r] = live ? o_lp[o] : -INFINITY;
+    rec_cum[r] = live ? o_cum[o] : -INFINITY;
+    if (rec_shift) {
+        rec_shift[r] = live ? shift[srow] : -INFINITY;
+        rec_mass[r] = live ? mass[srow] : 0ull;
+    }
+    if (c == 0) beams[i] = K;
+}
+
+// One wave per child beam c: its exclusion segment [dst_ptr[c], dst_ptr[c + 1]) of dst = the source segment s = src_row[c] of the
+// other CSR — src_row null: s = c / w, the row's tight list — with pick[c] merged in (pick null or 0xFFFFFFFF: a plain copy), then
+// 0xFFFFFFFF to the end.  The source is non-decreasing with a 0xFFFFFFFF tail allowed and does not hold the pick (the scan has just
+// offered it), so the pick's place is the number of entries below it, counted by the wave; the merged sequence is written in one
+// pass.  The destination has room: a child's segment has one entry of slack per step beyond its row's list.
+__global__ __launch_bounds__(256) void beam_segments_kernel(int nc, uint32_t w, const uint64_t* __restrict__ src_ptr, const uint32_t* __restrict__ src,
+                                                            const uint32_t* __restrict__ src_row, const uint32_t* __restrict__ pick,
+                                                            const uint64_t* __restrict__ dst_ptr, uint32_t* __restrict__ dst) {
+    constexpr uint32_t NONE = 0xFFFFFFFFu;
+    const int c = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
+    if (c >= nc) return;
+    const uint32_t lane = threadIdx.x & 63u;
+    const size_t s = src_row ? (size_t)src_row[c] : (size_t)c / w;
+    const uint64_t s0 = src_ptr[s], have = src_ptr[s + 1] - s0;
+    const uint64_t d0 = dst_ptr[c], room = dst_ptr[c + 1] - d0;
+    const uint32_t v = pick ? pick[c] : NONE;
+    uint64_t pos = have; /* the pick's place: past every entry when there is none to merge */
+    if (v != NONE) {
+        uint32_t below = 0;
+        for (uint64_t q = lane; q < have; q += 64u) below += src[s0 + q] < v ? 1u : 0u;
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) below += __shfl_xor(below, off, 64);
+        pos = below;
+    }
+    const uint64_t merged = have + (v != NONE ? 1u : 0u);
+    for (uint64_t q = lane; q < room; q += 64u) {
+        uint32_t x = NONE;
+        if (q < merged) x = q < pos ? src[s0 + q] : q == pos ? v : src[s0 + q - 1];
+        dst[d0 + q] = x;
+    }
+}
+
+// EWMA ahead of the in-place cell step: row b of Sout / lout = row in_row[b] of Sin / lin, 16 B per lane
+__global__ __launch_bounds__(256) void beam_gather_rows_kernel(const uint32_t* __restrict__ in_row, int n, int d, const float* __restrict__ Sin,
+                                                               const unsigned long long* __restrict__ lin, float* __restrict__ Sout,
+                                                               unsigned long long* __restrict__ lout) {
+    const int L = d / 4;
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t b = idx / L;
+    if (b >= (size_t)n) return;
+    const int c4 = (int)(idx % L) * 4;
+    const size_t r = in_row[b];
+    st4(Sout + b * d + c4, ld4(Sin + r * d + c4));
+    if (c4 == 0) lout[b] = lin[r];
+}
+
+// One wave per (row i, beam b) at the chunk's end: beam b < beams[i] of the row's last real step lengths[i] - 1 is walked back by
+// the record's parent pointers, lane 0 writing entry j of out [n][w][steps] for j = lengths[i] - 1 .. 0; the other lanes write the
+// padding (0xFFFFFFFF, -inf, -inf, -inf, 0) — every entry of a beam b >= beams[i] and every j >= lengths[i].  out_cum [n][w]: the
+// beam's cum at the last real step, -inf for a missing beam.
+__global__ __launch_bounds__(256) void beam_backtrack_kernel(int n, uint32_t w, uint32_t steps, const uint32_t* __restrict__ lengths,
+                                                             const uint32_t* __restrict__ beams, const uint32_t* __restrict__ rec_parent,
+                                                             const uint32_t* __restrict__ rec_item, const float* __restrict__ rec_score,
+                                                             const float* __restrict__ rec_lp, const float* __restrict__ rec_cum,
+                                                             const float* __restrict__ rec_shift, const unsigned long long* __restrict__ rec_mass,
+                                                             uint32_t* __restrict__ out_items, float* __restrict__ out_scores,
+                                                             float* __restrict__ out_lp, float* __restrict__ out_cum, float* __restrict__ out_shift,
+                                                             unsigned long long* __restrict__ out_mass) {
+    const size_t g = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (g >= (size_t)n * w) return;
+    const uint32_t lane = threadIdx.x & 63u;
+    const size_t i = g / w;
+    const uint32_t b = (uint32_t)(g % w);
+    const uint32_t len = b < beams[i] ? lengths[i] : 0u;
+    const size_t o = g * steps;
+    for (uint32_t j = len + lane; j < steps; j += 64u) {
+        out_items[o + j] = 0xFFFFFFFFu;
+        out_scores[o + j] = -INFINITY;
+        out_lp[o + j] = -INFINITY;
+        if (out_shift) {
+            out_shift[o + j] = -INFINITY;
+            out_mass[o + j] = 0ull;
+        }
+    }
+    if (lane != 0) return;
+    const size_t nw = (size_t)n * w;
+    out_cum[g] = len ? rec_cum[(size_t)(len - 1) * nw + g] : -INFINITY;
+    uint32_t c = b;
+    for (uint32_t j = len; j-- > 0;) {
+        const size_t r = (size_t)j * nw + i * w + c;
+        out_items[o + j] = rec_item[r];
+        out_scores[o + j] = rec_score[r];
+        out_lp[o + j] = rec_lp[r];
+        if (out_shift) {
+            out_shift[o + j] = rec_shift[r];
+            out_mass[o + j] = rec_mass[r];
+        }
+        c = rec_parent[r];
+        if (c >= w) c = 0; /* never, from beam_select_kernel: an index stays in range */
+    }
+}
+
 namespace {
 
 inline unsigned blocks_for(size_t threads) { return (unsigned)((threads + 255) / 256); }
@@ -836,6 +1086,86 @@ int launch_rollout_step(const ModelView& m, const SessionView& sv, const Rollout
     }
 #undef SBR_ROLLOUT_D
     return m.ng ? 2 : 1;
+}
+
+namespace {
+
+/* step j of a beam chunk: every beam row one cell step by its feed item into parity j & 1 from its parent's row in_row — the store's
+ * rows through the slot at j == 0 — LSTM by the unchanged step kernel and the ended rows' carry, EWMA by the gather and the unchanged
+ * in-place step */
+template <int D>
+void beam_step_d(const ModelView& m, const SessionView& sv, const BeamRows& r, uint32_t j, hipStream_t s) {
+    const int nb = r.n * (int)r.w;
+    const size_t parity_stride = (size_t)nb * D;
+    const float* Hin = j == 0 ? sv.H : r.Hs + (size_t)((j - 1) & 1u) * parity_stride;
+    float* Hout = r.Hs + (size_t)(j & 1u) * parity_stride;
+    const unsigned long long* len = j == 0 ? sv.len : nullptr;
+    if (m.ng) {
+        const float* Cin = j == 0 ? sv.C : r.Cs + (size_t)((j - 1) & 1u) * parity_stride;
+        float* Cout = r.Cs + (size_t)(j & 1u) * parity_stride;
+        const dim3 grid((unsigned)((nb + 31) / 32), D / 16);
+        if (m.ng == 4)
+            hipLaunchKernelGGL((session_lstm_step_kernel<D, 4>), grid, dim3(256), 0, s, m, r.feed, nb, r.in_row, len, Hin, Cin, Hout, Cout);
+        else
+            hipLaunchKernelGGL((session_lstm_step_kernel<D, 3>), grid, dim3(192), 0, s, m, r.feed, nb, r.in_row, len, Hin, Cin, Hout, Cout);
+        hipLaunchKernelGGL(rollout_carry_kernel, dim3(blocks_for((size_t)nb * (D / 4))), dim3(256), 0, s, r.ended, nb, D, r.in_row, len, Hin, Cin,
+                           Hout, Cout);
+        return;
+    }
+    const unsigned long long* lin = j == 0 ? sv.len : r.len + (size_t)((j - 1) & 1u) * nb;
+    unsigned long long* lout = r.len + (size_t)(j & 1u) * nb;
+    hipLaunchKernelGGL(beam_gather_rows_kernel, dim3(blocks_for((size_t)nb * (D / 4))), dim3(256), 0, s, r.in_row, nb, D, Hin, lin, Hout, lout);
+    hipLaunchKernelGGL((session_ewma_step_kernel<D>), dim3(blocks_for((size_t)nb * (D / 4))), dim3(256), 0, s, m, r.ident, r.start, r.count, nb,
+                       r.feed, Hout, lout, 1);
+}
+
+}  // namespace
+
+int launch_beam_begin(const BeamRows& r, hipStream_t s) {
+    if (r.n <= 0) return 0;
+    hipLaunchKernelGGL(beam_begin_kernel, dim3(blocks_for((size_t)r.n)), dim3(256), 0, s, r.n, r.steps, r.row_ended, r.lengths, r.beams);
+    return 1;
+}
+
+int launch_beam_select(const BeamRows& r, uint32_t j, const BeamScan& sc, const BeamRecord& rec, hipStream_t s) {
+    if (r.n <= 0) return 0;
+    hipLaunchKernelGGL(beam_select_kernel, dim3((unsigned)r.n), dim3(256), 0, s, r.n, r.w, j, r.slot, sc.items, sc.scores, sc.shift, sc.mass, sc.inv_t,
+                       sc.fbits, r.row_ended, r.lengths, r.beams, r.alive, r.cum, r.ended, r.in_row, r.src_row, r.feed, r.count, r.pick,
+                       rec.parent, rec.item, rec.score, rec.lp, rec.cum, rec.shift, rec.mass);
+    return 1;
+}
+
+int launch_beam_segments(int nc, uint32_t w, const uint64_t* src_ptr, const uint32_t* src, const uint32_t* src_row, const uint32_t* pick,
+                         const uint64_t* dst_ptr, uint32_t* dst, hipStream_t s) {
+    if (nc <= 0) return 0;
+    hipLaunchKernelGGL(beam_segments_kernel, dim3((unsigned)((nc + 3) / 4)), dim3(256), 0, s, nc, w, src_ptr, src, src_row, pick, dst_ptr, dst);
+    return 1;
+}
+
+int launch_beam_step(const ModelView& m, const SessionView& sv, const BeamRows& r, uint32_t j, hipStream_t s) {
+    if (r.n <= 0) return 0;
+#define SBR_BEAM_D(DD)                         \
+    case DD:                                   \
+        beam_step_d<DD>(m, sv, r, j, s);       \
+        break;
+    switch (m.d) {
+        SBR_BEAM_D(16)
+        SBR_BEAM_D(32)
+        SBR_BEAM_D(64)
+        SBR_BEAM_D(128)
+        SBR_BEAM_D(256)
+        default: return -1; /* no such storage width: the caller fails the call */
+    }
+#undef SBR_BEAM_D
+    return 2;
+}
+
+int launch_beam_backtrack(const BeamRows& r, const BeamRecord& rec, const BeamOut& o, hipStream_t s) {
+    if (r.n <= 0) return 0;
+    const size_t nb = (size_t)r.n * r.w;
+    hipLaunchKernelGGL(beam_backtrack_kernel, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, s, r.n, r.w, r.steps, r.lengths, r.beams, rec.parent,
+                       rec.item, rec.score, rec.lp, rec.cum, rec.shift, rec.mass, o.items, o.scores, o.lp, o.cum, o.shift, o.mass);
+    return 1;
 }
 
 void launch_session_reset(const SessionView& sv, const uint32_t* slot, int n, int d, hipStream_t s) {

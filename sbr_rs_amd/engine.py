@@ -212,6 +212,42 @@ def _rollout_args(steps, mode, temperature):
     return int(steps), mode == "sample"
 
 
+class Beams:
+    """What ``Sessions.beam_search`` returns, beams in selection order at each row's last real step: ``items`` u32 / ``scores`` f32
+    [n, W, steps] — beam b's path and each pick's plain score against the beam's state at that step — ``step_log_probs`` f32 [n, W,
+    steps], the contract's lp of each pick, and ``log_probs`` f32 [n, W], the beam's cum; padding (0xFFFFFFFF, -inf), -inf in both
+    log-probabilities.  ``lengths`` u32 [n]: the real steps of each row; ``beams`` u32 [n]: its live beams (fewer than W while the
+    distinct paths are fewer).  With ``partitions``: ``shift`` f32 / ``mass`` u64 [n, W, steps] and ``frac_bits``, each step's
+    ``log_partition`` of the beam (-inf / 0 at padding); else None."""
+
+    def __init__(self, items, scores, step_log_probs, log_probs, lengths, beams, shift=None, mass=None, frac_bits=None):
+        self.items, self.scores, self.step_log_probs, self.log_probs = items, scores, step_log_probs, log_probs
+        self.lengths, self.beams = lengths, beams
+        self.shift, self.mass, self.frac_bits = shift, mass, frac_bits
+
+    def best(self):
+        """Beam 0 of every row, u32 [n, steps]: the most likely continuation found."""
+        return self.items[:, 0, :].copy()
+
+    def rows(self, b: int = 0):
+        """Beam b's real picks of each row, one u32 array per row (empty where the row has fewer than b + 1 beams): what
+        ``Sessions.append(slots, beams.rows(b))`` makes happen."""
+        return [self.items[i, b, : int(n)].copy() if b < int(k) else np.zeros(0, np.uint32)
+                for i, (n, k) in enumerate(zip(self.lengths, self.beams))]
+
+
+def _beam_args(steps, width, temperature):
+    """The checks of a beam search that need no library: steps, width, temperature -> (steps, width)."""
+    from ._abi import BEAM_MAX_WIDTH, ROLLOUT_MAX_STEPS
+
+    if isinstance(steps, bool) or int(steps) != steps or not 1 <= int(steps) <= ROLLOUT_MAX_STEPS:
+        raise ValueError(f"steps: 1..{ROLLOUT_MAX_STEPS}; got {steps!r}")
+    if isinstance(width, bool) or int(width) != width or not 1 <= int(width) <= BEAM_MAX_WIDTH:
+        raise ValueError(f"width: 1..{BEAM_MAX_WIDTH}; got {width!r}")
+    _rollout_args(1, "greedy", temperature)
+    return int(steps), int(width)
+
+
 ABOVE_MAX_RESULTS = 1 << 24  # the *_above calls' default max_results: the entries of the one buffer they call with
 ABOVE_ORDERS = ("score", "id")
 
@@ -1535,6 +1571,25 @@ class Model:
         finally:
             store.close()
 
+    def beam_search(self, histories, steps: int, width: int = 4, temperature: float = 1.0, exclude_history: bool = True, any_of=None,
+                    none_of=None, allow_repeats: bool = False, partitions: bool = False) -> "Beams":
+        """``Sessions.beam_search`` from histories (a list of item-id sequences), DEFINED as rollout's Model form is: a temporary
+        store of one slot per history, ``append`` of each history's last max_sequence_length items, and ``store.beam_search`` of all
+        slots with — ``exclude_history`` — each history's items as ``exclude``."""
+        _beam_args(steps, width, temperature)
+        seqs = [np.asarray(h, dtype=np.uint32).ravel() for h in histories]
+        if not seqs:
+            raise ValueError("histories: at least one")
+        T = int(self.hp.max_sequence_length)
+        store = Sessions(self, len(seqs))
+        try:
+            slots = np.arange(len(seqs), dtype=np.uint32)
+            store.append(slots, [s[-T:] if s.size > T else s for s in seqs])
+            return store.beam_search(slots, steps, width=width, temperature=temperature, exclude=seqs if exclude_history else None,
+                                     any_of=any_of, none_of=none_of, allow_repeats=allow_repeats, partitions=partitions)
+        finally:
+            store.close()
+
     def item_set(self, item_ids) -> "ItemSet":
         """An item set of this model (sbr_item_set_create; ``ItemSet``): ``item_ids`` in any order, duplicates allowed, each below
         num_items.  Its rows are gathered to the device once; every catalogue call is then offered restricted to the set."""
@@ -1972,6 +2027,48 @@ class Sessions:
         if final_state:
             out.h, out.c, out.len = h, c, self.lengths(sl) + lengths.astype(np.uint64)
         return out
+
+    def beam_search(self, slots, steps: int, width: int = 4, temperature: float = 1.0, exclude=None, any_of=None, none_of=None,
+                    include_seen: bool = False, allow_repeats: bool = False, partitions: bool = False) -> Beams:
+        """The ``width`` most likely next-``steps`` continuations of each slot, searched on the device (sbr_sessions_beam_search;
+        greedy, deterministic) WITHOUT writing the store.  Eligibility is ``rollout``'s: ``exclude``, the seen-item memory unless
+        ``include_seen``, ``any_of`` / ``none_of``, minus the beam's own path unless ``allow_repeats``.  At every step each live
+        beam offers its first ``width`` eligible items in every call's order, each offer's log-probability lp is the contract's f32
+        approximation of log(w / mass) under ``log_partition`` at ``temperature`` (finite where the scores are; not
+        ``Partition.log_prob``, which is -inf where w == 0), and the row keeps the ``width`` best offers by (cumulative lp
+        descending, parent beam ascending, offer position ascending).  ``partitions``: each (beam, step)'s exact shift and mass too.
+        With width 1 the items are greedy ``rollout``'s."""
+        from ._abi import ROLLOUT_ALLOW_REPEATS, ROLLOUT_INCLUDE_SEEN, SbrBeamArgs
+
+        steps, width = _beam_args(steps, width, temperature)
+        if include_seen and not self._seen:
+            raise ValueError("include_seen: this store has no seen-item memory (sessions(capacity, remember=W))")
+        sl = self._slots(slots)
+        n = sl.size
+        masks = _tag_masks(any_of, none_of, n)
+        ep, ei = _exclusion_csr(exclude, n)
+        ba = SbrBeamArgs()
+        ba.steps, ba.width = steps, width
+        ba.flags = (ROLLOUT_ALLOW_REPEATS if allow_repeats else 0) | (ROLLOUT_INCLUDE_SEEN if include_seen else 0)
+        ba.temperature = float(np.float32(temperature))
+        shape = (n, width, steps)
+        items = np.zeros(shape, dtype=np.uint32)
+        scores = np.zeros(shape, dtype=np.float32)
+        step_lp = np.zeros(shape, dtype=np.float32)
+        cum = np.zeros((n, width), dtype=np.float32)
+        lengths = np.zeros(max(n, 1), dtype=np.uint32)
+        beams = np.zeros(max(n, 1), dtype=np.uint32)
+        shift = np.zeros(shape, dtype=np.float32) if partitions else None
+        mass = np.zeros(shape, dtype=np.uint64) if partitions else None
+        fb = C.c_uint32(0)
+
+        def opt(a):
+            return None if a is None else _ptr(a)
+
+        _check(self._L.sbr_sessions_beam_search(self._h, _ptr(sl), n, C.byref(ba), opt(ep), opt(ei), None if masks is None else _ptr(masks[0]),
+                                                None if masks is None else _ptr(masks[1]), _ptr(items), _ptr(scores), _ptr(step_lp), _ptr(cum),
+                                                _ptr(lengths), _ptr(beams), opt(shift), opt(mass), C.byref(fb) if partitions else None))
+        return Beams(items, scores, step_lp, cum, lengths[:n], beams[:n], shift=shift, mass=mass, frac_bits=fb.value if partitions else None)
 
     def state(self, slots):
         """Checkpoint of the named slots: (h [n, embedding_dim], c likewise — None for EWMA —, len [n] u64)."""

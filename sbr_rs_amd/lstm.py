@@ -504,6 +504,14 @@ class _ImplicitSequenceModel:
                                    exclude_history=exclude_history, any_of=any_of, none_of=none_of, allow_repeats=allow_repeats,
                                    log_prob=log_prob, final_state=final_state)
 
+    def beam_search(self, histories, steps: int, width: int = 4, temperature: float = 1.0, exclude_history: bool = True, any_of=None,
+                    none_of=None, allow_repeats: bool = False, partitions: bool = False):
+        """The ``width`` most likely next-``steps`` continuations of each history, searched on the device (``engine.Beams``;
+        ``engine.Sessions.beam_search`` is the call, and its docstring the contract): defined as a temporary session store,
+        ``append`` of each history's last max_sequence_length items and ``store.beam_search``."""
+        return self.params.beam_search(histories, steps, width=width, temperature=temperature, exclude_history=exclude_history,
+                                       any_of=any_of, none_of=none_of, allow_repeats=allow_repeats, partitions=partitions)
+
     def load_sessions(self, path, capacity=None, remember=None, replay: bool = False):
         """A session store restored from a file written by ``store.save(path)`` (``persistence.load_sessions``).  With
         ``replay=True`` only the remembered items are restored and every state is recomputed from them on the device under this
