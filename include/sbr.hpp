@@ -1137,7 +1137,10 @@ class Sessions {
     /// store — a rollout is hypothetical; append its rows to make it happen.  Step j picks among what `recommend` would offer at
     /// call time minus picks 0 .. j - 1 (with allow_repeats: the picks stay eligible), scored against the state after those picks.
     /// The insert of a pick into its row's exclusion list costs O(list) per step; steps <= SBR_ROLLOUT_MAX_STEPS.
-    Result<Rollout, PredictionError> rollout(const std::vector<std::uint32_t>& slots, const RolloutArgs& a) const {
+    Result<Rollout, PredictionError> rollout(const std::vector<std::uint32_t>& slots, const RolloutArgs& a) const { return rollout_in(nullptr, slots, a); }
+    /// rollout, or (set non-null) the same within an item set: sbr_item_set_rollout through a store descriptor of these slots
+    /// (ItemSet::OnSessions::rollout).
+    Result<Rollout, PredictionError> rollout_in(sbr_item_set* set, const std::vector<std::uint32_t>& slots, const RolloutArgs& a) const {
         using R = Result<Rollout, PredictionError>;
         if (a.steps < 1 || a.steps > SBR_ROLLOUT_MAX_STEPS) throw EngineError(SBR_ERR_INVALID_ARGUMENT, "Sessions::rollout: steps outside 1..SBR_ROLLOUT_MAX_STEPS");
         if (!a.excl_ptr.empty() && (a.excl_ptr.size() != slots.size() + 1 || a.excl_ptr.back() > a.excl_items.size()))
@@ -1168,15 +1171,21 @@ class Sessions {
             if (a.lstm) r.c.resize(n * dim_);
         }
         const std::uint32_t none = 0;
-        const sbr_status st = sbr_sessions_rollout(h_, slots.data(), (std::uint64_t)n, &ra, a.excl_ptr.empty() ? nullptr : a.excl_ptr.data(),
-                                                   a.excl_ptr.empty() ? nullptr : (a.excl_items.empty() ? &none : a.excl_items.data()),
-                                                   filtered ? any.data() : nullptr, filtered ? none_of.data() : nullptr, r.items.data(),
-                                                   r.scores.data(), a.sample ? r.keys.data() : nullptr, r.lengths.data(),
-                                                   a.log_prob ? r.partition.shift.data() : nullptr, a.log_prob ? r.partition.mass.data() : nullptr,
-                                                   a.log_prob ? &r.partition.frac_bits : nullptr, a.final_state ? r.h.data() : nullptr,
-                                                   a.final_state && a.lstm ? r.c.data() : nullptr);
+        const sbr_scan_rows d = store_rows(slots, a.excl_ptr, a.excl_items, filtered ? any.data() : nullptr, filtered ? none_of.data() : nullptr);
+        const sbr_status st =
+            set ? sbr_item_set_rollout(set, &d, (std::uint64_t)n, &ra, r.items.data(), r.scores.data(), a.sample ? r.keys.data() : nullptr, r.lengths.data(),
+                                       a.log_prob ? r.partition.shift.data() : nullptr, a.log_prob ? r.partition.mass.data() : nullptr,
+                                       a.log_prob ? &r.partition.frac_bits : nullptr, a.final_state ? r.h.data() : nullptr,
+                                       a.final_state && a.lstm ? r.c.data() : nullptr)
+                : sbr_sessions_rollout(h_, slots.data(), (std::uint64_t)n, &ra, a.excl_ptr.empty() ? nullptr : a.excl_ptr.data(),
+                                       a.excl_ptr.empty() ? nullptr : (a.excl_items.empty() ? &none : a.excl_items.data()),
+                                       filtered ? any.data() : nullptr, filtered ? none_of.data() : nullptr, r.items.data(),
+                                       r.scores.data(), a.sample ? r.keys.data() : nullptr, r.lengths.data(),
+                                       a.log_prob ? r.partition.shift.data() : nullptr, a.log_prob ? r.partition.mass.data() : nullptr,
+                                       a.log_prob ? &r.partition.frac_bits : nullptr, a.final_state ? r.h.data() : nullptr,
+                                       a.final_state && a.lstm ? r.c.data() : nullptr);
         if (st == SBR_ERR_INVALID_PREDICTION) return R::Err(PredictionError::InvalidPredictionValue);
-        check(st, "sbr_sessions_rollout");
+        check(st, set ? "sbr_item_set_rollout" : "sbr_sessions_rollout");
         if (a.log_prob) { /* one partition row per (row, step): the library's one host statement of the weights */
             r.log_prob = r.partition.log_prob(r.scores);
             for (std::size_t p = 0; p < cells; ++p)
@@ -1193,7 +1202,10 @@ class Sessions {
     /// deterministic) WITHOUT writing the store.  Eligibility is rollout's, minus each beam's own path unless allow_repeats; each
     /// live beam offers its first width eligible items per step, and the row keeps the width best offers by (cumulative f32 lp
     /// descending, parent beam ascending, offer position ascending).  width <= SBR_BEAM_MAX_WIDTH, steps <= SBR_ROLLOUT_MAX_STEPS.
-    Result<Beams, PredictionError> beam_search(const std::vector<std::uint32_t>& slots, const BeamArgs& a) const {
+    Result<Beams, PredictionError> beam_search(const std::vector<std::uint32_t>& slots, const BeamArgs& a) const { return beam_search_in(nullptr, slots, a); }
+    /// beam_search, or (set non-null) the same within an item set: sbr_item_set_beam_search through a store descriptor of these
+    /// slots (ItemSet::OnSessions::beam_search).
+    Result<Beams, PredictionError> beam_search_in(sbr_item_set* set, const std::vector<std::uint32_t>& slots, const BeamArgs& a) const {
         using R = Result<Beams, PredictionError>;
         if (a.steps < 1 || a.steps > SBR_ROLLOUT_MAX_STEPS) throw EngineError(SBR_ERR_INVALID_ARGUMENT, "Sessions::beam_search: steps outside 1..SBR_ROLLOUT_MAX_STEPS");
         if (a.width < 1 || a.width > SBR_BEAM_MAX_WIDTH) throw EngineError(SBR_ERR_INVALID_ARGUMENT, "Sessions::beam_search: width outside 1..SBR_BEAM_MAX_WIDTH");
@@ -1224,15 +1236,33 @@ class Sessions {
             r.partition.mass.resize(cells);
         }
         const std::uint32_t none = 0;
-        const sbr_status st = sbr_sessions_beam_search(h_, slots.data(), (std::uint64_t)n, &ba, a.excl_ptr.empty() ? nullptr : a.excl_ptr.data(),
-                                                       a.excl_ptr.empty() ? nullptr : (a.excl_items.empty() ? &none : a.excl_items.data()),
-                                                       filtered ? any.data() : nullptr, filtered ? none_of.data() : nullptr, r.items.data(),
-                                                       r.scores.data(), r.step_lp.data(), r.cum.data(), r.lengths.data(), r.beams.data(),
-                                                       a.partitions ? r.partition.shift.data() : nullptr, a.partitions ? r.partition.mass.data() : nullptr,
-                                                       a.partitions ? &r.partition.frac_bits : nullptr);
+        const sbr_scan_rows d = store_rows(slots, a.excl_ptr, a.excl_items, filtered ? any.data() : nullptr, filtered ? none_of.data() : nullptr);
+        const sbr_status st =
+            set ? sbr_item_set_beam_search(set, &d, (std::uint64_t)n, &ba, r.items.data(), r.scores.data(), r.step_lp.data(), r.cum.data(),
+                                           r.lengths.data(), r.beams.data(), a.partitions ? r.partition.shift.data() : nullptr,
+                                           a.partitions ? r.partition.mass.data() : nullptr, a.partitions ? &r.partition.frac_bits : nullptr)
+                : sbr_sessions_beam_search(h_, slots.data(), (std::uint64_t)n, &ba, a.excl_ptr.empty() ? nullptr : a.excl_ptr.data(),
+                                           a.excl_ptr.empty() ? nullptr : (a.excl_items.empty() ? &none : a.excl_items.data()),
+                                           filtered ? any.data() : nullptr, filtered ? none_of.data() : nullptr, r.items.data(),
+                                           r.scores.data(), r.step_lp.data(), r.cum.data(), r.lengths.data(), r.beams.data(),
+                                           a.partitions ? r.partition.shift.data() : nullptr, a.partitions ? r.partition.mass.data() : nullptr,
+                                           a.partitions ? &r.partition.frac_bits : nullptr);
         if (st == SBR_ERR_INVALID_PREDICTION) return R::Err(PredictionError::InvalidPredictionValue);
-        check(st, "sbr_sessions_beam_search");
+        check(st, set ? "sbr_item_set_beam_search" : "sbr_sessions_beam_search");
         return R::Ok(std::move(r));
+    }
+    /// The store descriptor (struct sbr_scan_rows) of these slots with the caller's lists and masks, flags 0: the rows of
+    /// rollout_in / beam_search_in through a set.  The arrays must outlive the call.
+    sbr_scan_rows store_rows(const std::vector<std::uint32_t>& slots, const std::vector<std::uint64_t>& excl_ptr,
+                             const std::vector<std::uint32_t>& excl_items, const std::uint32_t* any_of, const std::uint32_t* none_of) const {
+        static const std::uint32_t none = 0;
+        sbr_scan_rows d{};
+        d.store = h_;
+        d.slots = slots.empty() ? &none : slots.data();
+        if (!excl_ptr.empty()) { d.excl_ptr = excl_ptr.data(); d.excl_items = excl_items.empty() ? &none : excl_items.data(); }
+        d.any_of = any_of;
+        d.none_of = none_of;
+        return d;
     }
     /// `recommend_diverse` under a tag filter: the pool holds eligible items only (sbr_sessions_recommend_diverse_filtered).
     Result<Recommendations, PredictionError> recommend_diverse_filtered(const std::vector<std::uint32_t>& slots, std::size_t k, std::size_t pool,
@@ -1516,15 +1546,21 @@ class Sessions {
 /// Obtained from ImplicitSequenceModel::item_set; the model (and a store it is used with) must outlive it.  Movable, not copyable.
 class ItemSet {
   public:
-    ItemSet(sbr_model* model, const std::vector<std::uint32_t>& item_ids, std::size_t embedding_dim, std::size_t num_items)
-        : m_(model), dim_(embedding_dim), num_items_(num_items) {
+    /// max_sequence_length / lstm: the model's, for rollout and beam_search over histories (0: not known, those two refuse).
+    ItemSet(sbr_model* model, const std::vector<std::uint32_t>& item_ids, std::size_t embedding_dim, std::size_t num_items,
+            std::size_t max_sequence_length = 0, bool lstm = true)
+        : m_(model), dim_(embedding_dim), num_items_(num_items), max_len_(max_sequence_length), lstm_(lstm) {
         check(sbr_item_set_create(model, item_ids.empty() ? nullptr : item_ids.data(), (std::uint64_t)item_ids.size(), &h_), "sbr_item_set_create");
     }
     ItemSet(const ItemSet&) = delete;
     ItemSet& operator=(const ItemSet&) = delete;
-    ItemSet(ItemSet&& o) noexcept : h_(o.h_), m_(o.m_), dim_(o.dim_), num_items_(o.num_items_) { o.h_ = nullptr; }
+    ItemSet(ItemSet&& o) noexcept : h_(o.h_), m_(o.m_), dim_(o.dim_), num_items_(o.num_items_), max_len_(o.max_len_), lstm_(o.lstm_) { o.h_ = nullptr; }
     ItemSet& operator=(ItemSet&& o) noexcept {
-        if (this != &o) { release(); h_ = o.h_; m_ = o.m_; dim_ = o.dim_; num_items_ = o.num_items_; o.h_ = nullptr; }
+        if (this != &o) {
+            release();
+            h_ = o.h_; m_ = o.m_; dim_ = o.dim_; num_items_ = o.num_items_; max_len_ = o.max_len_; lstm_ = o.lstm_;
+            o.h_ = nullptr;
+        }
         return *this;
     }
     ~ItemSet() { release(); }
@@ -1842,12 +1878,39 @@ class ItemSet {
                                                                    const std::vector<std::uint32_t>& excl_items = {}, const TagFilter& filter = {}) const {
             return set_.recommend_diverse(set_.of(store_, slots, excl_ptr, excl_items, false, filter), k, pool, trade_off, metric);
         }
+        /// Sessions::rollout within the set (sbr_item_set_rollout): the store's own rollout with every item outside the set added
+        /// to each row's exclusion list, bit for bit; frac_bits is the model's.
+        Result<Rollout, PredictionError> rollout(const std::vector<std::uint32_t>& slots, const RolloutArgs& a) const {
+            return store_.rollout_in(set_.h_, slots, a);
+        }
+        /// Sessions::beam_search within the set (sbr_item_set_beam_search), under rollout's rule.
+        Result<Beams, PredictionError> beam_search(const std::vector<std::uint32_t>& slots, const BeamArgs& a) const {
+            return store_.beam_search_in(set_.h_, slots, a);
+        }
 
       private:
         const ItemSet& set_;
         const Sessions& store_;
     };
     OnSessions on(const Sessions& store) const { return OnSessions(*this, store); }
+
+    /// ImplicitSequenceModel::rollout within the set, DEFINED as that call is: a temporary store of one slot per user, `append` of
+    /// each history's last max_sequence_length items, and on(store).rollout of all slots — with exclude_history each history's
+    /// items as its exclusion list, replacing a.excl_ptr / a.excl_items; a.lstm is set from the model.
+    Result<Rollout, PredictionError> rollout(const data::CompressedInteractions& histories, RolloutArgs a, bool exclude_history = true) const {
+        std::vector<std::uint32_t> slots;
+        Sessions store = histories_store("ItemSet::rollout", histories, exclude_history, &slots, &a.excl_ptr, &a.excl_items);
+        a.lstm = lstm_;
+        a.include_seen = false;
+        return on(store).rollout(slots, a);
+    }
+    /// ImplicitSequenceModel::beam_search within the set, DEFINED as rollout's histories form is.
+    Result<Beams, PredictionError> beam_search(const data::CompressedInteractions& histories, BeamArgs a, bool exclude_history = true) const {
+        std::vector<std::uint32_t> slots;
+        Sessions store = histories_store("ItemSet::beam_search", histories, exclude_history, &slots, &a.excl_ptr, &a.excl_items);
+        a.include_seen = false;
+        return on(store).beam_search(slots, a);
+    }
 
   private:
     static Recommendations top_rows(std::size_t n, std::size_t k) {
@@ -1876,9 +1939,37 @@ class ItemSet {
         if (h_) sbr_item_set_destroy(h_);
         h_ = nullptr;
     }
+    /// ImplicitSequenceModel::rollout's temporary store: one slot per user, each history's last max_sequence_length items appended;
+    /// with exclude_history each history's items become the exclusion list (replacing excl_ptr / excl_items).
+    Sessions histories_store(const char* me, const data::CompressedInteractions& histories, bool exclude_history, std::vector<std::uint32_t>* slots,
+                             std::vector<std::uint64_t>* excl_ptr, std::vector<std::uint32_t>* excl_items) const {
+        const std::vector<std::uint64_t>& up = histories.user_pointers();
+        const std::vector<std::uint32_t>& ids = histories.item_ids();
+        const std::size_t n = histories.num_users();
+        if (n == 0) throw EngineError(SBR_ERR_INVALID_ARGUMENT, std::string(me) + ": at least one history");
+        if (max_len_ == 0) throw EngineError(SBR_ERR_INVALID_ARGUMENT, std::string(me) + ": a set made by ImplicitSequenceModel::item_set");
+        std::vector<std::uint32_t> tail;
+        std::vector<std::uint64_t> tail_ptr(n + 1, 0);
+        slots->resize(n);
+        for (std::size_t u = 0; u < n; ++u) {
+            (*slots)[u] = (std::uint32_t)u;
+            const std::uint64_t keep = std::min<std::uint64_t>(up[u + 1] - up[u], max_len_);
+            tail.insert(tail.end(), ids.begin() + (std::ptrdiff_t)(up[u + 1] - keep), ids.begin() + (std::ptrdiff_t)up[u + 1]);
+            tail_ptr[u + 1] = tail.size();
+        }
+        Sessions store(m_, n, dim_);
+        store.append(*slots, tail_ptr, tail);
+        if (exclude_history) {
+            excl_ptr->assign(up.begin(), up.end());
+            for (std::uint64_t& p : *excl_ptr) p -= up.front();
+            excl_items->assign(ids.begin() + (std::ptrdiff_t)up.front(), ids.begin() + (std::ptrdiff_t)up.back());
+        }
+        return store;
+    }
     sbr_item_set* h_ = nullptr;
     sbr_model* m_ = nullptr;
-    std::size_t dim_ = 0, num_items_ = 0;
+    std::size_t dim_ = 0, num_items_ = 0, max_len_ = 0;
+    bool lstm_ = true;
 };
 
 /// Owner of the device replicas behind one model object: `num_threads` replicas (≙ the worker
@@ -2809,7 +2900,8 @@ class ImplicitSequenceModel : public OnlineRankingModel<ImplicitUser> {
     /// An item set of this model on the primary replica (see ItemSet): `item_ids` in any order, duplicates allowed, each below
     /// num_items.  Destroy it before this model; call its refresh() after `fit`.
     ItemSet item_set(const std::vector<std::uint32_t>& item_ids) const {
-        return ItemSet(replicas_->primary(), item_ids, replicas_->hparams().embedding_dim, replicas_->hparams().num_items);
+        return ItemSet(replicas_->primary(), item_ids, replicas_->hparams().embedding_dim, replicas_->hparams().num_items,
+                       replicas_->hparams().max_sequence_length, replicas_->hparams().model != 2);
     }
 
     /// The engine handle (replica 0), for evaluation's fused path and for parameter access.

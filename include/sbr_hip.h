@@ -853,7 +853,8 @@ sbr_status sbr_sessions_log_partition(sbr_sessions* st, const uint32_t* slots, u
  * SBR_ERR_INVALID_ARGUMENT, with nothing launched: args NULL, steps out of range, unknown flags, a temperature sbr_sample_args
  * refuses (checked in both modes), SBR_ROLLOUT_INCLUDE_SEEN on a store without memory, masks on a model without tags, a stale store,
  * an open fit plan, a slot out of range or named twice.  SBR_ERR_INVALID_PREDICTION: a non-finite score at any step fails the whole
- * call, as in sbr_recommend: what the outputs then hold is unspecified, and no binding returns it.  Not built: k > 1 per step (see BEAM SEARCH below), item sets, a rollout that commits, caps or
+ * call, as in sbr_recommend: what the outputs then hold is unspecified, and no binding returns it.  Within an item set:
+ * sbr_item_set_rollout (ITEM SETS below).  Not built: k > 1 per step (see BEAM SEARCH below), a rollout that commits, caps or
  * thresholds inside a rollout, a per-step temperature, rollouts from *_reps rows. */
 #define SBR_ROLLOUT_MAX_STEPS 1024u
 #define SBR_ROLLOUT_SAMPLE 1u
@@ -903,7 +904,8 @@ sbr_status sbr_sessions_rollout(sbr_sessions* st, const uint32_t* slots, uint64_
  * SBR_ERR_INVALID_ARGUMENT, with nothing launched: args NULL, width or steps out of range, unknown flags (SBR_ROLLOUT_SAMPLE among
  * them), a temperature sbr_sample_args refuses, SBR_ROLLOUT_INCLUDE_SEEN on a store without memory, masks on a model without tags, a
  * stale store, an open fit plan, a slot out of range or named twice.  SBR_ERR_INVALID_PREDICTION: a non-finite score at any step
- * fails the whole call.  Not built: stochastic beam search, item sets, caps, beams that commit to the store. */
+ * fails the whole call.  Within an item set: sbr_item_set_beam_search (ITEM SETS below).  Not built: stochastic beam search, caps,
+ * beams that commit to the store. */
 #define SBR_BEAM_MAX_WIDTH 32u
 typedef struct sbr_beam_args {
     uint32_t steps;
@@ -1123,8 +1125,9 @@ const char* sbr_status_string(sbr_status s);
  *   representations  reps [num_rows][embedding_dim] as the *_reps calls', flags 0, with the optional lists excl_ptr / excl_items;
  *   a store          store / slots as the sbr_sessions_* scans', the store current and of the set's model, flags as theirs
  *                    (SBR_RECOMMEND_INCLUDE_HISTORY: do not exclude the seen items), with the optional lists.
- * any_of / none_of (both NULL: no filter) are the tag masks of the filtered forms, one pair per row.  The seven calls take the
- * descriptor and then the argument tail of their *_reps siblings without the lists and masks, which the descriptor carries. */
+ * any_of / none_of (both NULL: no filter) are the tag masks of the filtered forms, one pair per row.  The seven scan calls take the
+ * descriptor and then the argument tail of their *_reps siblings without the lists and masks, which the descriptor carries; the
+ * rollout and beam-search calls take a store descriptor and the argument tail of their sbr_sessions_* siblings. */
 typedef struct sbr_item_set sbr_item_set;
 typedef struct sbr_scan_rows {     /* exactly one of the three sources */
     const uint64_t* user_ptr; const uint32_t* item_ids; uint32_t flags;   /* histories; SBR_RECOMMEND_INCLUDE_HISTORY */
@@ -1152,6 +1155,20 @@ sbr_status sbr_item_set_recommend_top(sbr_item_set* set, const struct sbr_scan_r
                                       uint64_t* out_counts, uint64_t* out_total, uint64_t capacity, uint32_t* out_ids, float* out_scores);
 sbr_status sbr_item_set_recommend_capped(sbr_item_set* set, const struct sbr_scan_rows* rows, uint64_t num_rows, uint32_t k,
                                          const struct sbr_cap_args* cap, uint32_t* out_items, float* out_scores, uint8_t* out_complete);
+/* ROLLOUT and BEAM SEARCH within a set: sbr_sessions_rollout / sbr_sessions_beam_search of rows->store and rows->slots with every
+ * item outside S appended to each row's exclusion list, bit for bit — items (catalogue ids), scores, keys (the same draw per
+ * (seed + j, stream, catalogue id)), lengths, padding, out_h / out_c, out_step_lp / out_cum / out_beams, shift and mass, and
+ * out_frac_bits the MODEL's F.  A set of the whole catalogue is the plain call; an empty set ends every row at step 0 (out_h / out_c
+ * the slots' current states, beams 0).  Only the store source: user_ptr or reps is SBR_ERR_INVALID_ARGUMENT, and so is rows->flags
+ * != 0 — include_seen is said once, as SBR_ROLLOUT_INCLUDE_SEEN in args->flags.  excl_ptr / excl_items and any_of / none_of are the
+ * plain call's, entries outside S ignored.  Every other argument rule is the plain call's, with the set's lifecycle above.  Per step
+ * the unchanged scans run over the set's sub-table and the picks fed back are catalogue ids. */
+sbr_status sbr_item_set_rollout(sbr_item_set* set, const struct sbr_scan_rows* rows, uint64_t num_rows, const struct sbr_rollout_args* args,
+                                uint32_t* out_items, float* out_scores, float* out_keys, uint32_t* out_lengths, float* out_shift,
+                                uint64_t* out_mass, uint32_t* out_frac_bits, float* out_h, float* out_c);
+sbr_status sbr_item_set_beam_search(sbr_item_set* set, const struct sbr_scan_rows* rows, uint64_t num_rows, const struct sbr_beam_args* args,
+                                    uint32_t* out_items, float* out_scores, float* out_step_lp, float* out_cum, uint32_t* out_lengths,
+                                    uint32_t* out_beams, float* out_shift, uint64_t* out_mass, uint32_t* out_frac_bits);
 
 #define SBR_ABI_VERSION 13u /* what sbr_abi_version returns from a library built from this header */
 uint32_t sbr_abi_version(void);

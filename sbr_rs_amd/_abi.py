@@ -140,6 +140,8 @@ class SbrCapArgs(C.Structure):
     ]
 
 
+# sbr_item_set_rollout / sbr_item_set_beam_search take a store descriptor (store / slots, the optional lists and masks, flags 0) and
+# then the argument tail of sbr_sessions_rollout / sbr_sessions_beam_search after their masks: (args, outputs...).
 class SbrScanRows(C.Structure):
     """struct sbr_scan_rows of the sbr_item_set_* scans: exactly one of user_ptr / reps / store names the rows"""
     _fields_ = [

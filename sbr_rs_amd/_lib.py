@@ -210,6 +210,9 @@ def load():
         "sbr_item_set_recommend_above": [vp, vp, C.c_uint64, vp, vp, u64p, C.c_uint64, vp, vp],
         "sbr_item_set_recommend_top": [vp, vp, C.c_uint64, vp, vp, vp, u64p, C.c_uint64, vp, vp],
         "sbr_item_set_recommend_capped": [vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp],
+        # (set, store descriptor, num_rows, args, ...) and the output tail of sbr_sessions_rollout / sbr_sessions_beam_search
+        "sbr_item_set_rollout": [vp, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+        "sbr_item_set_beam_search": [vp, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -285,4 +288,5 @@ DECLARED_SYMBOLS = [
     "sbr_item_set_create", "sbr_item_set_destroy", "sbr_item_set_size", "sbr_item_set_items", "sbr_item_set_refresh",
     "sbr_item_set_recommend", "sbr_item_set_recommend_diverse", "sbr_item_set_recommend_sampled", "sbr_item_set_log_partition",
     "sbr_item_set_recommend_above", "sbr_item_set_recommend_top", "sbr_item_set_recommend_capped",
+    "sbr_item_set_rollout", "sbr_item_set_beam_search",
 ]

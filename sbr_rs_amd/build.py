@@ -261,6 +261,15 @@ def build_beam_tests(force: bool = False, verbose: bool = True) -> str:
     return _build_cpp_program(BEAM_SRC, BEAM_BIN, force, verbose)
 
 
+ITEM_SET_ROLLOUT_SRC = os.path.join(REPO, "tests", "cpp", "item_set_rollout_tests.cpp")
+ITEM_SET_ROLLOUT_BIN = os.path.join(REPO, "tests", "cpp", "_build", "item_set_rollout_tests")
+
+
+def build_item_set_rollout_tests(force: bool = False, verbose: bool = True) -> str:
+    """g++ build of the C++ host layer's rollout / beam-search within an item set test program."""
+    return _build_cpp_program(ITEM_SET_ROLLOUT_SRC, ITEM_SET_ROLLOUT_BIN, force, verbose)
+
+
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv))
     print(build_facade_tests(force="--force" in sys.argv))
@@ -284,3 +293,4 @@ if __name__ == "__main__":
     print(build_item_set_tests(force="--force" in sys.argv))
     print(build_rollout_tests(force="--force" in sys.argv))
     print(build_beam_tests(force="--force" in sys.argv))
+    print(build_item_set_rollout_tests(force="--force" in sys.argv))

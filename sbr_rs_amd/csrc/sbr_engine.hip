@@ -6087,10 +6087,22 @@ size_t rollout_chunk_cap(const sbr_model* m, uint32_t w, uint32_t steps) {
 
 /* One chunk, rows [c0, c0 + nu) of the call: the scratch state and the exclusion CSR with slack, then per step the unchanged k = 1
  * scan (and the partition on the same descriptor), rollout_advance_kernel and one cell step — all queued without a synchronisation —
- * and at the end one flag check and the copies out, as scan_launch does. */
+ * and at the end one flag check and the copies out, as scan_launch does.
+ * With `set` (current; null: the catalogue) the scans run over its sub-table as recommend_scan's do: the tight exclusion CSR becomes
+ * positions of the set before it is spread, the set's tag words are gathered once per chunk, F is the model's and the noise is
+ * hashed from the catalogue ids; the advance turns the picks into ids.  An empty set runs no scan: every pick is padding. */
 sbr_status sessions_rollout_chunk(sbr_sessions* st, const uint32_t* slots, const std::vector<int>& rep0, const uint64_t* excl_ptr,
-                                  const uint32_t* excl_items, const RolloutCall& rc, size_t c0, size_t nu) {
+                                  const uint32_t* excl_items, const RolloutCall& rc, const sbr_item_set* set, size_t c0, size_t nu) {
     sbr_model* m = st->m;
+    const bool none = set && set->ids.empty();
+    const uint32_t ns = set ? (uint32_t)set->ids.size() : 0u;
+    const uint32_t scanned = set ? std::max(ns, 1u) : (uint32_t)m->hp.num_items; /* what the scan's buffers are carved for */
+    sbr::ModelView cat = m->mv; /* what the scans read: the catalogue, or the set's sub-table, whose item j is S[j] */
+    if (set && !none) {
+        cat.E = set->E;
+        cat.b = set->b;
+        cat.num_items = ns;
+    }
     const size_t d = (size_t)m->d, dl = (size_t)m->dl, S = rc.steps;
     const bool lstm = m->ng != 0, sample = rc.sm != nullptr, part = rc.out_shift != nullptr;
     const bool final_state = rc.out_h != nullptr;
@@ -6118,8 +6130,10 @@ sbr_status sessions_rollout_chunk(sbr_sessions* st, const uint32_t* slots, const
     unsigned long long* d_start = nullptr;
     float *pt_scores = nullptr, *pt_shift = nullptr, *fin_h = nullptr, *fin_c = nullptr;
     unsigned long long* pt_mass = nullptr;
+    uint32_t* set_tags = nullptr; /* set: its tag words, gathered by this chunk */
     SBRCHK(carve_arena(m, [&](DeviceArena& ar) {
-        tb.carve(ar, (uint32_t)m->hp.num_items, nu, nexcl, 1, rc.flt != nullptr);
+        tb.carve(ar, scanned, nu, nexcl, 1, rc.flt != nullptr);
+        if (set && rc.flt) set_tags = ar.take<uint32_t>(scanned);
         src_ptr = ar.take<uint64_t>(nu + 1);
         src = ar.take<uint32_t>(nsrc + 1);
         if (seen_w) seen_caller = ar.take<uint32_t>(ncaller + 1);
@@ -6185,20 +6199,25 @@ sbr_status sessions_rollout_chunk(sbr_sessions* st, const uint32_t* slots, const
     rr.n = (int)nu; rr.steps = rc.steps;
     rr.slot = d_slot; rr.ident = d_ident; rr.start = d_start;
     /* the step's scan: the pick's descriptor, and with the partition in sample mode a second one whose k = 1 scan is the plain one */
-    sbr::TopkScan sc = tb.scan(nu, 1, excl, true, rc.flt ? m->item_tags : nullptr);
+    sbr::TopkScan sc = tb.scan(nu, 1, excl, true, !rc.flt ? nullptr : set ? set_tags : m->item_tags);
     sbr::TopkScan sc_pt = sc;
     if (sample) {
         sc.g = sbr::SampleNoise{rc.sm->inv_t, smb.keys};
         sc_pt.out_items = pt_items;
         sc_pt.out_scores = pt_scores;
     }
-    const sbr::RolloutPick pick{tb.items, sample ? smb.plain : tb.scores, sample ? tb.scores : nullptr, pt_shift, pt_mass};
+    /* a set's picks leave as ids: the plain scan's are positions, the sampled launch's already ids */
+    const sbr::RolloutPick pick{tb.items, sample ? smb.plain : tb.scores, sample ? tb.scores : nullptr, pt_shift, pt_mass,
+                                none ? nullptr : set ? set->d_ids : nullptr, ns, sample};
     const size_t parity_stride = nu * d;
     HIPCHK(hipMemsetAsync(tb.flag, 0, 4, m->stream));
+    if (none) HIPCHK(hipMemsetAsync(tb.items, 0xFF, nu * 4, m->stream)); /* nothing to scan: every step's pick is padding */
     {
         ScopedTimer t(m, SBR_K_RANK, 0);
         int n = sbr::launch_rollout_begin(m->mv, st->v, rr, m->stream);
         if (seen_w) n += sbr::launch_session_seen_lists(st->seen, d_slot, (int)nu, src_ptr, seen_caller, src, m->stream);
+        if (set && !none && nsrc) n += sbr::launch_subset_positions(set->d_ids, ns, src_ptr, (uint32_t)nu, src, m->stream);
+        if (set_tags && !none) n += sbr::launch_subset_words(set->d_ids, ns, m->item_tags, set_tags, m->stream);
         if (excl) n += sbr::launch_rollout_segments(src_ptr, src, (int)nu, slack, tb.excl, m->stream);
         t.tp.launches = (uint64_t)n;
     }
@@ -6209,11 +6228,14 @@ sbr_status sessions_rollout_chunk(sbr_sessions* st, const uint32_t* slots, const
         {
             ScopedTimer t(m, SBR_K_RANK, 0);
             int n = 0;
-            if (sample)
-                n += sbr::launch_recommend_sampled(m->mv, reps, sc, sbr::SampleScan{rc.sm->seed + (uint64_t)j, smb.streams, smb.pair_row,
-                                                                                   smb.pair_item, smb.plain, nullptr}, m->stream);
-            if (part) n += sbr::launch_log_partition(m->mv, reps, sc_pt, sbr::PartitionScan{rc.inv_t, pt_shift, pt_mass, 0u}, m->stream);
-            else if (!sample) n += sbr::launch_recommend(m->mv, reps, sc, m->stream);
+            if (!none) { /* a set's mass is held to the model's F, and its noise to the catalogue ids */
+                const uint32_t f_items = set ? (uint32_t)m->hp.num_items : 0u;
+                if (sample)
+                    n += sbr::launch_recommend_sampled(cat, reps, sc, sbr::SampleScan{rc.sm->seed + (uint64_t)j, smb.streams, smb.pair_row,
+                                                                                     smb.pair_item, smb.plain, set ? set->d_ids : nullptr}, m->stream);
+                if (part) n += sbr::launch_log_partition(cat, reps, sc_pt, sbr::PartitionScan{rc.inv_t, pt_shift, pt_mass, f_items}, m->stream);
+                else if (!sample) n += sbr::launch_recommend(cat, reps, sc, m->stream);
+            }
             n += sbr::launch_rollout_advance(rr, j, pick, slack ? tb.eptr : nullptr, tb.excl, ro, m->stream);
             t.tp.launches = (uint64_t)n;
         }
@@ -6244,12 +6266,13 @@ sbr_status sessions_rollout_chunk(sbr_sessions* st, const uint32_t* slots, const
     return SBR_OK;
 }
 
-}  // namespace
+sbr_status enter_item_set(const sbr_item_set* set);
 
-sbr_status sbr_sessions_rollout(sbr_sessions* st, const uint32_t* slots, uint64_t n, const struct sbr_rollout_args* args,
-                                const uint64_t* excl_ptr, const uint32_t* excl_items, const uint32_t* any_of, const uint32_t* none_of,
-                                uint32_t* out_items, float* out_scores, float* out_keys, uint32_t* out_lengths, float* out_shift,
-                                uint64_t* out_mass, uint32_t* out_frac_bits, float* out_h, float* out_c) {
+/* sbr_sessions_rollout, or (set non-null: the caller checked that it is the store's model's) sbr_item_set_rollout */
+sbr_status rollout_call(sbr_sessions* st, const sbr_item_set* set, const uint32_t* slots, uint64_t n, const struct sbr_rollout_args* args,
+                        const uint64_t* excl_ptr, const uint32_t* excl_items, const uint32_t* any_of, const uint32_t* none_of,
+                        uint32_t* out_items, float* out_scores, float* out_keys, uint32_t* out_lengths, float* out_shift,
+                        uint64_t* out_mass, uint32_t* out_frac_bits, float* out_h, float* out_c) {
     constexpr uint32_t known = SBR_ROLLOUT_SAMPLE | SBR_ROLLOUT_ALLOW_REPEATS | SBR_ROLLOUT_INCLUDE_SEEN;
     if (!st || !args || (n && !out_items)) return SBR_ERR_INVALID_ARGUMENT;
     if (args->steps < 1 || args->steps > SBR_ROLLOUT_MAX_STEPS || (args->flags & ~known)) return SBR_ERR_INVALID_ARGUMENT;
@@ -6265,6 +6288,7 @@ sbr_status sbr_sessions_rollout(sbr_sessions* st, const uint32_t* slots, uint64_
     if (!excl_args_ok(excl_ptr, excl_items, n)) return SBR_ERR_INVALID_ARGUMENT;
     sbr_model* m = st->m;
     std::lock_guard<std::mutex> lock(m->mu);
+    if (set) SBRCHK(enter_item_set(set));
     SBRCHK(enter_sessions(st));
     SBRCHK(check_slots(st, slots, n));
     if (excl_ptr) SBRCHK(check_csr(m, excl_ptr, n, excl_items, false));
@@ -6280,9 +6304,20 @@ sbr_status sbr_sessions_rollout(sbr_sessions* st, const uint32_t* slots, uint64_
     rc.out_shift = out_shift; rc.out_mass = out_mass; rc.out_h = out_h; rc.out_c = out_c;
     const std::vector<int> rep0 = session_rep_rows(st, slots, n);
     const size_t cap = rollout_chunk_cap(m, rc.seen ? st->seen.w : 0, rc.steps);
-    for (size_t c0 = 0; c0 < n; c0 += cap) SBRCHK(sessions_rollout_chunk(st, slots, rep0, excl_ptr, excl_items, rc, c0, std::min<size_t>(cap, n - c0)));
-    if (out_frac_bits) *out_frac_bits = sbr_softmax_fbits((uint32_t)m->hp.num_items);
+    for (size_t c0 = 0; c0 < n; c0 += cap)
+        SBRCHK(sessions_rollout_chunk(st, slots, rep0, excl_ptr, excl_items, rc, set, c0, std::min<size_t>(cap, n - c0)));
+    if (out_frac_bits) *out_frac_bits = sbr_softmax_fbits((uint32_t)m->hp.num_items); /* the model's, with or without a set */
     return SBR_OK;
+}
+
+}  // namespace
+
+sbr_status sbr_sessions_rollout(sbr_sessions* st, const uint32_t* slots, uint64_t n, const struct sbr_rollout_args* args,
+                                const uint64_t* excl_ptr, const uint32_t* excl_items, const uint32_t* any_of, const uint32_t* none_of,
+                                uint32_t* out_items, float* out_scores, float* out_keys, uint32_t* out_lengths, float* out_shift,
+                                uint64_t* out_mass, uint32_t* out_frac_bits, float* out_h, float* out_c) {
+    return rollout_call(st, nullptr, slots, n, args, excl_ptr, excl_items, any_of, none_of, out_items, out_scores, out_keys, out_lengths,
+                        out_shift, out_mass, out_frac_bits, out_h, out_c);
 }
 
 /* ---------------------------------------------------------------------------------------------
@@ -6321,12 +6356,24 @@ size_t sessions_beam_chunk(const sbr_model* m, uint32_t seen_w, uint32_t w, uint
 /* One chunk, rows [c0, c0 + nu) of the call, nb = nu W beam rows: the tight exclusion lists and the segment CSR, then per step the
  * unchanged top-k scan at k = W with its partition (launch_topk_partition: n rows at step 0, nb after), beam_select_kernel, the
  * children's segments and one cell step — all queued without a synchronisation — and at the end the backtrack, one flag check and
- * the copies out. */
+ * the copies out.
+ * With `set` (current; null: the catalogue) the scans run over its sub-table as recommend_scan's do: the tight lists become positions
+ * of the set before any segment is made from them, the set's tag words are gathered once per chunk, F is the model's; the selection
+ * feeds and records ids and merges positions.  An empty set runs no scan: every row ends at step 0. */
 sbr_status sessions_beam_chunk_run(sbr_sessions* st, const uint32_t* slots, const std::vector<int>& rep0, const uint64_t* excl_ptr,
-                                   const uint32_t* excl_items, const BeamCall& bc, size_t c0, size_t nu) {
+                                   const uint32_t* excl_items, const BeamCall& bc, const sbr_item_set* set, size_t c0, size_t nu) {
     sbr_model* m = st->m;
     const size_t d = (size_t)m->d, S = bc.steps, W = bc.w, nb = nu * W;
     const uint32_t num_items = (uint32_t)m->hp.num_items;
+    const bool none = set && set->ids.empty();
+    const uint32_t ns = set ? (uint32_t)set->ids.size() : 0u;
+    const uint32_t scanned = set ? std::max(ns, 1u) : num_items; /* what the scan's buffers are carved for */
+    sbr::ModelView cat = m->mv; /* what the scans read: the catalogue, or the set's sub-table, whose item j is S[j] */
+    if (set && !none) {
+        cat.E = set->E;
+        cat.b = set->b;
+        cat.num_items = ns;
+    }
     const bool lstm = m->ng != 0, part_out = bc.out_shift != nullptr;
     const size_t seen_w = bc.seen ? st->seen.w : 0;
     const uint32_t slack = bc.allow_repeats ? 0u : bc.steps;
@@ -6344,13 +6391,13 @@ sbr_status sessions_beam_chunk_run(sbr_sessions* st, const uint32_t* slots, cons
     const size_t nsrc = nu * seen_w + ncaller, nseg = W * nsrc + nb * slack;
     const bool excl = excl_ptr || seen_w || slack; /* without any of them nothing is ever excluded */
     uint32_t per = 0;
-    const size_t nlist = std::max(nu * sbr::recommend_groups((uint32_t)nu, num_items, bc.w, &per),
-                                  nb * sbr::recommend_groups((uint32_t)nb, num_items, bc.w, &per));
+    const size_t nlist = std::max(nu * sbr::recommend_groups((uint32_t)nu, scanned, bc.w, &per),
+                                  nb * sbr::recommend_groups((uint32_t)nb, scanned, bc.w, &per));
     int* d_rep = nullptr;
     uint2* lists = nullptr;
     uint32_t *lens = nullptr, *scan_items = nullptr, *flag = nullptr, *d_slot = nullptr, *d_ident = nullptr;
     uint32_t *any0 = nullptr, *none0 = nullptr, *anyb = nullptr, *noneb = nullptr;
-    uint32_t *src = nullptr, *seen_caller = nullptr, *seg[2] = {nullptr, nullptr};
+    uint32_t *src = nullptr, *seen_caller = nullptr, *seg[2] = {nullptr, nullptr}, *set_tags = nullptr;
     uint64_t *src_ptr = nullptr, *seg_ptr = nullptr;
     unsigned long long *d_start = nullptr, *mass = nullptr;
     float *scan_scores = nullptr, *shift = nullptr;
@@ -6372,6 +6419,7 @@ sbr_status sessions_beam_chunk_run(sbr_sessions* st, const uint32_t* slots, cons
             none0 = ar.take<uint32_t>(nu);
             anyb = ar.take<uint32_t>(nb);
             noneb = ar.take<uint32_t>(nb);
+            if (set) set_tags = ar.take<uint32_t>(scanned);
         }
         src_ptr = ar.take<uint64_t>(nu + 1);
         src = ar.take<uint32_t>(nsrc + 1);
@@ -6450,13 +6498,16 @@ sbr_status sessions_beam_chunk_run(sbr_sessions* st, const uint32_t* slots, cons
     br.n = (int)nu; br.w = bc.w; br.steps = bc.steps;
     br.slot = d_slot; br.ident = d_ident; br.start = d_start;
     const uint32_t fb = sbr_softmax_fbits(num_items);
-    const sbr::BeamScan bs{scan_items, scan_scores, shift, mass, bc.inv_t, fb};
+    const sbr::BeamScan bs{scan_items, scan_scores, shift, mass, bc.inv_t, fb, none ? nullptr : set ? set->d_ids : nullptr};
     const size_t parity_stride = nb * d;
     HIPCHK(hipMemsetAsync(flag, 0, 4, m->stream));
+    if (none) HIPCHK(hipMemsetAsync(scan_items, 0xFF, nb * W * 4, m->stream)); /* nothing to scan: no parent has an offer */
     {
         ScopedTimer t(m, SBR_K_RANK, 0);
         int n = sbr::launch_beam_begin(br, m->stream);
         if (seen_w) n += sbr::launch_session_seen_lists(st->seen, d_slot, (int)nu, src_ptr, seen_caller, src, m->stream);
+        if (set && !none && nsrc) n += sbr::launch_subset_positions(set->d_ids, ns, src_ptr, (uint32_t)nu, src, m->stream);
+        if (set_tags && !none) n += sbr::launch_subset_words(set->d_ids, ns, m->item_tags, set_tags, m->stream);
         if (excl && !slack) n += sbr::launch_beam_segments((int)nb, bc.w, src_ptr, src, nullptr, nullptr, seg_ptr, seg[0], m->stream);
         t.tp.launches = (uint64_t)n;
     }
@@ -6471,11 +6522,12 @@ sbr_status sessions_beam_chunk_run(sbr_sessions* st, const uint32_t* slots, cons
         sc.excl_items = j == 0 ? src : seg[slack ? (j - 1) & 1u : 0];
         sc.lists = lists; sc.lens = lens; sc.out_items = scan_items; sc.out_scores = scan_scores;
         sc.nonfinite_flag = flag;
-        sc.f = sbr::TagMasks{bc.flt ? m->item_tags : nullptr, j == 0 ? any0 : anyb, j == 0 ? none0 : noneb};
+        sc.f = sbr::TagMasks{!bc.flt ? nullptr : set ? set_tags : m->item_tags, j == 0 ? any0 : anyb, j == 0 ? none0 : noneb};
         const float* reps = j == 0 ? st->v.H : br.Hs + (size_t)((j - 1) & 1u) * parity_stride;
         {
             ScopedTimer t(m, SBR_K_RANK, 0);
-            int n = sbr::launch_topk_partition(m->mv, reps, sc, sbr::PartitionScan{bc.inv_t, shift, mass, 0u}, m->stream);
+            /* a set's mass is held to the model's F */
+            int n = none ? 0 : sbr::launch_topk_partition(cat, reps, sc, sbr::PartitionScan{bc.inv_t, shift, mass, set ? num_items : 0u}, m->stream);
             n += sbr::launch_beam_select(br, j, bs, rec, m->stream); /* the kernel indexes the record by step */
             if (j + 1 < bc.steps && slack)
                 n += sbr::launch_beam_segments((int)nb, bc.w, j == 0 ? src_ptr : seg_ptr, j == 0 ? src : seg[(j - 1) & 1u], br.src_row, br.pick,
@@ -6508,12 +6560,11 @@ sbr_status sessions_beam_chunk_run(sbr_sessions* st, const uint32_t* slots, cons
     return SBR_OK;
 }
 
-}  // namespace
-
-sbr_status sbr_sessions_beam_search(sbr_sessions* st, const uint32_t* slots, uint64_t n, const struct sbr_beam_args* args,
-                                    const uint64_t* excl_ptr, const uint32_t* excl_items, const uint32_t* any_of, const uint32_t* none_of,
-                                    uint32_t* out_items, float* out_scores, float* out_step_lp, float* out_cum, uint32_t* out_lengths,
-                                    uint32_t* out_beams, float* out_shift, uint64_t* out_mass, uint32_t* out_frac_bits) {
+/* sbr_sessions_beam_search, or (set non-null: the caller checked that it is the store's model's) sbr_item_set_beam_search */
+sbr_status beam_call(sbr_sessions* st, const sbr_item_set* set, const uint32_t* slots, uint64_t n, const struct sbr_beam_args* args,
+                     const uint64_t* excl_ptr, const uint32_t* excl_items, const uint32_t* any_of, const uint32_t* none_of,
+                     uint32_t* out_items, float* out_scores, float* out_step_lp, float* out_cum, uint32_t* out_lengths,
+                     uint32_t* out_beams, float* out_shift, uint64_t* out_mass, uint32_t* out_frac_bits) {
     constexpr uint32_t known = SBR_ROLLOUT_ALLOW_REPEATS | SBR_ROLLOUT_INCLUDE_SEEN;
     if (!st || !args || (n && !out_items)) return SBR_ERR_INVALID_ARGUMENT;
     if (args->steps < 1 || args->steps > SBR_ROLLOUT_MAX_STEPS || (args->flags & ~known)) return SBR_ERR_INVALID_ARGUMENT;
@@ -6528,6 +6579,7 @@ sbr_status sbr_sessions_beam_search(sbr_sessions* st, const uint32_t* slots, uin
     if (!excl_args_ok(excl_ptr, excl_items, n)) return SBR_ERR_INVALID_ARGUMENT;
     sbr_model* m = st->m;
     std::lock_guard<std::mutex> lock(m->mu);
+    if (set) SBRCHK(enter_item_set(set));
     SBRCHK(enter_sessions(st));
     SBRCHK(check_slots(st, slots, n));
     if (excl_ptr) SBRCHK(check_csr(m, excl_ptr, n, excl_items, false));
@@ -6543,9 +6595,20 @@ sbr_status sbr_sessions_beam_search(sbr_sessions* st, const uint32_t* slots, uin
     bc.out_lengths = out_lengths; bc.out_beams = out_beams; bc.out_shift = out_shift; bc.out_mass = out_mass;
     const std::vector<int> rep0 = session_rep_rows(st, slots, n);
     const size_t cap = sessions_beam_chunk(m, bc.seen ? st->seen.w : 0, bc.w, bc.steps);
-    for (size_t c0 = 0; c0 < n; c0 += cap) SBRCHK(sessions_beam_chunk_run(st, slots, rep0, excl_ptr, excl_items, bc, c0, std::min<size_t>(cap, n - c0)));
-    if (out_frac_bits) *out_frac_bits = sbr_softmax_fbits((uint32_t)m->hp.num_items);
+    for (size_t c0 = 0; c0 < n; c0 += cap)
+        SBRCHK(sessions_beam_chunk_run(st, slots, rep0, excl_ptr, excl_items, bc, set, c0, std::min<size_t>(cap, n - c0)));
+    if (out_frac_bits) *out_frac_bits = sbr_softmax_fbits((uint32_t)m->hp.num_items); /* the model's, with or without a set */
     return SBR_OK;
+}
+
+}  // namespace
+
+sbr_status sbr_sessions_beam_search(sbr_sessions* st, const uint32_t* slots, uint64_t n, const struct sbr_beam_args* args,
+                                    const uint64_t* excl_ptr, const uint32_t* excl_items, const uint32_t* any_of, const uint32_t* none_of,
+                                    uint32_t* out_items, float* out_scores, float* out_step_lp, float* out_cum, uint32_t* out_lengths,
+                                    uint32_t* out_beams, float* out_shift, uint64_t* out_mass, uint32_t* out_frac_bits) {
+    return beam_call(st, nullptr, slots, n, args, excl_ptr, excl_items, any_of, none_of, out_items, out_scores, out_step_lp, out_cum, out_lengths,
+                     out_beams, out_shift, out_mass, out_frac_bits);
 }
 
 /* ---------------------------------------------------------------------------------------------
@@ -6744,6 +6807,32 @@ sbr_status sbr_item_set_recommend_capped(sbr_item_set* set, const struct sbr_sca
     ScanVariant v;
     v.cp = &cp;
     return item_set_scan(set, rows, num_rows, pool, out_items, out_scores, v);
+}
+
+namespace {
+
+/* the store descriptor of an item set's rollout or beam search: a store of the set's model, no other source, flags 0 (include_seen is
+ * the args' flag); the rest is the plain call's to check */
+bool set_store_rows(const sbr_item_set* set, const sbr_scan_rows* r) {
+    return set && r && r->store && !r->user_ptr && !r->item_ids && !r->reps && r->flags == 0 && r->store->m == set->m;
+}
+
+}  // namespace
+
+sbr_status sbr_item_set_rollout(sbr_item_set* set, const struct sbr_scan_rows* rows, uint64_t num_rows, const struct sbr_rollout_args* args,
+                                uint32_t* out_items, float* out_scores, float* out_keys, uint32_t* out_lengths, float* out_shift,
+                                uint64_t* out_mass, uint32_t* out_frac_bits, float* out_h, float* out_c) {
+    if (!set_store_rows(set, rows)) return SBR_ERR_INVALID_ARGUMENT;
+    return rollout_call(rows->store, set, rows->slots, num_rows, args, rows->excl_ptr, rows->excl_items, rows->any_of, rows->none_of, out_items,
+                        out_scores, out_keys, out_lengths, out_shift, out_mass, out_frac_bits, out_h, out_c);
+}
+
+sbr_status sbr_item_set_beam_search(sbr_item_set* set, const struct sbr_scan_rows* rows, uint64_t num_rows, const struct sbr_beam_args* args,
+                                    uint32_t* out_items, float* out_scores, float* out_step_lp, float* out_cum, uint32_t* out_lengths,
+                                    uint32_t* out_beams, float* out_shift, uint64_t* out_mass, uint32_t* out_frac_bits) {
+    if (!set_store_rows(set, rows)) return SBR_ERR_INVALID_ARGUMENT;
+    return beam_call(rows->store, set, rows->slots, num_rows, args, rows->excl_ptr, rows->excl_items, rows->any_of, rows->none_of, out_items,
+                     out_scores, out_step_lp, out_cum, out_lengths, out_beams, out_shift, out_mass, out_frac_bits);
 }
 
 sbr_status sbr_sessions_score_candidates(sbr_sessions* st, const uint32_t* slots, uint64_t n, const uint64_t* cand_ptr,

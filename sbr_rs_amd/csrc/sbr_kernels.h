@@ -564,7 +564,8 @@ int launch_session_replay_feed(const SeenView& sn, const uint32_t* slot, const u
  *   `slack` entries of 0xFFFFFFFF.
  * launch_rollout_advance: step j's picks p (stride 1, the scan's outputs; keys / shift / mass null where o's are) into column j of
  *   o [n][steps], the rows' ends, the feed, and — ins_ptr non-null — each live pick into its row's segment [ins_ptr[i],
- *   ins_ptr[i + 1]) of excl, which must end in 0xFFFFFFFF.
+ *   ins_ptr[i + 1]) of excl, which must end in 0xFFFFFFFF.  With p.ids (an item set's scan) the segments hold positions of the set
+ *   and the outputs and the feed catalogue ids (RolloutPick).
  * launch_rollout_step: one cell step of every row by its feed item (LSTM: from the store through `slot` at j == 0; an ended row keeps
  *   its state).  Each returns the launches it queued; launch_rollout_step -1 where there is no kernel for m.d. */
 struct RolloutRows {
@@ -580,6 +581,10 @@ struct RolloutPick {
     const uint32_t* items;
     const float *scores, *keys, *shift;
     const unsigned long long* mass;
+    const uint32_t* ids = nullptr; /* an item set's scan: its num_ids ascending catalogue ids; the segments hold positions, the outputs
+                                      and the feed ids.  items are positions, or (is_id: the sampled launch maps them) already ids */
+    uint32_t num_ids = 0;
+    bool is_id = false;
 };
 struct RolloutOut {
     uint32_t* items;
@@ -625,6 +630,7 @@ struct BeamScan {
     const unsigned long long* mass;
     float inv_t;
     uint32_t fbits;
+    const uint32_t* ids = nullptr; /* an item set's scan: items are positions of its ascending ids; feed and the record take ids[item] */
 };
 struct BeamRecord {
     uint32_t *parent, *item;

@@ -645,11 +645,17 @@ __global__ __launch_bounds__(256) void rollout_segments_kernel(const uint64_t* _
 //     the wave; the tail from there moves up by one entry, 64 at a time from the top, each round's loads complete (its stores carry
 //     the loaded values) before its stores and so before the next round's stores, which land below it; then lane 0 writes the pick.
 //     O(segment) per row and step.
+// Within an item set (ids non-null: its num_ids sorted catalogue ids, the scan ran over its sub-table) the segments hold positions of
+// the set while the outputs and the feed are catalogue ids: a pick that arrives as a position (pick_is_id == 0: the plain scan's) leaves
+// as ids[pick] and is inserted as itself; one that arrives as a catalogue id (the sampled launch maps its rows) leaves as itself and is
+// inserted at its position, found by the wave's binary search over ids (every lane the same probes: one load per probe).  An ended
+// row's stand-in feed is then ids[0], so no row outside the set is read.
 // No atomics; rows are independent and a row is one wave's.
 __global__ __launch_bounds__(256) void rollout_advance_kernel(int n, uint32_t steps, uint32_t j, const uint32_t* __restrict__ pick_items,
                                                               const float* __restrict__ pick_scores, const float* __restrict__ pick_keys,
                                                               const float* __restrict__ pick_shift,
                                                               const unsigned long long* __restrict__ pick_mass,
+                                                              const uint32_t* __restrict__ ids, uint32_t num_ids, uint32_t pick_is_id,
                                                               const uint64_t* __restrict__ ins_ptr, uint32_t* excl, uint32_t* ended,
                                                               uint32_t* __restrict__ lengths, uint32_t* __restrict__ feed,
                                                               uint32_t* __restrict__ count, uint32_t* __restrict__ out_items,
@@ -660,18 +666,31 @@ __global__ __launch_bounds__(256) void rollout_advance_kernel(int n, uint32_t st
     if (i >= n) return;
     const uint32_t lane = threadIdx.x & 63u;
     const bool was = ended[i] != 0u;
-    const uint32_t v = was ? NONE : pick_items[i];
-    const bool live = v != NONE;
+    const uint32_t picked = was ? NONE : pick_items[i];
+    const bool live = picked != NONE;
+    uint32_t id = picked, v = picked; /* what leaves and feeds; what the segment takes */
+    if (ids && live) {
+        if (pick_is_id) {
+            uint32_t lo = 0, hi = num_ids;
+            while (lo < hi) {
+                const uint32_t mid = (lo + hi) >> 1;
+                if (ids[mid] < picked) lo = mid + 1; else hi = mid;
+            }
+            v = lo;
+        } else {
+            id = ids[picked];
+        }
+    }
     if (lane == 0) {
         const size_t o = (size_t)i * steps + j;
-        out_items[o] = v;
+        out_items[o] = id;
         out_scores[o] = live ? pick_scores[i] : -INFINITY;
         if (out_keys) out_keys[o] = live ? pick_keys[i] : -INFINITY;
         if (out_shift) {
             out_shift[o] = live ? pick_shift[i] : -INFINITY;
             out_mass[o] = live ? pick_mass[i] : 0ull;
         }
-        feed[i] = live ? v : 0u;
+        feed[i] = live ? id : ids ? ids[0] : 0u;
         count[i] = live ? 1u : 0u;
         if (!live && !was) {
             ended[i] = 1u;
@@ -752,7 +771,11 @@ __global__ __launch_bounds__(256) void beam_begin_kernel(int n, uint32_t steps, 
 // slot[i] at j == 0, else i W + parent), src_row (the segment the child's is copied from: i at j == 0, else i W + parent), feed /
 // count (the cell step's item; count 0 on ended rows), pick (merged into the segment; 0xFFFFFFFF: nothing).  A row's parents are
 // read into LDS before any of its children is written, so alive / cum are updated in place.
+// Within an item set (ids non-null: its sorted catalogue ids, the scan ran over its sub-table) the scan's items are positions of the
+// set: pick stays the position (the segments are positions), feed and the record's item become ids[position], and the stand-in feed
+// of a carried beam is ids[0], so no row outside the set is read.
 __global__ __launch_bounds__(256) void beam_select_kernel(int n, uint32_t w, uint32_t j, const uint32_t* __restrict__ slot,
+                                                          const uint32_t* __restrict__ ids,
                                                           const uint32_t* __restrict__ scan_items, const float* __restrict__ scan_scores,
                                                           const float* __restrict__ shift, const unsigned long long* __restrict__ mass,
                                                           float inv_t, uint32_t fbits, uint32_t* row_ended, uint32_t* __restrict__ lengths,
@@ -834,7 +857,7 @@ __global__ __launch_bounds__(256) void beam_select_kernel(int n, uint32_t w, uin
         }
         in_row[b] = j == 0 ? slot[i] : (uint32_t)b;
         src_row[b] = j == 0 ? (uint32_t)i : (uint32_t)b;
-        feed[b] = 0u;
+        feed[b] = ids ? ids[0] : 0u;
         count[b] = 0u;
         pick[b] = NONE;
         ended[b] = 1u;
@@ -850,9 +873,10 @@ __global__ __launch_bounds__(256) void beam_select_kernel(int n, uint32_t w, uin
     const size_t srow = j == 0 ? (size_t)i : b0 + p;
     const uint32_t item = scan_items[srow * w + q];
     const uint32_t it = item == NONE ? 0u : item;
+    const uint32_t id = ids ? ids[it] : it; /* a position of the set < its size: the scan offered it, or 0 */
     in_row[b] = j == 0 ? slot[i] : (uint32_t)(b0 + p);
     src_row[b] = j == 0 ? (uint32_t)i : (uint32_t)(b0 + p);
-    feed[b] = it;
+    feed[b] = id;
     count[b] = 1u;
     pick[b] = it;
     ended[b] = 0u;
@@ -860,7 +884,7 @@ __global__ __launch_bounds__(256) void beam_select_kernel(int n, uint32_t w, uin
     cum[b] = live ? o_cum[o] : -INFINITY;
     const size_t r = (size_t)j * n * w + b;
     rec_parent[r] = live ? p : 0u;
-    rec_item[r] = live ? item : NONE;
+    rec_item[r] = live ? id : NONE;
     rec_score[r] = live ? scan_scores[srow * w + q] : -INFINITY;
     rec_lp[r] = live ? o_lp[o] : -INFINITY;
     rec_cum[r] = live ? o_cum[o] : -INFINITY;
@@ -1065,7 +1089,7 @@ int launch_rollout_advance(const RolloutRows& r, uint32_t j, const RolloutPick& 
                            hipStream_t s) {
     if (r.n <= 0) return 0;
     hipLaunchKernelGGL(rollout_advance_kernel, dim3((unsigned)((r.n + 3) / 4)), dim3(256), 0, s, r.n, r.steps, j, p.items, p.scores, p.keys, p.shift,
-                       p.mass, ins_ptr, excl, r.ended, r.lengths, r.feed, r.count, o.items, o.scores, o.keys, o.shift, o.mass);
+                       p.mass, p.ids, p.num_ids, p.is_id ? 1u : 0u, ins_ptr, excl, r.ended, r.lengths, r.feed, r.count, o.items, o.scores, o.keys, o.shift, o.mass);
     return 1;
 }
 
@@ -1129,7 +1153,7 @@ int launch_beam_begin(const BeamRows& r, hipStream_t s) {
 
 int launch_beam_select(const BeamRows& r, uint32_t j, const BeamScan& sc, const BeamRecord& rec, hipStream_t s) {
     if (r.n <= 0) return 0;
-    hipLaunchKernelGGL(beam_select_kernel, dim3((unsigned)r.n), dim3(256), 0, s, r.n, r.w, j, r.slot, sc.items, sc.scores, sc.shift, sc.mass, sc.inv_t,
+    hipLaunchKernelGGL(beam_select_kernel, dim3((unsigned)r.n), dim3(256), 0, s, r.n, r.w, j, r.slot, sc.ids, sc.items, sc.scores, sc.shift, sc.mass, sc.inv_t,
                        sc.fbits, r.row_ended, r.lengths, r.beams, r.alive, r.cum, r.ended, r.in_row, r.src_row, r.feed, r.count, r.pick,
                        rec.parent, rec.item, rec.score, rec.lp, rec.cum, rec.shift, rec.mass);
     return 1;

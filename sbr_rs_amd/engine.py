@@ -1987,6 +1987,13 @@ class Sessions:
         left ends: padding from there on, ``lengths[i]`` its real steps.  ``log_prob``: each step's exact partition at
         ``temperature`` and the pick's log-probability under it, in either mode.  ``final_state``: the states after all picks.
         The insert of a pick into its row's exclusion list costs O(list) per step; steps <= 1 024."""
+        return self._rollout(None, slots, steps, mode, temperature, seed, streams, exclude, any_of, none_of, include_seen, allow_repeats,
+                             log_prob, final_state)
+
+    def _rollout(self, item_set, slots, steps, mode, temperature, seed, streams, exclude, any_of, none_of, include_seen, allow_repeats,
+                 log_prob, final_state) -> Rollout:
+        """``rollout`` of this store, or within ``item_set`` (sbr_item_set_rollout; None: the catalogue).  Every argument is
+        checked here before the library is called."""
         from ._abi import ROLLOUT_ALLOW_REPEATS, ROLLOUT_INCLUDE_SEEN, ROLLOUT_SAMPLE, SbrRolloutArgs
 
         steps, sample = _rollout_args(steps, mode, temperature)
@@ -2014,9 +2021,13 @@ class Sessions:
         def opt(a):
             return None if a is None else _ptr(a)
 
-        _check(self._L.sbr_sessions_rollout(self._h, _ptr(sl), n, C.byref(ra), opt(ep), opt(ei), None if masks is None else _ptr(masks[0]),
-                                            None if masks is None else _ptr(masks[1]), _ptr(items), _ptr(scores), opt(keys), _ptr(lengths),
-                                            opt(shift), opt(mass), C.byref(fb) if log_prob else None, opt(h), opt(c)))
+        outs = (_ptr(items), _ptr(scores), opt(keys), _ptr(lengths), opt(shift), opt(mass), C.byref(fb) if log_prob else None, opt(h), opt(c))
+        if item_set is None:
+            _check(self._L.sbr_sessions_rollout(self._h, _ptr(sl), n, C.byref(ra), opt(ep), opt(ei), None if masks is None else _ptr(masks[0]),
+                                                None if masks is None else _ptr(masks[1]), *outs))
+        else:
+            src = self._set_rows(sl, masks, ep, ei)
+            item_set._check(self._L.sbr_item_set_rollout(item_set._h, C.byref(src.desc), n, C.byref(ra), *outs))
         lengths = lengths[:n]
         out = Rollout(items, scores, lengths, keys=keys)
         if log_prob:  # one partition row per (row, step): the host's one statement of the weights, no second exponential
@@ -2038,6 +2049,12 @@ class Sessions:
         ``Partition.log_prob``, which is -inf where w == 0), and the row keeps the ``width`` best offers by (cumulative lp
         descending, parent beam ascending, offer position ascending).  ``partitions``: each (beam, step)'s exact shift and mass too.
         With width 1 the items are greedy ``rollout``'s."""
+        return self._beam_search(None, slots, steps, width, temperature, exclude, any_of, none_of, include_seen, allow_repeats, partitions)
+
+    def _beam_search(self, item_set, slots, steps, width, temperature, exclude, any_of, none_of, include_seen, allow_repeats,
+                     partitions) -> Beams:
+        """``beam_search`` of this store, or within ``item_set`` (sbr_item_set_beam_search; None: the catalogue).  Every argument
+        is checked here before the library is called."""
         from ._abi import ROLLOUT_ALLOW_REPEATS, ROLLOUT_INCLUDE_SEEN, SbrBeamArgs
 
         steps, width = _beam_args(steps, width, temperature)
@@ -2065,10 +2082,20 @@ class Sessions:
         def opt(a):
             return None if a is None else _ptr(a)
 
-        _check(self._L.sbr_sessions_beam_search(self._h, _ptr(sl), n, C.byref(ba), opt(ep), opt(ei), None if masks is None else _ptr(masks[0]),
-                                                None if masks is None else _ptr(masks[1]), _ptr(items), _ptr(scores), _ptr(step_lp), _ptr(cum),
-                                                _ptr(lengths), _ptr(beams), opt(shift), opt(mass), C.byref(fb) if partitions else None))
+        outs = (_ptr(items), _ptr(scores), _ptr(step_lp), _ptr(cum), _ptr(lengths), _ptr(beams), opt(shift), opt(mass),
+                C.byref(fb) if partitions else None)
+        if item_set is None:
+            _check(self._L.sbr_sessions_beam_search(self._h, _ptr(sl), n, C.byref(ba), opt(ep), opt(ei), None if masks is None else _ptr(masks[0]),
+                                                    None if masks is None else _ptr(masks[1]), *outs))
+        else:
+            src = self._set_rows(sl, masks, ep, ei)
+            item_set._check(self._L.sbr_item_set_beam_search(item_set._h, C.byref(src.desc), n, C.byref(ba), *outs))
         return Beams(items, scores, step_lp, cum, lengths[:n], beams[:n], shift=shift, mass=mass, frac_bits=fb.value if partitions else None)
+
+    def _set_rows(self, sl, masks, ep, ei) -> "_ScanRows":
+        """The store descriptor of a rollout or beam search through an item set: flags 0, include_seen goes in the args."""
+        buf = sl if sl.size else np.zeros(1, dtype=np.uint32)
+        return _scan_rows(sl.size, masks, ep, ei, (self, buf), None, store=self._h.value, slots=buf.ctypes.data)
 
     def state(self, slots):
         """Checkpoint of the named slots: (h [n, embedding_dim], c likewise — None for EWMA —, len [n] u64)."""
@@ -2329,6 +2356,47 @@ class ItemSet:
         """``Model.recommend_diverse`` within the set: the pool is the set's ``recommend`` row."""
         return self._diverse(self._hist(user_ptr, item_ids, include_history, any_of, none_of), k, pool, trade_off, metric)
 
+    def _temporary_store(self, histories):
+        """Model.rollout's temporary store: one slot per history, each history's last max_sequence_length items appended."""
+        seqs = [np.asarray(h, dtype=np.uint32).ravel() for h in histories]
+        if not seqs:
+            raise ValueError("histories: at least one")
+        T = int(self.model.hp.max_sequence_length)
+        store = Sessions(self.model, len(seqs))
+        try:
+            slots = np.arange(len(seqs), dtype=np.uint32)
+            store.append(slots, [s[-T:] if s.size > T else s for s in seqs])
+        except BaseException:
+            store.close()
+            raise
+        return store, slots, seqs
+
+    def rollout(self, histories, steps: int, mode: str = "greedy", temperature: float = 1.0, seed: int = 0, streams=None,
+                exclude_history: bool = True, any_of=None, none_of=None, allow_repeats: bool = False, log_prob: bool = False,
+                final_state: bool = False) -> Rollout:
+        """``Model.rollout`` within the set, DEFINED as it is: a temporary store of one slot per history, ``append`` of each
+        history's last max_sequence_length items, and ``on(store).rollout`` of all slots with — ``exclude_history`` — each
+        history's items as ``exclude``."""
+        _rollout_args(steps, mode, temperature)
+        store, slots, seqs = self._temporary_store(histories)
+        try:
+            return self.on(store).rollout(slots, steps, mode=mode, temperature=temperature, seed=seed, streams=streams,
+                                          exclude=seqs if exclude_history else None, any_of=any_of, none_of=none_of,
+                                          allow_repeats=allow_repeats, log_prob=log_prob, final_state=final_state)
+        finally:
+            store.close()
+
+    def beam_search(self, histories, steps: int, width: int = 4, temperature: float = 1.0, exclude_history: bool = True, any_of=None,
+                    none_of=None, allow_repeats: bool = False, partitions: bool = False) -> "Beams":
+        """``Model.beam_search`` within the set, DEFINED as ``rollout``'s histories form is, through ``on(store).beam_search``."""
+        _beam_args(steps, width, temperature)
+        store, slots, seqs = self._temporary_store(histories)
+        try:
+            return self.on(store).beam_search(slots, steps, width=width, temperature=temperature, exclude=seqs if exclude_history else None,
+                                              any_of=any_of, none_of=none_of, allow_repeats=allow_repeats, partitions=partitions)
+        finally:
+            store.close()
+
     # ---- representations ----
     def recommend_reps(self, reps, k: int, exclude=None, any_of=None, none_of=None):
         return self._recommend(self._reps(reps, exclude, any_of, none_of), k)
@@ -2403,6 +2471,20 @@ class ItemSetSessions:
 
     def nth_score(self, slots, n, exclude=None, any_of=None, none_of=None, include_seen: bool = False):
         return self.item_set._above(self._src(slots, exclude, any_of, none_of, include_seen), None, None, "id", True, n)
+
+    def rollout(self, slots, steps: int, mode: str = "greedy", temperature: float = 1.0, seed: int = 0, streams=None, exclude=None,
+                any_of=None, none_of=None, include_seen: bool = False, allow_repeats: bool = False, log_prob: bool = False,
+                final_state: bool = False) -> Rollout:
+        """``Sessions.rollout`` within the set (sbr_item_set_rollout): what the store's own call returns with every item outside
+        the set added to each row's ``exclude``, bit for bit; ``frac_bits`` is the model's."""
+        return self.store._rollout(self.item_set, slots, steps, mode, temperature, seed, streams, exclude, any_of, none_of, include_seen,
+                                   allow_repeats, log_prob, final_state)
+
+    def beam_search(self, slots, steps: int, width: int = 4, temperature: float = 1.0, exclude=None, any_of=None, none_of=None,
+                    include_seen: bool = False, allow_repeats: bool = False, partitions: bool = False) -> Beams:
+        """``Sessions.beam_search`` within the set (sbr_item_set_beam_search), under ``rollout``'s rule."""
+        return self.store._beam_search(self.item_set, slots, steps, width, temperature, exclude, any_of, none_of, include_seen,
+                                       allow_repeats, partitions)
 
 
 def release_cached_memory() -> None:

@@ -608,6 +608,20 @@ class ItemSetView:
         return self.set.recommend_diverse(up, it, k, pool, trade_off=trade_off, metric=metric, include_history=not exclude_history,
                                           any_of=any_of, none_of=none_of)
 
+    def rollout(self, histories, steps: int, mode: str = "greedy", temperature: float = 1.0, seed: int = 0, streams=None,
+                exclude_history: bool = True, any_of=None, none_of=None, allow_repeats: bool = False, log_prob: bool = False,
+                final_state: bool = False):
+        """The model's ``rollout`` within the set (``engine.ItemSet.rollout``)."""
+        return self.set.rollout(histories, steps, mode=mode, temperature=temperature, seed=seed, streams=streams,
+                                exclude_history=exclude_history, any_of=any_of, none_of=none_of, allow_repeats=allow_repeats,
+                                log_prob=log_prob, final_state=final_state)
+
+    def beam_search(self, histories, steps: int, width: int = 4, temperature: float = 1.0, exclude_history: bool = True, any_of=None,
+                    none_of=None, allow_repeats: bool = False, partitions: bool = False):
+        """The model's ``beam_search`` within the set (``engine.ItemSet.beam_search``)."""
+        return self.set.beam_search(histories, steps, width=width, temperature=temperature, exclude_history=exclude_history,
+                                    any_of=any_of, none_of=none_of, allow_repeats=allow_repeats, partitions=partitions)
+
 
 class ImplicitLSTMModel(_ImplicitSequenceModel):
     """An LSTM-based sequence model for implicit feedback (lstm.rs:386-416)."""
