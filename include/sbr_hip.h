@@ -1250,6 +1250,48 @@ sbr_status sbr_selftest_stream_delay(uint32_t delay_us, int32_t with_join, float
 sbr_status sbr_selftest_scratch(uint32_t kind, uint64_t bytes, void* out_host);
 sbr_status sbr_selftest_arena(sbr_model* m, uint64_t bytes, void* out_host);
 
+/* Guarded-scratch test hook (tests/test_guarded_scratch_gpu.py): where the kernels WRITE.  The cache's blocks and
+ * the arena's takes lie back to back, rounded to 256 bytes, a cache hit up to twice the request: a store past the end of its
+ * buffer faults nowhere.  The environment variable
+ *     SBR_TEST_GUARD=<KiB>     1..1048576; unset, 0 or malformed: off
+ * read each time memory is handed out, puts a band of KiB x 1024 guard bytes (0xA5) in front of every block of the cache
+ * (device and pinned host; hit, fresh, or past the cache's 64 MiB) and behind it — from the first byte past the REQUESTED size,
+ * through the rounding and the unused part of a cache hit — and likewise behind every take of a carve of the serving arena and in
+ * front of its first take.  With SBR_TEST_POISON as well, the poison byte fills the payload and the guard byte the bands.  The
+ * bands are compared with the guard byte when a block is given back, at the head of the model's next carve and when the model
+ * releases its arena; a changed band is a count and a record below (and is filled again), never an abort.  Reads past a buffer,
+ * a stride that jumps a whole band, stores into another live buffer's payload, the pages of a partitioned table and exportable
+ * lists, and the caller's own output arrays are not seen.
+ * sbr_test_guard_report: synchronises the device, checks every live block of the cache and (m non-null) the current carve of m's
+ * arena, adds what the checks above found since the last report, and resets the counters.
+ * sbr_selftest_guard: the method's own check — a device block (where = SBR_GUARD_DEVICE_BLOCK), a pinned block, three arena takes
+ * of m, or a device block past the cache's 64 MiB (SBR_GUARD_BIG_BLOCK; reported as a device block), each of 4 196 bytes (the big
+ * block: 64 MiB more); the library sets ONE byte with hipMemset / memset — side > 0: the first byte past the request (of the
+ * middle take), side < 0: the last byte before the block (before the first take) — and out[0] is the report of that alone;
+ * out[1] the same on the re-used allocation: the cache hit, the second carve.  Pending findings of other checks are kept for the
+ * next sbr_test_guard_report.  Hook off: nothing is written and both reports are zero.  m is needed for the arena only. */
+enum {
+    SBR_GUARD_NONE = 0,
+    SBR_GUARD_DEVICE_BLOCK = 1,
+    SBR_GUARD_PINNED_BLOCK = 2,
+    SBR_GUARD_ARENA_TAKE = 3,
+    SBR_GUARD_BIG_BLOCK = 4
+};
+typedef struct sbr_guard_report {
+    uint64_t blocks;     /* cache blocks checked */
+    uint64_t takes;      /* arena takes checked */
+    uint64_t bytes;      /* guard bytes compared */
+    uint64_t violations; /* bands with at least one changed byte */
+    /* the first violated band: */
+    uint64_t where;      /* SBR_GUARD_* */
+    uint64_t ordinal;    /* of the take within its carve; of the block among the guarded blocks handed out since the last report */
+    uint64_t requested;  /* bytes the owner asked for */
+    int64_t offset;      /* of the first changed byte: +1 = the first byte past the request, -1 = the last byte before its start */
+    uint64_t changed;    /* changed bytes in that band */
+} sbr_guard_report;
+sbr_status sbr_test_guard_report(sbr_model* m, sbr_guard_report* out);
+sbr_status sbr_selftest_guard(sbr_model* m, uint32_t where, int32_t side, sbr_guard_report out[2]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -158,6 +158,44 @@ class SbrScanRows(C.Structure):
     ]
 
 
+GUARD_NONE, GUARD_DEVICE_BLOCK, GUARD_PINNED_BLOCK, GUARD_ARENA_TAKE, GUARD_BIG_BLOCK = range(5)  # SBR_GUARD_*
+GUARD_WHERE = ("none", "device block", "pinned block", "arena take")
+
+
+class SbrGuardReport(C.Structure):
+    """struct sbr_guard_report of sbr_test_guard_report / sbr_selftest_guard (SBR_TEST_GUARD)"""
+    _fields_ = [
+        ("blocks", C.c_uint64),
+        ("takes", C.c_uint64),
+        ("bytes", C.c_uint64),
+        ("violations", C.c_uint64),
+        ("where", C.c_uint64),
+        ("ordinal", C.c_uint64),
+        ("requested", C.c_uint64),
+        ("offset", C.c_int64),
+        ("changed", C.c_uint64),
+    ]
+
+    @property
+    def checked(self) -> int:
+        """blocks and takes checked"""
+        return int(self.blocks + self.takes)
+
+    def first(self):
+        """(where, ordinal, requested, offset, changed) of the first violated band, or None"""
+        if not self.violations:
+            return None
+        return int(self.where), int(self.ordinal), int(self.requested), int(self.offset), int(self.changed)
+
+    def __str__(self):
+        s = f"{self.blocks} blocks + {self.takes} takes checked ({self.bytes} guard bytes): {self.violations} violated"
+        if self.violations:
+            side = f"{self.offset} bytes past its end" if self.offset > 0 else f"{-self.offset} bytes before its start"
+            s += (f"; first: {GUARD_WHERE[self.where]} #{self.ordinal} of {self.requested} requested bytes, first changed byte {side}, "
+                  f"{self.changed} bytes changed")
+        return s
+
+
 def storage_dim(embedding_dim: int) -> int:
     """Width the engine stores an embedding_dim in (16 / 32 / 64 / 128 / 256; the extra columns are zero and stay
     zero — sbr_engine.hip `storage_dim`).  Parameters, user representations and predictions use embedding_dim;

@@ -140,6 +140,8 @@ def load():
         "sbr_selftest_stream_delay": [C.c_uint32, C.c_int32, fp],
         "sbr_selftest_scratch": [C.c_uint32, C.c_uint64, vp],
         "sbr_selftest_arena": [vp, C.c_uint64, vp],
+        "sbr_test_guard_report": [vp, vp],
+        "sbr_selftest_guard": [vp, C.c_uint32, C.c_int32, vp],
         "sbr_sessions_create": [vp, C.c_uint64, C.POINTER(vp)],
         "sbr_sessions_create_seen": [vp, C.c_uint64, C.c_uint32, C.POINTER(vp)],
         "sbr_sessions_seen_capacity": [vp, u32p],
@@ -265,6 +267,7 @@ DECLARED_SYMBOLS = [
     "sbr_recommend", "sbr_recommend_reps", "sbr_rank_targets", "sbr_rank_targets_reps", "sbr_similar_items",
     "sbr_user_representations", "sbr_score_candidates", "sbr_score_candidates_reps", "sbr_recommend_among", "sbr_recommend_among_reps",
     "sbr_test_delays_queued", "sbr_selftest_stream_delay", "sbr_selftest_scratch", "sbr_selftest_arena",
+    "sbr_test_guard_report", "sbr_selftest_guard",
     "sbr_sessions_create", "sbr_sessions_destroy", "sbr_sessions_capacity", "sbr_sessions_reset", "sbr_sessions_reset_all",
     "sbr_sessions_append", "sbr_sessions_lengths", "sbr_sessions_representations", "sbr_sessions_get_state", "sbr_sessions_set_state",
     "sbr_sessions_recommend", "sbr_sessions_score_candidates",

@@ -62,38 +62,107 @@ int test_poison_byte() {
     return (*after == 0 && v >= 1 && v <= 255) ? (int)v : 0;
 }
 
+/* The guarded-scratch test hook: SBR_TEST_GUARD=<KiB>, read each time memory is handed out.  Every block of
+ * ScratchCache::get and every take of the serving arena gets a band of G = KiB x 1024 bytes of kGuardByte behind it — from the first
+ * byte past the REQUESTED size, through the alignment padding and the unused part of a cache hit — and one in front (of a block;
+ * of the first take of a carve).  The bands are compared with kGuardByte when a block is given back, at the head of the next carve
+ * and on sbr_test_guard_report: a store past its buffer is a count and a record, never an abort
+ * (tests/test_guarded_scratch_gpu.py).  0 = off (unset, 0 or malformed): one getenv, nothing else. */
+constexpr int kGuardByte = 0xA5; /* none of the poison patterns 0xFF / 0x7F / 0x80, and no zero */
+size_t test_guard_bytes() {
+    const char* e = std::getenv("SBR_TEST_GUARD");
+    if (!e || !*e) return 0;
+    char* after = nullptr;
+    const unsigned long v = std::strtoul(e, &after, 10);
+    return (*after == 0 && v >= 1 && v <= (1ul << 20)) ? (size_t)v << 10 : 0;
+}
+
+/* What the guard checks found since sbr_test_guard_report last read them (process-wide), and the staging buffer of a check. */
+struct GuardState {
+    std::mutex mu;
+    sbr_guard_report r = {};
+    uint64_t allocs = 0; /* guarded blocks handed out since the last report: the ordinal of the next one */
+    std::vector<uint8_t> staging;
+};
+GuardState& guard_state() {
+    static GuardState* g = new GuardState;
+    return *g;
+}
+
+/* One band [band, band + n) — pinned host memory, or device memory whose streams are drained — against kGuardByte.  offset0: the
+ * position of the band's first byte as the report states it (+1: the first byte past the request; -n: n bytes before its start).
+ * A changed band is counted once: it is filled again. */
+void guard_check_band(uint8_t* band, size_t n, bool host, uint64_t where, uint64_t ordinal, uint64_t requested, int64_t offset0) {
+    if (!n) return;
+    GuardState& gs = guard_state();
+    std::lock_guard<std::mutex> g(gs.mu);
+    const uint8_t* src = band;
+    if (!host) {
+        if (gs.staging.size() < n) gs.staging.resize(n);
+        if (hipMemcpy(gs.staging.data(), band, n, hipMemcpyDeviceToHost) != hipSuccess) return;
+        src = gs.staging.data();
+    }
+    gs.r.bytes += n;
+    uint64_t word;
+    std::memset(&word, kGuardByte, 8);
+    size_t first = n, changed = 0, i = 0;
+    while (i < n) {
+        uint64_t w;
+        if (i + 8 <= n && (std::memcpy(&w, src + i, 8), w == word)) { i += 8; continue; }
+        const size_t end = std::min(n, i + 8);
+        for (; i < end; ++i)
+            if (src[i] != (uint8_t)kGuardByte) { if (first == n) first = i; ++changed; }
+    }
+    if (!changed) return;
+    gs.r.violations += 1;
+    if (gs.r.where == SBR_GUARD_NONE) {
+        gs.r.where = where; gs.r.ordinal = ordinal; gs.r.requested = requested;
+        gs.r.offset = offset0 + (int64_t)first; gs.r.changed = changed;
+    }
+    if (host) std::memset(band, kGuardByte, n);
+    else if (hipMemset(band, kGuardByte, n) == hipSuccess) (void)hipDeviceSynchronize();
+}
+
 /* Scratch of a fit call recycled across calls.  The reference's own bench re-fits one model in a loop (benches/benchmark.rs:40-42:
  * 10 000 interactions, three epochs per call): ~40 hipMalloc + 10 hipHostMalloc at sbr_fit_begin and as many frees at the end
  * cost 4-18 ms per call there — more than the call's kernels.  Blocks up to 64 MiB go back to this process-wide cache (768 MiB at
  * most, per kind) instead of the driver and are handed out again to requests of at most twice... the same size class; anything
  * larger takes the driver's path as before.  A block is cached only after the streams that used it were synchronised
- * (sbr_fit_plan_destroy, sbr_model_destroy), and nothing relies on fresh memory being zero.  sbr_release_cached_memory() empties it. */
+ * (sbr_fit_plan_destroy, sbr_model_destroy), and nothing relies on fresh memory being zero.  sbr_release_cached_memory() empties it.
+ * Under SBR_TEST_GUARD a block is allocated with `guard` bytes in front of p and behind p + bytes, is handed out only to requests
+ * made under the same guard size, and is `live` whatever its size, so that put finds its bands. */
 struct ScratchCache {
     static constexpr size_t kMaxBlock = 64ull << 20, kMaxTotal = 768ull << 20;
-    struct Blk { void* p; size_t bytes; int device; bool host; };
+    struct Blk { void* p; size_t bytes; int device; bool host; size_t guard = 0, req = 0; uint64_t ordinal = 0; };
     std::mutex mu;
     std::vector<Blk> idle;
     std::unordered_map<void*, Blk> live;
     size_t cached[2] = {0, 0}; /* device, pinned host */
     static bool enabled() { return true; }
     hipError_t get(void** out, size_t bytes, bool host) {
+        const size_t guard = test_guard_bytes();
         size_t stored = 0;
-        const hipError_t e = get_block(out, bytes, host, &stored);
+        const hipError_t e = get_block(out, bytes, host, &stored, guard);
         if (e != hipSuccess) return e;
-        if (const int poison = test_poison_byte()) {
-            if (host) {
-                std::memset(*out, poison, stored);
-            } else { /* the model's streams are non-blocking: a null-stream memset is ordered against nothing without the sync */
-                hipError_t pe = hipMemset(*out, poison, stored);
-                if (pe == hipSuccess) pe = hipDeviceSynchronize();
-                if (pe != hipSuccess) { put(*out, host); *out = nullptr; return pe; }
-            }
+        const int poison = test_poison_byte();
+        if (!poison && !guard) return hipSuccess;
+        uint8_t* p = static_cast<uint8_t*>(*out);
+        if (host) {
+            if (poison) std::memset(p, poison, stored);
+            if (guard) { std::memset(p - guard, kGuardByte, guard); std::memset(p + bytes, kGuardByte, stored - bytes + guard); }
+        } else { /* the model's streams are non-blocking: a null-stream memset is ordered against nothing without the sync */
+            hipError_t pe = poison ? hipMemset(p, poison, stored) : hipSuccess;
+            if (guard && pe == hipSuccess) pe = hipMemset(p - guard, kGuardByte, guard);
+            if (guard && pe == hipSuccess) pe = hipMemset(p + bytes, kGuardByte, stored - bytes + guard);
+            if (pe == hipSuccess) pe = hipDeviceSynchronize();
+            if (pe != hipSuccess) { put(*out, host); *out = nullptr; return pe; }
         }
         return hipSuccess;
     }
     /* *stored = the size of the block handed out: a cache hit may be up to twice the request */
-    hipError_t get_block(void** out, size_t bytes, bool host, size_t* stored) {
+    hipError_t get_block(void** out, size_t bytes, bool host, size_t* stored, size_t guard) {
         *out = nullptr;
+        const size_t req = bytes;
         bytes = (bytes + 255) & ~(size_t)255;
         int device = 0;
         if (!host) (void)hipGetDevice(&device);
@@ -102,57 +171,97 @@ struct ScratchCache {
             size_t best = idle.size();
             for (size_t i = 0; i < idle.size(); ++i) {
                 const Blk& b = idle[i];
-                if (b.host != host || (!host && b.device != device) || b.bytes < bytes || b.bytes > 2 * bytes + 4096) continue;
+                if (b.host != host || (!host && b.device != device) || b.bytes < bytes || b.bytes > 2 * bytes + 4096 || b.guard != guard) continue;
                 if (best == idle.size() || b.bytes < idle[best].bytes) best = i;
             }
             if (best != idle.size()) {
-                const Blk b = idle[best];
+                Blk b = idle[best];
                 idle[best] = idle.back();
                 idle.pop_back();
                 cached[host] -= b.bytes;
+                if (guard) { b.req = req; b.ordinal = next_ordinal(); }
                 live[b.p] = b;
                 *out = b.p;
                 *stored = b.bytes;
                 return hipSuccess;
             }
         }
-        const hipError_t e = host ? hipHostMalloc(out, bytes, hipHostMallocDefault) : hipMalloc(out, bytes);
+        const size_t total = bytes + 2 * guard;
+        bool retried = false;
+        hipError_t e = host ? hipHostMalloc(out, total, hipHostMallocDefault) : hipMalloc(out, total);
         if (e != hipSuccess) {
             bool have_cached;
             {
                 std::lock_guard<std::mutex> g(mu);
                 have_cached = cached[0] + cached[1] != 0;
             }
-            if (e == hipErrorOutOfMemory && have_cached) { /* give the cache back and try once more */
-                trim();
-                *stored = bytes;
-                return host ? hipHostMalloc(out, bytes, hipHostMallocDefault) : hipMalloc(out, bytes);
-            }
-            return e;
+            if (e != hipErrorOutOfMemory || !have_cached) return e;
+            trim(); /* give the cache back and try once more */
+            retried = true;
+            e = host ? hipHostMalloc(out, total, hipHostMallocDefault) : hipMalloc(out, total);
+            if (e != hipSuccess) return e;
         }
         *stored = bytes;
-        if (enabled() && bytes <= kMaxBlock) {
+        *out = static_cast<uint8_t*>(*out) + guard;
+        if (enabled() && ((bytes <= kMaxBlock && !retried) || guard)) {
             std::lock_guard<std::mutex> g(mu);
-            live[*out] = Blk{*out, bytes, device, host};
+            Blk b{*out, bytes, device, host};
+            if (guard) { b.guard = guard; b.req = req; b.ordinal = next_ordinal(); }
+            live[*out] = b;
         }
         return hipSuccess;
     }
+    static uint64_t next_ordinal() {
+        GuardState& gs = guard_state();
+        std::lock_guard<std::mutex> g(gs.mu);
+        return gs.allocs++;
+    }
+    /* both bands of a live guarded block; the streams that used it are drained */
+    static void check(const Blk& b) {
+        uint8_t* p = static_cast<uint8_t*>(b.p);
+        const uint64_t where = b.host ? SBR_GUARD_PINNED_BLOCK : SBR_GUARD_DEVICE_BLOCK;
+        {
+            GuardState& gs = guard_state();
+            std::lock_guard<std::mutex> g(gs.mu);
+            gs.r.blocks += 1;
+        }
+        guard_check_band(p - b.guard, b.guard, b.host, where, b.ordinal, b.req, -(int64_t)b.guard);
+        guard_check_band(p + b.req, b.bytes - b.req + b.guard, b.host, where, b.ordinal, b.req, 1);
+    }
+    static void release(const Blk& b) {
+        void* raw = static_cast<uint8_t*>(b.p) - b.guard;
+        if (b.host) (void)hipHostFree(raw); else (void)hipFree(raw);
+    }
     void put(void* p, bool host) {
         if (!p) return;
+        Blk b{p, 0, 0, host};
         {
             std::lock_guard<std::mutex> g(mu);
             auto it = live.find(p);
             if (it != live.end()) {
-                const Blk b = it->second;
+                b = it->second;
                 live.erase(it);
-                if (b.host == host && cached[host] + b.bytes <= kMaxTotal) {
-                    idle.push_back(b);
-                    cached[host] += b.bytes;
-                    return;
-                }
             }
         }
-        if (host) (void)hipHostFree(p); else (void)hipFree(p);
+        if (b.guard) check(b);
+        if (b.bytes && b.bytes <= kMaxBlock && b.host == host) {
+            std::lock_guard<std::mutex> g(mu);
+            if (cached[host] + b.bytes <= kMaxTotal) {
+                idle.push_back(b);
+                cached[host] += b.bytes;
+                return;
+            }
+        }
+        b.host = host;
+        release(b);
+    }
+    void check_live() {
+        std::vector<Blk> blocks;
+        {
+            std::lock_guard<std::mutex> g(mu);
+            for (const auto& kv : live) if (kv.second.guard) blocks.push_back(kv.second);
+        }
+        for (const Blk& b : blocks) check(b);
     }
     void trim() {
         std::vector<Blk> drop;
@@ -161,9 +270,7 @@ struct ScratchCache {
             drop.swap(idle);
             cached[0] = cached[1] = 0;
         }
-        for (const Blk& b : drop) {
-            if (b.host) (void)hipHostFree(b.p); else (void)hipFree(b.p);
-        }
+        for (const Blk& b : drop) release(b);
     }
 };
 ScratchCache& scratch_cache() {
@@ -433,9 +540,15 @@ struct DeviceArena {
     size_t cap = 0, used = 0;
     bool measuring = false;
     bool overrun = false; /* a take since the last reserve went past cap (and got null): the call fails */
-    void measure() { used = 0; measuring = true; }
+    /* SBR_TEST_GUARD: `guard` bytes in front of the first take and behind every take's padded end, counted by the measuring pass
+     * like the takes themselves; `takes` = the current carve's, for the checks (carve_arena, check_arena_guards) */
+    struct Take { size_t at, req, band_end; };
+    size_t guard = 0, front = 0;
+    std::vector<Take> takes;
+    void measure(size_t guard_bytes = 0) { guard = guard_bytes; used = guard; measuring = true; }
     sbr_status reserve(size_t need) {
-        used = 0;
+        used = front = guard;
+        takes.clear();
         measuring = overrun = false;
         if (need <= cap) return SBR_OK;
         if (base) (void)hipFree(base);
@@ -448,14 +561,31 @@ struct DeviceArena {
     static size_t padded(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
     template <typename T>
     T* take(size_t count) {
-        const size_t at = used;
-        used += padded((count ? count : 1) * sizeof(T));
+        const size_t at = used, bytes = (count ? count : 1) * sizeof(T);
+        used += padded(bytes) + guard;
         if (measuring) return nullptr;
         if (used > cap) { overrun = true; return nullptr; }
+        if (guard) takes.push_back(Take{at, bytes, used});
         return reinterpret_cast<T*>(base + at);
     }
-    void release() { if (base) (void)hipFree(base); base = nullptr; cap = used = 0; }
+    void release() { if (base) (void)hipFree(base); base = nullptr; cap = used = front = 0; takes.clear(); }
 };
+
+/* SBR_TEST_GUARD: the bands of the arena's current carve against the guard byte; the model's stream is drained.  A carve made
+ * with the hook off has no takes on record: nothing happens. */
+static void check_arena_guards(DeviceArena& ar) {
+    if (ar.takes.empty()) return;
+    {
+        GuardState& gs = guard_state();
+        std::lock_guard<std::mutex> g(gs.mu);
+        gs.r.takes += ar.takes.size();
+    }
+    guard_check_band(ar.base, ar.front, false, SBR_GUARD_ARENA_TAKE, 0, ar.takes[0].req, -(int64_t)ar.front);
+    for (size_t i = 0; i < ar.takes.size(); ++i) {
+        const DeviceArena::Take& t = ar.takes[i];
+        guard_check_band(ar.base + t.at + t.req, t.band_end - (t.at + t.req), false, SBR_GUARD_ARENA_TAKE, i, t.req, 1);
+    }
+}
 
 struct sbr_model {
     sbr_hparams hp;
@@ -1156,6 +1286,7 @@ void sbr_model_destroy(sbr_model* m) {
     dfree(m->item_tags);
     dfree(m->item_groups);
     for (auto& tp : m->pending) { hipEventDestroy(tp.a); hipEventDestroy(tp.b); }
+    check_arena_guards(m->eval_arena);
     m->eval_arena.release();
     if (m->own_stream && m->stream) hipStreamDestroy(m->stream);
     if (m->side) { hipStreamSynchronize(m->side); hipStreamDestroy(m->side); }
@@ -3526,16 +3657,24 @@ using Carve = std::function<void(DeviceArena&)>; /* a run of takes */
  * runs once measuring, the arena is reserved to what that took, and it runs again for real. */
 sbr_status carve_arena(sbr_model* m, const Carve& carve) {
     DeviceArena& ar = m->eval_arena;
-    ar.measure();
+    const size_t guard = test_guard_bytes();
+    ar.measure(guard);
     carve(ar);
     HIPCHK(hipStreamSynchronize(m->stream)); /* nothing of an earlier call may still read the arena */
     const size_t need = ar.used;
+    check_arena_guards(ar); /* SBR_TEST_GUARD: what the last carve's kernels left of its bands (the measuring pass keeps its takes) */
     SBRCHK(ar.reserve(need));
     if (const int poison = test_poison_byte()) { /* what this carve uses, not cap: an earlier call may have grown it to gigabytes */
         HIPCHK(hipMemsetAsync(ar.base, poison, need, m->stream));
-        HIPCHK(hipStreamSynchronize(m->stream)); /* a caller may fill its buffers with blocking copies, which no stream orders */
+        if (!guard) HIPCHK(hipStreamSynchronize(m->stream)); /* a caller may fill its buffers with blocking copies, which no stream orders */
     }
     carve(ar);
+    if (guard && !ar.overrun) { /* behind the poison fill on the same stream: poison in the payload, the guard byte in the bands */
+        HIPCHK(hipMemsetAsync(ar.base, kGuardByte, ar.front, m->stream));
+        for (const DeviceArena::Take& t : ar.takes) HIPCHK(hipMemsetAsync(ar.base + t.at + t.req, kGuardByte, t.band_end - (t.at + t.req), m->stream));
+        HIPCHK(hipStreamSynchronize(m->stream));
+    }
+    if (ar.overrun) ar.takes.clear(); /* no bands were filled */
     return ar.overrun ? SBR_ERR_OUT_OF_MEMORY : SBR_OK;
 }
 
@@ -7380,6 +7519,87 @@ sbr_status sbr_selftest_arena(sbr_model* m, uint64_t bytes, void* out_host) {
         HIPCHK(hipStreamSynchronize(m->stream));
     }
     return SBR_OK;
+}
+
+/* read-and-reset of the guard counters; `put_back` non-null: those become the counters (sbr_selftest_guard hands back what it set aside) */
+static sbr_guard_report guard_counters_exchange(uint64_t* allocs, const sbr_guard_report* put_back) {
+    GuardState& gs = guard_state();
+    std::lock_guard<std::mutex> g(gs.mu);
+    const sbr_guard_report r = gs.r;
+    const uint64_t a = gs.allocs;
+    gs.r = put_back ? *put_back : sbr_guard_report{};
+    gs.allocs = put_back && allocs ? *allocs : 0;
+    if (allocs) *allocs = a;
+    return r;
+}
+
+sbr_status sbr_test_guard_report(sbr_model* m, sbr_guard_report* out) {
+    int nd = 0, current = 0;
+    if (hipGetDeviceCount(&nd) != hipSuccess || nd == 0) return SBR_ERR_NO_DEVICE;
+    if (!out) return SBR_ERR_INVALID_ARGUMENT;
+    HIPCHK(hipGetDevice(&current));
+    for (int dev = 0; dev < nd; ++dev) { /* a live block may belong to any device's streams */
+        HIPCHK(hipSetDevice(dev));
+        HIPCHK(hipDeviceSynchronize());
+    }
+    HIPCHK(hipSetDevice(current));
+    if (m) {
+        std::lock_guard<std::mutex> lock(m->mu);
+        SBRCHK(ensure_device(m));
+        check_arena_guards(m->eval_arena);
+        HIPCHK(hipSetDevice(current));
+    }
+    scratch_cache().check_live();
+    *out = guard_counters_exchange(nullptr, nullptr);
+    return SBR_OK;
+}
+
+/* What the guard can see: one byte, set by the library itself inside its own allocation, on the first and on the re-used one. */
+sbr_status sbr_selftest_guard(sbr_model* m, uint32_t where, int32_t side, sbr_guard_report out[2]) {
+    int nd = 0;
+    if (hipGetDeviceCount(&nd) != hipSuccess || nd == 0) return SBR_ERR_NO_DEVICE;
+    if (where < SBR_GUARD_DEVICE_BLOCK || where > SBR_GUARD_BIG_BLOCK || side == 0 || !out || (where == SBR_GUARD_ARENA_TAKE && !m))
+        return SBR_ERR_INVALID_ARGUMENT;
+    const size_t bytes = 4096 + 100 + (where == SBR_GUARD_BIG_BLOCK ? ScratchCache::kMaxBlock : 0);
+    const uint8_t other = (uint8_t)~kGuardByte;
+    std::unique_lock<std::mutex> lock;
+    if (where == SBR_GUARD_ARENA_TAKE) { /* what the last call's kernels left of the current carve's bands is a real finding: it is kept */
+        lock = std::unique_lock<std::mutex>(m->mu);
+        SBRCHK(enter_reader(m));
+        HIPCHK(hipStreamSynchronize(m->stream));
+        check_arena_guards(m->eval_arena);
+    }
+    uint64_t kept_allocs = 0;
+    const sbr_guard_report kept = guard_counters_exchange(&kept_allocs, nullptr);
+    sbr_status st = SBR_OK;
+    if (where == SBR_GUARD_ARENA_TAKE) {
+        for (int round = 0; round < 2 && st == SBR_OK; ++round) {
+            uint8_t* p[3] = {nullptr, nullptr, nullptr};
+            st = carve_arena(m, [&](DeviceArena& ar) { for (auto& q : p) q = ar.take<uint8_t>(bytes); });
+            (void)guard_counters_exchange(nullptr, nullptr); /* the head of the second carve checked the first one's bands */
+            if (st != SBR_OK) break;
+            if (test_guard_bytes() && hipMemsetAsync(side > 0 ? p[1] + bytes : p[0] - 1, other, 1, m->stream) != hipSuccess) st = SBR_ERR_HIP;
+            if (hipStreamSynchronize(m->stream) != hipSuccess) st = SBR_ERR_HIP;
+            check_arena_guards(m->eval_arena);
+            out[round] = guard_counters_exchange(nullptr, nullptr);
+        }
+    } else {
+        const bool host = where == SBR_GUARD_PINNED_BLOCK;
+        for (int round = 0; round < 2 && st == SBR_OK; ++round) {
+            uint8_t* p = nullptr;
+            if (scratch_cache().get(reinterpret_cast<void**>(&p), bytes, host) != hipSuccess) { st = SBR_ERR_OUT_OF_MEMORY; break; }
+            if (test_guard_bytes()) {
+                uint8_t* at = side > 0 ? p + bytes : p - 1;
+                if (host) *at = other;
+                else if (hipMemset(at, other, 1) != hipSuccess || hipDeviceSynchronize() != hipSuccess) st = SBR_ERR_HIP;
+            }
+            scratch_cache().put(p, host); /* checks the bands before the block is cached (or, past 64 MiB, freed) */
+            out[round] = guard_counters_exchange(nullptr, nullptr);
+        }
+    }
+    uint64_t a = kept_allocs;
+    (void)guard_counters_exchange(&a, &kept);
+    return st;
 }
 
 sbr_status sbr_set_device(int32_t ordinal) {

@@ -8,7 +8,7 @@ import weakref
 import numpy as np
 
 from . import _lib
-from ._abi import NUM_KERNEL_FAMILIES, KernelFamily, SbrHparams, Status, storage_dim
+from ._abi import NUM_KERNEL_FAMILIES, KernelFamily, SbrGuardReport, SbrHparams, Status, storage_dim
 from .errors import EngineError, FittingError, InvalidArgument, PredictionError
 
 
@@ -442,6 +442,22 @@ def selftest_stream_delay(delay_us: int, with_join: bool) -> float:
     out = C.c_float()
     _check(_lib.load().sbr_selftest_stream_delay(int(delay_us), 1 if with_join else 0, C.byref(out)))
     return out.value
+
+
+def guard_report(model=None) -> SbrGuardReport:
+    """sbr_test_guard_report (SBR_TEST_GUARD): what the guard bands around the scratch cache's live blocks and, with ``model``, its
+    arena's current carve show now, plus what the checks at put / carve found since the last report.  Reads and resets."""
+    out = SbrGuardReport()
+    _check(_lib.load().sbr_test_guard_report(None if model is None else model._h, C.byref(out)))
+    return out
+
+
+def selftest_guard(model, where: int, side: int):
+    """sbr_selftest_guard: the reports of one byte set by the library just past (side > 0) or just before (side < 0) an
+    allocation of kind ``where`` (GUARD_*), on the first and on the re-used allocation."""
+    out = (SbrGuardReport * 2)()
+    _check(_lib.load().sbr_selftest_guard(None if model is None else model._h, int(where), int(side), out))
+    return out[0], out[1]
 
 
 def device_info():

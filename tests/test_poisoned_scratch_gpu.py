@@ -656,10 +656,11 @@ def test_sessions_on_poisoned_stores(poison, kind, d):
 # ------------------------------------------------------------------------------------------------
 # training: whole fits against the oracle
 # ------------------------------------------------------------------------------------------------
-def _fit(kind, loss, d, items=150, users=60, T=20, B=64, opt=0, fusion=None, calls=1):
-    """Two epochs (and `calls` fit calls) on `users` histories of up to T + 5 items against the oracle: every parameter and
-    accumulator bit for bit, the lagged loss figure, the reported loss to 1e-6 (an order-free f64 sum), mrr_score's ranks."""
-    ptr, it = synthetic_interactions(users, items, T + 5, seed=23, zipf=True)
+def _fit(kind, loss, d, items=150, users=60, T=20, B=64, opt=0, fusion=None, calls=1, data=None):
+    """Two epochs (and `calls` fit calls) on `users` histories of up to T + 5 items (or on data = (ptr, items), which
+    tests/test_guarded_scratch_gpu.py shapes to a step's row count) against the oracle: every parameter and accumulator bit for
+    bit, the lagged loss figure, the reported loss to 1e-6 (an order-free f64 sum), mrr_score's ranks."""
+    ptr, it = data if data is not None else synthetic_interactions(users, items, T + 5, seed=23, zipf=True)
     hp = hparams(items, T, d, int(kind), loss, B=B, epochs=2, opt=opt, lr=0.02 if opt else 0.16)
     g, o = parity.make_pair(hp)
     if fusion is not None:
