@@ -4389,6 +4389,7 @@ struct Partition {
     float inv_t;
     float* out_shift;
     uint64_t* out_mass;
+    uint32_t* out_frac_bits; /* scan_call writes the model's F here after success */
 };
 
 /* the arguments the *_log_partition calls share: false for a temperature sample_args refuses or an output that is missing */
@@ -4396,7 +4397,7 @@ bool partition_args(float temperature, uint64_t n, float* out_shift, uint64_t* o
     const sbr_sample_args a{temperature, 0, nullptr};
     Sample sm;
     if (!sample_args(&a, nullptr, &sm) || !out_frac_bits || (n && (!out_shift || !out_mass))) return false;
-    *out = Partition{sm.inv_t, out_shift, out_mass};
+    *out = Partition{sm.inv_t, out_shift, out_mass, out_frac_bits};
     return true;
 }
 
@@ -4456,6 +4457,7 @@ struct Above {
     uint32_t* out_ids;
     float* out_scores;
     uint64_t total;
+    uint64_t* out_total;         /* scan_call writes `total` here after success (the audience calls do that themselves) */
     const uint64_t* n = nullptr; /* the budget form: thresholds is null */
     float* out_cuts = nullptr;
 };
@@ -4466,7 +4468,7 @@ bool above_args(const float* thresholds, uint64_t n, uint64_t* out_counts, uint6
     if (!out_total || (n && (!thresholds || !out_counts)) || (out_scores && !out_ids)) return false;
     for (uint64_t i = 0; i < n; ++i)
         if (std::isnan(thresholds[i])) return false;
-    *out = Above{thresholds, out_counts, capacity, out_ids, out_scores, 0};
+    *out = Above{thresholds, out_counts, capacity, out_ids, out_scores, 0, out_total};
     return true;
 }
 
@@ -4474,7 +4476,7 @@ bool above_args(const float* thresholds, uint64_t n, uint64_t* out_counts, uint6
 bool top_args(const uint64_t* n, uint64_t rows, float* out_cuts, uint64_t* out_counts, uint64_t* out_total, uint64_t capacity, uint32_t* out_ids,
               float* out_scores, Above* out) {
     if (!out_total || (rows && (!n || !out_counts || !out_cuts)) || (out_scores && !out_ids)) return false;
-    *out = Above{nullptr, out_counts, capacity, out_ids, out_scores, 0, n, out_cuts};
+    *out = Above{nullptr, out_counts, capacity, out_ids, out_scores, 0, out_total, n, out_cuts};
     return true;
 }
 
@@ -4601,18 +4603,55 @@ struct ScanVariant {
     bool cosine = false;                            /* item rows: rank by cosine, not by the plain dot product */
     const std::vector<uint32_t>* subset = nullptr;  /* recommend_among's item set */
     const Diverse* dv = nullptr;
-    const TagFilterArg* flt = nullptr;
-    const Sample* sm = nullptr;
+    const TagFilterArg* flt = nullptr; /* through scan_call, null: the rows' own masks, a filter unless both are null */
+    Sample* sm = nullptr;             /* the caller's own: scan_call sets a store's fallback streams in it */
     const Partition* pt = nullptr;
     Above* ab = nullptr;
     const Capped* cp = nullptr;
     const sbr_item_set* set = nullptr; /* the scan runs over the set's resident sub-table; not with item rows or a subset */
-    static ScanVariant of(const Diverse* dv, const TagFilterArg* flt, const Sample* sm = nullptr, const Partition* pt = nullptr) {
-        ScanVariant v;
-        v.dv = dv; v.flt = flt; v.sm = sm; v.pt = pt;
-        return v;
+};
+
+/* What the scans of (m, set) read and are carved for: the catalogue (set null), or the set's resident sub-table, whose item j is
+ * S[j].  An empty set has no table: no scan runs (`none`), and buffers are carved as for one item. */
+struct SetView {
+    sbr::ModelView cat;
+    uint32_t ns = 0;      /* the set's items; 0 without a set */
+    uint32_t scanned;     /* the items the scan's buffers are carved for */
+    bool none = false;    /* an empty set: nothing to scan */
+    SetView(const sbr_model* m, const sbr_item_set* set) : cat(m->mv), scanned((uint32_t)m->hp.num_items) {
+        if (!set) return;
+        ns = (uint32_t)set->ids.size();
+        scanned = std::max(ns, 1u);
+        none = ns == 0;
+        if (none) return;
+        cat.E = set->E;
+        cat.b = set->b;
+        cat.num_items = ns;
     }
 };
+
+/* The tag masks of a chunk's nu rows, each `rep` times over (beam search: once per beam), to d_any / d_none: row i's are the call's
+ * row users[i], or c0 + i where users is null.  *host holds the words (any_of, then none_of) until the stream is drained. */
+sbr_status upload_masks(sbr_model* m, const TagFilterArg& flt, const uint64_t* users, size_t c0, size_t nu, size_t rep, uint32_t* d_any,
+                        uint32_t* d_none, std::vector<uint32_t>* host) {
+    const size_t nb = nu * rep;
+    host->assign(2 * nb, 0u);
+    for (size_t i = 0; i < nb; ++i) {
+        const uint64_t u = users ? users[i / rep] : c0 + i / rep;
+        if (flt.any_of) (*host)[i] = flt.any_of[u];
+        if (flt.none_of) (*host)[nb + i] = flt.none_of[u];
+    }
+    HIPCHK(hipMemcpyAsync(d_any, host->data(), nb * 4, hipMemcpyHostToDevice, m->stream));
+    HIPCHK(hipMemcpyAsync(d_none, host->data() + nb, nb * 4, hipMemcpyHostToDevice, m->stream));
+    return SBR_OK;
+}
+
+/* a chunk cap's TEST HOOK: NAME=n (n >= 1) in the environment, read per call, stands in for `cap` */
+size_t chunk_override(const char* name, size_t cap) {
+    const char* e = std::getenv(name);
+    const long long v = e ? std::atoll(e) : 0;
+    return v >= 1 ? (size_t)v : cap;
+}
 
 /* top-k of every user of `s`, in chunks; results to out_items / out_scores (host, num_users x k; scores optional).  With item rows
  * (similar_items: the users are the queries) the launch makes the rows itself and ranks by cosine (v.cosine), or by the plain dot
@@ -4672,13 +4711,9 @@ sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, 
     const size_t seen_w = s.seen ? s.seen->w : 0;
     std::vector<uint64_t> users(num_users);
     for (uint64_t u = 0; u < num_users; ++u) users[u] = u;
-    const uint32_t scanned_items = set ? (uint32_t)set->ids.size() : v.subset ? (uint32_t)v.subset->size() : (uint32_t)m->hp.num_items;
-    sbr::ModelView cat = m->mv; /* what the launches scan: the catalogue, or the set's sub-table, whose item j is S[j] */
-    if (set) {
-        cat.E = set->E;
-        cat.b = set->b;
-        cat.num_items = scanned_items;
-    }
+    const SetView sv(m, set);
+    const sbr::ModelView& cat = sv.cat; /* what the launches scan */
+    const uint32_t scanned_items = v.subset ? (uint32_t)v.subset->size() : sv.scanned;
     const size_t cap = recommend_users_cap(scanned_items, k);
     for (Chunk ch; next_chunk(users, cap, s, m->hp.max_sequence_length, &ch);) {
         const size_t nu = ch.users.size();
@@ -4739,15 +4774,7 @@ sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, 
         } else if (excl)
             SBRCHK(upload_csr(m, tb.eptr, ur.b.list_ptr, tb.excl, ur.b.list_items));
         std::vector<uint32_t> masks; /* the chunk's users' any_of, then their none_of */
-        if (v.flt) {
-            masks.assign(2 * nu, 0u);
-            for (size_t i = 0; i < nu; ++i) {
-                if (v.flt->any_of) masks[i] = v.flt->any_of[ch.users[i]];
-                if (v.flt->none_of) masks[nu + i] = v.flt->none_of[ch.users[i]];
-            }
-            HIPCHK(hipMemcpyAsync(tb.any_of, masks.data(), nu * 4, hipMemcpyHostToDevice, m->stream));
-            HIPCHK(hipMemcpyAsync(tb.none_of, masks.data() + nu, nu * 4, hipMemcpyHostToDevice, m->stream));
-        }
+        if (v.flt) SBRCHK(upload_masks(m, *v.flt, ch.users.data(), 0, nu, 1, tb.any_of, tb.none_of, &masks));
         std::vector<uint64_t> streams; /* the chunk's users' streams */
         if (sm) {
             streams.resize(nu);
@@ -4843,101 +4870,81 @@ bool capped_args(const sbr_cap_args* a, uint32_t k, uint8_t* out_complete, Cappe
     return true;
 }
 
-/* the plain calls, their *_filtered forms (flt non-null) and their diverse forms (dv non-null: k is the pool) */
-sbr_status recommend_call(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users, uint32_t k, uint32_t flags,
-                          uint32_t* out_items, float* out_scores, const TagFilterArg* flt, const Diverse* dv = nullptr,
-                          const Sample* sm = nullptr, const Capped* cp = nullptr) {
-    if (!m || !user_ptr || (num_users && !out_items)) return SBR_ERR_INVALID_ARGUMENT;
-    if (!scan_k_ok(m, k, dv, cp) || (flags & ~SBR_RECOMMEND_INCLUDE_HISTORY)) return SBR_ERR_INVALID_ARGUMENT;
-    std::lock_guard<std::mutex> lock(m->mu);
-    SBRCHK(enter_reader(m));
-    SBRCHK(check_csr(m, user_ptr, num_users, item_ids, false));
-    /* the WHOLE history is masked (evaluation.rs:30-32) */
-    ScanVariant v = ScanVariant::of(dv, flt, sm);
-    v.cp = cp;
-    return recommend_scan(m, RepSource::of_histories(user_ptr, item_ids, 0, !(flags & SBR_RECOMMEND_INCLUDE_HISTORY)), num_users, k, out_items,
-                          out_scores, v);
-}
+/* The rows of a call of the scan families, from the one source `kind` states: histories (flags: SBR_RECOMMEND_INCLUDE_HISTORY only;
+ * the lists are the histories themselves), the caller's representations, or a session store's slots (flags: the same flag, and only
+ * on a store with memory), the last two with optional exclusion lists; and the rows' optional tag masks, which make a filter unless
+ * both are null (a *_filtered call states its filter in the variant instead).  sbr_scan_rows' fields and the kind. */
+struct ScanRows {
+    enum Kind { Histories, Reps, Store } kind = Histories;
+    const uint64_t* user_ptr = nullptr;
+    const uint32_t* item_ids = nullptr;
+    uint32_t flags = 0;
+    const float* reps = nullptr;
+    sbr_sessions* store = nullptr;
+    const uint32_t* slots = nullptr;
+    const uint64_t* excl_ptr = nullptr;
+    const uint32_t* excl_items = nullptr;
+    const uint32_t *any_of = nullptr, *none_of = nullptr;
+    static ScanRows of_histories(const uint64_t* user_ptr, const uint32_t* item_ids, uint32_t flags, const uint32_t* any_of = nullptr,
+                                 const uint32_t* none_of = nullptr) {
+        ScanRows r;
+        r.kind = Histories; r.user_ptr = user_ptr; r.item_ids = item_ids; r.flags = flags; r.any_of = any_of; r.none_of = none_of;
+        return r;
+    }
+    static ScanRows of_reps(const float* reps, const uint64_t* excl_ptr, const uint32_t* excl_items, const uint32_t* any_of = nullptr,
+                            const uint32_t* none_of = nullptr) {
+        ScanRows r;
+        r.kind = Reps; r.reps = reps; r.excl_ptr = excl_ptr; r.excl_items = excl_items; r.any_of = any_of; r.none_of = none_of;
+        return r;
+    }
+    static ScanRows of_store(sbr_sessions* store, const uint32_t* slots, const uint64_t* excl_ptr, const uint32_t* excl_items, uint32_t flags,
+                             const uint32_t* any_of = nullptr, const uint32_t* none_of = nullptr) {
+        ScanRows r;
+        r.kind = Store; r.store = store; r.slots = slots; r.excl_ptr = excl_ptr; r.excl_items = excl_items; r.flags = flags;
+        r.any_of = any_of; r.none_of = none_of;
+        return r;
+    }
+};
 
-sbr_status recommend_reps_call(sbr_model* m, const float* reps, uint64_t num_users, uint32_t k, const uint64_t* excl_ptr,
-                               const uint32_t* excl_items, uint32_t* out_items, float* out_scores, const TagFilterArg* flt,
-                               const Diverse* dv = nullptr, const Sample* sm = nullptr, const Capped* cp = nullptr) {
-    if (!m || (num_users && (!reps || !out_items))) return SBR_ERR_INVALID_ARGUMENT;
-    if (!scan_k_ok(m, k, dv, cp)) return SBR_ERR_INVALID_ARGUMENT;
-    if (!excl_args_ok(excl_ptr, excl_items, num_users)) return SBR_ERR_INVALID_ARGUMENT;
-    std::lock_guard<std::mutex> lock(m->mu);
-    SBRCHK(enter_reader(m));
-    if (excl_ptr) SBRCHK(check_csr(m, excl_ptr, num_users, excl_items, false));
-    ScanVariant v = ScanVariant::of(dv, flt, sm);
-    v.cp = cp;
-    return recommend_scan(m, RepSource::of_rows(reps, excl_ptr, excl_items), num_users, k, out_items, out_scores, v);
-}
+/* The one entry of the scan families (defined beside the session store, whose rows it reads): the 34 public entry points parse their
+ * family's arguments, name their rows and their variant, and call this. */
+sbr_status scan_call(sbr_model* m, const sbr_item_set* set, const ScanRows& r, uint64_t n, uint32_t k, uint32_t* out_items, float* out_scores,
+                     ScanVariant v);
+sbr_status enter_item_set(const sbr_item_set* set);
 
 }  // namespace
 
 sbr_status sbr_recommend(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users, uint32_t k, uint32_t flags,
                          uint32_t* out_items, float* out_scores) {
-    return recommend_call(m, user_ptr, item_ids, num_users, k, flags, out_items, out_scores, nullptr);
+    return scan_call(m, nullptr, ScanRows::of_histories(user_ptr, item_ids, flags), num_users, k, out_items, out_scores, ScanVariant());
 }
 
 sbr_status sbr_recommend_reps(sbr_model* m, const float* reps, uint64_t num_users, uint32_t k, const uint64_t* excl_ptr,
                               const uint32_t* excl_items, uint32_t* out_items, float* out_scores) {
-    return recommend_reps_call(m, reps, num_users, k, excl_ptr, excl_items, out_items, out_scores, nullptr);
+    return scan_call(m, nullptr, ScanRows::of_reps(reps, excl_ptr, excl_items), num_users, k, out_items, out_scores, ScanVariant());
 }
 
 /* ---------------------------------------------------------------------------------------------
  * the threshold form: every item at or over a per-row score, as CSR (sbr_catalogue.hip, above_gemm_kernel)
  * ------------------------------------------------------------------------------------------- */
-namespace {
-
-/* sbr_recommend_above and sbr_recommend_top: ab is above_args' or top_args' descriptor, args_ok what that returned */
-sbr_status recommend_above_call(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users, uint32_t flags,
-                                const uint32_t* any_of, const uint32_t* none_of, bool args_ok, Above& ab, uint64_t* out_total) {
-    TagFilterArg hold;
-    if (!m || !user_ptr || !args_ok) return SBR_ERR_INVALID_ARGUMENT;
-    if (flags & ~SBR_RECOMMEND_INCLUDE_HISTORY) return SBR_ERR_INVALID_ARGUMENT;
-    std::lock_guard<std::mutex> lock(m->mu);
-    SBRCHK(enter_reader(m));
-    SBRCHK(check_csr(m, user_ptr, num_users, item_ids, false));
-    ScanVariant v = ScanVariant::of(nullptr, sample_filter(any_of, none_of, &hold));
-    v.ab = &ab;
-    SBRCHK(recommend_scan(m, RepSource::of_histories(user_ptr, item_ids, 0, !(flags & SBR_RECOMMEND_INCLUDE_HISTORY)), num_users, 1, nullptr, nullptr, v));
-    *out_total = ab.total;
-    return SBR_OK;
-}
-
-/* sbr_recommend_above_reps and sbr_recommend_top_reps */
-sbr_status recommend_above_reps_call(sbr_model* m, const float* reps, uint64_t num_users, const uint64_t* excl_ptr, const uint32_t* excl_items,
-                                     const uint32_t* any_of, const uint32_t* none_of, bool args_ok, Above& ab, uint64_t* out_total) {
-    TagFilterArg hold;
-    if (!m || (num_users && !reps) || !args_ok) return SBR_ERR_INVALID_ARGUMENT;
-    if (!excl_args_ok(excl_ptr, excl_items, num_users)) return SBR_ERR_INVALID_ARGUMENT;
-    std::lock_guard<std::mutex> lock(m->mu);
-    SBRCHK(enter_reader(m));
-    if (excl_ptr) SBRCHK(check_csr(m, excl_ptr, num_users, excl_items, false));
-    ScanVariant v = ScanVariant::of(nullptr, sample_filter(any_of, none_of, &hold));
-    v.ab = &ab;
-    SBRCHK(recommend_scan(m, RepSource::of_rows(reps, excl_ptr, excl_items), num_users, 1, nullptr, nullptr, v));
-    *out_total = ab.total;
-    return SBR_OK;
-}
-
-}  // namespace
-
 sbr_status sbr_recommend_above(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users, const float* thresholds,
                                uint32_t flags, const uint32_t* any_of, const uint32_t* none_of, uint64_t* out_counts, uint64_t* out_total,
                                uint64_t capacity, uint32_t* out_ids, float* out_scores) {
     Above ab;
-    const bool ok = above_args(thresholds, num_users, out_counts, out_total, capacity, out_ids, out_scores, &ab);
-    return recommend_above_call(m, user_ptr, item_ids, num_users, flags, any_of, none_of, ok, ab, out_total);
+    if (!above_args(thresholds, num_users, out_counts, out_total, capacity, out_ids, out_scores, &ab)) return SBR_ERR_INVALID_ARGUMENT;
+    ScanVariant v;
+    v.ab = &ab;
+    return scan_call(m, nullptr, ScanRows::of_histories(user_ptr, item_ids, flags, any_of, none_of), num_users, 1, nullptr, nullptr, v);
 }
 
 sbr_status sbr_recommend_above_reps(sbr_model* m, const float* reps, uint64_t num_users, const float* thresholds, const uint64_t* excl_ptr,
                                     const uint32_t* excl_items, const uint32_t* any_of, const uint32_t* none_of, uint64_t* out_counts,
                                     uint64_t* out_total, uint64_t capacity, uint32_t* out_ids, float* out_scores) {
     Above ab;
-    const bool ok = above_args(thresholds, num_users, out_counts, out_total, capacity, out_ids, out_scores, &ab);
-    return recommend_above_reps_call(m, reps, num_users, excl_ptr, excl_items, any_of, none_of, ok, ab, out_total);
+    if (!above_args(thresholds, num_users, out_counts, out_total, capacity, out_ids, out_scores, &ab)) return SBR_ERR_INVALID_ARGUMENT;
+    ScanVariant v;
+    v.ab = &ab;
+    return scan_call(m, nullptr, ScanRows::of_reps(reps, excl_ptr, excl_items, any_of, none_of), num_users, 1, nullptr, nullptr, v);
 }
 
 /* the budget form: the exact best n[row] of every row and its cut (sbr_catalogue.hip, select_gemm_kernel; TOP in sbr_hip.h) */
@@ -4945,16 +4952,20 @@ sbr_status sbr_recommend_top(sbr_model* m, const uint64_t* user_ptr, const uint3
                              const uint32_t* any_of, const uint32_t* none_of, float* out_cuts, uint64_t* out_counts, uint64_t* out_total,
                              uint64_t capacity, uint32_t* out_ids, float* out_scores) {
     Above ab;
-    const bool ok = top_args(n, num_users, out_cuts, out_counts, out_total, capacity, out_ids, out_scores, &ab);
-    return recommend_above_call(m, user_ptr, item_ids, num_users, flags, any_of, none_of, ok, ab, out_total);
+    if (!top_args(n, num_users, out_cuts, out_counts, out_total, capacity, out_ids, out_scores, &ab)) return SBR_ERR_INVALID_ARGUMENT;
+    ScanVariant v;
+    v.ab = &ab;
+    return scan_call(m, nullptr, ScanRows::of_histories(user_ptr, item_ids, flags, any_of, none_of), num_users, 1, nullptr, nullptr, v);
 }
 
 sbr_status sbr_recommend_top_reps(sbr_model* m, const float* reps, uint64_t num_users, const uint64_t* n, const uint64_t* excl_ptr,
                                   const uint32_t* excl_items, const uint32_t* any_of, const uint32_t* none_of, float* out_cuts,
                                   uint64_t* out_counts, uint64_t* out_total, uint64_t capacity, uint32_t* out_ids, float* out_scores) {
     Above ab;
-    const bool ok = top_args(n, num_users, out_cuts, out_counts, out_total, capacity, out_ids, out_scores, &ab);
-    return recommend_above_reps_call(m, reps, num_users, excl_ptr, excl_items, any_of, none_of, ok, ab, out_total);
+    if (!top_args(n, num_users, out_cuts, out_counts, out_total, capacity, out_ids, out_scores, &ab)) return SBR_ERR_INVALID_ARGUMENT;
+    ScanVariant v;
+    v.ab = &ab;
+    return scan_call(m, nullptr, ScanRows::of_reps(reps, excl_ptr, excl_items, any_of, none_of), num_users, 1, nullptr, nullptr, v);
 }
 
 /* ---------------------------------------------------------------------------------------------
@@ -4988,14 +4999,18 @@ sbr_status sbr_model_get_item_tags(sbr_model* m, uint32_t* out) {
 sbr_status sbr_recommend_filtered(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users, uint32_t k,
                                   uint32_t flags, const uint32_t* any_of, const uint32_t* none_of, uint32_t* out_items, float* out_scores) {
     const TagFilterArg flt{any_of, none_of};
-    return recommend_call(m, user_ptr, item_ids, num_users, k, flags, out_items, out_scores, &flt);
+    ScanVariant v;
+    v.flt = &flt;
+    return scan_call(m, nullptr, ScanRows::of_histories(user_ptr, item_ids, flags), num_users, k, out_items, out_scores, v);
 }
 
 sbr_status sbr_recommend_filtered_reps(sbr_model* m, const float* reps, uint64_t num_users, uint32_t k, const uint64_t* excl_ptr,
                                        const uint32_t* excl_items, const uint32_t* any_of, const uint32_t* none_of, uint32_t* out_items,
                                        float* out_scores) {
     const TagFilterArg flt{any_of, none_of};
-    return recommend_reps_call(m, reps, num_users, k, excl_ptr, excl_items, out_items, out_scores, &flt);
+    ScanVariant v;
+    v.flt = &flt;
+    return scan_call(m, nullptr, ScanRows::of_reps(reps, excl_ptr, excl_items), num_users, k, out_items, out_scores, v);
 }
 
 /* ---------------------------------------------------------------------------------------------
@@ -5005,19 +5020,20 @@ sbr_status sbr_recommend_sampled(sbr_model* m, const uint64_t* user_ptr, const u
                                  const struct sbr_sample_args* sample, const uint32_t* any_of, const uint32_t* none_of, uint32_t* out_items,
                                  float* out_scores, float* out_keys) {
     Sample sm;
-    TagFilterArg hold;
     if (!sample_args(sample, out_keys, &sm)) return SBR_ERR_INVALID_ARGUMENT;
-    return recommend_call(m, user_ptr, item_ids, num_users, k, flags, out_items, out_scores, sample_filter(any_of, none_of, &hold), nullptr, &sm);
+    ScanVariant v;
+    v.sm = &sm;
+    return scan_call(m, nullptr, ScanRows::of_histories(user_ptr, item_ids, flags, any_of, none_of), num_users, k, out_items, out_scores, v);
 }
 
 sbr_status sbr_recommend_sampled_reps(sbr_model* m, const float* reps, uint64_t num_users, uint32_t k, const uint64_t* excl_ptr,
                                       const uint32_t* excl_items, const struct sbr_sample_args* sample, const uint32_t* any_of,
                                       const uint32_t* none_of, uint32_t* out_items, float* out_scores, float* out_keys) {
     Sample sm;
-    TagFilterArg hold;
     if (!sample_args(sample, out_keys, &sm)) return SBR_ERR_INVALID_ARGUMENT;
-    return recommend_reps_call(m, reps, num_users, k, excl_ptr, excl_items, out_items, out_scores, sample_filter(any_of, none_of, &hold), nullptr,
-                               &sm);
+    ScanVariant v;
+    v.sm = &sm;
+    return scan_call(m, nullptr, ScanRows::of_reps(reps, excl_ptr, excl_items, any_of, none_of), num_users, k, out_items, out_scores, v);
 }
 
 /* ---------------------------------------------------------------------------------------------
@@ -5048,33 +5064,20 @@ sbr_status sbr_log_partition(sbr_model* m, const uint64_t* user_ptr, const uint3
                              float temperature, const uint32_t* any_of, const uint32_t* none_of, float* out_shift, uint64_t* out_mass,
                              uint32_t* out_frac_bits) {
     Partition pt;
-    TagFilterArg hold;
-    if (!m || !user_ptr || !partition_args(temperature, num_users, out_shift, out_mass, out_frac_bits, &pt)) return SBR_ERR_INVALID_ARGUMENT;
-    if (flags & ~SBR_RECOMMEND_INCLUDE_HISTORY) return SBR_ERR_INVALID_ARGUMENT;
-    std::lock_guard<std::mutex> lock(m->mu);
-    SBRCHK(enter_reader(m));
-    SBRCHK(check_csr(m, user_ptr, num_users, item_ids, false));
-    const sbr_status r = recommend_scan(m, RepSource::of_histories(user_ptr, item_ids, 0, !(flags & SBR_RECOMMEND_INCLUDE_HISTORY)), num_users, 1,
-                                        nullptr, nullptr, ScanVariant::of(nullptr, sample_filter(any_of, none_of, &hold), nullptr, &pt));
-    if (r == SBR_OK) *out_frac_bits = sbr_softmax_fbits((uint32_t)m->hp.num_items);
-    return r;
+    if (!partition_args(temperature, num_users, out_shift, out_mass, out_frac_bits, &pt)) return SBR_ERR_INVALID_ARGUMENT;
+    ScanVariant v;
+    v.pt = &pt;
+    return scan_call(m, nullptr, ScanRows::of_histories(user_ptr, item_ids, flags, any_of, none_of), num_users, 1, nullptr, nullptr, v);
 }
 
 sbr_status sbr_log_partition_reps(sbr_model* m, const float* reps, uint64_t num_users, const uint64_t* excl_ptr, const uint32_t* excl_items,
                                   float temperature, const uint32_t* any_of, const uint32_t* none_of, float* out_shift, uint64_t* out_mass,
                                   uint32_t* out_frac_bits) {
     Partition pt;
-    TagFilterArg hold;
-    if (!m || (num_users && !reps) || !partition_args(temperature, num_users, out_shift, out_mass, out_frac_bits, &pt))
-        return SBR_ERR_INVALID_ARGUMENT;
-    if (!excl_args_ok(excl_ptr, excl_items, num_users)) return SBR_ERR_INVALID_ARGUMENT;
-    std::lock_guard<std::mutex> lock(m->mu);
-    SBRCHK(enter_reader(m));
-    if (excl_ptr) SBRCHK(check_csr(m, excl_ptr, num_users, excl_items, false));
-    const sbr_status r = recommend_scan(m, RepSource::of_rows(reps, excl_ptr, excl_items), num_users, 1, nullptr, nullptr,
-                                        ScanVariant::of(nullptr, sample_filter(any_of, none_of, &hold), nullptr, &pt));
-    if (r == SBR_OK) *out_frac_bits = sbr_softmax_fbits((uint32_t)m->hp.num_items);
-    return r;
+    if (!partition_args(temperature, num_users, out_shift, out_mass, out_frac_bits, &pt)) return SBR_ERR_INVALID_ARGUMENT;
+    ScanVariant v;
+    v.pt = &pt;
+    return scan_call(m, nullptr, ScanRows::of_reps(reps, excl_ptr, excl_items, any_of, none_of), num_users, 1, nullptr, nullptr, v);
 }
 
 namespace {
@@ -5234,7 +5237,9 @@ sbr_status sbr_recommend_diverse_max_pool(const sbr_model* m, uint32_t* out) {
 sbr_status sbr_recommend_diverse(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users, uint32_t k, uint32_t pool,
                                  float trade_off, uint32_t metric, uint32_t flags, uint32_t* out_items, float* out_scores) {
     const Diverse dv{k, trade_off, metric};
-    return recommend_call(m, user_ptr, item_ids, num_users, pool, flags, out_items, out_scores, nullptr, &dv);
+    ScanVariant v;
+    v.dv = &dv;
+    return scan_call(m, nullptr, ScanRows::of_histories(user_ptr, item_ids, flags), num_users, pool, out_items, out_scores, v);
 }
 
 sbr_status sbr_recommend_diverse_filtered(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users, uint32_t k,
@@ -5242,14 +5247,19 @@ sbr_status sbr_recommend_diverse_filtered(sbr_model* m, const uint64_t* user_ptr
                                           const uint32_t* none_of, uint32_t* out_items, float* out_scores) {
     const TagFilterArg flt{any_of, none_of};
     const Diverse dv{k, trade_off, metric};
-    return recommend_call(m, user_ptr, item_ids, num_users, pool, flags, out_items, out_scores, &flt, &dv);
+    ScanVariant v;
+    v.dv = &dv;
+    v.flt = &flt;
+    return scan_call(m, nullptr, ScanRows::of_histories(user_ptr, item_ids, flags), num_users, pool, out_items, out_scores, v);
 }
 
 sbr_status sbr_recommend_diverse_reps(sbr_model* m, const float* reps, uint64_t num_users, uint32_t k, uint32_t pool, float trade_off,
                                       uint32_t metric, const uint64_t* excl_ptr, const uint32_t* excl_items, uint32_t* out_items,
                                       float* out_scores) {
     const Diverse dv{k, trade_off, metric};
-    return recommend_reps_call(m, reps, num_users, pool, excl_ptr, excl_items, out_items, out_scores, nullptr, &dv);
+    ScanVariant v;
+    v.dv = &dv;
+    return scan_call(m, nullptr, ScanRows::of_reps(reps, excl_ptr, excl_items), num_users, pool, out_items, out_scores, v);
 }
 
 sbr_status sbr_recommend_diverse_filtered_reps(sbr_model* m, const float* reps, uint64_t num_users, uint32_t k, uint32_t pool, float trade_off,
@@ -5257,7 +5267,10 @@ sbr_status sbr_recommend_diverse_filtered_reps(sbr_model* m, const float* reps, 
                                                const uint32_t* none_of, uint32_t* out_items, float* out_scores) {
     const TagFilterArg flt{any_of, none_of};
     const Diverse dv{k, trade_off, metric};
-    return recommend_reps_call(m, reps, num_users, pool, excl_ptr, excl_items, out_items, out_scores, &flt, &dv);
+    ScanVariant v;
+    v.dv = &dv;
+    v.flt = &flt;
+    return scan_call(m, nullptr, ScanRows::of_reps(reps, excl_ptr, excl_items), num_users, pool, out_items, out_scores, v);
 }
 
 /* ---------------------------------------------------------------------------------------------
@@ -5292,22 +5305,22 @@ sbr_status sbr_recommend_capped(sbr_model* m, const uint64_t* user_ptr, const ui
                                 const struct sbr_cap_args* cap, const uint32_t* any_of, const uint32_t* none_of, uint32_t* out_items,
                                 float* out_scores, uint8_t* out_complete) {
     Capped cp;
-    TagFilterArg hold;
     uint32_t pool = 0;
     if (!capped_args(cap, k, out_complete, &cp, &pool)) return SBR_ERR_INVALID_ARGUMENT;
-    return recommend_call(m, user_ptr, item_ids, num_users, pool, flags, out_items, out_scores, sample_filter(any_of, none_of, &hold), nullptr,
-                          nullptr, &cp);
+    ScanVariant v;
+    v.cp = &cp;
+    return scan_call(m, nullptr, ScanRows::of_histories(user_ptr, item_ids, flags, any_of, none_of), num_users, pool, out_items, out_scores, v);
 }
 
 sbr_status sbr_recommend_capped_reps(sbr_model* m, const float* reps, uint64_t num_users, uint32_t k, const uint64_t* excl_ptr,
                                      const uint32_t* excl_items, const struct sbr_cap_args* cap, const uint32_t* any_of,
                                      const uint32_t* none_of, uint32_t* out_items, float* out_scores, uint8_t* out_complete) {
     Capped cp;
-    TagFilterArg hold;
     uint32_t pool = 0;
     if (!capped_args(cap, k, out_complete, &cp, &pool)) return SBR_ERR_INVALID_ARGUMENT;
-    return recommend_reps_call(m, reps, num_users, pool, excl_ptr, excl_items, out_items, out_scores, sample_filter(any_of, none_of, &hold),
-                               nullptr, nullptr, &cp);
+    ScanVariant v;
+    v.cp = &cp;
+    return scan_call(m, nullptr, ScanRows::of_reps(reps, excl_ptr, excl_items, any_of, none_of), num_users, pool, out_items, out_scores, v);
 }
 
 /* ---------------------------------------------------------------------------------------------
@@ -5339,7 +5352,8 @@ sbr_status similar_items_call(sbr_model* m, const uint32_t* query_items, uint64_
             eptr[j + 1] = eitems.size();
         }
     }
-    ScanVariant v = ScanVariant::of(nullptr, flt);
+    ScanVariant v;
+    v.flt = flt;
     v.cosine = metric == SBR_SIMILAR_COSINE;
     return recommend_scan(m, RepSource::of_item_rows(query_items, self ? excl_ptr : eptr.data(), self ? excl_items : eitems.data()), num_queries, k,
                           out_items, out_scores, v);
@@ -5757,11 +5771,7 @@ sbr_status sessions_gather(sbr_sessions* st, const uint32_t* rows, uint64_t n, f
 size_t replay_chunk_cap(const sbr_model* m, uint32_t w) {
     constexpr size_t budget = (size_t)256 << 20;
     const size_t per = 8 + (size_t)w * 4 + (m->ng ? (size_t)m->d * 16 : 8);
-    size_t cap = std::max<size_t>(budget / per, 1);
-    if (const char* e = std::getenv("SBR_SESSIONS_REPLAY_CHUNK")) {
-        const long long v = std::atoll(e);
-        if (v >= 1) cap = (size_t)v;
-    }
+    const size_t cap = chunk_override("SBR_SESSIONS_REPLAY_CHUNK", std::max<size_t>(budget / per, 1));
     return std::min<size_t>(cap, (size_t)0x7FFFFFFF / w);
 }
 
@@ -6078,41 +6088,86 @@ RepSource RepSource::of_sessions(const sbr_sessions* st, const std::vector<int>&
     return s;
 }
 
-/* sbr_sessions_recommend*, and with dv (k is the pool) sbr_sessions_recommend_diverse*, which have no flags argument: flags = 0 */
-sbr_status sessions_recommend_call(sbr_sessions* st, const uint32_t* slots, uint64_t n, uint32_t k, const uint64_t* excl_ptr,
-                                   const uint32_t* excl_items, uint32_t flags, uint32_t* out_items, float* out_scores, const TagFilterArg* flt,
-                                   const Diverse* dv = nullptr, const Sample* sm = nullptr, const Partition* pt = nullptr, Above* ab = nullptr,
-                                   const Capped* cp = nullptr) {
-    if (!st || (n && !out_items && !pt && !ab)) return SBR_ERR_INVALID_ARGUMENT;
-    /* a store with memory takes sbr_recommend's flag; one without keeps refusing every flag */
-    if (st->seen.w ? (flags & ~SBR_RECOMMEND_INCLUDE_HISTORY) != 0 : flags != 0) return SBR_ERR_INVALID_ARGUMENT;
-    if (!scan_k_ok(st->m, k, dv, cp)) return SBR_ERR_INVALID_ARGUMENT;
-    if (!excl_args_ok(excl_ptr, excl_items, n)) return SBR_ERR_INVALID_ARGUMENT;
-    sbr_model* m = st->m;
-    std::lock_guard<std::mutex> lock(m->mu);
-    SBRCHK(enter_sessions(st));
-    SBRCHK(check_slots(st, slots, n));
-    if (excl_ptr) SBRCHK(check_csr(m, excl_ptr, n, excl_items, false));
-    const std::vector<int> rows = session_rep_rows(st, slots, n);
-    const bool seen = st->seen.w && !(flags & SBR_RECOMMEND_INCLUDE_HISTORY);
-    ScanVariant v = ScanVariant::of(dv, flt, sm, pt);
-    v.ab = ab;
-    v.cp = cp;
-    return recommend_scan(m, RepSource::of_sessions(st, rows, excl_ptr, excl_items, seen ? slots : nullptr), n, k, out_items, out_scores, v);
+/* What a scan call has entered once it may read its rows: the model's mutex, held until the call ends, and of a store's slots the
+ * rows of the store they read (session_rep_rows), which outlive the scan. */
+struct ScanEntry {
+    std::lock_guard<std::mutex> lock;
+    std::vector<int> rows;
+    explicit ScanEntry(sbr_model* m) : lock(m->mu) {}
+    /* the set's entry (null: the catalogue), then the store's or the reader's, then the slots, then the lists: the order of refusal
+     * of every scan; `st` is r's store (null: another source) */
+    sbr_status enter(sbr_model* m, const sbr_item_set* set, sbr_sessions* st, const ScanRows& r, uint64_t n) {
+        if (set) SBRCHK(enter_item_set(set));
+        if (st) SBRCHK(enter_sessions(st));
+        else if (!set) SBRCHK(enter_reader(m)); /* a set's entry is the reader's already */
+        if (st) SBRCHK(check_slots(st, r.slots, n));
+        if (r.kind == ScanRows::Histories) SBRCHK(check_csr(m, r.user_ptr, n, r.item_ids, false));
+        else if (r.excl_ptr) SBRCHK(check_csr(m, r.excl_ptr, n, r.excl_items, false));
+        if (st) rows = session_rep_rows(st, r.slots, n);
+        return SBR_OK;
+    }
+};
+
+sbr_model* model_of(const sbr_sessions* st) { return st ? st->m : nullptr; } /* a null store is scan_call's to refuse */
+
+/* a store with memory takes sbr_recommend's flag, which ignores the memory for the call; one without refuses every flag */
+bool store_flags_ok(const sbr_sessions* st, uint32_t flags) {
+    return st->seen.w ? (flags & ~SBR_RECOMMEND_INCLUDE_HISTORY) == 0 : flags == 0;
+}
+
+/* Every call of the scan families, on the model (set null) or through an item set of it.  First what needs no device, so that a
+ * machine without one still answers SBR_ERR_INVALID_ARGUMENT and writes nothing; then ScanEntry's sequence under the model's
+ * mutex; then recommend_scan, whose own checks (tags or groups not set, ...) come last.  After success, and only then, the
+ * threshold and budget forms' *out_total and log_partition's *out_frac_bits — the model's F, with or without a set. */
+sbr_status scan_call(sbr_model* m, const sbr_item_set* set, const ScanRows& r, uint64_t n, uint32_t k, uint32_t* out_items, float* out_scores,
+                     ScanVariant v) {
+    if (!m || (n && !out_items && !v.pt && !v.ab) || !scan_k_ok(m, k, v.dv, v.cp)) return SBR_ERR_INVALID_ARGUMENT;
+    sbr_sessions* st = nullptr;
+    switch (r.kind) {
+    case ScanRows::Histories:
+        if (!r.user_ptr || (r.flags & ~SBR_RECOMMEND_INCLUDE_HISTORY)) return SBR_ERR_INVALID_ARGUMENT;
+        break;
+    case ScanRows::Reps:
+        if (n && !r.reps) return SBR_ERR_INVALID_ARGUMENT;
+        break;
+    case ScanRows::Store:
+        st = r.store;
+        if (!st || st->m != m || !store_flags_ok(st, r.flags)) return SBR_ERR_INVALID_ARGUMENT;
+        break;
+    }
+    if (r.kind != ScanRows::Histories && !excl_args_ok(r.excl_ptr, r.excl_items, n)) return SBR_ERR_INVALID_ARGUMENT;
+    ScanEntry e(m);
+    SBRCHK(e.enter(m, set, st, r, n));
+    const bool include = (r.flags & SBR_RECOMMEND_INCLUDE_HISTORY) != 0;
+    RepSource s;
+    if (r.kind == ScanRows::Histories) s = RepSource::of_histories(r.user_ptr, r.item_ids, 0, !include); /* the WHOLE history is masked (evaluation.rs:30-32) */
+    else if (r.kind == ScanRows::Reps) s = RepSource::of_rows(r.reps, r.excl_ptr, r.excl_items);
+    else s = RepSource::of_sessions(st, e.rows, r.excl_ptr, r.excl_items, st->seen.w && !include ? r.slots : nullptr);
+    if (st && v.sm) v.sm->fallback = r.slots; /* a session's default stream is its slot id */
+    TagFilterArg hold;
+    if (!v.flt) v.flt = sample_filter(r.any_of, r.none_of, &hold);
+    v.set = set;
+    SBRCHK(recommend_scan(m, s, n, k, out_items, out_scores, v));
+    if (v.ab) *v.ab->out_total = v.ab->total;
+    if (v.pt) *v.pt->out_frac_bits = sbr_softmax_fbits((uint32_t)m->hp.num_items);
+    return SBR_OK;
 }
 
 }  // namespace
 
 sbr_status sbr_sessions_recommend(sbr_sessions* st, const uint32_t* slots, uint64_t n, uint32_t k, const uint64_t* excl_ptr,
                                   const uint32_t* excl_items, uint32_t flags, uint32_t* out_items, float* out_scores) {
-    return sessions_recommend_call(st, slots, n, k, excl_ptr, excl_items, flags, out_items, out_scores, nullptr);
+    return scan_call(model_of(st), nullptr, ScanRows::of_store(st, slots, excl_ptr, excl_items, flags), n, k, out_items, out_scores,
+                     ScanVariant());
 }
 
 sbr_status sbr_sessions_recommend_filtered(sbr_sessions* st, const uint32_t* slots, uint64_t n, uint32_t k, const uint64_t* excl_ptr,
                                            const uint32_t* excl_items, uint32_t flags, const uint32_t* any_of, const uint32_t* none_of,
                                            uint32_t* out_items, float* out_scores) {
     const TagFilterArg flt{any_of, none_of};
-    return sessions_recommend_call(st, slots, n, k, excl_ptr, excl_items, flags, out_items, out_scores, &flt);
+    ScanVariant v;
+    v.flt = &flt;
+    return scan_call(model_of(st), nullptr, ScanRows::of_store(st, slots, excl_ptr, excl_items, flags), n, k, out_items, out_scores, v);
 }
 
 sbr_status sbr_sessions_recommend_sampled(sbr_sessions* st, const uint32_t* slots, uint64_t n, uint32_t k, const uint64_t* excl_ptr,
@@ -6120,65 +6175,60 @@ sbr_status sbr_sessions_recommend_sampled(sbr_sessions* st, const uint32_t* slot
                                           const uint32_t* any_of, const uint32_t* none_of, uint32_t* out_items, float* out_scores,
                                           float* out_keys) {
     Sample sm;
-    TagFilterArg hold;
     if (!sample_args(sample, out_keys, &sm)) return SBR_ERR_INVALID_ARGUMENT;
-    sm.fallback = slots; /* a session's default stream is its slot id */
-    return sessions_recommend_call(st, slots, n, k, excl_ptr, excl_items, flags, out_items, out_scores, sample_filter(any_of, none_of, &hold),
-                                   nullptr, &sm);
+    ScanVariant v;
+    v.sm = &sm;
+    return scan_call(model_of(st), nullptr, ScanRows::of_store(st, slots, excl_ptr, excl_items, flags, any_of, none_of), n, k, out_items, out_scores, v);
 }
 
 sbr_status sbr_sessions_log_partition(sbr_sessions* st, const uint32_t* slots, uint64_t n, const uint64_t* excl_ptr, const uint32_t* excl_items,
                                       uint32_t flags, float temperature, const uint32_t* any_of, const uint32_t* none_of, float* out_shift,
                                       uint64_t* out_mass, uint32_t* out_frac_bits) {
     Partition pt;
-    TagFilterArg hold;
-    if (!st || !partition_args(temperature, n, out_shift, out_mass, out_frac_bits, &pt)) return SBR_ERR_INVALID_ARGUMENT;
-    const sbr_status r = sessions_recommend_call(st, slots, n, 1, excl_ptr, excl_items, flags, nullptr, nullptr,
-                                                 sample_filter(any_of, none_of, &hold), nullptr, nullptr, &pt);
-    if (r == SBR_OK) *out_frac_bits = sbr_softmax_fbits((uint32_t)st->m->hp.num_items);
-    return r;
+    if (!partition_args(temperature, n, out_shift, out_mass, out_frac_bits, &pt)) return SBR_ERR_INVALID_ARGUMENT;
+    ScanVariant v;
+    v.pt = &pt;
+    return scan_call(model_of(st), nullptr, ScanRows::of_store(st, slots, excl_ptr, excl_items, flags, any_of, none_of), n, 1, nullptr, nullptr, v);
 }
 
 sbr_status sbr_sessions_recommend_above(sbr_sessions* st, const uint32_t* slots, uint64_t n, const float* thresholds, const uint64_t* excl_ptr,
                                         const uint32_t* excl_items, uint32_t flags, const uint32_t* any_of, const uint32_t* none_of,
                                         uint64_t* out_counts, uint64_t* out_total, uint64_t capacity, uint32_t* out_ids, float* out_scores) {
     Above ab;
-    TagFilterArg hold;
-    if (!st || !above_args(thresholds, n, out_counts, out_total, capacity, out_ids, out_scores, &ab)) return SBR_ERR_INVALID_ARGUMENT;
-    SBRCHK(sessions_recommend_call(st, slots, n, 1, excl_ptr, excl_items, flags, nullptr, nullptr, sample_filter(any_of, none_of, &hold), nullptr,
-                                   nullptr, nullptr, &ab));
-    *out_total = ab.total;
-    return SBR_OK;
+    if (!above_args(thresholds, n, out_counts, out_total, capacity, out_ids, out_scores, &ab)) return SBR_ERR_INVALID_ARGUMENT;
+    ScanVariant v;
+    v.ab = &ab;
+    return scan_call(model_of(st), nullptr, ScanRows::of_store(st, slots, excl_ptr, excl_items, flags, any_of, none_of), n, 1, nullptr, nullptr, v);
 }
 
 sbr_status sbr_sessions_recommend_top(sbr_sessions* st, const uint32_t* slots, uint64_t n, const uint64_t* top_n, const uint64_t* excl_ptr,
                                       const uint32_t* excl_items, uint32_t flags, const uint32_t* any_of, const uint32_t* none_of, float* out_cuts,
                                       uint64_t* out_counts, uint64_t* out_total, uint64_t capacity, uint32_t* out_ids, float* out_scores) {
     Above ab;
-    TagFilterArg hold;
-    if (!st || !top_args(top_n, n, out_cuts, out_counts, out_total, capacity, out_ids, out_scores, &ab)) return SBR_ERR_INVALID_ARGUMENT;
-    SBRCHK(sessions_recommend_call(st, slots, n, 1, excl_ptr, excl_items, flags, nullptr, nullptr, sample_filter(any_of, none_of, &hold), nullptr,
-                                   nullptr, nullptr, &ab));
-    *out_total = ab.total;
-    return SBR_OK;
+    if (!top_args(top_n, n, out_cuts, out_counts, out_total, capacity, out_ids, out_scores, &ab)) return SBR_ERR_INVALID_ARGUMENT;
+    ScanVariant v;
+    v.ab = &ab;
+    return scan_call(model_of(st), nullptr, ScanRows::of_store(st, slots, excl_ptr, excl_items, flags, any_of, none_of), n, 1, nullptr, nullptr, v);
 }
 
 sbr_status sbr_sessions_recommend_capped(sbr_sessions* st, const uint32_t* slots, uint64_t n, uint32_t k, const uint64_t* excl_ptr,
                                          const uint32_t* excl_items, uint32_t flags, const struct sbr_cap_args* cap, const uint32_t* any_of,
                                          const uint32_t* none_of, uint32_t* out_items, float* out_scores, uint8_t* out_complete) {
     Capped cp;
-    TagFilterArg hold;
     uint32_t pool = 0;
     if (!capped_args(cap, k, out_complete, &cp, &pool)) return SBR_ERR_INVALID_ARGUMENT;
-    return sessions_recommend_call(st, slots, n, pool, excl_ptr, excl_items, flags, out_items, out_scores, sample_filter(any_of, none_of, &hold),
-                                   nullptr, nullptr, nullptr, nullptr, &cp);
+    ScanVariant v;
+    v.cp = &cp;
+    return scan_call(model_of(st), nullptr, ScanRows::of_store(st, slots, excl_ptr, excl_items, flags, any_of, none_of), n, pool, out_items, out_scores, v);
 }
 
 sbr_status sbr_sessions_recommend_diverse(sbr_sessions* st, const uint32_t* slots, uint64_t n, uint32_t k, uint32_t pool, float trade_off,
                                           uint32_t metric, const uint64_t* excl_ptr, const uint32_t* excl_items, uint32_t* out_items,
                                           float* out_scores) {
     const Diverse dv{k, trade_off, metric};
-    return sessions_recommend_call(st, slots, n, pool, excl_ptr, excl_items, 0, out_items, out_scores, nullptr, &dv);
+    ScanVariant v;
+    v.dv = &dv;
+    return scan_call(model_of(st), nullptr, ScanRows::of_store(st, slots, excl_ptr, excl_items, 0), n, pool, out_items, out_scores, v);
 }
 
 sbr_status sbr_sessions_recommend_diverse_filtered(sbr_sessions* st, const uint32_t* slots, uint64_t n, uint32_t k, uint32_t pool,
@@ -6186,7 +6236,10 @@ sbr_status sbr_sessions_recommend_diverse_filtered(sbr_sessions* st, const uint3
                                                    const uint32_t* any_of, const uint32_t* none_of, uint32_t* out_items, float* out_scores) {
     const TagFilterArg flt{any_of, none_of};
     const Diverse dv{k, trade_off, metric};
-    return sessions_recommend_call(st, slots, n, pool, excl_ptr, excl_items, 0, out_items, out_scores, &flt, &dv);
+    ScanVariant v;
+    v.dv = &dv;
+    v.flt = &flt;
+    return scan_call(model_of(st), nullptr, ScanRows::of_store(st, slots, excl_ptr, excl_items, 0), n, pool, out_items, out_scores, v);
 }
 
 /* ---------------------------------------------------------------------------------------------
@@ -6194,13 +6247,105 @@ sbr_status sbr_sessions_recommend_diverse_filtered(sbr_sessions* st, const uint3
  * ------------------------------------------------------------------------------------------- */
 namespace {
 
-/* what a rollout call asks for beside its slots and lists; the outputs are host arrays over the call's rows, null: not wanted */
-struct RolloutCall {
-    uint32_t steps;
+/* What a rollout and a beam-search call share: the store's rows (slots, their optional lists, rep0 = session_rep_rows), the set
+ * (null: the catalogue), and what steps_call makes of the args' steps, flags and masks. */
+struct StepsCall {
+    const sbr_item_set* set;
+    const uint32_t* slots;
+    const uint64_t* excl_ptr;
+    const uint32_t* excl_items;
+    const std::vector<int>* rep0;
+    uint32_t steps, w;       /* w: the beam width; a rollout's 1 */
     bool allow_repeats, seen;
-    const Sample* sm;        /* null: greedy */
     const TagFilterArg* flt; /* null: no filter */
-    float inv_t;             /* the partition's, = sm->inv_t in sample mode */
+    float inv_t;             /* the partition's */
+};
+
+/* The half of a chunk the two share — rows [c0, c0 + nu) of the call, `nrows` of them on the device (a rollout's nu, a beam
+ * search's nu W): the caller's lists, the tight exclusion CSR `src` (the seen lists merged with the caller's, as positions of the
+ * set) that the steps' own segments are spread from, the slots, the identity rows of the scratch states, the set's tag words, and
+ * the tail.  What differs — the scan's buffers, the rows' records and the per-step loop — stays with the two chunk functions. */
+struct StepsChunk {
+    sbr_sessions* st;
+    sbr_model* m;
+    const StepsCall& sc;
+    const SetView sv;
+    const size_t c0, nu, nrows, seen_w;
+    const uint32_t slack;  /* room per row for the picks to come, which the steps exclude unless repeats are allowed */
+    UserBatch ub;          /* the caller's lists of the chunk's rows, sorted and de-duplicated */
+    size_t ncaller = 0, nsrc = 0;
+    bool excl = false;     /* without lists, memory or slack nothing is ever excluded */
+    uint64_t* src_ptr = nullptr;
+    uint32_t *src = nullptr, *seen_caller = nullptr, *d_slot = nullptr, *d_ident = nullptr, *set_tags = nullptr;
+    unsigned long long* d_start = nullptr;
+    /* read by asynchronous copies: they live until finish() has drained the stream */
+    std::vector<uint64_t> h_src_ptr;
+    std::vector<uint32_t> h_ident, masks, masks_rows;
+    std::vector<unsigned long long> h_start;
+
+    StepsChunk(sbr_sessions* st_, const StepsCall& sc_, size_t c0_, size_t nu_, size_t nrows_)
+        : st(st_), m(st_->m), sc(sc_), sv(st_->m, sc_.set), c0(c0_), nu(nu_), nrows(nrows_), seen_w(sc_.seen ? st_->seen.w : 0),
+          slack(sc_.allow_repeats ? 0u : sc_.steps) {
+        if (sc.excl_ptr) {
+            std::vector<const uint32_t*> list(nu);
+            std::vector<uint64_t> n(nu);
+            for (size_t i = 0; i < nu; ++i) {
+                list[i] = sc.excl_items ? sc.excl_items + sc.excl_ptr[c0 + i] : nullptr;
+                n[i] = sc.excl_ptr[c0 + i + 1] - sc.excl_ptr[c0 + i];
+            }
+            prepare_users(list, n, m->hp.max_sequence_length, true, &ub);
+        }
+        ncaller = ub.list_items.size();
+        nsrc = nu * seen_w + ncaller;
+        excl = sc.excl_ptr || seen_w || slack;
+    }
+    const uint32_t* tags() const { return !sc.flt ? nullptr : sc.set ? set_tags : m->item_tags; }
+    void carve(DeviceArena& ar) {
+        if (sc.set && sc.flt) set_tags = ar.take<uint32_t>(sv.scanned);
+        src_ptr = ar.take<uint64_t>(nu + 1);
+        src = ar.take<uint32_t>(nsrc + 1);
+        if (seen_w) seen_caller = ar.take<uint32_t>(ncaller + 1);
+        d_slot = ar.take<uint32_t>(nu);
+        d_ident = ar.take<uint32_t>(nrows);
+        d_start = ar.take<unsigned long long>(nrows);
+    }
+    /* the uploads: the rows' representations' rows to d_rep, the slots, the identities and the tight CSR */
+    sbr_status upload(int* d_rep) {
+        h_src_ptr.resize(nu + 1);
+        h_ident.resize(nrows);
+        h_start.resize(nrows);
+        for (size_t i = 0; i <= nu; ++i) h_src_ptr[i] = i * seen_w + (ub.list_ptr.empty() ? 0 : ub.list_ptr[i]);
+        for (size_t i = 0; i < nrows; ++i) { h_ident[i] = (uint32_t)i; h_start[i] = i; }
+        HIPCHK(hipMemcpyAsync(d_rep, sc.rep0->data() + c0, nu * 4, hipMemcpyHostToDevice, m->stream));
+        HIPCHK(hipMemcpyAsync(d_slot, sc.slots + c0, nu * 4, hipMemcpyHostToDevice, m->stream));
+        HIPCHK(hipMemcpyAsync(d_ident, h_ident.data(), nrows * 4, hipMemcpyHostToDevice, m->stream));
+        HIPCHK(hipMemcpyAsync(d_start, h_start.data(), nrows * 8, hipMemcpyHostToDevice, m->stream));
+        if (excl) SBRCHK(upload_csr(m, src_ptr, h_src_ptr, seen_w ? seen_caller : src, ub.list_items));
+        return SBR_OK;
+    }
+    /* what runs ahead of the steps' own segments: the seen lists, and for a set the lists as positions and its tag words */
+    int prelaunch() {
+        int n = seen_w ? sbr::launch_session_seen_lists(st->seen, d_slot, (int)nu, src_ptr, seen_caller, src, m->stream) : 0;
+        if (sc.set && !sv.none && nsrc) n += sbr::launch_subset_positions(sc.set->d_ids, sv.ns, src_ptr, (uint32_t)nu, src, m->stream);
+        if (set_tags && !sv.none) n += sbr::launch_subset_words(sc.set->d_ids, sv.ns, m->item_tags, set_tags, m->stream);
+        return n;
+    }
+    /* the tail, as scan_launch's: the stream drained, the flag — a non-finite score at any step fails the whole call — and the results */
+    sbr_status finish(const uint32_t* d_flag, std::initializer_list<CopyOut> outs) {
+        HIPCHK(hipGetLastError());
+        uint32_t flag = 0;
+        HIPCHK(hipStreamSynchronize(m->stream));
+        HIPCHK(hipMemcpy(&flag, d_flag, 4, hipMemcpyDeviceToHost));
+        if (flag) return SBR_ERR_INVALID_PREDICTION;
+        for (const CopyOut& o : outs)
+            if (o.host) HIPCHK(hipMemcpy(o.host, o.device, o.bytes, hipMemcpyDeviceToHost));
+        return SBR_OK;
+    }
+};
+
+/* what a rollout call asks for beside StepsCall; the outputs are host arrays over the call's rows, null: not wanted */
+struct RolloutCall : StepsCall {
+    const Sample* sm;        /* null: greedy; inv_t = sm->inv_t in sample mode */
     uint32_t* out_items;
     float *out_scores, *out_keys;
     uint32_t* out_lengths;
@@ -6213,15 +6358,10 @@ struct RolloutCall {
  * exclusion segment with the slack, twice (the tight lists it is spread from), its columns of the outputs and its scratch state —
  * keeps the chunk within 256 MB.  SBR_ROLLOUT_CHUNK=n (n >= 1) is a TEST HOOK read per call that replaces both, after
  * SBR_SESSIONS_REPLAY_CHUNK. */
-size_t rollout_chunk_cap(const sbr_model* m, uint32_t w, uint32_t steps) {
+size_t rollout_chunk_cap(const sbr_model* m, uint32_t w, uint32_t /* beam width */, uint32_t steps) {
     constexpr size_t budget = (size_t)256 << 20;
     const size_t per = ((size_t)w + steps) * 8 + (size_t)steps * 24 + (size_t)m->d * 16 + 64;
-    size_t cap = std::min(recommend_users_cap((uint32_t)m->hp.num_items, 1), std::max<size_t>(budget / per, 1));
-    if (const char* e = std::getenv("SBR_ROLLOUT_CHUNK")) {
-        const long long v = std::atoll(e);
-        if (v >= 1) cap = (size_t)v;
-    }
-    return cap;
+    return chunk_override("SBR_ROLLOUT_CHUNK", std::min(recommend_users_cap((uint32_t)m->hp.num_items, 1), std::max<size_t>(budget / per, 1)));
 }
 
 /* One chunk, rows [c0, c0 + nu) of the call: the scratch state and the exclusion CSR with slack, then per step the unchanged k = 1
@@ -6230,55 +6370,27 @@ size_t rollout_chunk_cap(const sbr_model* m, uint32_t w, uint32_t steps) {
  * With `set` (current; null: the catalogue) the scans run over its sub-table as recommend_scan's do: the tight exclusion CSR becomes
  * positions of the set before it is spread, the set's tag words are gathered once per chunk, F is the model's and the noise is
  * hashed from the catalogue ids; the advance turns the picks into ids.  An empty set runs no scan: every pick is padding. */
-sbr_status sessions_rollout_chunk(sbr_sessions* st, const uint32_t* slots, const std::vector<int>& rep0, const uint64_t* excl_ptr,
-                                  const uint32_t* excl_items, const RolloutCall& rc, const sbr_item_set* set, size_t c0, size_t nu) {
+sbr_status sessions_rollout_chunk(sbr_sessions* st, const StepsCall& call, size_t c0, size_t nu) {
+    const RolloutCall& rc = static_cast<const RolloutCall&>(call);
     sbr_model* m = st->m;
-    const bool none = set && set->ids.empty();
-    const uint32_t ns = set ? (uint32_t)set->ids.size() : 0u;
-    const uint32_t scanned = set ? std::max(ns, 1u) : (uint32_t)m->hp.num_items; /* what the scan's buffers are carved for */
-    sbr::ModelView cat = m->mv; /* what the scans read: the catalogue, or the set's sub-table, whose item j is S[j] */
-    if (set && !none) {
-        cat.E = set->E;
-        cat.b = set->b;
-        cat.num_items = ns;
-    }
+    StepsChunk f(st, rc, c0, nu, nu);
+    const sbr_item_set* set = rc.set;
+    const sbr::ModelView& cat = f.sv.cat; /* what the scans read */
+    const bool none = f.sv.none, excl = f.excl;
+    const uint32_t slack = f.slack;
     const size_t d = (size_t)m->d, dl = (size_t)m->dl, S = rc.steps;
     const bool lstm = m->ng != 0, sample = rc.sm != nullptr, part = rc.out_shift != nullptr;
     const bool final_state = rc.out_h != nullptr;
-    const size_t seen_w = rc.seen ? st->seen.w : 0;
-    const uint32_t slack = rc.allow_repeats ? 0u : rc.steps;
-    UserBatch ub; /* the caller's lists of the chunk's rows, sorted and de-duplicated */
-    if (excl_ptr) {
-        std::vector<const uint32_t*> list(nu);
-        std::vector<uint64_t> n(nu);
-        for (size_t i = 0; i < nu; ++i) {
-            list[i] = excl_items ? excl_items + excl_ptr[c0 + i] : nullptr;
-            n[i] = excl_ptr[c0 + i + 1] - excl_ptr[c0 + i];
-        }
-        prepare_users(list, n, m->hp.max_sequence_length, true, &ub);
-    }
-    const size_t ncaller = ub.list_items.size();
-    const size_t nsrc = nu * seen_w + ncaller, nexcl = nsrc + nu * slack;
-    const bool excl = excl_ptr || seen_w || slack; /* without any of them nothing is ever excluded */
     TopkBufs tb;
     SampleBufs smb{};
     sbr::RolloutRows rr{};
     sbr::RolloutOut ro{};
-    uint64_t* src_ptr = nullptr;
-    uint32_t *src = nullptr, *seen_caller = nullptr, *d_slot = nullptr, *d_ident = nullptr, *pt_items = nullptr;
-    unsigned long long* d_start = nullptr;
+    uint32_t* pt_items = nullptr;
     float *pt_scores = nullptr, *pt_shift = nullptr, *fin_h = nullptr, *fin_c = nullptr;
     unsigned long long* pt_mass = nullptr;
-    uint32_t* set_tags = nullptr; /* set: its tag words, gathered by this chunk */
     SBRCHK(carve_arena(m, [&](DeviceArena& ar) {
-        tb.carve(ar, scanned, nu, nexcl, 1, rc.flt != nullptr);
-        if (set && rc.flt) set_tags = ar.take<uint32_t>(scanned);
-        src_ptr = ar.take<uint64_t>(nu + 1);
-        src = ar.take<uint32_t>(nsrc + 1);
-        if (seen_w) seen_caller = ar.take<uint32_t>(ncaller + 1);
-        d_slot = ar.take<uint32_t>(nu);
-        d_ident = ar.take<uint32_t>(nu);
-        d_start = ar.take<unsigned long long>(nu);
+        tb.carve(ar, f.sv.scanned, nu, f.nsrc + nu * slack, 1, rc.flt != nullptr);
+        f.carve(ar);
         rr.Hs = ar.take<float>((lstm ? 2 : 1) * nu * d);
         if (lstm) rr.Cs = ar.take<float>(2 * nu * d);
         rr.len = ar.take<unsigned long long>(nu);
@@ -6303,42 +6415,22 @@ sbr_status sessions_rollout_chunk(sbr_sessions* st, const uint32_t* slots, const
         }
     }));
     /* the host vectors below are read by asynchronous copies: they live until the stream is drained at the end */
-    std::vector<uint64_t> h_src_ptr(nu + 1), h_eptr(nu + 1);
-    std::vector<uint32_t> h_ident(nu);
-    std::vector<unsigned long long> h_start(nu);
-    for (size_t i = 0; i <= nu; ++i) {
-        h_src_ptr[i] = i * seen_w + (ub.list_ptr.empty() ? 0 : ub.list_ptr[i]);
-        h_eptr[i] = h_src_ptr[i] + i * slack;
-    }
-    for (size_t i = 0; i < nu; ++i) { h_ident[i] = (uint32_t)i; h_start[i] = i; }
-    HIPCHK(hipMemcpyAsync(tb.rep, rep0.data() + c0, nu * 4, hipMemcpyHostToDevice, m->stream));
-    HIPCHK(hipMemcpyAsync(d_slot, slots + c0, nu * 4, hipMemcpyHostToDevice, m->stream));
-    HIPCHK(hipMemcpyAsync(d_ident, h_ident.data(), nu * 4, hipMemcpyHostToDevice, m->stream));
-    HIPCHK(hipMemcpyAsync(d_start, h_start.data(), nu * 8, hipMemcpyHostToDevice, m->stream));
-    if (excl) {
+    SBRCHK(f.upload(tb.rep));
+    std::vector<uint64_t> h_eptr(nu + 1), streams;
+    if (excl) { /* each row's tight list and its slack */
+        for (size_t i = 0; i <= nu; ++i) h_eptr[i] = f.h_src_ptr[i] + i * slack;
         HIPCHK(hipMemcpyAsync(tb.eptr, h_eptr.data(), (nu + 1) * 8, hipMemcpyHostToDevice, m->stream));
-        SBRCHK(upload_csr(m, src_ptr, h_src_ptr, seen_w ? seen_caller : src, ub.list_items));
     }
-    std::vector<uint32_t> masks; /* the chunk's rows' any_of, then their none_of */
-    if (rc.flt) {
-        masks.assign(2 * nu, 0u);
-        for (size_t i = 0; i < nu; ++i) {
-            if (rc.flt->any_of) masks[i] = rc.flt->any_of[c0 + i];
-            if (rc.flt->none_of) masks[nu + i] = rc.flt->none_of[c0 + i];
-        }
-        HIPCHK(hipMemcpyAsync(tb.any_of, masks.data(), nu * 4, hipMemcpyHostToDevice, m->stream));
-        HIPCHK(hipMemcpyAsync(tb.none_of, masks.data() + nu, nu * 4, hipMemcpyHostToDevice, m->stream));
-    }
-    std::vector<uint64_t> streams;
+    if (rc.flt) SBRCHK(upload_masks(m, *rc.flt, nullptr, c0, nu, 1, tb.any_of, tb.none_of, &f.masks));
     if (sample) {
         streams.resize(nu);
-        for (size_t i = 0; i < nu; ++i) streams[i] = rc.sm->streams ? rc.sm->streams[c0 + i] : (uint64_t)slots[c0 + i];
+        for (size_t i = 0; i < nu; ++i) streams[i] = rc.sm->streams ? rc.sm->streams[c0 + i] : (uint64_t)rc.slots[c0 + i];
         HIPCHK(hipMemcpyAsync(smb.streams, streams.data(), nu * 8, hipMemcpyHostToDevice, m->stream));
     }
     rr.n = (int)nu; rr.steps = rc.steps;
-    rr.slot = d_slot; rr.ident = d_ident; rr.start = d_start;
+    rr.slot = f.d_slot; rr.ident = f.d_ident; rr.start = f.d_start;
     /* the step's scan: the pick's descriptor, and with the partition in sample mode a second one whose k = 1 scan is the plain one */
-    sbr::TopkScan sc = tb.scan(nu, 1, excl, true, !rc.flt ? nullptr : set ? set_tags : m->item_tags);
+    sbr::TopkScan sc = tb.scan(nu, 1, excl, true, f.tags());
     sbr::TopkScan sc_pt = sc;
     if (sample) {
         sc.g = sbr::SampleNoise{rc.sm->inv_t, smb.keys};
@@ -6347,23 +6439,20 @@ sbr_status sessions_rollout_chunk(sbr_sessions* st, const uint32_t* slots, const
     }
     /* a set's picks leave as ids: the plain scan's are positions, the sampled launch's already ids */
     const sbr::RolloutPick pick{tb.items, sample ? smb.plain : tb.scores, sample ? tb.scores : nullptr, pt_shift, pt_mass,
-                                none ? nullptr : set ? set->d_ids : nullptr, ns, sample};
+                                none ? nullptr : set ? set->d_ids : nullptr, f.sv.ns, sample};
     const size_t parity_stride = nu * d;
     HIPCHK(hipMemsetAsync(tb.flag, 0, 4, m->stream));
     if (none) HIPCHK(hipMemsetAsync(tb.items, 0xFF, nu * 4, m->stream)); /* nothing to scan: every step's pick is padding */
     {
         ScopedTimer t(m, SBR_K_RANK, 0);
-        int n = sbr::launch_rollout_begin(m->mv, st->v, rr, m->stream);
-        if (seen_w) n += sbr::launch_session_seen_lists(st->seen, d_slot, (int)nu, src_ptr, seen_caller, src, m->stream);
-        if (set && !none && nsrc) n += sbr::launch_subset_positions(set->d_ids, ns, src_ptr, (uint32_t)nu, src, m->stream);
-        if (set_tags && !none) n += sbr::launch_subset_words(set->d_ids, ns, m->item_tags, set_tags, m->stream);
-        if (excl) n += sbr::launch_rollout_segments(src_ptr, src, (int)nu, slack, tb.excl, m->stream);
+        int n = sbr::launch_rollout_begin(m->mv, st->v, rr, m->stream) + f.prelaunch();
+        if (excl) n += sbr::launch_rollout_segments(f.src_ptr, f.src, (int)nu, slack, tb.excl, m->stream);
         t.tp.launches = (uint64_t)n;
     }
     for (uint32_t j = 0; j < rc.steps; ++j) {
         /* step 0 scans the store's rows in place (an empty slot: the empty-history row); later steps the scratch the step before wrote */
         const float* reps = j == 0 ? st->v.H : lstm ? rr.Hs + (size_t)((j - 1) & 1u) * parity_stride : rr.Hs;
-        sc.rep_row = sc_pt.rep_row = j == 0 ? tb.rep : reinterpret_cast<const int*>(d_ident);
+        sc.rep_row = sc_pt.rep_row = j == 0 ? tb.rep : reinterpret_cast<const int*>(f.d_ident);
         {
             ScopedTimer t(m, SBR_K_RANK, 0);
             int n = 0;
@@ -6385,68 +6474,66 @@ sbr_status sessions_rollout_chunk(sbr_sessions* st, const uint32_t* slots, const
     if (final_state) { /* the first embedding_dim columns of the rows after the last step */
         const sbr::SessionView fin{lstm ? rr.Hs + (size_t)((rc.steps - 1) & 1u) * parity_stride : rr.Hs,
                                    lstm ? rr.Cs + (size_t)((rc.steps - 1) & 1u) * parity_stride : nullptr, nullptr};
-        sbr::launch_session_get_state(fin, d_ident, (int)nu, m->d, m->dl, fin_h, fin_c, nullptr, m->stream);
+        sbr::launch_session_get_state(fin, f.d_ident, (int)nu, m->d, m->dl, fin_h, fin_c, nullptr, m->stream);
     }
-    HIPCHK(hipGetLastError());
-    uint32_t flag = 0;
-    HIPCHK(hipStreamSynchronize(m->stream));
-    HIPCHK(hipMemcpy(&flag, tb.flag, 4, hipMemcpyDeviceToHost));
-    if (flag) return SBR_ERR_INVALID_PREDICTION; /* a non-finite score at any step fails the whole call */
-    const CopyOut outs[] = {{rc.out_items + c0 * S, ro.items, nu * S * 4},
-                            {rc.out_scores ? rc.out_scores + c0 * S : nullptr, ro.scores, nu * S * 4},
-                            {rc.out_keys ? rc.out_keys + c0 * S : nullptr, ro.keys, nu * S * 4},
-                            {rc.out_lengths ? rc.out_lengths + c0 : nullptr, rr.lengths, nu * 4},
-                            {part ? rc.out_shift + c0 * S : nullptr, ro.shift, nu * S * 4},
-                            {part ? rc.out_mass + c0 * S : nullptr, ro.mass, nu * S * 8},
-                            {rc.out_h ? rc.out_h + c0 * dl : nullptr, fin_h, nu * dl * 4},
-                            {rc.out_c ? rc.out_c + c0 * dl : nullptr, fin_c, nu * dl * 4}};
-    for (const CopyOut& o : outs)
-        if (o.host) HIPCHK(hipMemcpy(o.host, o.device, o.bytes, hipMemcpyDeviceToHost));
-    return SBR_OK;
+    return f.finish(tb.flag, {{rc.out_items + c0 * S, ro.items, nu * S * 4},
+                              {rc.out_scores ? rc.out_scores + c0 * S : nullptr, ro.scores, nu * S * 4},
+                              {rc.out_keys ? rc.out_keys + c0 * S : nullptr, ro.keys, nu * S * 4},
+                              {rc.out_lengths ? rc.out_lengths + c0 : nullptr, rr.lengths, nu * 4},
+                              {part ? rc.out_shift + c0 * S : nullptr, ro.shift, nu * S * 4},
+                              {part ? rc.out_mass + c0 * S : nullptr, ro.mass, nu * S * 8},
+                              {rc.out_h ? rc.out_h + c0 * dl : nullptr, fin_h, nu * dl * 4},
+                              {rc.out_c ? rc.out_c + c0 * dl : nullptr, fin_c, nu * dl * 4}});
 }
 
-sbr_status enter_item_set(const sbr_item_set* set);
+/* The entry rollout_call and beam_call share, behind their own argument checks (st and its call's set, slots and lists are the
+ * caller's, checked non-null where they must be): the steps and the flag bits, include_seen without memory, the lists' pairing;
+ * ScanEntry's sequence under the model's mutex; the filter, which needs the model's tags; then `chunk` over the rows, `cap` of them
+ * at a time, and *out_frac_bits (null: not wanted) — the model's F, with or without a set. */
+sbr_status steps_call(sbr_sessions* st, StepsCall* sc, uint64_t n, uint32_t steps, uint32_t flags, uint32_t known, const uint32_t* any_of,
+                      const uint32_t* none_of, size_t (*cap)(const sbr_model*, uint32_t seen_w, uint32_t w, uint32_t steps),
+                      sbr_status (*chunk)(sbr_sessions*, const StepsCall&, size_t c0, size_t nu), uint32_t* out_frac_bits) {
+    if (steps < 1 || steps > SBR_ROLLOUT_MAX_STEPS || (flags & ~known)) return SBR_ERR_INVALID_ARGUMENT;
+    if ((flags & SBR_ROLLOUT_INCLUDE_SEEN) && !st->seen.w) return SBR_ERR_INVALID_ARGUMENT; /* nothing to include */
+    if (!excl_args_ok(sc->excl_ptr, sc->excl_items, n)) return SBR_ERR_INVALID_ARGUMENT;
+    sbr_model* m = st->m;
+    ScanEntry e(m);
+    SBRCHK(e.enter(m, sc->set, st, ScanRows::of_store(st, sc->slots, sc->excl_ptr, sc->excl_items, 0), n));
+    TagFilterArg hold;
+    sc->flt = sample_filter(any_of, none_of, &hold);
+    if (sc->flt && !m->item_tags) return SBR_ERR_INVALID_ARGUMENT;
+    sc->rep0 = &e.rows;
+    sc->steps = steps;
+    sc->allow_repeats = (flags & SBR_ROLLOUT_ALLOW_REPEATS) != 0;
+    sc->seen = st->seen.w && !(flags & SBR_ROLLOUT_INCLUDE_SEEN);
+    const size_t per = cap(m, sc->seen ? st->seen.w : 0, sc->w, steps);
+    for (size_t c0 = 0; c0 < n; c0 += per) SBRCHK(chunk(st, *sc, c0, std::min<size_t>(per, n - c0)));
+    if (out_frac_bits) *out_frac_bits = sbr_softmax_fbits((uint32_t)m->hp.num_items);
+    return SBR_OK;
+}
 
 /* sbr_sessions_rollout, or (set non-null: the caller checked that it is the store's model's) sbr_item_set_rollout */
 sbr_status rollout_call(sbr_sessions* st, const sbr_item_set* set, const uint32_t* slots, uint64_t n, const struct sbr_rollout_args* args,
                         const uint64_t* excl_ptr, const uint32_t* excl_items, const uint32_t* any_of, const uint32_t* none_of,
                         uint32_t* out_items, float* out_scores, float* out_keys, uint32_t* out_lengths, float* out_shift,
                         uint64_t* out_mass, uint32_t* out_frac_bits, float* out_h, float* out_c) {
-    constexpr uint32_t known = SBR_ROLLOUT_SAMPLE | SBR_ROLLOUT_ALLOW_REPEATS | SBR_ROLLOUT_INCLUDE_SEEN;
     if (!st || !args || (n && !out_items)) return SBR_ERR_INVALID_ARGUMENT;
-    if (args->steps < 1 || args->steps > SBR_ROLLOUT_MAX_STEPS || (args->flags & ~known)) return SBR_ERR_INVALID_ARGUMENT;
     const bool sample = (args->flags & SBR_ROLLOUT_SAMPLE) != 0;
     Sample sm;
-    TagFilterArg hold;
     if (!sample_args(&args->sample, out_keys, &sm)) return SBR_ERR_INVALID_ARGUMENT;
     if (!sample && out_keys) return SBR_ERR_INVALID_ARGUMENT; /* a greedy pick has no key */
     if ((out_shift != nullptr) != (out_mass != nullptr) || (out_shift && !out_frac_bits)) return SBR_ERR_INVALID_ARGUMENT;
-    if ((args->flags & SBR_ROLLOUT_INCLUDE_SEEN) && !st->seen.w) return SBR_ERR_INVALID_ARGUMENT; /* nothing to include */
-    if (out_c && (!out_h || !st->m->ng)) return SBR_ERR_INVALID_ARGUMENT;                         /* c: the LSTM's, with h */
+    if (out_c && (!out_h || !st->m->ng)) return SBR_ERR_INVALID_ARGUMENT; /* c: the LSTM's, with h */
     if (out_h && st->m->ng && !out_c) return SBR_ERR_INVALID_ARGUMENT;
-    if (!excl_args_ok(excl_ptr, excl_items, n)) return SBR_ERR_INVALID_ARGUMENT;
-    sbr_model* m = st->m;
-    std::lock_guard<std::mutex> lock(m->mu);
-    if (set) SBRCHK(enter_item_set(set));
-    SBRCHK(enter_sessions(st));
-    SBRCHK(check_slots(st, slots, n));
-    if (excl_ptr) SBRCHK(check_csr(m, excl_ptr, n, excl_items, false));
     RolloutCall rc{};
-    rc.steps = args->steps;
-    rc.allow_repeats = (args->flags & SBR_ROLLOUT_ALLOW_REPEATS) != 0;
-    rc.seen = st->seen.w && !(args->flags & SBR_ROLLOUT_INCLUDE_SEEN);
+    rc.set = set; rc.slots = slots; rc.excl_ptr = excl_ptr; rc.excl_items = excl_items;
+    rc.w = 1;
     rc.sm = sample ? &sm : nullptr;
-    rc.flt = sample_filter(any_of, none_of, &hold);
-    if (rc.flt && !m->item_tags) return SBR_ERR_INVALID_ARGUMENT;
     rc.inv_t = sm.inv_t;
     rc.out_items = out_items; rc.out_scores = out_scores; rc.out_keys = out_keys; rc.out_lengths = out_lengths;
     rc.out_shift = out_shift; rc.out_mass = out_mass; rc.out_h = out_h; rc.out_c = out_c;
-    const std::vector<int> rep0 = session_rep_rows(st, slots, n);
-    const size_t cap = rollout_chunk_cap(m, rc.seen ? st->seen.w : 0, rc.steps);
-    for (size_t c0 = 0; c0 < n; c0 += cap)
-        SBRCHK(sessions_rollout_chunk(st, slots, rep0, excl_ptr, excl_items, rc, set, c0, std::min<size_t>(cap, n - c0)));
-    if (out_frac_bits) *out_frac_bits = sbr_softmax_fbits((uint32_t)m->hp.num_items); /* the model's, with or without a set */
-    return SBR_OK;
+    return steps_call(st, &rc, n, args->steps, args->flags, SBR_ROLLOUT_SAMPLE | SBR_ROLLOUT_ALLOW_REPEATS | SBR_ROLLOUT_INCLUDE_SEEN, any_of,
+                      none_of, rollout_chunk_cap, sessions_rollout_chunk, out_frac_bits);
 }
 
 }  // namespace
@@ -6464,12 +6551,8 @@ sbr_status sbr_sessions_rollout(sbr_sessions* st, const uint32_t* slots, uint64_
  * ------------------------------------------------------------------------------------------- */
 namespace {
 
-/* what a beam-search call asks for beside its slots and lists; the outputs are host arrays over the call's rows, null: not wanted */
-struct BeamCall {
-    uint32_t steps, w;
-    bool allow_repeats, seen;
-    const TagFilterArg* flt; /* null: no filter */
-    float inv_t;
+/* what a beam-search call asks for beside StepsCall; the outputs are host arrays over the call's rows, null: not wanted */
+struct BeamCall : StepsCall {
     uint32_t* out_items;
     float *out_scores, *out_lp, *out_cum;
     uint32_t *out_lengths, *out_beams;
@@ -6484,12 +6567,7 @@ struct BeamCall {
 size_t sessions_beam_chunk(const sbr_model* m, uint32_t seen_w, uint32_t w, uint32_t steps) {
     constexpr size_t budget = (size_t)256 << 20;
     const size_t per = (size_t)w * (((size_t)seen_w + steps) * 8 + (size_t)steps * 56 + (size_t)m->d * 16 + 128) + (size_t)seen_w * 8 + 64;
-    size_t cap = std::max<size_t>(std::min(recommend_users_cap((uint32_t)m->hp.num_items, w) / w, budget / per), 1);
-    if (const char* e = std::getenv("SBR_BEAM_CHUNK")) {
-        const long long v = std::atoll(e);
-        if (v >= 1) cap = (size_t)v;
-    }
-    return cap;
+    return chunk_override("SBR_BEAM_CHUNK", std::max<size_t>(std::min(recommend_users_cap((uint32_t)m->hp.num_items, w) / w, budget / per), 1));
 }
 
 /* One chunk, rows [c0, c0 + nu) of the call, nb = nu W beam rows: the tight exclusion lists and the segment CSR, then per step the
@@ -6499,55 +6577,34 @@ size_t sessions_beam_chunk(const sbr_model* m, uint32_t seen_w, uint32_t w, uint
  * With `set` (current; null: the catalogue) the scans run over its sub-table as recommend_scan's do: the tight lists become positions
  * of the set before any segment is made from them, the set's tag words are gathered once per chunk, F is the model's; the selection
  * feeds and records ids and merges positions.  An empty set runs no scan: every row ends at step 0. */
-sbr_status sessions_beam_chunk_run(sbr_sessions* st, const uint32_t* slots, const std::vector<int>& rep0, const uint64_t* excl_ptr,
-                                   const uint32_t* excl_items, const BeamCall& bc, const sbr_item_set* set, size_t c0, size_t nu) {
+sbr_status sessions_beam_chunk_run(sbr_sessions* st, const StepsCall& call, size_t c0, size_t nu) {
+    const BeamCall& bc = static_cast<const BeamCall&>(call);
     sbr_model* m = st->m;
     const size_t d = (size_t)m->d, S = bc.steps, W = bc.w, nb = nu * W;
-    const uint32_t num_items = (uint32_t)m->hp.num_items;
-    const bool none = set && set->ids.empty();
-    const uint32_t ns = set ? (uint32_t)set->ids.size() : 0u;
-    const uint32_t scanned = set ? std::max(ns, 1u) : num_items; /* what the scan's buffers are carved for */
-    sbr::ModelView cat = m->mv; /* what the scans read: the catalogue, or the set's sub-table, whose item j is S[j] */
-    if (set && !none) {
-        cat.E = set->E;
-        cat.b = set->b;
-        cat.num_items = ns;
-    }
+    StepsChunk f(st, bc, c0, nu, nb);
+    const sbr_item_set* set = bc.set;
+    const uint32_t num_items = (uint32_t)m->hp.num_items, scanned = f.sv.scanned, slack = f.slack;
+    const sbr::ModelView& cat = f.sv.cat; /* what the scans read */
+    const bool none = f.sv.none, excl = f.excl;
     const bool lstm = m->ng != 0, part_out = bc.out_shift != nullptr;
-    const size_t seen_w = bc.seen ? st->seen.w : 0;
-    const uint32_t slack = bc.allow_repeats ? 0u : bc.steps;
-    UserBatch ub; /* the caller's lists of the chunk's rows, sorted and de-duplicated */
-    if (excl_ptr) {
-        std::vector<const uint32_t*> list(nu);
-        std::vector<uint64_t> n(nu);
-        for (size_t i = 0; i < nu; ++i) {
-            list[i] = excl_items ? excl_items + excl_ptr[c0 + i] : nullptr;
-            n[i] = excl_ptr[c0 + i + 1] - excl_ptr[c0 + i];
-        }
-        prepare_users(list, n, m->hp.max_sequence_length, true, &ub);
-    }
-    const size_t ncaller = ub.list_items.size();
-    const size_t nsrc = nu * seen_w + ncaller, nseg = W * nsrc + nb * slack;
-    const bool excl = excl_ptr || seen_w || slack; /* without any of them nothing is ever excluded */
+    const size_t nseg = W * f.nsrc + nb * slack;
     uint32_t per = 0;
     const size_t nlist = std::max(nu * sbr::recommend_groups((uint32_t)nu, scanned, bc.w, &per),
                                   nb * sbr::recommend_groups((uint32_t)nb, scanned, bc.w, &per));
     int* d_rep = nullptr;
     uint2* lists = nullptr;
-    uint32_t *lens = nullptr, *scan_items = nullptr, *flag = nullptr, *d_slot = nullptr, *d_ident = nullptr;
+    uint32_t *lens = nullptr, *scan_items = nullptr, *flag = nullptr;
     uint32_t *any0 = nullptr, *none0 = nullptr, *anyb = nullptr, *noneb = nullptr;
-    uint32_t *src = nullptr, *seen_caller = nullptr, *seg[2] = {nullptr, nullptr}, *set_tags = nullptr;
-    uint64_t *src_ptr = nullptr, *seg_ptr = nullptr;
-    unsigned long long *d_start = nullptr, *mass = nullptr;
+    uint32_t* seg[2] = {nullptr, nullptr};
+    uint64_t* seg_ptr = nullptr;
+    unsigned long long* mass = nullptr;
     float *scan_scores = nullptr, *shift = nullptr;
     sbr::BeamRows br{};
     sbr::BeamRecord rec{};
     sbr::BeamOut bo{};
     SBRCHK(carve_arena(m, [&](DeviceArena& ar) {
         d_rep = ar.take<int>(nu);
-        d_slot = ar.take<uint32_t>(nu);
-        d_ident = ar.take<uint32_t>(nb);
-        d_start = ar.take<unsigned long long>(nb);
+        f.carve(ar);
         lists = ar.take<uint2>(nlist * W);
         lens = ar.take<uint32_t>(nlist);
         scan_items = ar.take<uint32_t>(nb * W);
@@ -6558,11 +6615,7 @@ sbr_status sessions_beam_chunk_run(sbr_sessions* st, const uint32_t* slots, cons
             none0 = ar.take<uint32_t>(nu);
             anyb = ar.take<uint32_t>(nb);
             noneb = ar.take<uint32_t>(nb);
-            if (set) set_tags = ar.take<uint32_t>(scanned);
         }
-        src_ptr = ar.take<uint64_t>(nu + 1);
-        src = ar.take<uint32_t>(nsrc + 1);
-        if (seen_w) seen_caller = ar.take<uint32_t>(ncaller + 1);
         seg_ptr = ar.take<uint64_t>(nb + 1);
         seg[0] = ar.take<uint32_t>(nseg + 1);
         if (slack) seg[1] = ar.take<uint32_t>(nseg + 1);
@@ -6599,43 +6652,20 @@ sbr_status sessions_beam_chunk_run(sbr_sessions* st, const uint32_t* slots, cons
         bo.cum = ar.take<float>(nb);
     }));
     /* the host vectors below are read by asynchronous copies: they live until the stream is drained at the end */
-    std::vector<uint64_t> h_src_ptr(nu + 1), h_seg_ptr(nb + 1, 0);
-    std::vector<uint32_t> h_ident(nb);
-    std::vector<unsigned long long> h_start(nb);
-    for (size_t i = 0; i <= nu; ++i) h_src_ptr[i] = i * seen_w + (ub.list_ptr.empty() ? 0 : ub.list_ptr[i]);
-    for (size_t b = 0; b < nb; ++b) {
-        const size_t i = b / W;
-        h_seg_ptr[b + 1] = h_seg_ptr[b] + (h_src_ptr[i + 1] - h_src_ptr[i]) + slack;
-        h_ident[b] = (uint32_t)b;
-        h_start[b] = b;
-    }
-    HIPCHK(hipMemcpyAsync(d_rep, rep0.data() + c0, nu * 4, hipMemcpyHostToDevice, m->stream));
-    HIPCHK(hipMemcpyAsync(d_slot, slots + c0, nu * 4, hipMemcpyHostToDevice, m->stream));
-    HIPCHK(hipMemcpyAsync(d_ident, h_ident.data(), nb * 4, hipMemcpyHostToDevice, m->stream));
-    HIPCHK(hipMemcpyAsync(d_start, h_start.data(), nb * 8, hipMemcpyHostToDevice, m->stream));
-    if (excl) {
+    SBRCHK(f.upload(d_rep));
+    uint64_t* const src_ptr = f.src_ptr;
+    uint32_t* const src = f.src;
+    std::vector<uint64_t> h_seg_ptr(nb + 1, 0);
+    if (excl) { /* every beam row's segment: its row's tight list and the slack */
+        for (size_t b = 0; b < nb; ++b) h_seg_ptr[b + 1] = h_seg_ptr[b] + (f.h_src_ptr[b / W + 1] - f.h_src_ptr[b / W]) + slack;
         HIPCHK(hipMemcpyAsync(seg_ptr, h_seg_ptr.data(), (nb + 1) * 8, hipMemcpyHostToDevice, m->stream));
-        SBRCHK(upload_csr(m, src_ptr, h_src_ptr, seen_w ? seen_caller : src, ub.list_items));
     }
-    std::vector<uint32_t> masks; /* the chunk's rows' any_of, then their none_of, then the same per beam row */
-    if (bc.flt) {
-        masks.assign(2 * nu + 2 * nb, 0u);
-        for (size_t i = 0; i < nu; ++i) {
-            const uint32_t a = bc.flt->any_of ? bc.flt->any_of[c0 + i] : 0u, z = bc.flt->none_of ? bc.flt->none_of[c0 + i] : 0u;
-            masks[i] = a;
-            masks[nu + i] = z;
-            for (size_t b = 0; b < W; ++b) {
-                masks[2 * nu + i * W + b] = a;
-                masks[2 * nu + nb + i * W + b] = z;
-            }
-        }
-        HIPCHK(hipMemcpyAsync(any0, masks.data(), nu * 4, hipMemcpyHostToDevice, m->stream));
-        HIPCHK(hipMemcpyAsync(none0, masks.data() + nu, nu * 4, hipMemcpyHostToDevice, m->stream));
-        HIPCHK(hipMemcpyAsync(anyb, masks.data() + 2 * nu, nb * 4, hipMemcpyHostToDevice, m->stream));
-        HIPCHK(hipMemcpyAsync(noneb, masks.data() + 2 * nu + nb, nb * 4, hipMemcpyHostToDevice, m->stream));
+    if (bc.flt) { /* step 0 scans the rows, the later steps their beams */
+        SBRCHK(upload_masks(m, *bc.flt, nullptr, c0, nu, 1, any0, none0, &f.masks));
+        SBRCHK(upload_masks(m, *bc.flt, nullptr, c0, nu, W, anyb, noneb, &f.masks_rows));
     }
     br.n = (int)nu; br.w = bc.w; br.steps = bc.steps;
-    br.slot = d_slot; br.ident = d_ident; br.start = d_start;
+    br.slot = f.d_slot; br.ident = f.d_ident; br.start = f.d_start;
     const uint32_t fb = sbr_softmax_fbits(num_items);
     const sbr::BeamScan bs{scan_items, scan_scores, shift, mass, bc.inv_t, fb, none ? nullptr : set ? set->d_ids : nullptr};
     const size_t parity_stride = nb * d;
@@ -6643,10 +6673,7 @@ sbr_status sessions_beam_chunk_run(sbr_sessions* st, const uint32_t* slots, cons
     if (none) HIPCHK(hipMemsetAsync(scan_items, 0xFF, nb * W * 4, m->stream)); /* nothing to scan: no parent has an offer */
     {
         ScopedTimer t(m, SBR_K_RANK, 0);
-        int n = sbr::launch_beam_begin(br, m->stream);
-        if (seen_w) n += sbr::launch_session_seen_lists(st->seen, d_slot, (int)nu, src_ptr, seen_caller, src, m->stream);
-        if (set && !none && nsrc) n += sbr::launch_subset_positions(set->d_ids, ns, src_ptr, (uint32_t)nu, src, m->stream);
-        if (set_tags && !none) n += sbr::launch_subset_words(set->d_ids, ns, m->item_tags, set_tags, m->stream);
+        int n = sbr::launch_beam_begin(br, m->stream) + f.prelaunch();
         if (excl && !slack) n += sbr::launch_beam_segments((int)nb, bc.w, src_ptr, src, nullptr, nullptr, seg_ptr, seg[0], m->stream);
         t.tp.launches = (uint64_t)n;
     }
@@ -6654,14 +6681,14 @@ sbr_status sessions_beam_chunk_run(sbr_sessions* st, const uint32_t* slots, cons
         /* step 0 scans the store's rows in place, one per row (an empty slot: the empty-history row); later steps the beam rows the
          * step before wrote, with their own segments */
         sbr::TopkScan sc{};
-        sc.rep_row = j == 0 ? d_rep : reinterpret_cast<const int*>(d_ident);
+        sc.rep_row = j == 0 ? d_rep : reinterpret_cast<const int*>(f.d_ident);
         sc.n = (uint32_t)(j == 0 ? nu : nb);
         sc.k = bc.w;
         sc.excl_ptr = !excl ? nullptr : j == 0 ? src_ptr : seg_ptr;
         sc.excl_items = j == 0 ? src : seg[slack ? (j - 1) & 1u : 0];
         sc.lists = lists; sc.lens = lens; sc.out_items = scan_items; sc.out_scores = scan_scores;
         sc.nonfinite_flag = flag;
-        sc.f = sbr::TagMasks{!bc.flt ? nullptr : set ? set_tags : m->item_tags, j == 0 ? any0 : anyb, j == 0 ? none0 : noneb};
+        sc.f = sbr::TagMasks{f.tags(), j == 0 ? any0 : anyb, j == 0 ? none0 : noneb};
         const float* reps = j == 0 ? st->v.H : br.Hs + (size_t)((j - 1) & 1u) * parity_stride;
         {
             ScopedTimer t(m, SBR_K_RANK, 0);
@@ -6681,22 +6708,14 @@ sbr_status sessions_beam_chunk_run(sbr_sessions* st, const uint32_t* slots, cons
         ScopedTimer t(m, SBR_K_RANK, 0);
         t.tp.launches = (uint64_t)sbr::launch_beam_backtrack(br, rec, bo, m->stream);
     }
-    HIPCHK(hipGetLastError());
-    uint32_t flag_h = 0;
-    HIPCHK(hipStreamSynchronize(m->stream));
-    HIPCHK(hipMemcpy(&flag_h, flag, 4, hipMemcpyDeviceToHost));
-    if (flag_h) return SBR_ERR_INVALID_PREDICTION; /* a non-finite score at any step fails the whole call */
-    const CopyOut outs[] = {{bc.out_items + c0 * W * S, bo.items, nb * S * 4},
-                            {bc.out_scores ? bc.out_scores + c0 * W * S : nullptr, bo.scores, nb * S * 4},
-                            {bc.out_lp ? bc.out_lp + c0 * W * S : nullptr, bo.lp, nb * S * 4},
-                            {bc.out_cum ? bc.out_cum + c0 * W : nullptr, bo.cum, nb * 4},
-                            {bc.out_lengths ? bc.out_lengths + c0 : nullptr, br.lengths, nu * 4},
-                            {bc.out_beams ? bc.out_beams + c0 : nullptr, br.beams, nu * 4},
-                            {part_out ? bc.out_shift + c0 * W * S : nullptr, bo.shift, nb * S * 4},
-                            {part_out ? bc.out_mass + c0 * W * S : nullptr, bo.mass, nb * S * 8}};
-    for (const CopyOut& o : outs)
-        if (o.host) HIPCHK(hipMemcpy(o.host, o.device, o.bytes, hipMemcpyDeviceToHost));
-    return SBR_OK;
+    return f.finish(flag, {{bc.out_items + c0 * W * S, bo.items, nb * S * 4},
+                           {bc.out_scores ? bc.out_scores + c0 * W * S : nullptr, bo.scores, nb * S * 4},
+                           {bc.out_lp ? bc.out_lp + c0 * W * S : nullptr, bo.lp, nb * S * 4},
+                           {bc.out_cum ? bc.out_cum + c0 * W : nullptr, bo.cum, nb * 4},
+                           {bc.out_lengths ? bc.out_lengths + c0 : nullptr, br.lengths, nu * 4},
+                           {bc.out_beams ? bc.out_beams + c0 : nullptr, br.beams, nu * 4},
+                           {part_out ? bc.out_shift + c0 * W * S : nullptr, bo.shift, nb * S * 4},
+                           {part_out ? bc.out_mass + c0 * W * S : nullptr, bo.mass, nb * S * 8}});
 }
 
 /* sbr_sessions_beam_search, or (set non-null: the caller checked that it is the store's model's) sbr_item_set_beam_search */
@@ -6704,40 +6723,21 @@ sbr_status beam_call(sbr_sessions* st, const sbr_item_set* set, const uint32_t* 
                      const uint64_t* excl_ptr, const uint32_t* excl_items, const uint32_t* any_of, const uint32_t* none_of,
                      uint32_t* out_items, float* out_scores, float* out_step_lp, float* out_cum, uint32_t* out_lengths,
                      uint32_t* out_beams, float* out_shift, uint64_t* out_mass, uint32_t* out_frac_bits) {
-    constexpr uint32_t known = SBR_ROLLOUT_ALLOW_REPEATS | SBR_ROLLOUT_INCLUDE_SEEN;
     if (!st || !args || (n && !out_items)) return SBR_ERR_INVALID_ARGUMENT;
-    if (args->steps < 1 || args->steps > SBR_ROLLOUT_MAX_STEPS || (args->flags & ~known)) return SBR_ERR_INVALID_ARGUMENT;
     if (args->width < 1 || args->width > SBR_BEAM_MAX_WIDTH) return SBR_ERR_INVALID_ARGUMENT;
     sbr_sample_args sa{};
     sa.temperature = args->temperature;
     Sample sm;
-    TagFilterArg hold;
     if (!sample_args(&sa, nullptr, &sm)) return SBR_ERR_INVALID_ARGUMENT;
     if ((out_shift != nullptr) != (out_mass != nullptr) || (out_shift != nullptr) != (out_frac_bits != nullptr)) return SBR_ERR_INVALID_ARGUMENT;
-    if ((args->flags & SBR_ROLLOUT_INCLUDE_SEEN) && !st->seen.w) return SBR_ERR_INVALID_ARGUMENT; /* nothing to include */
-    if (!excl_args_ok(excl_ptr, excl_items, n)) return SBR_ERR_INVALID_ARGUMENT;
-    sbr_model* m = st->m;
-    std::lock_guard<std::mutex> lock(m->mu);
-    if (set) SBRCHK(enter_item_set(set));
-    SBRCHK(enter_sessions(st));
-    SBRCHK(check_slots(st, slots, n));
-    if (excl_ptr) SBRCHK(check_csr(m, excl_ptr, n, excl_items, false));
     BeamCall bc{};
-    bc.steps = args->steps;
+    bc.set = set; bc.slots = slots; bc.excl_ptr = excl_ptr; bc.excl_items = excl_items;
     bc.w = args->width;
-    bc.allow_repeats = (args->flags & SBR_ROLLOUT_ALLOW_REPEATS) != 0;
-    bc.seen = st->seen.w && !(args->flags & SBR_ROLLOUT_INCLUDE_SEEN);
-    bc.flt = sample_filter(any_of, none_of, &hold);
-    if (bc.flt && !m->item_tags) return SBR_ERR_INVALID_ARGUMENT;
     bc.inv_t = sm.inv_t;
     bc.out_items = out_items; bc.out_scores = out_scores; bc.out_lp = out_step_lp; bc.out_cum = out_cum;
     bc.out_lengths = out_lengths; bc.out_beams = out_beams; bc.out_shift = out_shift; bc.out_mass = out_mass;
-    const std::vector<int> rep0 = session_rep_rows(st, slots, n);
-    const size_t cap = sessions_beam_chunk(m, bc.seen ? st->seen.w : 0, bc.w, bc.steps);
-    for (size_t c0 = 0; c0 < n; c0 += cap)
-        SBRCHK(sessions_beam_chunk_run(st, slots, rep0, excl_ptr, excl_items, bc, set, c0, std::min<size_t>(cap, n - c0)));
-    if (out_frac_bits) *out_frac_bits = sbr_softmax_fbits((uint32_t)m->hp.num_items); /* the model's, with or without a set */
-    return SBR_OK;
+    return steps_call(st, &bc, n, args->steps, args->flags, SBR_ROLLOUT_ALLOW_REPEATS | SBR_ROLLOUT_INCLUDE_SEEN, any_of, none_of,
+                      sessions_beam_chunk, sessions_beam_chunk_run, out_frac_bits);
 }
 
 }  // namespace
@@ -6776,47 +6776,21 @@ sbr_status enter_item_set(const sbr_item_set* set) {
     return set->gen == set->m->param_gen && set->m->open_plans == 0 ? SBR_OK : SBR_ERR_INVALID_ARGUMENT;
 }
 
-/* One call through a set: r names exactly one source of rows, v the family (its set, filter and noise are filled in here), sm the
- * noise of a sampled call (a store's default streams are its slots). */
-sbr_status item_set_scan(sbr_item_set* set, const sbr_scan_rows* r, uint64_t n, uint32_t k, uint32_t* out_items, float* out_scores,
-                         ScanVariant v, Sample* sm = nullptr) {
-    if (!set || !r) return SBR_ERR_INVALID_ARGUMENT;
-    if ((r->user_ptr != nullptr) + (r->reps != nullptr) + (r->store != nullptr) != 1) return SBR_ERR_INVALID_ARGUMENT;
-    if (n && !out_items && !v.pt && !v.ab) return SBR_ERR_INVALID_ARGUMENT;
-    sbr_model* m = set->m;
-    if (!scan_k_ok(m, k, v.dv, v.cp)) return SBR_ERR_INVALID_ARGUMENT;
-    TagFilterArg hold;
-    v.flt = sample_filter(r->any_of, r->none_of, &hold);
-    v.sm = sm;
-    v.set = set;
-    if (r->user_ptr) { /* histories: the lists are the histories themselves */
-        if (r->excl_ptr || r->excl_items || (r->flags & ~SBR_RECOMMEND_INCLUDE_HISTORY)) return SBR_ERR_INVALID_ARGUMENT;
-        std::lock_guard<std::mutex> lock(m->mu);
-        SBRCHK(enter_item_set(set));
-        SBRCHK(check_csr(m, r->user_ptr, n, r->item_ids, false));
-        return recommend_scan(m, RepSource::of_histories(r->user_ptr, r->item_ids, 0, !(r->flags & SBR_RECOMMEND_INCLUDE_HISTORY)), n, k, out_items,
-                              out_scores, v);
+/* A set call's descriptor as scan_call's rows: false unless it names exactly one source of rows and none of the fields that source
+ * forbids — histories no lists, representations no flags, item_ids or slots, a store no item_ids. */
+bool item_set_rows(const sbr_item_set* set, const sbr_scan_rows* r, ScanRows* out) {
+    if (!set || !r || (r->user_ptr != nullptr) + (r->reps != nullptr) + (r->store != nullptr) != 1) return false;
+    if (r->user_ptr) {
+        if (r->excl_ptr || r->excl_items) return false;
+        *out = ScanRows::of_histories(r->user_ptr, r->item_ids, r->flags, r->any_of, r->none_of);
+    } else if (r->reps) {
+        if (r->flags || r->item_ids || r->slots) return false;
+        *out = ScanRows::of_reps(r->reps, r->excl_ptr, r->excl_items, r->any_of, r->none_of);
+    } else {
+        if (r->item_ids) return false;
+        *out = ScanRows::of_store(r->store, r->slots, r->excl_ptr, r->excl_items, r->flags, r->any_of, r->none_of);
     }
-    if (!excl_args_ok(r->excl_ptr, r->excl_items, n)) return SBR_ERR_INVALID_ARGUMENT;
-    if (r->reps) {
-        if (r->flags || r->item_ids || r->slots) return SBR_ERR_INVALID_ARGUMENT;
-        std::lock_guard<std::mutex> lock(m->mu);
-        SBRCHK(enter_item_set(set));
-        if (r->excl_ptr) SBRCHK(check_csr(m, r->excl_ptr, n, r->excl_items, false));
-        return recommend_scan(m, RepSource::of_rows(r->reps, r->excl_ptr, r->excl_items), n, k, out_items, out_scores, v);
-    }
-    sbr_sessions* st = r->store;
-    if (st->m != m || r->item_ids) return SBR_ERR_INVALID_ARGUMENT;
-    if (st->seen.w ? (r->flags & ~SBR_RECOMMEND_INCLUDE_HISTORY) != 0 : r->flags != 0) return SBR_ERR_INVALID_ARGUMENT;
-    std::lock_guard<std::mutex> lock(m->mu);
-    SBRCHK(enter_item_set(set));
-    SBRCHK(enter_sessions(st));
-    SBRCHK(check_slots(st, r->slots, n));
-    if (r->excl_ptr) SBRCHK(check_csr(m, r->excl_ptr, n, r->excl_items, false));
-    const std::vector<int> rows = session_rep_rows(st, r->slots, n);
-    const bool seen = st->seen.w && !(r->flags & SBR_RECOMMEND_INCLUDE_HISTORY);
-    if (sm) sm->fallback = r->slots;
-    return recommend_scan(m, RepSource::of_sessions(st, rows, r->excl_ptr, r->excl_items, seen ? r->slots : nullptr), n, k, out_items, out_scores, v);
+    return true;
 }
 
 }  // namespace
@@ -6887,65 +6861,73 @@ sbr_status sbr_item_set_refresh(sbr_item_set* set) {
 
 sbr_status sbr_item_set_recommend(sbr_item_set* set, const struct sbr_scan_rows* rows, uint64_t num_rows, uint32_t k, uint32_t* out_items,
                                   float* out_scores) {
-    return item_set_scan(set, rows, num_rows, k, out_items, out_scores, ScanVariant());
+    ScanRows r;
+    if (!item_set_rows(set, rows, &r)) return SBR_ERR_INVALID_ARGUMENT;
+    return scan_call(set->m, set, r, num_rows, k, out_items, out_scores, ScanVariant());
 }
 
 sbr_status sbr_item_set_recommend_diverse(sbr_item_set* set, const struct sbr_scan_rows* rows, uint64_t num_rows, uint32_t k, uint32_t pool,
                                           float trade_off, uint32_t metric, uint32_t* out_items, float* out_scores) {
     const Diverse dv{k, trade_off, metric};
+    ScanRows r;
     ScanVariant v;
+    if (!item_set_rows(set, rows, &r)) return SBR_ERR_INVALID_ARGUMENT;
     v.dv = &dv;
-    return item_set_scan(set, rows, num_rows, pool, out_items, out_scores, v);
+    return scan_call(set->m, set, r, num_rows, pool, out_items, out_scores, v);
 }
 
 sbr_status sbr_item_set_recommend_sampled(sbr_item_set* set, const struct sbr_scan_rows* rows, uint64_t num_rows, uint32_t k,
                                           const struct sbr_sample_args* sample, uint32_t* out_items, float* out_scores, float* out_keys) {
     Sample sm;
-    if (!sample_args(sample, out_keys, &sm)) return SBR_ERR_INVALID_ARGUMENT;
-    return item_set_scan(set, rows, num_rows, k, out_items, out_scores, ScanVariant(), &sm);
+    ScanRows r;
+    ScanVariant v;
+    if (!sample_args(sample, out_keys, &sm) || !item_set_rows(set, rows, &r)) return SBR_ERR_INVALID_ARGUMENT;
+    v.sm = &sm;
+    return scan_call(set->m, set, r, num_rows, k, out_items, out_scores, v);
 }
 
 sbr_status sbr_item_set_log_partition(sbr_item_set* set, const struct sbr_scan_rows* rows, uint64_t num_rows, float temperature, float* out_shift,
                                       uint64_t* out_mass, uint32_t* out_frac_bits) {
     Partition pt;
-    if (!set || !partition_args(temperature, num_rows, out_shift, out_mass, out_frac_bits, &pt)) return SBR_ERR_INVALID_ARGUMENT;
+    ScanRows r;
     ScanVariant v;
+    if (!partition_args(temperature, num_rows, out_shift, out_mass, out_frac_bits, &pt) || !item_set_rows(set, rows, &r))
+        return SBR_ERR_INVALID_ARGUMENT;
     v.pt = &pt;
-    const sbr_status r = item_set_scan(set, rows, num_rows, 1, nullptr, nullptr, v);
-    if (r == SBR_OK) *out_frac_bits = sbr_softmax_fbits((uint32_t)set->m->hp.num_items); /* the model's, not the set's */
-    return r;
+    return scan_call(set->m, set, r, num_rows, 1, nullptr, nullptr, v);
 }
 
 sbr_status sbr_item_set_recommend_above(sbr_item_set* set, const struct sbr_scan_rows* rows, uint64_t num_rows, const float* thresholds,
                                         uint64_t* out_counts, uint64_t* out_total, uint64_t capacity, uint32_t* out_ids, float* out_scores) {
     Above ab;
-    if (!above_args(thresholds, num_rows, out_counts, out_total, capacity, out_ids, out_scores, &ab)) return SBR_ERR_INVALID_ARGUMENT;
+    ScanRows r;
     ScanVariant v;
+    if (!above_args(thresholds, num_rows, out_counts, out_total, capacity, out_ids, out_scores, &ab) || !item_set_rows(set, rows, &r))
+        return SBR_ERR_INVALID_ARGUMENT;
     v.ab = &ab;
-    SBRCHK(item_set_scan(set, rows, num_rows, 1, nullptr, nullptr, v));
-    *out_total = ab.total;
-    return SBR_OK;
+    return scan_call(set->m, set, r, num_rows, 1, nullptr, nullptr, v);
 }
 
 sbr_status sbr_item_set_recommend_top(sbr_item_set* set, const struct sbr_scan_rows* rows, uint64_t num_rows, const uint64_t* n, float* out_cuts,
                                       uint64_t* out_counts, uint64_t* out_total, uint64_t capacity, uint32_t* out_ids, float* out_scores) {
     Above ab;
-    if (!top_args(n, num_rows, out_cuts, out_counts, out_total, capacity, out_ids, out_scores, &ab)) return SBR_ERR_INVALID_ARGUMENT;
+    ScanRows r;
     ScanVariant v;
+    if (!top_args(n, num_rows, out_cuts, out_counts, out_total, capacity, out_ids, out_scores, &ab) || !item_set_rows(set, rows, &r))
+        return SBR_ERR_INVALID_ARGUMENT;
     v.ab = &ab;
-    SBRCHK(item_set_scan(set, rows, num_rows, 1, nullptr, nullptr, v));
-    *out_total = ab.total;
-    return SBR_OK;
+    return scan_call(set->m, set, r, num_rows, 1, nullptr, nullptr, v);
 }
 
 sbr_status sbr_item_set_recommend_capped(sbr_item_set* set, const struct sbr_scan_rows* rows, uint64_t num_rows, uint32_t k,
                                          const struct sbr_cap_args* cap, uint32_t* out_items, float* out_scores, uint8_t* out_complete) {
     Capped cp;
-    uint32_t pool = 0;
-    if (!capped_args(cap, k, out_complete, &cp, &pool)) return SBR_ERR_INVALID_ARGUMENT;
+    ScanRows r;
     ScanVariant v;
+    uint32_t pool = 0;
+    if (!capped_args(cap, k, out_complete, &cp, &pool) || !item_set_rows(set, rows, &r)) return SBR_ERR_INVALID_ARGUMENT;
     v.cp = &cp;
-    return item_set_scan(set, rows, num_rows, pool, out_items, out_scores, v);
+    return scan_call(set->m, set, r, num_rows, pool, out_items, out_scores, v);
 }
 
 namespace {
