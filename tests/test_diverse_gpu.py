@@ -93,7 +93,7 @@ def test_matches_expectation(d, items, metric, kind):
             assert np.all(got[0][1, min(k, 5):] == NO_ITEM) and np.all(got[0][1, : min(k, 5)] != NO_ITEM)
 
 
-@pytest.mark.parametrize("d,pool", [(128, 256), (256, 128), (16, 1024)])
+@pytest.mark.parametrize("d,pool", [(128, 256), (256, 128), (16, 1024), (32, 1024), (64, 512)])
 def test_pool_at_the_lds_limit(d, pool):
     items, k = 1500, pool // 2
     E, bias = _planted(items, d, d)

@@ -73,7 +73,8 @@ SHAPES = [(ModelKind.EWMA, 16, 1100, 24, 130),
           (ModelKind.LSTM_NORMAL, 32, 300, 24, 48),
           (ModelKind.LSTM_COUPLED, 256, 70, 6, 30),
           (ModelKind.EWMA, 100, 517, 6, 130),
-          (ModelKind.LSTM_NORMAL, 128, 200, 6, 40)]
+          (ModelKind.LSTM_NORMAL, 128, 200, 6, 40),
+          (ModelKind.LSTM_COUPLED, 64, 70, 6, 30)]
 
 
 @functools.lru_cache(maxsize=None)

@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """Summarise a rocprofv3 rocpd database (kernel trace) into the same table `--stats` prints:
-per-kernel calls / total / average / min / max / share.  Usage: rocpd_stats.py results.db [out.md] [--window KERNEL FIRST COUNT]
+per-kernel calls / total / average / min / max / share.  Usage: rocpd_stats.py results.db [out.md] [--counts] [--window KERNEL FIRST COUNT]
+--counts: the distinct kernel names with their launch counts only, sorted by name.
 --window: a second table over the TIMED region only — the dispatches from the FIRST-th dispatch of KERNEL (a substring; in start order)
 up to, not including, its (FIRST + COUNT)-th: what bench.py's HIP events bracket (warm-up and the second, all-timers pass left out)."""
 import re
@@ -24,6 +25,11 @@ def main():
     for name, n, tot, avg, mn, mx in rows:
         lines.append(f"| `{short(name)}` | {n} | {tot / 1e6:.3f} | {avg / 1e3:.2f} | {mn / 1e3:.2f} | {mx / 1e3:.2f} | {100 * tot / total:.1f} |")
     text = "\n".join(lines)
+    if "--counts" in sys.argv:  # which kernels ran, and how often: the names in order, no durations
+        counts = {}
+        for name, n, *_ in rows:
+            counts[short(name)] = counts.get(short(name), 0) + n
+        text = "\n".join(["| kernel | calls |", "|---|---|"] + [f"| `{k}` | {n} |" for k, n in sorted(counts.items())])
     if "--window" in sys.argv:
         i = sys.argv.index("--window")
         kern, first, count = sys.argv[i + 1], int(sys.argv[i + 2]), int(sys.argv[i + 3])
