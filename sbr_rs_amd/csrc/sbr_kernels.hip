@@ -2960,6 +2960,7 @@ void launch_recurrent_forward(const ModelView& m, const MbView& mb, float* H, co
                 /* 16-sequence tiles for small minibatches: below SBR_SEQ_RT1_MAX_TILES 32-sequence tiles the chip is not
                  * full and the kernel time is the longest tile's chain of dependent steps — half-size tiles halve the step */
                 const bool tiny = rt_env ? rt_env == 1 : (mb.B + 31) / 32 < SBR_SEQ_RT1_MAX_TILES;
+                bool launched = false;
                 if (tiny) {  /* every d <= 128: at d = 32 a 16-row step is 64 MFMAs per wave instead of 128 */
                     constexpr int RT = 1;
                     const int ntiles = (mb.B + 16 * RT - 1) / (16 * RT);
@@ -2967,14 +2968,20 @@ void launch_recurrent_forward(const ModelView& m, const MbView& mb, float* H, co
                         hipLaunchKernelGGL((lstm_fwd_seq_kernel<DD, 4, RT, UPW>), dim3(ntiles), dim3((DD / 16 / UPW) * 64), 0, s, m, mb, H, w, ntiles);
                     else
                         hipLaunchKernelGGL((lstm_fwd_seq_kernel<DD, 3, RT, UPW>), dim3(ntiles), dim3((DD / 16 / UPW) * 64), 0, s, m, mb, H, w, ntiles);
-                } else if (big && DD >= 64) {
-                    constexpr int RT = 4;
-                    const int ntiles = (mb.B + 16 * RT - 1) / (16 * RT);
-                    if (m.ng == 4)
-                        hipLaunchKernelGGL((lstm_fwd_seq_kernel<DD, 4, RT, UPW>), dim3(ntiles), dim3((DD / 16 / UPW) * 64), 0, s, m, mb, H, w, ntiles);
-                    else
-                        hipLaunchKernelGGL((lstm_fwd_seq_kernel<DD, 3, RT, UPW>), dim3(ntiles), dim3((DD / 16 / UPW) * 64), 0, s, m, mb, H, w, ntiles);
-                } else {
+                    launched = true;
+                }
+                if constexpr (DD >= 64) {  /* (d = 16 / 32 have no 64-sequence form: as launch_recurrent_backward, nothing is instantiated) */
+                    if (big && !launched) {
+                        constexpr int RT = 4;
+                        const int ntiles = (mb.B + 16 * RT - 1) / (16 * RT);
+                        if (m.ng == 4)
+                            hipLaunchKernelGGL((lstm_fwd_seq_kernel<DD, 4, RT, UPW>), dim3(ntiles), dim3((DD / 16 / UPW) * 64), 0, s, m, mb, H, w, ntiles);
+                        else
+                            hipLaunchKernelGGL((lstm_fwd_seq_kernel<DD, 3, RT, UPW>), dim3(ntiles), dim3((DD / 16 / UPW) * 64), 0, s, m, mb, H, w, ntiles);
+                        launched = true;
+                    }
+                }
+                if (!launched) {
                     constexpr int RT = 2;
                     const int ntiles = (mb.B + 16 * RT - 1) / (16 * RT);
                     if (m.ng == 4)
