@@ -724,6 +724,25 @@ inline std::vector<std::uint32_t> tag_masks(const std::vector<std::uint32_t>& ma
     return std::vector<std::uint32_t>(n ? n : 1, mask.empty() ? 0u : mask[0]);
 }
 
+/// The eligible-ranks call (ELIGIBLE RANKS in sbr_hip.h) over a descriptor's `rows` rows, on the model (set null) or through a set of
+/// it: one rank per target, in target order; Err(InvalidPredictionValue) on a non-finite score of a scanned pair.
+inline Result<std::vector<std::uint32_t>, PredictionError> eligible_ranks(sbr_model* model, sbr_item_set* set, const sbr_scan_rows& d, std::size_t rows,
+                                                                          const std::vector<std::uint64_t>& target_ptr,
+                                                                          const std::vector<std::uint32_t>& target_items, const char* where) {
+    using R = Result<std::vector<std::uint32_t>, PredictionError>;
+    if (target_ptr.size() != rows + 1 || target_ptr.back() < target_ptr.front() || target_ptr.back() > target_items.size())
+        throw EngineError(SBR_ERR_INVALID_ARGUMENT, where);
+    static const std::uint32_t none = 0;
+    std::vector<std::uint32_t> ranks((std::size_t)(target_ptr.back() - target_ptr.front()) + 1);
+    const std::uint32_t* items = target_items.empty() ? &none : target_items.data();
+    const sbr_status st = set ? sbr_item_set_rank_targets(set, &d, (std::uint64_t)rows, target_ptr.data(), items, ranks.data())
+                              : sbr_rank_targets_rows(model, &d, (std::uint64_t)rows, target_ptr.data(), items, ranks.data());
+    if (st == SBR_ERR_INVALID_PREDICTION) return R::Err(PredictionError::InvalidPredictionValue);
+    check(st, where);
+    ranks.pop_back();
+    return R::Ok(std::move(ranks));
+}
+
 /// The pool a *_capped call scans at, and its refusals ahead of the library: cap < 1, k < 1, pool < k, pool > SBR_RECOMMEND_MAX_K.
 inline sbr_cap_args cap_args(const CapArgs& a, std::size_t k, const char* me) {
     const std::uint64_t pool = a.pool ? a.pool : std::min<std::uint64_t>(1024, std::max<std::uint64_t>(64, 4 * (std::uint64_t)k));
@@ -920,15 +939,15 @@ inline std::vector<std::uint32_t> narrow(const std::vector<ItemId>& ids) {
 /// Obtained from ImplicitSequenceModel::sessions; the model must outlive it.  Movable, not copyable.
 class Sessions {
   public:
-    Sessions(sbr_model* model, std::size_t capacity, std::size_t embedding_dim, std::size_t seen_capacity = 0) : dim_(embedding_dim) {
+    Sessions(sbr_model* model, std::size_t capacity, std::size_t embedding_dim, std::size_t seen_capacity = 0) : m_(model), dim_(embedding_dim) {
         if (seen_capacity > SBR_SESSIONS_MAX_SEEN) throw EngineError(SBR_ERR_INVALID_ARGUMENT, "Sessions: seen_capacity above SBR_SESSIONS_MAX_SEEN");
         check(sbr_sessions_create_seen(model, (std::uint64_t)capacity, (std::uint32_t)seen_capacity, &h_), "sbr_sessions_create_seen");
     }
     Sessions(const Sessions&) = delete;
     Sessions& operator=(const Sessions&) = delete;
-    Sessions(Sessions&& o) noexcept : h_(o.h_), dim_(o.dim_) { o.h_ = nullptr; }
+    Sessions(Sessions&& o) noexcept : h_(o.h_), m_(o.m_), dim_(o.dim_) { o.h_ = nullptr; }
     Sessions& operator=(Sessions&& o) noexcept {
-        if (this != &o) { release(); h_ = o.h_; dim_ = o.dim_; o.h_ = nullptr; }
+        if (this != &o) { release(); h_ = o.h_; m_ = o.m_; dim_ = o.dim_; o.h_ = nullptr; }
         return *this;
     }
     ~Sessions() { release(); }
@@ -1523,6 +1542,29 @@ class Sessions {
                                      state.len.data()),
               "sbr_sessions_set_state");
     }
+    /// Exact ranks of each slot's targets target_items[target_ptr[i] .. target_ptr[i + 1]) among what the slot may be shown
+    /// (sbr_rank_targets_rows): the model's rank_targets for representations(slots) with the slot's seen items (unless
+    /// `include_seen`), the caller's lists and every item the filter forbids masked to f32::MIN — a masked target has rank
+    /// num_items.  The scan reads the store's rows in place.  "Rank the next event, then append it" is this call and `append`.
+    Result<std::vector<std::uint32_t>, PredictionError> rank_targets(const std::vector<std::uint32_t>& slots, const std::vector<std::uint64_t>& target_ptr,
+                                                                     const std::vector<std::uint32_t>& target_items,
+                                                                     const std::vector<std::uint64_t>& excl_ptr = {},
+                                                                     const std::vector<std::uint32_t>& excl_items = {}, bool include_seen = false,
+                                                                     const TagFilter& filter = {}) const {
+        if (!excl_ptr.empty() && (excl_ptr.size() != slots.size() + 1 || excl_ptr.back() > excl_items.size()))
+            throw EngineError(SBR_ERR_INVALID_ARGUMENT, "Sessions::rank_targets: one exclusion range per slot");
+        const bool filtered = !filter.any_of.empty() || !filter.none_of.empty();
+        const std::vector<std::uint32_t> any = tag_masks(filter.any_of, slots.size(), "Sessions::rank_targets: one any_of mask per slot");
+        const std::vector<std::uint32_t> none_of = tag_masks(filter.none_of, slots.size(), "Sessions::rank_targets: one none_of mask per slot");
+        static const std::uint32_t none = 0;
+        sbr_scan_rows d{};
+        d.store = h_;
+        d.slots = slots.empty() ? &none : slots.data();
+        d.flags = include_seen ? SBR_RECOMMEND_INCLUDE_HISTORY : 0u;
+        if (!excl_ptr.empty()) { d.excl_ptr = excl_ptr.data(); d.excl_items = excl_items.empty() ? &none : excl_items.data(); }
+        if (filtered) { d.any_of = any.data(); d.none_of = none_of.data(); }
+        return detail::eligible_ranks(m_, nullptr, d, slots.size(), target_ptr, target_items, "sbr_rank_targets_rows");
+    }
     sbr_sessions* handle() const { return h_; }
 
   private:
@@ -1531,6 +1573,7 @@ class Sessions {
         h_ = nullptr;
     }
     sbr_sessions* h_ = nullptr;
+    sbr_model* m_ = nullptr;
     std::size_t dim_;
 };
 
@@ -1682,6 +1725,13 @@ class ItemSet {
     }
 
     // ---- the families over any rows ----
+    /// Exact ranks of each row's targets among the set's items the row may be shown (sbr_item_set_rank_targets): the model's
+    /// rank_targets with every item outside the set masked as well — a target outside it has rank num_items, the catalogue's.
+    Result<std::vector<std::uint32_t>, PredictionError> rank_targets(const Rows& rows, const std::vector<std::uint64_t>& target_ptr,
+                                                                     const std::vector<std::uint32_t>& target_items) const {
+        const sbr_scan_rows d = rows.desc();
+        return detail::eligible_ranks(m_, h_, d, rows.size(), target_ptr, target_items, "sbr_item_set_rank_targets");
+    }
     Result<Recommendations, PredictionError> recommend(const Rows& rows, std::size_t k) const {
         if (k < 1 || k > SBR_RECOMMEND_MAX_K) throw EngineError(SBR_ERR_INVALID_ARGUMENT, "ItemSet::recommend: k outside 1..SBR_RECOMMEND_MAX_K");
         Recommendations r = top_rows(rows.size(), k);
@@ -1841,6 +1891,13 @@ class ItemSet {
     class OnSessions {
       public:
         OnSessions(const ItemSet& set, const Sessions& store) : set_(set), store_(store) {}
+        Result<std::vector<std::uint32_t>, PredictionError> rank_targets(const std::vector<std::uint32_t>& slots, const std::vector<std::uint64_t>& target_ptr,
+                                                                         const std::vector<std::uint32_t>& target_items,
+                                                                         const std::vector<std::uint64_t>& excl_ptr = {},
+                                                                         const std::vector<std::uint32_t>& excl_items = {}, bool include_seen = false,
+                                                                         const TagFilter& filter = {}) const {
+            return set_.rank_targets(set_.of(store_, slots, excl_ptr, excl_items, include_seen, filter), target_ptr, target_items);
+        }
         Result<Recommendations, PredictionError> recommend(const std::vector<std::uint32_t>& slots, std::size_t k, const std::vector<std::uint64_t>& excl_ptr = {},
                                                            const std::vector<std::uint32_t>& excl_items = {}, bool include_seen = false,
                                                            const TagFilter& filter = {}) const {
@@ -2774,6 +2831,26 @@ class ImplicitSequenceModel : public OnlineRankingModel<ImplicitUser> {
         return R::Ok(std::move(ranks));
     }
 
+    /// rank_targets among what each user may be shown (sbr_rank_targets_rows): every item the filter forbids is masked to f32::MIN
+    /// as the history is, so a forbidden target has rank num_items; an empty filter is the call above.  Needs set_item_tags.
+    Result<std::vector<std::uint32_t>, PredictionError> rank_targets(const data::CompressedInteractions& histories,
+                                                                     const std::vector<std::uint64_t>& target_ptr,
+                                                                     const std::vector<std::uint32_t>& target_items, const TagFilter& filter,
+                                                                     bool mask_history = true) const {
+        if (filter.any_of.empty() && filter.none_of.empty()) return rank_targets(histories, target_ptr, target_items, mask_history);
+        const std::size_t n = histories.num_users();
+        const std::vector<std::uint32_t> any = tag_masks(filter.any_of, n, "rank_targets: one any_of mask per user");
+        const std::vector<std::uint32_t> none_of = tag_masks(filter.none_of, n, "rank_targets: one none_of mask per user");
+        static const std::uint32_t none = 0;
+        sbr_scan_rows d{};
+        d.user_ptr = histories.user_pointers().data();
+        d.item_ids = histories.item_ids().empty() ? &none : histories.item_ids().data();
+        d.flags = mask_history ? 0u : SBR_RECOMMEND_INCLUDE_HISTORY;
+        d.any_of = any.data();
+        d.none_of = none_of.data();
+        return detail::eligible_ranks(replicas_->primary(), nullptr, d, n, target_ptr, target_items, "sbr_rank_targets_rows");
+    }
+
     /// Exact next-item rank at every position of every sequence from one forward pass per sequence (sbr_sequence_ranks): with
     /// W = min(n, max_sequence_length + 1) and w the last W items of user u, position p = 1 .. W - 1 ranks w[p] against the state
     /// after w[0 .. p), the distinct items of that prefix masked to f32::MIN unless `mask_history` is false — the number
@@ -3253,6 +3330,7 @@ inline Result<float, PredictionError> mrr_score(const models::detail::ImplicitSe
 /// the at-k ones row-major [num_users_ranked][ks.size()].
 struct RankingMetrics {
     std::vector<std::size_t> ks;
+    std::size_t targets_skipped = 0;  ///< ranking_metrics under a policy with Ineligible::Skip: the targets left out of every mean
     std::size_t num_users_ranked = 0;
     std::vector<std::size_t> users;  ///< the ranked users' indices
     std::vector<double> precision, recall, hit_rate, ndcg;  ///< one mean per k
@@ -3318,10 +3396,31 @@ inline RankingMetrics ranking_metrics_from_ranks(const std::vector<std::uint64_t
 /// holdout + 1 items are skipped (the reference's >= 2 at holdout = 1).  The exact ranks come from one device scan
 /// (ImplicitSequenceModel::rank_targets), whose cost does not depend on k; `out_ranks` (optional) receives them, one per
 /// distinct target in user order.  `users` of the result index the test set's users.
+/// What a target the serving policy can never show — in its own history, forbidden by the masks, outside the set — counts as: Miss
+/// keeps it at rank num_items (the reference's rule for a target in its own history), Skip leaves it out of every mean.
+enum class Ineligible { Miss, Skip };
+/// The serving policy the ranks are taken under: tag masks (one per user of the TEST SET, or one for all; needs set_item_tags) and an
+/// item set of the model; both empty: the plain evaluation.
+struct RankingPolicy {
+    models::TagFilter filter;
+    const models::ItemSet* item_set = nullptr;
+    Ineligible ineligible = Ineligible::Miss;
+};
+inline Result<RankingMetrics, PredictionError> ranking_metrics(const models::detail::ImplicitSequenceModel& model,
+                                                               const data::CompressedInteractions& test, const RankingPolicy& policy,
+                                                               const std::vector<std::size_t>& ks = {10, 100}, std::size_t holdout = 1,
+                                                               std::vector<std::uint32_t>* out_ranks = nullptr);
 inline Result<RankingMetrics, PredictionError> ranking_metrics(const models::detail::ImplicitSequenceModel& model,
                                                                const data::CompressedInteractions& test,
                                                                const std::vector<std::size_t>& ks = {10, 100}, std::size_t holdout = 1,
                                                                std::vector<std::uint32_t>* out_ranks = nullptr) {
+    return ranking_metrics(model, test, RankingPolicy{}, ks, holdout, out_ranks);
+}
+/// The same under a serving policy (ELIGIBLE RANKS in sbr_hip.h); `out_ranks` receives every rank, skipped targets included.
+inline Result<RankingMetrics, PredictionError> ranking_metrics(const models::detail::ImplicitSequenceModel& model,
+                                                               const data::CompressedInteractions& test, const RankingPolicy& policy,
+                                                               const std::vector<std::size_t>& ks, std::size_t holdout,
+                                                               std::vector<std::uint32_t>* out_ranks) {
     if (holdout < 1) throw std::invalid_argument("ranking_metrics: holdout must be >= 1");
     std::vector<std::size_t> users;
     std::vector<std::uint64_t> hist_ptr{0}, target_ptr{0}, timestamps;
@@ -3342,9 +3441,43 @@ inline Result<RankingMetrics, PredictionError> ranking_metrics(const models::det
     }
     timestamps.assign(hist_items.size(), 0);
     const data::CompressedInteractions histories(users.size(), test.num_items(), hist_ptr, hist_items, timestamps);
-    auto ranks = model.rank_targets(histories, target_ptr, target_items);
+    auto per_user = [&](const std::vector<std::uint32_t>& mask) {  // a per-user mask of the test set follows the users the split kept
+        if (mask.size() <= 1) return mask;
+        if (mask.size() != test.num_users()) throw std::invalid_argument("ranking_metrics: one mask per user of the test set");
+        std::vector<std::uint32_t> kept;
+        for (std::size_t u : users) kept.push_back(mask[u]);
+        return kept;
+    };
+    const models::TagFilter filter{per_user(policy.filter.any_of), per_user(policy.filter.none_of)};
+    const bool filtered = !filter.any_of.empty() || !filter.none_of.empty();
+    auto ranks = policy.item_set ? policy.item_set->rank_targets(policy.item_set->of(histories, true, filter), target_ptr, target_items)
+                                 : model.rank_targets(histories, target_ptr, target_items, filter);
     if (ranks.is_err()) return Result<RankingMetrics, PredictionError>::Err(ranks.unwrap_err());
-    RankingMetrics out = ranking_metrics_from_ranks(target_ptr, ranks.unwrap(), ks);
+    std::vector<std::uint64_t> kept_ptr = target_ptr;
+    std::vector<std::uint32_t> kept_ranks = ranks.unwrap();
+    std::size_t skipped = 0;
+    if (policy.ineligible == Ineligible::Skip) {  // the host statement of "the policy can show it": in the set, allowed, not in the history
+        const std::vector<std::uint32_t> tags = filtered ? model.item_tags() : std::vector<std::uint32_t>();
+        const std::vector<std::uint32_t> members = policy.item_set ? policy.item_set->items() : std::vector<std::uint32_t>();
+        kept_ptr.assign(1, 0);
+        kept_ranks.clear();
+        for (std::size_t i = 0; i < users.size(); ++i) {
+            const std::uint32_t any = filter.any_of.empty() ? 0u : filter.any_of[filter.any_of.size() == 1 ? 0 : i];
+            const std::uint32_t none = filter.none_of.empty() ? 0u : filter.none_of[filter.none_of.size() == 1 ? 0 : i];
+            for (std::uint64_t e = target_ptr[i]; e < target_ptr[i + 1]; ++e) {
+                const std::uint32_t t = target_items[e];
+                bool ok = !policy.item_set || std::binary_search(members.begin(), members.end(), t);
+                if (ok && filtered) ok = (tags[t] & none) == 0 && (any == 0 || (tags[t] & any) != 0);
+                if (ok) ok = std::find(hist_items.begin() + (std::ptrdiff_t)hist_ptr[i], hist_items.begin() + (std::ptrdiff_t)hist_ptr[i + 1], t) ==
+                             hist_items.begin() + (std::ptrdiff_t)hist_ptr[i + 1];
+                if (ok) kept_ranks.push_back(ranks.unwrap()[e]);
+                else ++skipped;
+            }
+            kept_ptr.push_back(kept_ranks.size());
+        }
+    }
+    RankingMetrics out = ranking_metrics_from_ranks(kept_ptr, kept_ranks, ks);
+    out.targets_skipped = skipped;
     for (std::size_t& u : out.users) u = users[u];
     if (out_ranks) *out_ranks = ranks.unwrap();
     return Result<RankingMetrics, PredictionError>::Ok(std::move(out));

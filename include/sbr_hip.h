@@ -496,7 +496,7 @@ sbr_status sbr_similar_items(sbr_model* m, const uint32_t* query_items, uint64_t
  * offered to the user's list, 4 bytes read beside each item row.
  * SBR_ERR_INVALID_ARGUMENT: a filtered call on a model without tags (even with both masks NULL), and wherever the plain call gives
  * it.  NOT BUILT: a filter together with sbr_recommend_among's subset (the tags would have to be gathered with the sub-table; there
- * is no such entry point), sbr_rank_targets under a filter, and persistence of the tags. */
+ * is no such entry point) and persistence of the tags.  sbr_rank_targets under a filter: sbr_rank_targets_rows, ELIGIBLE RANKS below. */
 sbr_status sbr_model_set_item_tags(sbr_model* m, const uint32_t* tags);
 sbr_status sbr_model_get_item_tags(sbr_model* m, uint32_t* out);
 sbr_status sbr_recommend_filtered(sbr_model* m, const uint64_t* user_ptr, const uint32_t* item_ids, uint64_t num_users,
@@ -1169,6 +1169,23 @@ sbr_status sbr_item_set_rollout(sbr_item_set* set, const struct sbr_scan_rows* r
 sbr_status sbr_item_set_beam_search(sbr_item_set* set, const struct sbr_scan_rows* rows, uint64_t num_rows, const struct sbr_beam_args* args,
                                     uint32_t* out_items, float* out_scores, float* out_step_lp, float* out_cum, uint32_t* out_lengths,
                                     uint32_t* out_beams, float* out_shift, uint64_t* out_mass, uint32_t* out_frac_bits);
+/* ELIGIBLE RANKS — sbr_rank_targets among what a row may be shown: under tag masks, through an item set, on a session store.
+ * For a row with list L (its history unless SBR_RECOMMEND_INCLUDE_HISTORY, or the caller's excl list, united with the slot's seen
+ * items on a store with memory unless that flag is given), masks (any_of, none_of) and an optional set S, let
+ *   M = unique(L) ∪ { i : tags[i] is not allowed by the masks } ∪ (catalogue \ S).
+ * The ranks are, integer for integer, what sbr_rank_targets_reps returns for the row's representation with the mask list M:
+ * m(i) = f32::MIN on M, else sbr_predict's score; rank(t) = #{ i in the catalogue : m(i) >= m(t) }.  So a target in M has rank
+ * num_items — the CATALOGUE's, also through a set — ties count against the target, duplicate targets get equal ranks, all-zero
+ * masks without a set is the plain call, and a set of every item is the model's call.  Targets are catalogue ids; an id >= num_items
+ * is SBR_ERR_INVALID_ARGUMENT.  The descriptor's sources, lists, masks and flags are those of the item-set scans above; masks need
+ * sbr_model_set_item_tags; a stale set or store and an open fit plan refuse the call; the flag on a store without memory is an
+ * error.  A non-finite score of a scanned pair fails the call (SBR_ERR_INVALID_PREDICTION) whether the masks allow the item or not;
+ * rows outside S are never read.  An empty set answers on the host: every rank is num_items.  out_ranks [target_ptr[num_rows] -
+ * target_ptr[0]] in target order; a row's targets are scanned rank_targets' way, up to 16 (8 at storage width 256) per scan row. */
+sbr_status sbr_rank_targets_rows(sbr_model* m, const struct sbr_scan_rows* rows, uint64_t num_rows, const uint64_t* target_ptr,
+                                 const uint32_t* target_items, uint32_t* out_ranks);
+sbr_status sbr_item_set_rank_targets(sbr_item_set* set, const struct sbr_scan_rows* rows, uint64_t num_rows, const uint64_t* target_ptr,
+                                     const uint32_t* target_items, uint32_t* out_ranks);
 
 #define SBR_ABI_VERSION 13u /* what sbr_abi_version returns from a library built from this header */
 uint32_t sbr_abi_version(void);

@@ -215,6 +215,9 @@ def load():
         # (set, store descriptor, num_rows, args, ...) and the output tail of sbr_sessions_rollout / sbr_sessions_beam_search
         "sbr_item_set_rollout": [vp, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
         "sbr_item_set_beam_search": [vp, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+        # eligible ranks: (model or set, const sbr_scan_rows*, num_rows, target_ptr, target_items, out_ranks)
+        "sbr_rank_targets_rows": [vp, vp, C.c_uint64, vp, vp, vp],
+        "sbr_item_set_rank_targets": [vp, vp, C.c_uint64, vp, vp, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -292,4 +295,5 @@ DECLARED_SYMBOLS = [
     "sbr_item_set_recommend", "sbr_item_set_recommend_diverse", "sbr_item_set_recommend_sampled", "sbr_item_set_log_partition",
     "sbr_item_set_recommend_above", "sbr_item_set_recommend_top", "sbr_item_set_recommend_capped",
     "sbr_item_set_rollout", "sbr_item_set_beam_search",
+    "sbr_rank_targets_rows", "sbr_item_set_rank_targets",
 ]

@@ -18,7 +18,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libsbr_hip.so")
 SOURCES = ["sbr_kernels.hip", "sbr_steps.hip", "sbr_sort.hip", "sbr_wave.hip", "sbr_report.hip", "sbr_catalogue.hip", "sbr_sessions.hip", "sbr_engine.hip"]
-HEADERS = ["sbr_kernels.h", "sbr_device.h", "sbr_wave_seq.h", "sbr_numerics.h", "sbr_approx.h", "sbr_ziggurat_tables.h", "sbr_replay_plan.h", os.path.join("..", "..", "include", "sbr_hip.h")]
+HEADERS = ["sbr_kernels.h", "sbr_device.h", "sbr_wave_seq.h", "sbr_numerics.h", "sbr_approx.h", "sbr_ziggurat_tables.h", "sbr_replay_plan.h", "sbr_rank_eligible.h", os.path.join("..", "..", "include", "sbr_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
          "-Wall", "-Wno-unused-function", "-Wno-unused-result", "-Wno-unused-value"] + os.environ.get("SBR_EXTRA_FLAGS", "").split()
 
@@ -270,6 +270,15 @@ def build_item_set_rollout_tests(force: bool = False, verbose: bool = True) -> s
     return _build_cpp_program(ITEM_SET_ROLLOUT_SRC, ITEM_SET_ROLLOUT_BIN, force, verbose)
 
 
+RANK_ELIGIBLE_SRC = os.path.join(REPO, "tests", "cpp", "rank_eligible_tests.cpp")
+RANK_ELIGIBLE_BIN = os.path.join(REPO, "tests", "cpp", "_build", "rank_eligible_tests")
+
+
+def build_rank_eligible_tests(force: bool = False, verbose: bool = True) -> str:
+    """g++ build of the C++ host layer's rank_targets under a filter / set / store test program."""
+    return _build_cpp_program(RANK_ELIGIBLE_SRC, RANK_ELIGIBLE_BIN, force, verbose)
+
+
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv))
     print(build_facade_tests(force="--force" in sys.argv))
@@ -294,3 +303,4 @@ if __name__ == "__main__":
     print(build_rollout_tests(force="--force" in sys.argv))
     print(build_beam_tests(force="--force" in sys.argv))
     print(build_item_set_rollout_tests(force="--force" in sys.argv))
+    print(build_rank_eligible_tests(force="--force" in sys.argv))

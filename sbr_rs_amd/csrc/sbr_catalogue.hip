@@ -28,6 +28,8 @@
  *   subset_gather_kernel   : recommend_among's sub-table E'[j] = E[S[j]], b'[j] = b[S[j]] of a sorted, unique item set S; the scan is
  *                            topk_gemm_kernel + topk_merge_kernel on a ModelView of E', b', |S|, and
  *   subset_ids_kernel      : maps the merged lists' positions in S back to catalogue ids
+ *   rank_eligible_*_kernel (sbr_rank_eligible.h, included below) : rank_targets under a tag filter, through an item set or over a
+ *                           session store's seen lists: the same three steps with the restriction as a mask list that is never built
  *   subset_positions_kernel, subset_words_kernel : an item set's launches (sbr_item_set_*: the sub-table is resident, gathered once):
  *                            the exclusion CSR in catalogue ids -> positions in S, in place, one wave per segment; the set's tag or
  *                            group words gathered per launch.  The sampled scan over a set is topk_gemm_kernel's GumbelMapped
@@ -2402,6 +2404,8 @@ int launch_rank_targets(const ModelView& m, const float* reps, const int* rep_ro
     });
     return 3;
 }
+
+#include "sbr_rank_eligible.h"
 
 uint32_t recommend_groups(uint32_t num_users, uint32_t num_items, uint32_t k, uint32_t* items_per_group) {
     // Two rounds of the chip's resident slots (two workgroups per CU at d <= 128), not launch_rank's six: a range's first k items

@@ -4598,8 +4598,39 @@ sbr_status above_chunk(sbr_model* m, const sbr::ModelView& cat, const float* A, 
     return SBR_OK;
 }
 
+/* The ranks form of a scan (rank_targets under a filter, through a set or on a store; k == 1, not with item rows, a subset, a
+ * selection, noise, a partition or a threshold): no top-k scan runs — the rows' targets [target_ptr[u], target_ptr[u + 1]) of
+ * target_items (catalogue ids) are ranked among what the row may see, into out_ranks in target order (ELIGIBLE RANKS in sbr_hip.h). */
+struct Ranks {
+    const uint64_t* target_ptr;
+    const uint32_t* target_items;
+    uint32_t* out_ranks;
+};
+
+/* device buffers of launch_rank_eligible over ns scan-users with nt targets, beside the scan's own (the exclusion CSR, masks, flag) */
+struct RanksBufs {
+    int* rep;
+    uint32_t *lu, *sptr, *tgt, *pos, *ranks, *buckets, *totals;
+    float *ts, *th, *tmin, *tmin2;
+    void carve(DeviceArena& ar, size_t ns, size_t nt, uint32_t tmax) {
+        rep = ar.take<int>(ns);
+        lu = ar.take<uint32_t>(ns);
+        sptr = ar.take<uint32_t>(ns + 1);
+        tgt = ar.take<uint32_t>(nt + 1);
+        ts = ar.take<float>(nt + 1);
+        pos = ar.take<uint32_t>(nt + 1);
+        ranks = ar.take<uint32_t>(nt + 1);
+        th = ar.take<float>(ns * tmax);
+        buckets = ar.take<uint32_t>(ns * tmax);
+        tmin = ar.take<float>(ns);
+        tmin2 = ar.take<float>(ns);
+        totals = ar.take<uint32_t>(ns);
+    }
+};
+
 /* which variant of the top-k scan a call asks for; the default is plain recommend */
 struct ScanVariant {
+    const Ranks* rk = nullptr;
     bool cosine = false;                            /* item rows: rank by cosine, not by the plain dot product */
     const std::vector<uint32_t>* subset = nullptr;  /* recommend_among's item set */
     const Diverse* dv = nullptr;
@@ -4673,6 +4704,9 @@ size_t chunk_override(const char* name, size_t cap) {
  * With v.cp (recommend_capped; the model's item groups set; not with item rows, a subset, v.dv, v.sm, v.pt or v.ab) the scan's rows
  * are the users' pools: the same launch keeps v.cp->k_out of each under the group cap, the results are num_users x v.cp->k_out and
  * v.cp->out_complete the rows' flags.
+ * With v.rk (the ranks form; k == 1, not with item rows, a subset, v.dv, v.sm, v.pt, v.ab or v.cp) no top-k scan runs: the chunks
+ * are runs of scan-users — a row's targets, at most rank_targets_tmax at a time — over the same representations, exclusion CSR,
+ * masks and set, ranked by launch_rank_eligible; out_items / out_scores are unused (null).
  * With v.set (an item set, current; not with item rows or v.subset) every form above scans the set's resident sub-table where it
  * scans the catalogue: the exclusion CSR — uploaded, or made by session_seen_lists_kernel — is turned into positions of the set on
  * the device (subset_positions_kernel), the tag and group words of the set are gathered into the arena per launch, the noise is
@@ -4691,9 +4725,30 @@ sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, 
     if (ab && (s.item_rows || v.subset || dv || sm || pt || k != 1)) return SBR_ERR_INVALID_ARGUMENT;
     const Capped* cp = v.cp;
     if (cp && (!m->item_groups || s.item_rows || v.subset || dv || sm || pt || ab)) return SBR_ERR_INVALID_ARGUMENT;
+    const Ranks* rk = v.rk;
+    if (rk && (s.item_rows || v.subset || dv || sm || pt || ab || cp || k != 1)) return SBR_ERR_INVALID_ARGUMENT;
     const sbr_item_set* set = v.set;
     if (set && (s.item_rows || v.subset)) return SBR_ERR_INVALID_ARGUMENT;
+    /* rk: the targets validated, and each row's cut into scan-users as rank_targets_scan cuts them — runs of at most tmax, in row
+     * and target order, sharing the row's representation, list and masks */
+    const uint32_t tmax = sbr::rank_targets_tmax(m->d);
+    std::vector<uint64_t> su_user, su_begin; /* the row of scan-user i; its first target, an index into target_items */
+    if (rk) {
+        if (!rk->target_ptr) return SBR_ERR_INVALID_ARGUMENT;
+        SBRCHK(check_csr(m, rk->target_ptr, num_users, rk->target_items, false));
+        if (rk->target_ptr[num_users] - rk->target_ptr[0] && !rk->out_ranks) return SBR_ERR_INVALID_ARGUMENT;
+        for (uint64_t u = 0; u < num_users; ++u)
+            for (uint64_t e = rk->target_ptr[u]; e < rk->target_ptr[u + 1]; e += tmax) {
+                su_user.push_back(u);
+                su_begin.push_back(e);
+            }
+    }
     if (set && set->ids.empty()) { /* nothing to scan: every row is one that may see nothing */
+        if (rk) { /* every target lies outside the set */
+            const uint64_t nt = rk->target_ptr[num_users] - rk->target_ptr[0];
+            if (nt) std::fill(rk->out_ranks, rk->out_ranks + nt, (uint32_t)m->hp.num_items);
+            return SBR_OK;
+        }
         const size_t ko = dv ? dv->k_out : cp ? cp->k_out : k;
         if (out_items) std::fill(out_items, out_items + num_users * ko, 0xFFFFFFFFu);
         if (out_scores) std::fill(out_scores, out_scores + num_users * ko, -INFINITY);
@@ -4715,10 +4770,14 @@ sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, 
     const sbr::ModelView& cat = sv.cat; /* what the launches scan */
     const uint32_t scanned_items = v.subset ? (uint32_t)v.subset->size() : sv.scanned;
     const size_t cap = recommend_users_cap(scanned_items, k);
-    for (Chunk ch; next_chunk(users, cap, s, m->hp.max_sequence_length, &ch);) {
-        const size_t nu = ch.users.size();
+    for (Chunk ch; next_chunk(rk ? su_user : users, rk ? eval_units_cap : cap, s, m->hp.max_sequence_length, &ch);) {
+        const size_t nu = ch.users.size(); /* rk: the chunk's distinct rows; its units are the scan-users [ch.c0, ch.c1) */
         UserReps ur; /* its lists: what is excluded (list_ptr empty: nothing) */
         TopkBufs tb;
+        RanksBufs rb{};
+        const size_t rk_ns = rk ? ch.c1 - ch.c0 : 0;
+        const uint64_t rk_t0 = rk ? su_begin[ch.c0] : 0; /* the chunk's targets are contiguous in target_items: [rk_t0, rk_t0 + rk_nt) */
+        const size_t rk_nt = rk ? (size_t)(std::min(su_begin[ch.c1 - 1] + tmax, rk->target_ptr[su_user[ch.c1 - 1] + 1]) - rk_t0) : 0;
         SubsetBufs sb;
         SampleBufs smb{};
         float* rnorm = nullptr; /* item rows: the catalogue's reciprocal norms, once per chunk (the arena does not outlive a carve) */
@@ -4742,6 +4801,7 @@ sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, 
             if (v.subset) sb.carve(ar, v.subset->size(), (size_t)m->d);
             if (sm) smb.carve(ar, nu, k);
             if (ab) abufs.carve(ar, scanned_items, nu, ab->n != nullptr);
+            if (rk) rb.carve(ar, rk_ns, rk_nt, tmax);
             if (pt) {
                 pt_mass = ar.take<unsigned long long>(nu);
                 pt_shift = ar.take<float>(nu);
@@ -4794,6 +4854,35 @@ sbr_status recommend_scan(sbr_model* m, const RepSource& s, uint64_t num_users, 
             if (cp) n += sbr::launch_subset_words(set->d_ids, scanned_items, m->item_groups, set_groups, m->stream);
             return n;
         };
+        if (rk) {
+            std::vector<int> srep(rk_ns);
+            std::vector<uint32_t> sptr(rk_ns + 1);
+            for (size_t i = 0; i < rk_ns; ++i) {
+                srep[i] = ur.rep_row[ch.lu[i]];
+                sptr[i] = (uint32_t)(su_begin[ch.c0 + i] - rk_t0);
+            }
+            sptr[rk_ns] = (uint32_t)rk_nt;
+            HIPCHK(hipMemcpyAsync(rb.rep, srep.data(), rk_ns * 4, hipMemcpyHostToDevice, m->stream));
+            HIPCHK(hipMemcpyAsync(rb.lu, ch.lu.data(), rk_ns * 4, hipMemcpyHostToDevice, m->stream));
+            HIPCHK(hipMemcpyAsync(rb.sptr, sptr.data(), (rk_ns + 1) * 4, hipMemcpyHostToDevice, m->stream));
+            HIPCHK(hipMemcpyAsync(rb.tgt, rk->target_items + rk_t0, rk_nt * 4, hipMemcpyHostToDevice, m->stream));
+            SBRCHK(scan_launch(m, tb.flag, [&] {
+                /* without masks, a set or a store's memory the lists are the host's sorted, de-duplicated ones: the plain call's launch */
+                if (!tags && !set && !s.seen)
+                    return sbr::launch_rank_targets(m->mv, ur.H, rb.rep, rb.lu, rb.sptr, (uint32_t)rk_ns, rb.tgt, excl ? tb.eptr : nullptr, tb.excl,
+                                                    rb.ts, rb.pos, rb.th, rb.tmin, rb.tmin2, rb.buckets, rb.totals, rb.ranks, tb.flag, m->stream);
+                sbr::RankEligible re{};
+                re.rep_row = rb.rep; re.su_user = rb.lu; re.sptr = rb.sptr; re.num_su = (uint32_t)rk_ns; re.tgt_items = rb.tgt;
+                re.list_ptr = excl ? tb.eptr : nullptr; re.list_items = tb.excl;
+                re.f = sbr::TagMasks{tags, tb.any_of, tb.none_of};
+                re.set_ids = set ? set->d_ids : nullptr;
+                re.num_items = (uint32_t)m->hp.num_items;
+                re.ts = rb.ts; re.pos = rb.pos; re.th = rb.th; re.tmin = rb.tmin; re.tmin2 = rb.tmin2;
+                re.buckets = rb.buckets; re.totals = rb.totals; re.ranks = rb.ranks; re.nonfinite_flag = tb.flag;
+                return prelaunch() + sbr::launch_rank_eligible(cat, ur.H, re, m->stream);
+            }, {{rk->out_ranks + (rk_t0 - rk->target_ptr[0]), rb.ranks, rk_nt * 4}}));
+            continue;
+        }
         if (ab) { /* the chunk's rows are the call's [ch.c0, ch.c1): every user is one unit */
             sbr::AboveScan as{};
             as.rep_row = tb.rep; as.n = (uint32_t)nu; as.thresholds = abufs.th;
@@ -4906,7 +4995,7 @@ struct ScanRows {
     }
 };
 
-/* The one entry of the scan families (defined beside the session store, whose rows it reads): the 34 public entry points parse their
+/* The one entry of the scan families (defined beside the session store, whose rows it reads): the 34 public entry points of the top-k families, and the two of the ranks form, parse their
  * family's arguments, name their rows and their variant, and call this. */
 sbr_status scan_call(sbr_model* m, const sbr_item_set* set, const ScanRows& r, uint64_t n, uint32_t k, uint32_t* out_items, float* out_scores,
                      ScanVariant v);
@@ -6121,7 +6210,7 @@ bool store_flags_ok(const sbr_sessions* st, uint32_t flags) {
  * threshold and budget forms' *out_total and log_partition's *out_frac_bits — the model's F, with or without a set. */
 sbr_status scan_call(sbr_model* m, const sbr_item_set* set, const ScanRows& r, uint64_t n, uint32_t k, uint32_t* out_items, float* out_scores,
                      ScanVariant v) {
-    if (!m || (n && !out_items && !v.pt && !v.ab) || !scan_k_ok(m, k, v.dv, v.cp)) return SBR_ERR_INVALID_ARGUMENT;
+    if (!m || (n && !out_items && !v.pt && !v.ab && !v.rk) || !scan_k_ok(m, k, v.dv, v.cp)) return SBR_ERR_INVALID_ARGUMENT;
     sbr_sessions* st = nullptr;
     switch (r.kind) {
     case ScanRows::Histories:
@@ -6778,8 +6867,8 @@ sbr_status enter_item_set(const sbr_item_set* set) {
 
 /* A set call's descriptor as scan_call's rows: false unless it names exactly one source of rows and none of the fields that source
  * forbids — histories no lists, representations no flags, item_ids or slots, a store no item_ids. */
-bool item_set_rows(const sbr_item_set* set, const sbr_scan_rows* r, ScanRows* out) {
-    if (!set || !r || (r->user_ptr != nullptr) + (r->reps != nullptr) + (r->store != nullptr) != 1) return false;
+bool descriptor_rows(const sbr_scan_rows* r, ScanRows* out) {
+    if (!r || (r->user_ptr != nullptr) + (r->reps != nullptr) + (r->store != nullptr) != 1) return false;
     if (r->user_ptr) {
         if (r->excl_ptr || r->excl_items) return false;
         *out = ScanRows::of_histories(r->user_ptr, r->item_ids, r->flags, r->any_of, r->none_of);
@@ -6792,6 +6881,8 @@ bool item_set_rows(const sbr_item_set* set, const sbr_scan_rows* r, ScanRows* ou
     }
     return true;
 }
+
+bool item_set_rows(const sbr_item_set* set, const sbr_scan_rows* r, ScanRows* out) { return set && descriptor_rows(r, out); }
 
 }  // namespace
 
@@ -6928,6 +7019,35 @@ sbr_status sbr_item_set_recommend_capped(sbr_item_set* set, const struct sbr_sca
     if (!capped_args(cap, k, out_complete, &cp, &pool) || !item_set_rows(set, rows, &r)) return SBR_ERR_INVALID_ARGUMENT;
     v.cp = &cp;
     return scan_call(set->m, set, r, num_rows, pool, out_items, out_scores, v);
+}
+
+/* ---------------------------------------------------------------------------------------------
+ * ELIGIBLE RANKS: rank_targets under tag masks, through an item set, on a session store (sbr_rank_eligible.h)
+ * ------------------------------------------------------------------------------------------- */
+namespace {
+
+/* the ranks form of scan_call over a descriptor's rows, on the model (set null) or through a set of it */
+sbr_status rank_targets_rows(sbr_model* m, const sbr_item_set* set, const sbr_scan_rows* rows, uint64_t num_rows, const uint64_t* target_ptr,
+                             const uint32_t* target_items, uint32_t* out_ranks) {
+    ScanRows r;
+    if (!m || !target_ptr || !descriptor_rows(rows, &r)) return SBR_ERR_INVALID_ARGUMENT;
+    const Ranks rk{target_ptr, target_items, out_ranks};
+    ScanVariant v;
+    v.rk = &rk;
+    return scan_call(m, set, r, num_rows, 1, nullptr, nullptr, v);
+}
+
+}  // namespace
+
+sbr_status sbr_rank_targets_rows(sbr_model* m, const struct sbr_scan_rows* rows, uint64_t num_rows, const uint64_t* target_ptr,
+                                 const uint32_t* target_items, uint32_t* out_ranks) {
+    return rank_targets_rows(m, nullptr, rows, num_rows, target_ptr, target_items, out_ranks);
+}
+
+sbr_status sbr_item_set_rank_targets(sbr_item_set* set, const struct sbr_scan_rows* rows, uint64_t num_rows, const uint64_t* target_ptr,
+                                     const uint32_t* target_items, uint32_t* out_ranks) {
+    if (!set) return SBR_ERR_INVALID_ARGUMENT;
+    return rank_targets_rows(set->m, set, rows, num_rows, target_ptr, target_items, out_ranks);
 }
 
 namespace {

@@ -300,6 +300,28 @@ constexpr uint32_t TK_MERGE_MAX = 8192;
 struct TagMasks {
     const uint32_t *tags, *any_of, *none_of;
 };
+/* rank_targets under a restriction (sbr_rank_eligible.h; the contract: ELIGIBLE RANKS in include/sbr_hip.h).  The scan-users are
+ * launch_rank_targets'; `cat` is what is scanned — the catalogue, or an item set's sub-table with set_ids its ascending catalogue
+ * ids (NULL: the catalogue) — and tgt_items stay catalogue ids.  su_user[s] indexes list_ptr / list_items — per user a
+ * non-decreasing segment of positions of cat, repeats and a 0xFFFFFFFF tail allowed (list_ptr NULL: none) — and f.any_of /
+ * f.none_of; f.tags [cat.num_items] are the scanned rows' tag words (NULL: no filter, and the scan is rank_targets_gemm_kernel).
+ * num_items: the catalogue's, the rank of a target that is masked.  Scratch as launch_rank_targets'. */
+struct RankEligible {
+    const int* rep_row;
+    const uint32_t *su_user, *sptr;
+    uint32_t num_su;
+    const uint32_t* tgt_items;
+    const uint64_t* list_ptr;
+    const uint32_t* list_items;
+    TagMasks f;
+    const uint32_t* set_ids;
+    uint32_t num_items;
+    float* ts;
+    uint32_t* pos;
+    float *th, *tmin, *tmin2;
+    uint32_t *buckets, *totals, *ranks, *nonfinite_flag;
+};
+int launch_rank_eligible(const ModelView& cat, const float* reps, const RankEligible& re, hipStream_t s);
 /* the noise of a sampled scan (topk_gemm_kernel's GumbelBias policy; keys NULL: not one): inv_t = float(1 / temperature), finite and
  * not zero, and keys [n], the rows' noise keys, which launch_recommend_sampled fills ahead of the scan */
 struct SampleNoise {

@@ -1475,11 +1475,16 @@ class Model:
                                                 _ptr(items), _ptr(scores)))
         return items, scores
 
-    def rank_targets(self, user_ptr, item_ids, target_ptr, target_items, include_history: bool = False) -> np.ndarray:
+    def rank_targets(self, user_ptr, item_ids, target_ptr, target_items, include_history: bool = False, any_of=None,
+                     none_of=None) -> np.ndarray:
         """Exact ranks of every user's targets among the whole catalogue from one scan (sbr_rank_targets): user u's history is
         item_ids[user_ptr[u]: user_ptr[u + 1]], its targets target_items[target_ptr[u]: target_ptr[u + 1]]; rank =
         #{items whose masked score >= the target's}, the whole history masked to f32::MIN unless include_history.  One u32 per
-        target, in target order."""
+        target, in target order.  With ``any_of`` / ``none_of`` (``recommend``'s masks; needs ``set_item_tags``) every item the
+        masks forbid is masked as well (sbr_rank_targets_rows): a forbidden target has rank num_items."""
+        if any_of is not None or none_of is not None:
+            return _rank_targets_rows(self._L.sbr_rank_targets_rows, self._h, _check,
+                                      _ModelRows(self)._hist(user_ptr, item_ids, include_history, any_of, none_of), target_ptr, target_items)
         up = np.ascontiguousarray(user_ptr, dtype=np.uint64)
         it = np.ascontiguousarray(item_ids, dtype=np.uint32)
         tp = np.ascontiguousarray(target_ptr, dtype=np.uint64)
@@ -1492,9 +1497,12 @@ class Model:
         _check(self._L.sbr_rank_targets(self._h, _ptr(up), _ptr(it), nu, _ptr(tp), _ptr(ti), flags, _ptr(ranks)))
         return ranks[: ti.size]
 
-    def rank_targets_reps(self, reps, target_ptr, target_items, exclude=None) -> np.ndarray:
+    def rank_targets_reps(self, reps, target_ptr, target_items, exclude=None, any_of=None, none_of=None) -> np.ndarray:
         """As rank_targets, from representations [U, embedding_dim]; exclude: None or one sequence of masked item ids per
         user."""
+        if any_of is not None or none_of is not None:
+            return _rank_targets_rows(self._L.sbr_rank_targets_rows, self._h, _check, _ModelRows(self)._reps(reps, exclude, any_of, none_of),
+                                      target_ptr, target_items)
         reps = np.ascontiguousarray(reps, dtype=np.float32).reshape(-1, self.dim)
         nu = reps.shape[0]
         tp = np.ascontiguousarray(target_ptr, dtype=np.uint64)
@@ -1890,6 +1898,16 @@ class Sessions:
         """``Model.recommend_above_reps(self.representations(slots), threshold, ...)`` with the scan reading the store's rows in
         place and the seen-item memory excluded exactly as in ``recommend`` (sbr_sessions_recommend_above)."""
         return self._recommend_above(slots, threshold, exclude, any_of, none_of, include_seen, max_results, order, False)
+
+    def rank_targets(self, slots, targets, exclude=None, any_of=None, none_of=None, include_seen: bool = False) -> np.ndarray:
+        """``Model.rank_targets_reps(self.representations(slots), targets, exclude=seen + exclude, ...)`` with the scan reading the
+        store's rows in place (sbr_rank_targets_rows): ``targets`` is one sequence of item ids per slot, or a CSR pair (ptr, ids);
+        the slot's seen items are masked as ``recommend`` excludes them unless ``include_seen``.  One u32 per target, in target
+        order.  Prequential evaluation is this call, then ``append`` of the same events."""
+        sl = self._slots(slots)
+        tp, ti = _items_csr(targets, sl.size)
+        return _rank_targets_rows(self._L.sbr_rank_targets_rows, self.model._h, _check,
+                                  _ModelRows(self.model)._store(self, sl, exclude, any_of, none_of, include_seen), tp, ti)
 
     def count_above(self, slots, threshold, exclude=None, any_of=None, none_of=None, include_seen: bool = False) -> np.ndarray:
         """``recommend_above(...).counts`` without writing any pair: one scan."""
@@ -2330,7 +2348,16 @@ class ItemSet:
                             self.model.item_groups() if groups is None else groups, int(cap), int(k), pool, max(self.size, 1))
         return items, scores, complete
 
+    def _rank_targets(self, src: _ScanRows, target_ptr, target_items) -> np.ndarray:
+        return _rank_targets_rows(self._L.sbr_item_set_rank_targets, self._h, self._check, src, target_ptr, target_items)
+
     # ---- histories: Model's methods of the same names ----
+    def rank_targets(self, user_ptr, item_ids, target_ptr, target_items, include_history: bool = False, any_of=None,
+                     none_of=None) -> np.ndarray:
+        """``Model.rank_targets`` within the set (sbr_item_set_rank_targets): a target outside the set has rank num_items, the
+        catalogue's."""
+        return self._rank_targets(self._hist(user_ptr, item_ids, include_history, any_of, none_of), target_ptr, target_items)
+
     def recommend(self, user_ptr, item_ids, k: int, include_history: bool = False, any_of=None, none_of=None):
         """``Model.recommend`` within the set (sbr_item_set_recommend)."""
         return self._recommend(self._hist(user_ptr, item_ids, include_history, any_of, none_of), k)
@@ -2414,6 +2441,9 @@ class ItemSet:
             store.close()
 
     # ---- representations ----
+    def rank_targets_reps(self, reps, target_ptr, target_items, exclude=None, any_of=None, none_of=None) -> np.ndarray:
+        return self._rank_targets(self._reps(reps, exclude, any_of, none_of), target_ptr, target_items)
+
     def recommend_reps(self, reps, k: int, exclude=None, any_of=None, none_of=None):
         return self._recommend(self._reps(reps, exclude, any_of, none_of), k)
 
@@ -2445,6 +2475,29 @@ class ItemSet:
         return self._diverse(self._reps(reps, exclude, any_of, none_of), k, pool, trade_off, metric)
 
 
+class _ModelRows:
+    """The three sources of rows as ``ItemSet`` names them, for a descriptor call on the model itself (no set)."""
+
+    def __init__(self, model: "Model"):
+        self.model = model
+
+    _hist, _reps, _store = ItemSet._hist, ItemSet._reps, ItemSet._store
+
+
+def _rank_targets_rows(fn, handle, check, src: _ScanRows, target_ptr, target_items) -> np.ndarray:
+    """The eligible-ranks call ``fn`` (sbr_rank_targets_rows / sbr_item_set_rank_targets) over the rows ``src``: one u32 per
+    target, in target order."""
+    tp = np.ascontiguousarray(target_ptr, dtype=np.uint64)
+    ti = np.ascontiguousarray(target_items, dtype=np.uint32)
+    if tp.ndim != 1 or tp.size != src.n + 1:
+        raise ValueError("one target range per row")
+    nt = int(tp[-1] - tp[0])  # ti may hold a dummy entry where there is no target at all
+    ranks = np.zeros(max(nt, 1), dtype=np.uint32)
+    buf = ti if ti.size else np.zeros(1, dtype=np.uint32)
+    check(fn(handle, C.byref(src.desc), src.n, _ptr(tp), _ptr(buf), _ptr(ranks)))
+    return ranks[:nt]
+
+
 class ItemSetSessions:
     """``ItemSet.on(store)``: the scan methods of ``Sessions`` under their names and keywords, restricted to the set.  The store
     must be current and of the set's model; its seen items are excluded as the store's own calls exclude them."""
@@ -2457,6 +2510,12 @@ class ItemSetSessions:
 
     def recommend(self, slots, k: int, exclude=None, any_of=None, none_of=None, include_seen: bool = False):
         return self.item_set._recommend(self._src(slots, exclude, any_of, none_of, include_seen), k)
+
+    def rank_targets(self, slots, targets, exclude=None, any_of=None, none_of=None, include_seen: bool = False) -> np.ndarray:
+        """``Sessions.rank_targets`` within the set."""
+        sl = Sessions._slots(slots)
+        tp, ti = _items_csr(targets, sl.size)
+        return self.item_set._rank_targets(self._src(sl, exclude, any_of, none_of, include_seen), tp, ti)
 
     def recommend_capped(self, slots, k: int, cap: int = 1, pool=None, exclude=None, any_of=None, none_of=None,
                          include_seen: bool = False, exact: bool = True):

@@ -29,20 +29,29 @@ def _csr(seqs, dtype=np.uint32):
     return ptr, np.ascontiguousarray(items, dtype=dtype)
 
 
-def rank_targets(model, histories, targets, mask_history: bool = True):
+def rank_targets(model, histories, targets, mask_history: bool = True, any_of=None, none_of=None, item_set=None):
     """Exact rank of every target of every user among the whole catalogue, on the device in one scan (``sbr_rank_targets``).
 
     ``histories`` and ``targets`` are one item-id sequence per user (a user may have no targets, or an empty history: the
     state of item 0, as ``recommend``).  rank(u, t) = #{items i : m(u, i) >= m(u, t)} with m = the score of ``predict``, or
     f32::MIN for every item of the WHOLE history while ``mask_history`` — the rule of evaluation.rs:30-41 applied to each
     target on its own: the target counts itself, ties count against it, a target inside the masked history has rank
-    num_items, duplicate targets get equal ranks.  -> one uint32 array per user, in target order."""
+    num_items, duplicate targets get equal ranks.  -> one uint32 array per user, in target order.
+
+    ``any_of`` / ``none_of`` (``recommend``'s tag masks: a scalar or one per user) and ``item_set`` (an ``ItemSet`` of the model)
+    state the serving policy the ranks are taken under: every item the masks forbid and every item outside the set is masked
+    to f32::MIN as the history is, so a target the policy can never show has rank num_items (:func:`eligible_targets`)."""
     params = getattr(model, "params", model)
     if len(histories) != len(targets):
         raise ValueError("one target sequence per history")
     up, it = _csr(histories)
     tp, ti = _csr(targets)
-    ranks = params.rank_targets(up, it, tp, ti, include_history=not mask_history)
+    if item_set is not None:
+        ranks = item_set.rank_targets(up, it, tp, ti, include_history=not mask_history, any_of=any_of, none_of=none_of)
+    elif any_of is not None or none_of is not None:
+        ranks = params.rank_targets(up, it, tp, ti, include_history=not mask_history, any_of=any_of, none_of=none_of)
+    else:
+        ranks = params.rank_targets(up, it, tp, ti, include_history=not mask_history)
     tp = tp.astype(np.int64)
     return [ranks[tp[u]: tp[u + 1]].copy() for u in range(len(targets))]
 
@@ -113,14 +122,94 @@ def holdout_split(test: CompressedInteractions, holdout: int = 1):
     return np.array(users, dtype=np.int64), histories, targets
 
 
-def ranking_metrics(model, test: CompressedInteractions, ks=(10, 100), holdout: int = 1, mask_history: bool = True):
+def eligible_targets(model, histories, targets, mask_history: bool = True, any_of=None, none_of=None, item_set=None):
+    """Whether the serving policy could show each target at all — the host statement of "not in M" for :func:`rank_targets`:
+    the target is in the item set (if one is given), its tag word ``item_tags()[t]`` is allowed by the user's masks
+    ((tag & none_of) == 0 and (any_of == 0 or (tag & any_of) != 0)), and while ``mask_history`` it is not in the user's history.
+    Pure numpy over ``model.item_tags()`` and ``item_set.items``.  -> one bool array per user, in target order."""
+    params = getattr(model, "params", model)
+    if len(histories) != len(targets):
+        raise ValueError("one target sequence per history")
+    nu = len(targets)
+
+    def per_user(mask):
+        if mask is None:
+            return np.zeros(nu, dtype=np.uint32)
+        a = np.asarray(mask)
+        if a.ndim == 0:
+            return np.full(nu, int(a) & 0xFFFFFFFF, dtype=np.uint32)
+        a = a.ravel().astype(np.uint32)
+        if a.size != nu:
+            raise ValueError("one mask per user")
+        return a
+
+    filtered = any_of is not None or none_of is not None
+    anyv, nonev = per_user(any_of), per_user(none_of)
+    tags = np.asarray(params.item_tags(), dtype=np.uint32) if filtered else None
+    members = None if item_set is None else np.asarray(item_set.items, dtype=np.uint32)
+    out = []
+    for u in range(nu):
+        t = np.asarray(targets[u], dtype=np.uint32).ravel()
+        ok = np.ones(t.size, dtype=bool)
+        if members is not None:
+            ok &= np.isin(t, members)
+        if filtered:
+            w = tags[t]
+            ok &= (w & nonev[u]) == 0
+            if anyv[u]:
+                ok &= (w & anyv[u]) != 0
+        if mask_history:
+            ok &= ~np.isin(t, np.asarray(histories[u], dtype=np.uint32).ravel())
+        out.append(ok)
+    return out
+
+
+def apply_ineligible(ranks_per_user, eligible_per_user, ineligible: str = "miss"):
+    """The ``ineligible`` rule of :func:`ranking_metrics` on rank rows: ``"miss"`` keeps every rank (a target the policy can
+    never show stays at rank num_items: a miss at every k), ``"skip"`` drops the targets that are not eligible.
+    -> (rank rows, number of targets dropped)."""
+    if ineligible not in ("miss", "skip"):
+        raise ValueError('ineligible: "miss" or "skip"')
+    if len(ranks_per_user) != len(eligible_per_user):
+        raise ValueError("one eligibility row per rank row")
+    if ineligible == "miss":
+        return [np.asarray(r) for r in ranks_per_user], 0
+    rows, skipped = [], 0
+    for r, e in zip(ranks_per_user, eligible_per_user):
+        r, e = np.asarray(r), np.asarray(e, dtype=bool)
+        if r.shape != e.shape:
+            raise ValueError("one eligibility flag per rank")
+        rows.append(r[e])
+        skipped += int(r.size - int(e.sum()))
+    return rows, skipped
+
+
+def ranking_metrics(model, test: CompressedInteractions, ks=(10, 100), holdout: int = 1, mask_history: bool = True, any_of=None,
+                    none_of=None, item_set=None, ineligible: str = "miss"):
     """precision@k, recall@k, hit-rate@k and NDCG@k at every k of ``ks``, MRR and mean rank over a hold-out of the last
     ``holdout`` items of each test sequence (:func:`holdout_split`), from exact catalogue ranks computed in one device scan
     whose cost does not depend on k (:func:`rank_targets`).  Users with fewer than ``holdout + 1`` items are skipped.
-    -> the dict of :func:`ranking_metrics_from_ranks`; its ``users`` index the test set's users."""
+    -> the dict of :func:`ranking_metrics_from_ranks`; its ``users`` index the test set's users.
+
+    ``any_of`` / ``none_of`` (a scalar, or one mask per user of the TEST SET) and ``item_set`` evaluate under a serving policy
+    (:func:`rank_targets`).  ``ineligible`` says what a target the policy can never show (:func:`eligible_targets`) counts as:
+    ``"miss"`` keeps it at rank num_items — the reference's rule for a target in its own history — and ``"skip"`` leaves it out of
+    every mean (a user left without targets is not ranked); ``targets_skipped`` reports how many were left out."""
+    if ineligible not in ("miss", "skip"):
+        raise ValueError('ineligible: "miss" or "skip"')
     users, histories, targets = holdout_split(test, holdout)
-    ranks = rank_targets(model, histories, targets, mask_history=mask_history) if len(users) else []
+
+    def of_users(mask):  # a per-user mask of the test set follows the users the split kept
+        return mask if mask is None or np.ndim(mask) == 0 else np.asarray(mask).ravel()[users]
+
+    any_u, none_u = of_users(any_of), of_users(none_of)
+    policy = dict(mask_history=mask_history, any_of=any_u, none_of=none_u, item_set=item_set)
+    ranks = rank_targets(model, histories, targets, **policy) if len(users) else []
+    skipped = 0
+    if ineligible == "skip" and len(users):
+        ranks, skipped = apply_ineligible(ranks, eligible_targets(model, histories, targets, **policy), "skip")
     out = ranking_metrics_from_ranks(ranks, ks)
+    out["targets_skipped"] = skipped
     out["users"] = users[out["users"]] if len(users) else users
     return out
 

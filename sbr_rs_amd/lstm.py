@@ -518,12 +518,12 @@ class _ImplicitSequenceModel:
         model's parameters (``engine.Sessions.replay``): the route after a retrain."""
         return self.params.load_sessions(path, capacity=capacity, remember=remember, replay=replay)
 
-    def rank_targets(self, histories, targets, mask_history: bool = True):
+    def rank_targets(self, histories, targets, mask_history: bool = True, any_of=None, none_of=None, item_set=None):
         """Exact catalogue ranks of each user's targets from one device scan (``evaluation.rank_targets``): one uint32 array
         per user, in target order."""
         from .evaluation import rank_targets
 
-        return rank_targets(self, histories, targets, mask_history=mask_history)
+        return rank_targets(self, histories, targets, mask_history=mask_history, any_of=any_of, none_of=none_of, item_set=item_set)
 
     def sequence_ranks(self, test, mask_history: bool = True, last=None):
         """Exact next-item rank at every position of every test sequence from one forward pass per sequence
@@ -579,6 +579,12 @@ class ItemSetView:
         up, it = self.model._csr(interactions_or_histories)
         return self.set.recommend_above(up, it, threshold, include_history=not exclude_history, any_of=any_of, none_of=none_of,
                                         max_results=max_results, order=order)
+
+    def rank_targets(self, histories, targets, mask_history: bool = True, any_of=None, none_of=None):
+        """``model.rank_targets`` within the set (``evaluation.rank_targets(..., item_set=...)``): one uint32 array per user."""
+        from .evaluation import rank_targets
+
+        return rank_targets(self.model, histories, targets, mask_history=mask_history, any_of=any_of, none_of=none_of, item_set=self.set)
 
     def count_above(self, interactions_or_histories, threshold, exclude_history: bool = True, any_of=None, none_of=None):
         up, it = self.model._csr(interactions_or_histories)
